@@ -1,13 +1,18 @@
 """bench.py -- imagined env-steps/s of the MI355X-native CMBPO rollout (+ CPO update ms).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--branches B] [--task AntSafe-v2]
-                    [--scaling weak|strong] [--maxroll T]
+                    [--scaling weak|strong] [--maxroll T] [--dump-outputs DIR] [--full]
 
 One "step" = one full imagined-rollout phase of the reference trainer on one batch of start states:
 ``ModelSampler.reset -> sample() x (maxroll-1) -> finish_all_paths -> ModelBuffer.get()``
 (algorithms/cmbpo.py:251-269, the span the reference times as `times/epoch_rollout_model`, :293),
 with the inputs (start states, weights) already resident in HBM.  metric value = imagined env-steps
 (sum of alive branches over the steps, `msampler/samples_added`) per second, whole job over all ranks.
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's get() list if --dump-outputs is given
+(rank 0; see dump_outputs) and prints the JSON line.  --full adds everything else after the timed steps: a phase with
+HIP events (roofline of the ensemble forward, get()'s HBM rate), the CPO update and ensemble-training timings, the
+shipped configurations' rollout phases and the CPU baseline of the oracle (--no-extras / --no-cpu-baseline drop parts).
 
 Workload at N = 1: AntSafe-v2 shapes (obs 29, act 8), 7-member 512x512 swish ensemble, 5 elites, 3+3
 critic members, 128x128 tanh policy, B = 100 000 branches per GPU, maxroll 35 (34 stored steps),
@@ -55,12 +60,21 @@ def parse_args(argv=None):
     ap.add_argument("--budget-frac", type=float, default=0.0,
                     help="> 0: every sample() gets max_samples = frac * (the job's branches) * (maxroll - 1), the early-termination "
                          "rule of samplers/model_sampler.py:282-287 (sharded: the cross-rank budget plan, one all-gather per step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline rollout only (no update / training / sub-configs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also the roofline / get() events phase, CPO update, ensemble training, "
+                         "shipped sub-configs and CPU baseline (a plain run measures the headline rollout only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's get() arrays (a fixed seeded sample of rows) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: headline rollout and its events phase only (no update / training / sub-configs)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--dry-run", action="store_true",
                     help="rendezvous, one all-reduce and the JSON line only (launcher test on machines without a GPU)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args, argv, deadline_s=900.0):
@@ -216,18 +230,23 @@ def ens_flops_per_row(w):
     return 2.0 * E * ((D + A) * H + H * H + H * 2 * (D + 1))
 
 
+def ens_matrix_path(w):
+    """Matrix path of the ensemble forward at this width: 0 fp32 MFMAs (ens_mlp), 1 six bf16 terms (ens_split),
+    2 three f16 terms (ens_h3); only the 512-wide forward has the split paths."""
+    from cmbpo_amd import _lib
+    return _lib.lib().cmbpo_get_ens_matrix_path() if w["ws"][1].shape[1] == 512 else 0
+
+
 def ens_roofline(w, events):
     """Roofline entry of the dominant kernel (the fused ensemble forward) from HIP events on its launch stream.
     `achieved` = ALGORITHMIC float32 flops per second; the peak is that of the matrix path the launches took."""
-    from cmbpo_amd import _lib
-    H = w["ws"][1].shape[1]
     k_ms = [s.elapsed_time(e) for s, e, _ in events]
     k_rows = [n for _, _, n in events]
     if not k_ms:
         return None
     flop_row = ens_flops_per_row(w)
     achieved = flop_row * float(np.sum(k_rows)) / (float(np.sum(k_ms)) * 1e-3) / 1e12
-    path = _lib.lib().cmbpo_get_ens_matrix_path() if H == 512 else 0
+    path = ens_matrix_path(w)
     peak, basis, kernel = {
         0: (PEAK_FP32_MFMA_TFLOPS, "fp32 MFMA dense 157.3 TFLOP/s", "ens_mlp_kernel<512,*,swish,prob>"),
         1: (PEAK_BF16_MFMA_TFLOPS / 6, "bf16 dense 2500 TFLOP/s / 6 MFMAs per f32 product",
@@ -261,6 +280,29 @@ def get_roofline(w, get_events):
             "kernel": "flatten_kernel (vector-field tiles + scalar-field tiles in one launch)", "flatten_us": float(np.mean(fl_ms)) * 1e3,
             "get_us_offsets_to_flatten": float(np.mean(all_ms)) * 1e3, "bytes_per_sample": per_sample,
             "samples": float(np.mean(n))}
+
+
+# ModelBuffer.get()'s list, in the reference's order (buffers/modelbuffer.py get(): pi_info keys sorted)
+OUTPUT_NAMES = ("obs", "act", "adv", "cadv", "ret", "cret", "logp", "val", "cval", "cost", "log_std", "mu")
+DUMP_ROWS = 65536               # sampled rows of a phase's get() list (3.4 M at the headline shape)
+DUMP_BYTES = 48 << 20           # ... at most this much in all, whatever the task's widths
+
+
+def dump_outputs(out_dir, samples, res, seed=1234):
+    """--dump-outputs: what the timed path's caller receives from its last step -- the get() list -- as
+    DIR/<name>.npy (float32), plus samples_added.npy (the step's `msampler/samples_added`) and sample_index.npy
+    (float64).  The rows are a fixed sample: `seed` picks them from the phase's sample count, sorted, so two runs with
+    the same arguments (the same inputs, the same count) write the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(res[0].shape[0])
+    row_bytes = 8 + 4 * sum(int(np.prod(x.shape[1:])) for x in res)
+    rows = min(n, DUMP_ROWS, DUMP_BYTES // row_bytes)
+    idx = np.sort(np.random.default_rng(seed).choice(n, rows, replace=False)) if rows < n else np.arange(n)
+    sel = torch.from_numpy(idx).to(res[0].device)
+    for name, x in zip(OUTPUT_NAMES, res):
+        np.save(os.path.join(out_dir, name + ".npy"), x.index_select(0, sel).float().cpu().numpy())
+    np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "samples_added.npy"), np.array([samples], np.float64))
 
 
 def run_config(name, task, B, maxroll, mode, device, reps=3, dkl_scale=0.6, budget_frac=0.75, seed=0, budget_binds=False):
@@ -579,27 +621,32 @@ def main():
     t0 = time.perf_counter()
     samples, n_budget, n_steps = 0, 0, 0
     for _ in range(args.steps):
-        n, _ = rollout_phase(sampler, pool, start, max_samples)
+        n, last = rollout_phase(sampler, pool, start, max_samples)
         samples += n
         n_budget += int(sampler.n_budget_terminated)
         n_steps += int(sampler._n_episodes)
     torch.cuda.synchronize()
     comm.barrier()
     dt = time.perf_counter() - t0
-    # one more phase with HIP events around the dominant kernel and get()'s kernels (events need the step as separate
-    # calls: the timed phases above run it as the single call the sampler makes by default)
-    env.kernel_events, pool.get_events = [], []
-    rollout_phase(sampler, pool, start, max_samples)
-    torch.cuda.synchronize()
-    events, env.kernel_events = env.kernel_events, None
-    get_events, pool.get_events = pool.get_events, None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, n, last)
+    del last
+    events, get_events = [], []
+    if args.full:
+        # one more phase with HIP events around the dominant kernel and get()'s kernels (events need the step as separate
+        # calls: the timed phases above run it as the single call the sampler makes by default)
+        env.kernel_events, pool.get_events = [], []
+        rollout_phase(sampler, pool, start, max_samples)
+        torch.cuda.synchronize()
+        events, env.kernel_events = env.kernel_events, None
+        get_events, pool.get_events = pool.get_events, None
 
     t = torch.tensor([dt], dtype=torch.float64, device=device)
     comm.all_reduce_max(t)
     dt_max = float(t.item())
     tot, n_budget = comm.all_reduce_host([samples, n_budget])
 
-    extras = not args.no_extras
+    extras = args.full and not args.no_extras
     upd, train, subs = None, None, []
     D, A, E, H = w["obs_dim"], w["act_dim"], w["ws"][0].shape[0], w["ws"][1].shape[1]
     if extras:
@@ -649,10 +696,11 @@ def main():
         del res, obs_t, act_t, ret_t, x_dyn, t_dyn
 
     roof = ens_roofline(w, events)
+    ens_kind = ("ens_mlp", "ens_split", "ens_h3")[ens_matrix_path(w)]
     # HBM traffic of the dominant kernel from PMC counters collected OFFLINE (separate rocprofv3 --pmc passes, see the
     # json file), scaled to this run's rows per launch -- not a measurement of this run
     pmc_file = {"ens_h3": ("r03", "pmc_traffic_h3.json"), "ens_split": ("r01", "pmc_traffic_split.json"),
-                "ens_mlp": ("r01", "pmc_traffic.json")}[roof["kernel"].split("_kernel")[0]] if roof else None
+                "ens_mlp": ("r01", "pmc_traffic.json")}[ens_kind]
     if roof is not None:
         roof["traffic"] = None
         roof["traffic_offline_pmc"] = None
@@ -692,7 +740,7 @@ def main():
                        "tools/split_f16_probe.hip); cmbpo_set_ens_matrix_path(1) selects six bf16 terms, (0) fp32 MFMAs"),
             "ens_split": ("float32 inputs, outputs and accumulation; the ensemble forward's float32 products run as six exact bf16 "
                           "partial products each (operands split exactly into 3 bf16 pieces)"),
-            "ens_mlp": "float32 throughout (fp32 MFMAs)"}[roof["kernel"].split("_kernel")[0]] if roof else None
+            "ens_mlp": "float32 throughout (fp32 MFMAs)"}[ens_kind]
         out = {
             "metric": "imagined env-steps/sec (ensemble rollout) + CPO update ms",
             "value": tot / dt_max,
@@ -719,9 +767,10 @@ def main():
                        "n_budget_terminated_per_phase": n_budget / args.steps, "sampler_steps_per_phase_rank0": n_steps / args.steps,
                        "branches_per_gpu": B, "branches_total": args.branches if args.scaling == "strong" else B * world,
                        "horizon": maxroll - 1, "task": task, "samples_per_step": tot / args.steps, "arithmetic": arith},
-            "roofline": roof,
-            "gae_get": get_roofline(w, get_events),
         }
+        if args.full:
+            out["roofline"] = roof
+            out["gae_get"] = get_roofline(w, get_events)
         if upd is not None:
             out["cpo_update"] = upd
             out["ensemble_train"] = train

@@ -2,6 +2,9 @@
 
 Usage (build container only; /root/reference does not exist on the GPU box):
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
+G7 (--update-only, or the full run) needs the BLAS kernel choices of worlds.PINNED_BLAS_ENV set in the environment:
+    env MKL_CBWR=COMPATIBLE OPENBLAS_CORETYPE=Haswell ATEN_CPU_CAPABILITY=avx2 OMP_NUM_THREADS=1 MKL_NUM_THREADS=1 \
+        OPENBLAS_NUM_THREADS=1 PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py --update-only
 
 Writes tests/golden/*.npz (data only: inputs and the reference's outputs).  The TF-graph half of the
 reference cannot run (no TensorFlow), so the model / policy objects handed to the reference's
@@ -367,6 +370,10 @@ def main():
 # G7: the reference's CPOAgent.update_pi driven by a fake session evaluating the restated graph
 # ------------------------------------------------------------------------------------------------
 def gen_update_pi(out):
+    from worlds import PINNED_BLAS_ENV, blas_env_is_pinned
+    if not blas_env_is_pinned():
+        raise SystemExit("G7 is recorded with the BLAS kernel choices pinned: run with " +
+                         " ".join(f"{k}={v}" for k, v in PINNED_BLAS_ENV.items()))
     from policies.cpo_policy import CPOAgent
     from oracle import refupdate
     obs_dim, act_dim, hidden, n, T = 6, 3, 16, 256, 20

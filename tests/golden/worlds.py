@@ -4,6 +4,21 @@ Pure functions of a seed: nothing here touches the reference tree, so tests can 
 """
 import numpy as np
 
+# G7 (the reference's CPOAgent.update_pi on the restated float32 policy graph) is pinned bit for bit, and float32 BLAS
+# results depend on the kernels a library picks for the CPU it runs on: MKL behind torch's CPU matmuls, OpenBLAS behind
+# NumPy's dot.  Its recording and its test run in processes started with these choices pinned, which every x86-64
+# host with AVX2 executes alike.
+PINNED_BLAS_ENV = {"MKL_CBWR": "COMPATIBLE", "OPENBLAS_CORETYPE": "Haswell", "ATEN_CPU_CAPABILITY": "avx2",
+                   "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1", "OPENBLAS_NUM_THREADS": "1"}
+# host settings that would override the pinned kernel choice
+UNPINNED_BLAS_VARS = ("MKL_ENABLE_INSTRUCTIONS", "MKL_DEBUG_CPU_TYPE")
+
+
+def blas_env_is_pinned():
+    import os
+    return (all(os.environ.get(k) == v for k, v in PINNED_BLAS_ENV.items())
+            and not any(k in os.environ for k in UNPINNED_BLAS_VARS))
+
 
 def build_world(seed, task, hidden, E=7, out_scale=1.0, q_boost=0.0):
     """Seeded weights shared by the generator and the tests (tests rebuild them from `seed`)."""

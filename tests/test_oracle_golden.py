@@ -123,8 +123,26 @@ def test_g5_rollout_oracle_matches_reference_trace(name):
 
 def test_g7_update_pi_logic_matches_reference():
     """oracle.refupdate.update_pi vs the reference's CPOAgent.update_pi (recorded with a fake session that
-    evaluates the same restated graph): case selection, dual variables, step, backtracking, margin."""
+    evaluates the same restated graph): case selection, dual variables, step, backtracking, margin.  Bit for bit, so
+    the check runs in a child process with the BLAS kernel choices of G7's recording (worlds.PINNED_BLAS_ENV):
+    MKL and OpenBLAS pick float32 kernels by CPU, and those round differently."""
+    import subprocess
+    import sys
+    sys.path.insert(0, GOLD)
+    from worlds import PINNED_BLAS_ENV, UNPINNED_BLAS_VARS
+    env = {k: v for k, v in os.environ.items() if k not in UNPINNED_BLAS_VARS}
+    env.update(PINNED_BLAS_ENV)
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import sys; sys.path[:0] = [%r, %r, %r]; import test_oracle_golden as t; t._check_g7_update_pi()"
+            % (os.path.dirname(here), here, GOLD))
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, (r.stdout[-3000:] + r.stderr[-3000:])
+
+
+def _check_g7_update_pi():
+    from worlds import blas_env_is_pinned
     from oracle import refupdate
+    assert blas_env_is_pinned(), "G7 is compared with the BLAS kernel choices of its recording (worlds.PINNED_BLAS_ENV)"
     g = _load("g7_update_pi")
     D, A, H, T = int(g["obs_dim"]), int(g["act_dim"]), int(g["hidden"]), int(g["T"])
     cases = set()
