@@ -33,9 +33,6 @@ _sz = C.c_size_t
 SIGNATURES = {
     "cmbpo_last_error": (C.c_char_p, []),
     "cmbpo_version": (_i, []),
-    "cmbpo_set_block_rows": (_i, [_i]),
-    "cmbpo_set_stagger": (_i, [_i]),
-    "cmbpo_set_dispatch_mode": (_i, [_i]),
     "cmbpo_set_ens_matrix_path": (_i, [_i]),
     "cmbpo_get_ens_matrix_path": (_i, []),
     "cmbpo_set_ens_f16_min_rows": (_i, [_i]),

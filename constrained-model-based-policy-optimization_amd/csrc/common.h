@@ -10,6 +10,14 @@ void cmbpo_set_error(const char *fmt, ...);
 // the saved-activation block a Fisher-vector product on this batch would read (NULL: recompute); part of the key of a
 // captured CG graph, whose kernel arguments contain it
 const void *cmbpo_pi_act_token(const cmbpo_pi_t *h, const cmbpo_pi_batch_t *b);
+// Launch state of the current device (hipGetDevice), kept per device and safe to call from several host threads.
+// CU count (256 if the query fails)
+int cmbpo_cu_count();
+// raise the dynamic-LDS limit of `kern` on the current device to at least `bytes` (the runtime is asked only when the
+// device's high-water mark for the kernel grows); CMBPO_EHIP with the error set if it refuses
+int cmbpo_grant_lds(const void *kern, size_t bytes);
+template <typename K>
+int cmbpo_grant_lds(K *kern, size_t bytes) { return cmbpo_grant_lds(reinterpret_cast<const void *>(kern), bytes); }
 
 #define CMBPO_HIP_CHECK(expr)                                                  \
   do {                                                                         \

@@ -1,7 +1,12 @@
-// Error reporting + version for the C-ABI library.
+// Error reporting, version and per-device launch state for the C-ABI library.
 #include "common.h"
 
 #include <stdarg.h>
+
+#include <atomic>
+#include <map>
+#include <mutex>
+#include <utility>
 
 static thread_local char g_err[512] = "no error";
 
@@ -15,3 +20,36 @@ void cmbpo_set_error(const char *fmt, ...) {
 extern "C" const char *cmbpo_last_error(void) { return g_err; }
 
 extern "C" int cmbpo_version(void) { return 1; }
+
+namespace {
+constexpr int kMaxDevices = 64;
+std::atomic<int> g_cu_count[kMaxDevices];   // 0: not asked yet
+std::mutex g_lds_mu;
+std::map<std::pair<int, const void *>, size_t> g_lds_granted;   // (device, kernel) -> dynamic LDS already granted
+}  // namespace
+
+int cmbpo_cu_count() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+  const bool cached = dev >= 0 && dev < kMaxDevices;
+  int n = cached ? g_cu_count[dev].load(std::memory_order_relaxed) : 0;
+  if (n == 0) {
+    hipDeviceProp_t prop;
+    n = (dev >= 0 && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount
+                                                                                                       : 256;
+    if (cached) g_cu_count[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
+int cmbpo_grant_lds(const void *kern, size_t bytes) {
+  int dev = 0;
+  CMBPO_HIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(g_lds_mu);
+  size_t &granted = g_lds_granted[{dev, kern}];
+  if (bytes > granted) {
+    CMBPO_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    granted = bytes;
+  }
+  return CMBPO_OK;
+}

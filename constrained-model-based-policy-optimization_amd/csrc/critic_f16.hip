@@ -570,20 +570,10 @@ int cmbpo_internal_critic_pair_ride(cmbpo_mlp *v, cmbpo_mlp *vc, const float *d_
   }
   // large batches without a rider: members one after the other with their weights in LDS (critic_big_kernel)
   if (!a.has_pol && n_rows >= cmbpo_internal_critic_big_min()) {
-    hipDeviceProp_t prop;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-      int dev = 0;
-      n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                 ? prop.multiProcessorCount : 256;
-    }
+    const int n_cu = cmbpo_cu_count();
     auto launch_big = [&](auto geo, auto kern) -> int {
       using G = decltype(geo);
-      static bool attr = false;
-      if (!attr) {
-        CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS));
-        attr = true;
-      }
+      if (int rc = cmbpo_grant_lds(kern, G::LDS)) return rc;
       int ch = (cmbpo_ceil_div(n_rows, n_cu) + 31) / 32 * 32;      // one chunk per CU where the batch allows
       if (ch > G::CH) ch = G::CH;
       hipLaunchKernelGGL(kern, dim3(cmbpo_ceil_div(n_rows, ch)), dim3(512), G::LDS, s, a, ch);

@@ -892,13 +892,7 @@ int cmbpo_internal_launch_h3(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s) {
   k.w0 = base + m->h3_off[0]; k.w1 = base + m->h3_off[1]; k.w2 = base + m->h3_off[2];
   k.w0_stride = m->h3_stride[0]; k.w1_stride = m->h3_stride[1]; k.w2_stride = m->h3_stride[2];
   k.stats = reinterpret_cast<const float *>(reinterpret_cast<const char *>(m->d_h3) + m->h3_stats_off * 16);
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    hipDeviceProp_t prop;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-    if (n_cu <= 0) n_cu = 256;
-  }
+  const int n_cu = cmbpo_cu_count();
   // Rows per item: the cheapest plan by a two-number model per item size -- the first round of a launch costs an item's
   // latency, every further round its steady-state time (tenths of a microsecond, measured by forcing each size over 17 row
   // counts, profiles/r03/h3_split_plan_sweep.log: 32 / 64 / 128 rows = 22.0 / 31.0 / 55.0 us then 17.5 / 30.0 / 54.0 us per
@@ -940,7 +934,6 @@ int cmbpo_internal_launch_h3(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s) {
       }
   }
   const int S0 = m->h3_s0, OTP = m->h3_otp;
-  static bool attr_done[5][5][5] = {};
   // one launch: items [item0, end) of the (member-major) item list at rt 32-row tiles per item; end < 0: all of it
   auto launch = [&](int rt, int item0, int end) -> int {
     const int tiles = cmbpo_ceil_div(a.n_rows, 32 * rt);
@@ -953,11 +946,7 @@ int cmbpo_internal_launch_h3(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s) {
     const int grid = n_here < n_cu ? n_here : n_cu;
 #define CMBPO_H3_CASE(S0_, OTP_, RT_)                                                                                  \
   if (S0 == S0_ && OTP == OTP_ && rt == RT_) {                                                                         \
-    if (!attr_done[S0_][OTP_][RT_]) {                                                                                  \
-      CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ens_h3_kernel<S0_, OTP_, RT_>),               \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(S0_, RT_)));      \
-      attr_done[S0_][OTP_][RT_] = true;                                                                                \
-    }                                                                                                                  \
+    if (int rc = cmbpo_grant_lds(ens_h3_kernel<S0_, OTP_, RT_>, lds)) return rc;                                      \
     hipLaunchKernelGGL((ens_h3_kernel<S0_, OTP_, RT_>), dim3(grid), dim3(kThreadsH), lds, s, k);                      \
   }
 #define CMBPO_H3_CASES(RT_)                                                                                            \

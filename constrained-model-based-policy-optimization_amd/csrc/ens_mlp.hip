@@ -219,26 +219,11 @@ __global__ __launch_bounds__(kThreads, (BT == 1 ? 2 : 1)) void ens_mlp_kernel(
       oconst[2 * p.out_dim + tid] = p.out_mu ? p.out_mu[tid] : 0.0f;
     }
   }
-  // Persistent workgroups: the grid is sized to what is co-resident (2 per CU for the 512-wide ensemble) and
-  // each workgroup strides over the (member chunk, row tile) items in member-major order, so the hardware
-  // dispatcher never has to back-fill a CU (measured: 20-36 us gaps per slot on half of the CUs with one
-  // workgroup per item) and concurrently running workgroups share one member's weights in L2.
-  __shared__ int s_item;
-  for (int item = blockIdx.x;;) {
-  if (p.work_counter) {
-    // dynamic claiming: one returning device-scope atomic per item (MI355X_MICROARCH "dequeue": 0.3-1 us)
-    if (tid == 0) s_item = atomicAdd(p.work_counter, 1);
-    __syncthreads();
-    item = s_item;
-  }
-  if (item >= p.n_items) break;
+  // one workgroup per item = (member chunk, row tile), member-major
+  const int item = blockIdx.x;
   const int chunk = item / p.tiles;
   const int row0 = (item - chunk * p.tiles) * BB;
-  if (row0 >= n_rows) {
-    if (!p.work_counter) item += gridDim.x;
-    else __syncthreads();
-    continue;
-  }
+  if (row0 >= n_rows) return;
 #ifdef CMBPO_STAMPS
   const int stamp_item = item;
 #endif
@@ -542,9 +527,6 @@ __global__ __launch_bounds__(kThreads, (BT == 1 ? 2 : 1)) void ens_mlp_kernel(
   }
   STAMP(7);
   STAMP(9);
-  __syncthreads();   // the next item re-uses xbuf / rows / red / s_item
-  if (!p.work_counter) item += gridDim.x;
-  }  // persistent item loop
 }
 
 // Host-side packing: W[K][N] row-major -> [n-tile][k-group][lane][4].
@@ -727,63 +709,24 @@ extern "C" int cmbpo_mlp_load_policy_flat(cmbpo_mlp_t *m, const float *d_flat, v
 
 namespace {
 
-int g_dispatch_mode = 0;   // 0: one workgroup per item (hardware dispatch), 1: persistent static, 2: persistent dynamic
-int *g_work_counter = nullptr;
-
-int device_cu_count() {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    hipDeviceProp_t prop;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      n_cu = prop.multiProcessorCount;
-    if (n_cu <= 0) n_cu = 256;
-  }
-  return n_cu;
-}
-
 template <int HID, int BT, int ACT, int HEAD>
 int launch_one(MlpKernelArgs &a, int tiles, int chunks, size_t lds, hipStream_t s) {
   auto kern = ens_mlp_kernel<HID, BT, ACT, HEAD>;
-  static size_t attr_bytes = 0;   // the kernel also has a few bytes of static LDS: ask for what is needed
-  static size_t occ_lds = ~(size_t)0;
-  static int per_cu = 1;
-  if (lds > attr_bytes) {
-    CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_bytes = lds;
-  }
-  if (occ_lds != lds) {   // co-resident workgroups per CU for this LDS footprint
-    int nb = 0;
-    CMBPO_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, kThreads, lds));
-    per_cu = nb < 1 ? 1 : (nb > 4 ? 4 : nb);
-    occ_lds = lds;
-  }
+  if (int rc = cmbpo_grant_lds(kern, lds)) return rc;
   a.tiles = tiles;
   a.n_items = tiles * chunks;
-  a.n_cu = device_cu_count();
-  const int resident = per_cu * a.n_cu;
-  int grid = a.n_items < resident ? a.n_items : resident;
-  a.work_counter = nullptr;
-  if (g_dispatch_mode == 0) {
-    grid = a.n_items;                       // every workgroup runs exactly one item
-  } else if (g_dispatch_mode == 2) {
-    if (!g_work_counter) CMBPO_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&g_work_counter), sizeof(int)));
-    CMBPO_HIP_CHECK(hipMemsetAsync(g_work_counter, 0, sizeof(int), s));
-    a.work_counter = g_work_counter;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, s, a);
+  a.n_cu = cmbpo_cu_count();
+  hipLaunchKernelGGL(kern, dim3(a.n_items), dim3(kThreads), lds, s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
 
-int g_block_rows = 32;  // 32 (2 workgroups / CU) or 64 (1 workgroup / CU)
 // matrix path of the 512-wide PROB forward: 0 fp32 MFMAs, 1 ens_split.hip (six bf16 terms), 2 ens_h3.hip (three f16 terms)
 int g_split_path = getenv("CMBPO_ENS_SPLIT") ? atoi(getenv("CMBPO_ENS_SPLIT")) : CMBPO_ENS_SPLIT_F16;
 // rows below which the 512-wide forward falls back to the bf16 kernel: none since the f16 kernel has 32- and 64-row items
 // (22 us against the bf16 kernel's 43 at 1000 rows, AntSafe shapes); the knob stays for experiments
 int g_h3_min_rows = getenv("CMBPO_ENS_H3_MIN_ROWS") ? atoi(getenv("CMBPO_ENS_H3_MIN_ROWS")) : 0;
-int g_stagger = 10;     // x s_sleep(127) (~8k cycles each) for the second dispatch batch
+constexpr int kStaggerSleeps = 10;   // x s_sleep(127) (~8k cycles each) for the second dispatch batch
 int g_lds_pad = 0;      // diagnostic: extra dynamic LDS bytes (forces one workgroup per CU)
 
 int launch_mlp(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s, int head_override = -1) {
@@ -806,7 +749,7 @@ int launch_mlp(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s, int head_override 
 #ifdef CMBPO_STAMPS
   a.stamps = g_stamps;
 #endif
-  a.stagger_sleeps = (H == 512 && head != CMBPO_HEAD_TRAIN) ? g_stagger : 0;
+  a.stagger_sleeps = (H == 512 && head != CMBPO_HEAD_TRAIN) ? kStaggerSleeps : 0;
   a.ensemble = E;
   a.e_chunk = (head == CMBPO_HEAD_PROB || head == CMBPO_HEAD_TRAIN) ? 1 : E;
   a.in_dim = m->in_dim; a.in_pad = m->in_pad;
@@ -824,8 +767,7 @@ int launch_mlp(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s, int head_override 
   if (head == CMBPO_HEAD_DETMEAN && H == 128 && m->act == CMBPO_ACT_SWISH && m->o_width == 1 && m->in_pad <= 64 && E <= 8 &&
       g_split_path && a.n_rows >= 32768)
     return cmbpo_internal_launch_critic_split(m, a, s);
-  const int BT = (H == 512 && g_block_rows == 64 && head != CMBPO_HEAD_TRAIN) ? 2 : 1;
-  const int BB = 32 * BT;
+  const int BB = 32;
   const int tiles = cmbpo_ceil_div(a.n_rows, BB);
   const int grid_y = cmbpo_ceil_div(E, a.e_chunk);
   const size_t hbuf = (size_t)H * BB * 4;
@@ -840,8 +782,7 @@ int launch_mlp(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s, int head_override 
     if (H == 128) CMBPO_LAUNCH(128, 1, CMBPO_ACT_SWISH, CMBPO_HEAD_TRAIN);
     if (H == 256) CMBPO_LAUNCH(256, 1, CMBPO_ACT_SWISH, CMBPO_HEAD_TRAIN);
   } else if (head == CMBPO_HEAD_PROB && m->act == CMBPO_ACT_SWISH) {
-    if (H == 512 && BT == 1) CMBPO_LAUNCH(512, 1, CMBPO_ACT_SWISH, CMBPO_HEAD_PROB);
-    if (H == 512 && BT == 2) CMBPO_LAUNCH(512, 2, CMBPO_ACT_SWISH, CMBPO_HEAD_PROB);
+    if (H == 512) CMBPO_LAUNCH(512, 1, CMBPO_ACT_SWISH, CMBPO_HEAD_PROB);
     if (H == 128) CMBPO_LAUNCH(128, 1, CMBPO_ACT_SWISH, CMBPO_HEAD_PROB);
     if (H == 256) CMBPO_LAUNCH(256, 1, CMBPO_ACT_SWISH, CMBPO_HEAD_PROB);
   } else if (head == CMBPO_HEAD_DETMEAN && m->act == CMBPO_ACT_SWISH) {
@@ -879,26 +820,8 @@ extern "C" int cmbpo_set_ens_f16_min_rows(int rows) {
 
 extern "C" int cmbpo_get_ens_matrix_path(void) { return g_split_path; }
 
-extern "C" int cmbpo_set_dispatch_mode(int mode) {
-  CMBPO_REQUIRE(mode >= 0 && mode <= 2, "cmbpo_set_dispatch_mode: 0 (per-item), 1 (persistent static), 2 (persistent dynamic)");
-  g_dispatch_mode = mode;
-  return CMBPO_OK;
-}
-
 extern "C" int cmbpo_debug_set_lds_pad(int bytes) {
   g_lds_pad = bytes;
-  return CMBPO_OK;
-}
-
-extern "C" int cmbpo_set_stagger(int sleeps) {
-  CMBPO_REQUIRE(sleeps >= 0 && sleeps <= 64, "cmbpo_set_stagger: 0..64");
-  g_stagger = sleeps;
-  return CMBPO_OK;
-}
-
-extern "C" int cmbpo_set_block_rows(int rows) {
-  CMBPO_REQUIRE(rows == 32 || rows == 64, "cmbpo_set_block_rows: 32 or 64");
-  g_block_rows = rows;
   return CMBPO_OK;
 }
 

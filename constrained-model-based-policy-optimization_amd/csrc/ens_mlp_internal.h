@@ -34,8 +34,7 @@ struct MlpKernelArgs {
   float *out3;  //                     | log_std broadcast
   unsigned long long *stamps;  // diagnostic builds only
   int stagger_sleeps;          // s_sleep(127) repetitions for the second dispatch batch (0 = off)
-  int tiles, n_items, n_cu;    // persistent grid: items = member chunks x row tiles, member-major
-  int *work_counter;           // device counter for dynamic item claiming (nullptr: static striding)
+  int tiles, n_items, n_cu;    // items = member chunks x row tiles, member-major; n_cu places the stagger
   // training forward (HEAD_TRAIN): rows are gathered through a per-member index list and every intermediate
   // the backward pass needs is exported, indexed [member][batch row][...]
   int row_idx_stride;          // elements between the index lists of consecutive members

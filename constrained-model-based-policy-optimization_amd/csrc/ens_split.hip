@@ -600,13 +600,7 @@ int cmbpo_internal_launch_split(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s) {
   k.slabs0 = (m->in_pad + 15) / 16;
   const int OT = m->o_tiles;
   CMBPO_REQUIRE(OT >= 1 && OT <= 4, "ens_split: %d output tiles", OT);
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    hipDeviceProp_t prop;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-    if (n_cu <= 0) n_cu = 256;
-  }
+  const int n_cu = cmbpo_cu_count();
   // 64-row items halve the weight stream per row; while 32-row items still find a CU each (small rollout batches, where
   // an item's latency is the step's) they take 0.8 of a 64-row item's time.  Measured, AntSafe shapes: 42 / 42 / 45 us
   // at 256 / 512 / 1000 rows against 51 / 52 / 54 us; at 2000 rows 32-row items would share CUs: 74 us against 62.
@@ -621,14 +615,9 @@ int cmbpo_internal_launch_split(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s) {
   CMBPO_REQUIRE((size_t)4 * OT * 32 * (rows + 1) <= img, "ens_split: partial-output image does not fit");
   const int resident = (BT == 1 ? 2 : 1) * n_cu;
   const int grid = k.m.n_items < resident ? k.m.n_items : resident;
-  static size_t attr_bytes[5][3] = {};
 #define CMBPO_SPLIT_CASE(OT_, BT_)                                                                                   \
   if (OT == OT_ && BT == BT_) {                                                                                      \
-    if (lds > attr_bytes[OT_][BT_]) {                                                                                \
-      CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ens_split_kernel<OT_, BT_>),                \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                    \
-      attr_bytes[OT_][BT_] = lds;                                                                                    \
-    }                                                                                                                \
+    if (int rc = cmbpo_grant_lds(ens_split_kernel<OT_, BT_>, lds)) return rc;                                       \
     hipLaunchKernelGGL((ens_split_kernel<OT_, BT_>), dim3(grid), dim3(kThreadsS), lds, s, k);                       \
   }
   CMBPO_SPLIT_CASE(1, 1) CMBPO_SPLIT_CASE(2, 1) CMBPO_SPLIT_CASE(3, 1) CMBPO_SPLIT_CASE(4, 1)
@@ -648,12 +637,7 @@ int cmbpo_internal_launch_critic_split(cmbpo_mlp *m, MlpKernelArgs &a, hipStream
   k.slabs0 = (m->in_pad + 15) / 16;
   const int items = cmbpo_ceil_div(a.n_rows, 64);
   const size_t lds = ((size_t)64 * (k.slabs0 * 16 + 4) + (size_t)64 * HSC + (size_t)m->ensemble * (3 * HC + 4)) * sizeof(float);
-  static size_t attr_bytes = 0;
-  if (lds > attr_bytes) {
-    CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(critic_split_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_bytes = lds;
-  }
+  if (int rc = cmbpo_grant_lds(critic_split_kernel, lds)) return rc;
   hipLaunchKernelGGL(critic_split_kernel, dim3(items), dim3(kThreadsC), lds, s, k);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;

@@ -1965,12 +1965,7 @@ int launch_wgrad(cmbpo_trainer *t, int layer, int batch, hipStream_t s) {
   fill_wgrad_args(t, layer, batch, a, n_cols);
   a.n_tiles = cmbpo_ceil_div(n_cols, 64);
   const size_t lds = 2 * 128 * 64 * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(wgrad_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  if (int rc = cmbpo_grant_lds(wgrad_kernel, lds)) return rc;
   hipLaunchKernelGGL(wgrad_kernel, dim3((H / 128) * a.n_tiles, t->ks[layer], t->E), dim3(kThreads), lds, s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
@@ -1998,12 +1993,7 @@ int launch_wgrad_all(cmbpo_trainer *t, int batch, hipStream_t s) {
   }
   all.first[3] = blocks;
   if (train_f16()) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(wgrad_all_kernel<true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, kWgradF16Lds));
-      attr_set = true;
-    }
+    if (int rc = cmbpo_grant_lds(wgrad_all_kernel<true>, kWgradF16Lds)) return rc;
     hipLaunchKernelGGL(wgrad_all_kernel<true>, dim3(blocks), dim3(kThreads), kWgradF16Lds, s, all);
   } else {
     hipLaunchKernelGGL(wgrad_all_kernel<false>, dim3(blocks), dim3(kThreads), 2 * (8 * 512 / 4 + 8 * 64 / 4) * sizeof(f32x4), s, all);
@@ -2043,12 +2033,7 @@ void fill_wgrad_args(cmbpo_trainer *t, int layer, int batch, WgradArgs &a, int &
 
 template <int HID>
 int launch_bwd(const BwdArgs &a, int tiles, int E, size_t lds, hipStream_t s) {
-  static size_t attr_bytes = 0;
-  if (lds > attr_bytes) {
-    CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(bwd_chain_kernel<HID>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_bytes = lds;
-  }
+  if (int rc = cmbpo_grant_lds(bwd_chain_kernel<HID>, lds)) return rc;
   hipLaunchKernelGGL(bwd_chain_kernel<HID>, dim3(tiles, E), dim3(kThreads), lds, s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
@@ -2115,12 +2100,7 @@ int launch_bwd_h(cmbpo_trainer *t, const BwdArgs &b, int batch, hipStream_t s) {
   a.s3 = t->b16_s3;
   a.tiles32 = cmbpo_ceil_div(batch, 32);
   const size_t lds = bh_lds_bytes(t->b16_s3);
-  static size_t attr_bytes = 0;
-  if (lds > attr_bytes) {
-    CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(bwd_chain_h_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds));
-    attr_bytes = lds;
-  }
+  if (int rc = cmbpo_grant_lds(bwd_chain_h_kernel, lds)) return rc;
   hipLaunchKernelGGL(bwd_chain_h_kernel, dim3(cmbpo_ceil_div(batch, kBhRows), E), dim3(kBhThreads), lds, s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
@@ -2152,12 +2132,7 @@ int launch_fwd_h(cmbpo_trainer *t, const float *d_inputs, const int32_t *d_idx, 
     a.out_sig = m->has_out_scaler ? m->d_blob + m->off_out_var : nullptr;
   }
   a.tiles32 = cmbpo_ceil_div(rows, 32);
-  static bool attr = false;
-  if (!attr) {
-    CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(fwd_train_h_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)fh_lds_bytes()));
-    attr = true;
-  }
+  if (int rc = cmbpo_grant_lds(fwd_train_h_kernel, fh_lds_bytes())) return rc;
   hipLaunchKernelGGL(fwd_train_h_kernel, dim3(cmbpo_ceil_div(rows, kBhRows), t->E), dim3(kBhThreads), fh_lds_bytes(), s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
@@ -2242,20 +2217,10 @@ int launch_fused(cmbpo_trainer *t, const float *d_inputs, const float *d_targets
   const int G = t->ks[0];
   // every partial slot is written: workgroups beyond the batch's tiles store zeros
   if (t->IP <= 32) {
-    static bool set1 = false;
-    if (!set1) {
-      CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(fused_mse_step_kernel<1>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-      set1 = true;
-    }
+    if (int rc = cmbpo_grant_lds(fused_mse_step_kernel<1>, 152 * 1024)) return rc;
     hipLaunchKernelGGL(fused_mse_step_kernel<1>, dim3(G, t->E), dim3(kThreads), lds, s, a);
   } else {
-    static bool set2 = false;
-    if (!set2) {
-      CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(fused_mse_step_kernel<2>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-      set2 = true;
-    }
+    if (int rc = cmbpo_grant_lds(fused_mse_step_kernel<2>, 152 * 1024)) return rc;
     hipLaunchKernelGGL(fused_mse_step_kernel<2>, dim3(G, t->E), dim3(kThreads), lds, s, a);
   }
   CMBPO_HIP_CHECK(hipGetLastError());

@@ -851,13 +851,9 @@ size_t lds_bytes(const PiDims &d, bool f16) {
 }
 
 template <class KERN>
-int launch_pi_k(cmbpo_pi *h, PiArgs &a, hipStream_t s, KERN kern, size_t &attr_bytes, bool f16, bool reduce) {
+int launch_pi_k(cmbpo_pi *h, PiArgs &a, hipStream_t s, KERN kern, bool f16, bool reduce) {
   const size_t lds = lds_bytes(h->d, f16);   // (the kernels also have a few bytes of static LDS: ask for what is needed)
-  if (lds > attr_bytes) {
-    CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_bytes = lds;
-  }
+  if (int rc = cmbpo_grant_lds(kern, lds)) return rc;
   const int tiles = cmbpo_ceil_div(a.n, BB);
   const int resident = (h->d.H == HID ? 2 : 1) * h->n_cu;   // two 76.8 KB workgroups per CU (one of 150 KB at 256 hidden units)
   const int grid = tiles < resident ? tiles : resident;
@@ -873,12 +869,11 @@ int launch_pi_k(cmbpo_pi *h, PiArgs &a, hipStream_t s, KERN kern, size_t &attr_b
 
 template <int MODE, int N_IT>
 int launch_pi_n(cmbpo_pi *h, PiArgs &a, hipStream_t s) {
-  static size_t attr[4] = {0, 0, 0, 0};   // per kernel: the dynamic LDS already granted
-  if (h->d.H == 256) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 256>, attr[3], false, MODE != MODE_EVAL);
-  if (pi_path() == 0) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 128>, attr[0], false, MODE != MODE_EVAL);
+  if (h->d.H == 256) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 256>, false, MODE != MODE_EVAL);
+  if (pi_path() == 0) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 128>, false, MODE != MODE_EVAL);
   if (MODE == MODE_FVP && a.cache_r != nullptr)
-    return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, true>, attr[1], true, MODE != MODE_EVAL);
-  return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, false>, attr[2], true, MODE != MODE_EVAL);
+    return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, true>, true, MODE != MODE_EVAL);
+  return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, false>, true, MODE != MODE_EVAL);
 }
 
 template <int MODE>
@@ -960,14 +955,7 @@ extern "C" int cmbpo_pi_create(cmbpo_pi_t **out, int obs_dim, int hidden, int ac
   h->pack_floats = off;
   h->has_params = false;
   h->act = nullptr; h->act_tiles = 0; h->act_keep = false; h->act_valid = false; h->act_obs = nullptr; h->act_n = 0; h->act_hits = 0;
-  hipDeviceProp_t prop;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-    cmbpo_set_error("cmbpo_pi_create: cannot query the device");
-    delete h;
-    return CMBPO_EHIP;
-  }
-  h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  h->n_cu = cmbpo_cu_count();
   h->part_ld = (d.P + 63) / 64 * 64;
   h->parts = nullptr;
   h->blob16 = nullptr;

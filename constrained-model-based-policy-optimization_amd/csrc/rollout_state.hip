@@ -1436,13 +1436,7 @@ extern "C" int cmbpo_buffer_flatten(const cmbpo_rollout_t *r, const int32_t *d_o
   }
   hipStream_t s = (hipStream_t)stream;
   const int dmax = r->obs_dim > r->act_dim ? r->obs_dim : r->act_dim;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    hipDeviceProp_t prop;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-    if (n_cu <= 0) n_cu = 256;
-  }
+  const int n_cu = cmbpo_cu_count();
   // no path is longer than the steps the rollout took: tiles (and their LDS) are sized for those
   const int Tt = r->ptr > 0 ? r->ptr : 1;
   // branches per workgroup of the vector fields: as many as keep the [branch][step][dim] tile within 64 KB (two
@@ -1465,22 +1459,18 @@ extern "C" int cmbpo_buffer_flatten(const cmbpo_rollout_t *r, const int32_t *d_o
   const size_t lds = lds_v > lds_s ? lds_v : lds_s;
   const bool is_short = Tt <= 8;
   const int n_vec = cmbpo_ceil_div(r->B, vt);
-  static size_t attr[2][2] = {{64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024}};
-  auto launch = [&](auto kern, size_t &granted, int n_scalar) -> int {
-    if (lds > granted) {
-      CMBPO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      granted = lds;
-    }
+  auto launch = [&](auto kern, int n_scalar) -> int {
+    if (int rc = cmbpo_grant_lds(kern, lds)) return rc;
     hipLaunchKernelGGL(kern, dim3(n_vec + n_scalar), dim3(256), lds, s, *r, d_offsets, d_stats, fa, vt, Tt, n_vec);
     return CMBPO_OK;
   };
   int rc;
   if (rows == 16) {
-    rc = is_short ? launch(flatten_kernel<16, true>, attr[0][1], cmbpo_ceil_div(r->B, 16))
-                  : launch(flatten_kernel<16, false>, attr[0][0], cmbpo_ceil_div(r->B, 16));
+    rc = is_short ? launch(flatten_kernel<16, true>, cmbpo_ceil_div(r->B, 16))
+                  : launch(flatten_kernel<16, false>, cmbpo_ceil_div(r->B, 16));
   } else {
-    rc = is_short ? launch(flatten_kernel<kFlatRows, true>, attr[1][1], cmbpo_ceil_div(r->B, kFlatRows))
-                  : launch(flatten_kernel<kFlatRows, false>, attr[1][0], cmbpo_ceil_div(r->B, kFlatRows));
+    rc = is_short ? launch(flatten_kernel<kFlatRows, true>, cmbpo_ceil_div(r->B, kFlatRows))
+                  : launch(flatten_kernel<kFlatRows, false>, cmbpo_ceil_div(r->B, kFlatRows));
   }
   if (rc) return rc;
   CMBPO_HIP_CHECK(hipGetLastError());

@@ -31,10 +31,8 @@ for _ in range(3):
 h = C.CDLL(so)
 pad = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 h.cmbpo_debug_set_lds_pad(pad)
-h.cmbpo_set_stagger(int(sys.argv[3]) if len(sys.argv) > 3 else 0)
 h.cmbpo_debug_set_stamps.argtypes = [C.c_void_p]
 h.cmbpo_debug_set_stamps(stamps.data_ptr())
-print('stagger', sys.argv[3] if len(sys.argv) > 3 else 0)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record()
 m.predict_ensemble(obs, act=act, out=(mean, var))
