@@ -8,7 +8,7 @@
 // pieces a1 = f16(a s), a2 = f16(a s - a1) (the difference is exact in float32): 11 + 1 + 11 significant bits, i.e.
 // a s = (a1 + a2)(1 + d), |d| <= 2^-24 -- a float32 rounding.  Then
 //     a . b  =  [a2 b1 + a1 b2 + a1 b1] / (s t)  +  O(2^-23 |ab|)
-// as three v_mfma_f32_32x32x16_f16 with fp32 accumulation (every partial product exact, smallest first; the dropped
+// as three f16 MFMAs with fp32 accumulation (32x32x16 in layer 0, 16x16x32 in layers 1 and 2) (every partial product exact, smallest first; the dropped
 // a2 b2 <= 2^-24 |ab|).  Measured (tools/split_f16_probe.hip): error 3.2e-7 of sum|a_k b_k| at K = 512 -- the fp32 MFMA
 // chain 7.6e-7, the six-term bf16 split 6.2e-7 -- at half the matrix instructions of the latter.
 // Scales (all powers of two, so scaling and unscaling are exact):
@@ -46,18 +46,23 @@ constexpr int HIDH = 512;
 
 // Geometry of an item of RT 32-row tiles (4: the throughput shape; 2 / 1: the same kernel for rollout batches too small
 // to give every CU a 128-row item -- an item's latency is the step's there).  Whatever RT, a chunk of h1 is 8 (n-tile,
-// row-tile) pairs = one per wave, and a step of the fused layer-0/1 loop is 16 (slab, row tile) positions of 6 MFMAs.
+// row-tile) pairs = one per wave, and a step of the fused layer-0/1 loop is 16 (32-deep slab, 16-row tile) positions of
+// 12 v_mfma_f32_16x16x32_f16 (4 hidden 16-tiles x 3 terms).
 template <int RT>
 struct Geo {
   static constexpr int ROWS = 32 * RT;
   static constexpr int NTC = 8 / RT;           // hidden n-tiles per chunk
   static constexpr int CK = 32 * NTC;          // hidden units per chunk
   static constexpr int NCH = HIDH / CK;        // chunks
-  static constexpr int SLC = CK / 16;          // 16-deep slabs per chunk
+  static constexpr int SLC = CK / 32;          // 32-deep layer-1 slabs per chunk
   static constexpr int CSTR = CK + 8;          // row stride (halves) of a chunk image: 16-B slots per row odd -> conflict-free
   static constexpr int TPR = kThreadsH / ROWS; // threads staging one input row
   static constexpr int KPT = 64 / TPR;         // input elements per staging thread
-  static constexpr int DA = RT == 4 ? 2 : 4;   // ring of layer-1 weight fragments (slabs): DA - 1 slabs of lookahead
+  // ring of layer-1 weight fragments in half slabs (4 f16x8 = 16 registers: two hidden 16-tiles x two pieces): a half is
+  // requested as soon as the one DH halves before it has fed its last MFMA.  At 128 rows (128 accumulator registers) two:
+  // a half arrives 6 MFMAs ahead of its use (a third spills ~70 registers in the loop).
+  static constexpr int DH = RT == 4 ? 2 : 4;
+  static constexpr int NPH = (2 * SLC) % DH == 0 ? 1 : DH;   // steps after which the ring's registers line up again
   static constexpr int CBUF_BYTES = 2 * ROWS * CSTR * 2;          // one chunk image (both pieces)
   static constexpr bool W0_LDS = RT == 4;      // W0 fragments shared by several waves pass through LDS
 };
@@ -126,32 +131,42 @@ __global__ void h3_stats_kernel(const float *blob, size_t off0, size_t off1, siz
   }
 }
 
-// ---- fp32 pack -> two f16 images [n-tile][k-slab 16][piece 2][lane 64][8 halves] -----------------------------------------
-// lane (r, h), element j of slab s holds W[n = 32 tile + r][k = 16 s + 8 h + j] * scale; tiles >= src_tiles and k beyond the
-// pack are zero.  perm (output layer: its B operand is an accumulator tile, whose register i of lane half h is hidden
-// unit (i & 3) + 8 (i >> 2) + 4 h of the tile): slab s covers registers 8 (s & 1) .. + 7 of hidden n-tile s >> 1, i.e.
-// k = 32 (s >> 1) + (i & 3) + 8 (i >> 2) + 4 h with i = 8 (s & 1) + j.
+// ---- fp32 pack -> two f16 images [n-tile][k-slab][piece 2][lane 64][8 halves] -------------------------------------------
+// mode 0 / 1: v_mfma_f32_32x32x16_f16 A fragments, 32-wide n-tiles, 16-deep slabs.  Lane (r, h), element j of slab s holds
+// W[n = 32 tile + r][k = 16 s + 8 h + j] * scale.  1 (perm; policy / critic output layers: the B operand is a 32x32
+// accumulator tile, whose register i of lane half h is hidden unit (i & 3) + 8 (i >> 2) + 4 h of the tile): slab s covers
+// registers 8 (s & 1) .. + 7 of hidden n-tile s >> 1, i.e. k = 32 (s >> 1) + (i & 3) + 8 (i >> 2) + 4 h with i = 8 (s & 1) + j.
+// mode 2 / 3: v_mfma_f32_16x16x32_f16 A fragments, 16-wide n-tiles, 32-deep slabs.  Lane (r, g) = (l & 15, l >> 4), element
+// j of slab s holds W[n = 16 tile + r][k = 32 s + 8 pi(g) + j], pi = (0, 2, 1, 3) (the B reads of ens_h3's layer 1 take the
+// k chunks of an image row in that order: conflict-free ds_read_b128, see read_b there).  3 (ens_h3's output layer: the B
+// operand is two 16x16 accumulator tiles of hidden units, register i of lane group g of tile u = unit 16 u + 4 g + i):
+// k = 32 s + 16 (j >> 2) + 4 g + (j & 3).
+// n beyond the source's tiles and k beyond the pack are zero.
 __global__ void h3_pack_kernel(const float *src, size_t src_stride, int kg, int src_tiles, f16x8 *dst, size_t dst_stride,
-                               int n_tiles, int slabs, int members, const float *stats, int layer, int perm) {
+                               int n_tiles, int slabs, int members, const float *stats, int layer, int mode) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long per = (long)n_tiles * slabs * 64;
   if (idx >= per * members) return;
   const int e = (int)(idx / per);
   const int rem = (int)(idx - (long)e * per);
   const int lane = rem & 63, s = (rem >> 6) % slabs, tile = (rem >> 6) / slabs;
-  const int r = lane & 31, h = lane >> 5;
+  const bool m16 = mode >= 2;
+  const int n = m16 ? 16 * tile + (lane & 15) : 32 * tile + (lane & 31);
+  const int r = n & 31, g = m16 ? lane >> 4 : lane >> 5;
   const float scale = stats[(size_t)e * NSTAT + 4 * layer];
   const float *sp = src + (size_t)e * src_stride;
   f16x8 p1, p2;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    int k = 16 * s + 8 * h + j;
-    if (perm) {
+    int k;
+    if (mode == 0) k = 16 * s + 8 * g + j;
+    else if (mode == 1) {
       const int i = 8 * (s & 1) + j;
-      k = 32 * (s >> 1) + (i & 3) + 8 * (i >> 2) + 4 * h;
-    }
+      k = 32 * (s >> 1) + (i & 3) + 8 * (i >> 2) + 4 * g;
+    } else if (mode == 2) k = 32 * s + 8 * ((g & 1) * 2 + (g >> 1)) + j;
+    else k = 32 * s + 16 * (j >> 2) + 4 * g + (j & 3);
     float v = 0.0f;
-    if (tile < src_tiles && (k >> 3) < kg) v = sp[(((size_t)tile * kg + (k >> 3)) * 64 + ((k >> 2) & 1) * 32 + r) * 4 + (k & 3)];
+    if ((n >> 5) < src_tiles && (k >> 3) < kg) v = sp[(((size_t)(n >> 5) * kg + (k >> 3)) * 64 + ((k >> 2) & 1) * 32 + r) * 4 + (k & 3)];
     _Float16 q1, q2;
     split_h(v * scale, q1, q2);
     p1[j] = q1; p2[j] = q2;
@@ -185,15 +200,8 @@ __device__ __forceinline__ void static_for(F &&f) {
 #ifndef IN_SCALE_RCP
 #define IN_SCALE_RCP 1       // input scaler as (x - mu) (1 / sigma) (0: the IEEE division, diagnostic)
 #endif
-#ifndef H3_PEEL_LAST
-#define H3_PEEL_LAST 1      // the fused loop's last step as an instance of its own, without the production of a chunk nobody reads
-                            // (0: round 2's branch-free loop; measured 1.212 / 1.215 -> 1.199 / 1.198 ms per 100 k-row forward)
-#endif
 #ifndef H3_STORE8
 #define H3_STORE8 1         // diagnostic: 0 = the outputs as 4-byte lane stores (round 2)
-#endif
-#ifndef H3_TAIL_RING
-#define H3_TAIL_RING 0      // diagnostic: 1 = W2 fragments through the two-slab ring for every shape (round 2's tail)
 #endif
 
 struct H3Args {
@@ -209,7 +217,7 @@ template <int S0, int OTP, int RT>
 __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
   using G = Geo<RT>;
   constexpr int ROWSH = G::ROWS, NTC = G::NTC, CK = G::CK, NCH = G::NCH, SLC = G::SLC, CSTR = G::CSTR, TPR = G::TPR,
-                KPT = G::KPT, DA = G::DA, CBUF_BYTES = G::CBUF_BYTES;
+                KPT = G::KPT, DH = G::DH, NPH = G::NPH, CBUF_BYTES = G::CBUF_BYTES;
   constexpr int XSTR = 16 * S0 + 8;
   constexpr int NPASS = OTP / 2;         // output tiles are taken two at a time
   constexpr int NUNIT = RT * NPASS;      // (row tile, pass) units of the tail
@@ -408,30 +416,42 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
       return *reinterpret_cast<const f32x4 *>(bias0 + cc * CK + 32 * l0_tn + 8 * q + 4 * hh);
     };
 
-    f32x16 acc[2][RT];
+    // Layer 1 on v_mfma_f32_16x16x32_f16 (the same work as 32x32x16 at less power per FLOP; the chip holds its clock by
+    // power): wave w owns hidden units 64 w .. 64 w + 63 as four 16-tiles u x the item's 2 RT 16-row tiles v (128
+    // accumulator registers at RT == 4).  Column c of row tile v is item row 16 v + sig(c): sig even for c in {0..3, 12..15},
+    // odd for c in {4..11}.  With that and the image row's k chunks taken in the order pi = (0, 2, 1, 3) (h3_pack_kernel, mode
+    // 2), the ds_read_b128 of a B fragment is conflict-free: its 16-lane groups are {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}
+    // (+32), the row stride is odd in 16-B slots, so a group reads rows of one parity from one chunk and rows of the other
+    // from a chunk two slots away (the plain order is 2-way).
+    constexpr int VT = 2 * RT;
+    const int c16 = lane & 15, g4 = lane >> 4;
+    const int sig = c16 < 4 ? 2 * c16 : (c16 < 12 ? 2 * c16 - 7 : 2 * c16 - 16);
+    const int pik = 8 * (2 * (g4 & 1) + (g4 >> 1));
+    f32x4 acc[4][VT];
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+    for (int u = 0; u < 4; ++u)
 #pragma unroll
-      for (int bt = 0; bt < RT; ++bt)
+      for (int v = 0; v < VT; ++v)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][bt][i] = 0.0f;
-    const f16x8 *w1a = a.w1 + (size_t)e * a.w1_stride + (size_t)(2 * wave) * 32 * 128 + lane;   // [tile][slab 32][piece][lane]
-    f16x8 A[DA][2][2];     // ring over the layer-1 slabs: [slab % DA][n-tile][piece], DA - 1 slabs of lookahead
-    f16x8 Bt[3][2];        // rolling window over the (slab, row tile) sequence: current, +1, +2 (two LDS reads in flight)
-    auto load_a = [&](f16x8 (&x)[2][2], int s) {
+        for (int i = 0; i < 4; ++i) acc[u][v][i] = 0.0f;
+    const f16x8 *w1a = a.w1 + (size_t)e * a.w1_stride + (size_t)(4 * wave) * 16 * 128 + lane;   // [16-tile][slab 16][piece][lane]
+    f16x8 A[DH][2][2];     // ring over half slabs: [half % DH][16-tile of the pair][piece]; half h = 2 slab + (tiles 2, 3)
+    f16x8 Bt[2][2];        // [position & 1][piece]: the next position's fragments are read during the current one
+    auto load_h = [&](f16x8 (&x)[2][2], int h) {
+      h = h < 31 ? h : 31;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        const f16x8 *q = w1a + ((size_t)t * 32 + s) * 128;
+        const f16x8 *q = w1a + ((size_t)(2 * (h & 1) + t) * 16 + (h >> 1)) * 128;
         x[t][0] = q[0]; x[t][1] = q[64];
       }
     };
-    auto read_bt = [&](f16x8 (&x)[2], const _Float16 *img, int bt, int sl) {
-      const _Float16 *q = img + (size_t)(32 * bt + r) * CSTR + 16 * sl + 8 * hh;
+    auto read_b = [&](f16x8 (&x)[2], const _Float16 *img, int v, int sl) {
+      const _Float16 *q = img + (size_t)(16 * v + sig) * CSTR + 32 * sl + pik;
       x[0] = *reinterpret_cast<const f16x8 *>(q);
       x[1] = *reinterpret_cast<const f16x8 *>(q + (size_t)ROWSH * CSTR);
     };
 #pragma unroll
-    for (int s = 0; s < DA - 1; ++s) load_a(A[s], s);
+    for (int h = 0; h < DH; ++h) load_h(A[h], h);
     {   // chunk 0 of h1: nothing to overlap it with yet
       f32x16 d;
 #pragma unroll
@@ -453,15 +473,16 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
     H3_BARRIER();
     H3_STAMP(2);
 
-    // One step = the 96 layer-1 MFMAs of chunk c -- 16 (slab, row tile) positions of 6, in 8 groups of 12 -- with the
+    // One step = the 192 layer-1 MFMAs of chunk c -- 16 (slab, row tile) positions of 12, in 8 slots of 24 -- with the
     // production of chunk c + 1 dealt out between them: a wave issues in order, so what stands between two MFMAs runs in the
-    // shadow of the first.  Groups 0 .. S0-1 carry the layer-0 MFMAs of one input slab each (operands read one group
-    // ahead), groups 4 .. 7 one quarter of the swish / lift / split epilogue each, one piece behind every MFMA.  The last
-    // step has no chunk to produce: it is an instance of its own (H3_PEEL_LAST).
-    // H3_PEEL_LAST: the last step as an instance of its own without the production of a chunk nobody reads (9 MFMAs, a
-    // quarter-chunk epilogue and its LDS stores per wave)
-    auto step = [&](auto LASTC, const int c) {
+    // shadow of the first.  Slots 0 .. S0-1 carry the layer-0 MFMAs (32x32x16) of one input slab each (operands read one
+    // slot ahead), slots 4 .. 7 one quarter of the swish / lift / split epilogue each, a piece behind every second MFMA.
+    // Within a position the MFMAs of tiles 0, 1 come first: the last position of a slab frees that half of the ring 6 MFMAs
+    // before the other.  PH = c % NPH: where the ring stands (compile-time register indices).  The last step has no chunk to
+    // produce: an instance of its own.
+    auto step = [&](auto LASTC, const int c, auto PHC) {
       constexpr bool LAST = decltype(LASTC)::value;
+      constexpr int PH = decltype(PHC)::value;
       f16x8 wst;
       const bool stage_w0 = c + 2 < NCH;
       const int cw = stage_w0 ? c + 2 : NCH - 1;
@@ -472,8 +493,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
       L0Ops l0;
       Epi4 es;
       f32x4 bv = {0.0f, 0.0f, 0.0f, 0.0f};
-      read_bt(Bt[0], img, 0, 0);
-      read_bt(Bt[1], img, 1 % RT, 1 / RT);
+      read_b(Bt[0], img, 0, 0);
       if constexpr (!LAST) l0_read(l0, c + 1, 0);
 #pragma unroll
       for (int slot = 0; slot < 8; ++slot) {
@@ -487,51 +507,40 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
           }
         }
 #pragma unroll
-        for (int i = 0; i < 12; ++i) {
-          const int pos = 2 * slot + i / 6;                       // position in the (slab, row tile) sequence
-          const int sl = pos / RT, bt = pos % RT;
-          const int t = (i / 3) % 2, term = i % 3;
-          if (i % 6 == 0) {
-#ifndef H3_DIAG_NOA
-            if (bt == 0) {                                         // a new slab: request the one DA - 1 ahead
-              const int sn = c * SLC + sl + DA - 1;
-              load_a(A[(sl + DA - 1) % DA], sn < 32 ? sn : 31);
-            }
-#endif
-#ifndef H3_DIAG_NOBT
-            if (pos + 2 < 16) read_bt(Bt[(pos + 2) % 3], img, (pos + 2) % RT, (pos + 2) / RT);
-#endif
+        for (int i = 0; i < 24; ++i) {
+          const int pos = 2 * slot + i / 12;                      // position in the (slab, row tile) sequence
+          const int sl = pos / VT, v = pos % VT;
+          const int u = (i % 12) / 3, term = i % 3;
+          const int hl = 2 * sl + (u >> 1);                       // half of this step
+          f16x8(&Ah)[2][2] = A[(PH * 2 * SLC + hl) % DH];
+          if (i % 12 == 0) {
+            if (pos + 1 < 16) read_b(Bt[(pos + 1) & 1], img, (pos + 1) % VT, (pos + 1) / VT);
             if (i == 0) __builtin_amdgcn_sched_barrier(0);
           }
-          f16x8(&Ac)[2][2] = A[sl % DA];
-          f32x16 &ac = acc[t][bt];
-          const f16x8 &b1 = Bt[pos % 3][0], &b2 = Bt[pos % 3][1];
-          if (term == 0) ac = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ac[t][1], b1, ac, 0, 0, 0);
-          else if (term == 1) ac = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ac[t][0], b2, ac, 0, 0, 0);
-          else ac = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ac[t][0], b1, ac, 0, 0, 0);
-#ifndef H3_DIAG_NOL0
-          if (!LAST && slot < S0 && i == 5) {          // layer-0 MFMAs of input slab `slot`, then the next slab's operands
+          f32x4 &ac = acc[u][v];
+          const f16x8 &b1 = Bt[pos & 1][0], &b2 = Bt[pos & 1][1];
+          if (term == 0) ac = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[u & 1][1], b1, ac, 0, 0, 0);
+          else if (term == 1) ac = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[u & 1][0], b2, ac, 0, 0, 0);
+          else ac = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[u & 1][0], b1, ac, 0, 0, 0);
+          if (v == VT - 1 && (i % 12 == 5 || i % 12 == 11) && !(LAST && hl + DH >= 2 * SLC))
+            load_h(Ah, c * 2 * SLC + hl + DH);                    // the half's last MFMA: its successor DH halves on
+          if (!LAST && slot < S0 && i == 11) {                    // layer-0 MFMAs of input slab `slot`, then the next slab's operands
             mm3(d, l0.a1, l0.a2, l0.b1, l0.b2);
             if (slot + 1 < S0) l0_read(l0, c + 1, slot + 1);
           }
-#endif
-#ifdef H3_DIAG_NOEPI_LOOP
-          if (false) {
-#else
-          if (!LAST && slot >= 4) {
-#endif
-            const int q = slot - 4;
-            if (i == 0) epi_stage<0, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (i == 1) epi_stage<1, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (i == 2) epi_stage<2, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (i == 3) epi_stage<3, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (i == 4) epi_stage<4, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (i == 5) epi_stage<5, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (i == 6) epi_stage<6, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (i == 7) epi_stage<7, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (i == 8) epi_stage<8, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (i == 9) epi_stage<9, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (i == 10) l0_store(es, c + 1, q);
+          if (!LAST && slot >= 4 && i % 2 == 0) {
+            const int q = slot - 4, k = i / 2;
+            if (k == 0) epi_stage<0, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 1) epi_stage<1, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 2) epi_stage<2, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 3) epi_stage<3, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 4) epi_stage<4, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 5) epi_stage<5, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 6) epi_stage<6, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 7) epi_stage<7, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 8) epi_stage<8, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 9) epi_stage<9, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 10) l0_store(es, c + 1, q);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -546,14 +555,14 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
       H3_BARRIER();
       H3_STAMP(5);
     };
-#if H3_PEEL_LAST
+    {
+      constexpr int NREG = NCH - 1, NFULL = NREG / NPH * NPH;
 #pragma unroll 1
-    for (int c = 0; c < NCH - 1; ++c) step(std::false_type{}, c);
-    step(std::true_type{}, NCH - 1);
-#else
-#pragma unroll 1
-    for (int c = 0; c < NCH; ++c) step(std::false_type{}, c);
-#endif
+      for (int c0 = 0; c0 < NFULL; c0 += NPH)
+        static_for<0, NPH>([&](auto P) { step(std::false_type{}, c0 + decltype(P)::value, P); });
+      static_for<0, NREG - NFULL>([&](auto P) { step(std::false_type{}, NFULL + decltype(P)::value, P); });
+      step(std::true_type{}, NREG, std::integral_constant<int, NREG % NPH>{});
+    }
 
     // the next item's rows, biases and output bias: in flight behind the tail
     fetch_x(tid);
@@ -563,11 +572,11 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
     {
       float keep = 0.0f;      // every accumulator register stays live: the loop's MFMAs must all execute
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int u = 0; u < 4; ++u)
 #pragma unroll
-        for (int bt = 0; bt < RT; ++bt)
+        for (int v = 0; v < VT; ++v)
 #pragma unroll
-          for (int i = 0; i < 16; ++i) keep += acc[t][bt][i];
+          for (int i = 0; i < 4; ++i) keep += acc[u][v][i];
       if (keep == 123.456f) p.out0[0] = keep;
     }
     H3_BARRIER();
@@ -575,10 +584,11 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
 #endif
 
     // ---- tail: h2 -> output layer -> head -> stores, one (32-row tile, pair of output tiles) unit at a time.
-    // h2 never leaves the registers: an accumulator tile's rows are the next product's k index, so the wave's own 64 hidden
-    // units (4 slabs) are its slice of the output layer's K (W2 images packed in the matching k order), and the eight
-    // waves' partial outputs are added up through LDS in a fixed order.
-    const f16x8 *w2w = a.w2 + (size_t)e * a.w2_stride + lane + (size_t)(4 * wave) * 128;   // + (tile * 32 + S) * 128 + piece * 64
+    // h2 never leaves the registers: an accumulator tile's hidden units are the next product's k index, so the wave's own 64
+    // hidden units (2 32-deep k steps: 16-tiles 2 ks, 2 ks + 1 as one B fragment, W2 packed in that k order, h3_pack_kernel
+    // mode 3) are its slice of the output layer's K, and the eight waves' partial outputs are added up through LDS in a fixed
+    // order.  The output layer runs on 16x16x32 too: output 16-tile ot = 2 tt + a of the pair tt, 16-row tile vv of the unit.
+    const f16x8 *w2w = a.w2 + (size_t)e * a.w2_stride + lane;   // + (16-tile * 16 + slab) * 128 + piece * 64
     auto reduce_unit = [&](int u) {
       // wave w adds up registers 4q .. 4q+3 (q = w & 3) of output tile tt = w >> 2 of this unit over the eight waves,
       // applies the head (models/pens/pe.py:815-835) and leaves the values in the staging tile [row][column of the pair]
@@ -633,164 +643,135 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
         }
       }
     };
-    if constexpr (NPASS == 1 && !H3_TAIL_RING) {
-      // Two output tiles (every shipped task but Humanoid): the wave's 16 W2 fragments (its 4 slabs x 2 tiles x 2 pieces)
-      // stay in 64 registers for the four row tiles of the item -- requested once, behind the first row tile's epilogue,
-      // instead of once per row tile (a third of the item's L2 -> CU traffic, and an L2 round trip in front of every slab's
-      // MFMAs: the chip holds its clock by power, and weight fragments from L2 are what costs most of it beside the MFMAs).
-      f16x8 w2r[4][2][2];      // [slab][output tile][piece]
-      static_for<0, 4>([&](auto SI) {
-        constexpr int S = decltype(SI)::value;
+    // h2 of 32-row tile rt: swish, lift, split -- straight into B fragments [16-row tile vv][k step ks][piece]
+    auto h2_frag = [&](u32x4 (&bfu)[2][2][2], auto RTI) {
+      constexpr int rt = decltype(RTI)::value;
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-          const f16x8 *q = w2w + ((size_t)tt * 32 + S) * 128;
-          w2r[S][tt][0] = q[0]; w2r[S][tt][1] = q[64];
+      for (int vv = 0; vv < 2; ++vv) {
+        const int row = 32 * rt + 16 * vv + sig;
+        const float inv1_l = r_inv1[row] * kLog2e;
+        const float t2_l = H3_EPI_FUSE ? pow2_rcp(r_t2[row]) * kLog2e : r_t2[row] * kLn2;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias1 + 64 * wave + 16 * u + 4 * g4);
+          Epi4 es;
+          epi_all<false, true, H3_EPI_FUSE>(es, acc[u][2 * rt + vv], 0, inv1_l, bv, t2_l);
+          bfu[vv][u >> 1][0][2 * (u & 1)] = es.q1[0]; bfu[vv][u >> 1][0][2 * (u & 1) + 1] = es.q1[1];
+          bfu[vv][u >> 1][1][2 * (u & 1)] = es.q2[0]; bfu[vv][u >> 1][1][2 * (u & 1) + 1] = es.q2[1];
         }
-      });
+      }
+    };
+    // the output layer's MFMAs of k step ks for output tile pair tt: o[a][vv] += W2 fragments w[a][piece] x h2 fragments
+    auto out_mm = [&](f32x4 (&o)[2][2], const f16x8 (&w)[2][2], const u32x4 (&bfu)[2][2][2], int ks) {
+#pragma unroll
+      for (int vv = 0; vv < 2; ++vv) {
+        const f16x8 b1 = __builtin_bit_cast(f16x8, bfu[vv][ks][0]), b2 = __builtin_bit_cast(f16x8, bfu[vv][ks][1]);
+#pragma unroll
+        for (int aa = 0; aa < 2; ++aa) mm3(o[aa][vv], w[aa][0], w[aa][1], b1, b2);
+      }
+    };
+    // partial outputs of unit u to LDS in the layout of a 32x32 tile pair (what reduce_unit reads): lane (r, h), register
+    // group q of tile tt = outputs 32 tt + 8 q + 4 h .. + 3 of row r; a 16x16 lane (c, g) of o[tt][a][vv] holds outputs
+    // 32 tt + 16 a + 4 g .. + 3 of row 16 vv + sig(c)
+    auto put_partials = [&](const f32x4 (&o)[2][2][2], int u) {
+      f32x4 *pw = pbuf + ((size_t)(u & 1) * 64 + (size_t)wave * 8) * 64;
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int aa = 0; aa < 2; ++aa)
+#pragma unroll
+          for (int vv = 0; vv < 2; ++vv)
+            pw[(size_t)(tt * 4 + 2 * aa + (g4 >> 1)) * 64 + 16 * vv + sig + 32 * (g4 & 1)] = o[tt][aa][vv];
+    };
+    auto zero_o = [&](f32x4 (&o)[2][2][2]) {
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int aa = 0; aa < 2; ++aa)
+#pragma unroll
+          for (int vv = 0; vv < 2; ++vv)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[tt][aa][vv][i] = 0.0f;
+    };
+    if constexpr (NPASS == 1) {
+      // Two output tiles (every shipped task but Humanoid): the wave's 16 W2 fragments (its 2 k steps x 4 output 16-tiles x 2
+      // pieces) stay in 64 registers for the four row tiles of the item -- requested once, behind the first row tile's
+      // epilogue, instead of once per row tile (a third of the item's L2 -> CU traffic, and an L2 round trip in front of every
+      // k step's MFMAs: the chip holds its clock by power, and weight fragments from L2 are what costs most of it beside the MFMAs).
+      f16x8 w2r[2][2][2][2];      // [k step][output tile pair][a][piece]
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int ot = 0; ot < 4; ++ot) {
+          const f16x8 *q = w2w + ((size_t)ot * 16 + 2 * wave + ks) * 128;
+          w2r[ks][ot >> 1][ot & 1][0] = q[0]; w2r[ks][ot >> 1][ot & 1][1] = q[64];
+        }
       // The tail as four stages per row tile, A: swish / lift / split of h2 (VALU) -> B: output-layer MFMAs + partial sums to
       // LDS -> [barrier] -> C: sum of the eight waves' partials + head -> D: stores.  Between two barriers a wave runs
       // D(k-2), C(k-1), B(k), A(k+1).  Measured (profiles/r03/h3_variants_5.log, _6.log): each stage costs about what its
       // instructions cost alone (A 5.7 %, B 5.1 %, C + D 4.5 % of a forward); giving the two waves of a SIMD opposite orders
-      // inside an interval (-DH3_TAIL_STAGGER: waves 4-7 run A(k+1) first) or dealing A(k+1) out between B(k)'s MFMAs
-      // changed nothing (1.264 -> 1.269 ms), so the plain order stands.
-      u32x4 bfu[2][4][2];        // [row tile & 1][slab of this wave's K slice][piece]
-      auto stA = [&](auto RTI) {
-        constexpr int rt = decltype(RTI)::value;
-        const float inv1_l = r_inv1[32 * rt + r] * kLog2e;
-        const float t2_l = H3_EPI_FUSE ? pow2_rcp(r_t2[32 * rt + r]) * kLog2e : r_t2[32 * rt + r] * kLn2;
-        static_for<0, 8>([&](auto QD) {
-          constexpr int quad = decltype(QD)::value, S = quad >> 1, jq = quad & 1, q = 2 * (S & 1) + jq;
-          const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias1 + 64 * wave + 32 * (S >> 1) + 8 * q + 4 * hh);
-          Epi4 es;
-#ifdef H3_DIAG_TAIL_NOA
-          es.q1[0] = __float_as_uint(acc[S >> 1][rt][4 * q] + bv[0]) & 0x3fff3fffu; es.q1[1] = __float_as_uint(acc[S >> 1][rt][4 * q + 1] + inv1_l) & 0x3fff3fffu;
-          es.q2[0] = __float_as_uint(acc[S >> 1][rt][4 * q + 2] + t2_l) & 0x3fff3fffu; es.q2[1] = __float_as_uint(acc[S >> 1][rt][4 * q + 3]) & 0x3fff3fffu;
-#else
-          epi_all<false, true, H3_EPI_FUSE>(es, acc[S >> 1][rt], q, inv1_l, bv, t2_l);
-#endif
-          bfu[rt & 1][S][0][2 * jq] = es.q1[0]; bfu[rt & 1][S][0][2 * jq + 1] = es.q1[1];
-          bfu[rt & 1][S][1][2 * jq] = es.q2[0]; bfu[rt & 1][S][1][2 * jq + 1] = es.q2[1];
-        });
-      };
+      // inside an interval or dealing A(k+1) out between B(k)'s MFMAs changed nothing (1.264 -> 1.269 ms), so the plain
+      // order stands.
+      u32x4 bfu[2][2][2][2];     // [row tile & 1][16-row tile][k step][piece]
+      auto stA = [&](auto RTI) { h2_frag(bfu[decltype(RTI)::value & 1], RTI); };
       auto stB = [&](auto RTI) {
         constexpr int rt = decltype(RTI)::value;
-        f32x16 o[2];
+        f32x4 o[2][2][2];
+        zero_o(o);
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
+        for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-          for (int i = 0; i < 16; ++i) o[tt][i] = 0.0f;
-        static_for<0, 4>([&](auto SI) {
-          constexpr int S = decltype(SI)::value;
-          const f16x8 b1 = __builtin_bit_cast(f16x8, bfu[rt & 1][S][0]), b2 = __builtin_bit_cast(f16x8, bfu[rt & 1][S][1]);
-#ifdef H3_DIAG_TAIL_NOB
-#pragma unroll
-          for (int tt = 0; tt < 2; ++tt) { o[tt][S] += (float)b1[tt] + (float)w2r[S][tt][0][0]; o[tt][S + 4] += (float)b2[tt] + (float)w2r[S][tt][1][1]; }
-#else
-#pragma unroll
-          for (int tt = 0; tt < 2; ++tt) mm3(o[tt], w2r[S][tt][0], w2r[S][tt][1], b1, b2);
-#endif
-        });
-        f32x4 *pw = pbuf + ((size_t)(rt & 1) * 64 + (size_t)wave * 8) * 64 + lane;
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x4 v = {o[tt][4 * q], o[tt][4 * q + 1], o[tt][4 * q + 2], o[tt][4 * q + 3]};
-            pw[(size_t)(tt * 4 + q) * 64] = v;
-          }
+          for (int tt = 0; tt < 2; ++tt) out_mm(o[tt], w2r[ks][tt], bfu[rt & 1], ks);
+        put_partials(o, rt);
       };
       stA(std::integral_constant<int, 0>{});
       static_for<0, RT + 2>([&](auto KI) {
         constexpr int k = decltype(KI)::value;      // interval k: D(k - 2), C(k - 1), B(k), A(k + 1)
-        auto matrix_side = [&]() {
-#ifndef H3_DIAG_TAIL_NOD
-          if constexpr (k >= 2 && k - 2 < RT) store_unit(k - 2);
-#endif
-#ifndef H3_DIAG_TAIL_NOC
-          if constexpr (k >= 1 && k - 1 < RT) reduce_unit(k - 1);
-#endif
-          if constexpr (k < RT) stB(std::integral_constant<int, (k < RT ? k : 0)>{});
-        };
-        auto valu_side = [&]() {
-          if constexpr (k + 1 < RT) stA(std::integral_constant<int, (k + 1 < RT ? k + 1 : 0)>{});
-        };
-#ifdef H3_TAIL_STAGGER      // diagnostic (from the second interval on: in the first it spills 45 registers)
-        if (k == 0 || wave < 4) { matrix_side(); valu_side(); }
-        else { valu_side(); matrix_side(); }
-#else
-        matrix_side(); valu_side();
-#endif
+        if constexpr (k >= 2 && k - 2 < RT) store_unit(k - 2);
+        if constexpr (k >= 1 && k - 1 < RT) reduce_unit(k - 1);
+        if constexpr (k < RT) stB(std::integral_constant<int, (k < RT ? k : 0)>{});
+        if constexpr (k + 1 < RT) stA(std::integral_constant<int, (k + 1 < RT ? k + 1 : 0)>{});
         H3_STAMP(7);
         if constexpr (k + 1 < RT + 2) H3_BARRIER();
         H3_STAMP(8);
       });
     } else {
+      // four output tiles (Humanoid): per row tile two passes over the output layer, the W2 fragments of one (k step, tile
+      // pair) stage in flight behind the MFMAs of the previous
+      static_for<0, RT>([&](auto RTI) {
+        constexpr int rt = decltype(RTI)::value;
+        f16x8 wf[2][2][2];       // [ping-pong][a][piece]
+        auto load_w2 = [&](f16x8 (&x)[2][2], int pass, int st) {   // stage st = 2 ks + tt
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      f16x8 wf[2][2][2];       // [ping-pong][output tile of the pair][piece]
-      auto load_w2 = [&](f16x8 (&x)[2][2], int pass, int S) {
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-          const f16x8 *q = w2w + ((size_t)(2 * pass + tt) * 32 + S) * 128;
-          x[tt][0] = q[0]; x[tt][1] = q[64];
-        }
-      };
-      load_w2(wf[0], 0, 0);
-      // this row tile of h2: swish, lift, split -- straight into B fragments
-      f16x8 bf[4][2];
-      {
-        u32x4 bfu[4][2];
-        const float inv1_l = r_inv1[32 * rt + r] * kLog2e;
-        const float t2_l = H3_EPI_FUSE ? pow2_rcp(r_t2[32 * rt + r]) * kLog2e : r_t2[32 * rt + r] * kLn2;
-#pragma unroll
-        for (int S = 0; S < 4; ++S)
-#pragma unroll
-          for (int jq = 0; jq < 2; ++jq) {
-            const int q = 2 * (S & 1) + jq;
-            const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias1 + 64 * wave + 32 * (S >> 1) + 8 * q + 4 * hh);
-            Epi4 es;
-            epi_all<false, true, H3_EPI_FUSE>(es, acc[S >> 1][rt], q, inv1_l, bv, t2_l);
-            bfu[S][0][2 * jq] = es.q1[0]; bfu[S][0][2 * jq + 1] = es.q1[1];
-            bfu[S][1][2 * jq] = es.q2[0]; bfu[S][1][2 * jq + 1] = es.q2[1];
+          for (int aa = 0; aa < 2; ++aa) {
+            const f16x8 *q = w2w + ((size_t)(4 * pass + 2 * (st & 1) + aa) * 16 + 2 * wave + (st >> 1)) * 128;
+            x[aa][0] = q[0]; x[aa][1] = q[64];
           }
+        };
+        load_w2(wf[0], 0, 0);
+        u32x4 bfu[2][2][2];
+        h2_frag(bfu, RTI);
 #pragma unroll
-        for (int S = 0; S < 4; ++S)
+        for (int pass = 0; pass < NPASS; ++pass) {
+          const int u = rt * NPASS + pass;
+          f32x4 o[2][2][2];
+          zero_o(o);
 #pragma unroll
-          for (int pc = 0; pc < 2; ++pc) bf[S][pc] = __builtin_bit_cast(f16x8, bfu[S][pc]);
-      }
-#pragma unroll
-      for (int pass = 0; pass < NPASS; ++pass) {
-        const int u = rt * NPASS + pass;
-        f32x16 o[2];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) o[tt][i] = 0.0f;
-#pragma unroll
-        for (int S = 0; S < 4; ++S) {
-          const int nS = (S + 1) & 3, npass = (S == 3) ? pass + 1 : pass;
-          if (S < 3 || pass + 1 < NPASS) load_w2(wf[(S & 1) ^ 1], npass, nS);
-#pragma unroll
-          for (int tt = 0; tt < 2; ++tt) mm3(o[tt], wf[S & 1][tt][0], wf[S & 1][tt][1], bf[S][0], bf[S][1]);
-        }
-        f32x4 *pw = pbuf + ((size_t)(u & 1) * 64 + (size_t)wave * 8) * 64 + lane;
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x4 v = {o[tt][4 * q], o[tt][4 * q + 1], o[tt][4 * q + 2], o[tt][4 * q + 3]};
-            pw[(size_t)(tt * 4 + q) * 64] = v;
+          for (int st = 0; st < 4; ++st) {
+            if (st < 3 || pass + 1 < NPASS) load_w2(wf[(st & 1) ^ 1], st == 3 ? pass + 1 : pass, (st + 1) & 3);
+            out_mm(o[st & 1], wf[st & 1], bfu, st >> 1);
           }
-        H3_STAMP(7);
-        H3_BARRIER();       // unit u's partials are complete; unit u - 1's staging tile too
-        H3_STAMP(8);
-        if (u > 0) store_unit(u - 1);
-        reduce_unit(u);
-        H3_STAMP(9);
-      }
-    }
-    H3_BARRIER();
-    store_unit(NUNIT - 1);
+          put_partials(o, u);
+          H3_STAMP(7);
+          H3_BARRIER();       // unit u's partials are complete; unit u - 1's staging tile too
+          H3_STAMP(8);
+          if (u > 0) store_unit(u - 1);
+          reduce_unit(u);
+          H3_STAMP(9);
+        }
+      });
+      H3_BARRIER();
+      store_unit(NUNIT - 1);
     }
     H3_STAMP(10);
     H3_BARRIER();     // the LDS regions are rewritten by the next item's stage
@@ -811,8 +792,8 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
 static int ensure_h3(cmbpo_mlp *m, hipStream_t s) {
   const int H = m->hidden, E = m->ensemble;
   const int S0 = m->h3_s0, OTP = m->h3_otp;
-  const int slabs[3] = {S0, H / 16, H / 16};
-  const int tiles[3] = {H / 32, H / 32, OTP};
+  const int slabs[3] = {S0, H / 32, H / 32};        // layer 0: 32x32x16 fragments; layers 1, 2: 16x16x32 (pack modes 2, 3)
+  const int tiles[3] = {H / 32, H / 16, 2 * OTP};
   if (m->d_h3 == nullptr) {
     size_t off = 0;
     for (int l = 0; l < 3; ++l) {
@@ -842,7 +823,7 @@ static int ensure_h3(cmbpo_mlp *m, hipStream_t s) {
     const long total = (long)tiles[l] * slabs[l] * 64 * E;
     hipLaunchKernelGGL(h3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, m->d_blob + src_off[l], src_stride,
                        kg[l], src_tiles[l], reinterpret_cast<f16x8 *>(m->d_h3) + m->h3_off[l], m->h3_stride[l], tiles[l], slabs[l],
-                       E, stats, l, l == 2 ? 1 : 0);
+                       E, stats, l, l == 0 ? 0 : l + 1);
   }
   CMBPO_HIP_CHECK(hipGetLastError());
   m->h3_version = m->pack_version;

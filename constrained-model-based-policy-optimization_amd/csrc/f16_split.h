@@ -50,6 +50,11 @@ __device__ __forceinline__ void mm3(f32x16 &acc, const f16x8 &a1, const f16x8 &a
   acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b2, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1, acc, 0, 0, 0);
 }
+__device__ __forceinline__ void mm3(f32x4 &acc, const f16x8 &a1, const f16x8 &a2, const f16x8 &b1, const f16x8 &b2) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, b1, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b2, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b1, acc, 0, 0, 0);
+}
 
 // ---- two floats x t -> their two f16 pieces, packed ------------------------------------------------------------------
 // p1 = f16(x t), p2 = f16(x t - p1): one v_fma_mix each (see the epilogue below).  HAZ: the pieces feed an MFMA straight from
@@ -85,8 +90,9 @@ constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
 // division by tn as the multiplier of ONE fma that also adds the 1 (stage 4) -- so the mixed-precision FMAs of the split form
 // z (sigma tn) themselves (exact inside the FMA) and the separate product z sigma (stage 7) is gone: 6 instead of 7 vector
 // instructions per activation (5 + the scaling in PRE's case).  e = inf (z -> -inf) gives sigma tn = 0, e = 0 gives tn.
-template <int K, bool PIN, bool PRE = false, bool FUSE = false>
-__device__ __forceinline__ void epi_stage(Epi4 &s, const f32x16 &d, int q, float inv, const f32x4 &bv, float tn) {
+// (d: a 32x32 accumulator tile, values 4q .. 4q+3, or a 16x16 one, q = 0)
+template <int K, bool PIN, bool PRE = false, bool FUSE = false, class D>
+__device__ __forceinline__ void epi_stage(Epi4 &s, const D &d, int q, float inv, const f32x4 &bv, float tn) {
   if constexpr (PRE && K == 1) {
     // (nothing: the scaling is in inv / bv)
   } else if constexpr (PRE && (K == 2 || K == 3)) {
@@ -167,8 +173,8 @@ __device__ __forceinline__ void epi_stage(Epi4 &s, const f32x16 &d, int q, float
     if (PIN) asm volatile("" : "+v"(s.q2[0]), "+v"(s.q2[1]));
   }
 }
-template <bool PIN, bool PRE = false, bool FUSE = false>
-__device__ __forceinline__ void epi_all(Epi4 &s, const f32x16 &d, int q, float inv, const f32x4 &bv, float tn) {
+template <bool PIN, bool PRE = false, bool FUSE = false, class D>
+__device__ __forceinline__ void epi_all(Epi4 &s, const D &d, int q, float inv, const f32x4 &bv, float tn) {
   epi_stage<0, PIN, PRE, FUSE>(s, d, q, inv, bv, tn); epi_stage<1, PIN, PRE, FUSE>(s, d, q, inv, bv, tn);
   epi_stage<2, PIN, PRE, FUSE>(s, d, q, inv, bv, tn); epi_stage<3, PIN, PRE, FUSE>(s, d, q, inv, bv, tn);
   epi_stage<4, PIN, PRE, FUSE>(s, d, q, inv, bv, tn); epi_stage<5, PIN, PRE, FUSE>(s, d, q, inv, bv, tn);
