@@ -48,3 +48,17 @@ static inline int cmbpo_ceil_div(int a, int b) { return (a + b - 1) / b; }
 __device__ __forceinline__ float cmbpo_fast_tanh(float x) {
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x));
 }
+
+// A workgroup barrier that orders LDS traffic only: the LDS counter is drained, then s_barrier.  __syncthreads() is a
+// workgroup-scope fence + s_barrier, in front of which hipcc waits vmcnt(0), i.e. for every global access still in flight;
+// here the compiler still tracks the loads and waits for each one where its value is used.  NOT for a barrier that publishes
+// LDS-DMA data (counted in vmcnt).
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// sum over the 64 lanes of a wave, valid in lane 0
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}

@@ -15,13 +15,8 @@
 #include "f16_split.h"
 #include "policy_f16_tile.h"
 
-#include <stdlib.h>
-
 namespace {
 
-#ifndef IN_SCALE_RCP
-#define IN_SCALE_RCP 1     // input scaler as (x - mu) (1 / sigma) (0: the IEEE division, diagnostic)
-#endif
 constexpr int HC = 128;          // hidden units
 constexpr int NT = HC / 32;      // n-tiles
 constexpr int S1 = HC / 16;      // k-slabs of layer 1
@@ -97,7 +92,7 @@ __global__ __launch_bounds__(512) void critic_pair_kernel(const CfArgs a) {
       const CfNet &M = a.net[n2];
       const int kc = k < a.obs_dim ? k : 0;
       s_mu[n2][k] = (M.in_mu && k < a.obs_dim) ? M.in_mu[kc] : 0.0f;
-      s_sig[n2][k] = (M.in_mu && k < a.obs_dim) ? (IN_SCALE_RCP ? 1.0f / M.in_sig[kc] : M.in_sig[kc]) : 1.0f;      // 1 / sigma
+      s_sig[n2][k] = (M.in_mu && k < a.obs_dim) ? 1.0f / M.in_sig[kc] : 1.0f;      // 1 / sigma
     }
     __syncthreads();
     if (a.has_store) {
@@ -147,7 +142,7 @@ __global__ __launch_bounds__(512) void critic_pair_kernel(const CfArgs a) {
       const int k = 16 * s + 8 * hh + j;
       // TensorStandardScaler.transform, utils.py:156, as (x - mu) (1 / sigma): within an ulp of the division (sixteen IEEE
       // divisions per lane were a fifth of a (tile, member) unit's vector instructions)
-      float x = IN_SCALE_RCP ? (xraw[r * (KP + 1) + k] - s_mu[ni][k]) * s_sig[ni][k] : (xraw[r * (KP + 1) + k] - s_mu[ni][k]) / s_sig[ni][k];
+      float x = (xraw[r * (KP + 1) + k] - s_mu[ni][k]) * s_sig[ni][k];
       if (k >= a.obs_dim) x = 0.0f;
       xs[s][j] = x;
       m0 = fmaxf(m0, fabsf(x));
@@ -190,7 +185,7 @@ __global__ __launch_bounds__(512) void critic_pair_kernel(const CfArgs a) {
       for (int q = 0; q < 4; ++q) {
         const f32x4 bv = *reinterpret_cast<const f32x4 *>(b0 + 32 * t + 8 * q + 4 * hh);
         Epi4 es;
-        epi_all<false, true, true>(es, acc[t], q, inv0l, bv, it1);     // (pre-scaled operands, the lift in the reciprocal: f16_split.h)
+        epi_all<false>(es, acc[t], q, inv0l, bv, it1);     // (pre-scaled operands, the lift in the reciprocal: f16_split.h)
         const int S = 2 * t + (q >> 1), o = 2 * (q & 1);
         bu[S][0][o] = es.q1[0]; bu[S][0][o + 1] = es.q1[1];
         bu[S][1][o] = es.q2[0]; bu[S][1][o + 1] = es.q2[1];
@@ -288,7 +283,7 @@ __global__ __launch_bounds__(512) void critic_big_kernel(const CfArgs a, int ch_
     const CfNet &M = a.net[n2];
     const int kc = k < a.obs_dim ? k : 0;
     s_mu[n2 * KP + k] = (M.in_mu && k < a.obs_dim) ? M.in_mu[kc] : 0.0f;
-    s_sig[n2 * KP + k] = (M.in_mu && k < a.obs_dim) ? (IN_SCALE_RCP ? 1.0f / M.in_sig[kc] : M.in_sig[kc]) : 1.0f;      // 1 / sigma
+    s_sig[n2 * KP + k] = (M.in_mu && k < a.obs_dim) ? 1.0f / M.in_sig[kc] : 1.0f;      // 1 / sigma
   }
   __syncthreads();
   for (int base = 0; base < tiles * 32 * KP; base += 512 * 4) {     // four requests in flight per thread
@@ -343,7 +338,7 @@ __global__ __launch_bounds__(512) void critic_big_kernel(const CfArgs a, int ch_
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int k = 16 * s + 8 * hh + j;
-          float x = IN_SCALE_RCP ? (xt[r * XS + k] - s_mu[ni * KP + k]) * s_sig[ni * KP + k] : (xt[r * XS + k] - s_mu[ni * KP + k]) / s_sig[ni * KP + k];   // TensorStandardScaler.transform, utils.py:156 (x 1 / sigma)
+          float x = (xt[r * XS + k] - s_mu[ni * KP + k]) * s_sig[ni * KP + k];   // TensorStandardScaler.transform, utils.py:156 (x 1 / sigma)
           if (k >= a.obs_dim) x = 0.0f;
           xs[s][j] = x;
           m0 = fmaxf(m0, fabsf(x));
@@ -385,7 +380,7 @@ __global__ __launch_bounds__(512) void critic_big_kernel(const CfArgs a, int ch_
           for (int q = 0; q < 4; ++q) {
             const f32x4 bv = *reinterpret_cast<const f32x4 *>(b0 + 32 * tt + 8 * q + 4 * hh);
             Epi4 es;
-            epi_all<false, true, true>(es, acc[tt], q, inv0l, bv, it1);
+            epi_all<false>(es, acc[tt], q, inv0l, bv, it1);
             const int S = 2 * tt + (q >> 1), o = 2 * (q & 1);
             bu[S][0][o] = es.q1[0]; bu[S][0][o + 1] = es.q1[1];
             bu[S][1][o] = es.q2[0]; bu[S][1][o + 1] = es.q2[1];
@@ -500,12 +495,6 @@ extern "C" int cmbpo_critic_pair_predict(cmbpo_mlp_t *v, cmbpo_mlp_t *vc, const 
                                          nullptr, nullptr, nullptr, stream);
 }
 
-// rows from which the critics run member after member with LDS-resident weights (critic_big_kernel; no rider there)
-int cmbpo_internal_critic_big_min() {
-  static const int v = getenv("CMBPO_CRITIC_BIG_MIN") ? atoi(getenv("CMBPO_CRITIC_BIG_MIN")) : 24576;
-  return v;
-}
-
 // can the actor ride along? (its f16 kernel applies, same input width, room for one more wave)
 bool cmbpo_internal_critic_pair_can_ride(const cmbpo_mlp *v, const cmbpo_mlp *vc, const cmbpo_mlp *policy) {
   return cmbpo_critic_pair_supported(v, vc) && policy && cmbpo_internal_policy_f16_eligible(policy) && policy->in_dim == v->in_dim &&
@@ -563,13 +552,13 @@ int cmbpo_internal_critic_pair_ride(cmbpo_mlp *v, cmbpo_mlp *vc, const float *d_
   }
   a.has_store = 0;
   if (store_vec != nullptr) {
-    CMBPO_REQUIRE(d_row_idx != nullptr && n_rows < cmbpo_internal_critic_big_min() && store_vec->fin_code,
+    CMBPO_REQUIRE(d_row_idx != nullptr && n_rows < kCriticBigMin && store_vec->fin_code,
                   "critic pair: the store rides with the one-wave-per-member kernel on a row list only");
     a.sv = *store_vec;
     a.has_store = 1;
   }
   // large batches without a rider: members one after the other with their weights in LDS (critic_big_kernel)
-  if (!a.has_pol && n_rows >= cmbpo_internal_critic_big_min()) {
+  if (!a.has_pol && n_rows >= kCriticBigMin) {
     const int n_cu = cmbpo_cu_count();
     auto launch_big = [&](auto geo, auto kern) -> int {
       using G = decltype(geo);

@@ -34,8 +34,6 @@
 #include "ens_mlp_internal.h"
 #include "f16_split.h"
 
-#include <stdlib.h>
-
 #include <type_traits>
 
 namespace {
@@ -185,24 +183,9 @@ __device__ __forceinline__ void static_for(F &&f) {
 }
 
 // The item loop's barriers order LDS traffic only (images, partial sums, staging tiles; nothing stored to global memory is read
-// back inside the kernel).  __syncthreads() is a workgroup fence + s_barrier, in front of which hipcc waits vmcnt(0): for
-// every global access in flight -- the output stores of the previous unit (a write acknowledgement from HBM), the next
-// item's input rows and row indices, the weight fragments requested a slab ahead.  Draining the LDS counter is enough.
-#ifdef H3_FULL_BARRIERS      // diagnostic: round 2's barriers
-#define H3_BARRIER() __syncthreads()
-#else
-#define H3_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#endif
-
-#ifndef H3_EPI_FUSE
-#define H3_EPI_FUSE 1       // diagnostic: 0 = round 2's epilogue (separate product z sigma(z), the lift in the split's FMAs)
-#endif
-#ifndef IN_SCALE_RCP
-#define IN_SCALE_RCP 1       // input scaler as (x - mu) (1 / sigma) (0: the IEEE division, diagnostic)
-#endif
-#ifndef H3_STORE8
-#define H3_STORE8 1         // diagnostic: 0 = the outputs as 4-byte lane stores (round 2)
-#endif
+// back inside the kernel), so they are lds_barrier()s: a __syncthreads() would wait for every global access in flight -- the
+// output stores of the previous unit (a write acknowledgement from HBM), the next item's input rows and row indices, the
+// weight fragments requested a slab ahead.
 
 struct H3Args {
   MlpKernelArgs m;
@@ -243,7 +226,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
   if (threadIdx.x < 64) {   // input scaler, once per workgroup (TensorStandardScaler.transform, models/pens/utils.py:156)
     const int k = threadIdx.x;
     in_mu_l[k] = (p.in_mu && k < p.in_dim) ? p.in_mu[k] : 0.0f;
-    in_sig_l[k] = (p.in_mu && k < p.in_dim) ? (IN_SCALE_RCP ? 1.0f / p.in_sig[k] : p.in_sig[k]) : 1.0f;      // 1 / sigma: see the stage
+    in_sig_l[k] = (p.in_mu && k < p.in_dim) ? 1.0f / p.in_sig[k] : 1.0f;      // 1 / sigma: see the stage
   }
   __syncthreads();
 
@@ -290,9 +273,6 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
   const unsigned long long t_rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
 
-#ifdef H3_EXP_PRIO
-  if (threadIdx.x >= 256) __builtin_amdgcn_s_setprio(1);     // the second-dispatched half loses every arbitration otherwise
-#endif
   for (int item = a.item0 + blockIdx.x; item < p.n_items; item += gridDim.x) {
     // the thread index, re-read inside the loop through an opaque move: everything derived from it is recomputed per
     // item instead of being hoisted out of the loop and parked in scratch (the loop body needs every register)
@@ -322,7 +302,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
           w0r[u] = w0e[(size_t)(j < 2 * W0P ? j : 0) * 64 + lane];
         }
       }
-      bias0[tid] = bpre[0] * kLog2e;      // (the epilogues work on z log2(e): epi_stage<.., PRE>)
+      bias0[tid] = bpre[0] * kLog2e;      // (the epilogues work on z log2(e): f16_split.h)
       bias1[tid] = bpre[1] * kLog2e;
       if (tid < O_PAD) {
         // y = A_n z + B_n with z = o + b2_n; n < out: mean = sig z + mu; out <= n < 2 out: var = exp(z + 2 log sig)
@@ -340,7 +320,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
         const int k = KPT * xc + u;
         // TensorStandardScaler.transform (models/pens/utils.py:156) as (x - mu) (1 / sigma): within an ulp of the division, a
         // tenth of its instructions (sixteen IEEE divisions per thread were a third of the stage)
-        float x = IN_SCALE_RCP ? (xpre[u] - in_mu_l[k & 63]) * in_sig_l[k & 63] : (xpre[u] - in_mu_l[k & 63]) / in_sig_l[k & 63];
+        float x = (xpre[u] - in_mu_l[k & 63]) * in_sig_l[k & 63];
         x = (k < p.in_dim && rr_pre >= 0) ? x : 0.0f;
         xs[u] = x;
         m = fmaxf(m, fabsf(x));
@@ -388,13 +368,13 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
     }
     fetch_row(item + gridDim.x, tid);     // the next item's row index: lands during the layers
     H3_STAMP(0);
-    H3_BARRIER();
+    lds_barrier();
     H3_STAMP(1);
 
     // ---- layers 0 + 1, fused over the 8 chunks of h1 -------------------------------------------------------------------
     const int l0_tn = wave & (NTC - 1), l0_bt = wave / NTC;     // this wave's (n-tile, row-tile) pair of every chunk
     const float inv0_l = r_inv0[32 * l0_bt + r] * kLog2e;
-    const float t1_l = H3_EPI_FUSE ? pow2_rcp(r_t1[32 * l0_bt + r]) * kLog2e : r_t1[32 * l0_bt + r] * kLn2;     // (FUSE: the epilogue takes 1 / lift)
+    const float t1_l = pow2_rcp(r_t1[32 * l0_bt + r]) * kLog2e;     // (the epilogue takes 1 / lift)
     const _Float16 *xb0 = ximg + (size_t)(32 * l0_bt + r) * XSTR + 8 * hh;
     // layer-0 operands of one 16-deep slab: W0 fragments of the chunk (LDS copy) and this wave's rows of the x image
     struct L0Ops { f16x8 a1, a2, b1, b2; };
@@ -466,11 +446,11 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
       for (int q = 0; q < 4; ++q) {
         Epi4 es;
         const f32x4 bv = l0_bias(0, q);
-        epi_all<false, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
+        epi_all<false>(es, d, q, inv0_l, bv, t1_l);
         l0_store(es, 0, q);
       }
     }
-    H3_BARRIER();
+    lds_barrier();
     H3_STAMP(2);
 
     // One step = the 192 layer-1 MFMAs of chunk c -- 16 (slab, row tile) positions of 12, in 8 slots of 24 -- with the
@@ -530,16 +510,14 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
           }
           if (!LAST && slot >= 4 && i % 2 == 0) {
             const int q = slot - 4, k = i / 2;
-            if (k == 0) epi_stage<0, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (k == 1) epi_stage<1, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (k == 2) epi_stage<2, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (k == 3) epi_stage<3, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (k == 4) epi_stage<4, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (k == 5) epi_stage<5, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (k == 6) epi_stage<6, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (k == 7) epi_stage<7, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (k == 8) epi_stage<8, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
-            if (k == 9) epi_stage<9, true, true, H3_EPI_FUSE>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 0) epi_stage<0, true>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 2) epi_stage<2, true>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 3) epi_stage<3, true>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 4) epi_stage<4, true>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 5) epi_stage<5, true>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 6) epi_stage<6, true>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 8) epi_stage<8, true>(es, d, q, inv0_l, bv, t1_l);
+            if (k == 9) epi_stage<9, true>(es, d, q, inv0_l, bv, t1_l);
             if (k == 10) l0_store(es, c + 1, q);
           }
           __builtin_amdgcn_sched_barrier(0);
@@ -552,7 +530,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
           if (j < W0P) w0buf[((size_t)(c & 1) * W0P + j) * 64 + lane] = wst;
         }
       }
-      H3_BARRIER();
+      lds_barrier();
       H3_STAMP(5);
     };
     {
@@ -568,20 +546,6 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
     fetch_x(tid);
     fetch_bias(item + gridDim.x, tid);
     H3_STAMP(6);
-#ifdef H3_DIAG_NOTAIL
-    {
-      float keep = 0.0f;      // every accumulator register stays live: the loop's MFMAs must all execute
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < VT; ++v)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) keep += acc[u][v][i];
-      if (keep == 123.456f) p.out0[0] = keep;
-    }
-    H3_BARRIER();
-    continue;
-#endif
 
     // ---- tail: h2 -> output layer -> head -> stores, one (32-row tile, pair of output tiles) unit at a time.
     // h2 never leaves the registers: an accumulator tile's hidden units are the next product's k index, so the wave's own 64
@@ -612,7 +576,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
     auto store_unit = [&](int u) {
       // a row's means / variances are contiguous runs of `out` floats; lane = column of the pair
       const int rt = u / NPASS, pass = u % NPASS;
-      if (H3_STORE8 && NPASS == 1 && (out & 1) == 0) {
+      if (NPASS == 1 && (out & 1) == 0) {
         // even widths (every shipped task): 8-byte stores, two rows per instruction -- lanes 0 .. out - 1 carry row A's
         // (mean | var) as `out` float pairs, lanes out .. 2 out - 1 row B's (rows are 8-byte aligned: out 4 bytes a row)
         const int half = lane >= out ? 1 : 0, c = 2 * (lane - half * out);
@@ -630,6 +594,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
         }
         return;
       }
+      // two passes over the output layer, or an odd width: 4-byte lane stores
       const int n = 64 * pass + lane;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -650,12 +615,12 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
       for (int vv = 0; vv < 2; ++vv) {
         const int row = 32 * rt + 16 * vv + sig;
         const float inv1_l = r_inv1[row] * kLog2e;
-        const float t2_l = H3_EPI_FUSE ? pow2_rcp(r_t2[row]) * kLog2e : r_t2[row] * kLn2;
+        const float t2_l = pow2_rcp(r_t2[row]) * kLog2e;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias1 + 64 * wave + 16 * u + 4 * g4);
           Epi4 es;
-          epi_all<false, true, H3_EPI_FUSE>(es, acc[u][2 * rt + vv], 0, inv1_l, bv, t2_l);
+          epi_all<false>(es, acc[u][2 * rt + vv], 0, inv1_l, bv, t2_l);
           bfu[vv][u >> 1][0][2 * (u & 1)] = es.q1[0]; bfu[vv][u >> 1][0][2 * (u & 1) + 1] = es.q1[1];
           bfu[vv][u >> 1][1][2 * (u & 1)] = es.q2[0]; bfu[vv][u >> 1][1][2 * (u & 1) + 1] = es.q2[1];
         }
@@ -732,7 +697,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
         if constexpr (k < RT) stB(std::integral_constant<int, (k < RT ? k : 0)>{});
         if constexpr (k + 1 < RT) stA(std::integral_constant<int, (k + 1 < RT ? k + 1 : 0)>{});
         H3_STAMP(7);
-        if constexpr (k + 1 < RT + 2) H3_BARRIER();
+        if constexpr (k + 1 < RT + 2) lds_barrier();
         H3_STAMP(8);
       });
     } else {
@@ -763,18 +728,18 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
           }
           put_partials(o, u);
           H3_STAMP(7);
-          H3_BARRIER();       // unit u's partials are complete; unit u - 1's staging tile too
+          lds_barrier();       // unit u's partials are complete; unit u - 1's staging tile too
           H3_STAMP(8);
           if (u > 0) store_unit(u - 1);
           reduce_unit(u);
           H3_STAMP(9);
         }
       });
-      H3_BARRIER();
+      lds_barrier();
       store_unit(NUNIT - 1);
     }
     H3_STAMP(10);
-    H3_BARRIER();     // the LDS regions are rewritten by the next item's stage
+    lds_barrier();     // the LDS regions are rewritten by the next item's stage
     H3_STAMP(11);
   }  // persistent item loop
 #ifdef CMBPO_STAMPS
@@ -848,7 +813,7 @@ void cmbpo_internal_f16_pack(const cmbpo_mlp *m, int layer, void *dst, size_t ds
                      perm);
 }
 
-static int g_h3_rt = getenv("CMBPO_ENS_H3_RT") ? atoi(getenv("CMBPO_ENS_H3_RT")) : 0;   // 0: by row count; 1 / 2 / 4 forces it
+static int g_h3_rt = 0;   // 0: by row count; 1 / 2 / 4 forces it
 extern "C" int cmbpo_set_ens_f16_row_tiles(int rt) {
   CMBPO_REQUIRE(rt == 0 || rt == 1 || rt == 2 || rt == 4, "cmbpo_set_ens_f16_row_tiles: 0 (by row count), 1, 2 or 4");
   g_h3_rt = rt;
@@ -886,8 +851,7 @@ int cmbpo_internal_launch_h3(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s) {
   // member-major order in every list, so a suffix of one list is a suffix of the others; a row's arithmetic does not depend
   // on the item it travels in (tests: bitwise against the forced sizes).
   const int E = m->ensemble;
-  static const int split_tail = getenv("CMBPO_ENS_H3_SPLIT_TAIL") ? atoi(getenv("CMBPO_ENS_H3_SPLIT_TAIL")) : 1;
-  static const int split_gap = getenv("CMBPO_ENS_H3_SPLIT_GAP") ? 10 * atoi(getenv("CMBPO_ENS_H3_SPLIT_GAP")) : 40;   // launch boundary
+  constexpr int kSplitGap = 40;     // the cost of the boundary between the two launches (tenths of a microsecond)
   int RT = g_h3_rt, RT_tail = 0, full = 0, tail_start = 0;
   if (RT == 0) {
     const int first_two[3] = {220, 310, 550}, steady_two[3] = {175, 300, 540};
@@ -900,19 +864,18 @@ int cmbpo_internal_launch_h3(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s) {
       const long cost = cost_of(i, cmbpo_ceil_div(cmbpo_ceil_div(a.n_rows, 32 * rts[i]) * E, n_cu));
       if (best < 0 || cost <= best) { best = cost; RT = rts[i]; }
     }
-    if (split_tail)
-      for (int i = 1; i < 3; ++i) {
-        const int tiles_m = cmbpo_ceil_div(a.n_rows, 32 * rts[i]), n_m = tiles_m * E;
-        const int fl = n_m / n_cu * n_cu, left = n_m - fl;
-        if (fl == 0 || left == 0) continue;
-        const int e0 = fl / tiles_m, t0 = fl - e0 * tiles_m;
-        for (int j = 0; j < i; ++j) {
-          const int tiles_t = cmbpo_ceil_div(a.n_rows, 32 * rts[j]);
-          const int start = e0 * tiles_t + (rts[i] / rts[j]) * t0, n_tail = tiles_t * E - start;
-          const long cost = cost_of(i, fl / n_cu) + cost_of(j, cmbpo_ceil_div(n_tail, n_cu)) + split_gap;
-          if (cost < best) { best = cost; RT = rts[i]; RT_tail = rts[j]; full = fl; tail_start = start; }
-        }
+    for (int i = 1; i < 3; ++i) {
+      const int tiles_m = cmbpo_ceil_div(a.n_rows, 32 * rts[i]), n_m = tiles_m * E;
+      const int fl = n_m / n_cu * n_cu, left = n_m - fl;
+      if (fl == 0 || left == 0) continue;
+      const int e0 = fl / tiles_m, t0 = fl - e0 * tiles_m;
+      for (int j = 0; j < i; ++j) {
+        const int tiles_t = cmbpo_ceil_div(a.n_rows, 32 * rts[j]);
+        const int start = e0 * tiles_t + (rts[i] / rts[j]) * t0, n_tail = tiles_t * E - start;
+        const long cost = cost_of(i, fl / n_cu) + cost_of(j, cmbpo_ceil_div(n_tail, n_cu)) + kSplitGap;
+        if (cost < best) { best = cost; RT = rts[i]; RT_tail = rts[j]; full = fl; tail_start = start; }
       }
+    }
   }
   const int S0 = m->h3_s0, OTP = m->h3_otp;
   // one launch: items [item0, end) of the (member-major) item list at rt 32-row tiles per item; end < 0: all of it

@@ -26,7 +26,6 @@
 #include "mfma_tile.h"
 
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 #include <vector>
 
@@ -722,12 +721,11 @@ int launch_one(MlpKernelArgs &a, int tiles, int chunks, size_t lds, hipStream_t 
 }
 
 // matrix path of the 512-wide PROB forward: 0 fp32 MFMAs, 1 ens_split.hip (six bf16 terms), 2 ens_h3.hip (three f16 terms)
-int g_split_path = getenv("CMBPO_ENS_SPLIT") ? atoi(getenv("CMBPO_ENS_SPLIT")) : CMBPO_ENS_SPLIT_F16;
+int g_split_path = CMBPO_ENS_SPLIT_F16;
 // rows below which the 512-wide forward falls back to the bf16 kernel: none since the f16 kernel has 32- and 64-row items
-// (22 us against the bf16 kernel's 43 at 1000 rows, AntSafe shapes); the knob stays for experiments
-int g_h3_min_rows = getenv("CMBPO_ENS_H3_MIN_ROWS") ? atoi(getenv("CMBPO_ENS_H3_MIN_ROWS")) : 0;
+// (22 us against the bf16 kernel's 43 at 1000 rows, AntSafe shapes); cmbpo_set_ens_f16_min_rows sets one for experiments
+int g_h3_min_rows = 0;
 constexpr int kStaggerSleeps = 10;   // x s_sleep(127) (~8k cycles each) for the second dispatch batch
-int g_lds_pad = 0;      // diagnostic: extra dynamic LDS bytes (forces one workgroup per CU)
 
 int launch_mlp(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s, int head_override = -1) {
   const int head = head_override >= 0 ? head_override : m->head;
@@ -773,10 +771,10 @@ int launch_mlp(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s, int head_override 
   const size_t hbuf = (size_t)H * BB * 4;
   const size_t red = ((size_t)kWaves * m->o_tiles * 32 * (BB + 1) * 4 + 15) / 16 * 16;
   const size_t lds = (hbuf > red ? hbuf : red) + (size_t)m->in_pad * BB * 4 + (2 * H + m->o_tiles * 32 + 3 * m->out_dim) * 4 + BB * 4;
-  CMBPO_REQUIRE(lds + g_lds_pad <= 160 * 1024, "ens_mlp: LDS budget exceeded (%zu B)", lds + g_lds_pad);
+  CMBPO_REQUIRE(lds <= 160 * 1024, "ens_mlp: LDS budget exceeded (%zu B)", lds);
 
 #define CMBPO_LAUNCH(HID_, BT_, ACT_, HEAD_) \
-  return launch_one<HID_, BT_, ACT_, HEAD_>(a, tiles, grid_y, lds + g_lds_pad, s)
+  return launch_one<HID_, BT_, ACT_, HEAD_>(a, tiles, grid_y, lds, s)
   if (head == CMBPO_HEAD_TRAIN && m->act == CMBPO_ACT_SWISH) {
     if (H == 512) CMBPO_LAUNCH(512, 1, CMBPO_ACT_SWISH, CMBPO_HEAD_TRAIN);
     if (H == 128) CMBPO_LAUNCH(128, 1, CMBPO_ACT_SWISH, CMBPO_HEAD_TRAIN);
@@ -819,11 +817,6 @@ extern "C" int cmbpo_set_ens_f16_min_rows(int rows) {
 }
 
 extern "C" int cmbpo_get_ens_matrix_path(void) { return g_split_path; }
-
-extern "C" int cmbpo_debug_set_lds_pad(int bytes) {
-  g_lds_pad = bytes;
-  return CMBPO_OK;
-}
 
 extern "C" int cmbpo_ens_forward(cmbpo_mlp_t *m, const float *d_obs, int obs_dim,
                                  const float *d_act, int act_dim, const int32_t *d_row_idx,

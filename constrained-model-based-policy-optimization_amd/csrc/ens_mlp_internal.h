@@ -82,7 +82,8 @@ bool cmbpo_internal_policy_f16_eligible(const cmbpo_mlp *m);
 int cmbpo_internal_launch_policy_f16(cmbpo_mlp *m, const MlpKernelArgs &a, hipStream_t s);
 int cmbpo_internal_policy_f16_args(cmbpo_mlp *m, void *pf_args, int *s0_out, hipStream_t s);
 // both critics and, riding along as one more wave per tile, the actor at the same rows (critic_f16.hip)
-int cmbpo_internal_critic_big_min();
+// rows from which the critics run member after member with LDS-resident weights (critic_big_kernel; no rider there)
+constexpr int kCriticBigMin = 24576;
 bool cmbpo_internal_critic_pair_can_ride(const cmbpo_mlp *v, const cmbpo_mlp *vc, const cmbpo_mlp *policy);
 // optional passenger of the critics' launch at small batches: the vector half of the rollout step's store (obs, act, mu, log_std
 // of every row that was not finished before the store -> column `col_off / B` of the buffers), copied by each tile's workgroup for

@@ -25,19 +25,12 @@
 
 #include <math.h>
 #include <new>
-#include <stdlib.h>
 #include <string.h>
 #include <vector>
 
 namespace {
 
 constexpr int kThreads = 256;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 // ------------------------------------------------------------------------------------------------------------
 // loss: per-member sums, then d(train_loss)/d(raw output)
@@ -1050,168 +1043,19 @@ __global__ __launch_bounds__(kThreads, 2) void wgrad_kernel(const WgradArgs p) {
   }
 }
 
-// Workgroup-tiled variant for the 512-wide ensembles.  The register-direct kernel above moves (128 + 64) x 4 bytes per
+// Workgroup-tiled weight gradients of the 512-wide ensembles.  The register-direct kernel above moves (128 + 64) x 4 bytes per
 // 2 x 128 x 64 x 2 flops -- 21 flop/B, i.e. ~7 TB/s of L2 traffic at the MFMA peak, and it measured 52 TFLOP/s on dW1.
-// Here the 4 waves form a WM x WN grid of 128 x 64 wave tiles over the SAME batch rows and share the operands through
-// LDS: per 8-row block the workgroup stages one [8][128 WM] slab of A and one [8][64 WN] slab of B (global -> registers
-// one block ahead -> LDS, double buffered, one barrier per block), every wave reads its fragments back as one
-// ds_read_b128 / ds_read_b64 per row pair.  (2 x 2): 256 x 128 tile, 43 flop/B; (4 x 1): 512 x 64 for the narrow
-// operands of the first / last layer.  No cross-wave reduction: each wave owns its output tile.
-template <int WM, int WN>
-__device__ __forceinline__ void wgrad_lds_body(const WgradArgs &p, f32x4 *slab_mem, int bx, int by, int e) {
-  constexpr int TM = 128 * WM, TN = 64 * WN;
-  constexpr int A4 = 8 * TM / 4, B4 = 8 * TN / 4;          // float4 per slab
-  constexpr int A_PER = A4 / kThreads, B_PER = (B4 + kThreads - 1) / kThreads;
-  f32x4 *slab[2] = {slab_mem, slab_mem + A4 + B4};
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i = lane & 31, h = lane >> 5;
-  const int wm = wave / WN, wn = wave - wm * WN;
-  const int mt = bx / p.n_tiles, nt = bx - mt * p.n_tiles;
-  const int m0 = mt * TM, n0 = nt * TN;
-  const int start = by * p.rows_per_wg;
-  const int end = min(start + p.rows_per_wg, p.B);
-  const float *Abase = p.A + (size_t)e * p.B * p.lda + m0;
-  const float *Bbase = p.Bm + (size_t)e * p.B * p.ldb + n0;
-
-  f32x16 acc[4][2];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.0f;
-  const bool sum_b = p.bias_mode == 1 && mt == 0 && wm == 0, sum_a = p.bias_mode == 2 && nt == 0 && wn == 0;
-  f32x4 asum = {0.0f, 0.0f, 0.0f, 0.0f};
-  float2 bsum = {0.0f, 0.0f};
-
-  // two register staging sets: a slab is requested TWO blocks (~2 x 2048 MFMA cycles) before it is written to LDS --
-  // one block of lead does not cover an L2 miss (the operands stream from HBM / MALL, they are read once per XCD)
-  f32x4 ra0[A_PER], rb0[B_PER], ra1[A_PER], rb1[B_PER];
-  auto fetch = [&](int r0, f32x4 (&ra)[A_PER], f32x4 (&rb)[B_PER]) {
-#pragma unroll
-    for (int u = 0; u < A_PER; ++u) {
-      const int q = tid + u * kThreads;
-      const int row = q / (TM / 4), c4 = q - row * (TM / 4);
-      ra[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      if (r0 + row < end) ra[u] = *reinterpret_cast<const f32x4 *>(Abase + (size_t)(r0 + row) * p.lda + 4 * c4);
-    }
-#pragma unroll
-    for (int u = 0; u < B_PER; ++u) {
-      const int q = tid + u * kThreads;
-      const int row = q / (TN / 4), c4 = q - row * (TN / 4);
-      rb[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      if (q < B4 && r0 + row < end && n0 + 4 * c4 < p.ldb)
-        rb[u] = *reinterpret_cast<const f32x4 *>(Bbase + (size_t)(r0 + row) * p.ldb + 4 * c4);
-    }
-  };
-  auto stash = [&](int buf, const f32x4 (&ra)[A_PER], const f32x4 (&rb)[B_PER]) {
-#pragma unroll
-    for (int u = 0; u < A_PER; ++u) slab[buf][tid + u * kThreads] = ra[u];
-#pragma unroll
-    for (int u = 0; u < B_PER; ++u)
-      if (tid + u * kThreads < B4) slab[buf][A4 + tid + u * kThreads] = rb[u];
-  };
-  auto compute = [&](int buf) {
-    const float *As = reinterpret_cast<const float *>(slab[buf]) + wm * 128 + 4 * i;
-    const float *Bs = reinterpret_cast<const float *>(slab[buf] + A4) + wn * 64 + 2 * i;
-    f32x4 a[4];
-    float2 b[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      a[u] = *reinterpret_cast<const f32x4 *>(As + (2 * u + h) * TM);
-      b[u] = *reinterpret_cast<const float2 *>(Bs + (2 * u + h) * TN);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) {
-        acc[mi][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][mi], b[u].x, acc[mi][0], 0, 0, 0);
-        acc[mi][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][mi], b[u].y, acc[mi][1], 0, 0, 0);
-      }
-    if (sum_b) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { bsum.x += b[u].x; bsum.y += b[u].y; }
-    }
-    if (sum_a) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) asum += a[u];
-    }
-  };
-
-  if (start < end) {
-    fetch(start, ra0, rb0);
-    if (start + 8 < end) fetch(start + 8, ra1, rb1);
-    stash(0, ra0, rb0);
-    __syncthreads();
-    // even blocks live in slab[0], odd blocks in slab[1]
-#pragma unroll 1
-    for (int r0 = start; r0 < end; r0 += 16) {
-      if (r0 + 16 < end) fetch(r0 + 16, ra0, rb0);
-      compute(0);
-      if (r0 + 8 < end) stash(1, ra1, rb1);
-      __syncthreads();
-      if (r0 + 8 >= end) break;
-      if (r0 + 24 < end) fetch(r0 + 24, ra1, rb1);
-      compute(1);
-      if (r0 + 16 < end) stash(0, ra0, rb0);
-      __syncthreads();
-    }
-  }
-
-  const int m0w = m0 + wm * 128, n0w = n0 + wn * 64;
-  if (sum_b) {
-    const float x = bsum.x + __shfl_xor(bsum.x, 32, 64), y = bsum.y + __shfl_xor(bsum.y, 32, 64);
-    float *dst = p.bias_out + (size_t)by * p.bias_part + (size_t)e * p.bias_member;
-    if (h == 0) {
-      if (n0w + 2 * i < p.bias_n) dst[n0w + 2 * i] = x;
-      if (n0w + 2 * i + 1 < p.bias_n) dst[n0w + 2 * i + 1] = y;
-    }
-  }
-  if (sum_a) {
-    float *dst = p.bias_out + (size_t)by * p.bias_part + (size_t)e * p.bias_member;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float x = asum[c] + __shfl_xor(asum[c], 32, 64);
-      if (h == 0 && m0w + 4 * i + c < p.bias_n) dst[m0w + 4 * i + c] = x;
-    }
-  }
-  float *out = p.out + (size_t)by * p.out_part + (size_t)e * p.out_member;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int irow = (r & 3) + 8 * (r >> 2) + 4 * h;
-    if (!p.transposed) {
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) {
-        const int m = m0w + 4 * irow + mi;
-        const int n = n0w + 2 * i;
-        float *dst = out + (size_t)m * p.ldc + n;
-        if (n + 1 < p.n_out) {
-          if ((p.ldc & 1) == 0) *reinterpret_cast<float2 *>(dst) = float2{acc[mi][0][r], acc[mi][1][r]};
-          else { dst[0] = acc[mi][0][r]; dst[1] = acc[mi][1][r]; }
-        } else if (n < p.n_out) {
-          dst[0] = acc[mi][0][r];
-        }
-      }
-    } else {
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        const int n = n0w + 2 * i + ni;
-        if (n < p.n_out)
-          *reinterpret_cast<f32x4 *>(out + (size_t)n * p.ldc + m0w + 4 * irow) =
-              f32x4{acc[0][ni][r], acc[1][ni][r], acc[2][ni][r], acc[3][ni][r]};
-      }
-    }
-  }
-}
-
-// The same tiling on the f16 pipe: each float32 product as three v_mfma_f32_32x32x16_f16 on two-piece operands (f16_split.h).
-// K of an MFMA = 16 batch rows, so a block is 16 rows: global -> registers two blocks ahead -> split (one power-of-two lift
-// per (member, operand), from the largest magnitude the producing kernel left in `amax / bmax`: the batch is the K dimension,
-// so a lift may not vary from row to row) -> LDS as two-piece [row][feature] images -> the hardware's transposed read
-// (ds_read_b64_tr_b16: four batch rows of one feature per read, cdna_hip_programming.md T10) delivers MFMA fragments with
-// the batch on the k index.  24 MFMAs of 32 cycles per block and wave against the 64 of 64 cycles the fp32 form needs for
-// the same 16 rows.  Row strides of the images are 16 dwords past a multiple of 64 (8 for the 512-wide A slab, which has to
-// fit two workgroups per CU): the four rows of a transposed read fall on different banks.
+// Here the 4 waves form a WM x WN grid of 128 x 64 wave tiles over the SAME batch rows and share the operands through LDS
+// (double buffered, one barrier per block): (2 x 2) a 256 x 128 tile, (4 x 1) 512 x 64 for the narrow operands of the first /
+// last layer.  No cross-wave reduction: each wave owns its output tile.  Each float32 product is three
+// v_mfma_f32_32x32x16_f16 on two-piece operands (f16_split.h).  K of an MFMA = 16 batch rows, so a block is 16 rows: global
+// -> registers two blocks ahead -> split (one power-of-two lift per (member, operand), from the largest magnitude the
+// producing kernel left in `amax / bmax`: the batch is the K dimension, so a lift may not vary from row to row) -> LDS as
+// two-piece [row][feature] images -> the hardware's transposed read (ds_read_b64_tr_b16: four batch rows of one feature per
+// read, cdna_hip_programming.md T10) delivers MFMA fragments with the batch on the k index.  24 MFMAs of 32 cycles per block
+// and wave against the 64 of 64 cycles an fp32 form needs for the same 16 rows.  Row strides of the images are 16 dwords past
+// a multiple of 64 (8 for the 512-wide A slab, which has to fit two workgroups per CU): the four rows of a transposed read
+// fall on different banks.
 template <int WM, int WN>
 __device__ __forceinline__ void wgrad_f16_body(const WgradArgs &p, char *smem, int bx, int by, int e) {
   constexpr int TM = 128 * WM, TN = 64 * WN;
@@ -1437,9 +1281,8 @@ struct WgradAllArgs {
 
 constexpr int kWgradF16Lds = 2 * (2 * 16 * (512 + 16) * 2 + 2 * 16 * (64 + 32) * 2);   // the (4 x 1) tiles' two buffers: 79 872 B
 
-template <bool F16>
 __global__ __launch_bounds__(kThreads, 2) void wgrad_all_kernel(const WgradAllArgs p) {
-  extern __shared__ f32x4 slab_mem[];     // fp32: 2 x (8 x 512 / 4 + 8 x 64 / 4) float4; f16: kWgradF16Lds bytes
+  extern __shared__ f32x4 slab_mem[];     // kWgradF16Lds bytes
   const int blk = blockIdx.x;
   const int seg = blk < p.first[1] ? 0 : (blk < p.first[2] ? 1 : 2);
   int q = blk - p.first[seg];
@@ -1453,15 +1296,13 @@ __global__ __launch_bounds__(kThreads, 2) void wgrad_all_kernel(const WgradAllAr
     const int bx = slot % T;
     const int c = (slot / T) * 8 + xcd;
     if (c >= p.n_chunks0) return;
-    if constexpr (F16) wgrad_f16_body<2, 2>(p.g[0], reinterpret_cast<char *>(slab_mem), bx, c % p.ks[0], c / p.ks[0]);
-    else wgrad_lds_body<2, 2>(p.g[0], slab_mem, bx, c % p.ks[0], c / p.ks[0]);
+    wgrad_f16_body<2, 2>(p.g[0], reinterpret_cast<char *>(slab_mem), bx, c % p.ks[0], c / p.ks[0]);
     return;
   }
   const int bx = q % p.tiles[seg];
   q /= p.tiles[seg];
   const int by = q % p.ks[seg], e = q / p.ks[seg];
-  if constexpr (F16) wgrad_f16_body<4, 1>(p.g[seg], reinterpret_cast<char *>(slab_mem), bx, by, e);
-  else wgrad_lds_body<4, 1>(p.g[seg], slab_mem, bx, by, e);
+  wgrad_f16_body<4, 1>(p.g[seg], reinterpret_cast<char *>(slab_mem), bx, by, e);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1941,16 +1782,6 @@ struct cmbpo_trainer {
 
 namespace {
 
-// 0: the training GEMMs as fp32 MFMAs (rounds 1-2); 1: three f16 MFMAs per product on split operands (512-wide ensembles)
-int g_train_f16 = -1;
-bool train_f16() {
-  if (g_train_f16 < 0) {
-    const char *e = getenv("CMBPO_TRAIN_F16");
-    g_train_f16 = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_train_f16 != 0;
-}
-
 int wgrad_rows_per_wg(int batch, int ks) {
   int rows = cmbpo_ceil_div(batch, ks);
   return (rows + 15) / 16 * 16;   // whole 16-row blocks (the f16 form's K per MFMA; the fp32 form needs a multiple of 8)
@@ -1992,12 +1823,8 @@ int launch_wgrad_all(cmbpo_trainer *t, int batch, hipStream_t s) {
     }
   }
   all.first[3] = blocks;
-  if (train_f16()) {
-    if (int rc = cmbpo_grant_lds(wgrad_all_kernel<true>, kWgradF16Lds)) return rc;
-    hipLaunchKernelGGL(wgrad_all_kernel<true>, dim3(blocks), dim3(kThreads), kWgradF16Lds, s, all);
-  } else {
-    hipLaunchKernelGGL(wgrad_all_kernel<false>, dim3(blocks), dim3(kThreads), 2 * (8 * 512 / 4 + 8 * 64 / 4) * sizeof(f32x4), s, all);
-  }
+  if (int rc = cmbpo_grant_lds(wgrad_all_kernel, kWgradF16Lds)) return rc;
+  hipLaunchKernelGGL(wgrad_all_kernel, dim3(blocks), dim3(kThreads), kWgradF16Lds, s, all);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -2037,12 +1864,6 @@ int launch_bwd(const BwdArgs &a, int tiles, int E, size_t lds, hipStream_t s) {
   hipLaunchKernelGGL(bwd_chain_kernel<HID>, dim3(tiles, E), dim3(kThreads), lds, s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
-}
-
-// 0 / 1: the backward chain as fp32 MFMAs / on the f16 path where the shape allows (CMBPO_TRAIN_BWD_F16=0 turns it off)
-bool bwd_f16() {
-  static const bool on = !(getenv("CMBPO_TRAIN_BWD_F16") && getenv("CMBPO_TRAIN_BWD_F16")[0] == '0');
-  return on && train_f16();
 }
 
 // the images of the f16 training kernels from the current packs, in one launch (train_pack_all_kernel): the members' lifts come
@@ -2227,14 +2048,9 @@ int launch_fused(cmbpo_trainer *t, const float *d_inputs, const float *d_targets
   return CMBPO_OK;
 }
 
-bool fwd_f16() {
-  static const bool on = !(getenv("CMBPO_TRAIN_FWD_F16") && getenv("CMBPO_TRAIN_FWD_F16")[0] == '0');
-  return on && train_f16();
-}
-
 int run_forward(cmbpo_trainer *t, const float *d_inputs, const int32_t *d_idx, int idx_stride, int rows, bool exports,
                 hipStream_t s, const float *d_targets = nullptr) {
-  if (t->b16 && t->b16_fwd && fwd_f16()) return launch_fwd_h(t, d_inputs, d_idx, idx_stride, rows, exports, s, d_targets);
+  if (t->b16 && t->b16_fwd) return launch_fwd_h(t, d_inputs, d_idx, idx_stride, rows, exports, s, d_targets);
   MlpKernelArgs a{};
   a.obs = d_inputs; a.obs_dim = t->I; a.act = nullptr; a.act_dim = 0;
   a.row_idx = d_idx; a.row_idx_stride = idx_stride;
@@ -2293,18 +2109,12 @@ extern "C" int cmbpo_trainer_create(cmbpo_trainer_t **out, cmbpo_mlp_t *m, int m
     int ks = cmbpo_ceil_div(512, wgs);
     if (H == 512) {
       // 512-wide: the three GEMMs are ONE launch (wgrad_all_kernel) -- together they should fill one round of two
-      // workgroups per CU, not one round each.  Measured on the f16 kernels (tools/sweep_wgrad_ks.sh, E = 7: 6 for the
+      // workgroups per CU, not one round each.  Measured on the f16 kernels (profiles/r03/wgrad_ks_sweep.log, E = 7: 6 for the
       // square layer and 8 for the narrow ones against round 2's 9 / 16: 284 -> 243 us per step at batch 2048, 193 -> 180 at
       // 512, 953 -> 919 at 8192): fewer, longer workgroups hide the operand loads better and leave Adam fewer partials.
       const int narrow = (cmbpo_ceil_div(t->IP, 64) + cmbpo_ceil_div(t->OPk, 64)) * E * 8;
       const int square = (H / 256) * (H / 128) * E;
       ks = (l == 1) ? (int)(0.85f * (float)(512 - narrow) / (float)square) : 8;
-    }
-    if (const char *env = getenv("CMBPO_WGRAD_KS")) {   // tuning aid: grid K split of the square layer
-      if (l == 1 && atoi(env) > 0) ks = atoi(env);
-    }
-    if (const char *env = getenv("CMBPO_WGRAD_KS_NARROW")) {   // ... and of the two narrow layers
-      if (l != 1 && atoi(env) > 0) ks = atoi(env);
     }
     const int max_ks = max_batch / 32 < 1 ? 1 : max_batch / 32;
     if (ks > max_ks) ks = max_ks;
@@ -2539,7 +2349,7 @@ extern "C" int cmbpo_trainer_step(cmbpo_trainer_t *t, const float *d_inputs, int
   }
   const size_t lds = ((size_t)H / 4 * 32 + (size_t)t->OPk / 4 * 32) * sizeof(f32x4);
   const int tiles = cmbpo_ceil_div(batch, 32);
-  if (t->b16 && bwd_f16()) rc = launch_bwd_h(t, b, batch, s);
+  if (t->b16) rc = launch_bwd_h(t, b, batch, s);
   else rc = (H == 512) ? launch_bwd<512>(b, tiles, E, lds, s) : (H == 256 ? launch_bwd<256>(b, tiles, E, lds, s) : launch_bwd<128>(b, tiles, E, lds, s));
   if (rc != CMBPO_OK) return rc;
 

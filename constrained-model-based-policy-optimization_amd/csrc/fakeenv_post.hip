@@ -32,33 +32,12 @@ struct PostArgs {
   float *cost, *dkl_path, *ep_var_mean, *ep_var;
 };
 
-// numpy's float32 pairwise sum for n < 128 (the contiguous-axis np.mean/np.sum path):
-// 8 strided partial sums, tree-combined, then the tail sequentially.
-__device__ float np_sum_f32(const float *a, int n) {
-  if (n < 8) {
-    float s = 0.0f;
-    for (int i = 0; i < n; ++i) s = __fadd_rn(s, a[i]);
-    return s;
-  }
-  float r[8];
-  for (int k = 0; k < 8; ++k) r[k] = a[k];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8)
-    for (int k = 0; k < 8; ++k) r[k] = __fadd_rn(r[k], a[i + k]);
-  float res = __fadd_rn(__fadd_rn(__fadd_rn(r[0], r[1]), __fadd_rn(r[2], r[3])),
-                        __fadd_rn(__fadd_rn(r[4], r[5]), __fadd_rn(r[6], r[7])));
-  for (; i < n; ++i) res = __fadd_rn(res, a[i]);
-  return res;
-}
-
 // np.clip(x, lo, hi): comparisons are false for a NaN, which therefore passes through (fminf / fmaxf would drop it)
 __device__ __forceinline__ float clip_np(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // EC: the ensemble size at compile time (0: read it at run time) -- with a run-time size the member loops are unrolled to
 // kEMax and masked: 56 pair terms computed and selected for the 42 that exist, a third more instructions
-#ifndef POST_WAVES
 #define POST_WAVES 5      // waves per SIMD the register allocation aims at (swept 4 / 5 / 6 / 8: 57.7 / 51.1 / 51.3 / 77.4 us at 100 k rows)
-#endif
 template <int EC>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgs p) {
   extern __shared__ float sm[];
@@ -219,13 +198,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
   }
   __syncthreads();
 
-#ifndef POST_TAIL_PAR
-#define POST_TAIL_PAR 1      // diagnostic: 0 = one thread per row walks the row's sums alone (round 2's tail)
-#endif
-#if POST_TAIL_PAR
-  // Eight lanes per row: numpy's pairwise sum IS eight strided partial sums -- lane k carries r[k] -- combined in a fixed tree
-  // (np_sum_f32 above, operation for operation), so the row means keep their bits while the dependent chain of D additions
-  // that one thread per row walked (twice, with 248 threads of the workgroup waiting) becomes D / 8 + 3.
+  // Eight lanes per row: numpy's float32 pairwise sum for n < 128 (the contiguous-axis np.mean / np.sum path) IS eight strided
+  // partial sums -- lane k carries r[k] -- combined in a fixed tree, then the tail added in order; done here operation for
+  // operation, so the row means reproduce numpy's bit for bit while the dependent chain of D additions that one thread per row
+  // walked (twice, with 248 threads of the workgroup waiting) becomes D / 8 + 3.
   if (tid < 8 * kRows) {
     const int rw = tid >> 3, k = tid & 7;
     const int r = s_row[rw];
@@ -254,16 +230,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
     if (r < 0 || k != 0) return;
     p.dkl_path[r] = sd / (float)D;      // fake_env.py:113
     p.ep_var_mean[r] = sv / (float)D;   // model_sampler.py:322
-#else
-  if (tid < kRows) {
-    const int r = s_row[tid];
-    if (r < 0) return;
-    const float *nx = s_next + tid * D;
-    p.dkl_path[r] = np_sum_f32(s_dkl + tid * D, D) / (float)D;      // fake_env.py:113
-    p.ep_var_mean[r] = np_sum_f32(s_var + tid * D, D) / (float)D;   // model_sampler.py:322
-    bool fin = true;
-    for (int d = 0; d < D; ++d) fin = fin && isfinite(nx[d]);
-#endif
     const int me = p.elite[r];
     p.rew[r] = p.mean[me * mstride + (size_t)r * p.out_dim + D];    // fake_env.py:148-151
     uint8_t done = 0;

@@ -48,12 +48,6 @@ __global__ void gae_segments_kernel(const SegArgs a) {
   }
 }
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 // st: [0] n [1] adv_mean [2] adv_std [3] cadv_mean | raw [8] sum adv [9] sum cadv [10] sum (adv-mean)^2
 __global__ __launch_bounds__(256) void norm_moments(int n, const float *adv, const float *cadv, int pass, double *st) {
   __shared__ double sm[8];
@@ -63,7 +57,7 @@ __global__ __launch_bounds__(256) void norm_moments(int n, const float *adv, con
     if (pass == 0) { s0 += adv[i]; s1 += cadv[i]; }
     else { const float d = __fsub_rn(adv[i], mean); s0 += (double)__fmul_rn(d, d); }
   }
-  s0 = wsum(s0); s1 = wsum(s1);
+  s0 = wave_sum(s0); s1 = wave_sum(s1);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (lane == 0) { sm[w] = s0; sm[4 + w] = s1; }
   __syncthreads();

@@ -78,20 +78,12 @@ __device__ __forceinline__ void mfma_layer(const f32x4 *__restrict__ wp,
   int g = g0;
 #pragma unroll 1
   for (; g + 1 < g1; g += 2) {
-#ifdef CMBPO_DIAG_NOLOAD   // diagnostic: same MFMA stream, operands never refreshed
-    if (g == g0) request(g + 1, a1, b1);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_block<NT, BT>(a0, b0, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_block<NT, BT>(a1, b1, acc);
-#else
     request(g + 1, a1, b1);
     __builtin_amdgcn_sched_barrier(0);
     mfma_block<NT, BT>(a0, b0, acc);
     request((g + 2 < g1) ? g + 2 : g + 1, a0, b0);
     __builtin_amdgcn_sched_barrier(0);
     mfma_block<NT, BT>(a1, b1, acc);
-#endif
   }
   if (g < g1) mfma_block<NT, BT>(a0, b0, acc);
 }

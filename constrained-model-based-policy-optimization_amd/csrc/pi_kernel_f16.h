@@ -16,9 +16,6 @@
 #pragma once
 #include <utility>
 
-#ifndef PI_DEFER_DMA
-#define PI_DEFER_DMA 1      // 0: round 3's first form (the barrier that ends a tile waits for the next tile's saved activations)
-#endif
 constexpr float T_TANH = 16384.0f;      // |tanh| <= 1
 constexpr float T_TANH_INV = 1.0f / 16384.0f;
 constexpr int RSH = 2 * RS;             // row stride of a two-piece image, in halves
@@ -30,17 +27,10 @@ constexpr int RW = 4;                   // slabs in the matrix ring
 constexpr int ACT_TILE4 = 2 * BB * RS / 4;                 // float4s per tile
 constexpr int ACT_PIECES = (ACT_TILE4 * 16 + 1023) / 1024; // 1-KiB wave-instructions per tile (the last one partly past the block)
 
-// A barrier that orders the workgroup's LDS traffic only.  __syncthreads() is a workgroup-scope fence + s_barrier: hipcc waits
-// vmcnt(0) in front of it, i.e. for every global load still in flight -- the per-sample batch columns requested at the top
-// of a tile for its element phase, the next tile's observations, the matrix ring: each became an exposed L2 / HBM round
-// trip at the next barrier (the first barrier of a tile alone waited ~3 k cycles).  Here only the LDS counter is drained;
-// the compiler still tracks the loads and waits for each one where its value is used.  NOT for a barrier that publishes
-// LDS-DMA data (counted in vmcnt): the one that ends a tile stays a __syncthreads().
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ float pow2_inv(float t) {   // exact inverse of a power of two in [2^-126, 2^126]
-  return __uint_as_float(0x7F000000u - __float_as_uint(t));
-}
+// Barriers that order LDS traffic only are lds_barrier()s (common.h): behind a __syncthreads() the per-sample batch columns
+// requested at the top of a tile for its element phase, the next tile's observations and the matrix ring each became an
+// exposed L2 / HBM round trip (the first barrier of a tile alone waited ~3 k cycles).  A barrier that publishes LDS-DMA data
+// (counted in vmcnt) stays a __syncthreads().
 
 template <class F, int... I>
 __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) {
@@ -214,15 +204,6 @@ __device__ __forceinline__ void gemm_r(f32x16 &acc, Ring &R, const u32x4 *(&imgs
 // ~12 permutes that packed them.  EXEC must be all ones (the gather crosses lanes): every call site is workgroup-uniform.
 typedef __fp16 h16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 __device__ __forceinline__ void frag_T(const _Float16 *img, int ks, int c0, f16x8 &p1, f16x8 &p2, int lane) {
-#ifdef PI_FRAG_GATHER      // diagnostic: round 2's two-byte gathers
-  const _Float16 *q = img + (8 * (lane >> 5) + ks) * RSH + c0 + (lane & 31);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    p1[e] = q[e * RSH];
-    p2[e] = q[e * RSH + P2H];
-  }
-  return;
-#endif
   typedef __attribute__((address_space(3))) h16x4 *lds_h4;
   const int t = lane & 15, g = lane >> 4;
   const _Float16 *a = img + (8 * (g >> 1) + ks + (t >> 2)) * RSH + c0 + 16 * (g & 1) + 4 * (t & 3);
@@ -417,13 +398,12 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
   }
   // with the saved activations the only batch column a product reads is log_std_old: fetched one tile ahead like x, so that
   // the barrier that waits for the activations (vmcnt(0)) finds no younger load of this tile in front of it
-  constexpr bool LSO_PRE = ACT_DMA && PI_DEFER_DMA;
   float lso_pre = 0.0f;
   auto fetch_lso = [&](int t, int tid) {
     const int er0 = t * BB + (tid & 31), a0 = tid >> 5;
     lso_pre = (er0 < p.n && a0 < d.A) ? p.ls_old[(size_t)er0 * d.A + a0] : 0.0f;
   };
-  if constexpr (LSO_PRE) {
+  if constexpr (ACT_DMA) {
     if ((int)blockIdx.x < n_tiles) fetch_lso(blockIdx.x, tid0);
   }
 #ifdef CMBPO_STAMPS
@@ -477,7 +457,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
           e_cadv = p.cadv[er0];
         }
         if (a0 < d.A) {
-          if constexpr (MODE != MODE_GRAD && !LSO_PRE) lso0 = p.ls_old[(size_t)er0 * d.A + a0];
+          if constexpr (MODE != MODE_GRAD && !ACT_DMA) lso0 = p.ls_old[(size_t)er0 * d.A + a0];
           if constexpr (MODE != MODE_FVP) e_act0 = p.act[(size_t)er0 * d.A + a0];
           if constexpr (MODE == MODE_EVAL) e_mu0 = p.mu_old[(size_t)er0 * d.A + a0];
         }
@@ -487,24 +467,18 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
     float t_x = 1.0f, it_x = 1.0f;
     if constexpr (!FWD) {
       // ---- h1, h2 as cmbpo_pi_loss_grad left them (same parameters, same batch): the LDS block itself, so the products
-      // see identical bits; it was requested behind the previous tile's dW2 (before the loop for the first tile) and the
-      // barrier that ended that tile waited for it
-      if constexpr (PI_DEFER_DMA) {
-        // ... and THIS barrier publishes the block: its LDS-DMA (counted in vmcnt) was requested behind the previous tile's
-        // dW2 and has had the rest of that tile and this tile's staging to arrive (it used to be waited for by the barrier
-        // that ends a tile, a few hundred cycles after the request: ~14 % of a tile at that barrier)
-        lso0 = lso_pre;
-        __syncthreads();
-        asm volatile("" ::"v"(warm));   // the previous tile's warm-up load must be issued, its value is not used
-      } else {
-        lds_barrier();
-      }
+      // see identical bits.  Its LDS-DMA (counted in vmcnt) was requested behind the previous tile's dW2 (before the loop for
+      // the first tile) and has had the rest of that tile and this tile's staging to arrive: THIS barrier publishes it (the
+      // barrier that ends a tile, a few hundred cycles after the request, waited ~14 % of a tile for it)
+      lso0 = lso_pre;
+      __syncthreads();
+      asm volatile("" ::"v"(warm));   // the previous tile's warm-up load must be issued, its value is not used
       t_x = pow2_lift(__uint_as_float(mx[0]));
-      it_x = pow2_inv(t_x);
+      it_x = pow2_rcp(t_x);
     } else {
       lds_barrier();
       t_x = pow2_lift(__uint_as_float(mx[0]));
-      it_x = pow2_inv(t_x);
+      it_x = pow2_rcp(t_x);
       // ---- forward ----------------------------------------------------------------------------------
       acc = load_bias(p.w.b0, wave * 32, lane);     // (the bias in lifted units: it is there when the MFMAs are)
 #pragma unroll
@@ -542,7 +516,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
     PI_STAMP(0);
     if constexpr (MODE == MODE_FVP) {
       // ---- JVP chain: dh1 = (1-h1^2)(x dW0 + db0) ; dh2 = (1-h2^2)(dh1 W1 + h1 dW1 + db1) -----------
-      const float t1 = pow2_lift(__builtin_fmaf(__uint_as_float(mx[0]), bnd_x, bnd_0)), it1 = pow2_inv(t1);
+      const float t1 = pow2_lift(__builtin_fmaf(__uint_as_float(mx[0]), bnd_x, bnd_0)), it1 = pow2_rcp(t1);
       acc = load_bias(p.v.b0, wave * 32, lane);
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] *= p.v.lift[L_F0] * t_x;
@@ -588,7 +562,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
       lds_barrier();   // dh2 complete; every wave is done reading dh1 (u1R becomes the reduction image)
       PI_STAMP(6);
       {
-        const float t_d = pow2_lift(__uint_as_float(mx[2])), it_d = pow2_inv(t_d);
+        const float t_d = pow2_lift(__uint_as_float(mx[2])), it_d = pow2_rcp(t_d);
         const float mv = (p.v.lift[8 + L_F2] * T_TANH_INV) * (p.w.lift[L_F2] * t_d), un = p.w.lift[8 + L_F2] * it_d;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] *= mv;
@@ -702,8 +676,8 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
 
     // ---- backward: delta2 = (W2 cot) (1-h2^2) ; delta1 = (W1 delta2) (1-h1^2) --------------------------
     const float cm = __uint_as_float(mx[1]);
-    const float t_c = pow2_lift(cm), it_c = pow2_inv(t_c);
-    const float t2 = pow2_lift(cm * bnd_c), it2 = pow2_inv(t2);
+    const float t_c = pow2_lift(cm), it_c = pow2_rcp(t_c);
+    const float t2 = pow2_lift(cm * bnd_c), it2 = pow2_rcp(t2);
     zero(acc);
     gemm_r<ST, P_WB2, 2, false>(acc, R, imgs, BSplit{wR + j * 36 + 8 * h, t_c}, lane);
     {
@@ -730,7 +704,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
     PI_STAMP(10);
     // ---- weight gradients: K = the tile's samples ---------------------------------------------------
     if (tile + (int)gridDim.x < n_tiles) fetch_x(tile + gridDim.x, tid);
-    if constexpr (LSO_PRE) {
+    if constexpr (ACT_DMA) {
       if (tile + (int)gridDim.x < n_tiles) fetch_lso(tile + gridDim.x, tid);
     }
     if constexpr (MODE == MODE_FVP && CACHED) {
@@ -753,15 +727,15 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
       if (tile + (int)gridDim.x < n_tiles) fetch_act(tile + gridDim.x, lane);
     }
     {
-      const float t_d1 = pow2_lift(__uint_as_float(mx[3])), it_d1 = pow2_inv(t_d1);
+      const float t_d1 = pow2_lift(__uint_as_float(mx[3])), it_d1 = pow2_rcp(t_d1);
       float unused = 0.0f;
       wgrad_s<true>(gW0[0], xR, XS, 0, t_x, d1R, RS, wave * 32, t_d1, it_x * it_d1, it_d1, gbias0, lane);
       if constexpr (N_IT == 2) wgrad_s<false>(gW0[N_IT - 1], xR, XS, 32, t_x, d1R, RS, wave * 32, t_d1, it_x * it_d1, 0.0f, unused, lane);
     }
-    if constexpr (!(ACT_DMA && PI_DEFER_DMA)) asm volatile("" ::"v"(warm));   // the warm-up load must be issued, its value is not used
+    if constexpr (!ACT_DMA) asm volatile("" ::"v"(warm));   // (no warm-up load here; the empty asm keeps the measured schedule)
     ring_fill<ST>(R, imgs, lane);   // the next tile's first slabs: they land behind its staging
-    if constexpr (ACT_DMA && PI_DEFER_DMA) lds_barrier();   // x / delta1 have no reader left; the activations are waited for later
-    else __syncthreads();           // (waits for the LDS-DMA of the next tile's saved activations as well)
+    if constexpr (ACT_DMA) lds_barrier();   // x / delta1 have no reader left; the activations are waited for later
+    else __syncthreads();
     PI_STAMP(13);
   }
 #ifdef CMBPO_STAMPS
@@ -806,11 +780,11 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
   if constexpr (MODE != MODE_FVP) {
     // tid < 32 hold the per-sample sums; s_kl is spread over every thread
     __shared__ double sd[4];
-    const double kl = wave_sum_d(s_kl);
+    const double kl = wave_sum(s_kl);
     if (lane == 0) sd[wave] = kl;
     __syncthreads();
     if (wave == 0) {
-      const double n = wave_sum_d(s_n), ra = wave_sum_d(s_ra), rc = wave_sum_d(s_rc), c = wave_sum_d(s_cost);
+      const double n = wave_sum(s_n), ra = wave_sum(s_ra), rc = wave_sum(s_rc), c = wave_sum(s_cost);
       if (lane == 0) {
         atomicAdd(&p.sums[0], n);
         atomicAdd(&p.sums[1], ra);

@@ -577,11 +577,11 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
   if constexpr (MODE != MODE_FVP) {
     // tid < 32 hold the per-sample sums; s_kl is spread over every thread
     __shared__ double sd[NW];
-    const double kl = wave_sum_d(s_kl);
+    const double kl = wave_sum(s_kl);
     if (lane == 0) sd[wave] = kl;
     __syncthreads();
     if (wave == 0) {
-      const double n = wave_sum_d(s_n), ra = wave_sum_d(s_ra), rc = wave_sum_d(s_rc), c = wave_sum_d(s_cost);
+      const double n = wave_sum(s_n), ra = wave_sum(s_ra), rc = wave_sum(s_rc), c = wave_sum(s_cost);
       if (lane == 0) {
         atomicAdd(&p.sums[0], n);
         atomicAdd(&p.sums[1], ra);
@@ -786,14 +786,7 @@ PiPack pack_ptrs(const cmbpo_pi *h, const float *base) {
 }
 
 // 0: every product as fp32 MFMAs (round 1); 1: the 128 x 128 products as three f16 MFMAs on split operands
-int g_pi_path = -1;
-int pi_path() {
-  if (g_pi_path < 0) {
-    const char *e = getenv("CMBPO_PI_F16");
-    g_pi_path = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_pi_path;
-}
+int g_pi_path = 1;
 
 int do_pack(const cmbpo_pi *h, float *dst, const float *flat, hipStream_t s) {
   const PiDims &d = h->d;
@@ -870,7 +863,7 @@ int launch_pi_k(cmbpo_pi *h, PiArgs &a, hipStream_t s, KERN kern, bool f16, bool
 template <int MODE, int N_IT>
 int launch_pi_n(cmbpo_pi *h, PiArgs &a, hipStream_t s) {
   if (h->d.H == 256) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 256>, false, MODE != MODE_EVAL);
-  if (pi_path() == 0) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 128>, false, MODE != MODE_EVAL);
+  if (g_pi_path == 0) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 128>, false, MODE != MODE_EVAL);
   if (MODE == MODE_FVP && a.cache_r != nullptr)
     return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, true>, true, MODE != MODE_EVAL);
   return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, false>, true, MODE != MODE_EVAL);
@@ -906,7 +899,7 @@ int fill_args(cmbpo_pi *h, const cmbpo_pi_batch_t *b, PiArgs &a, const char *who
 // the saved activations a Fisher-vector product on batch b may read, or NULL
 const f32x4 *act_for(const cmbpo_pi *h, const cmbpo_pi_batch_t *b) {
   if (!h->act_keep || !h->act_valid || h->act == nullptr || b->obs != h->act_obs || b->n != h->act_n ||
-      h->act_path != (h->d.H == HID ? pi_path() : 0))      // (the two matrix paths keep different images)
+      h->act_path != (h->d.H == HID ? g_pi_path : 0))      // (the two matrix paths keep different images)
     return nullptr;
   return reinterpret_cast<const f32x4 *>(h->act);
 }
@@ -990,7 +983,7 @@ extern "C" void cmbpo_pi_destroy(cmbpo_pi_t *h) {
 extern "C" void cmbpo_debug_set_pi_stamps(unsigned long long *p) { g_pi_stamps = p; }
 #endif
 extern "C" void cmbpo_set_pi_matrix_path(int path) { g_pi_path = path != 0 ? 1 : 0; }
-extern "C" int cmbpo_get_pi_matrix_path(void) { return pi_path(); }
+extern "C" int cmbpo_get_pi_matrix_path(void) { return g_pi_path; }
 
 extern "C" int cmbpo_pi_num_params(const cmbpo_pi_t *h) { return h ? h->d.P : -1; }
 
@@ -1025,7 +1018,7 @@ extern "C" int cmbpo_pi_loss_grad(cmbpo_pi_t *h, const cmbpo_pi_batch_t *b, int 
   const bool save = h->act_keep && act_for(h, b) == nullptr && act_reserve(h, b->n);
   if (save) a.cache_w = reinterpret_cast<f32x4 *>(h->act);
   if (int rc = launch_pi<MODE_GRAD>(h, a, s)) return rc;
-  if (save) { h->act_valid = true; h->act_obs = b->obs; h->act_n = b->n; h->act_path = h->d.H == HID ? pi_path() : 0; }
+  if (save) { h->act_valid = true; h->act_obs = b->obs; h->act_n = b->n; h->act_path = h->d.H == HID ? g_pi_path : 0; }
   return CMBPO_OK;
 }
 

@@ -12,7 +12,6 @@
 #include <type_traits>
 
 #include <math.h>
-#include <stdlib.h>
 
 namespace {
 
@@ -44,13 +43,6 @@ __device__ __forceinline__ int block_excl_scan(int v, int *sm, int *total) {
   __syncthreads();
   *total = sm[16];
   return inc - v + (w > 0 ? sm[w - 1] : 0);
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
 }
 
 __device__ __forceinline__ double wave_max(double v) {
@@ -421,15 +413,10 @@ __global__ __launch_bounds__(256) void store_stats_kernel(const cmbpo_rollout_t 
 // launch boundary (decide 2 x 5, finish 5, store 9 + 6 us of a 140 us step at 1000 branches).  Up to kBookMax alive rows
 // one 1024-thread workgroup walks them in a fixed order: same decisions, same per-branch arithmetic, the step's sums added
 // in a fixed tree.  (Single-rank path: the cross-shard budget exchange keeps the separate kernels.)
-// Round 3 (tools/sweep_book_max.sh): with the large-batch step's launches pipelined and its actor ahead of the host's wait, the
-// separate kernels win from ~1000 rows on (4 % at 1250 and 2500 rows, 8 % at 4000; the one-workgroup path wins by 5 - 10 % at
-// 400 - 700): the threshold came down from 4096.  (CMBPO_BOOK_MAX: 0 .. 65536; the kernels walk any count)
-constexpr int kBookMaxDefault = 1024;
-static const int kBookMax = [] {
-  const char *e = getenv("CMBPO_BOOK_MAX");
-  const int v = e ? atoi(e) : kBookMaxDefault;
-  return v < 0 ? 0 : (v > 65536 ? 65536 : v);
-}();
+// Round 3: with the large-batch step's launches pipelined and its actor ahead of the host's wait, the separate kernels win
+// from ~1000 rows on (4 % at 1250 and 2500 rows, 8 % at 4000; the one-workgroup path wins by 5 - 10 % at 400 - 700): the
+// threshold came down from 4096.
+constexpr int kBookMax = 1024;
 
 // spec (cmbpo_rollout_run's look-ahead): the step was enqueued before the host saw the previous step's counters -- it is void
 // when that step raised the halt word (book_post_kernel)
@@ -919,13 +906,8 @@ __global__ __launch_bounds__(256) void get_pass2_kernel(const cmbpo_rollout_t r,
 // through LDS ([branch][step][dim]) and writes each branch's samples as one run -- the runs of a tile are adjacent, the
 // tile's output is a single contiguous block.  (Reading the output order straight from the buffers touched a 116-byte run
 // per sample: 2.9 TB/s.)  Vector fields: 16-branch tiles (63 KB of LDS for obs at T = 34); scalar fields: 64-branch tiles.
-#ifndef FLAT_WAVES
 #define FLAT_WAVES 3
-#endif
-#ifndef FLAT_WIDE_TILES
-#define FLAT_WIDE_TILES 1      // 0: 16-branch tiles whatever the rollout's length (diagnostic)
-#endif
-constexpr int kVecTile = FLAT_WIDE_TILES ? 64 : 16;      // (16 at 34 steps of AntSafe shapes by the 64 KB rule below; 64 after a rollout of <= 8 steps)
+constexpr int kVecTile = 64;      // (16 at 34 steps of AntSafe shapes by the 64 KB rule below; 64 after a rollout of <= 8 steps)
 constexpr int kFlatRows = 64;
 
 struct FlatArgs {
@@ -1064,7 +1046,7 @@ __device__ __forceinline__ void flatten_vec_body(const cmbpo_rollout_t &r, const
     flat_vec_out(tile + ts, fa.out[10] + (size_t)o0 * A, A, nb, T, cnt, o0, smap, tid);
     flat_vec_out(tile + 2 * ts, fa.out[11] + (size_t)o0 * A, A, nb, T, cnt, o0, smap, tid);
   };
-  if constexpr (SHORT) body(std::integral_constant<int, 2>{}, std::integral_constant<int, FLAT_WIDE_TILES ? 8 : 2>{});
+  if constexpr (SHORT) body(std::integral_constant<int, 2>{}, std::integral_constant<int, 8>{});
   else body(std::integral_constant<int, 9>{}, std::integral_constant<int, 2>{});
 }
 
@@ -1442,14 +1424,12 @@ extern "C" int cmbpo_buffer_flatten(const cmbpo_rollout_t *r, const int32_t *d_o
   // branches per workgroup of the vector fields: as many as keep the [branch][step][dim] tile within 64 KB (two
   // workgroups per CU; 16 at AntSafe shapes and 34 steps, 64 after a rollout that ended within 8 steps), fewer while the
   // buffer has less than four tiles per CU
-  static const int vt_max = getenv("CMBPO_FLAT_VT") ? atoi(getenv("CMBPO_FLAT_VT")) : kVecTile;
-  const int vt_cap = Tt <= 8 ? kVecTile : 16;     // (64-branch tiles only after short rollouts: the 2 x 8-load pass)
-  int vt = vt_max < 1 ? 1 : (vt_max > vt_cap ? vt_cap : vt_max);
+  int vt = Tt <= 8 ? kVecTile : 16;     // (64-branch tiles only after short rollouts: the 2 x 8-load pass)
   const int dtile = dmax > 3 * r->act_dim ? dmax : 3 * r->act_dim;     // obs alone, then act | log_std | mu side by side
   while (vt > 1 && (size_t)vt * Tt * dtile * sizeof(float) > 64 * 1024) vt >>= 1;
   // ... and as keep a step's run of the tile (vt x dim floats) inside the 8 x 16 bytes per lane of the short rollouts' load
   // pass (flat_vec_in; a longer run falls back to its element-wise loop)
-  if (FLAT_WIDE_TILES && Tt <= 8)
+  if (Tt <= 8)
     while (vt > 4 && vt * dmax > 2048) vt >>= 1;
   while (vt > 4 && cmbpo_ceil_div(r->B, vt) < 4 * n_cu) vt >>= 1;
   const int rows = cmbpo_ceil_div(r->B, kFlatRows) < 2 * n_cu ? 16 : kFlatRows;

@@ -6,7 +6,6 @@
 #include "common.h"
 #include "ens_mlp_internal.h"
 
-#include <stdlib.h>
 #include <string.h>
 #include <time.h>
 
@@ -61,7 +60,7 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   const bool small = ahead.on || (n_alive <= cmbpo_rollout_book_pre_max_rows() && !r->use_host_budget);
   // small batches: decide + finish(PRE) + the store's scalar half in one launch; its vector half (obs, act, mu, log_std) rides
   // in the critics' launch below where that is the one-wave-per-member kernel (8 us as a launch of its own at 1000 rows)
-  const bool vec_rides = small && cmbpo_critic_pair_supported(v, vc) && n_alive < cmbpo_internal_critic_big_min();
+  const bool vec_rides = small && cmbpo_critic_pair_supported(v, vc) && n_alive < kCriticBigMin;
   if (small) {
     if ((rc = cmbpo_internal_book_pre(r, n_alive, ahead.on ? 1 : 0, vec_rides ? 0 : 1, stream))) return rc;
   } else {
@@ -77,8 +76,7 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   if (cmbpo_critic_pair_supported(v, vc)) {      // both critics in one launch (csrc/critic_f16.hip)
     // ... and, where it fits, the actor for the next step as one more wave per tile: both read next_obs, the store above has
     // consumed this step's actions, and nothing below reads them
-    static const int ride_max = getenv("CMBPO_RIDE_MAX_ROWS") ? atoi(getenv("CMBPO_RIDE_MAX_ROWS")) : (1 << 30);
-    const bool ride = d_eps_next != nullptr && n_alive <= ride_max && n_alive < cmbpo_internal_critic_big_min() &&
+    const bool ride = d_eps_next != nullptr && n_alive < kCriticBigMin &&
                       cmbpo_internal_critic_pair_can_ride(v, vc, policy);     // (large batches: the member-after-member kernel)
     CmbpoStoreVec sv{};
     if (vec_rides) {
@@ -152,8 +150,6 @@ Mirror &mirror() {
   Mirror &m = g_mirror[dev];
   if (!m.tried) {
     m.tried = true;
-    const char *e = getenv("CMBPO_STEP_MIRROR");
-    if (e && e[0] == '0') return m;
     void *h = nullptr, *d = nullptr;
     if (hipHostMalloc(&h, (size_t)kMirrorSlots * kMirrorDwords * 4, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable) == hipSuccess &&
         hipHostGetDevicePointer(&d, h, 0) == hipSuccess) {
@@ -209,10 +205,9 @@ extern "C" int cmbpo_rollout_run(cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *p
     { const float *t = r->vc_t; r->vc_t = r->vc_n; r->vc_n = t; }
     r->ptr += 1;
   };
-  static const bool ahead_env = !(getenv("CMBPO_STEP_AHEAD") && getenv("CMBPO_STEP_AHEAD")[0] == '0');
   while (done < max_steps && n_alive > 0 && r->ptr < r->T) {
     Mirror &mir = mirror();
-    if (ahead_env && mir.d && n_alive <= cmbpo_rollout_book_pre_max_rows() && cmbpo_critic_pair_supported(v, vc)) {
+    if (mir.d && n_alive <= cmbpo_rollout_book_pre_max_rows() && cmbpo_critic_pair_supported(v, vc)) {
       // ---- small batches, to the end of the call: step k + 1 is enqueued BEFORE the host waits for step k's counters, so the
       // GPU never idles across the host's round trip (13 of 93 us per step at 1000 branches).  Nothing the host does between
       // two steps needs the counters -- the lists are swapped after every small-batch step, the column advances by one -- except
@@ -278,8 +273,7 @@ extern "C" int cmbpo_rollout_run(cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *p
       // large batches (no rider in the critics' launch): the actor for the next step goes out BEHIND the counters and ahead of
       // the host's wait for them -- it needs neither (it evaluates every row this step stepped, outputs slot indexed, exactly
       // what the rider does), and the host's round trip hides behind it
-      static const bool early_actor = !(getenv("CMBPO_EARLY_ACTOR") && getenv("CMBPO_EARLY_ACTOR")[0] == '0');
-      if (early_actor && eps_next != nullptr && !ready && r->ptr + 1 < r->T) {
+      if (eps_next != nullptr && !ready && r->ptr + 1 < r->T) {
         auto w = [](const float *q) { return const_cast<float *>(q); };
         if (int rc2 = cmbpo_policy_forward(policy, r->next_obs, r->obs_dim, eps_next, r->alive_idx, nullptr, n_alive, w(r->act_t),
                                            w(r->logp_t), w(r->mu_t), w(r->ls_t), stream))

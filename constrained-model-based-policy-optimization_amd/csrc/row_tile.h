@@ -69,12 +69,6 @@ __device__ __forceinline__ float half_sum(float v) {
   return v;
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 // load the activation tile rows n_base.. of this wave's columns from a row-layout image
 __device__ __forceinline__ f32x16 load_tile_R(const float *ldsR, int strideR, int n_base, int lane) {
   const int j = lane & 31, h = lane >> 5;

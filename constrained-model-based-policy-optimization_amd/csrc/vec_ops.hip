@@ -12,16 +12,10 @@ namespace {
 
 constexpr int kT = 1024;
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 // block-wide sum broadcast to every thread
 __device__ __forceinline__ double block_sum_all(double v, double *sm) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  v = wsum(v);
+  v = wave_sum(v);
   __syncthreads();
   if (lane == 0) sm[w] = v;
   __syncthreads();

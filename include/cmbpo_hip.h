@@ -57,8 +57,8 @@ int cmbpo_version(void);
  * three bf16 pieces (3 x 8 = 24 mantissa bits) and a.b = sum_{i+j<=4} a_i b_j runs as six
  * v_mfma_f32_32x32x16_bf16 with fp32 accumulation -- every partial product exact, dropped terms <= 2^-24 |ab|,
  * measured error 6.2e-7 of sum|a_k b_k| at K = 512 against 7.6e-7 for the fp32 MFMA chain
- * (tools/split_bf16_probe.hip) -- at about twice the matrix rate.  Both pass the same parity tests.  The
- * environment variable CMBPO_ENS_SPLIT=0/1/2 sets the initial value.  The switch also covers the critics
+ * (tools/split_bf16_probe.hip) -- at about twice the matrix rate.  Both pass the same parity tests.  The switch
+ * also covers the critics
  * (cmbpo_ens_predict_mean at 128 hidden units, one output; paths 1 and 2 both mean the bf16 split there); every other
  * shape / head uses fp32 MFMAs.
  * CMBPO_ENS_SPLIT_F16 (default since round 2, csrc/ens_h3.hip): every operand is lifted by a power of two into the top
@@ -397,8 +397,7 @@ long cmbpo_pi_saved_activation_uses(const cmbpo_pi_t *h);
 /* Arithmetic of the policy kernels' matrix products (forward, JVP, backward and
  * weight-gradient): 1 (default) = three f16 MFMAs on two-piece operands (11 + 1 +
  * 11 mantissa bits, fp32 accumulation: the error of a product stays at fp32's,
- * see DESIGN.md 3a), 0 = fp32 MFMAs throughout (round 1).  Environment
- * CMBPO_PI_F16=0 selects 0 at load. */
+ * see DESIGN.md 3a), 0 = fp32 MFMAs throughout (round 1). */
 void cmbpo_set_pi_matrix_path(int path);
 int cmbpo_get_pi_matrix_path(void);
 

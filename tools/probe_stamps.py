@@ -6,7 +6,7 @@ sys.path.insert(0, ROOT)
 PKG = os.path.join(ROOT, "constrained-model-based-policy-optimization_amd")
 so = "/tmp/libcmbpo_stamps.so"
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                       "-ffp-contract=off", "-DCMBPO_STAMPS"] + (["-DCMBPO_DIAG_NOLOAD"] if os.environ.get("NOLOAD") else []) + sorted(glob.glob(os.path.join(PKG, "csrc", "*.hip"))) + ["-o", so])
+                       "-ffp-contract=off", "-DCMBPO_STAMPS"] + sorted(glob.glob(os.path.join(PKG, "csrc", "*.hip"))) + ["-o", so])
 import numpy as np, torch
 import cmbpo_amd
 from cmbpo_amd import _lib
@@ -29,8 +29,6 @@ stamps = torch.zeros(E * tiles * 12, dtype=torch.int64, device="cuda")
 for _ in range(3):
     m.predict_ensemble(obs, act=act, out=(mean, var))
 h = C.CDLL(so)
-pad = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-h.cmbpo_debug_set_lds_pad(pad)
 h.cmbpo_debug_set_stamps.argtypes = [C.c_void_p]
 h.cmbpo_debug_set_stamps(stamps.data_ptr())
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -38,7 +36,7 @@ e0.record()
 m.predict_ensemble(obs, act=act, out=(mean, var))
 e1.record()
 torch.cuda.synchronize()
-print("lds pad", pad, "kernel ms", e0.elapsed_time(e1))
+print("kernel ms", e0.elapsed_time(e1))
 st10 = stamps.cpu().numpy().reshape(-1, 12).astype(np.int64)
 st = st10[:, :8]
 clk = (st10[:, 7] - st10[:, 0]) / np.maximum(st10[:, 9] - st10[:, 8], 1) * 100.0
