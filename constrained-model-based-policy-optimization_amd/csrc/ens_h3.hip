@@ -66,21 +66,40 @@ struct Geo {
 };
 
 // ---- LDS map (bytes) ---------------------------------------------------------------------------------------------
-// [0, ...)            layers 0 / 1: chunk images [2][2 pieces][ROWS][CSTR] | x image [2][ROWS][XSTR] | W0 chunk [2][4 S0 KB]
-//                     tail (aliases the above): partial outputs [2][8 waves][2 tiles][16][64] f32 | staging [2][32][SWS]
-// [OFF_CONST, ...)    bias0 | bias1 | head constants | per-row scales | input scaler
+// An item after the first of a workgroup is staged AHEAD -- its split input image, per-row scales, constants and the first
+// two W0 chunks are written during the last step of its predecessor's fused loop, whose tail then still runs -- so what the
+// stage writes lies behind everything the tail touches, and the per-item constants exist twice (by item parity):
+// [0, ...)            layers 0 / 1: chunk images [2][2 pieces][ROWS][CSTR]
+//                     tail (aliases them): partial outputs [8 waves][2 tiles][16][64] f32 | staging [2][32][SWS]
+// [OFF_XIMG, ...)     x image [2][ROWS][XSTR] | W0 chunk [2][4 S0 KB]
+// [OFF_CONST, ...)    2 x { bias0 | bias1 | head constants | per-row scales } | input scaler
+// That fits the CU's 160 KB only with ONE buffer of partial outputs (64 KB; two would put the tail alone at 147 712 B), at
+// the price of a second barrier per tail unit between the sum over the previous unit's partials and the next write.
+// <4, *, 4> alone keeps the old order (the stage at the top of every item, one copy of the constants, two buffers of
+// partial outputs, which cover the x image and the W0 chunks): LDS forces it -- 82 176 B of tail buffers + 69 632 B of
+// x image and W0 chunks + two constants copies 16 896 B = 168 704 B against the CU's 163 840.
 constexpr int PBUF_BYTES = kWavesH * 2 * 16 * 64 * 4;     // partial outputs of one unit: [8 waves][2 tiles][4][64 lanes] x 16 B
 constexpr int SWS = 65;                                   // row stride of a staging tile (floats): odd
 constexpr int STG_BYTES = 32 * SWS * 4;
+__host__ __device__ constexpr bool stage_ahead(int S0, int RT) { return !(S0 == 4 && RT == 4); }
+__host__ __device__ constexpr int tail_bytes(int S0, int RT) { return (stage_ahead(S0, RT) ? 1 : 2) * PBUF_BYTES + 2 * STG_BYTES; }
 __host__ __device__ constexpr int ximg_bytes(int S0, int RT) { return 2 * 32 * RT * (16 * S0 + 8) * 2; }
 __host__ __device__ constexpr int w0buf_bytes(int S0, int RT) { return RT == 4 ? 2 * S0 * 2 * 1024 : 0; }   // one chunk
-__host__ __device__ constexpr int off_const(int S0, int RT) {
-  const int cb = RT == 4 ? Geo<4>::CBUF_BYTES : (RT == 2 ? Geo<2>::CBUF_BYTES : Geo<1>::CBUF_BYTES);
-  const int a = 2 * cb + ximg_bytes(S0, RT) + 2 * w0buf_bytes(S0, RT), b = 2 * PBUF_BYTES + 2 * STG_BYTES;
-  return ((a > b ? a : b) + 15) / 16 * 16;
+__host__ __device__ constexpr int r16(int v) { return (v + 15) / 16 * 16; }
+__host__ __device__ constexpr int off_ximg(int S0, int RT) {
+  const int cb = 2 * (RT == 4 ? Geo<4>::CBUF_BYTES : (RT == 2 ? Geo<2>::CBUF_BYTES : Geo<1>::CBUF_BYTES));
+  return stage_ahead(S0, RT) && tail_bytes(S0, RT) > cb ? r16(tail_bytes(S0, RT)) : cb;
 }
-constexpr int CONST_FLOATS = 2 * HIDH + 2 * 128 + 6 * 128 + 2 * 64;
-__host__ __device__ constexpr int lds_bytes(int S0, int RT) { return off_const(S0, RT) + CONST_FLOATS * 4; }
+__host__ __device__ constexpr int off_const(int S0, int RT) {
+  const int a = off_ximg(S0, RT) + ximg_bytes(S0, RT) + 2 * w0buf_bytes(S0, RT);
+  return r16(a > tail_bytes(S0, RT) ? a : tail_bytes(S0, RT));
+}
+constexpr int ITEM_FLOATS = 2 * HIDH + 2 * 128 + 6 * 128;     // the per-item constants
+__host__ __device__ constexpr int lds_bytes(int S0, int RT) {
+  return off_const(S0, RT) + ((stage_ahead(S0, RT) ? 2 : 1) * ITEM_FLOATS + 2 * 64) * 4;
+}
+static_assert(lds_bytes(4, 4) == 156416 && lds_bytes(3, 4) == 152320 && lds_bytes(2, 4) <= 160 * 1024 &&
+              lds_bytes(4, 2) <= 160 * 1024 && lds_bytes(4, 1) <= 160 * 1024, "ens_h3: LDS map");
 
 #ifdef CMBPO_STAMPS
 #define H3_STAMP(k)                                                         \
@@ -187,6 +206,29 @@ __device__ __forceinline__ void static_for(F &&f) {
 // output stores of the previous unit (a write acknowledgement from HBM), the next item's input rows and row indices, the
 // weight fragments requested a slab ahead.
 
+// The stage of an item in pieces (stage_piece in the kernel); pieces 0 .. kReqEarly - 1 only request (in the old order they
+// travel behind the tail).  Where the pieces stand in the last fused step (slot of 24 MFMAs, MFMA i of the slot): slots 0 / 1
+// request; slots 2 .. 4 (a memory round trip under load) carry nothing but the rounds of the W0 chunks and the constants
+// that wait for the biases alone -- nothing else of the stage is independent of the raw rows; slots 5 .. 7 consume them, a
+// piece behind every second MFMA (the row scales' divisions get two gaps each).  Measured: with the rows consumed from
+// slot 4 on a 100 k-row forward is 1.2 % slower than with this table (1 084 against 1 071 us), with the rows REQUESTED behind the
+// ring's last loads of the step (slot 4) and consumed in slot 7 as slow as the old order -- vmcnt counts in order, so every
+// wait for a weight fragment requested after the rows waits for the rows too.
+constexpr int kPieces = 24, kReqEarly = 5;
+__host__ __device__ constexpr int piece_at(int slot, int i) {
+  if (i % 2 != 0) return -1;
+  const int k = i / 2;
+  if (slot == 0) return k % 3 == 0 ? k / 3 : -1;                                                // raw rows: 0 .. 3
+  if (slot == 1) return k == 0 ? 4 : (k == 2 ? 5 : (k == 4 ? 6 : -1));                          // biases, head, W0 round 0
+  if (slot == 3) return k == 4 ? 13 : -1;                                                       // W0 round 1
+  if (slot == 4) return k == 1 ? 7 : -1;                                                        // biases, head constants -> LDS
+  if (slot == 5) return k == 4 ? 20 : (k >= 6 && k < 10 ? 2 + k : -1);                          // W0 round 2; scaler: 8 .. 11
+  // row maximum + lift 12, row scales 14 / 15, split 16 .. 19, x image 21
+  if (slot == 6) return k == 0 ? 12 : (k == 1 ? 14 : (k == 3 ? 15 : (k == 5 ? 16 : (k >= 7 && k <= 9 ? 10 + k : (k == 10 ? 21 : -1)))));
+  if (slot == 7) return k < 2 ? 22 + k : -1;                                                    // the last KB of W0, the next row index
+  return -1;
+}
+
 struct H3Args {
   MlpKernelArgs m;
   const f16x8 *w0, *w1, *w2;
@@ -206,20 +248,27 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
   constexpr int NUNIT = RT * NPASS;      // (row tile, pass) units of the tail
   constexpr int O_PAD = 32 * OTP;
   constexpr int W0P = NTC * S0 * 2;      // 1-KB pieces of one W0 chunk
+  constexpr bool AHEAD = stage_ahead(S0, RT);
   const MlpKernelArgs &p = a.m;
   extern __shared__ f32x4 smem4[];
   char *smem = reinterpret_cast<char *>(smem4);
   _Float16 *cbuf = reinterpret_cast<_Float16 *>(smem);                               // [2][2][128][CSTR]
-  _Float16 *ximg = reinterpret_cast<_Float16 *>(smem + 2 * CBUF_BYTES);              // [2][128][XSTR]
-  f16x8 *w0buf = reinterpret_cast<f16x8 *>(smem + 2 * CBUF_BYTES + ximg_bytes(S0, RT));   // [2][W0P][64] (RT == 4 only)
-  f32x4 *pbuf = reinterpret_cast<f32x4 *>(smem);                                     // [2][8 waves][2 tiles][4][64] x 16 B
-  float *stg = reinterpret_cast<float *>(smem + 2 * PBUF_BYTES);                     // [2][32][SWS]
+  _Float16 *ximg = reinterpret_cast<_Float16 *>(smem + off_ximg(S0, RT));            // [2][128][XSTR]
+  f16x8 *w0buf = reinterpret_cast<f16x8 *>(smem + off_ximg(S0, RT) + ximg_bytes(S0, RT));   // [2][W0P][64] (RT == 4 only)
+  constexpr bool PB2 = !AHEAD;           // two buffers of partial outputs (by unit parity)
+  f32x4 *pbuf = reinterpret_cast<f32x4 *>(smem);                                     // [PB2 ? 2 : 1][8 waves][2 tiles][4][64] x 16 B
+  float *stg = reinterpret_cast<float *>(smem + (PB2 ? 2 : 1) * PBUF_BYTES);         // [2][32][SWS]
   float *cst = reinterpret_cast<float *>(smem + off_const(S0, RT));
-  float *bias0 = cst, *bias1 = cst + HIDH, *hc_a = cst + 2 * HIDH, *hc_c = hc_a + 128;
-  int *rowidx = reinterpret_cast<int *>(hc_c + 128);
-  float *r_inv0 = reinterpret_cast<float *>(rowidx) + 128, *r_t1 = r_inv0 + 128, *r_inv1 = r_t1 + 128, *r_t2 = r_inv1 + 128,
-        *r_inv2 = r_t2 + 128;
-  float *in_mu_l = r_inv2 + 128, *in_sig_l = in_mu_l + 64;
+  // the per-item constants: copy `par` (item parity within the workgroup's list; one copy where nothing is staged ahead)
+  struct Cst { float *bias0, *bias1, *hc_a, *hc_c; int *rowidx; float *r_inv0, *r_t1, *r_inv1, *r_t2, *r_inv2; };
+  auto cst_of = [&](int par) {
+    Cst c;
+    c.bias0 = cst + (AHEAD ? par : 0) * ITEM_FLOATS; c.bias1 = c.bias0 + HIDH; c.hc_a = c.bias0 + 2 * HIDH; c.hc_c = c.hc_a + 128;
+    c.rowidx = reinterpret_cast<int *>(c.hc_c + 128);
+    c.r_inv0 = c.hc_c + 256; c.r_t1 = c.r_inv0 + 128; c.r_inv1 = c.r_t1 + 128; c.r_t2 = c.r_inv1 + 128; c.r_inv2 = c.r_t2 + 128;
+    return c;
+  };
+  float *in_mu_l = cst + (AHEAD ? 2 : 1) * ITEM_FLOATS, *in_sig_l = in_mu_l + 64;
 
   const int n_rows = p.n_rows_dev ? *p.n_rows_dev : p.n_rows;
   const int out = p.out_dim;
@@ -230,12 +279,16 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
   }
   __syncthreads();
 
-  // ---- prefetch registers: the NEXT item's raw input rows, biases and output bias travel behind the current item's tail.
-  // Every load is unconditional (clamped addresses, the selection happens on the values): a load inside a per-element
-  // branch makes hipcc wait for it there, one memory round trip per element.
-  float xpre[KPT];
-  float bpre[2], b2pre = 0.0f;
-  int rr_pre = -1;
+  // The workgroup's items: item0 + blockIdx.x + j gridDim.x, without those whose rows all lie beyond the (device) row count.
+  auto next_alive = [&](int it) {     // (uniform)
+    while (it < p.n_items) {
+      const int e2 = it / p.tiles;
+      if ((it - e2 * p.tiles) * ROWSH < n_rows) break;
+      it += gridDim.x;
+    }
+    return it;
+  };
+  int rr_pre = -1;      // row index of this thread's row of the item that is staged next
   auto fetch_row = [&](int it, int tid) {
     const int xb = tid / TPR;
     const int e2 = it / p.tiles;
@@ -245,131 +298,198 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
     if (p.row_idx) v = p.row_idx[v];
     rr_pre = ok ? v : -1;
   };
-  auto fetch_x = [&](int tid) {
-    const int xc = tid % TPR;
-    const int rr = rr_pre >= 0 ? rr_pre : 0;
-    const float *orow = p.obs + (size_t)rr * p.obs_dim;
-    const float *arow = p.act_dim > 0 ? p.act + (size_t)rr * p.act_dim - p.obs_dim : orow;
+
+  // ---- the stage of an item: constants, per-row scales, the split input image, the first two W0 chunks -> LDS, in
+  // kPieces pieces of at most ~20 issue cycles (the x loads' address arithmetic and the row scales' divisions somewhat more).
+  // The first item of a workgroup runs them in a row in front of its layers; every later item's pieces are dealt out between
+  // the layer-1 MFMAs of its predecessor's last fused step (step(), STG), which has no chunk to produce and whose x image,
+  // W0 ring and other constants copy nobody reads any more.  Pieces 0 .. 6 only request: raw rows (clamped addresses, the
+  // selection happens on the values: a load inside a per-element branch makes hipcc wait for it there), biases | head
+  // constants, the member's statistics, the first KB per wave of W0 chunks 0 / 1 (they pass through four registers, W0R
+  // rounds).  The others consume, behind the counted vmcnt waits hipcc places (the weight ring's loads stay in flight).
+  // An empty volatile asm after a piece keeps it where it stands.
+  constexpr int W0R = G::W0_LDS ? (2 * W0P + kWavesH - 1) / kWavesH : 1;
+  constexpr int GQ = KPT / 4;        // input elements per piece
+  struct StageRegs {
+    float x[KPT];
+    float b0, b1, b2, hs, hm, hl;    // biases of this thread's hidden unit / output, output scaler
+    float st[7];                     // the member's statistics (uniform)
+    f16x8 w0r[W0R];
+    float m, t0, t1, t2;
+    unsigned q1[KPT / 2], q2[KPT / 2];   // the two f16 pieces, packed
+  };
+  auto stage_piece = [&](auto KC, auto FRONTC, StageRegs &s, const int es, const Cst &c, const int tid, const int it_next) {
+    constexpr int K = decltype(KC)::value;
+    constexpr bool FRONT = decltype(FRONTC)::value;
+    const int xb = tid / TPR, xc = tid % TPR;
+    if constexpr (K < 4) {
+      const int rr = rr_pre >= 0 ? rr_pre : 0;
+      const float *orow = p.obs + (size_t)rr * p.obs_dim;
+      const float *arow = p.act_dim > 0 ? p.act + (size_t)rr * p.act_dim - p.obs_dim : orow;
 #pragma unroll
-    for (int u = 0; u < KPT; ++u) {
-      const int k = KPT * xc + u;
-      const float *q = (k < p.obs_dim) ? orow + k : ((k < p.in_dim) ? arow + k : orow);
-      xpre[u] = *q;
+      for (int u = GQ * K; u < GQ * K + GQ; ++u) {
+        // (selects on values, not on address expressions: the load stays unconditional)
+        const int k = KPT * xc + u;
+        const bool in_obs = k < p.obs_dim, in_act = !in_obs & (k < p.in_dim);
+        const float *base = in_act ? arow : orow;
+        const int off = (in_obs | in_act) ? k : 0;
+        s.x[u] = base[off];
+      }
+    } else if constexpr (K == 4) {
+      s.b0 = p.b0[(size_t)es * HIDH + tid];
+      s.b1 = p.b1[(size_t)es * HIDH + tid];
+      const int ob = p.o_tiles * 32;
+      s.b2 = p.b2[(size_t)es * ob + (tid < ob ? tid : 0)];
+    } else if constexpr (K == 5) {
+      s.hs = 1.0f; s.hm = 0.0f; s.hl = 0.0f;
+      if (p.out_mu) {     // (uniform)
+        const int ia = tid < out ? tid : out - 1, il = tid < out ? 0 : (tid < 2 * out ? tid - out : out - 1);
+        s.hs = p.out_sig[ia]; s.hm = p.out_mu[ia]; s.hl = p.out_lsig2[il];
+      }
+      const float *st = a.stats + (size_t)es * NSTAT;
+      s.st[0] = st[0]; s.st[1] = st[1]; s.st[2] = st[2]; s.st[3] = st[4]; s.st[4] = st[5]; s.st[5] = st[6]; s.st[6] = st[8];
+    } else if constexpr (K == 6 || K == 13 || K == 20 || K == 22) {
+      // The W0 chunks.  In front of an item: every KB of the wave requested at once (piece 6), written at the end (piece 22),
+      // as many registers as rounds.  Staged ahead: in rounds through four registers -- round u writes what round u - 1
+      // requested and requests the next KB.
+      if constexpr (G::W0_LDS) {
+        const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        const f16x8 *w0s = a.w0 + (size_t)es * a.w0_stride;
+        auto get = [&](f16x8 &x, int u) { const int j = wave + kWavesH * u; x = w0s[(size_t)(j < 2 * W0P ? j : 0) * 64 + lane]; };
+        auto put = [&](const f16x8 &x, int u) { const int j = wave + kWavesH * u; if (j < 2 * W0P) w0buf[(size_t)j * 64 + lane] = x; };
+        if constexpr (FRONT) {
+#pragma unroll
+          for (int u = 0; u < W0R; ++u) {
+            if constexpr (K == 6) get(s.w0r[u], u);
+            if constexpr (K == 22) put(s.w0r[u], u);
+          }
+        } else {
+          constexpr int u = K == 6 ? 0 : (K == 13 ? 1 : (K == 20 ? 2 : 3));
+          static_assert(W0R <= 3, "ens_h3: rounds of the W0 chunks");
+          if constexpr (u >= 1 && u <= W0R) put(s.w0r[0], u - 1);
+          if constexpr (u < W0R) get(s.w0r[0], u);
+        }
+      }
+    } else if constexpr (K == 7) {
+      c.bias0[tid] = s.b0 * kLog2e;      // (the epilogues work on z log2(e): f16_split.h)
+      c.bias1[tid] = s.b1 * kLog2e;
+      if (tid < O_PAD) {
+        // y = A_n z + B_n with z = o + b2_n; n < out: mean = sig z + mu; out <= n < 2 out: var = exp(z + 2 log sig)
+        // (models/pens/pe.py:815-835)
+        const bool is_mean = tid < out, is_var = !is_mean & (tid < 2 * out);
+        float A = is_var ? 1.0f : 0.0f, Bc = is_var ? s.hl : 0.0f;
+        A = is_mean ? s.hs : A; Bc = is_mean ? s.hm : Bc;
+        c.hc_a[tid] = A;
+        c.hc_c[tid] = A * s.b2 + Bc;
+      }
+    } else if constexpr (K < 12) {
+      if constexpr (K == 8) s.m = 0.0f;
+#pragma unroll
+      for (int u = GQ * (K - 8); u < GQ * (K - 8) + GQ; ++u) {
+        const int k = KPT * xc + u;
+        // TensorStandardScaler.transform (models/pens/utils.py:156) as (x - mu) (1 / sigma): within an ulp of the division, a
+        // tenth of its instructions (sixteen IEEE divisions per thread were a third of the stage)
+        float x = (s.x[u] - in_mu_l[k & 63]) * in_sig_l[k & 63];
+        const bool keep = (k < p.in_dim) & (rr_pre >= 0);
+        x = keep ? x : 0.0f;
+        s.x[u] = x;
+        s.m = fmaxf(s.m, fabsf(x));
+        asm volatile("" : "+v"(s.x[u]));
+      }
+      asm volatile("" : "+v"(s.m));
+    } else if constexpr (K == 12) {
+#pragma unroll
+      for (int o = 1; o < TPR; o <<= 1) s.m = fmaxf(s.m, __shfl_xor(s.m, o, 64));
+      s.t0 = pow2_lift(s.m);
+      asm volatile("" : "+v"(s.m), "+v"(s.t0));
+    } else if constexpr (K == 14) {
+      if (xc == 0) {
+        const float bound1 = (s.st[1] * s.m + s.st[2]) * 1.001f, t1 = pow2_lift(bound1);
+        const float bound2 = (s.st[4] * bound1 + s.st[5]) * 1.001f, t2 = pow2_lift(bound2);
+        c.rowidx[xb] = rr_pre;
+        c.r_inv0[xb] = 1.0f / (s.st[0] * s.t0);
+        c.r_t1[xb] = t1;
+        c.r_t2[xb] = t2;
+        s.t1 = t1; s.t2 = t2;
+      }
+    } else if constexpr (K == 15) {
+      if (xc == 0) {
+        c.r_inv1[xb] = 1.0f / (s.st[3] * s.t1);
+        c.r_inv2[xb] = 1.0f / (s.st[6] * s.t2);
+      }
+    } else if constexpr (K < 20) {
+#pragma unroll
+      for (int u = GQ * (K - 16); u < GQ * (K - 16) + GQ; ++u) {
+        _Float16 h1, h2;
+        split_h(s.x[u] * s.t0, h1, h2);
+        // (the halves of a dword one after the other: u even first)
+        if (u % 2 == 0) { s.q1[u / 2] = __builtin_bit_cast(unsigned short, h1); s.q2[u / 2] = __builtin_bit_cast(unsigned short, h2); }
+        else {
+          s.q1[u / 2] |= (unsigned)__builtin_bit_cast(unsigned short, h1) << 16;
+          s.q2[u / 2] |= (unsigned)__builtin_bit_cast(unsigned short, h2) << 16;
+          asm volatile("" : "+v"(s.q1[u / 2]), "+v"(s.q2[u / 2]));
+        }
+      }
+    } else if constexpr (K == 21) {
+      if (KPT * xc < 16 * S0) {
+        _Float16 *d1 = ximg + (size_t)xb * XSTR + KPT * xc, *d2 = d1 + (size_t)ROWSH * XSTR;
+        if constexpr (KPT >= 8) {
+#pragma unroll
+          for (int v = 0; v < KPT / 8; ++v) {
+            u32x4 w1, w2;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { w1[u] = s.q1[4 * v + u]; w2[u] = s.q2[4 * v + u]; }
+            reinterpret_cast<u32x4 *>(d1)[v] = w1; reinterpret_cast<u32x4 *>(d2)[v] = w2;
+          }
+        } else {
+          *reinterpret_cast<uint2 *>(d1) = make_uint2(s.q1[0], s.q1[1]);
+          *reinterpret_cast<uint2 *>(d2) = make_uint2(s.q2[0], s.q2[1]);
+        }
+      }
+    } else {
+      fetch_row(it_next, tid);     // the row index of the item after: lands during the layers
     }
   };
-  auto fetch_bias = [&](int it, int tid) {
-    const int e2 = (it < p.n_items) ? it / p.tiles : 0;
-    bpre[0] = p.b0[(size_t)e2 * HIDH + tid];
-    bpre[1] = p.b1[(size_t)e2 * HIDH + tid];
-    const int ob = p.o_tiles * 32;
-    b2pre = p.b2[(size_t)e2 * ob + (tid < ob ? tid : 0)];
-  };
-  fetch_row(a.item0 + blockIdx.x, threadIdx.x);
-  fetch_x(threadIdx.x);
-  fetch_bias(a.item0 + blockIdx.x, threadIdx.x);
 #ifdef CMBPO_STAMPS
   unsigned long long t_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long t_last = __builtin_amdgcn_s_memtime();
   const unsigned long long t_rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
 
-  for (int item = a.item0 + blockIdx.x; item < p.n_items; item += gridDim.x) {
+  StageRegs sr;       // requests in flight: the first item's, and (old order only) the next item's behind the tail
+  // the stage in a row in front of an item's layers: the first item of a workgroup -- every item in the old order
+  auto stage_front = [&](int es, const Cst &c, int tid, int it_next) {
+    static_for<kReqEarly, kPieces>([&](auto P) { stage_piece(P, std::true_type{}, sr, es, c, tid, it_next); });
+    H3_STAMP(0);
+    lds_barrier();
+    H3_STAMP(1);
+  };
+  int item = next_alive(a.item0 + blockIdx.x);
+  int nxt = next_alive(item + gridDim.x);
+  int par = 0;
+  if (item < p.n_items) {
+    fetch_row(item, threadIdx.x);
+    const int e0 = item / p.tiles;
+    static_for<0, kReqEarly>([&](auto P) { stage_piece(P, std::true_type{}, sr, e0, cst_of(0), threadIdx.x, 0); });
+    if constexpr (AHEAD) stage_front(e0, cst_of(0), threadIdx.x, nxt);
+  }
+
+  while (item < p.n_items) {
     // the thread index, re-read inside the loop through an opaque move: everything derived from it is recomputed per
     // item instead of being hoisted out of the loop and parked in scratch (the loop body needs every register)
     int tid = threadIdx.x;
     asm volatile("v_mov_b32 %0, %0" : "+v"(tid));
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const int xb = tid / TPR, xc = tid % TPR;   // stage: row of the item, KPT-wide k part
     const int e = item / p.tiles;
-    const int row0 = (item - e * p.tiles) * ROWSH;
-    if (row0 >= n_rows) {    // (uniform) nothing alive in this tile; keep the prefetch chain going
-      fetch_row(item + gridDim.x, tid);
-      fetch_x(tid);
-      fetch_bias(item + gridDim.x, tid);
-      continue;
-    }
-    const float *st = a.stats + (size_t)e * NSTAT;
-    // ---- stage: constants, per-row scales, the split input image, the first two W0 chunks --------------------------
+    const int e_nxt = (nxt < p.n_items ? nxt : item) / p.tiles;
+    const int nxt2 = next_alive(nxt + gridDim.x);
+    const Cst cc = cst_of(par);
+    float *const bias0 = cc.bias0, *const bias1 = cc.bias1, *const hc_a = cc.hc_a, *const hc_c = cc.hc_c;
+    int *const rowidx = cc.rowidx;
+    float *const r_inv0 = cc.r_inv0, *const r_t1 = cc.r_t1, *const r_inv1 = cc.r_inv1, *const r_t2 = cc.r_t2, *const r_inv2 = cc.r_inv2;
     const f16x8 *w0e = a.w0 + (size_t)e * a.w0_stride;
-    {
-      constexpr int W0R = G::W0_LDS ? (2 * W0P + kWavesH - 1) / kWavesH : 1;
-      f16x8 w0r[W0R];
-      if constexpr (G::W0_LDS) {
-#pragma unroll
-        for (int u = 0; u < W0R; ++u) {
-          const int j = wave + kWavesH * u;
-          w0r[u] = w0e[(size_t)(j < 2 * W0P ? j : 0) * 64 + lane];
-        }
-      }
-      bias0[tid] = bpre[0] * kLog2e;      // (the epilogues work on z log2(e): f16_split.h)
-      bias1[tid] = bpre[1] * kLog2e;
-      if (tid < O_PAD) {
-        // y = A_n z + B_n with z = o + b2_n; n < out: mean = sig z + mu; out <= n < 2 out: var = exp(z + 2 log sig)
-        // (models/pens/pe.py:815-835)
-        float A = 0.0f, Bc = 0.0f;
-        if (tid < out) { A = p.out_mu ? p.out_sig[tid] : 1.0f; Bc = p.out_mu ? p.out_mu[tid] : 0.0f; }
-        else if (tid < 2 * out) { A = 1.0f; Bc = p.out_mu ? p.out_lsig2[tid - out] : 0.0f; }
-        hc_a[tid] = A;
-        hc_c[tid] = A * b2pre + Bc;
-      }
-      float xs[KPT];
-      float m = 0.0f;
-#pragma unroll
-      for (int u = 0; u < KPT; ++u) {
-        const int k = KPT * xc + u;
-        // TensorStandardScaler.transform (models/pens/utils.py:156) as (x - mu) (1 / sigma): within an ulp of the division, a
-        // tenth of its instructions (sixteen IEEE divisions per thread were a third of the stage)
-        float x = (xpre[u] - in_mu_l[k & 63]) * in_sig_l[k & 63];
-        x = (k < p.in_dim && rr_pre >= 0) ? x : 0.0f;
-        xs[u] = x;
-        m = fmaxf(m, fabsf(x));
-      }
-#pragma unroll
-      for (int o = 1; o < TPR; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-      const float t0 = pow2_lift(m);
-      if (xc == 0) {
-        const float bound1 = (st[1] * m + st[2]) * 1.001f, t1 = pow2_lift(bound1);
-        const float bound2 = (st[5] * bound1 + st[6]) * 1.001f, t2 = pow2_lift(bound2);
-        rowidx[xb] = rr_pre;
-        r_inv0[xb] = 1.0f / (st[0] * t0);
-        r_t1[xb] = t1;
-        r_inv1[xb] = 1.0f / (st[4] * t1);
-        r_t2[xb] = t2;
-        r_inv2[xb] = 1.0f / (st[8] * t2);
-      }
-      if (KPT * xc < 16 * S0) {
-        _Float16 q1[KPT], q2[KPT];
-#pragma unroll
-        for (int u = 0; u < KPT; ++u) split_h(xs[u] * t0, q1[u], q2[u]);
-        _Float16 *d1 = ximg + (size_t)xb * XSTR + KPT * xc, *d2 = d1 + (size_t)ROWSH * XSTR;
-        if constexpr (KPT >= 8) {
-#pragma unroll
-          for (int v = 0; v < KPT / 8; ++v) {
-            f16x8 w1, w2;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { w1[u] = q1[8 * v + u]; w2[u] = q2[8 * v + u]; }
-            reinterpret_cast<f16x8 *>(d1)[v] = w1; reinterpret_cast<f16x8 *>(d2)[v] = w2;
-          }
-        } else {
-          f16x4 w1, w2;
-#pragma unroll
-          for (int u = 0; u < 4; ++u) { w1[u] = q1[u]; w2[u] = q2[u]; }
-          *reinterpret_cast<f16x4 *>(d1) = w1; *reinterpret_cast<f16x4 *>(d2) = w2;
-        }
-      }
-      if constexpr (G::W0_LDS) {
-#pragma unroll
-        for (int u = 0; u < W0R; ++u) {
-          const int j = wave + kWavesH * u;
-          if (j < 2 * W0P) w0buf[(size_t)j * 64 + lane] = w0r[u];     // chunks 0, 1
-        }
-      }
-    }
-    fetch_row(item + gridDim.x, tid);     // the next item's row index: lands during the layers
-    H3_STAMP(0);
-    lds_barrier();
-    H3_STAMP(1);
+    if constexpr (!AHEAD) stage_front(e, cc, tid, nxt);
 
     // ---- layers 0 + 1, fused over the 8 chunks of h1 -------------------------------------------------------------------
     const int l0_tn = wave & (NTC - 1), l0_bt = wave / NTC;     // this wave's (n-tile, row-tile) pair of every chunk
@@ -459,10 +579,23 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
     // slot ahead), slots 4 .. 7 one quarter of the swish / lift / split epilogue each, a piece behind every second MFMA.
     // Within a position the MFMAs of tiles 0, 1 come first: the last position of a slab frees that half of the ring 6 MFMAs
     // before the other.  PH = c % NPH: where the ring stands (compile-time register indices).  The last step has no chunk to
-    // produce: an instance of its own.
+    // produce: an instance of its own, which carries the next item's stage in the empty gaps (STG), every piece behind a
+    // uniform branch on "there is a next item" (two instances of the step, with and without the stage, cost two hundred
+    // spilled registers where they meet again).
     auto step = [&](auto LASTC, const int c, auto PHC) {
       constexpr bool LAST = decltype(LASTC)::value;
       constexpr int PH = decltype(PHC)::value;
+      constexpr bool STG = LAST && AHEAD;
+      const bool have_next = nxt < p.n_items;
+      // the stage's own registers, thread index (an opaque move again: nothing of the stage is computed at the top of the
+      // item and carried through the loop) and constants copy
+      StageRegs sa;
+      int tid_s = 0;
+      if constexpr (STG) {
+        tid_s = threadIdx.x;
+        asm volatile("v_mov_b32 %0, %0" : "+v"(tid_s));
+      }
+      const Cst cn = cst_of(par ^ 1);
       f16x8 wst;
       const bool stage_w0 = c + 2 < NCH;
       const int cw = stage_w0 ? c + 2 : NCH - 1;
@@ -475,8 +608,8 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
       f32x4 bv = {0.0f, 0.0f, 0.0f, 0.0f};
       read_b(Bt[0], img, 0, 0);
       if constexpr (!LAST) l0_read(l0, c + 1, 0);
-#pragma unroll
-      for (int slot = 0; slot < 8; ++slot) {
+      static_for<0, 8>([&](auto SLOTC) {       // (compile-time slot and MFMA index: the stage's pieces are chosen by them)
+        constexpr int slot = decltype(SLOTC)::value;
         if (!LAST && slot >= 4) bv = l0_bias(c + 1, slot - 4);
         if constexpr (G::W0_LDS && !LAST) {
           // W0 fragments of chunk c + 2 pass through four registers, one 1-KB piece at a time
@@ -486,8 +619,8 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
             wst = w0e[((size_t)cw * W0P + (wave + kWavesH < W0P ? wave + kWavesH : wave)) * 64 + lane];
           }
         }
-#pragma unroll
-        for (int i = 0; i < 24; ++i) {
+        static_for<0, 24>([&](auto IC) {
+          constexpr int i = decltype(IC)::value;
           const int pos = 2 * slot + i / 12;                      // position in the (slab, row tile) sequence
           const int sl = pos / VT, v = pos % VT;
           const int u = (i % 12) / 3, term = i % 3;
@@ -520,8 +653,17 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
             if (k == 9) epi_stage<9, true>(es, d, q, inv0_l, bv, t1_l);
             if (k == 10) l0_store(es, c + 1, q);
           }
+          if constexpr (STG && piece_at(slot, i) >= 0)
+            if (have_next) stage_piece(std::integral_constant<int, (piece_at(slot, i) >= 0 ? piece_at(slot, i) : 0)>{}, std::false_type{}, sa, e_nxt, cn, tid_s, nxt2);
           __builtin_amdgcn_sched_barrier(0);
-        }
+        });
+      });
+      if constexpr (STG) {     // ("slot 8": behind the last MFMA)
+        static_for<0, 24>([&](auto IC) {
+          constexpr int pc = piece_at(8, decltype(IC)::value);
+          if constexpr (pc >= 0)
+            if (have_next) stage_piece(std::integral_constant<int, (pc >= 0 ? pc : 0)>{}, std::false_type{}, sa, e_nxt, cn, tid_s, nxt2);
+        });
       }
       H3_STAMP(4);
       if constexpr (G::W0_LDS && !LAST) {
@@ -541,10 +683,10 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
       static_for<0, NREG - NFULL>([&](auto P) { step(std::false_type{}, NFULL + decltype(P)::value, P); });
       step(std::true_type{}, NREG, std::integral_constant<int, NREG % NPH>{});
     }
-
-    // the next item's rows, biases and output bias: in flight behind the tail
-    fetch_x(tid);
-    fetch_bias(item + gridDim.x, tid);
+    if constexpr (!AHEAD) {
+      // old order: the next item's requests travel behind the tail
+      if (nxt < p.n_items) static_for<0, kReqEarly>([&](auto P) { stage_piece(P, std::true_type{}, sr, e_nxt, cc, tid, 0); });
+    }
     H3_STAMP(6);
 
     // ---- tail: h2 -> output layer -> head -> stores, one (32-row tile, pair of output tiles) unit at a time.
@@ -558,7 +700,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
       // applies the head (models/pens/pe.py:815-835) and leaves the values in the staging tile [row][column of the pair]
       const int rt = u / NPASS, pass = u % NPASS;
       const int tt = wave >> 2, q = wave & 3;
-      const f32x4 *pp = pbuf + ((size_t)(u & 1) * 64 + (size_t)tt * 4 + q) * 64 + lane;
+      const f32x4 *pp = pbuf + ((size_t)(PB2 ? u & 1 : 0) * 64 + (size_t)tt * 4 + q) * 64 + lane;
       f32x4 v = pp[0];
 #pragma unroll
       for (int wv = 1; wv < kWavesH; ++wv) v += pp[(size_t)wv * 8 * 64];
@@ -639,7 +781,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
     // group q of tile tt = outputs 32 tt + 8 q + 4 h .. + 3 of row r; a 16x16 lane (c, g) of o[tt][a][vv] holds outputs
     // 32 tt + 16 a + 4 g .. + 3 of row 16 vv + sig(c)
     auto put_partials = [&](const f32x4 (&o)[2][2][2], int u) {
-      f32x4 *pw = pbuf + ((size_t)(u & 1) * 64 + (size_t)wave * 8) * 64;
+      f32x4 *pw = pbuf + ((size_t)(PB2 ? u & 1 : 0) * 64 + (size_t)wave * 8) * 64;
 #pragma unroll
       for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
@@ -673,7 +815,8 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
         }
       // The tail as four stages per row tile, A: swish / lift / split of h2 (VALU) -> B: output-layer MFMAs + partial sums to
       // LDS -> [barrier] -> C: sum of the eight waves' partials + head -> D: stores.  Between two barriers a wave runs
-      // D(k-2), C(k-1), B(k), A(k+1).  Measured (profiles/r03/h3_variants_5.log, _6.log): each stage costs about what its
+      // D(k-2), C(k-1), B(k), A(k+1); with one buffer of partial outputs a barrier of its own stands between B(k)'s MFMAs
+      // and its partial sums' writes (every wave has read unit k-1's by then).  Measured (profiles/r03/h3_variants_5.log, _6.log): each stage costs about what its
       // instructions cost alone (A 5.7 %, B 5.1 %, C + D 4.5 % of a forward); giving the two waves of a SIMD opposite orders
       // inside an interval or dealing A(k+1) out between B(k)'s MFMAs changed nothing (1.264 -> 1.269 ms), so the plain
       // order stands.
@@ -687,6 +830,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
           for (int tt = 0; tt < 2; ++tt) out_mm(o[tt], w2r[ks][tt], bfu[rt & 1], ks);
+        if (!PB2 && rt > 0) lds_barrier();
         put_partials(o, rt);
       };
       stA(std::integral_constant<int, 0>{});
@@ -726,6 +870,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
             if (st < 3 || pass + 1 < NPASS) load_w2(wf[(st & 1) ^ 1], st == 3 ? pass + 1 : pass, (st + 1) & 3);
             out_mm(o[st & 1], wf[st & 1], bfu, st >> 1);
           }
+          if (!PB2 && u > 0) lds_barrier();     // one buffer of partial outputs: every wave has summed unit u - 1's
           put_partials(o, u);
           H3_STAMP(7);
           lds_barrier();       // unit u's partials are complete; unit u - 1's staging tile too
@@ -739,8 +884,9 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
       store_unit(NUNIT - 1);
     }
     H3_STAMP(10);
-    lds_barrier();     // the LDS regions are rewritten by the next item's stage
+    lds_barrier();     // the tail's buffers are the next item's chunk images (old order: and its stage's x image)
     H3_STAMP(11);
+    item = nxt; nxt = nxt2; par ^= 1;
   }  // persistent item loop
 #ifdef CMBPO_STAMPS
   if (p.stamps && threadIdx.x == 0) {

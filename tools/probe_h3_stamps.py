@@ -47,12 +47,14 @@ torch.cuda.synchronize()
 print("kernel ms (stamped build)", e0.elapsed_time(e1))
 st = stamps.cpu().numpy().reshape(256, 16).astype(np.float64)
 items = (B + 127) // 128 * E / 256.0
-names = ["stage", "stage barrier", "prologue L0 + barrier", "chunk: L0 part", "chunk: L1 slabs", "chunk: W0 write + barrier",
-         "prefetch issue", "tail: h2 epilogue", "tail: L2 (+partials)", "tail: barrier + head", "tail: barrier + stores", "tail: barrier"]
+# (the first item of a workgroup is staged in front of its layers: slots 0 / 1; every later one during its predecessor's
+# last fused step, whose cycles are part of "chunk: L1 slabs" -- <4,*,4> stages every item in front)
+names = ["stage (first item of a workgroup)", "stage barrier (first item)", "prologue L0 + barrier", "chunk: L0 part",
+         "chunk: L1 slabs (+ next item's stage)", "chunk: W0 write + barrier", "prefetch issue (old order only)", "tail: h2 epilogue", "tail: L2 (+partials)", "tail: barrier + head", "tail: barrier + stores", "tail: barrier"]
 tot = st[:, :12].sum(axis=1)
 clk = tot / np.maximum(st[:, 12], 1) * 100.0
 print("in-kernel clock MHz (median over workgroups): %.0f" % np.median(clk))
 print("cycles per item (mean over workgroups): %.0f   items per workgroup %.1f" % (tot.mean() / items, items))
 for k, n in enumerate(names):
-    print(f"  {n:28s} {st[:, k].mean() / items:9.0f} cycles/item  {st[:, k].mean() / tot.mean() * 100:5.1f}%")
+    print(f"  {n:40s} {st[:, k].mean() / items:9.0f} cycles/item  {st[:, k].mean() / tot.mean() * 100:5.1f}%")
 print("ideal MFMA cycles per item and SIMD (2 waves): L0 %d, L1 %d, L2 %d" % (2 * 72 * 32, 2 * 768 * 32, 2 * 96 * 32))
