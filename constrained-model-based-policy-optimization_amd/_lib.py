@@ -150,6 +150,19 @@ SIGNATURES.update({
     "cmbpo_trainer_steps_done": (C.c_long, [_p]),
 })
 
+# start states of an imagined-rollout round (csrc/start_states.hip)
+START_MAX_RUNS = 1024                          # CMBPO_START_MAX_RUNS
+START_TABLE_INTS = 8 + 11 * START_MAX_RUNS     # CMBPO_START_TABLE_INTS
+START_CDF_DOUBLES = 8 + 4 * START_MAX_RUNS     # CMBPO_START_CDF_DOUBLES
+SIGNATURES.update({
+    "cmbpo_start_table_build": (_i, [_p, C.c_long, _p, _p]),
+    "cmbpo_start_epoch_draw": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, C.c_long, _i, _i, _p, _p, _p, _p, _p]),
+    "cmbpo_start_kl_parts": (_i, [_i]),
+    "cmbpo_start_kl_partials": (_i, [_p] * 4 + [_i] * 3 + [_p, _i, _p]),
+    "cmbpo_start_cdf": (_i, [_p, _p, _i, _i, _p, C.c_double, _p, _p]),
+    "cmbpo_start_boltz_draw": (_i, [_p, _p, _p, _i, _p, C.c_long, _i, _p, _p, _p]),
+})
+
 _lib = None
 
 

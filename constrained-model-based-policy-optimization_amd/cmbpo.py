@@ -62,7 +62,7 @@ class CMBPO:
                  initial_real_samples_per_epoch=5000, min_real_samples_per_epoch=500, batch_size_policy=25000,
                  n_epochs=int(10e7), n_initial_exploration_steps=0, initial_exploration_policy=None, epoch_length=1000,
                  model_train_kwargs=None, initial_model_train_kwargs=None, shuffle_on_device=True, device=None,
-                 session=None, **_unused):
+                 session=None, start_state_sampling='host', **_unused):
         if m_learn_cost:
             raise NotImplementedError("m_learn_cost: the learned cost head is unused by every shipped config")
         # RLAlgorithm.__init__ (algorithms/rl_algorithm.py:22-74)
@@ -100,6 +100,11 @@ class CMBPO:
         # per-epoch shuffle_rows of PE.train on the GPU (same distribution, other random numbers): the host argsort of
         # an [E, n] array costs more than the epoch's kernels from n ~ 1e5 on.  False restores the reference's draws.
         self._shuffle_on_device = bool(shuffle_on_device)
+        # 'host': the reference's NumPy draws over the host archive (its random stream).  'device': the same chain on the
+        # buffer's device mirror (CPOBuffer.sample_start_states: other random numbers, no host copy of a batch-sized array)
+        if start_state_sampling not in ('host', 'device'):
+            raise ValueError("start_state_sampling: 'host' or 'device', got %r" % (start_state_sampling,))
+        self._start_state_sampling = start_state_sampling
 
         if use_model:
             self._model = build_PE(in_dim=self.obs_dim + self.act_dim, out_dim=self.obs_dim + 1, name='DynEns',
@@ -184,6 +189,19 @@ class CMBPO:
         return [a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32,
                                                                       device=self.device) for a in arrays]
 
+    def _reset_to_start_states(self, policy):
+        """algorithms/cmbpo.py:239-251: draw the start states of a rollout round and reset the model sampler to them."""
+        B = self._rollout_batch_size
+        if self._start_state_sampling == 'device':
+            self.model_sampler.reset(None, batch_size=B, fill=lambda cur_obs: self._buffer.sample_start_states(
+                policy, B, alpha=self.sampling_alpha, out=cur_obs))
+            return
+        ep_b = self._buffer.epoch_batch(batch_size=B, epochs=self._buffer.epochs_list, fields=['observations', 'pi_infos'])
+        kls = np.clip(policy.compute_DKL(ep_b['observations'], ep_b['mu'], ep_b['log_std']), a_min=0, a_max=None)
+        btz_dist = self._buffer.boltz_dist(kls, alpha=self.sampling_alpha)
+        btz_b = self._buffer.distributed_batch_from_archive(B, btz_dist, fields=['observations', 'pi_infos'])
+        self.model_sampler.reset(btz_b['observations'])
+
     # -- the loop ------------------------------------------------------------------------------------------
     def _train(self):
         """Generator over diagnostics dicts; ``{'done': True, ...}`` ends it (algorithms/cmbpo.py:177-430)."""
@@ -215,13 +233,7 @@ class CMBPO:
                     self._set_rollout_length()
                 while keep_rolling:
                     # starting states: Boltzmann distribution over the archived epochs, temperature = policy KL
-                    ep_b = self._buffer.epoch_batch(batch_size=self._rollout_batch_size, epochs=self._buffer.epochs_list,
-                                                    fields=['observations', 'pi_infos'])
-                    kls = np.clip(policy.compute_DKL(ep_b['observations'], ep_b['mu'], ep_b['log_std']), a_min=0, a_max=None)
-                    btz_dist = self._buffer.boltz_dist(kls, alpha=self.sampling_alpha)
-                    btz_b = self._buffer.distributed_batch_from_archive(self._rollout_batch_size, btz_dist,
-                                                                        fields=['observations', 'pi_infos'])
-                    self.model_sampler.reset(btz_b['observations'])
+                    self._reset_to_start_states(policy)
                     # the reference's loop over sample() (:352-360: stop at 99 % of the batch or at alive_ratio <= 0.1),
                     # taken in native code
                     self.model_sampler.sample_many(max_samples=int(self.approx_model_batch - samples_added),

@@ -11,8 +11,13 @@ arrays (as in the reference); the arithmetic of the path runs i
     truncated to ``ptr`` and a dump into the off-policy archive.
 
 The archive accessors the trainer uses for start-state sampling (``epoch_batch``, ``boltz_dist``,
-``distributed_batch_from_archive``, ``algorithms/cmbpo.py:241-245``) are kept as thin NumPy index plumbing; moving
-them to the device is SURVEY §8(f) row N3.
+``distributed_batch_from_archive``, ``algorithms/cmbpo.py:241-245``) are kept as thin NumPy index plumbing, as the
+reference has them.  The same chain also runs on the device: ``enable_device_archive``
+keeps a device mirror of the four archive columns it reads (observations, mu, log_std, epochs), appended to by
+``dump_to_archive``, and ``sample_start_states`` draws the start states of a rollout round from it with the kernels of
+``csrc/start_states.hip`` -- per-epoch uniform draw, per-epoch policy KL, Boltzmann CDF, inverse-CDF draw written into
+the rollout state -- without a host copy of any batch-sized array.  The mirror is opt-in: nothing is allocated or
+written until it is enabled, and the host archive and the NumPy random stream of the accessors above are untouched.
 """
 import warnings
 
@@ -35,6 +40,7 @@ class CPOBuffer:
         self.device = torch.device(device if device is not None else "cuda")
         self.pi_info_shapes = None
         self.gamma, self.lam, self.cost_gamma, self.cost_lam = 0.99, 0.95, 0.99, 0.95
+        self._dev = None              # device mirror of the archive (enable_device_archive)
         self.reset_buffers()
         self.reset_arch()
 
@@ -69,6 +75,10 @@ class CPOBuffer:
             self.arch_dict["pi_infos"] = self.pi_info_archive
         self.archive_ptr = 0
         self.max_pointer = 0
+        if self._dev is not None:
+            for k, t in self._dev.items():
+                t.fill_(-1) if k == "epochs" else t.zero_()
+            self._dev_version += 1
 
     def initialize(self, pi_info_shapes, gamma=0.99, lam=0.95, cost_gamma=0.99, cost_lam=0.95):
         """cpobuffer.py:79-97."""
@@ -80,6 +90,9 @@ class CPOBuffer:
         self.arch_dict["pi_infos"] = self.pi_info_archive
         self.sorted_pi_info_keys = sorted(pi_info_shapes.keys())
         self.gamma, self.lam, self.cost_gamma, self.cost_lam = gamma, lam, cost_gamma, cost_lam
+        if self._dev is not None:       # (the pi_info archives were just replaced)
+            self._dev = None
+            self.enable_device_archive()
 
     # convenient views with the reference's attribute names
     @property
@@ -162,6 +175,8 @@ class CPOBuffer:
                     a[kk][dst] = self.pi_info_bufs[kk][:self.ptr]
             else:
                 a[dst] = self.buf_dict[k][:self.ptr]
+        if self._dev is not None:
+            self._mirror(dst)
         self.archive_ptr += self.ptr
         self.max_pointer = max(self.archive_ptr, self.max_pointer)
 
@@ -231,3 +246,194 @@ class CPOBuffer:
             return None
         idx = np.array([np.random.choice(np.flatnonzero(self.epoch_archive == e), size=batch_size) for e in epochs])
         return self._take(idx, fields)
+
+    # -- device mirror of the archive and start-state sampling on it (csrc/start_states.hip) ------------
+    _MIRRORED = ("observations", "mu", "log_std", "epochs")
+
+    def _host_column(self, k):
+        return self.pi_info_archive[k] if k in ("mu", "log_std") else self.arch_dict[k]
+
+    def enable_device_archive(self):
+        """Allocate the device mirror of the columns start-state sampling reads -- observations [archive_size, obs],
+        mu / log_std [archive_size, A] float32, epochs [archive_size] int32 (-1 = empty) -- and fill it from the host
+        archive.  From here on ``dump_to_archive`` appends every slab to it and ``reset_arch`` resets it."""
+        if self._dev is not None:
+            return
+        if not self.pi_info_shapes or sorted(self.pi_info_shapes) != ["log_std", "mu"]:
+            raise _lib.CmbpoHipError("enable_device_archive: initialize() the buffer with the Gaussian pi_info "
+                                     "{mu, log_std} first")
+        if self.archive_size > 2 ** 31 - 1:
+            raise _lib.CmbpoHipError("enable_device_archive: archive indices are int32")
+        n, dev = self.archive_size, self.device
+        self._dev = {k: torch.empty((n,) + self._host_column(k).shape[1:], device=dev,
+                                    dtype=torch.int32 if k == "epochs" else torch.float32) for k in self._MIRRORED}
+        self._dev_version = 0          # bumped by every write to the mirror; the run table is rebuilt when it lags
+        self._table_version = -1
+        self._table = torch.zeros(_lib.START_TABLE_INTS, dtype=torch.int32, device=dev)
+        self._cdf = torch.zeros(_lib.START_CDF_DOUBLES, dtype=torch.float64, device=dev)
+        self._start_scratch = {}
+        self.start_generator = torch.Generator(device=dev)     # the uniforms of sample_start_states
+        self.start_generator.manual_seed(0)
+        self.last_start = {}
+        self._mirror(slice(0, n))
+
+    def _mirror(self, dst):
+        for k in self._MIRRORED:
+            h = self._host_column(k)[dst]
+            if k == "epochs":
+                h = h.astype(np.int32)
+            self._dev[k][dst].copy_(torch.from_numpy(np.ascontiguousarray(h)))
+        self._dev_version += 1
+
+    def device_archive(self):
+        """The mirror's tensors by column name (enabled on first use)."""
+        self.enable_device_archive()
+        return self._dev
+
+    def _start_table(self):
+        """The run table of the mirrored epoch column, rebuilt only after the archive changed; its epochs present and
+        their sample counts are read back once per rebuild (the only host read of the path)."""
+        self.enable_device_archive()
+        if self._table_version != self._dev_version:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().cmbpo_start_table_build(self._dev["epochs"].data_ptr(), self.archive_size,
+                                                               self._table.data_ptr(), _lib.current_stream()),
+                           "cmbpo_start_table_build")
+                t = self._table.cpu().numpy()
+                void = float(self._cdf[1].item())       # (a synchronising read: taken here, once per archive change)
+                self._cdf[1] = 0.0
+            if void:
+                raise _lib.CmbpoHipError("start states: a round since the last archive change had no finite Boltzmann "
+                                         "mass (NaN or infinite policy KL): its start states are void")
+            M = _lib.START_MAX_RUNS
+            if t[2]:
+                raise _lib.CmbpoHipError("start-state table: the archive's epoch column has more than %d runs of equal "
+                                         "tags (epochs are expected in contiguous slabs)" % M)
+            n_ep = int(t[1])
+            self._start_info = dict(n_runs=int(t[0]), n_epochs=n_ep, filled=int(t[3]),
+                                    epochs=t[8 + 3 * M:8 + 3 * M + n_ep].astype(np.int64),
+                                    counts=t[8 + 4 * M:8 + 4 * M + n_ep].astype(np.int64),
+                                    run_start=t[8:8 + int(t[0])].copy(), run_len=t[8 + M:8 + M + int(t[0])].copy())
+            self._table_version = self._dev_version
+        return self._start_info
+
+    def _scratch(self, name, shape, dtype):
+        """Scratch tensors live until a call asks for another shape (a new batch size reallocates)."""
+        t = self._start_scratch.get(name)
+        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+            t = torch.zeros(shape, dtype=dtype, device=self.device)
+            self._start_scratch[name] = t
+        return t
+
+    def _uniforms(self, shape, u):
+        if u is None:
+            return torch.rand(shape, generator=self.start_generator, dtype=torch.float64, device=self.device)
+        if isinstance(u, torch.Tensor):
+            t = u.to(device=self.device, dtype=torch.float64).contiguous()
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(u, dtype=np.float64)).to(self.device)
+        if tuple(t.shape) != tuple(shape):
+            raise _lib.CmbpoHipError("start states: uniforms of shape %r, expected %r" % (tuple(t.shape), tuple(shape)))
+        return t
+
+    def device_epoch_batch(self, batch_size, epochs=None, u=None):
+        """``epoch_batch`` (cpobuffer.py:466-524) on the mirror: for every epoch (default: all present, ascending)
+        ``batch_size`` members drawn with the uniforms ``u`` [n_epochs, batch_size] (float64 in [0, 1); drawn from
+        ``start_generator`` when None) as ``members_e[min(floor(u n_e), n_e - 1)]``.  Returns device tensors
+        ``idx`` [n_epochs, B] int32 and ``observations`` / ``mu`` / ``log_std`` [n_epochs, B, .]."""
+        info = self._start_table()
+        if info["n_epochs"] == 0:
+            raise _lib.CmbpoHipError("start states: the archive is empty")
+        B, dev = int(batch_size), self.device
+        if B < 1:
+            raise _lib.CmbpoHipError("start states: batch_size %d" % B)
+        sel = None
+        if epochs is not None:
+            assert len(np.shape(epochs)) == 1
+            ep = np.array(epochs)
+            if np.any(ep > info["epochs"][-1]) or np.any(ep < info["epochs"][0]):
+                print('Warning: epoch not contained in buffer.')
+                return None
+            place = np.searchsorted(info["epochs"], ep)
+            if np.any(info["epochs"][np.minimum(place, info["n_epochs"] - 1)] != ep):
+                raise _lib.CmbpoHipError("start states: epoch without samples in the archive")
+            sel = torch.from_numpy(place.astype(np.int32)).to(dev)
+        E = info["n_epochs"] if sel is None else int(sel.numel())
+        D, A = self._dev["observations"].shape[1], self._dev["mu"].shape[1]
+        with torch.cuda.device(dev):
+            ut = self._uniforms((E, B), u)
+            out = dict(idx=self._scratch("idx_epoch", (E, B), torch.int32),
+                       observations=self._scratch("obs_epoch", (E, B, D), torch.float32),
+                       mu=self._scratch("mu_epoch", (E, B, A), torch.float32),
+                       log_std=self._scratch("ls_epoch", (E, B, A), torch.float32))
+            _lib.check(_lib.lib().cmbpo_start_epoch_draw(
+                self._table.data_ptr(), _lib.ptr(sel), E, B, ut.data_ptr(), self._dev["observations"].data_ptr(),
+                self._dev["mu"].data_ptr(), self._dev["log_std"].data_ptr(), self.archive_size, D, A,
+                out["idx"].data_ptr(), out["observations"].data_ptr(), out["mu"].data_ptr(), out["log_std"].data_ptr(),
+                _lib.current_stream()), "cmbpo_start_epoch_draw")
+        return out
+
+    def device_epoch_kl(self, policy, ep_b, alpha=1):
+        """``np.clip(policy.compute_DKL(...), 0)`` (cmbpo.py:220, cpo_policy.py:837-845) on the rows of
+        ``device_epoch_batch``: the actor's forward pass, the per-row KL(current || stored) with ordered float64 sums, and
+        -- in the same launch that folds them -- the Boltzmann CDF for ``alpha`` that ``device_boltz_draw`` searches.
+        Returns the device tensor kl [n_epochs] float64."""
+        obs, mu_old, ls_old = ep_b["observations"], ep_b["mu"], ep_b["log_std"]
+        E, B, A = mu_old.shape
+        if E != self._start_table()["n_epochs"]:
+            raise _lib.CmbpoHipError("start states: the KL needs a batch of every epoch present")
+        lib, dev = _lib.lib(), self.device
+        with torch.cuda.device(dev):
+            n_part = lib.cmbpo_start_kl_parts(B)
+            o = {k: self._scratch("pi_" + k, (E * B, A), torch.float32) for k in ("pi", "mu", "log_std", "eps")}
+            o["logp_pi"] = self._scratch("pi_logp", (E * B,), torch.float32)
+            part = self._scratch("kl_part", (E, n_part), torch.float64)
+            kl = self._scratch("kl", (E,), torch.float64)
+            policy.actor.forward_device(obs.view(E * B, -1), o["eps"], o)     # (eps stays zero: pi = mu, unused)
+            _lib.check(lib.cmbpo_start_kl_partials(o["mu"].data_ptr(), o["log_std"].data_ptr(), mu_old.data_ptr(),
+                                                   ls_old.data_ptr(), E, B, A, part.data_ptr(), n_part,
+                                                   _lib.current_stream()), "cmbpo_start_kl_partials")
+            _lib.check(lib.cmbpo_start_cdf(self._table.data_ptr(), part.data_ptr(), n_part, B, kl.data_ptr(), float(alpha),
+                                           self._cdf.data_ptr(), _lib.current_stream()), "cmbpo_start_cdf")
+        return kl
+
+    def device_boltz_draw(self, batch_size, u=None, out=None, kls=None, alpha=1):
+        """``boltz_dist`` + ``distributed_batch_from_archive`` (cpobuffer.py:385-396,413-464) on the mirror: ``batch_size``
+        archive rows drawn as ``searchsorted(cdf, u, side='right')`` and their observations written into ``out``
+        [B, obs] (allocated when None).  ``kls`` [n_epochs] (host or device, already clipped) rebuilds the CDF for
+        ``alpha`` first; None uses the one ``device_epoch_kl`` left.  Returns (out, idx [B] int32), device tensors."""
+        info = self._start_table()
+        if info["n_epochs"] == 0:
+            raise _lib.CmbpoHipError("start states: the archive is empty")
+        B, dev, lib = int(batch_size), self.device, _lib.lib()
+        D = self._dev["observations"].shape[1]
+        with torch.cuda.device(dev):
+            if kls is not None:
+                k = self._uniforms((info["n_epochs"],), kls)
+                _lib.check(lib.cmbpo_start_cdf(self._table.data_ptr(), None, 0, 0, k.data_ptr(), float(alpha),
+                                               self._cdf.data_ptr(), _lib.current_stream()), "cmbpo_start_cdf")
+            ut = self._uniforms((B,), u)
+            if out is None:
+                out = self._scratch("start_obs", (B, D), torch.float32)
+            if not (isinstance(out, torch.Tensor) and out.device == ut.device and out.dtype == torch.float32
+                    and tuple(out.shape) == (B, D) and out.is_contiguous()):
+                raise _lib.CmbpoHipError("start states: `out` must be a contiguous float32 [%d, %d] tensor on %s" % (B, D, dev))
+            idx = self._scratch("idx_draw", (B,), torch.int32)
+            _lib.check(lib.cmbpo_start_boltz_draw(self._table.data_ptr(), self._cdf.data_ptr(), ut.data_ptr(), B,
+                                                  self._dev["observations"].data_ptr(), self.archive_size, D,
+                                                  idx.data_ptr(), out.data_ptr(), _lib.current_stream()),
+                       "cmbpo_start_boltz_draw")
+        return out, idx
+
+    def sample_start_states(self, policy, batch_size, alpha=1, out=None, u_epoch=None, u_draw=None):
+        """Lines 239-251 of algorithms/cmbpo.py in five launches on the device: a batch of every archived epoch, the
+        current policy's mean KL to each, the Boltzmann distribution over the epochs, ``batch_size`` archive rows drawn
+        from it.  Their observations are written into ``out`` (e.g. the rollout state's ``cur_obs``) and returned.  The
+        uniforms come from ``start_generator`` unless handed in (``u_epoch`` [n_epochs, B], ``u_draw`` [B], float64 in
+        [0, 1)).  ``last_start`` keeps the device tensors of the round (epoch-batch indices, KLs, drawn indices)."""
+        ep_b = self.device_epoch_batch(batch_size, u=u_epoch)
+        kl = self.device_epoch_kl(policy, ep_b, alpha=alpha)
+        out, idx = self.device_boltz_draw(batch_size, u=u_draw, out=out)
+        self.last_start = dict(idx_epoch=ep_b["idx"], kl=kl, idx=idx,
+                               ep_probs=self._cdf[8 + 3 * _lib.START_MAX_RUNS:][:kl.numel()])
+        return out

@@ -144,16 +144,26 @@ class ModelSampler:
                                                   idx.data_ptr(), None, n, t[key].data_ptr(), stream),
                        "cmbpo_ens_predict_mean")
 
-    def reset(self, observations):
-        """model_sampler.py:203-237: start all branches from `observations` [B, obs]."""
-        self.batch_size = int(observations.shape[0])
+    def reset(self, observations, fill=None, batch_size=None):
+        """model_sampler.py:203-237: start all branches from `observations` [B, obs].  With `observations` None,
+        `fill(cur_obs)` writes the `batch_size` start states into the rollout state's own [B, obs] device tensor
+        (CPOBuffer.sample_start_states: no staging copy)."""
+        if observations is None:
+            if fill is None or batch_size is None:
+                raise ValueError("reset(None) needs fill= and batch_size=")
+            self.batch_size = int(batch_size)
+        else:
+            self.batch_size = int(observations.shape[0])
         self.policy.reset()
         pool = self.pool
         with torch.cuda.device(self.device):
             pool.reset(self.batch_size)
-            obs = observations if isinstance(observations, torch.Tensor) else \
-                torch.from_numpy(np.ascontiguousarray(observations, dtype=np.float32))
-            pool.t["cur_obs"].copy_(obs.to(self.device, torch.float32))
+            if observations is None:
+                fill(pool.t["cur_obs"])
+            else:
+                obs = observations if isinstance(observations, torch.Tensor) else \
+                    torch.from_numpy(np.ascontiguousarray(observations, dtype=np.float32))
+                pool.t["cur_obs"].copy_(obs.to(self.device, torch.float32))
             pool.rs.max_path_length = self._max_path_length
             pool.rs.uncertainty_mode = 1 if self.rollout_mode == "uncertainty" else 0
             pool.rs.dkl_lim = float(self.dkl_lim)

@@ -517,6 +517,50 @@ int cmbpo_trainer_losses(cmbpo_trainer_t *t, const float *d_inputs, int in_dim,
                          int idx_stride, int n_rows, float *d_losses, void *stream);
 long cmbpo_trainer_steps_done(const cmbpo_trainer_t *t);
 
+/* ---- start states of an imagined-rollout round (csrc/start_states.hip) -----
+ * algorithms/cmbpo.py:239-251 on a device mirror of CPOBuffer's archive: observations [n][obs_dim],
+ * mu / log_std [n][act_dim] float32 and the epoch column int32 [n] (-1 = empty slot).  The epoch
+ * column is a few runs of equal tags (one slab per CPOBuffer.get, split by a wrap-around); every
+ * entry works on the run table of cmbpo_start_table_build, never on the [n] column.  d_table is
+ * int32[CMBPO_START_TABLE_INTS]: [0] runs, [1] epochs present, [2] != 0 if the column has more
+ * than CMBPO_START_MAX_RUNS runs (the table is then unusable), [3] filled slots; from
+ * [8 + 3 * MAX_RUNS] the sorted epochs present (epochs_list, buffers/cpobuffer.py:148-153), from
+ * [8 + 4 * MAX_RUNS] their sample counts (np.bincount). */
+#define CMBPO_START_MAX_RUNS 1024
+#define CMBPO_START_TABLE_INTS (8 + 11 * CMBPO_START_MAX_RUNS)
+#define CMBPO_START_CDF_DOUBLES (8 + 4 * CMBPO_START_MAX_RUNS)
+int cmbpo_start_table_build(const int32_t *d_epochs, long n, int32_t *d_table, void *stream);
+/* CPOBuffer.epoch_batch (buffers/cpobuffer.py:466-524) with the uniforms handed in: row e * batch + b
+ * is member min(floor(d_u[e][b] * n_e), n_e - 1) of np.flatnonzero(epoch_archive == epochs_list[e]);
+ * d_idx gets the archive indices, the three outputs the drawn rows ([n_epochs * batch][.]).
+ * d_epoch_sel (may be NULL) makes group e the epoch at place d_epoch_sel[e] of epochs_list. */
+int cmbpo_start_epoch_draw(const int32_t *d_table, const int32_t *d_epoch_sel, int n_epochs, int batch, const double *d_u,
+                           const float *d_obs, const float *d_mu, const float *d_logstd, long n,
+                           int obs_dim, int act_dim, int32_t *d_idx, float *d_obs_out, float *d_mu_out,
+                           float *d_logstd_out, void *stream);
+/* CPOPolicy.compute_DKL (policies/cpo_policy.py:837-845) after the actor's forward pass on the
+ * gathered rows: gaussian_kl(current, stored) per row (network/ac_network.py:50-55), summed in
+ * float64 per workgroup in a fixed order into d_part[n_epochs][n_part], n_part =
+ * cmbpo_start_kl_parts(batch); cmbpo_start_cdf folds them. */
+int cmbpo_start_kl_parts(int batch);
+int cmbpo_start_kl_partials(const float *d_mu, const float *d_logstd, const float *d_mu_old,
+                            const float *d_logstd_old, int n_epochs, int batch, int act_dim,
+                            double *d_part, int n_part, void *stream);
+/* np.clip(kls, 0) (algorithms/cmbpo.py:220), CPOBuffer.boltz_dist (buffers/cpobuffer.py:385-396) and
+ * the normalised float64 cumulative sum np.random.choice(p=) searches (:454), per run.  d_part != NULL:
+ * d_kl[e] = max(sum_k d_part[e][k] / batch, 0) is written; NULL: d_kl is read.  d_cdf is
+ * double[CMBPO_START_CDF_DOUBLES]: [0] the unnormalised total, [1] set to 1 (never cleared here) when
+ * it is not a positive finite number -- a NaN KL, no mass: draws from such a CDF are void --, from
+ * [8 + 3 * MAX_RUNS] the epochs' Boltzmann probabilities. */
+int cmbpo_start_cdf(const int32_t *d_table, const double *d_part, int n_part, int batch, double *d_kl,
+                    double alpha, double *d_cdf, void *stream);
+/* CPOBuffer.distributed_batch_from_archive (buffers/cpobuffer.py:413-464) with the uniforms handed in:
+ * d_idx[b] = cdf.searchsorted(d_u[b], side='right'), row d_idx[b] of d_obs -> d_out[b] (the rollout
+ * state's cur_obs). */
+int cmbpo_start_boltz_draw(const int32_t *d_table, const double *d_cdf, const double *d_u, int batch,
+                           const float *d_obs, long n, int obs_dim, int32_t *d_idx, float *d_out,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif
