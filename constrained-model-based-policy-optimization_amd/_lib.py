@@ -16,6 +16,7 @@ HEAD_PROB, HEAD_DETMEAN, HEAD_GAUSS_PI = 0, 1, 2
 LOSS_DEFAULT, LOSS_NLL = 0, 1      # cmbpo_trainer_set_loss
 ENS_FP32, ENS_SPLIT_BF16, ENS_SPLIT_F16 = 0, 1, 2    # cmbpo_set_ens_matrix_path
 TASK_DEFAULT, TASK_HCS, TASK_ANTSAFE = 0, 1, 2
+TASK_LEARNED_COST = 0x100     # CMBPO_TASK_LEARNED_COST: flag bit or-ed into a rule id (learned cost head)
 
 # models/statics.py:56-69 -- task name -> rule id
 TASK_IDS = {
@@ -148,6 +149,7 @@ SIGNATURES.update({
     "cmbpo_trainer_epoch": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
     "cmbpo_trainer_losses": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _p, _p]),
     "cmbpo_trainer_steps_done": (C.c_long, [_p]),
+    "cmbpo_trainer_f16_paths": (_i, [_p]),
 })
 
 # start states of an imagined-rollout round (csrc/start_states.hip)

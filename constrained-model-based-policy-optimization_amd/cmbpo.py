@@ -8,8 +8,12 @@ behind the other modules of this package; imagined samples stay on the device fr
 (``ModelBuffer.get(as_tensors=True)``), the real samples of an epoch are uploaded once.
 
 Differences from the reference, all outside the numerics: gtimer stamps are a plain ``time.perf_counter`` dict; the
-logger is the in-memory ``logger.EpochLogger``; ``m_learn_cost`` (a learned cost head) is not supported, as in
-``fake_env.FakeEnv``.
+logger is the in-memory ``logger.EpochLogger``.
+
+``m_learn_cost=True`` (``algorithms/cmbpo.py:46,123``) gives the dynamics ensemble one more output column trained on the
+real costs (``format_samples_for_dyn(append_c=True)``, ``:470``) and has ``FakeEnv`` take the cost of an imagined sample
+from it (``predicts_cost=True``, ``:137-142``) instead of the task's cost rule: the only way an imagined sample of a
+task without such a rule carries a cost at all.
 """
 import time
 import warnings
@@ -63,8 +67,6 @@ class CMBPO:
                  n_epochs=int(10e7), n_initial_exploration_steps=0, initial_exploration_policy=None, epoch_length=1000,
                  model_train_kwargs=None, initial_model_train_kwargs=None, shuffle_on_device=True, device=None,
                  session=None, start_state_sampling='host', **_unused):
-        if m_learn_cost:
-            raise NotImplementedError("m_learn_cost: the learned cost head is unused by every shipped config")
         # RLAlgorithm.__init__ (algorithms/rl_algorithm.py:22-74)
         self.sampler = sampler if sampler is not None else CpoSampler(max_path_length=getattr(policy, "max_path_length", 1000))
         self._n_epochs, self._epoch_length = n_epochs, epoch_length
@@ -88,6 +90,7 @@ class CMBPO:
         self._buffer.initialize(pi_info_shapes, gamma=policy.gamma, lam=policy.lam, cost_gamma=policy.cost_gamma,
                                 cost_lam=policy.cost_lam)
         self._use_model = use_model
+        self._m_learn_cost = bool(m_learn_cost)
         self._m_train_freq = m_train_freq
         self._rollout_batch_size = int(rollout_batch_size)
         self._rollout_schedule = list(rollout_schedule)
@@ -107,12 +110,14 @@ class CMBPO:
         self._start_state_sampling = start_state_sampling
 
         if use_model:
-            self._model = build_PE(in_dim=self.obs_dim + self.act_dim, out_dim=self.obs_dim + 1, name='DynEns',
-                                   loss=m_loss_type, hidden_dims=m_hidden_dims, lr=m_lr, num_networks=m_networks,
-                                   num_elites=m_elites, use_scaler_in=m_use_scaler_in, use_scaler_out=m_use_scaler_out,
-                                   decay=1e-6, max_logvar=.5, min_logvar=-10, device=self.device)
+            # outputs: delta-obs | reward (| cost, with the learned cost head: algorithms/cmbpo.py:121-123)
+            self._model = build_PE(in_dim=self.obs_dim + self.act_dim, out_dim=self.obs_dim + 1 + int(self._m_learn_cost),
+                                   name='DynEns', loss=m_loss_type, hidden_dims=m_hidden_dims, lr=m_lr,
+                                   num_networks=m_networks, num_elites=m_elites, use_scaler_in=m_use_scaler_in,
+                                   use_scaler_out=m_use_scaler_out, decay=1e-6, max_logvar=.5, min_logvar=-10,
+                                   device=self.device)
             self.fake_env = FakeEnv(true_environment=env, task=self._task, model=self._model, predicts_delta=True,
-                                    predicts_rew=True, predicts_cost=False)
+                                    predicts_rew=True, predicts_cost=self._m_learn_cost)
             self.rollout_mode = rollout_mode
             self.model_buf = ModelBuffer(batch_size=self._rollout_batch_size, obs_dim=self.obs_dim, act_dim=self.act_dim,
                                          max_path_length=maxroll, device=self.device)
@@ -169,7 +174,7 @@ class CMBPO:
         """algorithms/cmbpo.py:455-486"""
         model_samples = self._buffer.get_archive(['observations', 'actions', 'next_observations', 'rewards', 'costs',
                                                   'terminals', 'epochs'])
-        dyn_ins, dyn_outs = format_samples_for_dyn(model_samples, append_r=True, append_c=False)
+        dyn_ins, dyn_outs = format_samples_for_dyn(model_samples, append_r=True, append_c=self._m_learn_cost)
         return self._model.train(dyn_ins, dyn_outs, batch_size=batch_size, max_epochs=max_epochs,
                                  min_epoch_before_break=min_epochs, holdout_ratio=0.2, max_t=self._max_model_t,
                                  shuffle_on_device=self._shuffle_on_device)

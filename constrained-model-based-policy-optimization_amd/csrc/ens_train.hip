@@ -2415,3 +2415,8 @@ extern "C" int cmbpo_trainer_losses(cmbpo_trainer_t *t, const float *d_inputs, i
 }
 
 extern "C" long cmbpo_trainer_steps_done(const cmbpo_trainer_t *t) { return t ? t->step : -1; }
+
+extern "C" int cmbpo_trainer_f16_paths(const cmbpo_trainer_t *t) {
+  if (!t) return -1;
+  return (t->b16 ? 1 : 0) | (t->b16 && t->b16_fwd ? 2 : 0);
+}

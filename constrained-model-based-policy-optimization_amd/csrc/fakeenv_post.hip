@@ -22,6 +22,7 @@ constexpr int kEMax = kEMaxRt;
 
 struct PostArgs {
   int task, ensemble, obs_dim, act_dim, out_dim;
+  int learned_cost;   // 1: cost = column obs_dim + 1 of the elite member (fake_env.py:139-143), the task's cost rule is skipped
   const float *mean, *var;
   int ld_rows;
   const float *obs, *act;
@@ -249,6 +250,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
       const float xdist = __fmul_rn(nx[D - 1], 10.0f);
       cost = (fabsf(xdist) < 2.0f) ? 1.0f : 0.0f;
     }
+    // learned cost head (fake_env.py:139-143, predicts_cost=True): the elite member's mean of the last column, stored as it is;
+    // the termination rule above still applies (TERMS_BY_TASK does not depend on predicts_cost).  A branch uniform over the
+    // launch, taken by one lane per row: as a template parameter it would double the instances for one load.
+    if (p.learned_cost) cost = p.mean[me * mstride + (size_t)r * p.out_dim + D + 1];
     p.term[r] = done;
     p.cost[r] = cost;
   }
@@ -263,7 +268,10 @@ extern "C" int cmbpo_fakeenv_post(int task, int ensemble, int obs_dim, int act_d
                                   float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost,
                                   float *d_dkl_path, float *d_ep_var_mean, float *d_ep_var,
                                   void *stream) {
-  CMBPO_REQUIRE(task >= CMBPO_TASK_DEFAULT && task <= CMBPO_TASK_ANTSAFE, "cmbpo_fakeenv_post: bad task %d", task);
+  const int learned_cost = (task & CMBPO_TASK_LEARNED_COST) ? 1 : 0;     // every other bit outside the rule id is an error
+  const int task_arg = task;
+  task &= ~CMBPO_TASK_LEARNED_COST;
+  CMBPO_REQUIRE(task >= CMBPO_TASK_DEFAULT && task <= CMBPO_TASK_ANTSAFE, "cmbpo_fakeenv_post: bad task %d", task_arg);
   CMBPO_REQUIRE(ensemble >= 2 && ensemble <= kEMax, "cmbpo_fakeenv_post: ensemble %d not in [2, %d]", ensemble, kEMax);
   CMBPO_REQUIRE(obs_dim >= 1 && obs_dim <= 512 && act_dim >= 0, "cmbpo_fakeenv_post: bad dims");
   if (task == CMBPO_TASK_ANTSAFE)
@@ -275,7 +283,8 @@ extern "C" int cmbpo_fakeenv_post(int task, int ensemble, int obs_dim, int act_d
   if (n_rows == 0) return CMBPO_OK;
   PostArgs a{};
   a.task = task; a.ensemble = ensemble; a.obs_dim = obs_dim; a.act_dim = act_dim;
-  a.out_dim = obs_dim + 1;  // delta-obs + reward (algorithms/cmbpo.py:121-123, m_learn_cost=False)
+  a.out_dim = obs_dim + 1 + learned_cost;  // delta-obs + reward (+ cost: algorithms/cmbpo.py:121-123, m_learn_cost)
+  a.learned_cost = learned_cost;
   a.mean = d_mean; a.var = d_var; a.ld_rows = ld_rows; a.obs = d_obs; a.act = d_act;
   a.elite = d_elite; a.row_idx = d_row_idx; a.n_rows_dev = d_n_rows; a.n_rows = n_rows;
   a.next_obs = d_next_obs; a.rew = d_rew; a.term = d_term; a.cost = d_cost;

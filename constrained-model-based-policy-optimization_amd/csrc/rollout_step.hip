@@ -38,6 +38,10 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
                      const Ahead &ahead, void *stream) {
   CMBPO_REQUIRE(r && policy && model && v && vc && d_eps && d_elite && d_mean && d_var, "cmbpo_rollout_step: NULL argument");
   CMBPO_REQUIRE(n_alive >= 1 && n_alive <= r->B, "cmbpo_rollout_step: n_alive %d not in [1, B=%d]", n_alive, r->B);
+  // the scratch rows are as wide as the model's output: a learned-cost flag that does not match the model would read the wrong columns
+  CMBPO_REQUIRE(model->out_dim == r->obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0),
+                "cmbpo_rollout_step: model out_dim %d does not match obs_dim %d + 1 (+ 1 with CMBPO_TASK_LEARNED_COST), task 0x%x",
+                model->out_dim, r->obs_dim, task);
   // the per-step arrays are inputs of the bookkeeping kernels (const in the struct) and outputs of the forward passes
   auto w = [](const float *p) { return const_cast<float *>(p); };
   int rc;

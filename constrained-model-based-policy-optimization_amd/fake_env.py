@@ -8,9 +8,13 @@ Differences that are part of the contract:
   * the per-branch elite draw (``random_inds``, :174-178, global NumPy RNG) can be injected through
     ``model_inds=`` so a test / a sharded run can reproduce it; by default it is drawn with a
     seeded ``numpy.random.Generator`` owned by this object;
-  * ``deterministic=False`` (mean + std, :105-106), the 3-D input path (:84-101, unused by the
-    trainer and not an inverse) and learned costs (``predicts_cost``,
-    ``m_learn_cost=False`` in every config) raise NotImplementedError.
+  * ``deterministic=False`` (mean + std, :105-106) and the 3-D input path (:84-101, unused by the
+    trainer and not an inverse) raise NotImplementedError.
+
+``predicts_cost=True`` (:139-143, ``m_learn_cost`` of the trainer) takes the cost of a branch from the
+elite member's mean of the model's last output column (``output_dim == obs_dim + 2``) instead of the
+task's cost rule; the task's termination rule still applies.  ``info['cost']`` is then the float32
+prediction, not thresholded.
 """
 import numpy as np
 import torch
@@ -30,14 +34,18 @@ class FakeEnv:
         self._is_probabilistic = model.is_probabilistic
         if not (self._uses_ensemble and self._is_probabilistic):
             raise NotImplementedError("the HIP path needs a probabilistic ensemble (all CMBPO configs)")
-        if not (predicts_delta and predicts_rew) or predicts_cost:
-            raise NotImplementedError("HIP path: predicts_delta=True, predicts_rew=True, predicts_cost=False "
-                                      "(algorithms/cmbpo.py:137-142)")
-        self._predicts_delta, self._predicts_rew, self._predicts_cost = True, True, False
+        if not (predicts_delta and predicts_rew):
+            raise NotImplementedError("HIP path: predicts_delta=True, predicts_rew=True (algorithms/cmbpo.py:137-142)")
+        self._predicts_delta, self._predicts_rew, self._predicts_cost = True, True, bool(predicts_cost)
         self.input_dim = model.in_dim
         self.output_dim = model.out_dim
-        assert self.input_dim == self.obs_dim + self.act_dim and self.output_dim == self.obs_dim + 1
+        assert self.input_dim == self.obs_dim + self.act_dim
+        assert self.output_dim == self.obs_dim + 1 + int(self._predicts_cost)
+        # the `task` argument of the native entry points: the rule id, with the learned-cost flag where the model has the head
+        # (every caller that passes it -- this class, ModelSampler, the probes -- thereby runs the mode the scratch is sized for)
         self._task_id = _lib.TASK_IDS.get(task, _lib.TASK_DEFAULT)
+        if self._predicts_cost:
+            self._task_id |= _lib.TASK_LEARNED_COST
         self._rng = np.random.default_rng(seed)
         self.device = model.device
         # bench.py sets this to a list to collect (start, end) HIP events around the dominant kernel
@@ -60,7 +68,7 @@ class FakeEnv:
         """Device-resident step: all arguments are CUDA tensors indexed by branch slot.
 
         out: dict with next_obs[B,obs], rew[B], term[B] u8, cost[B], dkl_path[B], ep_var_mean[B]
-        (and optionally ep_var[B,obs]).  scratch: (mean, var)[E,B,obs+1].
+        (and optionally ep_var[B,obs]).  scratch: (mean, var)[E,B,output_dim].
         """
         B = obs.shape[0]
         n = B if row_idx is None else (row_idx.shape[0] if n_rows is None else n_rows)
@@ -120,7 +128,7 @@ class FakeEnv:
             self.step_device(o, a, inds, out)
         next_obs, r, terms = out["next_obs"], out["rew"][:, None], out["term"].bool()[:, None]
         c = out["cost"][:, None]
-        if self._task_id == _lib.TASK_DEFAULT:
+        if self._task_id == _lib.TASK_DEFAULT:      # (not with a learned cost: the float32 prediction is the cost)
             c = c.bool()  # np.zeros_like(terms) is a bool array (models/fake_env.py:145-146)
         dkl_path, ep_var = out["dkl_path"], out["ep_var"]
         dkl_mean = dkl_path.mean()

@@ -223,6 +223,11 @@ class EnsembleTrainer:
     def steps_done(self):
         return int(_lib.lib().cmbpo_trainer_steps_done(self._h))
 
+    @property
+    def f16_paths(self):
+        """Bit 0: the backward chain runs on the f16 kernels, bit 1: the training forward too (fixed by the shapes)."""
+        return int(_lib.lib().cmbpo_trainer_f16_paths(self._h))
+
 
 def _to_dev(x, device):
     """(tensor on device, was_numpy)."""

@@ -47,6 +47,12 @@ extern "C" {
 #define CMBPO_TASK_DEFAULT 0  /* no_done, zero (bool) cost: Hopper/Humanoid */
 #define CMBPO_TASK_HCS 1      /* HalfCheetahSafe-v2: no_done + hcs_cost_f    */
 #define CMBPO_TASK_ANTSAFE 2  /* AntSafe-v2: antsafe_term_fn + antsafe_c_fn  */
+/* Flag bit, or-ed into the `task` argument of cmbpo_fakeenv_post / cmbpo_rollout_step / cmbpo_rollout_run: the model has a
+ * learned cost head (algorithms/cmbpo.py:46,123 m_learn_cost; models/fake_env.py:139-151 predicts_cost).  (mean, var) are
+ * then [E, ld_rows, obs + 2], the cost is column obs + 1 of the elite member's mean (stored as it is, non-finite values
+ * included), the reward column obs; the task's termination rule still applies, its cost rule does not.  Any other bit
+ * outside the rule id is rejected. */
+#define CMBPO_TASK_LEARNED_COST 0x100
 
 const char *cmbpo_last_error(void);
 int cmbpo_version(void);
@@ -161,7 +167,8 @@ int cmbpo_policy_forward(cmbpo_mlp_t *m, const float *d_obs, int obs_dim,
  * (obs, act, next_obs).  d_elite is the per-row member index (the draw of
  * models/fake_env.py:174-178, injected by the caller).  Row addressing as in
  * cmbpo_ens_forward.  d_cost is float (bool cast for the default task),
- * d_term is uint8.  d_ep_var_mean = mean over obs dims of ens_ep_var (what
+ * d_term is uint8.  d_mean / d_var are [E, ld_rows, obs + 1], or
+ * [E, ld_rows, obs + 2] with CMBPO_TASK_LEARNED_COST set in `task`.  d_ep_var_mean = mean over obs dims of ens_ep_var (what
  * samplers/model_sampler.py:322,343 consume); d_ep_var [.,obs_dim] optional. */
 int cmbpo_fakeenv_post(int task, int ensemble, int obs_dim, int act_dim,
                        const float *d_mean, const float *d_var, int ld_rows,
@@ -280,7 +287,7 @@ int cmbpo_rollout_compact(const cmbpo_rollout_t *r, void *stream);
 /* The whole step in one call (single-GPU jobs without a cross-shard budget exchange): cmbpo_policy_forward ->
  * cmbpo_ens_forward -> cmbpo_fakeenv_post -> decide -> finish(PRE) -> store -> cmbpo_ens_predict_mean x 2 at next_obs ->
  * finish(POST), every buffer taken from *r (slot-indexed d_eps [B, act], d_elite [B]; scratch d_mean / d_var
- * [E, B, obs + 1]).  n_alive = the host's copy of iscal[CMBPO_I_N_ALIVE]. */
+ * [E, B, model out_dim]: obs + 1, or obs + 2 with CMBPO_TASK_LEARNED_COST in `task`).  n_alive = the host's copy of iscal[CMBPO_I_N_ALIVE]. */
 /* Small rollout batches: decide + finish(PRE) + store (+ its statistics) as one single-workgroup launch for up to
  * cmbpo_rollout_book_pre_max_rows() alive rows (same decisions and per-branch arithmetic as the separate calls;
  * single-rank path).  cmbpo_rollout_step uses it by itself. */
@@ -516,6 +523,9 @@ int cmbpo_trainer_losses(cmbpo_trainer_t *t, const float *d_inputs, int in_dim,
                          const float *d_targets, int target_dim, const int32_t *d_idx,
                          int idx_stride, int n_rows, float *d_losses, void *stream);
 long cmbpo_trainer_steps_done(const cmbpo_trainer_t *t);
+/* Which kernels a training step of this trainer runs: bit 0 the f16 backward chain, bit 1 the f16 training forward
+ * (0: the fp32 kernels; -1: NULL handle).  Fixed at creation by the network's shapes. */
+int cmbpo_trainer_f16_paths(const cmbpo_trainer_t *t);
 
 /* ---- start states of an imagined-rollout round (csrc/start_states.hip) -----
  * algorithms/cmbpo.py:239-251 on a device mirror of CPOBuffer's archive: observations [n][obs_dim],
