@@ -17,8 +17,13 @@ LOSS_DEFAULT, LOSS_NLL = 0, 1      # cmbpo_trainer_set_loss
 ENS_FP32, ENS_SPLIT_BF16, ENS_SPLIT_F16 = 0, 1, 2    # cmbpo_set_ens_matrix_path
 TASK_DEFAULT, TASK_HCS, TASK_ANTSAFE = 0, 1, 2
 TASK_LEARNED_COST = 0x100     # CMBPO_TASK_LEARNED_COST: flag bit or-ed into a rule id (learned cost head)
+TASK_USER_BASE, TASK_USER_SLOTS = 16, 64     # CMBPO_TASK_USER_BASE / _SLOTS: ids of registered rule tables (cmbpo_amd.statics)
+RULE_MAX_CLAUSES = 16
+RULE_HEALTHY, RULE_FATAL, RULE_COST = 0, 1, 2                     # clause roles
+RULE_SRC_NEXT_OBS, RULE_SRC_OBS, RULE_SRC_ACT = 0, 1, 2           # clause sources
+RULE_ABS, RULE_LO_STRICT, RULE_HI_STRICT, RULE_ANY = 1, 2, 4, 8   # clause flags
 
-# models/statics.py:56-69 -- task name -> rule id
+# models/statics.py:56-69 -- task name -> rule id (statics.register_task adds the names of registered rule tables)
 TASK_IDS = {
     "default": TASK_DEFAULT,
     "HalfCheetah-v2": TASK_DEFAULT,
@@ -51,6 +56,25 @@ SIGNATURES = {
                                 _p, _p, _p, _p, _p, _p, _p, _p]),
 }
 
+
+
+class RuleClauseStruct(C.Structure):
+    """ctypes image of ``cmbpo_rule_clause_t`` (32 bytes)."""
+    _fields_ = [(n, C.c_int32) for n in ("role", "src", "col0", "n_cols", "flags")] + \
+               [(n, C.c_float) for n in ("scale", "lo", "hi")]
+
+
+class TaskRulesStruct(C.Structure):
+    """ctypes image of ``cmbpo_task_rules_t`` (528 bytes)."""
+    _fields_ = [(n, C.c_int32) for n in ("n_clauses", "require_finite", "cost_on_term", "reserved")] + \
+               [("clause", RuleClauseStruct * RULE_MAX_CLAUSES)]
+
+
+SIGNATURES.update({
+    "cmbpo_task_rules_register": (_i, [C.POINTER(TaskRulesStruct), C.POINTER(C.c_int)]),
+    "cmbpo_task_rules_get": (_i, [_i, C.POINTER(TaskRulesStruct)]),
+    "cmbpo_task_rules_count": (_i, []),
+})
 
 
 class RolloutStruct(C.Structure):

@@ -14,6 +14,9 @@ logger is the in-memory ``logger.EpochLogger``.
 real costs (``format_samples_for_dyn(append_c=True)``, ``:470``) and has ``FakeEnv`` take the cost of an imagined sample
 from it (``predicts_cost=True``, ``:137-142``) instead of the task's cost rule: the only way an imagined sample of a
 task without such a rule carries a cost at all.
+
+``static_fns`` takes a ``statics.TaskRules``: user-defined termination / cost rules for the imagined rollouts, with
+precedence over ``task`` (which may itself be a name given to ``statics.register_task``).
 """
 import time
 import warnings
@@ -77,7 +80,12 @@ class CMBPO:
         self.obs_dim = int(np.prod(env.observation_space.shape))
         self.act_dim = int(np.prod(env.action_space.shape))
         self.n_env_interacts = n_env_interacts
+        if static_fns is not None:
+            from .statics import TaskRules
+            if not isinstance(static_fns, TaskRules):
+                raise TypeError("static_fns: a cmbpo_amd.statics.TaskRules, got %r" % (static_fns,))
         self._task = task
+        self._static_fns = static_fns
         self.eval_every_n_steps = eval_every_n_steps
         self._training_environment = env
         self._policy = policy
@@ -116,7 +124,8 @@ class CMBPO:
                                    num_networks=m_networks, num_elites=m_elites, use_scaler_in=m_use_scaler_in,
                                    use_scaler_out=m_use_scaler_out, decay=1e-6, max_logvar=.5, min_logvar=-10,
                                    device=self.device)
-            self.fake_env = FakeEnv(true_environment=env, task=self._task, model=self._model, predicts_delta=True,
+            rules_task = self._task if static_fns is None else static_fns      # static_fns takes precedence over the task name
+            self.fake_env = FakeEnv(true_environment=env, task=rules_task, model=self._model, predicts_delta=True,
                                     predicts_rew=True, predicts_cost=self._m_learn_cost)
             self.rollout_mode = rollout_mode
             self.model_buf = ModelBuffer(batch_size=self._rollout_batch_size, obs_dim=self.obs_dim, act_dim=self.act_dim,

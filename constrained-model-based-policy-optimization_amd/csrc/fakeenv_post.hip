@@ -7,9 +7,12 @@
 //   models/pens/utils.py:15-57   (gaussian_kl_np, average_dkl: all E*E ordered pairs, clip [0, 1e10])
 //   models/statics.py:3-53       (no_done, hcs_cost_f, antsafe_term_fn, antsafe_c_fn incl. the
 //                                 `a*b*c*z_rot >= -0.7` precedence quirk)
+// and, for a registered rule id (csrc/task_rules.hip), the user's clause table in place of the three built-in rule sets.
 #include "common.h"
 
 #include <math.h>
+
+#include <type_traits>
 
 namespace {
 
@@ -33,14 +36,22 @@ struct PostArgs {
   float *cost, *dkl_path, *ep_var_mean, *ep_var;
 };
 
+// RULES: the launch of a registered rule id carries its clause table behind the arguments, by value (528 bytes, uniform: scalar
+// loads from the kernel-argument segment) -- instances of their own, so the built-in tasks' kernels are what they were
+struct PostArgsRules : PostArgs {
+  cmbpo_task_rules_t rules;     // columns resolved on the host: col0 absolute, n_cols a count, all inside the source's width
+};
+template <bool RULES>
+using PostArgsT = std::conditional_t<RULES, PostArgsRules, PostArgs>;
+
 // np.clip(x, lo, hi): comparisons are false for a NaN, which therefore passes through (fminf / fmaxf would drop it)
 __device__ __forceinline__ float clip_np(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // EC: the ensemble size at compile time (0: read it at run time) -- with a run-time size the member loops are unrolled to
 // kEMax and masked: 56 pair terms computed and selected for the 42 that exist, a third more instructions
 #define POST_WAVES 5      // waves per SIMD the register allocation aims at (swept 4 / 5 / 6 / 8: 57.7 / 51.1 / 51.3 / 77.4 us at 100 k rows)
-template <int EC>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgs p) {
+template <int EC, bool RULES = false>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgsT<RULES> p) {
   extern __shared__ float sm[];
   const int D = p.obs_dim;
   float *s_dkl = sm;                  // [kRows][D]
@@ -228,6 +239,34 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
     for (int d = k; d < D; d += 8) fin = fin && isfinite(nx[d]);
     const unsigned long long okm = __ballot(fin);
     fin = ((okm >> (8 * rw)) & 0xffull) == 0xffull;
+    // The clause table (include/cmbpo_hip.h): a clause's columns go over the row's eight lanes like `fin`, one ballot per
+    // clause; the loop and every field of a clause are uniform over the launch.  All 64 lanes are still here (rows past the
+    // end read their stale LDS image and nothing from global memory; their result is dropped below).
+    [[maybe_unused]] bool rule_done = false, rule_obj = false;
+    if constexpr (RULES) {
+      for (int c = 0; c < p.rules.n_clauses; ++c) {
+        const cmbpo_rule_clause_t &cl = p.rules.clause[c];
+        const bool any = (cl.flags & CMBPO_RULE_ANY) != 0;
+        bool all_k = true, any_k = false;
+        for (int d = cl.col0 + k; d < cl.col0 + cl.n_cols; d += 8) {
+          float x = 0.0f;
+          if (cl.src == CMBPO_RULE_SRC_NEXT_OBS) x = nx[d];
+          else if (r >= 0) x = cl.src == CMBPO_RULE_SRC_OBS ? p.obs[(size_t)r * D + d] : p.act[(size_t)r * p.act_dim + d];
+          float f = __fmul_rn(x, cl.scale);
+          if (cl.flags & CMBPO_RULE_ABS) f = fabsf(f);
+          // positive tests: false for a NaN, like NumPy's comparisons
+          const bool lo_ok = (cl.flags & CMBPO_RULE_LO_STRICT) ? f > cl.lo : f >= cl.lo;
+          const bool hi_ok = (cl.flags & CMBPO_RULE_HI_STRICT) ? f < cl.hi : f <= cl.hi;
+          all_k = all_k && lo_ok && hi_ok;
+          any_k = any_k || (lo_ok && hi_ok);
+        }
+        const unsigned lanes = (unsigned)(__ballot(any ? any_k : all_k) >> (8 * rw)) & 0xffu;
+        const bool holds = any ? lanes != 0u : lanes == 0xffu;
+        if (cl.role == CMBPO_RULE_HEALTHY) rule_done = rule_done || !holds;
+        else if (cl.role == CMBPO_RULE_FATAL) rule_done = rule_done || holds;
+        else rule_obj = rule_obj || holds;
+      }
+    }
     if (r < 0 || k != 0) return;
     p.dkl_path[r] = sd / (float)D;      // fake_env.py:113
     p.ep_var_mean[r] = sv / (float)D;   // model_sampler.py:322
@@ -235,7 +274,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
     p.rew[r] = p.mean[me * mstride + (size_t)r * p.out_dim + D];    // fake_env.py:148-151
     uint8_t done = 0;
     float cost = 0.0f;
-    if (p.task == CMBPO_TASK_ANTSAFE) {
+    if constexpr (RULES) {
+      done = ((p.rules.require_finite && !fin) || rule_done) ? 1 : 0;
+      const float obj = rule_obj ? 1.0f : 0.0f;
+      cost = p.rules.cost_on_term ? fminf(__fadd_rn((float)done, obj), 1.0f) : obj;      // statics.py:51-52
+    } else if (p.task == CMBPO_TASK_ANTSAFE) {
       // statics.py:17-53
       const float z = nx[0];
       const float q1 = nx[2], q2 = nx[3];
@@ -271,11 +314,15 @@ extern "C" int cmbpo_fakeenv_post(int task, int ensemble, int obs_dim, int act_d
   const int learned_cost = (task & CMBPO_TASK_LEARNED_COST) ? 1 : 0;     // every other bit outside the rule id is an error
   const int task_arg = task;
   task &= ~CMBPO_TASK_LEARNED_COST;
-  CMBPO_REQUIRE(task >= CMBPO_TASK_DEFAULT && task <= CMBPO_TASK_ANTSAFE, "cmbpo_fakeenv_post: bad task %d", task_arg);
+  const bool user = task >= CMBPO_TASK_USER_BASE && task < CMBPO_TASK_USER_BASE + CMBPO_TASK_USER_SLOTS;
+  CMBPO_REQUIRE((task >= CMBPO_TASK_DEFAULT && task <= CMBPO_TASK_ANTSAFE) || user, "cmbpo_fakeenv_post: bad task %d", task_arg);
   CMBPO_REQUIRE(ensemble >= 2 && ensemble <= kEMax, "cmbpo_fakeenv_post: ensemble %d not in [2, %d]", ensemble, kEMax);
   CMBPO_REQUIRE(obs_dim >= 1 && obs_dim <= 512 && act_dim >= 0, "cmbpo_fakeenv_post: bad dims");
   if (task == CMBPO_TASK_ANTSAFE)
     CMBPO_REQUIRE(obs_dim >= 5, "cmbpo_fakeenv_post: AntSafe rules need obs_dim >= 5");
+  PostArgsRules ar{};
+  if (user)     // (registered? columns inside obs_dim / act_dim? -- host code, before any HIP call)
+    if (int rc = cmbpo_internal_task_rules_resolve("cmbpo_fakeenv_post", task_arg, obs_dim, act_dim, d_act != nullptr, &ar.rules)) return rc;
   CMBPO_REQUIRE(d_mean && d_var && d_obs && d_elite && d_next_obs && d_rew && d_term && d_cost &&
                     d_dkl_path && d_ep_var_mean,
                 "cmbpo_fakeenv_post: NULL buffer");
@@ -291,7 +338,12 @@ extern "C" int cmbpo_fakeenv_post(int task, int ensemble, int obs_dim, int act_d
   a.dkl_path = d_dkl_path; a.ep_var_mean = d_ep_var_mean; a.ep_var = d_ep_var;
   const size_t lds = (size_t)3 * kRows * obs_dim * sizeof(float) + kRows * sizeof(int);
   const dim3 grid(cmbpo_ceil_div(n_rows, kRows));
-  if (ensemble == 7) hipLaunchKernelGGL(fakeenv_post_kernel<7>, grid, dim3(kThreads), lds, (hipStream_t)stream, a);   // the shipped configs
+  if (user) {
+    static_cast<PostArgs &>(ar) = a;
+    if (ensemble == 7) hipLaunchKernelGGL((fakeenv_post_kernel<7, true>), grid, dim3(kThreads), lds, (hipStream_t)stream, ar);
+    else if (ensemble == 5) hipLaunchKernelGGL((fakeenv_post_kernel<5, true>), grid, dim3(kThreads), lds, (hipStream_t)stream, ar);
+    else hipLaunchKernelGGL((fakeenv_post_kernel<0, true>), grid, dim3(kThreads), lds, (hipStream_t)stream, ar);
+  } else if (ensemble == 7) hipLaunchKernelGGL(fakeenv_post_kernel<7>, grid, dim3(kThreads), lds, (hipStream_t)stream, a);   // the shipped configs
   else if (ensemble == 5) hipLaunchKernelGGL(fakeenv_post_kernel<5>, grid, dim3(kThreads), lds, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(fakeenv_post_kernel<0>, grid, dim3(kThreads), lds, (hipStream_t)stream, a);
   CMBPO_HIP_CHECK(hipGetLastError());

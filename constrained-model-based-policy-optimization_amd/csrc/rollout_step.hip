@@ -42,6 +42,9 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   CMBPO_REQUIRE(model->out_dim == r->obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0),
                 "cmbpo_rollout_step: model out_dim %d does not match obs_dim %d + 1 (+ 1 with CMBPO_TASK_LEARNED_COST), task 0x%x",
                 model->out_dim, r->obs_dim, task);
+  // a user rule id: registered, and its columns inside this rollout's widths -- before the first launch of the step, not at the third
+  if ((task & ~CMBPO_TASK_LEARNED_COST) >= CMBPO_TASK_USER_BASE)
+    if (int rc0 = cmbpo_internal_task_rules_resolve("cmbpo_rollout_step", task, r->obs_dim, r->act_dim, r->act_t != nullptr, nullptr)) return rc0;
   // the per-step arrays are inputs of the bookkeeping kernels (const in the struct) and outputs of the forward passes
   auto w = [](const float *p) { return const_cast<float *>(p); };
   int rc;

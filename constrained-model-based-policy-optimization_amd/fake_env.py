@@ -15,11 +15,14 @@ Differences that are part of the contract:
 elite member's mean of the model's last output column (``output_dim == obs_dim + 2``) instead of the
 task's cost rule; the task's termination rule still applies.  ``info['cost']`` is then the float32
 prediction, not thresholded.
+
+``task`` is a built-in task name, a name given to ``statics.register_task``, or a ``statics.TaskRules`` (user-defined
+termination / cost rules, evaluated by the same kernel); any other name is the default task, as in the reference.
 """
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, statics
 
 
 class FakeEnv:
@@ -43,7 +46,11 @@ class FakeEnv:
         assert self.output_dim == self.obs_dim + 1 + int(self._predicts_cost)
         # the `task` argument of the native entry points: the rule id, with the learned-cost flag where the model has the head
         # (every caller that passes it -- this class, ModelSampler, the probes -- thereby runs the mode the scratch is sized for)
-        self._task_id = _lib.TASK_IDS.get(task, _lib.TASK_DEFAULT)
+        self._task_id, self._rules = statics.lookup(task)
+        # where the reference's step() returns np.zeros_like(terms), a bool array (models/fake_env.py:145-146): no learned
+        # cost and no cost function for the task
+        self._bool_cost = not self._predicts_cost and (
+            self._task_id == _lib.TASK_DEFAULT or (self._rules is not None and not self._rules.has_cost))
         if self._predicts_cost:
             self._task_id |= _lib.TASK_LEARNED_COST
         self._rng = np.random.default_rng(seed)
@@ -128,7 +135,7 @@ class FakeEnv:
             self.step_device(o, a, inds, out)
         next_obs, r, terms = out["next_obs"], out["rew"][:, None], out["term"].bool()[:, None]
         c = out["cost"][:, None]
-        if self._task_id == _lib.TASK_DEFAULT:      # (not with a learned cost: the float32 prediction is the cost)
+        if self._bool_cost:      # (not with a learned cost: the float32 prediction is the cost)
             c = c.bool()  # np.zeros_like(terms) is a bool array (models/fake_env.py:145-146)
         dkl_path, ep_var = out["dkl_path"], out["ep_var"]
         dkl_mean = dkl_path.mean()

@@ -54,6 +54,55 @@ extern "C" {
  * outside the rule id is rejected. */
 #define CMBPO_TASK_LEARNED_COST 0x100
 
+/* User-defined termination / cost rules: what a user of the reference adds to TERMS_BY_TASK / COST_BY_TASK as a NumPy
+ * function (models/statics.py:56-69), declared as a table of at most 16 clauses and evaluated by cmbpo_fakeenv_post on the
+ * device.  A registered table is a rule id CMBPO_TASK_USER_BASE + slot (16..79, below the flag bit), valid wherever a
+ * built-in id is.
+ *
+ * A clause tests the columns [col0, col0 + n_cols) of one source row (col0 < 0 counts from the end, n_cols == -1 means
+ * through the last column; resolved against obs_dim / act_dim at launch).  Per column, in float32 with single roundings:
+ *   f = fl32(x * scale);  f = |f| with CMBPO_RULE_ABS;
+ *   the column holds iff (LO_STRICT ? f > lo : f >= lo) && (HI_STRICT ? f < hi : f <= hi)
+ * -- written positively, so a NaN never holds (NumPy's comparisons); lo = -inf / hi = +inf leave a side open.  The clause
+ * holds iff all its columns hold, or any of them with CMBPO_RULE_ANY.
+ *   done = (require_finite && !isfinite(next_obs).all()) || some HEALTHY clause does not hold || some FATAL clause holds
+ *   obj  = 1.0f if some COST clause holds, else 0.0f
+ *   cost = cost_on_term ? min(1, done + obj) : obj            (the shape of models/statics.py:51-52)
+ * With CMBPO_TASK_LEARNED_COST the cost is the model's column; COST clauses and cost_on_term are ignored, done is not. */
+#define CMBPO_TASK_USER_BASE 16
+#define CMBPO_TASK_USER_SLOTS 64
+#define CMBPO_RULE_MAX_CLAUSES 16
+#define CMBPO_RULE_HEALTHY 0      /* role: the branch is done if the clause does NOT hold */
+#define CMBPO_RULE_FATAL 1        /*       the branch is done if the clause holds         */
+#define CMBPO_RULE_COST 2         /*       the step costs 1 if the clause holds           */
+#define CMBPO_RULE_SRC_NEXT_OBS 0 /* src */
+#define CMBPO_RULE_SRC_OBS 1
+#define CMBPO_RULE_SRC_ACT 2
+#define CMBPO_RULE_ABS 1          /* flags */
+#define CMBPO_RULE_LO_STRICT 2
+#define CMBPO_RULE_HI_STRICT 4
+#define CMBPO_RULE_ANY 8
+
+typedef struct cmbpo_rule_clause {
+  int32_t role, src, col0, n_cols, flags;
+  float scale, lo, hi;
+} cmbpo_rule_clause_t; /* 32 bytes */
+
+typedef struct cmbpo_task_rules {
+  int32_t n_clauses, require_finite, cost_on_term, reserved;
+  cmbpo_rule_clause_t clause[CMBPO_RULE_MAX_CLAUSES];
+} cmbpo_task_rules_t; /* 528 bytes */
+
+/* Validates the table (host code only: n_clauses in 0..16, known role / src / flags, finite scale, lo / hi not NaN with
+ * lo <= hi, n_cols >= 1 or -1, require_finite / cost_on_term 0 or 1, reserved == 0) and stores it; *out_task is its rule
+ * id.  A table byte-identical to a stored one gets that one's id.  CMBPO_EINVAL with a message naming the field, or
+ * saying that all CMBPO_TASK_USER_SLOTS slots are taken.  Safe to call from several threads. */
+int cmbpo_task_rules_register(const cmbpo_task_rules_t *rules, int *out_task);
+/* the table behind a registered rule id (the learned-cost bit is ignored); CMBPO_EINVAL if the id is not registered */
+int cmbpo_task_rules_get(int task, cmbpo_task_rules_t *out);
+/* number of registered tables */
+int cmbpo_task_rules_count(void);
+
 const char *cmbpo_last_error(void);
 int cmbpo_version(void);
 
@@ -169,7 +218,10 @@ int cmbpo_policy_forward(cmbpo_mlp_t *m, const float *d_obs, int obs_dim,
  * cmbpo_ens_forward.  d_cost is float (bool cast for the default task),
  * d_term is uint8.  d_mean / d_var are [E, ld_rows, obs + 1], or
  * [E, ld_rows, obs + 2] with CMBPO_TASK_LEARNED_COST set in `task`.  d_ep_var_mean = mean over obs dims of ens_ep_var (what
- * samplers/model_sampler.py:322,343 consume); d_ep_var [.,obs_dim] optional. */
+ * samplers/model_sampler.py:322,343 consume); d_ep_var [.,obs_dim] optional.
+ * `task` is a built-in rule id or one cmbpo_task_rules_register returned (term / cost from its clause table), with or
+ * without CMBPO_TASK_LEARNED_COST; an unregistered id, a clause whose columns lie outside obs_dim / act_dim, or a clause on
+ * the actions with d_act == NULL is CMBPO_EINVAL, decided before any HIP call. */
 int cmbpo_fakeenv_post(int task, int ensemble, int obs_dim, int act_dim,
                        const float *d_mean, const float *d_var, int ld_rows,
                        const float *d_obs, const float *d_act,
