@@ -65,8 +65,8 @@ __global__ __launch_bounds__(512) void critic_pair_kernel(const CfArgs a) {
   const int ni = is_pol ? 0 : wave / E, e = is_pol ? 0 : wave - ni * E;     // this wave's critic and member
   const CfNet &N = a.net[ni];
   // first weight fragments of layer 0: requested before anything else
-  const f16x8 *w0 = N.w0 + (size_t)e * N.w0_stride + lane;      // + ((tile * S0 + s) * 2 + piece) * 64
-  const f16x8 *w1 = N.w1 + (size_t)e * N.w1_stride + lane;      // + ((tile * S1 + s) * 2 + piece) * 64
+  const f16x8 *w0 = N.w0 + (size_t)e * N.w0_stride + lane;
+  const f16x8 *w1 = N.w1 + (size_t)e * N.w1_stride + lane;
   // The wave streams its member's weights alone (80 KB from L2) and every slab is 12 MFMAs = 0.2 us of work against a load
   // latency several times that: all of W0 and the first slabs of W1 are requested before the input is even staged, and
   // layer 1 keeps a ring of RW slabs in flight.
@@ -75,8 +75,8 @@ __global__ __launch_bounds__(512) void critic_pair_kernel(const CfArgs a) {
   auto load_w = [&](f16x8 (&x)[NT][2], const f16x8 *w, int slabs, int s) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const f16x8 *q = w + ((size_t)(t * slabs + s) * 2) * 64;
-      x[t][0] = q[0]; x[t][1] = q[64];
+      const f16x8 *q = w + IMAGE_INDEX(t, slabs, s, 2, 0);
+      x[t][0] = q[0]; x[t][1] = q[kImageLanes];
     }
   };
   // rows, scalers, raw observation rows: staged by every wave of the workgroup (two barriers)
@@ -247,7 +247,7 @@ template <int S0>
 struct BigGeo {
   static constexpr int KP = 16 * S0, XS = KP + 1;
   static constexpr int CH = S0 <= 2 ? 512 : (S0 == 3 ? 256 : 192);    // rows per workgroup (LDS: weights + the chunk's rows)
-  static constexpr int W0Q = NT * S0 * 2 * 64, W1Q = NT * S1 * 2 * 64;   // f16x8 units
+  static constexpr int W0Q = (int)IMAGE_UNITS(NT, S0, 2), W1Q = (int)IMAGE_UNITS(NT, S1, 2);   // f16x8 units
   static constexpr size_t LDS = (size_t)(W0Q + W1Q) * 16 + (size_t)CH * XS * 4 + (size_t)2 * CH * 4 + (size_t)CH * 4 + (size_t)4 * KP * 4;
 };
 
@@ -364,8 +364,8 @@ __global__ __launch_bounds__(512) void critic_big_kernel(const CfArgs a, int ch_
         }
 #pragma unroll
         for (int tt = 0; tt < NT; ++tt) {
-          const f16x8 *q = w0 + ((size_t)(tt * S0 + s) * 2) * 64;
-          mm3(acc[tt], q[0], q[64], b1, b2);
+          const f16x8 *q = w0 + IMAGE_INDEX(tt, S0, s, 2, 0);
+          mm3(acc[tt], q[0], q[kImageLanes], b1, b2);
         }
       }
       // h1 = swish(. + b0), lifted and split: accumulator registers 8 half .. + 7 of tile tt are slab 2 tt + half of layer 1
@@ -397,8 +397,8 @@ __global__ __launch_bounds__(512) void critic_big_kernel(const CfArgs a, int ch_
       for (int s = 0; s < S1; ++s) {
 #pragma unroll
         for (int tt = 0; tt < NT; ++tt) {
-          const f16x8 *q = w1 + ((size_t)(tt * S1 + s) * 2) * 64;
-          mm3(acc[tt], q[0], q[64], bf[s][0], bf[s][1]);
+          const f16x8 *q = w1 + IMAGE_INDEX(tt, S1, s, 2, 0);
+          mm3(acc[tt], q[0], q[kImageLanes], bf[s][0], bf[s][1]);
         }
       }
       // h2 = swish(. + b1); output = h2 . W2[:, 0] + b2; output scaler
@@ -441,7 +441,7 @@ __global__ void cf16_consts_kernel(const float *b0, const float *b1, const float
   float v;
   if (f == 0) v = b0[(size_t)e * HC + k] * kLog2e;
   else if (f == 1) v = b1[(size_t)e * HC + k] * kLog2e;
-  else v = w2[(size_t)e * w2_stride + ((size_t)(k >> 3) * 64 + ((k >> 2) & 1) * 32) * 4 + (k & 3)] * kLn2;     // packed (k, n = 0)
+  else v = w2[(size_t)e * w2_stride + pack_index(k, 0, HC / 8)] * kLn2;     // column 0 of the packed W2
   cst[(size_t)e * 3 * HC + t] = v;
 }
 
@@ -450,8 +450,8 @@ int ensure_cf16(cmbpo_mlp *m, hipStream_t s) {
   const int E = m->ensemble;
   const int S0 = m->h3_s0;
   if (m->d_h3 == nullptr) {
-    m->h3_stride[0] = (size_t)NT * S0 * 2 * 64;
-    m->h3_stride[1] = (size_t)NT * S1 * 2 * 64;
+    m->h3_stride[0] = IMAGE_UNITS(NT, S0, 2);
+    m->h3_stride[1] = IMAGE_UNITS(NT, S1, 2);
     m->h3_stride[2] = 0;
     m->h3_off[0] = 0;
     m->h3_off[1] = m->h3_stride[0] * E;
@@ -471,8 +471,8 @@ int ensure_cf16(cmbpo_mlp *m, hipStream_t s) {
   f16x8 *base = reinterpret_cast<f16x8 *>(m->d_h3);
   cmbpo_internal_f16_pack(m, 0, base + m->h3_off[0], m->h3_stride[0], NT, S0, 0, stats, s);
   cmbpo_internal_f16_pack(m, 1, base + m->h3_off[1], m->h3_stride[1], NT, S1, 1, stats, s);
-  hipLaunchKernelGGL(cf16_consts_kernel, dim3(E), dim3(3 * HC), 0, s, m->d_blob + m->off_b0, m->d_blob + m->off_b1, m->d_blob + m->off_wp2,
-                     (size_t)m->o_tiles * (HC / 8) * 256, stats + (size_t)E * NSTAT);
+  hipLaunchKernelGGL(cf16_consts_kernel, dim3(E), dim3(3 * HC), 0, s, m->d_blob + m->off_b0, m->d_blob + m->off_b1, m->pack(2),
+                     m->pack_floats(2), stats + (size_t)E * NSTAT);
   CMBPO_HIP_CHECK(hipGetLastError());
   m->h3_version = m->pack_version;
   return CMBPO_OK;
@@ -527,13 +527,10 @@ int cmbpo_internal_critic_pair_ride(cmbpo_mlp *v, cmbpo_mlp *vc, const float *d_
     n.w0 = base + m->h3_off[0]; n.w1 = base + m->h3_off[1];
     n.w0_stride = m->h3_stride[0]; n.w1_stride = m->h3_stride[1];
     n.b0 = blob + m->off_b0; n.b1 = blob + m->off_b1; n.b2 = blob + m->off_b2;
-    n.w2 = blob + m->off_wp2; n.w2_stride = (size_t)m->o_tiles * (HC / 8) * 256;
+    n.w2 = m->pack(2); n.w2_stride = m->pack_floats(2);
     n.stats = reinterpret_cast<const float *>(reinterpret_cast<const char *>(m->d_h3) + m->h3_stats_off * 16);
     n.cst = n.stats + (size_t)m->ensemble * NSTAT;
-    n.in_mu = m->has_in_scaler ? blob + m->off_in_mu : nullptr;
-    n.in_sig = m->has_in_scaler ? blob + m->off_in_var : nullptr;
-    n.out_mu = m->has_out_scaler ? blob + m->off_out_mu : nullptr;
-    n.out_sig = m->has_out_scaler ? blob + m->off_out_var : nullptr;
+    n.in_mu = m->in_mu(); n.in_sig = m->in_sig(); n.out_mu = m->out_mu(); n.out_sig = m->out_sig();
     n.out = outs[i];
   }
   a.obs = d_obs; a.obs_dim = obs_dim; a.ensemble = v->ensemble;

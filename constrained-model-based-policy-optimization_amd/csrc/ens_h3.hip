@@ -122,14 +122,14 @@ __global__ void h3_stats_kernel(const float *blob, size_t off0, size_t off1, siz
   const int e = blockIdx.x, l = blockIdx.y, tid = threadIdx.x;
   const int tiles = l == 2 ? o_tiles : hidden / 32, kg = l == 0 ? kg0 : hidden / 8;
   const size_t woff = l == 0 ? off0 : (l == 1 ? off1 : off2), boff = l == 0 ? offb0 : (l == 1 ? offb1 : offb2);
-  const float *w = blob + woff + (size_t)e * tiles * kg * 256;
+  const float *w = blob + woff + e * pack_floats(tiles, kg);
   const float *b = blob + boff + (size_t)e * tiles * 32;
   float wmax = 0.0f, l1 = 0.0f, bmax = 0.0f;
   if (tid < tiles * 32) {
     const int tile = tid >> 5, r = tid & 31;
     for (int g = 0; g < kg; ++g)
       for (int h = 0; h < 2; ++h) {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(w + (((size_t)tile * kg + g) * 64 + h * 32 + r) * 4);
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(w + pack_index_tile(tile, r, 8 * g + 4 * h, kg));
         for (int s = 0; s < 4; ++s) { const float a = fabsf(v[s]); wmax = fmaxf(wmax, a); l1 += a; }
       }
     bmax = fabsf(b[tid]);
@@ -162,7 +162,7 @@ __global__ void h3_stats_kernel(const float *blob, size_t off0, size_t off1, siz
 __global__ void h3_pack_kernel(const float *src, size_t src_stride, int kg, int src_tiles, f16x8 *dst, size_t dst_stride,
                                int n_tiles, int slabs, int members, const float *stats, int layer, int mode) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long per = (long)n_tiles * slabs * 64;
+  const long per = (long)IMAGE_UNITS(n_tiles, slabs, 1);
   if (idx >= per * members) return;
   const int e = (int)(idx / per);
   const int rem = (int)(idx - (long)e * per);
@@ -183,13 +183,13 @@ __global__ void h3_pack_kernel(const float *src, size_t src_stride, int kg, int 
     } else if (mode == 2) k = 32 * s + 8 * ((g & 1) * 2 + (g >> 1)) + j;
     else k = 32 * s + 16 * (j >> 2) + 4 * g + (j & 3);
     float v = 0.0f;
-    if ((n >> 5) < src_tiles && (k >> 3) < kg) v = sp[(((size_t)(n >> 5) * kg + (k >> 3)) * 64 + ((k >> 2) & 1) * 32 + r) * 4 + (k & 3)];
+    if ((n >> 5) < src_tiles && (k >> 3) < kg) v = sp[pack_index_tile(n >> 5, r, k, kg)];
     _Float16 q1, q2;
     split_h(v * scale, q1, q2);
     p1[j] = q1; p2[j] = q2;
   }
-  f16x8 *d = dst + (size_t)e * dst_stride + ((size_t)tile * slabs + s) * 2 * 64 + lane;
-  d[0] = p1; d[64] = p2;
+  f16x8 *d = dst + (size_t)e * dst_stride + IMAGE_INDEX(tile, slabs, s, 2, 0) + lane;
+  d[0] = p1; d[kImageLanes] = p2;
 }
 
 // compile-time loop: f(integral_constant<int, I>) for I in [I0, N) -- indices of register arrays must be constants
@@ -908,7 +908,7 @@ static int ensure_h3(cmbpo_mlp *m, hipStream_t s) {
   if (m->d_h3 == nullptr) {
     size_t off = 0;
     for (int l = 0; l < 3; ++l) {
-      m->h3_stride[l] = (size_t)tiles[l] * slabs[l] * 2 * 64;
+      m->h3_stride[l] = IMAGE_UNITS(tiles[l], slabs[l], 2);
       m->h3_off[l] = off;
       off += m->h3_stride[l] * E;
     }
@@ -924,18 +924,10 @@ static int ensure_h3(cmbpo_mlp *m, hipStream_t s) {
   }
   if (m->h3_version == m->pack_version) return CMBPO_OK;
   float *stats = reinterpret_cast<float *>(reinterpret_cast<char *>(m->d_h3) + m->h3_stats_off * 16);
-  hipLaunchKernelGGL(h3_stats_kernel, dim3(E, 3), dim3(kThreadsH), 0, s, m->d_blob, m->off_wp0, m->off_wp1, m->off_wp2,
-                     m->off_b0, m->off_b1, m->off_b2, m->in_pad / 8, m->o_tiles, H, stats);
-  const size_t src_off[3] = {m->off_wp0, m->off_wp1, m->off_wp2};
-  const int kg[3] = {m->in_pad / 8, H / 8, H / 8};
-  const int src_tiles[3] = {H / 32, H / 32, m->o_tiles};
-  for (int l = 0; l < 3; ++l) {
-    const size_t src_stride = (size_t)src_tiles[l] * kg[l] * 256;
-    const long total = (long)tiles[l] * slabs[l] * 64 * E;
-    hipLaunchKernelGGL(h3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, m->d_blob + src_off[l], src_stride,
-                       kg[l], src_tiles[l], reinterpret_cast<f16x8 *>(m->d_h3) + m->h3_off[l], m->h3_stride[l], tiles[l], slabs[l],
-                       E, stats, l, l == 0 ? 0 : l + 1);
-  }
+  cmbpo_internal_f16_stats(m, stats, s);
+  for (int l = 0; l < 3; ++l)
+    cmbpo_internal_f16_pack(m, l, reinterpret_cast<f16x8 *>(m->d_h3) + m->h3_off[l], m->h3_stride[l], tiles[l], slabs[l],
+                            l == 0 ? 0 : l + 1, stats, s);
   CMBPO_HIP_CHECK(hipGetLastError());
   m->h3_version = m->pack_version;
   return CMBPO_OK;
@@ -948,15 +940,10 @@ void cmbpo_internal_f16_stats(const cmbpo_mlp *m, float *stats, hipStream_t s) {
 }
 void cmbpo_internal_f16_pack(const cmbpo_mlp *m, int layer, void *dst, size_t dst_stride, int n_tiles, int slabs, int perm,
                              const float *stats, hipStream_t s) {
-  const int H = m->hidden;
-  const size_t src_off[3] = {m->off_wp0, m->off_wp1, m->off_wp2};
-  const int kg[3] = {m->in_pad / 8, H / 8, H / 8};
-  const int src_tiles[3] = {H / 32, H / 32, m->o_tiles};
-  const size_t src_stride = (size_t)src_tiles[layer] * kg[layer] * 256;
-  const long total = (long)n_tiles * slabs * 64 * m->ensemble;
-  hipLaunchKernelGGL(h3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, m->d_blob + src_off[layer], src_stride,
-                     kg[layer], src_tiles[layer], reinterpret_cast<f16x8 *>(dst), dst_stride, n_tiles, slabs, m->ensemble, stats, layer,
-                     perm);
+  const long total = (long)(IMAGE_UNITS(n_tiles, slabs, 1) * m->ensemble);
+  hipLaunchKernelGGL(h3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, m->pack(layer), m->pack_floats(layer),
+                     m->pack_kg(layer), m->pack_tiles(layer), reinterpret_cast<f16x8 *>(dst), dst_stride, n_tiles, slabs, m->ensemble,
+                     stats, layer, perm);
 }
 
 static int g_h3_rt = 0;   // 0: by row count; 1 / 2 / 4 forces it

@@ -166,12 +166,12 @@ __device__ __forceinline__ void activate_regs(f32x16 (&acc)[NT][BT]) {
 template <int NT, int BT>
 __device__ __forceinline__ void mfma_from_regs(const f32x4 *__restrict__ wp, int g_base, const f32x16 (&hreg)[NT][BT],
                                                int lane, f32x16 (&out)[BT]) {
-  f32x4 a_cur = wp[(size_t)g_base * 64 + lane], a_nxt;
+  f32x4 a_cur = wp[PACK_VEC4S(1, g_base) + lane], a_nxt;
 #pragma unroll
   for (int i = 0; i < NT * 4; ++i) {
     const int t = i >> 2, q = i & 3;
     const int inext = (i + 1 < NT * 4) ? i + 1 : i;
-    a_nxt = wp[(size_t)(g_base + inext) * 64 + lane];
+    a_nxt = wp[PACK_VEC4S(1, g_base + inext) + lane];
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int s = 0; s < 4; ++s)
@@ -334,8 +334,8 @@ __global__ __launch_bounds__(kThreads, (BT == 1 ? 2 : 1)) void ens_mlp_kernel(
     {
       f32x16 acc[NT][BT];
       init_acc_bias<NT, BT>(acc, bias_l, wave * NT * 32, lane);
-      const f32x4 *wp = p.wp0 + e * p.wp0_stride + (size_t)(wave * NT) * kg0 * 64;
-      mfma_layer<NT, BT>(wp, (size_t)kg0 * 64, 0, kg0, xbuf, lane, acc);
+      const f32x4 *wp = p.wp0 + e * p.wp0_stride + PACK_VEC4S(wave * NT, kg0);
+      mfma_layer<NT, BT>(wp, PACK_VEC4S(1, kg0), 0, kg0, xbuf, lane, acc);
       STAMP(2);
       if constexpr (HEAD == CMBPO_HEAD_TRAIN) {
         float hm = hidden_train<NT, BT, HID, true>(acc, wave * NT * 32, hbuf, lane, p.tr_h1, p.tr_g1,
@@ -352,10 +352,10 @@ __global__ __launch_bounds__(kThreads, (BT == 1 ? 2 : 1)) void ens_mlp_kernel(
     {
       f32x16 acc[NT][BT];
       init_acc_bias<NT, BT>(acc, bias_l + HID, wave * NT * 32, lane);
-      const f32x4 *wp = p.wp1 + e * p.wp1_stride + (size_t)(wave * NT) * KG_H * 64;
+      const f32x4 *wp = p.wp1 + e * p.wp1_stride + PACK_VEC4S(wave * NT, KG_H);
       // (a two-group-deep ring, mfma_layer<..., DEPTH = 2>, measured no faster: the lone-wave loss is the
       // ~27-cycle issue cost of each global_load_dwordx4 next to the MFMAs, not exposed latency)
-      mfma_layer<NT, BT>(wp, (size_t)KG_H * 64, 0, KG_H, hbuf, lane, acc);
+      mfma_layer<NT, BT>(wp, PACK_VEC4S(1, KG_H), 0, KG_H, hbuf, lane, acc);
       STAMP(4);
       if constexpr (HEAD == CMBPO_HEAD_TRAIN) {
         float hm = hidden_train<NT, BT, HID, false>(acc, wave * NT * 32, nullptr, lane, p.tr_h2, p.tr_g2,
@@ -379,13 +379,13 @@ __global__ __launch_bounds__(kThreads, (BT == 1 ? 2 : 1)) void ens_mlp_kernel(
         // Column 0 of the packed W2 sits in lanes 0 / 32 of every k-group: a broadcast 16-B load per (t, q).
         if (p.o_width == 1) {
           valu_out = true;
-          const f32x4 *w2c = p.wp2 + e * p.wp2_stride + (size_t)(wave * NT * 4) * 64 + h * 32;
+          const f32x4 *w2c = p.wp2 + e * p.wp2_stride + PACK_VEC4S(1, wave * NT * 4) + h * 32;
           float partial = 0.0f;
 #pragma unroll
           for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-              const f32x4 w = w2c[(size_t)(4 * t + q) * 64];
+              const f32x4 w = w2c[PACK_VEC4S(1, 4 * t + q)];
 #pragma unroll
               for (int s = 0; s < 4; ++s) partial = fmaf(acc[t][0][4 * q + s], w[s], partial);
             }
@@ -399,7 +399,7 @@ __global__ __launch_bounds__(kThreads, (BT == 1 ? 2 : 1)) void ens_mlp_kernel(
         for (int bt = 0; bt < BT; ++bt)
 #pragma unroll
           for (int r = 0; r < 16; ++r) part[bt][r] = 0.0f;
-        const f32x4 *wp2 = p.wp2 + e * p.wp2_stride + (size_t)ot * KG_H * 64;
+        const f32x4 *wp2 = p.wp2 + e * p.wp2_stride + PACK_VEC4S(ot, KG_H);
         mfma_from_regs<NT, BT>(wp2, wave * NT * 4, acc, lane, part);
 #pragma unroll
         for (int bt = 0; bt < BT; ++bt)
@@ -528,20 +528,10 @@ __global__ __launch_bounds__(kThreads, (BT == 1 ? 2 : 1)) void ens_mlp_kernel(
   STAMP(9);
 }
 
-// Host-side packing: W[K][N] row-major -> [n-tile][k-group][lane][4].
+// Host-side packing: W[K][N] row-major -> the fp32 pack (pack_layout.h), zero padded.
 void pack_weights(const float *w, int K, int N, int k_pad, int n_tiles, float *dst) {
-  const int kg = k_pad / 8;
-  for (int nt = 0; nt < n_tiles; ++nt)
-    for (int g = 0; g < kg; ++g)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int i = lane & 31, h = lane >> 5;
-        const int n = nt * 32 + i;
-        for (int s = 0; s < 4; ++s) {
-          const int k = 8 * g + 4 * h + s;
-          dst[(((size_t)nt * kg + g) * 64 + lane) * 4 + s] =
-              (k < K && n < N) ? w[(size_t)k * N + n] : 0.0f;
-        }
-      }
+  for (int k = 0; k < k_pad; ++k)
+    for (int n = 0; n < n_tiles * 32; ++n) dst[pack_index(k, n, k_pad / 8)] = (k < K && n < N) ? w[(size_t)k * N + n] : 0.0f;
 }
 
 }  // namespace
@@ -574,9 +564,9 @@ extern "C" int cmbpo_mlp_create(cmbpo_mlp_t **out, int ensemble, int in_dim, int
   const int E = ensemble, H = hidden;
   size_t off = 0;
   auto take = [&](size_t n) { size_t o = off; off += (n + 3) / 4 * 4; return o; };
-  m->off_wp0 = take((size_t)E * (H / 32) * (m->in_pad / 8) * 256);
-  m->off_wp1 = take((size_t)E * (H / 32) * (H / 8) * 256);
-  m->off_wp2 = take((size_t)E * m->o_tiles * (H / 8) * 256);
+  m->off_wp0 = take(E * m->pack_floats(0));
+  m->off_wp1 = take(E * m->pack_floats(1));
+  m->off_wp2 = take(E * m->pack_floats(2));
   m->off_b0 = take((size_t)E * H);
   m->off_b1 = take((size_t)E * H);
   m->off_b2 = take((size_t)E * m->o_tiles * 32);
@@ -617,13 +607,10 @@ extern "C" int cmbpo_mlp_load(cmbpo_mlp_t *m, const float *h_w0, const float *h_
   const int E = m->ensemble, H = m->hidden, I = m->in_dim, O = m->o_width;
   m->h_blob.assign(m->blob_floats, 0.0f);
   float *hb = m->h_blob.data();
-  const size_t s0 = (size_t)(H / 32) * (m->in_pad / 8) * 256;
-  const size_t s1 = (size_t)(H / 32) * (H / 8) * 256;
-  const size_t s2 = (size_t)m->o_tiles * (H / 8) * 256;
   for (int e = 0; e < E; ++e) {
-    pack_weights(h_w0 + (size_t)e * I * H, I, H, m->in_pad, H / 32, hb + m->off_wp0 + e * s0);
-    pack_weights(h_w1 + (size_t)e * H * H, H, H, H, H / 32, hb + m->off_wp1 + e * s1);
-    pack_weights(h_w2 + (size_t)e * H * O, H, O, H, m->o_tiles, hb + m->off_wp2 + e * s2);
+    pack_weights(h_w0 + (size_t)e * I * H, I, H, m->in_pad, H / 32, hb + m->off_wp0 + e * m->pack_floats(0));
+    pack_weights(h_w1 + (size_t)e * H * H, H, H, H, H / 32, hb + m->off_wp1 + e * m->pack_floats(1));
+    pack_weights(h_w2 + (size_t)e * H * O, H, O, H, m->o_tiles, hb + m->off_wp2 + e * m->pack_floats(2));
     memcpy(hb + m->off_b0 + (size_t)e * H, h_b0 + (size_t)e * H, H * sizeof(float));
     memcpy(hb + m->off_b1 + (size_t)e * H, h_b1 + (size_t)e * H, H * sizeof(float));
     memcpy(hb + m->off_b2 + (size_t)e * m->o_tiles * 32, h_b2 + (size_t)e * O, O * sizeof(float));
@@ -666,8 +653,8 @@ __global__ void policy_flat_load_kernel(const float *flat, float *blob, FlatLoad
   const int oW0 = 0, ob0 = a.I * a.H, oW1 = ob0 + a.H, ob1 = oW1 + a.H * a.H, oW2 = ob1 + a.H, ob2 = oW2 + a.H * a.O,
             ols = ob2 + a.O;
   auto pack = [&](int i, int K, int N, int k_pad, int src_off, size_t dst_off) {
-    const int s = i & 3, lane = (i >> 2) & 63, kg = k_pad / 8, g = (i >> 8) % kg, nt = (i >> 8) / kg;
-    const int n = nt * 32 + (lane & 31), k = 8 * g + 4 * (lane >> 5) + s;
+    int k, n;
+    pack_unindex(i, k_pad / 8, k, n);
     blob[dst_off + i] = (k < K && n < N) ? flat[src_off + (size_t)k * N + n] : 0.0f;
   };
   int i = idx;
@@ -697,7 +684,7 @@ extern "C" int cmbpo_mlp_load_policy_flat(cmbpo_mlp_t *m, const float *d_flat, v
   a.I = m->in_dim; a.H = m->hidden; a.O = m->o_width; a.in_pad = m->in_pad; a.o_tiles = m->o_tiles;
   a.off_wp0 = m->off_wp0; a.off_wp1 = m->off_wp1; a.off_wp2 = m->off_wp2;
   a.off_b0 = m->off_b0; a.off_b1 = m->off_b1; a.off_b2 = m->off_b2; a.off_log_std = m->off_log_std;
-  a.n0 = (a.H / 32) * (a.in_pad / 8) * 256; a.n1 = (a.H / 32) * (a.H / 8) * 256; a.n2 = a.o_tiles * (a.H / 8) * 256;
+  a.n0 = (int)m->pack_floats(0); a.n1 = (int)m->pack_floats(1); a.n2 = (int)m->pack_floats(2);
   const int total = a.n0 + a.n1 + a.n2 + 2 * a.H + a.o_tiles * 32 + a.O;
   ++m->pack_version;        // (the f16 images of the rollout actor follow the packs' version)
   hipLaunchKernelGGL(policy_flat_load_kernel, dim3(cmbpo_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, d_flat,
@@ -731,18 +718,13 @@ int launch_mlp(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s, int head_override 
   const int head = head_override >= 0 ? head_override : m->head;
   const float *blob = m->d_blob;
   const int E = m->ensemble, H = m->hidden;
-  a.wp0 = reinterpret_cast<const f32x4 *>(blob + m->off_wp0);
-  a.wp1 = reinterpret_cast<const f32x4 *>(blob + m->off_wp1);
-  a.wp2 = reinterpret_cast<const f32x4 *>(blob + m->off_wp2);
-  a.wp0_stride = (size_t)(H / 32) * (m->in_pad / 8) * 64;
-  a.wp1_stride = (size_t)(H / 32) * (H / 8) * 64;
-  a.wp2_stride = (size_t)m->o_tiles * (H / 8) * 64;
+  a.wp0 = reinterpret_cast<const f32x4 *>(m->pack(0));
+  a.wp1 = reinterpret_cast<const f32x4 *>(m->pack(1));
+  a.wp2 = reinterpret_cast<const f32x4 *>(m->pack(2));
+  a.wp0_stride = m->pack_floats(0) / 4; a.wp1_stride = m->pack_floats(1) / 4; a.wp2_stride = m->pack_floats(2) / 4;
   a.b0 = blob + m->off_b0; a.b1 = blob + m->off_b1; a.b2 = blob + m->off_b2;
-  a.in_mu = m->has_in_scaler ? blob + m->off_in_mu : nullptr;
-  a.in_sig = m->has_in_scaler ? blob + m->off_in_var : nullptr;
-  a.out_mu = m->has_out_scaler ? blob + m->off_out_mu : nullptr;
-  a.out_sig = m->has_out_scaler ? blob + m->off_out_var : nullptr;
-  a.out_lsig2 = m->has_out_scaler ? blob + m->off_out_lsig2 : nullptr;
+  a.in_mu = m->in_mu(); a.in_sig = m->in_sig();
+  a.out_mu = m->out_mu(); a.out_sig = m->out_sig(); a.out_lsig2 = m->out_lsig2();
   a.log_std = blob + m->off_log_std;
 #ifdef CMBPO_STAMPS
   a.stamps = g_stamps;

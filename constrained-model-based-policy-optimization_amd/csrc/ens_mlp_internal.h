@@ -1,6 +1,7 @@
 // Internal (not part of the C-ABI): shared between ens_mlp.hip and ens_train.hip.
 #pragma once
 #include "common.h"
+#include "pack_layout.h"
 
 #include <vector>
 
@@ -66,6 +67,17 @@ struct cmbpo_mlp {
   unsigned long h3_version = ~0ul;
   size_t h3_off[3] = {0, 0, 0}, h3_stride[3] = {0, 0, 0}, h3_stats_off = 0;   // 16-B units
   int h3_s0 = 0, h3_otp = 0;   // k-slabs of the input layer, padded output tiles
+  // fp32 pack of layer l (pack_layout.h): n-tiles, k-groups, floats per member, device pointer
+  int pack_tiles(int l) const { return l == 2 ? o_tiles : hidden / 32; }
+  int pack_kg(int l) const { return (l == 0 ? in_pad : hidden) / 8; }
+  size_t pack_floats(int l) const { return ::pack_floats(pack_tiles(l), pack_kg(l)); }
+  float *pack(int l) const { return d_blob + (l == 0 ? off_wp0 : l == 1 ? off_wp1 : off_wp2); }
+  // scalers (nullptr: none)
+  const float *in_mu() const { return has_in_scaler ? d_blob + off_in_mu : nullptr; }
+  const float *in_sig() const { return has_in_scaler ? d_blob + off_in_var : nullptr; }
+  const float *out_mu() const { return has_out_scaler ? d_blob + off_out_mu : nullptr; }
+  const float *out_sig() const { return has_out_scaler ? d_blob + off_out_var : nullptr; }
+  const float *out_lsig2() const { return has_out_scaler ? d_blob + off_out_lsig2 : nullptr; }
 };
 
 // fills the weight / scaler pointers of `a` from the handle and launches the kernel matching (hidden, act, head);

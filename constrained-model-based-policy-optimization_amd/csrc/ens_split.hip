@@ -68,7 +68,7 @@ __device__ __forceinline__ float swishf(float x) { return x * __builtin_amdgcn_r
 __global__ void split_pack_kernel(const float *src, size_t src_stride, int kg, bf16x8 *dst, size_t dst_stride, int n_tiles,
                                   int slabs, int members, int perm) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long per = (long)n_tiles * slabs * 64;
+  const long per = (long)IMAGE_UNITS(n_tiles, slabs, 1);
   if (idx >= per * members) return;
   const int e = (int)(idx / per);
   const int rem = (int)(idx - (long)e * per);
@@ -84,12 +84,12 @@ __global__ void split_pack_kernel(const float *src, size_t src_stride, int kg, b
       k = 128 * (s >> 3) + 32 * ((s >> 1) & 3) + (i & 3) + 8 * (i >> 2) + 4 * h;
     }
     float v = 0.0f;
-    if ((k >> 3) < kg) v = sp[(((size_t)tile * kg + (k >> 3)) * 64 + ((k >> 2) & 1) * 32 + r) * 4 + (k & 3)];
+    if ((k >> 3) < kg) v = sp[pack_index_tile(tile, r, k, kg)];
     if (j < 4) lo[j] = v; else hi[j - 4] = v;
   }
   const Split3 sp3 = split8(lo, hi);
-  bf16x8 *d = dst + (size_t)e * dst_stride + ((size_t)tile * slabs + s) * 3 * 64 + lane;
-  d[0] = sp3.p1; d[64] = sp3.p2; d[128] = sp3.p3;
+  bf16x8 *d = dst + (size_t)e * dst_stride + IMAGE_INDEX(tile, slabs, s, 3, 0) + lane;
+  d[0] = sp3.p1; d[kImageLanes] = sp3.p2; d[2 * kImageLanes] = sp3.p3;
 }
 
 struct SplitArgs {
@@ -113,14 +113,14 @@ template <int BT>
 __device__ __forceinline__ void split_layer(f32x16 (&acc)[NTS][BT], const bf16x8 *wp, int slabs, const float *img, int stride,
                                             int wave, int lane) {
   const int r = lane & 31, h = lane >> 5;
-  const bf16x8 *wa = wp + (size_t)(NTS * wave) * slabs * 3 * 64 + lane;
-  const size_t tstep = (size_t)slabs * 3 * 64;
+  const bf16x8 *wa = wp + IMAGE_UNITS(NTS * wave, slabs, 3) + lane;
+  const size_t tstep = IMAGE_UNITS(1, slabs, 3);
   const float *b0 = img + (size_t)r * stride + 8 * h, *b1 = b0 + (size_t)32 * stride;
   auto load_a = [&](Split3 (&a)[NTS], int s) {
 #pragma unroll
     for (int t = 0; t < NTS; ++t) {
-      const bf16x8 *q = wa + t * tstep + (size_t)s * 192;
-      a[t].p1 = q[0]; a[t].p2 = q[64]; a[t].p3 = q[128];
+      const bf16x8 *q = wa + t * tstep + IMAGE_UNITS(1, s, 3);
+      a[t].p1 = q[0]; a[t].p2 = q[kImageLanes]; a[t].p3 = q[2 * kImageLanes];
     }
   };
   auto read_b = [&](int s) {
@@ -333,8 +333,8 @@ __global__ __launch_bounds__(kThreadsS, (BT == 1 ? 2 : 1)) void ens_split_kernel
         Split3 wa[OT];
 #pragma unroll
         for (int t2 = 0; t2 < OT; ++t2) {
-          const bf16x8 *q = w2 + ((size_t)t2 * S2 + S) * 192;
-          wa[t2].p1 = q[0]; wa[t2].p2 = q[64]; wa[t2].p3 = q[128];
+          const bf16x8 *q = w2 + IMAGE_INDEX(t2, S2, S, 3, 0);
+          wa[t2].p1 = q[0]; wa[t2].p2 = q[kImageLanes]; wa[t2].p3 = q[2 * kImageLanes];
         }
 #pragma unroll
         for (int bt = 0; bt < BT; ++bt) {
@@ -406,11 +406,11 @@ constexpr int HSC = HC + 4;
 // first weight fragments (slab 0) of a layer: the caller requests them ahead of the previous layer's epilogue, so the short
 // layers of a 128-wide member (2 and 8 slabs) do not start with an exposed L2 round trip each
 __device__ __forceinline__ void load_first_rows(Split3 (&a)[4], const bf16x8 *wp, int slabs, int lane) {
-  const size_t tstep = (size_t)slabs * 3 * 64;
+  const size_t tstep = IMAGE_UNITS(1, slabs, 3);
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const bf16x8 *q = wp + lane + t * tstep;
-    a[t].p1 = q[0]; a[t].p2 = q[64]; a[t].p3 = q[128];
+    a[t].p1 = q[0]; a[t].p2 = q[kImageLanes]; a[t].p3 = q[2 * kImageLanes];
   }
 }
 
@@ -419,13 +419,13 @@ __device__ __forceinline__ void split_layer_rows(f32x16 (&acc)[4], Split3 (&A0)[
                                                  const float *rows_img, int stride, int lane) {
   const int r = lane & 31, h = lane >> 5;
   const bf16x8 *wa = wp + lane;
-  const size_t tstep = (size_t)slabs * 3 * 64;
+  const size_t tstep = IMAGE_UNITS(1, slabs, 3);
   const float *b0 = rows_img + (size_t)r * stride + 8 * h;
   auto load_a = [&](Split3 (&a)[4], int s) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const bf16x8 *q = wa + t * tstep + (size_t)s * 192;
-      a[t].p1 = q[0]; a[t].p2 = q[64]; a[t].p3 = q[128];
+      const bf16x8 *q = wa + t * tstep + IMAGE_UNITS(1, s, 3);
+      a[t].p1 = q[0]; a[t].p2 = q[kImageLanes]; a[t].p3 = q[2 * kImageLanes];
     }
   };
   Split3 A1[4], B[2];
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(kThreadsC) void critic_split_kernel(const SplitArgs
     else if (k < 2 * HC) v = p.b1[(size_t)e * HC + (k - HC)];
     else if (k < 3 * HC) {
       const int kk = k - 2 * HC;      // column 0 of the packed W2: pack index of (k = kk, n = 0)
-      v = reinterpret_cast<const float *>(p.wp2 + (size_t)e * p.wp2_stride)[(((size_t)(kk >> 3)) * 64 + ((kk >> 2) & 1) * 32) * 4 + (kk & 3)];
+      v = reinterpret_cast<const float *>(p.wp2 + (size_t)e * p.wp2_stride)[pack_index(kk, 0, HC / 8)];
     } else if (k == 3 * HC) v = p.b2[(size_t)e * p.o_tiles * 32];
     cst[i] = v;
   }
@@ -563,7 +563,7 @@ static int ensure_split(cmbpo_mlp *m, hipStream_t s) {
   if (m->d_split == nullptr) {
     size_t off = 0;
     for (int l = 0; l < 3; ++l) {
-      m->sp_stride[l] = (size_t)tiles[l] * slabs[l] * 3 * 64;
+      m->sp_stride[l] = IMAGE_UNITS(tiles[l], slabs[l], 3);
       m->sp_off[l] = off;
       off += m->sp_stride[l] * E;
     }
@@ -576,14 +576,11 @@ static int ensure_split(cmbpo_mlp *m, hipStream_t s) {
     m->split_version = ~0ul;
   }
   if (m->split_version == m->pack_version) return CMBPO_OK;
-  const size_t src_off[3] = {m->off_wp0, m->off_wp1, m->off_wp2};
-  const int kg[3] = {m->in_pad / 8, H / 8, H / 8};
   for (int l = 0; l < 3; ++l) {
-    const size_t src_stride = (size_t)tiles[l] * kg[l] * 256;
-    const long total = (long)tiles[l] * slabs[l] * 64 * E;
-    hipLaunchKernelGGL(split_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, m->d_blob + src_off[l],
-                       src_stride, kg[l], reinterpret_cast<bf16x8 *>(m->d_split) + m->sp_off[l], m->sp_stride[l], tiles[l],
-                       slabs[l], E, l == 2 ? 1 : 0);
+    const long total = (long)(IMAGE_UNITS(tiles[l], slabs[l], 1) * E);
+    hipLaunchKernelGGL(split_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, m->pack(l), m->pack_floats(l),
+                       m->pack_kg(l), reinterpret_cast<bf16x8 *>(m->d_split) + m->sp_off[l], m->sp_stride[l], tiles[l], slabs[l], E,
+                       l == 2 ? 1 : 0);
   }
   CMBPO_HIP_CHECK(hipGetLastError());
   m->split_version = m->pack_version;

@@ -41,9 +41,8 @@ struct LossArgs {
   const int32_t *idx;      // [E][idx_stride] rows of `targets` (nullptr: row b)
   int idx_stride;
   const float *out_mu, *out_sig;   // output scaler (nullptr: identity)
-  int E, B, O, D, OPk, prob;
-  double *sums;            // [3][E]: sum (mean - t)^2 | sum (var - mse)^2 | sum log_var^2
-  float *d3;               // [E][B][OPk]
+  int E, B, O, D;
+  double *sums;            // [E]: sum (mean - t)^2
 };
 
 __device__ __forceinline__ float scaled_target(const LossArgs &p, int e, int b, int d) {
@@ -55,30 +54,22 @@ __device__ __forceinline__ float scaled_target(const LossArgs &p, int e, int b, 
 
 __global__ __launch_bounds__(kThreads) void loss_sums_kernel(const LossArgs p) {
   const int e = blockIdx.y;
-  double s_mse = 0.0, s_vl = 0.0, s_lv = 0.0;
+  double s_mse = 0.0;
   const int n = p.B * p.D;
   for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
     const int b = i / p.D, d = i - b * p.D;
     const float *orow = p.o + ((size_t)e * p.B + b) * p.O;
     const float diff = orow[d] - scaled_target(p, e, b, d);
-    const float mse = diff * diff;
-    s_mse += (double)mse;
-    if (p.prob) {
-      const float lv = orow[p.D + d];
-      const float dv = expf(lv) - mse;
-      s_vl += (double)(dv * dv);
-      s_lv += (double)(lv * lv);
-    }
+    s_mse += (double)(diff * diff);
   }
-  __shared__ double sm[3][kThreads / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  s_mse = wave_sum(s_mse); s_vl = wave_sum(s_vl); s_lv = wave_sum(s_lv);
-  if (lane == 0) { sm[0][w] = s_mse; sm[1][w] = s_vl; sm[2][w] = s_lv; }
+  __shared__ double sm[kThreads / 64];
+  s_mse = wave_sum(s_mse);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s_mse;
   __syncthreads();
-  if (threadIdx.x < 3) {
+  if (threadIdx.x == 0) {
     double t = 0.0;
-    for (int i = 0; i < kThreads / 64; ++i) t += sm[threadIdx.x][i];
-    atomicAdd(p.sums + (size_t)threadIdx.x * p.E + e, t);
+    for (int i = 0; i < kThreads / 64; ++i) t += sm[i];
+    atomicAdd(p.sums + e, t);
   }
 }
 
@@ -97,12 +88,12 @@ __global__ void loss_finalize_kernel(const double *sums, int E, double inv_count
 struct BwdArgs {
   const f32x4 *wpb2, *wpb1;
   size_t wpb2_stride, wpb1_stride;   // per member, float4 units
-  const float *d3, *g2, *g1;
+  const float *g2, *g1;
   float *d2, *d1;
   int B, OPk;
-  // fused output delta (d3 == nullptr on entry is not used: `fuse` selects): d(train_loss)/d(raw output) computed while
-  // the tile is staged, from the raw outputs, the gathered targets and the forward's per-tile loss statistics
-  int fuse, prob, O, D, n_items;
+  // the output delta d(train_loss)/d(raw output) is computed while the tile is staged, from the raw outputs, the gathered
+  // targets and the forward's per-tile loss statistics; prob: 0 MSE, 1 MSPE, 2 NLL
+  int prob, O, D, n_items;
   const float *o, *targets, *out_mu, *out_sig;
   const int32_t *idx;
   int idx_stride;
@@ -110,6 +101,55 @@ struct BwdArgs {
   float *d3_out;             // [E][B][OPk], written for the weight-gradient kernel
   float *opmax;              // [E * tiles][8]: largest |d1|, |d2|, |d3| of the tile into slots 3..5 (nullptr: not wanted)
 };
+
+// `ratio` of the MSPE loss, 0.05 * mean_all(mse) / mean_all((var - mse)^2): a constant of the step.  The two sums come from
+// the forward's per-tile statistics, added here in tile order by every workgroup of NW waves (same order everywhere:
+// reproducible).  Contains a barrier: the whole workgroup calls it.
+template <int NW>
+__device__ __forceinline__ float mspe_ratio(const BwdArgs &p, int tid) {
+  __shared__ double s_tot[2][NW];
+  double tm = 0.0, tv = 0.0;
+  for (int w = tid; w < p.n_items; w += 64 * NW) {
+    tm += p.loss_part[(size_t)w * 3];
+    tv += p.loss_part[(size_t)w * 3 + 1];
+  }
+  tm = wave_sum(tm); tv = wave_sum(tv);
+  if ((tid & 63) == 0) { s_tot[0][tid >> 6] = tm; s_tot[1][tid >> 6] = tv; }
+  __syncthreads();
+  if constexpr (NW == 4) {
+    tm = (s_tot[0][0] + s_tot[0][1]) + (s_tot[0][2] + s_tot[0][3]);
+    tv = (s_tot[1][0] + s_tot[1][1]) + (s_tot[1][2] + s_tot[1][3]);
+  } else {
+    tm = 0.0; tv = 0.0;
+    for (int w = 0; w < NW; ++w) { tm += s_tot[0][w]; tv += s_tot[1][w]; }
+  }
+  return (float)(0.05 * tm / tv);
+}
+
+// Output delta d(train_loss)/d(raw output k) of batch row `row` (< B) of member e; inv_bd = 1 / (B D).
+// MSPE (pe.py:921-973): total_e = mean (m - t)^2 + ratio * mean (var - sg(mse))^2 + 0.05 * mean_all lv^2; train_loss =
+// sum_e total_e, so the regulariser (a scalar broadcast onto every member) counts E times.
+// MSE (pe.py:911-919): total_e = mean 0.5 (o - t)^2.
+// NLL (pe.py:840-919, inc_var_loss = True; prob == 2): total_e = mean 0.5 exp(-lv) (m - t)^2 + mean 0.5 lv; no
+// coupling between members.  (Its max_logvar / min_logvar variables only carry a constant regulariser gradient
+// and never enter the network, pe.py:198-209,263,789-838: they are host-side bookkeeping, pens.PE.)
+__device__ __forceinline__ float output_delta(const BwdArgs &p, int e, int row, int k, float ratio, float inv_bd) {
+  if (k >= p.O) return 0.0f;
+  const float *orow = p.o + ((size_t)e * p.B + row) * p.O;
+  const int src = p.idx ? p.idx[(size_t)e * p.idx_stride + row] : row;
+  const int dd = (k < p.D) ? k : k - p.D;
+  float t = p.targets[(size_t)src * p.D + dd];
+  if (p.out_mu) t = (t - p.out_mu[dd]) / p.out_sig[dd];
+  const float diff = orow[dd] - t;
+  if (!p.prob) return diff * inv_bd;
+  if (p.prob == 2) {
+    const float iv = expf(-orow[p.D + dd]);
+    return (k < p.D) ? iv * diff * inv_bd : (0.5f - 0.5f * iv * diff * diff) * inv_bd;
+  }
+  if (k < p.D) return 2.0f * diff * inv_bd;
+  const float lv = orow[k], var = expf(lv);
+  return (2.0f * ratio * (var - diff * diff) * var + 0.1f * lv) * inv_bd;
+}
 
 template <int HID>
 __global__ __launch_bounds__(kThreads, 2) void bwd_chain_kernel(const BwdArgs p) {
@@ -122,45 +162,8 @@ __global__ __launch_bounds__(kThreads, 2) void bwd_chain_kernel(const BwdArgs p)
   const int kgo = p.OPk / 8;
   __shared__ float s_dmax[3][kThreads / 64];   // per-wave maxima of |d3|, |d2|, |d1| of this tile
   float dmax = 0.0f;
-  if (!p.fuse) {
-    float *xf = reinterpret_cast<float *>(xbuf);
-    for (int i = tid; i < BB * p.OPk; i += kThreads) {
-      const int b = i / p.OPk, k = i - b * p.OPk;
-      float v = 0.0f;
-      if (row0 + b < p.B) v = p.d3[((size_t)e * p.B + row0 + b) * p.OPk + k];
-      xf[((k >> 2) * BB + b) * 4 + (k & 3)] = v;
-      dmax = fmaxf(dmax, fabsf(v));
-    }
-  } else {
-    // Output deltas d(train_loss)/d(raw output).
-    // MSPE (pe.py:921-973): total_e = mean (m - t)^2 + ratio * mean (var - sg(mse))^2 + 0.05 * mean_all lv^2, with
-    // ratio = 0.05 * mean_all(mse) / mean_all((var - mse)^2) a constant of the step; train_loss = sum_e total_e, so the
-    // regulariser (a scalar broadcast onto every member) counts E times.
-    // MSE (pe.py:911-919): total_e = mean 0.5 (o - t)^2.
-    // The two sums behind `ratio` come from the forward's per-tile statistics, added here in tile order by every
-    // workgroup (same order everywhere: reproducible).
-    // NLL (pe.py:840-919, inc_var_loss = True; prob == 2): total_e = mean 0.5 exp(-lv) (m - t)^2 + mean 0.5 lv; no
-    // coupling between members.  (Its max_logvar / min_logvar variables only carry a constant regulariser gradient
-    // and never enter the network, pe.py:198-209,263,789-838: they are host-side bookkeeping, pens.PE.)
-    __shared__ double s_tot[2][kThreads / 64];
-    float ratio = 0.0f;
-    if (p.prob == 1) {
-      double tm = 0.0, tv = 0.0;
-      for (int w = tid; w < p.n_items; w += kThreads) {
-        tm += p.loss_part[(size_t)w * 3];
-        tv += p.loss_part[(size_t)w * 3 + 1];
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        tm += __shfl_down(tm, o, 64);
-        tv += __shfl_down(tv, o, 64);
-      }
-      if (lane == 0) { s_tot[0][wave] = tm; s_tot[1][wave] = tv; }
-      __syncthreads();
-      tm = (s_tot[0][0] + s_tot[0][1]) + (s_tot[0][2] + s_tot[0][3]);
-      tv = (s_tot[1][0] + s_tot[1][1]) + (s_tot[1][2] + s_tot[1][3]);
-      ratio = (float)(0.05 * tm / tv);
-    }
+  {
+    const float ratio = p.prob == 1 ? mspe_ratio<kThreads / 64>(p, tid) : 0.0f;
     const float inv_bd = 1.0f / ((float)p.B * (float)p.D);
     float *xf = reinterpret_cast<float *>(xbuf);
     for (int i = tid; i < BB * p.OPk; i += kThreads) {
@@ -168,37 +171,14 @@ __global__ __launch_bounds__(kThreads, 2) void bwd_chain_kernel(const BwdArgs p)
       float v = 0.0f;
       const int row = row0 + b;
       if (row < p.B) {
-        if (k < p.O) {
-          const float *orow = p.o + ((size_t)e * p.B + row) * p.O;
-          const int src = p.idx ? p.idx[(size_t)e * p.idx_stride + row] : row;
-          const int dd = (k < p.D) ? k : k - p.D;
-          float t = p.targets[(size_t)src * p.D + dd];
-          if (p.out_mu) t = (t - p.out_mu[dd]) / p.out_sig[dd];
-          const float diff = orow[dd] - t;
-          if (!p.prob) {
-            v = diff * inv_bd;
-          } else if (p.prob == 2) {
-            const float iv = expf(-orow[p.D + dd]);
-            v = (k < p.D) ? iv * diff * inv_bd : (0.5f - 0.5f * iv * diff * diff) * inv_bd;
-          } else if (k < p.D) {
-            v = 2.0f * diff * inv_bd;
-          } else {
-            const float lv = orow[k], var = expf(lv);
-            v = (2.0f * ratio * (var - diff * diff) * var + 0.1f * lv) * inv_bd;
-          }
-        }
+        v = output_delta(p, e, row, k, ratio, inv_bd);
         p.d3_out[((size_t)e * p.B + row) * p.OPk + k] = v;
       }
       xf[((k >> 2) * BB + b) * 4 + (k & 3)] = v;
       dmax = fmaxf(dmax, fabsf(v));
     }
   }
-  auto wave_max_to = [&](float m, float *slot) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if (lane == 0) slot[wave] = m;
-  };
-  wave_max_to(dmax, s_dmax[0]);
+  if (const float wm = wave_max(dmax); lane == 0) s_dmax[0][wave] = wm;
   dmax = 0.0f;
   const int j = lane & 31, h = lane >> 5;
   const bool valid = row0 + j < p.B;
@@ -226,7 +206,7 @@ __global__ __launch_bounds__(kThreads, 2) void bwd_chain_kernel(const BwdArgs p)
   load_g(p.g2);      // in flight under the first GEMM
   zero_acc();
   __syncthreads();
-  mfma_layer<NT, 1>(p.wpb2 + e * p.wpb2_stride + (size_t)(wave * NT) * kgo * 64, (size_t)kgo * 64, 0, kgo, xbuf, lane, acc);
+  mfma_layer<NT, 1>(p.wpb2 + e * p.wpb2_stride + PACK_VEC4S(wave * NT, kgo), PACK_VEC4S(1, kgo), 0, kgo, xbuf, lane, acc);
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -241,12 +221,12 @@ __global__ __launch_bounds__(kThreads, 2) void bwd_chain_kernel(const BwdArgs p)
         dmax = fmaxf(fmaxf(dmax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
       }
     }
-  wave_max_to(dmax, s_dmax[1]);
+  if (const float wm = wave_max(dmax); lane == 0) s_dmax[1][wave] = wm;
   dmax = 0.0f;
   load_g(p.g1);
   zero_acc();
   __syncthreads();
-  mfma_layer<NT, 1>(p.wpb1 + e * p.wpb1_stride + (size_t)(wave * NT) * KG_H * 64, (size_t)KG_H * 64, 0, KG_H, hbuf, lane, acc);
+  mfma_layer<NT, 1>(p.wpb1 + e * p.wpb1_stride + PACK_VEC4S(wave * NT, KG_H), PACK_VEC4S(1, KG_H), 0, KG_H, hbuf, lane, acc);
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -261,7 +241,7 @@ __global__ __launch_bounds__(kThreads, 2) void bwd_chain_kernel(const BwdArgs p)
       }
     }
   if (p.opmax) {
-    wave_max_to(dmax, s_dmax[2]);
+    if (const float wm = wave_max(dmax); lane == 0) s_dmax[2][wave] = wm;
     __syncthreads();
     if (tid < 3) {
       const float *sm = s_dmax[2 - tid];      // slots 3, 4, 5 = d1, d2, d3
@@ -314,59 +294,19 @@ __global__ __launch_bounds__(kBhThreads) void bwd_chain_h_kernel(const BwdHArgs 
   const float *st = a.stats + (size_t)e * NSTAT;
   if (tid < kBhRows) s_rowmax[tid] = 0u;
   float dmax = 0.0f;
-  // ---- output deltas (the fp32 kernel's arithmetic, operation for operation) -> fp32 tile, row maxima ---------------------
+  // ---- output deltas -> fp32 tile, row maxima ----------------------------------------------------------------------------
   {
-    __shared__ double s_tot[2][kBhThreads / 64];
     float ratio = 0.0f;
-    if (p.prob == 1) {
-      double tm = 0.0, tv = 0.0;
-      for (int w = tid; w < p.n_items; w += kBhThreads) {
-        tm += p.loss_part[(size_t)w * 3];
-        tv += p.loss_part[(size_t)w * 3 + 1];
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        tm += __shfl_down(tm, o, 64);
-        tv += __shfl_down(tv, o, 64);
-      }
-      if (lane == 0) { s_tot[0][wave] = tm; s_tot[1][wave] = tv; }
-      __syncthreads();
-      tm = 0.0; tv = 0.0;
-      for (int w = 0; w < kBhThreads / 64; ++w) { tm += s_tot[0][w]; tv += s_tot[1][w]; }
-      ratio = (float)(0.05 * tm / tv);
-    } else {
-      __syncthreads();
-    }
+    if (p.prob == 1) ratio = mspe_ratio<kBhThreads / 64>(p, tid);
+    else __syncthreads();        // s_rowmax is cleared
     const float inv_bd = 1.0f / ((float)p.B * (float)p.D);
     for (int i = tid; i < kBhRows * p.OPk; i += kBhThreads) {
       const int b = i / p.OPk, k = i - b * p.OPk;
       float v = 0.0f;
       const int row = row0 + b;
       if (row < p.B) {
-        if (p.fuse) {
-          if (k < p.O) {
-            const float *orow = p.o + ((size_t)e * p.B + row) * p.O;
-            const int src = p.idx ? p.idx[(size_t)e * p.idx_stride + row] : row;
-            const int dd = (k < p.D) ? k : k - p.D;
-            float t = p.targets[(size_t)src * p.D + dd];
-            if (p.out_mu) t = (t - p.out_mu[dd]) / p.out_sig[dd];
-            const float diff = orow[dd] - t;
-            if (!p.prob) {
-              v = diff * inv_bd;
-            } else if (p.prob == 2) {
-              const float iv = expf(-orow[p.D + dd]);
-              v = (k < p.D) ? iv * diff * inv_bd : (0.5f - 0.5f * iv * diff * diff) * inv_bd;
-            } else if (k < p.D) {
-              v = 2.0f * diff * inv_bd;
-            } else {
-              const float lv = orow[k], var = expf(lv);
-              v = (2.0f * ratio * (var - diff * diff) * var + 0.1f * lv) * inv_bd;
-            }
-          }
-          p.d3_out[((size_t)e * p.B + row) * p.OPk + k] = v;
-        } else {
-          v = p.d3[((size_t)e * p.B + row) * p.OPk + k];
-        }
+        v = output_delta(p, e, row, k, ratio, inv_bd);
+        p.d3_out[((size_t)e * p.B + row) * p.OPk + k] = v;
       }
       d3f[b * p.OPk + k] = v;
       const float av = fabsf(v);
@@ -374,12 +314,7 @@ __global__ __launch_bounds__(kBhThreads) void bwd_chain_h_kernel(const BwdHArgs 
       if (av > 0.0f) atomicMax(&s_rowmax[b], __float_as_uint(av));     // (non-negative floats order like their bit patterns)
     }
   }
-  auto wave_max_to = [&](float m, float *slot) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if (lane == 0) slot[wave] = m;
-  };
-  wave_max_to(dmax, s_dmax[0]);
+  if (const float wm = wave_max(dmax); lane == 0) s_dmax[0][wave] = wm;
   dmax = 0.0f;
   __syncthreads();
   if (tid < kBhRows) {
@@ -439,14 +374,14 @@ __global__ __launch_bounds__(kBhThreads) void bwd_chain_h_kernel(const BwdHArgs 
   load_g(p.g2);
   zero_acc();
   {
-    const f16x8 *w2 = a.w2t + (size_t)e * a.w2t_stride + lane;       // + ((tile * s3 + s) * 2 + piece) * 64
+    const f16x8 *w2 = a.w2t + (size_t)e * a.w2t_stride + lane;
     f16x8 A2[4][2][2];
 #pragma unroll
     for (int s = 0; s < 4; ++s)
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        const f16x8 *q = w2 + ((size_t)((2 * wave + t) * a.s3 + (s < a.s3 ? s : 0)) * 2) * 64;
-        A2[s][t][0] = q[0]; A2[s][t][1] = q[64];
+        const f16x8 *q = w2 + IMAGE_INDEX(2 * wave + t, a.s3, s < a.s3 ? s : 0, 2, 0);
+        A2[s][t][0] = q[0]; A2[s][t][1] = q[kImageLanes];
       }
     __syncthreads();           // the d3 image is complete
 #pragma unroll
@@ -485,20 +420,20 @@ __global__ __launch_bounds__(kBhThreads) void bwd_chain_h_kernel(const BwdHArgs 
         *reinterpret_cast<uint2 *>(c1 + (size_t)kBhRows * kBhD2Str) = make_uint2(q2[0], q2[1]);
       }
   }
-  wave_max_to(dmax, s_dmax[1]);
+  if (const float wm = wave_max(dmax); lane == 0) s_dmax[1][wave] = wm;
   dmax = 0.0f;
   // ---- d1 = (d2 W1^T) * g1 -----------------------------------------------------------------------------------------------
   load_g(p.g1);
   zero_acc();
   {
-    const f16x8 *w1 = a.w1t + (size_t)e * a.w1t_stride + lane;       // + ((tile * 32 + s) * 2 + piece) * 64
+    const f16x8 *w1 = a.w1t + (size_t)e * a.w1t_stride + lane;
     constexpr int S1 = kBhHid / 16, RING = 3;
     f16x8 A1[RING][2][2];
     auto load_a = [&](f16x8 (&x)[2][2], int s) {
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        const f16x8 *q = w1 + ((size_t)((2 * wave + t) * S1 + s) * 2) * 64;
-        x[t][0] = q[0]; x[t][1] = q[64];
+        const f16x8 *q = w1 + IMAGE_INDEX(2 * wave + t, S1, s, 2, 0);
+        x[t][0] = q[0]; x[t][1] = q[kImageLanes];
       }
     };
 #pragma unroll
@@ -534,7 +469,7 @@ __global__ __launch_bounds__(kBhThreads) void bwd_chain_h_kernel(const BwdHArgs 
       }
   }
   if (p.opmax) {
-    wave_max_to(dmax, s_dmax[2]);
+    if (const float wm = wave_max(dmax); lane == 0) s_dmax[2][wave] = wm;
     __syncthreads();
     if (tid < 3) {
       const float *sm = s_dmax[2 - tid];      // slots 3, 4, 5 = d1, d2, d3
@@ -642,12 +577,7 @@ __global__ __launch_bounds__(kBhThreads) void fwd_train_h_kernel(const FwdHArgs 
       }
     }
   }
-  auto wave_max_to = [&](float m, float *slot) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if (lane == 0) slot[wave] = m;
-  };
-  wave_max_to(xmax_t, s_opmax[0]);
+  if (const float wm = wave_max(xmax_t); lane == 0) s_opmax[0][wave] = wm;
   const bool valid[2] = {row0 + r < a.n_rows, row0 + 32 + r < a.n_rows};
   const size_t grow[2] = {((size_t)e * a.n_rows + row0 + r) * kBhHid, ((size_t)e * a.n_rows + row0 + 32 + r) * kBhHid};
   f32x16 acc[2][2];
@@ -695,7 +625,7 @@ __global__ __launch_bounds__(kBhThreads) void fwd_train_h_kernel(const FwdHArgs 
       if (hm > 0.0f) atomicMax(&rowmax[32 * bt + r], __float_as_uint(hm));
       if (valid[bt]) hmax_t = fmaxf(hmax_t, hm);
     }
-    wave_max_to(hmax_t, opslot);
+    if (const float wm = wave_max(hmax_t); lane == 0) opslot[wave] = wm;
   };
   auto split_image = [&](const unsigned *rowmax, float s_w, float (&inv_next)[2]) {
 #pragma unroll
@@ -719,14 +649,14 @@ __global__ __launch_bounds__(kBhThreads) void fwd_train_h_kernel(const FwdHArgs 
   // ---- layer 0 -----------------------------------------------------------------------------------------------------------
   zero_acc();
   {
-    const f16x8 *w0 = a.w0 + (size_t)e * a.w0_stride + lane;       // + ((tile * s0 + s) * 2 + piece) * 64
+    const f16x8 *w0 = a.w0 + (size_t)e * a.w0_stride + lane;
     f16x8 A0[4][2][2];
 #pragma unroll
     for (int s = 0; s < 4; ++s)
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        const f16x8 *q = w0 + ((size_t)((2 * wave + t) * a.s0 + (s < a.s0 ? s : 0)) * 2) * 64;
-        A0[s][t][0] = q[0]; A0[s][t][1] = q[64];
+        const f16x8 *q = w0 + IMAGE_INDEX(2 * wave + t, a.s0, s < a.s0 ? s : 0, 2, 0);
+        A0[s][t][0] = q[0]; A0[s][t][1] = q[kImageLanes];
       }
     __syncthreads();           // the x image and the rows' lifts are complete
 #pragma unroll
@@ -748,14 +678,14 @@ __global__ __launch_bounds__(kBhThreads) void fwd_train_h_kernel(const FwdHArgs 
   // ---- layer 1 -----------------------------------------------------------------------------------------------------------
   zero_acc();
   {
-    const f16x8 *w1 = a.w1 + (size_t)e * a.w1_stride + lane;       // + ((tile * 32 + s) * 2 + piece) * 64
+    const f16x8 *w1 = a.w1 + (size_t)e * a.w1_stride + lane;
     constexpr int S1 = kBhHid / 16, RING = 3;
     f16x8 A1[RING][2][2];
     auto load_a = [&](f16x8 (&x)[2][2], int s) {
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        const f16x8 *q = w1 + ((size_t)((2 * wave + t) * S1 + s) * 2) * 64;
-        x[t][0] = q[0]; x[t][1] = q[64];
+        const f16x8 *q = w1 + IMAGE_INDEX(2 * wave + t, S1, s, 2, 0);
+        x[t][0] = q[0]; x[t][1] = q[kImageLanes];
       }
     };
 #pragma unroll
@@ -780,17 +710,17 @@ __global__ __launch_bounds__(kBhThreads) void fwd_train_h_kernel(const FwdHArgs 
   // ---- output layer: waves 0-3, one (output tile, row tile) pair each ---------------------------------------------------
   if (wave < 4) {
     const int tt = wave & 1, bt = wave >> 1;
-    const f16x8 *w2 = a.w2 + (size_t)e * a.w2_stride + lane + (size_t)tt * 32 * 2 * 64;    // + (s * 2 + piece) * 64
+    constexpr int S1 = kBhHid / 16;
+    const f16x8 *w2 = a.w2 + (size_t)e * a.w2_stride + lane + IMAGE_UNITS(tt, S1, 2);
     f32x16 o;
 #pragma unroll
     for (int i = 0; i < 16; ++i) o[i] = 0.0f;
-    constexpr int S1 = kBhHid / 16;
     f16x8 A2[2][2];
-    A2[0][0] = w2[0]; A2[0][1] = w2[64];
+    A2[0][0] = w2[0]; A2[0][1] = w2[kImageLanes];
 #pragma unroll 4
     for (int s = 0; s < S1; ++s) {
       const int sn = s + 1 < S1 ? s + 1 : s;
-      A2[(s + 1) & 1][0] = w2[(size_t)sn * 128]; A2[(s + 1) & 1][1] = w2[(size_t)sn * 128 + 64];
+      A2[(s + 1) & 1][0] = w2[IMAGE_UNITS(1, sn, 2)]; A2[(s + 1) & 1][1] = w2[IMAGE_UNITS(1, sn, 2) + kImageLanes];
       f16x8 bf[2];
       read_b(bf, himg, kBhD2Str, bt, s);
       mm3(o, A2[s & 1][0], A2[s & 1][1], bf[0], bf[1]);
@@ -838,12 +768,7 @@ __global__ __launch_bounds__(kBhThreads) void fwd_train_h_kernel(const FwdHArgs 
       }
     }
     __shared__ double s_loss[3][kBhThreads / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      s0 += __shfl_down(s0, o, 64);
-      s1 += __shfl_down(s1, o, 64);
-      s2 += __shfl_down(s2, o, 64);
-    }
+    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
     if (lane == 0) { s_loss[0][wave] = s0; s_loss[1][wave] = s1; s_loss[2][wave] = s2; }
     __syncthreads();
     if (tid < 3) {
@@ -1081,8 +1006,7 @@ __device__ __forceinline__ void wgrad_f16_body(const WgradArgs &p, char *smem, i
       ma = fmaxf(ma, p.amax[((size_t)e * p.max_tiles + k) * kOpMax]);
       mb = fmaxf(mb, p.bmax[((size_t)e * p.max_tiles + k) * kOpMax]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { ma = fmaxf(ma, __shfl_xor(ma, o, 64)); mb = fmaxf(mb, __shfl_xor(mb, o, 64)); }
+    ma = wave_max(ma); mb = wave_max(mb);
     float *red = reinterpret_cast<float *>(smem);
     if (lane == 0) { red[wave] = ma; red[4 + wave] = mb; }
     __syncthreads();
@@ -1339,7 +1263,7 @@ __device__ __forceinline__ void load_frags(f32x4 (&a)[KG], const f32x4 *wp, int 
 #pragma unroll
   for (int g = 0; g < KG; ++g) {
     a[g] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    if (g < kg) a[g] = wp[(size_t)g * 64 + lane];
+    if (g < kg) a[g] = wp[PACK_VEC4S(1, g) + lane];
   }
 }
 
@@ -1382,10 +1306,10 @@ __global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const Fused
 
   // ---- the member's weights, once: forward fragments in registers, W1^T and the biases in LDS -----------------
   f32x4 f0[KG0], f1[KGH], f2[4], bk2[4];
-  load_frags<KG0>(f0, p.F0 + e * p.sF0 + (size_t)wave * p.kg0 * 64, p.kg0, lane);
-  load_frags<KGH>(f1, p.F1 + e * p.sF1 + (size_t)wave * KGH * 64, KGH, lane);
-  load_frags<4>(f2, p.F2 + e * p.sF2 + (size_t)wave * 4 * 64, 4, lane);        // K split: k-groups 4w .. 4w + 3
-  load_frags<4>(bk2, p.B2 + e * p.sB2 + (size_t)wave * p.kga * 64, p.kga, lane);
+  load_frags<KG0>(f0, p.F0 + e * p.sF0 + PACK_VEC4S(wave, p.kg0), p.kg0, lane);
+  load_frags<KGH>(f1, p.F1 + e * p.sF1 + PACK_VEC4S(wave, KGH), KGH, lane);
+  load_frags<4>(f2, p.F2 + e * p.sF2 + PACK_VEC4S(1, wave * 4), 4, lane);        // K split: k-groups 4w .. 4w + 3
+  load_frags<4>(bk2, p.B2 + e * p.sB2 + PACK_VEC4S(wave, p.kga), p.kga, lane);
   {
     const f32x4 *src = p.B1 + e * p.sB1;
     f32x4 tmp[KGH];
@@ -1395,7 +1319,7 @@ __global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const Fused
     for (int u = 0; u < KGH; ++u) bk1L[tid + u * kThreads] = tmp[u];
     biasL[tid] = (tid < HID) ? p.b0[(size_t)e * HID + tid] : p.b1[(size_t)e * HID + tid - HID];
   }
-  const f32x4 *bk1W = bk1L + (size_t)wave * KGH * 64 + lane;
+  const f32x4 *bk1W = bk1L + PACK_VEC4S(wave, KGH) + lane;
   const float *b2 = p.b2 + (size_t)e * p.b2_ld;
 
   f32x16 gW1[4], gW0[N_IT], gW2;
@@ -1529,7 +1453,7 @@ __global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const Fused
       const float *rl = d2R + j * RS + 4 * h;
 #pragma unroll
       for (int g = 0; g < KGH; ++g) {
-        const f32x4 a = bk1W[g * 64], b = *reinterpret_cast<const f32x4 *>(rl + 8 * g);
+        const f32x4 a = bk1W[PACK_VEC4S(1, g)], b = *reinterpret_cast<const f32x4 *>(rl + 8 * g);
 #pragma unroll
         for (int s2 = 0; s2 < 4; ++s2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s2], b[s2], acc, 0, 0, 0);
       }
@@ -1603,10 +1527,6 @@ struct AdamWArgs {
                                            // a member's elements are a whole number of blocks: the f16 backward chain lifts W^T by it
 };
 
-__device__ __forceinline__ size_t pack_index(int k, int n, int kg) {
-  return ((((size_t)(n >> 5) * kg + (k >> 3)) * 64 + ((k >> 2) & 1) * 32 + (n & 31)) << 2) + (k & 3);
-}
-
 __device__ __forceinline__ void adam_w(const AdamWArgs &p, unsigned block) {
   const size_t per = (size_t)p.K * p.N;
   const size_t i = (size_t)block * kThreads + threadIdx.x;
@@ -1632,9 +1552,7 @@ __device__ __forceinline__ void adam_w(const AdamWArgs &p, unsigned block) {
   }
   if (p.wmax_part) {      // (uniform per tensor)
     __shared__ float s_wm[kThreads / 64];
-    float m = fabsf(w);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    const float m = wave_max(fabsf(w));
     if ((threadIdx.x & 63) == 0) s_wm[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) p.wmax_part[block] = fmaxf(fmaxf(s_wm[0], s_wm[1]), fmaxf(s_wm[2], s_wm[3]));
@@ -1662,7 +1580,7 @@ __global__ __launch_bounds__(kThreads) void train_pack_all_kernel(const PackAllA
   for (int i = 1; i < 5; ++i)
     if (i < p.n_img && blockIdx.x >= p.first[i]) img = i;
   const int tid = threadIdx.x;
-  const long per = (long)p.n_tiles[img] * p.slabs[img] * 64;       // lanes of one member's image
+  const long per = (long)IMAGE_UNITS(p.n_tiles[img], p.slabs[img], 1);       // lanes of one member's image
   const long idx = (long)(blockIdx.x - p.first[img]) * kThreads + tid;
   const int e = (int)(idx / per);
   const int l = p.layer[img];
@@ -1672,8 +1590,7 @@ __global__ __launch_bounds__(kThreads) void train_pack_all_kernel(const PackAllA
   {
     const float *part = p.wmax[l] + (size_t)e * p.blocks[l];
     for (int i = tid; i < p.blocks[l]; i += kThreads) m = fmaxf(m, part[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = wave_max(m);
     if ((tid & 63) == 0) s_m[tid >> 6] = m;
     __syncthreads();
     m = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
@@ -1693,13 +1610,13 @@ __global__ __launch_bounds__(kThreads) void train_pack_all_kernel(const PackAllA
   for (int j = 0; j < 8; ++j) {
     const int k = 16 * sl + 8 * h + j;
     float v = 0.0f;
-    if (tile < p.src_tiles[img] && (k >> 3) < kg) v = sp[(((size_t)tile * kg + (k >> 3)) * 64 + ((k >> 2) & 1) * 32 + r) * 4 + (k & 3)];
+    if (tile < p.src_tiles[img] && (k >> 3) < kg) v = sp[pack_index_tile(tile, r, k, kg)];
     _Float16 q1, q2;
     split_h(v * scale, q1, q2);
     p1[j] = q1; p2[j] = q2;
   }
-  f16x8 *d = p.dst[img] + (size_t)e * p.dst_stride[img] + ((size_t)tile * p.slabs[img] + sl) * 2 * 64 + lane;
-  d[0] = p1; d[64] = p2;
+  f16x8 *d = p.dst[img] + (size_t)e * p.dst_stride[img] + IMAGE_INDEX(tile, p.slabs[img], sl, 2, 0) + lane;
+  d[0] = p1; d[kImageLanes] = p2;
 }
 
 struct AdamBArgs {
@@ -1763,7 +1680,8 @@ struct cmbpo_trainer {
   int fused;                     // 1: fused_mse_step_kernel computes the whole gradient
   float *pool;                   // one allocation
   float *W[3], *Bv[3], *mW[3], *vW[3], *mB[3], *vB[3];
-  float *wpb1, *wpb2;
+  float *wpb1, *wpb2;             // backward packs: W1^T, W2^T in the layout of the forward packs
+  size_t wpb1_floats, wpb2_floats;   // per member (the forward packs': cmbpo_mlp::pack_floats)
   float *x, *h1, *g1, *h2, *g2, *o, *d3, *d2, *d1;
   float *parts[3], *dB[3];
   double *sums;
@@ -1775,6 +1693,7 @@ struct cmbpo_trainer {
   void *b16 = nullptr;           // one allocation: W1^T | W2^T | W0 | W1 | W2 images | stats | block maxima of |W0|, |W1|, |W2|
   size_t b16_w2t_off = 0, b16_f_off[3] = {0, 0, 0}, b16_stats_off = 0;   // 16-byte units
   int b16_s3 = 0, b16_s0 = 0;    // k-slabs of the backward chain's first product / of the input layer
+  size_t b16_w1_units = 0, b16_w2t_units = 0, b16_w0_units = 0, b16_w2_units = 0;   // per member: W1^T and W1 | W2^T | W0 | W2
   int b16_blocks[3] = {0, 0, 0}; // 256-element blocks per member of W0, W1, W2 (Adam leaves each block's largest |w|)
   bool b16_fwd = false;          // the training forward runs on the f16 path too (probabilistic head, <= 64 inputs / outputs)
   unsigned long b16_version = ~0ul;   // pack version the images were built from
@@ -1875,7 +1794,6 @@ int prepare_f16(cmbpo_trainer *t, hipStream_t s) {
   f16x8 *base = reinterpret_cast<f16x8 *>(t->b16);
   float *stats = reinterpret_cast<float *>(base + t->b16_stats_off);
   float *wm0 = stats + (size_t)E * NSTAT, *wm1 = wm0 + (size_t)E * t->b16_blocks[0], *wm2 = wm1 + (size_t)E * t->b16_blocks[1];
-  const size_t w1t_stride = (size_t)(H / 32) * (H / 16) * 2 * 64, w2t_stride = (size_t)(H / 32) * t->b16_s3 * 2 * 64;
   PackAllArgs pa{};
   pa.wmax[0] = wm0; pa.wmax[1] = wm1; pa.wmax[2] = wm2;
   for (int l = 0; l < 3; ++l) pa.blocks[l] = t->b16_blocks[l];
@@ -1888,18 +1806,15 @@ int prepare_f16(cmbpo_trainer *t, hipStream_t s) {
     pa.dst[n] = dst; pa.dst_stride[n] = dst_stride; pa.n_tiles[n] = n_tiles; pa.slabs[n] = slabs; pa.layer[n] = layer;
     pa.writes_stats[n] = writes;
     pa.first[n] = blocks;
-    blocks += (unsigned)((size_t)n_tiles * slabs * 64 * E / kThreads);
+    blocks += (unsigned)(IMAGE_UNITS(n_tiles, slabs, 1) * E / kThreads);
     ++n;
   };
-  add(t->wpb1, (size_t)(H / 32) * (H / 8) * 256, H / 8, H / 32, base, w1t_stride, H / 32, H / 16, 1, 1);
-  add(t->wpb2, (size_t)(H / 32) * (t->OPk / 8) * 256, t->OPk / 8, H / 32, base + t->b16_w2t_off, w2t_stride, H / 32, t->b16_s3, 2, 1);
+  add(t->wpb1, t->wpb1_floats, H / 8, H / 32, base, t->b16_w1_units, H / 32, H / 16, 1, 1);
+  add(t->wpb2, t->wpb2_floats, t->OPk / 8, H / 32, base + t->b16_w2t_off, t->b16_w2t_units, H / 32, t->b16_s3, 2, 1);
   if (t->b16_fwd) {
-    float *blob = m->d_blob;
-    add(blob + m->off_wp0, (size_t)(H / 32) * (t->IP / 8) * 256, t->IP / 8, H / 32, base + t->b16_f_off[0],
-        (size_t)(H / 32) * t->b16_s0 * 2 * 64, H / 32, t->b16_s0, 0, 1);
-    add(blob + m->off_wp1, (size_t)(H / 32) * (H / 8) * 256, H / 8, H / 32, base + t->b16_f_off[1], w1t_stride, H / 32, H / 16, 1, 0);
-    add(blob + m->off_wp2, (size_t)m->o_tiles * (H / 8) * 256, H / 8, m->o_tiles, base + t->b16_f_off[2], (size_t)2 * (H / 16) * 2 * 64, 2,
-        H / 16, 2, 0);
+    add(m->pack(0), m->pack_floats(0), m->pack_kg(0), H / 32, base + t->b16_f_off[0], t->b16_w0_units, H / 32, t->b16_s0, 0, 1);
+    add(m->pack(1), m->pack_floats(1), m->pack_kg(1), H / 32, base + t->b16_f_off[1], t->b16_w1_units, H / 32, H / 16, 1, 0);
+    add(m->pack(2), m->pack_floats(2), m->pack_kg(2), m->o_tiles, base + t->b16_f_off[2], t->b16_w2_units, 2, H / 16, 2, 0);
   }
   pa.first[n] = blocks;
   pa.n_img = n;
@@ -1910,19 +1825,18 @@ int prepare_f16(cmbpo_trainer *t, hipStream_t s) {
 }
 
 int launch_bwd_h(cmbpo_trainer *t, const BwdArgs &b, int batch, hipStream_t s) {
-  const int E = t->E, H = t->H;
   if (int rc = prepare_f16(t, s)) return rc;
   f16x8 *base = reinterpret_cast<f16x8 *>(t->b16);
   BwdHArgs a{};
   a.b = b;
   a.w1t = base; a.w2t = base + t->b16_w2t_off;
-  a.w1t_stride = (size_t)(H / 32) * (H / 16) * 2 * 64; a.w2t_stride = (size_t)(H / 32) * t->b16_s3 * 2 * 64;
+  a.w1t_stride = t->b16_w1_units; a.w2t_stride = t->b16_w2t_units;
   a.stats = reinterpret_cast<const float *>(base + t->b16_stats_off);
   a.s3 = t->b16_s3;
   a.tiles32 = cmbpo_ceil_div(batch, 32);
   const size_t lds = bh_lds_bytes(t->b16_s3);
   if (int rc = cmbpo_grant_lds(bwd_chain_h_kernel, lds)) return rc;
-  hipLaunchKernelGGL(bwd_chain_h_kernel, dim3(cmbpo_ceil_div(batch, kBhRows), E), dim3(kBhThreads), lds, s, a);
+  hipLaunchKernelGGL(bwd_chain_h_kernel, dim3(cmbpo_ceil_div(batch, kBhRows), t->E), dim3(kBhThreads), lds, s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1931,17 +1845,14 @@ int launch_bwd_h(cmbpo_trainer *t, const BwdArgs &b, int batch, hipStream_t s) {
 int launch_fwd_h(cmbpo_trainer *t, const float *d_inputs, const int32_t *d_idx, int idx_stride, int rows, bool exports, hipStream_t s,
                  const float *d_targets) {
   cmbpo_mlp *m = t->m;
-  const int H = t->H;
   if (int rc = prepare_f16(t, s)) return rc;
   f16x8 *base = reinterpret_cast<f16x8 *>(t->b16);
   FwdHArgs a{};
   a.inputs = d_inputs; a.idx = d_idx; a.idx_stride = idx_stride;
   a.n_rows = rows; a.I = t->I; a.IP = t->IP; a.s0 = t->b16_s0;
-  a.in_mu = m->has_in_scaler ? m->d_blob + m->off_in_mu : nullptr;
-  a.in_sig = m->has_in_scaler ? m->d_blob + m->off_in_var : nullptr;
+  a.in_mu = m->in_mu(); a.in_sig = m->in_sig();
   a.w0 = base + t->b16_f_off[0]; a.w1 = base + t->b16_f_off[1]; a.w2 = base + t->b16_f_off[2];
-  a.w0_stride = (size_t)(H / 32) * t->b16_s0 * 2 * 64; a.w1_stride = (size_t)(H / 32) * (H / 16) * 2 * 64;
-  a.w2_stride = (size_t)2 * (H / 16) * 2 * 64;
+  a.w0_stride = t->b16_w0_units; a.w1_stride = t->b16_w1_units; a.w2_stride = t->b16_w2_units;
   a.b0 = m->d_blob + m->off_b0; a.b1 = m->d_blob + m->off_b1; a.b2 = m->d_blob + m->off_b2; a.b2_ld = m->o_tiles * 32;
   a.stats = reinterpret_cast<const float *>(base + t->b16_stats_off);
   a.O = t->O; a.D = t->D;
@@ -1949,8 +1860,7 @@ int launch_fwd_h(cmbpo_trainer *t, const float *d_inputs, const int32_t *d_idx, 
   a.o = t->o;
   if (d_targets) {
     a.targets = d_targets; a.loss_part = t->loss_part;
-    a.out_mu = m->has_out_scaler ? m->d_blob + m->off_out_mu : nullptr;
-    a.out_sig = m->has_out_scaler ? m->d_blob + m->off_out_var : nullptr;
+    a.out_mu = m->out_mu(); a.out_sig = m->out_sig();
   }
   a.tiles32 = cmbpo_ceil_div(rows, 32);
   if (int rc = cmbpo_grant_lds(fwd_train_h_kernel, fh_lds_bytes())) return rc;
@@ -1965,13 +1875,9 @@ int launch_update(cmbpo_trainer *t, int apply, float lr_t, hipStream_t s) {
   ++m->pack_version;   // the packed images change: derived images (ens_split.hip) are stale
   const int E = t->E, H = t->H;
   const int Ks[3] = {t->I, H, H}, Ns[3] = {H, H, t->O};
-  float *fwd[3] = {m->d_blob + m->off_wp0, m->d_blob + m->off_wp1, m->d_blob + m->off_wp2};
-  const int f_kg[3] = {t->IP / 8, H / 8, H / 8};
-  const size_t f_stride[3] = {(size_t)(H / 32) * (t->IP / 8) * 256, (size_t)(H / 32) * (H / 8) * 256,
-                              (size_t)m->o_tiles * (H / 8) * 256};
   float *bwd[3] = {nullptr, t->wpb1, t->wpb2};
   const int b_kg[3] = {0, H / 8, t->OPk / 8};
-  const size_t b_stride[3] = {0, (size_t)(H / 32) * (H / 8) * 256, (size_t)(H / 32) * (t->OPk / 8) * 256};
+  const size_t b_stride[3] = {0, t->wpb1_floats, t->wpb2_floats};
   float *blob_b[3] = {m->d_blob + m->off_b0, m->d_blob + m->off_b1, m->d_blob + m->off_b2};
   const int blob_ld[3] = {H, H, m->o_tiles * 32};
   AdamAllArgs all{};
@@ -1982,7 +1888,7 @@ int launch_update(cmbpo_trainer *t, int apply, float lr_t, hipStream_t s) {
     a.parts = t->parts[l]; a.n_parts = t->ks[l]; a.part_stride = t->wsize[l];
     a.decay = t->decay[l];
     a.E = E; a.K = Ks[l]; a.N = Ns[l];
-    a.fwd = fwd[l]; a.f_kg = f_kg[l]; a.f_stride = f_stride[l];
+    a.fwd = m->pack(l); a.f_kg = m->pack_kg(l); a.f_stride = m->pack_floats(l);
     a.bwd = bwd[l]; a.b_kg = b_kg[l]; a.b_stride = b_stride[l];
     a.lr_t = lr_t; a.b1 = t->b1; a.b2 = t->b2; a.eps = t->eps; a.apply = apply;
     a.wmax_part = nullptr;
@@ -2012,22 +1918,17 @@ int launch_update(cmbpo_trainer *t, int apply, float lr_t, hipStream_t s) {
 int launch_fused(cmbpo_trainer *t, const float *d_inputs, const float *d_targets, const int32_t *d_idx, int idx_stride,
                  int batch, hipStream_t s) {
   cmbpo_mlp *m = t->m;
-  const int H = t->H;
   FusedArgs a{};
-  a.F0 = reinterpret_cast<const f32x4 *>(m->d_blob + m->off_wp0);
-  a.F1 = reinterpret_cast<const f32x4 *>(m->d_blob + m->off_wp1);
-  a.F2 = reinterpret_cast<const f32x4 *>(m->d_blob + m->off_wp2);
+  a.F0 = reinterpret_cast<const f32x4 *>(m->pack(0));
+  a.F1 = reinterpret_cast<const f32x4 *>(m->pack(1));
+  a.F2 = reinterpret_cast<const f32x4 *>(m->pack(2));
   a.B1 = reinterpret_cast<const f32x4 *>(t->wpb1);
   a.B2 = reinterpret_cast<const f32x4 *>(t->wpb2);
-  a.sF0 = (size_t)(H / 32) * (t->IP / 8) * 64; a.sF1 = (size_t)(H / 32) * (H / 8) * 64;
-  a.sF2 = (size_t)m->o_tiles * (H / 8) * 64;
-  a.sB1 = (size_t)(H / 32) * (H / 8) * 64; a.sB2 = (size_t)(H / 32) * (t->OPk / 8) * 64;
+  a.sF0 = m->pack_floats(0) / 4; a.sF1 = m->pack_floats(1) / 4; a.sF2 = m->pack_floats(2) / 4;
+  a.sB1 = t->wpb1_floats / 4; a.sB2 = t->wpb2_floats / 4;
   a.b0 = m->d_blob + m->off_b0; a.b1 = m->d_blob + m->off_b1; a.b2 = m->d_blob + m->off_b2;
   a.b2_ld = m->o_tiles * 32;
-  a.in_mu = m->has_in_scaler ? m->d_blob + m->off_in_mu : nullptr;
-  a.in_sig = m->has_in_scaler ? m->d_blob + m->off_in_var : nullptr;
-  a.out_mu = m->has_out_scaler ? m->d_blob + m->off_out_mu : nullptr;
-  a.out_sig = m->has_out_scaler ? m->d_blob + m->off_out_var : nullptr;
+  a.in_mu = m->in_mu(); a.in_sig = m->in_sig(); a.out_mu = m->out_mu(); a.out_sig = m->out_sig();
   a.inputs = d_inputs; a.targets = d_targets; a.idx = d_idx; a.idx_stride = idx_stride;
   a.E = t->E; a.I = t->I; a.IP = t->IP; a.kg0 = t->IP / 8; a.O = t->O; a.kga = t->OPk / 8; a.B = batch;
   for (int l = 0; l < 3; ++l) {
@@ -2062,13 +1963,20 @@ int run_forward(cmbpo_trainer *t, const float *d_inputs, const int32_t *d_idx, i
   return cmbpo_internal_launch_mlp(t->m, a, s, CMBPO_HEAD_TRAIN);
 }
 
-void fill_loss_args(cmbpo_trainer *t, LossArgs &l, const float *d_targets, const int32_t *d_idx, int idx_stride, int rows) {
-  cmbpo_mlp *m = t->m;
-  l.o = t->o; l.targets = d_targets; l.idx = d_idx; l.idx_stride = idx_stride;
-  l.out_mu = m->has_out_scaler ? m->d_blob + m->off_out_mu : nullptr;
-  l.out_sig = m->has_out_scaler ? m->d_blob + m->off_out_var : nullptr;
-  l.E = t->E; l.B = rows; l.O = t->O; l.D = t->D; l.OPk = t->OPk; l.prob = t->prob;
-  l.sums = t->sums; l.d3 = t->d3;
+// the six parameter tensors (or one of their Adam moments: dw / db) between host arrays and the device
+int copy_tensors(const cmbpo_trainer *t, float *const *dw, float *const *db, const float *const (&h)[6], bool to_device, hipStream_t s) {
+  for (int i = 0; i < 6; ++i) {
+    float *d = (i & 1) ? db[i / 2] : dw[i / 2], *host = const_cast<float *>(h[i]);
+    const size_t bytes = ((i & 1) ? t->bsize[i / 2] : t->wsize[i / 2]) * sizeof(float);
+    if (to_device) CMBPO_HIP_CHECK(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, s));
+    else CMBPO_HIP_CHECK(hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, s));
+  }
+  return CMBPO_OK;
+}
+
+// lr_t of tf.train.AdamOptimizer at the trainer's step count
+float adam_rate(const cmbpo_trainer *t) {
+  return (float)((double)t->lr * sqrt(1.0 - pow((double)t->b2, (double)t->step)) / (1.0 - pow((double)t->b1, (double)t->step)));
 }
 
 }  // namespace
@@ -2129,13 +2037,14 @@ extern "C" int cmbpo_trainer_create(cmbpo_trainer_t **out, cmbpo_mlp_t *m, int m
     oB[l] = take(t->bsize[l]); omB[l] = take(t->bsize[l]); ovB[l] = take(t->bsize[l]);
     oP[l] = take(t->wsize[l] * t->ks[l]); odB[l] = take(t->bsize[l] * t->ks[l]);
   }
-  const size_t owpb1 = take((size_t)E * (H / 32) * (H / 8) * 256);
-  const size_t owpb2 = take((size_t)E * (H / 32) * (t->OPk / 8) * 256);
+  t->wpb1_floats = pack_floats(H / 32, H / 8);
+  t->wpb2_floats = pack_floats(H / 32, t->OPk / 8);
+  const size_t owpb1 = take(E * t->wpb1_floats), owpb2 = take(E * t->wpb2_floats);
   const size_t rows = (size_t)E * max_batch;
   const size_t ox = take(rows * t->IP), oh1 = take(rows * H), og1 = take(rows * H), oh2 = take(rows * H),
                og2 = take(rows * H), oo = take(rows * t->O), od3 = take(rows * t->OPk), od2 = take(rows * H),
                od1 = take(rows * H);
-  const size_t osums = take(2 * 3 * (size_t)E);   // doubles
+  const size_t osums = take(2 * (size_t)E);   // doubles
   const size_t olp = take(2 * 3 * (size_t)E * cmbpo_ceil_div(max_batch, 32));   // doubles
   const size_t oom = take((size_t)E * cmbpo_ceil_div(max_batch, 32) * kOpMax);
   hipError_t err = hipMalloc(reinterpret_cast<void **>(&t->pool), off * sizeof(float));
@@ -2168,11 +2077,12 @@ extern "C" int cmbpo_trainer_create(cmbpo_trainer_t **out, cmbpo_mlp_t *m, int m
     t->b16_s3 = cmbpo_ceil_div(t->OPk, 16);
     t->b16_s0 = cmbpo_ceil_div(t->IP, 16);
     t->b16_fwd = t->prob && t->IP <= 64 && t->O <= 64 && m->o_tiles <= 2;
-    const size_t w1t = (size_t)E * (H / 32) * (H / 16) * 2 * 64, w2t = (size_t)E * (H / 32) * t->b16_s3 * 2 * 64;
-    const size_t f0 = (size_t)E * (H / 32) * t->b16_s0 * 2 * 64, f2 = (size_t)E * 2 * (H / 16) * 2 * 64;
-    t->b16_w2t_off = w1t;
-    t->b16_f_off[0] = w1t + w2t; t->b16_f_off[1] = t->b16_f_off[0] + f0; t->b16_f_off[2] = t->b16_f_off[1] + w1t;
-    t->b16_stats_off = t->b16_f_off[2] + f2;
+    t->b16_w1_units = IMAGE_UNITS(H / 32, H / 16, 2); t->b16_w2t_units = IMAGE_UNITS(H / 32, t->b16_s3, 2);
+    t->b16_w0_units = IMAGE_UNITS(H / 32, t->b16_s0, 2); t->b16_w2_units = IMAGE_UNITS(2, H / 16, 2);
+    t->b16_w2t_off = E * t->b16_w1_units;
+    t->b16_f_off[0] = t->b16_w2t_off + E * t->b16_w2t_units; t->b16_f_off[1] = t->b16_f_off[0] + E * t->b16_w0_units;
+    t->b16_f_off[2] = t->b16_f_off[1] + E * t->b16_w1_units;
+    t->b16_stats_off = t->b16_f_off[2] + E * t->b16_w2_units;
     t->b16_blocks[0] = (int)((size_t)t->I * H / kThreads);
     t->b16_blocks[1] = (int)((size_t)H * H / kThreads);
     t->b16_blocks[2] = (int)((size_t)H * t->O / kThreads);
@@ -2199,11 +2109,7 @@ extern "C" int cmbpo_trainer_set_weights(cmbpo_trainer_t *t, const float *h_w0, 
                                          const float *h_b1, const float *h_w2, const float *h_b2, void *stream) {
   CMBPO_REQUIRE(t && h_w0 && h_b0 && h_w1 && h_b1 && h_w2 && h_b2, "cmbpo_trainer_set_weights: NULL argument");
   hipStream_t s = (hipStream_t)stream;
-  const float *hw[3] = {h_w0, h_w1, h_w2}, *hb[3] = {h_b0, h_b1, h_b2};
-  for (int l = 0; l < 3; ++l) {
-    CMBPO_HIP_CHECK(hipMemcpyAsync(t->W[l], hw[l], t->wsize[l] * sizeof(float), hipMemcpyHostToDevice, s));
-    CMBPO_HIP_CHECK(hipMemcpyAsync(t->Bv[l], hb[l], t->bsize[l] * sizeof(float), hipMemcpyHostToDevice, s));
-  }
+  if (int rc = copy_tensors(t, t->W, t->Bv, {h_w0, h_b0, h_w1, h_b1, h_w2, h_b2}, true, s)) return rc;
   // the packed images (and their zero padding) are rebuilt from the masters
   cmbpo_mlp *m = t->m;
   CMBPO_HIP_CHECK(hipMemsetAsync(m->d_blob + m->off_wp0, 0, (m->off_in_mu - m->off_wp0) * sizeof(float), s));
@@ -2218,11 +2124,7 @@ extern "C" int cmbpo_trainer_get_weights(cmbpo_trainer_t *t, float *h_w0, float 
                                          float *h_w2, float *h_b2, void *stream) {
   CMBPO_REQUIRE(t && h_w0 && h_b0 && h_w1 && h_b1 && h_w2 && h_b2, "cmbpo_trainer_get_weights: NULL argument");
   hipStream_t s = (hipStream_t)stream;
-  float *hw[3] = {h_w0, h_w1, h_w2}, *hb[3] = {h_b0, h_b1, h_b2};
-  for (int l = 0; l < 3; ++l) {
-    CMBPO_HIP_CHECK(hipMemcpyAsync(hw[l], t->W[l], t->wsize[l] * sizeof(float), hipMemcpyDeviceToHost, s));
-    CMBPO_HIP_CHECK(hipMemcpyAsync(hb[l], t->Bv[l], t->bsize[l] * sizeof(float), hipMemcpyDeviceToHost, s));
-  }
+  if (int rc = copy_tensors(t, t->W, t->Bv, {h_w0, h_b0, h_w1, h_b1, h_w2, h_b2}, false, s)) return rc;
   CMBPO_HIP_CHECK(hipStreamSynchronize(s));
   return CMBPO_OK;
 }
@@ -2233,11 +2135,7 @@ extern "C" int cmbpo_trainer_get_moments(cmbpo_trainer_t *t, int which, float *h
   CMBPO_REQUIRE(t && h_w0 && h_b0 && h_w1 && h_b1 && h_w2 && h_b2, "cmbpo_trainer_get_moments: NULL argument");
   CMBPO_REQUIRE(which == 0 || which == 1, "cmbpo_trainer_get_moments: which must be 0 (m) or 1 (v)");
   hipStream_t s = (hipStream_t)stream;
-  float *hw[3] = {h_w0, h_w1, h_w2}, *hb[3] = {h_b0, h_b1, h_b2};
-  for (int l = 0; l < 3; ++l) {
-    CMBPO_HIP_CHECK(hipMemcpyAsync(hw[l], which ? t->vW[l] : t->mW[l], t->wsize[l] * sizeof(float), hipMemcpyDeviceToHost, s));
-    CMBPO_HIP_CHECK(hipMemcpyAsync(hb[l], which ? t->vB[l] : t->mB[l], t->bsize[l] * sizeof(float), hipMemcpyDeviceToHost, s));
-  }
+  if (int rc = copy_tensors(t, which ? t->vW : t->mW, which ? t->vB : t->mB, {h_w0, h_b0, h_w1, h_b1, h_w2, h_b2}, false, s)) return rc;
   CMBPO_HIP_CHECK(hipStreamSynchronize(s));
   return CMBPO_OK;
 }
@@ -2249,11 +2147,7 @@ extern "C" int cmbpo_trainer_set_moments(cmbpo_trainer_t *t, int which, const fl
   CMBPO_REQUIRE(which == 0 || which == 1, "cmbpo_trainer_set_moments: which must be 0 (m) or 1 (v)");
   CMBPO_REQUIRE(steps_done >= 0, "cmbpo_trainer_set_moments: negative step count");
   hipStream_t s = (hipStream_t)stream;
-  const float *hw[3] = {h_w0, h_w1, h_w2}, *hb[3] = {h_b0, h_b1, h_b2};
-  for (int l = 0; l < 3; ++l) {
-    CMBPO_HIP_CHECK(hipMemcpyAsync(which ? t->vW[l] : t->mW[l], hw[l], t->wsize[l] * sizeof(float), hipMemcpyHostToDevice, s));
-    CMBPO_HIP_CHECK(hipMemcpyAsync(which ? t->vB[l] : t->mB[l], hb[l], t->bsize[l] * sizeof(float), hipMemcpyHostToDevice, s));
-  }
+  if (int rc = copy_tensors(t, which ? t->vW : t->mW, which ? t->vB : t->mB, {h_w0, h_b0, h_w1, h_b1, h_w2, h_b2}, true, s)) return rc;
   CMBPO_HIP_CHECK(hipStreamSynchronize(s));
   t->step = steps_done;
   return CMBPO_OK;
@@ -2325,8 +2219,7 @@ extern "C" int cmbpo_trainer_step(cmbpo_trainer_t *t, const float *d_inputs, int
     int rc = launch_fused(t, d_inputs, d_targets, d_idx, idx_stride, batch, s);
     if (rc != CMBPO_OK) return rc;
     t->step += 1;
-    const double lr_f = (double)t->lr * sqrt(1.0 - pow((double)t->b2, (double)t->step)) / (1.0 - pow((double)t->b1, (double)t->step));
-    return launch_update(t, 1, (float)lr_f, s);
+    return launch_update(t, 1, adam_rate(t), s);
   }
 
   // training forward (+ per-tile loss statistics) -> backward chain (+ output deltas) -> weight gradients -> Adam
@@ -2335,18 +2228,14 @@ extern "C" int cmbpo_trainer_step(cmbpo_trainer_t *t, const float *d_inputs, int
 
   BwdArgs b{};
   b.wpb2 = reinterpret_cast<const f32x4 *>(t->wpb2); b.wpb1 = reinterpret_cast<const f32x4 *>(t->wpb1);
-  b.wpb2_stride = (size_t)(H / 32) * (t->OPk / 8) * 64; b.wpb1_stride = (size_t)(H / 32) * (H / 8) * 64;
-  b.d3 = t->d3; b.g2 = t->g2; b.g1 = t->g1; b.d2 = t->d2; b.d1 = t->d1;
+  b.wpb2_stride = t->wpb2_floats / 4; b.wpb1_stride = t->wpb1_floats / 4;
+  b.g2 = t->g2; b.g1 = t->g1; b.d2 = t->d2; b.d1 = t->d1;
   b.B = batch; b.OPk = t->OPk;
-  {
-    cmbpo_mlp *m = t->m;
-    b.fuse = 1; b.prob = t->prob ? (t->nll ? 2 : 1) : 0; b.O = t->O; b.D = t->D; b.n_items = E * cmbpo_ceil_div(batch, 32);
-    b.o = t->o; b.targets = d_targets; b.idx = d_idx; b.idx_stride = idx_stride;
-    b.out_mu = m->has_out_scaler ? m->d_blob + m->off_out_mu : nullptr;
-    b.out_sig = m->has_out_scaler ? m->d_blob + m->off_out_var : nullptr;
-    b.loss_part = t->loss_part; b.d3_out = t->d3;
-    b.opmax = t->opmax;
-  }
+  b.prob = t->prob ? (t->nll ? 2 : 1) : 0; b.O = t->O; b.D = t->D; b.n_items = E * cmbpo_ceil_div(batch, 32);
+  b.o = t->o; b.targets = d_targets; b.idx = d_idx; b.idx_stride = idx_stride;
+  b.out_mu = t->m->out_mu(); b.out_sig = t->m->out_sig();
+  b.loss_part = t->loss_part; b.d3_out = t->d3;
+  b.opmax = t->opmax;
   const size_t lds = ((size_t)H / 4 * 32 + (size_t)t->OPk / 4 * 32) * sizeof(f32x4);
   const int tiles = cmbpo_ceil_div(batch, 32);
   if (t->b16) rc = launch_bwd_h(t, b, batch, s);
@@ -2365,8 +2254,7 @@ extern "C" int cmbpo_trainer_step(cmbpo_trainer_t *t, const float *d_inputs, int
   CMBPO_HIP_CHECK(hipGetLastError());
 
   t->step += 1;
-  const double lr_t = (double)t->lr * sqrt(1.0 - pow((double)t->b2, (double)t->step)) / (1.0 - pow((double)t->b1, (double)t->step));
-  return launch_update(t, 1, (float)lr_t, s);
+  return launch_update(t, 1, adam_rate(t), s);
 }
 
 // One pass over the bootstrap index lists: ceil(n_rows / batch) train_ops enqueued back to back (the inner loop of
@@ -2397,15 +2285,17 @@ extern "C" int cmbpo_trainer_losses(cmbpo_trainer_t *t, const float *d_inputs, i
                 n_rows, t->max_batch);
   hipStream_t s = (hipStream_t)stream;
   const int E = t->E;
-  CMBPO_HIP_CHECK(hipMemsetAsync(t->sums, 0, 3 * (size_t)E * sizeof(double), s));
+  CMBPO_HIP_CHECK(hipMemsetAsync(t->sums, 0, (size_t)E * sizeof(double), s));
   for (int r0 = 0; r0 < n_rows; r0 += t->max_batch) {
     const int rows = min(t->max_batch, n_rows - r0);
     const int32_t *idx = d_idx ? d_idx + r0 : nullptr;
     int rc = run_forward(t, d_inputs, idx, idx_stride, rows, false, s);
     if (rc != CMBPO_OK) return rc;
-    LossArgs l{};
-    fill_loss_args(t, l, d_targets, idx, idx_stride, rows);
-    l.prob = 0;   // only the squared error of the mean head is needed
+    LossArgs l{};   // (only the squared error of the mean head is needed)
+    l.o = t->o; l.targets = d_targets; l.idx = idx; l.idx_stride = idx_stride;
+    l.out_mu = t->m->out_mu(); l.out_sig = t->m->out_sig();
+    l.E = E; l.B = rows; l.O = t->O; l.D = t->D;
+    l.sums = t->sums;
     const int gx = min(cmbpo_ceil_div(rows * t->D, kThreads), 64);
     hipLaunchKernelGGL(loss_sums_kernel, dim3(gx, E), dim3(kThreads), 0, s, l);
   }

@@ -2,6 +2,7 @@
 // two into the top of the f16 range, as two f16 pieces; a float32 product as three MFMAs; the swish / lift / split epilogue.
 #pragma once
 #include "common.h"
+#include "pack_layout.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));

@@ -7,6 +7,7 @@
 //   * accumulator tile: lane holds column j = l & 31, rows (r & 3) + 8 (r >> 2) + 4 h, r = 0..15.
 #pragma once
 #include "common.h"
+#include "pack_layout.h"
 
 // One dense layer slice: acc[t][bt] += A(n-tile t) * B(b-tile bt) over k-groups
 // [g0, g1).  wp points at this wave's first n-tile for k-group 0; consecutive
@@ -41,7 +42,7 @@ __device__ __forceinline__ void mfma_layer(const f32x4 *__restrict__ wp,
   const f32x4 *lds_lane = lds_in + h * BB + j;
   const float *row_lane = reinterpret_cast<const float *>(lds_in) + j * row_stride + 4 * h;
   auto request = [&](int g, f32x4 (&a)[NT], f32x4 (&b)[BT]) {
-    const f32x4 *wg = wp + (size_t)g * 64;          // wave-uniform: scalar pointer arithmetic
+    const f32x4 *wg = wp + PACK_VEC4S(1, g);         // wave-uniform: scalar pointer arithmetic
 #pragma unroll
     for (int t = 0; t < NT; ++t) a[t] = (wg + t * nt_stride)[lane];
 #pragma unroll

@@ -33,9 +33,9 @@ bool policy_eligible(const cmbpo_mlp *m) {
 int ensure_pf16(cmbpo_mlp *m, hipStream_t s) {
   const int S0 = m->h3_s0;
   if (m->d_h3 == nullptr) {
-    m->h3_stride[0] = (size_t)NTP * S0 * 2 * 64;
-    m->h3_stride[1] = (size_t)NTP * SP1 * 2 * 64;
-    m->h3_stride[2] = (size_t)SP1 * 2 * 64;
+    m->h3_stride[0] = IMAGE_UNITS(NTP, S0, 2);
+    m->h3_stride[1] = IMAGE_UNITS(NTP, SP1, 2);
+    m->h3_stride[2] = IMAGE_UNITS(1, SP1, 2);
     m->h3_off[0] = 0;
     m->h3_off[1] = m->h3_stride[0];
     m->h3_off[2] = m->h3_off[1] + m->h3_stride[1];

@@ -48,8 +48,8 @@ __device__ __forceinline__ void policy_tile(const PfArgs &a, int row0, int n_row
   auto load_w = [&](f16x8 (&x)[NTP][2], const f16x8 *w, int slabs, int s) {
 #pragma unroll
     for (int t = 0; t < NTP; ++t) {
-      const f16x8 *q = w + ((size_t)(t * slabs + s) * 2) * 64;
-      x[t][0] = q[0]; x[t][1] = q[64];
+      const f16x8 *q = w + IMAGE_INDEX(t, slabs, s, 2, 0);
+      x[t][0] = q[0]; x[t][1] = q[kImageLanes];
     }
   };
 #pragma unroll
@@ -154,7 +154,7 @@ __device__ __forceinline__ void policy_tile(const PfArgs &a, int row0, int n_row
   // the output layer is one n-tile: its eight slabs (two pieces each) are requested while the epilogue runs
   f16x8 W2[SP1][2];
 #pragma unroll
-  for (int s = 0; s < SP1; ++s) { W2[s][0] = w2[(size_t)(2 * s) * 64]; W2[s][1] = w2[(size_t)(2 * s + 1) * 64]; }
+  for (int s = 0; s < SP1; ++s) { W2[s][0] = w2[IMAGE_INDEX(0, SP1, s, 2, 0)]; W2[s][1] = w2[IMAGE_INDEX(0, SP1, s, 2, 1)]; }
   to_frags(a.b1, inv1);
   // ---- mu = h2 W2 + b2 ----------------------------------------------------------------------------------------------------
   f32x16 o;

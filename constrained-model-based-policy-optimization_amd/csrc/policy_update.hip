@@ -87,7 +87,7 @@ struct PiArgs {
 
 // ---- packing (device side, so set_params / FVP directions never visit the host) -------------------
 // One launch packs every piece of a flat parameter vector.  Matrix pieces:
-//   dst[off + ((nt*kg + g)*64 + lane)*4 + s] = src[n*sn + k*sk], n = nt*32 + (lane&31) < n_lim, k = 8g + 4(lane>>5) + s < k_lim
+//   dst[off + pack_index(k, n, kg)] = src[n*sn + k*sk], n < n_lim, k < k_lim   (pack_layout.h)
 // vector pieces (kg == 0): dst[off + i] = i < n_lim ? src[i] : 0.
 struct PackPiece {
   int dst_off, src_off, n_lim, k_lim, sn, sk, kg, count;   // count = floats written (incl. zero padding)
@@ -134,8 +134,7 @@ __device__ __forceinline__ void pack_f16_part(u32x4 *dst16, const float *flat, c
     const f32x4 q = src4[e];
     mx = fmaxf(fmaxf(mx, fmaxf(fabsf(q[0]), fabsf(q[1]))), fmaxf(fabsf(q[2]), fabsf(q[3])));
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  mx = wave_max(mx);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
   __syncthreads();
   const float S = pow2_lift(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
@@ -155,9 +154,9 @@ __device__ __forceinline__ void pack_f16_part(u32x4 *dst16, const float *flat, c
     const float v = (n < im.n_lim && k0 + e < im.k_lim) ? row[(size_t)(k0 + e) * im.sk] * S : 0.0f;
     split_h(v, p1.hv[e], p2.hv[e]);
   }
-  u32x4 *img = dst16 + im.dst_off + (size_t)((nt * im.slabs + s) * 2) * 64 + lane;
+  u32x4 *img = dst16 + im.dst_off + IMAGE_INDEX(nt, im.slabs, s, 2, 0) + lane;
   img[0] = p1.q;
-  img[64] = p2.q;
+  img[kImageLanes] = p2.q;
 }
 
 __device__ __forceinline__ void pack_max_part(u32x4 *dst16, const float *flat, const PackPlan &plan) {
@@ -202,8 +201,8 @@ __global__ void pack_all_kernel(float *dst, const float *flat, const PackPlan pl
   if (pc.kg == 0) {
     v = (idx < pc.n_lim) ? src[idx] : 0.0f;
   } else {
-    const int s = idx & 3, lane = (idx >> 2) & 63, g = (idx >> 8) % pc.kg, nt = (idx >> 8) / pc.kg;
-    const int n = nt * 32 + (lane & 31), k = 8 * g + 4 * (lane >> 5) + s;
+    int k, n;
+    pack_unindex(idx, pc.kg, k, n);
     v = (n < pc.n_lim && k < pc.k_lim) ? src[(size_t)n * pc.sn + (size_t)k * pc.sk] : 0.0f;
   }
   dst[pc.dst_off + idx] = v;
@@ -346,7 +345,7 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
       __syncthreads();
       // ---- forward ----------------------------------------------------------------------------------
       acc[0][0] = load_bias(p.w.b0, wave * 32, lane);
-      mfma_layer<1, 1, true>(p.w.F0 + (size_t)wave * d.kg0 * 64, 0, 0, d.kg0, xR4, lane, acc, XS);
+      mfma_layer<1, 1, true>(p.w.F0 + PACK_VEC4S(wave, d.kg0), 0, 0, d.kg0, xR4, lane, acc, XS);
       {
         f32x16 hv;
 #pragma unroll
@@ -355,7 +354,7 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
       }
       __syncthreads();
       acc[0][0] = load_bias(p.w.b1, wave * 32, lane);
-      mfma_layer<1, 1, true>(p.w.F1 + (size_t)wave * KGH * 64, 0, 0, KGH, h1R4, lane, acc, RS);
+      mfma_layer<1, 1, true>(p.w.F1 + PACK_VEC4S(wave, KGH), 0, 0, KGH, h1R4, lane, acc, RS);
       {
         f32x16 hv;
 #pragma unroll
@@ -379,7 +378,7 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     if constexpr (MODE == MODE_FVP) {
       // ---- JVP chain: dh1 = (1-h1^2)(x dW0 + db0) ; dh2 = (1-h2^2)(dh1 W1 + h1 dW1 + db1) -----------
       acc[0][0] = load_bias(p.v.b0, wave * 32, lane);
-      mfma_layer<1, 1, true>(p.v.F0 + (size_t)wave * d.kg0 * 64, 0, 0, d.kg0, xR4, lane, acc, XS);
+      mfma_layer<1, 1, true>(p.v.F0 + PACK_VEC4S(wave, d.kg0), 0, 0, d.kg0, xR4, lane, acc, XS);
       {
         const f32x16 hh = load_tile_R(h1R, RS, wave * 32, lane);
         f32x16 o;
@@ -389,9 +388,9 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
       }
       // the h1 dW1 half does not need dh1: it runs ahead of the barrier and absorbs the waves' skew
       acc[0][0] = load_bias(p.v.b1, wave * 32, lane);
-      mfma_layer<1, 1, true>(p.v.F1 + (size_t)wave * KGH * 64, 0, 0, KGH, h1R4, lane, acc, RS);
+      mfma_layer<1, 1, true>(p.v.F1 + PACK_VEC4S(wave, KGH), 0, 0, KGH, h1R4, lane, acc, RS);
       __syncthreads();
-      mfma_layer<1, 1, true>(p.w.F1 + (size_t)wave * KGH * 64, 0, 0, KGH, u1R4, lane, acc, RS);
+      mfma_layer<1, 1, true>(p.w.F1 + PACK_VEC4S(wave, KGH), 0, 0, KGH, u1R4, lane, acc, RS);
       {
         const f32x16 hh = load_tile_R(h2R, RS, wave * 32, lane);
         f32x16 o;
@@ -499,7 +498,7 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
 
     // ---- backward: delta2 = (W2 cot) (1-h2^2) ; delta1 = (W1 delta2) (1-h1^2) --------------------------
     zero(acc[0][0]);
-    mfma_layer<1, 1, true>(p.w.B2 + (size_t)wave * d.kga * 64, 0, 0, d.kga, wR4, lane, acc, 36);
+    mfma_layer<1, 1, true>(p.w.B2 + PACK_VEC4S(wave, d.kga), 0, 0, d.kga, wR4, lane, acc, 36);
     {
       const f32x16 hh = load_tile_R(h2R, RS, wave * 32, lane);
       f32x16 o;
@@ -509,7 +508,7 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     }
     __syncthreads();
     zero(acc[0][0]);
-    mfma_layer<1, 1, true>(p.w.B1 + (size_t)wave * KGH * 64, 0, 0, KGH, u2R4, lane, acc, RS);
+    mfma_layer<1, 1, true>(p.w.B1 + PACK_VEC4S(wave, KGH), 0, 0, KGH, u2R4, lane, acc, RS);
     {
       const f32x16 hh = load_tile_R(h1R, RS, wave * 32, lane);
       f32x16 o;
@@ -799,12 +798,12 @@ int do_pack(const cmbpo_pi *h, float *dst, const float *flat, hipStream_t s) {
   };
   // forward packs: A[i = out unit][k = in unit] = W[k][i]
   const int H = d.H, NT = H / 32, KH = H / 8;
-  add(h->off_F0, d.oW0, H, d.D, 1, H, d.kg0, NT * d.kg0 * 256);
-  add(h->off_F1, d.oW1, H, H, 1, H, KH, NT * KH * 256);
-  add(h->off_F2, d.oW2, d.A, H, 1, d.A, KH, KH * 256);
+  add(h->off_F0, d.oW0, H, d.D, 1, H, d.kg0, (int)pack_floats(NT, d.kg0));
+  add(h->off_F1, d.oW1, H, H, 1, H, KH, (int)pack_floats(NT, KH));
+  add(h->off_F2, d.oW2, d.A, H, 1, d.A, KH, (int)pack_floats(1, KH));
   // backward packs: A[i = in unit][k = out unit] = W[i][k]
-  add(h->off_B1, d.oW1, H, H, H, 1, KH, NT * KH * 256);
-  add(h->off_B2, d.oW2, H, d.A, d.A, 1, d.kga, NT * d.kga * 256);
+  add(h->off_B1, d.oW1, H, H, H, 1, KH, (int)pack_floats(NT, KH));
+  add(h->off_B2, d.oW2, H, d.A, d.A, 1, d.kga, (int)pack_floats(NT, d.kga));
   add(h->off_b0, d.ob0, H, 0, 0, 0, 0, H);
   add(h->off_b1, d.ob1, H, 0, 0, 0, 0, H);
   add(h->off_b2, d.ob2, d.A, 0, 0, 0, 0, 32);
@@ -819,7 +818,7 @@ int do_pack(const cmbpo_pi *h, float *dst, const float *flat, hipStream_t s) {
   auto add16 = [&](int src_off, int sn, int sk, int n_lim, int k_lim, int n_tiles, int slabs, int dst_off, int lift_idx) {
     plan.img[ni] = H16Img{src_off, sn, sk, n_lim, k_lim, n_tiles, slabs, dst_off, lift_idx};
     plan.img_blk[ni++] = blk;
-    blk += cmbpo_ceil_div(n_tiles * slabs * 64, 256);
+    blk += cmbpo_ceil_div((int)IMAGE_UNITS(n_tiles, slabs, 1), 256);
   };
   if (H == HID) {      // (the f16 kernels are written for 128 hidden units: a 256-wide policy runs the fp32 MFMAs)
   add16(d.oW0, 1, HID, HID, d.D, 4, s0, H16_F0, L_F0);          // A[unit][input] = W0[input][unit]
@@ -942,8 +941,8 @@ extern "C" int cmbpo_pi_create(cmbpo_pi_t **out, int obs_dim, int hidden, int ac
   d.ob2 = d.oW2 + H * act_dim; d.ols = d.ob2 + act_dim; d.P = d.ols + act_dim;
   size_t off = 0;
   auto take = [&](size_t n) { size_t o = off; off += (n + 3) / 4 * 4; return o; };
-  h->off_F0 = take((size_t)NT * d.kg0 * 256); h->off_F1 = take((size_t)NT * KH * 256); h->off_F2 = take((size_t)KH * 256);
-  h->off_B1 = take((size_t)NT * KH * 256); h->off_B2 = take((size_t)NT * d.kga * 256);
+  h->off_F0 = take(pack_floats(NT, d.kg0)); h->off_F1 = take(pack_floats(NT, KH)); h->off_F2 = take(pack_floats(1, KH));
+  h->off_B1 = take(pack_floats(NT, KH)); h->off_B2 = take(pack_floats(NT, d.kga));
   h->off_b0 = take(H); h->off_b1 = take(H); h->off_b2 = take(32); h->off_ls = take(32);
   h->pack_floats = off;
   h->has_params = false;

@@ -9,6 +9,7 @@
 // buffers make both the per-step store and the per-branch backward GAE recurrence coalesced
 // (adjacent lanes = adjacent branches).
 #include "common.h"
+#include "rollout_internal.h"
 #include <type_traits>
 
 #include <math.h>

@@ -5,20 +5,13 @@
 // Every buffer is a field of the rollout struct; nothing here adds arithmetic.
 #include "common.h"
 #include "ens_mlp_internal.h"
+#include "rollout_internal.h"
 
 #include <string.h>
 #include <time.h>
 
 #include <atomic>
 #include <mutex>
-
-int cmbpo_internal_book_post_mirror(const cmbpo_rollout_t *r, int n_alive, uint32_t *d_host_out, uint32_t seq, int spec, int min_alive,
-                                    double stop_total, void *stream);
-int cmbpo_internal_scalars_mirror(const cmbpo_rollout_t *r, uint32_t *d_host_out, uint32_t seq, void *stream);
-int cmbpo_internal_book_pre(const cmbpo_rollout_t *r, int n_alive, int spec, int with_vec, void *stream);
-int cmbpo_internal_store_nostats(const cmbpo_rollout_t *r, void *stream);
-int cmbpo_internal_finish_post_fold(const cmbpo_rollout_t *r, void *stream);
-int cmbpo_internal_spec_words(const cmbpo_rollout_t *r, int begin, void *stream);
 
 // A step enqueued AHEAD of the previous step's counters (cmbpo_rollout_run, small batches): n_alive is then an upper bound (the
 // alive count only falls), every kernel reads the row count on the device, and the step is void if the previous one met a stop

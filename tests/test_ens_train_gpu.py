@@ -73,6 +73,8 @@ CASES = [  # E, I, H, D, loss, batch
     (3, 11, 128, 4, "NLL", 100),
     (3, 29, 256, 1, "MSE", 100),     # the base config's default critic width (configs/baseconfig/base.py:16,19): the general path
     (4, 20, 256, 6, "MSPE", 150),    # ... and a probabilistic ensemble of that width
+    (2, 20, 512, 40, "MSPE", 70),    # 80 raw outputs (> 64): the fp32 backward chain and training forward of a 512-wide ensemble
+    (2, 70, 512, 5, "MSPE", 40),     # 72 padded inputs (> 64): the f16 backward chain behind the fp32 training forward, probabilistic head
 ]
 
 
@@ -105,7 +107,7 @@ def test_first_step_gradients_and_losses(hip_lib, E, I, H, D, loss, batch):
     assert tr.steps_done == 1
 
 
-@pytest.mark.parametrize("E,I,H,D,loss,batch", CASES[:3] + CASES[-1:])
+@pytest.mark.parametrize("E,I,H,D,loss,batch", CASES[:3] + [(4, 20, 256, 6, "MSPE", 150)])
 def test_several_adam_steps_track_oracle(hip_lib, E, I, H, D, loss, batch):
     _need_gpu()
     rng, pe, ref, x, t, ws, bs = _make(E, I, H, D, loss, 500, seed=7 + E)
@@ -136,6 +138,20 @@ def test_several_adam_steps_track_oracle(hip_lib, E, I, H, D, loss, batch):
         rm, rv = refcpu.ens_forward(xs, gw, gb, sc_in, sc_out)
         np.testing.assert_allclose(mean, rm, rtol=2e-4, atol=2e-4)
         np.testing.assert_allclose(var, rv, rtol=2e-3, atol=1e-6)
+
+
+@pytest.mark.parametrize("E,I,H,D,loss,bits", [
+    (7, 37, 512, 30, "MSPE", 3),     # f16 backward chain and f16 training forward
+    (2, 20, 512, 1, "MSE", 1),       # deterministic head: the f16 backward chain only
+    (2, 70, 512, 5, "MSPE", 1),      # more than 64 padded inputs: likewise
+    (2, 20, 512, 40, "MSPE", 0),     # more than 64 padded outputs: the fp32 kernels
+    (3, 11, 128, 4, "MSPE", 0),      # not 512-wide
+])
+def test_f16_path_selection(hip_lib, E, I, H, D, loss, bits):
+    """Which training kernels a shape gets: bit 0 the f16 backward chain, bit 1 the f16 training forward."""
+    _need_gpu()
+    pe = _make(E, I, H, D, loss, 64, seed=1)[1]
+    assert pe._ensure_trainer(64).f16_paths == bits
 
 
 def test_step_is_bitwise_reproducible(hip_lib):
