@@ -54,6 +54,8 @@ SIGNATURES = {
     "cmbpo_policy_forward": (_i, [_p, _p, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
     "cmbpo_fakeenv_post": (_i, [_i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i,
                                 _p, _p, _p, _p, _p, _p, _p, _p]),
+    "cmbpo_fakeenv_post_noise": (_i, [_i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i,
+                                      _p, _p, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 
@@ -93,7 +95,9 @@ class RolloutStruct(C.Structure):
             "dkl_acc", "path_ret", "path_cost", "path_dyn_var", "store_part",
             "obs_buf", "act_buf", "mu_buf", "ls_buf",
             "rew_buf", "val_buf", "cost_buf", "cval_buf", "logp_buf",
-            "adv_buf", "ret_buf", "cadv_buf", "cret_buf")]
+            "adv_buf", "ret_buf", "cadv_buf", "cret_buf",
+            "xi")]                      # stochastic transitions: NULL = off
+        + [("xi_stride", C.c_int64)]
     )
 
 

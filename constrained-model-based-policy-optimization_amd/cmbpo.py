@@ -15,6 +15,10 @@ real costs (``format_samples_for_dyn(append_c=True)``, ``:470``) and has ``FakeE
 from it (``predicts_cost=True``, ``:137-142``) instead of the task's cost rule: the only way an imagined sample of a
 task without such a rule carries a cost at all.
 
+``m_stochastic=True`` samples the imagined transitions from the elite member's predictive distribution N(mean, var)
+instead of placing them at its mean (``ModelSampler(stochastic=True)``; the reference has the hook in
+``models/fake_env.py:103-108`` but never switches it on).  The uncertainty calibration stays deterministic.
+
 ``static_fns`` takes a ``statics.TaskRules``: user-defined termination / cost rules for the imagined rollouts, with
 precedence over ``task`` (which may itself be a name given to ``statics.register_task``).
 """
@@ -69,7 +73,7 @@ class CMBPO:
                  initial_real_samples_per_epoch=5000, min_real_samples_per_epoch=500, batch_size_policy=25000,
                  n_epochs=int(10e7), n_initial_exploration_steps=0, initial_exploration_policy=None, epoch_length=1000,
                  model_train_kwargs=None, initial_model_train_kwargs=None, shuffle_on_device=True, device=None,
-                 session=None, start_state_sampling='host', **_unused):
+                 session=None, start_state_sampling='host', m_stochastic=False, **_unused):
         # RLAlgorithm.__init__ (algorithms/rl_algorithm.py:22-74)
         self.sampler = sampler if sampler is not None else CpoSampler(max_path_length=getattr(policy, "max_path_length", 1000))
         self._n_epochs, self._epoch_length = n_epochs, epoch_length
@@ -133,7 +137,8 @@ class CMBPO:
             self.model_buf.initialize(pi_info_shapes, gamma=policy.gamma, lam=policy.lam, cost_gamma=policy.cost_gamma,
                                       cost_lam=policy.cost_lam)
             self.model_sampler = ModelSampler(max_path_length=maxroll, batch_size=self._rollout_batch_size,
-                                              logger=None, rollout_mode=self.rollout_mode)
+                                              logger=None, rollout_mode=self.rollout_mode,
+                                              stochastic=bool(m_stochastic))
         self.init_real_samples = initial_real_samples_per_epoch
         self.min_real_samples = min_real_samples_per_epoch
         self.batch_size_policy = batch_size_policy

@@ -41,8 +41,17 @@ struct PostArgs {
 struct PostArgsRules : PostArgs {
   cmbpo_task_rules_t rules;     // columns resolved on the host: col0 absolute, n_cols a count, all inside the source's width
 };
-template <bool RULES>
-using PostArgsT = std::conditional_t<RULES, PostArgsRules, PostArgs>;
+// NOISE: stochastic transitions (fake_env.py:103-108 with a random factor: mean + std * xi) -- the draws' pointer exists only
+// in the argument types of the NOISE instances, the same device: a launch without draws runs the kernels it always ran
+struct PostArgsNoise : PostArgs {
+  const float *xi;              // [., obs_dim] N(0, 1) draws, slot indexed like obs; one draw per (row, dim) for all members
+};
+struct PostArgsRulesNoise : PostArgsRules {
+  const float *xi;
+};
+template <bool RULES, bool NOISE>
+using PostArgsT = std::conditional_t<NOISE, std::conditional_t<RULES, PostArgsRulesNoise, PostArgsNoise>,
+                                     std::conditional_t<RULES, PostArgsRules, PostArgs>>;
 
 // np.clip(x, lo, hi): comparisons are false for a NaN, which therefore passes through (fminf / fmaxf would drop it)
 __device__ __forceinline__ float clip_np(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
@@ -50,8 +59,8 @@ __device__ __forceinline__ float clip_np(float x, float lo, float hi) { return x
 // EC: the ensemble size at compile time (0: read it at run time) -- with a run-time size the member loops are unrolled to
 // kEMax and masked: 56 pair terms computed and selected for the 42 that exist, a third more instructions
 #define POST_WAVES 5      // waves per SIMD the register allocation aims at (swept 4 / 5 / 6 / 8: 57.7 / 51.1 / 51.3 / 77.4 us at 100 k rows)
-template <int EC, bool RULES = false>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgsT<RULES> p) {
+template <int EC, bool RULES = false, bool NOISE = false>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgsT<RULES, NOISE> p) {
   extern __shared__ float sm[];
   const int D = p.obs_dim;
   float *s_dkl = sm;                  // [kRows][D]
@@ -89,7 +98,18 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
       v0s[e] = p.var[(e < E ? e : 0) * mstride + base];
     }
     const int me = p.elite[r];
-    const float mean_me = p.mean[me * mstride + base], obs_rd = p.obs[(size_t)r * D + d];
+    float mean_me = p.mean[me * mstride + base];
+    const float obs_rd = p.obs[(size_t)r * D + d];
+    if constexpr (NOISE) {
+      // fake_env.py:104-106 with a random factor: every member's mean moves by fl32(fl32(sqrt(var)) * xi), two roundings (the
+      // reference's `+ pred_std` is xi == 1), BEFORE the uncertainty measures (:112-113 run on the shifted means) and the fast-path
+      // test; the variances stay what they are.  sqrtf, not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the latter is
+      // v_sqrt_f32 (1 ulp), and np.sqrt rounds correctly.
+      const float xi = p.xi[(size_t)r * D + d], var_me = p.var[me * mstride + base];
+#pragma unroll
+      for (int e = 0; e < kEMax; ++e) mu[e] = __fadd_rn(mu[e], __fmul_rn(sqrtf(v0s[e]), xi));
+      mean_me = __fadd_rn(mean_me, __fmul_rn(sqrtf(var_me), xi));
+    }
 #pragma unroll
     for (int e = 0; e < kEMax; ++e) {
       if (e < E) {
@@ -302,31 +322,35 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
   }
 }
 
-}  // namespace
+// one launch of the instance for (ensemble size, RULES, NOISE)
+template <bool RULES, bool NOISE>
+void launch_post(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsT<RULES, NOISE> &a) {
+  if (ensemble == 7) hipLaunchKernelGGL((fakeenv_post_kernel<7, RULES, NOISE>), grid, dim3(kThreads), lds, stream, a);   // the shipped configs
+  else if (ensemble == 5) hipLaunchKernelGGL((fakeenv_post_kernel<5, RULES, NOISE>), grid, dim3(kThreads), lds, stream, a);
+  else hipLaunchKernelGGL((fakeenv_post_kernel<0, RULES, NOISE>), grid, dim3(kThreads), lds, stream, a);
+}
 
-extern "C" int cmbpo_fakeenv_post(int task, int ensemble, int obs_dim, int act_dim,
-                                  const float *d_mean, const float *d_var, int ld_rows,
-                                  const float *d_obs, const float *d_act, const int32_t *d_elite,
-                                  const int32_t *d_row_idx, const int32_t *d_n_rows, int n_rows,
-                                  float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost,
-                                  float *d_dkl_path, float *d_ep_var_mean, float *d_ep_var,
-                                  void *stream) {
+// both entry points; `who` prefixes the messages, d_xi == NULL: the deterministic instances
+int post_impl(const char *who, int task, int ensemble, int obs_dim, int act_dim, const float *d_mean, const float *d_var, int ld_rows,
+              const float *d_obs, const float *d_act, const int32_t *d_elite, const int32_t *d_row_idx, const int32_t *d_n_rows,
+              int n_rows, float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost, float *d_dkl_path, float *d_ep_var_mean,
+              float *d_ep_var, const float *d_xi, void *stream) {
   const int learned_cost = (task & CMBPO_TASK_LEARNED_COST) ? 1 : 0;     // every other bit outside the rule id is an error
   const int task_arg = task;
   task &= ~CMBPO_TASK_LEARNED_COST;
   const bool user = task >= CMBPO_TASK_USER_BASE && task < CMBPO_TASK_USER_BASE + CMBPO_TASK_USER_SLOTS;
-  CMBPO_REQUIRE((task >= CMBPO_TASK_DEFAULT && task <= CMBPO_TASK_ANTSAFE) || user, "cmbpo_fakeenv_post: bad task %d", task_arg);
-  CMBPO_REQUIRE(ensemble >= 2 && ensemble <= kEMax, "cmbpo_fakeenv_post: ensemble %d not in [2, %d]", ensemble, kEMax);
-  CMBPO_REQUIRE(obs_dim >= 1 && obs_dim <= 512 && act_dim >= 0, "cmbpo_fakeenv_post: bad dims");
+  CMBPO_REQUIRE((task >= CMBPO_TASK_DEFAULT && task <= CMBPO_TASK_ANTSAFE) || user, "%s: bad task %d", who, task_arg);
+  CMBPO_REQUIRE(ensemble >= 2 && ensemble <= kEMax, "%s: ensemble %d not in [2, %d]", who, ensemble, kEMax);
+  CMBPO_REQUIRE(obs_dim >= 1 && obs_dim <= 512 && act_dim >= 0, "%s: bad dims", who);
   if (task == CMBPO_TASK_ANTSAFE)
-    CMBPO_REQUIRE(obs_dim >= 5, "cmbpo_fakeenv_post: AntSafe rules need obs_dim >= 5");
+    CMBPO_REQUIRE(obs_dim >= 5, "%s: AntSafe rules need obs_dim >= 5", who);
   PostArgsRules ar{};
   if (user)     // (registered? columns inside obs_dim / act_dim? -- host code, before any HIP call)
-    if (int rc = cmbpo_internal_task_rules_resolve("cmbpo_fakeenv_post", task_arg, obs_dim, act_dim, d_act != nullptr, &ar.rules)) return rc;
+    if (int rc = cmbpo_internal_task_rules_resolve(who, task_arg, obs_dim, act_dim, d_act != nullptr, &ar.rules)) return rc;
   CMBPO_REQUIRE(d_mean && d_var && d_obs && d_elite && d_next_obs && d_rew && d_term && d_cost &&
                     d_dkl_path && d_ep_var_mean,
-                "cmbpo_fakeenv_post: NULL buffer");
-  CMBPO_REQUIRE(n_rows >= 0 && ld_rows >= n_rows, "cmbpo_fakeenv_post: n_rows %d / ld_rows %d", n_rows, ld_rows);
+                "%s: NULL buffer", who);
+  CMBPO_REQUIRE(n_rows >= 0 && ld_rows >= n_rows, "%s: n_rows %d / ld_rows %d", who, n_rows, ld_rows);
   if (n_rows == 0) return CMBPO_OK;
   PostArgs a{};
   a.task = task; a.ensemble = ensemble; a.obs_dim = obs_dim; a.act_dim = act_dim;
@@ -338,14 +362,50 @@ extern "C" int cmbpo_fakeenv_post(int task, int ensemble, int obs_dim, int act_d
   a.dkl_path = d_dkl_path; a.ep_var_mean = d_ep_var_mean; a.ep_var = d_ep_var;
   const size_t lds = (size_t)3 * kRows * obs_dim * sizeof(float) + kRows * sizeof(int);
   const dim3 grid(cmbpo_ceil_div(n_rows, kRows));
-  if (user) {
-    static_cast<PostArgs &>(ar) = a;
-    if (ensemble == 7) hipLaunchKernelGGL((fakeenv_post_kernel<7, true>), grid, dim3(kThreads), lds, (hipStream_t)stream, ar);
-    else if (ensemble == 5) hipLaunchKernelGGL((fakeenv_post_kernel<5, true>), grid, dim3(kThreads), lds, (hipStream_t)stream, ar);
-    else hipLaunchKernelGGL((fakeenv_post_kernel<0, true>), grid, dim3(kThreads), lds, (hipStream_t)stream, ar);
-  } else if (ensemble == 7) hipLaunchKernelGGL(fakeenv_post_kernel<7>, grid, dim3(kThreads), lds, (hipStream_t)stream, a);   // the shipped configs
-  else if (ensemble == 5) hipLaunchKernelGGL(fakeenv_post_kernel<5>, grid, dim3(kThreads), lds, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(fakeenv_post_kernel<0>, grid, dim3(kThreads), lds, (hipStream_t)stream, a);
+  hipStream_t s = (hipStream_t)stream;
+  if (user) static_cast<PostArgs &>(ar) = a;
+  if (d_xi != nullptr) {
+    if (user) {
+      PostArgsRulesNoise an{};
+      static_cast<PostArgsRules &>(an) = ar;
+      an.xi = d_xi;
+      launch_post<true, true>(ensemble, grid, lds, s, an);
+    } else {
+      PostArgsNoise an{};
+      static_cast<PostArgs &>(an) = a;
+      an.xi = d_xi;
+      launch_post<false, true>(ensemble, grid, lds, s, an);
+    }
+  } else if (user) launch_post<true, false>(ensemble, grid, lds, s, ar);
+  else launch_post<false, false>(ensemble, grid, lds, s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
+}
+
+}  // namespace
+
+extern "C" int cmbpo_fakeenv_post(int task, int ensemble, int obs_dim, int act_dim,
+                                  const float *d_mean, const float *d_var, int ld_rows,
+                                  const float *d_obs, const float *d_act, const int32_t *d_elite,
+                                  const int32_t *d_row_idx, const int32_t *d_n_rows, int n_rows,
+                                  float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost,
+                                  float *d_dkl_path, float *d_ep_var_mean, float *d_ep_var,
+                                  void *stream) {
+  return post_impl("cmbpo_fakeenv_post", task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite, d_row_idx,
+                   d_n_rows, n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, nullptr, stream);
+}
+
+// ... with stochastic transitions: next_obs = mean + std * xi + obs (see the kernel); d_xi == NULL is cmbpo_fakeenv_post
+extern "C" int cmbpo_fakeenv_post_noise(int task, int ensemble, int obs_dim, int act_dim,
+                                        const float *d_mean, const float *d_var, int ld_rows,
+                                        const float *d_obs, const float *d_act, const int32_t *d_elite,
+                                        const int32_t *d_row_idx, const int32_t *d_n_rows, int n_rows,
+                                        float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost,
+                                        float *d_dkl_path, float *d_ep_var_mean, float *d_ep_var,
+                                        const float *d_xi, void *stream) {
+  if (d_xi == nullptr)
+    return cmbpo_fakeenv_post(task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite, d_row_idx, d_n_rows,
+                              n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, stream);
+  return post_impl("cmbpo_fakeenv_post_noise", task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite,
+                   d_row_idx, d_n_rows, n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, d_xi, stream);
 }

@@ -28,7 +28,7 @@ struct Ahead {
 static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy, cmbpo_mlp_t *model, cmbpo_mlp_t *v,
                      cmbpo_mlp_t *vc, int task, int ensemble, const float *d_eps, const int32_t *d_elite, float *d_mean,
                      float *d_var, bool policy_ready, const float *d_eps_next, bool *next_ready, uint32_t *d_mirror, uint32_t seq,
-                     const Ahead &ahead, void *stream) {
+                     const Ahead &ahead, const float *d_xi, void *stream) {
   CMBPO_REQUIRE(r && policy && model && v && vc && d_eps && d_elite && d_mean && d_var, "cmbpo_rollout_step: NULL argument");
   CMBPO_REQUIRE(n_alive >= 1 && n_alive <= r->B, "cmbpo_rollout_step: n_alive %d not in [1, B=%d]", n_alive, r->B);
   // the scratch rows are as wide as the model's output: a learned-cost flag that does not match the model would read the wrong columns
@@ -53,9 +53,10 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   if ((rc = cmbpo_ens_forward(model, r->cur_obs, r->obs_dim, r->act_t, r->act_dim, r->alive_idx, d_n, n_alive, r->B,
                               d_mean, d_var, stream)))
     return rc;
-  if ((rc = cmbpo_fakeenv_post(task, ensemble, r->obs_dim, r->act_dim, d_mean, d_var, r->B, r->cur_obs, r->act_t, d_elite,
-                               r->alive_idx, d_n, n_alive, w(r->next_obs), w(r->rew_t), const_cast<uint8_t *>(r->term_t), w(r->cost_t),
-                               w(r->dkl_t), w(r->epv_t), nullptr, stream)))
+  // (d_xi == NULL: cmbpo_fakeenv_post, the deterministic transition)
+  if ((rc = cmbpo_fakeenv_post_noise(task, ensemble, r->obs_dim, r->act_dim, d_mean, d_var, r->B, r->cur_obs, r->act_t, d_elite,
+                                     r->alive_idx, d_n, n_alive, w(r->next_obs), w(r->rew_t), const_cast<uint8_t *>(r->term_t),
+                                     w(r->cost_t), w(r->dkl_t), w(r->epv_t), nullptr, d_xi, stream)))
     return rc;
   const bool small = ahead.on || (n_alive <= cmbpo_rollout_book_pre_max_rows() && !r->use_host_budget);
   // small batches: decide + finish(PRE) + the store's scalar half in one launch; its vector half (obs, act, mu, log_std) rides
@@ -112,7 +113,7 @@ extern "C" int cmbpo_rollout_step(const cmbpo_rollout_t *r, int n_alive, cmbpo_m
                                   const int32_t *d_elite, float *d_mean, float *d_var, void *stream) {
   bool unused = false;
   return step_impl(r, n_alive, policy, model, v, vc, task, ensemble, d_eps, d_elite, d_mean, d_var, false, nullptr, &unused, nullptr, 0u,
-                   Ahead{}, stream);
+                   Ahead{}, r ? r->xi : nullptr, stream);
 }
 
 // Several steps in one call: what ModelSampler.sample()'s caller does between two steps (read the step's counters, swap the
@@ -194,6 +195,8 @@ extern "C" int cmbpo_rollout_run(cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *p
   CMBPO_REQUIRE(max_steps >= 1, "cmbpo_rollout_run: max_steps %d", max_steps);
   CMBPO_REQUIRE(!r->use_host_budget, "cmbpo_rollout_run: the cross-shard budget exchange needs the per-step path");
   int done = 0, swaps = 0;
+  // transition noise of step k of this call (the struct's field stays what it was)
+  auto xi_at = [&](int k) -> const float * { return r->xi ? r->xi + (size_t)k * (size_t)r->xi_stride : nullptr; };
   bool ready = false;     // the actor for the step about to run was evaluated by the previous step's critic launch
   auto advance = [&](bool swap_lists) {     // what the per-step caller does between two steps
     if (swap_lists) {
@@ -224,7 +227,7 @@ extern "C" int cmbpo_rollout_run(cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *p
         p.seq = next_seq();
         const int rc = step_impl(r, n_alive, policy, model, v, vc, task, ensemble, d_eps + (size_t)k * eps_stride,
                                  d_elite + (size_t)k * elite_stride, d_mean, d_var, ready, eps_next, &next_ready,
-                                 mir.d + (size_t)p.slot * kMirrorDwords, p.seq, ah, stream);
+                                 mir.d + (size_t)p.slot * kMirrorDwords, p.seq, ah, xi_at(k), stream);
         ready = next_ready;
         if (rc == 0) cmbpo_set_error("cmbpo_rollout_run: look-ahead step took the large-batch path");
         return rc == 1 ? CMBPO_OK : (rc == 0 ? CMBPO_EINVAL : rc);
@@ -258,7 +261,8 @@ extern "C" int cmbpo_rollout_run(cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *p
     const uint32_t seq = next_seq();
     uint32_t *d_slot = mir.d ? mir.d + (size_t)slot * kMirrorDwords : nullptr;
     int rc = step_impl(r, n_alive, policy, model, v, vc, task, ensemble, d_eps + (size_t)done * eps_stride,
-                       d_elite + (size_t)done * elite_stride, d_mean, d_var, ready, eps_next, &next_ready, d_slot, seq, Ahead{}, stream);
+                       d_elite + (size_t)done * elite_stride, d_mean, d_var, ready, eps_next, &next_ready, d_slot, seq, Ahead{},
+                       xi_at(done), stream);
     ready = next_ready;
     if (rc != 0 && rc != 1) return rc;
     char *h = static_cast<char *>(h_scalars) + (size_t)done * 384;

@@ -9,7 +9,11 @@ Differences that are part of the contract:
     ``model_inds=`` so a test / a sharded run can reproduce it; by default it is drawn with a
     seeded ``numpy.random.Generator`` owned by this object;
   * ``deterministic=False`` (mean + std, :105-106) and the 3-D input path (:84-101, unused by the
-    trainer and not an inverse) raise NotImplementedError.
+    trainer and not an inverse, SURVEY §8a R4(8)) raise NotImplementedError;
+  * ``noise=`` ([n, obs_dim], NumPy or CUDA tensor, in the order of ``obs``) samples the transition:
+    ``next_obs = mean + std * noise + obs`` per observation dimension, one draw per (row, dimension) for all members;
+    the uncertainty measures are taken on the shifted means, reward and learned cost are the elite's unperturbed columns
+    (``cmbpo_fakeenv_post_noise``).  ``noise=np.ones(...)`` is the reference's ``deterministic=False``.
 
 ``predicts_cost=True`` (:139-143, ``m_learn_cost`` of the trainer) takes the cost of a branch from the
 elite member's mean of the model's last output column (``output_dim == obs_dim + 2``) instead of the
@@ -71,13 +75,17 @@ class FakeEnv:
         elites = np.asarray(self._model.elite_inds, dtype=np.int32)
         return elites[self._rng.integers(0, len(elites), size=size)]
 
-    def step_device(self, obs, act, model_inds, out, row_idx=None, n_rows=None, scratch=None):
-        """Device-resident step: all arguments are CUDA tensors indexed by branch slot.
+    def step_device(self, obs, act, model_inds, out, row_idx=None, n_rows=None, scratch=None, noise=None):
+        """Device-resident step: all arguments are CUDA tensors indexed by branch slot (noise: [B, obs_dim] float32
+        N(0, 1) draws for stochastic transitions, None: the elite member's mean).
 
         out: dict with next_obs[B,obs], rew[B], term[B] u8, cost[B], dkl_path[B], ep_var_mean[B]
         (and optionally ep_var[B,obs]).  scratch: (mean, var)[E,B,output_dim].
         """
         B = obs.shape[0]
+        if noise is not None and not (noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
+                                      and tuple(noise.shape) == (B, self.obs_dim)):
+            raise ValueError("noise must be a contiguous float32 CUDA tensor of shape [%d, %d]" % (B, self.obs_dim))
         n = B if row_idx is None else (row_idx.shape[0] if n_rows is None else n_rows)
         E = self._model.num_nets
         if scratch is None:
@@ -97,25 +105,33 @@ class FakeEnv:
         if ev is not None:
             ev[1].record()
             self.kernel_events.append((ev[0], ev[1], n))
-        _lib.check(lib.cmbpo_fakeenv_post(self._task_id, E, self.obs_dim, self.act_dim, _lib.ptr(mean),
-                                          _lib.ptr(var), B, _lib.ptr(obs), _lib.ptr(act),
-                                          _lib.ptr(model_inds), _lib.ptr(row_idx), None, n,
-                                          _lib.ptr(out["next_obs"]), _lib.ptr(out["rew"]),
-                                          _lib.ptr(out["term"]), _lib.ptr(out["cost"]),
-                                          _lib.ptr(out["dkl_path"]), _lib.ptr(out["ep_var_mean"]),
-                                          _lib.ptr(out.get("ep_var")), stream), "cmbpo_fakeenv_post")
+        post = (self._task_id, E, self.obs_dim, self.act_dim, _lib.ptr(mean),
+                _lib.ptr(var), B, _lib.ptr(obs), _lib.ptr(act),
+                _lib.ptr(model_inds), _lib.ptr(row_idx), None, n,
+                _lib.ptr(out["next_obs"]), _lib.ptr(out["rew"]),
+                _lib.ptr(out["term"]), _lib.ptr(out["cost"]),
+                _lib.ptr(out["dkl_path"]), _lib.ptr(out["ep_var_mean"]),
+                _lib.ptr(out.get("ep_var")))
+        if noise is None:
+            _lib.check(lib.cmbpo_fakeenv_post(*post, stream), "cmbpo_fakeenv_post")
+        else:
+            _lib.check(lib.cmbpo_fakeenv_post_noise(*post, _lib.ptr(noise), stream), "cmbpo_fakeenv_post_noise")
         return out
 
-    def step(self, obs, act, deterministic=True, model_inds=None):
+    def step(self, obs, act, deterministic=True, model_inds=None, noise=None):
         assert len(obs.shape) == len(act.shape)
         assert obs.shape[-1] == self.obs_dim and act.shape[-1] == self.act_dim
         if not deterministic:
-            raise NotImplementedError("deterministic=False (mean + std) is never used by the trainer")
+            raise NotImplementedError("deterministic=False (mean + std) is never used by the trainer; pass "
+                                      "noise=np.ones((n, obs_dim), np.float32) for the reference's mean + std, or "
+                                      "N(0, 1) draws to sample the transition")
         if len(obs.shape) == 3:
             raise NotImplementedError("3-D inputs (forward_shuffle) are never used by the trainer")
         single = len(obs.shape) == 1
         if single:
             obs, act = obs[None], act[None]
+            if noise is not None and len(noise.shape) == 1:
+                noise = noise[None]
         was_np = not isinstance(obs, torch.Tensor)
         with torch.cuda.device(self.device):
             o = torch.as_tensor(np.ascontiguousarray(obs, dtype=np.float32) if was_np else obs,
@@ -123,6 +139,12 @@ class FakeEnv:
             a = torch.as_tensor(np.ascontiguousarray(act, dtype=np.float32) if was_np else act,
                                 dtype=torch.float32, device=self.device).contiguous()
             n = o.shape[0]
+            xi = None
+            if noise is not None:
+                xi = torch.as_tensor(np.ascontiguousarray(noise, dtype=np.float32) if not isinstance(noise, torch.Tensor)
+                                     else noise, dtype=torch.float32, device=self.device).contiguous()
+                if tuple(xi.shape) != (n, self.obs_dim):
+                    raise ValueError("noise must have shape [%d, %d], got %s" % (n, self.obs_dim, tuple(xi.shape)))
             if model_inds is None:
                 model_inds = self.random_inds(n)
             inds = torch.as_tensor(np.asarray(model_inds, dtype=np.int32), device=self.device) \
@@ -132,7 +154,7 @@ class FakeEnv:
                        term=torch.empty(n, dtype=torch.uint8, device=self.device),
                        cost=torch.empty(n, **f), dkl_path=torch.empty(n, **f),
                        ep_var_mean=torch.empty(n, **f), ep_var=torch.empty((n, self.obs_dim), **f))
-            self.step_device(o, a, inds, out)
+            self.step_device(o, a, inds, out, noise=xi)
         next_obs, r, terms = out["next_obs"], out["rew"][:, None], out["term"].bool()[:, None]
         c = out["cost"][:, None]
         if self._bool_cost:      # (not with a learned cost: the float32 prediction is the cost)

@@ -16,6 +16,9 @@ Event order, bootstraps and the budget rule follow ``model_sampler.py:239-375`` 
     are deterministic), so the extra ``get_v`` / ``get_vc`` calls of ``_finish_paths`` (``:401-407``) vanish;
   * branches never move: an ordered alive list replaces the boolean-mask compaction (``:300-311``).
 
+``ModelSampler(stochastic=True)`` samples every imagined transition from the elite member's N(mean, var) (``xi`` draws of
+the sampler's generator, ``cmbpo_fakeenv_post_noise``); off, the draws and the results are what they were without it.
+
 ``sample()`` returns ``(next_obs, reward, terminal, info)`` like the reference, but as slot-indexed CUDA
 tensors (the trainer only reads ``info['alive_ratio']``, ``algorithms/cmbpo.py:254-263``).
 """
@@ -33,12 +36,13 @@ EPS = 1e-8  # utilities/utils.py:19
 
 class ModelSampler:
     def __init__(self, max_path_length, batch_size=1000, rollout_mode=False, logger=None, seed=0,
-                 comm=None):
+                 comm=None, stochastic=False):
         self._max_path_length = int(max_path_length)
         self.batch_size = int(batch_size)
         self.rollout_mode = rollout_mode
         self.logger = logger
         self.comm = comm
+        self.stochastic = bool(stochastic)     # transitions drawn from N(mean, var) instead of the elite member's mean
         self.dkl_lim = float("inf")
         self.env = self.policy = self.pool = None
         self._n_episodes = 0
@@ -192,11 +196,13 @@ class ModelSampler:
         full[idx.long()] = torch.as_tensor(np.ascontiguousarray(compact), device=self.device).to(dtype)
         return full
 
-    def sample(self, max_samples=None, eps=None, model_inds=None):
+    def sample(self, max_samples=None, eps=None, model_inds=None, xi=None):
         """One imagined step of every alive branch (model_sampler.py:239-375).
 
         eps / model_inds (optional, compact alive-only order like the reference's arrays) inject the
-        N(0,1) action noise (ac_network.py:109) and the per-branch elite draw (fake_env.py:174-178).
+        N(0,1) action noise (ac_network.py:109) and the per-branch elite draw (fake_env.py:174-178);
+        xi ([n, obs_dim], the same order) the transition noise: next_obs = mean + std * xi + obs.  Without it a
+        `stochastic` sampler draws its own, any other sampler steps to the elite member's mean.
         """
         pool, env, pol = self.pool, self.env, self.policy
         assert pool.has_room                       # pool full! empty before sampling.
@@ -205,7 +211,7 @@ class ModelSampler:
             # this shard has nothing left but the others may: keep the collectives of the step matched
             return self._idle_step(max_samples)
         assert pool.n_alive > 0                    # reset before sampling !
-        if not sharded and eps is None and model_inds is None and env.kernel_events is None:
+        if not sharded and eps is None and model_inds is None and xi is None and env.kernel_events is None:
             if torch.cuda.current_device() != self.device.index:
                 with torch.cuda.device(self.device):
                     return self._sample_fast(max_samples)
@@ -215,11 +221,11 @@ class ModelSampler:
         n, B, A = pool.n_alive, self.batch_size, pool.act_dim
         with torch.cuda.device(self.device):
             idx = t["alive_idx"]
-            if eps is None or model_inds is None:
+            if eps is None or model_inds is None or (xi is None and self.stochastic):
                 # action noise and elite picks are drawn for several steps at a time (three torch launches per chunk
                 # instead of per step: at small rollout batches a step is a chain of launch latencies)
                 ck = getattr(self, "_draws", None)
-                if ck is None or ck[0] >= ck[1].shape[0] or ck[1].shape[1] != B:
+                if ck is None or ck[0] >= ck[1].shape[0] or ck[1].shape[1] != B or (ck[3] is None) == self.stochastic:
                     ck = self._draw_chunk()
                 k = ck[0]
                 ck[0] = k + 1
@@ -231,6 +237,11 @@ class ModelSampler:
                 inds_t = ck[2][k]
             else:
                 inds_t = self._scatter(model_inds, idx[:n], None, torch.int32)
+            if xi is not None:
+                xi_t = self._scatter(xi, idx[:n], pool.obs_dim)
+            else:
+                xi_t = ck[3][k] if self.stochastic else None
+            rs.xi = None if xi_t is None else xi_t.data_ptr()
             if getattr(self, "_scratch", None) is None or self._scratch[0].shape[1] != B:
                 E, O = env._model.num_nets, env.output_dim
                 self._scratch = (torch.empty((E, B, O), dtype=torch.float32, device=self.device),
@@ -260,7 +271,7 @@ class ModelSampler:
                 env.step_device(t["cur_obs"], t["act_t"], inds_t,
                                 dict(next_obs=t["next_obs"], rew=t["rew_t"], term=t["term_t"], cost=t["cost_t"],
                                      dkl_path=t["dkl_t"], ep_var_mean=t["epv_t"]),
-                                row_idx=idx, n_rows=n, scratch=self._scratch)
+                                row_idx=idx, n_rows=n, scratch=self._scratch, noise=xi_t)
                 if exchange:
                     # budget rule across shards: gather {n_alive, n_unc, total}, rank the survivors globally
                     pool._call("cmbpo_rollout_count")
@@ -303,13 +314,18 @@ class ModelSampler:
     def _draw_chunk(self):
         """Action noise and elite picks for several steps at a time (three torch launches per chunk instead of per step:
         at small rollout batches a step is a chain of launch latencies).  Returns the chunk list
-        [next step, eps [K, B, A], elite indices [K, B]]."""
+        [next step, eps [K, B, A], elite indices [K, B], xi [K, B, obs] or None].  A `stochastic` sampler draws the
+        transition noise after the elite picks, with K such that the chunk's bytes stay under the same cap; any other
+        sampler makes exactly the generator calls it always made."""
         B, A = self.batch_size, self.pool.act_dim
-        step_bytes = max(B * A * 4, 1)
+        step_bytes = max(B * (A + (self.pool.obs_dim if self.stochastic else 0)) * 4, 1)
         K = max(1, min(40, max(2 ** 23 // step_bytes, min(8, 2 ** 28 // step_bytes))))    # a whole rollout at small batches
         e_ck = torch.randn((K, B, A), generator=self._gen, dtype=torch.float32, device=self.device)
         d_ck = torch.randint(0, len(self._elites), (K, B), generator=self._gen, device=self.device)
-        self._draws = [0, e_ck, self._elites[d_ck]]
+        x_ck = None
+        if self.stochastic:
+            x_ck = torch.randn((K, B, self.pool.obs_dim), generator=self._gen, dtype=torch.float32, device=self.device)
+        self._draws = [0, e_ck, self._elites[d_ck], x_ck]
         return self._draws
 
     def _sample_fast(self, max_samples):
@@ -321,7 +337,7 @@ class ModelSampler:
         t, rs = pool.t, pool.rs
         n, B, A = pool.n_alive, self.batch_size, pool.act_dim
         ck = self._draws
-        if ck is None or ck[0] >= ck[1].shape[0] or ck[1].shape[1] != B:
+        if ck is None or ck[0] >= ck[1].shape[0] or ck[1].shape[1] != B or (ck[3] is None) == self.stochastic:
             ck = self._draw_chunk()
         k = ck[0]
         ck[0] = k + 1
@@ -336,6 +352,7 @@ class ModelSampler:
             self._handles = (pol.actor.mlp.handle, env._model.mlp.handle, pol.v.mlp.handle, pol.vc.mlp.handle,
                              self._scratch[0].data_ptr(), self._scratch[1].data_ptr())
         h = self._handles
+        rs.xi = ck[3].data_ptr() + k * B * pool.obs_dim * 4 if ck[3] is not None else None
         rs.max_samples = int(max_samples) if max_samples else 0
         rs.dkl_lim = float(self.dkl_lim)
         rs.max_path_length = self._max_path_length
@@ -416,10 +433,13 @@ class ModelSampler:
             done_o, alive_o, swaps_o = self._run_out
             while left > 0 and pool.n_alive > 0 and pool.has_room:
                 ck = self._draws
-                if ck is None or ck[0] >= ck[1].shape[0] or ck[1].shape[1] != B:
+                if ck is None or ck[0] >= ck[1].shape[0] or ck[1].shape[1] != B or (ck[3] is None) == self.stochastic:
                     ck = self._draw_chunk()
                 k = ck[0]
                 take = min(left, ck[1].shape[0] - k, 64)
+                # transition noise: step j of the call reads xi + j * xi_stride
+                rs.xi = ck[3].data_ptr() + k * B * pool.obs_dim * 4 if ck[3] is not None else None
+                rs.xi_stride = B * pool.obs_dim
                 _lib.check(lib.cmbpo_rollout_run(
                     C.byref(rs), pool.n_alive, h[0], h[1], h[2], h[3], env._task_id, env._model.num_nets,
                     ck[1].data_ptr() + k * B * A * 4, ck[2].data_ptr() + k * B * ck[2].element_size(), B * A, B,

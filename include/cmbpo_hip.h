@@ -211,7 +211,7 @@ int cmbpo_policy_forward(cmbpo_mlp_t *m, const float *d_obs, int obs_dim,
 /* FakeEnv.step after the ensemble forward (models/fake_env.py:104-151):
  * std = sqrt(var); ens_ep_var = var_E(mean[..., :obs]); dkl_path = mean_d
  * average_dkl(mean, std) (models/pens/utils.py:15-57, all E members);
- * next_obs = mean[elite[b], b, :obs] + obs (delta model, deterministic=True);
+ * next_obs = mean[elite[b], b, :obs] + obs (delta model, deterministic=True; cmbpo_fakeenv_post_noise below samples it);
  * r = mean[elite[b], b, obs]; term / cost from models/statics.py evaluated on
  * (obs, act, next_obs).  d_elite is the per-row member index (the draw of
  * models/fake_env.py:174-178, injected by the caller).  Row addressing as in
@@ -230,6 +230,24 @@ int cmbpo_fakeenv_post(int task, int ensemble, int obs_dim, int act_dim,
                        float *d_rew, uint8_t *d_term, float *d_cost,
                        float *d_dkl_path, float *d_ep_var_mean,
                        float *d_ep_var, void *stream);
+/* The same step with stochastic transitions: the imagined next state is drawn from the elite member's predictive
+ * distribution, N(mean, var) per observation dimension, instead of placed at its mean (the `deterministic=False` hook of
+ * models/fake_env.py:103-108, whose `+ pred_std` carries no random factor: it is the special case xi == 1).  d_xi is
+ * [., obs_dim] float32, slot indexed like d_obs (leading dimension ld_rows rows), one draw per (row, dimension) shared by
+ * all members of the row; only the observation columns move:
+ *   std_e = fl32(sqrt(var_e)) (correctly rounded);  m~_e = fl32(mean_e[:obs] + fl32(std_e * xi))   (no fused multiply-add)
+ *   ens_ep_var, dkl_path: cmbpo_fakeenv_post's formulas on m~_e and the unperturbed var_e (fake_env.py:112-113 run on the
+ *   shifted means);  next_obs = fl32(m~_elite + obs);  r and the learned cost: the elite's unperturbed mean columns;
+ *   term / cost rules on (obs, act, next_obs) as in cmbpo_fakeenv_post.
+ * d_xi == NULL forwards to cmbpo_fakeenv_post; the same argument checks, all before any HIP call. */
+int cmbpo_fakeenv_post_noise(int task, int ensemble, int obs_dim, int act_dim,
+                             const float *d_mean, const float *d_var, int ld_rows,
+                             const float *d_obs, const float *d_act,
+                             const int32_t *d_elite, const int32_t *d_row_idx,
+                             const int32_t *d_n_rows, int n_rows, float *d_next_obs,
+                             float *d_rew, uint8_t *d_term, float *d_cost,
+                             float *d_dkl_path, float *d_ep_var_mean,
+                             float *d_ep_var, const float *d_xi, void *stream);
 
 /* ------------------------------------------------------------------------ *
  * Device-resident rollout state: the fused counterpart of ModelSampler
@@ -275,6 +293,9 @@ typedef struct cmbpo_rollout {
   float *obs_buf, *act_buf, *mu_buf, *ls_buf;             /* [T,B,dim]         */
   float *rew_buf, *val_buf, *cost_buf, *cval_buf, *logp_buf; /* [T,B]          */
   float *adv_buf, *ret_buf, *cadv_buf, *cret_buf;         /* [T,B]             */
+  /* stochastic transitions (cmbpo_fakeenv_post_noise): NULL = off */
+  const float *xi;          /* [B,obs] N(0,1) draws of the step, slot indexed   */
+  int64_t xi_stride;        /* cmbpo_rollout_run: step k of a call reads xi + k * xi_stride */
 } cmbpo_rollout_t;
 
 /* iscal slots */
@@ -339,7 +360,8 @@ int cmbpo_rollout_compact(const cmbpo_rollout_t *r, void *stream);
 /* The whole step in one call (single-GPU jobs without a cross-shard budget exchange): cmbpo_policy_forward ->
  * cmbpo_ens_forward -> cmbpo_fakeenv_post -> decide -> finish(PRE) -> store -> cmbpo_ens_predict_mean x 2 at next_obs ->
  * finish(POST), every buffer taken from *r (slot-indexed d_eps [B, act], d_elite [B]; scratch d_mean / d_var
- * [E, B, model out_dim]: obs + 1, or obs + 2 with CMBPO_TASK_LEARNED_COST in `task`).  n_alive = the host's copy of iscal[CMBPO_I_N_ALIVE]. */
+ * [E, B, model out_dim]: obs + 1, or obs + 2 with CMBPO_TASK_LEARNED_COST in `task`).  n_alive = the host's copy of iscal[CMBPO_I_N_ALIVE].
+ * With r->xi != NULL the post-processing is cmbpo_fakeenv_post_noise on those draws. */
 /* Small rollout batches: decide + finish(PRE) + store (+ its statistics) as one single-workgroup launch for up to
  * cmbpo_rollout_book_pre_max_rows() alive rows (same decisions and per-branch arithmetic as the separate calls;
  * single-rank path).  cmbpo_rollout_step uses it by itself. */
@@ -362,7 +384,8 @@ int cmbpo_rollout_step(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *polic
  * until max_steps, no branch alive, at most min_alive alive (`alive_ratio <= 0.1`), total_samples >= stop_total
  * (stop_total = NaN: no such test; a threshold <= 0 is reached by the first step, as in the reference's
  * `_total_samples + samples_added >= .99 * approx_model_batch`) or a full buffer.  *r is left as the caller of cmbpo_rollout_step would leave it.
- * d_eps / d_elite: the draws of the first step; step k reads them k * eps_stride / k * elite_stride elements on.
+ * d_eps / d_elite: the draws of the first step; step k reads them k * eps_stride / k * elite_stride elements on, and, with
+ * r->xi != NULL, the transition noise at r->xi + k * r->xi_stride (the field itself is left as it was found).
  * h_scalars: [max_steps][384 bytes] of host memory (pinned), the counters of every step taken (iscal | dscal);
  * *list_swaps = how often alive_idx / alive_idx_out changed places. */
 int cmbpo_rollout_run(cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy, cmbpo_mlp_t *model, cmbpo_mlp_t *v,
