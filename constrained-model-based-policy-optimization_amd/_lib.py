@@ -180,6 +180,19 @@ SIGNATURES.update({
     "cmbpo_trainer_f16_paths": (_i, [_p]),
 })
 
+class TrainExtrasStruct(C.Structure):
+    """ctypes image of ``cmbpo_train_extras_t``: sample weights [N], old predictions [N][D] (device pointers, NULL = off)
+    and the clip range of the clipped value loss."""
+    _fields_ = [("d_weights", C.c_void_p), ("d_old_pred", C.c_void_p), ("kl_cliprange", C.c_float)]
+
+
+_ep = C.POINTER(TrainExtrasStruct)
+SIGNATURES.update({
+    "cmbpo_trainer_step_ex": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _ep, _p]),
+    "cmbpo_trainer_epoch_ex": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _i, _ep, _p]),
+    "cmbpo_trainer_losses_ex": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _p, _ep, _p]),
+})
+
 # start states of an imagined-rollout round (csrc/start_states.hip)
 START_MAX_RUNS = 1024                          # CMBPO_START_MAX_RUNS
 START_TABLE_INTS = 8 + 11 * START_MAX_RUNS     # CMBPO_START_TABLE_INTS

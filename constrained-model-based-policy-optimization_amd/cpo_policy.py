@@ -86,8 +86,10 @@ class CPOPolicy:
         self.vf_train_kwargs = dict(batch_size=self.vf_batch_size, min_epoch_before_break=self.vf_epochs,
                                     max_epochs=self.vf_epochs, holdout_ratio=self.vf_holdout)
         self.vf_decay = kw.get("vf_decay", 1e-6)
-        if kw.get("vf_clipping", False):
-            raise NotImplementedError("vf_clipping is off in every shipped config")
+        # cpo_policy.py:349-351: clip the critics' losses around the buffer's old values (a trust-region like update)
+        self.vf_cliploss = bool(kw.get("vf_clipping", False))
+        self.vf_cliprange = kw.get("vf_cliprange", 0.1)
+        self.cvf_cliprange = kw.get("cvf_cliprange", 0.1)
         self.vf_ensemble = kw.get("vf_ensemble_size", 5)
         self.vf_elites = kw.get("vf_elites", 3)
         self.vf_activation = kw.get("vf_activation", "ReLU")
@@ -117,8 +119,8 @@ class CPOPolicy:
                       num_elites=self.vf_elites, loss="MSE", activation="swish",
                       use_scaler_in=True, use_scaler_out=True, device=self.device, lr=self.vf_lr,
                       decay=self.vf_decay)
-        self.v = PE(self.obs_dim, 1, name="VEnsemble", **common)
-        self.vc = PE(self.obs_dim, 1, name="VCEnsemble", **common)
+        self.v = PE(self.obs_dim, 1, name="VEnsemble", clip_loss=self.vf_cliploss, kl_cliprange=self.vf_cliprange, **common)
+        self.vc = PE(self.obs_dim, 1, name="VCEnsemble", clip_loss=self.vf_cliploss, kl_cliprange=self.cvf_cliprange, **common)
         # pi_info placeholders' shapes (network/ac_network.py:113,120; algorithms/cmbpo.py:94)
         self.pi_info_shapes = {"mu": [self.act_dim], "log_std": [self.act_dim]}
         self._gen = torch.Generator(device=self.device)
@@ -220,9 +222,10 @@ class CPOPolicy:
         self.logger.store(**pre)
         train_kwargs = self.vf_train_kwargs.copy()
         train_kwargs.update(kwargs)
-        self.train_vf(obs, ret, **train_kwargs)
+        old_v, old_vc = (buf_inputs[7], buf_inputs[8]) if self.vf_cliploss else (None, None)
+        self.train_vf(obs, ret, old_v=old_v, **train_kwargs)
         if train_vc:
-            self.train_vc(obs, cret, **train_kwargs)
+            self.train_vc(obs, cret, old_vc=old_vc, **train_kwargs)
         if self.comm is not None and self.comm.world > 1:    # replicas: rank 0's critics are everyone's
             self.v.sync_weights(self.comm)
             self.vc.sync_weights(self.comm)
@@ -231,12 +234,16 @@ class CPOPolicy:
         self.logger.store(**deltas)
         return dict(pre=pre, post=post)
 
-    def train_vf(self, obs, ret, **kwargs):
-        """cpo_policy.py:700-715"""
+    def train_vf(self, obs, ret, old_v=None, **kwargs):
+        """cpo_policy.py:700-715; ``old_v``: the buffer's value column, the centre of the clip under vf_clipping"""
+        if self.vf_cliploss:
+            kwargs["old_pred"] = old_v[:, None]
         return self.v.train(obs, ret[:, None], **kwargs)
 
-    def train_vc(self, obs, cret, **kwargs):
+    def train_vc(self, obs, cret, old_vc=None, **kwargs):
         """cpo_policy.py:717-731"""
+        if self.vf_cliploss:
+            kwargs["old_pred"] = old_vc[:, None]
         return self.vc.train(obs, cret[:, None], **kwargs)
 
     def compute_v_losses(self, buf_inputs, rng=None):

@@ -26,11 +26,40 @@
 #include <math.h>
 #include <new>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 namespace {
 
 constexpr int kThreads = 256;
+
+// ------------------------------------------------------------------------------------------------------------
+// Optional terms of the deterministic ('MSE') loss, pe.py:866-868,881-905,917: per-sample weights and the clipped
+// prediction of a trust-region value update.  Kernels that know them are template instances of their own whose argument
+// type carries this block; the plain instances have neither the pointers nor the code.
+// ------------------------------------------------------------------------------------------------------------
+struct ValueExtras {
+  const float *w;          // [N] weight of data row r (nullptr: 1)
+  const float *old_pred;   // [N][D] earlier prediction of row r, unscaled (nullptr: no clipping)
+  const float *clip_c;     // the step's clip range c = sqrt(2) sqrt(kl old_var) (old_var_final_kernel); read when old_pred is set
+};
+
+// (m_c - t') w of one output, with the gradient of tf.clip_by_value: nothing outside [-c, c].  olds is the scaled old prediction.
+__device__ __forceinline__ float value_delta(float m, float t, bool clip, float olds, float c, float w) {
+  float d = m - t;
+  if (clip) {
+    const float dm = m - olds;
+    const float mc = olds + fminf(fmaxf(dm, -c), c);
+    d = (dm >= -c && dm <= c) ? mc - t : 0.0f;
+  }
+  return w * d;
+}
+
+__device__ __forceinline__ float scaled_old(const ValueExtras &x, int src, int D, int d, const float *out_mu, const float *out_sig) {
+  float v = x.old_pred[(size_t)src * D + d];
+  if (out_mu) v = (v - out_mu[d]) / out_sig[d];     // the transform of the targets: both sides of the clip in one unit
+  return v;
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // loss: per-member sums, then d(train_loss)/d(raw output)
@@ -44,6 +73,9 @@ struct LossArgs {
   int E, B, O, D;
   double *sums;            // [E]: sum (mean - t)^2
 };
+struct LossWArgs : LossArgs {
+  const float *w;          // [N] sample weights: sum w[row] (mean - t)^2
+};
 
 __device__ __forceinline__ float scaled_target(const LossArgs &p, int e, int b, int d) {
   const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
@@ -52,7 +84,8 @@ __device__ __forceinline__ float scaled_target(const LossArgs &p, int e, int b, 
   return t;
 }
 
-__global__ __launch_bounds__(kThreads) void loss_sums_kernel(const LossArgs p) {
+template <class P>
+__global__ __launch_bounds__(kThreads) void loss_sums_kernel(const P p) {
   const int e = blockIdx.y;
   double s_mse = 0.0;
   const int n = p.B * p.D;
@@ -60,7 +93,12 @@ __global__ __launch_bounds__(kThreads) void loss_sums_kernel(const LossArgs p) {
     const int b = i / p.D, d = i - b * p.D;
     const float *orow = p.o + ((size_t)e * p.B + b) * p.O;
     const float diff = orow[d] - scaled_target(p, e, b, d);
-    s_mse += (double)(diff * diff);
+    if constexpr (std::is_same<P, LossWArgs>::value) {
+      const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
+      s_mse += (double)p.w[row] * (double)(diff * diff);
+    } else {
+      s_mse += (double)(diff * diff);
+    }
   }
   __shared__ double sm[kThreads / 64];
   s_mse = wave_sum(s_mse);
@@ -77,6 +115,50 @@ __global__ __launch_bounds__(kThreads) void loss_sums_kernel(const LossArgs p) {
 __global__ void loss_finalize_kernel(const double *sums, int E, double inv_count, float *out) {
   const int e = threadIdx.x;
   if (e < E) out[e] = (float)(0.5 * sums[e] * inv_count);
+}
+
+// The clip range of one step (pe.py:890-893): old_var = mean over every member, row and output of 0.5 (old' - t')^2, c = sqrt(2)
+// sqrt(kl old_var).  It depends on the data alone, so it runs in front of the step: block k adds its elements (k, k + grid, ...
+// in units of 256) in float64 and leaves one partial, the second kernel adds the partials in index order, rounds once to
+// float32 and forms c.  No atomics: the step stays bitwise reproducible.
+constexpr int kOldVarParts = 128;
+struct OldVarArgs {
+  const float *targets, *old_pred;   // [N][D]
+  const int32_t *idx;
+  int idx_stride;
+  const float *out_mu, *out_sig;
+  int E, B, D;
+  double *part;                      // [gridDim.x]
+};
+
+__global__ __launch_bounds__(kThreads) void old_var_part_kernel(const OldVarArgs p) {
+  const long n = (long)p.E * p.B * p.D;
+  const int bd = p.B * p.D;
+  double s = 0.0;
+  for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) {
+    const int e = (int)(i / bd), r = (int)(i - (long)e * bd);
+    const int b = r / p.D, d = r - b * p.D;
+    const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
+    float t = p.targets[(size_t)row * p.D + d], o = p.old_pred[(size_t)row * p.D + d];
+    if (p.out_mu) { t = (t - p.out_mu[d]) / p.out_sig[d]; o = (o - p.out_mu[d]) / p.out_sig[d]; }
+    const float diff = o - t;
+    s += (double)(0.5f * (diff * diff));
+  }
+  __shared__ double sm[kThreads / 64];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) p.part[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+
+__global__ __launch_bounds__(64) void old_var_final_kernel(const double *part, int n_part, double inv_count, float kl, float *clip_c) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n_part; i += 64) s += part[i];
+  s = wave_sum(s);
+  if (threadIdx.x == 0) {
+    const float old_var = (float)(s * inv_count);
+    *clip_c = sqrtf(2.0f) * sqrtf(kl * old_var);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -100,6 +182,9 @@ struct BwdArgs {
   const double *loss_part;   // [n_items][3]
   float *d3_out;             // [E][B][OPk], written for the weight-gradient kernel
   float *opmax;              // [E * tiles][8]: largest |d1|, |d2|, |d3| of the tile into slots 3..5 (nullptr: not wanted)
+};
+struct BwdXArgs : BwdArgs {
+  ValueExtras x;             // deterministic heads (prob == 0) only
 };
 
 // `ratio` of the MSPE loss, 0.05 * mean_all(mse) / mean_all((var - mse)^2): a constant of the step.  The two sums come from
@@ -133,13 +218,19 @@ __device__ __forceinline__ float mspe_ratio(const BwdArgs &p, int tid) {
 // NLL (pe.py:840-919, inc_var_loss = True; prob == 2): total_e = mean 0.5 exp(-lv) (m - t)^2 + mean 0.5 lv; no
 // coupling between members.  (Its max_logvar / min_logvar variables only carry a constant regulariser gradient
 // and never enter the network, pe.py:198-209,263,789-838: they are host-side bookkeeping, pens.PE.)
-__device__ __forceinline__ float output_delta(const BwdArgs &p, int e, int row, int k, float ratio, float inv_bd) {
+template <class P>
+__device__ __forceinline__ float output_delta(const P &p, int e, int row, int k, float ratio, float inv_bd) {
   if (k >= p.O) return 0.0f;
   const float *orow = p.o + ((size_t)e * p.B + row) * p.O;
   const int src = p.idx ? p.idx[(size_t)e * p.idx_stride + row] : row;
   const int dd = (k < p.D) ? k : k - p.D;
   float t = p.targets[(size_t)src * p.D + dd];
   if (p.out_mu) t = (t - p.out_mu[dd]) / p.out_sig[dd];
+  if constexpr (std::is_same<P, BwdXArgs>::value) {     // weighted / clipped 'MSE' (DESIGN §3j); the host admits no other head
+    const bool clip = p.x.old_pred != nullptr;
+    const float olds = clip ? scaled_old(p.x, src, p.D, dd, p.out_mu, p.out_sig) : 0.0f;
+    return value_delta(orow[dd], t, clip, olds, clip ? *p.x.clip_c : 0.0f, p.x.w ? p.x.w[src] : 1.0f) * inv_bd;
+  }
   const float diff = orow[dd] - t;
   if (!p.prob) return diff * inv_bd;
   if (p.prob == 2) {
@@ -151,8 +242,8 @@ __device__ __forceinline__ float output_delta(const BwdArgs &p, int e, int row, 
   return (2.0f * ratio * (var - diff * diff) * var + 0.1f * lv) * inv_bd;
 }
 
-template <int HID>
-__global__ __launch_bounds__(kThreads, 2) void bwd_chain_kernel(const BwdArgs p) {
+template <int HID, class P>
+__global__ __launch_bounds__(kThreads, 2) void bwd_chain_kernel(const P p) {
   constexpr int BB = 32, NT = HID / 128, KG_H = HID / 8;
   extern __shared__ f32x4 smem[];
   f32x4 *hbuf = smem;                    // d2 tile, T-layout [HID/4][BB]
@@ -261,8 +352,9 @@ __global__ __launch_bounds__(kThreads, 2) void bwd_chain_kernel(const BwdArgs p)
 //   row tiles) -> stored, and split into the [64][512] two-piece image under a lift known before the product (|d2| <=
 //   1.1 max |W2| OPk max |d3[row]|) -> d1 = (d2 W1^T) * g1 (A fragments a slab ahead through a three-slot ring) -> stored.
 // ------------------------------------------------------------------------------------------------------------
+template <class BA>
 struct BwdHArgs {
-  BwdArgs b;
+  BA b;
   const f16x8 *w2t, *w1t;          // images [member][n-tile 16][k-slab][piece 2][lane 64] of 8 halves
   size_t w2t_stride, w1t_stride;    // per member, 16-byte units
   const float *stats;               // [E][NSTAT]: the weights' lift of layer l at [4 l], max |W| at [4 l + 3]
@@ -277,8 +369,9 @@ __host__ __device__ constexpr size_t bh_lds_bytes(int s3) {
   return (size_t)2 * kBhRows * kBhD2Str * 2 + (size_t)2 * kBhRows * bh_d3str(s3) * 2 + (size_t)4 * kBhRows * 4;
 }
 
-__global__ __launch_bounds__(kBhThreads) void bwd_chain_h_kernel(const BwdHArgs a) {
-  const BwdArgs &p = a.b;
+template <class BA>
+__global__ __launch_bounds__(kBhThreads) void bwd_chain_h_kernel(const BwdHArgs<BA> a) {
+  const BA &p = a.b;
   extern __shared__ f32x4 smem[];
   _Float16 *d2img = reinterpret_cast<_Float16 *>(smem);                         // [2 pieces][64][kBhD2Str]
   float *d3f = reinterpret_cast<float *>(smem);                                 // [64][OPk] fp32 (aliases d2img: consumed first)
@@ -1251,6 +1344,9 @@ struct FusedArgs {
   float *pW[3], *pB[3];                    // partial buffers [workgroup][E][...]
   size_t sW[3], sB[3];                     // floats per partial
 };
+struct FusedXArgs : FusedArgs {
+  ValueExtras x;
+};
 
 // One workgroup per CU (the grid is at most 32 x E workgroups) buys a 512-register budget, and that changes the
 // shape of the kernel: with one 32-column n-tile per wave a k-group is only 4 MFMAs (256 cycles), far too short to
@@ -1282,8 +1378,9 @@ __device__ __forceinline__ void mfma_frags(const f32x4 (&a)[KG], int kg, const f
   }
 }
 
-template <int N_IT>
-__global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const FusedArgs p) {
+template <int N_IT, class P>
+__global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const P p) {
+  constexpr bool X = std::is_same<P, FusedXArgs>::value;     // weights / clipping
   constexpr int HID = 128, KGH = HID / 8, RS = HID + 4, RED_LD = BB + 1;
   constexpr int KG0 = 4 * N_IT;             // k-groups of the (padded) input width
   extern __shared__ f32x4 smem4[];
@@ -1335,6 +1432,11 @@ __global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const Fused
 
   // gather (and scale) this thread's share of a tile's rows / targets into registers
   float xn[KG0], tn[4];
+  float on[X ? 4 : 1], wn = 1.0f;           // X: the scaled old predictions beside the targets, the row's weight
+  float clip_c = 0.0f;
+  if constexpr (X) {
+    if (p.x.old_pred) clip_c = *p.x.clip_c;
+  }
   auto gather = [&](int tile) {
     const int row0 = tile * BB;
 #pragma unroll
@@ -1363,7 +1465,12 @@ __global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const Fused
         if (p.out_mu) t = (t - p.out_mu[a]) / p.out_sig[a];
         tn[it] = t;
       }
+      if constexpr (X) {
+        on[it] = 0.0f;
+        if (a < p.O && src >= 0 && p.x.old_pred) on[it] = scaled_old(p.x, src, p.O, a, p.out_mu, p.out_sig);
+      }
     }
+    if constexpr (X) wn = (src >= 0 && p.x.w) ? p.x.w[src] : 1.0f;
   };
   if ((int)blockIdx.x < n_tiles) gather(blockIdx.x);
   __syncthreads();
@@ -1381,6 +1488,12 @@ __global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const Fused
     float tc[4];
 #pragma unroll
     for (int it = 0; it < 4; ++it) tc[it] = tn[it];
+    float oc[X ? 4 : 1], wc = 1.0f;
+    if constexpr (X) {
+#pragma unroll
+      for (int it = 0; it < 4; ++it) oc[it] = on[it];
+      wc = wn;
+    }
     __syncthreads();
     if (tile + (int)gridDim.x < n_tiles) gather(tile + gridDim.x);   // in flight under this tile's chain
     // ---- forward -------------------------------------------------------------------------------------------
@@ -1431,7 +1544,8 @@ __global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const Fused
           m += red[(2 * 32 + a) * RED_LD + eb];
           m += red[(3 * 32 + a) * RED_LD + eb];
           m += b2[a];
-          const float cot = valid ? (m - tc[it]) * inv_bd : 0.0f;
+          float cot = valid ? (m - tc[it]) * inv_bd : 0.0f;
+          if constexpr (X) cot = valid ? value_delta(m, tc[it], p.x.old_pred != nullptr, oc[it], clip_c, wc) * inv_bd : 0.0f;
           wR[eb * 36 + a] = cot;
           gb2p[it] += cot;
         }
@@ -1686,6 +1800,7 @@ struct cmbpo_trainer {
   float *parts[3], *dB[3];
   double *sums;
   double *loss_part;             // [E * ceil(max_batch / 32)][3] per-tile loss statistics of the training forward
+  double *old_var_part;          // [kOldVarParts] partial sums of a clipped step's old_var, then (as a float) its clip range c
   size_t wsize[3], bsize[3];
   float *opmax;                  // [E][ceil(max_batch / 32)][kOpMax] per-tile largest |x|, |h1|, |h2|, |d1|, |d2|, |d3| of the step
   // the backward chain on the f16 path (bwd_chain_h_kernel; 512-wide, at most 64 padded outputs): two-piece images of W1^T and
@@ -1777,10 +1892,10 @@ void fill_wgrad_args(cmbpo_trainer *t, int layer, int batch, WgradArgs &a, int &
   a.max_tiles = cmbpo_ceil_div(batch, 32);
 }
 
-template <int HID>
-int launch_bwd(const BwdArgs &a, int tiles, int E, size_t lds, hipStream_t s) {
-  if (int rc = cmbpo_grant_lds(bwd_chain_kernel<HID>, lds)) return rc;
-  hipLaunchKernelGGL(bwd_chain_kernel<HID>, dim3(tiles, E), dim3(kThreads), lds, s, a);
+template <int HID, class P>
+int launch_bwd(const P &a, int tiles, int E, size_t lds, hipStream_t s) {
+  if (int rc = cmbpo_grant_lds(bwd_chain_kernel<HID, P>, lds)) return rc;
+  hipLaunchKernelGGL((bwd_chain_kernel<HID, P>), dim3(tiles, E), dim3(kThreads), lds, s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1824,10 +1939,11 @@ int prepare_f16(cmbpo_trainer *t, hipStream_t s) {
   return CMBPO_OK;
 }
 
-int launch_bwd_h(cmbpo_trainer *t, const BwdArgs &b, int batch, hipStream_t s) {
+template <class BA>
+int launch_bwd_h(cmbpo_trainer *t, const BA &b, int batch, hipStream_t s) {
   if (int rc = prepare_f16(t, s)) return rc;
   f16x8 *base = reinterpret_cast<f16x8 *>(t->b16);
-  BwdHArgs a{};
+  BwdHArgs<BA> a{};
   a.b = b;
   a.w1t = base; a.w2t = base + t->b16_w2t_off;
   a.w1t_stride = t->b16_w1_units; a.w2t_stride = t->b16_w2t_units;
@@ -1835,8 +1951,8 @@ int launch_bwd_h(cmbpo_trainer *t, const BwdArgs &b, int batch, hipStream_t s) {
   a.s3 = t->b16_s3;
   a.tiles32 = cmbpo_ceil_div(batch, 32);
   const size_t lds = bh_lds_bytes(t->b16_s3);
-  if (int rc = cmbpo_grant_lds(bwd_chain_h_kernel, lds)) return rc;
-  hipLaunchKernelGGL(bwd_chain_h_kernel, dim3(cmbpo_ceil_div(batch, kBhRows), t->E), dim3(kBhThreads), lds, s, a);
+  if (int rc = cmbpo_grant_lds(bwd_chain_h_kernel<BA>, lds)) return rc;
+  hipLaunchKernelGGL(bwd_chain_h_kernel<BA>, dim3(cmbpo_ceil_div(batch, kBhRows), t->E), dim3(kBhThreads), lds, s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1915,10 +2031,12 @@ int launch_update(cmbpo_trainer *t, int apply, float lr_t, hipStream_t s) {
   return CMBPO_OK;
 }
 
+template <class P>
 int launch_fused(cmbpo_trainer *t, const float *d_inputs, const float *d_targets, const int32_t *d_idx, int idx_stride,
-                 int batch, hipStream_t s) {
+                 int batch, hipStream_t s, const ValueExtras *x = nullptr) {
   cmbpo_mlp *m = t->m;
-  FusedArgs a{};
+  P a{};
+  if constexpr (std::is_same<P, FusedXArgs>::value) a.x = *x;
   a.F0 = reinterpret_cast<const f32x4 *>(m->pack(0));
   a.F1 = reinterpret_cast<const f32x4 *>(m->pack(1));
   a.F2 = reinterpret_cast<const f32x4 *>(m->pack(2));
@@ -1939,12 +2057,38 @@ int launch_fused(cmbpo_trainer *t, const float *d_inputs, const float *d_targets
   const int G = t->ks[0];
   // every partial slot is written: workgroups beyond the batch's tiles store zeros
   if (t->IP <= 32) {
-    if (int rc = cmbpo_grant_lds(fused_mse_step_kernel<1>, 152 * 1024)) return rc;
-    hipLaunchKernelGGL(fused_mse_step_kernel<1>, dim3(G, t->E), dim3(kThreads), lds, s, a);
+    if (int rc = cmbpo_grant_lds(fused_mse_step_kernel<1, P>, 152 * 1024)) return rc;
+    hipLaunchKernelGGL((fused_mse_step_kernel<1, P>), dim3(G, t->E), dim3(kThreads), lds, s, a);
   } else {
-    if (int rc = cmbpo_grant_lds(fused_mse_step_kernel<2>, 152 * 1024)) return rc;
-    hipLaunchKernelGGL(fused_mse_step_kernel<2>, dim3(G, t->E), dim3(kThreads), lds, s, a);
+    if (int rc = cmbpo_grant_lds(fused_mse_step_kernel<2, P>, 152 * 1024)) return rc;
+    hipLaunchKernelGGL((fused_mse_step_kernel<2, P>), dim3(G, t->E), dim3(kThreads), lds, s, a);
   }
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
+template <class P>
+int launch_bwd_any(cmbpo_trainer *t, const P &b, int batch, hipStream_t s) {
+  const int H = t->H, E = t->E;
+  const size_t lds = ((size_t)H / 4 * 32 + (size_t)t->OPk / 4 * 32) * sizeof(f32x4);
+  const int tiles = cmbpo_ceil_div(batch, 32);
+  if (t->b16) return launch_bwd_h(t, b, batch, s);
+  return (H == 512) ? launch_bwd<512>(b, tiles, E, lds, s) : (H == 256 ? launch_bwd<256>(b, tiles, E, lds, s) : launch_bwd<128>(b, tiles, E, lds, s));
+}
+
+// the clip range of a step into t->old_var_part's last slot (old_var_part_kernel, old_var_final_kernel)
+float *clip_range_slot(cmbpo_trainer *t) { return reinterpret_cast<float *>(t->old_var_part + kOldVarParts); }
+
+int launch_old_var(cmbpo_trainer *t, const float *d_targets, const float *d_old_pred, const int32_t *d_idx, int idx_stride, int batch,
+                   float kl, hipStream_t s) {
+  OldVarArgs a{};
+  a.targets = d_targets; a.old_pred = d_old_pred; a.idx = d_idx; a.idx_stride = idx_stride;
+  a.out_mu = t->m->out_mu(); a.out_sig = t->m->out_sig();
+  a.E = t->E; a.B = batch; a.D = t->D; a.part = t->old_var_part;
+  const long n = (long)t->E * batch * t->D;
+  const int parts = (int)((n + kThreads - 1) / kThreads < kOldVarParts ? (n + kThreads - 1) / kThreads : kOldVarParts);
+  hipLaunchKernelGGL(old_var_part_kernel, dim3(parts), dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL(old_var_final_kernel, dim3(1), dim3(64), 0, s, t->old_var_part, parts, 1.0 / (double)n, kl, clip_range_slot(t));
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -2047,6 +2191,7 @@ extern "C" int cmbpo_trainer_create(cmbpo_trainer_t **out, cmbpo_mlp_t *m, int m
   const size_t osums = take(2 * (size_t)E);   // doubles
   const size_t olp = take(2 * 3 * (size_t)E * cmbpo_ceil_div(max_batch, 32));   // doubles
   const size_t oom = take((size_t)E * cmbpo_ceil_div(max_batch, 32) * kOpMax);
+  const size_t oov = take(2 * (size_t)(kOldVarParts + 1));   // doubles
   hipError_t err = hipMalloc(reinterpret_cast<void **>(&t->pool), off * sizeof(float));
   if (err != hipSuccess) {
     cmbpo_set_error("cmbpo_trainer_create: hipMalloc(%zu) failed: %s", off * sizeof(float), hipGetErrorString(err));
@@ -2072,6 +2217,7 @@ extern "C" int cmbpo_trainer_create(cmbpo_trainer_t **out, cmbpo_mlp_t *m, int m
   t->sums = reinterpret_cast<double *>(P + osums);
   t->loss_part = reinterpret_cast<double *>(P + olp);
   t->opmax = P + oom;
+  t->old_var_part = reinterpret_cast<double *>(P + oov);
   if (H == 512 && !t->fused && t->OPk <= 64) {
     // images for the f16 training kernels (bwd_chain_h_kernel, fwd_train_h_kernel); without them the fp32 kernels run
     t->b16_s3 = cmbpo_ceil_div(t->OPk, 16);
@@ -2204,29 +2350,38 @@ extern "C" int cmbpo_mlp_set_scalers(cmbpo_mlp_t *m, const float *h_in_mu, const
   return CMBPO_OK;
 }
 
-extern "C" int cmbpo_trainer_step(cmbpo_trainer_t *t, const float *d_inputs, int in_dim, const float *d_targets,
-                                  int target_dim, const int32_t *d_idx, int idx_stride, int batch, void *stream) {
-  CMBPO_REQUIRE(t && d_inputs && d_targets, "cmbpo_trainer_step: NULL argument");
-  if (!t->m->loaded) { cmbpo_set_error("cmbpo_trainer_step: weights not loaded"); return CMBPO_ESTATE; }
-  CMBPO_REQUIRE(in_dim == t->I, "cmbpo_trainer_step: in_dim %d != %d", in_dim, t->I);
-  CMBPO_REQUIRE(target_dim == t->D, "cmbpo_trainer_step: target_dim %d != %d", target_dim, t->D);
-  CMBPO_REQUIRE(batch >= 1 && batch <= t->max_batch, "cmbpo_trainer_step: batch %d not in [1, %d]", batch, t->max_batch);
-  CMBPO_REQUIRE(d_idx == nullptr || idx_stride >= 0, "cmbpo_trainer_step: negative idx_stride");
-  hipStream_t s = (hipStream_t)stream;
-  const int E = t->E, H = t->H;
+namespace {
 
+// One train_op.  x == nullptr: the plain step.  `who` names the entry point in messages.
+int trainer_step(const char *who, cmbpo_trainer_t *t, const float *d_inputs, int in_dim, const float *d_targets, int target_dim,
+                 const int32_t *d_idx, int idx_stride, int batch, const ValueExtras *x, float kl, void *stream) {
+  CMBPO_REQUIRE(t && d_inputs && d_targets, "%s: NULL argument", who);
+  if (!t->m->loaded) { cmbpo_set_error("%s: weights not loaded", who); return CMBPO_ESTATE; }
+  CMBPO_REQUIRE(in_dim == t->I, "%s: in_dim %d != %d", who, in_dim, t->I);
+  CMBPO_REQUIRE(target_dim == t->D, "%s: target_dim %d != %d", who, target_dim, t->D);
+  CMBPO_REQUIRE(batch >= 1 && batch <= t->max_batch, "%s: batch %d not in [1, %d]", who, batch, t->max_batch);
+  CMBPO_REQUIRE(d_idx == nullptr || idx_stride >= 0, "%s: negative idx_stride", who);
+  hipStream_t s = (hipStream_t)stream;
+  const int E = t->E;
+  int rc;
+
+  if (x && x->old_pred) {
+    rc = launch_old_var(t, d_targets, x->old_pred, d_idx, idx_stride, batch, kl, s);
+    if (rc != CMBPO_OK) return rc;
+  }
   if (t->fused) {
-    int rc = launch_fused(t, d_inputs, d_targets, d_idx, idx_stride, batch, s);
+    rc = x ? launch_fused<FusedXArgs>(t, d_inputs, d_targets, d_idx, idx_stride, batch, s, x)
+           : launch_fused<FusedArgs>(t, d_inputs, d_targets, d_idx, idx_stride, batch, s);
     if (rc != CMBPO_OK) return rc;
     t->step += 1;
     return launch_update(t, 1, adam_rate(t), s);
   }
 
   // training forward (+ per-tile loss statistics) -> backward chain (+ output deltas) -> weight gradients -> Adam
-  int rc = run_forward(t, d_inputs, d_idx, idx_stride, batch, true, s, d_targets);
+  rc = run_forward(t, d_inputs, d_idx, idx_stride, batch, true, s, d_targets);
   if (rc != CMBPO_OK) return rc;
 
-  BwdArgs b{};
+  BwdXArgs b{};
   b.wpb2 = reinterpret_cast<const f32x4 *>(t->wpb2); b.wpb1 = reinterpret_cast<const f32x4 *>(t->wpb1);
   b.wpb2_stride = t->wpb2_floats / 4; b.wpb1_stride = t->wpb1_floats / 4;
   b.g2 = t->g2; b.g1 = t->g1; b.d2 = t->d2; b.d1 = t->d1;
@@ -2236,13 +2391,15 @@ extern "C" int cmbpo_trainer_step(cmbpo_trainer_t *t, const float *d_inputs, int
   b.out_mu = t->m->out_mu(); b.out_sig = t->m->out_sig();
   b.loss_part = t->loss_part; b.d3_out = t->d3;
   b.opmax = t->opmax;
-  const size_t lds = ((size_t)H / 4 * 32 + (size_t)t->OPk / 4 * 32) * sizeof(f32x4);
-  const int tiles = cmbpo_ceil_div(batch, 32);
-  if (t->b16) rc = launch_bwd_h(t, b, batch, s);
-  else rc = (H == 512) ? launch_bwd<512>(b, tiles, E, lds, s) : (H == 256 ? launch_bwd<256>(b, tiles, E, lds, s) : launch_bwd<128>(b, tiles, E, lds, s));
+  if (x) {
+    b.x = *x;
+    rc = launch_bwd_any<BwdXArgs>(t, b, batch, s);
+  } else {
+    rc = launch_bwd_any<BwdArgs>(t, b, batch, s);
+  }
   if (rc != CMBPO_OK) return rc;
 
-  if (H == 512) {
+  if (t->H == 512) {
     rc = launch_wgrad_all(t, batch, s);
     if (rc != CMBPO_OK) return rc;
   } else {
@@ -2259,29 +2416,27 @@ extern "C" int cmbpo_trainer_step(cmbpo_trainer_t *t, const float *d_inputs, int
 
 // One pass over the bootstrap index lists: ceil(n_rows / batch) train_ops enqueued back to back (the inner loop of
 // PE.train, models/pens/pe.py:541-563), the last one on the ragged remainder.
-extern "C" int cmbpo_trainer_epoch(cmbpo_trainer_t *t, const float *d_inputs, int in_dim, const float *d_targets,
-                                   int target_dim, const int32_t *d_idx, int idx_stride, int n_rows, int batch,
-                                   void *stream) {
-  CMBPO_REQUIRE(t && d_inputs && d_targets && d_idx, "cmbpo_trainer_epoch: NULL argument");
-  CMBPO_REQUIRE(n_rows >= 1 && batch >= 1 && batch <= t->max_batch, "cmbpo_trainer_epoch: n_rows %d / batch %d (max %d)",
-                n_rows, batch, t->max_batch);
-  CMBPO_REQUIRE(idx_stride >= n_rows, "cmbpo_trainer_epoch: idx_stride %d < n_rows %d", idx_stride, n_rows);
+int trainer_epoch(const char *who, cmbpo_trainer_t *t, const float *d_inputs, int in_dim, const float *d_targets, int target_dim,
+                  const int32_t *d_idx, int idx_stride, int n_rows, int batch, const ValueExtras *x, float kl, void *stream) {
+  CMBPO_REQUIRE(t && d_inputs && d_targets && d_idx, "%s: NULL argument", who);
+  CMBPO_REQUIRE(n_rows >= 1 && batch >= 1 && batch <= t->max_batch, "%s: n_rows %d / batch %d (max %d)", who, n_rows, batch, t->max_batch);
+  CMBPO_REQUIRE(idx_stride >= n_rows, "%s: idx_stride %d < n_rows %d", who, idx_stride, n_rows);
   for (int r0 = 0; r0 < n_rows; r0 += batch) {
     const int b = min(batch, n_rows - r0);
-    const int rc = cmbpo_trainer_step(t, d_inputs, in_dim, d_targets, target_dim, d_idx + r0, idx_stride, b, stream);
+    const int rc = trainer_step(who, t, d_inputs, in_dim, d_targets, target_dim, d_idx + r0, idx_stride, b, x, kl, stream);
     if (rc != CMBPO_OK) return rc;
   }
   return CMBPO_OK;
 }
 
-extern "C" int cmbpo_trainer_losses(cmbpo_trainer_t *t, const float *d_inputs, int in_dim, const float *d_targets,
-                                    int target_dim, const int32_t *d_idx, int idx_stride, int n_rows, float *d_losses,
-                                    void *stream) {
-  CMBPO_REQUIRE(t && d_inputs && d_targets && d_losses, "cmbpo_trainer_losses: NULL argument");
-  if (!t->m->loaded) { cmbpo_set_error("cmbpo_trainer_losses: weights not loaded"); return CMBPO_ESTATE; }
-  CMBPO_REQUIRE(in_dim == t->I && target_dim == t->D, "cmbpo_trainer_losses: dims (%d, %d) != (%d, %d)", in_dim, target_dim, t->I, t->D);
-  CMBPO_REQUIRE(n_rows >= 1, "cmbpo_trainer_losses: n_rows %d", n_rows);
-  CMBPO_REQUIRE(d_idx != nullptr || n_rows <= t->max_batch, "cmbpo_trainer_losses: %d direct rows exceed max_batch %d (pass an index list)",
+// `self.loss`; d_weights == nullptr: unweighted
+int trainer_losses(const char *who, cmbpo_trainer_t *t, const float *d_inputs, int in_dim, const float *d_targets, int target_dim,
+                   const int32_t *d_idx, int idx_stride, int n_rows, float *d_losses, const float *d_weights, void *stream) {
+  CMBPO_REQUIRE(t && d_inputs && d_targets && d_losses, "%s: NULL argument", who);
+  if (!t->m->loaded) { cmbpo_set_error("%s: weights not loaded", who); return CMBPO_ESTATE; }
+  CMBPO_REQUIRE(in_dim == t->I && target_dim == t->D, "%s: dims (%d, %d) != (%d, %d)", who, in_dim, target_dim, t->I, t->D);
+  CMBPO_REQUIRE(n_rows >= 1, "%s: n_rows %d", who, n_rows);
+  CMBPO_REQUIRE(d_idx != nullptr || n_rows <= t->max_batch, "%s: %d direct rows exceed max_batch %d (pass an index list)", who,
                 n_rows, t->max_batch);
   hipStream_t s = (hipStream_t)stream;
   const int E = t->E;
@@ -2291,17 +2446,92 @@ extern "C" int cmbpo_trainer_losses(cmbpo_trainer_t *t, const float *d_inputs, i
     const int32_t *idx = d_idx ? d_idx + r0 : nullptr;
     int rc = run_forward(t, d_inputs, idx, idx_stride, rows, false, s);
     if (rc != CMBPO_OK) return rc;
-    LossArgs l{};   // (only the squared error of the mean head is needed)
+    LossWArgs l{};   // (only the squared error of the mean head is needed)
     l.o = t->o; l.targets = d_targets; l.idx = idx; l.idx_stride = idx_stride;
     l.out_mu = t->m->out_mu(); l.out_sig = t->m->out_sig();
     l.E = E; l.B = rows; l.O = t->O; l.D = t->D;
     l.sums = t->sums;
+    l.w = d_weights;
     const int gx = min(cmbpo_ceil_div(rows * t->D, kThreads), 64);
-    hipLaunchKernelGGL(loss_sums_kernel, dim3(gx, E), dim3(kThreads), 0, s, l);
+    if (d_weights) hipLaunchKernelGGL(loss_sums_kernel<LossWArgs>, dim3(gx, E), dim3(kThreads), 0, s, l);
+    else hipLaunchKernelGGL(loss_sums_kernel<LossArgs>, dim3(gx, E), dim3(kThreads), 0, s, static_cast<const LossArgs &>(l));
   }
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, s, t->sums, E, 1.0 / ((double)n_rows * t->D), d_losses);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
+}
+
+// The checks of the *_ex entries, all before any HIP call.  Returns CMBPO_OK with *on = false when the block asks for nothing
+// (the caller forwards to the plain entry).  Clipping is never part of `self.loss`: `losses` ignores old_pred and the range.
+int check_extras(const char *who, const cmbpo_trainer_t *t, const cmbpo_train_extras_t *ex, bool losses, ValueExtras *x, bool *on) {
+  *on = false;
+  if (!ex || (!ex->d_weights && (losses || !ex->d_old_pred))) return CMBPO_OK;
+  const bool clip = !losses && ex->d_old_pred;
+  CMBPO_REQUIRE(!clip || (isfinite(ex->kl_cliprange) && ex->kl_cliprange >= 0.0f), "%s: kl_cliprange %g is not a finite number >= 0", who,
+                (double)ex->kl_cliprange);
+  CMBPO_REQUIRE(t != nullptr, "%s: NULL argument", who);
+  CMBPO_REQUIRE(!(t->prob && !t->nll), "%s: the 'MSPE' loss takes neither weights nor old predictions (_mspe_loss, pe.py:921)", who);
+  CMBPO_REQUIRE(!(t->prob && clip), "%s: clipping on a probabilistic head needs old_pred_var (pe.py:895-900): not provided", who);
+  CMBPO_REQUIRE(!t->prob, "%s: weights are provided for deterministic ('MSE') heads only", who);
+  x->w = ex->d_weights;
+  x->old_pred = clip ? ex->d_old_pred : nullptr;
+  x->clip_c = clip ? clip_range_slot(const_cast<cmbpo_trainer_t *>(t)) : nullptr;
+  *on = true;
+  return CMBPO_OK;
+}
+
+}  // namespace
+
+extern "C" int cmbpo_trainer_step(cmbpo_trainer_t *t, const float *d_inputs, int in_dim, const float *d_targets,
+                                  int target_dim, const int32_t *d_idx, int idx_stride, int batch, void *stream) {
+  return trainer_step("cmbpo_trainer_step", t, d_inputs, in_dim, d_targets, target_dim, d_idx, idx_stride, batch, nullptr, 0.0f, stream);
+}
+
+extern "C" int cmbpo_trainer_epoch(cmbpo_trainer_t *t, const float *d_inputs, int in_dim, const float *d_targets,
+                                   int target_dim, const int32_t *d_idx, int idx_stride, int n_rows, int batch,
+                                   void *stream) {
+  return trainer_epoch("cmbpo_trainer_epoch", t, d_inputs, in_dim, d_targets, target_dim, d_idx, idx_stride, n_rows, batch, nullptr, 0.0f,
+                       stream);
+}
+
+extern "C" int cmbpo_trainer_losses(cmbpo_trainer_t *t, const float *d_inputs, int in_dim, const float *d_targets,
+                                    int target_dim, const int32_t *d_idx, int idx_stride, int n_rows, float *d_losses,
+                                    void *stream) {
+  return trainer_losses("cmbpo_trainer_losses", t, d_inputs, in_dim, d_targets, target_dim, d_idx, idx_stride, n_rows, d_losses, nullptr,
+                        stream);
+}
+
+extern "C" int cmbpo_trainer_step_ex(cmbpo_trainer_t *t, const float *d_inputs, int in_dim, const float *d_targets,
+                                     int target_dim, const int32_t *d_idx, int idx_stride, int batch,
+                                     const cmbpo_train_extras_t *extras, void *stream) {
+  ValueExtras x{};
+  bool on;
+  if (int rc = check_extras("cmbpo_trainer_step_ex", t, extras, false, &x, &on)) return rc;
+  if (!on) return cmbpo_trainer_step(t, d_inputs, in_dim, d_targets, target_dim, d_idx, idx_stride, batch, stream);
+  return trainer_step("cmbpo_trainer_step_ex", t, d_inputs, in_dim, d_targets, target_dim, d_idx, idx_stride, batch, &x,
+                      extras->kl_cliprange, stream);
+}
+
+extern "C" int cmbpo_trainer_epoch_ex(cmbpo_trainer_t *t, const float *d_inputs, int in_dim, const float *d_targets,
+                                      int target_dim, const int32_t *d_idx, int idx_stride, int n_rows, int batch,
+                                      const cmbpo_train_extras_t *extras, void *stream) {
+  ValueExtras x{};
+  bool on;
+  if (int rc = check_extras("cmbpo_trainer_epoch_ex", t, extras, false, &x, &on)) return rc;
+  if (!on) return cmbpo_trainer_epoch(t, d_inputs, in_dim, d_targets, target_dim, d_idx, idx_stride, n_rows, batch, stream);
+  return trainer_epoch("cmbpo_trainer_epoch_ex", t, d_inputs, in_dim, d_targets, target_dim, d_idx, idx_stride, n_rows, batch, &x,
+                       extras->kl_cliprange, stream);
+}
+
+extern "C" int cmbpo_trainer_losses_ex(cmbpo_trainer_t *t, const float *d_inputs, int in_dim, const float *d_targets,
+                                       int target_dim, const int32_t *d_idx, int idx_stride, int n_rows, float *d_losses,
+                                       const cmbpo_train_extras_t *extras, void *stream) {
+  ValueExtras x{};
+  bool on;
+  if (int rc = check_extras("cmbpo_trainer_losses_ex", t, extras, true, &x, &on)) return rc;
+  if (!on) return cmbpo_trainer_losses(t, d_inputs, in_dim, d_targets, target_dim, d_idx, idx_stride, n_rows, d_losses, stream);
+  return trainer_losses("cmbpo_trainer_losses_ex", t, d_inputs, in_dim, d_targets, target_dim, d_idx, idx_stride, n_rows, d_losses, x.w,
+                        stream);
 }
 
 extern "C" long cmbpo_trainer_steps_done(const cmbpo_trainer_t *t) { return t ? t->step : -1; }

@@ -16,7 +16,8 @@ Training (``PE.train``, ``models/pens/pe.py:457-646``; SURVEY §8(f) rows N1 / N
 reference's host control flow (holdout split, bootstrap indices, epoch loop, early stopping,
 elite ranking) and runs every ``sess.run(train_op)`` / ``sess.run(self.loss)`` as HIP kernels
 over device-resident data (``csrc/ens_train.hip``).  Losses: 'MSPE' (dynamics) and 'MSE'
-(critics), the two every shipped config uses.
+(critics), the two every shipped config uses, 'NLL', and for 'MSE' the sample-weighted and clipped
+variants (``weighted`` / ``clip_loss``).
 """
 import ctypes as C
 import itertools
@@ -195,28 +196,58 @@ class EnsembleTrainer:
             _lib.check(_lib.lib().cmbpo_trainer_reset_optimizer(self._h, _lib.current_stream()),
                        "cmbpo_trainer_reset_optimizer")
 
-    def step(self, inputs, targets, idx_ptr, idx_stride, batch):
-        """One train_op on device tensors inputs[N,in] / targets[N,D]; member e uses rows idx[e*idx_stride + b]."""
-        with torch.cuda.device(self.mlp.device):
-            _lib.check(_lib.lib().cmbpo_trainer_step(
-                self._h, _lib.ptr(inputs), inputs.shape[1], _lib.ptr(targets), targets.shape[1], idx_ptr,
-                int(idx_stride), int(batch), _lib.current_stream()), "cmbpo_trainer_step")
+    @staticmethod
+    def _extras(weights, old_pred, kl_cliprange):
+        """``cmbpo_train_extras_t`` of float32 device tensors weights[N] / old_pred[N,D] (None: the plain entry)."""
+        if weights is None and old_pred is None:
+            return None
+        return _lib.TrainExtrasStruct(_lib.ptr(weights), _lib.ptr(old_pred), float(kl_cliprange))
 
-    def epoch(self, inputs, targets, idx, batch):
+    def step(self, inputs, targets, idx_ptr, idx_stride, batch, weights=None, old_pred=None, kl_cliprange=0.1):
+        """One train_op on device tensors inputs[N,in] / targets[N,D]; member e uses rows idx[e*idx_stride + b].
+        ``weights`` [N] / ``old_pred`` [N,D] (device tensors addressed through the same rows) weight the samples / clip the
+        prediction around the old one (deterministic heads)."""
+        ex = self._extras(weights, old_pred, kl_cliprange)
+        with torch.cuda.device(self.mlp.device):
+            if ex is None:
+                _lib.check(_lib.lib().cmbpo_trainer_step(
+                    self._h, _lib.ptr(inputs), inputs.shape[1], _lib.ptr(targets), targets.shape[1], idx_ptr,
+                    int(idx_stride), int(batch), _lib.current_stream()), "cmbpo_trainer_step")
+            else:
+                _lib.check(_lib.lib().cmbpo_trainer_step_ex(
+                    self._h, _lib.ptr(inputs), inputs.shape[1], _lib.ptr(targets), targets.shape[1], idx_ptr,
+                    int(idx_stride), int(batch), C.byref(ex), _lib.current_stream()), "cmbpo_trainer_step_ex")
+
+    def epoch(self, inputs, targets, idx, batch, weights=None, old_pred=None, kl_cliprange=0.1):
         """All minibatches of one epoch over idx[E, n] (int32 device tensor), enqueued in one call."""
+        ex = self._extras(weights, old_pred, kl_cliprange)
         with torch.cuda.device(self.mlp.device):
-            _lib.check(_lib.lib().cmbpo_trainer_epoch(
-                self._h, _lib.ptr(inputs), inputs.shape[1], _lib.ptr(targets), targets.shape[1], _lib.ptr(idx),
-                int(idx.shape[1]), int(idx.shape[1]), int(batch), _lib.current_stream()), "cmbpo_trainer_epoch")
+            if ex is None:
+                _lib.check(_lib.lib().cmbpo_trainer_epoch(
+                    self._h, _lib.ptr(inputs), inputs.shape[1], _lib.ptr(targets), targets.shape[1], _lib.ptr(idx),
+                    int(idx.shape[1]), int(idx.shape[1]), int(batch), _lib.current_stream()), "cmbpo_trainer_epoch")
+            else:
+                _lib.check(_lib.lib().cmbpo_trainer_epoch_ex(
+                    self._h, _lib.ptr(inputs), inputs.shape[1], _lib.ptr(targets), targets.shape[1], _lib.ptr(idx),
+                    int(idx.shape[1]), int(idx.shape[1]), int(batch), C.byref(ex), _lib.current_stream()),
+                    "cmbpo_trainer_epoch_ex")
 
-    def losses(self, inputs, targets, idx, idx_stride, n_rows, out=None):
-        """`self.loss` per member (device tensor [E]); idx: int32 device tensor of rows (idx_stride 0: shared)."""
+    def losses(self, inputs, targets, idx, idx_stride, n_rows, out=None, weights=None):
+        """`self.loss` per member (device tensor [E]); idx: int32 device tensor of rows (idx_stride 0: shared).
+        ``weights`` [N]: the weighted loss (never clipped)."""
         if out is None:
             out = torch.empty(self.mlp.ensemble, dtype=torch.float32, device=self.mlp.device)
+        ex = self._extras(weights, None, 0.0)
         with torch.cuda.device(self.mlp.device):
-            _lib.check(_lib.lib().cmbpo_trainer_losses(
-                self._h, _lib.ptr(inputs), inputs.shape[1], _lib.ptr(targets), targets.shape[1], _lib.ptr(idx),
-                int(idx_stride), int(n_rows), _lib.ptr(out), _lib.current_stream()), "cmbpo_trainer_losses")
+            if ex is None:
+                _lib.check(_lib.lib().cmbpo_trainer_losses(
+                    self._h, _lib.ptr(inputs), inputs.shape[1], _lib.ptr(targets), targets.shape[1], _lib.ptr(idx),
+                    int(idx_stride), int(n_rows), _lib.ptr(out), _lib.current_stream()), "cmbpo_trainer_losses")
+            else:
+                _lib.check(_lib.lib().cmbpo_trainer_losses_ex(
+                    self._h, _lib.ptr(inputs), inputs.shape[1], _lib.ptr(targets), targets.shape[1], _lib.ptr(idx),
+                    int(idx_stride), int(n_rows), _lib.ptr(out), C.byref(ex), _lib.current_stream()),
+                    "cmbpo_trainer_losses_ex")
         return out
 
     @property
@@ -344,8 +375,17 @@ class PE(TrainControl):
 
     def __init__(self, in_dim, out_dim, name="BNN", hidden_dims=(512, 512), num_networks=7,
                  num_elites=5, loss="MSPE", activation="swish", use_scaler_in=False,
-                 use_scaler_out=False, device=None, lr=1e-3, decay=1e-4, max_logvar=.5, min_logvar=-6, **_unused):
+                 use_scaler_out=False, device=None, lr=1e-3, decay=1e-4, max_logvar=.5, min_logvar=-6,
+                 clip_loss=False, kl_cliprange=0.1, weighted=False, **_unused):
         hidden_dims = tuple(int(h) for h in hidden_dims)
+        # clipped / sample-weighted value losses (pe.py:67-68,150,232-244): the deterministic 'MSE' head only
+        if (clip_loss or weighted) and loss != "MSE":
+            raise NotImplementedError("clip_loss / weighted are provided for loss='MSE' (the clipped 'NLL' loss needs "
+                                      "old_pred_var, _mspe_loss takes neither); got %r" % (loss,))
+        if clip_loss and not (np.isfinite(kl_cliprange) and kl_cliprange >= 0):
+            raise ValueError("kl_cliprange must be a finite number >= 0; got %r" % (kl_cliprange,))
+        self.clip_loss, self.kl_cliprange, self.weighted = bool(clip_loss), float(kl_cliprange), bool(weighted)
+        self._train_extras = (None, None, self.kl_cliprange)
         if len(hidden_dims) != 2 or hidden_dims[0] != hidden_dims[1]:
             raise ValueError("the HIP path supports two equal hidden layers (all shipped configs: "
                              "(512,512) dynamics, (128,128) critics); got %r" % (hidden_dims,))
@@ -639,8 +679,17 @@ class PE(TrainControl):
         if self.loss_type not in ("MSPE", "MSE", "NLL"):
             raise NotImplementedError("HIP training covers 'MSPE', 'MSE' (the shipped configs) and 'NLL'; got %r"
                                       % (self.loss_type,))
-        if kwargs.get("weights") is not None or kwargs.get("old_pred") is not None:
-            raise NotImplementedError("weighted / clipped losses (vf_clipping) are off in every shipped config")
+        weights, old_pred = kwargs.get("weights"), kwargs.get("old_pred")
+        if weights is not None and not self.weighted:
+            raise NotImplementedError("weights= needs a model built with weighted=True (loss 'MSE')")
+        if old_pred is not None and not self.clip_loss:
+            raise NotImplementedError("old_pred= needs a model built with clip_loss=True (loss 'MSE')")
+        if self.clip_loss and old_pred is None:
+            raise ValueError("a clip_loss model trains on old_pred= (the predictions the clip is centred on)")
+        kl = kwargs.get("kl_cliprange", self.kl_cliprange)       # pe.py:495-496
+        if self.clip_loss and not (np.isfinite(kl) and kl >= 0):
+            raise ValueError("kl_cliprange must be a finite number >= 0; got %r" % (kl,))
+        self._train_extras = (weights, old_pred, float(kl))
 
     def _begin_train(self, inputs, targets, train_rows_h, holdout_rows_h, batch_size):
         """Data to the device once, scaler fit on the training rows (pe.py:518-523), trainer handle."""
@@ -668,6 +717,20 @@ class PE(TrainControl):
             (self.scaler_out.cached_mu, self.scaler_out.cached_var) if self.use_scaler_out else None)
         c["loss_buf"] = torch.empty(self.num_nets, dtype=torch.float32, device=self.device)
         c["batch_size"] = int(batch_size)
+        # the whole arrays, addressed through the same row indices as inputs and targets
+        weights, old_pred, c["kl"] = self._train_extras
+        self._train_extras = (None, None, self.kl_cliprange)
+        n = c["x"].shape[0]
+        c["w"] = c["old"] = None
+        if weights is not None:
+            c["w"] = _to_dev(weights, self.device)[0].reshape(-1)
+            if c["w"].shape[0] != n:
+                raise ValueError("weights: %d entries for %d rows" % (c["w"].shape[0], n))
+        if old_pred is not None:
+            c["old"] = _to_dev(old_pred, self.device)[0]
+            c["old"] = c["old"][:, None] if c["old"].dim() == 1 else c["old"]
+            if c["old"].shape != c["t"].shape:
+                raise ValueError("old_pred %r does not match the targets %r" % (tuple(c["old"].shape), tuple(c["t"].shape)))
 
     def _begin_epoch(self, idxs_h):
         """Rows of the full data set each member visits this epoch: train_rows[idxs] (inputs[batch_idxs], pe.py:543)."""
@@ -681,12 +744,13 @@ class PE(TrainControl):
     def _train_batch(self, batch_num, rows):
         c = self._ctx
         n = c["gidx"].shape[1]
-        c["tr"].step(c["x"], c["t"], c["gidx"].data_ptr() + 4 * batch_num * c["batch_size"], n, rows)
+        c["tr"].step(c["x"], c["t"], c["gidx"].data_ptr() + 4 * batch_num * c["batch_size"], n, rows,
+                     weights=c["w"], old_pred=c["old"], kl_cliprange=c["kl"])
         self._weights_on_device = True
 
     def _train_epoch(self, n, batch_size):
         c = self._ctx
-        c["tr"].epoch(c["x"], c["t"], c["gidx"], batch_size)
+        c["tr"].epoch(c["x"], c["t"], c["gidx"], batch_size, weights=c["w"], old_pred=c["old"], kl_cliprange=c["kl"])
         self._weights_on_device = True
         return int(np.ceil(n / batch_size))
 
@@ -702,7 +766,7 @@ class PE(TrainControl):
             # the reference feeds empty arrays here and ranks NaN losses (argsort keeps the member order)
             return np.full(self.num_nets, np.nan, np.float32)
         return c["tr"].losses(c["x"], c["t"], c["holdout_rows"], 0, c["holdout_rows"].shape[0],
-                              out=c["loss_buf"]).cpu().numpy()
+                              out=c["loss_buf"], weights=c["w"]).cpu().numpy()
 
     def _finish_train(self):
         self._ctx = None
@@ -713,14 +777,12 @@ def build_PE(in_dim, out_dim, name="BNN", hidden_dims=(200, 200, 200), num_netwo
              lr_decay=None, decay_steps=None, use_scaler_in=False, use_scaler_out=False,
              clip_loss=False, kl_cliprange=0.1, max_logvar=.5, min_logvar=-6, session=None, device=None):
     """Same signature as models/pens/pe_factory.py:9-29 (Adam with a constant learning rate; lr_decay is unused by
-    every shipped config)."""
+    every shipped config).  ``clip_loss`` / ``kl_cliprange``: the clipped value loss of 'MSE' models (PE)."""
     if output_activation is not None:
         raise NotImplementedError("output activations are unused by every shipped config")
     if lr_decay is not None:
         raise NotImplementedError("learning-rate decay is unused by every shipped config")
-    if clip_loss:
-        raise NotImplementedError("clipped value losses (vf_clipping) are off in every shipped config")
     return PE(in_dim, out_dim, name=name, hidden_dims=hidden_dims, num_networks=num_networks,
               num_elites=num_elites, loss=loss, activation=activation, use_scaler_in=use_scaler_in,
               use_scaler_out=use_scaler_out, device=device, lr=lr, decay=decay, max_logvar=max_logvar,
-              min_logvar=min_logvar)
+              min_logvar=min_logvar, clip_loss=clip_loss, kl_cliprange=kl_cliprange)

@@ -597,6 +597,35 @@ int cmbpo_trainer_epoch(cmbpo_trainer_t *t, const float *d_inputs, int in_dim,
 int cmbpo_trainer_losses(cmbpo_trainer_t *t, const float *d_inputs, int in_dim,
                          const float *d_targets, int target_dim, const int32_t *d_idx,
                          int idx_stride, int n_rows, float *d_losses, void *stream);
+/* Optional terms of the deterministic ('MSE') loss, _nll_loss(inc_var_loss=False, weights=, oldpred_v=), pe.py:866-868,
+ * 881-905,917.  Both arrays are addressed through the same row indices as inputs and targets.
+ *   d_weights   [N] float32, non-negative, or NULL: loss_e = mean_b w[r] mean_d 0.5 (m - t')^2 (the mean divides by the batch,
+ *               not by the sum of the weights), in the train loss and in `self.loss`;
+ *   d_old_pred  [N][target_dim] float32 or NULL: the clipped prediction m_c = old' + clip(m - old', -c, c) replaces m in the
+ *               TRAIN loss, c = sqrt(2) sqrt(kl_cliprange old_var), old_var = mean over every member, row and output of the
+ *               step of 0.5 (old' - t')^2.  old' is d_old_pred through the output scaler, like the targets t' (the reference
+ *               subtracts scaled targets from unscaled predictions, pe.py:879,890-893; with the scaler off the two agree).
+ *               `self.loss` is never clipped: cmbpo_trainer_losses_ex ignores d_old_pred and kl_cliprange;
+ *   kl_cliprange  finite, >= 0; read when d_old_pred is set.
+ * A NULL block, or one that sets neither array, is the plain entry, bit for bit.  Refused (CMBPO_EINVAL before any device
+ * work): a probabilistic head (the 'MSPE' loss takes neither term, clipping an 'NLL' head needs old_pred_var), a negative or
+ * non-finite kl_cliprange. */
+typedef struct cmbpo_train_extras {
+  const float *d_weights;
+  const float *d_old_pred;
+  float kl_cliprange;
+} cmbpo_train_extras_t;
+int cmbpo_trainer_step_ex(cmbpo_trainer_t *t, const float *d_inputs, int in_dim,
+                          const float *d_targets, int target_dim, const int32_t *d_idx,
+                          int idx_stride, int batch, const cmbpo_train_extras_t *extras, void *stream);
+int cmbpo_trainer_epoch_ex(cmbpo_trainer_t *t, const float *d_inputs, int in_dim,
+                           const float *d_targets, int target_dim, const int32_t *d_idx,
+                           int idx_stride, int n_rows, int batch, const cmbpo_train_extras_t *extras,
+                           void *stream);
+int cmbpo_trainer_losses_ex(cmbpo_trainer_t *t, const float *d_inputs, int in_dim,
+                            const float *d_targets, int target_dim, const int32_t *d_idx,
+                            int idx_stride, int n_rows, float *d_losses,
+                            const cmbpo_train_extras_t *extras, void *stream);
 long cmbpo_trainer_steps_done(const cmbpo_trainer_t *t);
 /* Which kernels a training step of this trainer runs: bit 0 the f16 backward chain, bit 1 the f16 training forward
  * (0: the fp32 kernels; -1: NULL handle).  Fixed at creation by the network's shapes. */
