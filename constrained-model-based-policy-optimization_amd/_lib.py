@@ -128,6 +128,17 @@ SIGNATURES.update({
 })
 
 
+class IvGaeStruct(C.Structure):
+    """ctypes image of ``cmbpo_iv_gae_t``: the arrays of the inverse-variance-weighted GAE that travel beside the rollout struct."""
+    _fields_ = [(n, C.c_void_p) for n in ("cumvar_buf", "lam_vec", "lam_pow", "clam_vec", "clam_pow")] + [("eps", C.c_double)]
+
+
+SIGNATURES.update({
+    "cmbpo_rollout_iv_attach": (_i, [_rp, C.POINTER(IvGaeStruct)]),
+    "cmbpo_rollout_iv_detach": (_i, [_rp]),
+})
+
+
 
 class PiBatchStruct(C.Structure):
     """ctypes image of ``cmbpo_pi_batch_t``."""

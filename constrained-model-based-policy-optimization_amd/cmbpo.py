@@ -19,6 +19,10 @@ task without such a rule carries a cost at all.
 instead of placing them at its mean (``ModelSampler(stochastic=True)``; the reference has the hook in
 ``models/fake_env.py:103-108`` but never switches it on).  The uncertainty calibration stays deterministic.
 
+``m_iv_gae=True`` weights the k-step returns of every imagined branch by the inverse of the epistemic variance accumulated
+on the way to them (``ModelBuffer(iv_gae=True, iv_eps=m_iv_eps)``: the weighted branch of the reference's
+``discount_cumsum``, which its model buffer prepares for but never calls).  Real samples are not affected.
+
 ``static_fns`` takes a ``statics.TaskRules``: user-defined termination / cost rules for the imagined rollouts, with
 precedence over ``task`` (which may itself be a name given to ``statics.register_task``).
 """
@@ -73,7 +77,8 @@ class CMBPO:
                  initial_real_samples_per_epoch=5000, min_real_samples_per_epoch=500, batch_size_policy=25000,
                  n_epochs=int(10e7), n_initial_exploration_steps=0, initial_exploration_policy=None, epoch_length=1000,
                  model_train_kwargs=None, initial_model_train_kwargs=None, shuffle_on_device=True, device=None,
-                 session=None, start_state_sampling='host', m_stochastic=False, **_unused):
+                 session=None, start_state_sampling='host', m_stochastic=False, m_iv_gae=False, m_iv_eps=1e-8,
+                 **_unused):
         # RLAlgorithm.__init__ (algorithms/rl_algorithm.py:22-74)
         self.sampler = sampler if sampler is not None else CpoSampler(max_path_length=getattr(policy, "max_path_length", 1000))
         self._n_epochs, self._epoch_length = n_epochs, epoch_length
@@ -133,7 +138,8 @@ class CMBPO:
                                     predicts_rew=True, predicts_cost=self._m_learn_cost)
             self.rollout_mode = rollout_mode
             self.model_buf = ModelBuffer(batch_size=self._rollout_batch_size, obs_dim=self.obs_dim, act_dim=self.act_dim,
-                                         max_path_length=maxroll, device=self.device)
+                                         max_path_length=maxroll, device=self.device, iv_gae=bool(m_iv_gae),
+                                         iv_eps=m_iv_eps)
             self.model_buf.initialize(pi_info_shapes, gamma=policy.gamma, lam=policy.lam, cost_gamma=policy.cost_gamma,
                                       cost_lam=policy.cost_lam)
             self.model_sampler = ModelSampler(max_path_length=maxroll, batch_size=self._rollout_batch_size,

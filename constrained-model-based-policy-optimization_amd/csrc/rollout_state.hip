@@ -14,6 +14,9 @@
 
 #include <math.h>
 
+#include <mutex>
+#include <unordered_map>
+
 namespace {
 
 constexpr int kScanThreads = 1024;
@@ -222,10 +225,52 @@ __global__ __launch_bounds__(kScanThreads) void decide_budget_kernel(const cmbpo
 
 // reward + cost GAE of one finished path and its termination mark (modelbuffer.py:138-182; discount_cumsum =
 // lfilter([1], [1, -g*l]) on the reversed row with a float64 state, utilities/utils.py:184-188)
-__device__ __forceinline__ void gae_finish_path(const cmbpo_rollout_t &r, int b, float lv, float lcv, bool zero_boot) {
+// iv.cumvar_buf != NULL: the weighted branch of discount_cumsum (utilities/utils.py:189-208) with the inverse-variance weights
+// w[u] = 1 / (eps + cumvar[u]) -- the same deltas, one reverse pass, every float64 operation rounded on its own:
+//   lw = w[L-1] * lam^L;  S_t = sum_{u=t}^{L-2} w[u] * lam_vec[u] (from u = L-2 downwards);  W_t = (1-lam) * S_t + lw
+//   Y_t = delta_t * W_t + gamma * Y_{t+1};  adv_t = Y_t / W_t        (lam_vec, lam^L: the host's tables -- no pow here)
+__device__ __forceinline__ void gae_finish_path(const cmbpo_rollout_t &r, const cmbpo_iv_gae_t &iv, int b, float lv, float lcv,
+                                                bool zero_boot) {
   const int L = r.len[b];
   const size_t B = (size_t)r.B;
   const float g32 = (float)r.gamma, cg32 = (float)r.cost_gamma;
+  if (iv.cumvar_buf != nullptr) {
+    if (L > 0) {
+      const double w_last = __ddiv_rn(1.0, __dadd_rn(iv.eps, iv.cumvar_buf[(size_t)(L - 1) * B + b]));
+      const double lw = __dmul_rn(w_last, iv.lam_pow[L]), clw = __dmul_rn(w_last, iv.clam_pow[L]);
+      const double oml = __dsub_rn(1.0, r.lam), coml = __dsub_rn(1.0, r.cost_lam);
+      double s = 0.0, cs = 0.0, y = 0.0, cy = 0.0;
+      float vnext = lv, cvnext = lcv;
+      for (int t = L - 1; t >= 0; --t) {
+        const size_t o = (size_t)t * B + b;
+        const float rw = r.rew_buf[o], v = r.val_buf[o], c = r.cost_buf[o], cv = r.cval_buf[o];
+        double delta;
+        if (zero_boot) {
+          delta = __dsub_rn(__dadd_rn((double)rw, __dmul_rn(r.gamma, (double)vnext)), (double)v);
+        } else {
+          delta = (double)__fsub_rn(__fadd_rn(rw, __fmul_rn(g32, vnext)), v);
+        }
+        const float cdelta = __fsub_rn(__fadd_rn(c, __fmul_rn(cg32, cvnext)), cv);
+        if (t < L - 1) {   // (the last weight is lw alone: the reference zeroes w[L-1] before the sum)
+          const double w = __ddiv_rn(1.0, __dadd_rn(iv.eps, iv.cumvar_buf[o]));
+          s = __dadd_rn(__dmul_rn(w, iv.lam_vec[t]), s);
+          cs = __dadd_rn(__dmul_rn(w, iv.clam_vec[t]), cs);
+        }
+        const double wn = __dadd_rn(__dmul_rn(oml, s), lw), cwn = __dadd_rn(__dmul_rn(coml, cs), clw);
+        y = __dadd_rn(__dmul_rn(delta, wn), __dmul_rn(r.gamma, y));
+        cy = __dadd_rn(__dmul_rn((double)cdelta, cwn), __dmul_rn(r.cost_gamma, cy));
+        const float adv = (float)__ddiv_rn(y, wn), cadv = (float)__ddiv_rn(cy, cwn);
+        r.adv_buf[o] = adv;
+        r.ret_buf[o] = __fadd_rn(adv, v);
+        r.cadv_buf[o] = cadv;
+        r.cret_buf[o] = __fadd_rn(cadv, cv);
+        vnext = v;
+        cvnext = cv;
+      }
+    }
+    r.alive[b] = 0;
+    return;
+  }
   const double gl = r.gamma * r.lam, cgl = r.cost_gamma * r.cost_lam;
   double y = 0.0, cy = 0.0;
   float vnext = lv, cvnext = lcv;
@@ -259,7 +304,7 @@ __device__ __forceinline__ void store_stats_body(const cmbpo_rollout_t &r);
 // fold_stats (the rollout step at large batches, mode 1): workgroup 0 first folds the sums store_kernel's tiles left -- the
 // store is a launch further back, so no atomics are needed, and nothing before the end of this kernel reads the accumulators
 // (a launch of its own until round 3: store_stats_kernel)
-__global__ __launch_bounds__(256) void finish_kernel(const cmbpo_rollout_t r, int mode, int fold_stats) {
+__global__ __launch_bounds__(256) void finish_kernel(const cmbpo_rollout_t r, int mode, int fold_stats, const cmbpo_iv_gae_t iv) {
   if (fold_stats && blockIdx.x == 0) store_stats_body(r);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int n = r.iscal[CMBPO_I_N_ALIVE];
@@ -295,7 +340,7 @@ __global__ __launch_bounds__(256) void finish_kernel(const cmbpo_rollout_t r, in
     lv = r.v_t[b];
     lcv = r.vc_t[b];
   }
-  gae_finish_path(r, b, lv, lcv, zero_boot);
+  gae_finish_path(r, iv, b, lv, lcv, zero_boot);
 }
 
 // ---- store: transition -> column ptr, sampler accumulators ---------------------------------------
@@ -306,7 +351,7 @@ __global__ __launch_bounds__(256) void finish_kernel(const cmbpo_rollout_t r, in
 // order: no atomics, reproducible accumulators.
 constexpr int kStoreRows = 64;
 
-__global__ __launch_bounds__(256) void store_kernel(const cmbpo_rollout_t r) {
+__global__ __launch_bounds__(256) void store_kernel(const cmbpo_rollout_t r, const cmbpo_iv_gae_t iv) {
   __shared__ int s_slot[kStoreRows];   // branch slot of each row of the tile, -1: not stored
   const int n = r.iscal[CMBPO_I_N_ALIVE];
   const int tid = threadIdx.x;
@@ -336,7 +381,9 @@ __global__ __launch_bounds__(256) void store_kernel(const cmbpo_rollout_t r) {
       const double pr = r.path_ret[b] + (double)rw;
       r.path_ret[b] = pr;
       r.path_cost[b] += (double)c;
-      r.path_dyn_var[b] += (double)epv;
+      const double pv = r.path_dyn_var[b] + (double)epv;
+      r.path_dyn_var[b] = pv;
+      if (iv.cumvar_buf != nullptr) iv.cumvar_buf[col] = pv;   // iv-weighted GAE: the variance accumulated up to this column
       r.dkl_acc[b] += (double)dk;
       a_cnt = 1.0; a_cost = c; a_rew = rw; a_v = v; a_vc = vc;
       a_epv = (double)epv * D;
@@ -421,7 +468,7 @@ constexpr int kBookMax = 1024;
 
 // spec (cmbpo_rollout_run's look-ahead): the step was enqueued before the host saw the previous step's counters -- it is void
 // when that step raised the halt word (book_post_kernel)
-__global__ __launch_bounds__(kScanThreads) void book_pre_kernel(const cmbpo_rollout_t r, int spec) {
+__global__ __launch_bounds__(kScanThreads) void book_pre_kernel(const cmbpo_rollout_t r, int spec, const cmbpo_iv_gae_t iv) {
   __shared__ int sm_i[17];
   __shared__ double sm_d[16];
   __shared__ double sm_m[8 * 16];
@@ -488,7 +535,7 @@ __global__ __launch_bounds__(kScanThreads) void book_pre_kernel(const cmbpo_roll
     const int b = r.alive_idx[i];
     const uint8_t code = r.fin_code[b];
     if (code) {
-      gae_finish_path(r, b, code == 2 ? 0.0f : r.v_t[b], r.vc_t[b], code == 2);
+      gae_finish_path(r, iv, b, code == 2 ? 0.0f : r.v_t[b], r.vc_t[b], code == 2);
       continue;
     }
     const size_t col = (size_t)r.ptr * B + b;
@@ -503,7 +550,9 @@ __global__ __launch_bounds__(kScanThreads) void book_pre_kernel(const cmbpo_roll
     const double pr = r.path_ret[b] + (double)rw;
     r.path_ret[b] = pr;
     r.path_cost[b] += (double)c;
-    r.path_dyn_var[b] += (double)epv;
+    const double pv = r.path_dyn_var[b] + (double)epv;
+    r.path_dyn_var[b] = pv;
+    if (iv.cumvar_buf != nullptr) iv.cumvar_buf[col] = pv;     // (as in store_kernel)
     r.dkl_acc[b] += (double)dk;
     a_cnt += 1.0; a_cost += c; a_rew += rw; a_v += v; a_vc += vc;
     a_epv += (double)epv * D;
@@ -581,7 +630,7 @@ __global__ __launch_bounds__(256) void store_vec_kernel(const cmbpo_rollout_t r,
 // (at most min_alive rows left, total_samples >= stop_total unless NaN; algorithms/cmbpo.py:356-359) are taken here, the halt
 // word travels in the mirrored block and iscal[CMBPO_I_N_EFF] (the row count the next step's forward kernels read) drops to 0.
 __global__ __launch_bounds__(kScanThreads) void book_post_kernel(const cmbpo_rollout_t r, uint32_t *host_out, uint32_t seq, int spec,
-                                                                 int min_alive, double stop_total) {
+                                                                 int min_alive, double stop_total, const cmbpo_iv_gae_t iv) {
   __shared__ int sm_i[17];
   __shared__ double sm_d[16];
   const int tid = threadIdx.x;
@@ -593,10 +642,10 @@ __global__ __launch_bounds__(kScanThreads) void book_post_kernel(const cmbpo_rol
     const int b = r.alive_idx[i];
     if (r.fin_code[b]) continue;              // finished before the store
     if (horizon) {
-      gae_finish_path(r, b, r.v_n[b], r.vc_n[b], false);
+      gae_finish_path(r, iv, b, r.v_n[b], r.vc_n[b], false);
       ++nfin;
     } else if (r.term_t[b]) {
-      gae_finish_path(r, b, 0.0f, r.vc_n[b], true);   // float64 zeros bootstrap; the cost value still bootstraps (:364)
+      gae_finish_path(r, iv, b, 0.0f, r.vc_n[b], true);   // float64 zeros bootstrap; the cost value still bootstraps (:364)
       ++nfin;
     }
   }
@@ -1143,7 +1192,42 @@ int check_rollout(const cmbpo_rollout_t *r, const char *who) {
   return CMBPO_OK;
 }
 
+// ---- inverse-variance-weighted GAE: the state beside the struct ----------------------------------------------------------
+// cmbpo_rollout_t is frozen, so the feature's arrays travel in a table keyed by r->iscal (unique per buffer), like the rule
+// tables of task_rules.hip.  Every host entry point below that launches a store or a finish kernel looks the key up and hands
+// the entry to the kernel by value; no entry = cumvar_buf NULL = the un-weighted recurrence.
+std::mutex g_iv_mu;
+std::unordered_map<const void *, cmbpo_iv_gae_t> g_iv;
+
+cmbpo_iv_gae_t iv_lookup(const cmbpo_rollout_t *r) {
+  cmbpo_iv_gae_t iv = {};
+  std::lock_guard<std::mutex> lock(g_iv_mu);
+  if (!g_iv.empty()) {
+    const auto it = g_iv.find(r->iscal);
+    if (it != g_iv.end()) iv = it->second;
+  }
+  return iv;
+}
+
 }  // namespace
+
+extern "C" int cmbpo_rollout_iv_attach(const cmbpo_rollout_t *r, const cmbpo_iv_gae_t *iv) {
+  CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_iv_attach: NULL rollout struct / iscal");
+  CMBPO_REQUIRE(iv != nullptr, "cmbpo_rollout_iv_attach: NULL cmbpo_iv_gae_t");
+  CMBPO_REQUIRE(iv->cumvar_buf != nullptr, "cmbpo_rollout_iv_attach: NULL cumvar_buf (cmbpo_rollout_iv_detach switches the feature off)");
+  CMBPO_REQUIRE(iv->lam_vec && iv->lam_pow && iv->clam_vec && iv->clam_pow, "cmbpo_rollout_iv_attach: NULL lambda table");
+  CMBPO_REQUIRE(isfinite(iv->eps) && iv->eps > 0.0, "cmbpo_rollout_iv_attach: eps %g is not a positive finite number", iv->eps);
+  std::lock_guard<std::mutex> lock(g_iv_mu);
+  g_iv[r->iscal] = *iv;
+  return CMBPO_OK;
+}
+
+extern "C" int cmbpo_rollout_iv_detach(const cmbpo_rollout_t *r) {
+  CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_iv_detach: NULL rollout struct / iscal");
+  std::lock_guard<std::mutex> lock(g_iv_mu);
+  g_iv.erase(r->iscal);
+  return CMBPO_OK;
+}
 
 extern "C" int cmbpo_rollout_reset(const cmbpo_rollout_t *r, void *stream) {
   if (int rc = check_rollout(r, "cmbpo_rollout_reset")) return rc;
@@ -1183,7 +1267,7 @@ extern "C" int cmbpo_rollout_finish(const cmbpo_rollout_t *r, int mode, void *st
                 "cmbpo_rollout_finish: NULL buffer");
   if (mode == 1) CMBPO_REQUIRE(r->v_n && r->vc_n && r->term_t, "cmbpo_rollout_finish: POST needs v_n, vc_n, term_t");
   else CMBPO_REQUIRE(r->v_t && r->vc_t, "cmbpo_rollout_finish: needs v_t, vc_t");
-  hipLaunchKernelGGL(finish_kernel, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, mode, 0);
+  hipLaunchKernelGGL(finish_kernel, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, mode, 0, iv_lookup(r));
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1198,7 +1282,7 @@ extern "C" int cmbpo_rollout_store(const cmbpo_rollout_t *r, void *stream) {
                     r->cval_buf && r->logp_buf,
                 "cmbpo_rollout_store: NULL buffer");
   CMBPO_REQUIRE(r->store_part != nullptr, "cmbpo_rollout_store: NULL store_part scratch");
-  hipLaunchKernelGGL(store_kernel, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r);
+  hipLaunchKernelGGL(store_kernel, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, iv_lookup(r));
   hipLaunchKernelGGL(store_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *r);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
@@ -1212,7 +1296,7 @@ int cmbpo_internal_store_nostats(const cmbpo_rollout_t *r, void *stream) {
                     r->epv_t && r->obs_buf && r->act_buf && r->mu_buf && r->ls_buf && r->rew_buf && r->val_buf && r->cost_buf &&
                     r->cval_buf && r->logp_buf && r->store_part,
                 "cmbpo_rollout_store: NULL array");
-  hipLaunchKernelGGL(store_kernel, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r);
+  hipLaunchKernelGGL(store_kernel, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, iv_lookup(r));
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1221,7 +1305,7 @@ int cmbpo_internal_finish_post_fold(const cmbpo_rollout_t *r, void *stream) {
   CMBPO_REQUIRE(r->v_n && r->vc_n && r->term_t && r->rew_buf && r->val_buf && r->cost_buf && r->cval_buf && r->adv_buf && r->ret_buf &&
                     r->cadv_buf && r->cret_buf && r->store_part,
                 "cmbpo_rollout_finish (POST): NULL array");
-  hipLaunchKernelGGL(finish_kernel, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, 1, 1);
+  hipLaunchKernelGGL(finish_kernel, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, 1, 1, iv_lookup(r));
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1240,7 +1324,7 @@ extern "C" int cmbpo_rollout_book_pre(const cmbpo_rollout_t *r, int n_alive, voi
                     r->logp_buf && r->adv_buf && r->ret_buf && r->cadv_buf && r->cret_buf,
                 "cmbpo_rollout_book_pre: NULL buffer");
   if (n_alive == 0) return CMBPO_OK;
-  hipLaunchKernelGGL(book_pre_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, 0);
+  hipLaunchKernelGGL(book_pre_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, 0, iv_lookup(r));
   hipLaunchKernelGGL(store_vec_kernel, dim3(cmbpo_ceil_div(n_alive, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, 0);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
@@ -1256,7 +1340,7 @@ int cmbpo_internal_book_pre(const cmbpo_rollout_t *r, int n_alive, int spec, int
                     r->cost_t && r->epv_t && r->obs_buf && r->act_buf && r->mu_buf && r->ls_buf && r->rew_buf && r->val_buf &&
                     r->cost_buf && r->cval_buf && r->logp_buf && r->adv_buf && r->ret_buf && r->cadv_buf && r->cret_buf,
                 "cmbpo_rollout_book_pre: NULL array");
-  hipLaunchKernelGGL(book_pre_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, spec);
+  hipLaunchKernelGGL(book_pre_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, spec, iv_lookup(r));
   if (with_vec)
     hipLaunchKernelGGL(store_vec_kernel, dim3(cmbpo_ceil_div(n_alive, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, spec);
   CMBPO_HIP_CHECK(hipGetLastError());
@@ -1281,7 +1365,8 @@ extern "C" int cmbpo_rollout_book_post(const cmbpo_rollout_t *r, int n_alive, vo
   CMBPO_REQUIRE(r->v_n && r->vc_n && r->term_t && r->rew_buf && r->val_buf && r->cost_buf && r->cval_buf && r->adv_buf &&
                     r->ret_buf && r->cadv_buf && r->cret_buf,
                 "cmbpo_rollout_book_post: NULL array");
-  hipLaunchKernelGGL(book_post_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, (uint32_t *)nullptr, 0u, 0, 0, 0.0);
+  hipLaunchKernelGGL(book_post_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, (uint32_t *)nullptr, 0u, 0, 0, 0.0,
+                     iv_lookup(r));
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1320,7 +1405,7 @@ int cmbpo_internal_book_post_mirror(const cmbpo_rollout_t *r, int n_alive, uint3
   CMBPO_REQUIRE(reinterpret_cast<const char *>(r->dscal) == reinterpret_cast<const char *>(r->iscal) + 128,
                 "cmbpo_rollout_book_post: iscal[32] and dscal[32] must be one 384-byte block");
   hipLaunchKernelGGL(book_post_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, d_host_out, seq, spec, min_alive,
-                     stop_total);
+                     stop_total, iv_lookup(r));
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }

@@ -8,13 +8,22 @@ Layout differences (performance only, invisible through the API):
   * buffers are time-major ``[T, B, ...]`` and allocated once; ``reset()`` zeroes pointers instead of
     re-allocating 17 arrays (``modelbuffer.py:53-98``, SURVEY appendix A item 17);
   * ``next_obs`` / ``dyn_error`` / ``term`` / ``roll_lengths`` buffers are never read by ``get()`` in the
-    reference (``modelbuffer.py:212-218``) and are not kept;
+    reference (``modelbuffer.py:212-218``) and are not kept -- except with ``iv_gae=True``, which keeps the running float64
+    sum of ``dyn_error`` per stored entry (``cumvar_buf``): the weights of the inverse-variance-weighted GAE;
   * ``populated_mask[b, t]`` is represented as ``t < len[b]`` (alive branches share ``ptr``).
 
 ``get()`` returns the reference's 12-array list ``[obs, act, adv, cadv, ret, cret, logp, val, cval, cost,
 log_std, mu]`` (``pi_info`` sorted by key) in branch-major, time-minor order.
+
+``iv_gae=True`` (or ``set_iv_gae(True)``) switches ``finish_path_multiple`` -- and every finish of the device-resident
+sampler -- to the weighted branch of the reference's ``discount_cumsum(x, discount, lam, weights=...)``
+(``utilities/utils.py:189-208``) with ``w[u] = 1 / (iv_eps + sum_{s<=u} dyn_error_s)``: a k-step return counts by the inverse
+of the epistemic variance accumulated on the way to it.  The reference's buffer keeps ``dyn_error_buf`` for this and comments
+both GAE lines accordingly (``modelbuffer.py:167,176``) but calls the un-weighted branch; off (the default) is that behaviour.
+Constant weights do not reduce to plain GAE: the reference folds the weight beyond the last step into the last one.
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -25,6 +34,30 @@ from ._lib import RolloutStruct
 EPS = 1e-8  # utilities/utils.py:19
 
 
+def iv_tables(lam, T):
+    """The two float64 lambda tables of the weighted GAE: lam_vec[T] by lfilter's recurrence (lam_vec[0] = 1, lam_vec[u] =
+    lam * lam_vec[u-1], utilities/utils.py:195-197) and lam ** L for L = 0..T by Python's pow (:192) -- built on the host so
+    that the device has no pow of its own to disagree with."""
+    lam = float(lam)
+    vec = np.empty(int(T), np.float64)
+    v = 1.0
+    for u in range(int(T)):
+        vec[u] = v
+        v = lam * v
+    return vec, np.array([lam ** L for L in range(int(T) + 1)], np.float64)
+
+
+def _iv_release(key):
+    """Finaliser of a buffer: no entry of the library's table may outlive the arrays it points to."""
+    try:
+        if key[0]:
+            rs = RolloutStruct()
+            rs.iscal = key[0]
+            _lib.lib().cmbpo_rollout_iv_detach(C.byref(rs))
+    except Exception:      # interpreter shutdown
+        pass
+
+
 def _np_or_t(x, device, dtype=torch.float32):
     if isinstance(x, torch.Tensor):
         return x.to(device=device, dtype=dtype)
@@ -33,7 +66,7 @@ def _np_or_t(x, device, dtype=torch.float32):
 
 class ModelBuffer:
     def __init__(self, batch_size, obs_dim, act_dim, max_path_length, device=None, comm=None,
-                 *args, **kwargs):
+                 *args, iv_gae=False, iv_eps=1e-8, **kwargs):
         self.max_path_length = int(max_path_length)
         self.batch_size = int(batch_size)
         self.capacity = int(batch_size)
@@ -44,12 +77,18 @@ class ModelBuffer:
         self.comm = comm                      # optional dist.Comm for sharded statistics
         self.pi_info_shapes = None
         self.gamma, self.lam, self.cost_gamma, self.cost_lam = 0.99, 0.95, 0.99, 0.95
+        self.iv_gae, self.iv_eps = bool(iv_gae), self._check_iv_eps(iv_eps)
+        self.rs = None
+        self._iv_key = [0]                    # iscal of the arrays the library's table may hold an entry for
+        weakref.finalize(self, _iv_release, self._iv_key)
         self._alloc(self.capacity)
         self.reset()
 
     # ------------------------------------------------------------------------------------------
     def _alloc(self, B):
         T, D, A, dev = self.max_path_length, self.obs_dim, self.act_dim, self.device
+        if self.rs is not None:               # the table's key is the old iscal
+            _lib.check(_lib.lib().cmbpo_rollout_iv_detach(C.byref(self.rs)), "cmbpo_rollout_iv_detach")
         f = dict(dtype=torch.float32, device=dev)
         d = dict(dtype=torch.float64, device=dev)
         t = {}
@@ -87,12 +126,54 @@ class ModelBuffer:
         self.rs.dkl_lim = float("inf")
         self.rs.max_path_length = T
         self._bind_all()
+        self._iv_key[0] = self.t["iscal"].data_ptr()
+        self._iv_sync()
 
     def _bind_all(self):
         for name, _ in RolloutStruct._fields_:
             if name in self.t:
                 setattr(self.rs, name, self.t[name].data_ptr())
         self.rs.use_host_budget = 0
+
+    # -- inverse-variance-weighted GAE ----------------------------------------------------------
+    @staticmethod
+    def _check_iv_eps(iv_eps):
+        iv_eps = float(iv_eps)
+        if not (iv_eps > 0.0 and np.isfinite(iv_eps)):
+            raise ValueError(f"iv_eps must be a positive finite number, got {iv_eps}")
+        return iv_eps
+
+    def set_iv_gae(self, on, iv_eps=1e-8):
+        """Switch the inverse-variance-weighted GAE on or off; legal whenever nothing is stored."""
+        iv_eps = self._check_iv_eps(iv_eps)
+        if self.ptr != 0 or self._size != 0:
+            raise RuntimeError("set_iv_gae: the buffer holds samples (call it after get() / reset())")
+        self.iv_gae, self.iv_eps = bool(on), iv_eps
+        self._iv_sync()
+
+    def _iv_sync(self):
+        """Attach (on: for the current arrays, lambdas and iv_eps) or detach (off: and free) the state beside the struct."""
+        lib, t = _lib.lib(), self.t
+        if not self.iv_gae:
+            _lib.check(lib.cmbpo_rollout_iv_detach(C.byref(self.rs)), "cmbpo_rollout_iv_detach")
+            t.pop("cumvar_buf", None)
+            t.pop("iv_tables", None)
+            return
+        T, B, dev = self.max_path_length, self.capacity, self.device
+        if "cumvar_buf" not in t:
+            t["cumvar_buf"] = torch.zeros((T, B), dtype=torch.float64, device=dev)
+        tabs = torch.from_numpy(np.concatenate(iv_tables(self.lam, T) + iv_tables(self.cost_lam, T)))
+        if "iv_tables" in t:
+            t["iv_tables"].copy_(tabs)        # same addresses: ordered on the stream behind the kernels that read the old values
+        else:
+            t["iv_tables"] = tabs.to(dev)
+        base = t["iv_tables"].data_ptr()
+        iv = _lib.IvGaeStruct()
+        iv.cumvar_buf = t["cumvar_buf"].data_ptr()
+        iv.lam_vec, iv.lam_pow = base, base + 8 * T
+        iv.clam_vec, iv.clam_pow = base + 8 * (2 * T + 1), base + 8 * (3 * T + 1)
+        iv.eps = self.iv_eps
+        _lib.check(lib.cmbpo_rollout_iv_attach(C.byref(self.rs), C.byref(iv)), "cmbpo_rollout_iv_attach")
 
     def swap(self, a, b):
         """Exchange two same-shaped state arrays (cur_obs <-> next_obs, v_t <-> v_n, ...)."""
@@ -115,6 +196,8 @@ class ModelBuffer:
         self.gamma, self.lam, self.cost_gamma, self.cost_lam = gamma, lam, cost_gamma, cost_lam
         self.rs.gamma, self.rs.lam = float(gamma), float(lam)
         self.rs.cost_gamma, self.rs.cost_lam = float(cost_gamma), float(cost_lam)
+        if self.iv_gae:
+            self._iv_sync()                   # the tables follow the lambdas
 
     def reset(self, batch_size=None):
         """modelbuffer.py:53-98 (pointers only; the buffers are reused unless the batch size changes)."""

@@ -394,6 +394,25 @@ int cmbpo_rollout_run(cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy, cmbp
                       double stop_total, int min_alive, void *h_scalars, int *steps_done, int *n_alive_out,
                       int *list_swaps, void *stream);
 
+/* Inverse-variance-weighted GAE for imagined rollouts: the weighted branch of the reference's
+ * discount_cumsum(x, discount, lam, weights=..., axis=-1) (utilities/utils.py:189-208) with the weights
+ *   w[u] = 1 / (eps + sum_{s<=u} (double)epv_s)       (the branch's accumulated epistemic variance, path_dyn_var)
+ * applied to the reward and the cost deltas of every finished branch (DESIGN 3k has the recurrence).  cmbpo_rollout_t
+ * stays as it is; the feature's arrays travel beside it: attach them to a buffer (the key is r->iscal) and every call
+ * above that stores (cmbpo_rollout_store, _book_pre, _step, _run) writes path_dyn_var into cumvar_buf[ptr * B + b] and
+ * every call that finishes paths (cmbpo_rollout_finish, _book_pre, _book_post, _step, _run) takes the weighted branch.
+ * Device pointers, owned by the caller, valid until the detach; attach again after any of them or r->iscal moved.
+ * lam_vec[0] = 1, lam_vec[u] = lam * lam_vec[u - 1]; lam_pow[L] = lam ** L (the host's pow); clam_*: the same for cost_lam.
+ * Constant weights do not give plain GAE: the reference folds the weight beyond the last step into the last one. */
+typedef struct cmbpo_iv_gae {
+  double *cumvar_buf;            /* [T,B] */
+  const double *lam_vec, *lam_pow, *clam_vec, *clam_pow;   /* [T], [T+1], [T], [T+1] */
+  double eps;
+} cmbpo_iv_gae_t;
+int cmbpo_rollout_iv_attach(const cmbpo_rollout_t *r, const cmbpo_iv_gae_t *iv);
+/* Back to the un-weighted recurrence (no error when nothing was attached). */
+int cmbpo_rollout_iv_detach(const cmbpo_rollout_t *r);
+
 /* ModelBuffer.get (modelbuffer.py:184-226): d_offsets[B+1] = exclusive scan of
  * len; d_stats[8] = {n, adv_mean, adv_std, cadv_mean, ret_mean, cret_mean}
  * (two-pass mean / std of utilities/mpi_tools.py:71-92).  With d_gstats
