@@ -56,6 +56,8 @@ SIGNATURES = {
                                 _p, _p, _p, _p, _p, _p, _p, _p]),
     "cmbpo_fakeenv_post_noise": (_i, [_i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i,
                                       _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "cmbpo_fakeenv_post_disagreement": (_i, [_i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i,
+                                             _p, _p, _p, _p, _p, _p, _p, _p, C.c_float, C.c_float, _p, _p, _p]),
 }
 
 
@@ -105,6 +107,7 @@ class RolloutStruct(C.Structure):
 I_N_ALIVE, I_N_UNC, I_N_FIN_PRE, I_N_STORED, I_N_ALIVE_OUT, I_SIZE, I_N_FIN_POST = 0, 1, 2, 3, 4, 5, 6
 (D_TOTAL_SAMPLES, D_TOTAL_COST, D_TOTAL_REW, D_TOTAL_VS, D_TOTAL_CVS, D_TOTAL_DKL, D_TOTAL_DYN_EP_VAR,
  D_MAX_DKL, D_MAX_PATH_RETURN, D_DKL_SUM_T, D_STEP_MAX_DKL, D_SUM_PATH_RET, D_SUM_PATH_COST) = range(13)
+D_TOTAL_REW_VAR, D_TOTAL_COST_VAR = 13, 14      # ensemble disagreement on reward / cost, summed over the stored rows
 
 _rp = C.POINTER(RolloutStruct)
 SIGNATURES.update({
@@ -136,6 +139,19 @@ class IvGaeStruct(C.Structure):
 SIGNATURES.update({
     "cmbpo_rollout_iv_attach": (_i, [_rp, C.POINTER(IvGaeStruct)]),
     "cmbpo_rollout_iv_detach": (_i, [_rp]),
+})
+
+
+class DisagreementStruct(C.Structure):
+    """ctypes image of ``cmbpo_disagreement_t``: the pessimism coefficients and the arrays of the ensemble disagreement on
+    reward and cost that travel beside the rollout struct."""
+    _fields_ = [("kappa_rew", C.c_float), ("kappa_cost", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("rew_var_t", "cost_var_t", "path_rew_var", "path_cost_var", "part")]
+
+
+SIGNATURES.update({
+    "cmbpo_rollout_disagreement_attach": (_i, [_rp, C.POINTER(DisagreementStruct)]),
+    "cmbpo_rollout_disagreement_detach": (_i, [_rp]),
 })
 
 

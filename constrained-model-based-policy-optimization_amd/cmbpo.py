@@ -23,6 +23,12 @@ instead of placing them at its mean (``ModelSampler(stochastic=True)``; the refe
 on the way to them (``ModelBuffer(iv_gae=True, iv_eps=m_iv_eps)``: the weighted branch of the reference's
 ``discount_cumsum``, which its model buffer prepares for but never calls).  Real samples are not affected.
 
+``m_disagreement=True`` measures the ensemble's disagreement on the reward and the learned-cost column along the imagined
+rollouts (``msampler/rew_var_perstep``, ``msampler/cost_var_perstep``); ``m_rew_pessimism`` / ``m_cost_pessimism`` (kappa >= 0,
+> 0 implies the measurement) make the imagined reward ``r - kappa_r * sigma_r`` and the imagined learned cost
+``c + kappa_c * sigma_c``: a constraint is no longer satisfied on the say-so of one member (``FakeEnv(disagreement=...)``).
+``m_cost_pessimism > 0`` needs ``m_learn_cost=True``.  Real samples and the rollout lengths are not affected.
+
 ``static_fns`` takes a ``statics.TaskRules``: user-defined termination / cost rules for the imagined rollouts, with
 precedence over ``task`` (which may itself be a name given to ``statics.register_task``).
 """
@@ -78,6 +84,7 @@ class CMBPO:
                  n_epochs=int(10e7), n_initial_exploration_steps=0, initial_exploration_policy=None, epoch_length=1000,
                  model_train_kwargs=None, initial_model_train_kwargs=None, shuffle_on_device=True, device=None,
                  session=None, start_state_sampling='host', m_stochastic=False, m_iv_gae=False, m_iv_eps=1e-8,
+                 m_disagreement=False, m_rew_pessimism=0.0, m_cost_pessimism=0.0,
                  **_unused):
         # RLAlgorithm.__init__ (algorithms/rl_algorithm.py:22-74)
         self.sampler = sampler if sampler is not None else CpoSampler(max_path_length=getattr(policy, "max_path_length", 1000))
@@ -108,6 +115,8 @@ class CMBPO:
                                 cost_lam=policy.cost_lam)
         self._use_model = use_model
         self._m_learn_cost = bool(m_learn_cost)
+        if float(m_cost_pessimism) > 0.0 and not self._m_learn_cost:
+            raise ValueError("m_cost_pessimism > 0 needs m_learn_cost=True: only a learned cost head has an ensemble spread")
         self._m_train_freq = m_train_freq
         self._rollout_batch_size = int(rollout_batch_size)
         self._rollout_schedule = list(rollout_schedule)
@@ -135,7 +144,9 @@ class CMBPO:
                                    device=self.device)
             rules_task = self._task if static_fns is None else static_fns      # static_fns takes precedence over the task name
             self.fake_env = FakeEnv(true_environment=env, task=rules_task, model=self._model, predicts_delta=True,
-                                    predicts_rew=True, predicts_cost=self._m_learn_cost)
+                                    predicts_rew=True, predicts_cost=self._m_learn_cost,
+                                    disagreement=bool(m_disagreement), rew_pessimism=m_rew_pessimism,
+                                    cost_pessimism=m_cost_pessimism)
             self.rollout_mode = rollout_mode
             self.model_buf = ModelBuffer(batch_size=self._rollout_batch_size, obs_dim=self.obs_dim, act_dim=self.act_dim,
                                          max_path_length=maxroll, device=self.device, iv_gae=bool(m_iv_gae),

@@ -20,7 +20,8 @@ void cmbpo_set_error(const char *fmt, ...) {
 extern "C" const char *cmbpo_last_error(void) { return g_err; }
 
 // 2: cmbpo_fakeenv_post_noise, cmbpo_rollout_t.xi / xi_stride; 3: cmbpo_train_extras_t, cmbpo_trainer_{step,epoch,losses}_ex
-extern "C" int cmbpo_version(void) { return 4; }
+// (4: cmbpo_iv_gae_t;) 5: cmbpo_fakeenv_post_disagreement, cmbpo_disagreement_t, CMBPO_D_TOTAL_REW_VAR / _COST_VAR
+extern "C" int cmbpo_version(void) { return 5; }
 
 namespace {
 constexpr int kMaxDevices = 64;

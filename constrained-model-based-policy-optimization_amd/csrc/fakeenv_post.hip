@@ -50,8 +50,18 @@ struct PostArgsRulesNoise : PostArgsRules {
   const float *xi;
 };
 template <bool RULES, bool NOISE>
-using PostArgsT = std::conditional_t<NOISE, std::conditional_t<RULES, PostArgsRulesNoise, PostArgsNoise>,
-                                     std::conditional_t<RULES, PostArgsRules, PostArgs>>;
+using PostArgsBase = std::conditional_t<NOISE, std::conditional_t<RULES, PostArgsRulesNoise, PostArgsNoise>,
+                                        std::conditional_t<RULES, PostArgsRules, PostArgs>>;
+// DIS: ensemble disagreement on the reward and the learned-cost column (np.var over ALL members, like ens_ep_var on the
+// observation columns) and the pessimistic reward / cost made from it -- again fields that exist only in the argument types
+// of instances of their own: a launch without the feature runs the kernels it always ran, with the arguments it always had
+template <bool RULES, bool NOISE>
+struct PostArgsDis : PostArgsBase<RULES, NOISE> {
+  float kappa_rew, kappa_cost;    // >= 0, finite; 0: the elite member's value goes out untouched
+  float *rew_var, *cost_var;      // [.] slot indexed like rew / cost
+};
+template <bool RULES, bool NOISE, bool DIS = false>
+using PostArgsT = std::conditional_t<DIS, PostArgsDis<RULES, NOISE>, PostArgsBase<RULES, NOISE>>;
 
 // np.clip(x, lo, hi): comparisons are false for a NaN, which therefore passes through (fminf / fmaxf would drop it)
 __device__ __forceinline__ float clip_np(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
@@ -59,8 +69,8 @@ __device__ __forceinline__ float clip_np(float x, float lo, float hi) { return x
 // EC: the ensemble size at compile time (0: read it at run time) -- with a run-time size the member loops are unrolled to
 // kEMax and masked: 56 pair terms computed and selected for the 42 that exist, a third more instructions
 #define POST_WAVES 5      // waves per SIMD the register allocation aims at (swept 4 / 5 / 6 / 8: 57.7 / 51.1 / 51.3 / 77.4 us at 100 k rows)
-template <int EC, bool RULES = false, bool NOISE = false>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgsT<RULES, NOISE> p) {
+template <int EC, bool RULES = false, bool NOISE = false, bool DIS = false>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgsT<RULES, NOISE, DIS> p) {
   extern __shared__ float sm[];
   const int D = p.obs_dim;
   float *s_dkl = sm;                  // [kRows][D]
@@ -238,6 +248,21 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
     const int rw = tid >> 3, k = tid & 7;
     const int r = s_row[rw];
     const float *nx = s_next + rw * D;
+    // DIS: lane k of the row owns member k -- its reward (and learned-cost) mean and the row's elite index are requested
+    // here, ahead of the row sums that hide the round trip; one lane walking 2 E dependent loads behind everything else
+    // would add them to the end of the workgroup's life.  Rows past the end and lanes past E load nothing.
+    [[maybe_unused]] float xr = 0.0f, xc = 0.0f;
+    [[maybe_unused]] int me_k = 0;
+    if constexpr (DIS) {
+      if (r >= 0) {
+        me_k = p.elite[r];
+        if (k < E) {
+          const size_t o = k * mstride + (size_t)r * p.out_dim + D;
+          xr = p.mean[o];
+          if (p.learned_cost) xc = p.mean[o + 1];
+        }
+      }
+    }
     auto row_sum = [&](const float *a) {
       float res;
       if (D < 8) {
@@ -287,11 +312,49 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
         else rule_obj = rule_obj || holds;
       }
     }
+    // DIS: np.var over the members (axis 0) in the order of the observation columns above -- s = ((x0 + x1) + x2) + ...,
+    // m = s / E, q = sum (x_e - m)^2 in member order, var = q / E -- with the row's lane 0 reading member e from lane e.  All
+    // 64 lanes are still here; the elite's own values come from the same registers (the bits the plain entry loads).
+    [[maybe_unused]] float rew_var = 0.0f, cost_var = 0.0f, rew_me = 0.0f, cost_me = 0.0f;
+    if constexpr (DIS) {
+      const int l0 = 8 * rw;
+      auto member_var = [&](float x, float *x_me) {
+        float xe[kEMax];
+#pragma unroll
+        for (int e = 0; e < kEMax; ++e) xe[e] = __shfl(x, l0 + e, 64);
+        *x_me = __shfl(x, l0 + (me_k & 7), 64);
+        float s = 0.0f;
+#pragma unroll
+        for (int e = 0; e < kEMax; ++e)
+          if (e < E) s = __fadd_rn(s, xe[e]);
+        const float mbar = s / (float)E;
+        float sq = 0.0f;
+#pragma unroll
+        for (int e = 0; e < kEMax; ++e)
+          if (e < E) {
+            const float dlt = __fsub_rn(xe[e], mbar);
+            sq = __fadd_rn(sq, __fmul_rn(dlt, dlt));
+          }
+        return sq / (float)E;
+      };
+      rew_var = member_var(xr, &rew_me);
+      if (p.learned_cost) cost_var = member_var(xc, &cost_me);     // (uniform over the launch; a static cost rule has no spread: +0)
+    }
     if (r < 0 || k != 0) return;
     p.dkl_path[r] = sd / (float)D;      // fake_env.py:113
     p.ep_var_mean[r] = sv / (float)D;   // model_sampler.py:322
-    const int me = p.elite[r];
-    p.rew[r] = p.mean[me * mstride + (size_t)r * p.out_dim + D];    // fake_env.py:148-151
+    int me;
+    if constexpr (DIS) me = me_k;
+    else me = p.elite[r];
+    if constexpr (DIS) {
+      // r - kappa * sigma only where kappa > 0 (uniform over the launch): with kappa == 0 the elite's value goes out bit for
+      // bit whatever the other members hold, a NaN included.  sqrtf: correctly rounded, as in the NOISE path.
+      p.rew_var[r] = rew_var;
+      p.cost_var[r] = cost_var;
+      p.rew[r] = p.kappa_rew > 0.0f ? __fsub_rn(rew_me, __fmul_rn(p.kappa_rew, sqrtf(rew_var))) : rew_me;
+    } else {
+      p.rew[r] = p.mean[me * mstride + (size_t)r * p.out_dim + D];    // fake_env.py:148-151
+    }
     uint8_t done = 0;
     float cost = 0.0f;
     if constexpr (RULES) {
@@ -316,25 +379,42 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
     // learned cost head (fake_env.py:139-143, predicts_cost=True): the elite member's mean of the last column, stored as it is;
     // the termination rule above still applies (TERMS_BY_TASK does not depend on predicts_cost).  A branch uniform over the
     // launch, taken by one lane per row: as a template parameter it would double the instances for one load.
-    if (p.learned_cost) cost = p.mean[me * mstride + (size_t)r * p.out_dim + D + 1];
+    if constexpr (DIS) {
+      if (p.learned_cost) cost = p.kappa_cost > 0.0f ? __fadd_rn(cost_me, __fmul_rn(p.kappa_cost, sqrtf(cost_var))) : cost_me;
+    } else {
+      if (p.learned_cost) cost = p.mean[me * mstride + (size_t)r * p.out_dim + D + 1];
+    }
     p.term[r] = done;
     p.cost[r] = cost;
   }
 }
 
-// one launch of the instance for (ensemble size, RULES, NOISE)
-template <bool RULES, bool NOISE>
-void launch_post(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsT<RULES, NOISE> &a) {
-  if (ensemble == 7) hipLaunchKernelGGL((fakeenv_post_kernel<7, RULES, NOISE>), grid, dim3(kThreads), lds, stream, a);   // the shipped configs
-  else if (ensemble == 5) hipLaunchKernelGGL((fakeenv_post_kernel<5, RULES, NOISE>), grid, dim3(kThreads), lds, stream, a);
-  else hipLaunchKernelGGL((fakeenv_post_kernel<0, RULES, NOISE>), grid, dim3(kThreads), lds, stream, a);
+// one launch of the instance for (ensemble size, RULES, NOISE, DIS)
+template <bool RULES, bool NOISE, bool DIS = false>
+void launch_post(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsT<RULES, NOISE, DIS> &a) {
+  if (ensemble == 7) hipLaunchKernelGGL((fakeenv_post_kernel<7, RULES, NOISE, DIS>), grid, dim3(kThreads), lds, stream, a);   // the shipped configs
+  else if (ensemble == 5) hipLaunchKernelGGL((fakeenv_post_kernel<5, RULES, NOISE, DIS>), grid, dim3(kThreads), lds, stream, a);
+  else hipLaunchKernelGGL((fakeenv_post_kernel<0, RULES, NOISE, DIS>), grid, dim3(kThreads), lds, stream, a);
 }
 
-// both entry points; `who` prefixes the messages, d_xi == NULL: the deterministic instances
+// what cmbpo_fakeenv_post_disagreement adds to the arguments (NULL: the instances without the feature)
+struct DisExtra {
+  float kappa_rew, kappa_cost;
+  float *rew_var, *cost_var;
+};
+template <bool RULES, bool NOISE>
+void launch_post_dis(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsBase<RULES, NOISE> &a, const DisExtra &dis) {
+  PostArgsDis<RULES, NOISE> ad{};
+  static_cast<PostArgsBase<RULES, NOISE> &>(ad) = a;
+  ad.kappa_rew = dis.kappa_rew; ad.kappa_cost = dis.kappa_cost; ad.rew_var = dis.rew_var; ad.cost_var = dis.cost_var;
+  launch_post<RULES, NOISE, true>(ensemble, grid, lds, stream, ad);
+}
+
+// all three entry points; `who` prefixes the messages, d_xi == NULL: the deterministic instances
 int post_impl(const char *who, int task, int ensemble, int obs_dim, int act_dim, const float *d_mean, const float *d_var, int ld_rows,
               const float *d_obs, const float *d_act, const int32_t *d_elite, const int32_t *d_row_idx, const int32_t *d_n_rows,
               int n_rows, float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost, float *d_dkl_path, float *d_ep_var_mean,
-              float *d_ep_var, const float *d_xi, void *stream) {
+              float *d_ep_var, const float *d_xi, void *stream, const DisExtra *dis = nullptr) {
   const int learned_cost = (task & CMBPO_TASK_LEARNED_COST) ? 1 : 0;     // every other bit outside the rule id is an error
   const int task_arg = task;
   task &= ~CMBPO_TASK_LEARNED_COST;
@@ -350,6 +430,15 @@ int post_impl(const char *who, int task, int ensemble, int obs_dim, int act_dim,
   CMBPO_REQUIRE(d_mean && d_var && d_obs && d_elite && d_next_obs && d_rew && d_term && d_cost &&
                     d_dkl_path && d_ep_var_mean,
                 "%s: NULL buffer", who);
+  if (dis != nullptr) {
+    // (x >= 0 is false for a NaN; the infinities are excluded on their own)
+    CMBPO_REQUIRE(dis->kappa_rew >= 0.0f && isfinite(dis->kappa_rew), "%s: kappa_rew %g is not a finite number >= 0", who, (double)dis->kappa_rew);
+    CMBPO_REQUIRE(dis->kappa_cost >= 0.0f && isfinite(dis->kappa_cost), "%s: kappa_cost %g is not a finite number >= 0", who, (double)dis->kappa_cost);
+    CMBPO_REQUIRE(!(dis->kappa_cost > 0.0f) || learned_cost,
+                  "%s: kappa_cost %g > 0 needs CMBPO_TASK_LEARNED_COST (a static cost rule has no member spread), task %d", who,
+                  (double)dis->kappa_cost, task_arg);
+    CMBPO_REQUIRE(dis->rew_var && dis->cost_var, "%s: NULL buffer (d_rew_var / d_cost_var)", who);
+  }
   CMBPO_REQUIRE(n_rows >= 0 && ld_rows >= n_rows, "%s: n_rows %d / ld_rows %d", who, n_rows, ld_rows);
   if (n_rows == 0) return CMBPO_OK;
   PostArgs a{};
@@ -369,13 +458,18 @@ int post_impl(const char *who, int task, int ensemble, int obs_dim, int act_dim,
       PostArgsRulesNoise an{};
       static_cast<PostArgsRules &>(an) = ar;
       an.xi = d_xi;
-      launch_post<true, true>(ensemble, grid, lds, s, an);
+      if (dis) launch_post_dis<true, true>(ensemble, grid, lds, s, an, *dis);
+      else launch_post<true, true>(ensemble, grid, lds, s, an);
     } else {
       PostArgsNoise an{};
       static_cast<PostArgs &>(an) = a;
       an.xi = d_xi;
-      launch_post<false, true>(ensemble, grid, lds, s, an);
+      if (dis) launch_post_dis<false, true>(ensemble, grid, lds, s, an, *dis);
+      else launch_post<false, true>(ensemble, grid, lds, s, an);
     }
+  } else if (dis) {
+    if (user) launch_post_dis<true, false>(ensemble, grid, lds, s, ar, *dis);
+    else launch_post_dis<false, false>(ensemble, grid, lds, s, a, *dis);
   } else if (user) launch_post<true, false>(ensemble, grid, lds, s, ar);
   else launch_post<false, false>(ensemble, grid, lds, s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
@@ -408,4 +502,20 @@ extern "C" int cmbpo_fakeenv_post_noise(int task, int ensemble, int obs_dim, int
                               n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, stream);
   return post_impl("cmbpo_fakeenv_post_noise", task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite,
                    d_row_idx, d_n_rows, n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, d_xi, stream);
+}
+
+// ... with the ensemble's disagreement on the reward and the learned-cost column measured, and the pessimistic reward / cost made
+// from it (see the kernel's DIS parts and the header); d_xi may be NULL: the deterministic transition
+extern "C" int cmbpo_fakeenv_post_disagreement(int task, int ensemble, int obs_dim, int act_dim,
+                                               const float *d_mean, const float *d_var, int ld_rows,
+                                               const float *d_obs, const float *d_act, const int32_t *d_elite,
+                                               const int32_t *d_row_idx, const int32_t *d_n_rows, int n_rows,
+                                               float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost,
+                                               float *d_dkl_path, float *d_ep_var_mean, float *d_ep_var,
+                                               const float *d_xi, float kappa_rew, float kappa_cost,
+                                               float *d_rew_var, float *d_cost_var, void *stream) {
+  const DisExtra dis{kappa_rew, kappa_cost, d_rew_var, d_cost_var};
+  return post_impl("cmbpo_fakeenv_post_disagreement", task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite,
+                   d_row_idx, d_n_rows, n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, d_xi, stream,
+                   &dis);
 }

@@ -9,3 +9,5 @@ int cmbpo_internal_book_pre(const cmbpo_rollout_t *r, int n_alive, int spec, int
 int cmbpo_internal_store_nostats(const cmbpo_rollout_t *r, void *stream);
 int cmbpo_internal_finish_post_fold(const cmbpo_rollout_t *r, void *stream);
 int cmbpo_internal_spec_words(const cmbpo_rollout_t *r, int begin, void *stream);
+// the disagreement state attached beside *r (all-zero and 0 if none): the one-call step post-processes with it
+int cmbpo_internal_disagreement_lookup(const cmbpo_rollout_t *r, cmbpo_disagreement_t *out);

@@ -110,8 +110,12 @@ __device__ __forceinline__ void block_reduce_many(double (&v)[NS + NM], double *
 }
 
 // ---- reset -------------------------------------------------------------------------------------
-__global__ void reset_kernel(const cmbpo_rollout_t r) {
+__global__ void reset_kernel(const cmbpo_rollout_t r, const cmbpo_disagreement_t dg) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < r.B && dg.part != nullptr) {      // (the totals are dscal slots: zeroed below)
+    dg.path_rew_var[b] = 0.0;
+    dg.path_cost_var[b] = 0.0;
+  }
   if (b < r.B) {
     r.alive[b] = 1;
     r.fin_code[b] = 0;
@@ -300,12 +304,13 @@ __device__ __forceinline__ void gae_finish_path(const cmbpo_rollout_t &r, const 
 }
 
 // ---- finish: reward + cost GAE, then mark terminated (modelbuffer.py:138-182) -------------------
-__device__ __forceinline__ void store_stats_body(const cmbpo_rollout_t &r);
+__device__ __forceinline__ void store_stats_body(const cmbpo_rollout_t &r, const cmbpo_disagreement_t &dg);
 // fold_stats (the rollout step at large batches, mode 1): workgroup 0 first folds the sums store_kernel's tiles left -- the
 // store is a launch further back, so no atomics are needed, and nothing before the end of this kernel reads the accumulators
 // (a launch of its own until round 3: store_stats_kernel)
-__global__ __launch_bounds__(256) void finish_kernel(const cmbpo_rollout_t r, int mode, int fold_stats, const cmbpo_iv_gae_t iv) {
-  if (fold_stats && blockIdx.x == 0) store_stats_body(r);
+__global__ __launch_bounds__(256) void finish_kernel(const cmbpo_rollout_t r, int mode, int fold_stats, const cmbpo_iv_gae_t iv,
+                                                  const cmbpo_disagreement_t dg) {
+  if (fold_stats && blockIdx.x == 0) store_stats_body(r, dg);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int n = r.iscal[CMBPO_I_N_ALIVE];
   if (i >= n) return;
@@ -351,7 +356,7 @@ __global__ __launch_bounds__(256) void finish_kernel(const cmbpo_rollout_t r, in
 // order: no atomics, reproducible accumulators.
 constexpr int kStoreRows = 64;
 
-__global__ __launch_bounds__(256) void store_kernel(const cmbpo_rollout_t r, const cmbpo_iv_gae_t iv) {
+__global__ __launch_bounds__(256) void store_kernel(const cmbpo_rollout_t r, const cmbpo_iv_gae_t iv, const cmbpo_disagreement_t dg) {
   __shared__ int s_slot[kStoreRows];   // branch slot of each row of the tile, -1: not stored
   const int n = r.iscal[CMBPO_I_N_ALIVE];
   const int tid = threadIdx.x;
@@ -390,6 +395,22 @@ __global__ __launch_bounds__(256) void store_kernel(const cmbpo_rollout_t r, con
       a_maxdkl = (double)dk;
       a_maxret = pr;
     }
+    // ensemble disagreement on reward / cost (attached: dg.part != NULL, uniform): the branch's float64 sums over its stored
+    // steps, and the tile's sums beside store_part's eight
+    if (dg.part != nullptr) {
+      double a_rv = 0, a_cv = 0;
+      if (b >= 0) {
+        a_rv = (double)dg.rew_var_t[b];
+        a_cv = (double)dg.cost_var_t[b];
+        dg.path_rew_var[b] += a_rv;
+        dg.path_cost_var[b] += a_cv;
+      }
+      const double w0 = wave_sum(a_rv), w1 = wave_sum(a_cv);
+      if (tid == 0) {
+        dg.part[2 * (size_t)blockIdx.x] = w0;
+        dg.part[2 * (size_t)blockIdx.x + 1] = w1;
+      }
+    }
     const double v0 = wave_sum(a_cnt), v1 = wave_sum(a_cost), v2 = wave_sum(a_rew), v3 = wave_sum(a_v);
     const double v4 = wave_sum(a_vc), v5 = wave_sum(a_epv), v6 = wave_max(a_maxdkl), v7 = wave_max(a_maxret);
     if (tid == 0) {
@@ -418,7 +439,7 @@ __global__ __launch_bounds__(256) void store_kernel(const cmbpo_rollout_t r, con
 }
 
 // fold the per-tile sums of store_kernel into the counters / accumulators (the 256 threads of one workgroup, fixed order)
-__device__ __forceinline__ void store_stats_body(const cmbpo_rollout_t &r) {
+__device__ __forceinline__ void store_stats_body(const cmbpo_rollout_t &r, const cmbpo_disagreement_t &dg) {
   __shared__ double sm_d[16];
   const int n = r.iscal[CMBPO_I_N_ALIVE];
   const int n_wg = (n + kStoreRows - 1) / kStoreRows;
@@ -452,9 +473,22 @@ __device__ __forceinline__ void store_stats_body(const cmbpo_rollout_t &r) {
     r.dscal[CMBPO_D_MAX_DKL] = fmax(r.dscal[CMBPO_D_MAX_DKL], s[6]);
     r.dscal[CMBPO_D_MAX_PATH_RETURN] = fmax(r.dscal[CMBPO_D_MAX_PATH_RETURN], s[7]);
   }
+  if (dg.part != nullptr) {      // (uniform) the tiles' disagreement sums, in the same fixed order
+    double u0 = 0.0, u1 = 0.0;
+    for (int w = threadIdx.x; w < n_wg; w += 256) {
+      u0 += dg.part[2 * (size_t)w];
+      u1 += dg.part[2 * (size_t)w + 1];
+    }
+    u0 = block_sum(u0, sm_d);
+    u1 = block_sum(u1, sm_d);
+    if (threadIdx.x == 0 && s[0] > 0.0) {
+      r.dscal[CMBPO_D_TOTAL_REW_VAR] += u0;
+      r.dscal[CMBPO_D_TOTAL_COST_VAR] += u1;
+    }
+  }
 }
 
-__global__ __launch_bounds__(256) void store_stats_kernel(const cmbpo_rollout_t r) { store_stats_body(r); }
+__global__ __launch_bounds__(256) void store_stats_kernel(const cmbpo_rollout_t r, const cmbpo_disagreement_t dg) { store_stats_body(r, dg); }
 
 // ---- small rollout batches: decide -> finish(PRE) -> store -> statistics as ONE workgroup --------------------------------
 // At the shipped configurations' 1e3 - 1e4 branches each of the five kernels above is a few microseconds of work behind a
@@ -468,7 +502,8 @@ constexpr int kBookMax = 1024;
 
 // spec (cmbpo_rollout_run's look-ahead): the step was enqueued before the host saw the previous step's counters -- it is void
 // when that step raised the halt word (book_post_kernel)
-__global__ __launch_bounds__(kScanThreads) void book_pre_kernel(const cmbpo_rollout_t r, int spec, const cmbpo_iv_gae_t iv) {
+__global__ __launch_bounds__(kScanThreads) void book_pre_kernel(const cmbpo_rollout_t r, int spec, const cmbpo_iv_gae_t iv,
+                                                             const cmbpo_disagreement_t dg) {
   __shared__ int sm_i[17];
   __shared__ double sm_d[16];
   __shared__ double sm_m[8 * 16];
@@ -531,6 +566,7 @@ __global__ __launch_bounds__(kScanThreads) void book_pre_kernel(const cmbpo_roll
   const size_t B = (size_t)r.B;
   const int D = r.obs_dim;
   double a_cnt = 0, a_cost = 0, a_rew = 0, a_v = 0, a_vc = 0, a_epv = 0, a_maxdkl = 0, a_maxret = 0;
+  double a_rv = 0, a_cv = 0;      // ensemble disagreement on reward / cost over the stored rows (attached only)
   for (int i = tid; i < n; i += kScanThreads) {
     const int b = r.alive_idx[i];
     const uint8_t code = r.fin_code[b];
@@ -553,6 +589,12 @@ __global__ __launch_bounds__(kScanThreads) void book_pre_kernel(const cmbpo_roll
     const double pv = r.path_dyn_var[b] + (double)epv;
     r.path_dyn_var[b] = pv;
     if (iv.cumvar_buf != nullptr) iv.cumvar_buf[col] = pv;     // (as in store_kernel)
+    if (dg.part != nullptr) {                                  // (as in store_kernel)
+      const double rv = (double)dg.rew_var_t[b], cv_ = (double)dg.cost_var_t[b];
+      dg.path_rew_var[b] += rv;
+      dg.path_cost_var[b] += cv_;
+      a_rv += rv; a_cv += cv_;
+    }
     r.dkl_acc[b] += (double)dk;
     a_cnt += 1.0; a_cost += c; a_rew += rw; a_v += v; a_vc += vc;
     a_epv += (double)epv * D;
@@ -581,6 +623,14 @@ __global__ __launch_bounds__(kScanThreads) void book_pre_kernel(const cmbpo_roll
     r.dscal[CMBPO_D_TOTAL_DKL] += dkl_mean * s0;
     r.dscal[CMBPO_D_MAX_DKL] = fmax(r.dscal[CMBPO_D_MAX_DKL], s6);
     r.dscal[CMBPO_D_MAX_PATH_RETURN] = fmax(r.dscal[CMBPO_D_MAX_PATH_RETURN], s7);
+  }
+  if (dg.part != nullptr) {      // (uniform; a reduction of its own: the detached kernel keeps the one it had)
+    double rd[2] = {a_rv, a_cv};
+    block_reduce_many<2, 0>(rd, sm_m);
+    if (tid == 0 && s0 > 0.0) {
+      r.dscal[CMBPO_D_TOTAL_REW_VAR] += rd[0];
+      r.dscal[CMBPO_D_TOTAL_COST_VAR] += rd[1];
+    }
   }
 }
 
@@ -1209,7 +1259,47 @@ cmbpo_iv_gae_t iv_lookup(const cmbpo_rollout_t *r) {
   return iv;
 }
 
+// ---- ensemble disagreement on reward / cost: the same arrangement (part == NULL: nothing attached) ------------------------
+std::mutex g_dg_mu;
+std::unordered_map<const void *, cmbpo_disagreement_t> g_dg;
+
+cmbpo_disagreement_t dg_lookup(const cmbpo_rollout_t *r) {
+  cmbpo_disagreement_t dg = {};
+  std::lock_guard<std::mutex> lock(g_dg_mu);
+  if (!g_dg.empty()) {
+    const auto it = g_dg.find(r->iscal);
+    if (it != g_dg.end()) dg = it->second;
+  }
+  return dg;
+}
+
 }  // namespace
+
+int cmbpo_internal_disagreement_lookup(const cmbpo_rollout_t *r, cmbpo_disagreement_t *out) {
+  *out = dg_lookup(r);
+  return out->part != nullptr ? 1 : 0;
+}
+
+extern "C" int cmbpo_rollout_disagreement_attach(const cmbpo_rollout_t *r, const cmbpo_disagreement_t *dg) {
+  CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_disagreement_attach: NULL rollout struct / iscal");
+  CMBPO_REQUIRE(dg != nullptr, "cmbpo_rollout_disagreement_attach: NULL cmbpo_disagreement_t");
+  CMBPO_REQUIRE(dg->rew_var_t && dg->cost_var_t, "cmbpo_rollout_disagreement_attach: NULL rew_var_t / cost_var_t");
+  CMBPO_REQUIRE(dg->path_rew_var && dg->path_cost_var, "cmbpo_rollout_disagreement_attach: NULL path_rew_var / path_cost_var");
+  CMBPO_REQUIRE(dg->part != nullptr, "cmbpo_rollout_disagreement_attach: NULL part (cmbpo_rollout_disagreement_detach switches the feature off)");
+  CMBPO_REQUIRE(dg->kappa_rew >= 0.0f && isfinite(dg->kappa_rew) && dg->kappa_cost >= 0.0f && isfinite(dg->kappa_cost),
+                "cmbpo_rollout_disagreement_attach: kappa_rew %g / kappa_cost %g: finite numbers >= 0", (double)dg->kappa_rew,
+                (double)dg->kappa_cost);
+  std::lock_guard<std::mutex> lock(g_dg_mu);
+  g_dg[r->iscal] = *dg;
+  return CMBPO_OK;
+}
+
+extern "C" int cmbpo_rollout_disagreement_detach(const cmbpo_rollout_t *r) {
+  CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_disagreement_detach: NULL rollout struct / iscal");
+  std::lock_guard<std::mutex> lock(g_dg_mu);
+  g_dg.erase(r->iscal);
+  return CMBPO_OK;
+}
 
 extern "C" int cmbpo_rollout_iv_attach(const cmbpo_rollout_t *r, const cmbpo_iv_gae_t *iv) {
   CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_iv_attach: NULL rollout struct / iscal");
@@ -1233,7 +1323,7 @@ extern "C" int cmbpo_rollout_reset(const cmbpo_rollout_t *r, void *stream) {
   if (int rc = check_rollout(r, "cmbpo_rollout_reset")) return rc;
   CMBPO_REQUIRE(r->dkl_acc && r->path_ret && r->path_cost && r->path_dyn_var, "cmbpo_rollout_reset: NULL accumulators");
   const int n = r->B > 32 ? r->B : 32;
-  hipLaunchKernelGGL(reset_kernel, dim3(cmbpo_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, *r);
+  hipLaunchKernelGGL(reset_kernel, dim3(cmbpo_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, *r, dg_lookup(r));
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1267,7 +1357,7 @@ extern "C" int cmbpo_rollout_finish(const cmbpo_rollout_t *r, int mode, void *st
                 "cmbpo_rollout_finish: NULL buffer");
   if (mode == 1) CMBPO_REQUIRE(r->v_n && r->vc_n && r->term_t, "cmbpo_rollout_finish: POST needs v_n, vc_n, term_t");
   else CMBPO_REQUIRE(r->v_t && r->vc_t, "cmbpo_rollout_finish: needs v_t, vc_t");
-  hipLaunchKernelGGL(finish_kernel, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, mode, 0, iv_lookup(r));
+  hipLaunchKernelGGL(finish_kernel, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, mode, 0, iv_lookup(r), dg_lookup(r));
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1282,8 +1372,9 @@ extern "C" int cmbpo_rollout_store(const cmbpo_rollout_t *r, void *stream) {
                     r->cval_buf && r->logp_buf,
                 "cmbpo_rollout_store: NULL buffer");
   CMBPO_REQUIRE(r->store_part != nullptr, "cmbpo_rollout_store: NULL store_part scratch");
-  hipLaunchKernelGGL(store_kernel, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, iv_lookup(r));
-  hipLaunchKernelGGL(store_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *r);
+  const cmbpo_disagreement_t dg = dg_lookup(r);
+  hipLaunchKernelGGL(store_kernel, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, iv_lookup(r), dg);
+  hipLaunchKernelGGL(store_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *r, dg);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1296,7 +1387,8 @@ int cmbpo_internal_store_nostats(const cmbpo_rollout_t *r, void *stream) {
                     r->epv_t && r->obs_buf && r->act_buf && r->mu_buf && r->ls_buf && r->rew_buf && r->val_buf && r->cost_buf &&
                     r->cval_buf && r->logp_buf && r->store_part,
                 "cmbpo_rollout_store: NULL array");
-  hipLaunchKernelGGL(store_kernel, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, iv_lookup(r));
+  hipLaunchKernelGGL(store_kernel, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, iv_lookup(r),
+                     dg_lookup(r));
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1305,7 +1397,7 @@ int cmbpo_internal_finish_post_fold(const cmbpo_rollout_t *r, void *stream) {
   CMBPO_REQUIRE(r->v_n && r->vc_n && r->term_t && r->rew_buf && r->val_buf && r->cost_buf && r->cval_buf && r->adv_buf && r->ret_buf &&
                     r->cadv_buf && r->cret_buf && r->store_part,
                 "cmbpo_rollout_finish (POST): NULL array");
-  hipLaunchKernelGGL(finish_kernel, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, 1, 1, iv_lookup(r));
+  hipLaunchKernelGGL(finish_kernel, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, 1, 1, iv_lookup(r), dg_lookup(r));
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1324,7 +1416,7 @@ extern "C" int cmbpo_rollout_book_pre(const cmbpo_rollout_t *r, int n_alive, voi
                     r->logp_buf && r->adv_buf && r->ret_buf && r->cadv_buf && r->cret_buf,
                 "cmbpo_rollout_book_pre: NULL buffer");
   if (n_alive == 0) return CMBPO_OK;
-  hipLaunchKernelGGL(book_pre_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, 0, iv_lookup(r));
+  hipLaunchKernelGGL(book_pre_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, 0, iv_lookup(r), dg_lookup(r));
   hipLaunchKernelGGL(store_vec_kernel, dim3(cmbpo_ceil_div(n_alive, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, 0);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
@@ -1340,7 +1432,7 @@ int cmbpo_internal_book_pre(const cmbpo_rollout_t *r, int n_alive, int spec, int
                     r->cost_t && r->epv_t && r->obs_buf && r->act_buf && r->mu_buf && r->ls_buf && r->rew_buf && r->val_buf &&
                     r->cost_buf && r->cval_buf && r->logp_buf && r->adv_buf && r->ret_buf && r->cadv_buf && r->cret_buf,
                 "cmbpo_rollout_book_pre: NULL array");
-  hipLaunchKernelGGL(book_pre_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, spec, iv_lookup(r));
+  hipLaunchKernelGGL(book_pre_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, spec, iv_lookup(r), dg_lookup(r));
   if (with_vec)
     hipLaunchKernelGGL(store_vec_kernel, dim3(cmbpo_ceil_div(n_alive, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, spec);
   CMBPO_HIP_CHECK(hipGetLastError());

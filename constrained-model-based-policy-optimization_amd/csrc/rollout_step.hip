@@ -53,6 +53,15 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   if ((rc = cmbpo_ens_forward(model, r->cur_obs, r->obs_dim, r->act_t, r->act_dim, r->alive_idx, d_n, n_alive, r->B,
                               d_mean, d_var, stream)))
     return rc;
+  // ensemble disagreement attached beside *r: its instance of the post kernel, penalised rew_t / cost_t (d_xi may be NULL)
+  cmbpo_disagreement_t dg;
+  if (cmbpo_internal_disagreement_lookup(r, &dg)) {
+    if ((rc = cmbpo_fakeenv_post_disagreement(task, ensemble, r->obs_dim, r->act_dim, d_mean, d_var, r->B, r->cur_obs, r->act_t, d_elite,
+                                              r->alive_idx, d_n, n_alive, w(r->next_obs), w(r->rew_t), const_cast<uint8_t *>(r->term_t),
+                                              w(r->cost_t), w(r->dkl_t), w(r->epv_t), nullptr, d_xi, dg.kappa_rew, dg.kappa_cost,
+                                              dg.rew_var_t, dg.cost_var_t, stream)))
+      return rc;
+  } else
   // (d_xi == NULL: cmbpo_fakeenv_post, the deterministic transition)
   if ((rc = cmbpo_fakeenv_post_noise(task, ensemble, r->obs_dim, r->act_dim, d_mean, d_var, r->B, r->cur_obs, r->act_t, d_elite,
                                      r->alive_idx, d_n, n_alive, w(r->next_obs), w(r->rew_t), const_cast<uint8_t *>(r->term_t),

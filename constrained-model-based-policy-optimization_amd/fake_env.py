@@ -20,6 +20,14 @@ elite member's mean of the model's last output column (``output_dim == obs_dim +
 task's cost rule; the task's termination rule still applies.  ``info['cost']`` is then the float32
 prediction, not thresholded.
 
+``disagreement=True`` measures what the members that were not picked say about reward and cost: ``step()`` adds
+``info['ensemble_rew_var']`` / ``info['ensemble_cost_var']`` (``np.var`` over all members of the reward column and, with
+``predicts_cost``, of the cost column; without it the cost variance is 0).  ``rew_pessimism`` / ``cost_pessimism`` (kappa >= 0;
+> 0 switches the measurement on) make the returned reward ``r - kappa_r * sqrt(rew_var)`` and the learned cost
+``c + kappa_c * sqrt(cost_var)`` (``cmbpo_fakeenv_post_disagreement``); ``set_pessimism(rew, cost)`` changes them later.
+``cost_pessimism > 0`` needs ``predicts_cost``: a static cost rule has no member spread.  Off (the default) the calls made
+and the keys returned are what they were.
+
 ``task`` is a built-in task name, a name given to ``statics.register_task``, or a ``statics.TaskRules`` (user-defined
 termination / cost rules, evaluated by the same kernel); any other name is the default task, as in the reference.
 """
@@ -31,7 +39,7 @@ from . import _lib, statics
 
 class FakeEnv:
     def __init__(self, true_environment, task, model, predicts_delta, predicts_rew, predicts_cost,
-                 seed=0):
+                 seed=0, disagreement=False, rew_pessimism=0.0, cost_pessimism=0.0):
         self.env = true_environment
         self.obs_dim = int(np.prod(self.observation_space.shape))
         self.act_dim = int(np.prod(self.action_space.shape))
@@ -58,6 +66,9 @@ class FakeEnv:
         if self._predicts_cost:
             self._task_id |= _lib.TASK_LEARNED_COST
         self._rng = np.random.default_rng(seed)
+        self._disagreement = bool(disagreement)
+        self.rew_pessimism = self.cost_pessimism = 0.0
+        self.set_pessimism(rew_pessimism, cost_pessimism)
         self.device = model.device
         # bench.py sets this to a list to collect (start, end) HIP events around the dominant kernel
         self.kernel_events = None
@@ -70,6 +81,20 @@ class FakeEnv:
     def action_space(self):
         return self.env.action_space
 
+    @property
+    def disagreement(self):
+        """True when the ensemble's disagreement on reward / cost is measured (switched on, or a coefficient > 0)."""
+        return self._disagreement or self.rew_pessimism > 0.0 or self.cost_pessimism > 0.0
+
+    def set_pessimism(self, rew, cost):
+        """The coefficients of the pessimistic reward r - rew * sigma_r and learned cost c + cost * sigma_c."""
+        rew, cost = float(rew), float(cost)
+        if not (np.isfinite(rew) and rew >= 0.0 and np.isfinite(cost) and cost >= 0.0):
+            raise ValueError(f"rew_pessimism / cost_pessimism must be finite numbers >= 0, got {rew}, {cost}")
+        if cost > 0.0 and not self._predicts_cost:
+            raise ValueError("cost_pessimism > 0 needs predicts_cost=True: a static cost rule has no ensemble spread")
+        self.rew_pessimism, self.cost_pessimism = rew, cost
+
     def random_inds(self, size):
         """One elite per branch (models/fake_env.py:174-178), from this object's seeded generator."""
         elites = np.asarray(self._model.elite_inds, dtype=np.int32)
@@ -80,7 +105,8 @@ class FakeEnv:
         N(0, 1) draws for stochastic transitions, None: the elite member's mean).
 
         out: dict with next_obs[B,obs], rew[B], term[B] u8, cost[B], dkl_path[B], ep_var_mean[B]
-        (and optionally ep_var[B,obs]).  scratch: (mean, var)[E,B,output_dim].
+        (and optionally ep_var[B,obs]).  scratch: (mean, var)[E,B,output_dim].  With `disagreement` on, out also needs
+        rew_var[B] and cost_var[B]; they are filled, and rew / cost are the penalised values.
         """
         B = obs.shape[0]
         if noise is not None and not (noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
@@ -112,7 +138,11 @@ class FakeEnv:
                 _lib.ptr(out["term"]), _lib.ptr(out["cost"]),
                 _lib.ptr(out["dkl_path"]), _lib.ptr(out["ep_var_mean"]),
                 _lib.ptr(out.get("ep_var")))
-        if noise is None:
+        if self.disagreement:
+            _lib.check(lib.cmbpo_fakeenv_post_disagreement(*post, _lib.ptr(noise), self.rew_pessimism, self.cost_pessimism,
+                                                           _lib.ptr(out["rew_var"]), _lib.ptr(out["cost_var"]), stream),
+                       "cmbpo_fakeenv_post_disagreement")
+        elif noise is None:
             _lib.check(lib.cmbpo_fakeenv_post(*post, stream), "cmbpo_fakeenv_post")
         else:
             _lib.check(lib.cmbpo_fakeenv_post_noise(*post, _lib.ptr(noise), stream), "cmbpo_fakeenv_post_noise")
@@ -154,6 +184,8 @@ class FakeEnv:
                        term=torch.empty(n, dtype=torch.uint8, device=self.device),
                        cost=torch.empty(n, **f), dkl_path=torch.empty(n, **f),
                        ep_var_mean=torch.empty(n, **f), ep_var=torch.empty((n, self.obs_dim), **f))
+            if self.disagreement:
+                out.update(rew_var=torch.empty(n, **f), cost_var=torch.empty(n, **f))
             self.step_device(o, a, inds, out, noise=xi)
         next_obs, r, terms = out["next_obs"], out["rew"][:, None], out["term"].bool()[:, None]
         c = out["cost"][:, None]
@@ -169,6 +201,11 @@ class FakeEnv:
             next_obs, r, c, terms = next_obs[0], r[0], c[0], terms[0]
         info = {"ensemble_dkl_mean": dkl_mean, "ensemble_dkl_path": dkl_path,
                 "ensemble_ep_var": ep_var, "rew": r, "cost": c}
+        if self.disagreement:
+            rv, cv = out["rew_var"], out["cost_var"]
+            if was_np:
+                rv, cv = rv.cpu().numpy(), cv.cpu().numpy()
+            info["ensemble_rew_var"], info["ensemble_cost_var"] = rv, cv
         return next_obs, r, terms, info
 
     def close(self):

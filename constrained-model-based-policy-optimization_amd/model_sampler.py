@@ -19,6 +19,10 @@ Event order, bootstraps and the budget rule follow ``model_sampler.py:239-375`` 
 ``ModelSampler(stochastic=True)`` samples every imagined transition from the elite member's N(mean, var) (``xi`` draws of
 the sampler's generator, ``cmbpo_fakeenv_post_noise``); off, the draws and the results are what they were without it.
 
+``reset()`` takes the disagreement switch and the pessimism coefficients of its ``env`` (``FakeEnv(disagreement=...,
+rew_pessimism=..., cost_pessimism=...)``) and hands them to the pool: every step then measures the ensemble's disagreement on
+reward and cost, stores the penalised values and adds the variances of the stored rows to two more accumulators.
+
 ``sample()`` returns ``(next_obs, reward, terminal, info)`` like the reference, but as slot-indexed CUDA
 tensors (the trainer only reads ``info['alive_ratio']``, ``algorithms/cmbpo.py:254-263``).
 """
@@ -109,17 +113,23 @@ class ModelSampler:
         return self._host["total_dkl"] / (self._host["total_samples"] + EPS)
 
     def get_diagnostics(self):
-        """model_sampler.py:89-133 (same keys; variance terms the reference never fills stay 0)."""
+        """model_sampler.py:89-133 (same keys; variance terms the reference never fills stay 0).
+
+        With the environment's disagreement switch on, ``rew_var_perstep`` / ``cost_var_perstep`` are the ensemble's variance
+        on the reward / cost column averaged over the stored samples (the reference declares ``_total_rew_var`` /
+        ``_total_cost_var`` and never fills them), and with a pessimism coefficient > 0 ``rew_rate`` / ``cost_rate`` are rates
+        of the PENALISED values: the pool stores what the constrained update will see.  ``ens_mean_var`` stays 0."""
         _, d = self._read_scalars()
         L = _lib
         tot = d[L.D_TOTAL_SAMPLES]
+        on = bool(getattr(self.pool, "disagreement", False))
         diagnostics = OrderedDict({"pool-size": self.pool.size})
         diagnostics.update({
             "msampler/samples_added": tot,
             "msampler/rollout_H_max": self._n_episodes,
             "msampler/rollout_H_mean": tot / (self.batch_size + EPS),
-            "msampler/rew_var_perstep": 0.0,
-            "msampler/cost_var_perstep": 0.0,
+            "msampler/rew_var_perstep": d[L.D_TOTAL_REW_VAR] / (tot + EPS) if on else 0.0,
+            "msampler/cost_var_perstep": d[L.D_TOTAL_COST_VAR] / (tot + EPS) if on else 0.0,
             "msampler/dyn_var_perstep": d[L.D_TOTAL_DYN_EP_VAR] / (tot + EPS),
             "msampler/cost_rate": d[L.D_SUM_PATH_COST] / (tot + EPS),
             "msampler/rew_rate": d[L.D_SUM_PATH_RET] / (tot + EPS),
@@ -162,6 +172,10 @@ class ModelSampler:
         pool = self.pool
         with torch.cuda.device(self.device):
             pool.reset(self.batch_size)
+            # the environment's disagreement switch and pessimism coefficients (nothing is stored here; arrays allocated by
+            # the call start at zero, arrays that were attached have just been zeroed)
+            pool.set_disagreement(getattr(self.env, "disagreement", False), getattr(self.env, "rew_pessimism", 0.0),
+                                  getattr(self.env, "cost_pessimism", 0.0))
             if observations is None:
                 fill(pool.t["cur_obs"])
             else:
@@ -268,9 +282,11 @@ class ModelSampler:
                                          dict(pi=t["act_t"], logp_pi=t["logp_t"], mu=t["mu_t"], log_std=t["ls_t"]),
                                          row_idx=idx, n_rows=n)
                 # dynamics ensemble + FakeEnv post-processing
-                env.step_device(t["cur_obs"], t["act_t"], inds_t,
-                                dict(next_obs=t["next_obs"], rew=t["rew_t"], term=t["term_t"], cost=t["cost_t"],
-                                     dkl_path=t["dkl_t"], ep_var_mean=t["epv_t"]),
+                outs = dict(next_obs=t["next_obs"], rew=t["rew_t"], term=t["term_t"], cost=t["cost_t"],
+                            dkl_path=t["dkl_t"], ep_var_mean=t["epv_t"])
+                if pool.disagreement:       # (the arrays attached beside the struct: the store below reads them)
+                    outs.update(rew_var=t["rew_var_t"], cost_var=t["cost_var_t"])
+                env.step_device(t["cur_obs"], t["act_t"], inds_t, outs,
                                 row_idx=idx, n_rows=n, scratch=self._scratch, noise=xi_t)
                 if exchange:
                     # budget rule across shards: gather {n_alive, n_unc, total}, rank the survivors globally

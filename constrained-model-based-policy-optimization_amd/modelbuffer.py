@@ -21,6 +21,11 @@ sampler -- to the weighted branch of the reference's ``discount_cumsum(x, discou
 of the epistemic variance accumulated on the way to it.  The reference's buffer keeps ``dyn_error_buf`` for this and comments
 both GAE lines accordingly (``modelbuffer.py:167,176``) but calls the un-weighted branch; off (the default) is that behaviour.
 Constant weights do not reduce to plain GAE: the reference folds the weight beyond the last step into the last one.
+
+``set_disagreement(on, rew_pessimism, cost_pessimism)`` attaches the arrays of the ensemble disagreement on reward and cost
+(``cmbpo_disagreement_t``: this step's ``rew_var_t`` / ``cost_var_t``, the per-branch float64 sums ``path_rew_var`` /
+``path_cost_var`` over the stored steps, the scratch of the step's totals) beside the rollout struct; ``ModelSampler.reset``
+calls it with its environment's settings.  Off (the default) nothing is allocated and nothing is measured.
 """
 import ctypes as C
 import weakref
@@ -48,12 +53,13 @@ def iv_tables(lam, T):
 
 
 def _iv_release(key):
-    """Finaliser of a buffer: no entry of the library's table may outlive the arrays it points to."""
+    """Finaliser of a buffer: no entry of the library's tables may outlive the arrays it points to."""
     try:
         if key[0]:
             rs = RolloutStruct()
             rs.iscal = key[0]
             _lib.lib().cmbpo_rollout_iv_detach(C.byref(rs))
+            _lib.lib().cmbpo_rollout_disagreement_detach(C.byref(rs))
     except Exception:      # interpreter shutdown
         pass
 
@@ -78,6 +84,7 @@ class ModelBuffer:
         self.pi_info_shapes = None
         self.gamma, self.lam, self.cost_gamma, self.cost_lam = 0.99, 0.95, 0.99, 0.95
         self.iv_gae, self.iv_eps = bool(iv_gae), self._check_iv_eps(iv_eps)
+        self.disagreement, self.rew_pessimism, self.cost_pessimism = False, 0.0, 0.0
         self.rs = None
         self._iv_key = [0]                    # iscal of the arrays the library's table may hold an entry for
         weakref.finalize(self, _iv_release, self._iv_key)
@@ -89,6 +96,7 @@ class ModelBuffer:
         T, D, A, dev = self.max_path_length, self.obs_dim, self.act_dim, self.device
         if self.rs is not None:               # the table's key is the old iscal
             _lib.check(_lib.lib().cmbpo_rollout_iv_detach(C.byref(self.rs)), "cmbpo_rollout_iv_detach")
+            _lib.check(_lib.lib().cmbpo_rollout_disagreement_detach(C.byref(self.rs)), "cmbpo_rollout_disagreement_detach")
         f = dict(dtype=torch.float32, device=dev)
         d = dict(dtype=torch.float64, device=dev)
         t = {}
@@ -128,6 +136,7 @@ class ModelBuffer:
         self._bind_all()
         self._iv_key[0] = self.t["iscal"].data_ptr()
         self._iv_sync()
+        self._dis_sync()
 
     def _bind_all(self):
         for name, _ in RolloutStruct._fields_:
@@ -174,6 +183,44 @@ class ModelBuffer:
         iv.clam_vec, iv.clam_pow = base + 8 * (2 * T + 1), base + 8 * (3 * T + 1)
         iv.eps = self.iv_eps
         _lib.check(lib.cmbpo_rollout_iv_attach(C.byref(self.rs), C.byref(iv)), "cmbpo_rollout_iv_attach")
+
+    # -- ensemble disagreement on reward / cost --------------------------------------------------
+    def set_disagreement(self, on, rew_pessimism=0.0, cost_pessimism=0.0):
+        """Measure the ensemble's disagreement on reward and cost along the rollout (and hold kappa * sigma against the
+        branch where a coefficient is > 0, which implies `on`); legal whenever nothing is stored."""
+        kr, kc = float(rew_pessimism), float(cost_pessimism)
+        if not (np.isfinite(kr) and kr >= 0.0 and np.isfinite(kc) and kc >= 0.0):
+            raise ValueError(f"rew_pessimism / cost_pessimism must be finite numbers >= 0, got {kr}, {kc}")
+        on = bool(on) or kr > 0.0 or kc > 0.0
+        if (on, kr, kc) == (self.disagreement, self.rew_pessimism, self.cost_pessimism):
+            return
+        if self.ptr != 0 or self._size != 0:
+            raise RuntimeError("set_disagreement: the buffer holds samples (call it after get() / reset())")
+        self.disagreement, self.rew_pessimism, self.cost_pessimism = on, kr, kc
+        self._dis_sync()
+
+    def _dis_sync(self):
+        """Attach (on: for the current arrays and coefficients) or detach (off: and free) the state beside the struct."""
+        lib, t = _lib.lib(), self.t
+        names = ("rew_var_t", "cost_var_t", "path_rew_var", "path_cost_var", "dis_part")
+        if not self.disagreement:
+            _lib.check(lib.cmbpo_rollout_disagreement_detach(C.byref(self.rs)), "cmbpo_rollout_disagreement_detach")
+            for n in names:
+                t.pop(n, None)
+            return
+        B, dev = self.capacity, self.device
+        if "dis_part" not in t:
+            t["rew_var_t"] = torch.zeros(B, dtype=torch.float32, device=dev)
+            t["cost_var_t"] = torch.zeros(B, dtype=torch.float32, device=dev)
+            t["path_rew_var"] = torch.zeros(B, dtype=torch.float64, device=dev)
+            t["path_cost_var"] = torch.zeros(B, dtype=torch.float64, device=dev)
+            t["dis_part"] = torch.zeros(((B + 63) // 64) * 2, dtype=torch.float64, device=dev)
+        dg = _lib.DisagreementStruct()
+        dg.kappa_rew, dg.kappa_cost = self.rew_pessimism, self.cost_pessimism
+        dg.rew_var_t, dg.cost_var_t = t["rew_var_t"].data_ptr(), t["cost_var_t"].data_ptr()
+        dg.path_rew_var, dg.path_cost_var = t["path_rew_var"].data_ptr(), t["path_cost_var"].data_ptr()
+        dg.part = t["dis_part"].data_ptr()
+        _lib.check(lib.cmbpo_rollout_disagreement_attach(C.byref(self.rs), C.byref(dg)), "cmbpo_rollout_disagreement_attach")
 
     def swap(self, a, b):
         """Exchange two same-shaped state arrays (cur_obs <-> next_obs, v_t <-> v_n, ...)."""

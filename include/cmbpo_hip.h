@@ -248,6 +248,28 @@ int cmbpo_fakeenv_post_noise(int task, int ensemble, int obs_dim, int act_dim,
                              float *d_rew, uint8_t *d_term, float *d_cost,
                              float *d_dkl_path, float *d_ep_var_mean,
                              float *d_ep_var, const float *d_xi, void *stream);
+/* The same step with the ensemble's disagreement on the reward and the learned-cost column measured and, where a coefficient is
+ * > 0, held against the branch (cmbpo_fakeenv_post_noise's arguments, d_xi may be NULL: the deterministic transition):
+ *   d_rew_var[r]  = np.var(mean[:, r, obs], axis=0) over ALL E members, float32, in ens_ep_var's order of operations:
+ *                   s = ((x_0 + x_1) + x_2) + ...; m = s / E; q = sum_e (x_e - m)^2 in member order; var = q / E (no contraction)
+ *   d_cost_var[r] = the same on column obs + 1 with CMBPO_TASK_LEARNED_COST, else +0 (a static cost rule has no member spread)
+ *   r    = fl32(r_elite - fl32(kappa_rew * sqrtf(rew_var)))     if kappa_rew > 0, else r_elite bit for bit
+ *   cost = fl32(c_elite + fl32(kappa_cost * sqrtf(cost_var)))   if kappa_cost > 0, else c_elite bit for bit
+ * (sqrtf correctly rounded).  Both columns are never moved by d_xi, so the variances are those of the unperturbed means.  With
+ * a coefficient of 0 no other member's value reaches the output (a NaN there stays there); with one > 0 non-finite members
+ * propagate as NumPy propagates them.  next_obs, term, dkl_path, ep_var* do not depend on the feature.  Both new outputs are
+ * slot indexed like d_rew and required.  cmbpo_fakeenv_post's argument checks; kappa_* finite and >= 0, kappa_cost > 0 only
+ * with CMBPO_TASK_LEARNED_COST, non-NULL outputs -- all before any HIP call. */
+int cmbpo_fakeenv_post_disagreement(int task, int ensemble, int obs_dim, int act_dim,
+                                    const float *d_mean, const float *d_var, int ld_rows,
+                                    const float *d_obs, const float *d_act,
+                                    const int32_t *d_elite, const int32_t *d_row_idx,
+                                    const int32_t *d_n_rows, int n_rows, float *d_next_obs,
+                                    float *d_rew, uint8_t *d_term, float *d_cost,
+                                    float *d_dkl_path, float *d_ep_var_mean,
+                                    float *d_ep_var, const float *d_xi,
+                                    float kappa_rew, float kappa_cost,
+                                    float *d_rew_var, float *d_cost_var, void *stream);
 
 /* ------------------------------------------------------------------------ *
  * Device-resident rollout state: the fused counterpart of ModelSampler
@@ -323,6 +345,8 @@ typedef struct cmbpo_rollout {
 #define CMBPO_D_STEP_MAX_DKL 10
 #define CMBPO_D_SUM_PATH_RET 11
 #define CMBPO_D_SUM_PATH_COST 12
+#define CMBPO_D_TOTAL_REW_VAR 13   /* sums of rew_var_t / cost_var_t over the stored rows (cmbpo_rollout_disagreement_attach; */
+#define CMBPO_D_TOTAL_COST_VAR 14  /* the reference declares _total_rew_var / _total_cost_var and never fills them)          */
 
 /* ModelSampler.reset + ModelBuffer.reset (model_sampler.py:203-237,
  * modelbuffer.py:53-98): all B branches alive, lists / accumulators zeroed.
@@ -361,7 +385,8 @@ int cmbpo_rollout_compact(const cmbpo_rollout_t *r, void *stream);
  * cmbpo_ens_forward -> cmbpo_fakeenv_post -> decide -> finish(PRE) -> store -> cmbpo_ens_predict_mean x 2 at next_obs ->
  * finish(POST), every buffer taken from *r (slot-indexed d_eps [B, act], d_elite [B]; scratch d_mean / d_var
  * [E, B, model out_dim]: obs + 1, or obs + 2 with CMBPO_TASK_LEARNED_COST in `task`).  n_alive = the host's copy of iscal[CMBPO_I_N_ALIVE].
- * With r->xi != NULL the post-processing is cmbpo_fakeenv_post_noise on those draws. */
+ * With r->xi != NULL the post-processing is cmbpo_fakeenv_post_noise on those draws; with a cmbpo_disagreement_t attached it is
+ * cmbpo_fakeenv_post_disagreement (with or without draws). */
 /* Small rollout batches: decide + finish(PRE) + store (+ its statistics) as one single-workgroup launch for up to
  * cmbpo_rollout_book_pre_max_rows() alive rows (same decisions and per-branch arithmetic as the separate calls;
  * single-rank path).  cmbpo_rollout_step uses it by itself. */
@@ -412,6 +437,27 @@ typedef struct cmbpo_iv_gae {
 int cmbpo_rollout_iv_attach(const cmbpo_rollout_t *r, const cmbpo_iv_gae_t *iv);
 /* Back to the un-weighted recurrence (no error when nothing was attached). */
 int cmbpo_rollout_iv_detach(const cmbpo_rollout_t *r);
+
+/* Ensemble disagreement on reward and cost along imagined rollouts, and the pessimistic rollout made from it.  Like the
+ * weighted GAE the state travels beside an unchanged cmbpo_rollout_t (key: r->iscal).  Attached,
+ *   - every call that post-processes (cmbpo_rollout_step, _run) runs cmbpo_fakeenv_post_disagreement with kappa_rew /
+ *     kappa_cost into rew_var_t / cost_var_t, so rew_t / cost_t -- and with them the buffers, the sums and the GAE -- are the
+ *     penalised values; the alive masks and the budget rule do not depend on them;
+ *   - every call that stores (cmbpo_rollout_store, _book_pre, _step, _run) adds, for the stored rows, rew_var_t[b] to
+ *     path_rew_var[b] and cost_var_t[b] to path_cost_var[b] (float64, in step order) and the step's sums over those rows to
+ *     dscal[CMBPO_D_TOTAL_REW_VAR] / [CMBPO_D_TOTAL_COST_VAR] (per-workgroup partial sums in `part`, added in a fixed order);
+ *   - cmbpo_rollout_reset zeroes path_rew_var / path_cost_var.
+ * A caller that post-processes by itself passes the same arrays to cmbpo_fakeenv_post_disagreement.  Device pointers, owned by
+ * the caller, valid until the detach; attach again after any of them or r->iscal moved.  part: 2 * ceil(B / 64) doubles. */
+typedef struct cmbpo_disagreement {
+  float kappa_rew, kappa_cost;
+  float *rew_var_t, *cost_var_t;          /* [B] this step, slot indexed */
+  double *path_rew_var, *path_cost_var;   /* [B] sums over the branch's stored steps */
+  double *part;                           /* scratch for per-workgroup partial sums, sized by the builder */
+} cmbpo_disagreement_t;
+int cmbpo_rollout_disagreement_attach(const cmbpo_rollout_t *r, const cmbpo_disagreement_t *dg);
+/* Back to the elite member's reward and cost, nothing measured (no error when nothing was attached). */
+int cmbpo_rollout_disagreement_detach(const cmbpo_rollout_t *r);
 
 /* ModelBuffer.get (modelbuffer.py:184-226): d_offsets[B+1] = exclusive scan of
  * len; d_stats[8] = {n, adv_mean, adv_std, cadv_mean, ret_mean, cret_mean}
