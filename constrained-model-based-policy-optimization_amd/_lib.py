@@ -233,6 +233,27 @@ SIGNATURES.update({
     "cmbpo_start_boltz_draw": (_i, [_p, _p, _p, _i, _p, C.c_long, _i, _p, _p, _p]),
 })
 
+# open-loop model validation: k-step replay of real trajectories (csrc/replay.hip)
+REPLAY_OPEN_LOOP, REPLAY_ONE_STEP = 0, 1       # CMBPO_REPLAY_OPEN_LOOP / _ONE_STEP
+REPLAY_SCALAR_SUMS, REPLAY_COUNTS = 4, 10      # columns of `sums` behind the obs_dim squared errors; columns of `counts`
+
+
+class ReplayStruct(C.Structure):
+    """ctypes image of ``cmbpo_replay_t`` (184 bytes), field for field."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "H", "obs_dim", "act_dim", "mode", "reserved")] + \
+               [(n, C.c_void_p) for n in ("act", "next_obs", "rew", "cost", "term", "len", "cur_obs", "alive",
+                                          "p_next_obs", "p_rew", "p_term", "p_cost", "p_dkl_path", "p_ep_var_mean",
+                                          "mean", "var", "part_sum", "part_cnt", "sums", "counts")]
+
+
+_pp = C.POINTER(ReplayStruct)
+SIGNATURES.update({
+    "cmbpo_replay_parts": (_i, [_i]),
+    "cmbpo_replay_compare": (_i, [_pp, _i, _p]),
+    "cmbpo_replay_finish": (_i, [_pp, _p]),
+    "cmbpo_replay_run": (_i, [_pp, _p, _i, _i, _p, _p]),
+})
+
 _lib = None
 
 

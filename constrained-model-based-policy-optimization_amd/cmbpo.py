@@ -29,6 +29,12 @@ rollouts (``msampler/rew_var_perstep``, ``msampler/cost_var_perstep``); ``m_rew_
 ``c + kappa_c * sigma_c``: a constraint is no longer satisfied on the say-so of one member (``FakeEnv(disagreement=...)``).
 ``m_cost_pessimism > 0`` needs ``m_learn_cost=True``.  Real samples and the rollout lengths are not affected.
 
+``m_validate_horizon=H`` (> 0; the reference has nothing like it) replays, every epoch, ``m_validate_windows`` windows of up to H
+consecutive real steps of that epoch through the model with the recorded actions and reports how the prediction error
+compounds, which real costs and terminations the imagined signal misses, and whether the epistemic variance is the size of
+the error (``model/val_*``; ``validate_model``, ``FakeEnv.replay``).  It reads and does not steer: it draws from generators of
+its own, and policy and model after a run are bitwise those of the run without it.
+
 ``static_fns`` takes a ``statics.TaskRules``: user-defined termination / cost rules for the imagined rollouts, with
 precedence over ``task`` (which may itself be a name given to ``statics.register_task``).
 """
@@ -85,6 +91,7 @@ class CMBPO:
                  model_train_kwargs=None, initial_model_train_kwargs=None, shuffle_on_device=True, device=None,
                  session=None, start_state_sampling='host', m_stochastic=False, m_iv_gae=False, m_iv_eps=1e-8,
                  m_disagreement=False, m_rew_pessimism=0.0, m_cost_pessimism=0.0,
+                 m_validate_horizon=0, m_validate_windows=1024,
                  **_unused):
         # RLAlgorithm.__init__ (algorithms/rl_algorithm.py:22-74)
         self.sampler = sampler if sampler is not None else CpoSampler(max_path_length=getattr(policy, "max_path_length", 1000))
@@ -156,6 +163,12 @@ class CMBPO:
             self.model_sampler = ModelSampler(max_path_length=maxroll, batch_size=self._rollout_batch_size,
                                               logger=None, rollout_mode=self.rollout_mode,
                                               stochastic=bool(m_stochastic))
+        # open-loop validation of the model on each epoch's real samples (0: off -- no call, no key, no random number)
+        self._validate_horizon, self._validate_windows = int(m_validate_horizon), int(m_validate_windows)
+        if self._validate_horizon < 0 or (self._validate_horizon > 0 and self._validate_windows < 1):
+            raise ValueError("m_validate_horizon must be >= 0 and m_validate_windows >= 1, got %r, %r"
+                             % (m_validate_horizon, m_validate_windows))
+        self._validate_rng = None      # the window draws: a stream of their own, made by the first validate_model()
         self.init_real_samples = initial_real_samples_per_epoch
         self.min_real_samples = min_real_samples_per_epoch
         self.batch_size_policy = batch_size_policy
@@ -209,6 +222,35 @@ class CMBPO:
         return self._model.train(dyn_ins, dyn_outs, batch_size=batch_size, max_epochs=max_epochs,
                                  min_epoch_before_break=min_epochs, holdout_ratio=0.2, max_t=self._max_model_t,
                                  shuffle_on_device=self._shuffle_on_device)
+
+    def validate_model(self, epochs=None, horizon=None, n_windows=None):
+        """Open-loop validation of the dynamics model: ``n_windows`` windows of up to ``horizon`` consecutive
+        real steps from the archive (``epochs``: only windows starting in these) replayed through the model with the
+        recorded actions, ``FakeEnv.replay``.  The loop calls it right after the epoch's real samples have moved into the
+        archive, on that epoch only: ``train_model`` ran before the move, so no training run has seen them (prequential
+        validation -- nothing is held back from training).  Returns the ``val_*`` diagnostics; ``last_validation`` keeps
+        the whole per-horizon table."""
+        if not self._use_model:
+            raise ValueError("validate_model: the trainer was built with use_model=False, there is no model to validate")
+        H = int(horizon or self._validate_horizon)
+        if H < 1:
+            raise ValueError("validate_model: pass horizon >= 1 (the trainer was built with m_validate_horizon=0)")
+        if self._validate_rng is None:
+            self._validate_rng = np.random.default_rng(0x76616c)
+        _, _, win = self._buffer.windows(H, int(n_windows or self._validate_windows), epochs=epochs, rng=self._validate_rng)
+        tab = self.fake_env.replay(**win)
+        self.last_validation = tab
+        ratio = lambda a, b: float(a) / float(b) if b > 0 else float('nan')
+        cm, tm = tab['cost_cm'].sum(axis=0), tab['term_cm'].sum(axis=0)      # [real, predicted], all horizons
+        last = H - 1
+        return {'val_n_h1': int(tab['n'][0]), 'val_n_hH': int(tab['n'][last]),
+                'val_mse_obs_h1': float(np.mean(tab['mse_obs'][0])), 'val_mse_obs_hH': float(np.mean(tab['mse_obs'][last])),
+                'val_mse_rew_hH': float(tab['mse_rew'][last]),
+                'val_cost_miss_rate': ratio(cm[1, 0], cm[1, 0] + cm[1, 1]),
+                'val_cost_false_alarm_rate': ratio(cm[0, 1], cm[0, 0] + cm[0, 1]),
+                'val_term_false_rate': ratio(tm[0, 1], tm[0, 0] + tm[0, 1]),
+                'val_epvar_over_mse_hH': ratio(tab['ep_var_mean'][last], np.mean(tab['mse_obs'][last])),
+                'val_nonfinite': int(tab['n_nonfinite'].sum())}
 
     def _set_rollout_length(self):
         """algorithms/cmbpo.py:494-512"""
@@ -320,6 +362,11 @@ class CMBPO:
             real_samples, buf_diag = self._buffer.get()
             metrics.update({k + '_r': v for k, v in policy.run_diagnostics(real_samples).items()})
             metrics.update(buf_diag)
+            if self._validate_horizon > 0 and self._use_model:
+                t_val = time.perf_counter()      # a stamp of its own: 'train' keeps what it always contained
+                metrics.update(self.validate_model(epochs=[self.policy_epoch]))
+                self.times['validate_model'] = time.perf_counter() - t_val
+                t0 += self.times['validate_model']
 
             # ---- updates on real + imagined samples ------------------------------------------------------------
             if model_samples:

@@ -247,6 +247,57 @@ class CPOBuffer:
         idx = np.array([np.random.choice(np.flatnonzero(self.epoch_archive == e), size=batch_size) for e in epochs])
         return self._take(idx, fields)
 
+    # -- windows of consecutive real steps for FakeEnv.replay (open-loop model validation) --------------
+    def path_continues(self):
+        """bool [arch_size]: archive step i continues into step i + 1.  The archive stores no path boundaries, so this test
+        is the boundary: ``terminals[i]`` is False, ``next_observations[i]`` equals ``observations[i + 1]`` in every column
+        bit for bit, i + 1 is a filled slot, and -- once the archive has wrapped -- the pair does not straddle
+        ``archive_ptr`` (the newest sample in front of it, the oldest behind it)."""
+        N = self.arch_size
+        cont = np.zeros(N, np.bool_)
+        if N > 1:
+            a = self.arch_dict
+            nxt = np.ascontiguousarray(a["next_observations"][:N - 1]).reshape(N - 1, -1).view(np.uint32)
+            obs = np.ascontiguousarray(a["observations"][1:N]).reshape(N - 1, -1).view(np.uint32)
+            cont[:N - 1] = ~a["terminals"][:N - 1] & (nxt == obs).all(axis=1)
+        if self.archive_full and 0 < self.archive_ptr <= N:
+            cont[self.archive_ptr - 1] = False
+        return cont
+
+    def windows(self, horizon, n, epochs=None, rng=None):
+        """``n`` windows of up to ``horizon`` consecutive archived steps, for ``FakeEnv.replay``.  Start indices are drawn
+        uniformly, with replacement, from the filled slots (``epochs``: only from slots tagged with one of these epochs)
+        with ``rng`` (a ``numpy.random.Generator``; None: a fresh one -- NumPy's global stream is never touched).  A window
+        runs to the end of its path (``path_continues``) or ``horizon`` steps, whichever comes first: paths shorter than the
+        horizon are kept, with their length, not discarded.
+
+        Returns ``(start, length, arrays)``: archive index [n] and number of real steps [n] of every window, and the
+        keyword arguments of ``FakeEnv.replay`` -- ``obs0`` [n, obs], ``actions`` / ``next_obs`` [H, n, .], ``rewards`` /
+        ``costs`` / ``terminals`` [H, n], ``lengths`` -- time-major; the steps behind ``length`` repeat the window's last
+        real step (padding, never compared)."""
+        H, n = int(horizon), int(n)
+        if H < 1 or n < 1:
+            raise ValueError("windows: horizon and n must be >= 1, got %d, %d" % (H, n))
+        N = self.arch_size
+        ok = np.ones(N, np.bool_)
+        if epochs is not None:
+            ok = np.isin(self.epoch_archive[:N], np.asarray(epochs).reshape(-1))
+        cand = np.flatnonzero(ok)
+        if cand.size == 0:
+            raise ValueError("windows: no archived sample%s" % ("" if epochs is None else " of epochs %r" % (list(np.ravel(epochs)),)))
+        rng = np.random.default_rng() if rng is None else rng
+        start = cand[rng.integers(0, cand.size, size=n)]
+        ends = np.flatnonzero(~self.path_continues())            # the last step of every path (slot N - 1 is always one)
+        remaining = ends[np.searchsorted(ends, start)] - start + 1
+        length = np.minimum(H, remaining).astype(np.int32)
+        idx = start[None, :] + np.minimum(np.arange(H)[:, None], length[None, :] - 1)
+        a = self.arch_dict
+        flat = lambda x: x.reshape(x.shape[:2] + (-1,))
+        arrays = dict(obs0=a["observations"][start].reshape(n, -1), actions=flat(a["actions"][idx]),
+                      next_obs=flat(a["next_observations"][idx]), rewards=a["rewards"][idx], costs=a["costs"][idx],
+                      terminals=a["terminals"][idx], lengths=length)
+        return start, length, arrays
+
     # -- device mirror of the archive and start-state sampling on it (csrc/start_states.hip, DESIGN §3f) ------------
     _MIRRORED = ("observations", "mu", "log_std", "epochs")
 

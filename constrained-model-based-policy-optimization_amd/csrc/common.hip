@@ -21,7 +21,8 @@ extern "C" const char *cmbpo_last_error(void) { return g_err; }
 
 // 2: cmbpo_fakeenv_post_noise, cmbpo_rollout_t.xi / xi_stride; 3: cmbpo_train_extras_t, cmbpo_trainer_{step,epoch,losses}_ex
 // (4: cmbpo_iv_gae_t;) 5: cmbpo_fakeenv_post_disagreement, cmbpo_disagreement_t, CMBPO_D_TOTAL_REW_VAR / _COST_VAR
-extern "C" int cmbpo_version(void) { return 5; }
+// 6: cmbpo_replay_t, cmbpo_replay_{parts,compare,finish,run}
+extern "C" int cmbpo_version(void) { return 6; }
 
 namespace {
 constexpr int kMaxDevices = 64;

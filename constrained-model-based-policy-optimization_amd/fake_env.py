@@ -28,6 +28,9 @@ prediction, not thresholded.
 ``cost_pessimism > 0`` needs ``predicts_cost``: a static cost rule has no member spread.  Off (the default) the calls made
 and the keys returned are what they were.
 
+``replay(...)`` has no counterpart in the reference: it replays windows of real steps through the model with the recorded
+actions and returns, per horizon, how far the predictions are from the recording (open-loop model validation).
+
 ``task`` is a built-in task name, a name given to ``statics.register_task``, or a ``statics.TaskRules`` (user-defined
 termination / cost rules, evaluated by the same kernel); any other name is the default task, as in the reference.
 """
@@ -66,6 +69,8 @@ class FakeEnv:
         if self._predicts_cost:
             self._task_id |= _lib.TASK_LEARNED_COST
         self._rng = np.random.default_rng(seed)
+        # the elite draws of replay(): a stream of its own, so that a run that validates is in all else the run that does not
+        self._replay_rng = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(1,)))
         self._disagreement = bool(disagreement)
         self.rew_pessimism = self.cost_pessimism = 0.0
         self.set_pessimism(rew_pessimism, cost_pessimism)
@@ -207,6 +212,54 @@ class FakeEnv:
                 rv, cv = rv.cpu().numpy(), cv.cpu().numpy()
             info["ensemble_rew_var"], info["ensemble_cost_var"] = rv, cv
         return next_obs, r, terms, info
+
+    def replay(self, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, model_inds=None, mode='open_loop'):
+        """Open-loop model validation: replay B windows of up to H consecutive REAL steps through the model and hold its
+        predictions against the recording, horizon by horizon (``cmbpo_replay_run``).
+
+        obs0 [B, obs] is each window's first real observation; actions [H, B, act], next_obs [H, B, obs], rewards / costs /
+        terminals [H, B] are the recorded steps, time-major (NumPy arrays or CUDA tensors; ``CPOBuffer.windows`` gathers
+        them); lengths [B] in 1..H is the number of real steps of each window (None: H), the steps behind it are padding.
+        ``mode='open_loop'`` feeds the model its own prediction, a window ends with its length, at a recorded terminal or at
+        a predicted termination; ``mode='one_step'`` feeds it the real next observation (teacher-forced), a predicted
+        termination is counted and does not end the window.  A window whose prediction is not finite counts in
+        ``n_nonfinite`` at that horizon, ends, and enters no sum.
+
+        model_inds: None -- one elite per window and step, drawn from a generator this method owns (nothing is consumed from
+        ``np.random``, torch's generators or ``random_inds``' generator); an int -- every window through that member; an
+        [H, B] array.
+
+        A replay always measures the UNPENALISED means: it runs ``cmbpo_ens_forward`` and the plain ``cmbpo_fakeenv_post``,
+        never the noise or disagreement entries, whatever ``disagreement`` / ``rew_pessimism`` / ``cost_pessimism`` are.
+
+        Returns a dict of NumPy arrays, one row per horizon h = 0..H-1: ``n`` (windows compared), ``n_nonfinite``,
+        ``mse_obs`` [H, obs], ``mse_rew``, ``mse_cost``, ``cost_cm`` / ``term_cm`` [H, 2, 2] indexed [real, predicted] (a
+        real cost is ``cost > 0``, a predicted one ``cost > 0.5``), ``ep_var_mean`` and ``dkl_mean`` (the means of the step's
+        ``ep_var_mean`` / ``dkl_path`` over the same windows), and the float64 sums they were divided from: ``se_obs``,
+        ``se_rew``, ``se_cost``, ``sum_ep_var``, ``sum_dkl``.  A horizon with ``n == 0`` has NaN means and zero counts."""
+        from .replay import ReplayBuffers
+        E = self._model.num_nets
+        with torch.cuda.device(self.device):
+            rb = ReplayBuffers(obs0, actions, next_obs, rewards, costs, terminals, lengths=lengths, mode=mode, ensemble=E,
+                               out_dim=self.output_dim, device=self.device)
+            if (rb.obs_dim, rb.act_dim) != (self.obs_dim, self.act_dim):
+                raise ValueError("replay: windows of width (%d, %d), the model's is (%d, %d)"
+                                 % (rb.obs_dim, rb.act_dim, self.obs_dim, self.act_dim))
+            H, B = rb.H, rb.B
+            if model_inds is None:
+                elites = np.asarray(self._model.elite_inds, dtype=np.int32)
+                inds = elites[self._replay_rng.integers(0, len(elites), size=(H, B))]
+            elif isinstance(model_inds, torch.Tensor):
+                inds = model_inds.detach().cpu().numpy()
+            elif np.ndim(model_inds) == 0:
+                inds = np.full((H, B), int(model_inds))
+            else:
+                inds = np.asarray(model_inds)
+            if inds.shape != (H, B) or inds.min() < 0 or inds.max() >= E:
+                raise ValueError("replay: model_inds must be an int or an [%d, %d] array of members in 0..%d" % (H, B, E - 1))
+            elite = torch.from_numpy(np.ascontiguousarray(inds, dtype=np.int32)).to(self.device)
+            rb.run(self._model.mlp.handle, self._task_id, E, elite)
+            return rb.table()
 
     def close(self):
         pass

@@ -740,6 +740,70 @@ int cmbpo_start_boltz_draw(const int32_t *d_table, const double *d_cdf, const do
                            const float *d_obs, long n, int obs_dim, int32_t *d_idx, float *d_out,
                            void *stream);
 
+/* ---- open-loop model validation: k-step replay of real trajectories (csrc/replay.hip) -----
+ * The reference has no such diagnostic.  A replay takes B windows of up to H consecutive REAL steps (time-major arrays, step h
+ * of window b at [h][b]), starts the model at each window's first real observation (cur_obs, alive = 1 on entry) and applies
+ * the recorded actions; at every horizon h the prediction of cmbpo_ens_forward + the plain cmbpo_fakeenv_post from cur_obs is
+ * held against the recording.  The noise and disagreement entries are never called: a replay measures the unpenalised means.
+ *
+ * cmbpo_replay_compare, for every row alive on entry to step h, in this order:
+ *   1. a non-finite value in p_next_obs[b], p_rew[b] or p_cost[b]: the row counts in n_nonfinite[h], dies, adds nothing else;
+ *   2. otherwise it counts in n[h] and adds
+ *        se_obs[h][d] += (double)e * (double)e,  e = fl32(p_next_obs[b][d] - next_obs[h][b][d]);  se_rew, se_cost likewise;
+ *        cost_cm[h][cost[h][b] > 0][p_cost[b] > 0.5] += 1;   term_cm[h][term[h][b] != 0][p_term[b] != 0] += 1;
+ *        sum_ep_var[h] += (double)p_ep_var_mean[b];   sum_dkl[h] += (double)p_dkl_path[b];
+ *   3. it lives on to h + 1 iff h + 1 < len[b], term[h][b] == 0 and (CMBPO_REPLAY_OPEN_LOOP only) p_term[b] == 0; then
+ *        cur_obs[b] = p_next_obs[b] (CMBPO_REPLAY_OPEN_LOOP) or next_obs[h][b] (CMBPO_REPLAY_ONE_STEP: teacher-forced; a
+ *        predicted termination is counted and does not end the window); otherwise alive[b] = 0;
+ *   4. a dead row is frozen: its cur_obs is not written (neither by the step at which it dies), nothing of it is read.
+ * Sums are float64, counts int64: per-workgroup partials (slot = workgroup, cmbpo_replay_parts(B) slots per horizon) written by
+ * cmbpo_replay_compare, added in slot order by cmbpo_replay_finish; no floating-point atomics, two runs are bitwise equal.
+ *   sums   [H][obs_dim + 4]: se_obs[0 .. obs_dim) | se_rew | se_cost | sum_ep_var | sum_dkl
+ *   counts [H][10]:          n | n_nonfinite | cost_cm[0][0], [0][1], [1][0], [1][1] ([real][pred]) | term_cm likewise
+ * A horizon no compare call was made for holds whatever the partials held.  len is not checked (1 <= len[b] <= H). */
+#define CMBPO_REPLAY_OPEN_LOOP 0
+#define CMBPO_REPLAY_ONE_STEP 1
+#define CMBPO_REPLAY_SCALAR_SUMS 4
+#define CMBPO_REPLAY_COUNTS 10
+
+typedef struct cmbpo_replay {
+  int32_t B, H, obs_dim, act_dim, mode, reserved;
+  /* recorded, time-major */
+  const float *act;         /* [H,B,act]   (cmbpo_replay_run only)              */
+  const float *next_obs;    /* [H,B,obs]                                        */
+  const float *rew, *cost;  /* [H,B]                                            */
+  const uint8_t *term;      /* [H,B]                                            */
+  const int32_t *len;       /* [B] real steps of the window, 1 .. H             */
+  /* state */
+  float *cur_obs;           /* [B,obs] the observation step h starts from       */
+  uint8_t *alive;           /* [B]                                              */
+  /* cmbpo_fakeenv_post's outputs for the step, slot indexed */
+  float *p_next_obs;        /* [B,obs]                                          */
+  float *p_rew;             /* [B]                                              */
+  uint8_t *p_term;          /* [B]                                              */
+  float *p_cost, *p_dkl_path, *p_ep_var_mean; /* [B]                            */
+  float *mean, *var;        /* [E,B,model out_dim] scratch of the forward (cmbpo_replay_run only) */
+  /* partial sums and the result table */
+  double *part_sum;         /* [H][cmbpo_replay_parts(B)][obs + 4]              */
+  int64_t *part_cnt;        /* [H][cmbpo_replay_parts(B)][10]                   */
+  double *sums;             /* [H][obs + 4]                                     */
+  int64_t *counts;          /* [H][10]                                          */
+} cmbpo_replay_t; /* 184 bytes */
+
+/* Every entry: CMBPO_EINVAL with a message naming the entry point for B < 1, H < 1, bad dims, an unknown mode, a NULL array it
+ * uses, h outside [0, H) -- all before any HIP call. */
+/* partial-sum slots per horizon of a replay of n_rows windows (0 for n_rows < 1) */
+int cmbpo_replay_parts(int n_rows);
+/* one horizon step of comparison and advance on the prediction arrays in *rp */
+int cmbpo_replay_compare(const cmbpo_replay_t *rp, int h, void *stream);
+/* partials -> sums / counts, all H horizons */
+int cmbpo_replay_finish(const cmbpo_replay_t *rp, void *stream);
+/* H x (cmbpo_ens_forward on all B rows -> cmbpo_fakeenv_post -> cmbpo_replay_compare), then cmbpo_replay_finish, enqueued
+ * without a host wait; bitwise the result of the same calls issued one at a time.  d_elite is [H][B]: the member of window b
+ * at step h.  `task` as for cmbpo_fakeenv_post; the two callees' own refusals are passed on under this entry point's name. */
+int cmbpo_replay_run(const cmbpo_replay_t *rp, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif
