@@ -2,12 +2,24 @@
 #pragma once
 #include "common.h"
 
-int cmbpo_internal_book_post_mirror(const cmbpo_rollout_t *r, int n_alive, uint32_t *d_host_out, uint32_t seq, int spec, int min_alive,
-                                    double stop_total, void *stream);
+// what is attached beside *r (cmbpo_rollout_iv_attach / cmbpo_rollout_disagreement_attach); a feature that is not: all-zero
+struct RolloutSide {
+  cmbpo_iv_gae_t iv;
+  cmbpo_disagreement_t dg;
+};
+RolloutSide cmbpo_internal_side_lookup(const cmbpo_rollout_t *r);
+
+// One host launcher per bookkeeping kernel: the public entry of the same name calls it with the side state it looked up, the
+// one-call step with the one it looked up for the whole step.  `who` names the entry point in the messages.
+// with_stats == 0: without the statistics launch -- finish(POST) with fold_stats == 1 folds the step's sums instead
+int cmbpo_internal_store(const cmbpo_rollout_t *r, const RolloutSide &sd, int with_stats, const char *who, void *stream);
+int cmbpo_internal_finish(const cmbpo_rollout_t *r, const RolloutSide &sd, int mode, int fold_stats, const char *who, void *stream);
+// spec: the step was enqueued ahead of the previous step's counters (n_alive is an upper bound then).  with_vec == 0: the vector
+// half of the store rides in the critics' launch (CmbpoStoreVec) instead of store_vec_kernel.
+int cmbpo_internal_book_pre(const cmbpo_rollout_t *r, const RolloutSide &sd, int n_alive, int spec, int with_vec, const char *who,
+                            void *stream);
+// d_host_out != NULL: the counters mirrored into host-mapped memory (device address of 128 dwords) and `seq` behind them
+int cmbpo_internal_book_post(const cmbpo_rollout_t *r, const RolloutSide &sd, int n_alive, uint32_t *d_host_out, uint32_t seq, int spec,
+                             int min_alive, double stop_total, const char *who, void *stream);
 int cmbpo_internal_scalars_mirror(const cmbpo_rollout_t *r, uint32_t *d_host_out, uint32_t seq, void *stream);
-int cmbpo_internal_book_pre(const cmbpo_rollout_t *r, int n_alive, int spec, int with_vec, void *stream);
-int cmbpo_internal_store_nostats(const cmbpo_rollout_t *r, void *stream);
-int cmbpo_internal_finish_post_fold(const cmbpo_rollout_t *r, void *stream);
 int cmbpo_internal_spec_words(const cmbpo_rollout_t *r, int begin, void *stream);
-// the disagreement state attached beside *r (all-zero and 0 if none): the one-call step post-processes with it
-int cmbpo_internal_disagreement_lookup(const cmbpo_rollout_t *r, cmbpo_disagreement_t *out);

@@ -1242,42 +1242,34 @@ int check_rollout(const cmbpo_rollout_t *r, const char *who) {
   return CMBPO_OK;
 }
 
-// ---- inverse-variance-weighted GAE: the state beside the struct ----------------------------------------------------------
-// cmbpo_rollout_t is frozen, so the feature's arrays travel in a table keyed by r->iscal (unique per buffer), like the rule
-// tables of task_rules.hip.  Every host entry point below that launches a store or a finish kernel looks the key up and hands
-// the entry to the kernel by value; no entry = cumvar_buf NULL = the un-weighted recurrence.
-std::mutex g_iv_mu;
-std::unordered_map<const void *, cmbpo_iv_gae_t> g_iv;
+// ---- the state beside the struct: inverse-variance-weighted GAE and ensemble disagreement -----------------------------------
+// cmbpo_rollout_t is frozen, so the features' arrays travel in ONE table keyed by r->iscal (unique per buffer), like the rule
+// tables of task_rules.hip: an entry holds both features' structs, a feature that is not attached all-zero (cumvar_buf NULL =
+// the un-weighted recurrence, part NULL = no disagreement).  A public entry point that launches a reset, store or finish kernel
+// looks the key up and hands the structs to the kernel by value; the one-call step looks it up once for all its launches.
+std::mutex g_side_mu;
+std::unordered_map<const void *, RolloutSide> g_side;
 
-cmbpo_iv_gae_t iv_lookup(const cmbpo_rollout_t *r) {
-  cmbpo_iv_gae_t iv = {};
-  std::lock_guard<std::mutex> lock(g_iv_mu);
-  if (!g_iv.empty()) {
-    const auto it = g_iv.find(r->iscal);
-    if (it != g_iv.end()) iv = it->second;
-  }
-  return iv;
-}
-
-// ---- ensemble disagreement on reward / cost: the same arrangement (part == NULL: nothing attached) ------------------------
-std::mutex g_dg_mu;
-std::unordered_map<const void *, cmbpo_disagreement_t> g_dg;
-
-cmbpo_disagreement_t dg_lookup(const cmbpo_rollout_t *r) {
-  cmbpo_disagreement_t dg = {};
-  std::lock_guard<std::mutex> lock(g_dg_mu);
-  if (!g_dg.empty()) {
-    const auto it = g_dg.find(r->iscal);
-    if (it != g_dg.end()) dg = it->second;
-  }
-  return dg;
+// attach (feature != NULL: replaces what was attached) or detach one feature; an entry with neither left is dropped
+template <typename F>
+void side_set(const cmbpo_rollout_t *r, F RolloutSide::*which, const F *feature) {
+  std::lock_guard<std::mutex> lock(g_side_mu);
+  if (feature == nullptr && g_side.find(r->iscal) == g_side.end()) return;
+  RolloutSide &sd = g_side[r->iscal];
+  sd.*which = feature ? *feature : F{};
+  if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr) g_side.erase(r->iscal);
 }
 
 }  // namespace
 
-int cmbpo_internal_disagreement_lookup(const cmbpo_rollout_t *r, cmbpo_disagreement_t *out) {
-  *out = dg_lookup(r);
-  return out->part != nullptr ? 1 : 0;
+// (r == NULL: nothing; the launcher's own check refuses it)
+RolloutSide cmbpo_internal_side_lookup(const cmbpo_rollout_t *r) {
+  RolloutSide sd = {};
+  if (r == nullptr) return sd;
+  std::lock_guard<std::mutex> lock(g_side_mu);
+  const auto it = g_side.find(r->iscal);
+  if (it != g_side.end()) sd = it->second;
+  return sd;
 }
 
 extern "C" int cmbpo_rollout_disagreement_attach(const cmbpo_rollout_t *r, const cmbpo_disagreement_t *dg) {
@@ -1289,15 +1281,13 @@ extern "C" int cmbpo_rollout_disagreement_attach(const cmbpo_rollout_t *r, const
   CMBPO_REQUIRE(dg->kappa_rew >= 0.0f && isfinite(dg->kappa_rew) && dg->kappa_cost >= 0.0f && isfinite(dg->kappa_cost),
                 "cmbpo_rollout_disagreement_attach: kappa_rew %g / kappa_cost %g: finite numbers >= 0", (double)dg->kappa_rew,
                 (double)dg->kappa_cost);
-  std::lock_guard<std::mutex> lock(g_dg_mu);
-  g_dg[r->iscal] = *dg;
+  side_set(r, &RolloutSide::dg, dg);
   return CMBPO_OK;
 }
 
 extern "C" int cmbpo_rollout_disagreement_detach(const cmbpo_rollout_t *r) {
   CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_disagreement_detach: NULL rollout struct / iscal");
-  std::lock_guard<std::mutex> lock(g_dg_mu);
-  g_dg.erase(r->iscal);
+  side_set<cmbpo_disagreement_t>(r, &RolloutSide::dg, nullptr);
   return CMBPO_OK;
 }
 
@@ -1307,15 +1297,13 @@ extern "C" int cmbpo_rollout_iv_attach(const cmbpo_rollout_t *r, const cmbpo_iv_
   CMBPO_REQUIRE(iv->cumvar_buf != nullptr, "cmbpo_rollout_iv_attach: NULL cumvar_buf (cmbpo_rollout_iv_detach switches the feature off)");
   CMBPO_REQUIRE(iv->lam_vec && iv->lam_pow && iv->clam_vec && iv->clam_pow, "cmbpo_rollout_iv_attach: NULL lambda table");
   CMBPO_REQUIRE(isfinite(iv->eps) && iv->eps > 0.0, "cmbpo_rollout_iv_attach: eps %g is not a positive finite number", iv->eps);
-  std::lock_guard<std::mutex> lock(g_iv_mu);
-  g_iv[r->iscal] = *iv;
+  side_set(r, &RolloutSide::iv, iv);
   return CMBPO_OK;
 }
 
 extern "C" int cmbpo_rollout_iv_detach(const cmbpo_rollout_t *r) {
   CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_iv_detach: NULL rollout struct / iscal");
-  std::lock_guard<std::mutex> lock(g_iv_mu);
-  g_iv.erase(r->iscal);
+  side_set<cmbpo_iv_gae_t>(r, &RolloutSide::iv, nullptr);
   return CMBPO_OK;
 }
 
@@ -1323,7 +1311,8 @@ extern "C" int cmbpo_rollout_reset(const cmbpo_rollout_t *r, void *stream) {
   if (int rc = check_rollout(r, "cmbpo_rollout_reset")) return rc;
   CMBPO_REQUIRE(r->dkl_acc && r->path_ret && r->path_cost && r->path_dyn_var, "cmbpo_rollout_reset: NULL accumulators");
   const int n = r->B > 32 ? r->B : 32;
-  hipLaunchKernelGGL(reset_kernel, dim3(cmbpo_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, *r, dg_lookup(r));
+  hipLaunchKernelGGL(reset_kernel, dim3(cmbpo_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, *r,
+                     cmbpo_internal_side_lookup(r).dg);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1349,94 +1338,72 @@ extern "C" int cmbpo_rollout_count(const cmbpo_rollout_t *r, void *stream) {
   return launch_decide(r, 1, (hipStream_t)stream);
 }
 
+// the required fields that more than one launcher below asks for
+static bool has_step_arrays(const cmbpo_rollout_t *r) {
+  return r->cur_obs && r->act_t && r->logp_t && r->mu_t && r->ls_t && r->v_t && r->vc_t && r->rew_t && r->cost_t && r->dkl_t && r->epv_t;
+}
+static bool has_sample_bufs(const cmbpo_rollout_t *r) {
+  return r->obs_buf && r->act_buf && r->mu_buf && r->ls_buf && r->rew_buf && r->val_buf && r->cost_buf && r->cval_buf && r->logp_buf;
+}
+static bool has_gae_bufs(const cmbpo_rollout_t *r) {
+  return r->rew_buf && r->val_buf && r->cost_buf && r->cval_buf && r->adv_buf && r->ret_buf && r->cadv_buf && r->cret_buf;
+}
+
+// fold_stats: the first workgroup folds the sums of a store that ran without its statistics launch (the rollout step at large
+// batches: a launch further on, nothing reads the accumulators in between)
+int cmbpo_internal_finish(const cmbpo_rollout_t *r, const RolloutSide &sd, int mode, int fold_stats, const char *who, void *stream) {
+  if (int rc = check_rollout(r, who)) return rc;
+  CMBPO_REQUIRE(mode >= 0 && mode <= 2, "%s: bad mode %d", who, mode);
+  CMBPO_REQUIRE(has_gae_bufs(r), "%s: NULL buffer", who);
+  if (mode == 1) CMBPO_REQUIRE(r->v_n && r->vc_n && r->term_t, "%s: POST needs v_n, vc_n, term_t", who);
+  else CMBPO_REQUIRE(r->v_t && r->vc_t, "%s: needs v_t, vc_t", who);
+  if (fold_stats) CMBPO_REQUIRE(r->store_part != nullptr, "%s: NULL store_part scratch", who);
+  hipLaunchKernelGGL(finish_kernel, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, mode, fold_stats, sd.iv,
+                     sd.dg);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
 extern "C" int cmbpo_rollout_finish(const cmbpo_rollout_t *r, int mode, void *stream) {
-  if (int rc = check_rollout(r, "cmbpo_rollout_finish")) return rc;
-  CMBPO_REQUIRE(mode >= 0 && mode <= 2, "cmbpo_rollout_finish: bad mode %d", mode);
-  CMBPO_REQUIRE(r->rew_buf && r->val_buf && r->cost_buf && r->cval_buf && r->adv_buf && r->ret_buf &&
-                    r->cadv_buf && r->cret_buf,
-                "cmbpo_rollout_finish: NULL buffer");
-  if (mode == 1) CMBPO_REQUIRE(r->v_n && r->vc_n && r->term_t, "cmbpo_rollout_finish: POST needs v_n, vc_n, term_t");
-  else CMBPO_REQUIRE(r->v_t && r->vc_t, "cmbpo_rollout_finish: needs v_t, vc_t");
-  hipLaunchKernelGGL(finish_kernel, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, mode, 0, iv_lookup(r), dg_lookup(r));
+  return cmbpo_internal_finish(r, cmbpo_internal_side_lookup(r), mode, 0, "cmbpo_rollout_finish", stream);
+}
+
+int cmbpo_internal_store(const cmbpo_rollout_t *r, const RolloutSide &sd, int with_stats, const char *who, void *stream) {
+  if (int rc = check_rollout(r, who)) return rc;
+  CMBPO_REQUIRE(r->ptr < r->T, "%s: buffer full (ptr %d == T)", who, r->ptr);  // modelbuffer.py:115
+  CMBPO_REQUIRE(has_step_arrays(r), "%s: NULL step array", who);
+  CMBPO_REQUIRE(has_sample_bufs(r), "%s: NULL buffer", who);
+  CMBPO_REQUIRE(r->store_part != nullptr, "%s: NULL store_part scratch", who);
+  hipLaunchKernelGGL(store_kernel, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, sd.iv, sd.dg);
+  if (with_stats) hipLaunchKernelGGL(store_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *r, sd.dg);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
 
 extern "C" int cmbpo_rollout_store(const cmbpo_rollout_t *r, void *stream) {
-  if (int rc = check_rollout(r, "cmbpo_rollout_store")) return rc;
-  CMBPO_REQUIRE(r->ptr < r->T, "cmbpo_rollout_store: buffer full (ptr %d == T)", r->ptr);  // modelbuffer.py:115
-  CMBPO_REQUIRE(r->cur_obs && r->act_t && r->logp_t && r->mu_t && r->ls_t && r->v_t && r->vc_t && r->rew_t &&
-                    r->cost_t && r->dkl_t && r->epv_t,
-                "cmbpo_rollout_store: NULL step array");
-  CMBPO_REQUIRE(r->obs_buf && r->act_buf && r->mu_buf && r->ls_buf && r->rew_buf && r->val_buf && r->cost_buf &&
-                    r->cval_buf && r->logp_buf,
-                "cmbpo_rollout_store: NULL buffer");
-  CMBPO_REQUIRE(r->store_part != nullptr, "cmbpo_rollout_store: NULL store_part scratch");
-  const cmbpo_disagreement_t dg = dg_lookup(r);
-  hipLaunchKernelGGL(store_kernel, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, iv_lookup(r), dg);
-  hipLaunchKernelGGL(store_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *r, dg);
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
-}
-
-// the rollout step at large batches: the store without its statistics launch, and the finish(POST) that folds them
-int cmbpo_internal_store_nostats(const cmbpo_rollout_t *r, void *stream) {
-  if (int rc = check_rollout(r, "cmbpo_rollout_store")) return rc;
-  CMBPO_REQUIRE(r->ptr < r->T, "cmbpo_rollout_store: buffer full (ptr %d == T)", r->ptr);
-  CMBPO_REQUIRE(r->cur_obs && r->act_t && r->logp_t && r->mu_t && r->ls_t && r->v_t && r->vc_t && r->rew_t && r->cost_t && r->dkl_t &&
-                    r->epv_t && r->obs_buf && r->act_buf && r->mu_buf && r->ls_buf && r->rew_buf && r->val_buf && r->cost_buf &&
-                    r->cval_buf && r->logp_buf && r->store_part,
-                "cmbpo_rollout_store: NULL array");
-  hipLaunchKernelGGL(store_kernel, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, iv_lookup(r),
-                     dg_lookup(r));
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
-}
-int cmbpo_internal_finish_post_fold(const cmbpo_rollout_t *r, void *stream) {
-  if (int rc = check_rollout(r, "cmbpo_rollout_finish")) return rc;
-  CMBPO_REQUIRE(r->v_n && r->vc_n && r->term_t && r->rew_buf && r->val_buf && r->cost_buf && r->cval_buf && r->adv_buf && r->ret_buf &&
-                    r->cadv_buf && r->cret_buf && r->store_part,
-                "cmbpo_rollout_finish (POST): NULL array");
-  hipLaunchKernelGGL(finish_kernel, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, 1, 1, iv_lookup(r), dg_lookup(r));
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
+  return cmbpo_internal_store(r, cmbpo_internal_side_lookup(r), 1, "cmbpo_rollout_store", stream);
 }
 
 extern "C" int cmbpo_rollout_book_pre_max_rows(void) { return kBookMax; }
 
-extern "C" int cmbpo_rollout_book_pre(const cmbpo_rollout_t *r, int n_alive, void *stream) {
-  if (int rc = check_rollout(r, "cmbpo_rollout_book_pre")) return rc;
-  CMBPO_REQUIRE(n_alive >= 0 && n_alive <= kBookMax, "cmbpo_rollout_book_pre: %d alive rows, at most %d", n_alive, kBookMax);
-  CMBPO_REQUIRE(!r->use_host_budget, "cmbpo_rollout_book_pre: the cross-shard budget exchange uses the separate kernels");
-  CMBPO_REQUIRE(r->ptr < r->T, "cmbpo_rollout_book_pre: buffer full (ptr %d == T)", r->ptr);
-  CMBPO_REQUIRE(r->dkl_t && r->dkl_acc && r->cur_obs && r->act_t && r->logp_t && r->mu_t && r->ls_t && r->v_t && r->vc_t &&
-                    r->rew_t && r->cost_t && r->epv_t,
-                "cmbpo_rollout_book_pre: NULL step array");
-  CMBPO_REQUIRE(r->obs_buf && r->act_buf && r->mu_buf && r->ls_buf && r->rew_buf && r->val_buf && r->cost_buf && r->cval_buf &&
-                    r->logp_buf && r->adv_buf && r->ret_buf && r->cadv_buf && r->cret_buf,
-                "cmbpo_rollout_book_pre: NULL buffer");
+int cmbpo_internal_book_pre(const cmbpo_rollout_t *r, const RolloutSide &sd, int n_alive, int spec, int with_vec, const char *who,
+                            void *stream) {
+  if (int rc = check_rollout(r, who)) return rc;
+  CMBPO_REQUIRE(n_alive >= 0 && n_alive <= kBookMax, "%s: %d alive rows, at most %d", who, n_alive, kBookMax);
+  CMBPO_REQUIRE(!r->use_host_budget, "%s: the cross-shard budget exchange uses the separate kernels", who);
+  CMBPO_REQUIRE(r->ptr < r->T, "%s: buffer full (ptr %d == T)", who, r->ptr);
+  CMBPO_REQUIRE(has_step_arrays(r) && r->dkl_acc, "%s: NULL step array", who);
+  CMBPO_REQUIRE(has_sample_bufs(r) && has_gae_bufs(r), "%s: NULL buffer", who);
   if (n_alive == 0) return CMBPO_OK;
-  hipLaunchKernelGGL(book_pre_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, 0, iv_lookup(r), dg_lookup(r));
-  hipLaunchKernelGGL(store_vec_kernel, dim3(cmbpo_ceil_div(n_alive, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, 0);
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
-}
-
-// the same inside cmbpo_rollout_step / _run.  spec: the step was enqueued ahead of the previous step's counters (n_alive is an
-// upper bound then).  with_vec == 0: the vector half of the store rides in the critics' launch (CmbpoStoreVec) instead of
-// store_vec_kernel.
-int cmbpo_internal_book_pre(const cmbpo_rollout_t *r, int n_alive, int spec, int with_vec, void *stream) {
-  if (int rc = check_rollout(r, "cmbpo_rollout_book_pre")) return rc;
-  CMBPO_REQUIRE(n_alive >= 1 && n_alive <= kBookMax && !r->use_host_budget && r->ptr < r->T, "book_pre (step): bad state");
-  CMBPO_REQUIRE(r->dkl_t && r->dkl_acc && r->cur_obs && r->act_t && r->logp_t && r->mu_t && r->ls_t && r->v_t && r->vc_t && r->rew_t &&
-                    r->cost_t && r->epv_t && r->obs_buf && r->act_buf && r->mu_buf && r->ls_buf && r->rew_buf && r->val_buf &&
-                    r->cost_buf && r->cval_buf && r->logp_buf && r->adv_buf && r->ret_buf && r->cadv_buf && r->cret_buf,
-                "cmbpo_rollout_book_pre: NULL array");
-  hipLaunchKernelGGL(book_pre_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, spec, iv_lookup(r), dg_lookup(r));
+  hipLaunchKernelGGL(book_pre_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, spec, sd.iv, sd.dg);
   if (with_vec)
     hipLaunchKernelGGL(store_vec_kernel, dim3(cmbpo_ceil_div(n_alive, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, spec);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
+}
+
+extern "C" int cmbpo_rollout_book_pre(const cmbpo_rollout_t *r, int n_alive, void *stream) {
+  return cmbpo_internal_book_pre(r, cmbpo_internal_side_lookup(r), n_alive, 0, 1, "cmbpo_rollout_book_pre", stream);
 }
 
 // look-ahead bookkeeping of cmbpo_rollout_run: begin = no halt, the forward kernels' row count = the alive count; end = no halt
@@ -1451,16 +1418,23 @@ int cmbpo_internal_spec_words(const cmbpo_rollout_t *r, int begin, void *stream)
   return CMBPO_OK;
 }
 
-extern "C" int cmbpo_rollout_book_post(const cmbpo_rollout_t *r, int n_alive, void *stream) {
-  if (int rc = check_rollout(r, "cmbpo_rollout_book_post")) return rc;
-  CMBPO_REQUIRE(n_alive >= 0 && n_alive <= kBookMax, "cmbpo_rollout_book_post: %d alive rows, at most %d", n_alive, kBookMax);
-  CMBPO_REQUIRE(r->v_n && r->vc_n && r->term_t && r->rew_buf && r->val_buf && r->cost_buf && r->cval_buf && r->adv_buf &&
-                    r->ret_buf && r->cadv_buf && r->cret_buf,
-                "cmbpo_rollout_book_post: NULL array");
-  hipLaunchKernelGGL(book_post_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, (uint32_t *)nullptr, 0u, 0, 0, 0.0,
-                     iv_lookup(r));
+// spec, min_alive, stop_total: see book_post_kernel
+int cmbpo_internal_book_post(const cmbpo_rollout_t *r, const RolloutSide &sd, int n_alive, uint32_t *d_host_out, uint32_t seq, int spec,
+                             int min_alive, double stop_total, const char *who, void *stream) {
+  if (int rc = check_rollout(r, who)) return rc;
+  CMBPO_REQUIRE(n_alive >= 0 && n_alive <= kBookMax, "%s: %d alive rows, at most %d", who, n_alive, kBookMax);
+  CMBPO_REQUIRE(r->v_n && r->vc_n && r->term_t && has_gae_bufs(r), "%s: NULL array", who);
+  if (d_host_out)
+    CMBPO_REQUIRE(reinterpret_cast<const char *>(r->dscal) == reinterpret_cast<const char *>(r->iscal) + 128,
+                  "%s: iscal[32] and dscal[32] must be one 384-byte block", who);
+  hipLaunchKernelGGL(book_post_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, d_host_out, seq, spec, min_alive,
+                     stop_total, sd.iv);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
+}
+
+extern "C" int cmbpo_rollout_book_post(const cmbpo_rollout_t *r, int n_alive, void *stream) {
+  return cmbpo_internal_book_post(r, cmbpo_internal_side_lookup(r), n_alive, nullptr, 0u, 0, 0, 0.0, "cmbpo_rollout_book_post", stream);
 }
 
 // the counters into the host mirror behind whatever ran before on the stream (large batches: the step ends with multi-workgroup
@@ -1481,23 +1455,6 @@ int cmbpo_internal_scalars_mirror(const cmbpo_rollout_t *r, uint32_t *d_host_out
   CMBPO_REQUIRE(reinterpret_cast<const char *>(r->dscal) == reinterpret_cast<const char *>(r->iscal) + 128,
                 "scalars mirror: iscal[32] and dscal[32] must be one 384-byte block");
   hipLaunchKernelGGL(scalars_mirror_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, *r, d_host_out, seq);
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
-}
-
-// the same with the counters mirrored into host-mapped memory (d_host_out: device address of 128 dwords) and `seq` behind them
-// spec: see book_post_kernel
-int cmbpo_internal_book_post_mirror(const cmbpo_rollout_t *r, int n_alive, uint32_t *d_host_out, uint32_t seq, int spec, int min_alive,
-                                    double stop_total, void *stream) {
-  if (int rc = check_rollout(r, "cmbpo_rollout_book_post")) return rc;
-  CMBPO_REQUIRE(n_alive >= 0 && n_alive <= kBookMax, "cmbpo_rollout_book_post: %d alive rows, at most %d", n_alive, kBookMax);
-  CMBPO_REQUIRE(r->v_n && r->vc_n && r->term_t && r->rew_buf && r->val_buf && r->cost_buf && r->cval_buf && r->adv_buf &&
-                    r->ret_buf && r->cadv_buf && r->cret_buf,
-                "cmbpo_rollout_book_post: NULL array");
-  CMBPO_REQUIRE(reinterpret_cast<const char *>(r->dscal) == reinterpret_cast<const char *>(r->iscal) + 128,
-                "cmbpo_rollout_book_post: iscal[32] and dscal[32] must be one 384-byte block");
-  hipLaunchKernelGGL(book_post_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, d_host_out, seq, spec, min_alive,
-                     stop_total, iv_lookup(r));
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }

@@ -53,9 +53,11 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   if ((rc = cmbpo_ens_forward(model, r->cur_obs, r->obs_dim, r->act_t, r->act_dim, r->alive_idx, d_n, n_alive, r->B,
                               d_mean, d_var, stream)))
     return rc;
-  // ensemble disagreement attached beside *r: its instance of the post kernel, penalised rew_t / cost_t (d_xi may be NULL)
-  cmbpo_disagreement_t dg;
-  if (cmbpo_internal_disagreement_lookup(r, &dg)) {
+  // what is attached beside *r, looked up once for every launch of the step
+  const RolloutSide sd = cmbpo_internal_side_lookup(r);
+  const cmbpo_disagreement_t &dg = sd.dg;
+  // ensemble disagreement: its instance of the post kernel, penalised rew_t / cost_t (d_xi may be NULL)
+  if (dg.part != nullptr) {
     if ((rc = cmbpo_fakeenv_post_disagreement(task, ensemble, r->obs_dim, r->act_dim, d_mean, d_var, r->B, r->cur_obs, r->act_t, d_elite,
                                               r->alive_idx, d_n, n_alive, w(r->next_obs), w(r->rew_t), const_cast<uint8_t *>(r->term_t),
                                               w(r->cost_t), w(r->dkl_t), w(r->epv_t), nullptr, d_xi, dg.kappa_rew, dg.kappa_cost,
@@ -72,7 +74,7 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   // in the critics' launch below where that is the one-wave-per-member kernel (8 us as a launch of its own at 1000 rows)
   const bool vec_rides = small && cmbpo_critic_pair_supported(v, vc) && n_alive < kCriticBigMin;
   if (small) {
-    if ((rc = cmbpo_internal_book_pre(r, n_alive, ahead.on ? 1 : 0, vec_rides ? 0 : 1, stream))) return rc;
+    if ((rc = cmbpo_internal_book_pre(r, sd, n_alive, ahead.on ? 1 : 0, vec_rides ? 0 : 1, "cmbpo_rollout_book_pre", stream))) return rc;
   } else {
     // large batches.  No branch can finish before the store unless the uncertainty test or a sample budget is on; the step's
     // sums are folded by the first workgroup of finish(POST) below instead of a launch of their own (nothing reads the
@@ -80,8 +82,8 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
     const bool fold_late = !r->use_host_budget;
     if ((rc = cmbpo_rollout_decide(r, stream))) return rc;
     if (r->uncertainty_mode || r->max_samples != 0 || r->use_host_budget)
-      if ((rc = cmbpo_rollout_finish(r, 0, stream))) return rc;
-    if ((rc = fold_late ? cmbpo_internal_store_nostats(r, stream) : cmbpo_rollout_store(r, stream))) return rc;
+      if ((rc = cmbpo_internal_finish(r, sd, 0, 0, "cmbpo_rollout_finish", stream))) return rc;
+    if ((rc = cmbpo_internal_store(r, sd, fold_late ? 0 : 1, "cmbpo_rollout_store", stream))) return rc;
   }
   if (cmbpo_critic_pair_supported(v, vc)) {      // both critics in one launch (csrc/critic_f16.hip)
     // ... and, where it fits, the actor for the next step as one more wave per tile: both read next_obs, the store above has
@@ -108,13 +110,12 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   }
   if (small) {
     // finish(POST) + compaction in one launch (with the step's counters mirrored to the host, if asked)
-    if ((rc = d_mirror ? cmbpo_internal_book_post_mirror(r, n_alive, d_mirror, seq, ahead.on ? 1 : 0, ahead.min_alive, ahead.stop_total,
-                                                         stream)
-                       : cmbpo_rollout_book_post(r, n_alive, stream)))
+    if ((rc = cmbpo_internal_book_post(r, sd, n_alive, d_mirror, seq, ahead.on ? 1 : 0, ahead.min_alive, ahead.stop_total,
+                                       "cmbpo_rollout_book_post", stream)))
       return rc;
     return 1;                                                              // the alive list has been rebuilt: swap it
   }
-  return r->use_host_budget ? cmbpo_rollout_finish(r, 1, stream) : cmbpo_internal_finish_post_fold(r, stream);
+  return cmbpo_internal_finish(r, sd, 1, r->use_host_budget ? 0 : 1, "cmbpo_rollout_finish", stream);
 }
 
 extern "C" int cmbpo_rollout_step(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy, cmbpo_mlp_t *model,

@@ -56,6 +56,8 @@ class ModelSampler:
         self._calib_total_dkl = 0.0
         self._calib_total_samples = 0.0
         self._diag = None
+        self.global_alive = 1                       # alive branches over all shards (sharded samplers), see reset()
+        self._global_total_samples = 0.0
 
     # -- wiring -----------------------------------------------------------------------------------
     def initialize(self, env, policy, pool):
@@ -63,8 +65,11 @@ class ModelSampler:
         self.device = pool.device
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(self._seed)
-        self._elites = None
-        self._handles = None
+        # everything bound to the device starts over
+        self._elites = self._elites_host = None     # the model's elite indices on the device / as last uploaded
+        self._draws = None                          # chunk of draws, see _draw_chunk()
+        self._scratch = self._handles = None        # see _prepare_call()
+        self._run_host = self._run_out = None       # sample_many(): pinned counters of a call's steps, its three out-words
 
     def set_policy(self, policy):
         self.policy = policy
@@ -100,7 +105,7 @@ class ModelSampler:
         """`_total_samples` summed over the shards (== `_total_samples` on one GPU): what a stop rule on the job's sample
         count has to read (algorithms/cmbpo.py:356-357)."""
         if self.comm is not None and self.comm.world > 1:
-            return getattr(self, "_global_total_samples", 0.0)
+            return self._global_total_samples
         return self._host["total_samples"]
 
     @property
@@ -195,7 +200,7 @@ class ModelSampler:
         self.n_budget_terminated = 0     # branches the `max_samples` rule ended early (model_sampler.py:282-287), this shard
         self._host = dict(total_samples=0.0, total_dkl=0.0)
         elites = np.asarray(self.env._model.elite_inds, dtype=np.int32)
-        if getattr(self, "_elites_host", None) is None or not np.array_equal(self._elites_host, elites):
+        if self._elites_host is None or not np.array_equal(self._elites_host, elites):
             # (uploaded again only when the elites changed: a host-to-device copy per reset otherwise)
             self._elites_host = elites.copy()
             self._elites = torch.as_tensor(elites, device=self.device)
@@ -218,112 +223,76 @@ class ModelSampler:
         xi ([n, obs_dim], the same order) the transition noise: next_obs = mean + std * xi + obs.  Without it a
         `stochastic` sampler draws its own, any other sampler steps to the elite member's mean.
         """
-        pool, env, pol = self.pool, self.env, self.policy
+        pool = self.pool
         assert pool.has_room                       # pool full! empty before sampling.
         sharded = self.comm is not None and self.comm.world > 1
         if sharded and pool.n_alive == 0:
             # this shard has nothing left but the others may: keep the collectives of the step matched
             return self._idle_step(max_samples)
         assert pool.n_alive > 0                    # reset before sampling !
-        if not sharded and eps is None and model_inds is None and xi is None and env.kernel_events is None:
-            if torch.cuda.current_device() != self.device.index:
-                with torch.cuda.device(self.device):
-                    return self._sample_fast(max_samples)
-            return self._sample_fast(max_samples)
+        if torch.cuda.current_device() != self.device.index:
+            with torch.cuda.device(self.device):
+                return self._step(sharded, max_samples, eps, model_inds, xi)
+        return self._step(sharded, max_samples, eps, model_inds, xi)
+
+    def _step(self, sharded, max_samples, eps, model_inds, xi):
+        """sample() on the sampler's device.  On one rank with the sampler's own draws the whole step is ONE C call
+        (cmbpo_rollout_step) plus the read of the step's counters -- at the shipped configurations' 1e3 - 1e4 branches a step
+        is ~100 us of kernels, so the host side of that case is kept to pointer arithmetic."""
+        pool, env, pol = self.pool, self.env, self.policy
         self._n_episodes += 1
         t, rs = pool.t, pool.rs
-        n, B, A = pool.n_alive, self.batch_size, pool.act_dim
-        with torch.cuda.device(self.device):
-            idx = t["alive_idx"]
-            if eps is None or model_inds is None or (xi is None and self.stochastic):
-                # action noise and elite picks are drawn for several steps at a time (three torch launches per chunk
-                # instead of per step: at small rollout batches a step is a chain of launch latencies)
-                ck = getattr(self, "_draws", None)
-                if ck is None or ck[0] >= ck[1].shape[0] or ck[1].shape[1] != B or (ck[3] is None) == self.stochastic:
-                    ck = self._draw_chunk()
-                k = ck[0]
-                ck[0] = k + 1
-            if eps is None:
-                eps_t = ck[1][k]
-            else:
-                eps_t = self._scatter(eps, idx[:n], A)
-            if model_inds is None:
-                inds_t = ck[2][k]
-            else:
-                inds_t = self._scatter(model_inds, idx[:n], None, torch.int32)
+        n = pool.n_alive
+        h = self._prepare_call(max_samples)
+        exchange = sharded and rs.max_samples != 0      # the reference's `if max_samples:` (negative budgets count)
+        separate = exchange or env.kernel_events is not None
+        if eps is None or model_inds is None or (xi is None and self.stochastic):
+            ck, k, eps_ptr, inds_ptr, xi_ptr = self._next_draws()
+            ck[0] = k + 1
+        if separate or eps is not None or model_inds is not None or xi is not None:
+            # injected draws are scattered to slot order; the separate entries below take tensors
+            idx = t["alive_idx"][:n]
+            eps_t = ck[1][k] if eps is None else self._scatter(eps, idx, pool.act_dim)
+            inds_t = ck[2][k] if model_inds is None else self._scatter(model_inds, idx, None, torch.int32)
             if xi is not None:
-                xi_t = self._scatter(xi, idx[:n], pool.obs_dim)
+                xi_t = self._scatter(xi, idx, pool.obs_dim)
             else:
                 xi_t = ck[3][k] if self.stochastic else None
-            rs.xi = None if xi_t is None else xi_t.data_ptr()
-            if getattr(self, "_scratch", None) is None or self._scratch[0].shape[1] != B:
-                E, O = env._model.num_nets, env.output_dim
-                self._scratch = (torch.empty((E, B, O), dtype=torch.float32, device=self.device),
-                                 torch.empty((E, B, O), dtype=torch.float32, device=self.device))
-            rs.max_samples = int(max_samples) if max_samples else 0
-            rs.dkl_lim = float(self.dkl_lim)
-            rs.max_path_length = self._max_path_length
-            rs.use_host_budget = 0
-            exchange = sharded and rs.max_samples != 0      # the reference's `if max_samples:` (negative budgets count)
-            compacted = False
-            if not exchange and env.kernel_events is None:
-                # the whole step in one call: at small rollout batches a step is bound by host latency
-                rc = _lib.lib().cmbpo_rollout_step(
-                    C.byref(rs), n, pol.actor.mlp.handle, env._model.mlp.handle, pol.v.mlp.handle, pol.vc.mlp.handle,
-                    env._task_id, env._model.num_nets, eps_t.data_ptr(), inds_t.data_ptr(),
-                    self._scratch[0].data_ptr(), self._scratch[1].data_ptr(), _lib.current_stream())
-                if rc == 1:         # small batch: finish(POST) and the compaction ran inside the call
-                    compacted = True
-                else:
-                    _lib.check(rc, "cmbpo_rollout_step")
-            else:
-                # policy: pi, logp, mu, log_std at the current observations
-                pol.actor.forward_device(t["cur_obs"], eps_t,
-                                         dict(pi=t["act_t"], logp_pi=t["logp_t"], mu=t["mu_t"], log_std=t["ls_t"]),
-                                         row_idx=idx, n_rows=n)
-                # dynamics ensemble + FakeEnv post-processing
-                outs = dict(next_obs=t["next_obs"], rew=t["rew_t"], term=t["term_t"], cost=t["cost_t"],
-                            dkl_path=t["dkl_t"], ep_var_mean=t["epv_t"])
-                if pool.disagreement:       # (the arrays attached beside the struct: the store below reads them)
-                    outs.update(rew_var=t["rew_var_t"], cost_var=t["cost_var_t"])
-                env.step_device(t["cur_obs"], t["act_t"], inds_t, outs,
-                                row_idx=idx, n_rows=n, scratch=self._scratch, noise=xi_t)
-                if exchange:
-                    # budget rule across shards: gather {n_alive, n_unc, total}, rank the survivors globally
-                    pool._call("cmbpo_rollout_count")
-                    rows = self.comm.all_gather_i32(t["iscal"][8:12]).cpu().numpy()
-                    excess, rank_off = budget_plan(rows, self.comm.rank, rs.max_samples)
-                    rs.use_host_budget, rs.host_excess, rs.host_rank_off = 1, int(excess), int(rank_off)
-                pool._call("cmbpo_rollout_decide")
-                pool._call("cmbpo_rollout_finish", 0)
-                pool._call("cmbpo_rollout_store")
-                self._critics("next_obs", "v_n", "vc_n", n)
-                pool._call("cmbpo_rollout_finish", 1)
-            # the host sync of the step: counters of what finished / was stored + the accumulators
-            isc, dsc = self._read_scalars()
-            self.n_budget_terminated += int(isc[_lib.I_N_FIN_PRE]) - int(isc[_lib.I_N_UNC])
-            if compacted:
-                pool.swap("alive_idx", "alive_idx_out")
-            elif int(isc[_lib.I_N_FIN_PRE]) + int(isc[_lib.I_N_FIN_POST]) > 0:
-                pool._call("cmbpo_rollout_compact")      # the alive list only changes when a branch finished
-                pool.swap("alive_idx", "alive_idx_out")
-                # the survivors' count follows from the counters just read: no second host synchronisation
-                pool._n_alive = n - int(isc[_lib.I_N_FIN_PRE]) - int(isc[_lib.I_N_FIN_POST])
-            pool.swap("cur_obs", "next_obs")
-            pool.swap("v_t", "v_n")
-            pool.swap("vc_t", "vc_n")
-            pool.ptr += 1
-            rs.ptr = pool.ptr
-        self._host["total_samples"] = float(dsc[_lib.D_TOTAL_SAMPLES])
-        self._host["total_dkl"] = float(dsc[_lib.D_TOTAL_DKL])
-        alive = pool.n_alive
-        if self.comm is not None and self.comm.world > 1:
-            g = self.comm.all_reduce_host([alive, self.batch_size, self._host["total_samples"]])
-            alive_ratio, self._global_total_samples = g[0] / g[1], g[2]
-            self.global_alive = int(g[0])
+            eps_ptr, inds_ptr, xi_ptr = eps_t.data_ptr(), inds_t.data_ptr(), None if xi_t is None else xi_t.data_ptr()
+        rs.xi = xi_ptr
+        rc = 0
+        if not separate:
+            # the whole step in one call: at small rollout batches a step is bound by host latency
+            rc = _lib.lib().cmbpo_rollout_step(C.byref(rs), n, h[0], h[1], h[2], h[3], env._task_id, env._model.num_nets,
+                                               eps_ptr, inds_ptr, h[4], h[5], _lib.current_stream())
+            if rc != 1:         # (1, small batch: finish(POST) and the compaction ran inside the call)
+                _lib.check(rc, "cmbpo_rollout_step")
         else:
-            alive_ratio = alive / self.batch_size
-        info = {"alive_ratio": alive_ratio, "ensemble_dkl_path": t["dkl_t"], "cost": t["cost_t"]}
+            idx = t["alive_idx"]
+            # policy: pi, logp, mu, log_std at the current observations
+            pol.actor.forward_device(t["cur_obs"], eps_t,
+                                     dict(pi=t["act_t"], logp_pi=t["logp_t"], mu=t["mu_t"], log_std=t["ls_t"]),
+                                     row_idx=idx, n_rows=n)
+            # dynamics ensemble + FakeEnv post-processing
+            outs = dict(next_obs=t["next_obs"], rew=t["rew_t"], term=t["term_t"], cost=t["cost_t"],
+                        dkl_path=t["dkl_t"], ep_var_mean=t["epv_t"])
+            if pool.disagreement:       # (the arrays attached beside the struct: the store below reads them)
+                outs.update(rew_var=t["rew_var_t"], cost_var=t["cost_var_t"])
+            env.step_device(t["cur_obs"], t["act_t"], inds_t, outs,
+                            row_idx=idx, n_rows=n, scratch=self._scratch, noise=xi_t)
+            if exchange:
+                # budget rule across shards: gather {n_alive, n_unc, total}, rank the survivors globally
+                pool._call("cmbpo_rollout_count")
+                rows = self.comm.all_gather_i32(t["iscal"][8:12]).cpu().numpy()
+                excess, rank_off = budget_plan(rows, self.comm.rank, rs.max_samples)
+                rs.use_host_budget, rs.host_excess, rs.host_rank_off = 1, int(excess), int(rank_off)
+            pool._call("cmbpo_rollout_decide")
+            pool._call("cmbpo_rollout_finish", 0)
+            pool._call("cmbpo_rollout_store")
+            self._critics("next_obs", "v_n", "vc_n", n)
+            pool._call("cmbpo_rollout_finish", 1)
+        isc, dsc = self._read_scalars()         # the host sync of the step: what finished / was stored + the accumulators
+        info = self._after_step(rc == 1, isc, dsc, n, sharded)
         # after the swap the step's next_obs is the new cur_obs
         return t["cur_obs"], t["rew_t"], t["term_t"], info
 
@@ -344,46 +313,45 @@ class ModelSampler:
         self._draws = [0, e_ck, self._elites[d_ck], x_ck]
         return self._draws
 
-    def _sample_fast(self, max_samples):
-        """sample() on one rank with the sampler's own draws: the whole step is ONE C call (cmbpo_rollout_step) plus the
-        read of the step's counters.  Same results as the general path below -- at the shipped configurations' 1e3 - 1e4
-        branches a step is ~100 us of kernels, so the host side is kept to pointer arithmetic."""
-        pool, env, pol = self.pool, self.env, self.policy
-        self._n_episodes += 1
-        t, rs = pool.t, pool.rs
-        n, B, A = pool.n_alive, self.batch_size, pool.act_dim
+    def _next_draws(self):
+        """The draw chunk, its first unused step k and the device addresses of that step's eps, elite indices and xi (None without
+        transition noise).  The chunk is drawn again when it is used up or was drawn for another batch size or another
+        `stochastic`.  The caller advances chunk[0] by the steps it takes."""
         ck = self._draws
+        B = self.batch_size
         if ck is None or ck[0] >= ck[1].shape[0] or ck[1].shape[1] != B or (ck[3] is None) == self.stochastic:
             ck = self._draw_chunk()
         k = ck[0]
-        ck[0] = k + 1
-        eps_ptr = ck[1].data_ptr() + k * B * A * 4
-        inds_ptr = ck[2].data_ptr() + k * B * ck[2].element_size()
-        if getattr(self, "_scratch", None) is None or self._scratch[0].shape[1] != B:
-            E, O = env._model.num_nets, env.output_dim
-            self._scratch = (torch.empty((E, B, O), dtype=torch.float32, device=self.device),
-                             torch.empty((E, B, O), dtype=torch.float32, device=self.device))
+        return (ck, k, ck[1].data_ptr() + k * B * self.pool.act_dim * 4, ck[2].data_ptr() + k * B * ck[2].element_size(),
+                ck[3].data_ptr() + k * B * self.pool.obs_dim * 4 if ck[3] is not None else None)
+
+    def _prepare_call(self, max_samples):
+        """What every native step call needs first: the ensemble's scratch, the handle tuple (actor, model, v, vc, scratch mean,
+        scratch var; rebuilt after reset(), set_policy() and a new scratch) and the step's limits in the struct."""
+        env, pol, rs = self.env, self.policy, self.pool.rs
+        if self._scratch is None or self._scratch[0].shape[1] != self.batch_size:
+            shape = (env._model.num_nets, self.batch_size, env.output_dim)
+            self._scratch = (torch.empty(shape, dtype=torch.float32, device=self.device),
+                             torch.empty(shape, dtype=torch.float32, device=self.device))
             self._handles = None
-        if getattr(self, "_handles", None) is None:
+        if self._handles is None:
             self._handles = (pol.actor.mlp.handle, env._model.mlp.handle, pol.v.mlp.handle, pol.vc.mlp.handle,
                              self._scratch[0].data_ptr(), self._scratch[1].data_ptr())
-        h = self._handles
-        rs.xi = ck[3].data_ptr() + k * B * pool.obs_dim * 4 if ck[3] is not None else None
         rs.max_samples = int(max_samples) if max_samples else 0
         rs.dkl_lim = float(self.dkl_lim)
         rs.max_path_length = self._max_path_length
         rs.use_host_budget = 0
-        stream = _lib.current_stream()
-        rc = _lib.lib().cmbpo_rollout_step(C.byref(rs), n, h[0], h[1], h[2], h[3], env._task_id, env._model.num_nets,
-                                           eps_ptr, inds_ptr, h[4], h[5], stream)
-        if rc != 1:
-            _lib.check(rc, "cmbpo_rollout_step")
-        isc, dsc = self._read_scalars()         # the host sync of the step
+        return self._handles
+
+    def _after_step(self, compacted, isc, dsc, n, sharded):
+        """The host's part of a step of `n` alive rows, from the counters it left: the alive list (`compacted`: already rebuilt
+        inside the call), the cur / next arrays, the column, the totals.  Returns the step's info."""
+        pool = self.pool
         self.n_budget_terminated += int(isc[_lib.I_N_FIN_PRE]) - int(isc[_lib.I_N_UNC])
-        if rc == 1:                             # small batch: finish(POST) and the compaction ran inside the call
+        if compacted:
             pool.swap("alive_idx", "alive_idx_out")
         elif int(isc[_lib.I_N_FIN_PRE]) + int(isc[_lib.I_N_FIN_POST]) > 0:
-            pool._call("cmbpo_rollout_compact")
+            pool._call("cmbpo_rollout_compact")      # the alive list only changes when a branch finished
             pool.swap("alive_idx", "alive_idx_out")
             # the survivors' count follows from the counters just read: no second host synchronisation
             pool._n_alive = n - int(isc[_lib.I_N_FIN_PRE]) - int(isc[_lib.I_N_FIN_POST])
@@ -391,11 +359,23 @@ class ModelSampler:
         pool.swap("v_t", "v_n")
         pool.swap("vc_t", "vc_n")
         pool.ptr += 1
-        rs.ptr = pool.ptr
-        self._host["total_samples"] = float(dsc[_lib.D_TOTAL_SAMPLES])
-        self._host["total_dkl"] = float(dsc[_lib.D_TOTAL_DKL])
-        info = {"alive_ratio": pool.n_alive / self.batch_size, "ensemble_dkl_path": t["dkl_t"], "cost": t["cost_t"]}
-        return t["cur_obs"], t["rew_t"], t["term_t"], info
+        pool.rs.ptr = pool.ptr
+        return self._step_info(dsc, sharded)
+
+    def _step_info(self, dsc, sharded):
+        """The info of a step, after taking the sampler's totals from the accumulators `dsc` it left (None: an idle step, nothing
+        moved).  `sharded`: alive_ratio and the totals over all shards (one collective)."""
+        pool, t = self.pool, self.pool.t
+        if dsc is not None:
+            self._host["total_samples"] = float(dsc[_lib.D_TOTAL_SAMPLES])
+            self._host["total_dkl"] = float(dsc[_lib.D_TOTAL_DKL])
+        if sharded:
+            g = self.comm.all_reduce_host([pool.n_alive, self.batch_size, self._host["total_samples"]])
+            alive_ratio, self._global_total_samples = g[0] / g[1], g[2]
+            self.global_alive = int(g[0])
+        else:
+            alive_ratio = pool.n_alive / self.batch_size
+        return {"alive_ratio": alive_ratio, "ensemble_dkl_path": t["dkl_t"], "cost": t["cost_t"]}
 
     def sample_many(self, max_steps=None, max_samples=None, stop_total=None, min_alive_ratio=None):
         """Consecutive sample() calls without the interpreter between them (cmbpo_rollout_run): the rollout loop of
@@ -404,7 +384,7 @@ class ModelSampler:
         test made after a step, as the reference's loop makes them.  `max_samples` is the budget every step is given.
         Returns (steps taken, info of the last step).  On a sharded sampler, with injected draws or with kernel events
         on, the same loop runs over sample()."""
-        pool, env, pol = self.pool, self.env, self.policy
+        pool, env = self.pool, self.env
         sharded = self.comm is not None and self.comm.world > 1
         min_alive = int(np.floor(min_alive_ratio * self.batch_size + 1e-9)) if min_alive_ratio is not None else 0
         left = int(max_steps) if max_steps is not None else (1 << 30)
@@ -425,46 +405,30 @@ class ModelSampler:
                     break
             return steps, info
         t, rs = pool.t, pool.rs
-        B, A = self.batch_size, pool.act_dim
+        B = self.batch_size
         lib = _lib.lib()
         with torch.cuda.device(self.device):
-            if getattr(self, "_scratch", None) is None or self._scratch[0].shape[1] != B:
-                E, O = env._model.num_nets, env.output_dim
-                self._scratch = (torch.empty((E, B, O), dtype=torch.float32, device=self.device),
-                                 torch.empty((E, B, O), dtype=torch.float32, device=self.device))
-                self._handles = None
-            if getattr(self, "_handles", None) is None:
-                self._handles = (pol.actor.mlp.handle, env._model.mlp.handle, pol.v.mlp.handle, pol.vc.mlp.handle,
-                                 self._scratch[0].data_ptr(), self._scratch[1].data_ptr())
-            h = self._handles
-            if getattr(self, "_run_host", None) is None:
+            h = self._prepare_call(max_samples)
+            if self._run_host is None:
                 self._run_host = torch.empty((64, 384), dtype=torch.uint8, pin_memory=True)
                 self._run_out = (C.c_int(0), C.c_int(0), C.c_int(0))
-            rs.max_samples = int(max_samples) if max_samples else 0
-            rs.dkl_lim = float(self.dkl_lim)
-            rs.max_path_length = self._max_path_length
-            rs.use_host_budget = 0
             stream = _lib.current_stream()
             stop = float("nan") if stop_total is None else float(stop_total)     # NaN: no stop rule on the total
             done_o, alive_o, swaps_o = self._run_out
             while left > 0 and pool.n_alive > 0 and pool.has_room:
-                ck = self._draws
-                if ck is None or ck[0] >= ck[1].shape[0] or ck[1].shape[1] != B or (ck[3] is None) == self.stochastic:
-                    ck = self._draw_chunk()
-                k = ck[0]
+                # (transition noise: step j of the call reads xi + j * xi_stride)
+                ck, k, eps_ptr, inds_ptr, rs.xi = self._next_draws()
                 take = min(left, ck[1].shape[0] - k, 64)
-                # transition noise: step j of the call reads xi + j * xi_stride
-                rs.xi = ck[3].data_ptr() + k * B * pool.obs_dim * 4 if ck[3] is not None else None
                 rs.xi_stride = B * pool.obs_dim
                 _lib.check(lib.cmbpo_rollout_run(
                     C.byref(rs), pool.n_alive, h[0], h[1], h[2], h[3], env._task_id, env._model.num_nets,
-                    ck[1].data_ptr() + k * B * A * 4, ck[2].data_ptr() + k * B * ck[2].element_size(), B * A, B,
+                    eps_ptr, inds_ptr, B * pool.act_dim, B,
                     h[4], h[5], take, stop, min_alive, self._run_host.data_ptr(), C.byref(done_o), C.byref(alive_o),
                     C.byref(swaps_o), stream), "cmbpo_rollout_run")
                 done = done_o.value
                 if done == 0:
                     break
-                # the struct was advanced in native code: bring the tensor table to the same state
+                # the struct was advanced in native code (what _after_step does per step): bring the tensor table to the same state
                 if done & 1:
                     for a, b in (("cur_obs", "next_obs"), ("v_t", "v_n"), ("vc_t", "vc_n")):
                         t[a], t[b] = t[b], t[a]
@@ -481,9 +445,7 @@ class ModelSampler:
                 isc, dsc = last[:128].view(torch.int32).numpy().copy(), last[128:].view(torch.float64).numpy().copy()
                 pool._n_alive, pool._size = alive_o.value, int(isc[_lib.I_SIZE])
                 self._dsc = dsc
-                self._host["total_samples"] = float(dsc[_lib.D_TOTAL_SAMPLES])
-                self._host["total_dkl"] = float(dsc[_lib.D_TOTAL_DKL])
-                info = {"alive_ratio": pool.n_alive / B, "ensemble_dkl_path": t["dkl_t"], "cost": t["cost_t"]}
+                info = self._step_info(dsc, False)
                 if done < take:       # a stop test fired inside the call
                     break
         if local_only:
@@ -492,7 +454,8 @@ class ModelSampler:
             g = self.comm.all_reduce_host([pool.n_alive, self.batch_size, self._host["total_samples"],
                                            pool.n_alive if pool.has_room else 0])
             self.global_alive, self._global_total_samples = int(g[3]), g[2]
-            info = {"alive_ratio": g[0] / g[1], "ensemble_dkl_path": t["dkl_t"], "cost": t["cost_t"]}
+            info = self._step_info(None, False)
+            info["alive_ratio"] = g[0] / g[1]
         return steps, info
 
     def _idle_step(self, max_samples):
@@ -502,15 +465,12 @@ class ModelSampler:
                 pool.rs.max_samples = int(max_samples)
                 pool._call("cmbpo_rollout_count")
                 self.comm.all_gather_i32(t["iscal"][8:12])
-        g = self.comm.all_reduce_host([0, self.batch_size, self._host["total_samples"]])
-        self.global_alive, self._global_total_samples = int(g[0]), g[2]
-        info = {"alive_ratio": g[0] / g[1], "ensemble_dkl_path": t["dkl_t"], "cost": t["cost_t"]}
-        return t["cur_obs"], t["rew_t"], t["term_t"], info
+        return t["cur_obs"], t["rew_t"], t["term_t"], self._step_info(None, True)
 
     def any_alive(self):
         """True while any shard still has alive branches (== pool.n_alive > 0 on one GPU)."""
         if self.comm is not None and self.comm.world > 1:
-            return getattr(self, "global_alive", 1) > 0
+            return self.global_alive > 0
         return self.pool.n_alive > 0
 
     def finish_all_paths(self):

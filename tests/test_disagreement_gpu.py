@@ -401,6 +401,57 @@ def test_rollout_with_disagreement(hip_lib, which):
     np.testing.assert_array_equal(_bits(pes["get"][0]), _bits(zero["get"][0]))       # the same observations
 
 
+def _roll_attached(w, start, dkl_lim, budget, how, attach, detach_iv=False):
+    """One rollout with the sampler's own draws (seed 5) and the features of `attach` ('iv': the weighted GAE, 'dg': the
+    disagreement with both kappas 0) attached beside the struct in that order; detach_iv: the weighted GAE is switched off
+    again before the rollout.  how: 'loop' (sample()) or 'many' (sample_many()).  Returns get()'s twelve arrays and the two
+    variance diagnostics."""
+    sampler, pool = _world(w, start.shape[0], dkl_lim, "dg" in attach, (0.0, 0.0))
+    for f in attach:
+        if f == "iv":
+            pool.set_iv_gae(True)
+        else:
+            pool.set_disagreement(True)
+    if detach_iv:
+        pool.set_iv_gae(False)
+    sampler._gen.manual_seed(5)
+    sampler.reset(start)         # (takes the environment's switch: the same as what is attached, nothing is attached again)
+    assert pool.iv_gae == ("iv" in attach and not detach_iv) and pool.disagreement == ("dg" in attach)
+    while sampler.any_alive() and pool.has_room:
+        if how == "many":
+            sampler.sample_many(max_samples=budget)
+        else:
+            sampler.sample(max_samples=budget)
+    assert pool.ptr == T
+    diag = sampler.finish_all_paths()
+    return pool.get()[0], (diag["msampler/rew_var_perstep"], diag["msampler/cost_var_perstep"])
+
+
+@pytest.mark.parametrize("how", ["loop", "many"])
+@pytest.mark.parametrize("which", [0, 1], ids=["one_workgroup", "above"])
+def test_iv_gae_and_disagreement_together(hip_lib, which, how):
+    """The weighted GAE and the disagreement share one table beside the struct: attached to the same buffer, in either order,
+    each computes what it computes alone (kappa = 0: the disagreement only measures), and switching one off leaves the other.
+    B = 300 on the one-workgroup bookkeeping kernels, B = their limit + 76 on the separate store / finish kernels."""
+    _need_gpu()
+    B = (300, hip_lib.cmbpo_rollout_book_pre_max_rows() + 76)[which]
+    w, start, dkl_lim, budget = _plan(B)
+    iv_only = _roll_attached(w, start, dkl_lim, budget, how, ("iv",))
+    dg_only = _roll_attached(w, start, dkl_lim, budget, how, ("dg",))
+    assert iv_only[1] == (0.0, 0.0) and dg_only[1][0] > 0.0 and dg_only[1][1] > 0.0
+    # (the weighted recurrence is another one: a run that lost it would pass as the un-weighted run)
+    assert (iv_only[0][2] != dg_only[0][2]).any() and (iv_only[0][3] != dg_only[0][3]).any()
+    for order in (("iv", "dg"), ("dg", "iv")):
+        both = _roll_attached(w, start, dkl_lim, budget, how, order)
+        for k, a, b in zip(NAMES, both[0], iv_only[0]):
+            np.testing.assert_array_equal(_bits(a), _bits(b), err_msg=f"{order} {k}")
+        assert both[1] == dg_only[1], order
+    left = _roll_attached(w, start, dkl_lim, budget, how, ("iv", "dg"), detach_iv=True)
+    for k, a, b in zip(NAMES, left[0], dg_only[0]):
+        np.testing.assert_array_equal(_bits(a), _bits(b), err_msg=f"iv switched off: {k}")
+    assert left[1] == dg_only[1]
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # 3. FakeEnv and errors
 # ------------------------------------------------------------------------------------------------------------------
