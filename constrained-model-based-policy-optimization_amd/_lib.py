@@ -189,6 +189,29 @@ SIGNATURES.update({
     "cmbpo_adv_normalize": (_i, [_i, _p, _p, _p, _p]),
 })
 
+
+class PiPpoCfgStruct(C.Structure):
+    """ctypes image of ``cmbpo_pi_ppo_cfg_t``."""
+    _fields_ = [("clip_ratio", C.c_float), ("clipped_adv", C.c_int32), ("objective_penalized", C.c_int32),
+                ("ent_reg", C.c_float), ("pi_lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("adam_eps", C.c_float), ("target_kl", C.c_float), ("kl_margin", C.c_float)]
+
+
+# slots of the first-order loop's state block (doubles; the layout is documented in the header)
+PPO_STATE_DOUBLES = 32
+(PPO_ST_STOP, PPO_ST_ITERS, PPO_ST_KL, PPO_ST_ADAM_T, PPO_ST_PEN_PARAM, PPO_ST_PEN_M, PPO_ST_PEN_V, PPO_ST_PEN_T,
+ PPO_ST_PENALTY, PPO_ST_CR, PPO_ST_CC, PPO_ST_PRE) = range(12)
+PPO_ST_POST = PPO_ST_PRE + 8
+PPO_ST_CLIP = 27
+
+_cp = C.POINTER(PiPpoCfgStruct)
+SIGNATURES.update({
+    "cmbpo_pi_ppo_grad": (_i, [_p, _bp, _cp, _p, _p, _p, _p]),
+    "cmbpo_vec_adam_step": (_i, [_i, _p, _p, _p, _p, _p, C.c_float, C.c_float, C.c_float, C.c_float, _p]),
+    "cmbpo_ppo_penalty_step": (_i, [_p, _p, C.c_double, C.c_double, C.c_double, _i, _p]),
+    "cmbpo_pi_ppo_run": (_i, [_p, _bp, _cp, _p, _p, _p, _p, _i, _p]),
+})
+
 # ensemble training (csrc/ens_train.hip)
 SIGNATURES.update({
     "cmbpo_trainer_create": (_i, [C.POINTER(_p), _p, _i, C.c_float, _p]),

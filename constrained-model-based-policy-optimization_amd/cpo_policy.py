@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .cpo_update import CPOAgent, PolicyOps, _NullLogger
+from .cpo_update import CPOAgent, PPOLagAgent, PolicyOps, _NullLogger
 from .pens import PE, EnsembleMLP, _to_dev
 
 
@@ -108,11 +108,23 @@ class CPOPolicy:
         self.real_c_buffer = [self.cost_lim] * 300     # cpo_policy.py:356
         self.logger = logger if logger is not None else _NullLogger()
         self.comm = kw.get("comm", None)
+        self.pi_optimizer = kw.get("pi_optimizer", "trust_region")
+        if self.pi_optimizer not in ("trust_region", "first_order"):
+            raise ValueError("pi_optimizer must be 'trust_region' or 'first_order', got %r" % (self.pi_optimizer,))
+        if self.pi_optimizer == "first_order" and self.comm is not None and getattr(self.comm, "world", 1) > 1:
+            raise NotImplementedError("pi_optimizer='first_order' is not sharded: each of its iterations would need an "
+                                      "all-reduce (world size %d)" % self.comm.world)
         self.actor = GaussianActor(self.obs_dim, self.act_dim, self.hidden_sizes_a, device)
         self.device = self.actor.device
         # cpo_policy.py:366-374: the agent's hyper-parameters
-        self.agent = CPOAgent(constrained=self.constrain_cost, learn_margin=True, c_gamma=self.cost_gamma,
-                              max_path_length=self.max_path_length, ent_reg=self.ent_reg)
+        if self.pi_optimizer == "trust_region":
+            self.agent = CPOAgent(constrained=self.constrain_cost, learn_margin=True, c_gamma=self.cost_gamma,
+                                  max_path_length=self.max_path_length, ent_reg=self.ent_reg)
+        else:
+            names = ("clipped_adv", "objective_penalized", "learn_penalty", "penalty_init", "penalty_lr",
+                     "penalty_param_loss", "pi_lr", "pi_iters", "clip_ratio", "kl_margin")
+            self.agent = PPOLagAgent(constrained=self.constrain_cost, max_path_length=self.max_path_length,
+                                     ent_reg=self.ent_reg, **{k: kw[k] for k in names if k in kw})
         self.agent.set_logger(self.logger)
         self.ops = PolicyOps(self.obs_dim, self.act_dim, self.actor.hidden, self.device, comm=self.comm)
         common = dict(hidden_dims=self.hidden_sizes_c, num_networks=self.vf_ensemble,
@@ -141,8 +153,9 @@ class CPOPolicy:
                   'Loss' + self.v.name, 'Loss' + self.vc.name, 'Loss' + self.v.name + 'Delta',
                   'Loss' + self.vc.name + 'Delta'):
             self.logger.log_tabular(k, average_only=True)
-        self.logger.log_tabular('Penalty', 0)
-        self.logger.log_tabular('PenaltyDelta', 0)
+        if self.pi_optimizer == "trust_region":       # (the first-order agent has logged its own)
+            self.logger.log_tabular('Penalty', 0)
+            self.logger.log_tabular('PenaltyDelta', 0)
 
     def set_params(self, params):
         """Actor parameters ([W0,b0,W1,b1,W2,b2,log_std] or one flat vector) -> rollout + update handles."""
@@ -265,7 +278,10 @@ class CPOPolicy:
         import os
         names = ("W0", "b0", "W1", "b1", "W2", "b2", "log_std")
         path = os.path.join(checkpoint_dir, "policy_%s.npz" % timestep)
-        np.savez(path, **dict(zip(names, self.actor.params)))
+        extra = {}
+        if self.pi_optimizer == "first_order":     # penalty_param with its Adam moments, the policy's Adam moments and t
+            extra = self.agent.state_dict(self.ops)
+        np.savez(path, **dict(zip(names, self.actor.params)), **extra)
         if self.v.finalized:
             self.v.save(checkpoint_dir, timestep)
         if self.vc.finalized:
@@ -276,6 +292,8 @@ class CPOPolicy:
         import os
         z = np.load(os.path.join(checkpoint_dir, "policy_%s.npz" % timestep))
         self.set_params([z[k] for k in ("W0", "b0", "W1", "b1", "W2", "b2", "log_std")])
+        if self.pi_optimizer == "first_order" and "ppo_penalty_param" in z.files:
+            self.agent.load_state_dict(self.ops, z)
         for critic in (self.v, self.vc):
             if os.path.exists(os.path.join(checkpoint_dir, "%s_%s.nns" % (critic.name, timestep))):
                 critic.load(checkpoint_dir, timestep)

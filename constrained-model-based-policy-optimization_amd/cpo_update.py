@@ -15,6 +15,13 @@ accept / reject decision is the reference's, on host scalars).  The decision log
 (lam, nu), step, backtracking) follows the reference line for line in meaning.  Reductions are sums weighted
 by sample counts (all-reduced over ranks when a ``dist.Comm`` is given) instead of ``mpi_avg`` of per-rank means
 (``utilities/mpi_tools.py:67-69``), and counts are never cast to float32.
+
+``PPOLagAgent`` is the other family the reference's Agent declares (first-order, clipped, penalised: PPO-Lagrangian):
+
+    penalty_param step                                   -> cmbpo_ppo_penalty_step
+    pi_iters x [gradient + KL, gate, Adam, re-pack]      -> cmbpo_pi_ppo_run (one call, no host wait inside)
+
+with one host read per update; ``PolicyOps.ppo_grad`` / ``adam_step`` are the loop's building blocks.
 """
 import ctypes as C
 
@@ -83,6 +90,22 @@ class PolicyOps:
         self.batch = _lib.PiBatchStruct()
         self._keep = None
         self.n_global = 0
+
+    # first-order updates: Adam moments of the flat vector, the loop's state block (penalty_param and its moments included)
+    # and two blocks of loss sums.  Like TF's optimiser slots they persist across updates, and set_params from outside
+    # leaves them alone.  They come into being with the first first-order use: a trust-region job holds what it always held.
+    _FIRST_ORDER = ("adam_m", "adam_v", "ppo_state", "ppo_sums", "cost_sums")
+
+    def __getattr__(self, name):          # (reached only for attributes that do not exist yet)
+        if name in PolicyOps._FIRST_ORDER and "P" in self.__dict__:
+            with torch.cuda.device(self.device):
+                self.adam_m = torch.zeros(self.P, dtype=torch.float32, device=self.device)
+                self.adam_v = torch.zeros(self.P, dtype=torch.float32, device=self.device)
+                self.ppo_state = torch.zeros(_lib.PPO_STATE_DOUBLES, dtype=torch.float64, device=self.device)
+                self.ppo_sums = torch.zeros(8, dtype=torch.float64, device=self.device)
+                self.cost_sums = torch.zeros(8, dtype=torch.float64, device=self.device)
+            return self.__dict__[name]
+        raise AttributeError(name)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -223,6 +246,76 @@ class PolicyOps:
         _lib.check(_lib.lib().cmbpo_pi_eval(self._h, C.byref(self.batch), sums.data_ptr(), self._s()), "cmbpo_pi_eval")
         self._reduce(sums)
         return sums
+
+    # -- first-order penalised updates (PPO-Lagrangian) ---------------------------------------------------------------
+    @staticmethod
+    def ppo_cfg(clip_ratio=0.2, clipped_adv=True, objective_penalized=True, ent_reg=0.0, pi_lr=3e-4, beta1=0.9,
+                beta2=0.999, adam_eps=1e-8, target_kl=0.01, kl_margin=1.2):
+        """The ``cmbpo_pi_ppo_cfg_t`` of a first-order update."""
+        return _lib.PiPpoCfgStruct(float(clip_ratio), int(bool(clipped_adv)), int(bool(objective_penalized)),
+                                   float(ent_reg), float(pi_lr), float(beta1), float(beta2), float(adam_eps),
+                                   float(target_kl), float(kl_margin))
+
+    def _single(self, what):
+        if self.comm is not None and self.comm.world > 1:
+            raise NotImplementedError(what + ": first-order updates are not sharded (one all-reduce per iteration)")
+
+    def set_penalty_param(self, penalty_param):
+        """penalty_param -> the state block; penalty = softplus(penalty_param), c_r and c_c follow (no Adam step)."""
+        with torch.cuda.device(self.device):
+            self.ppo_state[_lib.PPO_ST_PEN_PARAM] = float(penalty_param)
+            self.penalty_refresh()
+
+    def penalty_refresh(self):
+        """penalty, c_r, c_c of the penalty_param the state block holds (no Adam step)."""
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().cmbpo_ppo_penalty_step(self.ppo_state.data_ptr(), None, 0.0, 1.0, 0.0, 1, self._s()),
+                       "cmbpo_ppo_penalty_step")
+
+    def penalty_step(self, cost_lim, max_path_length, penalty_lr, penalty_param_loss, sums=None):
+        """One Adam step on penalty_param against cur_cost = sums[4] / sums[0] * max_path_length (default: the bound
+        batch's own cost column); refreshes penalty, c_r, c_c."""
+        with torch.cuda.device(self.device):
+            if sums is None:
+                sums = self.cost_sums
+                sums[0] = float(self.n_local)
+                sums[4:5] = self._keep[5].sum(dtype=torch.float64)
+            _lib.check(_lib.lib().cmbpo_ppo_penalty_step(self.ppo_state.data_ptr(), sums.data_ptr(), float(cost_lim),
+                                                         float(max_path_length), float(penalty_lr),
+                                                         int(bool(penalty_param_loss)), self._s()),
+                       "cmbpo_ppo_penalty_step")
+
+    def ppo_grad_dev(self, cfg, out, sums):
+        """out = (sum of the per-sample gradients of the clipped, penalised loss) / N; `sums` gets the pass's loss sums."""
+        self._single("ppo_grad")
+        _lib.check(_lib.lib().cmbpo_pi_ppo_grad(self._h, C.byref(self.batch), C.byref(cfg), self.ppo_state.data_ptr(),
+                                                self.vec.data_ptr(), sums.data_ptr(), self._s()), "cmbpo_pi_ppo_grad")
+        return self.lincomb(out, 1.0 / float(self.n_global), self.vec)
+
+    def ppo_grad(self, cfg):
+        with torch.cuda.device(self.device):
+            g = self.ppo_grad_dev(cfg, self.work["g"], self.ppo_sums)
+            return g.cpu().numpy(), self.ppo_sums.cpu().numpy()
+
+    def adam_step(self, g, lr, beta1=0.9, beta2=0.999, eps=1e-8):
+        """One TF-Adam step of the flat parameters along the device (or NumPy) gradient g; the handle is not re-packed
+        (``set_params(ops.params)`` does that)."""
+        with torch.cuda.device(self.device):
+            if not isinstance(g, torch.Tensor):
+                self.dirv.copy_(torch.from_numpy(np.ascontiguousarray(g, dtype=F32)))
+                g = self.dirv
+            _lib.check(_lib.lib().cmbpo_vec_adam_step(self.P, g.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(),
+                                                      self.params.data_ptr(), self.ppo_state.data_ptr(), float(lr),
+                                                      float(beta1), float(beta2), float(eps), self._s()),
+                       "cmbpo_vec_adam_step")
+
+    def ppo_run(self, cfg, iters):
+        """`iters` gated iterations and the final evaluation, enqueued in one call; results are in ``ppo_state``."""
+        self._single("ppo_run")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().cmbpo_pi_ppo_run(self._h, C.byref(self.batch), C.byref(cfg), self.params.data_ptr(),
+                                                   self.adam_m.data_ptr(), self.adam_v.data_ptr(),
+                                                   self.ppo_state.data_ptr(), int(iters), self._s()), "cmbpo_pi_ppo_run")
 
     # -- NumPy-facing forms (tests, diagnostics) -----------------------------------------------------------------
     def loss_grad(self, which):
@@ -424,3 +517,125 @@ class CPOAgent:
         info["post"] = dict(LossPi=pi_l_new, SurrCost=surr_cost_new, KL=kl, Entropy=F32(ent_new),
                             SurrAdv=F32(-float(pi_l_new) - self.ent_reg * ent_new))
         return info
+
+
+class PPOLagAgent:
+    """The first-order family the reference's Agent declares (policies/cpo_policy.py:30-123: first_order, clipped_adv,
+    objective_penalized, learn_penalty, penalty_param_loss) and never builds (:568-569): PPO with a clipped surrogate and a
+    learned Lagrangian penalty on the cost surrogate.  ``reward_penalized`` stays out (it changes what the buffers store)."""
+
+    def __init__(self, constrained=True, clipped_adv=True, objective_penalized=True, learn_penalty=True, penalty_init=1.0,
+                 penalty_lr=5e-2, penalty_param_loss=True, pi_lr=3e-4, pi_iters=80, clip_ratio=0.2, kl_margin=1.2,
+                 ent_reg=0.0, max_path_length=1):
+        self.constrained = constrained
+        self.clipped_adv, self.clip_ratio = clipped_adv, clip_ratio
+        self.objective_penalized = bool(objective_penalized and constrained)
+        self.learn_penalty = bool(learn_penalty and constrained)
+        self.penalty_init, self.penalty_lr, self.penalty_param_loss = penalty_init, penalty_lr, penalty_param_loss
+        self.pi_lr, self.pi_iters, self.kl_margin = pi_lr, int(pi_iters), kl_margin
+        self.ent_reg = ent_reg
+        self.max_path_length = max_path_length
+        self.reward_penalized = False
+        self.trust_region = False
+        self.first_order = True
+        self.cares_about_cost = constrained
+        self.logger = _NullLogger()
+        self._ops = None          # the PolicyOps whose state block holds penalty_param
+        self._penalty = None      # the penalty after the last update (host copy, for PenaltyDelta)
+
+    def set_logger(self, logger):
+        self.logger = logger
+
+    def log(self):
+        for k in ('Penalty', 'PenaltyDelta', 'StopIter', 'ClipFrac'):
+            self.logger.log_tabular(k, average_only=True)
+
+    def _ent(self, log_std):
+        return float(np.sum(np.asarray(log_std, np.float64) + 0.5 * np.log(2 * np.pi * np.e)))   # ac_network.py:57-61
+
+    def penalty_param_init(self):
+        """softplus^-1(penalty_init), as safety-starter-agents initialises the variable"""
+        return float(np.log(max(np.exp(self.penalty_init) - 1, 1e-8)))
+
+    def attach(self, ops):
+        """First use of `ops` (or a new one): the state block gets the initial penalty."""
+        if self._ops is not ops:
+            self._ops = ops
+            ops.set_penalty_param(self.penalty_param_init())
+            self._penalty = float(np.log1p(np.exp(self.penalty_param_init())))
+
+    def cfg(self, ops, target_kl):
+        return ops.ppo_cfg(clip_ratio=self.clip_ratio, clipped_adv=self.clipped_adv,
+                           objective_penalized=self.objective_penalized, ent_reg=self.ent_reg, pi_lr=self.pi_lr,
+                           target_kl=target_kl, kl_margin=self.kl_margin)
+
+    def _loss(self, surr_adv, surr_cost, ent, penalty):
+        obj = surr_adv + self.ent_reg * ent
+        if self.objective_penalized:
+            obj = (obj - penalty * surr_cost) / (1 + penalty)
+        return F32(-obj)
+
+    def measures(self, ops):
+        """LossPi, SurrCost, SurrAdv, Entropy, KL at the current parameters (the unclipped surrogate)."""
+        s = ops.evals()
+        n = s[0]
+        ent = self._ent(ops.get_params()[-ops.A:])
+        pen = float(ops.ppo_state[_lib.PPO_ST_PENALTY]) if self._ops is ops else 0.0
+        return dict(LossPi=self._loss(s[1] / n, s[2] / n, ent, pen), SurrCost=F32(s[2] / n), SurrAdv=F32(s[1] / n),
+                    Entropy=F32(ent), KL=F32(s[3] / n))
+
+    def update_pi(self, ops, target_kl, cost_lim, real_cost_buf=None):
+        """Penalty step (learn_penalty), then `pi_iters` gated Adam iterations on the device, then ONE host read.
+
+        Returns `pre` / `post` measures, `params`, `cur_cret_avg` as CPOAgent.update_pi does, plus Penalty (the one the
+        iterations used), PenaltyDelta (its change in this update), StopIter (the 1-based iteration whose KL exceeded
+        kl_margin * target_kl and whose step was not taken; pi_iters if none did) and ClipFrac (share of samples whose
+        advantage term was clipped away at the last iteration that was evaluated).  `pre` holds the clipped surrogate at
+        theta_old, `post` the unclipped one of the final evaluation."""
+        S, A = _lib, ops.A
+        self.attach(ops)
+        with torch.cuda.device(ops.device):
+            if self.learn_penalty:
+                ops.penalty_step(cost_lim, self.max_path_length, self.penalty_lr, self.penalty_param_loss)
+            ls_old = ops.params[-A:].clone()
+            ops.ppo_run(self.cfg(ops, target_kl), self.pi_iters)
+            st, params, ls_old = ops.early_read(ops.ppo_state, ops.params, ls_old, tag="ppo")()   # <- the host read
+        pen = float(st[S.PPO_ST_PENALTY])
+        pre_s, post_s = st[S.PPO_ST_PRE:S.PPO_ST_PRE + 8], st[S.PPO_ST_POST:S.PPO_ST_POST + 8]
+        n = pre_s[0]
+        ent_old, ent_new = self._ent(ls_old), self._ent(params[-A:])
+        stop = int(st[S.PPO_ST_STOP])
+        info = dict(Penalty=F32(pen), PenaltyDelta=F32(pen - self._penalty), StopIter=stop if stop else self.pi_iters,
+                    ClipFrac=F32(st[S.PPO_ST_CLIP] / n), stopped=bool(stop), steps=int(st[S.PPO_ST_ITERS]))
+        self._penalty = pen
+        self.logger.store(Penalty=info["Penalty"], PenaltyDelta=info["PenaltyDelta"], StopIter=info["StopIter"],
+                          ClipFrac=info["ClipFrac"])
+        info["cur_cret_avg"] = F32(pre_s[4] / n * self.max_path_length)            # cpo_policy.py:533
+        info["params"] = params
+        info["pre"] = dict(LossPi=self._loss(pre_s[1] / n, pre_s[2] / n, ent_old, pen), SurrCost=F32(pre_s[2] / n),
+                           SurrAdv=F32(pre_s[1] / n), Entropy=F32(ent_old))
+        info["post"] = dict(LossPi=self._loss(post_s[1] / n, post_s[2] / n, ent_new, pen), SurrCost=F32(post_s[2] / n),
+                            SurrAdv=F32(post_s[1] / n), Entropy=F32(ent_new), KL=F32(post_s[3] / n))
+        return info
+
+    # -- checkpoints: what the optimiser carries from one update to the next -----------------------------------------
+    def state_dict(self, ops):
+        self.attach(ops)
+        st = ops.ppo_state.cpu().numpy()
+        S = _lib
+        return dict(ppo_penalty_param=st[S.PPO_ST_PEN_PARAM:S.PPO_ST_PEN_T + 1].copy(),     # param, m, v, t
+                    ppo_adam_t=st[S.PPO_ST_ADAM_T:S.PPO_ST_ADAM_T + 1].copy(),
+                    ppo_adam_m=ops.adam_m.cpu().numpy(), ppo_adam_v=ops.adam_v.cpu().numpy())
+
+    def load_state_dict(self, ops, z):
+        self.attach(ops)
+        S = _lib
+        with torch.cuda.device(ops.device):
+            ops.ppo_state[S.PPO_ST_PEN_PARAM:S.PPO_ST_PEN_T + 1] = torch.from_numpy(
+                np.asarray(z["ppo_penalty_param"], np.float64)).to(ops.device)
+            ops.ppo_state[S.PPO_ST_ADAM_T] = float(np.asarray(z["ppo_adam_t"]).reshape(-1)[0])
+            ops.adam_m.copy_(torch.from_numpy(np.asarray(z["ppo_adam_m"], F32)))
+            ops.adam_v.copy_(torch.from_numpy(np.asarray(z["ppo_adam_v"], F32)))
+            ops.penalty_refresh()          # penalty, c_r, c_c of the loaded penalty_param
+        p = float(np.asarray(z["ppo_penalty_param"]).reshape(-1)[0])
+        self._penalty = float(np.log1p(np.exp(-abs(p))) + max(p, 0.0))

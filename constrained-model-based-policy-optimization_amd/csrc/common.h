@@ -10,6 +10,14 @@ void cmbpo_set_error(const char *fmt, ...);
 // the saved-activation block a Fisher-vector product on this batch would read (NULL: recompute); part of the key of a
 // captured CG graph, whose kernel arguments contain it
 const void *cmbpo_pi_act_token(const cmbpo_pi_t *h, const cmbpo_pi_batch_t *b);
+// slots of the first-order loop's device state block (doubles; cmbpo_hip.h documents the layout, _lib.py mirrors it)
+enum { ST_STOP = 0, ST_ITERS = 1, ST_KL = 2, ST_ADAM_T = 3, ST_PEN_PARAM = 4, ST_PEN_M = 5, ST_PEN_V = 6, ST_PEN_T = 7,
+       ST_PENALTY = 8, ST_CR = 9, ST_CC = 10, ST_PRE = 11, ST_POST = 19, ST_CLIP = 27 };
+static_assert(ST_CLIP < CMBPO_PPO_STATE_DOUBLES && ST_POST + 8 <= ST_CLIP, "state block layout");
+// the update kernel of cmbpo_vec_adam_step at the t that d_state holds (vec_ops.hip); gated: return at entry once the
+// first-order loop's stop word is set
+int cmbpo_vec_adam_apply(int P, const float *d_g, float *d_m, float *d_v, float *d_theta, const double *d_state, float lr,
+                         float beta1, float beta2, float eps, int gated, hipStream_t stream);
 // Launch state of the current device (hipGetDevice), kept per device and safe to call from several host threads.
 // CU count (256 if the query fails)
 int cmbpo_cu_count();

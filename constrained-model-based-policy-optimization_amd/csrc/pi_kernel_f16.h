@@ -300,6 +300,9 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
   static_assert(ST::tab.L == (MODE == MODE_EVAL ? P_WF2 + 2 : P_WB1 + 8), "stream positions");
 
   extern __shared__ f32x4 smem4[];
+  if constexpr (MODE == MODE_PPO) {
+    if ((p.ppo_flags & PPO_GATED) && p.state[ST_STOP] != 0.0) return;     // the loop's gate has stopped it (uniform: one scalar load, one branch)
+  }
   const PiDims d = p.d;
   float *sm = reinterpret_cast<float *>(smem4);
   float *xR = sm;                       // [BB][XS] fp32
@@ -338,6 +341,15 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
   float gbias1 = 0.0f, gbias0 = 0.0f;   // d/d b1, d/d b0 of unit 32 wave + (lane & 31); the samples split over the two lane halves
   float gb2p[4] = {0, 0, 0, 0}, glsp[4] = {0, 0, 0, 0};   // per (a = tid/32 + 8*it) partials over this thread's b
   double s_n = 0, s_ra = 0, s_rc = 0, s_kl = 0, s_cost = 0;
+  double s_obj = 0;     // MODE_PPO: the clipped objective ...
+  int s_nclip = 0;      // ... and the samples whose advantage term is clipped away
+  float ppo_cr = 1.0f, ppo_cc = 0.0f;
+  if constexpr (MODE == MODE_PPO) {
+    if (p.ppo_flags & PPO_PENALIZED) {
+      ppo_cr = (float)p.state[ST_CR];
+      ppo_cc = (float)p.state[ST_CC];
+    }
+  }
   Ring R;
   ring_fill<ST>(R, imgs, tid0 & 63);
   __shared__ unsigned s_mx[2][4];    // per tile parity: largest |x|, |cotangent|, |dh2|, |delta1| (float bits)
@@ -459,7 +471,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
         if (a0 < d.A) {
           if constexpr (MODE != MODE_GRAD && !ACT_DMA) lso0 = p.ls_old[(size_t)er0 * d.A + a0];
           if constexpr (MODE != MODE_FVP) e_act0 = p.act[(size_t)er0 * d.A + a0];
-          if constexpr (MODE == MODE_EVAL) e_mu0 = p.mu_old[(size_t)er0 * d.A + a0];
+          if constexpr (MODE == MODE_EVAL || MODE == MODE_PPO) e_mu0 = p.mu_old[(size_t)er0 * d.A + a0];
         }
       }
     }
@@ -624,6 +636,11 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
             const float z = (((it == 0) ? e_act0 : p.act[(size_t)er * d.A + a]) - m) / sd;
             z_[it] = z;
             term = -0.5f * (z * z + 2.0f * ls + 1.8378770664093453f);   // gaussian_likelihood :46-48
+            if constexpr (MODE == MODE_PPO) {   // the KL of the same pass, here, where mu is at hand (MODE_EVAL: second loop)
+              const float lso = (it == 0) ? lso0 : p.ls_old[(size_t)er * d.A + a];
+              const float dm = ((it == 0) ? e_mu0 : p.mu_old[(size_t)er * d.A + a]) - m;
+              s_kl += (double)gauss_kl_term(dm, ls, lso);
+            }
           }
           wR[eb * 36 + a] = term;   // scratch: per-(b, a) log-likelihood terms
         }
@@ -635,8 +652,18 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
       for (int a = 0; a < d.A; ++a) logp += wR[eb * 36 + a];
       const float ratio = valid ? expf(logp - e_logp) : 0.0f;                // cpo_policy.py:522
       const float adv = e_adv, cadv = e_cadv;                                // (zero past the batch end)
+      float ppo_w = 0.0f;
+      if constexpr (MODE == MODE_PPO) {
+        float obj;
+        bool active;
+        ppo_w = ppo_weight(ratio, adv, cadv, p.clip, (p.ppo_flags & PPO_CLIPPED) != 0, ppo_cr, ppo_cc, obj, active);
+        if (tid < 32 && valid) {
+          s_obj += (double)obj;
+          s_nclip += active ? 0 : 1;
+        }
+      }
       if (tid < 32 && valid) {
-        s_n += 1.0;
+        if constexpr (MODE != MODE_PPO) s_n += 1.0;      // (MODE_PPO counts its rows at the end: no registers for it)
         s_ra += (double)(ratio * adv);
         s_rc += (double)(ratio * cadv);
         s_cost += (double)p.cost[er];
@@ -651,11 +678,11 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
               // gaussian_kl(mu, log_std, mu_old, log_std_old), ac_network.py:50-55
               const float ls = p.w.ls[a], lso = (it == 0) ? lso0 : p.ls_old[(size_t)er * d.A + a];
               const float dm = ((it == 0) ? e_mu0 : p.mu_old[(size_t)er * d.A + a]) - mu_[it];
-              const float pre = 0.5f * ((dm * dm + expf(2.0f * ls)) / (expf(2.0f * lso) + 1e-8f) - 1.0f) + lso - ls;
-              s_kl += (double)pre;
+              s_kl += (double)gauss_kl_term(dm, ls, lso);
             }
-          } else {
-            const float wgt = (p.which == 0) ? -adv : cadv;
+          }
+          if constexpr (MODE != MODE_EVAL) {
+            const float wgt = (MODE == MODE_PPO) ? ppo_w : ((p.which == 0) ? -adv : cadv);
             const float ls = p.w.ls[a];
             const float sd = expf(ls);
             const float inv = 1.0f / (sd + 1e-8f);
@@ -772,7 +799,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
       const float sb = half_sum(gb2p[it]), sl = half_sum(glsp[it]);
       if (a < d.A && (tid & 31) == 0) {
         part[d.ob2 + a] = sb;
-        if constexpr (MODE == MODE_GRAD) part[d.ols + a] = sl;
+        if constexpr (MODE != MODE_FVP) part[d.ols + a] = sl;
         else part[d.ols + a] = sl * p.v.ls[a];
       }
     }
@@ -785,7 +812,15 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
     __syncthreads();
     if (wave == 0) {
       const double n = wave_sum(s_n), ra = wave_sum(s_ra), rc = wave_sum(s_rc), c = wave_sum(s_cost);
-      if (lane == 0) {
+      if constexpr (MODE == MODE_PPO) {
+        const double ob = wave_sum(s_obj), nc = wave_sum((double)s_nclip);
+        if (lane == 0) {
+          double *sp = p.sums_part + (size_t)blockIdx.x * 8;
+          int rows = 0;
+          for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) rows += min(BB, p.n - t * BB);
+          sp[0] = (double)rows; sp[1] = ob; sp[2] = rc; sp[3] = sd[0] + sd[1] + sd[2] + sd[3]; sp[4] = c; sp[5] = nc; sp[6] = ra; sp[7] = 0.0;
+        }
+      } else if (lane == 0) {
         atomicAdd(&p.sums[0], n);
         atomicAdd(&p.sums[1], ra);
         atomicAdd(&p.sums[2], rc);

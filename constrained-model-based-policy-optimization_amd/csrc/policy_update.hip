@@ -36,7 +36,12 @@ constexpr int RED_LD = BB + 1;
 // still fit one image: 32 x 268)
 __host__ __device__ constexpr int pi_rs(int H) { return H == 128 ? 132 : H + 12; }
 
-enum { MODE_EVAL = 0, MODE_GRAD = 1, MODE_FVP = 2 };
+enum { MODE_EVAL = 0, MODE_GRAD = 1, MODE_FVP = 2, MODE_PPO = 3 };
+// MODE_PPO (first-order updates): MODE_GRAD with the per-sample weight of the clipped, penalised surrogate, plus MODE_EVAL's
+// KL in the same pass; its loss sums leave as per-workgroup partials (added up in workgroup order: reproducible bits)
+// PPO_GATED: the pass belongs to cmbpo_pi_ppo_run and returns at entry once the stop word is set; a lone
+// cmbpo_pi_ppo_grad ignores the word (it stays set after a run that the gate ended)
+enum { PPO_CLIPPED = 1, PPO_PENALIZED = 2, PPO_GATED = 4 };
 
 #ifdef CMBPO_STAMPS   // diagnostic build only (tools/probe_pi_stamps.py): where wave 0 of each workgroup spends its cycles
 #define PI_STAMP(k)                                                         \
@@ -83,7 +88,30 @@ struct PiArgs {
   const f32x4 *cache_r;   // FVP: saved hidden activations of this batch ([tile][h1 | h2][32][128]) or NULL (recompute)
   f32x4 *cache_w;         // GRAD: where to save them, or NULL
   unsigned long long *stamps;
+  // MODE_PPO only (behind every field the other modes read: their kernel-argument offsets stay where they were)
+  const double *state;    // [CMBPO_PPO_STATE_DOUBLES]: stop word, c_r, c_c
+  double *sums_part;      // [grid][8] per-workgroup loss sums
+  float clip;             // clip_ratio
+  int ppo_flags;          // PPO_CLIPPED | PPO_PENALIZED | PPO_GATED
 };
+
+// the per-sample weight of the clipped, penalised surrogate's cotangent, and what the sample adds to the objective:
+//   min_adv = adv > 0 ? (1 + clip) adv : (1 - clip) adv;  active = !clipped || ratio adv <= min_adv   (positive test: a NaN
+//   ratio is inactive; on a tie the first argument of the minimum is the active one, as in tf.minimum)
+//   w = -c_r (active ? adv : 0) + c_c cadv
+__device__ __forceinline__ float ppo_weight(float ratio, float adv, float cadv, float clip, bool clipped, float c_r, float c_c,
+                                            float &obj, bool &active) {
+  const float ra = ratio * adv;
+  const float min_adv = adv > 0.0f ? (1.0f + clip) * adv : (1.0f - clip) * adv;
+  active = !clipped || (ra <= min_adv);
+  obj = active ? ra : min_adv;
+  return -c_r * (active ? adv : 0.0f) + c_c * cadv;
+}
+
+// one (sample, action) term of gaussian_kl(mu, log_std, mu_old, log_std_old), ac_network.py:50-55; dm = mu_old - mu
+__device__ __forceinline__ float gauss_kl_term(float dm, float ls, float lso) {
+  return 0.5f * ((dm * dm + expf(2.0f * ls)) / (expf(2.0f * lso) + 1e-8f) - 1.0f) + lso - ls;
+}
 
 // ---- packing (device side, so set_params / FVP directions never visit the host) -------------------
 // One launch packs every piece of a flat parameter vector.  Matrix pieces:
@@ -176,7 +204,7 @@ __device__ __forceinline__ void pack_max_part(u32x4 *dst16, const float *flat, c
     reinterpret_cast<float *>(dst16 + H16_INV)[INV_MX + threadIdx.x] = threadIdx.x < 3 ? red[threadIdx.x][0] : 0.0f;
 }
 
-__global__ void pack_all_kernel(float *dst, const float *flat, const PackPlan plan, u32x4 *dst16) {
+__device__ __forceinline__ void pack_all_body(float *dst, const float *flat, const PackPlan &plan, u32x4 *dst16) {
   if ((int)blockIdx.x == plan.nb32) {
     pack_max_part(dst16, flat, plan);
     return;
@@ -208,6 +236,10 @@ __global__ void pack_all_kernel(float *dst, const float *flat, const PackPlan pl
   dst[pc.dst_off + idx] = v;
 }
 
+__global__ void pack_all_kernel(float *dst, const float *flat, const PackPlan plan, u32x4 *dst16) {
+  pack_all_body(dst, flat, plan, dst16);
+}
+
 // Every activation image lives in LDS ONCE, in the row layout [sample][RS] (RS / 4 odd): it is the B operand of
 // the forward / JVP / backward chains (conflict-free 16-B reads, mfma_layer<.., ROWS = true>) and the A / B
 // operand of the weight-gradient MFMAs (conflict-free 4-B reads).  76.8 KB per workgroup -> two per CU.
@@ -218,6 +250,9 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
   constexpr int kThreads = 2 * HIDT, HID = HIDT, KGH = HIDT / 8, RS = pi_rs(HIDT), NW = HIDT / 32;
   constexpr int AS = kThreads / 32, NITE = 32 / AS;     // element phase: a = tid / 32 + AS it, it < NITE
   extern __shared__ f32x4 smem4[];
+  if constexpr (MODE == MODE_PPO) {
+    if ((p.ppo_flags & PPO_GATED) && p.state[ST_STOP] != 0.0) return;     // the loop's gate has stopped it (uniform: one scalar load, one branch)
+  }
   const PiDims d = p.d;
   float *sm = reinterpret_cast<float *>(smem4);
   const int XS = d.in_pad + 4;
@@ -250,6 +285,15 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
   float gbias = 0.0f;   // thread n < 128: d/d b1[n]; thread 128 + n: d/d b0[n] (column sums of the delta images)
   float gb2p[NITE] = {}, glsp[NITE] = {};   // per (a = tid/32 + AS*it) partials over this thread's b
   double s_n = 0, s_ra = 0, s_rc = 0, s_kl = 0, s_cost = 0;
+  double s_obj = 0;     // MODE_PPO: the clipped objective ...
+  int s_nclip = 0;      // ... and the samples whose advantage term is clipped away
+  float ppo_cr = 1.0f, ppo_cc = 0.0f;
+  if constexpr (MODE == MODE_PPO) {
+    if (p.ppo_flags & PPO_PENALIZED) {
+      ppo_cr = (float)p.state[ST_CR];
+      ppo_cc = (float)p.state[ST_CC];
+    }
+  }
 
   // zero the padded cotangent columns (a in [A, 36)) and the padded input columns (k in [D, in_pad)) once: nothing
   // else ever writes them
@@ -319,7 +363,7 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
         if (a0 < d.A) {
           if constexpr (MODE != MODE_GRAD) lso0 = p.ls_old[(size_t)er0 * d.A + a0];
           if constexpr (MODE != MODE_FVP) e_act0 = p.act[(size_t)er0 * d.A + a0];
-          if constexpr (MODE == MODE_EVAL) e_mu0 = p.mu_old[(size_t)er0 * d.A + a0];
+          if constexpr (MODE == MODE_EVAL || MODE == MODE_PPO) e_mu0 = p.mu_old[(size_t)er0 * d.A + a0];
         }
       }
     }
@@ -450,6 +494,11 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
             const float z = (((it == 0) ? e_act0 : p.act[(size_t)er * d.A + a]) - m) / sd;
             z_[it] = z;
             term = -0.5f * (z * z + 2.0f * ls + 1.8378770664093453f);   // gaussian_likelihood :46-48
+            if constexpr (MODE == MODE_PPO) {   // the KL of the same pass, here, where mu is at hand (MODE_EVAL: second loop)
+              const float lso = (it == 0) ? lso0 : p.ls_old[(size_t)er * d.A + a];
+              const float dm = ((it == 0) ? e_mu0 : p.mu_old[(size_t)er * d.A + a]) - m;
+              s_kl += (double)gauss_kl_term(dm, ls, lso);
+            }
           }
           wR[eb * 36 + a] = term;   // scratch: per-(b, a) log-likelihood terms
         }
@@ -461,8 +510,18 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
       for (int a = 0; a < d.A; ++a) logp += wR[eb * 36 + a];
       const float ratio = valid ? expf(logp - e_logp) : 0.0f;                // cpo_policy.py:522
       const float adv = e_adv, cadv = e_cadv;                                // (zero past the batch end)
+      float ppo_w = 0.0f;
+      if constexpr (MODE == MODE_PPO) {
+        float obj;
+        bool active;
+        ppo_w = ppo_weight(ratio, adv, cadv, p.clip, (p.ppo_flags & PPO_CLIPPED) != 0, ppo_cr, ppo_cc, obj, active);
+        if (tid < 32 && valid) {
+          s_obj += (double)obj;
+          s_nclip += active ? 0 : 1;
+        }
+      }
       if (tid < 32 && valid) {
-        s_n += 1.0;
+        if constexpr (MODE != MODE_PPO) s_n += 1.0;      // (MODE_PPO counts its rows at the end: no registers for it)
         s_ra += (double)(ratio * adv);
         s_rc += (double)(ratio * cadv);
         s_cost += (double)p.cost[er];
@@ -477,11 +536,11 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
               // gaussian_kl(mu, log_std, mu_old, log_std_old), ac_network.py:50-55
               const float ls = p.w.ls[a], lso = (it == 0) ? lso0 : p.ls_old[(size_t)er * d.A + a];
               const float dm = ((it == 0) ? e_mu0 : p.mu_old[(size_t)er * d.A + a]) - mu_[it];
-              const float pre = 0.5f * ((dm * dm + expf(2.0f * ls)) / (expf(2.0f * lso) + 1e-8f) - 1.0f) + lso - ls;
-              s_kl += (double)pre;
+              s_kl += (double)gauss_kl_term(dm, ls, lso);
             }
-          } else {
-            const float wgt = (p.which == 0) ? -adv : cadv;
+          }
+          if constexpr (MODE != MODE_EVAL) {
+            const float wgt = (MODE == MODE_PPO) ? ppo_w : ((p.which == 0) ? -adv : cadv);
             const float ls = p.w.ls[a];
             const float sd = expf(ls);
             const float inv = 1.0f / (sd + 1e-8f);
@@ -568,7 +627,7 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
       const float sb = half_sum(gb2p[it]), sl = half_sum(glsp[it]);
       if (a < d.A && (tid & 31) == 0) {
         part[d.ob2 + a] = sb;
-        if constexpr (MODE == MODE_GRAD) part[d.ols + a] = sl;
+        if constexpr (MODE != MODE_FVP) part[d.ols + a] = sl;
         else part[d.ols + a] = sl * p.v.ls[a];
       }
     }
@@ -581,7 +640,18 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     __syncthreads();
     if (wave == 0) {
       const double n = wave_sum(s_n), ra = wave_sum(s_ra), rc = wave_sum(s_rc), c = wave_sum(s_cost);
-      if (lane == 0) {
+      if constexpr (MODE == MODE_PPO) {
+        const double ob = wave_sum(s_obj), nc = wave_sum((double)s_nclip);
+        if (lane == 0) {
+          double klt = sd[0];
+#pragma unroll
+          for (int wv = 1; wv < NW; ++wv) klt += sd[wv];
+          double *sp = p.sums_part + (size_t)blockIdx.x * 8;
+          int rows = 0;
+          for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) rows += min(BB, p.n - t * BB);
+          sp[0] = (double)rows; sp[1] = ob; sp[2] = rc; sp[3] = klt; sp[4] = c; sp[5] = nc; sp[6] = ra; sp[7] = 0.0;
+        }
+      } else if (lane == 0) {
         atomicAdd(&p.sums[0], n);
         atomicAdd(&p.sums[1], ra);
         atomicAdd(&p.sums[2], rc);
@@ -740,6 +810,110 @@ __global__ void cg_commit_kernel(double *scal) {
   }
 }
 
+// ---- first-order loop (MODE_PPO): reduce / scale, gate ----------------------------------------------------------------------
+// vec[i] = sum over workgroups of part[w][i] (reduce_parts_kernel's order: same bits); with scale != 0 the loop's form
+// vec[i] * inv_n - (i in the log_std block ? c_r ent_reg : 0): the entropy term sits inside the bracket that 1 + penalty
+// divides.  Workgroup 0 also adds up the workgroups' loss sums, sum k on wave k, in a fixed order.
+__global__ __launch_bounds__(1024) void ppo_reduce_kernel(const float *part, int part_ld, int n_parts, int P, float *vec, int scale,
+                                                          float inv_n, float ent_reg, int ols, int penalized, const double *state,
+                                                          int gated, const double *sums_part, double *sums) {
+  if (gated && state[ST_STOP] != 0.0) return;
+  __shared__ float sm[16][64];
+  const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int i = blockIdx.x * 64 + c;
+  if (blockIdx.x == 0 && g < 8) {
+    double t = 0.0;
+    for (int w = c; w < n_parts; w += 64) t += sums_part[(size_t)w * 8 + g];
+    t = wave_sum(t);
+    if (c == 0) sums[g] = t;
+  }
+  float s = 0.0f;
+  if (i < P)
+    // (eight partials in flight per thread, added in the order of the plain loop: same bits)
+    for (int w = g; w < n_parts; w += 16 * 8) {
+      float v[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = (w + 16 * k < n_parts) ? part[(size_t)(w + 16 * k) * part_ld + i] : 0.0f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (w + 16 * k < n_parts) s += v[k];
+    }
+  sm[g][c] = s;
+  __syncthreads();
+  if (g == 0 && i < P) {
+    float t[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) t[k] = sm[k][c];
+#pragma unroll
+    for (int st = 1; st < 16; st <<= 1)
+#pragma unroll
+      for (int k = 0; k + st < 16; k += 2 * st) t[k] += t[k + st];
+    float o = t[0];
+    if (scale) {
+      o *= inv_n;
+      if (i >= ols) o -= (penalized ? (float)state[ST_CR] : 1.0f) * ent_reg;
+    }
+    vec[i] = o;
+  }
+}
+
+// The gate: kl = sum kl / n of the parameters this iteration measured.  Within kl_lim the step is taken (Adam's t and the
+// count of steps advance here, in front of the update kernel); beyond it -- or not a number: the test is the positive one --
+// the 1-based index of the iteration becomes the sticky stop word and everything enqueued behind returns at entry.
+__global__ void ppo_gate_kernel(double *state, const double *sums, int iter, double kl_lim) {
+  if (threadIdx.x != 0 || state[ST_STOP] != 0.0) return;
+  const double kl = sums[3] / sums[0];
+  state[ST_KL] = kl;
+  state[ST_CLIP] = sums[5];
+  if (iter == 1)
+    for (int k = 0; k < 8; ++k) state[ST_PRE + k] = sums[k];
+  if (kl <= kl_lim) {
+    state[ST_ADAM_T] += 1.0;
+    state[ST_ITERS] += 1.0;
+  } else {
+    state[ST_STOP] = (double)iter;
+  }
+}
+
+__global__ void ppo_begin_kernel(double *state) {
+  if (threadIdx.x == 0) state[ST_STOP] = state[ST_ITERS] = state[ST_KL] = state[ST_CLIP] = 0.0;
+  if (threadIdx.x < 16) state[ST_PRE + threadIdx.x] = 0.0;
+}
+
+__global__ void ppo_post_kernel(double *state, const double *sums) {
+  if (threadIdx.x < 8) state[ST_POST + threadIdx.x] = sums[threadIdx.x];
+}
+
+// softplus(x) = log(1 + e^x), its derivative the logistic function (float64, stable on both sides)
+__device__ __forceinline__ double softplus_d(double x) { return x > 0.0 ? x + log1p(exp(-x)) : log1p(exp(x)); }
+__device__ __forceinline__ double sigmoid_d(double x) { return x > 0.0 ? 1.0 / (1.0 + exp(-x)) : exp(x) / (1.0 + exp(x)); }
+
+// penalty_loss = -penalty_param (cur_cost - cost_lim)  (or -softplus(penalty_param) (...)); one TF-Adam step on the scalar
+__global__ void ppo_penalty_kernel(double *state, const double *sums, double cost_lim, double max_path_length, double lr,
+                                   int param_loss, double b1, double b2, double eps) {
+  if (threadIdx.x != 0) return;
+  double x = state[ST_PEN_PARAM];
+  if (sums != nullptr) {      // (NULL: refresh only -- penalty, c_r, c_c of the penalty_param the block holds)
+    const double cur_cost = sums[4] / sums[0] * max_path_length;      // cpo_policy.py:533
+    const double g = param_loss ? -(cur_cost - cost_lim) : -sigmoid_d(x) * (cur_cost - cost_lim);
+    const double t = state[ST_PEN_T] + 1.0;
+    const double m = state[ST_PEN_M] + (g - state[ST_PEN_M]) * (1.0 - b1);
+    const double v = state[ST_PEN_V] + (g * g - state[ST_PEN_V]) * (1.0 - b2);
+    const double lr_t = lr * sqrt(1.0 - pow(b2, t)) / (1.0 - pow(b1, t));
+    x -= lr_t * m / (sqrt(v) + eps);
+    state[ST_PEN_PARAM] = x; state[ST_PEN_M] = m; state[ST_PEN_V] = v; state[ST_PEN_T] = t;
+  }
+  const double pen = softplus_d(x);
+  state[ST_PENALTY] = pen;
+  state[ST_CR] = 1.0 / (1.0 + pen);
+  state[ST_CC] = pen / (1.0 + pen);
+}
+
+__global__ void pack_all_gated_kernel(float *dst, const float *flat, const PackPlan plan, u32x4 *dst16, const double *state) {
+  if (state[ST_STOP] != 0.0) return;
+  pack_all_body(dst, flat, plan, dst16);
+}
+
 }  // namespace
 
 struct cmbpo_pi {
@@ -764,6 +938,10 @@ struct cmbpo_pi {
   const float *act_obs;   // the batch the saved activations belong to
   int act_n;
   long act_hits;          // Fisher-vector products that read the saved activations (diagnostics)
+  // first-order updates (MODE_PPO): allocated by the first such call, so that a trust-region handle holds what it always held
+  double *ppo_part;       // [2 n_cu][8] per-workgroup loss sums
+  double *ppo_sums;       // [8] the loop's own sums (callers of cmbpo_pi_ppo_grad bring theirs)
+  float *ppo_g;           // [part_ld] the loop's gradient
 };
 
 namespace {
@@ -787,7 +965,7 @@ PiPack pack_ptrs(const cmbpo_pi *h, const float *base) {
 // 0: every product as fp32 MFMAs (round 1); 1: the 128 x 128 products as three f16 MFMAs on split operands
 int g_pi_path = 1;
 
-int do_pack(const cmbpo_pi *h, float *dst, const float *flat, hipStream_t s) {
+int do_pack(const cmbpo_pi *h, float *dst, const float *flat, hipStream_t s, const double *gate = nullptr) {
   const PiDims &d = h->d;
   CMBPO_REQUIRE((reinterpret_cast<uintptr_t>(flat) & 15u) == 0, "policy pack: the flat vector must be 16-byte aligned");
   PackPlan plan;
@@ -831,8 +1009,12 @@ int do_pack(const cmbpo_pi *h, float *dst, const float *flat, hipStream_t s) {
   }
   plan.img_blk[ni] = blk;
   plan.n_img = ni;
-  hipLaunchKernelGGL(pack_all_kernel, dim3(plan.nb32 + 1 + blk), dim3(256), 0, s, dst, flat, plan,
-                     h->blob16 + (params ? 0 : H16_PACK));
+  if (gate != nullptr)      // the first-order loop: a stopped loop packs nothing
+    hipLaunchKernelGGL(pack_all_gated_kernel, dim3(plan.nb32 + 1 + blk), dim3(256), 0, s, dst, flat, plan,
+                       h->blob16 + (params ? 0 : H16_PACK), gate);
+  else
+    hipLaunchKernelGGL(pack_all_kernel, dim3(plan.nb32 + 1 + blk), dim3(256), 0, s, dst, flat, plan,
+                       h->blob16 + (params ? 0 : H16_PACK));
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -861,11 +1043,13 @@ int launch_pi_k(cmbpo_pi *h, PiArgs &a, hipStream_t s, KERN kern, bool f16, bool
 
 template <int MODE, int N_IT>
 int launch_pi_n(cmbpo_pi *h, PiArgs &a, hipStream_t s) {
-  if (h->d.H == 256) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 256>, false, MODE != MODE_EVAL);
-  if (g_pi_path == 0) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 128>, false, MODE != MODE_EVAL);
-  if (MODE == MODE_FVP && a.cache_r != nullptr)
-    return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, true>, true, MODE != MODE_EVAL);
-  return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, false>, true, MODE != MODE_EVAL);
+  if (h->d.H == 256) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 256>, false, MODE == MODE_GRAD || MODE == MODE_FVP);
+  if (g_pi_path == 0) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 128>, false, MODE == MODE_GRAD || MODE == MODE_FVP);
+  if constexpr (MODE != MODE_PPO) {
+    if (MODE == MODE_FVP && a.cache_r != nullptr)
+      return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, true>, true, MODE == MODE_GRAD || MODE == MODE_FVP);
+  }
+  return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, false>, true, MODE == MODE_GRAD || MODE == MODE_FVP);
 }
 
 template <int MODE>
@@ -951,6 +1135,7 @@ extern "C" int cmbpo_pi_create(cmbpo_pi_t **out, int obs_dim, int hidden, int ac
   h->part_ld = (d.P + 63) / 64 * 64;
   h->parts = nullptr;
   h->blob16 = nullptr;
+  h->ppo_part = nullptr; h->ppo_sums = nullptr; h->ppo_g = nullptr;
   if (hipMalloc(reinterpret_cast<void **>(&h->blob), 2 * off * sizeof(float)) != hipSuccess ||
       hipMalloc(reinterpret_cast<void **>(&h->blob16), (size_t)2 * H16_PACK * sizeof(u32x4)) != hipSuccess ||
       hipMalloc(reinterpret_cast<void **>(&h->parts), (size_t)2 * h->n_cu * h->part_ld * sizeof(float)) != hipSuccess ||
@@ -975,6 +1160,9 @@ extern "C" void cmbpo_pi_destroy(cmbpo_pi_t *h) {
   if (h->cg_z) (void)hipFree(h->cg_z);
   if (h->cg_part) (void)hipFree(h->cg_part);
   if (h->act) (void)hipFree(h->act);
+  if (h->ppo_part) (void)hipFree(h->ppo_part);
+  if (h->ppo_sums) (void)hipFree(h->ppo_sums);
+  if (h->ppo_g) (void)hipFree(h->ppo_g);
   delete h;
 }
 
@@ -1073,4 +1261,94 @@ extern "C" int cmbpo_pi_eval(cmbpo_pi_t *h, const cmbpo_pi_batch_t *b, double *d
   CMBPO_HIP_CHECK(hipMemsetAsync(d_sums, 0, 8 * sizeof(double), s));
   a.vec = nullptr; a.sums = d_sums;
   return launch_pi<MODE_EVAL>(h, a, s);
+}
+
+// ---- first-order penalised updates (PPO-Lagrangian) ---------------------------------------------------------------------
+namespace {
+
+int ppo_check_cfg(const cmbpo_pi_ppo_cfg_t *c, const char *who) {
+  CMBPO_REQUIRE(c != nullptr, "%s: cfg is NULL", who);
+  CMBPO_REQUIRE(c->clip_ratio >= 0.0f && c->clip_ratio < 1.0f, "%s: clip_ratio %g not in [0, 1)", who, (double)c->clip_ratio);
+  return CMBPO_OK;
+}
+
+// the handle's first-order buffers
+int ppo_reserve(cmbpo_pi *h, const char *who) {
+  CMBPO_REQUIRE(h != nullptr, "%s: NULL handle", who);
+  if (h->ppo_part == nullptr) {
+    if (hipMalloc(reinterpret_cast<void **>(&h->ppo_part), (size_t)2 * h->n_cu * 8 * sizeof(double)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&h->ppo_sums), 8 * sizeof(double)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&h->ppo_g), (size_t)h->part_ld * sizeof(float)) != hipSuccess) {
+      (void)hipGetLastError();
+      if (h->ppo_part) (void)hipFree(h->ppo_part);
+      if (h->ppo_sums) (void)hipFree(h->ppo_sums);
+      h->ppo_part = nullptr; h->ppo_sums = nullptr; h->ppo_g = nullptr;
+      cmbpo_set_error("%s: hipMalloc failed", who);
+      return CMBPO_ENOMEM;
+    }
+  }
+  return CMBPO_OK;
+}
+
+// one MODE_PPO pass and its reduction: the raw gradient sum (scale == 0) or the loop's scaled form
+int ppo_pass(cmbpo_pi *h, const cmbpo_pi_batch_t *b, const cmbpo_pi_ppo_cfg_t *c, const double *d_state, float *d_vec,
+             double *d_sums, int scale, int gated, hipStream_t s, const char *who) {
+  PiArgs a{};
+  if (int rc = fill_args(h, b, a, who)) return rc;
+  CMBPO_REQUIRE(b->act && b->adv && b->cadv && b->logp_old && b->cost && b->mu_old && b->logstd_old, "%s: NULL buffer", who);
+  a.which = 0; a.vec = d_vec; a.sums = nullptr;
+  a.state = d_state; a.sums_part = h->ppo_part; a.clip = c->clip_ratio;
+  a.ppo_flags = (c->clipped_adv ? PPO_CLIPPED : 0) | (c->objective_penalized ? PPO_PENALIZED : 0) | (gated ? PPO_GATED : 0);
+  if (int rc = launch_pi<MODE_PPO>(h, a, s)) return rc;
+  hipLaunchKernelGGL(ppo_reduce_kernel, dim3(cmbpo_ceil_div(h->d.P, 64)), dim3(1024), 0, s, h->parts, h->part_ld, h->last_grid,
+                     h->d.P, d_vec, scale, (float)(1.0 / (double)b->n), c->ent_reg, h->d.ols, c->objective_penalized ? 1 : 0,
+                     d_state, gated, h->ppo_part, d_sums);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
+}  // namespace
+
+extern "C" int cmbpo_pi_ppo_grad(cmbpo_pi_t *h, const cmbpo_pi_batch_t *b, const cmbpo_pi_ppo_cfg_t *cfg, const double *d_state,
+                                 float *d_vec, double *d_sums, void *stream) {
+  if (int rc = ppo_check_cfg(cfg, "cmbpo_pi_ppo_grad")) return rc;
+  CMBPO_REQUIRE(d_state && d_vec && d_sums, "cmbpo_pi_ppo_grad: NULL buffer");
+  if (int rc = ppo_reserve(h, "cmbpo_pi_ppo_grad")) return rc;
+  return ppo_pass(h, b, cfg, d_state, d_vec, d_sums, 0, 0, (hipStream_t)stream, "cmbpo_pi_ppo_grad");
+}
+
+extern "C" int cmbpo_ppo_penalty_step(double *d_state, const double *d_sums, double cost_lim, double max_path_length,
+                                      double penalty_lr, int penalty_param_loss, void *stream) {
+  CMBPO_REQUIRE(d_state != nullptr, "cmbpo_ppo_penalty_step: d_state is NULL");
+  hipLaunchKernelGGL(ppo_penalty_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_state, d_sums, cost_lim,
+                     max_path_length, penalty_lr, penalty_param_loss, 0.9, 0.999, 1e-8);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
+extern "C" int cmbpo_pi_ppo_run(cmbpo_pi_t *h, const cmbpo_pi_batch_t *b, const cmbpo_pi_ppo_cfg_t *cfg, float *d_theta,
+                                float *d_m, float *d_v, double *d_state, int iters, void *stream) {
+  if (int rc = ppo_check_cfg(cfg, "cmbpo_pi_ppo_run")) return rc;
+  CMBPO_REQUIRE(h && d_theta && d_m && d_v && d_state, "cmbpo_pi_ppo_run: NULL buffer");
+  CMBPO_REQUIRE(iters >= 1, "cmbpo_pi_ppo_run: iters %d < 1", iters);
+  if (int rc = ppo_reserve(h, "cmbpo_pi_ppo_run")) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ppo_begin_kernel, dim3(1), dim3(64), 0, s, d_state);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  const double kl_lim = (double)cfg->kl_margin * (double)cfg->target_kl;
+  for (int it = 1; it <= iters; ++it) {
+    if (int rc = ppo_pass(h, b, cfg, d_state, h->ppo_g, h->ppo_sums, 1, 1, s, "cmbpo_pi_ppo_run")) return rc;
+    hipLaunchKernelGGL(ppo_gate_kernel, dim3(1), dim3(64), 0, s, d_state, h->ppo_sums, it, kl_lim);
+    CMBPO_HIP_CHECK(hipGetLastError());
+    if (int rc = cmbpo_vec_adam_apply(h->d.P, h->ppo_g, d_m, d_v, d_theta, d_state, cfg->pi_lr, cfg->beta1, cfg->beta2,
+                                      cfg->adam_eps, 1, s))
+      return rc;
+    if (int rc = do_pack(h, h->blob, d_theta, s, d_state)) return rc;
+    h->act_valid = false;
+  }
+  // the measures at the parameters that survived
+  if (int rc = cmbpo_pi_eval(h, b, h->ppo_sums, stream)) return rc;
+  hipLaunchKernelGGL(ppo_post_kernel, dim3(1), dim3(64), 0, s, d_state, h->ppo_sums);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
 }

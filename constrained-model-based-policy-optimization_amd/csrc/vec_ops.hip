@@ -92,7 +92,47 @@ __global__ __launch_bounds__(kT) void dots_kernel(int P, int n, const DotArgs a,
   }
 }
 
+// tf.train.AdamOptimizer on the flat vector (the form of ens_train.hip): m += (g - m)(1 - b1); v += (g^2 - v)(1 - b2);
+// theta -= lr_t m / (sqrt(v) + eps), lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) at the t the state block holds (advanced in
+// front of this kernel, by adam_advance_kernel or by the first-order loop's gate)
+__global__ __launch_bounds__(256) void adam_kernel(int P, const float *g, float *m, float *v, float *theta, const double *state,
+                                                   float lr, float b1, float b2, float eps, int gated) {
+  if (gated && state[ST_STOP] != 0.0) return;
+  const double t = state[ST_ADAM_T];
+  const float lr_t = (float)((double)lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= P) return;
+  const float gi = g[i];
+  float mi = m[i], vi = v[i];
+  mi += (gi - mi) * (1.0f - b1);
+  vi += (gi * gi - vi) * (1.0f - b2);
+  theta[i] -= lr_t * mi / (sqrtf(vi) + eps);
+  m[i] = mi;
+  v[i] = vi;
+}
+
+__global__ void adam_advance_kernel(double *state) {
+  if (threadIdx.x == 0) state[ST_ADAM_T] += 1.0;
+}
+
 }  // namespace
+
+int cmbpo_vec_adam_apply(int P, const float *d_g, float *d_m, float *d_v, float *d_theta, const double *d_state, float lr,
+                         float beta1, float beta2, float eps, int gated, hipStream_t stream) {
+  hipLaunchKernelGGL(adam_kernel, dim3(cmbpo_ceil_div(P, 256)), dim3(256), 0, stream, P, d_g, d_m, d_v, d_theta, d_state, lr,
+                     beta1, beta2, eps, gated);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
+extern "C" int cmbpo_vec_adam_step(int P, const float *d_g, float *d_m, float *d_v, float *d_theta, double *d_state, float lr,
+                                   float beta1, float beta2, float eps, void *stream) {
+  CMBPO_REQUIRE(P >= 1 && d_g && d_m && d_v && d_theta && d_state, "cmbpo_vec_adam_step: bad argument");
+  CMBPO_REQUIRE(beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f, "cmbpo_vec_adam_step: betas not in [0, 1)");
+  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_state);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return cmbpo_vec_adam_apply(P, d_g, d_m, d_v, d_theta, d_state, lr, beta1, beta2, eps, 0, (hipStream_t)stream);
+}
 
 extern "C" int cmbpo_cg_init(int P, const float *d_b, float *d_x, float *d_r, float *d_p, double *d_scal, void *stream) {
   CMBPO_REQUIRE(P >= 1 && d_b && d_x && d_r && d_p && d_scal, "cmbpo_cg_init: bad argument");

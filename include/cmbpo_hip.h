@@ -603,6 +603,57 @@ int cmbpo_vec_lincomb(int P, float a, const float *d_x, float b, const float *d_
  * host arrays of device pointers. */
 int cmbpo_vec_dots(int P, int n, const float *const *h_x, const float *const *h_y, double *d_out, void *stream);
 
+/* ---- first-order penalised policy updates (PPO-Lagrangian; the `first_order` family that the reference's Agent declares,
+ * policies/cpo_policy.py:30-123, and its graph builder leaves unimplemented, :568-569) -------------------------------
+ * pi_objective = mean(clipped_adv ? min(ratio adv, min_adv) : ratio adv) + ent_reg entropy, with
+ * min_adv = adv > 0 ? (1 + clip) adv : (1 - clip) adv; with objective_penalized it becomes
+ * (pi_objective - penalty mean(ratio cadv)) / (1 + penalty); pi_loss = -pi_objective.
+ *
+ * d_state: CMBPO_PPO_STATE_DOUBLES doubles on the device, owned by the caller, zeroed once, persistent across updates:
+ *   [0]      stop word: 0 while the loop runs; the 1-based index of the iteration whose KL exceeded
+ *            kl_margin * target_kl once it has stopped (that iteration's step is not taken)
+ *   [1]      steps taken by the current / last cmbpo_pi_ppo_run
+ *   [2]      KL of the last iteration that was evaluated
+ *   [3]      Adam t of the parameter vector (advances only when a step is taken)
+ *   [4..7]   penalty_param, its Adam m, v, t
+ *   [8..10]  penalty = softplus(penalty_param), c_r = 1 / (1 + penalty), c_c = penalty / (1 + penalty)
+ *   [11..18] the loss sums of the first iteration of the last run (the "pre" measures), layout below
+ *   [19..26] the cmbpo_pi_eval sums at the final parameters of the last run (the "post" measures)
+ *   [27]     clip count of the last iteration that was evaluated;  [28..31] reserved
+ * Loss sums of a MODE_PPO pass, d_sums[8] = {n, sum objective term, sum ratio cadv, sum_n sum_a kl, sum cost,
+ * number of samples whose advantage term is clipped away, sum ratio adv (unclipped), 0}; they are added up in
+ * workgroup order, so equal inputs give equal bits. */
+#define CMBPO_PPO_STATE_DOUBLES 32
+typedef struct cmbpo_pi_ppo_cfg {
+  float clip_ratio;
+  int32_t clipped_adv;          /* 0: plain surrogate ratio adv */
+  int32_t objective_penalized;  /* 0: c_r = 1, c_c = 0 whatever d_state holds */
+  float ent_reg;
+  float pi_lr, beta1, beta2, adam_eps;
+  float target_kl, kl_margin;
+} cmbpo_pi_ppo_cfg_t;
+
+/* One pass over the batch: d_vec = sum_n grad of the per-sample loss -c_r (active ? ratio adv : 0) + c_c ratio cadv (divide
+ * by N and subtract c_r ent_reg on the log_std block to get grad pi_loss), d_sums as above, KL included.  Reads c_r / c_c
+ * from d_state and ignores its stop word, which stays set after a run that the gate ended. */
+int cmbpo_pi_ppo_grad(cmbpo_pi_t *h, const cmbpo_pi_batch_t *b, const cmbpo_pi_ppo_cfg_t *cfg, const double *d_state,
+                      float *d_vec, double *d_sums, void *stream);
+/* tf.train.AdamOptimizer on a flat vector: t = ++d_state[3]; lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t);
+ * m += (g - m)(1 - beta1); v += (g^2 - v)(1 - beta2); theta -= lr_t m / (sqrt(v) + eps). */
+int cmbpo_vec_adam_step(int P, const float *d_g, float *d_m, float *d_v, float *d_theta, double *d_state, float lr,
+                        float beta1, float beta2, float eps, void *stream);
+/* The learned penalty: cur_cost = d_sums[4] / d_sums[0] * max_path_length (cpo_policy.py:533); penalty_loss =
+ * -penalty_param (cur_cost - cost_lim), or -softplus(penalty_param) (cur_cost - cost_lim) with penalty_param_loss == 0;
+ * one scalar Adam step (beta 0.9 / 0.999, eps 1e-8), then penalty, c_r, c_c are refreshed.  d_sums == NULL: no step,
+ * only the refresh (after penalty_param was written from outside, e.g. from a checkpoint). */
+int cmbpo_ppo_penalty_step(double *d_state, const double *d_sums, double cost_lim, double max_path_length,
+                           double penalty_lr, int penalty_param_loss, void *stream);
+/* `iters` iterations of [MODE_PPO pass -> reduce, / N, entropy term -> gate -> Adam on d_theta -> pack d_theta into the
+ * handle], every launch returning at entry once the gate has set the stop word, then cmbpo_pi_eval at the parameters that
+ * survived; nothing waits for the host.  d_theta must hold the handle's current parameters (16-byte aligned). */
+int cmbpo_pi_ppo_run(cmbpo_pi_t *h, const cmbpo_pi_batch_t *b, const cmbpo_pi_ppo_cfg_t *cfg, float *d_theta,
+                     float *d_m, float *d_v, double *d_state, int iters, void *stream);
+
 /* ---- ensemble training (csrc/ens_train.hip) -------------------------
  * The TensorFlow train_op of the reference ensembles (models/pens/pe.py:252-274,312-318:
  * train_loss = sum_e loss_e + sum_l decay_l * l2_loss(W_l), tf.train.AdamOptimizer(lr)) for the
