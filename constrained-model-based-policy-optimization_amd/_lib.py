@@ -128,6 +128,7 @@ SIGNATURES.update({
     "cmbpo_buffer_moments": (_i, [_rp, _i, _p, _p]),
     "cmbpo_buffer_prepare": (_i, [_rp, _p, _p, _p]),
     "cmbpo_buffer_flatten": (_i, [_rp, _p, _p, C.POINTER(C.c_void_p), _p]),
+    "cmbpo_buffer_trust_weights": (_i, [_rp, _p, C.c_double, _p, _p]),
 })
 
 
@@ -172,6 +173,7 @@ SIGNATURES.update({
     "cmbpo_pi_fvp": (_i, [_p, _bp, _p, _p, _p]),
     "cmbpo_pi_keep_activations": (_i, [_p, _i]),
     "cmbpo_pi_saved_activation_uses": (C.c_long, [_p]),
+    "cmbpo_pi_set_sample_weights": (_i, [_p, _p, _i, _p]),
     "cmbpo_set_pi_matrix_path": (None, [_i]),
     "cmbpo_get_pi_matrix_path": (_i, []),
     "cmbpo_pi_eval": (_i, [_p, _bp, _p, _p]),

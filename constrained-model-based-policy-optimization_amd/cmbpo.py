@@ -91,7 +91,7 @@ class CMBPO:
                  model_train_kwargs=None, initial_model_train_kwargs=None, shuffle_on_device=True, device=None,
                  session=None, start_state_sampling='host', m_stochastic=False, m_iv_gae=False, m_iv_eps=1e-8,
                  m_disagreement=False, m_rew_pessimism=0.0, m_cost_pessimism=0.0,
-                 m_validate_horizon=0, m_validate_windows=1024,
+                 m_validate_horizon=0, m_validate_windows=1024, m_imagined_weight=1.0, m_trust_var=None,
                  **_unused):
         # RLAlgorithm.__init__ (algorithms/rl_algorithm.py:22-74)
         self.sampler = sampler if sampler is not None else CpoSampler(max_path_length=getattr(policy, "max_path_length", 1000))
@@ -124,6 +124,18 @@ class CMBPO:
         self._m_learn_cost = bool(m_learn_cost)
         if float(m_cost_pessimism) > 0.0 and not self._m_learn_cost:
             raise ValueError("m_cost_pessimism > 0 needs m_learn_cost=True: only a learned cost head has an ensemble spread")
+        # trust-weighted updates: a real sample weighs 1, an imagined one m_imagined_weight, times its trust weight
+        # m_trust_var / (m_trust_var + accumulated model variance) when m_trust_var is set.  (1.0, None): no weights anywhere.
+        self._imagined_weight = float(m_imagined_weight)
+        if not (self._imagined_weight > 0.0 and np.isfinite(self._imagined_weight)):
+            raise ValueError("m_imagined_weight must be a positive finite number, got %r" % (m_imagined_weight,))
+        if m_trust_var is not None:
+            if not m_iv_gae:
+                raise ValueError("m_trust_var needs m_iv_gae=True: the accumulated model variance is only kept there")
+            if not (float(m_trust_var) > 0.0 and np.isfinite(float(m_trust_var))):
+                raise ValueError("m_trust_var must be a positive finite number or None, got %r" % (m_trust_var,))
+        self._trust_var = None if m_trust_var is None else float(m_trust_var)
+        self._weighted = bool(use_model) and (self._imagined_weight != 1.0 or self._trust_var is not None)
         self._m_train_freq = m_train_freq
         self._rollout_batch_size = int(rollout_batch_size)
         self._rollout_schedule = list(rollout_schedule)
@@ -160,6 +172,8 @@ class CMBPO:
                                          iv_eps=m_iv_eps)
             self.model_buf.initialize(pi_info_shapes, gamma=policy.gamma, lam=policy.lam, cost_gamma=policy.cost_gamma,
                                       cost_lam=policy.cost_lam)
+            if self._trust_var is not None:
+                self.model_buf.set_trust_weights(self._trust_var)
             self.model_sampler = ModelSampler(max_path_length=maxroll, batch_size=self._rollout_batch_size,
                                               logger=None, rollout_mode=self.rollout_mode,
                                               stochastic=bool(m_stochastic))
@@ -304,6 +318,7 @@ class CMBPO:
             self.times = {}
             samples_added = 0
             model_samples = None
+            model_weights = None      # (weighted updates only) one weight per row of model_samples
             keep_rolling = True
             metrics = {}
             if self._use_model:
@@ -323,6 +338,10 @@ class CMBPO:
                     model_samples_new, buffer_diagnostics_new = self.model_buf.get(as_tensors=True)
                     model_samples = [torch.cat((o, n), dim=0) for o, n in zip(model_samples, model_samples_new)] \
                         if model_samples else model_samples_new
+                    if self._weighted:
+                        w_new_rows = self.model_buf.last_weights * self._imagined_weight if self._trust_var is not None else \
+                            torch.full((len(model_samples_new[0]),), self._imagined_weight, dtype=torch.float32, device=self.device)
+                        model_weights = w_new_rows if model_weights is None else torch.cat((model_weights, w_new_rows))
                     new_n_samples = len(model_samples_new[0]) + EPS
                     w_old = samples_added / (new_n_samples + samples_added)
                     w_new = new_n_samples / (new_n_samples + samples_added)
@@ -373,10 +392,19 @@ class CMBPO:
                 train_samples = [torch.cat((r, m), dim=0) for r, m in zip(self._to_device(real_samples), model_samples)]
             else:
                 train_samples = real_samples
+            weights = None
+            if model_samples and model_weights is not None:
+                n_real = len(real_samples[0])
+                weights = torch.cat((torch.ones(n_real, dtype=torch.float32, device=self.device), model_weights))
+                w_imagined = float(model_weights.sum(dtype=torch.float64))
+                metrics_policy = {'policy/weight_sum_share_imagined': w_imagined / (w_imagined + n_real)}
+            else:
+                metrics_policy = {}
             policy.update_real_c(real_samples)
-            policy.update_policy(train_samples)
+            policy.update_policy(train_samples, weights=weights)
+            critic_kw = {'weights': weights} if weights is not None and getattr(policy, 'vf_weighted', False) else {}
             policy.update_critic(train_samples, train_vc=bool((train_samples[-3] > 0).any()),
-                                 shuffle_on_device=self._shuffle_on_device)
+                                 shuffle_on_device=self._shuffle_on_device, **critic_kw)
             if self._use_model:
                 self.approx_model_batch = self.batch_size_policy - n_real_samples
             self.policy_epoch += 1
@@ -385,6 +413,7 @@ class CMBPO:
 
             self.sampler.log()
             new_diagnostics = dict(self.logger.dump_tabular(print_out=False))
+            new_diagnostics.update(metrics_policy)
             new_diagnostics.update(OrderedDict((
                 *((f'times/{k}', self.times[k]) for k in sorted(self.times)),
                 *((f'model/{k}', metrics[k]) for k in sorted(metrics)),

@@ -131,6 +131,10 @@ class CPOPolicy:
                       num_elites=self.vf_elites, loss="MSE", activation="swish",
                       use_scaler_in=True, use_scaler_out=True, device=self.device, lr=self.vf_lr,
                       decay=self.vf_decay)
+        # vf_weighted: both critics take per-sample weights in their training loss (update_critic(weights=))
+        self.vf_weighted = bool(kw.get("vf_weighted", False))
+        if self.vf_weighted:
+            common["weighted"] = True
         self.v = PE(self.obs_dim, 1, name="VEnsemble", clip_loss=self.vf_cliploss, kl_cliprange=self.vf_cliprange, **common)
         self.vc = PE(self.obs_dim, 1, name="VCEnsemble", clip_loss=self.vf_cliploss, kl_cliprange=self.cvf_cliprange, **common)
         # pi_info placeholders' shapes (network/ac_network.py:113,120; algorithms/cmbpo.py:94)
@@ -168,10 +172,10 @@ class CPOPolicy:
             self._ops_version = self.actor.version
 
     # -- update (policies/cpo_policy.py:600-656, 733-754, 837-845) ------------------------------------
-    def _bind(self, buf_inputs):
+    def _bind(self, buf_inputs, weights=None):
         # buf_fields order (cpo_policy.py:472-477): obs, act, adv, cadv, ret, cret, logp_old, v, vc, cost, log_std, mu
         obs, act, adv, cadv, _ret, _cret, logp_old, _v, _vc, cost, log_std, mu = buf_inputs
-        self.ops.bind(obs, act, adv, cadv, logp_old, cost, mu, log_std)
+        self.ops.bind(obs, act, adv, cadv, logp_old, cost, mu, log_std, weights=weights)
 
     def update_real_c(self, buf_inputs):
         """cpo_policy.py:733-737: running window of real epoch costs that drives the margin."""
@@ -180,10 +184,11 @@ class CPOPolicy:
         self.real_c_buffer.append(m * self.max_path_length)
         self.real_c_buffer.pop(0)
 
-    def update_policy(self, buf_inputs):
-        """cpo_policy.py:600-656: pre-measures, CPOAgent.update_pi, post-measures and deltas."""
+    def update_policy(self, buf_inputs, weights=None):
+        """cpo_policy.py:600-656: pre-measures, CPOAgent.update_pi, post-measures and deltas.  ``weights`` ([n], >= 0):
+        a sample of weight w counts as w copies of itself in the whole update (PolicyOps.bind)."""
         self._sync_ops()
-        self._bind(buf_inputs)
+        self._bind(buf_inputs, weights)
         info = self.agent.update_pi(self.ops, self.target_kl, self.cost_lim, self.real_c_buffer)
         # (the batch's mean cost comes out of the update's own loss kernel -- the same sum, over every rank's samples --
         # instead of a reduction and a blocking read of their own in front of it)
@@ -202,10 +207,10 @@ class CPOPolicy:
         self.logger.store(KL=post["KL"], **deltas)
         return info
 
-    def run_diagnostics(self, buf_inputs):
-        """cpo_policy.py:739-754: actor measures and both critic validation losses."""
+    def run_diagnostics(self, buf_inputs, weights=None):
+        """cpo_policy.py:739-754: actor measures (weighted means under ``weights``) and both critic validation losses."""
         self._sync_ops()
-        self._bind(buf_inputs)
+        self._bind(buf_inputs, weights)
         m = self.agent.measures(self.ops)
         out = dict(LossPi=m["LossPi"], SurrCost=m["SurrCost"], Entropy=m["Entropy"])
         if self.v.finalized and self.vc.finalized:
@@ -226,16 +231,21 @@ class CPOPolicy:
             return np.array([one(o, m, l) for o, m, l in zip(obs_batch, mu_batch, logstd_batch)])
         return one(obs_batch, mu_batch, logstd_batch)
 
-    def update_critic(self, buf_inputs, train_vc=True, **kwargs):
+    def update_critic(self, buf_inputs, weights=None, train_vc=True, **kwargs):
         """cpo_policy.py:658-698: loss measures, train the return critic (and the cost critic) on the buffer, loss
         measures again, deltas to the logger.  ``kwargs`` override vf_train_kwargs (and may carry ``rng`` /
-        ``shuffle_on_device`` for PE.train)."""
+        ``shuffle_on_device`` for PE.train).  ``weights`` ([n]): per-sample weights of both training losses (PE.train);
+        the policy must have been built with ``vf_weighted=True``."""
+        if weights is not None and not self.vf_weighted:
+            raise ValueError("update_critic(weights=): the policy was built without vf_weighted=True")
         obs, ret, cret = buf_inputs[0], buf_inputs[4], buf_inputs[5]
         pre = self.compute_v_losses(buf_inputs)
         self.logger.store(**pre)
         train_kwargs = self.vf_train_kwargs.copy()
         train_kwargs.update(kwargs)
         old_v, old_vc = (buf_inputs[7], buf_inputs[8]) if self.vf_cliploss else (None, None)
+        if weights is not None:
+            train_kwargs["weights"] = weights
         self.train_vf(obs, ret, old_v=old_v, **train_kwargs)
         if train_vc:
             self.train_vc(obs, cret, old_vc=old_vc, **train_kwargs)

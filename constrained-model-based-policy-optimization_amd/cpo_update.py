@@ -89,6 +89,7 @@ class PolicyOps:
         self.scal = torch.zeros(16, dtype=torch.float64, device=self.device)   # [0] cg r.r ; [8..] dot products
         self.batch = _lib.PiBatchStruct()
         self._keep = None
+        self._w, self.w_sum = None, None      # the bound batch's sample weights and their (global) sum
         self.n_global = 0
 
     # first-order updates: Adam moments of the flat vector, the loop's state block (penalty_param and its moments included)
@@ -162,14 +163,37 @@ class PolicyOps:
     def get_params(self):
         return self.params.cpu().numpy()
 
-    def bind(self, obs, act, adv, cadv, logp_old, cost, mu_old, logstd_old):
-        """Bind the actor feed (actor_phs, cpo_policy.py:479-487); arrays stay on the device for the whole update."""
+    def bind(self, obs, act, adv, cadv, logp_old, cost, mu_old, logstd_old, weights=None):
+        """Bind the actor feed (actor_phs, cpo_policy.py:479-487); arrays stay on the device for the whole update.
+
+        ``weights`` ([n], finite, >= 0, sum > 0): a sample of weight w counts as w copies of itself in every kernel of the
+        update, and the normaliser becomes W = sum w.  Every bind sets or clears the handle's weights."""
         def dev(x):
             t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=F32))
             return t.to(self.device, torch.float32).contiguous()
         ts = [dev(x) for x in (obs, act, adv, cadv, logp_old, cost, mu_old, logstd_old)]
         n = ts[0].shape[0]
         assert ts[0].shape == (n, self.D) and ts[1].shape == (n, self.A) and ts[6].shape == (n, self.A)
+        w, w_sum = None, None
+        if weights is not None:
+            if tuple(weights.shape) != (n,):
+                raise ValueError("weights: shape %r, the batch has %d samples" % (tuple(weights.shape), n))
+            with torch.cuda.device(self.device):
+                w = dev(weights)
+                # one read: [entries that are not finite or < 0, float64 sum of the rest]
+                bad = ~(torch.isfinite(w) & (w >= 0))
+                chk = torch.stack([bad.sum().to(torch.float64),
+                                   torch.where(bad, torch.zeros_like(w), w).sum(dtype=torch.float64)]).cpu().tolist()
+            if self.comm is not None:      # (every rank raises, or none: nobody is left waiting in an all-reduce)
+                chk = self.comm.all_reduce_host(chk)
+            if chk[0]:
+                raise ValueError("weights must be finite and >= 0")
+            w_sum = float(chk[1])
+            if not (np.isfinite(w_sum) and w_sum > 0):
+                raise ValueError("weights must have a positive finite sum (got %r)" % (w_sum,))
+        _lib.check(_lib.lib().cmbpo_pi_set_sample_weights(self._h, None if w is None else w.data_ptr(), n, self._s()),
+                   "cmbpo_pi_set_sample_weights")
+        self._w, self.w_sum = w, w_sum
         self._keep = ts
         b = self.batch
         b.n, b.obs_dim, b.act_dim = n, self.D, self.A
@@ -179,7 +203,11 @@ class PolicyOps:
         # a new feed: whatever activations the handle saved belong to the previous one
         _lib.check(_lib.lib().cmbpo_pi_keep_activations(self._h, 1 if self.keep_activations else 0),
                    "cmbpo_pi_keep_activations")
-        self.n_global = n if self.comm is None else int(self.comm.all_reduce_host([n])[0])
+        # the normaliser of every mean: the sample count, or the weights' sum
+        if w_sum is not None:
+            self.n_global = w_sum
+        else:
+            self.n_global = n if self.comm is None else int(self.comm.all_reduce_host([n])[0])
 
     def _reduce(self, *tensors):
         if self.comm is not None and self.comm.world > 1:
@@ -278,8 +306,12 @@ class PolicyOps:
         with torch.cuda.device(self.device):
             if sums is None:
                 sums = self.cost_sums
-                sums[0] = float(self.n_local)
-                sums[4:5] = self._keep[5].sum(dtype=torch.float64)
+                if getattr(self, "_w", None) is None:
+                    sums[0] = float(self.n_local)
+                    sums[4:5] = self._keep[5].sum(dtype=torch.float64)
+                else:
+                    sums[0] = float(self.w_sum)
+                    sums[4:5] = (self._w.double() * self._keep[5].double()).sum()
             _lib.check(_lib.lib().cmbpo_ppo_penalty_step(self.ppo_state.data_ptr(), sums.data_ptr(), float(cost_lim),
                                                          float(max_path_length), float(penalty_lr),
                                                          int(bool(penalty_param_loss)), self._s()),

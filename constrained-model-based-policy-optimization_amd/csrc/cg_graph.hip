@@ -26,6 +26,7 @@ struct CgKey {
   hipStream_t s;
   const void *act;   // saved activations the captured Fisher-vector products read (or NULL)
   int path;          // arithmetic path of the captured kernels (cmbpo_set_pi_matrix_path)
+  const void *wt;    // the handle's sample weights (or NULL): another array, or none, is another kernel argument
 };
 
 struct CgGraph {
@@ -48,12 +49,14 @@ extern "C" int cmbpo_pi_cg_solve(cmbpo_pi_t *h, const cmbpo_pi_batch_t *b, const
                                  int use_graph, void *stream) {
   CMBPO_REQUIRE(h && b && d_b && d_x && d_r && d_p && d_vec && d_scal, "cmbpo_pi_cg_solve: NULL argument");
   CMBPO_REQUIRE(iters >= 1 && iters <= 1000, "cmbpo_pi_cg_solve: iters %d", iters);
+  if (int rc = cmbpo_pi_weights_check(h, b, "cmbpo_pi_cg_solve")) return rc;      // (before the first launch)
   CgKey k;
   memset(&k, 0, sizeof(k));
   k.h = h; memcpy(&k.b, b, sizeof(k.b)); k.vec = d_vec; k.x = d_x; k.r = d_r; k.p = d_p; k.scal = d_scal;
   k.inv_n = inv_n; k.damping = damping; k.iters = iters; k.P = cmbpo_pi_num_params(h); k.s = (hipStream_t)stream;
   k.act = cmbpo_pi_act_token(h, b);
   k.path = cmbpo_get_pi_matrix_path();
+  k.wt = cmbpo_pi_weights_token(h);
   if (int rc = cmbpo_cg_init(k.P, d_b, d_x, d_r, d_p, d_scal, stream)) return rc;
   if (int rc = iteration(h, k)) return rc;            // eager: also performs any one-time kernel attribute set-up
   if (iters == 1) return cmbpo_pi_cg_commit(d_scal, stream);

@@ -10,6 +10,10 @@ void cmbpo_set_error(const char *fmt, ...);
 // the saved-activation block a Fisher-vector product on this batch would read (NULL: recompute); part of the key of a
 // captured CG graph, whose kernel arguments contain it
 const void *cmbpo_pi_act_token(const cmbpo_pi_t *h, const cmbpo_pi_batch_t *b);
+// the handle's sample weights (NULL: none): an argument of the captured kernels too, so part of the same key
+const void *cmbpo_pi_weights_token(const cmbpo_pi_t *h);
+// CMBPO_EINVAL with the error set when the handle holds weights for another number of samples than the batch brings
+int cmbpo_pi_weights_check(const cmbpo_pi_t *h, const cmbpo_pi_batch_t *b, const char *who);
 // slots of the first-order loop's device state block (doubles; cmbpo_hip.h documents the layout, _lib.py mirrors it)
 enum { ST_STOP = 0, ST_ITERS = 1, ST_KL = 2, ST_ADAM_T = 3, ST_PEN_PARAM = 4, ST_PEN_M = 5, ST_PEN_V = 6, ST_PEN_T = 7,
        ST_PENALTY = 8, ST_CR = 9, ST_CC = 10, ST_PRE = 11, ST_POST = 19, ST_CLIP = 27 };

@@ -287,7 +287,10 @@ __device__ __forceinline__ void wgrad_s(f32x16 &g, const float *X, int sx, int i
 }
 
 // ---- the kernel --------------------------------------------------------------------------------------------------------
-template <int MODE, int N_IT, bool CACHED>
+// WT: per-sample weights, as in pi_kernel.  The weighted cotangent needs no lift of its own: the tile maximum |cot| is taken
+// from the values the element phase writes, weight included, and the bound on delta2 is built on that maximum; dh1 and dh2
+// belong to the JVP chain, which no weight enters.
+template <int MODE, int N_IT, bool CACHED, bool WT = false>
 __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
   using ST = Stream<MODE, N_IT, CACHED>;
   constexpr int S0 = 2 * N_IT;          // slabs of the input layer (K = 32 N_IT >= D, zero padded)
@@ -343,6 +346,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
   double s_n = 0, s_ra = 0, s_rc = 0, s_kl = 0, s_cost = 0;
   double s_obj = 0;     // MODE_PPO: the clipped objective ...
   int s_nclip = 0;      // ... and the samples whose advantage term is clipped away
+  float s_clipw = 0.0f; // (WT: their weights; one thread adds a few hundred at most)
   float ppo_cr = 1.0f, ppo_cc = 0.0f;
   if constexpr (MODE == MODE_PPO) {
     if (p.ppo_flags & PPO_PENALIZED) {
@@ -410,10 +414,11 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
   }
   // with the saved activations the only batch column a product reads is log_std_old: fetched one tile ahead like x, so that
   // the barrier that waits for the activations (vmcnt(0)) finds no younger load of this tile in front of it
-  float lso_pre = 0.0f;
+  float lso_pre = 0.0f, w_pre = 0.0f;      // (WT: the sample's weight travels with it)
   auto fetch_lso = [&](int t, int tid) {
     const int er0 = t * BB + (tid & 31), a0 = tid >> 5;
     lso_pre = (er0 < p.n && a0 < d.A) ? p.ls_old[(size_t)er0 * d.A + a0] : 0.0f;
+    if constexpr (WT && !CMBPO_PI_WT_LATE) w_pre = (er0 < p.n) ? p.wt[er0] : 0.0f;
   };
   if constexpr (ACT_DMA) {
     if ((int)blockIdx.x < n_tiles) fetch_lso(blockIdx.x, tid0);
@@ -460,9 +465,11 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
     // per-sample batch columns: requested now, used in the element phase
     float lso0 = 0.0f;
     float e_act0 = 0.0f, e_mu0 = 0.0f, e_logp = 0.0f, e_adv = 0.0f, e_cadv = 0.0f;
+    float e_w = 0.0f;      // WT: this thread's sample weight
     {
       const int er0 = row0 + (tid & 31), a0 = tid >> 5;
       if (er0 < p.n) {
+        if constexpr (WT && !CMBPO_PI_WT_LATE && !ACT_DMA) e_w = p.wt[er0];
         if constexpr (MODE != MODE_FVP) {
           e_logp = p.logp_old[er0];
           e_adv = p.adv[er0];
@@ -483,6 +490,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
       // the first tile) and has had the rest of that tile and this tile's staging to arrive: THIS barrier publishes it (the
       // barrier that ends a tile, a few hundred cycles after the request, waited ~14 % of a tile for it)
       lso0 = lso_pre;
+      if constexpr (WT && !CMBPO_PI_WT_LATE) e_w = w_pre;
       __syncthreads();
       asm volatile("" ::"v"(warm));   // the previous tile's warm-up load must be issued, its value is not used
       t_x = pow2_lift(__uint_as_float(mx[0]));
@@ -602,6 +610,8 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
     // ---- element phase over (a, b): this thread owns b = tid & 31, a = tid/32 + 8*it ------------------
     const int eb = tid & 31, er = row0 + eb;
     const bool valid = er < p.n;
+    float sw = 1.0f;      // WT: the weight of sample er (0 past the batch end)
+    if constexpr (WT) sw = CMBPO_PI_WT_LATE ? (valid ? p.wt[er] : 0.0f) : e_w;
     float z_[4], mu_[4];
     float cmax = 0.0f;      // largest |cotangent| this thread writes
 #pragma unroll
@@ -620,8 +630,13 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
             // d2 KL / d mu^2 = 1 / (exp(2 ls_old) + eps)   (network/ac_network.py:52-53)
             const float lso = (it == 0) ? lso0 : p.ls_old[(size_t)er * d.A + a];
             const float v1 = expf(2.0f * lso) + 1e-8f;
-            cot = m / v1;
-            glsp[it] += c_e2[a] / v1;                           // d2 KL / d log_std^2 = 2 exp(2 ls) / (...)
+            if constexpr (WT) {                                 // (a weight of 1 leaves every bit where it was)
+              cot = (sw * m) / v1;
+              glsp[it] += sw * (c_e2[a] / v1);
+            } else {
+              cot = m / v1;
+              glsp[it] += c_e2[a] / v1;                         // d2 KL / d log_std^2 = 2 exp(2 ls) / (...)
+            }
           }
           wR[eb * 36 + a] = cot;
           gb2p[it] += cot;
@@ -639,7 +654,8 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
             if constexpr (MODE == MODE_PPO) {   // the KL of the same pass, here, where mu is at hand (MODE_EVAL: second loop)
               const float lso = (it == 0) ? lso0 : p.ls_old[(size_t)er * d.A + a];
               const float dm = ((it == 0) ? e_mu0 : p.mu_old[(size_t)er * d.A + a]) - m;
-              s_kl += (double)gauss_kl_term(dm, ls, lso);
+              if constexpr (WT) s_kl += (double)(sw * gauss_kl_term(dm, ls, lso));
+              else s_kl += (double)gauss_kl_term(dm, ls, lso);
             }
           }
           wR[eb * 36 + a] = term;   // scratch: per-(b, a) log-likelihood terms
@@ -651,7 +667,8 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
       float logp = 0.0f;
       for (int a = 0; a < d.A; ++a) logp += wR[eb * 36 + a];
       const float ratio = valid ? expf(logp - e_logp) : 0.0f;                // cpo_policy.py:522
-      const float adv = e_adv, cadv = e_cadv;                                // (zero past the batch end)
+      // (zero past the batch end)  WT: the weight rides in the advantages, see pi_kernel
+      const float adv = WT ? sw * e_adv : e_adv, cadv = WT ? sw * e_cadv : e_cadv;
       float ppo_w = 0.0f;
       if constexpr (MODE == MODE_PPO) {
         float obj;
@@ -659,14 +676,16 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
         ppo_w = ppo_weight(ratio, adv, cadv, p.clip, (p.ppo_flags & PPO_CLIPPED) != 0, ppo_cr, ppo_cc, obj, active);
         if (tid < 32 && valid) {
           s_obj += (double)obj;
-          s_nclip += active ? 0 : 1;
+          if constexpr (WT) s_clipw += active ? 0.0f : sw;
+          else s_nclip += active ? 0 : 1;
         }
       }
       if (tid < 32 && valid) {
-        if constexpr (MODE != MODE_PPO) s_n += 1.0;      // (MODE_PPO counts its rows at the end: no registers for it)
+        if constexpr (MODE != MODE_PPO) s_n += WT ? (double)sw : 1.0;      // (MODE_PPO counts its rows at the end: no registers for it)
         s_ra += (double)(ratio * adv);
         s_rc += (double)(ratio * cadv);
-        s_cost += (double)p.cost[er];
+        if constexpr (WT) s_cost += (double)sw * (double)p.cost[er];
+        else s_cost += (double)p.cost[er];
       }
       lds_barrier();   // every thread has read the scratch terms before they are overwritten
 #pragma unroll
@@ -678,7 +697,8 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
               // gaussian_kl(mu, log_std, mu_old, log_std_old), ac_network.py:50-55
               const float ls = p.w.ls[a], lso = (it == 0) ? lso0 : p.ls_old[(size_t)er * d.A + a];
               const float dm = ((it == 0) ? e_mu0 : p.mu_old[(size_t)er * d.A + a]) - mu_[it];
-              s_kl += (double)gauss_kl_term(dm, ls, lso);
+              if constexpr (WT) s_kl += (double)(sw * gauss_kl_term(dm, ls, lso));
+              else s_kl += (double)gauss_kl_term(dm, ls, lso);
             }
           }
           if constexpr (MODE != MODE_EVAL) {
@@ -813,12 +833,14 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
     if (wave == 0) {
       const double n = wave_sum(s_n), ra = wave_sum(s_ra), rc = wave_sum(s_rc), c = wave_sum(s_cost);
       if constexpr (MODE == MODE_PPO) {
-        const double ob = wave_sum(s_obj), nc = wave_sum((double)s_nclip);
+        const double ob = wave_sum(s_obj), nc = wave_sum(WT ? (double)s_clipw : (double)s_nclip);
+        const double wsum = WT ? wave_sum(tile_walk_weights(p.wt, p.n, n_tiles, lane)) : 0.0;
         if (lane == 0) {
           double *sp = p.sums_part + (size_t)blockIdx.x * 8;
           int rows = 0;
-          for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) rows += min(BB, p.n - t * BB);
-          sp[0] = (double)rows; sp[1] = ob; sp[2] = rc; sp[3] = sd[0] + sd[1] + sd[2] + sd[3]; sp[4] = c; sp[5] = nc; sp[6] = ra; sp[7] = 0.0;
+          if constexpr (!WT)
+            for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) rows += min(BB, p.n - t * BB);
+          sp[0] = WT ? wsum : (double)rows; sp[1] = ob; sp[2] = rc; sp[3] = sd[0] + sd[1] + sd[2] + sd[3]; sp[4] = c; sp[5] = nc; sp[6] = ra; sp[7] = 0.0;
         }
       } else if (lane == 0) {
         atomicAdd(&p.sums[0], n);

@@ -93,7 +93,15 @@ struct PiArgs {
   double *sums_part;      // [grid][8] per-workgroup loss sums
   float clip;             // clip_ratio
   int ppo_flags;          // PPO_CLIPPED | PPO_PENALIZED | PPO_GATED
+  // the weighted instantiations only (WT; behind everything else for the same reason)
+  const float *wt;        // [n] per-sample weights (cmbpo_pi_set_sample_weights) or NULL
 };
+
+// Where a weighted instantiation requests its sample's weight: with e_logp at the top of the tile (the load's latency passes
+// behind the forward chain, one VGPR stays live across it) or in the element phase, where it is first used.
+#ifndef CMBPO_PI_WT_LATE
+#define CMBPO_PI_WT_LATE 0
+#endif
 
 // the per-sample weight of the clipped, penalised surrogate's cotangent, and what the sample adds to the objective:
 //   min_adv = adv > 0 ? (1 + clip) adv : (1 - clip) adv;  active = !clipped || ratio adv <= min_adv   (positive test: a NaN
@@ -106,6 +114,17 @@ __device__ __forceinline__ float ppo_weight(float ratio, float adv, float cadv, 
   active = !clipped || (ra <= min_adv);
   obj = active ? ra : min_adv;
   return -c_r * (active ? adv : 0.0f) + c_c * cadv;
+}
+
+// MODE_PPO with weights: this lane's share of the weights of the workgroup's tiles (a second walk over them, behind the tile
+// loop, where it costs no register: the rows can be counted from the tile walk, their weights cannot)
+__device__ __forceinline__ double tile_walk_weights(const float *wt, int n, int n_tiles, int lane) {
+  double s = 0.0;
+  for (int t = blockIdx.x + (lane >> 5) * gridDim.x; t < n_tiles; t += 2 * gridDim.x) {
+    const int r = t * BB + (lane & 31);
+    if (r < n) s += (double)wt[r];
+  }
+  return s;
 }
 
 // one (sample, action) term of gaussian_kl(mu, log_std, mu_old, log_std_old), ac_network.py:50-55; dm = mu_old - mu
@@ -243,7 +262,9 @@ __global__ void pack_all_kernel(float *dst, const float *flat, const PackPlan pl
 // Every activation image lives in LDS ONCE, in the row layout [sample][RS] (RS / 4 odd): it is the B operand of
 // the forward / JVP / backward chains (conflict-free 16-B reads, mfma_layer<.., ROWS = true>) and the A / B
 // operand of the weight-gradient MFMAs (conflict-free 4-B reads).  76.8 KB per workgroup -> two per CU.
-template <int MODE, int N_IT, int HIDT>
+// WT: per-sample weights p.wt (a sample of weight w counts as w copies of itself); instantiations of their own, the
+// unweighted ones compile to what they were.
+template <int MODE, int N_IT, int HIDT, bool WT = false>
 __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const PiArgs p) {
   // HIDT = the hidden width (128: the shipped policies; 256: configs/baseconfig/base.py's default): a wave per 32 hidden
   // units, 2 HIDT threads, images of HIDT + pad floats a row
@@ -287,6 +308,7 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
   double s_n = 0, s_ra = 0, s_rc = 0, s_kl = 0, s_cost = 0;
   double s_obj = 0;     // MODE_PPO: the clipped objective ...
   int s_nclip = 0;      // ... and the samples whose advantage term is clipped away
+  float s_clipw = 0.0f; // (WT: their weights; one thread adds a few hundred at most)
   float ppo_cr = 1.0f, ppo_cc = 0.0f;
   if constexpr (MODE == MODE_PPO) {
     if (p.ppo_flags & PPO_PENALIZED) {
@@ -352,9 +374,11 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     // that its HBM latency passes behind the JVP chain instead of between two barriers
     float lso0 = 0.0f;
     float e_act0 = 0.0f, e_mu0 = 0.0f, e_logp = 0.0f, e_adv = 0.0f, e_cadv = 0.0f;   // same for the loss terms
+    float e_w = 0.0f;                                                                // WT: this thread's sample weight
     {
       const int er0 = row0 + (tid & 31), a0 = tid >> 5;
       if (er0 < p.n) {
+        if constexpr (WT && !CMBPO_PI_WT_LATE) e_w = p.wt[er0];
         if constexpr (MODE != MODE_FVP) {
           e_logp = p.logp_old[er0];
           e_adv = p.adv[er0];
@@ -462,6 +486,8 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     // ---- element phase over (a, b): this thread owns b = tid & 31, a = tid/32 + 8*it ------------------
     const int eb = tid & 31, er = row0 + eb;
     const bool valid = er < p.n;
+    float sw = 1.0f;      // WT: the weight of sample er (0 past the batch end)
+    if constexpr (WT) sw = CMBPO_PI_WT_LATE ? (valid ? p.wt[er] : 0.0f) : e_w;
     float z_[NITE], mu_[NITE];
     float logp_part = 0.0f;
 #pragma unroll
@@ -479,8 +505,13 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
             // d2 KL / d mu^2 = 1 / (exp(2 ls_old) + eps)   (network/ac_network.py:52-53)
             const float lso = (it == 0) ? lso0 : p.ls_old[(size_t)er * d.A + a];
             const float v1 = expf(2.0f * lso) + 1e-8f;
-            cot = m / v1;
-            glsp[it] += c_e2[a] / v1;                           // d2 KL / d log_std^2 = 2 exp(2 ls) / (...)
+            if constexpr (WT) {                                 // (a weight of 1 leaves every bit where it was)
+              cot = (sw * m) / v1;
+              glsp[it] += sw * (c_e2[a] / v1);
+            } else {
+              cot = m / v1;
+              glsp[it] += c_e2[a] / v1;                         // d2 KL / d log_std^2 = 2 exp(2 ls) / (...)
+            }
           }
           wR[eb * 36 + a] = cot;
           gb2p[it] += cot;
@@ -497,7 +528,8 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
             if constexpr (MODE == MODE_PPO) {   // the KL of the same pass, here, where mu is at hand (MODE_EVAL: second loop)
               const float lso = (it == 0) ? lso0 : p.ls_old[(size_t)er * d.A + a];
               const float dm = ((it == 0) ? e_mu0 : p.mu_old[(size_t)er * d.A + a]) - m;
-              s_kl += (double)gauss_kl_term(dm, ls, lso);
+              if constexpr (WT) s_kl += (double)(sw * gauss_kl_term(dm, ls, lso));
+              else s_kl += (double)gauss_kl_term(dm, ls, lso);
             }
           }
           wR[eb * 36 + a] = term;   // scratch: per-(b, a) log-likelihood terms
@@ -509,7 +541,9 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
       float logp = logp_part;
       for (int a = 0; a < d.A; ++a) logp += wR[eb * 36 + a];
       const float ratio = valid ? expf(logp - e_logp) : 0.0f;                // cpo_policy.py:522
-      const float adv = e_adv, cadv = e_cadv;                                // (zero past the batch end)
+      // (zero past the batch end)  WT: the weight rides in the advantages -- every term below is linear in them, the clip
+      // test is scale-invariant for w > 0 and w = 0 gives an active term of 0
+      const float adv = WT ? sw * e_adv : e_adv, cadv = WT ? sw * e_cadv : e_cadv;
       float ppo_w = 0.0f;
       if constexpr (MODE == MODE_PPO) {
         float obj;
@@ -517,14 +551,16 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
         ppo_w = ppo_weight(ratio, adv, cadv, p.clip, (p.ppo_flags & PPO_CLIPPED) != 0, ppo_cr, ppo_cc, obj, active);
         if (tid < 32 && valid) {
           s_obj += (double)obj;
-          s_nclip += active ? 0 : 1;
+          if constexpr (WT) s_clipw += active ? 0.0f : sw;
+          else s_nclip += active ? 0 : 1;
         }
       }
       if (tid < 32 && valid) {
-        if constexpr (MODE != MODE_PPO) s_n += 1.0;      // (MODE_PPO counts its rows at the end: no registers for it)
+        if constexpr (MODE != MODE_PPO) s_n += WT ? (double)sw : 1.0;      // (MODE_PPO counts its rows at the end: no registers for it)
         s_ra += (double)(ratio * adv);
         s_rc += (double)(ratio * cadv);
-        s_cost += (double)p.cost[er];
+        if constexpr (WT) s_cost += (double)sw * (double)p.cost[er];
+        else s_cost += (double)p.cost[er];
       }
       __syncthreads();   // every thread has read the scratch terms before they are overwritten
 #pragma unroll
@@ -536,7 +572,8 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
               // gaussian_kl(mu, log_std, mu_old, log_std_old), ac_network.py:50-55
               const float ls = p.w.ls[a], lso = (it == 0) ? lso0 : p.ls_old[(size_t)er * d.A + a];
               const float dm = ((it == 0) ? e_mu0 : p.mu_old[(size_t)er * d.A + a]) - mu_[it];
-              s_kl += (double)gauss_kl_term(dm, ls, lso);
+              if constexpr (WT) s_kl += (double)(sw * gauss_kl_term(dm, ls, lso));
+              else s_kl += (double)gauss_kl_term(dm, ls, lso);
             }
           }
           if constexpr (MODE != MODE_EVAL) {
@@ -641,15 +678,17 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     if (wave == 0) {
       const double n = wave_sum(s_n), ra = wave_sum(s_ra), rc = wave_sum(s_rc), c = wave_sum(s_cost);
       if constexpr (MODE == MODE_PPO) {
-        const double ob = wave_sum(s_obj), nc = wave_sum((double)s_nclip);
+        const double ob = wave_sum(s_obj), nc = wave_sum(WT ? (double)s_clipw : (double)s_nclip);
+        const double wsum = WT ? wave_sum(tile_walk_weights(p.wt, p.n, n_tiles, lane)) : 0.0;
         if (lane == 0) {
           double klt = sd[0];
 #pragma unroll
           for (int wv = 1; wv < NW; ++wv) klt += sd[wv];
           double *sp = p.sums_part + (size_t)blockIdx.x * 8;
           int rows = 0;
-          for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) rows += min(BB, p.n - t * BB);
-          sp[0] = (double)rows; sp[1] = ob; sp[2] = rc; sp[3] = klt; sp[4] = c; sp[5] = nc; sp[6] = ra; sp[7] = 0.0;
+          if constexpr (!WT)
+            for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) rows += min(BB, p.n - t * BB);
+          sp[0] = WT ? wsum : (double)rows; sp[1] = ob; sp[2] = rc; sp[3] = klt; sp[4] = c; sp[5] = nc; sp[6] = ra; sp[7] = 0.0;
         }
       } else if (lane == 0) {
         atomicAdd(&p.sums[0], n);
@@ -816,11 +855,18 @@ __global__ void cg_commit_kernel(double *scal) {
 // divides.  Workgroup 0 also adds up the workgroups' loss sums, sum k on wave k, in a fixed order.
 __global__ __launch_bounds__(1024) void ppo_reduce_kernel(const float *part, int part_ld, int n_parts, int P, float *vec, int scale,
                                                           float inv_n, float ent_reg, int ols, int penalized, const double *state,
-                                                          int gated, const double *sums_part, double *sums) {
+                                                          int gated, const double *sums_part, double *sums, int wsum) {
   if (gated && state[ST_STOP] != 0.0) return;
   __shared__ float sm[16][64];
+  __shared__ float s_inv;
   const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
   const int i = blockIdx.x * 64 + c;
+  if (wsum && scale && g == 8) {      // weighted: 1 / slot [0], which every workgroup adds up as workgroup 0 does below
+    double t = 0.0;
+    for (int w = c; w < n_parts; w += 64) t += sums_part[(size_t)w * 8];
+    t = wave_sum(t);
+    if (c == 0) s_inv = (float)(1.0 / t);
+  }
   if (blockIdx.x == 0 && g < 8) {
     double t = 0.0;
     for (int w = c; w < n_parts; w += 64) t += sums_part[(size_t)w * 8 + g];
@@ -850,7 +896,7 @@ __global__ __launch_bounds__(1024) void ppo_reduce_kernel(const float *part, int
       for (int k = 0; k + st < 16; k += 2 * st) t[k] += t[k + st];
     float o = t[0];
     if (scale) {
-      o *= inv_n;
+      o *= wsum ? s_inv : inv_n;
       if (i >= ols) o -= (penalized ? (float)state[ST_CR] : 1.0f) * ent_reg;
     }
     vec[i] = o;
@@ -942,6 +988,9 @@ struct cmbpo_pi {
   double *ppo_part;       // [2 n_cu][8] per-workgroup loss sums
   double *ppo_sums;       // [8] the loop's own sums (callers of cmbpo_pi_ppo_grad bring theirs)
   float *ppo_g;           // [part_ld] the loop's gradient
+  // per-sample weights (cmbpo_pi_set_sample_weights): the caller's array, NULL = every sample counts once
+  const float *wt;
+  int wt_n;
 };
 
 namespace {
@@ -1041,20 +1090,22 @@ int launch_pi_k(cmbpo_pi *h, PiArgs &a, hipStream_t s, KERN kern, bool f16, bool
   return CMBPO_OK;
 }
 
-template <int MODE, int N_IT>
+template <int MODE, int N_IT, bool WT>
 int launch_pi_n(cmbpo_pi *h, PiArgs &a, hipStream_t s) {
-  if (h->d.H == 256) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 256>, false, MODE == MODE_GRAD || MODE == MODE_FVP);
-  if (g_pi_path == 0) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 128>, false, MODE == MODE_GRAD || MODE == MODE_FVP);
+  if (h->d.H == 256) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 256, WT>, false, MODE == MODE_GRAD || MODE == MODE_FVP);
+  if (g_pi_path == 0) return launch_pi_k(h, a, s, pi_kernel<MODE, N_IT, 128, WT>, false, MODE == MODE_GRAD || MODE == MODE_FVP);
   if constexpr (MODE != MODE_PPO) {
     if (MODE == MODE_FVP && a.cache_r != nullptr)
-      return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, true>, true, MODE == MODE_GRAD || MODE == MODE_FVP);
+      return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, true, WT>, true, MODE == MODE_GRAD || MODE == MODE_FVP);
   }
-  return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, false>, true, MODE == MODE_GRAD || MODE == MODE_FVP);
+  return launch_pi_k(h, a, s, pi_kernel_h<MODE, N_IT, false, WT>, true, MODE == MODE_GRAD || MODE == MODE_FVP);
 }
 
+// (without weights a launch takes the instantiation it always took)
 template <int MODE>
 int launch_pi(cmbpo_pi *h, PiArgs &a, hipStream_t s) {
-  return h->d.n_it > 1 ? launch_pi_n<MODE, 2>(h, a, s) : launch_pi_n<MODE, 1>(h, a, s);
+  if (a.wt != nullptr) return h->d.n_it > 1 ? launch_pi_n<MODE, 2, true>(h, a, s) : launch_pi_n<MODE, 1, true>(h, a, s);
+  return h->d.n_it > 1 ? launch_pi_n<MODE, 2, false>(h, a, s) : launch_pi_n<MODE, 1, false>(h, a, s);
 }
 
 int fill_args(cmbpo_pi *h, const cmbpo_pi_batch_t *b, PiArgs &a, const char *who) {
@@ -1064,6 +1115,8 @@ int fill_args(cmbpo_pi *h, const cmbpo_pi_batch_t *b, PiArgs &a, const char *who
                 b->obs_dim, b->act_dim, h->d.D, h->d.A);
   CMBPO_REQUIRE(b->n >= 1, "%s: empty batch", who);
   CMBPO_REQUIRE(b->obs != nullptr, "%s: obs is NULL", who);
+  if (int rc = cmbpo_pi_weights_check(h, b, who)) return rc;
+  a.wt = h->wt;
   a.d = h->d;
   a.w = pack_ptrs(h, h->blob);
   a.v = pack_ptrs(h, h->blob + h->pack_floats);
@@ -1136,6 +1189,7 @@ extern "C" int cmbpo_pi_create(cmbpo_pi_t **out, int obs_dim, int hidden, int ac
   h->parts = nullptr;
   h->blob16 = nullptr;
   h->ppo_part = nullptr; h->ppo_sums = nullptr; h->ppo_g = nullptr;
+  h->wt = nullptr; h->wt_n = 0;
   if (hipMalloc(reinterpret_cast<void **>(&h->blob), 2 * off * sizeof(float)) != hipSuccess ||
       hipMalloc(reinterpret_cast<void **>(&h->blob16), (size_t)2 * H16_PACK * sizeof(u32x4)) != hipSuccess ||
       hipMalloc(reinterpret_cast<void **>(&h->parts), (size_t)2 * h->n_cu * h->part_ld * sizeof(float)) != hipSuccess ||
@@ -1192,6 +1246,26 @@ extern "C" int cmbpo_pi_keep_activations(cmbpo_pi_t *h, int enable) {
 extern "C" long cmbpo_pi_saved_activation_uses(const cmbpo_pi_t *h) { return h ? h->act_hits : -1; }
 
 const void *cmbpo_pi_act_token(const cmbpo_pi_t *h, const cmbpo_pi_batch_t *b) { return (h && b) ? act_for(h, b) : nullptr; }
+
+// The weights do not own memory and enqueue nothing: they are an argument of every later launch on this handle.  Saved
+// activations do not depend on them and are kept.
+extern "C" int cmbpo_pi_set_sample_weights(cmbpo_pi_t *h, const float *d_w, int n, void *stream) {
+  (void)stream;
+  CMBPO_REQUIRE(h != nullptr, "cmbpo_pi_set_sample_weights: NULL handle");
+  CMBPO_REQUIRE(d_w == nullptr || n >= 1, "cmbpo_pi_set_sample_weights: %d weights", n);
+  h->wt = d_w;
+  h->wt_n = d_w != nullptr ? n : 0;
+  return CMBPO_OK;
+}
+
+const void *cmbpo_pi_weights_token(const cmbpo_pi_t *h) { return h ? h->wt : nullptr; }
+
+int cmbpo_pi_weights_check(const cmbpo_pi_t *h, const cmbpo_pi_batch_t *b, const char *who) {
+  CMBPO_REQUIRE(h != nullptr && b != nullptr, "%s: NULL handle / batch", who);
+  CMBPO_REQUIRE(h->wt == nullptr || h->wt_n == b->n, "%s: the handle holds %d sample weights, the batch has %d samples", who,
+                h->wt_n, b->n);
+  return CMBPO_OK;
+}
 
 extern "C" int cmbpo_pi_loss_grad(cmbpo_pi_t *h, const cmbpo_pi_batch_t *b, int which, float *d_vec, double *d_sums,
                                   void *stream) {
@@ -1302,7 +1376,7 @@ int ppo_pass(cmbpo_pi *h, const cmbpo_pi_batch_t *b, const cmbpo_pi_ppo_cfg_t *c
   if (int rc = launch_pi<MODE_PPO>(h, a, s)) return rc;
   hipLaunchKernelGGL(ppo_reduce_kernel, dim3(cmbpo_ceil_div(h->d.P, 64)), dim3(1024), 0, s, h->parts, h->part_ld, h->last_grid,
                      h->d.P, d_vec, scale, (float)(1.0 / (double)b->n), c->ent_reg, h->d.ols, c->objective_penalized ? 1 : 0,
-                     d_state, gated, h->ppo_part, d_sums);
+                     d_state, gated, h->ppo_part, d_sums, a.wt != nullptr ? 1 : 0);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1313,6 +1387,7 @@ extern "C" int cmbpo_pi_ppo_grad(cmbpo_pi_t *h, const cmbpo_pi_batch_t *b, const
                                  float *d_vec, double *d_sums, void *stream) {
   if (int rc = ppo_check_cfg(cfg, "cmbpo_pi_ppo_grad")) return rc;
   CMBPO_REQUIRE(d_state && d_vec && d_sums, "cmbpo_pi_ppo_grad: NULL buffer");
+  { PiArgs chk{}; if (int rc = fill_args(h, b, chk, "cmbpo_pi_ppo_grad")) return rc; }      // (before the first allocation)
   if (int rc = ppo_reserve(h, "cmbpo_pi_ppo_grad")) return rc;
   return ppo_pass(h, b, cfg, d_state, d_vec, d_sums, 0, 0, (hipStream_t)stream, "cmbpo_pi_ppo_grad");
 }
@@ -1331,6 +1406,7 @@ extern "C" int cmbpo_pi_ppo_run(cmbpo_pi_t *h, const cmbpo_pi_batch_t *b, const 
   if (int rc = ppo_check_cfg(cfg, "cmbpo_pi_ppo_run")) return rc;
   CMBPO_REQUIRE(h && d_theta && d_m && d_v && d_state, "cmbpo_pi_ppo_run: NULL buffer");
   CMBPO_REQUIRE(iters >= 1, "cmbpo_pi_ppo_run: iters %d < 1", iters);
+  { PiArgs chk{}; if (int rc = fill_args(h, b, chk, "cmbpo_pi_ppo_run")) return rc; }       // (before the first launch)
   if (int rc = ppo_reserve(h, "cmbpo_pi_ppo_run")) return rc;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(ppo_begin_kernel, dim3(1), dim3(64), 0, s, d_state);

@@ -1493,6 +1493,33 @@ extern "C" int cmbpo_buffer_offsets(const cmbpo_rollout_t *r, int32_t *d_offsets
   return CMBPO_OK;
 }
 
+// Trust weights of the stored entries, in the order of get(): out[offsets[b] + t] = ref_var / (ref_var + cumvar[t][b]) for
+// t < len[b] -- 1 where the model has accumulated no variance, 1/2 at ref_var; a float32 store of a float64 quotient.
+// Thread = one (t, b) of the time-major side table (coalesced reads; the scattered 4-byte stores are a 24th of flatten's).
+static __global__ __launch_bounds__(256) void trust_weights_kernel(const cmbpo_rollout_t r, const double *cumvar,
+                                                                  const int32_t *offs, double ref_var, float *out) {
+  const size_t B = (size_t)r.B, total = B * (size_t)r.T;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int t = (int)(i / B), b = (int)(i - (size_t)t * B);
+    if (t < r.len[b]) out[(size_t)offs[b] + t] = (float)__ddiv_rn(ref_var, __dadd_rn(ref_var, cumvar[i]));
+  }
+}
+
+extern "C" int cmbpo_buffer_trust_weights(const cmbpo_rollout_t *r, const int32_t *d_offsets, double ref_var, float *d_out,
+                                          void *stream) {
+  if (int rc = check_rollout(r, "cmbpo_buffer_trust_weights")) return rc;
+  CMBPO_REQUIRE(d_offsets && d_out, "cmbpo_buffer_trust_weights: NULL argument");
+  CMBPO_REQUIRE(isfinite(ref_var) && ref_var > 0.0, "cmbpo_buffer_trust_weights: ref_var %g is not a positive finite number", ref_var);
+  const double *cumvar = cmbpo_internal_side_lookup(r).iv.cumvar_buf;
+  CMBPO_REQUIRE(cumvar != nullptr, "cmbpo_buffer_trust_weights: no accumulated variance is kept (cmbpo_rollout_iv_attach)");
+  const size_t total = (size_t)r->B * (size_t)r->T;
+  const size_t want = (total + 255) / 256;
+  hipLaunchKernelGGL(trust_weights_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream, *r,
+                     cumvar, d_offsets, ref_var, d_out);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
 extern "C" int cmbpo_buffer_moments(const cmbpo_rollout_t *r, int pass, double *d_stats, void *stream) {
   if (int rc = check_rollout(r, "cmbpo_buffer_moments")) return rc;
   CMBPO_REQUIRE(pass >= 0 && pass <= 3 && d_stats, "cmbpo_buffer_moments: bad pass %d / NULL stats", pass);

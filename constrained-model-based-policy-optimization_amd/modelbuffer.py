@@ -26,6 +26,11 @@ Constant weights do not reduce to plain GAE: the reference folds the weight beyo
 (``cmbpo_disagreement_t``: this step's ``rew_var_t`` / ``cost_var_t``, the per-branch float64 sums ``path_rew_var`` /
 ``path_cost_var`` over the stored steps, the scratch of the step's totals) beside the rollout struct; ``ModelSampler.reset``
 calls it with its environment's settings.  Off (the default) nothing is allocated and nothing is measured.
+
+``set_trust_weights(ref_var)`` (needs ``iv_gae``): every ``get()`` also leaves, in ``last_weights``, one trust weight per
+returned sample, ``ref_var / (ref_var + accumulated variance)`` from the same ``cumvar_buf`` (1 where the model has accumulated
+no variance, 1/2 at ``ref_var``; with ``ref_var = iv_eps`` proportional to the GAE's own weight) -- for the weighted policy and
+critic updates.  What ``get()`` returns is unchanged.
 """
 import ctypes as C
 import weakref
@@ -85,6 +90,7 @@ class ModelBuffer:
         self.gamma, self.lam, self.cost_gamma, self.cost_lam = 0.99, 0.95, 0.99, 0.95
         self.iv_gae, self.iv_eps = bool(iv_gae), self._check_iv_eps(iv_eps)
         self.disagreement, self.rew_pessimism, self.cost_pessimism = False, 0.0, 0.0
+        self.trust_var, self.last_weights = None, None
         self.rs = None
         self._iv_key = [0]                    # iscal of the arrays the library's table may hold an entry for
         weakref.finalize(self, _iv_release, self._iv_key)
@@ -157,8 +163,25 @@ class ModelBuffer:
         iv_eps = self._check_iv_eps(iv_eps)
         if self.ptr != 0 or self._size != 0:
             raise RuntimeError("set_iv_gae: the buffer holds samples (call it after get() / reset())")
+        if not on and self.trust_var is not None:
+            raise ValueError("set_iv_gae(False): the trust weights read the variance it keeps (set_trust_weights(None) first)")
         self.iv_gae, self.iv_eps = bool(on), iv_eps
         self._iv_sync()
+
+    def set_trust_weights(self, ref_var):
+        """Switch the trust weights of get() on (ref_var > 0: the accumulated variance at which a sample weighs 1/2) or off
+        (None); legal whenever nothing is stored."""
+        if ref_var is not None:
+            ref_var = float(ref_var)
+            if not (ref_var > 0.0 and np.isfinite(ref_var)):
+                raise ValueError(f"ref_var must be a positive finite number or None, got {ref_var}")
+            if not self.iv_gae:
+                raise ValueError("set_trust_weights needs iv_gae=True: the accumulated variance is only kept there")
+        if self.ptr != 0 or self._size != 0:
+            raise RuntimeError("set_trust_weights: the buffer holds samples (call it after get() / reset())")
+        self.trust_var = ref_var
+        if ref_var is None:
+            self.last_weights = None
 
     def _iv_sync(self):
         """Attach (on: for the current arrays, lambdas and iv_eps) or detach (off: and free) the state beside the struct."""
@@ -390,11 +413,24 @@ class ModelBuffer:
             if ev is not None:
                 ev[2].record()
                 self.get_events.append((ev[0], ev[1], ev[2], n))
+            wts = None
+            if self.trust_var is not None:      # (before reset(): the variance table is this rollout's)
+                wts = torch.empty(n, dtype=torch.float32, device=dev)
+                self._call("cmbpo_buffer_trust_weights", t["offsets"].data_ptr(), C.c_double(self.trust_var), wts.data_ptr())
+                w_stat = torch.stack([wts.mean(dtype=torch.float64), wts.min().double()])
             st = t["stats"].cpu().numpy()
             ret_mean, cret_mean = float(st[4]), float(st[5])
         else:
             ret_mean, cret_mean = 0, 0
+            wts = torch.empty(0, dtype=torch.float32, device=dev) if self.trust_var is not None else None
+            w_stat = torch.zeros(2, dtype=torch.float64)
         diagnostics = dict(poolm_batch_size=n, poolm_ret_mean=ret_mean, poolm_cret_mean=cret_mean)
+        if self.trust_var is not None:
+            w_stat = w_stat.cpu().numpy()
+            diagnostics.update(poolm_weight_mean=float(w_stat[0]), poolm_weight_min=float(w_stat[1]))
+            self.last_weights = wts if as_tensors else wts.cpu().numpy()
+        else:
+            self.last_weights = None
         res = outs if as_tensors else [o.cpu().numpy() for o in outs]
         self.reset()
         return res, diagnostics

@@ -477,6 +477,14 @@ int cmbpo_buffer_prepare(const cmbpo_rollout_t *r, int32_t *d_offsets, double *d
  * cadv (:198-204).  d_out[12] are device pointers sized for offsets[B] rows. */
 int cmbpo_buffer_flatten(const cmbpo_rollout_t *r, const int32_t *d_offsets,
                          const double *d_stats, float *const *h_out12, void *stream);
+/* Trust weights of the stored entries in the order of cmbpo_buffer_flatten:
+ * d_out[offsets[b] + t] = (float)(ref_var / (ref_var + cumvar[t][b])), t < len[b],
+ * computed in float64 from the accumulated model variance that the
+ * inverse-variance GAE keeps (cmbpo_rollout_iv_attach; an error without it):
+ * 1 where the model has accumulated no variance, 1/2 at ref_var (> 0, finite).
+ * d_out holds offsets[B] floats. */
+int cmbpo_buffer_trust_weights(const cmbpo_rollout_t *r, const int32_t *d_offsets, double ref_var, float *d_out,
+                               void *stream);
 
 /* ------------------------------------------------------------------------ *
  * CPO trust-region update: the policy-graph fetches of CPOAgent.update_pi
@@ -540,6 +548,20 @@ int cmbpo_pi_keep_activations(cmbpo_pi_t *h, int enable);
 /* Fisher-vector product launches that read saved activations so far (a launch
  * captured into the CG graph counts once); diagnostics / tests. */
 long cmbpo_pi_saved_activation_uses(const cmbpo_pi_t *h);
+/* Per-sample weights of every later launch on this handle (loss_grad, fvp, eval,
+ * the CG calls, ppo_grad, ppo_run): a sample of weight w counts as w copies of
+ * itself.  Every per-sample sum becomes a weighted sum: d_sums[0] = sum w,
+ * [1] = sum w ratio adv, [2] = sum w ratio cadv, [3] = sum w kl, [4] = sum w cost
+ * (first-order sums: [1] objective, [5] clipped-away, [6] ratio adv, each times
+ * w); vectors are sum w grad / sum w J^T M J v, and callers divide by sum w
+ * where they divided by n.  d_w: n finite floats >= 0 with a positive sum, on
+ * the device, kept alive by the caller; NULL clears the weights (n ignored).
+ * They stay with the handle until cleared or replaced; a launch whose batch has
+ * another n returns CMBPO_EINVAL before any HIP call.  Nothing is enqueued; saved
+ * activations do not depend on the weights and are kept; a cached CG graph is
+ * re-captured when the pointer changes.  Without weights every launch runs the
+ * kernel it ran before this function existed. */
+int cmbpo_pi_set_sample_weights(cmbpo_pi_t *h, const float *d_w, int n, void *stream);
 
 /* Arithmetic of the policy kernels' matrix products (forward, JVP, backward and
  * weight-gradient): 1 (default) = three f16 MFMAs on two-piece operands (11 + 1 +
