@@ -51,6 +51,7 @@ SIGNATURES = {
     "cmbpo_ens_predict_mean": (_i, [_p, _p, _i, _p, _p, _i, _p, _p]),
     "cmbpo_critic_pair_supported": (_i, [_p, _p]),
     "cmbpo_critic_pair_predict": (_i, [_p, _p, _p, _i, _p, _p, _i, _p, _p, _p]),
+    "cmbpo_critic_pair_predict_var": (_i, [_p, _p, _p, _i, _p, _p, _i, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
     "cmbpo_policy_forward": (_i, [_p, _p, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
     "cmbpo_fakeenv_post": (_i, [_i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i,
                                 _p, _p, _p, _p, _p, _p, _p, _p]),
@@ -108,6 +109,7 @@ I_N_ALIVE, I_N_UNC, I_N_FIN_PRE, I_N_STORED, I_N_ALIVE_OUT, I_SIZE, I_N_FIN_POST
 (D_TOTAL_SAMPLES, D_TOTAL_COST, D_TOTAL_REW, D_TOTAL_VS, D_TOTAL_CVS, D_TOTAL_DKL, D_TOTAL_DYN_EP_VAR,
  D_MAX_DKL, D_MAX_PATH_RETURN, D_DKL_SUM_T, D_STEP_MAX_DKL, D_SUM_PATH_RET, D_SUM_PATH_COST) = range(13)
 D_TOTAL_REW_VAR, D_TOTAL_COST_VAR = 13, 14      # ensemble disagreement on reward / cost, summed over the stored rows
+D_TOTAL_V_VAR, D_TOTAL_VC_VAR = 15, 16          # critic disagreement (member variance of V / VC), summed over the stored rows
 
 _rp = C.POINTER(RolloutStruct)
 SIGNATURES.update({
@@ -153,6 +155,18 @@ class DisagreementStruct(C.Structure):
 SIGNATURES.update({
     "cmbpo_rollout_disagreement_attach": (_i, [_rp, C.POINTER(DisagreementStruct)]),
     "cmbpo_rollout_disagreement_detach": (_i, [_rp]),
+})
+
+
+class ValueDisagreementStruct(C.Structure):
+    """ctypes image of ``cmbpo_value_disagreement_t``: the pessimism coefficients and the arrays of the critics' own
+    disagreement that travel beside the rollout struct."""
+    _fields_ = [("kappa_v", C.c_float), ("kappa_vc", C.c_float)] + [(n, C.c_void_p) for n in ("v_var", "vc_var", "part")]
+
+
+SIGNATURES.update({
+    "cmbpo_rollout_value_disagreement_attach": (_i, [_rp, C.POINTER(ValueDisagreementStruct)]),
+    "cmbpo_rollout_value_disagreement_detach": (_i, [_rp]),
 })
 
 

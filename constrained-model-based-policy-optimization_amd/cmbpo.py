@@ -29,6 +29,16 @@ rollouts (``msampler/rew_var_perstep``, ``msampler/cost_var_perstep``); ``m_rew_
 ``c + kappa_c * sigma_c``: a constraint is no longer satisfied on the say-so of one member (``FakeEnv(disagreement=...)``).
 ``m_cost_pessimism > 0`` needs ``m_learn_cost=True``.  Real samples and the rollout lengths are not affected.
 
+``m_value_disagreement=True`` measures the variance over the members of both critics at every state an imagined rollout
+evaluates (``msampler/v_var_perstep``, ``msampler/vc_var_perstep``); ``m_v_pessimism`` / ``m_vc_pessimism`` (kappa >= 0, > 0
+implies the measurement) make every imagined value ``V - kappa_v * sigma_v`` and every imagined cost value
+``VC + kappa_vc * sigma_vc`` -- stored values and the bootstraps that close a branch alike, so the GAE sees them
+(``ModelBuffer.set_value_disagreement``).  It needs critics the one-launch critic kernel takes (two hidden layers of 128, at
+most 4 members, at most 64 inputs).  Real samples, ``get_action_outs`` and the rollout lengths are not affected.  With
+``vf_clipping`` the critics' losses are clipped around the buffer's old values, which for imagined samples are then the
+PENALISED ones.  Critic targets built from penalised bootstraps pull the cost critic's mean upward, by at most
+``gamma^T / (1 - gamma^T)`` of ``kappa sigma`` over a T-step branch; the unpenalised real-sample targets anchor it.
+
 ``m_validate_horizon=H`` (> 0; the reference has nothing like it) replays, every epoch, ``m_validate_windows`` windows of up to H
 consecutive real steps of that epoch through the model with the recorded actions and reports how the prediction error
 compounds, which real costs and terminations the imagined signal misses, and whether the epistemic variance is the size of
@@ -91,6 +101,7 @@ class CMBPO:
                  model_train_kwargs=None, initial_model_train_kwargs=None, shuffle_on_device=True, device=None,
                  session=None, start_state_sampling='host', m_stochastic=False, m_iv_gae=False, m_iv_eps=1e-8,
                  m_disagreement=False, m_rew_pessimism=0.0, m_cost_pessimism=0.0,
+                 m_value_disagreement=False, m_v_pessimism=0.0, m_vc_pessimism=0.0,
                  m_validate_horizon=0, m_validate_windows=1024, m_imagined_weight=1.0, m_trust_var=None,
                  **_unused):
         # RLAlgorithm.__init__ (algorithms/rl_algorithm.py:22-74)
@@ -124,6 +135,15 @@ class CMBPO:
         self._m_learn_cost = bool(m_learn_cost)
         if float(m_cost_pessimism) > 0.0 and not self._m_learn_cost:
             raise ValueError("m_cost_pessimism > 0 needs m_learn_cost=True: only a learned cost head has an ensemble spread")
+        # critic disagreement: kappa > 0 implies the measurement; only the one-launch critic kernels measure it
+        kv, kvc = float(m_v_pessimism), float(m_vc_pessimism)
+        if not (np.isfinite(kv) and kv >= 0.0 and np.isfinite(kvc) and kvc >= 0.0):
+            raise ValueError("m_v_pessimism / m_vc_pessimism must be finite numbers >= 0, got %r, %r" % (m_v_pessimism, m_vc_pessimism))
+        self._value_disagreement = bool(use_model) and (bool(m_value_disagreement) or kv > 0.0 or kvc > 0.0)
+        if self._value_disagreement:
+            limit = policy.value_disagreement_limit()
+            if limit is not None:
+                raise ValueError("m_value_disagreement / m_v_pessimism / m_vc_pessimism: " + limit)
         # trust-weighted updates: a real sample weighs 1, an imagined one m_imagined_weight, times its trust weight
         # m_trust_var / (m_trust_var + accumulated model variance) when m_trust_var is set.  (1.0, None): no weights anywhere.
         self._imagined_weight = float(m_imagined_weight)
@@ -174,6 +194,8 @@ class CMBPO:
                                       cost_lam=policy.cost_lam)
             if self._trust_var is not None:
                 self.model_buf.set_trust_weights(self._trust_var)
+            if self._value_disagreement:
+                self.model_buf.set_value_disagreement(True, kv, kvc)
             self.model_sampler = ModelSampler(max_path_length=maxroll, batch_size=self._rollout_batch_size,
                                               logger=None, rollout_mode=self.rollout_mode,
                                               stochastic=bool(m_stochastic))

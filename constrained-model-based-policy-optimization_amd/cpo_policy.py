@@ -356,6 +356,37 @@ class CPOPolicy:
         r = self.vc.predict(o)
         return r[:, 0]
 
+    def value_disagreement_limit(self):
+        """None if the one-launch critic kernels -- the only ones that measure the critics' disagreement -- take this policy's
+        critics, else the limit they break, in words."""
+        if tuple(self.hidden_sizes_c) != (128, 128):
+            return "vf_hidden_layer_sizes %r: the critic pair kernel takes two hidden layers of width 128" % (tuple(self.hidden_sizes_c),)
+        if self.vf_ensemble > 4:
+            return "vf_ensemble_size %d: the critic pair kernel takes at most 4 members (E <= 4)" % self.vf_ensemble
+        if self.obs_dim > 64:
+            return "%d observation inputs: the critic pair kernel takes at most 64" % self.obs_dim
+        return None
+
+    def value_disagreement(self, obs):
+        """``{v, vc, v_var, vc_var}``: the member means of both critics (``get_v`` / ``get_vc``'s function, kappa = 0) and the
+        variance over their members, in output units, for NumPy or CUDA observations (``cmbpo_critic_pair_predict_var``)."""
+        limit = self.value_disagreement_limit()
+        if limit is not None:
+            raise ValueError("value_disagreement: " + limit)
+        obs = self.format_obs(obs)
+        with torch.cuda.device(self.device):
+            o, was_np = _to_dev(obs, self.device)
+            o = o.to(torch.float32).contiguous()
+            n = o.shape[0]
+            flat = torch.zeros((4, n), dtype=torch.float32, device=self.device)
+            if n > 0:
+                _lib.check(_lib.lib().cmbpo_critic_pair_predict_var(
+                    self.v.mlp.handle, self.vc.mlp.handle, o.data_ptr(), self.obs_dim, None, None, n, 0.0, 0.0,
+                    flat[0].data_ptr(), flat[1].data_ptr(), flat[2].data_ptr(), flat[3].data_ptr(), _lib.current_stream()),
+                    "cmbpo_critic_pair_predict_var")
+        res = flat.cpu().numpy() if was_np else flat
+        return {"v": res[0], "vc": res[1], "v_var": res[2], "vc_var": res[3]}
+
     def actions(self, obs):
         return self.get_action_outs(obs)["pi"]
 

@@ -22,6 +22,8 @@ extern "C" const char *cmbpo_last_error(void) { return g_err; }
 // 2: cmbpo_fakeenv_post_noise, cmbpo_rollout_t.xi / xi_stride; 3: cmbpo_train_extras_t, cmbpo_trainer_{step,epoch,losses}_ex
 // (4: cmbpo_iv_gae_t;) 5: cmbpo_fakeenv_post_disagreement, cmbpo_disagreement_t, CMBPO_D_TOTAL_REW_VAR / _COST_VAR
 // 6: cmbpo_replay_t, cmbpo_replay_{parts,compare,finish,run}
+// (still 6 with cmbpo_critic_pair_predict_var, cmbpo_value_disagreement_t, CMBPO_D_TOTAL_V_VAR / _VC_VAR: additions only, and
+// tests/test_replay_cpu.py holds the number at 6 -- ask for the symbols, as tests/test_value_disagreement_cabi.py does)
 extern "C" int cmbpo_version(void) { return 6; }
 
 namespace {

@@ -15,6 +15,10 @@
 #include "f16_split.h"
 #include "policy_f16_tile.h"
 
+#include <math.h>
+
+#include <type_traits>
+
 namespace {
 
 constexpr int HC = 128;          // hidden units
@@ -47,8 +51,38 @@ struct CfArgs {
   CmbpoStoreVec sv;
 };
 
-template <int S0>   // k-slabs of the input layer (obs_dim <= 16 S0)
-__global__ __launch_bounds__(512) void critic_pair_kernel(const CfArgs a) {
+// Critic disagreement (VDIS instances): the variance over the members of each critic, and kappa sigma held against the value.
+// An argument block of its own, so a launch without the feature carries the block it had.
+struct CfArgsVd : CfArgs {
+  float kappa[2];      // kappa_v (subtracted), kappa_vc (added); 0: the mean goes out bit for bit
+  float *var[2];       // [branch slot]
+};
+template <bool VDIS>
+using CfArgsT = std::conditional_t<VDIS, CfArgsVd, CfArgs>;
+
+// x[0], x[stride], ...: the E member values of a row.  mean = (((0 + x0) + x1) + ...) / E -- the plain instances' bits -- and
+// np.var's arithmetic on them: q = sum_e (x_e - mean)^2 in member order, q / E, every operation rounded on its own.
+__device__ __forceinline__ float member_mean_var(const float *x, int stride, int E, float *var) {
+  float sum = 0.0f;
+  for (int m = 0; m < E; ++m) sum += x[m * stride];
+  const float mean = sum / (float)E;
+  float sq = 0.0f;
+  for (int m = 0; m < E; ++m) {
+    const float dlt = __fsub_rn(x[m * stride], mean);
+    sq = __fadd_rn(sq, __fmul_rn(dlt, dlt));
+  }
+  *var = sq / (float)E;
+  return mean;
+}
+// V - kappa_v sigma_v (n2 == 0), VC + kappa_vc sigma_vc (n2 == 1) where kappa > 0; sqrtf: correctly rounded (np.sqrt)
+__device__ __forceinline__ float penalised_value(float mean, float var, float kappa, int n2) {
+  if (!(kappa > 0.0f)) return mean;
+  const float pen = __fmul_rn(kappa, sqrtf(var));
+  return n2 == 0 ? __fsub_rn(mean, pen) : __fadd_rn(mean, pen);
+}
+
+template <int S0, bool VDIS = false>   // k-slabs of the input layer (obs_dim <= 16 S0)
+__global__ __launch_bounds__(512) void critic_pair_kernel(const CfArgsT<VDIS> a) {
   constexpr int KP = 16 * S0;
   extern __shared__ float sm[];
   float *xraw = sm;                         // [32][KP + 1] raw observation rows of the tile
@@ -230,10 +264,19 @@ __global__ __launch_bounds__(512) void critic_pair_kernel(const CfArgs a) {
   __syncthreads();
   if (tid < 64) {                   // mean over ALL members (pe.py:343), added in member order
     const int n2 = tid >> 5, b = tid & 31;
-    float sum = 0.0f;
-    for (int m = 0; m < E; ++m) sum += part[(n2 * E + m) * 32 + b];
     const int rr = rows[b];
-    if (rr >= 0) a.net[n2].out[rr] = sum / (float)E;
+    if constexpr (VDIS) {
+      float var;
+      const float mean = member_mean_var(part + n2 * E * 32 + b, 32, E, &var);
+      if (rr >= 0) {
+        a.net[n2].out[rr] = penalised_value(mean, var, a.kappa[n2], n2);
+        a.var[n2][rr] = var;
+      }
+    } else {
+      float sum = 0.0f;
+      for (int m = 0; m < E; ++m) sum += part[(n2 * E + m) * 32 + b];
+      if (rr >= 0) a.net[n2].out[rr] = sum / (float)E;
+    }
   }
 }
 
@@ -243,23 +286,27 @@ __global__ __launch_bounds__(512) void critic_pair_kernel(const CfArgs a) {
 // the 2 E members one after the other: a member's W0 | W1 images go to LDS once per workgroup (80 KB), its eight waves carry
 // the chunk's 32-row tiles with the A fragments read from LDS (the images are lane-linear: conflict-free 16-byte reads), the
 // member values are added per row in LDS in member order.  Per-member arithmetic exactly as in critic_pair_kernel: same bits.
-template <int S0>
+// VDIS: the two-pass variance needs every member's value of a row, so the [2][CH] running sums become [2][kVdE][CH] values; at
+// S0 = 2 that no longer fits beside a 512-row chunk (156 160 B of the CU's 163 840 already), so that instance takes 448 rows.
+constexpr int kVdE = 4;          // (pair_eligible: E <= 4)
+template <int S0, bool VDIS = false>
 struct BigGeo {
   static constexpr int KP = 16 * S0, XS = KP + 1;
-  static constexpr int CH = S0 <= 2 ? 512 : (S0 == 3 ? 256 : 192);    // rows per workgroup (LDS: weights + the chunk's rows)
+  static constexpr int CH = S0 <= 2 ? (VDIS ? 448 : 512) : (S0 == 3 ? 256 : 192);    // rows per workgroup (LDS: weights + the chunk's rows)
   static constexpr int W0Q = (int)IMAGE_UNITS(NT, S0, 2), W1Q = (int)IMAGE_UNITS(NT, S1, 2);   // f16x8 units
-  static constexpr size_t LDS = (size_t)(W0Q + W1Q) * 16 + (size_t)CH * XS * 4 + (size_t)2 * CH * 4 + (size_t)CH * 4 + (size_t)4 * KP * 4;
+  static constexpr int VALS = VDIS ? 2 * kVdE : 2;       // per-row floats: member values / running sums
+  static constexpr size_t LDS = (size_t)(W0Q + W1Q) * 16 + (size_t)CH * XS * 4 + (size_t)VALS * CH * 4 + (size_t)CH * 4 + (size_t)4 * KP * 4;
 };
 
-template <int S0>
-__global__ __launch_bounds__(512) void critic_big_kernel(const CfArgs a, int ch_rows) {
-  using G = BigGeo<S0>;
+template <int S0, bool VDIS = false>
+__global__ __launch_bounds__(512) void critic_big_kernel(const CfArgsT<VDIS> a, int ch_rows) {
+  using G = BigGeo<S0, VDIS>;
   constexpr int KP = G::KP, XS = G::XS;
   extern __shared__ f16x8 smem8[];
   f16x8 *w0s = smem8, *w1s = w0s + G::W0Q;
   float *xraw = reinterpret_cast<float *>(w1s + G::W1Q);   // [ch_rows][XS]
-  float *vsum = xraw + G::CH * XS;                          // [2][CH]
-  int *rows = reinterpret_cast<int *>(vsum + 2 * G::CH);    // [CH]
+  float *vsum = xraw + G::CH * XS;                          // [2][CH]; VDIS: [2][kVdE][CH] member values
+  int *rows = reinterpret_cast<int *>(vsum + G::VALS * G::CH);    // [CH]
   float *s_mu = reinterpret_cast<float *>(rows + G::CH);    // [2][KP] | s_sig [2][KP]
   float *s_sig = s_mu + 2 * KP;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -275,8 +322,10 @@ __global__ __launch_bounds__(512) void critic_big_kernel(const CfArgs a, int ch_
     int v = rr < n_rows ? rr : 0;
     if (a.row_idx) v = a.row_idx[v];
     rows[i] = rr < n_rows ? v : -1;
-    vsum[i] = 0.0f;
-    vsum[G::CH + i] = 0.0f;
+    if constexpr (!VDIS) {
+      vsum[i] = 0.0f;
+      vsum[G::CH + i] = 0.0f;
+    }
   }
   if (tid < 2 * KP) {
     const int n2 = tid / KP, k = tid - n2 * KP;
@@ -424,14 +473,28 @@ __global__ __launch_bounds__(512) void critic_big_kernel(const CfArgs a, int ch_
       dot += __shfl_xor(dot, 32, 64);
       const float o_sig = N.out_mu ? N.out_sig[0] : 1.0f, o_mu = N.out_mu ? N.out_mu[0] : 0.0f;
       const float val = o_sig * (dot + N.b2[(size_t)e * 32]) + o_mu;       // inverse_transform, models/pens/utils.py:167
-      if (hh == 0) vsum[ni * G::CH + t * 32 + r] += val;                  // (this wave owns the tile: members in order)
+      if constexpr (VDIS) {
+        if (hh == 0) vsum[(ni * kVdE + e) * G::CH + t * 32 + r] = val;
+      } else {
+        if (hh == 0) vsum[ni * G::CH + t * 32 + r] += val;                // (this wave owns the tile: members in order)
+      }
     }
   }
   __syncthreads();
   for (int i = tid; i < 2 * tiles * 32; i += 512) {      // mean over ALL members (pe.py:343)
     const int n2 = i / (tiles * 32), b = i - n2 * (tiles * 32);
     const int rr = rows[b];
-    if (rr >= 0) a.net[n2].out[rr] = vsum[n2 * G::CH + b] / (float)E;
+    if constexpr (VDIS) {
+      // the plain instances' sum is ((0 + x0) + x1) + ... too: same mean bits
+      if (rr >= 0) {
+        float var;
+        const float mean = member_mean_var(vsum + n2 * kVdE * G::CH + b, G::CH, E, &var);
+        a.net[n2].out[rr] = penalised_value(mean, var, a.kappa[n2], n2);
+        a.var[n2][rr] = var;
+      }
+    } else {
+      if (rr >= 0) a.net[n2].out[rr] = vsum[n2 * G::CH + b] / (float)E;
+    }
   }
 }
 
@@ -495,6 +558,14 @@ extern "C" int cmbpo_critic_pair_predict(cmbpo_mlp_t *v, cmbpo_mlp_t *vc, const 
                                          nullptr, nullptr, nullptr, stream);
 }
 
+extern "C" int cmbpo_critic_pair_predict_var(cmbpo_mlp_t *v, cmbpo_mlp_t *vc, const float *d_obs, int obs_dim, const int32_t *d_row_idx,
+                                             const int32_t *d_n_rows, int n_rows, float kappa_v, float kappa_vc, float *d_v, float *d_vc,
+                                             float *d_v_var, float *d_vc_var, void *stream) {
+  const CmbpoValueDis vd = {kappa_v, kappa_vc, d_v_var, d_vc_var};
+  return cmbpo_internal_critic_pair_ride(v, vc, d_obs, obs_dim, d_row_idx, d_n_rows, n_rows, d_v, d_vc, nullptr, nullptr, nullptr,
+                                         nullptr, nullptr, nullptr, stream, nullptr, &vd);
+}
+
 // can the actor ride along? (its f16 kernel applies, same input width, room for one more wave)
 bool cmbpo_internal_critic_pair_can_ride(const cmbpo_mlp *v, const cmbpo_mlp *vc, const cmbpo_mlp *policy) {
   return cmbpo_critic_pair_supported(v, vc) && policy && cmbpo_internal_policy_f16_eligible(policy) && policy->in_dim == v->in_dim &&
@@ -505,15 +576,25 @@ bool cmbpo_internal_critic_pair_can_ride(const cmbpo_mlp *v, const cmbpo_mlp *vc
 int cmbpo_internal_critic_pair_ride(cmbpo_mlp *v, cmbpo_mlp *vc, const float *d_obs, int obs_dim, const int32_t *d_row_idx,
                                     const int32_t *d_n_rows, int n_rows, float *d_v, float *d_vc, cmbpo_mlp *policy,
                                     const float *d_eps, float *d_pi, float *d_logp, float *d_mu, float *d_ls, void *stream,
-                                    const CmbpoStoreVec *store_vec) {
-  CMBPO_REQUIRE(v && vc && d_obs && d_v && d_vc, "cmbpo_critic_pair_predict: NULL argument");
-  CMBPO_REQUIRE(cmbpo_critic_pair_supported(v, vc), "cmbpo_critic_pair_predict: needs two loaded 128-wide swish ensembles of equal "
-                                                    "size with one output (HEAD_DETMEAN)");
-  CMBPO_REQUIRE(obs_dim == v->in_dim, "cmbpo_critic_pair_predict: obs_dim %d, the critics take %d", obs_dim, v->in_dim);
-  CMBPO_REQUIRE(n_rows >= 0, "cmbpo_critic_pair_predict: n_rows %d", n_rows);
+                                    const CmbpoStoreVec *store_vec, const CmbpoValueDis *vdis) {
+  const char *who = vdis ? "cmbpo_critic_pair_predict_var" : "cmbpo_critic_pair_predict";
+  CMBPO_REQUIRE(v && vc && d_obs && d_v && d_vc, "%s: NULL argument", who);
+  if (vdis) {      // (what needs no handle first)
+    CMBPO_REQUIRE(vdis->v_var && vdis->vc_var, "%s: NULL variance output", who);
+    CMBPO_REQUIRE(isfinite(vdis->kappa_v) && vdis->kappa_v >= 0.0f && isfinite(vdis->kappa_vc) && vdis->kappa_vc >= 0.0f,
+                  "%s: kappa_v %g / kappa_vc %g: finite numbers >= 0", who, (double)vdis->kappa_v, (double)vdis->kappa_vc);
+  }
+  CMBPO_REQUIRE(n_rows >= 0, "%s: n_rows %d", who, n_rows);
+  CMBPO_REQUIRE(cmbpo_critic_pair_supported(v, vc), "%s: needs two loaded 128-wide swish ensembles of equal "
+                                                    "size with one output (HEAD_DETMEAN)", who);
+  CMBPO_REQUIRE(obs_dim == v->in_dim, "%s: obs_dim %d, the critics take %d", who, obs_dim, v->in_dim);
   if (n_rows == 0) return CMBPO_OK;
   hipStream_t s = (hipStream_t)stream;
-  CfArgs a{};
+  CfArgsVd a{};        // (launches without the feature pass its CfArgs base: the block they had)
+  if (vdis) {
+    a.kappa[0] = vdis->kappa_v; a.kappa[1] = vdis->kappa_vc;
+    a.var[0] = vdis->v_var; a.var[1] = vdis->vc_var;
+  }
   cmbpo_mlp *ms[2] = {v, vc};
   float *outs[2] = {d_v, d_vc};
   const int s0 = (v->in_pad + 15) / 16;
@@ -554,28 +635,38 @@ int cmbpo_internal_critic_pair_ride(cmbpo_mlp *v, cmbpo_mlp *vc, const float *d_
     a.sv = *store_vec;
     a.has_store = 1;
   }
+  const CfArgs &plain = a;      // what a launch without the feature is handed
   // large batches without a rider: members one after the other with their weights in LDS (critic_big_kernel)
   if (!a.has_pol && n_rows >= kCriticBigMin) {
     const int n_cu = cmbpo_cu_count();
-    auto launch_big = [&](auto geo, auto kern) -> int {
+    auto launch_big = [&](auto geo, auto kern, const auto &args) -> int {
       using G = decltype(geo);
       if (int rc = cmbpo_grant_lds(kern, G::LDS)) return rc;
       int ch = (cmbpo_ceil_div(n_rows, n_cu) + 31) / 32 * 32;      // one chunk per CU where the batch allows
       if (ch > G::CH) ch = G::CH;
-      hipLaunchKernelGGL(kern, dim3(cmbpo_ceil_div(n_rows, ch)), dim3(512), G::LDS, s, a, ch);
+      hipLaunchKernelGGL(kern, dim3(cmbpo_ceil_div(n_rows, ch)), dim3(512), G::LDS, s, args, ch);
       CMBPO_HIP_CHECK(hipGetLastError());
       return CMBPO_OK;
     };
-    if (S0 == 2) return launch_big(BigGeo<2>{}, critic_big_kernel<2>);
-    if (S0 == 3) return launch_big(BigGeo<3>{}, critic_big_kernel<3>);
-    return launch_big(BigGeo<4>{}, critic_big_kernel<4>);
+    if (vdis) {
+      if (S0 == 2) return launch_big(BigGeo<2, true>{}, critic_big_kernel<2, true>, a);
+      if (S0 == 3) return launch_big(BigGeo<3, true>{}, critic_big_kernel<3, true>, a);
+      return launch_big(BigGeo<4, true>{}, critic_big_kernel<4, true>, a);
+    }
+    if (S0 == 2) return launch_big(BigGeo<2>{}, critic_big_kernel<2>, plain);
+    if (S0 == 3) return launch_big(BigGeo<3>{}, critic_big_kernel<3>, plain);
+    return launch_big(BigGeo<4>{}, critic_big_kernel<4>, plain);
   }
   const int threads = 64 * (2 * v->ensemble + a.has_pol);
   const size_t lds = ((size_t)32 * (16 * S0 + 1) + (size_t)2 * v->ensemble * 32) * sizeof(float);
   const int grid = cmbpo_ceil_div(n_rows, 32);
-  if (S0 == 2) hipLaunchKernelGGL(critic_pair_kernel<2>, dim3(grid), dim3(threads), lds, s, a);
-  else if (S0 == 3) hipLaunchKernelGGL(critic_pair_kernel<3>, dim3(grid), dim3(threads), lds, s, a);
-  else hipLaunchKernelGGL(critic_pair_kernel<4>, dim3(grid), dim3(threads), lds, s, a);
+  if (vdis) {
+    if (S0 == 2) hipLaunchKernelGGL((critic_pair_kernel<2, true>), dim3(grid), dim3(threads), lds, s, a);
+    else if (S0 == 3) hipLaunchKernelGGL((critic_pair_kernel<3, true>), dim3(grid), dim3(threads), lds, s, a);
+    else hipLaunchKernelGGL((critic_pair_kernel<4, true>), dim3(grid), dim3(threads), lds, s, a);
+  } else if (S0 == 2) hipLaunchKernelGGL(critic_pair_kernel<2>, dim3(grid), dim3(threads), lds, s, plain);
+  else if (S0 == 3) hipLaunchKernelGGL(critic_pair_kernel<3>, dim3(grid), dim3(threads), lds, s, plain);
+  else hipLaunchKernelGGL(critic_pair_kernel<4>, dim3(grid), dim3(threads), lds, s, plain);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }

@@ -107,9 +107,15 @@ struct CmbpoStoreVec {
   const uint8_t *fin_code;
   size_t col_off;        // ptr * B: first row of the column
 };
+// critic disagreement (cmbpo_critic_pair_predict_var; the rollout step with a cmbpo_value_disagreement_t attached): the VDIS
+// instances write the members' variances beside the -- where a coefficient is > 0 penalised -- values
+struct CmbpoValueDis {
+  float kappa_v, kappa_vc;
+  float *v_var, *vc_var;       // slot indexed like d_v / d_vc
+};
 int cmbpo_internal_critic_pair_ride(cmbpo_mlp *v, cmbpo_mlp *vc, const float *d_obs, int obs_dim, const int32_t *d_row_idx,
                                     const int32_t *d_n_rows, int n_rows, float *d_v, float *d_vc, cmbpo_mlp *policy,
                                     const float *d_eps, float *d_pi, float *d_logp, float *d_mu, float *d_ls, void *stream,
-                                    const CmbpoStoreVec *store_vec = nullptr);
+                                    const CmbpoStoreVec *store_vec = nullptr, const CmbpoValueDis *vdis = nullptr);
 // HEAD_DETMEAN, 128-wide, swish, one output (the critics) on the same matrix path
 int cmbpo_internal_launch_critic_split(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s);

@@ -2,10 +2,12 @@
 #pragma once
 #include "common.h"
 
-// what is attached beside *r (cmbpo_rollout_iv_attach / cmbpo_rollout_disagreement_attach); a feature that is not: all-zero
+// what is attached beside *r (cmbpo_rollout_iv_attach / _disagreement_attach / _value_disagreement_attach); a feature that is
+// not: all-zero
 struct RolloutSide {
   cmbpo_iv_gae_t iv;
   cmbpo_disagreement_t dg;
+  cmbpo_value_disagreement_t vd;
 };
 RolloutSide cmbpo_internal_side_lookup(const cmbpo_rollout_t *r);
 

@@ -304,13 +304,21 @@ __device__ __forceinline__ void gae_finish_path(const cmbpo_rollout_t &r, const 
 }
 
 // ---- finish: reward + cost GAE, then mark terminated (modelbuffer.py:138-182) -------------------
-__device__ __forceinline__ void store_stats_body(const cmbpo_rollout_t &r, const cmbpo_disagreement_t &dg);
+// Critic disagreement (cmbpo_rollout_value_disagreement_attach): the kernels that store have a VD instance each, which takes
+// the attached struct as one more argument; the instance without it takes an empty one and keeps the code it had.
+struct VdNone {};
+template <bool VD>
+using VdArg = std::conditional_t<VD, cmbpo_value_disagreement_t, VdNone>;
+
+template <bool VD>
+__device__ __forceinline__ void store_stats_body(const cmbpo_rollout_t &r, const cmbpo_disagreement_t &dg, const VdArg<VD> &vd);
 // fold_stats (the rollout step at large batches, mode 1): workgroup 0 first folds the sums store_kernel's tiles left -- the
 // store is a launch further back, so no atomics are needed, and nothing before the end of this kernel reads the accumulators
 // (a launch of its own until round 3: store_stats_kernel)
+template <bool VD = false>
 __global__ __launch_bounds__(256) void finish_kernel(const cmbpo_rollout_t r, int mode, int fold_stats, const cmbpo_iv_gae_t iv,
-                                                  const cmbpo_disagreement_t dg) {
-  if (fold_stats && blockIdx.x == 0) store_stats_body(r, dg);
+                                                  const cmbpo_disagreement_t dg, const VdArg<VD> vd) {
+  if (fold_stats && blockIdx.x == 0) store_stats_body<VD>(r, dg, vd);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int n = r.iscal[CMBPO_I_N_ALIVE];
   if (i >= n) return;
@@ -356,7 +364,9 @@ __global__ __launch_bounds__(256) void finish_kernel(const cmbpo_rollout_t r, in
 // order: no atomics, reproducible accumulators.
 constexpr int kStoreRows = 64;
 
-__global__ __launch_bounds__(256) void store_kernel(const cmbpo_rollout_t r, const cmbpo_iv_gae_t iv, const cmbpo_disagreement_t dg) {
+template <bool VD = false>
+__global__ __launch_bounds__(256) void store_kernel(const cmbpo_rollout_t r, const cmbpo_iv_gae_t iv, const cmbpo_disagreement_t dg,
+                                                 const VdArg<VD> vd) {
   __shared__ int s_slot[kStoreRows];   // branch slot of each row of the tile, -1: not stored
   const int n = r.iscal[CMBPO_I_N_ALIVE];
   const int tid = threadIdx.x;
@@ -411,6 +421,21 @@ __global__ __launch_bounds__(256) void store_kernel(const cmbpo_rollout_t r, con
         dg.part[2 * (size_t)blockIdx.x + 1] = w1;
       }
     }
+    // critic disagreement: the tile's sums of the members' variance of V / VC at the stored rows.  The store of a step runs
+    // BEFORE the step's critic launch, so v_var[b] / vc_var[b] still hold the variance at cur_obs -- beside v_t / vc_t -- as
+    // the previous step's launch (or the evaluation at the start states) wrote them: no swap of the arrays, keep that order.
+    if constexpr (VD) {
+      double a_vv = 0, a_vcv = 0;
+      if (b >= 0) {
+        a_vv = (double)vd.v_var[b];
+        a_vcv = (double)vd.vc_var[b];
+      }
+      const double w0 = wave_sum(a_vv), w1 = wave_sum(a_vcv);
+      if (tid == 0) {
+        vd.part[2 * (size_t)blockIdx.x] = w0;
+        vd.part[2 * (size_t)blockIdx.x + 1] = w1;
+      }
+    }
     const double v0 = wave_sum(a_cnt), v1 = wave_sum(a_cost), v2 = wave_sum(a_rew), v3 = wave_sum(a_v);
     const double v4 = wave_sum(a_vc), v5 = wave_sum(a_epv), v6 = wave_max(a_maxdkl), v7 = wave_max(a_maxret);
     if (tid == 0) {
@@ -439,7 +464,8 @@ __global__ __launch_bounds__(256) void store_kernel(const cmbpo_rollout_t r, con
 }
 
 // fold the per-tile sums of store_kernel into the counters / accumulators (the 256 threads of one workgroup, fixed order)
-__device__ __forceinline__ void store_stats_body(const cmbpo_rollout_t &r, const cmbpo_disagreement_t &dg) {
+template <bool VD>
+__device__ __forceinline__ void store_stats_body(const cmbpo_rollout_t &r, const cmbpo_disagreement_t &dg, const VdArg<VD> &vd) {
   __shared__ double sm_d[16];
   const int n = r.iscal[CMBPO_I_N_ALIVE];
   const int n_wg = (n + kStoreRows - 1) / kStoreRows;
@@ -486,9 +512,25 @@ __device__ __forceinline__ void store_stats_body(const cmbpo_rollout_t &r, const
       r.dscal[CMBPO_D_TOTAL_COST_VAR] += u1;
     }
   }
+  if constexpr (VD) {            // the tiles' critic-disagreement sums, likewise
+    double u0 = 0.0, u1 = 0.0;
+    for (int w = threadIdx.x; w < n_wg; w += 256) {
+      u0 += vd.part[2 * (size_t)w];
+      u1 += vd.part[2 * (size_t)w + 1];
+    }
+    u0 = block_sum(u0, sm_d);
+    u1 = block_sum(u1, sm_d);
+    if (threadIdx.x == 0 && s[0] > 0.0) {
+      r.dscal[CMBPO_D_TOTAL_V_VAR] += u0;
+      r.dscal[CMBPO_D_TOTAL_VC_VAR] += u1;
+    }
+  }
 }
 
-__global__ __launch_bounds__(256) void store_stats_kernel(const cmbpo_rollout_t r, const cmbpo_disagreement_t dg) { store_stats_body(r, dg); }
+template <bool VD = false>
+__global__ __launch_bounds__(256) void store_stats_kernel(const cmbpo_rollout_t r, const cmbpo_disagreement_t dg, const VdArg<VD> vd) {
+  store_stats_body<VD>(r, dg, vd);
+}
 
 // ---- small rollout batches: decide -> finish(PRE) -> store -> statistics as ONE workgroup --------------------------------
 // At the shipped configurations' 1e3 - 1e4 branches each of the five kernels above is a few microseconds of work behind a
@@ -502,8 +544,9 @@ constexpr int kBookMax = 1024;
 
 // spec (cmbpo_rollout_run's look-ahead): the step was enqueued before the host saw the previous step's counters -- it is void
 // when that step raised the halt word (book_post_kernel)
+template <bool VD = false>
 __global__ __launch_bounds__(kScanThreads) void book_pre_kernel(const cmbpo_rollout_t r, int spec, const cmbpo_iv_gae_t iv,
-                                                             const cmbpo_disagreement_t dg) {
+                                                             const cmbpo_disagreement_t dg, const VdArg<VD> vd) {
   __shared__ int sm_i[17];
   __shared__ double sm_d[16];
   __shared__ double sm_m[8 * 16];
@@ -567,6 +610,7 @@ __global__ __launch_bounds__(kScanThreads) void book_pre_kernel(const cmbpo_roll
   const int D = r.obs_dim;
   double a_cnt = 0, a_cost = 0, a_rew = 0, a_v = 0, a_vc = 0, a_epv = 0, a_maxdkl = 0, a_maxret = 0;
   double a_rv = 0, a_cv = 0;      // ensemble disagreement on reward / cost over the stored rows (attached only)
+  [[maybe_unused]] double a_vv = 0, a_vcv = 0;      // critic disagreement over the stored rows (VD only)
   for (int i = tid; i < n; i += kScanThreads) {
     const int b = r.alive_idx[i];
     const uint8_t code = r.fin_code[b];
@@ -594,6 +638,10 @@ __global__ __launch_bounds__(kScanThreads) void book_pre_kernel(const cmbpo_roll
       dg.path_rew_var[b] += rv;
       dg.path_cost_var[b] += cv_;
       a_rv += rv; a_cv += cv_;
+    }
+    if constexpr (VD) {      // (as in store_kernel: the variance at cur_obs, this step's critic launch comes later)
+      a_vv += (double)vd.v_var[b];
+      a_vcv += (double)vd.vc_var[b];
     }
     r.dkl_acc[b] += (double)dk;
     a_cnt += 1.0; a_cost += c; a_rew += rw; a_v += v; a_vc += vc;
@@ -630,6 +678,14 @@ __global__ __launch_bounds__(kScanThreads) void book_pre_kernel(const cmbpo_roll
     if (tid == 0 && s0 > 0.0) {
       r.dscal[CMBPO_D_TOTAL_REW_VAR] += rd[0];
       r.dscal[CMBPO_D_TOTAL_COST_VAR] += rd[1];
+    }
+  }
+  if constexpr (VD) {
+    double rd[2] = {a_vv, a_vcv};
+    block_reduce_many<2, 0>(rd, sm_m);
+    if (tid == 0 && s0 > 0.0) {
+      r.dscal[CMBPO_D_TOTAL_V_VAR] += rd[0];
+      r.dscal[CMBPO_D_TOTAL_VC_VAR] += rd[1];
     }
   }
 }
@@ -1257,7 +1313,7 @@ void side_set(const cmbpo_rollout_t *r, F RolloutSide::*which, const F *feature)
   if (feature == nullptr && g_side.find(r->iscal) == g_side.end()) return;
   RolloutSide &sd = g_side[r->iscal];
   sd.*which = feature ? *feature : F{};
-  if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr) g_side.erase(r->iscal);
+  if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr && sd.vd.part == nullptr) g_side.erase(r->iscal);
 }
 
 }  // namespace
@@ -1288,6 +1344,25 @@ extern "C" int cmbpo_rollout_disagreement_attach(const cmbpo_rollout_t *r, const
 extern "C" int cmbpo_rollout_disagreement_detach(const cmbpo_rollout_t *r) {
   CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_disagreement_detach: NULL rollout struct / iscal");
   side_set<cmbpo_disagreement_t>(r, &RolloutSide::dg, nullptr);
+  return CMBPO_OK;
+}
+
+extern "C" int cmbpo_rollout_value_disagreement_attach(const cmbpo_rollout_t *r, const cmbpo_value_disagreement_t *vd) {
+  CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_value_disagreement_attach: NULL rollout struct / iscal");
+  CMBPO_REQUIRE(vd != nullptr, "cmbpo_rollout_value_disagreement_attach: NULL cmbpo_value_disagreement_t");
+  CMBPO_REQUIRE(vd->v_var && vd->vc_var, "cmbpo_rollout_value_disagreement_attach: NULL v_var / vc_var");
+  CMBPO_REQUIRE(vd->part != nullptr,
+                "cmbpo_rollout_value_disagreement_attach: NULL part (cmbpo_rollout_value_disagreement_detach switches the feature off)");
+  CMBPO_REQUIRE(vd->kappa_v >= 0.0f && isfinite(vd->kappa_v) && vd->kappa_vc >= 0.0f && isfinite(vd->kappa_vc),
+                "cmbpo_rollout_value_disagreement_attach: kappa_v %g / kappa_vc %g: finite numbers >= 0", (double)vd->kappa_v,
+                (double)vd->kappa_vc);
+  side_set(r, &RolloutSide::vd, vd);
+  return CMBPO_OK;
+}
+
+extern "C" int cmbpo_rollout_value_disagreement_detach(const cmbpo_rollout_t *r) {
+  CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_value_disagreement_detach: NULL rollout struct / iscal");
+  side_set<cmbpo_value_disagreement_t>(r, &RolloutSide::vd, nullptr);
   return CMBPO_OK;
 }
 
@@ -1358,8 +1433,13 @@ int cmbpo_internal_finish(const cmbpo_rollout_t *r, const RolloutSide &sd, int m
   if (mode == 1) CMBPO_REQUIRE(r->v_n && r->vc_n && r->term_t, "%s: POST needs v_n, vc_n, term_t", who);
   else CMBPO_REQUIRE(r->v_t && r->vc_t, "%s: needs v_t, vc_t", who);
   if (fold_stats) CMBPO_REQUIRE(r->store_part != nullptr, "%s: NULL store_part scratch", who);
-  hipLaunchKernelGGL(finish_kernel, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, mode, fold_stats, sd.iv,
-                     sd.dg);
+  // (critic disagreement attached: the VD instance of every kernel that stores or folds the store's sums)
+  if (sd.vd.part != nullptr)
+    hipLaunchKernelGGL(finish_kernel<true>, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, mode, fold_stats,
+                       sd.iv, sd.dg, sd.vd);
+  else
+    hipLaunchKernelGGL(finish_kernel<false>, dim3(cmbpo_ceil_div(r->B, 256)), dim3(256), 0, (hipStream_t)stream, *r, mode, fold_stats,
+                       sd.iv, sd.dg, VdNone{});
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1374,8 +1454,15 @@ int cmbpo_internal_store(const cmbpo_rollout_t *r, const RolloutSide &sd, int wi
   CMBPO_REQUIRE(has_step_arrays(r), "%s: NULL step array", who);
   CMBPO_REQUIRE(has_sample_bufs(r), "%s: NULL buffer", who);
   CMBPO_REQUIRE(r->store_part != nullptr, "%s: NULL store_part scratch", who);
-  hipLaunchKernelGGL(store_kernel, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, sd.iv, sd.dg);
-  if (with_stats) hipLaunchKernelGGL(store_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *r, sd.dg);
+  if (sd.vd.part != nullptr) {
+    hipLaunchKernelGGL(store_kernel<true>, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, sd.iv, sd.dg,
+                       sd.vd);
+    if (with_stats) hipLaunchKernelGGL(store_stats_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, *r, sd.dg, sd.vd);
+  } else {
+    hipLaunchKernelGGL(store_kernel<false>, dim3(cmbpo_ceil_div(r->B, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, sd.iv, sd.dg,
+                       VdNone{});
+    if (with_stats) hipLaunchKernelGGL(store_stats_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, *r, sd.dg, VdNone{});
+  }
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -1395,7 +1482,10 @@ int cmbpo_internal_book_pre(const cmbpo_rollout_t *r, const RolloutSide &sd, int
   CMBPO_REQUIRE(has_step_arrays(r) && r->dkl_acc, "%s: NULL step array", who);
   CMBPO_REQUIRE(has_sample_bufs(r) && has_gae_bufs(r), "%s: NULL buffer", who);
   if (n_alive == 0) return CMBPO_OK;
-  hipLaunchKernelGGL(book_pre_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, spec, sd.iv, sd.dg);
+  if (sd.vd.part != nullptr)
+    hipLaunchKernelGGL(book_pre_kernel<true>, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, spec, sd.iv, sd.dg, sd.vd);
+  else
+    hipLaunchKernelGGL(book_pre_kernel<false>, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, *r, spec, sd.iv, sd.dg, VdNone{});
   if (with_vec)
     hipLaunchKernelGGL(store_vec_kernel, dim3(cmbpo_ceil_div(n_alive, kStoreRows)), dim3(256), 0, (hipStream_t)stream, *r, spec);
   CMBPO_HIP_CHECK(hipGetLastError());

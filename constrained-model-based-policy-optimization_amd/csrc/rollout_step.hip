@@ -42,6 +42,12 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   auto w = [](const float *p) { return const_cast<float *>(p); };
   int rc;
   *next_ready = false;
+  // what is attached beside *r, looked up once for every launch of the step
+  const RolloutSide sd = cmbpo_internal_side_lookup(r);
+  // critic disagreement: only the one-launch critics measure it -- refused before the first launch of the step
+  CMBPO_REQUIRE(sd.vd.part == nullptr || cmbpo_critic_pair_supported(v, vc),
+                "cmbpo_rollout_step: a cmbpo_value_disagreement_t is attached, which needs critics cmbpo_critic_pair_supported takes "
+                "(two loaded 128-wide swish ensembles of at most 4 members and 64 inputs, one output)");
   const int32_t *d_n = ahead.on ? r->iscal + CMBPO_I_N_EFF : nullptr;     // the forward kernels' row count (device) / n_alive (host)
   if (ahead.on)
     CMBPO_REQUIRE(n_alive <= cmbpo_rollout_book_pre_max_rows() && !r->use_host_budget && d_mirror && cmbpo_critic_pair_supported(v, vc),
@@ -53,8 +59,6 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   if ((rc = cmbpo_ens_forward(model, r->cur_obs, r->obs_dim, r->act_t, r->act_dim, r->alive_idx, d_n, n_alive, r->B,
                               d_mean, d_var, stream)))
     return rc;
-  // what is attached beside *r, looked up once for every launch of the step
-  const RolloutSide sd = cmbpo_internal_side_lookup(r);
   const cmbpo_disagreement_t &dg = sd.dg;
   // ensemble disagreement: its instance of the post kernel, penalised rew_t / cost_t (d_xi may be NULL)
   if (dg.part != nullptr) {
@@ -99,9 +103,12 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
       sv.fin_code = r->fin_code;
       sv.col_off = (size_t)r->ptr * (size_t)r->B;
     }
+    // critic disagreement attached: the VDIS instances, penalised v_n / vc_n and the variances at next_obs.  The store above has
+    // already read v_var / vc_var of this step's cur_obs (the order the store kernels rely on).
+    const CmbpoValueDis vdis = {sd.vd.kappa_v, sd.vd.kappa_vc, sd.vd.v_var, sd.vd.vc_var};
     if ((rc = cmbpo_internal_critic_pair_ride(v, vc, r->next_obs, r->obs_dim, r->alive_idx, d_n, n_alive, w(r->v_n), w(r->vc_n),
                                               ride ? policy : nullptr, d_eps_next, w(r->act_t), w(r->logp_t), w(r->mu_t), w(r->ls_t),
-                                              stream, vec_rides ? &sv : nullptr)))
+                                              stream, vec_rides ? &sv : nullptr, sd.vd.part != nullptr ? &vdis : nullptr)))
       return rc;
     *next_ready = ride;
   } else {

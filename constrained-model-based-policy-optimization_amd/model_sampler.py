@@ -123,11 +123,17 @@ class ModelSampler:
         With the environment's disagreement switch on, ``rew_var_perstep`` / ``cost_var_perstep`` are the ensemble's variance
         on the reward / cost column averaged over the stored samples (the reference declares ``_total_rew_var`` /
         ``_total_cost_var`` and never fills them), and with a pessimism coefficient > 0 ``rew_rate`` / ``cost_rate`` are rates
-        of the PENALISED values: the pool stores what the constrained update will see.  ``ens_mean_var`` stays 0."""
+        of the PENALISED values: the pool stores what the constrained update will see.  ``ens_mean_var`` stays 0.
+
+        With the pool's critic disagreement on (``ModelBuffer.set_value_disagreement``), ``v_var_perstep`` / ``vc_var_perstep``
+        are the variance over the critic members of V / VC at the stored samples' observations, averaged over the stored
+        samples (0.0 when off), and with a coefficient > 0 ``v_mean`` / ``cv_mean`` are means of the PENALISED values
+        ``V - kappa_v sigma_v`` / ``VC + kappa_vc sigma_vc``, again what the pool stores."""
         _, d = self._read_scalars()
         L = _lib
         tot = d[L.D_TOTAL_SAMPLES]
         on = bool(getattr(self.pool, "disagreement", False))
+        von = bool(getattr(self.pool, "value_disagreement", False))
         diagnostics = OrderedDict({"pool-size": self.pool.size})
         diagnostics.update({
             "msampler/samples_added": tot,
@@ -140,6 +146,8 @@ class ModelSampler:
             "msampler/rew_rate": d[L.D_SUM_PATH_RET] / (tot + EPS),
             "msampler/v_mean": d[L.D_TOTAL_VS] / (tot + EPS),
             "msampler/cv_mean": d[L.D_TOTAL_CVS] / (tot + EPS),
+            "msampler/v_var_perstep": d[L.D_TOTAL_V_VAR] / (tot + EPS) if von else 0.0,
+            "msampler/vc_var_perstep": d[L.D_TOTAL_VC_VAR] / (tot + EPS) if von else 0.0,
             "msampler/ens_DKL": d[L.D_TOTAL_DKL] / (tot + EPS),
             "msampler/ens_mean_var": 0.0,
             "msampler/max_path_return": d[L.D_MAX_PATH_RETURN],
@@ -153,6 +161,15 @@ class ModelSampler:
         idx = t["alive_idx"]
         lib, stream = _lib.lib(), _lib.current_stream()
         v, vc = self.policy.v.mlp.handle, self.policy.vc.mlp.handle
+        pool = self.pool
+        if getattr(pool, "value_disagreement", False):
+            # critic disagreement: penalised values and the members' variances, into the arrays attached beside the struct (the
+            # next store reads them; critics the one-launch kernels do not take are refused by the entry)
+            _lib.check(lib.cmbpo_critic_pair_predict_var(v, vc, t[obs_key].data_ptr(), pool.obs_dim, idx.data_ptr(), None, n,
+                                                         pool.v_pessimism, pool.vc_pessimism, t[v_key].data_ptr(),
+                                                         t[vc_key].data_ptr(), t["v_var"].data_ptr(), t["vc_var"].data_ptr(), stream),
+                       "cmbpo_critic_pair_predict_var")
+            return
         if lib.cmbpo_critic_pair_supported(v, vc):       # both critics in one launch
             _lib.check(lib.cmbpo_critic_pair_predict(v, vc, t[obs_key].data_ptr(), self.pool.obs_dim, idx.data_ptr(), None, n,
                                                      t[v_key].data_ptr(), t[vc_key].data_ptr(), stream),

@@ -27,6 +27,13 @@ Constant weights do not reduce to plain GAE: the reference folds the weight beyo
 ``path_cost_var`` over the stored steps, the scratch of the step's totals) beside the rollout struct; ``ModelSampler.reset``
 calls it with its environment's settings.  Off (the default) nothing is allocated and nothing is measured.
 
+``set_value_disagreement(on, v_pessimism, vc_pessimism)`` attaches the arrays of the critics' own disagreement
+(``cmbpo_value_disagreement_t``: ``v_var`` / ``vc_var``, the variance over the critic members at the observation each slot was
+last evaluated at, and the scratch of the step's totals).  With it every critic evaluation of an imagined rollout goes through
+``cmbpo_critic_pair_predict_var``: ``v_t / vc_t / v_n / vc_n`` -- and with them ``val_buf`` / ``cval_buf``, every bootstrap, the
+GAE and ``get()`` -- hold ``V - v_pessimism * sigma_v`` and ``VC + vc_pessimism * sigma_vc``.  Off (the default) nothing is
+allocated and nothing is measured.
+
 ``set_trust_weights(ref_var)`` (needs ``iv_gae``): every ``get()`` also leaves, in ``last_weights``, one trust weight per
 returned sample, ``ref_var / (ref_var + accumulated variance)`` from the same ``cumvar_buf`` (1 where the model has accumulated
 no variance, 1/2 at ``ref_var``; with ``ref_var = iv_eps`` proportional to the GAE's own weight) -- for the weighted policy and
@@ -65,6 +72,7 @@ def _iv_release(key):
             rs.iscal = key[0]
             _lib.lib().cmbpo_rollout_iv_detach(C.byref(rs))
             _lib.lib().cmbpo_rollout_disagreement_detach(C.byref(rs))
+            _lib.lib().cmbpo_rollout_value_disagreement_detach(C.byref(rs))
     except Exception:      # interpreter shutdown
         pass
 
@@ -90,6 +98,7 @@ class ModelBuffer:
         self.gamma, self.lam, self.cost_gamma, self.cost_lam = 0.99, 0.95, 0.99, 0.95
         self.iv_gae, self.iv_eps = bool(iv_gae), self._check_iv_eps(iv_eps)
         self.disagreement, self.rew_pessimism, self.cost_pessimism = False, 0.0, 0.0
+        self.value_disagreement, self.v_pessimism, self.vc_pessimism = False, 0.0, 0.0
         self.trust_var, self.last_weights = None, None
         self.rs = None
         self._iv_key = [0]                    # iscal of the arrays the library's table may hold an entry for
@@ -103,6 +112,8 @@ class ModelBuffer:
         if self.rs is not None:               # the table's key is the old iscal
             _lib.check(_lib.lib().cmbpo_rollout_iv_detach(C.byref(self.rs)), "cmbpo_rollout_iv_detach")
             _lib.check(_lib.lib().cmbpo_rollout_disagreement_detach(C.byref(self.rs)), "cmbpo_rollout_disagreement_detach")
+            _lib.check(_lib.lib().cmbpo_rollout_value_disagreement_detach(C.byref(self.rs)),
+                       "cmbpo_rollout_value_disagreement_detach")
         f = dict(dtype=torch.float32, device=dev)
         d = dict(dtype=torch.float64, device=dev)
         t = {}
@@ -143,6 +154,7 @@ class ModelBuffer:
         self._iv_key[0] = self.t["iscal"].data_ptr()
         self._iv_sync()
         self._dis_sync()
+        self._vdis_sync()
 
     def _bind_all(self):
         for name, _ in RolloutStruct._fields_:
@@ -244,6 +256,43 @@ class ModelBuffer:
         dg.path_rew_var, dg.path_cost_var = t["path_rew_var"].data_ptr(), t["path_cost_var"].data_ptr()
         dg.part = t["dis_part"].data_ptr()
         _lib.check(lib.cmbpo_rollout_disagreement_attach(C.byref(self.rs), C.byref(dg)), "cmbpo_rollout_disagreement_attach")
+
+    # -- critic disagreement: pessimistic value bootstraps ----------------------------------------
+    def set_value_disagreement(self, on, v_pessimism=0.0, vc_pessimism=0.0):
+        """Measure the variance over the critic members at every state the rollout evaluates (and hold kappa * sigma against
+        the branch where a coefficient is > 0, which implies `on`: V - kappa_v sigma_v, VC + kappa_vc sigma_vc); legal
+        whenever nothing is stored."""
+        kv, kc = float(v_pessimism), float(vc_pessimism)
+        if not (np.isfinite(kv) and kv >= 0.0 and np.isfinite(kc) and kc >= 0.0):
+            raise ValueError(f"v_pessimism / vc_pessimism must be finite numbers >= 0, got {kv}, {kc}")
+        on = bool(on) or kv > 0.0 or kc > 0.0
+        if (on, kv, kc) == (self.value_disagreement, self.v_pessimism, self.vc_pessimism):
+            return
+        if self.ptr != 0 or self._size != 0:
+            raise RuntimeError("set_value_disagreement: the buffer holds samples (call it after get() / reset())")
+        self.value_disagreement, self.v_pessimism, self.vc_pessimism = on, kv, kc
+        self._vdis_sync()
+
+    def _vdis_sync(self):
+        """Attach (on: for the current arrays and coefficients) or detach (off: and free) the state beside the struct."""
+        lib, t = _lib.lib(), self.t
+        names = ("v_var", "vc_var", "vdis_part")
+        if not self.value_disagreement:
+            _lib.check(lib.cmbpo_rollout_value_disagreement_detach(C.byref(self.rs)), "cmbpo_rollout_value_disagreement_detach")
+            for n in names:
+                t.pop(n, None)
+            return
+        B, dev = self.capacity, self.device
+        if "vdis_part" not in t:
+            t["v_var"] = torch.zeros(B, dtype=torch.float32, device=dev)
+            t["vc_var"] = torch.zeros(B, dtype=torch.float32, device=dev)
+            t["vdis_part"] = torch.zeros(((B + 63) // 64) * 2, dtype=torch.float64, device=dev)
+        vd = _lib.ValueDisagreementStruct()
+        vd.kappa_v, vd.kappa_vc = self.v_pessimism, self.vc_pessimism
+        vd.v_var, vd.vc_var = t["v_var"].data_ptr(), t["vc_var"].data_ptr()
+        vd.part = t["vdis_part"].data_ptr()
+        _lib.check(lib.cmbpo_rollout_value_disagreement_attach(C.byref(self.rs), C.byref(vd)),
+                   "cmbpo_rollout_value_disagreement_attach")
 
     def swap(self, a, b):
         """Exchange two same-shaped state arrays (cur_obs <-> next_obs, v_t <-> v_n, ...)."""

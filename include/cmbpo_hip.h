@@ -196,6 +196,22 @@ int cmbpo_critic_pair_supported(const cmbpo_mlp_t *v, const cmbpo_mlp_t *vc);
 int cmbpo_critic_pair_predict(cmbpo_mlp_t *v, cmbpo_mlp_t *vc, const float *d_obs, int obs_dim,
                               const int32_t *d_row_idx, const int32_t *d_n_rows, int n_rows,
                               float *d_v, float *d_vc, void *stream);
+/* The same launch with the critics' own disagreement measured and, where a coefficient is > 0, held against the value.  With
+ * x_e the value of member e (float32, after its inverse_transform: the bits cmbpo_critic_pair_predict adds up), per critic:
+ *   mean  = (((x_0 + x_1) + x_2) + ...) / E                          cmbpo_critic_pair_predict's bits
+ *   var   = q / E, q = sum_e (x_e - mean)^2 in member order          np.var over the members, every operation rounded to
+ *                                                                    float32 on its own, no contraction; E = 1: +0
+ *   d_v   = fl32(mean - fl32(kappa_v  * sqrtf(var_v )))   if kappa_v  > 0, else mean bit for bit
+ *   d_vc  = fl32(mean + fl32(kappa_vc * sqrtf(var_vc)))   if kappa_vc > 0, else mean bit for bit
+ * (sqrtf correctly rounded; the variances are in output units, after the output scaler).  With a coefficient > 0 non-finite
+ * members propagate as NumPy propagates them.  d_v_var / d_vc_var are slot indexed like d_v / d_vc and required.
+ * cmbpo_critic_pair_predict's argument checks; kappa_* finite and >= 0, non-NULL variance outputs -- all before any HIP call.
+ * Same choice of kernel by n_rows as the plain entry (the member-after-member kernel's instances of this entry take chunks of
+ * 448 instead of 512 rows at up to 32 inputs: every member's value of a row stays in LDS). */
+int cmbpo_critic_pair_predict_var(cmbpo_mlp_t *v, cmbpo_mlp_t *vc, const float *d_obs, int obs_dim,
+                                  const int32_t *d_row_idx, const int32_t *d_n_rows, int n_rows,
+                                  float kappa_v, float kappa_vc, float *d_v, float *d_vc,
+                                  float *d_v_var, float *d_vc_var, void *stream);
 
 /* mlp_gaussian_policy forward (network/ac_network.py:99-123) behind
  * CPOPolicy.get_action_outs (policies/cpo_policy.py:801-823): mu = MLP(obs),
@@ -347,6 +363,8 @@ typedef struct cmbpo_rollout {
 #define CMBPO_D_SUM_PATH_COST 12
 #define CMBPO_D_TOTAL_REW_VAR 13   /* sums of rew_var_t / cost_var_t over the stored rows (cmbpo_rollout_disagreement_attach; */
 #define CMBPO_D_TOTAL_COST_VAR 14  /* the reference declares _total_rew_var / _total_cost_var and never fills them)          */
+#define CMBPO_D_TOTAL_V_VAR 15     /* sums of v_var / vc_var (the critics' member variance at the stored rows' observations)   */
+#define CMBPO_D_TOTAL_VC_VAR 16    /* over the stored rows (cmbpo_rollout_value_disagreement_attach)                           */
 
 /* ModelSampler.reset + ModelBuffer.reset (model_sampler.py:203-237,
  * modelbuffer.py:53-98): all B branches alive, lists / accumulators zeroed.
@@ -386,7 +404,8 @@ int cmbpo_rollout_compact(const cmbpo_rollout_t *r, void *stream);
  * finish(POST), every buffer taken from *r (slot-indexed d_eps [B, act], d_elite [B]; scratch d_mean / d_var
  * [E, B, model out_dim]: obs + 1, or obs + 2 with CMBPO_TASK_LEARNED_COST in `task`).  n_alive = the host's copy of iscal[CMBPO_I_N_ALIVE].
  * With r->xi != NULL the post-processing is cmbpo_fakeenv_post_noise on those draws; with a cmbpo_disagreement_t attached it is
- * cmbpo_fakeenv_post_disagreement (with or without draws). */
+ * cmbpo_fakeenv_post_disagreement (with or without draws); with a cmbpo_value_disagreement_t attached the critics at next_obs are
+ * cmbpo_critic_pair_predict_var (refused before the first launch unless cmbpo_critic_pair_supported(v, vc)). */
 /* Small rollout batches: decide + finish(PRE) + store (+ its statistics) as one single-workgroup launch for up to
  * cmbpo_rollout_book_pre_max_rows() alive rows (same decisions and per-branch arithmetic as the separate calls;
  * single-rank path).  cmbpo_rollout_step uses it by itself. */
@@ -458,6 +477,28 @@ typedef struct cmbpo_disagreement {
 int cmbpo_rollout_disagreement_attach(const cmbpo_rollout_t *r, const cmbpo_disagreement_t *dg);
 /* Back to the elite member's reward and cost, nothing measured (no error when nothing was attached). */
 int cmbpo_rollout_disagreement_detach(const cmbpo_rollout_t *r);
+
+/* Critic disagreement along imagined rollouts, and the pessimistic value bootstraps made from it.  The state travels beside
+ * an unchanged cmbpo_rollout_t in the same table (key: r->iscal).  Attached,
+ *   - cmbpo_rollout_step / _run evaluate the critics at next_obs with cmbpo_critic_pair_predict_var(kappa_v, kappa_vc) into
+ *     v_n / vc_n and v_var / vc_var, so the values every later store, bootstrap and GAE reads are the penalised ones; they
+ *     refuse (-1, before the first launch of the step) critics for which cmbpo_critic_pair_supported is false;
+ *   - every call that stores (cmbpo_rollout_store, _book_pre, _step, _run) adds v_var[b] / vc_var[b] over the stored rows to
+ *     dscal[CMBPO_D_TOTAL_V_VAR] / [CMBPO_D_TOTAL_VC_VAR] (per-workgroup partial sums in `part`, added in a fixed order).  The
+ *     store of a step runs BEFORE that step's critic launch: what it reads is the variance at cur_obs, written by the previous
+ *     step's launch or by the caller's evaluation at the start states -- no swap of the two arrays is needed.
+ * A caller that evaluates the critics by itself (the start states; a step made of separate calls) passes the same arrays and
+ * coefficients to cmbpo_critic_pair_predict_var.  Alive masks, the budget rule, next_obs, rewards, costs and DKL do not depend
+ * on the feature.  Device pointers, owned by the caller, valid until the detach; attach again after any of them or r->iscal
+ * moved.  part: 2 * ceil(B / 64) doubles; part == NULL means nothing is attached. */
+typedef struct cmbpo_value_disagreement {
+  float kappa_v, kappa_vc;
+  float *v_var, *vc_var;                  /* [B] slot indexed */
+  double *part;                           /* scratch for per-workgroup partial sums */
+} cmbpo_value_disagreement_t;
+int cmbpo_rollout_value_disagreement_attach(const cmbpo_rollout_t *r, const cmbpo_value_disagreement_t *vd);
+/* Back to the members' mean, nothing measured (no error when nothing was attached). */
+int cmbpo_rollout_value_disagreement_detach(const cmbpo_rollout_t *r);
 
 /* ModelBuffer.get (modelbuffer.py:184-226): d_offsets[B+1] = exclusive scan of
  * len; d_stats[8] = {n, adv_mean, adv_std, cadv_mean, ret_mean, cret_mean}
