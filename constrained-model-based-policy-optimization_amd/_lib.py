@@ -293,6 +293,23 @@ SIGNATURES.update({
     "cmbpo_replay_run": (_i, [_pp, _p, _i, _i, _p, _p]),
 })
 
+# predictive calibration in the replay: per calibrated column (obs_dim + 1 of them) six float64 sums and four int64 counts
+REPLAY_CALIB_SUMS, REPLAY_CALIB_COUNTS = 6, 4  # CMBPO_REPLAY_CALIB_SUMS / _COUNTS
+
+
+class ReplayCalibStruct(C.Structure):
+    """ctypes image of ``cmbpo_replay_calib_t`` (56 bytes), field for field."""
+    _fields_ = [(n, C.c_int32) for n in ("ensemble", "out_dim", "reserved")] + \
+               [(n, C.c_void_p) for n in ("elite", "part_sum", "part_cnt", "sums", "counts")]
+
+
+_cpp = C.POINTER(ReplayCalibStruct)
+SIGNATURES.update({
+    "cmbpo_replay_calibrate": (_i, [_pp, _cpp, _i, _p]),
+    "cmbpo_replay_calib_finish": (_i, [_pp, _cpp, _p]),
+    "cmbpo_replay_run_calibrated": (_i, [_pp, _cpp, _p, _i, _i, _p]),
+})
+
 _lib = None
 
 

@@ -45,6 +45,13 @@ compounds, which real costs and terminations the imagined signal misses, and whe
 the error (``model/val_*``; ``validate_model``, ``FakeEnv.replay``).  It reads and does not steer: it draws from generators of
 its own, and policy and model after a run are bitwise those of the run without it.
 
+``m_validate_calibration=True`` (needs ``m_validate_horizon > 0``) has that replay also measure whether the model's predictive
+VARIANCE is the size of the real error, per horizon and column (``model/val_z2_*``, ``val_cover*``, ``val_nll_tot_h1``,
+``val_ep_var_h1``, ``val_al_var_h1``, ``val_cal_skipped``; ``last_validation['calibration']``); it still reads and does not steer.
+``m_calibrated_noise=True`` (needs it and ``m_stochastic=True``) feeds the one-step result back: after every validation the
+transition noise of the imagined rollouts is scaled per observation column by the root of the maximum-likelihood variance
+temperature, clipped to ``m_noise_temperature_range`` (``ModelSampler.set_noise_scale``; ``model/noise_scale_mean``).
+
 ``static_fns`` takes a ``statics.TaskRules``: user-defined termination / cost rules for the imagined rollouts, with
 precedence over ``task`` (which may itself be a name given to ``statics.register_task``).
 """
@@ -88,6 +95,25 @@ def format_samples_for_dyn(samples, append_r=True, append_c=False):
     return inputs, outputs
 
 
+def _calibration_args(validate_horizon, use_model, stochastic, validate_calibration, calibrated_noise, temperature_range):
+    """The three calibration arguments of ``CMBPO`` checked against each other: (validate_calibration, calibrated_noise,
+    (lo, hi)) or a ValueError that says what is missing."""
+    validate_calibration, calibrated_noise = bool(validate_calibration), bool(calibrated_noise)
+    if validate_calibration and not (int(validate_horizon) > 0 and use_model):
+        raise ValueError("m_validate_calibration needs m_validate_horizon > 0 (and use_model=True): the calibration table is "
+                         "computed inside the validation replay")
+    if calibrated_noise and not (validate_calibration and bool(stochastic)):
+        raise ValueError("m_calibrated_noise needs m_stochastic=True and m_validate_calibration=True: it scales the transition "
+                         "noise by the temperature the validation measures")
+    try:
+        lo, hi = (float(x) for x in temperature_range)
+    except (TypeError, ValueError):
+        raise ValueError("m_noise_temperature_range: a pair (lo, hi), got %r" % (temperature_range,))
+    if not (0.0 < lo <= hi and np.isfinite(hi)):
+        raise ValueError("m_noise_temperature_range: 0 < lo <= hi < inf expected, got %r" % (temperature_range,))
+    return validate_calibration, calibrated_noise, (lo, hi)
+
+
 class CMBPO:
     """Constrained Model-Based Policy Optimization (``algorithms/cmbpo.py:30``)."""
 
@@ -103,7 +129,12 @@ class CMBPO:
                  m_disagreement=False, m_rew_pessimism=0.0, m_cost_pessimism=0.0,
                  m_value_disagreement=False, m_v_pessimism=0.0, m_vc_pessimism=0.0,
                  m_validate_horizon=0, m_validate_windows=1024, m_imagined_weight=1.0, m_trust_var=None,
+                 m_validate_calibration=False, m_calibrated_noise=False, m_noise_temperature_range=(0.25, 4.0),
                  **_unused):
+        # predictive calibration in the validation replay and, from its one-step row, the scale of the transition
+        # noise; refused in words before anything is built
+        self._validate_calibration, self._calibrated_noise, self._noise_temperature_range = _calibration_args(
+            m_validate_horizon, use_model, m_stochastic, m_validate_calibration, m_calibrated_noise, m_noise_temperature_range)
         # RLAlgorithm.__init__ (algorithms/rl_algorithm.py:22-74)
         self.sampler = sampler if sampler is not None else CpoSampler(max_path_length=getattr(policy, "max_path_length", 1000))
         self._n_epochs, self._epoch_length = n_epochs, epoch_length
@@ -274,12 +305,28 @@ class CMBPO:
         if self._validate_rng is None:
             self._validate_rng = np.random.default_rng(0x76616c)
         _, _, win = self._buffer.windows(H, int(n_windows or self._validate_windows), epochs=epochs, rng=self._validate_rng)
-        tab = self.fake_env.replay(**win)
+        tab = self.fake_env.replay(**win, calibration=True) if self._validate_calibration else self.fake_env.replay(**win)
         self.last_validation = tab
         ratio = lambda a, b: float(a) / float(b) if b > 0 else float('nan')
         cm, tm = tab['cost_cm'].sum(axis=0), tab['term_cm'].sum(axis=0)      # [real, predicted], all horizons
         last = H - 1
-        return {'val_n_h1': int(tab['n'][0]), 'val_n_hH': int(tab['n'][last]),
+        extra = {}
+        if self._validate_calibration:
+            # the per-column entries: means over the observation columns (the reward column is in the table)
+            cal, D = tab['calibration'], self.obs_dim
+            col = lambda k, h: float(np.mean(cal[k][h, :D]))
+            extra = {'val_z2_al_h1': col('z2_al', 0), 'val_z2_tot_h1': col('z2_tot', 0), 'val_z2_tot_hH': col('z2_tot', last),
+                     'val_cover1_tot_h1': col('cover1_tot', 0), 'val_cover2_tot_h1': col('cover2_tot', 0),
+                     'val_nll_tot_h1': col('nll_tot', 0), 'val_ep_var_h1': col('ep_var', 0), 'val_al_var_h1': col('al_var', 0),
+                     'val_cal_skipped': int(cal['n_skipped'].sum())}
+            if self._calibrated_noise:
+                if cal['n'][0] > 0:
+                    from .replay import temperature
+                    self.model_sampler.set_noise_scale(np.sqrt(temperature(cal, 'al', 0, *self._noise_temperature_range)))
+                scale = self.model_sampler.noise_scale
+                extra['noise_scale_mean'] = 1.0 if scale is None else float(np.mean(scale))
+        return {**extra,
+                'val_n_h1': int(tab['n'][0]), 'val_n_hH': int(tab['n'][last]),
                 'val_mse_obs_h1': float(np.mean(tab['mse_obs'][0])), 'val_mse_obs_hH': float(np.mean(tab['mse_obs'][last])),
                 'val_mse_rew_hH': float(tab['mse_rew'][last]),
                 'val_cost_miss_rate': ratio(cm[1, 0], cm[1, 0] + cm[1, 1]),

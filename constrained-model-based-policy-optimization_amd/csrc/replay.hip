@@ -5,6 +5,9 @@
 // the existing cmbpo_ens_forward + cmbpo_fakeenv_post (the unpenalised means, no noise); what is new is the comparison:
 //   replay_compare_kernel   one horizon step: per-row verdicts, squared errors, 2x2 counts, the row's next state
 //   replay_finish_kernel    per-workgroup partials -> the [H] result table, in slot order
+// and, for a replay that also checks the model's variance, between post and compare of a step:
+//   replay_calibrate_kernel     one horizon step of the calibration table: squared errors against two predictive variances
+//   replay_calib_finish_kernel  its partials -> the [H] calibration table, in slot order
 // Sums are float64, counts int64, every addition in a fixed order (no floating-point atomics): two runs are bitwise equal.
 #include "common.h"
 
@@ -147,6 +150,217 @@ __global__ __launch_bounds__(kThreads) void replay_finish_kernel(cmbpo_replay_t 
   }
 }
 
+// ---- predictive calibration ----------------------------------------------------------------------------------
+constexpr int kCalSums = CMBPO_REPLAY_CALIB_SUMS;     // e^2/v_al, e_tot^2/v_tot, log v_al, log v_tot, v_bar, s2 -- per column
+constexpr int kCalCounts = CMBPO_REPLAY_CALIB_COUNTS; // e^2 <= v_al, <= 4 v_al, e_tot^2 <= v_tot, <= 4 v_tot -- per column
+
+// The members' values of one (row, column) are B * out_dim floats apart and a thread's sum over them is sequential by
+// definition, so a loop of one load per member is a chain of E memory latencies.  Members e0 .. e0 + kCalBatch - 1 are loaded
+// together instead (behind the last member: that member again, the caller masks it), the arithmetic follows in member order.
+constexpr int kCalBatch = 8;
+constexpr int kCalRows = 4;
+__device__ __forceinline__ void load_members(const float *p, size_t member, int e0, int E, float (&out)[kCalBatch]) {
+#pragma unroll
+  for (int j = 0; j < kCalBatch; ++j) out[j] = p[(size_t)min(e0 + j, E - 1) * member];
+}
+
+// One horizon step of the calibration table; the geometry of replay_compare_kernel (kRows rows per workgroup, slot =
+// workgroup).  The [rows, out_dim] tile of one member's mean / var is one contiguous run, walked flat like the predictions
+// there: thread t sits on column t % W of row t / W and advances by kThreads / W rows, so a thread stays on one column and
+// keeps that column's six sums and four counts in registers; columns >= C = obs_dim + 1 (a learned cost) have no work.
+// Pass 1 settles the rows' verdicts (integer LDS flags: order cannot matter), pass 2 reads everything again (L1 / L2) and
+// sums.  Reads alive / predictions / recording / mean / var, writes its partial slot only.
+__global__ __launch_bounds__(kThreads) void replay_calibrate_kernel(cmbpo_replay_t rp, cmbpo_replay_calib_t rc, int h) {
+  __shared__ uint8_t s_alive[kRows];              // alive on entry
+  __shared__ int s_bad[kRows];                    // a non-finite prediction in the row (the compare kernel's verdict)
+  __shared__ int s_rej[kRows];                    // a mean / variance this table cannot use, or no such member
+  __shared__ int s_elite[kRows];
+  __shared__ uint8_t s_in[kRows];                 // the row enters the table
+  __shared__ double s_sum[kCalSums][kThreads];    // per-thread column sums, folded by the first W threads
+  __shared__ int s_cnt[kCalCounts][kThreads];
+
+  const int t = threadIdx.x;
+  const int B = rp.B, D = rp.obs_dim, E = rc.ensemble, O = rc.out_dim;
+  const int C = D + 1;
+  const int row0 = blockIdx.x * kRows;
+  const int rows = min(kRows, B - row0);
+  const size_t hb = (size_t)h * B;
+  double *psum = rc.part_sum + ((size_t)h * gridDim.x + blockIdx.x) * (kCalSums * C);
+  int64_t *pcnt = rc.part_cnt + ((size_t)h * gridDim.x + blockIdx.x) * (kCalCounts * C + 2);
+
+  if (t < kRows) {
+    const bool alive = t < rows && rp.alive[row0 + t] != 0;
+    bool bad = false, rej = false;
+    int m = 0;
+    if (alive) {
+      bad = !(isfinite(rp.p_rew[row0 + t]) && isfinite(rp.p_cost[row0 + t]));
+      m = rc.elite[hb + row0 + t];
+      rej = m < 0 || m >= E;
+      if (rej) m = 0;
+    }
+    s_alive[t] = alive;
+    s_bad[t] = bad;
+    s_rej[t] = rej;
+    s_elite[t] = m;
+  }
+  __syncthreads();
+
+  // pass 1a: the compare kernel's rule on the predicted observations
+  const float *pred = rp.p_next_obs + (size_t)row0 * D;
+  for (int i = t, total = rows * D; i < total; i += kThreads) {
+    const int r = i / D;
+    if (s_alive[r] && !isfinite(pred[i])) atomicOr(&s_bad[r], 1);
+  }
+  __syncthreads();
+
+  // pass 1b: every member's mean and variance of the calibrated columns
+  const int W = min(O, kThreads);          // columns of one sweep
+  const int rpp = kThreads / W;            // rows of one sweep
+  const int r0 = t / W;
+  const size_t member = (size_t)B * O;     // elements of one member's [B, out_dim]
+  const float *mean0 = rp.mean + (size_t)row0 * O, *var0 = rp.var + (size_t)row0 * O;
+  for (int c0 = 0; c0 < C; c0 += W) {      // (one trip unless out_dim > kThreads)
+    const int c = c0 + t % W;
+    if (r0 < rpp && c < C) {
+      // kCalRows of the thread's rows at a time (behind the last row: that row again, not marked), so that
+      // 2 * kCalBatch * kCalRows loads are in flight: what this pass costs is memory round trips, not bytes
+      for (int rb = r0; rb < rows; rb += kCalRows * rpp) {
+        for (int e0 = 0; e0 < E; e0 += kCalBatch) {
+          float mu[kCalRows][kCalBatch], v[kCalRows][kCalBatch];
+#pragma unroll
+          for (int k = 0; k < kCalRows; ++k) {
+            const size_t i = (size_t)min(rb + k * rpp, rows - 1) * O + c;
+            load_members(mean0 + i, member, e0, E, mu[k]);
+            load_members(var0 + i, member, e0, E, v[k]);
+          }
+#pragma unroll
+          for (int k = 0; k < kCalRows; ++k) {
+            const int r = rb + k * rpp;
+            bool good = true;
+#pragma unroll
+            for (int j = 0; j < kCalBatch; ++j) good = good && isfinite(mu[k][j]) && isfinite(v[k][j]) && v[k][j] > 0.0f;
+            if (r < rows && !good && s_alive[r] && !s_bad[r]) atomicOr(&s_rej[r], 1);
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  if (t < kRows) {
+    const bool cand = s_alive[t] != 0 && s_bad[t] == 0;      // the rows the compare kernel sums
+    const bool in = cand && s_rej[t] == 0;
+    s_in[t] = in;
+    const int64_t n_cal = lanes_set(in), n_skip = lanes_set(cand && !in);
+    if (t == 0) { pcnt[kCalCounts * C] = n_cal; pcnt[kCalCounts * C + 1] = n_skip; }
+  }
+  __syncthreads();
+
+  // pass 2: the sums
+  const float *real = rp.next_obs + (hb + row0) * D;
+  const double n_mem = (double)E;
+  for (int c0 = 0; c0 < C; c0 += W) {
+    const int c = c0 + t % W;
+    double a_zal = 0.0, a_ztot = 0.0, a_lal = 0.0, a_ltot = 0.0, a_vbar = 0.0, a_s2 = 0.0;
+    int n1_al = 0, n2_al = 0, n1_tot = 0, n2_tot = 0;
+    if (r0 < rpp && c < C) {
+      for (int r = r0; r < rows; r += rpp) {
+        if (!s_in[r]) continue;
+        const int m = s_elite[r];
+        const size_t i = (size_t)r * O + c;
+        const float ef = c < D ? __fsub_rn(pred[(size_t)r * D + c], real[(size_t)r * D + c])
+                               : __fsub_rn(rp.p_rew[row0 + r], rp.rew[hb + row0 + r]);
+        const double err = (double)ef;
+        // the first kCalBatch members stay in registers for the second loop and the elite's pick (E <= kCalBatch: one
+        // round trip per row); members behind them are read again (L1 / L2)
+        float mu0[kCalBatch], v0[kCalBatch];
+        load_members(mean0 + i, member, 0, E, mu0);
+        load_members(var0 + i, member, 0, E, v0);
+        float mu_mf = 0.0f, v_mf = 0.0f;
+        if (m >= kCalBatch) { mu_mf = mean0[m * member + i]; v_mf = var0[m * member + i]; }
+        double s_mu = 0.0, s_v = 0.0;
+#pragma unroll
+        for (int j = 0; j < kCalBatch; ++j) {
+          if (j < E) { s_mu += (double)mu0[j]; s_v += (double)v0[j]; }
+          if (j == m) { mu_mf = mu0[j]; v_mf = v0[j]; }
+        }
+        for (int e0 = kCalBatch; e0 < E; e0 += kCalBatch) {
+          float mu[kCalBatch], v[kCalBatch];
+          load_members(mean0 + i, member, e0, E, mu);
+          load_members(var0 + i, member, e0, E, v);
+#pragma unroll
+          for (int j = 0; j < kCalBatch; ++j)
+            if (e0 + j < E) { s_mu += (double)mu[j]; s_v += (double)v[j]; }
+        }
+        const double mu_bar = s_mu / n_mem, v_bar = s_v / n_mem;
+        double dev = 0.0;
+#pragma unroll
+        for (int j = 0; j < kCalBatch; ++j)
+          if (j < E) { const double d = (double)mu0[j] - mu_bar; dev += d * d; }
+        for (int e0 = kCalBatch; e0 < E; e0 += kCalBatch) {
+          float mu[kCalBatch];
+          load_members(mean0 + i, member, e0, E, mu);
+#pragma unroll
+          for (int j = 0; j < kCalBatch; ++j)
+            if (e0 + j < E) { const double d = (double)mu[j] - mu_bar; dev += d * d; }
+        }
+        const double s2 = dev / n_mem;
+        const double v_al = (double)v_mf;
+        const double v_tot = v_bar + s2;
+        const double e_tot = err + (mu_bar - (double)mu_mf);
+        const double q_al = err * err, q_tot = e_tot * e_tot;
+        a_zal += q_al / v_al;
+        a_ztot += q_tot / v_tot;
+        a_lal += log(v_al);
+        a_ltot += log(v_tot);
+        a_vbar += v_bar;
+        a_s2 += s2;
+        n1_al += q_al <= v_al;
+        n2_al += q_al <= 4.0 * v_al;
+        n1_tot += q_tot <= v_tot;
+        n2_tot += q_tot <= 4.0 * v_tot;
+      }
+    }
+    s_sum[0][t] = a_zal; s_sum[1][t] = a_ztot; s_sum[2][t] = a_lal; s_sum[3][t] = a_ltot; s_sum[4][t] = a_vbar; s_sum[5][t] = a_s2;
+    s_cnt[0][t] = n1_al; s_cnt[1][t] = n2_al; s_cnt[2][t] = n1_tot; s_cnt[3][t] = n2_tot;
+    __syncthreads();
+    if (t < W && c0 + t < C) {             // the rpp accumulators of a column, in a fixed order
+#pragma unroll
+      for (int k = 0; k < kCalSums; ++k) {
+        double s = s_sum[k][t];
+        for (int j = 1; j < rpp; ++j) s += s_sum[k][j * W + t];
+        psum[k * C + c0 + t] = s;
+      }
+#pragma unroll
+      for (int k = 0; k < kCalCounts; ++k) {
+        int64_t s = s_cnt[k][t];
+        for (int j = 1; j < rpp; ++j) s += s_cnt[k][j * W + t];
+        pcnt[k * C + c0 + t] = s;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// the calibration table: sums and counts over the slots, in slot order; one workgroup per horizon, one thread per entry
+__global__ __launch_bounds__(kThreads) void replay_calib_finish_kernel(cmbpo_replay_calib_t rc, int obs_dim, int n_part) {
+  const int h = blockIdx.x;
+  const int NS = kCalSums * (obs_dim + 1), NC = kCalCounts * (obs_dim + 1) + 2;
+  for (int j = threadIdx.x; j < NS + NC; j += kThreads) {
+    if (j < NS) {
+      const double *p = rc.part_sum + (size_t)h * n_part * NS + j;
+      double s = 0.0;
+      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NS];
+      rc.sums[(size_t)h * NS + j] = s;
+    } else {
+      const int64_t *p = rc.part_cnt + (size_t)h * n_part * NC + (j - NS);
+      int64_t s = 0;
+      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NC];
+      rc.counts[(size_t)h * NC + (j - NS)] = s;
+    }
+  }
+}
+
 int check_shape(const char *who, const cmbpo_replay_t *rp) {
   CMBPO_REQUIRE(rp != nullptr, "%s: descriptor is NULL", who);
   CMBPO_REQUIRE(rp->B >= 1, "%s: B %d < 1", who, rp->B);
@@ -187,12 +401,77 @@ int launch_finish(const cmbpo_replay_t *rp, hipStream_t s) {
   return CMBPO_OK;
 }
 
+int check_calib(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc) {
+  CMBPO_REQUIRE(rc != nullptr, "%s: calibration descriptor is NULL", who);
+  CMBPO_REQUIRE(rc->ensemble >= 1, "%s: ensemble %d < 1", who, rc->ensemble);
+  CMBPO_REQUIRE(rc->out_dim >= rp->obs_dim + 1, "%s: out_dim %d < obs_dim + 1 = %d", who, rc->out_dim, rp->obs_dim + 1);
+  CMBPO_REQUIRE(rc->reserved == 0, "%s: calibration reserved %d != 0", who, rc->reserved);
+  return CMBPO_OK;
+}
+
+int check_calibrate(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc) {
+  if (int r = check_compare(who, rp)) return r;
+  if (int r = check_calib(who, rp, rc)) return r;
+  CMBPO_REQUIRE(rp->mean && rp->var, "%s: NULL buffer (mean / var)", who);
+  CMBPO_REQUIRE(rc->elite, "%s: NULL buffer (elite)", who);
+  CMBPO_REQUIRE(rc->part_sum && rc->part_cnt, "%s: NULL buffer (calibration partials)", who);
+  return CMBPO_OK;
+}
+
+int check_calib_finish(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc) {
+  if (int r = check_shape(who, rp)) return r;
+  if (int r = check_calib(who, rp, rc)) return r;
+  CMBPO_REQUIRE(rc->part_sum && rc->part_cnt, "%s: NULL buffer (calibration partials)", who);
+  CMBPO_REQUIRE(rc->sums && rc->counts, "%s: NULL buffer (calibration table)", who);
+  return CMBPO_OK;
+}
+
+int launch_calibrate(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, int h, hipStream_t s) {
+  hipLaunchKernelGGL(replay_calibrate_kernel, dim3(cmbpo_replay_parts(rp->B)), dim3(kThreads), 0, s, *rp, *rc, h);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
+int launch_calib_finish(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, hipStream_t s) {
+  hipLaunchKernelGGL(replay_calib_finish_kernel, dim3(rp->H), dim3(kThreads), 0, s, *rc, rp->obs_dim, cmbpo_replay_parts(rp->B));
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
 // a callee's refusal, passed on under this entry point's name
 int refused_by(const char *who, int rc) {
   char inner[400];
   snprintf(inner, sizeof(inner), "%s", cmbpo_last_error());
   cmbpo_set_error("%s: %s", who, inner);
   return rc;
+}
+
+// cmbpo_replay_run (cal == nullptr: exactly its launches) and cmbpo_replay_run_calibrated (the calibrate kernel between post and
+// compare, its finish behind the plain one); every argument has been checked by the caller
+int run_steps(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *cal, cmbpo_mlp_t *model, int task, int ensemble,
+              const int32_t *d_elite, void *stream) {
+  const int B = rp->B, D = rp->obs_dim, A = rp->act_dim;
+  // the two callees' own argument checks, on a call of no rows (neither launches anything for it)
+  if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, rp->act, A, nullptr, nullptr, 0, B, rp->mean, rp->var, stream))
+    return refused_by(who, rc);
+  if (int rc = cmbpo_fakeenv_post(task, ensemble, D, A, rp->mean, rp->var, B, rp->cur_obs, rp->act, d_elite, nullptr, nullptr, 0,
+                                  rp->p_next_obs, rp->p_rew, rp->p_term, rp->p_cost, rp->p_dkl_path, rp->p_ep_var_mean, nullptr,
+                                  stream))
+    return refused_by(who, rc);
+  for (int h = 0; h < rp->H; ++h) {
+    const float *act_h = rp->act ? rp->act + (size_t)h * B * A : nullptr;
+    if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, act_h, A, nullptr, nullptr, B, B, rp->mean, rp->var, stream))
+      return refused_by(who, rc);
+    if (int rc = cmbpo_fakeenv_post(task, ensemble, D, A, rp->mean, rp->var, B, rp->cur_obs, act_h, d_elite + (size_t)h * B, nullptr,
+                                    nullptr, B, rp->p_next_obs, rp->p_rew, rp->p_term, rp->p_cost, rp->p_dkl_path,
+                                    rp->p_ep_var_mean, nullptr, stream))
+      return refused_by(who, rc);
+    if (cal)
+      if (int rc = launch_calibrate(rp, cal, h, (hipStream_t)stream)) return rc;
+    if (int rc = launch_compare(rp, h, (hipStream_t)stream)) return rc;
+  }
+  if (int rc = launch_finish(rp, (hipStream_t)stream)) return rc;
+  return cal ? launch_calib_finish(rp, cal, (hipStream_t)stream) : CMBPO_OK;
 }
 
 }  // namespace
@@ -219,23 +498,29 @@ extern "C" int cmbpo_replay_run(const cmbpo_replay_t *rp, cmbpo_mlp_t *model, in
   CMBPO_REQUIRE(model != nullptr, "%s: model handle is NULL", who);
   CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);
   CMBPO_REQUIRE((rp->act_dim == 0 || rp->act) && rp->mean && rp->var, "%s: NULL buffer (act / mean / var)", who);
-  const int B = rp->B, D = rp->obs_dim, A = rp->act_dim;
-  // the two callees' own argument checks, on a call of no rows (neither launches anything for it)
-  if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, rp->act, A, nullptr, nullptr, 0, B, rp->mean, rp->var, stream))
-    return refused_by(who, rc);
-  if (int rc = cmbpo_fakeenv_post(task, ensemble, D, A, rp->mean, rp->var, B, rp->cur_obs, rp->act, d_elite, nullptr, nullptr, 0,
-                                  rp->p_next_obs, rp->p_rew, rp->p_term, rp->p_cost, rp->p_dkl_path, rp->p_ep_var_mean, nullptr,
-                                  stream))
-    return refused_by(who, rc);
-  for (int h = 0; h < rp->H; ++h) {
-    const float *act_h = rp->act ? rp->act + (size_t)h * B * A : nullptr;
-    if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, act_h, A, nullptr, nullptr, B, B, rp->mean, rp->var, stream))
-      return refused_by(who, rc);
-    if (int rc = cmbpo_fakeenv_post(task, ensemble, D, A, rp->mean, rp->var, B, rp->cur_obs, act_h, d_elite + (size_t)h * B, nullptr,
-                                    nullptr, B, rp->p_next_obs, rp->p_rew, rp->p_term, rp->p_cost, rp->p_dkl_path,
-                                    rp->p_ep_var_mean, nullptr, stream))
-      return refused_by(who, rc);
-    if (int rc = launch_compare(rp, h, (hipStream_t)stream)) return rc;
-  }
-  return launch_finish(rp, (hipStream_t)stream);
+  return run_steps(who, rp, nullptr, model, task, ensemble, d_elite, stream);
+}
+
+extern "C" int cmbpo_replay_calibrate(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, int h, void *stream) {
+  const char *who = "cmbpo_replay_calibrate";
+  if (int r = check_calibrate(who, rp, rc)) return r;
+  CMBPO_REQUIRE(h >= 0 && h < rp->H, "%s: h %d outside [0, %d)", who, h, rp->H);
+  return launch_calibrate(rp, rc, h, (hipStream_t)stream);
+}
+
+extern "C" int cmbpo_replay_calib_finish(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, void *stream) {
+  if (int r = check_calib_finish("cmbpo_replay_calib_finish", rp, rc)) return r;
+  return launch_calib_finish(rp, rc, (hipStream_t)stream);
+}
+
+extern "C" int cmbpo_replay_run_calibrated(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, cmbpo_mlp_t *model, int task,
+                                           int ensemble, void *stream) {
+  const char *who = "cmbpo_replay_run_calibrated";
+  if (int r = check_calibrate(who, rp, rc)) return r;
+  if (int r = check_finish(who, rp)) return r;
+  if (int r = check_calib_finish(who, rp, rc)) return r;
+  CMBPO_REQUIRE(model != nullptr, "%s: model handle is NULL", who);
+  CMBPO_REQUIRE(rp->act_dim == 0 || rp->act, "%s: NULL buffer (act)", who);
+  CMBPO_REQUIRE(ensemble == rc->ensemble, "%s: ensemble %d, the calibration descriptor's is %d", who, ensemble, rc->ensemble);
+  return run_steps(who, rp, rc, model, task, ensemble, rc->elite, stream);
 }

@@ -213,7 +213,8 @@ class FakeEnv:
             info["ensemble_rew_var"], info["ensemble_cost_var"] = rv, cv
         return next_obs, r, terms, info
 
-    def replay(self, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, model_inds=None, mode='open_loop'):
+    def replay(self, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, model_inds=None, mode='open_loop',
+               calibration=False):
         """Open-loop model validation: replay B windows of up to H consecutive REAL steps through the model and hold its
         predictions against the recording, horizon by horizon (``cmbpo_replay_run``).
 
@@ -236,12 +237,17 @@ class FakeEnv:
         ``mse_obs`` [H, obs], ``mse_rew``, ``mse_cost``, ``cost_cm`` / ``term_cm`` [H, 2, 2] indexed [real, predicted] (a
         real cost is ``cost > 0``, a predicted one ``cost > 0.5``), ``ep_var_mean`` and ``dkl_mean`` (the means of the step's
         ``ep_var_mean`` / ``dkl_path`` over the same windows), and the float64 sums they were divided from: ``se_obs``,
-        ``se_rew``, ``se_cost``, ``sum_ep_var``, ``sum_dkl``.  A horizon with ``n == 0`` has NaN means and zero counts."""
+        ``se_rew``, ``se_cost``, ``sum_ep_var``, ``sum_dkl``.  A horizon with ``n == 0`` has NaN means and zero counts.
+
+        ``calibration=True`` runs ``cmbpo_replay_run_calibrated`` instead: the same launches with one more kernel
+        per step, the same table bit for bit, and under the key ``'calibration'`` the dict of
+        ``cmbpo_amd.replay.calibration_table`` -- is the predictive VARIANCE the size of the real error, per horizon and per
+        column (the observation columns, then the reward).  False is the call as it always was."""
         from .replay import ReplayBuffers
         E = self._model.num_nets
         with torch.cuda.device(self.device):
             rb = ReplayBuffers(obs0, actions, next_obs, rewards, costs, terminals, lengths=lengths, mode=mode, ensemble=E,
-                               out_dim=self.output_dim, device=self.device)
+                               out_dim=self.output_dim, device=self.device, calibration=bool(calibration))
             if (rb.obs_dim, rb.act_dim) != (self.obs_dim, self.act_dim):
                 raise ValueError("replay: windows of width (%d, %d), the model's is (%d, %d)"
                                  % (rb.obs_dim, rb.act_dim, self.obs_dim, self.act_dim))
@@ -258,6 +264,11 @@ class FakeEnv:
             if inds.shape != (H, B) or inds.min() < 0 or inds.max() >= E:
                 raise ValueError("replay: model_inds must be an int or an [%d, %d] array of members in 0..%d" % (H, B, E - 1))
             elite = torch.from_numpy(np.ascontiguousarray(inds, dtype=np.int32)).to(self.device)
+            if calibration:
+                rb.run_calibrated(self._model.mlp.handle, self._task_id, E, elite)
+                tab = rb.table()
+                tab['calibration'] = rb.calibration_table()
+                return tab
             rb.run(self._model.mlp.handle, self._task_id, E, elite)
             return rb.table()
 

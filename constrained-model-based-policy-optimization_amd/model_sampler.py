@@ -56,7 +56,8 @@ class ModelSampler:
         self._calib_total_dkl = 0.0
         self._calib_total_samples = 0.0
         self._diag = None
-        self.global_alive = 1                       # alive branches over all shards (sharded samplers), see reset()
+        self._noise_scale = None                    # [obs] factors on the xi draws (host tensor), see set_noise_scale()
+        self.global_alive = 1                      # alive branches over all shards (sharded samplers), see reset()
         self._global_total_samples = 0.0
 
     # -- wiring -----------------------------------------------------------------------------------
@@ -86,6 +87,31 @@ class ModelSampler:
 
     def set_max_path_length(self, path_length):
         self._max_path_length = int(path_length)
+
+    @property
+    def noise_scale(self):
+        """The factors of ``set_noise_scale`` as a float32 NumPy array, or None."""
+        return None if self._noise_scale is None else self._noise_scale.numpy().copy()
+
+    def set_noise_scale(self, scale):
+        """Calibrated transition noise: a `stochastic` sampler multiplies every xi chunk it draws from now on by
+        ``scale`` [obs] (array or tensor; one float32 rounding per element), which is the elite member's std scaled per
+        column.  An explicit ``xi=`` argument of ``sample`` is never scaled.  A scale that differs from the one in force drops
+        the rest of the chunk of draws in hand (the next step draws a new one under the new scale); the same scale again drops
+        nothing.  None (the default): the draws as they come, exactly the generator calls of a sampler that never heard of this."""
+        if scale is None:
+            if self._noise_scale is not None:
+                self._noise_scale, self._draws = None, None
+            return
+        if not self.stochastic:
+            raise ValueError("set_noise_scale: this sampler was built with stochastic=False, it draws no transition noise to scale")
+        s = torch.as_tensor(np.asarray(scale.detach().cpu() if isinstance(scale, torch.Tensor) else scale, dtype=np.float32))
+        if s.dim() != 1 or (self.pool is not None and s.shape[0] != self.pool.obs_dim):
+            raise ValueError("set_noise_scale: one factor per observation column expected, got shape %s" % (tuple(s.shape),))
+        if not bool(torch.isfinite(s).all()) or not bool((s > 0).all()):
+            raise ValueError("set_noise_scale: the factors must be finite and positive")
+        if self._noise_scale is None or not torch.equal(self._noise_scale, s):
+            self._noise_scale, self._draws = s, None
 
     def batch_ready(self):
         return self.pool.size >= self.pool.max_size
@@ -327,6 +353,8 @@ class ModelSampler:
         x_ck = None
         if self.stochastic:
             x_ck = torch.randn((K, B, self.pool.obs_dim), generator=self._gen, dtype=torch.float32, device=self.device)
+            if self._noise_scale is not None:
+                x_ck.mul_(self._noise_scale.to(self.device))
         self._draws = [0, e_ck, self._elites[d_ck], x_ck]
         return self._draws
 

@@ -5,6 +5,10 @@
 state, the post kernel's outputs of the step, the partial sums and the table -- and the ctypes image handed to
 ``cmbpo_replay_compare`` / ``_finish`` / ``_run``.  ``FakeEnv.replay`` is the user's entry; the tests and
 ``tools/probe_replay.py`` drive the single calls through this class.
+
+Predictive calibration: ``ReplayBuffers(..., calibration=True)`` also owns the arrays of
+``cmbpo_replay_calib_t``; ``calibration_table`` builds the per-horizon, per-column table from its raw sums and counts, and
+``temperature`` turns one row of it into the variance temperature ``ModelSampler.set_noise_scale`` takes the root of.
 """
 import ctypes as C
 
@@ -15,6 +19,9 @@ from . import _lib
 
 MODES = {"open_loop": _lib.REPLAY_OPEN_LOOP, "one_step": _lib.REPLAY_ONE_STEP}
 SUM_KEYS = ("se_rew", "se_cost", "sum_ep_var", "sum_dkl")      # columns obs_dim .. obs_dim + 3 of `sums`
+# the calibration table's raw arrays, [H, obs + 1] each, in the order of `sums` [H, 6, obs + 1] / `counts` [H, 4, obs + 1]
+CALIB_SUM_KEYS = ("sum_z2_al", "sum_z2_tot", "sum_log_v_al", "sum_log_v_tot", "sum_v_bar", "sum_s2")
+CALIB_COUNT_KEYS = ("n_cover1_al", "n_cover2_al", "n_cover1_tot", "n_cover2_tot")
 
 
 def _as(x, dtype, device):
@@ -26,10 +33,11 @@ def _as(x, dtype, device):
 
 class ReplayBuffers:
     def __init__(self, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, mode="open_loop", ensemble=0,
-                 out_dim=0, device="cuda"):
+                 out_dim=0, device="cuda", calibration=False):
         """obs0 [B, obs]; actions [H, B, act]; next_obs [H, B, obs]; rewards / costs / terminals [H, B] (a trailing axis
         of one is dropped); lengths [B] in 1..H (None: H).  NumPy arrays or tensors.  ``ensemble`` / ``out_dim`` > 0 also
-        allocate the forward's scratch ``cmbpo_replay_run`` needs."""
+        allocate the forward's scratch ``cmbpo_replay_run`` needs.  ``calibration=True`` (needs both) also allocates the
+        arrays of the calibration table and its member indices ``elite`` [H, B] int32, zeros until ``set_elite``."""
         if mode not in MODES:
             raise ValueError("replay mode: 'open_loop' or 'one_step', got %r" % (mode,))
         dev = torch.device(device)
@@ -77,6 +85,22 @@ class ReplayBuffers:
         for k, v in self.t.items():
             setattr(rs, k, v.data_ptr())
         self.rs = rs
+        self.cs = self.c = None
+        if calibration:
+            if ensemble < 1 or out_dim < D + 1:
+                raise ValueError("replay: calibration needs the forward's scratch: ensemble >= 1 and out_dim >= obs + 1 = %d, "
+                                 "got %d and %d" % (D + 1, ensemble, out_dim))
+            ns, nc = _lib.REPLAY_CALIB_SUMS * (D + 1), _lib.REPLAY_CALIB_COUNTS * (D + 1) + 2
+            self.c = dict(elite=torch.zeros((H, B), dtype=i32, device=dev),
+                          part_sum=torch.zeros((H, self.n_part, ns), dtype=torch.float64, device=dev),
+                          part_cnt=torch.zeros((H, self.n_part, nc), dtype=torch.int64, device=dev),
+                          sums=torch.zeros((H, ns), dtype=torch.float64, device=dev),
+                          counts=torch.zeros((H, nc), dtype=torch.int64, device=dev))
+            cs = _lib.ReplayCalibStruct()
+            cs.ensemble, cs.out_dim, cs.reserved = int(ensemble), int(out_dim), 0
+            for k, v in self.c.items():
+                setattr(cs, k, v.data_ptr())
+            self.cs = cs
 
     def step_outputs(self):
         """The dict ``FakeEnv.step_device`` fills: the prediction arrays ``cmbpo_replay_compare`` reads."""
@@ -98,6 +122,37 @@ class ReplayBuffers:
     def table(self):
         return table(self.t["sums"].cpu().numpy(), self.t["counts"].cpu().numpy(), self.obs_dim)
 
+    # -- predictive calibration (calibration=True) ---------------------------------------------------------------------
+    def _calib(self):
+        if self.cs is None:
+            raise ValueError("replay: these buffers were built with calibration=False")
+        return C.byref(self.cs)
+
+    def set_elite(self, elite):
+        """The member of every window at every step, [H, B] (what ``calibrate`` and ``run_calibrated`` read)."""
+        self._calib()
+        self.c["elite"].copy_(_as(elite, torch.int32, self.device).reshape(self.H, self.B))
+
+    def calibrate(self, h):
+        """``cmbpo_replay_calibrate``: call it BEFORE ``compare(h)``, which clears ``alive`` and overwrites ``cur_obs``."""
+        _lib.check(_lib.lib().cmbpo_replay_calibrate(C.byref(self.rs), self._calib(), int(h), _lib.current_stream()),
+                   "cmbpo_replay_calibrate")
+
+    def calib_finish(self):
+        _lib.check(_lib.lib().cmbpo_replay_calib_finish(C.byref(self.rs), self._calib(), _lib.current_stream()),
+                   "cmbpo_replay_calib_finish")
+
+    def run_calibrated(self, model_handle, task_id, ensemble, elite=None):
+        """``cmbpo_replay_run_calibrated``; elite: [H, B] members (None: those of the last ``set_elite``)."""
+        if elite is not None:
+            self.set_elite(elite)
+        _lib.check(_lib.lib().cmbpo_replay_run_calibrated(C.byref(self.rs), self._calib(), model_handle, int(task_id),
+                                                          int(ensemble), _lib.current_stream()), "cmbpo_replay_run_calibrated")
+
+    def calibration_table(self):
+        self._calib()
+        return calibration_table(self.c["sums"].cpu().numpy(), self.c["counts"].cpu().numpy(), self.obs_dim)
+
 
 def table(sums, counts, obs_dim):
     """The result dict from the raw ``sums`` [H, obs + 4] (float64) and ``counts`` [H, 10] (int64): means over the rows
@@ -118,3 +173,51 @@ def table(sums, counts, obs_dim):
         out["ep_var_mean"] = out["sum_ep_var"] / den + nan
         out["dkl_mean"] = out["sum_dkl"] / den + nan
     return out
+
+
+def calibration_table(sums, counts, obs_dim):
+    """The calibration dict from the raw ``sums`` [H, 6 (obs + 1)] (float64) and ``counts`` [H, 4 (obs + 1) + 2] (int64).
+    Column c < obs is observation column c, column obs the reward.  ``n`` / ``n_skipped`` [H]: the rows that entered / that the
+    plain table sums and this one rejects.  Per horizon and column, [H, obs + 1]: ``z2_al`` / ``z2_tot`` the mean squared
+    standardised error against the elite member's variance / the moment-matched mixture's (1 when calibrated; the maximum-
+    likelihood temperature of that variance), ``nll_*`` = 0.5 (log 2 pi + mean log v + z2), ``cover1_*`` / ``cover2_*`` the
+    share of errors inside one / two sigma (0.6827 / 0.9545 when calibrated), ``al_var`` / ``ep_var`` the means of the members'
+    mean variance and of the variance of their means, in the column's own units -- and the raw sums and counts
+    (``CALIB_SUM_KEYS``, ``CALIB_COUNT_KEYS``).  NaN means where ``n == 0``.  In ``open_loop`` mode only horizon 0 is a
+    one-step prediction: later rows show how far the one-step variance falls short of the compounded error."""
+    sums, counts = np.asarray(sums, np.float64), np.asarray(counts, np.int64)
+    H, Cc = sums.shape[0], int(obs_dim) + 1
+    ks, kc = _lib.REPLAY_CALIB_SUMS, _lib.REPLAY_CALIB_COUNTS
+    if sums.shape != (H, ks * Cc) or counts.shape != (H, kc * Cc + 2):
+        raise ValueError("calibration_table: sums [H, %d] and counts [H, %d] expected for obs_dim %d, got %s and %s"
+                         % (ks * Cc, kc * Cc + 2, obs_dim, sums.shape, counts.shape))
+    s, c = sums.reshape(H, ks, Cc), counts[:, :kc * Cc].reshape(H, kc, Cc)
+    n = counts[:, kc * Cc].copy()
+    out = dict(n=n, n_skipped=counts[:, kc * Cc + 1].copy())
+    for j, k in enumerate(CALIB_SUM_KEYS):
+        out[k] = s[:, j].copy()
+    for j, k in enumerate(CALIB_COUNT_KEYS):
+        out[k] = c[:, j].copy()
+    den = np.where(n > 0, n, 1).astype(np.float64)[:, None]
+    nan = np.where(n > 0, 0.0, np.nan)[:, None]
+    mean = lambda k: out[k] / den + nan
+    log2pi = np.log(2.0 * np.pi)
+    for which in ("al", "tot"):
+        out["z2_" + which] = mean("sum_z2_" + which)
+        out["nll_" + which] = 0.5 * (log2pi + mean("sum_log_v_" + which) + out["z2_" + which])
+        out["cover1_" + which] = mean("n_cover1_" + which)
+        out["cover2_" + which] = mean("n_cover2_" + which)
+    out["al_var"], out["ep_var"] = mean("sum_v_bar"), mean("sum_s2")
+    return out
+
+
+def temperature(cal, which="al", horizon=0, lo=0.25, hi=4.0):
+    """The variance temperature per observation column, [obs] float32: ``clip(z2_<which>[horizon, :obs], lo, hi)``, 1.0 where
+    the table has no value (NaN).  Its square root scales a standard deviation."""
+    if which not in ("al", "tot"):
+        raise ValueError("temperature: which is 'al' or 'tot', got %r" % (which,))
+    lo, hi = float(lo), float(hi)
+    if not (0.0 < lo <= hi and np.isfinite(hi)):
+        raise ValueError("temperature: 0 < lo <= hi < inf expected, got %r, %r" % (lo, hi))
+    z2 = np.asarray(cal["z2_" + which], np.float64)[int(horizon), :-1]
+    return np.where(np.isnan(z2), 1.0, np.clip(z2, lo, hi)).astype(np.float32)

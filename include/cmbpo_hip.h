@@ -918,6 +918,57 @@ int cmbpo_replay_finish(const cmbpo_replay_t *rp, void *stream);
 int cmbpo_replay_run(const cmbpo_replay_t *rp, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite,
                      void *stream);
 
+/* ---- predictive calibration in the replay (csrc/replay.hip) ---------------------------------
+ * Is the ensemble's VARIANCE right?  At horizon h of a replay the forward's (mean, var)[E][B][out_dim] scratch sits beside
+ * the post kernel's prediction and the recording; the calibration table holds the squared error of every CALIBRATED column
+ * against two predictive variances.  Calibrated columns: c = 0 .. obs_dim - 1 (the observation deltas) and c = obs_dim (the
+ * reward), C = obs_dim + 1 in all; a learned-cost column (binary) is left out.
+ *
+ * A row ENTERS the table at h iff (a) alive[b] != 0 on entry to the step -- which is why the calibrate call of a step goes
+ * BEFORE its compare call, the one that clears alive and overwrites cur_obs --, (b) p_next_obs[b], p_rew[b], p_cost[b] are
+ * finite (the compare call's rule), (c) mean[e][b][c] and var[e][b][c] are finite and var[e][b][c] > 0 for every member e and
+ * every c < C, and elite[h][b] lies in [0, ensemble).  Rows with (a) and (b) but not (c) count in n_skipped[h], rows with all
+ * three in n_cal[h]; nothing else of a row that does not enter is summed.
+ *
+ * Per entering row and column, float64 arithmetic on the float32 inputs, every operation rounded separately, members in the
+ * order 0 .. E-1, m = elite[h][b]:
+ *   e      = (double)fl32(p_next_obs[b][c] - next_obs[h][b][c])   (c < obs_dim),   (double)fl32(p_rew[b] - rew[h][b])   (c = obs_dim)
+ *   mu_bar = (sum_e mu_e) / E     v_bar = (sum_e v_e) / E     s2 = (sum_e (mu_e - mu_bar)^2) / E
+ *   v_al   = v_m                  v_tot = v_bar + s2          e_tot = e + (mu_bar - mu_m)
+ *   sums   [h][k][c], k = 0..5:  e^2 / v_al | e_tot^2 / v_tot | log v_al | log v_tot | v_bar | s2
+ *   counts [h][k][c], k = 0..3:  e^2 <= v_al | e^2 <= 4 v_al | e_tot^2 <= v_tot | e_tot^2 <= 4 v_tot
+ *   counts [h][4 C], [h][4 C + 1]:  n_cal | n_skipped
+ * In CMBPO_REPLAY_ONE_STEP every horizon is a one-step prediction; in CMBPO_REPLAY_OPEN_LOOP only h = 0 is: the later rows
+ * show how far the one-step variance falls short of the compounded error, they are no k-step predictive distribution.
+ * Per-workgroup partials (slot = workgroup, every entry written on every call) added in slot order by the finish call: no
+ * floating-point atomics, two runs are bitwise equal.  The prediction, recording, alive, mean and var arrays are those of
+ * the cmbpo_replay_t handed in beside the descriptor; which is not changed by any of this (184 bytes). */
+#define CMBPO_REPLAY_CALIB_SUMS 6
+#define CMBPO_REPLAY_CALIB_COUNTS 4
+
+typedef struct cmbpo_replay_calib {
+  int32_t ensemble, out_dim, reserved;  /* members E; columns of mean / var (>= obs_dim + 1); must be 0 */
+  const int32_t *elite;     /* [H,B] the member each window steps through at h     */
+  double *part_sum;         /* [H][cmbpo_replay_parts(B)][6 (obs + 1)]             */
+  int64_t *part_cnt;        /* [H][cmbpo_replay_parts(B)][4 (obs + 1) + 2]         */
+  double *sums;             /* [H][6 (obs + 1)]                                    */
+  int64_t *counts;          /* [H][4 (obs + 1) + 2]                                */
+} cmbpo_replay_calib_t; /* 56 bytes (4 of padding behind `reserved`) */
+
+/* Every entry: CMBPO_EINVAL with a message naming the entry point for a NULL descriptor, a NULL array it uses, ensemble < 1,
+ * out_dim < obs_dim + 1, reserved != 0, h outside [0, H) and every shape refusal of the compare call -- all before any HIP
+ * call. */
+/* one horizon step of the calibration table, from the arrays the compare call of the same step reads plus rp->mean / rp->var.
+ * Enqueue it BEFORE that step's compare call (see above); it writes nothing but its partial slot. */
+int cmbpo_replay_calibrate(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, int h, void *stream);
+/* partials -> rc->sums / rc->counts, all H horizons */
+int cmbpo_replay_calib_finish(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, void *stream);
+/* The run call with the calibrate call in every step: H x (forward -> post -> calibrate -> compare), then both finish calls,
+ * enqueued without a host wait; bitwise the single calls.  The members are rc->elite; `ensemble` must equal rc->ensemble.  The
+ * plain table, cur_obs and alive are bitwise those of the run call without calibration on the same inputs. */
+int cmbpo_replay_run_calibrated(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, cmbpo_mlp_t *model, int task,
+                                int ensemble, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
