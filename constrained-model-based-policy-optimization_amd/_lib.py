@@ -171,6 +171,25 @@ SIGNATURES.update({
 
 
 
+TERM_ELITE, TERM_ANY, TERM_MAJORITY = 0, 1, 2     # CMBPO_TERM_*: whose vote ends a branch (learned termination head)
+TERM_MEMBERS = {"elite": TERM_ELITE, "any": TERM_ANY, "majority": TERM_MAJORITY}
+
+
+class TermHeadStruct(C.Structure):
+    """ctypes image of ``cmbpo_term_head_t`` (24 bytes): threshold and vote of the learned termination head, and its two
+    optional per-row outputs."""
+    _fields_ = [("threshold", C.c_float), ("members", C.c_int32), ("term_pred", C.c_void_p), ("term_votes", C.c_void_p)]
+
+
+_tp = C.POINTER(TermHeadStruct)
+SIGNATURES.update({
+    "cmbpo_fakeenv_post_term": (_i, [_i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i,
+                                     _p, _p, _p, _p, _p, _p, _p, _p, C.c_float, C.c_float, _p, _p, _tp, _p]),
+    "cmbpo_rollout_term_head_attach": (_i, [_rp, _tp]),
+    "cmbpo_rollout_term_head_detach": (_i, [_rp]),
+})
+
+
 class PiBatchStruct(C.Structure):
     """ctypes image of ``cmbpo_pi_batch_t``."""
     _fields_ = [("n", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32)] + \
@@ -308,6 +327,11 @@ SIGNATURES.update({
     "cmbpo_replay_calibrate": (_i, [_pp, _cpp, _i, _p]),
     "cmbpo_replay_calib_finish": (_i, [_pp, _cpp, _p]),
     "cmbpo_replay_run_calibrated": (_i, [_pp, _cpp, _p, _i, _i, _p]),
+})
+
+# ... with the learned termination head in its post step
+SIGNATURES.update({
+    "cmbpo_replay_run_term": (_i, [_pp, _cpp, _tp, _p, _i, _i, _p, _p]),
 })
 
 _lib = None

@@ -52,6 +52,13 @@ VARIANCE is the size of the real error, per horizon and column (``model/val_z2_*
 transition noise of the imagined rollouts is scaled per observation column by the root of the maximum-likelihood variance
 temperature, clipped to ``m_noise_temperature_range`` (``ModelSampler.set_noise_scale``; ``model/noise_scale_mean``).
 
+``m_learn_term=True`` (the reference has nothing like it) gives the dynamics ensemble one more output column, the
+last one, trained on the real ``done`` flags (``format_samples_for_dyn(append_t=True)``: 1 only where the environment ended a
+path before the sampler's horizon, a time-out is target 0) and has ``FakeEnv`` end an imagined branch where the rule of
+``task`` / ``static_fns`` or that column says so (``predicts_term=True``; ``m_term_threshold``, ``m_term_members`` = 'elite' /
+'any' / 'majority').  With ``m_validate_horizon > 0`` the termination counts of ``model/val_*`` are then the head's, and
+``model/val_term_recall_h1`` / ``val_term_false_alarm_h1`` are added.  ``save`` / ``load`` keep threshold and vote.
+
 ``static_fns`` takes a ``statics.TaskRules``: user-defined termination / cost rules for the imagined rollouts, with
 precedence over ``task`` (which may itself be a name given to ``statics.register_task``).
 """
@@ -83,8 +90,13 @@ def update_dict(dict_a, dict_b, weight_a=.5, weight_b=.5):
     return out
 
 
-def format_samples_for_dyn(samples, append_r=True, append_c=False):
-    """models/pens/pe_factory.py:74-107: inputs = [obs | act], outputs = [next_obs - obs | rew (| cost)]."""
+def format_samples_for_dyn(samples, append_r=True, append_c=False, append_t=False, horizon=None):
+    """models/pens/pe_factory.py:74-107: inputs = [obs | act], outputs = [next_obs - obs | rew (| cost) (| term)].
+
+    ``append_t`` (the learned termination head, no counterpart in the reference) adds the termination target as the LAST
+    column: 1 only where ``samples['terminals']`` is set on a path shorter than the sampler's ``horizon``
+    (``samples['path_lengths']``, ``CPOBuffer.get_archive(['path_lengths', ...])``); a path that ran to the horizon ended by
+    time-out and is target 0, whatever the environment's own time limit reported."""
     obs, act, next_obs = samples['observations'], samples['actions'], samples['next_observations']
     inputs = np.concatenate((obs, act), axis=-1)
     outputs = next_obs - obs
@@ -92,6 +104,12 @@ def format_samples_for_dyn(samples, append_r=True, append_c=False):
         outputs = np.concatenate((outputs, np.squeeze(samples['rewards'])[..., None]), axis=-1)
     if append_c:
         outputs = np.concatenate((outputs, np.squeeze(samples['costs'])[..., None]), axis=-1)
+    if append_t:
+        if horizon is None or 'path_lengths' not in samples:
+            raise ValueError("format_samples_for_dyn(append_t=True) needs horizon= and samples['path_lengths']: a time-out is "
+                             "told from a termination by the path's length")
+        term = np.squeeze(samples['terminals']).astype(bool) & (np.squeeze(samples['path_lengths']) < int(horizon))
+        outputs = np.concatenate((outputs, term.astype(outputs.dtype)[..., None]), axis=-1)
     return inputs, outputs
 
 
@@ -130,6 +148,7 @@ class CMBPO:
                  m_value_disagreement=False, m_v_pessimism=0.0, m_vc_pessimism=0.0,
                  m_validate_horizon=0, m_validate_windows=1024, m_imagined_weight=1.0, m_trust_var=None,
                  m_validate_calibration=False, m_calibrated_noise=False, m_noise_temperature_range=(0.25, 4.0),
+                 m_learn_term=False, m_term_threshold=0.5, m_term_members='elite',
                  **_unused):
         # predictive calibration in the validation replay and, from its one-step row, the scale of the transition
         # noise; refused in words before anything is built
@@ -164,6 +183,14 @@ class CMBPO:
                                 cost_lam=policy.cost_lam)
         self._use_model = use_model
         self._m_learn_cost = bool(m_learn_cost)
+        # learned termination head: refused in words before anything is built
+        self._m_learn_term = bool(m_learn_term) and bool(use_model)
+        if self._m_learn_term:
+            from . import _lib
+            if not np.isfinite(float(m_term_threshold)):
+                raise ValueError("m_term_threshold must be a finite number, got %r" % (m_term_threshold,))
+            if m_term_members not in _lib.TERM_MEMBERS:
+                raise ValueError("m_term_members: 'elite', 'any' or 'majority', got %r" % (m_term_members,))
         if float(m_cost_pessimism) > 0.0 and not self._m_learn_cost:
             raise ValueError("m_cost_pessimism > 0 needs m_learn_cost=True: only a learned cost head has an ensemble spread")
         # critic disagreement: kappa > 0 implies the measurement; only the one-launch critic kernels measure it
@@ -206,8 +233,8 @@ class CMBPO:
         self._start_state_sampling = start_state_sampling
 
         if use_model:
-            # outputs: delta-obs | reward (| cost, with the learned cost head: algorithms/cmbpo.py:121-123)
-            self._model = build_PE(in_dim=self.obs_dim + self.act_dim, out_dim=self.obs_dim + 1 + int(self._m_learn_cost),
+            # outputs: delta-obs | reward (| cost, with the learned cost head: algorithms/cmbpo.py:121-123) (| term, the last)
+            self._model = build_PE(in_dim=self.obs_dim + self.act_dim, out_dim=self.obs_dim + 1 + int(self._m_learn_cost) + int(self._m_learn_term),
                                    name='DynEns', loss=m_loss_type, hidden_dims=m_hidden_dims, lr=m_lr,
                                    num_networks=m_networks, num_elites=m_elites, use_scaler_in=m_use_scaler_in,
                                    use_scaler_out=m_use_scaler_out, decay=1e-6, max_logvar=.5, min_logvar=-10,
@@ -216,7 +243,8 @@ class CMBPO:
             self.fake_env = FakeEnv(true_environment=env, task=rules_task, model=self._model, predicts_delta=True,
                                     predicts_rew=True, predicts_cost=self._m_learn_cost,
                                     disagreement=bool(m_disagreement), rew_pessimism=m_rew_pessimism,
-                                    cost_pessimism=m_cost_pessimism)
+                                    cost_pessimism=m_cost_pessimism, predicts_term=self._m_learn_term,
+                                    term_threshold=m_term_threshold, term_members=m_term_members)
             self.rollout_mode = rollout_mode
             self.model_buf = ModelBuffer(batch_size=self._rollout_batch_size, obs_dim=self.obs_dim, act_dim=self.act_dim,
                                          max_path_length=maxroll, device=self.device, iv_gae=bool(m_iv_gae),
@@ -283,9 +311,10 @@ class CMBPO:
 
     def train_model(self, min_epochs=5, max_epochs=100, batch_size=2048):
         """algorithms/cmbpo.py:455-486"""
-        model_samples = self._buffer.get_archive(['observations', 'actions', 'next_observations', 'rewards', 'costs',
-                                                  'terminals', 'epochs'])
-        dyn_ins, dyn_outs = format_samples_for_dyn(model_samples, append_r=True, append_c=self._m_learn_cost)
+        fields = ['observations', 'actions', 'next_observations', 'rewards', 'costs', 'terminals', 'epochs']
+        model_samples = self._buffer.get_archive(fields + (['path_lengths'] if self._m_learn_term else []))
+        dyn_ins, dyn_outs = format_samples_for_dyn(model_samples, append_r=True, append_c=self._m_learn_cost,
+                                                   append_t=self._m_learn_term, horizon=self.sampler.max_path_length)
         return self._model.train(dyn_ins, dyn_outs, batch_size=batch_size, max_epochs=max_epochs,
                                  min_epoch_before_break=min_epochs, holdout_ratio=0.2, max_t=self._max_model_t,
                                  shuffle_on_device=self._shuffle_on_device)
@@ -325,6 +354,11 @@ class CMBPO:
                     self.model_sampler.set_noise_scale(np.sqrt(temperature(cal, 'al', 0, *self._noise_temperature_range)))
                 scale = self.model_sampler.noise_scale
                 extra['noise_scale_mean'] = 1.0 if scale is None else float(np.mean(scale))
+        if self._m_learn_term:
+            # the head at h = 1, the one-step row: the share of real terminations it reports, of continuing steps it ends
+            t1 = tab['term_cm'][0]
+            extra.update({'val_term_recall_h1': ratio(t1[1, 1], t1[1, 0] + t1[1, 1]),
+                          'val_term_false_alarm_h1': ratio(t1[0, 1], t1[0, 0] + t1[0, 1])})
         return {**extra,
                 'val_n_h1': int(tab['n'][0]), 'val_n_hH': int(tab['n'][last]),
                 'val_mse_obs_h1': float(np.mean(tab['mse_obs'][0])), 'val_mse_obs_hH': float(np.mean(tab['mse_obs'][last])),
@@ -513,3 +547,20 @@ class CMBPO:
     def save(self, savedir):
         if self._use_model:
             self._model.save(savedir, self._epoch)
+            if self._m_learn_term:      # threshold and vote of the termination head, beside the model's files
+                import json
+                import os
+                with open(os.path.join(savedir, 'term_head_%d.json' % self._epoch), 'w') as fh:
+                    json.dump({'threshold': self.fake_env.term_threshold, 'members': self.fake_env.term_members}, fh)
+
+    def load(self, savedir, timestep):
+        """The model ``save`` wrote at epoch ``timestep`` and, with the termination head, its threshold and vote."""
+        if not self._use_model:
+            raise ValueError("load: the trainer was built with use_model=False, there is no model to load")
+        self._model.load(savedir, timestep)
+        if self._m_learn_term:
+            import json
+            import os
+            with open(os.path.join(savedir, 'term_head_%d.json' % int(timestep))) as fh:
+                head = json.load(fh)
+            self.fake_env.set_term_head(head['threshold'], head['members'])

@@ -213,7 +213,8 @@ class CPOBuffer:
 
     def _take(self, idx, fields):
         names, want_pi = self._fields(fields)
-        out = {k: self.arch_dict[k][idx] for k in names}
+        # ('path_lengths': derived from the path ends, not stored)
+        out = {k: (self.path_lengths() if k == 'path_lengths' else self.arch_dict[k])[idx] for k in names}
         if want_pi:
             out.update({k: self.pi_info_archive[k][idx] for k in self.sorted_pi_info_keys})
         return out
@@ -263,6 +264,30 @@ class CPOBuffer:
         if self.archive_full and 0 < self.archive_ptr <= N:
             cont[self.archive_ptr - 1] = False
         return cont
+
+    def path_lengths(self):
+        """int32 [archive_size]: the number of steps of the real path every archived step belongs to (0 in unfilled slots),
+        from the path ends of ``path_continues``.  Once the archive has wrapped, the oldest path -- the one behind
+        ``archive_ptr`` -- may have lost its first steps to newer samples: its length is not known and reported as the
+        largest int32, so that no test ``length < horizon`` holds for it."""
+        N = self.arch_size
+        out = np.zeros(self.archive_size, np.int32)
+        if N == 0:
+            return out
+        ends = np.flatnonzero(~self.path_continues())            # the last step of every path (slot N - 1 is always one)
+        starts = np.concatenate(([0], ends[:-1] + 1))
+        out[:N] = np.repeat((ends - starts + 1).astype(np.int32), ends - starts + 1)
+        if self.archive_full and 0 < self.archive_ptr < N:
+            k = np.searchsorted(ends, self.archive_ptr)           # the path that starts behind the newest sample
+            out[starts[k]:ends[k] + 1] = np.iinfo(np.int32).max
+        return out
+
+    def term_targets(self, horizon):
+        """float32 [archive_size]: the training target of a learned termination head -- 1 only where the
+        environment reported ``done`` on a path shorter than the sampler's ``horizon``.  A path that ran to the horizon ended
+        by time-out, which is no property of the state: target 0, even when the environment's own time limit set ``done`` on
+        that step.  ``terminals`` itself is not changed."""
+        return (self.arch_dict["terminals"] & (self.path_lengths() < int(horizon))).astype(np.float32)
 
     def windows(self, horizon, n, epochs=None, rng=None):
         """``n`` windows of up to ``horizon`` consecutive archived steps, for ``FakeEnv.replay``.  Start indices are drawn

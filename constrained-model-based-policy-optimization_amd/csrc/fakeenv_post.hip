@@ -62,6 +62,17 @@ struct PostArgsDis : PostArgsBase<RULES, NOISE> {
 };
 template <bool RULES, bool NOISE, bool DIS = false>
 using PostArgsT = std::conditional_t<DIS, PostArgsDis<RULES, NOISE>, PostArgsBase<RULES, NOISE>>;
+// TERM: the learned termination head (include/cmbpo_hip.h, cmbpo_term_head_t) -- the model's LAST column, out_dim - 1, read by
+// the row's eight lanes in the tail; once more fields that exist only in the argument types of instances of their own
+template <bool RULES, bool NOISE, bool DIS>
+struct PostArgsTerm : PostArgsT<RULES, NOISE, DIS> {
+  float threshold;                // finite
+  int members;                    // CMBPO_TERM_ELITE / _ANY / _MAJORITY
+  float *term_pred;               // [.] slot indexed like term, or NULL
+  uint8_t *term_votes;            // [.] or NULL
+};
+template <bool RULES, bool NOISE, bool DIS = false, bool TERM = false>
+using PostArgsX = std::conditional_t<TERM, PostArgsTerm<RULES, NOISE, DIS>, PostArgsT<RULES, NOISE, DIS>>;
 
 // np.clip(x, lo, hi): comparisons are false for a NaN, which therefore passes through (fminf / fmaxf would drop it)
 __device__ __forceinline__ float clip_np(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
@@ -69,8 +80,8 @@ __device__ __forceinline__ float clip_np(float x, float lo, float hi) { return x
 // EC: the ensemble size at compile time (0: read it at run time) -- with a run-time size the member loops are unrolled to
 // kEMax and masked: 56 pair terms computed and selected for the 42 that exist, a third more instructions
 #define POST_WAVES 5      // waves per SIMD the register allocation aims at (swept 4 / 5 / 6 / 8: 57.7 / 51.1 / 51.3 / 77.4 us at 100 k rows)
-template <int EC, bool RULES = false, bool NOISE = false, bool DIS = false>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgsT<RULES, NOISE, DIS> p) {
+template <int EC, bool RULES = false, bool NOISE = false, bool DIS = false, bool TERM = false>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgsX<RULES, NOISE, DIS, TERM> p) {
   extern __shared__ float sm[];
   const int D = p.obs_dim;
   float *s_dkl = sm;                  // [kRows][D]
@@ -263,6 +274,17 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
         }
       }
     }
+    // TERM: lane k of the row owns member k's value of the termination column (the model's last), requested here like the DIS
+    // loads; rows past the end and lanes past E load nothing
+    [[maybe_unused]] float xt = 0.0f;
+    [[maybe_unused]] int me_t = 0;
+    if constexpr (TERM) {
+      if (r >= 0) {
+        if constexpr (DIS) me_t = me_k;
+        else me_t = p.elite[r];
+        if (k < E) xt = p.mean[k * mstride + (size_t)r * p.out_dim + (p.out_dim - 1)];
+      }
+    }
     auto row_sum = [&](const float *a) {
       float res;
       if (D < 8) {
@@ -340,6 +362,15 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
       rew_var = member_var(xr, &rew_me);
       if (p.learned_cost) cost_var = member_var(xc, &cost_me);     // (uniform over the launch; a static cost rule has no spread: +0)
     }
+    // TERM: hit_e = x_e > threshold, written positively (a NaN never hits); one ballot gives the row's member mask in the row's
+    // byte -- the elite's bit is me & 7, the votes are a popcount.  All 64 lanes are still here.  The elite's own value goes out
+    // from the lane that loaded it.
+    [[maybe_unused]] unsigned term_mask = 0u;
+    if constexpr (TERM) {
+      const bool hit = r >= 0 && k < E && xt > p.threshold;
+      term_mask = (unsigned)(__ballot(hit) >> (8 * rw)) & 0xffu;
+      if (p.term_pred != nullptr && r >= 0 && k == (me_t & 7)) p.term_pred[r] = xt;
+    }
     if (r < 0 || k != 0) return;
     p.dkl_path[r] = sd / (float)D;      // fake_env.py:113
     p.ep_var_mean[r] = sv / (float)D;   // model_sampler.py:322
@@ -384,17 +415,25 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
     } else {
       if (p.learned_cost) cost = p.mean[me * mstride + (size_t)r * p.out_dim + D + 1];
     }
+    // TERM: term = rule_done || learned_done; the cost above has used the rule's own done.  `members` is uniform over the launch.
+    if constexpr (TERM) {
+      const int votes = __popc(term_mask);
+      const bool learned = p.members == CMBPO_TERM_ELITE ? ((term_mask >> (me_t & 7)) & 1u) != 0u
+                           : p.members == CMBPO_TERM_ANY ? votes > 0 : 2 * votes > E;
+      if (learned) done = 1;
+      if (p.term_votes != nullptr) p.term_votes[r] = (uint8_t)votes;
+    }
     p.term[r] = done;
     p.cost[r] = cost;
   }
 }
 
-// one launch of the instance for (ensemble size, RULES, NOISE, DIS)
-template <bool RULES, bool NOISE, bool DIS = false>
-void launch_post(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsT<RULES, NOISE, DIS> &a) {
-  if (ensemble == 7) hipLaunchKernelGGL((fakeenv_post_kernel<7, RULES, NOISE, DIS>), grid, dim3(kThreads), lds, stream, a);   // the shipped configs
-  else if (ensemble == 5) hipLaunchKernelGGL((fakeenv_post_kernel<5, RULES, NOISE, DIS>), grid, dim3(kThreads), lds, stream, a);
-  else hipLaunchKernelGGL((fakeenv_post_kernel<0, RULES, NOISE, DIS>), grid, dim3(kThreads), lds, stream, a);
+// one launch of the instance for (ensemble size, RULES, NOISE, DIS, TERM)
+template <bool RULES, bool NOISE, bool DIS = false, bool TERM = false>
+void launch_post(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsX<RULES, NOISE, DIS, TERM> &a) {
+  if (ensemble == 7) hipLaunchKernelGGL((fakeenv_post_kernel<7, RULES, NOISE, DIS, TERM>), grid, dim3(kThreads), lds, stream, a);   // the shipped configs
+  else if (ensemble == 5) hipLaunchKernelGGL((fakeenv_post_kernel<5, RULES, NOISE, DIS, TERM>), grid, dim3(kThreads), lds, stream, a);
+  else hipLaunchKernelGGL((fakeenv_post_kernel<0, RULES, NOISE, DIS, TERM>), grid, dim3(kThreads), lds, stream, a);
 }
 
 // what cmbpo_fakeenv_post_disagreement adds to the arguments (NULL: the instances without the feature)
@@ -402,19 +441,32 @@ struct DisExtra {
   float kappa_rew, kappa_cost;
   float *rew_var, *cost_var;
 };
+// ... and cmbpo_fakeenv_post_term (th == NULL: the instances without the head, with the argument block they always had)
+template <bool RULES, bool NOISE, bool DIS>
+void launch_post_term(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsT<RULES, NOISE, DIS> &a,
+                      const cmbpo_term_head_t *th) {
+  if (th == nullptr) return launch_post<RULES, NOISE, DIS>(ensemble, grid, lds, stream, a);
+  PostArgsTerm<RULES, NOISE, DIS> at{};
+  static_cast<PostArgsT<RULES, NOISE, DIS> &>(at) = a;
+  at.threshold = th->threshold; at.members = th->members; at.term_pred = th->term_pred; at.term_votes = th->term_votes;
+  launch_post<RULES, NOISE, DIS, true>(ensemble, grid, lds, stream, at);
+}
 template <bool RULES, bool NOISE>
-void launch_post_dis(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsBase<RULES, NOISE> &a, const DisExtra &dis) {
+void launch_post_ext(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsBase<RULES, NOISE> &a, const DisExtra *dis,
+                     const cmbpo_term_head_t *th) {
+  if (dis == nullptr) return launch_post_term<RULES, NOISE, false>(ensemble, grid, lds, stream, a, th);
   PostArgsDis<RULES, NOISE> ad{};
   static_cast<PostArgsBase<RULES, NOISE> &>(ad) = a;
-  ad.kappa_rew = dis.kappa_rew; ad.kappa_cost = dis.kappa_cost; ad.rew_var = dis.rew_var; ad.cost_var = dis.cost_var;
-  launch_post<RULES, NOISE, true>(ensemble, grid, lds, stream, ad);
+  ad.kappa_rew = dis->kappa_rew; ad.kappa_cost = dis->kappa_cost; ad.rew_var = dis->rew_var; ad.cost_var = dis->cost_var;
+  launch_post_term<RULES, NOISE, true>(ensemble, grid, lds, stream, ad, th);
 }
 
-// all three entry points; `who` prefixes the messages, d_xi == NULL: the deterministic instances
+// all four entry points; `who` prefixes the messages, d_xi == NULL: the deterministic instances
 int post_impl(const char *who, int task, int ensemble, int obs_dim, int act_dim, const float *d_mean, const float *d_var, int ld_rows,
               const float *d_obs, const float *d_act, const int32_t *d_elite, const int32_t *d_row_idx, const int32_t *d_n_rows,
               int n_rows, float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost, float *d_dkl_path, float *d_ep_var_mean,
-              float *d_ep_var, const float *d_xi, void *stream, const DisExtra *dis = nullptr) {
+              float *d_ep_var, const float *d_xi, void *stream, const DisExtra *dis = nullptr,
+              const cmbpo_term_head_t *th = nullptr) {
   const int learned_cost = (task & CMBPO_TASK_LEARNED_COST) ? 1 : 0;     // every other bit outside the rule id is an error
   const int task_arg = task;
   task &= ~CMBPO_TASK_LEARNED_COST;
@@ -424,6 +476,12 @@ int post_impl(const char *who, int task, int ensemble, int obs_dim, int act_dim,
   CMBPO_REQUIRE(obs_dim >= 1 && obs_dim <= 512 && act_dim >= 0, "%s: bad dims", who);
   if (task == CMBPO_TASK_ANTSAFE)
     CMBPO_REQUIRE(obs_dim >= 5, "%s: AntSafe rules need obs_dim >= 5", who);
+  if (th != nullptr) {
+    // (isfinite is false for a NaN; kEMax is what the row's eight lanes hold -- checked above, named again for the head)
+    CMBPO_REQUIRE(isfinite(th->threshold), "%s: termination head: threshold %g is not a finite number", who, (double)th->threshold);
+    CMBPO_REQUIRE(th->members >= CMBPO_TERM_ELITE && th->members <= CMBPO_TERM_MAJORITY,
+                  "%s: termination head: members %d not in 0..2 (CMBPO_TERM_ELITE / _ANY / _MAJORITY)", who, th->members);
+  }
   PostArgsRules ar{};
   if (user)     // (registered? columns inside obs_dim / act_dim? -- host code, before any HIP call)
     if (int rc = cmbpo_internal_task_rules_resolve(who, task_arg, obs_dim, act_dim, d_act != nullptr, &ar.rules)) return rc;
@@ -443,7 +501,7 @@ int post_impl(const char *who, int task, int ensemble, int obs_dim, int act_dim,
   if (n_rows == 0) return CMBPO_OK;
   PostArgs a{};
   a.task = task; a.ensemble = ensemble; a.obs_dim = obs_dim; a.act_dim = act_dim;
-  a.out_dim = obs_dim + 1 + learned_cost;  // delta-obs + reward (+ cost: algorithms/cmbpo.py:121-123, m_learn_cost)
+  a.out_dim = obs_dim + 1 + learned_cost + (th ? 1 : 0);  // delta-obs + reward (+ cost: algorithms/cmbpo.py:121-123, m_learn_cost) (+ the termination head's column)
   a.learned_cost = learned_cost;
   a.mean = d_mean; a.var = d_var; a.ld_rows = ld_rows; a.obs = d_obs; a.act = d_act;
   a.elite = d_elite; a.row_idx = d_row_idx; a.n_rows_dev = d_n_rows; a.n_rows = n_rows;
@@ -458,20 +516,15 @@ int post_impl(const char *who, int task, int ensemble, int obs_dim, int act_dim,
       PostArgsRulesNoise an{};
       static_cast<PostArgsRules &>(an) = ar;
       an.xi = d_xi;
-      if (dis) launch_post_dis<true, true>(ensemble, grid, lds, s, an, *dis);
-      else launch_post<true, true>(ensemble, grid, lds, s, an);
+      launch_post_ext<true, true>(ensemble, grid, lds, s, an, dis, th);
     } else {
       PostArgsNoise an{};
       static_cast<PostArgs &>(an) = a;
       an.xi = d_xi;
-      if (dis) launch_post_dis<false, true>(ensemble, grid, lds, s, an, *dis);
-      else launch_post<false, true>(ensemble, grid, lds, s, an);
+      launch_post_ext<false, true>(ensemble, grid, lds, s, an, dis, th);
     }
-  } else if (dis) {
-    if (user) launch_post_dis<true, false>(ensemble, grid, lds, s, ar, *dis);
-    else launch_post_dis<false, false>(ensemble, grid, lds, s, a, *dis);
-  } else if (user) launch_post<true, false>(ensemble, grid, lds, s, ar);
-  else launch_post<false, false>(ensemble, grid, lds, s, a);
+  } else if (user) launch_post_ext<true, false>(ensemble, grid, lds, s, ar, dis, th);
+  else launch_post_ext<false, false>(ensemble, grid, lds, s, a, dis, th);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -518,4 +571,29 @@ extern "C" int cmbpo_fakeenv_post_disagreement(int task, int ensemble, int obs_d
   return post_impl("cmbpo_fakeenv_post_disagreement", task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite,
                    d_row_idx, d_n_rows, n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, d_xi, stream,
                    &dis);
+}
+
+// ... with the learned termination head (see the kernel's TERM parts and the header); th == NULL: the entry points above
+extern "C" int cmbpo_fakeenv_post_term(int task, int ensemble, int obs_dim, int act_dim,
+                                       const float *d_mean, const float *d_var, int ld_rows,
+                                       const float *d_obs, const float *d_act, const int32_t *d_elite,
+                                       const int32_t *d_row_idx, const int32_t *d_n_rows, int n_rows,
+                                       float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost,
+                                       float *d_dkl_path, float *d_ep_var_mean, float *d_ep_var,
+                                       const float *d_xi, float kappa_rew, float kappa_cost,
+                                       float *d_rew_var, float *d_cost_var, const cmbpo_term_head_t *th, void *stream) {
+  // (kappa != 0 is true for a NaN: the disagreement path's own check names it)
+  const bool with_dis = d_rew_var != nullptr || d_cost_var != nullptr || kappa_rew != 0.0f || kappa_cost != 0.0f;
+  if (th == nullptr) {
+    if (with_dis)
+      return cmbpo_fakeenv_post_disagreement(task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite, d_row_idx,
+                                             d_n_rows, n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var,
+                                             d_xi, kappa_rew, kappa_cost, d_rew_var, d_cost_var, stream);
+    return cmbpo_fakeenv_post_noise(task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite, d_row_idx, d_n_rows,
+                                    n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, d_xi, stream);
+  }
+  const DisExtra dis{kappa_rew, kappa_cost, d_rew_var, d_cost_var};
+  return post_impl("cmbpo_fakeenv_post_term", task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite, d_row_idx,
+                   d_n_rows, n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, d_xi, stream,
+                   with_dis ? &dis : nullptr, th);
 }

@@ -1313,7 +1313,17 @@ void side_set(const cmbpo_rollout_t *r, F RolloutSide::*which, const F *feature)
   if (feature == nullptr && g_side.find(r->iscal) == g_side.end()) return;
   RolloutSide &sd = g_side[r->iscal];
   sd.*which = feature ? *feature : F{};
-  if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr && sd.vd.part == nullptr) g_side.erase(r->iscal);
+  if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr && sd.vd.part == nullptr && !sd.th_on) g_side.erase(r->iscal);
+}
+
+// the termination head: no kernel of this file reads it (the one-call step hands it to the post kernel)
+void side_set_term(const cmbpo_rollout_t *r, const cmbpo_term_head_t *th) {
+  std::lock_guard<std::mutex> lock(g_side_mu);
+  if (th == nullptr && g_side.find(r->iscal) == g_side.end()) return;
+  RolloutSide &sd = g_side[r->iscal];
+  sd.th = th ? *th : cmbpo_term_head_t{};
+  sd.th_on = th ? 1 : 0;
+  if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr && sd.vd.part == nullptr && !sd.th_on) g_side.erase(r->iscal);
 }
 
 }  // namespace
@@ -1363,6 +1373,23 @@ extern "C" int cmbpo_rollout_value_disagreement_attach(const cmbpo_rollout_t *r,
 extern "C" int cmbpo_rollout_value_disagreement_detach(const cmbpo_rollout_t *r) {
   CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_value_disagreement_detach: NULL rollout struct / iscal");
   side_set<cmbpo_value_disagreement_t>(r, &RolloutSide::vd, nullptr);
+  return CMBPO_OK;
+}
+
+extern "C" int cmbpo_rollout_term_head_attach(const cmbpo_rollout_t *r, const cmbpo_term_head_t *th) {
+  CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_term_head_attach: NULL rollout struct / iscal");
+  CMBPO_REQUIRE(th != nullptr, "cmbpo_rollout_term_head_attach: NULL cmbpo_term_head_t (cmbpo_rollout_term_head_detach switches the feature off)");
+  CMBPO_REQUIRE(isfinite(th->threshold), "cmbpo_rollout_term_head_attach: termination head: threshold %g is not a finite number",
+                (double)th->threshold);
+  CMBPO_REQUIRE(th->members >= CMBPO_TERM_ELITE && th->members <= CMBPO_TERM_MAJORITY,
+                "cmbpo_rollout_term_head_attach: termination head: members %d not in 0..2 (CMBPO_TERM_ELITE / _ANY / _MAJORITY)", th->members);
+  side_set_term(r, th);
+  return CMBPO_OK;
+}
+
+extern "C" int cmbpo_rollout_term_head_detach(const cmbpo_rollout_t *r) {
+  CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_term_head_detach: NULL rollout struct / iscal");
+  side_set_term(r, nullptr);
   return CMBPO_OK;
 }
 

@@ -31,7 +31,14 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
                      const Ahead &ahead, const float *d_xi, void *stream) {
   CMBPO_REQUIRE(r && policy && model && v && vc && d_eps && d_elite && d_mean && d_var, "cmbpo_rollout_step: NULL argument");
   CMBPO_REQUIRE(n_alive >= 1 && n_alive <= r->B, "cmbpo_rollout_step: n_alive %d not in [1, B=%d]", n_alive, r->B);
+  // what is attached beside *r, looked up once for every launch of the step
+  const RolloutSide sd = cmbpo_internal_side_lookup(r);
   // the scratch rows are as wide as the model's output: a learned-cost flag that does not match the model would read the wrong columns
+  if (sd.th_on)
+    CMBPO_REQUIRE(model->out_dim == r->obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0) + 1,
+                  "cmbpo_rollout_step: a termination head (cmbpo_term_head_t) is attached: model out_dim %d does not match obs_dim %d + 1 "
+                  "(+ 1 with CMBPO_TASK_LEARNED_COST) + 1 for the head's column, task 0x%x", model->out_dim, r->obs_dim, task);
+  else
   CMBPO_REQUIRE(model->out_dim == r->obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0),
                 "cmbpo_rollout_step: model out_dim %d does not match obs_dim %d + 1 (+ 1 with CMBPO_TASK_LEARNED_COST), task 0x%x",
                 model->out_dim, r->obs_dim, task);
@@ -42,8 +49,6 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   auto w = [](const float *p) { return const_cast<float *>(p); };
   int rc;
   *next_ready = false;
-  // what is attached beside *r, looked up once for every launch of the step
-  const RolloutSide sd = cmbpo_internal_side_lookup(r);
   // critic disagreement: only the one-launch critics measure it -- refused before the first launch of the step
   CMBPO_REQUIRE(sd.vd.part == nullptr || cmbpo_critic_pair_supported(v, vc),
                 "cmbpo_rollout_step: a cmbpo_value_disagreement_t is attached, which needs critics cmbpo_critic_pair_supported takes "
@@ -60,6 +65,16 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
                               d_mean, d_var, stream)))
     return rc;
   const cmbpo_disagreement_t &dg = sd.dg;
+  // the termination head: its instances of the post kernel, with or without the disagreement and the draws
+  if (sd.th_on) {
+    const bool dis = dg.part != nullptr;
+    if ((rc = cmbpo_fakeenv_post_term(task, ensemble, r->obs_dim, r->act_dim, d_mean, d_var, r->B, r->cur_obs, r->act_t, d_elite,
+                                      r->alive_idx, d_n, n_alive, w(r->next_obs), w(r->rew_t), const_cast<uint8_t *>(r->term_t),
+                                      w(r->cost_t), w(r->dkl_t), w(r->epv_t), nullptr, d_xi, dis ? dg.kappa_rew : 0.0f,
+                                      dis ? dg.kappa_cost : 0.0f, dis ? dg.rew_var_t : nullptr, dis ? dg.cost_var_t : nullptr, &sd.th,
+                                      stream)))
+      return rc;
+  } else
   // ensemble disagreement: its instance of the post kernel, penalised rew_t / cost_t (d_xi may be NULL)
   if (dg.part != nullptr) {
     if ((rc = cmbpo_fakeenv_post_disagreement(task, ensemble, r->obs_dim, r->act_dim, d_mean, d_var, r->B, r->cur_obs, r->act_t, d_elite,

@@ -28,12 +28,21 @@ prediction, not thresholded.
 ``cost_pessimism > 0`` needs ``predicts_cost``: a static cost rule has no member spread.  Off (the default) the calls made
 and the keys returned are what they were.
 
+``predicts_term=True`` (no counterpart in the reference, ``m_learn_term`` of the trainer): the model has one more
+output column, the LAST one, trained on the real ``done`` flags, and a branch also ends where that column says so:
+``term = rule_done or learned_done`` with ``learned_done`` the elite member's ``x > term_threshold`` (``term_members='elite'``),
+any member's (``'any'``) or more than half of all members' (``'majority'``).  The cost keeps the rule's own ``done``.  ``step()``
+adds ``info['term_pred']`` (the elite's value of the column) and ``info['term_votes']`` (members above the threshold, uint8);
+``set_term_head(threshold, members)`` changes the head later.  Off (the default) nothing changes.
+
 ``replay(...)`` has no counterpart in the reference: it replays windows of real steps through the model with the recorded
 actions and returns, per horizon, how far the predictions are from the recording (open-loop model validation).
 
 ``task`` is a built-in task name, a name given to ``statics.register_task``, or a ``statics.TaskRules`` (user-defined
 termination / cost rules, evaluated by the same kernel); any other name is the default task, as in the reference.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -42,7 +51,8 @@ from . import _lib, statics
 
 class FakeEnv:
     def __init__(self, true_environment, task, model, predicts_delta, predicts_rew, predicts_cost,
-                 seed=0, disagreement=False, rew_pessimism=0.0, cost_pessimism=0.0):
+                 seed=0, disagreement=False, rew_pessimism=0.0, cost_pessimism=0.0,
+                 predicts_term=False, term_threshold=0.5, term_members='elite'):
         self.env = true_environment
         self.obs_dim = int(np.prod(self.observation_space.shape))
         self.act_dim = int(np.prod(self.action_space.shape))
@@ -58,7 +68,8 @@ class FakeEnv:
         self.input_dim = model.in_dim
         self.output_dim = model.out_dim
         assert self.input_dim == self.obs_dim + self.act_dim
-        assert self.output_dim == self.obs_dim + 1 + int(self._predicts_cost)
+        self._predicts_term = bool(predicts_term)
+        assert self.output_dim == self.obs_dim + 1 + int(self._predicts_cost) + int(self._predicts_term)
         # the `task` argument of the native entry points: the rule id, with the learned-cost flag where the model has the head
         # (every caller that passes it -- this class, ModelSampler, the probes -- thereby runs the mode the scratch is sized for)
         self._task_id, self._rules = statics.lookup(task)
@@ -74,6 +85,9 @@ class FakeEnv:
         self._disagreement = bool(disagreement)
         self.rew_pessimism = self.cost_pessimism = 0.0
         self.set_pessimism(rew_pessimism, cost_pessimism)
+        self.term_threshold, self.term_members = 0.5, 'elite'
+        if self._predicts_term:
+            self.set_term_head(term_threshold, term_members)
         self.device = model.device
         # bench.py sets this to a list to collect (start, end) HIP events around the dominant kernel
         self.kernel_events = None
@@ -100,6 +114,30 @@ class FakeEnv:
             raise ValueError("cost_pessimism > 0 needs predicts_cost=True: a static cost rule has no ensemble spread")
         self.rew_pessimism, self.cost_pessimism = rew, cost
 
+    @property
+    def predicts_term(self):
+        return self._predicts_term
+
+    def set_term_head(self, threshold, members):
+        """Threshold and vote ('elite' / 'any' / 'majority') of the learned termination head."""
+        if not self._predicts_term:
+            raise ValueError("set_term_head needs predicts_term=True: the model has no termination column")
+        threshold = float(threshold)
+        if not np.isfinite(threshold):
+            raise ValueError(f"term_threshold must be a finite number, got {threshold}")
+        if members not in _lib.TERM_MEMBERS:
+            raise ValueError(f"term_members: 'elite', 'any' or 'majority', got {members!r}")
+        self.term_threshold, self.term_members = threshold, members
+
+    def term_head_struct(self, term_pred=None, term_votes=None):
+        """The ``cmbpo_term_head_t`` of this head (None without one); the two optional outputs are device tensors or None."""
+        if not self._predicts_term:
+            return None
+        th = _lib.TermHeadStruct()
+        th.threshold, th.members = self.term_threshold, _lib.TERM_MEMBERS[self.term_members]
+        th.term_pred, th.term_votes = _lib.ptr(term_pred), _lib.ptr(term_votes)
+        return th
+
     def random_inds(self, size):
         """One elite per branch (models/fake_env.py:174-178), from this object's seeded generator."""
         elites = np.asarray(self._model.elite_inds, dtype=np.int32)
@@ -111,7 +149,8 @@ class FakeEnv:
 
         out: dict with next_obs[B,obs], rew[B], term[B] u8, cost[B], dkl_path[B], ep_var_mean[B]
         (and optionally ep_var[B,obs]).  scratch: (mean, var)[E,B,output_dim].  With `disagreement` on, out also needs
-        rew_var[B] and cost_var[B]; they are filled, and rew / cost are the penalised values.
+        rew_var[B] and cost_var[B]; they are filled, and rew / cost are the penalised values.  With `predicts_term`, term is
+        rule_done or learned_done, and out's optional term_pred[B] / term_votes[B] u8 are filled.
         """
         B = obs.shape[0]
         if noise is not None and not (noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
@@ -143,7 +182,14 @@ class FakeEnv:
                 _lib.ptr(out["term"]), _lib.ptr(out["cost"]),
                 _lib.ptr(out["dkl_path"]), _lib.ptr(out["ep_var_mean"]),
                 _lib.ptr(out.get("ep_var")))
-        if self.disagreement:
+        if self._predicts_term:
+            dis = self.disagreement
+            th = self.term_head_struct(out.get("term_pred"), out.get("term_votes"))
+            _lib.check(lib.cmbpo_fakeenv_post_term(*post, _lib.ptr(noise), self.rew_pessimism if dis else 0.0,
+                                                   self.cost_pessimism if dis else 0.0, _lib.ptr(out["rew_var"]) if dis else None,
+                                                   _lib.ptr(out["cost_var"]) if dis else None, C.byref(th), stream),
+                       "cmbpo_fakeenv_post_term")
+        elif self.disagreement:
             _lib.check(lib.cmbpo_fakeenv_post_disagreement(*post, _lib.ptr(noise), self.rew_pessimism, self.cost_pessimism,
                                                            _lib.ptr(out["rew_var"]), _lib.ptr(out["cost_var"]), stream),
                        "cmbpo_fakeenv_post_disagreement")
@@ -191,6 +237,8 @@ class FakeEnv:
                        ep_var_mean=torch.empty(n, **f), ep_var=torch.empty((n, self.obs_dim), **f))
             if self.disagreement:
                 out.update(rew_var=torch.empty(n, **f), cost_var=torch.empty(n, **f))
+            if self._predicts_term:
+                out.update(term_pred=torch.empty(n, **f), term_votes=torch.empty(n, dtype=torch.uint8, device=self.device))
             self.step_device(o, a, inds, out, noise=xi)
         next_obs, r, terms = out["next_obs"], out["rew"][:, None], out["term"].bool()[:, None]
         c = out["cost"][:, None]
@@ -211,6 +259,11 @@ class FakeEnv:
             if was_np:
                 rv, cv = rv.cpu().numpy(), cv.cpu().numpy()
             info["ensemble_rew_var"], info["ensemble_cost_var"] = rv, cv
+        if self._predicts_term:
+            tp, tv = out["term_pred"], out["term_votes"]
+            if was_np:
+                tp, tv = tp.cpu().numpy(), tv.cpu().numpy()
+            info["term_pred"], info["term_votes"] = tp, tv
         return next_obs, r, terms, info
 
     def replay(self, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, model_inds=None, mode='open_loop',
@@ -231,7 +284,9 @@ class FakeEnv:
         [H, B] array.
 
         A replay always measures the UNPENALISED means: it runs ``cmbpo_ens_forward`` and the plain ``cmbpo_fakeenv_post``,
-        never the noise or disagreement entries, whatever ``disagreement`` / ``rew_pessimism`` / ``cost_pessimism`` are.
+        never the noise or disagreement entries, whatever ``disagreement`` / ``rew_pessimism`` / ``cost_pessimism`` are.  With
+        ``predicts_term`` the post step carries the head (``cmbpo_replay_run_term``): the predicted terminations, ``term_cm``
+        among them, are ``rule_done or learned_done``.
 
         Returns a dict of NumPy arrays, one row per horizon h = 0..H-1: ``n`` (windows compared), ``n_nonfinite``,
         ``mse_obs`` [H, obs], ``mse_rew``, ``mse_cost``, ``cost_cm`` / ``term_cm`` [H, 2, 2] indexed [real, predicted] (a
@@ -264,12 +319,13 @@ class FakeEnv:
             if inds.shape != (H, B) or inds.min() < 0 or inds.max() >= E:
                 raise ValueError("replay: model_inds must be an int or an [%d, %d] array of members in 0..%d" % (H, B, E - 1))
             elite = torch.from_numpy(np.ascontiguousarray(inds, dtype=np.int32)).to(self.device)
+            th = self.term_head_struct()
             if calibration:
-                rb.run_calibrated(self._model.mlp.handle, self._task_id, E, elite)
+                rb.run_calibrated(self._model.mlp.handle, self._task_id, E, elite, term_head=th)
                 tab = rb.table()
                 tab['calibration'] = rb.calibration_table()
                 return tab
-            rb.run(self._model.mlp.handle, self._task_id, E, elite)
+            rb.run(self._model.mlp.handle, self._task_id, E, elite, term_head=th)
             return rb.table()
 
     def close(self):

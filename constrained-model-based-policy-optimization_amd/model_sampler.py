@@ -23,6 +23,10 @@ the sampler's generator, ``cmbpo_fakeenv_post_noise``); off, the draws and the r
 rew_pessimism=..., cost_pessimism=...)``) and hands them to the pool: every step then measures the ensemble's disagreement on
 reward and cost, stores the penalised values and adds the variances of the stored rows to two more accumulators.
 
+``reset()`` likewise takes the learned termination head of its ``env`` (``FakeEnv(predicts_term=True, term_threshold=...,
+term_members=...)``): every step then ends a branch where the rule or the model's termination column says so, on the one-call
+step, the native loop and the sharded per-step path alike; ``pool.t['term_pred_t']`` / ``['term_votes_t']`` hold the step's values.
+
 ``sample()`` returns ``(next_obs, reward, terminal, info)`` like the reference, but as slot-indexed CUDA
 tensors (the trainer only reads ``info['alive_ratio']``, ``algorithms/cmbpo.py:254-263``).
 """
@@ -224,6 +228,9 @@ class ModelSampler:
             # the call start at zero, arrays that were attached have just been zeroed)
             pool.set_disagreement(getattr(self.env, "disagreement", False), getattr(self.env, "rew_pessimism", 0.0),
                                   getattr(self.env, "cost_pessimism", 0.0))
+            # ... and its learned termination head
+            pool.set_term_head(getattr(self.env, "predicts_term", False), getattr(self.env, "term_threshold", 0.5),
+                               getattr(self.env, "term_members", "elite"))
             if observations is None:
                 fill(pool.t["cur_obs"])
             else:
@@ -321,6 +328,8 @@ class ModelSampler:
                         dkl_path=t["dkl_t"], ep_var_mean=t["epv_t"])
             if pool.disagreement:       # (the arrays attached beside the struct: the store below reads them)
                 outs.update(rew_var=t["rew_var_t"], cost_var=t["cost_var_t"])
+            if pool.term_head is not None:
+                outs.update(term_pred=t["term_pred_t"], term_votes=t["term_votes_t"])
             env.step_device(t["cur_obs"], t["act_t"], inds_t, outs,
                             row_idx=idx, n_rows=n, scratch=self._scratch, noise=xi_t)
             if exchange:

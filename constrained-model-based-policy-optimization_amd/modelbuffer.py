@@ -73,6 +73,7 @@ def _iv_release(key):
             _lib.lib().cmbpo_rollout_iv_detach(C.byref(rs))
             _lib.lib().cmbpo_rollout_disagreement_detach(C.byref(rs))
             _lib.lib().cmbpo_rollout_value_disagreement_detach(C.byref(rs))
+            _lib.lib().cmbpo_rollout_term_head_detach(C.byref(rs))
     except Exception:      # interpreter shutdown
         pass
 
@@ -99,6 +100,7 @@ class ModelBuffer:
         self.iv_gae, self.iv_eps = bool(iv_gae), self._check_iv_eps(iv_eps)
         self.disagreement, self.rew_pessimism, self.cost_pessimism = False, 0.0, 0.0
         self.value_disagreement, self.v_pessimism, self.vc_pessimism = False, 0.0, 0.0
+        self.term_head = None                 # (threshold, members) of the learned termination head, None: off
         self.trust_var, self.last_weights = None, None
         self.rs = None
         self._iv_key = [0]                    # iscal of the arrays the library's table may hold an entry for
@@ -114,6 +116,7 @@ class ModelBuffer:
             _lib.check(_lib.lib().cmbpo_rollout_disagreement_detach(C.byref(self.rs)), "cmbpo_rollout_disagreement_detach")
             _lib.check(_lib.lib().cmbpo_rollout_value_disagreement_detach(C.byref(self.rs)),
                        "cmbpo_rollout_value_disagreement_detach")
+            _lib.check(_lib.lib().cmbpo_rollout_term_head_detach(C.byref(self.rs)), "cmbpo_rollout_term_head_detach")
         f = dict(dtype=torch.float32, device=dev)
         d = dict(dtype=torch.float64, device=dev)
         t = {}
@@ -155,6 +158,7 @@ class ModelBuffer:
         self._iv_sync()
         self._dis_sync()
         self._vdis_sync()
+        self._term_sync()
 
     def _bind_all(self):
         for name, _ in RolloutStruct._fields_:
@@ -293,6 +297,43 @@ class ModelBuffer:
         vd.part = t["vdis_part"].data_ptr()
         _lib.check(lib.cmbpo_rollout_value_disagreement_attach(C.byref(self.rs), C.byref(vd)),
                    "cmbpo_rollout_value_disagreement_attach")
+
+    # -- learned termination head ------------------------------------------------------------------
+    def set_term_head(self, on, threshold=0.5, members='elite'):
+        """End imagined branches where the model's termination column says so (``FakeEnv(predicts_term=True)``: the sampler
+        hands its environment's head over at every reset); legal whenever nothing is stored.  The step's ``term_pred_t`` /
+        ``term_votes_t`` [B] are kept beside the per-step arrays."""
+        head = None
+        if on:
+            threshold = float(threshold)
+            if not np.isfinite(threshold):
+                raise ValueError(f"term_threshold must be a finite number, got {threshold}")
+            if members not in _lib.TERM_MEMBERS:
+                raise ValueError(f"term_members: 'elite', 'any' or 'majority', got {members!r}")
+            head = (threshold, members)
+        if head == self.term_head:
+            return
+        if self.ptr != 0 or self._size != 0:
+            raise RuntimeError("set_term_head: the buffer holds samples (call it after get() / reset())")
+        self.term_head = head
+        self._term_sync()
+
+    def _term_sync(self):
+        """Attach (on: for the current arrays, threshold and vote) or detach (off: and free) the head beside the struct."""
+        lib, t = _lib.lib(), self.t
+        if self.term_head is None:
+            _lib.check(lib.cmbpo_rollout_term_head_detach(C.byref(self.rs)), "cmbpo_rollout_term_head_detach")
+            t.pop("term_pred_t", None)
+            t.pop("term_votes_t", None)
+            return
+        B, dev = self.capacity, self.device
+        if "term_pred_t" not in t:
+            t["term_pred_t"] = torch.zeros(B, dtype=torch.float32, device=dev)
+            t["term_votes_t"] = torch.zeros(B, dtype=torch.uint8, device=dev)
+        th = _lib.TermHeadStruct()
+        th.threshold, th.members = self.term_head[0], _lib.TERM_MEMBERS[self.term_head[1]]
+        th.term_pred, th.term_votes = t["term_pred_t"].data_ptr(), t["term_votes_t"].data_ptr()
+        _lib.check(lib.cmbpo_rollout_term_head_attach(C.byref(self.rs), C.byref(th)), "cmbpo_rollout_term_head_attach")
 
     def swap(self, a, b):
         """Exchange two same-shaped state arrays (cur_obs <-> next_obs, v_t <-> v_n, ...)."""

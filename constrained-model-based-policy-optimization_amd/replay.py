@@ -114,8 +114,14 @@ class ReplayBuffers:
     def finish(self):
         _lib.check(_lib.lib().cmbpo_replay_finish(C.byref(self.rs), _lib.current_stream()), "cmbpo_replay_finish")
 
-    def run(self, model_handle, task_id, ensemble, elite):
-        """``cmbpo_replay_run``; elite: [H, B] int32 device tensor."""
+    def run(self, model_handle, task_id, ensemble, elite, term_head=None):
+        """``cmbpo_replay_run``; elite: [H, B] int32 device tensor.  term_head: a ``_lib.TermHeadStruct`` -- the learned
+        termination head in the post step (``cmbpo_replay_run_term``)."""
+        if term_head is not None:
+            _lib.check(_lib.lib().cmbpo_replay_run_term(C.byref(self.rs), None, C.byref(term_head), model_handle, int(task_id),
+                                                        int(ensemble), elite.data_ptr(), _lib.current_stream()),
+                       "cmbpo_replay_run_term")
+            return
         _lib.check(_lib.lib().cmbpo_replay_run(C.byref(self.rs), model_handle, int(task_id), int(ensemble), elite.data_ptr(),
                                                _lib.current_stream()), "cmbpo_replay_run")
 
@@ -142,10 +148,16 @@ class ReplayBuffers:
         _lib.check(_lib.lib().cmbpo_replay_calib_finish(C.byref(self.rs), self._calib(), _lib.current_stream()),
                    "cmbpo_replay_calib_finish")
 
-    def run_calibrated(self, model_handle, task_id, ensemble, elite=None):
-        """``cmbpo_replay_run_calibrated``; elite: [H, B] members (None: those of the last ``set_elite``)."""
+    def run_calibrated(self, model_handle, task_id, ensemble, elite=None, term_head=None):
+        """``cmbpo_replay_run_calibrated``; elite: [H, B] members (None: those of the last ``set_elite``).  term_head: as in
+        ``run``."""
         if elite is not None:
             self.set_elite(elite)
+        if term_head is not None:
+            _lib.check(_lib.lib().cmbpo_replay_run_term(C.byref(self.rs), self._calib(), C.byref(term_head), model_handle,
+                                                        int(task_id), int(ensemble), None, _lib.current_stream()),
+                       "cmbpo_replay_run_term")
+            return
         _lib.check(_lib.lib().cmbpo_replay_run_calibrated(C.byref(self.rs), self._calib(), model_handle, int(task_id),
                                                           int(ensemble), _lib.current_stream()), "cmbpo_replay_run_calibrated")
 

@@ -287,6 +287,43 @@ int cmbpo_fakeenv_post_disagreement(int task, int ensemble, int obs_dim, int act
                                     float kappa_rew, float kappa_cost,
                                     float *d_rew_var, float *d_cost_var, void *stream);
 
+/* A learned termination head: the model has one more output column, trained on the real `done` flags, and the
+ * post-processing ends a branch where that column says so -- by the elite member's value or by a vote of the members.
+ *   tc   = obs_dim + 1 + (1 with CMBPO_TASK_LEARNED_COST): the LAST column; d_mean / d_var are [E, ld_rows, tc + 1]
+ *   x_e  = mean[e][r][tc]   (target units: 0 / 1)
+ *   hit_e = x_e > threshold   (a positive test: a NaN never hits; +inf does, -inf does not)
+ *   votes = sum_e hit_e over ALL E members
+ *   learned_done = hit_elite[r]  (CMBPO_TERM_ELITE) | votes > 0  (CMBPO_TERM_ANY) | 2 * votes > E  (CMBPO_TERM_MAJORITY)
+ *   term = rule_done || learned_done      for built-in ids, registered tables and the default task alike
+ * The cost keeps the RULE's own done (cost_on_term, AntSafe's clip(done + obj)): apart from the two optional outputs the head
+ * changes d_term and nothing else.  The column takes no transition noise; DKL, ep_var, next_obs, reward, cost and the
+ * disagreement variances do not read it.  term_pred[r] = x_elite (float32, stored as it is) and term_votes[r] = votes (uint8)
+ * are slot indexed like d_term; either may be NULL. */
+#define CMBPO_TERM_ELITE 0
+#define CMBPO_TERM_ANY 1
+#define CMBPO_TERM_MAJORITY 2
+typedef struct cmbpo_term_head {
+  float threshold;        /* finite */
+  int32_t members;        /* CMBPO_TERM_* */
+  float *term_pred;       /* [.] or NULL */
+  uint8_t *term_votes;    /* [.] or NULL */
+} cmbpo_term_head_t; /* 24 bytes */
+/* cmbpo_fakeenv_post_disagreement's arguments plus the head.  d_xi may be NULL (the deterministic transition);
+ * d_rew_var == d_cost_var == NULL with both kappas 0 means no disagreement (the instances without it); th == NULL forwards to
+ * the existing entry points, which then run what they always ran.  Beside their checks: a finite threshold, members in 0..2,
+ * ensemble <= 8 -- each refused with a message naming the field, before any HIP call. */
+int cmbpo_fakeenv_post_term(int task, int ensemble, int obs_dim, int act_dim,
+                            const float *d_mean, const float *d_var, int ld_rows,
+                            const float *d_obs, const float *d_act,
+                            const int32_t *d_elite, const int32_t *d_row_idx,
+                            const int32_t *d_n_rows, int n_rows, float *d_next_obs,
+                            float *d_rew, uint8_t *d_term, float *d_cost,
+                            float *d_dkl_path, float *d_ep_var_mean,
+                            float *d_ep_var, const float *d_xi,
+                            float kappa_rew, float kappa_cost,
+                            float *d_rew_var, float *d_cost_var,
+                            const cmbpo_term_head_t *th, void *stream);
+
 /* ------------------------------------------------------------------------ *
  * Device-resident rollout state: the fused counterpart of ModelSampler
  * (samplers/model_sampler.py:203-444) + ModelBuffer (buffers/modelbuffer.py).
@@ -499,6 +536,16 @@ typedef struct cmbpo_value_disagreement {
 int cmbpo_rollout_value_disagreement_attach(const cmbpo_rollout_t *r, const cmbpo_value_disagreement_t *vd);
 /* Back to the members' mean, nothing measured (no error when nothing was attached). */
 int cmbpo_rollout_value_disagreement_detach(const cmbpo_rollout_t *r);
+
+/* The learned termination head along imagined rollouts: a copy of *th travels beside an unchanged cmbpo_rollout_t in the same
+ * table (key: r->iscal).  Attached, cmbpo_rollout_step / _run post-process with cmbpo_fakeenv_post_term (with or without
+ * draws, with or without an attached cmbpo_disagreement_t), so term_t -- and with it every finish decision -- is
+ * rule_done || learned_done; before the first launch of a step they require model->out_dim == obs + 1 + learned cost + 1 and
+ * refuse (-1) any other width with a message naming the termination head.  term_pred / term_votes: [B] slot indexed, this
+ * step's values, or NULL.  Owned by the caller, valid until the detach.  The same checks as cmbpo_fakeenv_post_term. */
+int cmbpo_rollout_term_head_attach(const cmbpo_rollout_t *r, const cmbpo_term_head_t *th);
+/* Back to the rules alone (no error when nothing was attached). */
+int cmbpo_rollout_term_head_detach(const cmbpo_rollout_t *r);
 
 /* ModelBuffer.get (modelbuffer.py:184-226): d_offsets[B+1] = exclusive scan of
  * len; d_stats[8] = {n, adv_mean, adv_std, cadv_mean, ret_mean, cret_mean}
@@ -968,6 +1015,13 @@ int cmbpo_replay_calib_finish(const cmbpo_replay_t *rp, const cmbpo_replay_calib
  * plain table, cur_obs and alive are bitwise those of the run call without calibration on the same inputs. */
 int cmbpo_replay_run_calibrated(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, cmbpo_mlp_t *model, int task,
                                 int ensemble, void *stream);
+/* The replay with the learned termination head in its post step (cmbpo_fakeenv_post_term without noise or disagreement): p_term
+ * is rule_done || learned_done, so the termination counts of the table describe the head.  rc == NULL: cmbpo_replay_run's
+ * launches, else cmbpo_replay_run_calibrated's (the members are then rc->elite and d_elite may be NULL or equal to it).  The
+ * model's out_dim must be obs_dim + 1 + learned cost + 1 (refused with a message naming the termination head); th == NULL
+ * forwards to the two existing entry points.  Bitwise the result of the same calls issued one at a time. */
+int cmbpo_replay_run_term(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th,
+                          cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream);
 
 #ifdef __cplusplus
 }
