@@ -59,6 +59,14 @@ path before the sampler's horizon, a time-out is target 0) and has ``FakeEnv`` e
 'any' / 'majority').  With ``m_validate_horizon > 0`` the termination counts of ``model/val_*`` are then the head's, and
 ``model/val_term_recall_h1`` / ``val_term_false_alarm_h1`` are added.  ``save`` / ``load`` keep threshold and vote.
 
+``m_term_pos_weight`` (a number >= 0 or 'balanced'), ``m_term_loss_weight`` (both need ``m_learn_term``) and
+``m_cost_loss_weight`` (needs ``m_learn_cost``) weigh the model's two binary columns in its train loss (DESIGN §3s;
+``PE.set_column_weights``): a class weight on the real terminations, a column weight on the termination / cost column.
+'balanced' is ``clip(n_neg / max(n_pos, 1), 1, m_pos_weight_max)`` of each fit's termination targets, logged as
+``model/term_pos_weight``.  A class weight omega moves the level the column settles at from the termination rate p to
+``utils.pos_weight_level(p, omega)``; ``m_term_threshold`` keeps reading the column as it is.  ``save`` / ``load`` keep the
+four keys in ``column_weights_<epoch>.json``.  With the defaults nothing is attached.
+
 ``static_fns`` takes a ``statics.TaskRules``: user-defined termination / cost rules for the imagined rollouts, with
 precedence over ``task`` (which may itself be a name given to ``statics.register_task``).
 """
@@ -132,6 +140,44 @@ def _calibration_args(validate_horizon, use_model, stochastic, validate_calibrat
     return validate_calibration, calibrated_noise, (lo, hi)
 
 
+COLUMN_WEIGHT_KEYS = ('m_term_pos_weight', 'm_term_loss_weight', 'm_cost_loss_weight', 'm_pos_weight_max')
+
+
+def _column_weight_args(learn_term, learn_cost, term_pos_weight, term_loss_weight, cost_loss_weight, pos_weight_max):
+    """The four column-weight arguments of ``CMBPO`` checked against the heads they weigh: a dict of
+    ``COLUMN_WEIGHT_KEYS`` (floats, ``m_term_pos_weight`` possibly the string 'balanced') or a ValueError in words."""
+    def number(name, v, low_ok):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError("%s: a finite number, got %r" % (name, v))
+        if not (np.isfinite(f) and (f >= 0.0 if low_ok else f > 0.0)):
+            raise ValueError("%s: a finite number %s 0, got %r" % (name, ">=" if low_ok else ">", v))
+        return f
+
+    balanced = isinstance(term_pos_weight, str)
+    if balanced and term_pos_weight != 'balanced':
+        raise ValueError("m_term_pos_weight: a number >= 0 or 'balanced', got %r" % (term_pos_weight,))
+    out = {'m_term_pos_weight': 'balanced' if balanced else number('m_term_pos_weight', term_pos_weight, True),
+           'm_term_loss_weight': number('m_term_loss_weight', term_loss_weight, True),
+           'm_cost_loss_weight': number('m_cost_loss_weight', cost_loss_weight, True),
+           'm_pos_weight_max': number('m_pos_weight_max', pos_weight_max, False)}
+    if out['m_pos_weight_max'] < 1.0:
+        raise ValueError("m_pos_weight_max: the upper clip of 'balanced', >= 1, got %r" % (pos_weight_max,))
+    if not learn_term and (out['m_term_pos_weight'] != 1.0 or out['m_term_loss_weight'] != 1.0):
+        raise ValueError("m_term_pos_weight / m_term_loss_weight need m_learn_term=True: they weigh the termination column")
+    if not learn_cost and out['m_cost_loss_weight'] != 1.0:
+        raise ValueError("m_cost_loss_weight needs m_learn_cost=True: it weighs the learned cost column")
+    return out
+
+
+def balanced_pos_weight(targets, pos_weight_max):
+    """'balanced' class weight of a 0/1 target column: clip(n_neg / max(n_pos, 1), 1, pos_weight_max)."""
+    pos = int(np.count_nonzero(np.asarray(targets) > 0.5))
+    neg = int(np.size(targets)) - pos
+    return float(np.clip(neg / max(pos, 1), 1.0, float(pos_weight_max)))
+
+
 class CMBPO:
     """Constrained Model-Based Policy Optimization (``algorithms/cmbpo.py:30``)."""
 
@@ -149,7 +195,11 @@ class CMBPO:
                  m_validate_horizon=0, m_validate_windows=1024, m_imagined_weight=1.0, m_trust_var=None,
                  m_validate_calibration=False, m_calibrated_noise=False, m_noise_temperature_range=(0.25, 4.0),
                  m_learn_term=False, m_term_threshold=0.5, m_term_members='elite',
+                 m_term_pos_weight=1.0, m_term_loss_weight=1.0, m_cost_loss_weight=1.0, m_pos_weight_max=20.0,
                  **_unused):
+        # column / class weights of the model's binary columns; refused in words before anything is built
+        self._column_weights = _column_weight_args(bool(m_learn_term) and bool(use_model), bool(m_learn_cost), m_term_pos_weight,
+                                                   m_term_loss_weight, m_cost_loss_weight, m_pos_weight_max)
         # predictive calibration in the validation replay and, from its one-step row, the scale of the transition
         # noise; refused in words before anything is built
         self._validate_calibration, self._calibrated_noise, self._noise_temperature_range = _calibration_args(
@@ -315,9 +365,31 @@ class CMBPO:
         model_samples = self._buffer.get_archive(fields + (['path_lengths'] if self._m_learn_term else []))
         dyn_ins, dyn_outs = format_samples_for_dyn(model_samples, append_r=True, append_c=self._m_learn_cost,
                                                    append_t=self._m_learn_term, horizon=self.sampler.max_path_length)
-        return self._model.train(dyn_ins, dyn_outs, batch_size=batch_size, max_epochs=max_epochs,
-                                 min_epoch_before_break=min_epochs, holdout_ratio=0.2, max_t=self._max_model_t,
-                                 shuffle_on_device=self._shuffle_on_device)
+        extra = self._set_model_column_weights(dyn_outs)
+        out = self._model.train(dyn_ins, dyn_outs, batch_size=batch_size, max_epochs=max_epochs,
+                                min_epoch_before_break=min_epochs, holdout_ratio=0.2, max_t=self._max_model_t,
+                                shuffle_on_device=self._shuffle_on_device)
+        out.update(extra)
+        return out
+
+    def _set_model_column_weights(self, dyn_outs):
+        """The column / class weights of this fit onto the model: the termination column is the last one, the
+        cost column the one after the reward; 'balanced' is recomputed from this call's termination targets.  With the
+        defaults nothing is attached and nothing is logged."""
+        cw = self._column_weights
+        if (cw['m_term_pos_weight'], cw['m_term_loss_weight'], cw['m_cost_loss_weight']) == (1.0, 1.0, 1.0):
+            return {}
+        col, pos, extra = {}, {}, {}
+        if self._m_learn_term:
+            omega = cw['m_term_pos_weight']
+            if omega == 'balanced':
+                omega = balanced_pos_weight(dyn_outs[:, -1], cw['m_pos_weight_max'])
+            pos[-1], col[-1] = omega, cw['m_term_loss_weight']
+            extra['term_pos_weight'] = omega
+        if self._m_learn_cost:
+            col[self.obs_dim + 1] = cw['m_cost_loss_weight']
+        self._model.set_column_weights(col, pos)
+        return extra
 
     def validate_model(self, epochs=None, horizon=None, n_windows=None):
         """Open-loop validation of the dynamics model: ``n_windows`` windows of up to ``horizon`` consecutive
@@ -552,12 +624,31 @@ class CMBPO:
                 import os
                 with open(os.path.join(savedir, 'term_head_%d.json' % self._epoch), 'w') as fh:
                     json.dump({'threshold': self.fake_env.term_threshold, 'members': self.fake_env.term_members}, fh)
+            if self._m_learn_term or self._m_learn_cost:      # the column weights of the fits, a file of their own
+                import json
+                import os
+                with open(os.path.join(savedir, 'column_weights_%d.json' % self._epoch), 'w') as fh:
+                    json.dump(self._column_weights, fh)
+
+    def _load_column_weights(self, savedir, timestep):
+        """The four keys ``save`` wrote (a checkpoint from before them has no such file: the constructor's stay)."""
+        import json
+        import os
+        path = os.path.join(savedir, 'column_weights_%d.json' % int(timestep))
+        if not os.path.exists(path):
+            return
+        with open(path) as fh:
+            kw = json.load(fh)
+        self._column_weights = _column_weight_args(self._m_learn_term, self._m_learn_cost, *(kw[k] for k in COLUMN_WEIGHT_KEYS))
+        if (kw['m_term_pos_weight'], kw['m_term_loss_weight'], kw['m_cost_loss_weight']) == (1.0, 1.0, 1.0):
+            self._model.set_column_weights(None, None)
 
     def load(self, savedir, timestep):
         """The model ``save`` wrote at epoch ``timestep`` and, with the termination head, its threshold and vote."""
         if not self._use_model:
             raise ValueError("load: the trainer was built with use_model=False, there is no model to load")
         self._model.load(savedir, timestep)
+        self._load_column_weights(savedir, timestep)
         if self._m_learn_term:
             import json
             import os

@@ -77,6 +77,20 @@ struct LossWArgs : LossArgs {
   const float *w;          // [N] sample weights: sum w[row] (mean - t)^2
 };
 
+// Column and class weights of the probabilistic losses (the definition stands in include/cmbpo_hip.h): element (row,
+// d) of a member's batch weighs col[d], times pos[d] where the RAW target (before the output scaler) is positive.  The test is
+// written positively: a NaN target takes the plain weight.  Kernels that know them are instances of their own, like the ones of
+// ValueExtras above.
+struct ColWeights {
+  const float *col, *pos;  // [D] each, both set
+};
+__device__ __forceinline__ float column_weight(const ColWeights &c, int d, float raw_target) {
+  return c.col[d] * (raw_target > 0.5f ? c.pos[d] : 1.0f);
+}
+struct LossCArgs : LossArgs {
+  ColWeights c;            // sum w[row][d] (mean - t)^2
+};
+
 __device__ __forceinline__ float scaled_target(const LossArgs &p, int e, int b, int d) {
   const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
   float t = p.targets[(size_t)row * p.D + d];
@@ -96,6 +110,9 @@ __global__ __launch_bounds__(kThreads) void loss_sums_kernel(const P p) {
     if constexpr (std::is_same<P, LossWArgs>::value) {
       const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
       s_mse += (double)p.w[row] * (double)(diff * diff);
+    } else if constexpr (std::is_same<P, LossCArgs>::value) {
+      const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
+      s_mse += (double)column_weight(p.c, d, p.targets[(size_t)row * p.D + d]) * (double)(diff * diff);
     } else {
       s_mse += (double)(diff * diff);
     }
@@ -161,6 +178,64 @@ __global__ __launch_bounds__(64) void old_var_final_kernel(const double *part, i
   }
 }
 
+// The per-tile loss statistics of a column-weighted 'MSPE' step: sum w mse, sum w (var - mse)^2, sum lv^2 of every tile, from the
+// raw outputs the training forward stored, into the [items][3] layout its epilogue writes (mspe_ratio adds them).  ROWS = 32
+// walks the tiles of ens_mlp_kernel<HEAD_TRAIN> on 256 threads, ROWS = 64 the items of fwd_train_h_kernel on 512 (whose sums
+// stand in the first of an item's two 32-row slots): the same element-to-thread map, the same float32 terms and the same order
+// of the float64 sums as the forward that ran, so all-ones weights reproduce its statistics bit for bit.  No atomics.
+struct ColStatsArgs {
+  const float *o;          // [E][B][O] raw network output, O == 2 D
+  const float *targets;    // [N][D]
+  const int32_t *idx;
+  int idx_stride;
+  const float *out_mu, *out_sig;
+  int B, O, D, tiles32;
+  ColWeights c;
+  double *loss_part;       // [E * tiles32][3]
+};
+
+template <int ROWS>
+__global__ __launch_bounds__(8 * ROWS) void col_stats_kernel(const ColStatsArgs p) {
+  constexpr int NT = 8 * ROWS, NW = NT / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int e = blockIdx.y, row0 = blockIdx.x * ROWS;
+  const int D = p.D;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  for (int i = tid; i < ROWS * D; i += NT) {
+    const int b = i / D, d = i - b * D;
+    const int row = row0 + b;
+    if (row >= p.B) continue;
+    const int src = p.idx ? p.idx[(size_t)e * p.idx_stride + row] : row;
+    const float traw = p.targets[(size_t)src * D + d];
+    float t = traw;
+    if (p.out_mu) t = (t - p.out_mu[d]) / p.out_sig[d];
+    const float *orow = p.o + ((size_t)e * p.B + row) * p.O;
+    const float diff = orow[d] - t;
+    const float mse = diff * diff;
+    const float w = column_weight(p.c, d, traw);
+    s0 += (double)(w * mse);
+    const float lv = orow[D + d];
+    const float dv = expf(lv) - mse;
+    s1 += (double)(w * (dv * dv));
+    s2 += (double)(lv * lv);
+  }
+  __shared__ double s_loss[3][NW];
+  s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
+  if (lane == 0) { s_loss[0][wave] = s0; s_loss[1][wave] = s1; s_loss[2][wave] = s2; }
+  __syncthreads();
+  if (tid < 3) {
+    if constexpr (ROWS == 32) {
+      p.loss_part[((size_t)e * p.tiles32 + blockIdx.x) * 3 + tid] = (s_loss[tid][0] + s_loss[tid][1]) + (s_loss[tid][2] + s_loss[tid][3]);
+    } else {
+      const size_t item0 = (size_t)e * p.tiles32 + 2 * blockIdx.x;
+      double tsum = 0.0;
+      for (int w = 0; w < NW; ++w) tsum += s_loss[tid][w];
+      p.loss_part[item0 * 3 + tid] = tsum;
+      if (2 * (int)blockIdx.x + 1 < p.tiles32) p.loss_part[(item0 + 1) * 3 + tid] = 0.0;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // backward chain:  d2 = (d3 W2^T) * g2 ;  d1 = (d2 W1^T) * g1      (g = swish'(z) exported by the forward)
 // Same transposed-GEMM formulation as the forward (see ens_mlp.hip): rows of the batch on the MFMA columns, the
@@ -186,9 +261,13 @@ struct BwdArgs {
 struct BwdXArgs : BwdArgs {
   ValueExtras x;             // deterministic heads (prob == 0) only
 };
+struct BwdCArgs : BwdArgs {
+  ColWeights c;              // probabilistic heads (prob != 0) only; loss_part then holds the weighted sums (col_stats_kernel)
+};
 
 // `ratio` of the MSPE loss, 0.05 * mean_all(mse) / mean_all((var - mse)^2): a constant of the step.  The two sums come from
-// the forward's per-tile statistics, added here in tile order by every workgroup of NW waves (same order everywhere:
+// the forward's per-tile statistics (with column weights attached: sum w mse and sum w (var - mse)^2, rewritten by
+// col_stats_kernel in the same layout), added here in tile order by every workgroup of NW waves (same order everywhere:
 // reproducible).  Contains a barrier: the whole workgroup calls it.
 template <int NW>
 __device__ __forceinline__ float mspe_ratio(const BwdArgs &p, int tid) {
@@ -224,7 +303,8 @@ __device__ __forceinline__ float output_delta(const P &p, int e, int row, int k,
   const float *orow = p.o + ((size_t)e * p.B + row) * p.O;
   const int src = p.idx ? p.idx[(size_t)e * p.idx_stride + row] : row;
   const int dd = (k < p.D) ? k : k - p.D;
-  float t = p.targets[(size_t)src * p.D + dd];
+  const float traw = p.targets[(size_t)src * p.D + dd];
+  float t = traw;
   if (p.out_mu) t = (t - p.out_mu[dd]) / p.out_sig[dd];
   if constexpr (std::is_same<P, BwdXArgs>::value) {     // weighted / clipped 'MSE' (DESIGN §3j); the host admits no other head
     const bool clip = p.x.old_pred != nullptr;
@@ -232,6 +312,16 @@ __device__ __forceinline__ float output_delta(const P &p, int e, int row, int k,
     return value_delta(orow[dd], t, clip, olds, clip ? *p.x.clip_c : 0.0f, p.x.w ? p.x.w[src] : 1.0f) * inv_bd;
   }
   const float diff = orow[dd] - t;
+  if constexpr (std::is_same<P, BwdCArgs>::value) {     // column / class weights: w on every data term, the
+    const float w = column_weight(p.c, dd, traw);       // log-variance regulariser stays plain; the host admits no 'MSE' head.
+    if (p.prob == 2) {                                  // (with w == 1 every product below is the plain one: same bits)
+      const float iv = expf(-orow[p.D + dd]);
+      return (k < p.D) ? w * (iv * diff) * inv_bd : w * (0.5f - 0.5f * iv * diff * diff) * inv_bd;
+    }
+    if (k < p.D) return w * (2.0f * diff) * inv_bd;
+    const float lv = orow[k], var = expf(lv);
+    return (w * (2.0f * ratio * (var - diff * diff) * var) + 0.1f * lv) * inv_bd;
+  }
   if (!p.prob) return diff * inv_bd;
   if (p.prob == 2) {
     const float iv = expf(-orow[p.D + dd]);
@@ -1801,6 +1891,8 @@ struct cmbpo_trainer {
   double *sums;
   double *loss_part;             // [E * ceil(max_batch / 32)][3] per-tile loss statistics of the training forward
   double *old_var_part;          // [kOldVarParts] partial sums of a clipped step's old_var, then (as a float) its clip range c
+  float *colw;                   // [2][D] col_weight | pos_weight of cmbpo_trainer_set_column_weights
+  bool colw_on = false;          // ... attached: the step, the epoch and `self.loss` run their column-weighted instances
   size_t wsize[3], bsize[3];
   float *opmax;                  // [E][ceil(max_batch / 32)][kOpMax] per-tile largest |x|, |h1|, |h2|, |d1|, |d2|, |d3| of the step
   // the backward chain on the f16 path (bwd_chain_h_kernel; 512-wide, at most 64 padded outputs): two-piece images of W1^T and
@@ -2093,6 +2185,22 @@ int launch_old_var(cmbpo_trainer *t, const float *d_targets, const float *d_old_
   return CMBPO_OK;
 }
 
+ColWeights col_weights_of(const cmbpo_trainer *t) { return ColWeights{t->colw, t->colw + t->D}; }
+
+// the weighted loss statistics of an 'MSPE' step over the forward's (col_stats_kernel), in the layout of the forward that ran
+int launch_col_stats(cmbpo_trainer *t, const float *d_targets, const int32_t *d_idx, int idx_stride, int batch, hipStream_t s) {
+  ColStatsArgs a{};
+  a.o = t->o; a.targets = d_targets; a.idx = d_idx; a.idx_stride = idx_stride;
+  a.out_mu = t->m->out_mu(); a.out_sig = t->m->out_sig();
+  a.B = batch; a.O = t->O; a.D = t->D; a.tiles32 = cmbpo_ceil_div(batch, 32);
+  a.c = col_weights_of(t);
+  a.loss_part = t->loss_part;
+  if (t->b16 && t->b16_fwd) hipLaunchKernelGGL(col_stats_kernel<64>, dim3(cmbpo_ceil_div(batch, 64), t->E), dim3(512), 0, s, a);
+  else hipLaunchKernelGGL(col_stats_kernel<32>, dim3(a.tiles32, t->E), dim3(256), 0, s, a);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
 int run_forward(cmbpo_trainer *t, const float *d_inputs, const int32_t *d_idx, int idx_stride, int rows, bool exports,
                 hipStream_t s, const float *d_targets = nullptr) {
   if (t->b16 && t->b16_fwd) return launch_fwd_h(t, d_inputs, d_idx, idx_stride, rows, exports, s, d_targets);
@@ -2192,6 +2300,7 @@ extern "C" int cmbpo_trainer_create(cmbpo_trainer_t **out, cmbpo_mlp_t *m, int m
   const size_t olp = take(2 * 3 * (size_t)E * cmbpo_ceil_div(max_batch, 32));   // doubles
   const size_t oom = take((size_t)E * cmbpo_ceil_div(max_batch, 32) * kOpMax);
   const size_t oov = take(2 * (size_t)(kOldVarParts + 1));   // doubles
+  const size_t ocw = take(2 * (size_t)t->D);
   hipError_t err = hipMalloc(reinterpret_cast<void **>(&t->pool), off * sizeof(float));
   if (err != hipSuccess) {
     cmbpo_set_error("cmbpo_trainer_create: hipMalloc(%zu) failed: %s", off * sizeof(float), hipGetErrorString(err));
@@ -2218,6 +2327,7 @@ extern "C" int cmbpo_trainer_create(cmbpo_trainer_t **out, cmbpo_mlp_t *m, int m
   t->loss_part = reinterpret_cast<double *>(P + olp);
   t->opmax = P + oom;
   t->old_var_part = reinterpret_cast<double *>(P + oov);
+  t->colw = P + ocw;
   if (H == 512 && !t->fused && t->OPk <= 64) {
     // images for the f16 training kernels (bwd_chain_h_kernel, fwd_train_h_kernel); without them the fp32 kernels run
     t->b16_s3 = cmbpo_ceil_div(t->OPk, 16);
@@ -2304,6 +2414,41 @@ extern "C" int cmbpo_trainer_set_loss(cmbpo_trainer_t *t, int loss) {
   CMBPO_REQUIRE(loss == CMBPO_LOSS_DEFAULT || loss == CMBPO_LOSS_NLL, "cmbpo_trainer_set_loss: unknown loss %d", loss);
   CMBPO_REQUIRE(loss == CMBPO_LOSS_DEFAULT || t->prob, "cmbpo_trainer_set_loss: 'NLL' needs a probabilistic (HEAD_PROB) ensemble");
   t->nll = loss == CMBPO_LOSS_NLL;
+  return CMBPO_OK;
+}
+
+extern "C" int cmbpo_trainer_set_column_weights(cmbpo_trainer_t *t, const float *h_col_weight, const float *h_pos_weight,
+                                                int target_dim, void *stream) {
+  const char *who = "cmbpo_trainer_set_column_weights";
+  // every check stands before the first HIP call
+  if (h_col_weight || h_pos_weight) {
+    CMBPO_REQUIRE(target_dim >= 1, "%s: target_dim %d", who, target_dim);
+    bool positive = h_col_weight == nullptr;
+    for (int d = 0; d < target_dim; ++d) {
+      if (h_col_weight) {
+        CMBPO_REQUIRE(isfinite(h_col_weight[d]) && h_col_weight[d] >= 0.0f, "%s: col_weight[%d] = %g is not a finite number >= 0", who, d,
+                      (double)h_col_weight[d]);
+        positive = positive || h_col_weight[d] > 0.0f;
+      }
+      if (h_pos_weight)
+        CMBPO_REQUIRE(isfinite(h_pos_weight[d]) && h_pos_weight[d] >= 0.0f, "%s: pos_weight[%d] = %g is not a finite number >= 0", who, d,
+                      (double)h_pos_weight[d]);
+    }
+    CMBPO_REQUIRE(positive, "%s: col_weight has no positive entry (the loss would be the regulariser alone)", who);
+  }
+  CMBPO_REQUIRE(t != nullptr, "%s: handle is NULL", who);
+  if (!h_col_weight && !h_pos_weight) { t->colw_on = false; return CMBPO_OK; }
+  CMBPO_REQUIRE(t->prob, "%s: column weights are for probabilistic ('MSPE' / 'NLL') heads; a deterministic ('MSE') head takes "
+                "per-sample weights through cmbpo_trainer_step_ex", who);
+  CMBPO_REQUIRE(target_dim == t->D, "%s: target_dim %d != %d", who, target_dim, t->D);
+  hipStream_t s = (hipStream_t)stream;
+  const int D = t->D;
+  std::vector<float> tmp(2 * (size_t)D, 1.0f);
+  if (h_col_weight) memcpy(tmp.data(), h_col_weight, D * sizeof(float));
+  if (h_pos_weight) memcpy(tmp.data() + D, h_pos_weight, D * sizeof(float));
+  CMBPO_HIP_CHECK(hipMemcpyAsync(t->colw, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  CMBPO_HIP_CHECK(hipStreamSynchronize(s));   // tmp goes out of scope
+  t->colw_on = true;
   return CMBPO_OK;
 }
 
@@ -2394,6 +2539,15 @@ int trainer_step(const char *who, cmbpo_trainer_t *t, const float *d_inputs, int
   if (x) {
     b.x = *x;
     rc = launch_bwd_any<BwdXArgs>(t, b, batch, s);
+  } else if (t->colw_on) {
+    if (b.prob == 1) {
+      rc = launch_col_stats(t, d_targets, d_idx, idx_stride, batch, s);
+      if (rc != CMBPO_OK) return rc;
+    }
+    BwdCArgs c{};
+    static_cast<BwdArgs &>(c) = b;
+    c.c = col_weights_of(t);
+    rc = launch_bwd_any<BwdCArgs>(t, c, batch, s);
   } else {
     rc = launch_bwd_any<BwdArgs>(t, b, batch, s);
   }
@@ -2453,8 +2607,14 @@ int trainer_losses(const char *who, cmbpo_trainer_t *t, const float *d_inputs, i
     l.sums = t->sums;
     l.w = d_weights;
     const int gx = min(cmbpo_ceil_div(rows * t->D, kThreads), 64);
-    if (d_weights) hipLaunchKernelGGL(loss_sums_kernel<LossWArgs>, dim3(gx, E), dim3(kThreads), 0, s, l);
-    else hipLaunchKernelGGL(loss_sums_kernel<LossArgs>, dim3(gx, E), dim3(kThreads), 0, s, static_cast<const LossArgs &>(l));
+    if (d_weights) {
+      hipLaunchKernelGGL(loss_sums_kernel<LossWArgs>, dim3(gx, E), dim3(kThreads), 0, s, l);
+    } else if (t->colw_on) {
+      LossCArgs lc{};
+      static_cast<LossArgs &>(lc) = l;
+      lc.c = col_weights_of(t);
+      hipLaunchKernelGGL(loss_sums_kernel<LossCArgs>, dim3(gx, E), dim3(kThreads), 0, s, lc);
+    } else hipLaunchKernelGGL(loss_sums_kernel<LossArgs>, dim3(gx, E), dim3(kThreads), 0, s, static_cast<const LossArgs &>(l));
   }
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, s, t->sums, E, 1.0 / ((double)n_rows * t->D), d_losses);
   CMBPO_HIP_CHECK(hipGetLastError());

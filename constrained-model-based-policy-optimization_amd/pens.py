@@ -17,7 +17,8 @@ reference's host control flow (holdout split, bootstrap indices, epoch loop, ear
 elite ranking) and runs every ``sess.run(train_op)`` / ``sess.run(self.loss)`` as HIP kernels
 over device-resident data (``csrc/ens_train.hip``).  Losses: 'MSPE' (dynamics) and 'MSE'
 (critics), the two every shipped config uses, 'NLL', and for 'MSE' the sample-weighted and clipped
-variants (``weighted`` / ``clip_loss``).
+variants (``weighted`` / ``clip_loss``); for 'MSPE' / 'NLL' a weight per target column and a
+class weight per column (``col_weight`` / ``pos_weight``).
 """
 import ctypes as C
 import itertools
@@ -250,6 +251,15 @@ class EnsembleTrainer:
                     "cmbpo_trainer_losses_ex")
         return out
 
+    def set_column_weights(self, col_weight=None, pos_weight=None):
+        """Column / class weights of a probabilistic head (float32 host arrays of target_dim entries; both None detaches):
+        trainer state that ``step``, ``epoch`` and ``losses`` honour."""
+        a = col_weight if col_weight is not None else pos_weight
+        with torch.cuda.device(self.mlp.device):
+            _lib.check(_lib.lib().cmbpo_trainer_set_column_weights(
+                self._h, _lib.ptr(col_weight), _lib.ptr(pos_weight), 0 if a is None else int(a.shape[0]),
+                _lib.current_stream()), "cmbpo_trainer_set_column_weights")
+
     @property
     def steps_done(self):
         return int(_lib.lib().cmbpo_trainer_steps_done(self._h))
@@ -265,6 +275,27 @@ def _to_dev(x, device):
     if isinstance(x, torch.Tensor):
         return x.to(device=device, dtype=torch.float32).contiguous(), False
     return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(device), True
+
+
+def column_weight_array(w, out_dim, what):
+    """``col_weight`` / ``pos_weight`` of :class:`PE` as a float32 array of ``out_dim`` entries (None stays None): an array of
+    that length, or a ``{column: weight}`` dict over all-ones (negative columns count from the end)."""
+    if w is None:
+        return None
+    out_dim = int(out_dim)
+    if isinstance(w, dict):
+        a = np.ones(out_dim, np.float64)
+        for k, v in w.items():
+            if int(k) != k or not -out_dim <= int(k) < out_dim:
+                raise ValueError("%s: column %r of %d" % (what, k, out_dim))
+            a[int(k)] = float(v)
+    else:
+        a = np.asarray(w, np.float64).reshape(-1)
+        if a.shape[0] != out_dim:
+            raise ValueError("%s: %d entries for %d target columns" % (what, a.shape[0], out_dim))
+    if not np.all(np.isfinite(a) & (a >= 0)):
+        raise ValueError("%s: entries are finite numbers >= 0; got %r" % (what, a.tolist()))
+    return np.ascontiguousarray(a, dtype=np.float32)
 
 
 class TrainControl:
@@ -376,8 +407,11 @@ class PE(TrainControl):
     def __init__(self, in_dim, out_dim, name="BNN", hidden_dims=(512, 512), num_networks=7,
                  num_elites=5, loss="MSPE", activation="swish", use_scaler_in=False,
                  use_scaler_out=False, device=None, lr=1e-3, decay=1e-4, max_logvar=.5, min_logvar=-6,
-                 clip_loss=False, kl_cliprange=0.1, weighted=False, **_unused):
+                 clip_loss=False, kl_cliprange=0.1, weighted=False, col_weight=None, pos_weight=None, **_unused):
         hidden_dims = tuple(int(h) for h in hidden_dims)
+        self.loss_type, self._out_dim = loss, int(out_dim)
+        self._trainer = None
+        self.set_column_weights(col_weight, pos_weight)     # (checked before anything is created on the device)
         # clipped / sample-weighted value losses (pe.py:67-68,150,232-244): the deterministic 'MSE' head only
         if (clip_loss or weighted) and loss != "MSE":
             raise NotImplementedError("clip_loss / weighted are provided for loss='MSE' (the clipped 'NLL' loss needs "
@@ -648,6 +682,22 @@ class PE(TrainControl):
                 "cmbpo_ens_predict_mean")
         return res.cpu().numpy() if was_np else res
 
+    def set_column_weights(self, col_weight=None, pos_weight=None):
+        """Column and class weights of a probabilistic model's train loss and ``self.loss``: element (row, d)
+        weighs ``col_weight[d]``, times ``pos_weight[d]`` where the raw target is > 0.5.  Each is an array of ``out_dim``
+        entries or a ``{column: weight}`` dict (negative columns count from the end); both None detaches.  A 0/1 column of
+        positive rate p then settles at ``utils.pos_weight_level(p, pos_weight)``, not at p."""
+        cw = column_weight_array(col_weight, self._out_dim, "col_weight")
+        pw = column_weight_array(pos_weight, self._out_dim, "pos_weight")
+        if (cw is not None or pw is not None) and not self.is_probabilistic:
+            raise NotImplementedError("col_weight / pos_weight are for probabilistic models ('MSPE', 'NLL'); loss %r takes "
+                                      "per-sample weights (weighted=True)" % (self.loss_type,))
+        if cw is not None and not (cw > 0).any():
+            raise ValueError("col_weight has no positive entry")
+        self.col_weight, self.pos_weight = cw, pw
+        if self._trainer is not None:
+            self._trainer.set_column_weights(cw, pw)
+
     # -- training hooks (device side of TrainControl.train) -------------------------
     def _ensure_trainer(self, batch_size):
         if self._trainer is not None and self._trainer.max_batch >= batch_size:
@@ -664,6 +714,8 @@ class PE(TrainControl):
             (mw, mb), (vw, vb), steps = state
             self._trainer.set_moments(0, mw, mb, steps)
             self._trainer.set_moments(1, vw, vb, steps)
+        if self.col_weight is not None or self.pos_weight is not None:
+            self._trainer.set_column_weights(self.col_weight, self.pos_weight)
         return self._trainer
 
     def validate(self, inputs, targets):
@@ -775,9 +827,11 @@ class PE(TrainControl):
 def build_PE(in_dim, out_dim, name="BNN", hidden_dims=(200, 200, 200), num_networks=7, num_elites=5,
              loss="MSPE", activation="swish", output_activation=None, decay=1e-4, lr=1e-3,
              lr_decay=None, decay_steps=None, use_scaler_in=False, use_scaler_out=False,
-             clip_loss=False, kl_cliprange=0.1, max_logvar=.5, min_logvar=-6, session=None, device=None):
+             clip_loss=False, kl_cliprange=0.1, max_logvar=.5, min_logvar=-6, session=None, device=None,
+             col_weight=None, pos_weight=None):
     """Same signature as models/pens/pe_factory.py:9-29 (Adam with a constant learning rate; lr_decay is unused by
-    every shipped config).  ``clip_loss`` / ``kl_cliprange``: the clipped value loss of 'MSE' models (PE)."""
+    every shipped config).  ``clip_loss`` / ``kl_cliprange``: the clipped value loss of 'MSE' models (PE, DESIGN §3j);
+    ``col_weight`` / ``pos_weight``: column and class weights of probabilistic models (PE.set_column_weights)."""
     if output_activation is not None:
         raise NotImplementedError("output activations are unused by every shipped config")
     if lr_decay is not None:
@@ -785,4 +839,5 @@ def build_PE(in_dim, out_dim, name="BNN", hidden_dims=(200, 200, 200), num_netwo
     return PE(in_dim, out_dim, name=name, hidden_dims=hidden_dims, num_networks=num_networks,
               num_elites=num_elites, loss=loss, activation=activation, use_scaler_in=use_scaler_in,
               use_scaler_out=use_scaler_out, device=device, lr=lr, decay=decay, max_logvar=max_logvar,
-              min_logvar=min_logvar, clip_loss=clip_loss, kl_cliprange=kl_cliprange)
+              min_logvar=min_logvar, clip_loss=clip_loss, kl_cliprange=kl_cliprange, col_weight=col_weight,
+              pos_weight=pos_weight)

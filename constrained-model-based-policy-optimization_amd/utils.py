@@ -6,6 +6,16 @@ The variant is the RESOLVED dict (ray-tune ``sample_from`` entries already evalu
 from copy import deepcopy
 
 
+def pos_weight_level(p, omega):
+    """Where a 0/1 target column of positive rate ``p`` settles under the class weight ``omega`` (``PE(pos_weight=)``,
+    ``CMBPO(m_term_pos_weight=)``): the weighted least-squares level q = omega p / (omega p + 1 - p), not p."""
+    p, omega = float(p), float(omega)
+    if not (0.0 <= p <= 1.0 and omega >= 0.0):
+        raise ValueError("pos_weight_level: 0 <= p <= 1 and omega >= 0 expected, got %r, %r" % (p, omega))
+    den = omega * p + 1.0 - p
+    return omega * p / den if den > 0.0 else 0.0
+
+
 def get_cpobuffer(env, *args, **kwargs):
     from .cpobuffer import CPOBuffer
     return CPOBuffer(*args, observation_space=env.observation_space, action_space=env.action_space, **kwargs)

@@ -852,6 +852,27 @@ int cmbpo_trainer_losses_ex(cmbpo_trainer_t *t, const float *d_inputs, int in_di
                             const float *d_targets, int target_dim, const int32_t *d_idx,
                             int idx_stride, int n_rows, float *d_losses,
                             const cmbpo_train_extras_t *extras, void *stream);
+/* Column and class weights of the probabilistic train losses ('MSPE', 'NLL'); DESIGN §3s.  Two host arrays of target_dim
+ * floats, h_col_weight (NULL: all ones) and h_pos_weight (NULL: all ones).  For member e, batch row b with gathered data row r
+ * and target column d
+ *     w[b][d] = col_weight[d] * (targets[r][d] > 0.5f ? pos_weight[d] : 1)
+ * The test reads the RAW target, before the output scaler, and is written positively: a NaN target takes the plain weight.
+ * Every mean over (row, column) of a per-element data term becomes the mean of w times that term; the divisor stays B D (the
+ * mean divides by the batch, not by the weight sum, as with d_weights above); the log-variance regulariser stays unweighted:
+ *   MSPE  total_e = mean(w (m - t')^2) + ratio mean(w (var - sg(mse))^2) + 0.05 mean_all(lv^2),
+ *         ratio = 0.05 sum_all(w mse) / sum_all(w (var - mse)^2) over all members;
+ *         d/dm = 2 w (m - t') / (B D),   d/dlv = [2 ratio w (var - mse) var + 0.1 lv] / (B D)
+ *   NLL   total_e = mean(w 0.5 exp(-lv) (m - t')^2) + mean(w 0.5 lv);
+ *         d/dm = w exp(-lv) (m - t') / (B D),   d/dlv = w (0.5 - 0.5 exp(-lv) (m - t')^2) / (B D)
+ *   `self.loss` (cmbpo_trainer_losses) = 0.5 mean(w (m - t')^2): members are ranked by the loss they were trained on.
+ * On a 0/1 column with positive rate p and class weight omega the weighted least-squares level is
+ * q = omega p / (omega p + 1 - p), not p: whoever thresholds the column reads q.
+ * The weights are copied to the device and are trainer state: cmbpo_trainer_step, _epoch and _losses honour them until both
+ * arrays are NULL (detach: the plain kernels run again, bit for bit).  The *_ex entries go on refusing probabilistic heads.
+ * Refused (CMBPO_EINVAL before any device work): a negative or non-finite entry, a col_weight with no positive entry, a NULL
+ * trainer, a deterministic head (its per-sample weights go through cmbpo_trainer_step_ex), target_dim != the head's. */
+int cmbpo_trainer_set_column_weights(cmbpo_trainer_t *t, const float *h_col_weight, const float *h_pos_weight,
+                                     int target_dim, void *stream);
 long cmbpo_trainer_steps_done(const cmbpo_trainer_t *t);
 /* Which kernels a training step of this trainer runs: bit 0 the f16 backward chain, bit 1 the f16 training forward
  * (0: the fp32 kernels; -1: NULL handle).  Fixed at creation by the network's shapes. */
