@@ -9,6 +9,7 @@
 //                                 `a*b*c*z_rot >= -0.7` precedence quirk)
 // and, for a registered rule id (csrc/task_rules.hip), the user's clause table in place of the three built-in rule sets.
 #include "common.h"
+#include "fakeenv_post_internal.h"
 
 #include <math.h>
 
@@ -436,11 +437,7 @@ void launch_post(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const 
   else hipLaunchKernelGGL((fakeenv_post_kernel<0, RULES, NOISE, DIS, TERM>), grid, dim3(kThreads), lds, stream, a);
 }
 
-// what cmbpo_fakeenv_post_disagreement adds to the arguments (NULL: the instances without the feature)
-struct DisExtra {
-  float kappa_rew, kappa_cost;
-  float *rew_var, *cost_var;
-};
+// DisExtra (fakeenv_post_internal.h): what the disagreement adds to the arguments (NULL: the instances without the feature)
 // ... and cmbpo_fakeenv_post_term (th == NULL: the instances without the head, with the argument block they always had)
 template <bool RULES, bool NOISE, bool DIS>
 void launch_post_term(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsT<RULES, NOISE, DIS> &a,
@@ -461,15 +458,17 @@ void launch_post_ext(int ensemble, dim3 grid, size_t lds, hipStream_t stream, co
   launch_post_term<RULES, NOISE, true>(ensemble, grid, lds, stream, ad, th);
 }
 
-// all four entry points; `who` prefixes the messages, d_xi == NULL: the deterministic instances
-int post_impl(const char *who, int task, int ensemble, int obs_dim, int act_dim, const float *d_mean, const float *d_var, int ld_rows,
-              const float *d_obs, const float *d_act, const int32_t *d_elite, const int32_t *d_row_idx, const int32_t *d_n_rows,
-              int n_rows, float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost, float *d_dkl_path, float *d_ep_var_mean,
-              float *d_ep_var, const float *d_xi, void *stream, const DisExtra *dis = nullptr,
-              const cmbpo_term_head_t *th = nullptr) {
-  const int learned_cost = (task & CMBPO_TASK_LEARNED_COST) ? 1 : 0;     // every other bit outside the rule id is an error
-  const int task_arg = task;
-  task &= ~CMBPO_TASK_LEARNED_COST;
+}  // namespace
+
+int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream) {
+  const cmbpo_term_head_t *th = c.th;
+  const DisExtra *dis = c.dis_on ? &c.dis : nullptr;
+  // the naming rule (fakeenv_post_internal.h, DESIGN): the narrowest entry point that can express the call
+  const char *who = th ? "cmbpo_fakeenv_post_term" : dis ? "cmbpo_fakeenv_post_disagreement"
+                    : c.xi ? "cmbpo_fakeenv_post_noise" : "cmbpo_fakeenv_post";
+  const int obs_dim = c.obs_dim, act_dim = c.act_dim, ensemble = c.ensemble;
+  const int learned_cost = (c.task & CMBPO_TASK_LEARNED_COST) ? 1 : 0;     // every other bit outside the rule id is an error
+  const int task_arg = c.task, task = c.task & ~CMBPO_TASK_LEARNED_COST;
   const bool user = task >= CMBPO_TASK_USER_BASE && task < CMBPO_TASK_USER_BASE + CMBPO_TASK_USER_SLOTS;
   CMBPO_REQUIRE((task >= CMBPO_TASK_DEFAULT && task <= CMBPO_TASK_ANTSAFE) || user, "%s: bad task %d", who, task_arg);
   CMBPO_REQUIRE(ensemble >= 2 && ensemble <= kEMax, "%s: ensemble %d not in [2, %d]", who, ensemble, kEMax);
@@ -484,9 +483,8 @@ int post_impl(const char *who, int task, int ensemble, int obs_dim, int act_dim,
   }
   PostArgsRules ar{};
   if (user)     // (registered? columns inside obs_dim / act_dim? -- host code, before any HIP call)
-    if (int rc = cmbpo_internal_task_rules_resolve(who, task_arg, obs_dim, act_dim, d_act != nullptr, &ar.rules)) return rc;
-  CMBPO_REQUIRE(d_mean && d_var && d_obs && d_elite && d_next_obs && d_rew && d_term && d_cost &&
-                    d_dkl_path && d_ep_var_mean,
+    if (int rc = cmbpo_internal_task_rules_resolve(who, task_arg, obs_dim, act_dim, c.act != nullptr, &ar.rules)) return rc;
+  CMBPO_REQUIRE(c.mean && c.var && c.obs && c.elite && c.next_obs && c.rew && c.term && c.cost && c.dkl_path && c.ep_var_mean,
                 "%s: NULL buffer", who);
   if (dis != nullptr) {
     // (x >= 0 is false for a NaN; the infinities are excluded on their own)
@@ -497,30 +495,30 @@ int post_impl(const char *who, int task, int ensemble, int obs_dim, int act_dim,
                   (double)dis->kappa_cost, task_arg);
     CMBPO_REQUIRE(dis->rew_var && dis->cost_var, "%s: NULL buffer (d_rew_var / d_cost_var)", who);
   }
-  CMBPO_REQUIRE(n_rows >= 0 && ld_rows >= n_rows, "%s: n_rows %d / ld_rows %d", who, n_rows, ld_rows);
-  if (n_rows == 0) return CMBPO_OK;
+  CMBPO_REQUIRE(c.n_rows >= 0 && c.ld_rows >= c.n_rows, "%s: n_rows %d / ld_rows %d", who, c.n_rows, c.ld_rows);
+  if (c.n_rows == 0) return CMBPO_OK;
   PostArgs a{};
   a.task = task; a.ensemble = ensemble; a.obs_dim = obs_dim; a.act_dim = act_dim;
   a.out_dim = obs_dim + 1 + learned_cost + (th ? 1 : 0);  // delta-obs + reward (+ cost: algorithms/cmbpo.py:121-123, m_learn_cost) (+ the termination head's column)
   a.learned_cost = learned_cost;
-  a.mean = d_mean; a.var = d_var; a.ld_rows = ld_rows; a.obs = d_obs; a.act = d_act;
-  a.elite = d_elite; a.row_idx = d_row_idx; a.n_rows_dev = d_n_rows; a.n_rows = n_rows;
-  a.next_obs = d_next_obs; a.rew = d_rew; a.term = d_term; a.cost = d_cost;
-  a.dkl_path = d_dkl_path; a.ep_var_mean = d_ep_var_mean; a.ep_var = d_ep_var;
+  a.mean = c.mean; a.var = c.var; a.ld_rows = c.ld_rows; a.obs = c.obs; a.act = c.act;
+  a.elite = c.elite; a.row_idx = c.row_idx; a.n_rows_dev = c.n_rows_dev; a.n_rows = c.n_rows;
+  a.next_obs = c.next_obs; a.rew = c.rew; a.term = c.term; a.cost = c.cost;
+  a.dkl_path = c.dkl_path; a.ep_var_mean = c.ep_var_mean; a.ep_var = c.ep_var;
   const size_t lds = (size_t)3 * kRows * obs_dim * sizeof(float) + kRows * sizeof(int);
-  const dim3 grid(cmbpo_ceil_div(n_rows, kRows));
+  const dim3 grid(cmbpo_ceil_div(c.n_rows, kRows));
   hipStream_t s = (hipStream_t)stream;
   if (user) static_cast<PostArgs &>(ar) = a;
-  if (d_xi != nullptr) {
+  if (c.xi != nullptr) {
     if (user) {
       PostArgsRulesNoise an{};
       static_cast<PostArgsRules &>(an) = ar;
-      an.xi = d_xi;
+      an.xi = c.xi;
       launch_post_ext<true, true>(ensemble, grid, lds, s, an, dis, th);
     } else {
       PostArgsNoise an{};
       static_cast<PostArgs &>(an) = a;
-      an.xi = d_xi;
+      an.xi = c.xi;
       launch_post_ext<false, true>(ensemble, grid, lds, s, an, dis, th);
     }
   } else if (user) launch_post_ext<true, false>(ensemble, grid, lds, s, ar, dis, th);
@@ -529,71 +527,60 @@ int post_impl(const char *who, int task, int ensemble, int obs_dim, int act_dim,
   return CMBPO_OK;
 }
 
-}  // namespace
+// The four public entry points fill the descriptor and make that call; none forwards to another.  POST_COMMON: the 20 leading
+// parameters they share (the stream goes beside the descriptor).
+#define POST_COMMON                                                                                                              \
+  int task, int ensemble, int obs_dim, int act_dim, const float *d_mean, const float *d_var, int ld_rows, const float *d_obs,    \
+      const float *d_act, const int32_t *d_elite, const int32_t *d_row_idx, const int32_t *d_n_rows, int n_rows, float *d_next_obs, \
+      float *d_rew, uint8_t *d_term, float *d_cost, float *d_dkl_path, float *d_ep_var_mean, float *d_ep_var
+#define POST_COMMON_ARGS                                                                                                        \
+  task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite, d_row_idx, d_n_rows, n_rows, d_next_obs, d_rew, \
+      d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var
 
-extern "C" int cmbpo_fakeenv_post(int task, int ensemble, int obs_dim, int act_dim,
-                                  const float *d_mean, const float *d_var, int ld_rows,
-                                  const float *d_obs, const float *d_act, const int32_t *d_elite,
-                                  const int32_t *d_row_idx, const int32_t *d_n_rows, int n_rows,
-                                  float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost,
-                                  float *d_dkl_path, float *d_ep_var_mean, float *d_ep_var,
-                                  void *stream) {
-  return post_impl("cmbpo_fakeenv_post", task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite, d_row_idx,
-                   d_n_rows, n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, nullptr, stream);
+static FakeenvPostCall post_common(POST_COMMON) {
+  FakeenvPostCall c{};      // (every feature off)
+  c.task = task; c.ensemble = ensemble; c.obs_dim = obs_dim; c.act_dim = act_dim;
+  c.mean = d_mean; c.var = d_var; c.ld_rows = ld_rows; c.obs = d_obs; c.act = d_act;
+  c.elite = d_elite; c.row_idx = d_row_idx; c.n_rows_dev = d_n_rows; c.n_rows = n_rows;
+  c.next_obs = d_next_obs; c.rew = d_rew; c.term = d_term; c.cost = d_cost;
+  c.dkl_path = d_dkl_path; c.ep_var_mean = d_ep_var_mean; c.ep_var = d_ep_var;
+  return c;
+}
+
+extern "C" int cmbpo_fakeenv_post(POST_COMMON, void *stream) {
+  return cmbpo_internal_fakeenv_post(post_common(POST_COMMON_ARGS), stream);
 }
 
 // ... with stochastic transitions: next_obs = mean + std * xi + obs (see the kernel); d_xi == NULL is cmbpo_fakeenv_post
-extern "C" int cmbpo_fakeenv_post_noise(int task, int ensemble, int obs_dim, int act_dim,
-                                        const float *d_mean, const float *d_var, int ld_rows,
-                                        const float *d_obs, const float *d_act, const int32_t *d_elite,
-                                        const int32_t *d_row_idx, const int32_t *d_n_rows, int n_rows,
-                                        float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost,
-                                        float *d_dkl_path, float *d_ep_var_mean, float *d_ep_var,
-                                        const float *d_xi, void *stream) {
-  if (d_xi == nullptr)
-    return cmbpo_fakeenv_post(task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite, d_row_idx, d_n_rows,
-                              n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, stream);
-  return post_impl("cmbpo_fakeenv_post_noise", task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite,
-                   d_row_idx, d_n_rows, n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, d_xi, stream);
+extern "C" int cmbpo_fakeenv_post_noise(POST_COMMON, const float *d_xi, void *stream) {
+  FakeenvPostCall c = post_common(POST_COMMON_ARGS);
+  c.xi = d_xi;
+  return cmbpo_internal_fakeenv_post(c, stream);
 }
 
 // ... with the ensemble's disagreement on the reward and the learned-cost column measured, and the pessimistic reward / cost made
-// from it (see the kernel's DIS parts and the header); d_xi may be NULL: the deterministic transition
-extern "C" int cmbpo_fakeenv_post_disagreement(int task, int ensemble, int obs_dim, int act_dim,
-                                               const float *d_mean, const float *d_var, int ld_rows,
-                                               const float *d_obs, const float *d_act, const int32_t *d_elite,
-                                               const int32_t *d_row_idx, const int32_t *d_n_rows, int n_rows,
-                                               float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost,
-                                               float *d_dkl_path, float *d_ep_var_mean, float *d_ep_var,
-                                               const float *d_xi, float kappa_rew, float kappa_cost,
-                                               float *d_rew_var, float *d_cost_var, void *stream) {
-  const DisExtra dis{kappa_rew, kappa_cost, d_rew_var, d_cost_var};
-  return post_impl("cmbpo_fakeenv_post_disagreement", task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite,
-                   d_row_idx, d_n_rows, n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, d_xi, stream,
-                   &dis);
+// from it (see the kernel's DIS parts and the header); d_xi may be NULL: the deterministic transition.  Always on here: NULL
+// variance buffers are refused under this entry's name.
+extern "C" int cmbpo_fakeenv_post_disagreement(POST_COMMON, const float *d_xi, float kappa_rew, float kappa_cost, float *d_rew_var,
+                                               float *d_cost_var, void *stream) {
+  FakeenvPostCall c = post_common(POST_COMMON_ARGS);
+  c.xi = d_xi;
+  c.dis_on = true;
+  c.dis = DisExtra{kappa_rew, kappa_cost, d_rew_var, d_cost_var};
+  return cmbpo_internal_fakeenv_post(c, stream);
 }
 
-// ... with the learned termination head (see the kernel's TERM parts and the header); th == NULL: the entry points above
-extern "C" int cmbpo_fakeenv_post_term(int task, int ensemble, int obs_dim, int act_dim,
-                                       const float *d_mean, const float *d_var, int ld_rows,
-                                       const float *d_obs, const float *d_act, const int32_t *d_elite,
-                                       const int32_t *d_row_idx, const int32_t *d_n_rows, int n_rows,
-                                       float *d_next_obs, float *d_rew, uint8_t *d_term, float *d_cost,
-                                       float *d_dkl_path, float *d_ep_var_mean, float *d_ep_var,
-                                       const float *d_xi, float kappa_rew, float kappa_cost,
-                                       float *d_rew_var, float *d_cost_var, const cmbpo_term_head_t *th, void *stream) {
-  // (kappa != 0 is true for a NaN: the disagreement path's own check names it)
-  const bool with_dis = d_rew_var != nullptr || d_cost_var != nullptr || kappa_rew != 0.0f || kappa_cost != 0.0f;
-  if (th == nullptr) {
-    if (with_dis)
-      return cmbpo_fakeenv_post_disagreement(task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite, d_row_idx,
-                                             d_n_rows, n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var,
-                                             d_xi, kappa_rew, kappa_cost, d_rew_var, d_cost_var, stream);
-    return cmbpo_fakeenv_post_noise(task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite, d_row_idx, d_n_rows,
-                                    n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, d_xi, stream);
-  }
-  const DisExtra dis{kappa_rew, kappa_cost, d_rew_var, d_cost_var};
-  return post_impl("cmbpo_fakeenv_post_term", task, ensemble, obs_dim, act_dim, d_mean, d_var, ld_rows, d_obs, d_act, d_elite, d_row_idx,
-                   d_n_rows, n_rows, d_next_obs, d_rew, d_term, d_cost, d_dkl_path, d_ep_var_mean, d_ep_var, d_xi, stream,
-                   with_dis ? &dis : nullptr, th);
+// ... with the learned termination head (see the kernel's TERM parts and the header): the superset -- every feature is optional
+extern "C" int cmbpo_fakeenv_post_term(POST_COMMON, const float *d_xi, float kappa_rew, float kappa_cost, float *d_rew_var,
+                                       float *d_cost_var, const cmbpo_term_head_t *th, void *stream) {
+  FakeenvPostCall c = post_common(POST_COMMON_ARGS);
+  c.xi = d_xi;
+  // (kappa != 0 is true for a NaN: the disagreement's own check names it)
+  c.dis_on = d_rew_var != nullptr || d_cost_var != nullptr || kappa_rew != 0.0f || kappa_cost != 0.0f;
+  c.dis = DisExtra{kappa_rew, kappa_cost, d_rew_var, d_cost_var};
+  c.th = th;
+  return cmbpo_internal_fakeenv_post(c, stream);
 }
+
+#undef POST_COMMON
+#undef POST_COMMON_ARGS

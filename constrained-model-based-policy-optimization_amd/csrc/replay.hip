@@ -11,6 +11,7 @@
 // Sums are float64, counts int64, every addition in a fixed order (no floating-point atomics): two runs are bitwise equal.
 #include "common.h"
 #include "ens_mlp_internal.h"
+#include "fakeenv_post_internal.h"
 
 namespace {
 
@@ -447,35 +448,67 @@ int refused_by(const char *who, int rc) {
   return rc;
 }
 
-// cmbpo_replay_run (cal == nullptr: exactly its launches) and cmbpo_replay_run_calibrated (the calibrate kernel between post and
-// compare, its finish behind the plain one); every argument has been checked by the caller
+// the steps of a run: cal == nullptr is exactly cmbpo_replay_run's launches, else the calibrate kernel goes between post and
+// compare and its finish behind the plain one; th != nullptr: the head's instances of the post kernel.  Every argument has been
+// checked by the caller.
 int run_steps(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *cal, cmbpo_mlp_t *model, int task, int ensemble,
-              const int32_t *d_elite, void *stream, const cmbpo_term_head_t *th = nullptr) {
+              const int32_t *d_elite, const cmbpo_term_head_t *th, void *stream) {
   const int B = rp->B, D = rp->obs_dim, A = rp->act_dim;
-  // the post step: th == NULL is cmbpo_fakeenv_post itself (cmbpo_fakeenv_post_term forwards), else the head's instances
-  auto post = [&](const float *act_h, const int32_t *elite_h, int n) {
-    if (th == nullptr)
-      return cmbpo_fakeenv_post(task, ensemble, D, A, rp->mean, rp->var, B, rp->cur_obs, act_h, elite_h, nullptr, nullptr, n,
-                                rp->p_next_obs, rp->p_rew, rp->p_term, rp->p_cost, rp->p_dkl_path, rp->p_ep_var_mean, nullptr, stream);
-    return cmbpo_fakeenv_post_term(task, ensemble, D, A, rp->mean, rp->var, B, rp->cur_obs, act_h, elite_h, nullptr, nullptr, n,
-                                   rp->p_next_obs, rp->p_rew, rp->p_term, rp->p_cost, rp->p_dkl_path, rp->p_ep_var_mean, nullptr, nullptr,
-                                   0.0f, 0.0f, nullptr, nullptr, th, stream);
-  };
+  // the post step; act, elite and n_rows follow the horizon
+  FakeenvPostCall pc{};
+  pc.task = task; pc.ensemble = ensemble; pc.obs_dim = D; pc.act_dim = A;
+  pc.mean = rp->mean; pc.var = rp->var; pc.ld_rows = B; pc.obs = rp->cur_obs;
+  pc.next_obs = rp->p_next_obs; pc.rew = rp->p_rew; pc.term = rp->p_term; pc.cost = rp->p_cost;
+  pc.dkl_path = rp->p_dkl_path; pc.ep_var_mean = rp->p_ep_var_mean;
+  pc.th = th;
   // the two callees' own argument checks, on a call of no rows (neither launches anything for it)
   if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, rp->act, A, nullptr, nullptr, 0, B, rp->mean, rp->var, stream))
     return refused_by(who, rc);
-  if (int rc = post(rp->act, d_elite, 0)) return refused_by(who, rc);
+  pc.act = rp->act; pc.elite = d_elite; pc.n_rows = 0;
+  if (int rc = cmbpo_internal_fakeenv_post(pc, stream)) return refused_by(who, rc);
   for (int h = 0; h < rp->H; ++h) {
     const float *act_h = rp->act ? rp->act + (size_t)h * B * A : nullptr;
     if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, act_h, A, nullptr, nullptr, B, B, rp->mean, rp->var, stream))
       return refused_by(who, rc);
-    if (int rc = post(act_h, d_elite + (size_t)h * B, B)) return refused_by(who, rc);
+    pc.act = act_h; pc.elite = d_elite + (size_t)h * B; pc.n_rows = B;
+    if (int rc = cmbpo_internal_fakeenv_post(pc, stream)) return refused_by(who, rc);
     if (cal)
       if (int rc = launch_calibrate(rp, cal, h, (hipStream_t)stream)) return rc;
     if (int rc = launch_compare(rp, h, (hipStream_t)stream)) return rc;
   }
   if (int rc = launch_finish(rp, (hipStream_t)stream)) return rc;
   return cal ? launch_calib_finish(rp, cal, (hipStream_t)stream) : CMBPO_OK;
+}
+
+// The three run entry points: ONE check list, keyed on which of rc (calibration) and th (termination head) are given.  The
+// messages carry the name of the narrowest entry point that can express the call (DESIGN): th given -- cmbpo_replay_run_term,
+// else rc given -- cmbpo_replay_run_calibrated, else cmbpo_replay_run.  Where the entry points have always differed in the order
+// or the wording of a check, each combination keeps its own.
+int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th, cmbpo_mlp_t *model, int task,
+               int ensemble, const int32_t *d_elite, void *stream) {
+  const char *who = th ? "cmbpo_replay_run_term" : rc ? "cmbpo_replay_run_calibrated" : "cmbpo_replay_run";
+  if (int r = rc ? check_calibrate(who, rp, rc) : check_compare(who, rp)) return r;      // (check_calibrate: mean / var as well)
+  if (int r = check_finish(who, rp)) return r;
+  if (rc)
+    if (int r = check_calib_finish(who, rp, rc)) return r;
+  CMBPO_REQUIRE(model != nullptr, "%s: model handle is NULL", who);
+  if (!rc && !th) CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);     // (the plain run names it before act)
+  if (rc && !th) CMBPO_REQUIRE(rp->act_dim == 0 || rp->act, "%s: NULL buffer (act)", who);
+  else CMBPO_REQUIRE((rp->act_dim == 0 || rp->act) && rp->mean && rp->var, "%s: NULL buffer (act / mean / var)", who);
+  if (rc) {
+    CMBPO_REQUIRE(ensemble == rc->ensemble, "%s: ensemble %d, the calibration descriptor's is %d", who, ensemble, rc->ensemble);
+    // (cmbpo_replay_run_calibrated has no d_elite; without a head cmbpo_replay_run_term has always ignored its own)
+    if (th) CMBPO_REQUIRE(d_elite == nullptr || d_elite == rc->elite, "%s: d_elite differs from the calibration descriptor's elite", who);
+    d_elite = rc->elite;
+  }
+  if (th) {
+    CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);
+    const int want = rp->obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0) + 1;
+    CMBPO_REQUIRE(model->out_dim == want,
+                  "%s: termination head (cmbpo_term_head_t): model out_dim %d does not match obs_dim %d + 1 (+ 1 with CMBPO_TASK_LEARNED_COST) "
+                  "+ 1 for the head's column, task 0x%x", who, model->out_dim, rp->obs_dim, task);
+  }
+  return run_steps(who, rp, rc, model, task, ensemble, d_elite, th, stream);
 }
 
 }  // namespace
@@ -496,13 +529,7 @@ extern "C" int cmbpo_replay_finish(const cmbpo_replay_t *rp, void *stream) {
 
 extern "C" int cmbpo_replay_run(const cmbpo_replay_t *rp, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite,
                                 void *stream) {
-  const char *who = "cmbpo_replay_run";
-  if (int rc = check_compare(who, rp)) return rc;
-  if (int rc = check_finish(who, rp)) return rc;
-  CMBPO_REQUIRE(model != nullptr, "%s: model handle is NULL", who);
-  CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);
-  CMBPO_REQUIRE((rp->act_dim == 0 || rp->act) && rp->mean && rp->var, "%s: NULL buffer (act / mean / var)", who);
-  return run_steps(who, rp, nullptr, model, task, ensemble, d_elite, stream);
+  return replay_run(rp, nullptr, nullptr, model, task, ensemble, d_elite, stream);
 }
 
 extern "C" int cmbpo_replay_calibrate(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, int h, void *stream) {
@@ -519,37 +546,11 @@ extern "C" int cmbpo_replay_calib_finish(const cmbpo_replay_t *rp, const cmbpo_r
 
 extern "C" int cmbpo_replay_run_calibrated(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, cmbpo_mlp_t *model, int task,
                                            int ensemble, void *stream) {
-  const char *who = "cmbpo_replay_run_calibrated";
-  if (int r = check_calibrate(who, rp, rc)) return r;
-  if (int r = check_finish(who, rp)) return r;
-  if (int r = check_calib_finish(who, rp, rc)) return r;
-  CMBPO_REQUIRE(model != nullptr, "%s: model handle is NULL", who);
-  CMBPO_REQUIRE(rp->act_dim == 0 || rp->act, "%s: NULL buffer (act)", who);
-  CMBPO_REQUIRE(ensemble == rc->ensemble, "%s: ensemble %d, the calibration descriptor's is %d", who, ensemble, rc->ensemble);
-  return run_steps(who, rp, rc, model, task, ensemble, rc->elite, stream);
+  if (rc == nullptr) return check_calibrate("cmbpo_replay_run_calibrated", rp, rc);      // (this entry's own error, not the plain run)
+  return replay_run(rp, rc, nullptr, model, task, ensemble, nullptr, stream);
 }
-
 
 extern "C" int cmbpo_replay_run_term(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th,
                                      cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream) {
-  const char *who = "cmbpo_replay_run_term";
-  if (th == nullptr)
-    return rc ? cmbpo_replay_run_calibrated(rp, rc, model, task, ensemble, stream) : cmbpo_replay_run(rp, model, task, ensemble, d_elite, stream);
-  if (int r = rc ? check_calibrate(who, rp, rc) : check_compare(who, rp)) return r;
-  if (int r = check_finish(who, rp)) return r;
-  if (rc)
-    if (int r = check_calib_finish(who, rp, rc)) return r;
-  CMBPO_REQUIRE(model != nullptr, "%s: model handle is NULL", who);
-  CMBPO_REQUIRE((rp->act_dim == 0 || rp->act) && rp->mean && rp->var, "%s: NULL buffer (act / mean / var)", who);
-  if (rc) {
-    CMBPO_REQUIRE(ensemble == rc->ensemble, "%s: ensemble %d, the calibration descriptor's is %d", who, ensemble, rc->ensemble);
-    CMBPO_REQUIRE(d_elite == nullptr || d_elite == rc->elite, "%s: d_elite differs from the calibration descriptor's elite", who);
-    d_elite = rc->elite;
-  }
-  CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);
-  const int want = rp->obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0) + 1;
-  CMBPO_REQUIRE(model->out_dim == want,
-                "%s: termination head (cmbpo_term_head_t): model out_dim %d does not match obs_dim %d + 1 (+ 1 with CMBPO_TASK_LEARNED_COST) "
-                "+ 1 for the head's column, task 0x%x", who, model->out_dim, rp->obs_dim, task);
-  return run_steps(who, rp, rc, model, task, ensemble, d_elite, stream, th);
+  return replay_run(rp, rc, th, model, task, ensemble, d_elite, stream);
 }

@@ -1306,23 +1306,13 @@ int check_rollout(const cmbpo_rollout_t *r, const char *who) {
 std::mutex g_side_mu;
 std::unordered_map<const void *, RolloutSide> g_side;
 
-// attach (feature != NULL: replaces what was attached) or detach one feature; an entry with neither left is dropped
-template <typename F>
-void side_set(const cmbpo_rollout_t *r, F RolloutSide::*which, const F *feature) {
+// every attach and detach: take the lock, find or create the entry, apply the change (an attach replaces what was attached, a
+// detach leaves the feature all-zero), drop the entry when nothing is attached any more
+template <typename Change>
+void side_update(const cmbpo_rollout_t *r, Change change) {
   std::lock_guard<std::mutex> lock(g_side_mu);
-  if (feature == nullptr && g_side.find(r->iscal) == g_side.end()) return;
   RolloutSide &sd = g_side[r->iscal];
-  sd.*which = feature ? *feature : F{};
-  if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr && sd.vd.part == nullptr && !sd.th_on) g_side.erase(r->iscal);
-}
-
-// the termination head: no kernel of this file reads it (the one-call step hands it to the post kernel)
-void side_set_term(const cmbpo_rollout_t *r, const cmbpo_term_head_t *th) {
-  std::lock_guard<std::mutex> lock(g_side_mu);
-  if (th == nullptr && g_side.find(r->iscal) == g_side.end()) return;
-  RolloutSide &sd = g_side[r->iscal];
-  sd.th = th ? *th : cmbpo_term_head_t{};
-  sd.th_on = th ? 1 : 0;
+  change(sd);
   if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr && sd.vd.part == nullptr && !sd.th_on) g_side.erase(r->iscal);
 }
 
@@ -1347,13 +1337,13 @@ extern "C" int cmbpo_rollout_disagreement_attach(const cmbpo_rollout_t *r, const
   CMBPO_REQUIRE(dg->kappa_rew >= 0.0f && isfinite(dg->kappa_rew) && dg->kappa_cost >= 0.0f && isfinite(dg->kappa_cost),
                 "cmbpo_rollout_disagreement_attach: kappa_rew %g / kappa_cost %g: finite numbers >= 0", (double)dg->kappa_rew,
                 (double)dg->kappa_cost);
-  side_set(r, &RolloutSide::dg, dg);
+  side_update(r, [&](RolloutSide &sd) { sd.dg = *dg; });
   return CMBPO_OK;
 }
 
 extern "C" int cmbpo_rollout_disagreement_detach(const cmbpo_rollout_t *r) {
   CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_disagreement_detach: NULL rollout struct / iscal");
-  side_set<cmbpo_disagreement_t>(r, &RolloutSide::dg, nullptr);
+  side_update(r, [](RolloutSide &sd) { sd.dg = {}; });
   return CMBPO_OK;
 }
 
@@ -1366,13 +1356,13 @@ extern "C" int cmbpo_rollout_value_disagreement_attach(const cmbpo_rollout_t *r,
   CMBPO_REQUIRE(vd->kappa_v >= 0.0f && isfinite(vd->kappa_v) && vd->kappa_vc >= 0.0f && isfinite(vd->kappa_vc),
                 "cmbpo_rollout_value_disagreement_attach: kappa_v %g / kappa_vc %g: finite numbers >= 0", (double)vd->kappa_v,
                 (double)vd->kappa_vc);
-  side_set(r, &RolloutSide::vd, vd);
+  side_update(r, [&](RolloutSide &sd) { sd.vd = *vd; });
   return CMBPO_OK;
 }
 
 extern "C" int cmbpo_rollout_value_disagreement_detach(const cmbpo_rollout_t *r) {
   CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_value_disagreement_detach: NULL rollout struct / iscal");
-  side_set<cmbpo_value_disagreement_t>(r, &RolloutSide::vd, nullptr);
+  side_update(r, [](RolloutSide &sd) { sd.vd = {}; });
   return CMBPO_OK;
 }
 
@@ -1383,13 +1373,13 @@ extern "C" int cmbpo_rollout_term_head_attach(const cmbpo_rollout_t *r, const cm
                 (double)th->threshold);
   CMBPO_REQUIRE(th->members >= CMBPO_TERM_ELITE && th->members <= CMBPO_TERM_MAJORITY,
                 "cmbpo_rollout_term_head_attach: termination head: members %d not in 0..2 (CMBPO_TERM_ELITE / _ANY / _MAJORITY)", th->members);
-  side_set_term(r, th);
+  side_update(r, [&](RolloutSide &sd) { sd.th = *th; sd.th_on = 1; });      // (no kernel of this file reads it: the one-call step hands it to the post kernel)
   return CMBPO_OK;
 }
 
 extern "C" int cmbpo_rollout_term_head_detach(const cmbpo_rollout_t *r) {
   CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_term_head_detach: NULL rollout struct / iscal");
-  side_set_term(r, nullptr);
+  side_update(r, [](RolloutSide &sd) { sd.th = {}; sd.th_on = 0; });
   return CMBPO_OK;
 }
 
@@ -1399,13 +1389,13 @@ extern "C" int cmbpo_rollout_iv_attach(const cmbpo_rollout_t *r, const cmbpo_iv_
   CMBPO_REQUIRE(iv->cumvar_buf != nullptr, "cmbpo_rollout_iv_attach: NULL cumvar_buf (cmbpo_rollout_iv_detach switches the feature off)");
   CMBPO_REQUIRE(iv->lam_vec && iv->lam_pow && iv->clam_vec && iv->clam_pow, "cmbpo_rollout_iv_attach: NULL lambda table");
   CMBPO_REQUIRE(isfinite(iv->eps) && iv->eps > 0.0, "cmbpo_rollout_iv_attach: eps %g is not a positive finite number", iv->eps);
-  side_set(r, &RolloutSide::iv, iv);
+  side_update(r, [&](RolloutSide &sd) { sd.iv = *iv; });
   return CMBPO_OK;
 }
 
 extern "C" int cmbpo_rollout_iv_detach(const cmbpo_rollout_t *r) {
   CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_iv_detach: NULL rollout struct / iscal");
-  side_set<cmbpo_iv_gae_t>(r, &RolloutSide::iv, nullptr);
+  side_update(r, [](RolloutSide &sd) { sd.iv = {}; });
   return CMBPO_OK;
 }
 

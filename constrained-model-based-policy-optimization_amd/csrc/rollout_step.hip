@@ -5,6 +5,7 @@
 // Every buffer is a field of the rollout struct; nothing here adds arithmetic.
 #include "common.h"
 #include "ens_mlp_internal.h"
+#include "fakeenv_post_internal.h"
 #include "rollout_internal.h"
 
 #include <string.h>
@@ -64,30 +65,18 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   if ((rc = cmbpo_ens_forward(model, r->cur_obs, r->obs_dim, r->act_t, r->act_dim, r->alive_idx, d_n, n_alive, r->B,
                               d_mean, d_var, stream)))
     return rc;
-  const cmbpo_disagreement_t &dg = sd.dg;
-  // the termination head: its instances of the post kernel, with or without the disagreement and the draws
-  if (sd.th_on) {
-    const bool dis = dg.part != nullptr;
-    if ((rc = cmbpo_fakeenv_post_term(task, ensemble, r->obs_dim, r->act_dim, d_mean, d_var, r->B, r->cur_obs, r->act_t, d_elite,
-                                      r->alive_idx, d_n, n_alive, w(r->next_obs), w(r->rew_t), const_cast<uint8_t *>(r->term_t),
-                                      w(r->cost_t), w(r->dkl_t), w(r->epv_t), nullptr, d_xi, dis ? dg.kappa_rew : 0.0f,
-                                      dis ? dg.kappa_cost : 0.0f, dis ? dg.rew_var_t : nullptr, dis ? dg.cost_var_t : nullptr, &sd.th,
-                                      stream)))
-      return rc;
-  } else
-  // ensemble disagreement: its instance of the post kernel, penalised rew_t / cost_t (d_xi may be NULL)
-  if (dg.part != nullptr) {
-    if ((rc = cmbpo_fakeenv_post_disagreement(task, ensemble, r->obs_dim, r->act_dim, d_mean, d_var, r->B, r->cur_obs, r->act_t, d_elite,
-                                              r->alive_idx, d_n, n_alive, w(r->next_obs), w(r->rew_t), const_cast<uint8_t *>(r->term_t),
-                                              w(r->cost_t), w(r->dkl_t), w(r->epv_t), nullptr, d_xi, dg.kappa_rew, dg.kappa_cost,
-                                              dg.rew_var_t, dg.cost_var_t, stream)))
-      return rc;
-  } else
-  // (d_xi == NULL: cmbpo_fakeenv_post, the deterministic transition)
-  if ((rc = cmbpo_fakeenv_post_noise(task, ensemble, r->obs_dim, r->act_dim, d_mean, d_var, r->B, r->cur_obs, r->act_t, d_elite,
-                                     r->alive_idx, d_n, n_alive, w(r->next_obs), w(r->rew_t), const_cast<uint8_t *>(r->term_t),
-                                     w(r->cost_t), w(r->dkl_t), w(r->epv_t), nullptr, d_xi, stream)))
-    return rc;
+  // the post step, with what is attached beside *r (disagreement, termination head) and the draws (d_xi may be NULL)
+  FakeenvPostCall pc{};
+  pc.task = task; pc.ensemble = ensemble; pc.obs_dim = r->obs_dim; pc.act_dim = r->act_dim;
+  pc.mean = d_mean; pc.var = d_var; pc.ld_rows = r->B; pc.obs = r->cur_obs; pc.act = r->act_t;
+  pc.elite = d_elite; pc.row_idx = r->alive_idx; pc.n_rows_dev = d_n; pc.n_rows = n_alive;
+  pc.next_obs = w(r->next_obs); pc.rew = w(r->rew_t); pc.term = const_cast<uint8_t *>(r->term_t); pc.cost = w(r->cost_t);
+  pc.dkl_path = w(r->dkl_t); pc.ep_var_mean = w(r->epv_t);
+  pc.xi = d_xi;
+  pc.dis_on = sd.dg.part != nullptr;
+  pc.dis = DisExtra{sd.dg.kappa_rew, sd.dg.kappa_cost, sd.dg.rew_var_t, sd.dg.cost_var_t};
+  pc.th = sd.th_on ? &sd.th : nullptr;
+  if ((rc = cmbpo_internal_fakeenv_post(pc, stream))) return rc;
   const bool small = ahead.on || (n_alive <= cmbpo_rollout_book_pre_max_rows() && !r->use_host_budget);
   // small batches: decide + finish(PRE) + the store's scalar half in one launch; its vector half (obs, act, mu, log_std) rides
   // in the critics' launch below where that is the one-wave-per-member kernel (8 us as a launch of its own at 1000 rows)

@@ -175,28 +175,16 @@ class FakeEnv:
         if ev is not None:
             ev[1].record()
             self.kernel_events.append((ev[0], ev[1], n))
-        post = (self._task_id, E, self.obs_dim, self.act_dim, _lib.ptr(mean),
-                _lib.ptr(var), B, _lib.ptr(obs), _lib.ptr(act),
-                _lib.ptr(model_inds), _lib.ptr(row_idx), None, n,
-                _lib.ptr(out["next_obs"]), _lib.ptr(out["rew"]),
-                _lib.ptr(out["term"]), _lib.ptr(out["cost"]),
-                _lib.ptr(out["dkl_path"]), _lib.ptr(out["ep_var_mean"]),
-                _lib.ptr(out.get("ep_var")))
-        if self._predicts_term:
-            dis = self.disagreement
-            th = self.term_head_struct(out.get("term_pred"), out.get("term_votes"))
-            _lib.check(lib.cmbpo_fakeenv_post_term(*post, _lib.ptr(noise), self.rew_pessimism if dis else 0.0,
-                                                   self.cost_pessimism if dis else 0.0, _lib.ptr(out["rew_var"]) if dis else None,
-                                                   _lib.ptr(out["cost_var"]) if dis else None, C.byref(th), stream),
-                       "cmbpo_fakeenv_post_term")
-        elif self.disagreement:
-            _lib.check(lib.cmbpo_fakeenv_post_disagreement(*post, _lib.ptr(noise), self.rew_pessimism, self.cost_pessimism,
-                                                           _lib.ptr(out["rew_var"]), _lib.ptr(out["cost_var"]), stream),
-                       "cmbpo_fakeenv_post_disagreement")
-        elif noise is None:
-            _lib.check(lib.cmbpo_fakeenv_post(*post, stream), "cmbpo_fakeenv_post")
-        else:
-            _lib.check(lib.cmbpo_fakeenv_post_noise(*post, _lib.ptr(noise), stream), "cmbpo_fakeenv_post_noise")
+        # one call of the superset entry point, NULL / 0 for what is off (the library's message names the narrowest entry)
+        dis = (self.rew_pessimism, self.cost_pessimism, _lib.ptr(out["rew_var"]), _lib.ptr(out["cost_var"])) \
+            if self.disagreement else (0.0, 0.0, None, None)
+        th = self.term_head_struct(out.get("term_pred"), out.get("term_votes"))
+        _lib.check(lib.cmbpo_fakeenv_post_term(
+            self._task_id, E, self.obs_dim, self.act_dim, _lib.ptr(mean), _lib.ptr(var), B, _lib.ptr(obs), _lib.ptr(act),
+            _lib.ptr(model_inds), _lib.ptr(row_idx), None, n, _lib.ptr(out["next_obs"]), _lib.ptr(out["rew"]),
+            _lib.ptr(out["term"]), _lib.ptr(out["cost"]), _lib.ptr(out["dkl_path"]), _lib.ptr(out["ep_var_mean"]),
+            _lib.ptr(out.get("ep_var")), _lib.ptr(noise), *dis, C.byref(th) if th is not None else None, stream),
+            "cmbpo_fakeenv_post_term")
         return out
 
     def step(self, obs, act, deterministic=True, model_inds=None, noise=None):

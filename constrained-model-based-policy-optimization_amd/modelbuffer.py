@@ -39,6 +39,7 @@ returned sample, ``ref_var / (ref_var + accumulated variance)`` from the same ``
 no variance, 1/2 at ``ref_var``; with ``ref_var = iv_eps`` proportional to the GAE's own weight) -- for the weighted policy and
 critic updates.  What ``get()`` returns is unchanged.
 """
+import collections
 import ctypes as C
 import weakref
 
@@ -64,16 +65,77 @@ def iv_tables(lam, T):
     return vec, np.array([lam ** L for L in range(int(T) + 1)], np.float64)
 
 
+def _iv_fill(buf, iv):
+    """The weighted GAE's struct: the accumulated variance, eps, and the four lambda tables -- rewritten in place (same
+    addresses: ordered on the stream behind the kernels that read the old values) whenever the lambdas may have changed."""
+    t, T = buf.t, buf.max_path_length
+    t["iv_tables"].copy_(torch.from_numpy(np.concatenate(iv_tables(buf.lam, T) + iv_tables(buf.cost_lam, T))))
+    base = t["iv_tables"].data_ptr()
+    iv.cumvar_buf = t["cumvar_buf"].data_ptr()
+    iv.lam_vec, iv.lam_pow = base, base + 8 * T
+    iv.clam_vec, iv.clam_pow = base + 8 * (2 * T + 1), base + 8 * (3 * T + 1)
+    iv.eps = buf.iv_eps
+
+
+def _dis_fill(buf, dg):
+    t = buf.t
+    dg.kappa_rew, dg.kappa_cost = buf.rew_pessimism, buf.cost_pessimism
+    dg.rew_var_t, dg.cost_var_t = t["rew_var_t"].data_ptr(), t["cost_var_t"].data_ptr()
+    dg.path_rew_var, dg.path_cost_var = t["path_rew_var"].data_ptr(), t["path_cost_var"].data_ptr()
+    dg.part = t["dis_part"].data_ptr()
+
+
+def _vdis_fill(buf, vd):
+    t = buf.t
+    vd.kappa_v, vd.kappa_vc = buf.v_pessimism, buf.vc_pessimism
+    vd.v_var, vd.vc_var = t["v_var"].data_ptr(), t["vc_var"].data_ptr()
+    vd.part = t["vdis_part"].data_ptr()
+
+
+def _term_fill(buf, th):
+    t = buf.t
+    th.threshold, th.members = buf.term_head[0], _lib.TERM_MEMBERS[buf.term_head[1]]
+    th.term_pred, th.term_votes = t["term_pred_t"].data_ptr(), t["term_votes_t"].data_ptr()
+
+
+# The features kept beside the rollout struct, in the order they are attached: is it on, the arrays it owns in ``self.t``
+# ((name, shape, dtype) for capacity B and horizon T: allocated zeroed when it is switched on, freed when it is switched off), its
+# struct and how to fill it, the entry points that attach and detach it.  The next feature is one more row.
+_Side = collections.namedtuple("_Side", "on arrays struct fill attach detach")
+_part = lambda B: ((B + 63) // 64) * 2      # scratch of a step's two totals, per 64 branches
+_SIDE = {
+    "iv": _Side(lambda buf: buf.iv_gae,
+                lambda B, T: (("cumvar_buf", (T, B), torch.float64), ("iv_tables", (4 * T + 2,), torch.float64)),
+                _lib.IvGaeStruct, _iv_fill, "cmbpo_rollout_iv_attach", "cmbpo_rollout_iv_detach"),
+    "dis": _Side(lambda buf: buf.disagreement,
+                 lambda B, T: (("rew_var_t", (B,), torch.float32), ("cost_var_t", (B,), torch.float32),
+                               ("path_rew_var", (B,), torch.float64), ("path_cost_var", (B,), torch.float64),
+                               ("dis_part", (_part(B),), torch.float64)),
+                 _lib.DisagreementStruct, _dis_fill, "cmbpo_rollout_disagreement_attach", "cmbpo_rollout_disagreement_detach"),
+    "vdis": _Side(lambda buf: buf.value_disagreement,
+                  lambda B, T: (("v_var", (B,), torch.float32), ("vc_var", (B,), torch.float32),
+                                ("vdis_part", (_part(B),), torch.float64)),
+                  _lib.ValueDisagreementStruct, _vdis_fill, "cmbpo_rollout_value_disagreement_attach",
+                  "cmbpo_rollout_value_disagreement_detach"),
+    "term": _Side(lambda buf: buf.term_head is not None,
+                  lambda B, T: (("term_pred_t", (B,), torch.float32), ("term_votes_t", (B,), torch.uint8)),
+                  _lib.TermHeadStruct, _term_fill, "cmbpo_rollout_term_head_attach", "cmbpo_rollout_term_head_detach"),
+}
+
+
+def _detach_all(rs):
+    """Drop whatever the library's table holds under this struct's key (its iscal)."""
+    for side in _SIDE.values():
+        _lib.check(getattr(_lib.lib(), side.detach)(C.byref(rs)), side.detach)
+
+
 def _iv_release(key):
     """Finaliser of a buffer: no entry of the library's tables may outlive the arrays it points to."""
     try:
         if key[0]:
             rs = RolloutStruct()
             rs.iscal = key[0]
-            _lib.lib().cmbpo_rollout_iv_detach(C.byref(rs))
-            _lib.lib().cmbpo_rollout_disagreement_detach(C.byref(rs))
-            _lib.lib().cmbpo_rollout_value_disagreement_detach(C.byref(rs))
-            _lib.lib().cmbpo_rollout_term_head_detach(C.byref(rs))
+            _detach_all(rs)
     except Exception:      # interpreter shutdown
         pass
 
@@ -112,11 +174,7 @@ class ModelBuffer:
     def _alloc(self, B):
         T, D, A, dev = self.max_path_length, self.obs_dim, self.act_dim, self.device
         if self.rs is not None:               # the table's key is the old iscal
-            _lib.check(_lib.lib().cmbpo_rollout_iv_detach(C.byref(self.rs)), "cmbpo_rollout_iv_detach")
-            _lib.check(_lib.lib().cmbpo_rollout_disagreement_detach(C.byref(self.rs)), "cmbpo_rollout_disagreement_detach")
-            _lib.check(_lib.lib().cmbpo_rollout_value_disagreement_detach(C.byref(self.rs)),
-                       "cmbpo_rollout_value_disagreement_detach")
-            _lib.check(_lib.lib().cmbpo_rollout_term_head_detach(C.byref(self.rs)), "cmbpo_rollout_term_head_detach")
+            _detach_all(self.rs)
         f = dict(dtype=torch.float32, device=dev)
         d = dict(dtype=torch.float64, device=dev)
         t = {}
@@ -155,10 +213,8 @@ class ModelBuffer:
         self.rs.max_path_length = T
         self._bind_all()
         self._iv_key[0] = self.t["iscal"].data_ptr()
-        self._iv_sync()
-        self._dis_sync()
-        self._vdis_sync()
-        self._term_sync()
+        for feature in _SIDE:
+            self._side_sync(feature)
 
     def _bind_all(self):
         for name, _ in RolloutStruct._fields_:
@@ -182,7 +238,7 @@ class ModelBuffer:
         if not on and self.trust_var is not None:
             raise ValueError("set_iv_gae(False): the trust weights read the variance it keeps (set_trust_weights(None) first)")
         self.iv_gae, self.iv_eps = bool(on), iv_eps
-        self._iv_sync()
+        self._side_sync("iv")
 
     def set_trust_weights(self, ref_var):
         """Switch the trust weights of get() on (ref_var > 0: the accumulated variance at which a sample weighs 1/2) or off
@@ -199,30 +255,6 @@ class ModelBuffer:
         if ref_var is None:
             self.last_weights = None
 
-    def _iv_sync(self):
-        """Attach (on: for the current arrays, lambdas and iv_eps) or detach (off: and free) the state beside the struct."""
-        lib, t = _lib.lib(), self.t
-        if not self.iv_gae:
-            _lib.check(lib.cmbpo_rollout_iv_detach(C.byref(self.rs)), "cmbpo_rollout_iv_detach")
-            t.pop("cumvar_buf", None)
-            t.pop("iv_tables", None)
-            return
-        T, B, dev = self.max_path_length, self.capacity, self.device
-        if "cumvar_buf" not in t:
-            t["cumvar_buf"] = torch.zeros((T, B), dtype=torch.float64, device=dev)
-        tabs = torch.from_numpy(np.concatenate(iv_tables(self.lam, T) + iv_tables(self.cost_lam, T)))
-        if "iv_tables" in t:
-            t["iv_tables"].copy_(tabs)        # same addresses: ordered on the stream behind the kernels that read the old values
-        else:
-            t["iv_tables"] = tabs.to(dev)
-        base = t["iv_tables"].data_ptr()
-        iv = _lib.IvGaeStruct()
-        iv.cumvar_buf = t["cumvar_buf"].data_ptr()
-        iv.lam_vec, iv.lam_pow = base, base + 8 * T
-        iv.clam_vec, iv.clam_pow = base + 8 * (2 * T + 1), base + 8 * (3 * T + 1)
-        iv.eps = self.iv_eps
-        _lib.check(lib.cmbpo_rollout_iv_attach(C.byref(self.rs), C.byref(iv)), "cmbpo_rollout_iv_attach")
-
     # -- ensemble disagreement on reward / cost --------------------------------------------------
     def set_disagreement(self, on, rew_pessimism=0.0, cost_pessimism=0.0):
         """Measure the ensemble's disagreement on reward and cost along the rollout (and hold kappa * sigma against the
@@ -236,30 +268,7 @@ class ModelBuffer:
         if self.ptr != 0 or self._size != 0:
             raise RuntimeError("set_disagreement: the buffer holds samples (call it after get() / reset())")
         self.disagreement, self.rew_pessimism, self.cost_pessimism = on, kr, kc
-        self._dis_sync()
-
-    def _dis_sync(self):
-        """Attach (on: for the current arrays and coefficients) or detach (off: and free) the state beside the struct."""
-        lib, t = _lib.lib(), self.t
-        names = ("rew_var_t", "cost_var_t", "path_rew_var", "path_cost_var", "dis_part")
-        if not self.disagreement:
-            _lib.check(lib.cmbpo_rollout_disagreement_detach(C.byref(self.rs)), "cmbpo_rollout_disagreement_detach")
-            for n in names:
-                t.pop(n, None)
-            return
-        B, dev = self.capacity, self.device
-        if "dis_part" not in t:
-            t["rew_var_t"] = torch.zeros(B, dtype=torch.float32, device=dev)
-            t["cost_var_t"] = torch.zeros(B, dtype=torch.float32, device=dev)
-            t["path_rew_var"] = torch.zeros(B, dtype=torch.float64, device=dev)
-            t["path_cost_var"] = torch.zeros(B, dtype=torch.float64, device=dev)
-            t["dis_part"] = torch.zeros(((B + 63) // 64) * 2, dtype=torch.float64, device=dev)
-        dg = _lib.DisagreementStruct()
-        dg.kappa_rew, dg.kappa_cost = self.rew_pessimism, self.cost_pessimism
-        dg.rew_var_t, dg.cost_var_t = t["rew_var_t"].data_ptr(), t["cost_var_t"].data_ptr()
-        dg.path_rew_var, dg.path_cost_var = t["path_rew_var"].data_ptr(), t["path_cost_var"].data_ptr()
-        dg.part = t["dis_part"].data_ptr()
-        _lib.check(lib.cmbpo_rollout_disagreement_attach(C.byref(self.rs), C.byref(dg)), "cmbpo_rollout_disagreement_attach")
+        self._side_sync("dis")
 
     # -- critic disagreement: pessimistic value bootstraps ----------------------------------------
     def set_value_disagreement(self, on, v_pessimism=0.0, vc_pessimism=0.0):
@@ -275,28 +284,7 @@ class ModelBuffer:
         if self.ptr != 0 or self._size != 0:
             raise RuntimeError("set_value_disagreement: the buffer holds samples (call it after get() / reset())")
         self.value_disagreement, self.v_pessimism, self.vc_pessimism = on, kv, kc
-        self._vdis_sync()
-
-    def _vdis_sync(self):
-        """Attach (on: for the current arrays and coefficients) or detach (off: and free) the state beside the struct."""
-        lib, t = _lib.lib(), self.t
-        names = ("v_var", "vc_var", "vdis_part")
-        if not self.value_disagreement:
-            _lib.check(lib.cmbpo_rollout_value_disagreement_detach(C.byref(self.rs)), "cmbpo_rollout_value_disagreement_detach")
-            for n in names:
-                t.pop(n, None)
-            return
-        B, dev = self.capacity, self.device
-        if "vdis_part" not in t:
-            t["v_var"] = torch.zeros(B, dtype=torch.float32, device=dev)
-            t["vc_var"] = torch.zeros(B, dtype=torch.float32, device=dev)
-            t["vdis_part"] = torch.zeros(((B + 63) // 64) * 2, dtype=torch.float64, device=dev)
-        vd = _lib.ValueDisagreementStruct()
-        vd.kappa_v, vd.kappa_vc = self.v_pessimism, self.vc_pessimism
-        vd.v_var, vd.vc_var = t["v_var"].data_ptr(), t["vc_var"].data_ptr()
-        vd.part = t["vdis_part"].data_ptr()
-        _lib.check(lib.cmbpo_rollout_value_disagreement_attach(C.byref(self.rs), C.byref(vd)),
-                   "cmbpo_rollout_value_disagreement_attach")
+        self._side_sync("vdis")
 
     # -- learned termination head ------------------------------------------------------------------
     def set_term_head(self, on, threshold=0.5, members='elite'):
@@ -316,24 +304,24 @@ class ModelBuffer:
         if self.ptr != 0 or self._size != 0:
             raise RuntimeError("set_term_head: the buffer holds samples (call it after get() / reset())")
         self.term_head = head
-        self._term_sync()
+        self._side_sync("term")
 
-    def _term_sync(self):
-        """Attach (on: for the current arrays, threshold and vote) or detach (off: and free) the head beside the struct."""
-        lib, t = _lib.lib(), self.t
-        if self.term_head is None:
-            _lib.check(lib.cmbpo_rollout_term_head_detach(C.byref(self.rs)), "cmbpo_rollout_term_head_detach")
-            t.pop("term_pred_t", None)
-            t.pop("term_votes_t", None)
+    # -- the state beside the struct ------------------------------------------------------------
+    def _side_sync(self, feature):
+        """Attach (on: for the current arrays and settings) or detach (off: and free) one feature of _SIDE beside the struct."""
+        side, lib, t = _SIDE[feature], _lib.lib(), self.t
+        arrays = side.arrays(self.capacity, self.max_path_length)
+        if not side.on(self):
+            _lib.check(getattr(lib, side.detach)(C.byref(self.rs)), side.detach)
+            for name, _, _ in arrays:
+                t.pop(name, None)
             return
-        B, dev = self.capacity, self.device
-        if "term_pred_t" not in t:
-            t["term_pred_t"] = torch.zeros(B, dtype=torch.float32, device=dev)
-            t["term_votes_t"] = torch.zeros(B, dtype=torch.uint8, device=dev)
-        th = _lib.TermHeadStruct()
-        th.threshold, th.members = self.term_head[0], _lib.TERM_MEMBERS[self.term_head[1]]
-        th.term_pred, th.term_votes = t["term_pred_t"].data_ptr(), t["term_votes_t"].data_ptr()
-        _lib.check(lib.cmbpo_rollout_term_head_attach(C.byref(self.rs), C.byref(th)), "cmbpo_rollout_term_head_attach")
+        for name, shape, dtype in arrays:
+            if name not in t:
+                t[name] = torch.zeros(shape, dtype=dtype, device=self.device)
+        st = side.struct()
+        side.fill(self, st)
+        _lib.check(getattr(lib, side.attach)(C.byref(self.rs), C.byref(st)), side.attach)
 
     def swap(self, a, b):
         """Exchange two same-shaped state arrays (cur_obs <-> next_obs, v_t <-> v_n, ...)."""
@@ -357,7 +345,7 @@ class ModelBuffer:
         self.rs.gamma, self.rs.lam = float(gamma), float(lam)
         self.rs.cost_gamma, self.rs.cost_lam = float(cost_gamma), float(cost_lam)
         if self.iv_gae:
-            self._iv_sync()                   # the tables follow the lambdas
+            self._side_sync("iv")             # the tables follow the lambdas
 
     def reset(self, batch_size=None):
         """modelbuffer.py:53-98 (pointers only; the buffers are reused unless the batch size changes)."""

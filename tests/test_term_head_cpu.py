@@ -114,6 +114,73 @@ def test_null_head_forwards_to_the_existing_entry_points(lib):
     assert _post(lib, _lib.TASK_HCS, 7, 18, 6, None, buffers=True) == 0
 
 
+# ---- the naming rule: a message carries the name of the narrowest entry point that can express the call --------------------------
+# every post entry point x every subset of {xi, disagreement arguments, head} it can express
+_POST_CASES = [("cmbpo_fakeenv_post", False, False, False)]
+_POST_CASES += [("cmbpo_fakeenv_post_noise", xi, False, False) for xi in (False, True)]
+_POST_CASES += [("cmbpo_fakeenv_post_disagreement", xi, dis, False) for xi in (False, True) for dis in (False, True)]
+_POST_CASES += [("cmbpo_fakeenv_post_term", xi, dis, th) for xi in (False, True) for dis in (False, True) for th in (False, True)]
+
+
+def _post_entry(lib, entry, xi, dis, th, task, n_rows=0):
+    """One call of `entry` on host memory that is never dereferenced; returns (rc, the name the rule gives)."""
+    host = (C.c_float * 64)()
+    p = C.cast(host, C.c_void_p)
+    args = [task, 7, 18, 6, p, p, n_rows, p, p, p, None, None, n_rows, p, p, p, p, p, p, None]
+    if entry != "cmbpo_fakeenv_post":
+        args.append(p if xi else None)
+    if entry in ("cmbpo_fakeenv_post_disagreement", "cmbpo_fakeenv_post_term"):
+        args += [0.5, 0.25, p, p] if dis else [0.0, 0.0, None, None]
+    head = _head(0.5, 2)
+    if entry == "cmbpo_fakeenv_post_term":
+        args.append(C.byref(head) if th else None)
+    dis_on = dis or entry == "cmbpo_fakeenv_post_disagreement"        # that entry is the feature: always on
+    want = ("cmbpo_fakeenv_post_term" if th else "cmbpo_fakeenv_post_disagreement" if dis_on
+            else "cmbpo_fakeenv_post_noise" if xi else "cmbpo_fakeenv_post")
+    return getattr(lib, entry)(*args, None), want.encode()
+
+
+@pytest.mark.parametrize("entry,xi,dis,th", _POST_CASES)
+def test_post_messages_carry_the_name_the_rule_gives(lib, entry, xi, dis, th):
+    rc, want = _post_entry(lib, entry, xi, dis, th, task=9)
+    msg = lib.cmbpo_last_error()
+    assert rc == -1 and msg.startswith(want + b": bad task 9"), msg
+
+
+@pytest.mark.parametrize("entry,xi,dis,th", _POST_CASES)
+def test_post_of_no_rows_launches_nothing(lib, entry, xi, dis, th):
+    """Good arguments and n_rows == 0 return before the launch (there is no device here to launch on)."""
+    from cmbpo_amd import _lib
+    rc, want = _post_entry(lib, entry, xi, dis, th, task=_lib.TASK_HCS | _lib.TASK_LEARNED_COST)
+    if entry == "cmbpo_fakeenv_post_disagreement" and not dis:      # on without its buffers: refused under its own name
+        assert rc == -1 and lib.cmbpo_last_error().startswith(want + b": NULL buffer (d_rew_var / d_cost_var)")
+    else:
+        assert rc == 0, lib.cmbpo_last_error()
+
+
+@pytest.mark.parametrize("entry,rc_given,th_given,want", [
+    ("cmbpo_replay_run", False, False, b"cmbpo_replay_run"),
+    ("cmbpo_replay_run_calibrated", True, False, b"cmbpo_replay_run_calibrated"),
+    ("cmbpo_replay_run_calibrated", False, False, b"cmbpo_replay_run_calibrated"),     # its rc == NULL is its own error
+    ("cmbpo_replay_run_term", False, False, b"cmbpo_replay_run"),
+    ("cmbpo_replay_run_term", True, False, b"cmbpo_replay_run_calibrated"),
+    ("cmbpo_replay_run_term", False, True, b"cmbpo_replay_run_term"),
+    ("cmbpo_replay_run_term", True, True, b"cmbpo_replay_run_term")])
+def test_replay_messages_carry_the_name_the_rule_gives(lib, entry, rc_given, th_given, want):
+    from cmbpo_amd import _lib
+    rp, cal, head = _lib.ReplayStruct(), _lib.ReplayCalibStruct(), _head()      # all-zero descriptors: the first check fails
+    rc = C.byref(cal) if rc_given else None
+    th = C.byref(head) if th_given else None
+    if entry == "cmbpo_replay_run":
+        got = lib.cmbpo_replay_run(C.byref(rp), None, 0, 7, None, None)
+    elif entry == "cmbpo_replay_run_calibrated":
+        got = lib.cmbpo_replay_run_calibrated(C.byref(rp), rc, None, 0, 7, None)
+    else:
+        got = lib.cmbpo_replay_run_term(C.byref(rp), rc, th, None, 0, 7, None, None)
+    msg = lib.cmbpo_last_error()
+    assert got == -1 and msg.startswith(want + b": B 0 < 1"), msg
+
+
 def test_rollout_attach_and_replay_refusals(lib):
     from cmbpo_amd import _lib
     rs = _lib.RolloutStruct()

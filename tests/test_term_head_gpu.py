@@ -52,10 +52,11 @@ def _bits(a):
 # ------------------------------------------------------------------------------------------------------------------
 # 1. the post kernel
 # ------------------------------------------------------------------------------------------------------------------
-def _run_term(task_arg, obs, act, mean, var, inds, D, A, rows=None, xi=None, kappa=None, head=None, optional=True):
+def _run_term(task_arg, obs, act, mean, var, inds, D, A, rows=None, xi=None, kappa=None, head=None, optional=True,
+              entry="cmbpo_fakeenv_post_term"):
     """cmbpo_fakeenv_post_term on slot-indexed arrays; with `rows` only the listed slots are stepped.  kappa: None -- no
     disagreement (NULL arrays, both coefficients 0); head: None -- th == NULL, or (threshold, members).  Every output starts at a
-    sentinel."""
+    sentinel.  entry: a narrower entry point instead, with the leading part of the same arguments that it takes."""
     from cmbpo_amd import _lib
     dev = torch.device(DEV)
     B, E = obs.shape[0], mean.shape[0]
@@ -77,12 +78,15 @@ def _run_term(task_arg, obs, act, mean, var, inds, D, A, rows=None, xi=None, kap
         th.term_pred = _lib.ptr(out["term_pred"]) if optional else None
         th.term_votes = _lib.ptr(out["term_votes"]) if optional else None
     kr, kc = kappa if kappa is not None else (0.0, 0.0)
-    rc = _lib.lib().cmbpo_fakeenv_post_term(
+    args = [
         task_arg, E, D, A, _lib.ptr(d[2]), _lib.ptr(d[3]), B, _lib.ptr(d[0]), _lib.ptr(d[1]), _lib.ptr(d[4]), _lib.ptr(ri), None, n,
         _lib.ptr(out["next_obs"]), _lib.ptr(out["rew"]), _lib.ptr(out["term"]), _lib.ptr(out["cost"]), _lib.ptr(out["dkl_path"]),
         _lib.ptr(out["ep_var_mean"]), _lib.ptr(out["ep_var"]), _lib.ptr(d_xi), float(kr), float(kc),
         _lib.ptr(out["rew_var"]) if kappa is not None else None, _lib.ptr(out["cost_var"]) if kappa is not None else None,
-        None if th is None else C.byref(th), _lib.current_stream())
+        None if th is None else C.byref(th)]
+    take = {"cmbpo_fakeenv_post": 20, "cmbpo_fakeenv_post_noise": 21, "cmbpo_fakeenv_post_disagreement": 25, "cmbpo_fakeenv_post_term": 26}
+    assert all(a is None or a == 0.0 for a in args[take[entry]:]), "the entry point cannot express this call"
+    rc = getattr(_lib.lib(), entry)(*args[:take[entry]], _lib.current_stream())
     torch.cuda.synchronize()
     assert rc == 0, (rc, _lib.lib().cmbpo_last_error())
     return {k: v.cpu().numpy() for k, v in out.items()}
@@ -203,6 +207,90 @@ def test_post_kernel_term_head(hip_lib, E, D, n, listed):
                     bare = _run_term(task_arg, obs, act, mean, var, inds, D, A, rows, xi, kappa, head=(THR, "majority"), optional=False)
                     np.testing.assert_array_equal(bare["term"], on["term"], err_msg=tag)
                     assert (bare["term_pred"] == -7.0).all() and (bare["term_votes"] == 77).all()
+
+
+def _narrowest(xi, dis, head):
+    """The naming rule of the post step (DESIGN): the narrowest entry point that can express a feature set."""
+    return ("cmbpo_fakeenv_post_term" if head else "cmbpo_fakeenv_post_disagreement" if dis
+            else "cmbpo_fakeenv_post_noise" if xi else "cmbpo_fakeenv_post")
+
+
+@pytest.mark.parametrize("kind", ["antsafe", "table"])
+@pytest.mark.parametrize("E", [7, 5, 3])         # the kernel's three instances
+def test_every_entry_point_is_the_superset_call_bitwise(hip_lib, E, kind):
+    """{xi} x {disagreement} x {head}: the narrowest entry point of a feature set and cmbpo_fakeenv_post_term with the rest NULL / 0
+    write the same bits into every output -- one workgroup of eight rows and a ragged second, through an unsorted row list.  With
+    the head on the narrowest entry IS the superset: there the head-off outputs are those of the narrow entry over the narrower
+    copy of the means, and the decisions the specification's."""
+    _need_gpu()
+    D, A, n, B = 5, 2, 9, 12
+    rng = np.random.default_rng(zlib.crc32(f"{E}/{kind}/one-post-call".encode()))
+    rows = rng.permutation(B)[:n].astype(np.int32)
+    assert len(set(rows.tolist())) == n and (np.diff(rows) < 0).any()
+    obs = (rng.standard_normal((B, D)) * 0.1).astype(np.float32)
+    obs[rows[0::2], 0], obs[rows[1::2], 0] = 0.6, 5.0     # z: inside / outside the healthy band (the table ends the row)
+    obs[rows[0::4], 2] = 1.0                               # healthy and q1 = 1: z_rot = -1 < -0.7 (AntSafe ends the row)
+    act = rng.uniform(-1, 1, (B, A)).astype(np.float32)
+    inds = rng.integers(0, E, size=B).astype(np.int32)
+    xi_draws = rng.standard_normal((B, D)).astype(np.float32)
+    for dis in (False, True):
+        learned = dis                                 # kappa_cost > 0 needs the learned-cost column
+        O = ref.term_column(D, learned) + 1
+        mean = (rng.standard_normal((E, B, O)) * 0.3).astype(np.float32)
+        var = np.exp(rng.uniform(-12, 1, (E, B, O))).astype(np.float32)
+        mean[:, :, (0, 2)], var[:, :, (0, 2)] = 0.0, 1e-6      # z and q1 stay where obs put them, with or without the draws
+        mean[:, :, O - 1] = (0.5 + 0.4 * rng.standard_normal((E, B))).astype(np.float32)
+        narrow = np.ascontiguousarray(mean[..., :O - 1]), np.ascontiguousarray(var[..., :O - 1])
+        task_arg = _task_arg(kind, learned)
+        kappa = (0.5, 0.25) if dis else None
+        for xi in (None, xi_draws):
+            tag = f"{kind} E={E} xi={xi is not None} dis={dis}"
+            entry = _narrowest(xi is not None, dis, False)
+            own = _run_term(task_arg, obs, act, *narrow, inds, D, A, rows, xi, kappa, entry=entry)
+            sup = _run_term(task_arg, obs, act, *narrow, inds, D, A, rows, xi, kappa)
+            assert set(own["term"][rows].tolist()) == {0, 1}, tag                     # both values of done occur
+            for k in own:
+                np.testing.assert_array_equal(_bits(sup[k]), _bits(own[k]), err_msg=f"{tag} {k}")
+            on = _run_term(task_arg, obs, act, mean, var, inds, D, A, rows, xi, kappa, head=(THR, "majority"))
+            term, pred, votes, hit = ref.term_head(mean, inds, D, learned, THR, "majority", rows=rows, rule_done=own["term"][rows])
+            assert hit.any() and not hit.all(), tag
+            np.testing.assert_array_equal(on["term"][rows], term, err_msg=tag)
+            np.testing.assert_array_equal(_bits(on["term_pred"][rows]), _bits(pred), err_msg=tag)
+            np.testing.assert_array_equal(on["term_votes"][rows], votes, err_msg=tag)
+            for k in CLASSIC + ("rew_var", "cost_var"):
+                np.testing.assert_array_equal(_bits(on[k]), _bits(own[k]), err_msg=f"{tag} head on {k}")
+
+
+_SIDE_KEYS = {"iv": {"cumvar_buf", "iv_tables"}, "dis": {"rew_var_t", "cost_var_t", "path_rew_var", "path_cost_var", "dis_part"},
+              "vdis": {"v_var", "vc_var", "vdis_part"}, "term": {"term_pred_t", "term_votes_t"}}
+
+
+def test_model_buffer_side_arrays_follow_the_switches(hip_lib):
+    """Each feature beside the rollout struct on, off and on again: its arrays exist exactly while it is on, the other features'
+    arrays stay what they are (the same tensors), and a feature switched on again gets arrays of its own."""
+    _need_gpu()
+    from cmbpo_amd.modelbuffer import ModelBuffer
+    buf = ModelBuffer(4, 5, 2, 2, device=DEV)
+    switch = {"iv": lambda on: buf.set_iv_gae(on), "dis": lambda on: buf.set_disagreement(on, 0.5 if on else 0.0),
+              "vdis": lambda on: buf.set_value_disagreement(on), "term": lambda on: buf.set_term_head(on, 0.5, "majority")}
+    every = set().union(*_SIDE_KEYS.values())
+    base = set(buf.t)
+    assert not base & every
+    on_now = set()
+    for feature, keys in _SIDE_KEYS.items():
+        for on in (True, False, True):
+            before = dict(buf.t)
+            switch[feature](on)
+            on_now = on_now | {feature} if on else on_now - {feature}
+            assert set(buf.t) == base | set().union(*[_SIDE_KEYS[f] for f in on_now]), (feature, on)
+            for k, v in before.items():
+                if k not in keys:
+                    assert buf.t[k] is v, (feature, on, k)
+        assert buf.t["iscal"].data_ptr() == buf.rs.iscal
+    # a new batch size: every array anew, every feature still on
+    buf.reset(batch_size=6)
+    assert set(buf.t) == base | every and buf.t["cumvar_buf"].shape == (2, 6) and buf.t["dis_part"].shape == (2,)
+    assert buf.t["term_votes_t"].dtype == torch.uint8 and buf.t["v_var"].dtype == torch.float32
 
 
 # ------------------------------------------------------------------------------------------------------------------
