@@ -263,6 +263,7 @@ SIGNATURES.update({
     "cmbpo_trainer_losses": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _p, _p]),
     "cmbpo_trainer_steps_done": (C.c_long, [_p]),
     "cmbpo_trainer_f16_paths": (_i, [_p]),
+    "cmbpo_trainer_fused": (_i, [_p]),
 })
 
 class TrainExtrasStruct(C.Structure):

@@ -2700,3 +2700,5 @@ extern "C" int cmbpo_trainer_f16_paths(const cmbpo_trainer_t *t) {
   if (!t) return -1;
   return (t->b16 ? 1 : 0) | (t->b16 && t->b16_fwd ? 2 : 0);
 }
+
+extern "C" int cmbpo_trainer_fused(const cmbpo_trainer_t *t) { return t ? t->fused : -1; }

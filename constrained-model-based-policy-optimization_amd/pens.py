@@ -269,6 +269,11 @@ class EnsembleTrainer:
         """Bit 0: the backward chain runs on the f16 kernels, bit 1: the training forward too (fixed by the shapes)."""
         return int(_lib.lib().cmbpo_trainer_f16_paths(self._h))
 
+    @property
+    def fused(self):
+        """True: the step is the fused kernel of the 128-wide deterministic heads (fixed by the shapes)."""
+        return bool(_lib.lib().cmbpo_trainer_fused(self._h))
+
 
 def _to_dev(x, device):
     """(tensor on device, was_numpy)."""

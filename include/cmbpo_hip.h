@@ -877,6 +877,9 @@ long cmbpo_trainer_steps_done(const cmbpo_trainer_t *t);
 /* Which kernels a training step of this trainer runs: bit 0 the f16 backward chain, bit 1 the f16 training forward
  * (0: the fp32 kernels; -1: NULL handle).  Fixed at creation by the network's shapes. */
 int cmbpo_trainer_f16_paths(const cmbpo_trainer_t *t);
+/* 1: a training step of this trainer is one fused_mse_step_kernel launch in front of Adam (128-wide deterministic heads of at
+ * most 32 outputs and 64 padded inputs), 0: the general forward / backward-chain / weight-gradient kernels; -1: NULL handle. */
+int cmbpo_trainer_fused(const cmbpo_trainer_t *t);
 
 /* ---- start states of an imagined-rollout round (csrc/start_states.hip) -----
  * algorithms/cmbpo.py:239-251 on a device mirror of CPOBuffer's archive: observations [n][obs_dim],
