@@ -206,6 +206,7 @@ SIGNATURES.update({
     "cmbpo_pi_fvp": (_i, [_p, _bp, _p, _p, _p]),
     "cmbpo_pi_keep_activations": (_i, [_p, _i]),
     "cmbpo_pi_saved_activation_uses": (C.c_long, [_p]),
+    "cmbpo_pi_last_grid": (_i, [_p]),
     "cmbpo_pi_set_sample_weights": (_i, [_p, _p, _i, _p]),
     "cmbpo_set_pi_matrix_path": (None, [_i]),
     "cmbpo_get_pi_matrix_path": (_i, []),

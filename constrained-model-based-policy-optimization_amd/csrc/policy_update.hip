@@ -1244,6 +1244,7 @@ extern "C" int cmbpo_pi_keep_activations(cmbpo_pi_t *h, int enable) {
 }
 
 extern "C" long cmbpo_pi_saved_activation_uses(const cmbpo_pi_t *h) { return h ? h->act_hits : -1; }
+extern "C" int cmbpo_pi_last_grid(const cmbpo_pi_t *h) { return h ? h->last_grid : -1; }
 
 const void *cmbpo_pi_act_token(const cmbpo_pi_t *h, const cmbpo_pi_batch_t *b) { return (h && b) ? act_for(h, b) : nullptr; }
 

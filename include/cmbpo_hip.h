@@ -636,6 +636,10 @@ int cmbpo_pi_keep_activations(cmbpo_pi_t *h, int enable);
 /* Fisher-vector product launches that read saved activations so far (a launch
  * captured into the CG graph counts once); diagnostics / tests. */
 long cmbpo_pi_saved_activation_uses(const cmbpo_pi_t *h);
+/* Workgroups (= partial vectors) of the last loss_grad / fvp / eval / ppo_grad
+ * launch on this handle, 0 before the first; with fewer workgroups than 32-sample
+ * tiles each persistent workgroup walked more than one tile.  Read-only; tests. */
+int cmbpo_pi_last_grid(const cmbpo_pi_t *h);
 /* Per-sample weights of every later launch on this handle (loss_grad, fvp, eval,
  * the CG calls, ppo_grad, ppo_run): a sample of weight w counts as w copies of
  * itself.  Every per-sample sum becomes a weighted sum: d_sums[0] = sum w,
