@@ -30,6 +30,12 @@
 // n-tiles 2w, 2w+1 x four row tiles of layer 1 (128 accumulator registers).  h2 leaves the accumulators in two 64-row
 // halves through a [64][512] image; the output layer is split over (output tile, row tile, k half) units, its results
 // pass through an LDS staging tile so that rows are stored as contiguous runs.
+//
+// The split input image does not depend on the member.  The main launch of 128-row items on the stage-ahead instances
+// takes it ready from h3_ximage_kernel, which builds it once per row in front of that launch, instead of building it once
+// per (member, row): a tile's block travels to LDS by LDS-DMA, requested behind the weight ring's last wait of the
+// predecessor's last fused step (ens_h3_kernel<.., IMG = true>, piece_at_img).  Every other launch stages its
+// rows itself, as before.
 #include "common.h"
 #include "ens_mlp_internal.h"
 #include "f16_split.h"
@@ -229,16 +235,99 @@ __host__ __device__ constexpr int piece_at(int slot, int i) {
   return -1;
 }
 
+// The image instances (IMG): the split x image and the rows' maxima come ready from h3_ximage_kernel, so pieces 0 .. 3,
+// 8 .. 12, 16 .. 19 and 21 of the table above do not exist.  What takes their numbers: 0 / 1 request the image (LDS-DMA,
+// two 1-KiB pieces per wave each), 2 requests the row's maximum.  They stand behind the ring's last load of the step (slot 3,
+// MFMA 23) and behind the MFMA that waits for its last half (slot 4, MFMA 6): no wait for a weight fragment has them in
+// front of it.  Piece 22 ends with the wait for the image; only the next row index is requested after it.
+__host__ __device__ constexpr int piece_at_img(int slot, int i) {
+  if (i % 2 != 0) return -1;
+  const int k = i / 2;
+  if (slot == 1) return k == 0 ? 4 : (k == 2 ? 5 : (k == 4 ? 6 : -1));                          // biases, head, W0 round 0
+  if (slot == 3) return k == 4 ? 13 : -1;                                                       // W0 round 1
+  if (slot == 4) return k == 1 ? 7 : (k == 3 ? 2 : (k == 5 ? 0 : (k == 7 ? 1 : -1)));           // constants -> LDS; maximum, image
+  if (slot == 5) return k == 4 ? 20 : -1;                                                       // W0 round 2
+  if (slot == 6) return k == 1 ? 14 : (k == 3 ? 15 : -1);                                       // row scales
+  if (slot == 7) return k < 2 ? 22 + k : -1;                                                    // the last KB of W0 + the image's wait, the next row index
+  return -1;
+}
+__host__ __device__ constexpr int piece_of(bool img, int slot, int i) { return img ? piece_at_img(slot, i) : piece_at(slot, i); }
+
 struct H3Args {
   MlpKernelArgs m;
   const f16x8 *w0, *w1, *w2;
   size_t w0_stride, w1_stride, w2_stride;   // per member, in 16-B units
   const float *stats;                        // [E][NSTAT]
   int item0;                                 // first item of this launch (a launch may carry a suffix of the item list)
+  const char *ximg;                          // image instances: the tile blocks h3_ximage_kernel wrote
 };
 
+// ---- the x image of a launch's rows, once per row instead of once per (member, row) ----------------------------------
+// One block per 128-row tile of the launch's row list, in the layout of the kernel's LDS x image: [piece 2][128][XSTR]
+// halves, then the rows' max |x| as 128 floats.  The arithmetic is the stage's (pieces 0 .. 3, 8 .. 12, 16 .. 19, 21 of
+// stage_piece, same thread-to-element map): nothing of it depends on the member.  Rows beyond the row count and the 8 pad
+// halves of every row are zeros, so every byte of a block is written.  grid = tiles, 512 threads.
+__host__ __device__ constexpr int ximg_block_bytes(int S0) { return ximg_bytes(S0, 4) + 128 * 4; }
+template <int S0>
+__global__ __launch_bounds__(kThreadsH) void h3_ximage_kernel(const MlpKernelArgs p, char *img) {
+  static_assert(S0 < 4 && ximg_block_bytes(S0) % 512 == 0, "h3_ximage_kernel: pad halves are written by the thread behind the row's last element");
+  constexpr int XSTR = 16 * S0 + 8, TPR = Geo<4>::TPR, KPT = Geo<4>::KPT;
+  const int n_rows = p.n_rows_dev ? *p.n_rows_dev : p.n_rows;
+  const int tid = threadIdx.x, xb = tid / TPR, xc = tid % TPR;
+  __shared__ float mu_l[64], isig_l[64];      // the input scaler as the stage holds it: mu, 1 / sigma
+  if (tid < 64) {
+    mu_l[tid] = (p.in_mu && tid < p.in_dim) ? p.in_mu[tid] : 0.0f;
+    isig_l[tid] = (p.in_mu && tid < p.in_dim) ? 1.0f / p.in_sig[tid] : 1.0f;
+  }
+  __syncthreads();
+  const int rr = blockIdx.x * 128 + xb;
+  const bool ok = rr < n_rows;
+  int v = ok ? rr : 0;
+  if (p.row_idx) v = p.row_idx[v];
+  const float *orow = p.obs + (size_t)v * p.obs_dim;
+  const float *arow = p.act_dim > 0 ? p.act + (size_t)v * p.act_dim - p.obs_dim : orow;
+  float x[KPT];
+  float m = 0.0f;
+#pragma unroll
+  for (int u = 0; u < KPT; ++u) {
+    const int k = KPT * xc + u;
+    const bool in_obs = k < p.obs_dim, in_act = !in_obs & (k < p.in_dim);
+    const float *base = in_act ? arow : orow;
+    const float raw = base[(in_obs | in_act) ? k : 0];
+    float xv = (raw - mu_l[k]) * isig_l[k];
+    xv = ((k < p.in_dim) & ok) ? xv : 0.0f;
+    x[u] = xv;
+    m = fmaxf(m, fabsf(xv));
+  }
+#pragma unroll
+  for (int o = 1; o < TPR; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  const float t0 = pow2_lift(m);
+  char *blk = img + (size_t)blockIdx.x * ximg_block_bytes(S0);
+  _Float16 *d1 = reinterpret_cast<_Float16 *>(blk) + (size_t)xb * XSTR + KPT * xc, *d2 = d1 + (size_t)128 * XSTR;
+  if (KPT * xc < 16 * S0) {
+#pragma unroll
+    for (int w = 0; w < KPT / 8; ++w) {
+      f16x8 h1, h2;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        _Float16 a, b;
+        split_h(x[8 * w + j] * t0, a, b);
+        h1[j] = a; h2[j] = b;
+      }
+      reinterpret_cast<f16x8 *>(d1)[w] = h1; reinterpret_cast<f16x8 *>(d2)[w] = h2;
+    }
+  } else if (KPT * xc == 16 * S0) {
+    f16x8 z;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z[j] = (_Float16)0.0f;
+    *reinterpret_cast<f16x8 *>(d1) = z; *reinterpret_cast<f16x8 *>(d2) = z;
+  }
+  if (xc == 0) reinterpret_cast<float *>(blk + ximg_bytes(S0, 4))[xb] = m;
+}
+
 // S0: k-slabs of the input layer (in_pad <= 16 S0); OTP: output n-tiles, 2 or 4 (2 out_dim <= 32 OTP); RT: 32-row tiles per item
-template <int S0, int OTP, int RT>
+// IMG: the x image comes from h3_ximage_kernel's tile blocks by LDS-DMA (stage-ahead instances at RT == 4 only)
+template <int S0, int OTP, int RT, bool IMG = false>
 __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
   using G = Geo<RT>;
   constexpr int ROWSH = G::ROWS, NTC = G::NTC, CK = G::CK, NCH = G::NCH, SLC = G::SLC, CSTR = G::CSTR, TPR = G::TPR,
@@ -249,6 +338,9 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
   constexpr int O_PAD = 32 * OTP;
   constexpr int W0P = NTC * S0 * 2;      // 1-KB pieces of one W0 chunk
   constexpr bool AHEAD = stage_ahead(S0, RT);
+  static_assert(!IMG || (AHEAD && RT == 4), "ens_h3: the image instances are the stage-ahead ones at 128 rows");
+  constexpr int NXP = ximg_bytes(S0, RT) / 1024;     // 1-KiB pieces of the x image
+  static_assert(!IMG || ximg_bytes(S0, RT) % 1024 == 0, "ens_h3: the x image in whole LDS-DMA pieces");
   const MlpKernelArgs &p = a.m;
   extern __shared__ f32x4 smem4[];
   char *smem = reinterpret_cast<char *>(smem4);
@@ -272,7 +364,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
 
   const int n_rows = p.n_rows_dev ? *p.n_rows_dev : p.n_rows;
   const int out = p.out_dim;
-  if (threadIdx.x < 64) {   // input scaler, once per workgroup (TensorStandardScaler.transform, models/pens/utils.py:156)
+  if (!IMG && threadIdx.x < 64) {   // input scaler, once per workgroup (TensorStandardScaler.transform, models/pens/utils.py:156)
     const int k = threadIdx.x;
     in_mu_l[k] = (p.in_mu && k < p.in_dim) ? p.in_mu[k] : 0.0f;
     in_sig_l[k] = (p.in_mu && k < p.in_dim) ? 1.0f / p.in_sig[k] : 1.0f;      // 1 / sigma: see the stage
@@ -289,9 +381,11 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
     return it;
   };
   int rr_pre = -1;      // row index of this thread's row of the item that is staged next
+  int tile_pre = 0;     // (image instances) its row tile
   auto fetch_row = [&](int it, int tid) {
     const int xb = tid / TPR;
     const int e2 = it / p.tiles;
+    if constexpr (IMG) tile_pre = it < p.n_items ? it - e2 * p.tiles : 0;
     const int rr = (it - e2 * p.tiles) * ROWSH + xb;
     const bool ok = it < p.n_items && rr < n_rows;
     int v = ok ? rr : 0;
@@ -322,7 +416,31 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
     constexpr int K = decltype(KC)::value;
     constexpr bool FRONT = decltype(FRONTC)::value;
     const int xb = tid / TPR, xc = tid % TPR;
-    if constexpr (K < 4) {
+    if constexpr (IMG && (K < 4 || (K >= 8 && K <= 12) || (K >= 16 && K <= 19) || K == 21)) {
+      // The ready image: LDS-DMA, 16 B per lane, 1-KiB wave pieces dealt over the eight waves (destination = wave-uniform
+      // base + 16 lane), and the row's maximum.  The DMA is an asm statement: hipcc puts a wait for a DMA it knows of in
+      // front of the wave's next LDS access, which here is the B fragment of the next (slab, row tile) position.  What it
+      // does not know of it does not count: its counted waits for later loads only wait for more than they need.
+      const char *blk = a.ximg + (size_t)tile_pre * ximg_block_bytes(S0);
+      if constexpr (K < 2) {
+        const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        const unsigned lds_x = (unsigned)(unsigned long)(__attribute__((address_space(3))) char *)(smem + off_ximg(S0, RT));
+#pragma unroll
+        for (int u = 2 * K; u < 2 * K + 2; ++u) {
+          const int j = wave + kWavesH * u;
+          if (kWavesH * u < NXP && j < NXP) {     // (wave-uniform)
+            const char *g = blk + (size_t)j * 1024 + lane * 16;
+            const unsigned d = __builtin_amdgcn_readfirstlane(lds_x + j * 1024);
+            unsigned keep;
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(g), "s"(d) : "memory");
+          }
+        }
+        static_assert(NXP <= 4 * kWavesH, "ens_h3: pieces 0 / 1 request the whole x image");
+      } else if constexpr (K == 2) {
+        s.m = reinterpret_cast<const float *>(blk + ximg_bytes(S0, RT))[xb];
+      }
+    } else if constexpr (K < 4) {
       const int rr = rr_pre >= 0 ? rr_pre : 0;
       const float *orow = p.obs + (size_t)rr * p.obs_dim;
       const float *arow = p.act_dim > 0 ? p.act + (size_t)rr * p.act_dim - p.obs_dim : orow;
@@ -370,6 +488,9 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
           if constexpr (u < W0R) get(s.w0r[0], u);
         }
       }
+      // the x image has landed before the barrier that ends the stage (lds_barrier waits for LDS instructions only); every
+      // other load requested so far has been consumed, the next row index is requested behind this
+      if constexpr (IMG && K == 22) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else if constexpr (K == 7) {
       c.bias0[tid] = s.b0 * kLog2e;      // (the epilogues work on z log2(e): f16_split.h)
       c.bias1[tid] = s.b1 * kLog2e;
@@ -404,6 +525,7 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
       asm volatile("" : "+v"(s.m), "+v"(s.t0));
     } else if constexpr (K == 14) {
       if (xc == 0) {
+        if constexpr (IMG) s.t0 = pow2_lift(s.m);
         const float bound1 = (s.st[1] * s.m + s.st[2]) * 1.001f, t1 = pow2_lift(bound1);
         const float bound2 = (s.st[4] * bound1 + s.st[5]) * 1.001f, t2 = pow2_lift(bound2);
         c.rowidx[xb] = rr_pre;
@@ -653,14 +775,14 @@ __global__ __launch_bounds__(kThreadsH, 2) void ens_h3_kernel(const H3Args a) {
             if (k == 9) epi_stage<9, true>(es, d, q, inv0_l, bv, t1_l);
             if (k == 10) l0_store(es, c + 1, q);
           }
-          if constexpr (STG && piece_at(slot, i) >= 0)
-            if (have_next) stage_piece(std::integral_constant<int, (piece_at(slot, i) >= 0 ? piece_at(slot, i) : 0)>{}, std::false_type{}, sa, e_nxt, cn, tid_s, nxt2);
+          if constexpr (STG && piece_of(IMG, slot, i) >= 0)
+            if (have_next) stage_piece(std::integral_constant<int, (piece_of(IMG, slot, i) >= 0 ? piece_of(IMG, slot, i) : 0)>{}, std::false_type{}, sa, e_nxt, cn, tid_s, nxt2);
           __builtin_amdgcn_sched_barrier(0);
         });
       });
       if constexpr (STG) {     // ("slot 8": behind the last MFMA)
         static_for<0, 24>([&](auto IC) {
-          constexpr int pc = piece_at(8, decltype(IC)::value);
+          constexpr int pc = piece_of(IMG, 8, decltype(IC)::value);
           if constexpr (pc >= 0)
             if (have_next) stage_piece(std::integral_constant<int, (pc >= 0 ? pc : 0)>{}, std::false_type{}, sa, e_nxt, cn, tid_s, nxt2);
         });
@@ -953,6 +1075,33 @@ extern "C" int cmbpo_set_ens_f16_row_tiles(int rt) {
   return CMBPO_OK;
 }
 
+// rows from which the main launch at 128-row items takes the x image of h3_ximage_kernel: 0 = from the row count at which
+// every workgroup of that launch has at least two items (the first item of a workgroup is staged in front of its layers
+// either way, and the image costs a launch); < 0 never; 1 whenever the main launch has 128-row items
+static int g_h3_img_min_rows = 0;
+extern "C" int cmbpo_set_ens_f16_image_min_rows(int rows) {
+  g_h3_img_min_rows = rows;
+  return CMBPO_OK;
+}
+
+// room for the x image of n_rows rows in the handle: at least the caller's branch slots, so that it is allocated once
+static int ensure_ximg(cmbpo_mlp *m, int n_rows, int ld_rows, size_t block_bytes) {
+  const size_t need = (size_t)cmbpo_ceil_div(n_rows, 128);
+  if (m->d_ximg != nullptr && m->ximg_tiles >= need && m->ximg_block == block_bytes) return CMBPO_OK;
+  if (m->d_ximg) (void)hipFree(m->d_ximg);      // synchronises: nothing in flight still reads the old block
+  m->d_ximg = nullptr; m->ximg_tiles = 0;
+  const size_t slots = ld_rows > 0 ? (size_t)cmbpo_ceil_div(ld_rows, 128) : 0;
+  const size_t tiles = need > slots ? need : slots;
+  if (hipMalloc(&m->d_ximg, tiles * block_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    m->d_ximg = nullptr;
+    cmbpo_set_error("ens_h3: hipMalloc of the input image (%zu B) failed", tiles * block_bytes);
+    return CMBPO_ENOMEM;
+  }
+  m->ximg_tiles = tiles; m->ximg_block = block_bytes;
+  return CMBPO_OK;
+}
+
 bool cmbpo_internal_h3_eligible(const cmbpo_mlp *m) {
   return m->head == CMBPO_HEAD_PROB && m->hidden == 512 && m->act == CMBPO_ACT_SWISH && m->o_tiles <= 4 && m->in_pad <= 64 &&
          2 * m->out_dim == m->o_width;
@@ -983,6 +1132,7 @@ int cmbpo_internal_launch_h3(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s) {
   // 135 us by this model -- 134.5 measured -- against 147 for five rounds of 64-row items).  An item is (member, row tile) in
   // member-major order in every list, so a suffix of one list is a suffix of the others; a row's arithmetic does not depend
   // on the item it travels in (tests: bitwise against the forced sizes).
+  // The main launch at 128 rows reads its x image from h3_ximage_kernel's blocks where that pays (g_h3_img_min_rows).
   const int E = m->ensemble;
   constexpr int kSplitGap = 40;     // the cost of the boundary between the two launches (tenths of a microsecond)
   int RT = g_h3_rt, RT_tail = 0, full = 0, tail_start = 0;
@@ -1012,7 +1162,8 @@ int cmbpo_internal_launch_h3(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s) {
   }
   const int S0 = m->h3_s0, OTP = m->h3_otp;
   // one launch: items [item0, end) of the (member-major) item list at rt 32-row tiles per item; end < 0: all of it
-  auto launch = [&](int rt, int item0, int end) -> int {
+  // (the main launch of 128-row items on a stage-ahead instance reads the x image h3_ximage_kernel writes in front of it)
+  auto launch = [&](int rt, int item0, int end, bool main) -> int {
     const int tiles = cmbpo_ceil_div(a.n_rows, 32 * rt);
     k.m.tiles = tiles;
     k.m.n_items = end < 0 ? tiles * E : end;     // (the kernel's loop bound)
@@ -1021,24 +1172,37 @@ int cmbpo_internal_launch_h3(cmbpo_mlp *m, MlpKernelArgs &a, hipStream_t s) {
     CMBPO_REQUIRE(lds <= 160 * 1024, "ens_h3: LDS budget exceeded (%zu B)", lds);
     const int n_here = k.m.n_items - item0;
     const int grid = n_here < n_cu ? n_here : n_cu;
-#define CMBPO_H3_CASE(S0_, OTP_, RT_)                                                                                  \
-  if (S0 == S0_ && OTP == OTP_ && rt == RT_) {                                                                         \
-    if (int rc = cmbpo_grant_lds(ens_h3_kernel<S0_, OTP_, RT_>, lds)) return rc;                                      \
-    hipLaunchKernelGGL((ens_h3_kernel<S0_, OTP_, RT_>), dim3(grid), dim3(kThreadsH), lds, s, k);                      \
+    const bool img = main && rt == 4 && stage_ahead(S0, 4) && g_h3_img_min_rows >= 0 &&
+                     (g_h3_img_min_rows == 0 ? n_here >= 2 * n_cu : a.n_rows >= g_h3_img_min_rows);
+    k.ximg = nullptr;
+    if (img) {
+      if (int rc = ensure_ximg(m, a.n_rows, a.ld_rows, (size_t)ximg_block_bytes(S0))) return rc;
+      k.ximg = reinterpret_cast<const char *>(m->d_ximg);
+      if (S0 == 2) hipLaunchKernelGGL(h3_ximage_kernel<2>, dim3(tiles), dim3(kThreadsH), 0, s, k.m, reinterpret_cast<char *>(m->d_ximg));
+      else hipLaunchKernelGGL(h3_ximage_kernel<3>, dim3(tiles), dim3(kThreadsH), 0, s, k.m, reinterpret_cast<char *>(m->d_ximg));
+      CMBPO_HIP_CHECK(hipGetLastError());
+    }
+#define CMBPO_H3_CASE_I(S0_, OTP_, RT_, IMG_)                                                                          \
+  if (S0 == S0_ && OTP == OTP_ && rt == RT_ && img == IMG_) {                                                          \
+    if (int rc = cmbpo_grant_lds(ens_h3_kernel<S0_, OTP_, RT_, IMG_>, lds)) return rc;                                \
+    hipLaunchKernelGGL((ens_h3_kernel<S0_, OTP_, RT_, IMG_>), dim3(grid), dim3(kThreadsH), lds, s, k);                \
   }
+#define CMBPO_H3_CASE(S0_, OTP_, RT_) CMBPO_H3_CASE_I(S0_, OTP_, RT_, false)
 #define CMBPO_H3_CASES(RT_)                                                                                            \
   CMBPO_H3_CASE(2, 2, RT_) CMBPO_H3_CASE(3, 2, RT_) CMBPO_H3_CASE(4, 2, RT_)                                           \
   CMBPO_H3_CASE(2, 4, RT_) CMBPO_H3_CASE(3, 4, RT_) CMBPO_H3_CASE(4, 4, RT_)
     CMBPO_H3_CASES(4) CMBPO_H3_CASES(2) CMBPO_H3_CASES(1)
+    CMBPO_H3_CASE_I(2, 2, 4, true) CMBPO_H3_CASE_I(3, 2, 4, true) CMBPO_H3_CASE_I(2, 4, 4, true) CMBPO_H3_CASE_I(3, 4, 4, true)
 #undef CMBPO_H3_CASES
 #undef CMBPO_H3_CASE
+#undef CMBPO_H3_CASE_I
     CMBPO_HIP_CHECK(hipGetLastError());
     return CMBPO_OK;
   };
   if (RT_tail) {
-    if (int rc = launch(RT, 0, full)) return rc;
-    return launch(RT_tail, tail_start, -1);
+    if (int rc = launch(RT, 0, full, true)) return rc;
+    return launch(RT_tail, tail_start, -1, false);
   }
-  return launch(RT, 0, -1);
+  return launch(RT, 0, -1, true);
 }
 

@@ -590,6 +590,7 @@ extern "C" void cmbpo_mlp_destroy(cmbpo_mlp_t *m) {
   if (m->d_blob) (void)hipFree(m->d_blob);
   if (m->d_split) (void)hipFree(m->d_split);
   if (m->d_h3) (void)hipFree(m->d_h3);
+  if (m->d_ximg) (void)hipFree(m->d_ximg);
   delete m;
 }
 

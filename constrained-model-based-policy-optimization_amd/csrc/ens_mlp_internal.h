@@ -67,6 +67,10 @@ struct cmbpo_mlp {
   unsigned long h3_version = ~0ul;
   size_t h3_off[3] = {0, 0, 0}, h3_stride[3] = {0, 0, 0}, h3_stats_off = 0;   // 16-B units
   int h3_s0 = 0, h3_otp = 0;   // k-slabs of the input layer, padded output tiles
+  // the split input image of a forward's rows, one block per 128-row tile (ens_h3.hip, h3_ximage_kernel): written and read
+  // by the launches of one forward, so forwards on one handle are stream-ordered (as they are for the weight images)
+  void *d_ximg = nullptr;
+  size_t ximg_tiles = 0, ximg_block = 0;   // blocks allocated, bytes per block
   // fp32 pack of layer l (pack_layout.h): n-tiles, k-groups, floats per member, device pointer
   int pack_tiles(int l) const { return l == 2 ? o_tiles : hidden / 32; }
   int pack_kg(int l) const { return (l == 0 ? in_pad : hidden) / 8; }

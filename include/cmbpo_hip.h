@@ -132,6 +132,12 @@ int cmbpo_set_ens_f16_min_rows(int rows);
 /* Tuning knob: 32-row tiles per item of the CMBPO_ENS_SPLIT_F16 kernel: 4 (128-row items, the throughput shape), 2 or 1
  * (the same kernel for rollout batches too small to give every CU a 128-row item); 0 (default) chooses by row count. */
 int cmbpo_set_ens_f16_row_tiles(int rt);
+/* Tuning knob: calls of the CMBPO_ENS_SPLIT_F16 forward with at least this many rows build the split input image once per
+ * row (a small launch in front of the main one, which reads it by LDS-DMA) instead of once per (member, row) inside the
+ * main launch; only main launches of 128-row items on the stage-ahead instances (input width <= 48) take it.  0 (default):
+ * from the row count at which every workgroup of the main launch has at least two items; < 0: never; 1: whenever the main
+ * launch has 128-row items.  The outputs do not depend on it, bit for bit. */
+int cmbpo_set_ens_f16_image_min_rows(int rows);
 
 /* ------------------------------------------------------------------------ *
  * Ensemble MLP handle: a 3-layer (in -> H -> H -> O) ensemble of E members.
@@ -175,7 +181,11 @@ int cmbpo_mlp_load_policy_flat(cmbpo_mlp_t *m, const float *d_flat, void *stream
  * NULL with act_dim 0.  Row i of the call is branch d_row_idx[i] (or i when
  * d_row_idx is NULL); d_n_rows (device int, may be NULL) overrides n_rows so a
  * captured launch follows a device-side alive count.  Outputs are indexed
- * [member][branch slot][out_dim] with leading dimension ld_rows. */
+ * [member][branch slot][out_dim] with leading dimension ld_rows.
+ * Forwards on one handle are stream-ordered: the handle owns the f16 weight images and the split input image of the call's
+ * rows (both allocated on first use; the input image for ceil(ld_rows / 128) row tiles, regrown -- with a device
+ * synchronisation -- when a call needs more), and a forward reads what its own launches wrote there.  CMBPO_ENOMEM
+ * with a message, and no launch, when an allocation fails. */
 int cmbpo_ens_forward(cmbpo_mlp_t *m, const float *d_obs, int obs_dim,
                       const float *d_act, int act_dim, const int32_t *d_row_idx,
                       const int32_t *d_n_rows, int n_rows, int ld_rows,
