@@ -280,6 +280,7 @@ SIGNATURES.update({
     "cmbpo_trainer_epoch_ex": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _i, _ep, _p]),
     "cmbpo_trainer_losses_ex": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _p, _ep, _p]),
     "cmbpo_trainer_set_column_weights": (_i, [_p, _p, _p, _i, _p]),
+    "cmbpo_trainer_set_column_kinds": (_i, [_p, _p, _i, _p]),
 })
 
 # start states of an imagined-rollout round (csrc/start_states.hip)

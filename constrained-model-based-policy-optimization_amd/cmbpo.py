@@ -67,6 +67,12 @@ path before the sampler's horizon, a time-out is target 0) and has ``FakeEnv`` e
 ``utils.pos_weight_level(p, omega)``; ``m_term_threshold`` keeps reading the column as it is.  ``save`` / ``load`` keep the
 four keys in ``column_weights_<epoch>.json``.  With the defaults nothing is attached.
 
+``m_term_loss='logistic'`` (needs ``m_learn_term``) trains the termination column with the Bernoulli negative
+log-likelihood on its output read as a logit (``PE.set_logistic_columns([-1])``) and builds ``FakeEnv`` with
+``term_loss='logistic'``: ``m_term_threshold`` is then a probability strictly inside (0, 1), compared as a logit.  The weights
+above go on applying, as weights on the Bernoulli term.  The learned cost column is not offered: ``FakeEnv`` reads it as a
+magnitude.  ``save`` / ``load`` keep the choice in ``term_loss_<epoch>.json`` (a missing file means 'gaussian').
+
 ``static_fns`` takes a ``statics.TaskRules``: user-defined termination / cost rules for the imagined rollouts, with
 precedence over ``task`` (which may itself be a name given to ``statics.register_task``).
 """
@@ -140,6 +146,22 @@ def _calibration_args(validate_horizon, use_model, stochastic, validate_calibrat
     return validate_calibration, calibrated_noise, (lo, hi)
 
 
+def _term_loss_args(learn_term, term_loss, term_threshold):
+    """``m_term_loss`` checked against ``m_learn_term`` and ``m_term_threshold``, or a ValueError in words."""
+    if term_loss not in ('gaussian', 'logistic'):
+        raise ValueError("m_term_loss: 'gaussian' or 'logistic', got %r" % (term_loss,))
+    if term_loss == 'logistic':
+        if not learn_term:
+            raise ValueError("m_term_loss='logistic' needs m_learn_term=True (and use_model): it is the likelihood of the "
+                             "termination column")
+        from .utils import logit_threshold
+        try:
+            logit_threshold(term_threshold)
+        except ValueError as e:
+            raise ValueError("m_term_threshold: %s" % e) from None
+    return term_loss
+
+
 COLUMN_WEIGHT_KEYS = ('m_term_pos_weight', 'm_term_loss_weight', 'm_cost_loss_weight', 'm_pos_weight_max')
 
 
@@ -196,10 +218,12 @@ class CMBPO:
                  m_validate_calibration=False, m_calibrated_noise=False, m_noise_temperature_range=(0.25, 4.0),
                  m_learn_term=False, m_term_threshold=0.5, m_term_members='elite',
                  m_term_pos_weight=1.0, m_term_loss_weight=1.0, m_cost_loss_weight=1.0, m_pos_weight_max=20.0,
-                 **_unused):
+                 m_term_loss='gaussian', **_unused):
         # column / class weights of the model's binary columns; refused in words before anything is built
         self._column_weights = _column_weight_args(bool(m_learn_term) and bool(use_model), bool(m_learn_cost), m_term_pos_weight,
                                                    m_term_loss_weight, m_cost_loss_weight, m_pos_weight_max)
+        # the likelihood of the termination column; likewise
+        self._m_term_loss = _term_loss_args(bool(m_learn_term) and bool(use_model), m_term_loss, m_term_threshold)
         # predictive calibration in the validation replay and, from its one-step row, the scale of the transition
         # noise; refused in words before anything is built
         self._validate_calibration, self._calibrated_noise, self._noise_temperature_range = _calibration_args(
@@ -288,13 +312,14 @@ class CMBPO:
                                    name='DynEns', loss=m_loss_type, hidden_dims=m_hidden_dims, lr=m_lr,
                                    num_networks=m_networks, num_elites=m_elites, use_scaler_in=m_use_scaler_in,
                                    use_scaler_out=m_use_scaler_out, decay=1e-6, max_logvar=.5, min_logvar=-10,
-                                   device=self.device)
+                                   device=self.device,
+                                   logistic_columns=[-1] if m_term_loss == 'logistic' else None)
             rules_task = self._task if static_fns is None else static_fns      # static_fns takes precedence over the task name
             self.fake_env = FakeEnv(true_environment=env, task=rules_task, model=self._model, predicts_delta=True,
                                     predicts_rew=True, predicts_cost=self._m_learn_cost,
                                     disagreement=bool(m_disagreement), rew_pessimism=m_rew_pessimism,
                                     cost_pessimism=m_cost_pessimism, predicts_term=self._m_learn_term,
-                                    term_threshold=m_term_threshold, term_members=m_term_members)
+                                    term_threshold=m_term_threshold, term_members=m_term_members, term_loss=m_term_loss)
             self.rollout_mode = rollout_mode
             self.model_buf = ModelBuffer(batch_size=self._rollout_batch_size, obs_dim=self.obs_dim, act_dim=self.act_dim,
                                          max_path_length=maxroll, device=self.device, iv_gae=bool(m_iv_gae),
@@ -624,6 +649,9 @@ class CMBPO:
                 import os
                 with open(os.path.join(savedir, 'term_head_%d.json' % self._epoch), 'w') as fh:
                     json.dump({'threshold': self.fake_env.term_threshold, 'members': self.fake_env.term_members}, fh)
+                # the column's likelihood, a file of its own: term_head_<epoch>.json keeps exactly its keys
+                with open(os.path.join(savedir, 'term_loss_%d.json' % self._epoch), 'w') as fh:
+                    json.dump({'m_term_loss': self._m_term_loss}, fh)
             if self._m_learn_term or self._m_learn_cost:      # the column weights of the fits, a file of their own
                 import json
                 import os
@@ -643,10 +671,29 @@ class CMBPO:
         if (kw['m_term_pos_weight'], kw['m_term_loss_weight'], kw['m_cost_loss_weight']) == (1.0, 1.0, 1.0):
             self._model.set_column_weights(None, None)
 
+    def _load_term_loss(self, savedir, timestep):
+        """The likelihood of the termination column that ``save`` wrote (a checkpoint from before it has no such file:
+        'gaussian'), set on the model before its weights and scalers come in."""
+        import json
+        import os
+        if not self._m_learn_term:
+            return None
+        path = os.path.join(savedir, 'term_loss_%d.json' % int(timestep))
+        term_loss = 'gaussian'
+        if os.path.exists(path):
+            with open(path) as fh:
+                term_loss = json.load(fh)['m_term_loss']
+        if term_loss not in ('gaussian', 'logistic'):
+            raise ValueError("%s: m_term_loss %r" % (path, term_loss))
+        self._m_term_loss = term_loss
+        self._model.set_logistic_columns([-1] if term_loss == 'logistic' else None)
+        return term_loss
+
     def load(self, savedir, timestep):
         """The model ``save`` wrote at epoch ``timestep`` and, with the termination head, its threshold and vote."""
         if not self._use_model:
             raise ValueError("load: the trainer was built with use_model=False, there is no model to load")
+        term_loss = self._load_term_loss(savedir, timestep)
         self._model.load(savedir, timestep)
         self._load_column_weights(savedir, timestep)
         if self._m_learn_term:
@@ -654,4 +701,4 @@ class CMBPO:
             import os
             with open(os.path.join(savedir, 'term_head_%d.json' % int(timestep))) as fh:
                 head = json.load(fh)
-            self.fake_env.set_term_head(head['threshold'], head['members'])
+            self.fake_env.set_term_head(head['threshold'], head['members'], loss=term_loss)

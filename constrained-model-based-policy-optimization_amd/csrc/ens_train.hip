@@ -91,6 +91,22 @@ struct LossCArgs : LossArgs {
   ColWeights c;            // sum w[row][d] (mean - t)^2
 };
 
+// Column kinds of the probabilistic losses (the definition stands in include/cmbpo_hip.h at
+// cmbpo_trainer_set_column_kinds): kind[d] != 0 reads the mean output of column d as a logit z and trains it with the Bernoulli
+// negative log-likelihood of y = (raw target > 0.5f), never through the output scaler.  Kernels that know the kinds are instances
+// of their own again; they always carry ColWeights (all ones from the trainer's pool when none are attached).
+__device__ __forceinline__ float bernoulli_nll(float z, bool y) {     // softplus(z) - y z, finite for every finite z
+  return fmaxf(z, 0.0f) - (y ? z : 0.0f) + log1pf(expf(-fabsf(z)));
+}
+__device__ __forceinline__ float sigmoid_of(float z) {
+  if (z >= 0.0f) return 1.0f / (1.0f + expf(-z));
+  const float ez = expf(z);
+  return ez / (1.0f + ez);
+}
+struct LossLArgs : LossCArgs {
+  const unsigned char *kind;   // [D]; sum of w (mean - t)^2 on Gaussian columns and of 2 w l on logistic ones (finalize halves)
+};
+
 __device__ __forceinline__ float scaled_target(const LossArgs &p, int e, int b, int d) {
   const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
   float t = p.targets[(size_t)row * p.D + d];
@@ -106,11 +122,19 @@ __global__ __launch_bounds__(kThreads) void loss_sums_kernel(const P p) {
   for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
     const int b = i / p.D, d = i - b * p.D;
     const float *orow = p.o + ((size_t)e * p.B + b) * p.O;
+    if constexpr (std::is_same<P, LossLArgs>::value) {
+      if (p.kind[d]) {
+        const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
+        const float traw = p.targets[(size_t)row * p.D + d];
+        s_mse += 2.0 * (double)(column_weight(p.c, d, traw) * bernoulli_nll(orow[d], traw > 0.5f));
+        continue;
+      }
+    }
     const float diff = orow[d] - scaled_target(p, e, b, d);
     if constexpr (std::is_same<P, LossWArgs>::value) {
       const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
       s_mse += (double)p.w[row] * (double)(diff * diff);
-    } else if constexpr (std::is_same<P, LossCArgs>::value) {
+    } else if constexpr (std::is_same<P, LossCArgs>::value || std::is_same<P, LossLArgs>::value) {
       const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
       s_mse += (double)column_weight(p.c, d, p.targets[(size_t)row * p.D + d]) * (double)(diff * diff);
     } else {
@@ -194,8 +218,12 @@ struct ColStatsArgs {
   double *loss_part;       // [E * tiles32][3]
 };
 
-template <int ROWS>
-__global__ __launch_bounds__(8 * ROWS) void col_stats_kernel(const ColStatsArgs p) {
+struct ColStatsLArgs : ColStatsArgs {
+  const unsigned char *kind;   // [D]: logistic columns stay out of sum w mse and sum w (var - mse)^2, and in sum lv^2
+};
+
+template <int ROWS, class A>
+__device__ __forceinline__ void col_stats_body(const A &p) {
   constexpr int NT = 8 * ROWS, NW = NT / 64;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int e = blockIdx.y, row0 = blockIdx.x * ROWS;
@@ -210,6 +238,9 @@ __global__ __launch_bounds__(8 * ROWS) void col_stats_kernel(const ColStatsArgs 
     float t = traw;
     if (p.out_mu) t = (t - p.out_mu[d]) / p.out_sig[d];
     const float *orow = p.o + ((size_t)e * p.B + row) * p.O;
+    if constexpr (std::is_same<A, ColStatsLArgs>::value) {
+      if (p.kind[d]) { s2 += (double)(orow[D + d] * orow[D + d]); continue; }
+    }
     const float diff = orow[d] - t;
     const float mse = diff * diff;
     const float w = column_weight(p.c, d, traw);
@@ -235,6 +266,11 @@ __global__ __launch_bounds__(8 * ROWS) void col_stats_kernel(const ColStatsArgs 
     }
   }
 }
+
+template <int ROWS>
+__global__ __launch_bounds__(8 * ROWS) void col_stats_kernel(const ColStatsArgs p) { col_stats_body<ROWS>(p); }
+template <int ROWS>
+__global__ __launch_bounds__(8 * ROWS) void col_stats_l_kernel(const ColStatsLArgs p) { col_stats_body<ROWS>(p); }
 
 // ------------------------------------------------------------------------------------------------------------
 // backward chain:  d2 = (d3 W2^T) * g2 ;  d1 = (d2 W1^T) * g1      (g = swish'(z) exported by the forward)
@@ -263,6 +299,9 @@ struct BwdXArgs : BwdArgs {
 };
 struct BwdCArgs : BwdArgs {
   ColWeights c;              // probabilistic heads (prob != 0) only; loss_part then holds the weighted sums (col_stats_kernel)
+};
+struct BwdLArgs : BwdCArgs {
+  const unsigned char *kind; // [D] column kinds; loss_part holds the sums over the Gaussian columns (col_stats_l_kernel)
 };
 
 // `ratio` of the MSPE loss, 0.05 * mean_all(mse) / mean_all((var - mse)^2): a constant of the step.  The two sums come from
@@ -311,10 +350,18 @@ __device__ __forceinline__ float output_delta(const P &p, int e, int row, int k,
     const float olds = clip ? scaled_old(p.x, src, p.D, dd, p.out_mu, p.out_sig) : 0.0f;
     return value_delta(orow[dd], t, clip, olds, clip ? *p.x.clip_c : 0.0f, p.x.w ? p.x.w[src] : 1.0f) * inv_bd;
   }
+  if constexpr (std::is_same<P, BwdLArgs>::value) {     // a logistic column: w (sigma(z) - y) on the raw logit and
+    if (p.kind[dd]) {                                   // target; its log-variance output keeps 'MSPE''s regulariser alone
+      if (k < p.D) return column_weight(p.c, dd, traw) * (sigmoid_of(orow[dd]) - (traw > 0.5f ? 1.0f : 0.0f)) * inv_bd;
+      return p.prob == 2 ? 0.0f : (0.1f * orow[k]) * inv_bd;
+    }
+  }
   const float diff = orow[dd] - t;
-  if constexpr (std::is_same<P, BwdCArgs>::value) {     // column / class weights: w on every data term, the
-    const float w = column_weight(p.c, dd, traw);       // log-variance regulariser stays plain; the host admits no 'MSE' head.
-    if (p.prob == 2) {                                  // (with w == 1 every product below is the plain one: same bits)
+  // column / class weights, also the Gaussian columns of a model with kinds: w on every data term, the log-variance
+  // regulariser stays plain; the host admits no 'MSE' head.  (With w == 1 every product below is the plain one: same bits.)
+  if constexpr (std::is_same<P, BwdCArgs>::value || std::is_same<P, BwdLArgs>::value) {
+    const float w = column_weight(p.c, dd, traw);
+    if (p.prob == 2) {
       const float iv = expf(-orow[p.D + dd]);
       return (k < p.D) ? w * (iv * diff) * inv_bd : w * (0.5f - 0.5f * iv * diff * diff) * inv_bd;
     }
@@ -1893,6 +1940,9 @@ struct cmbpo_trainer {
   double *old_var_part;          // [kOldVarParts] partial sums of a clipped step's old_var, then (as a float) its clip range c
   float *colw;                   // [2][D] col_weight | pos_weight of cmbpo_trainer_set_column_weights
   bool colw_on = false;          // ... attached: the step, the epoch and `self.loss` run their column-weighted instances
+  float *ones;                   // [2][D] all-ones weights for the kind instances when no column weights are attached
+  unsigned char *kind;           // [D] column kinds of cmbpo_trainer_set_column_kinds
+  bool kind_on = false;          // ... attached (some column logistic): the kind instances run
   size_t wsize[3], bsize[3];
   float *opmax;                  // [E][ceil(max_batch / 32)][kOpMax] per-tile largest |x|, |h1|, |h2|, |d1|, |d2|, |d3| of the step
   // the backward chain on the f16 path (bwd_chain_h_kernel; 512-wide, at most 64 padded outputs): two-piece images of W1^T and
@@ -2185,18 +2235,27 @@ int launch_old_var(cmbpo_trainer *t, const float *d_targets, const float *d_old_
   return CMBPO_OK;
 }
 
-ColWeights col_weights_of(const cmbpo_trainer *t) { return ColWeights{t->colw, t->colw + t->D}; }
+ColWeights col_weights_of(const cmbpo_trainer *t) {
+  const float *w = t->colw_on ? t->colw : t->ones;
+  return ColWeights{w, w + t->D};
+}
 
 // the weighted loss statistics of an 'MSPE' step over the forward's (col_stats_kernel), in the layout of the forward that ran
 int launch_col_stats(cmbpo_trainer *t, const float *d_targets, const int32_t *d_idx, int idx_stride, int batch, hipStream_t s) {
-  ColStatsArgs a{};
+  ColStatsLArgs a{};
   a.o = t->o; a.targets = d_targets; a.idx = d_idx; a.idx_stride = idx_stride;
   a.out_mu = t->m->out_mu(); a.out_sig = t->m->out_sig();
   a.B = batch; a.O = t->O; a.D = t->D; a.tiles32 = cmbpo_ceil_div(batch, 32);
   a.c = col_weights_of(t);
   a.loss_part = t->loss_part;
-  if (t->b16 && t->b16_fwd) hipLaunchKernelGGL(col_stats_kernel<64>, dim3(cmbpo_ceil_div(batch, 64), t->E), dim3(512), 0, s, a);
-  else hipLaunchKernelGGL(col_stats_kernel<32>, dim3(a.tiles32, t->E), dim3(256), 0, s, a);
+  const ColStatsArgs &c = a;
+  const bool rows64 = t->b16 && t->b16_fwd;
+  if (t->kind_on) {
+    a.kind = t->kind;
+    if (rows64) hipLaunchKernelGGL(col_stats_l_kernel<64>, dim3(cmbpo_ceil_div(batch, 64), t->E), dim3(512), 0, s, a);
+    else hipLaunchKernelGGL(col_stats_l_kernel<32>, dim3(a.tiles32, t->E), dim3(256), 0, s, a);
+  } else if (rows64) hipLaunchKernelGGL(col_stats_kernel<64>, dim3(cmbpo_ceil_div(batch, 64), t->E), dim3(512), 0, s, c);
+  else hipLaunchKernelGGL(col_stats_kernel<32>, dim3(a.tiles32, t->E), dim3(256), 0, s, c);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -2301,6 +2360,7 @@ extern "C" int cmbpo_trainer_create(cmbpo_trainer_t **out, cmbpo_mlp_t *m, int m
   const size_t oom = take((size_t)E * cmbpo_ceil_div(max_batch, 32) * kOpMax);
   const size_t oov = take(2 * (size_t)(kOldVarParts + 1));   // doubles
   const size_t ocw = take(2 * (size_t)t->D);
+  const size_t oon = take(2 * (size_t)t->D), okd = take(((size_t)t->D + 3) / 4);   // (kinds: D bytes)
   hipError_t err = hipMalloc(reinterpret_cast<void **>(&t->pool), off * sizeof(float));
   if (err != hipSuccess) {
     cmbpo_set_error("cmbpo_trainer_create: hipMalloc(%zu) failed: %s", off * sizeof(float), hipGetErrorString(err));
@@ -2328,6 +2388,8 @@ extern "C" int cmbpo_trainer_create(cmbpo_trainer_t **out, cmbpo_mlp_t *m, int m
   t->opmax = P + oom;
   t->old_var_part = reinterpret_cast<double *>(P + oov);
   t->colw = P + ocw;
+  t->ones = P + oon;
+  t->kind = reinterpret_cast<unsigned char *>(P + okd);
   if (H == 512 && !t->fused && t->OPk <= 64) {
     // images for the f16 training kernels (bwd_chain_h_kernel, fwd_train_h_kernel); without them the fp32 kernels run
     t->b16_s3 = cmbpo_ceil_div(t->OPk, 16);
@@ -2452,6 +2514,33 @@ extern "C" int cmbpo_trainer_set_column_weights(cmbpo_trainer_t *t, const float 
   return CMBPO_OK;
 }
 
+extern "C" int cmbpo_trainer_set_column_kinds(cmbpo_trainer_t *t, const unsigned char *h_kind, int target_dim, void *stream) {
+  const char *who = "cmbpo_trainer_set_column_kinds";
+  // every check stands before the first HIP call
+  int n_logistic = 0;
+  if (h_kind) {
+    CMBPO_REQUIRE(target_dim >= 1, "%s: target_dim %d", who, target_dim);
+    for (int d = 0; d < target_dim; ++d) {
+      CMBPO_REQUIRE(h_kind[d] <= 1, "%s: kind[%d] = %d is neither 0 (Gaussian) nor 1 (logistic)", who, d, (int)h_kind[d]);
+      n_logistic += h_kind[d];
+    }
+    CMBPO_REQUIRE(n_logistic < target_dim, "%s: every column is logistic ('MSPE' has no ratio then, and a model with no Gaussian "
+                  "column is not a dynamics model)", who);
+  }
+  CMBPO_REQUIRE(t != nullptr, "%s: handle is NULL", who);
+  if (!n_logistic) { t->kind_on = false; return CMBPO_OK; }
+  CMBPO_REQUIRE(t->prob, "%s: column kinds are for probabilistic ('MSPE' / 'NLL') heads, not for a deterministic ('MSE') head", who);
+  CMBPO_REQUIRE(target_dim == t->D, "%s: target_dim %d != %d", who, target_dim, t->D);
+  hipStream_t s = (hipStream_t)stream;
+  const int D = t->D;
+  const std::vector<float> one(2 * (size_t)D, 1.0f);
+  CMBPO_HIP_CHECK(hipMemcpyAsync(t->ones, one.data(), one.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  CMBPO_HIP_CHECK(hipMemcpyAsync(t->kind, h_kind, D, hipMemcpyHostToDevice, s));
+  CMBPO_HIP_CHECK(hipStreamSynchronize(s));   // the host arrays may go out of scope
+  t->kind_on = true;
+  return CMBPO_OK;
+}
+
 extern "C" int cmbpo_trainer_reset_optimizer(cmbpo_trainer_t *t, void *stream) {
   CMBPO_REQUIRE(t != nullptr, "cmbpo_trainer_reset_optimizer: handle is NULL");
   hipStream_t s = (hipStream_t)stream;
@@ -2539,6 +2628,16 @@ int trainer_step(const char *who, cmbpo_trainer_t *t, const float *d_inputs, int
   if (x) {
     b.x = *x;
     rc = launch_bwd_any<BwdXArgs>(t, b, batch, s);
+  } else if (t->kind_on) {
+    if (b.prob == 1) {
+      rc = launch_col_stats(t, d_targets, d_idx, idx_stride, batch, s);
+      if (rc != CMBPO_OK) return rc;
+    }
+    BwdLArgs l{};
+    static_cast<BwdArgs &>(l) = b;
+    l.c = col_weights_of(t);
+    l.kind = t->kind;
+    rc = launch_bwd_any<BwdLArgs>(t, l, batch, s);
   } else if (t->colw_on) {
     if (b.prob == 1) {
       rc = launch_col_stats(t, d_targets, d_idx, idx_stride, batch, s);
@@ -2609,6 +2708,12 @@ int trainer_losses(const char *who, cmbpo_trainer_t *t, const float *d_inputs, i
     const int gx = min(cmbpo_ceil_div(rows * t->D, kThreads), 64);
     if (d_weights) {
       hipLaunchKernelGGL(loss_sums_kernel<LossWArgs>, dim3(gx, E), dim3(kThreads), 0, s, l);
+    } else if (t->kind_on) {
+      LossLArgs ll{};
+      static_cast<LossArgs &>(ll) = l;
+      ll.c = col_weights_of(t);
+      ll.kind = t->kind;
+      hipLaunchKernelGGL(loss_sums_kernel<LossLArgs>, dim3(gx, E), dim3(kThreads), 0, s, ll);
     } else if (t->colw_on) {
       LossCArgs lc{};
       static_cast<LossArgs &>(lc) = l;

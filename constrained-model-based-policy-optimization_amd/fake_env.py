@@ -34,6 +34,9 @@ output column, the LAST one, trained on the real ``done`` flags, and a branch al
 any member's (``'any'``) or more than half of all members' (``'majority'``).  The cost keeps the rule's own ``done``.  ``step()``
 adds ``info['term_pred']`` (the elite's value of the column) and ``info['term_votes']`` (members above the threshold, uint8);
 ``set_term_head(threshold, members)`` changes the head later.  Off (the default) nothing changes.
+``term_loss='logistic'`` (a model whose last column is logistic, ``PE(logistic_columns=[-1])``): the column is a
+logit z, ``term_threshold`` a probability tau strictly inside (0, 1), and the test ``sigma(z) > tau`` runs in the same kernel as
+``z > float32(logit(tau))``; ``info['term_pred']`` is ``sigma(z)`` in float32.
 
 ``replay(...)`` has no counterpart in the reference: it replays windows of real steps through the model with the recorded
 actions and returns, per horizon, how far the predictions are from the recording (open-loop model validation).
@@ -52,7 +55,7 @@ from . import _lib, statics
 class FakeEnv:
     def __init__(self, true_environment, task, model, predicts_delta, predicts_rew, predicts_cost,
                  seed=0, disagreement=False, rew_pessimism=0.0, cost_pessimism=0.0,
-                 predicts_term=False, term_threshold=0.5, term_members='elite'):
+                 predicts_term=False, term_threshold=0.5, term_members='elite', term_loss='gaussian'):
         self.env = true_environment
         self.obs_dim = int(np.prod(self.observation_space.shape))
         self.act_dim = int(np.prod(self.action_space.shape))
@@ -85,9 +88,13 @@ class FakeEnv:
         self._disagreement = bool(disagreement)
         self.rew_pessimism = self.cost_pessimism = 0.0
         self.set_pessimism(rew_pessimism, cost_pessimism)
-        self.term_threshold, self.term_members = 0.5, 'elite'
+        self.term_threshold, self.term_members, self.term_loss = 0.5, 'elite', 'gaussian'
+        if term_loss not in ('gaussian', 'logistic'):
+            raise ValueError(f"term_loss: 'gaussian' or 'logistic', got {term_loss!r}")
         if self._predicts_term:
-            self.set_term_head(term_threshold, term_members)
+            self.set_term_head(term_threshold, term_members, term_loss)
+        elif term_loss != 'gaussian':
+            raise ValueError("term_loss='logistic' needs predicts_term=True: the model has no termination column")
         self.device = model.device
         # bench.py sets this to a list to collect (start, end) HIP events around the dominant kernel
         self.kernel_events = None
@@ -118,23 +125,39 @@ class FakeEnv:
     def predicts_term(self):
         return self._predicts_term
 
-    def set_term_head(self, threshold, members):
-        """Threshold and vote ('elite' / 'any' / 'majority') of the learned termination head."""
+    def set_term_head(self, threshold, members, loss=None):
+        """Threshold and vote ('elite' / 'any' / 'majority') of the learned termination head; ``loss`` ('gaussian' /
+        'logistic', None: as it is) says how the column was trained.  Under 'logistic' the threshold is a probability strictly
+        inside (0, 1)."""
         if not self._predicts_term:
             raise ValueError("set_term_head needs predicts_term=True: the model has no termination column")
+        loss = self.term_loss if loss is None else loss
+        if loss not in ('gaussian', 'logistic'):
+            raise ValueError(f"term_loss: 'gaussian' or 'logistic', got {loss!r}")
         threshold = float(threshold)
         if not np.isfinite(threshold):
             raise ValueError(f"term_threshold must be a finite number, got {threshold}")
+        if loss == 'logistic':
+            from .utils import logit_threshold
+            logit_threshold(threshold)
         if members not in _lib.TERM_MEMBERS:
             raise ValueError(f"term_members: 'elite', 'any' or 'majority', got {members!r}")
-        self.term_threshold, self.term_members = threshold, members
+        self.term_threshold, self.term_members, self.term_loss = threshold, members, loss
+
+    @property
+    def term_kernel_threshold(self):
+        """The number the kernels compare the termination column with: ``term_threshold``, under 'logistic' its float32 logit."""
+        if self.term_loss == 'logistic':
+            from .utils import logit_threshold
+            return logit_threshold(self.term_threshold)
+        return self.term_threshold
 
     def term_head_struct(self, term_pred=None, term_votes=None):
         """The ``cmbpo_term_head_t`` of this head (None without one); the two optional outputs are device tensors or None."""
         if not self._predicts_term:
             return None
         th = _lib.TermHeadStruct()
-        th.threshold, th.members = self.term_threshold, _lib.TERM_MEMBERS[self.term_members]
+        th.threshold, th.members = self.term_kernel_threshold, _lib.TERM_MEMBERS[self.term_members]
         th.term_pred, th.term_votes = _lib.ptr(term_pred), _lib.ptr(term_votes)
         return th
 
@@ -150,7 +173,8 @@ class FakeEnv:
         out: dict with next_obs[B,obs], rew[B], term[B] u8, cost[B], dkl_path[B], ep_var_mean[B]
         (and optionally ep_var[B,obs]).  scratch: (mean, var)[E,B,output_dim].  With `disagreement` on, out also needs
         rew_var[B] and cost_var[B]; they are filled, and rew / cost are the penalised values.  With `predicts_term`, term is
-        rule_done or learned_done, and out's optional term_pred[B] / term_votes[B] u8 are filled.
+        rule_done or learned_done, and out's optional term_pred[B] / term_votes[B] u8 are filled (under
+        ``term_loss='logistic'`` term_pred carries the logit).
         """
         B = obs.shape[0]
         if noise is not None and not (noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
@@ -249,6 +273,8 @@ class FakeEnv:
             info["ensemble_rew_var"], info["ensemble_cost_var"] = rv, cv
         if self._predicts_term:
             tp, tv = out["term_pred"], out["term_votes"]
+            if self.term_loss == 'logistic':
+                tp = torch.sigmoid(tp)      # float32, of the kernel's value
             if was_np:
                 tp, tv = tp.cpu().numpy(), tv.cpu().numpy()
             info["term_pred"], info["term_votes"] = tp, tv

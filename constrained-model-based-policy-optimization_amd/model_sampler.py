@@ -229,7 +229,10 @@ class ModelSampler:
             pool.set_disagreement(getattr(self.env, "disagreement", False), getattr(self.env, "rew_pessimism", 0.0),
                                   getattr(self.env, "cost_pessimism", 0.0))
             # ... and its learned termination head
-            pool.set_term_head(getattr(self.env, "predicts_term", False), getattr(self.env, "term_threshold", 0.5),
+            # (the number the kernels compare with: under term_loss='logistic' the logit of the threshold, and the pool's
+            # term_pred_t then carries the logit)
+            pool.set_term_head(getattr(self.env, "predicts_term", False),
+                               getattr(self.env, "term_kernel_threshold", getattr(self.env, "term_threshold", 0.5)),
                                getattr(self.env, "term_members", "elite"))
             if observations is None:
                 fill(pool.t["cur_obs"])

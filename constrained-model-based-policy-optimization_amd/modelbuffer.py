@@ -290,7 +290,9 @@ class ModelBuffer:
     def set_term_head(self, on, threshold=0.5, members='elite'):
         """End imagined branches where the model's termination column says so (``FakeEnv(predicts_term=True)``: the sampler
         hands its environment's head over at every reset); legal whenever nothing is stored.  The step's ``term_pred_t`` /
-        ``term_votes_t`` [B] are kept beside the per-step arrays."""
+        ``term_votes_t`` [B] are kept beside the per-step arrays.  ``threshold`` is the number the kernel compares with: for a
+        logistic head (``FakeEnv(term_loss='logistic')``) the logit of the probability, and ``term_pred_t`` then
+        carries the logit."""
         head = None
         if on:
             threshold = float(threshold)

@@ -18,7 +18,8 @@ elite ranking) and runs every ``sess.run(train_op)`` / ``sess.run(self.loss)`` a
 over device-resident data (``csrc/ens_train.hip``).  Losses: 'MSPE' (dynamics) and 'MSE'
 (critics), the two every shipped config uses, 'NLL', and for 'MSE' the sample-weighted and clipped
 variants (``weighted`` / ``clip_loss``); for 'MSPE' / 'NLL' a weight per target column and a
-class weight per column (``col_weight`` / ``pos_weight``).
+class weight per column (``col_weight`` / ``pos_weight``) and a Bernoulli likelihood for binary target columns
+(``logistic_columns``).
 """
 import ctypes as C
 import itertools
@@ -260,6 +261,16 @@ class EnsembleTrainer:
                 self._h, _lib.ptr(col_weight), _lib.ptr(pos_weight), 0 if a is None else int(a.shape[0]),
                 _lib.current_stream()), "cmbpo_trainer_set_column_weights")
 
+    def set_column_kinds(self, kinds=None):
+        """Column kinds of a probabilistic head (a uint8 host array of target_dim entries, 0 Gaussian / 1 logistic; None or all
+        zeros detaches): trainer state that ``step``, ``epoch`` and ``losses`` honour."""
+        if kinds is not None:
+            kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
+        with torch.cuda.device(self.mlp.device):
+            _lib.check(_lib.lib().cmbpo_trainer_set_column_kinds(
+                self._h, _lib.ptr(kinds), 0 if kinds is None else int(kinds.shape[0]), _lib.current_stream()),
+                "cmbpo_trainer_set_column_kinds")
+
     @property
     def steps_done(self):
         return int(_lib.lib().cmbpo_trainer_steps_done(self._h))
@@ -301,6 +312,28 @@ def column_weight_array(w, out_dim, what):
     if not np.all(np.isfinite(a) & (a >= 0)):
         raise ValueError("%s: entries are finite numbers >= 0; got %r" % (what, a.tolist()))
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def column_kind_array(cols, out_dim, is_probabilistic=True, loss_type=None):
+    """``logistic_columns`` of :class:`PE` as a uint8 array of ``out_dim`` kinds (1 logistic), None for None / ``()``: a list
+    of columns, negative ones counting from the end."""
+    if cols is None:
+        return None
+    out_dim = int(out_dim)
+    cols = [cols] if np.isscalar(cols) else list(cols)
+    if not cols:
+        return None
+    kinds = np.zeros(out_dim, np.uint8)
+    for k in cols:
+        if isinstance(k, (bool, np.bool_)) or int(k) != k or not -out_dim <= int(k) < out_dim:
+            raise ValueError("logistic_columns: column %r of %d" % (k, out_dim))
+        kinds[int(k)] = 1
+    if not is_probabilistic:
+        raise NotImplementedError("logistic_columns are for probabilistic models ('MSPE', 'NLL'); got loss %r" % (loss_type,))
+    if kinds.all():
+        raise ValueError("logistic_columns: every column of %d is logistic ('MSPE' has no ratio then, and a model with no "
+                         "Gaussian column is not a dynamics model)" % out_dim)
+    return kinds
 
 
 class TrainControl:
@@ -412,11 +445,14 @@ class PE(TrainControl):
     def __init__(self, in_dim, out_dim, name="BNN", hidden_dims=(512, 512), num_networks=7,
                  num_elites=5, loss="MSPE", activation="swish", use_scaler_in=False,
                  use_scaler_out=False, device=None, lr=1e-3, decay=1e-4, max_logvar=.5, min_logvar=-6,
-                 clip_loss=False, kl_cliprange=0.1, weighted=False, col_weight=None, pos_weight=None, **_unused):
+                 clip_loss=False, kl_cliprange=0.1, weighted=False, col_weight=None, pos_weight=None, logistic_columns=None,
+                 **_unused):
         hidden_dims = tuple(int(h) for h in hidden_dims)
         self.loss_type, self._out_dim = loss, int(out_dim)
         self._trainer = None
+        self.scaler_out = None
         self.set_column_weights(col_weight, pos_weight)     # (checked before anything is created on the device)
+        self.set_logistic_columns(logistic_columns)
         # clipped / sample-weighted value losses (pe.py:67-68,150,232-244): the deterministic 'MSE' head only
         if (clip_loss or weighted) and loss != "MSE":
             raise NotImplementedError("clip_loss / weighted are provided for loss='MSE' (the clipped 'NLL' loss needs "
@@ -499,6 +535,8 @@ class PE(TrainControl):
         if scaler_out is not None and self.scaler_out is not None:
             self.scaler_out.cached_mu = np.asarray(scaler_out[0], np.float32).reshape(1, -1)
             self.scaler_out.cached_var = np.asarray(scaler_out[1], np.float32).reshape(1, -1)
+            if self._pin_logistic_scaler():
+                scaler_out = (self.scaler_out.cached_mu, self.scaler_out.cached_var)
         self.mlp.load(weights, biases,
                       in_scaler=scaler_in if self.use_scaler_in else None,
                       out_scaler=scaler_out if self.use_scaler_out else None)
@@ -632,7 +670,8 @@ class PE(TrainControl):
 
     # -- prediction --------------------------------------------------------------
     def predict_ensemble(self, inputs, act=None, row_idx=None, out=None):
-        """(mean, var)[E, B, out] for 2-D inputs (pe.py:688-697).
+        """(mean, var)[E, B, out] for 2-D inputs (pe.py:688-697).  In a logistic column (``logistic_columns``) the
+        mean is the logit itself (``utils.sigmoid`` gives the probability) and the variance means nothing.
 
         ``inputs`` is x[B, in] (or obs[B, obs] with ``act`` given separately, which saves
         the concat of fake_env.py:81).  The 3-D input path (pe.py:705-713) is unused by the
@@ -667,7 +706,8 @@ class PE(TrainControl):
     def predict(self, inputs, row_idx=None, out=None):
         """Mean over ALL members (pe.py:338-343, 648-669); probabilistic ensembles return (mean, var) with the
         disagreement of the member means added to the variance (pe.py:326-333; the member forward is the HIP kernel, the
-        reduction over the 7 members is two torch calls -- no caller of the training loop uses it)."""
+        reduction over the 7 members is two torch calls -- no caller of the training loop uses it).  In a logistic column
+        (``logistic_columns``) the mean is the mean of the members' logits."""
         if self.is_probabilistic:
             # pe.py:326-333: mean over members; var = mean member variance + variance of the member means
             assert len(inputs.shape) == 2
@@ -703,6 +743,35 @@ class PE(TrainControl):
         if self._trainer is not None:
             self._trainer.set_column_weights(cw, pw)
 
+    def set_logistic_columns(self, cols=None):
+        """Target columns trained with the Bernoulli negative log-likelihood on the mean output read as a logit (DESIGN §3v;
+        the definition stands in include/cmbpo_hip.h at cmbpo_trainer_set_column_kinds): a list of columns, negative ones
+        counting from the end; None or ``()`` detaches.  The output scaler is pinned to the identity in those columns, so
+        ``predict`` / ``predict_ensemble`` return the logit there.  ``col_weight`` / ``pos_weight`` go on applying, as weights on
+        the Bernoulli term."""
+        kinds = column_kind_array(cols, self._out_dim, self.is_probabilistic, self.loss_type)
+        self.column_kinds = kinds
+        if self._pin_logistic_scaler() and getattr(self, "finalized", False):
+            self.mlp.set_scalers(None, (self.scaler_out.cached_mu, self.scaler_out.cached_var))
+        if self._trainer is not None:
+            self._trainer.set_column_kinds(kinds)
+
+    @property
+    def logistic_columns(self):
+        return () if self.column_kinds is None else tuple(int(k) for k in np.nonzero(self.column_kinds)[0])
+
+    def _pin_logistic_scaler(self):
+        """The forward de-scales every mean as mean * sig + mu and the trainer ignores the scaler on logistic columns: mu = 0,
+        var = 1 there.  True if there was something to pin."""
+        if self.column_kinds is None or self.scaler_out is None:
+            return False
+        on = self.column_kinds.astype(bool)
+        self.scaler_out.cached_mu = np.array(self.scaler_out.cached_mu, np.float32)
+        self.scaler_out.cached_var = np.array(self.scaler_out.cached_var, np.float32)
+        self.scaler_out.cached_mu[:, on] = 0.0
+        self.scaler_out.cached_var[:, on] = 1.0
+        return True
+
     # -- training hooks (device side of TrainControl.train) -------------------------
     def _ensure_trainer(self, batch_size):
         if self._trainer is not None and self._trainer.max_batch >= batch_size:
@@ -721,6 +790,8 @@ class PE(TrainControl):
             self._trainer.set_moments(1, vw, vb, steps)
         if self.col_weight is not None or self.pos_weight is not None:
             self._trainer.set_column_weights(self.col_weight, self.pos_weight)
+        if self.column_kinds is not None:
+            self._trainer.set_column_kinds(self.column_kinds)
         return self._trainer
 
     def validate(self, inputs, targets):
@@ -768,6 +839,7 @@ class PE(TrainControl):
             self.scaler_in.fit(rows_of(inputs, train_rows_h, c["train_rows"]))
         if self.use_scaler_out:
             self.scaler_out.fit(rows_of(targets, train_rows_h, c["train_rows"]))
+            self._pin_logistic_scaler()
         c["tr"] = self._ensure_trainer(batch_size)
         self.mlp.set_scalers(
             (self.scaler_in.cached_mu, self.scaler_in.cached_var) if self.use_scaler_in else None,
@@ -833,10 +905,11 @@ def build_PE(in_dim, out_dim, name="BNN", hidden_dims=(200, 200, 200), num_netwo
              loss="MSPE", activation="swish", output_activation=None, decay=1e-4, lr=1e-3,
              lr_decay=None, decay_steps=None, use_scaler_in=False, use_scaler_out=False,
              clip_loss=False, kl_cliprange=0.1, max_logvar=.5, min_logvar=-6, session=None, device=None,
-             col_weight=None, pos_weight=None):
+             col_weight=None, pos_weight=None, logistic_columns=None):
     """Same signature as models/pens/pe_factory.py:9-29 (Adam with a constant learning rate; lr_decay is unused by
     every shipped config).  ``clip_loss`` / ``kl_cliprange``: the clipped value loss of 'MSE' models (PE, DESIGN §3j);
-    ``col_weight`` / ``pos_weight``: column and class weights of probabilistic models (PE.set_column_weights)."""
+    ``col_weight`` / ``pos_weight``: column and class weights of probabilistic models (PE.set_column_weights, DESIGN §3s);
+    ``logistic_columns``: binary target columns under the Bernoulli likelihood (PE.set_logistic_columns)."""
     if output_activation is not None:
         raise NotImplementedError("output activations are unused by every shipped config")
     if lr_decay is not None:
@@ -845,4 +918,4 @@ def build_PE(in_dim, out_dim, name="BNN", hidden_dims=(200, 200, 200), num_netwo
               num_elites=num_elites, loss=loss, activation=activation, use_scaler_in=use_scaler_in,
               use_scaler_out=use_scaler_out, device=device, lr=lr, decay=decay, max_logvar=max_logvar,
               min_logvar=min_logvar, clip_loss=clip_loss, kl_cliprange=kl_cliprange, col_weight=col_weight,
-              pos_weight=pos_weight)
+              pos_weight=pos_weight, logistic_columns=logistic_columns)

@@ -5,6 +5,8 @@ The variant is the RESOLVED dict (ray-tune ``sample_from`` entries already evalu
 (``get_env_from_params`` builds gym / safety-gym environments in the reference, which are out of scope here)."""
 from copy import deepcopy
 
+import numpy as np
+
 
 def pos_weight_level(p, omega):
     """Where a 0/1 target column of positive rate ``p`` settles under the class weight ``omega`` (``PE(pos_weight=)``,
@@ -14,6 +16,33 @@ def pos_weight_level(p, omega):
         raise ValueError("pos_weight_level: 0 <= p <= 1 and omega >= 0 expected, got %r, %r" % (p, omega))
     den = omega * p + 1.0 - p
     return omega * p / den if den > 0.0 else 0.0
+
+
+def sigmoid(z):
+    """sigma(z) of a logistic model column (``PE(logistic_columns=)``), float64, without overflow: 1 / (1 + exp(-z))
+    for z >= 0, exp(z) / (1 + exp(z)) otherwise."""
+    z = np.asarray(z, np.float64)
+    ez = np.exp(-np.abs(z))
+    out = np.where(z >= 0, 1.0 / (1.0 + ez), ez / (1.0 + ez))
+    return out if out.ndim else float(out)
+
+
+def logit(p):
+    """log(p / (1 - p)) in float64 for a probability strictly inside (0, 1): the inverse of :func:`sigmoid`."""
+    p = float(p)
+    if not 0.0 < p < 1.0:       # (written positively: NaN is refused)
+        raise ValueError("logit: a probability strictly inside (0, 1) expected, got %r" % (p,))
+    return float(np.log(p / (1.0 - p)))
+
+
+def logit_threshold(tau):
+    """The float32 number a logistic termination head compares its logit with: sigma(z) > tau is defined as
+    z > float32(log(tau / (1 - tau))) (include/cmbpo_hip.h at cmbpo_trainer_set_column_kinds)."""
+    try:
+        return float(np.float32(logit(tau)))
+    except (TypeError, ValueError):
+        raise ValueError("a logistic termination head reads term_threshold as a probability strictly inside (0, 1), "
+                         "got %r" % (tau,)) from None
 
 
 def get_cpobuffer(env, *args, **kwargs):

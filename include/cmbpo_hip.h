@@ -887,6 +887,29 @@ int cmbpo_trainer_losses_ex(cmbpo_trainer_t *t, const float *d_inputs, int in_di
  * trainer, a deterministic head (its per-sample weights go through cmbpo_trainer_step_ex), target_dim != the head's. */
 int cmbpo_trainer_set_column_weights(cmbpo_trainer_t *t, const float *h_col_weight, const float *h_pos_weight,
                                      int target_dim, void *stream);
+/* Column kinds of the probabilistic train losses: a Bernoulli likelihood for binary target columns; DESIGN §3v.  One host array
+ * h_kind of target_dim bytes: 0 Gaussian (the formulas above, term for term), 1 logistic.  NULL or all zeros detaches (the
+ * kernels that ran before run again, bit for bit).  For a logistic column d, member e, batch row b with gathered data row r:
+ *     z = o[e][b][d]                       the raw mean output, read as a logit; the output scaler is NOT applied to this
+ *                                          column, neither to the target nor to the output
+ *     y = targets[r][d] > 0.5f ? 1 : 0     on the RAW float32 target, written positively: a NaN target is 0 (the rule of
+ *                                          cmbpo_trainer_set_column_weights)
+ *     w = col_weight[d] * (y ? pos_weight[d] : 1)   with column weights attached, else 1
+ *     l = max(z, 0) - y z + log1p(exp(-|z|))        = softplus(z) - y z, finite for every finite z
+ *     sigma(z) = 1 / (1 + exp(-z)) for z >= 0, exp(z) / (1 + exp(z)) otherwise
+ * For both losses total_e adds mean(w l) over the logistic elements (the divisor stays B D), so d/dz = w (sigma(z) - y) / (B D).
+ * The log-variance output D + d of a logistic column has no data term: under 'MSPE' it keeps the unweighted regulariser alone
+ * (delta 0.1 lv / (B D)), under 'NLL' its delta is 0; nothing in the rollout reads that variance.  'MSPE''s
+ * ratio = 0.05 sum w mse / sum w (var - mse)^2 runs over the Gaussian columns only (all members, as before).
+ * `self.loss` (cmbpo_trainer_losses) = mean over (row, column) of 0.5 w (m - t')^2 on Gaussian columns and w l on logistic ones.
+ * With a class weight omega on a logistic column of positive rate p the fitted odds are omega times the true odds: the level is
+ * still q = omega p / (omega p + 1 - p).
+ * Reading the column: p = sigma(z); the test sigma(z) > tau is z > (float)log(tau / (1 - tau)), the logit taken in double on
+ * the host for tau strictly inside (0, 1).
+ * The kinds are copied to the device and are trainer state, like the column weights, and combine with them.  The *_ex entries
+ * go on refusing probabilistic heads.  Refused (CMBPO_EINVAL before any device work): a NULL trainer, a deterministic head,
+ * target_dim != the head's, a kind outside {0, 1}, an array that makes every column logistic. */
+int cmbpo_trainer_set_column_kinds(cmbpo_trainer_t *t, const unsigned char *h_kind, int target_dim, void *stream);
 long cmbpo_trainer_steps_done(const cmbpo_trainer_t *t);
 /* Which kernels a training step of this trainer runs: bit 0 the f16 backward chain, bit 1 the f16 training forward
  * (0: the fp32 kernels; -1: NULL handle).  Fixed at creation by the network's shapes. */
