@@ -191,6 +191,25 @@ SIGNATURES.update({
 })
 
 
+COST_MAGNITUDE, COST_LOGISTIC = 0, 1     # CMBPO_COST_*: how the learned-cost column is read
+COST_KINDS = {"gaussian": COST_MAGNITUDE, "logistic": COST_LOGISTIC}
+
+
+class CostHeadStruct(C.Structure):
+    """ctypes image of ``cmbpo_cost_head_t`` (16 bytes): the reading of the learned-cost column, the shift that undoes a class
+    weight, and the optional per-row output of the elite's raw logit."""
+    _fields_ = [("kind", C.c_int32), ("logit_shift", C.c_float), ("cost_logit", C.c_void_p)]
+
+
+_chp = C.POINTER(CostHeadStruct)
+SIGNATURES.update({
+    "cmbpo_fakeenv_post_cost": (_i, [_i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i,
+                                     _p, _p, _p, _p, _p, _p, _p, _p, C.c_float, C.c_float, _p, _p, _tp, _chp, _p]),
+    "cmbpo_rollout_cost_head_attach": (_i, [_rp, _chp]),
+    "cmbpo_rollout_cost_head_detach": (_i, [_rp]),
+})
+
+
 class PiBatchStruct(C.Structure):
     """ctypes image of ``cmbpo_pi_batch_t``."""
     _fields_ = [("n", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32)] + \
@@ -337,6 +356,11 @@ SIGNATURES.update({
 # ... with the learned termination head in its post step
 SIGNATURES.update({
     "cmbpo_replay_run_term": (_i, [_pp, _cpp, _tp, _p, _i, _i, _p, _p]),
+})
+
+# ... and with the cost head's reading (the superset)
+SIGNATURES.update({
+    "cmbpo_replay_run_cost": (_i, [_pp, _cpp, _tp, _chp, _p, _i, _i, _p, _p]),
 })
 
 _lib = None

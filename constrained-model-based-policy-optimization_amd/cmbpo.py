@@ -70,8 +70,17 @@ four keys in ``column_weights_<epoch>.json``.  With the defaults nothing is atta
 ``m_term_loss='logistic'`` (needs ``m_learn_term``) trains the termination column with the Bernoulli negative
 log-likelihood on its output read as a logit (``PE.set_logistic_columns([-1])``) and builds ``FakeEnv`` with
 ``term_loss='logistic'``: ``m_term_threshold`` is then a probability strictly inside (0, 1), compared as a logit.  The weights
-above go on applying, as weights on the Bernoulli term.  The learned cost column is not offered: ``FakeEnv`` reads it as a
-magnitude.  ``save`` / ``load`` keep the choice in ``term_loss_<epoch>.json`` (a missing file means 'gaussian').
+above go on applying, as weights on the Bernoulli term.  ``save`` / ``load`` keep the choice in ``term_loss_<epoch>.json`` (a
+missing file means 'gaussian').
+
+``m_cost_loss='logistic'`` (needs ``m_learn_cost``) does the same for the cost column, ``obs_dim + 1``: it is trained
+with the Bernoulli likelihood (targets above 0.5 count as 1) and ``FakeEnv(cost_loss='logistic')`` reads it as a logit, so every
+imagined cost is a probability in [0, 1].  A task whose cost is a magnitude, not an indicator, should keep 'gaussian'.
+``m_cost_pos_weight`` (a number >= 0 or 'balanced', needs ``m_learn_cost``) is the class weight of that column's positive
+targets, 'balanced' by the termination head's rule on each fit's cost targets and logged as ``model/cost_pos_weight``;
+``m_cost_pos_weight_undo=True`` (logistic only) subtracts ``log omega`` from the logit when it is read
+(``FakeEnv.set_cost_head(logit_shift=)``), which undoes what the weight did to the fitted level.  ``save`` / ``load`` keep all of
+it in ``cost_loss_<epoch>.json`` (a missing file means 'gaussian').
 
 ``static_fns`` takes a ``statics.TaskRules``: user-defined termination / cost rules for the imagined rollouts, with
 precedence over ``task`` (which may itself be a name given to ``statics.register_task``).
@@ -162,6 +171,40 @@ def _term_loss_args(learn_term, term_loss, term_threshold):
     return term_loss
 
 
+def _cost_loss_args(learn_cost, cost_loss, cost_pos_weight, undo, pos_weight_max):
+    """``m_cost_loss`` / ``m_cost_pos_weight`` / ``m_cost_pos_weight_undo`` checked against ``m_learn_cost``: the
+    tuple (loss, weight -- a float or 'balanced', undo) or a ValueError in words."""
+    if cost_loss not in ('gaussian', 'logistic'):
+        raise ValueError("m_cost_loss: 'gaussian' or 'logistic', got %r" % (cost_loss,))
+    if cost_loss == 'logistic' and not learn_cost:
+        raise ValueError("m_cost_loss='logistic' needs m_learn_cost=True (and use_model): it is the likelihood of the learned "
+                         "cost column")
+    if isinstance(cost_pos_weight, str):
+        if cost_pos_weight != 'balanced':
+            raise ValueError("m_cost_pos_weight: a number >= 0 or 'balanced', got %r" % (cost_pos_weight,))
+        weight = 'balanced'
+    else:
+        try:
+            weight = float(cost_pos_weight)
+        except (TypeError, ValueError):
+            raise ValueError("m_cost_pos_weight: a number >= 0 or 'balanced', got %r" % (cost_pos_weight,))
+        if not (np.isfinite(weight) and weight >= 0.0):
+            raise ValueError("m_cost_pos_weight: a finite number >= 0 or 'balanced', got %r" % (cost_pos_weight,))
+    if weight != 1.0 and not learn_cost:
+        raise ValueError("m_cost_pos_weight needs m_learn_cost=True: it weighs the positive class of the learned cost column")
+    if undo:
+        if cost_loss != 'logistic':
+            raise ValueError("m_cost_pos_weight_undo needs m_cost_loss='logistic': only a logit can be shifted back by log omega")
+        if weight != 'balanced' and not weight > 0.0:
+            raise ValueError("m_cost_pos_weight_undo needs m_cost_pos_weight > 0: log omega is the shift it undoes")
+    return cost_loss, weight, bool(undo)
+
+
+def cost_logit_shift(omega):
+    """The shift that undoes a class weight omega > 0 on a logistic column: log omega (known property)."""
+    return float(np.log(float(omega)))
+
+
 COLUMN_WEIGHT_KEYS = ('m_term_pos_weight', 'm_term_loss_weight', 'm_cost_loss_weight', 'm_pos_weight_max')
 
 
@@ -202,6 +245,8 @@ def balanced_pos_weight(targets, pos_weight_max):
 
 class CMBPO:
     """Constrained Model-Based Policy Optimization (``algorithms/cmbpo.py:30``)."""
+    # the reading of the cost column (DESIGN 3w) where the constructor has not set it: a magnitude, no class weight
+    _m_cost_loss, _cost_pos_weight, _cost_pos_weight_undo = 'gaussian', 1.0, False
 
     def __init__(self, env, policy, buffer, sampler=None, task='default', static_fns=None, n_env_interacts=1e7,
                  eval_every_n_steps=5e3, use_model=True, m_learn_cost=False, m_train_freq=250, m_loss_type='MSPE',
@@ -218,12 +263,16 @@ class CMBPO:
                  m_validate_calibration=False, m_calibrated_noise=False, m_noise_temperature_range=(0.25, 4.0),
                  m_learn_term=False, m_term_threshold=0.5, m_term_members='elite',
                  m_term_pos_weight=1.0, m_term_loss_weight=1.0, m_cost_loss_weight=1.0, m_pos_weight_max=20.0,
-                 m_term_loss='gaussian', **_unused):
+                 m_term_loss='gaussian', m_cost_loss='gaussian', m_cost_pos_weight=1.0, m_cost_pos_weight_undo=False,
+                 **_unused):
         # column / class weights of the model's binary columns; refused in words before anything is built
         self._column_weights = _column_weight_args(bool(m_learn_term) and bool(use_model), bool(m_learn_cost), m_term_pos_weight,
                                                    m_term_loss_weight, m_cost_loss_weight, m_pos_weight_max)
         # the likelihood of the termination column; likewise
         self._m_term_loss = _term_loss_args(bool(m_learn_term) and bool(use_model), m_term_loss, m_term_threshold)
+        # the likelihood and the class weight of the cost column; likewise
+        self._m_cost_loss, self._cost_pos_weight, self._cost_pos_weight_undo = _cost_loss_args(
+            bool(m_learn_cost) and bool(use_model), m_cost_loss, m_cost_pos_weight, m_cost_pos_weight_undo, m_pos_weight_max)
         # predictive calibration in the validation replay and, from its one-step row, the scale of the transition
         # noise; refused in words before anything is built
         self._validate_calibration, self._calibrated_noise, self._noise_temperature_range = _calibration_args(
@@ -313,13 +362,14 @@ class CMBPO:
                                    num_networks=m_networks, num_elites=m_elites, use_scaler_in=m_use_scaler_in,
                                    use_scaler_out=m_use_scaler_out, decay=1e-6, max_logvar=.5, min_logvar=-10,
                                    device=self.device,
-                                   logistic_columns=[-1] if m_term_loss == 'logistic' else None)
+                                   logistic_columns=self._logistic_columns())
             rules_task = self._task if static_fns is None else static_fns      # static_fns takes precedence over the task name
             self.fake_env = FakeEnv(true_environment=env, task=rules_task, model=self._model, predicts_delta=True,
                                     predicts_rew=True, predicts_cost=self._m_learn_cost,
                                     disagreement=bool(m_disagreement), rew_pessimism=m_rew_pessimism,
                                     cost_pessimism=m_cost_pessimism, predicts_term=self._m_learn_term,
-                                    term_threshold=m_term_threshold, term_members=m_term_members, term_loss=m_term_loss)
+                                    term_threshold=m_term_threshold, term_members=m_term_members, term_loss=m_term_loss,
+                                    cost_loss=m_cost_loss)
             self.rollout_mode = rollout_mode
             self.model_buf = ModelBuffer(batch_size=self._rollout_batch_size, obs_dim=self.obs_dim, act_dim=self.act_dim,
                                          max_path_length=maxroll, device=self.device, iv_gae=bool(m_iv_gae),
@@ -402,7 +452,7 @@ class CMBPO:
         cost column the one after the reward; 'balanced' is recomputed from this call's termination targets.  With the
         defaults nothing is attached and nothing is logged."""
         cw = self._column_weights
-        if (cw['m_term_pos_weight'], cw['m_term_loss_weight'], cw['m_cost_loss_weight']) == (1.0, 1.0, 1.0):
+        if (cw['m_term_pos_weight'], cw['m_term_loss_weight'], cw['m_cost_loss_weight'], self._cost_pos_weight) == (1.0, 1.0, 1.0, 1.0):
             return {}
         col, pos, extra = {}, {}, {}
         if self._m_learn_term:
@@ -413,6 +463,15 @@ class CMBPO:
             extra['term_pos_weight'] = omega
         if self._m_learn_cost:
             col[self.obs_dim + 1] = cw['m_cost_loss_weight']
+            if self._cost_pos_weight != 1.0:
+                # the class weight of the cost column, the termination head's rule on this fit's cost targets
+                omega = self._cost_pos_weight
+                if omega == 'balanced':
+                    omega = balanced_pos_weight(dyn_outs[:, self.obs_dim + 1], cw['m_pos_weight_max'])
+                pos[self.obs_dim + 1] = omega
+                extra['cost_pos_weight'] = omega
+                if self._cost_pos_weight_undo:
+                    self.fake_env.set_cost_head(logit_shift=cost_logit_shift(omega))
         self._model.set_column_weights(col, pos)
         return extra
 
@@ -652,6 +711,13 @@ class CMBPO:
                 # the column's likelihood, a file of its own: term_head_<epoch>.json keeps exactly its keys
                 with open(os.path.join(savedir, 'term_loss_%d.json' % self._epoch), 'w') as fh:
                     json.dump({'m_term_loss': self._m_term_loss}, fh)
+            if self._m_learn_cost:      # the reading of the cost column, a file of its own
+                import json
+                import os
+                with open(os.path.join(savedir, 'cost_loss_%d.json' % self._epoch), 'w') as fh:
+                    json.dump({'m_cost_loss': self._m_cost_loss, 'm_cost_pos_weight': self._cost_pos_weight,
+                               'm_cost_pos_weight_undo': self._cost_pos_weight_undo,
+                               'cost_logit_shift': self.fake_env.cost_logit_shift}, fh)
             if self._m_learn_term or self._m_learn_cost:      # the column weights of the fits, a file of their own
                 import json
                 import os
@@ -671,6 +737,27 @@ class CMBPO:
         if (kw['m_term_pos_weight'], kw['m_term_loss_weight'], kw['m_cost_loss_weight']) == (1.0, 1.0, 1.0):
             self._model.set_column_weights(None, None)
 
+    def _logistic_columns(self):
+        """The model columns trained with the Bernoulli likelihood: the cost column obs_dim + 1 and / or the last one."""
+        cols = ([self.obs_dim + 1] if self._m_cost_loss == 'logistic' else []) + ([-1] if self._m_term_loss == 'logistic' else [])
+        return cols or None
+
+    def _load_cost_loss(self, savedir, timestep):
+        """The reading of the cost column that ``save`` wrote (a checkpoint from before it has no such file: 'gaussian', no
+        class weight, no shift); read before the model's weights and scalers come in, like the termination column's."""
+        import json
+        import os
+        if not self._m_learn_cost:
+            return None
+        path = os.path.join(savedir, 'cost_loss_%d.json' % int(timestep))
+        kw = {'m_cost_loss': 'gaussian', 'm_cost_pos_weight': 1.0, 'm_cost_pos_weight_undo': False, 'cost_logit_shift': 0.0}
+        if os.path.exists(path):
+            with open(path) as fh:
+                kw.update(json.load(fh))
+        self._m_cost_loss, self._cost_pos_weight, self._cost_pos_weight_undo = _cost_loss_args(
+            True, kw['m_cost_loss'], kw['m_cost_pos_weight'], kw['m_cost_pos_weight_undo'], self._column_weights['m_pos_weight_max'])
+        return kw
+
     def _load_term_loss(self, savedir, timestep):
         """The likelihood of the termination column that ``save`` wrote (a checkpoint from before it has no such file:
         'gaussian'), set on the model before its weights and scalers come in."""
@@ -686,16 +773,21 @@ class CMBPO:
         if term_loss not in ('gaussian', 'logistic'):
             raise ValueError("%s: m_term_loss %r" % (path, term_loss))
         self._m_term_loss = term_loss
-        self._model.set_logistic_columns([-1] if term_loss == 'logistic' else None)
+        self._model.set_logistic_columns(self._logistic_columns())
         return term_loss
 
     def load(self, savedir, timestep):
         """The model ``save`` wrote at epoch ``timestep`` and, with the termination head, its threshold and vote."""
         if not self._use_model:
             raise ValueError("load: the trainer was built with use_model=False, there is no model to load")
+        cost_head = self._load_cost_loss(savedir, timestep)
         term_loss = self._load_term_loss(savedir, timestep)
+        if cost_head is not None and not self._m_learn_term:      # (with a termination head _load_term_loss has set both)
+            self._model.set_logistic_columns(self._logistic_columns())
         self._model.load(savedir, timestep)
         self._load_column_weights(savedir, timestep)
+        if cost_head is not None:
+            self.fake_env.set_cost_head(cost_head['m_cost_loss'], cost_head['cost_logit_shift'] if cost_head['m_cost_loss'] == 'logistic' else 0.0)
         if self._m_learn_term:
             import json
             import os

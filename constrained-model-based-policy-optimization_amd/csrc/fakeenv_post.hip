@@ -74,15 +74,38 @@ struct PostArgsTerm : PostArgsT<RULES, NOISE, DIS> {
 };
 template <bool RULES, bool NOISE, bool DIS = false, bool TERM = false>
 using PostArgsX = std::conditional_t<TERM, PostArgsTerm<RULES, NOISE, DIS>, PostArgsT<RULES, NOISE, DIS>>;
+// COST: the logistic learned-cost head (include/cmbpo_hip.h, cmbpo_cost_head_t, kind 1) -- column obs_dim + 1 is a logit and the
+// cost its probability; the same pattern: fields of an argument type of their own, selecting instances of their own.  They are
+// launched with CMBPO_TASK_LEARNED_COST only (checked on the host), so `learned_cost` is not read in their COST parts.
+template <bool RULES, bool NOISE, bool DIS, bool TERM>
+struct PostArgsCost : PostArgsX<RULES, NOISE, DIS, TERM> {
+  float logit_shift;              // finite; 0: the logit goes into sigma32 bit for bit
+  float *cost_logit;              // [.] slot indexed like cost: the elite's raw logit, or NULL
+};
+template <bool RULES, bool NOISE, bool DIS = false, bool TERM = false, bool COST = false>
+using PostArgsY = std::conditional_t<COST, PostArgsCost<RULES, NOISE, DIS, TERM>, PostArgsX<RULES, NOISE, DIS, TERM>>;
 
 // np.clip(x, lo, hi): comparisons are false for a NaN, which therefore passes through (fminf / fmaxf would drop it)
 __device__ __forceinline__ float clip_np(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
+// The ONE logistic function of the cost head: every instance and every lane computes a member's probability with it, so the
+// probability of a logit has the same bits wherever it is computed.  float32, no contraction (the file is built with
+// -ffp-contract=off; the division is the correctly rounded one); +inf -> 1, -inf -> 0, NaN -> NaN (`zs >= 0` is false for it).
+__device__ __forceinline__ float sigma32(float zs) {
+  if (zs >= 0.0f) return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-zs)));
+  const float e = expf(zs);
+  return __fdiv_rn(e, __fadd_rn(1.0f, e));
+}
+// zs = fl32(z - logit_shift); a shift of 0 executes no subtraction (uniform over the launch)
+__device__ __forceinline__ float cost_prob(float z, float logit_shift) {
+  return sigma32(logit_shift != 0.0f ? __fsub_rn(z, logit_shift) : z);
+}
+
 // EC: the ensemble size at compile time (0: read it at run time) -- with a run-time size the member loops are unrolled to
 // kEMax and masked: 56 pair terms computed and selected for the 42 that exist, a third more instructions
 #define POST_WAVES 5      // waves per SIMD the register allocation aims at (swept 4 / 5 / 6 / 8: 57.7 / 51.1 / 51.3 / 77.4 us at 100 k rows)
-template <int EC, bool RULES = false, bool NOISE = false, bool DIS = false, bool TERM = false>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgsX<RULES, NOISE, DIS, TERM> p) {
+template <int EC, bool RULES = false, bool NOISE = false, bool DIS = false, bool TERM = false, bool COST = false>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgsY<RULES, NOISE, DIS, TERM, COST> p) {
   extern __shared__ float sm[];
   const int D = p.obs_dim;
   float *s_dkl = sm;                  // [kRows][D]
@@ -271,7 +294,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
         if (k < E) {
           const size_t o = k * mstride + (size_t)r * p.out_dim + D;
           xr = p.mean[o];
-          if (p.learned_cost) xc = p.mean[o + 1];
+          if constexpr (COST) xc = p.mean[o + 1];
+          else if (p.learned_cost) xc = p.mean[o + 1];
         }
       }
     }
@@ -361,7 +385,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
         return sq / (float)E;
       };
       rew_var = member_var(xr, &rew_me);
-      if (p.learned_cost) cost_var = member_var(xc, &cost_me);     // (uniform over the launch; a static cost rule has no spread: +0)
+      if constexpr (COST) {
+        // lane k holds member k's logit: the elite's goes out raw from the lane that loaded it, then every lane turns its own
+        // into the probability -- E exponentials side by side -- and the variance is taken on the probabilities
+        if (p.cost_logit != nullptr && r >= 0 && k == (me_k & 7)) p.cost_logit[r] = xc;
+        xc = cost_prob(xc, p.logit_shift);
+        cost_var = member_var(xc, &cost_me);
+      } else if (p.learned_cost) cost_var = member_var(xc, &cost_me);     // (uniform over the launch; a static cost rule has no spread: +0)
     }
     // TERM: hit_e = x_e > threshold, written positively (a NaN never hits); one ballot gives the row's member mask in the row's
     // byte -- the elite's bit is me & 7, the votes are a popcount.  All 64 lanes are still here.  The elite's own value goes out
@@ -411,7 +441,19 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
     // learned cost head (fake_env.py:139-143, predicts_cost=True): the elite member's mean of the last column, stored as it is;
     // the termination rule above still applies (TERMS_BY_TASK does not depend on predicts_cost).  A branch uniform over the
     // launch, taken by one lane per row: as a template parameter it would double the instances for one load.
-    if constexpr (DIS) {
+    // COST: the column is a logit and the cost its probability; the pessimistic cost is clipped at 1 (c > 1 ? 1 : c: a NaN passes).
+    // Without DIS only the elite's logit is read, by this lane.
+    if constexpr (COST && DIS) {
+      cost = cost_me;
+      if (p.kappa_cost > 0.0f) {
+        const float c = __fadd_rn(cost_me, __fmul_rn(p.kappa_cost, sqrtf(cost_var)));
+        cost = c > 1.0f ? 1.0f : c;
+      }
+    } else if constexpr (COST) {
+      const float z = p.mean[me * mstride + (size_t)r * p.out_dim + D + 1];
+      if (p.cost_logit != nullptr) p.cost_logit[r] = z;
+      cost = cost_prob(z, p.logit_shift);
+    } else if constexpr (DIS) {
       if (p.learned_cost) cost = p.kappa_cost > 0.0f ? __fadd_rn(cost_me, __fmul_rn(p.kappa_cost, sqrtf(cost_var))) : cost_me;
     } else {
       if (p.learned_cost) cost = p.mean[me * mstride + (size_t)r * p.out_dim + D + 1];
@@ -429,33 +471,43 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
   }
 }
 
-// one launch of the instance for (ensemble size, RULES, NOISE, DIS, TERM)
-template <bool RULES, bool NOISE, bool DIS = false, bool TERM = false>
-void launch_post(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsX<RULES, NOISE, DIS, TERM> &a) {
-  if (ensemble == 7) hipLaunchKernelGGL((fakeenv_post_kernel<7, RULES, NOISE, DIS, TERM>), grid, dim3(kThreads), lds, stream, a);   // the shipped configs
-  else if (ensemble == 5) hipLaunchKernelGGL((fakeenv_post_kernel<5, RULES, NOISE, DIS, TERM>), grid, dim3(kThreads), lds, stream, a);
-  else hipLaunchKernelGGL((fakeenv_post_kernel<0, RULES, NOISE, DIS, TERM>), grid, dim3(kThreads), lds, stream, a);
+// one launch of the instance for (ensemble size, RULES, NOISE, DIS, TERM, COST)
+template <bool RULES, bool NOISE, bool DIS = false, bool TERM = false, bool COST = false>
+void launch_post(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsY<RULES, NOISE, DIS, TERM, COST> &a) {
+  if (ensemble == 7) hipLaunchKernelGGL((fakeenv_post_kernel<7, RULES, NOISE, DIS, TERM, COST>), grid, dim3(kThreads), lds, stream, a);   // the shipped configs
+  else if (ensemble == 5) hipLaunchKernelGGL((fakeenv_post_kernel<5, RULES, NOISE, DIS, TERM, COST>), grid, dim3(kThreads), lds, stream, a);
+  else hipLaunchKernelGGL((fakeenv_post_kernel<0, RULES, NOISE, DIS, TERM, COST>), grid, dim3(kThreads), lds, stream, a);
+}
+// ... and the logistic cost head (ch == NULL: the instances without it, with the argument block they always had)
+template <bool RULES, bool NOISE, bool DIS, bool TERM>
+void launch_post_cost(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsX<RULES, NOISE, DIS, TERM> &a,
+                      const cmbpo_cost_head_t *ch) {
+  if (ch == nullptr) return launch_post<RULES, NOISE, DIS, TERM>(ensemble, grid, lds, stream, a);
+  PostArgsCost<RULES, NOISE, DIS, TERM> ac{};
+  static_cast<PostArgsX<RULES, NOISE, DIS, TERM> &>(ac) = a;
+  ac.logit_shift = ch->logit_shift; ac.cost_logit = ch->cost_logit;
+  launch_post<RULES, NOISE, DIS, TERM, true>(ensemble, grid, lds, stream, ac);
 }
 
 // DisExtra (fakeenv_post_internal.h): what the disagreement adds to the arguments (NULL: the instances without the feature)
 // ... and cmbpo_fakeenv_post_term (th == NULL: the instances without the head, with the argument block they always had)
 template <bool RULES, bool NOISE, bool DIS>
 void launch_post_term(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsT<RULES, NOISE, DIS> &a,
-                      const cmbpo_term_head_t *th) {
-  if (th == nullptr) return launch_post<RULES, NOISE, DIS>(ensemble, grid, lds, stream, a);
+                      const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch) {
+  if (th == nullptr) return launch_post_cost<RULES, NOISE, DIS, false>(ensemble, grid, lds, stream, a, ch);
   PostArgsTerm<RULES, NOISE, DIS> at{};
   static_cast<PostArgsT<RULES, NOISE, DIS> &>(at) = a;
   at.threshold = th->threshold; at.members = th->members; at.term_pred = th->term_pred; at.term_votes = th->term_votes;
-  launch_post<RULES, NOISE, DIS, true>(ensemble, grid, lds, stream, at);
+  launch_post_cost<RULES, NOISE, DIS, true>(ensemble, grid, lds, stream, at, ch);
 }
 template <bool RULES, bool NOISE>
 void launch_post_ext(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsBase<RULES, NOISE> &a, const DisExtra *dis,
-                     const cmbpo_term_head_t *th) {
-  if (dis == nullptr) return launch_post_term<RULES, NOISE, false>(ensemble, grid, lds, stream, a, th);
+                     const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch) {
+  if (dis == nullptr) return launch_post_term<RULES, NOISE, false>(ensemble, grid, lds, stream, a, th, ch);
   PostArgsDis<RULES, NOISE> ad{};
   static_cast<PostArgsBase<RULES, NOISE> &>(ad) = a;
   ad.kappa_rew = dis->kappa_rew; ad.kappa_cost = dis->kappa_cost; ad.rew_var = dis->rew_var; ad.cost_var = dis->cost_var;
-  launch_post_term<RULES, NOISE, true>(ensemble, grid, lds, stream, ad, th);
+  launch_post_term<RULES, NOISE, true>(ensemble, grid, lds, stream, ad, th, ch);
 }
 
 }  // namespace
@@ -464,7 +516,9 @@ int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream) {
   const cmbpo_term_head_t *th = c.th;
   const DisExtra *dis = c.dis_on ? &c.dis : nullptr;
   // the naming rule (fakeenv_post_internal.h, DESIGN): the narrowest entry point that can express the call
-  const char *who = th ? "cmbpo_fakeenv_post_term" : dis ? "cmbpo_fakeenv_post_disagreement"
+  // (kind 0 is the magnitude reading: the instances without the head; `ch` below is the LOGISTIC head or NULL)
+  const cmbpo_cost_head_t *ch = (c.ch != nullptr && c.ch->kind == 1) ? c.ch : nullptr;
+  const char *who = c.ch ? "cmbpo_fakeenv_post_cost" : th ? "cmbpo_fakeenv_post_term" : dis ? "cmbpo_fakeenv_post_disagreement"
                     : c.xi ? "cmbpo_fakeenv_post_noise" : "cmbpo_fakeenv_post";
   const int obs_dim = c.obs_dim, act_dim = c.act_dim, ensemble = c.ensemble;
   const int learned_cost = (c.task & CMBPO_TASK_LEARNED_COST) ? 1 : 0;     // every other bit outside the rule id is an error
@@ -480,6 +534,12 @@ int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream) {
     CMBPO_REQUIRE(isfinite(th->threshold), "%s: termination head: threshold %g is not a finite number", who, (double)th->threshold);
     CMBPO_REQUIRE(th->members >= CMBPO_TERM_ELITE && th->members <= CMBPO_TERM_MAJORITY,
                   "%s: termination head: members %d not in 0..2 (CMBPO_TERM_ELITE / _ANY / _MAJORITY)", who, th->members);
+  }
+  if (c.ch != nullptr) {
+    CMBPO_REQUIRE(c.ch->kind == 0 || c.ch->kind == 1, "%s: cost head: kind %d not in {0, 1} (0 magnitude, 1 logistic)", who, c.ch->kind);
+    CMBPO_REQUIRE(isfinite(c.ch->logit_shift), "%s: cost head: logit_shift %g is not a finite number", who, (double)c.ch->logit_shift);
+    CMBPO_REQUIRE(c.ch->kind == 0 || learned_cost,
+                  "%s: cost head: kind 1 (logistic) needs CMBPO_TASK_LEARNED_COST (a static cost rule has no logit), task %d", who, task_arg);
   }
   PostArgsRules ar{};
   if (user)     // (registered? columns inside obs_dim / act_dim? -- host code, before any HIP call)
@@ -514,20 +574,20 @@ int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream) {
       PostArgsRulesNoise an{};
       static_cast<PostArgsRules &>(an) = ar;
       an.xi = c.xi;
-      launch_post_ext<true, true>(ensemble, grid, lds, s, an, dis, th);
+      launch_post_ext<true, true>(ensemble, grid, lds, s, an, dis, th, ch);
     } else {
       PostArgsNoise an{};
       static_cast<PostArgs &>(an) = a;
       an.xi = c.xi;
-      launch_post_ext<false, true>(ensemble, grid, lds, s, an, dis, th);
+      launch_post_ext<false, true>(ensemble, grid, lds, s, an, dis, th, ch);
     }
-  } else if (user) launch_post_ext<true, false>(ensemble, grid, lds, s, ar, dis, th);
-  else launch_post_ext<false, false>(ensemble, grid, lds, s, a, dis, th);
+  } else if (user) launch_post_ext<true, false>(ensemble, grid, lds, s, ar, dis, th, ch);
+  else launch_post_ext<false, false>(ensemble, grid, lds, s, a, dis, th, ch);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
 
-// The four public entry points fill the descriptor and make that call; none forwards to another.  POST_COMMON: the 20 leading
+// The five public entry points fill the descriptor and make that call; none forwards to another.  POST_COMMON: the 20 leading
 // parameters they share (the stream goes beside the descriptor).
 #define POST_COMMON                                                                                                              \
   int task, int ensemble, int obs_dim, int act_dim, const float *d_mean, const float *d_var, int ld_rows, const float *d_obs,    \
@@ -579,6 +639,19 @@ extern "C" int cmbpo_fakeenv_post_term(POST_COMMON, const float *d_xi, float kap
   c.dis_on = d_rew_var != nullptr || d_cost_var != nullptr || kappa_rew != 0.0f || kappa_cost != 0.0f;
   c.dis = DisExtra{kappa_rew, kappa_cost, d_rew_var, d_cost_var};
   c.th = th;
+  return cmbpo_internal_fakeenv_post(c, stream);
+}
+
+// ... with the learned cost head's reading (see the kernel's COST parts and the header): the superset -- every feature is optional;
+// ch == NULL or kind 0 is cmbpo_fakeenv_post_term's call
+extern "C" int cmbpo_fakeenv_post_cost(POST_COMMON, const float *d_xi, float kappa_rew, float kappa_cost, float *d_rew_var,
+                                       float *d_cost_var, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, void *stream) {
+  FakeenvPostCall c = post_common(POST_COMMON_ARGS);
+  c.xi = d_xi;
+  c.dis_on = d_rew_var != nullptr || d_cost_var != nullptr || kappa_rew != 0.0f || kappa_cost != 0.0f;
+  c.dis = DisExtra{kappa_rew, kappa_cost, d_rew_var, d_cost_var};
+  c.th = th;
+  c.ch = ch;
   return cmbpo_internal_fakeenv_post(c, stream);
 }
 

@@ -449,10 +449,10 @@ int refused_by(const char *who, int rc) {
 }
 
 // the steps of a run: cal == nullptr is exactly cmbpo_replay_run's launches, else the calibrate kernel goes between post and
-// compare and its finish behind the plain one; th != nullptr: the head's instances of the post kernel.  Every argument has been
+// compare and its finish behind the plain one; th / ch != nullptr: the heads' instances of the post kernel.  Every argument has been
 // checked by the caller.
 int run_steps(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *cal, cmbpo_mlp_t *model, int task, int ensemble,
-              const int32_t *d_elite, const cmbpo_term_head_t *th, void *stream) {
+              const int32_t *d_elite, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, void *stream) {
   const int B = rp->B, D = rp->obs_dim, A = rp->act_dim;
   // the post step; act, elite and n_rows follow the horizon
   FakeenvPostCall pc{};
@@ -461,6 +461,7 @@ int run_steps(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_cali
   pc.next_obs = rp->p_next_obs; pc.rew = rp->p_rew; pc.term = rp->p_term; pc.cost = rp->p_cost;
   pc.dkl_path = rp->p_dkl_path; pc.ep_var_mean = rp->p_ep_var_mean;
   pc.th = th;
+  pc.ch = ch;
   // the two callees' own argument checks, on a call of no rows (neither launches anything for it)
   if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, rp->act, A, nullptr, nullptr, 0, B, rp->mean, rp->var, stream))
     return refused_by(who, rc);
@@ -480,35 +481,41 @@ int run_steps(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_cali
   return cal ? launch_calib_finish(rp, cal, (hipStream_t)stream) : CMBPO_OK;
 }
 
-// The three run entry points: ONE check list, keyed on which of rc (calibration) and th (termination head) are given.  The
-// messages carry the name of the narrowest entry point that can express the call (DESIGN): th given -- cmbpo_replay_run_term,
-// else rc given -- cmbpo_replay_run_calibrated, else cmbpo_replay_run.  Where the entry points have always differed in the order
+// The four run entry points: ONE check list, keyed on which of rc (calibration), th (termination head) and ch (cost head) are
+// given.  The messages carry the name of the narrowest entry point that can express the call (DESIGN): ch given --
+// cmbpo_replay_run_cost, else th given -- cmbpo_replay_run_term, else rc given -- cmbpo_replay_run_calibrated, else
+// cmbpo_replay_run.  Where the entry points have always differed in the order
 // or the wording of a check, each combination keeps its own.
-int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th, cmbpo_mlp_t *model, int task,
-               int ensemble, const int32_t *d_elite, void *stream) {
-  const char *who = th ? "cmbpo_replay_run_term" : rc ? "cmbpo_replay_run_calibrated" : "cmbpo_replay_run";
+int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch,
+               cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream) {
+  const bool ext = th || ch;      // (the two entries that take d_elite beside a calibration descriptor share their checks)
+  const char *who = ch ? "cmbpo_replay_run_cost" : th ? "cmbpo_replay_run_term" : rc ? "cmbpo_replay_run_calibrated" : "cmbpo_replay_run";
   if (int r = rc ? check_calibrate(who, rp, rc) : check_compare(who, rp)) return r;      // (check_calibrate: mean / var as well)
   if (int r = check_finish(who, rp)) return r;
   if (rc)
     if (int r = check_calib_finish(who, rp, rc)) return r;
   CMBPO_REQUIRE(model != nullptr, "%s: model handle is NULL", who);
-  if (!rc && !th) CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);     // (the plain run names it before act)
-  if (rc && !th) CMBPO_REQUIRE(rp->act_dim == 0 || rp->act, "%s: NULL buffer (act)", who);
+  if (!rc && !ext) CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);     // (the plain run names it before act)
+  if (rc && !ext) CMBPO_REQUIRE(rp->act_dim == 0 || rp->act, "%s: NULL buffer (act)", who);
   else CMBPO_REQUIRE((rp->act_dim == 0 || rp->act) && rp->mean && rp->var, "%s: NULL buffer (act / mean / var)", who);
   if (rc) {
     CMBPO_REQUIRE(ensemble == rc->ensemble, "%s: ensemble %d, the calibration descriptor's is %d", who, ensemble, rc->ensemble);
     // (cmbpo_replay_run_calibrated has no d_elite; without a head cmbpo_replay_run_term has always ignored its own)
-    if (th) CMBPO_REQUIRE(d_elite == nullptr || d_elite == rc->elite, "%s: d_elite differs from the calibration descriptor's elite", who);
+    if (ext) CMBPO_REQUIRE(d_elite == nullptr || d_elite == rc->elite, "%s: d_elite differs from the calibration descriptor's elite", who);
     d_elite = rc->elite;
   }
+  if (ext) CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);
+  if (ch && ch->kind == 1)
+    CMBPO_REQUIRE(model->out_dim == rp->obs_dim + 2 + (th ? 1 : 0),
+                  "%s: logistic cost head (cmbpo_cost_head_t, kind 1): model out_dim %d does not match obs_dim %d + 2 (+ 1 with a "
+                  "termination head), task 0x%x", who, model->out_dim, rp->obs_dim, task);
   if (th) {
-    CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);
     const int want = rp->obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0) + 1;
     CMBPO_REQUIRE(model->out_dim == want,
                   "%s: termination head (cmbpo_term_head_t): model out_dim %d does not match obs_dim %d + 1 (+ 1 with CMBPO_TASK_LEARNED_COST) "
                   "+ 1 for the head's column, task 0x%x", who, model->out_dim, rp->obs_dim, task);
   }
-  return run_steps(who, rp, rc, model, task, ensemble, d_elite, th, stream);
+  return run_steps(who, rp, rc, model, task, ensemble, d_elite, th, ch, stream);
 }
 
 }  // namespace
@@ -529,7 +536,7 @@ extern "C" int cmbpo_replay_finish(const cmbpo_replay_t *rp, void *stream) {
 
 extern "C" int cmbpo_replay_run(const cmbpo_replay_t *rp, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite,
                                 void *stream) {
-  return replay_run(rp, nullptr, nullptr, model, task, ensemble, d_elite, stream);
+  return replay_run(rp, nullptr, nullptr, nullptr, model, task, ensemble, d_elite, stream);
 }
 
 extern "C" int cmbpo_replay_calibrate(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, int h, void *stream) {
@@ -547,10 +554,16 @@ extern "C" int cmbpo_replay_calib_finish(const cmbpo_replay_t *rp, const cmbpo_r
 extern "C" int cmbpo_replay_run_calibrated(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, cmbpo_mlp_t *model, int task,
                                            int ensemble, void *stream) {
   if (rc == nullptr) return check_calibrate("cmbpo_replay_run_calibrated", rp, rc);      // (this entry's own error, not the plain run)
-  return replay_run(rp, rc, nullptr, model, task, ensemble, nullptr, stream);
+  return replay_run(rp, rc, nullptr, nullptr, model, task, ensemble, nullptr, stream);
 }
 
 extern "C" int cmbpo_replay_run_term(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th,
                                      cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream) {
-  return replay_run(rp, rc, th, model, task, ensemble, d_elite, stream);
+  return replay_run(rp, rc, th, nullptr, model, task, ensemble, d_elite, stream);
+}
+
+extern "C" int cmbpo_replay_run_cost(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th,
+                                     const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite,
+                                     void *stream) {
+  return replay_run(rp, rc, th, ch, model, task, ensemble, d_elite, stream);
 }

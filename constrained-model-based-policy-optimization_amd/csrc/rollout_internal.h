@@ -2,14 +2,17 @@
 #pragma once
 #include "common.h"
 
-// what is attached beside *r (cmbpo_rollout_iv_attach / _disagreement_attach / _value_disagreement_attach / _term_head_attach);
-// a feature that is not: all-zero (an all-zero cmbpo_term_head_t is a valid head, so that one has a flag)
+// what is attached beside *r (cmbpo_rollout_iv_attach / _disagreement_attach / _value_disagreement_attach / _term_head_attach /
+// _cost_head_attach); a feature that is not: all-zero (an all-zero cmbpo_term_head_t is a valid head and an all-zero
+// cmbpo_cost_head_t the magnitude reading, so those two have a flag)
 struct RolloutSide {
   cmbpo_iv_gae_t iv;
   cmbpo_disagreement_t dg;
   cmbpo_value_disagreement_t vd;
   cmbpo_term_head_t th;
   int th_on;
+  cmbpo_cost_head_t ch;
+  int ch_on;
 };
 RolloutSide cmbpo_internal_side_lookup(const cmbpo_rollout_t *r);
 

@@ -1313,7 +1313,7 @@ void side_update(const cmbpo_rollout_t *r, Change change) {
   std::lock_guard<std::mutex> lock(g_side_mu);
   RolloutSide &sd = g_side[r->iscal];
   change(sd);
-  if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr && sd.vd.part == nullptr && !sd.th_on) g_side.erase(r->iscal);
+  if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr && sd.vd.part == nullptr && !sd.th_on && !sd.ch_on) g_side.erase(r->iscal);
 }
 
 }  // namespace
@@ -1380,6 +1380,23 @@ extern "C" int cmbpo_rollout_term_head_attach(const cmbpo_rollout_t *r, const cm
 extern "C" int cmbpo_rollout_term_head_detach(const cmbpo_rollout_t *r) {
   CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_term_head_detach: NULL rollout struct / iscal");
   side_update(r, [](RolloutSide &sd) { sd.th = {}; sd.th_on = 0; });
+  return CMBPO_OK;
+}
+
+extern "C" int cmbpo_rollout_cost_head_attach(const cmbpo_rollout_t *r, const cmbpo_cost_head_t *ch) {
+  CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_cost_head_attach: NULL rollout struct / iscal");
+  CMBPO_REQUIRE(ch != nullptr, "cmbpo_rollout_cost_head_attach: NULL cmbpo_cost_head_t (cmbpo_rollout_cost_head_detach switches the feature off)");
+  CMBPO_REQUIRE(ch->kind == 0 || ch->kind == 1, "cmbpo_rollout_cost_head_attach: cost head: kind %d not in {0, 1} (0 magnitude, 1 logistic)",
+                ch->kind);
+  CMBPO_REQUIRE(isfinite(ch->logit_shift), "cmbpo_rollout_cost_head_attach: cost head: logit_shift %g is not a finite number",
+                (double)ch->logit_shift);
+  side_update(r, [&](RolloutSide &sd) { sd.ch = *ch; sd.ch_on = 1; });      // (no kernel of this file reads it: the one-call step hands it to the post kernel)
+  return CMBPO_OK;
+}
+
+extern "C" int cmbpo_rollout_cost_head_detach(const cmbpo_rollout_t *r) {
+  CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_cost_head_detach: NULL rollout struct / iscal");
+  side_update(r, [](RolloutSide &sd) { sd.ch = {}; sd.ch_on = 0; });
   return CMBPO_OK;
 }
 

@@ -35,6 +35,15 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   // what is attached beside *r, looked up once for every launch of the step
   const RolloutSide sd = cmbpo_internal_side_lookup(r);
   // the scratch rows are as wide as the model's output: a learned-cost flag that does not match the model would read the wrong columns
+  if (sd.ch_on && sd.ch.kind == 1) {
+    // the logistic cost head: refused here, before the first launch of the step (the post step would refuse it at the third)
+    CMBPO_REQUIRE((task & CMBPO_TASK_LEARNED_COST) != 0,
+                  "cmbpo_rollout_step: a logistic cost head (cmbpo_cost_head_t, kind 1) is attached, which needs CMBPO_TASK_LEARNED_COST "
+                  "(a static cost rule has no logit), task 0x%x", task);
+    CMBPO_REQUIRE(model->out_dim == r->obs_dim + 2 + (sd.th_on ? 1 : 0),
+                  "cmbpo_rollout_step: a logistic cost head (cmbpo_cost_head_t, kind 1) is attached: model out_dim %d does not match "
+                  "obs_dim %d + 2 (+ 1 with a termination head attached), task 0x%x", model->out_dim, r->obs_dim, task);
+  }
   if (sd.th_on)
     CMBPO_REQUIRE(model->out_dim == r->obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0) + 1,
                   "cmbpo_rollout_step: a termination head (cmbpo_term_head_t) is attached: model out_dim %d does not match obs_dim %d + 1 "
@@ -65,7 +74,7 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   if ((rc = cmbpo_ens_forward(model, r->cur_obs, r->obs_dim, r->act_t, r->act_dim, r->alive_idx, d_n, n_alive, r->B,
                               d_mean, d_var, stream)))
     return rc;
-  // the post step, with what is attached beside *r (disagreement, termination head) and the draws (d_xi may be NULL)
+  // the post step, with what is attached beside *r (disagreement, termination head, cost head) and the draws (d_xi may be NULL)
   FakeenvPostCall pc{};
   pc.task = task; pc.ensemble = ensemble; pc.obs_dim = r->obs_dim; pc.act_dim = r->act_dim;
   pc.mean = d_mean; pc.var = d_var; pc.ld_rows = r->B; pc.obs = r->cur_obs; pc.act = r->act_t;
@@ -76,6 +85,7 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   pc.dis_on = sd.dg.part != nullptr;
   pc.dis = DisExtra{sd.dg.kappa_rew, sd.dg.kappa_cost, sd.dg.rew_var_t, sd.dg.cost_var_t};
   pc.th = sd.th_on ? &sd.th : nullptr;
+  pc.ch = sd.ch_on ? &sd.ch : nullptr;
   if ((rc = cmbpo_internal_fakeenv_post(pc, stream))) return rc;
   const bool small = ahead.on || (n_alive <= cmbpo_rollout_book_pre_max_rows() && !r->use_host_budget);
   // small batches: decide + finish(PRE) + the store's scalar half in one launch; its vector half (obs, act, mu, log_std) rides

@@ -38,6 +38,14 @@ adds ``info['term_pred']`` (the elite's value of the column) and ``info['term_vo
 logit z, ``term_threshold`` a probability tau strictly inside (0, 1), and the test ``sigma(z) > tau`` runs in the same kernel as
 ``z > float32(logit(tau))``; ``info['term_pred']`` is ``sigma(z)`` in float32.
 
+``cost_loss='logistic'`` (needs ``predicts_cost=True``; a model whose cost column is logistic,
+``PE(logistic_columns=[obs_dim + 1])``): the column is a logit z and the cost of a step its probability
+``sigma(z - cost_logit_shift)`` in [0, 1], computed in the kernel; the disagreement variance is taken on the members'
+probabilities and the pessimistic cost ``p + kappa_c * sqrt(var)`` is clipped at 1.  ``step()`` returns the probability as cost
+and adds ``info['cost_logit']`` (the elite's raw logit); ``set_cost_head(loss, logit_shift)`` changes the head later.
+``cost_logit_shift = log(omega)`` undoes a class weight omega the column was trained with.  Targets above 0.5 count as 1, so a
+task whose cost is a magnitude, not an indicator, should keep the default ``'gaussian'``.
+
 ``replay(...)`` has no counterpart in the reference: it replays windows of real steps through the model with the recorded
 actions and returns, per horizon, how far the predictions are from the recording (open-loop model validation).
 
@@ -55,7 +63,8 @@ from . import _lib, statics
 class FakeEnv:
     def __init__(self, true_environment, task, model, predicts_delta, predicts_rew, predicts_cost,
                  seed=0, disagreement=False, rew_pessimism=0.0, cost_pessimism=0.0,
-                 predicts_term=False, term_threshold=0.5, term_members='elite', term_loss='gaussian'):
+                 predicts_term=False, term_threshold=0.5, term_members='elite', term_loss='gaussian',
+                 cost_loss='gaussian', cost_logit_shift=0.0):
         self.env = true_environment
         self.obs_dim = int(np.prod(self.observation_space.shape))
         self.act_dim = int(np.prod(self.action_space.shape))
@@ -95,6 +104,8 @@ class FakeEnv:
             self.set_term_head(term_threshold, term_members, term_loss)
         elif term_loss != 'gaussian':
             raise ValueError("term_loss='logistic' needs predicts_term=True: the model has no termination column")
+        self.cost_loss, self.cost_logit_shift = 'gaussian', 0.0
+        self.set_cost_head(cost_loss, cost_logit_shift)
         self.device = model.device
         # bench.py sets this to a list to collect (start, end) HIP events around the dominant kernel
         self.kernel_events = None
@@ -161,6 +172,29 @@ class FakeEnv:
         th.term_pred, th.term_votes = _lib.ptr(term_pred), _lib.ptr(term_votes)
         return th
 
+    def set_cost_head(self, loss=None, logit_shift=None):
+        """How the learned-cost column is read: ``loss`` 'gaussian' (a magnitude, the reference's reading) or 'logistic' (a
+        logit; the cost is its probability), ``logit_shift`` the finite number subtracted from the logit first (log omega
+        undoes a class weight omega).  None leaves a setting as it is."""
+        loss = self.cost_loss if loss is None else loss
+        shift = self.cost_logit_shift if logit_shift is None else float(logit_shift)
+        if loss not in _lib.COST_KINDS:
+            raise ValueError(f"cost_loss: 'gaussian' or 'logistic', got {loss!r}")
+        if loss == 'logistic' and not self._predicts_cost:
+            raise ValueError("cost_loss='logistic' needs predicts_cost=True: the model has no cost column to read as a logit")
+        if not np.isfinite(shift):
+            raise ValueError(f"cost_logit_shift must be a finite number, got {shift}")
+        self.cost_loss, self.cost_logit_shift = loss, shift
+
+    def cost_head_struct(self, cost_logit=None):
+        """The ``cmbpo_cost_head_t`` of this head (None under 'gaussian': the call without one); the optional output is a device
+        tensor or None."""
+        if self.cost_loss != 'logistic':
+            return None
+        ch = _lib.CostHeadStruct()
+        ch.kind, ch.logit_shift, ch.cost_logit = _lib.COST_LOGISTIC, self.cost_logit_shift, _lib.ptr(cost_logit)
+        return ch
+
     def random_inds(self, size):
         """One elite per branch (models/fake_env.py:174-178), from this object's seeded generator."""
         elites = np.asarray(self._model.elite_inds, dtype=np.int32)
@@ -174,7 +208,8 @@ class FakeEnv:
         (and optionally ep_var[B,obs]).  scratch: (mean, var)[E,B,output_dim].  With `disagreement` on, out also needs
         rew_var[B] and cost_var[B]; they are filled, and rew / cost are the penalised values.  With `predicts_term`, term is
         rule_done or learned_done, and out's optional term_pred[B] / term_votes[B] u8 are filled (under
-        ``term_loss='logistic'`` term_pred carries the logit).
+        ``term_loss='logistic'`` term_pred carries the logit).  With ``cost_loss='logistic'`` cost is the probability and out's
+        optional cost_logit[B] is filled with the elite's raw logit.
         """
         B = obs.shape[0]
         if noise is not None and not (noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
@@ -203,12 +238,13 @@ class FakeEnv:
         dis = (self.rew_pessimism, self.cost_pessimism, _lib.ptr(out["rew_var"]), _lib.ptr(out["cost_var"])) \
             if self.disagreement else (0.0, 0.0, None, None)
         th = self.term_head_struct(out.get("term_pred"), out.get("term_votes"))
-        _lib.check(lib.cmbpo_fakeenv_post_term(
+        ch = self.cost_head_struct(out.get("cost_logit"))
+        _lib.check(lib.cmbpo_fakeenv_post_cost(
             self._task_id, E, self.obs_dim, self.act_dim, _lib.ptr(mean), _lib.ptr(var), B, _lib.ptr(obs), _lib.ptr(act),
             _lib.ptr(model_inds), _lib.ptr(row_idx), None, n, _lib.ptr(out["next_obs"]), _lib.ptr(out["rew"]),
             _lib.ptr(out["term"]), _lib.ptr(out["cost"]), _lib.ptr(out["dkl_path"]), _lib.ptr(out["ep_var_mean"]),
-            _lib.ptr(out.get("ep_var")), _lib.ptr(noise), *dis, C.byref(th) if th is not None else None, stream),
-            "cmbpo_fakeenv_post_term")
+            _lib.ptr(out.get("ep_var")), _lib.ptr(noise), *dis, C.byref(th) if th is not None else None,
+            C.byref(ch) if ch is not None else None, stream), "cmbpo_fakeenv_post_cost")
         return out
 
     def step(self, obs, act, deterministic=True, model_inds=None, noise=None):
@@ -251,6 +287,8 @@ class FakeEnv:
                 out.update(rew_var=torch.empty(n, **f), cost_var=torch.empty(n, **f))
             if self._predicts_term:
                 out.update(term_pred=torch.empty(n, **f), term_votes=torch.empty(n, dtype=torch.uint8, device=self.device))
+            if self.cost_loss == 'logistic':
+                out.update(cost_logit=torch.empty(n, **f))
             self.step_device(o, a, inds, out, noise=xi)
         next_obs, r, terms = out["next_obs"], out["rew"][:, None], out["term"].bool()[:, None]
         c = out["cost"][:, None]
@@ -278,6 +316,9 @@ class FakeEnv:
             if was_np:
                 tp, tv = tp.cpu().numpy(), tv.cpu().numpy()
             info["term_pred"], info["term_votes"] = tp, tv
+        if self.cost_loss == 'logistic':
+            cl = out["cost_logit"]
+            info["cost_logit"] = cl.cpu().numpy() if was_np else cl
         return next_obs, r, terms, info
 
     def replay(self, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, model_inds=None, mode='open_loop',
@@ -300,7 +341,9 @@ class FakeEnv:
         A replay always measures the UNPENALISED means: it runs ``cmbpo_ens_forward`` and the plain ``cmbpo_fakeenv_post``,
         never the noise or disagreement entries, whatever ``disagreement`` / ``rew_pessimism`` / ``cost_pessimism`` are.  With
         ``predicts_term`` the post step carries the head (``cmbpo_replay_run_term``): the predicted terminations, ``term_cm``
-        among them, are ``rule_done or learned_done``.
+        among them, are ``rule_done or learned_done``.  With ``cost_loss='logistic'`` it carries the cost head
+        (``cmbpo_replay_run_cost``): the predicted cost is the probability, so ``cost_cm``'s ``cost > 0.5`` is a decision rule
+        on a probability and ``mse_cost`` is the Brier score of the column.
 
         Returns a dict of NumPy arrays, one row per horizon h = 0..H-1: ``n`` (windows compared), ``n_nonfinite``,
         ``mse_obs`` [H, obs], ``mse_rew``, ``mse_cost``, ``cost_cm`` / ``term_cm`` [H, 2, 2] indexed [real, predicted] (a
@@ -333,13 +376,13 @@ class FakeEnv:
             if inds.shape != (H, B) or inds.min() < 0 or inds.max() >= E:
                 raise ValueError("replay: model_inds must be an int or an [%d, %d] array of members in 0..%d" % (H, B, E - 1))
             elite = torch.from_numpy(np.ascontiguousarray(inds, dtype=np.int32)).to(self.device)
-            th = self.term_head_struct()
+            th, ch = self.term_head_struct(), self.cost_head_struct()
             if calibration:
-                rb.run_calibrated(self._model.mlp.handle, self._task_id, E, elite, term_head=th)
+                rb.run_calibrated(self._model.mlp.handle, self._task_id, E, elite, term_head=th, cost_head=ch)
                 tab = rb.table()
                 tab['calibration'] = rb.calibration_table()
                 return tab
-            rb.run(self._model.mlp.handle, self._task_id, E, elite, term_head=th)
+            rb.run(self._model.mlp.handle, self._task_id, E, elite, term_head=th, cost_head=ch)
             return rb.table()
 
     def close(self):

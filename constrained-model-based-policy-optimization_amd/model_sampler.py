@@ -27,6 +27,9 @@ reward and cost, stores the penalised values and adds the variances of the store
 term_members=...)``): every step then ends a branch where the rule or the model's termination column says so, on the one-call
 step, the native loop and the sharded per-step path alike; ``pool.t['term_pred_t']`` / ``['term_votes_t']`` hold the step's values.
 
+``reset()`` also takes the reading of the learned-cost column (``FakeEnv(cost_loss='logistic', cost_logit_shift=...)``, DESIGN
+§3w): every step then stores the cost as a probability, and ``pool.t['cost_logit_t']`` holds the step's raw logits.
+
 ``sample()`` returns ``(next_obs, reward, terminal, info)`` like the reference, but as slot-indexed CUDA
 tensors (the trainer only reads ``info['alive_ratio']``, ``algorithms/cmbpo.py:254-263``).
 """
@@ -234,6 +237,8 @@ class ModelSampler:
             pool.set_term_head(getattr(self.env, "predicts_term", False),
                                getattr(self.env, "term_kernel_threshold", getattr(self.env, "term_threshold", 0.5)),
                                getattr(self.env, "term_members", "elite"))
+            # ... and the reading of its learned-cost column (a shift changed between two fits is picked up here)
+            pool.set_cost_head(getattr(self.env, "cost_loss", "gaussian"), getattr(self.env, "cost_logit_shift", 0.0))
             if observations is None:
                 fill(pool.t["cur_obs"])
             else:
@@ -333,6 +338,8 @@ class ModelSampler:
                 outs.update(rew_var=t["rew_var_t"], cost_var=t["cost_var_t"])
             if pool.term_head is not None:
                 outs.update(term_pred=t["term_pred_t"], term_votes=t["term_votes_t"])
+            if pool.cost_head is not None:
+                outs.update(cost_logit=t["cost_logit_t"])
             env.step_device(t["cur_obs"], t["act_t"], inds_t, outs,
                             row_idx=idx, n_rows=n, scratch=self._scratch, noise=xi_t)
             if exchange:

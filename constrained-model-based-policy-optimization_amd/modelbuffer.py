@@ -98,6 +98,11 @@ def _term_fill(buf, th):
     th.term_pred, th.term_votes = t["term_pred_t"].data_ptr(), t["term_votes_t"].data_ptr()
 
 
+def _cost_fill(buf, ch):
+    ch.kind, ch.logit_shift = _lib.COST_KINDS[buf.cost_head[0]], buf.cost_head[1]
+    ch.cost_logit = buf.t["cost_logit_t"].data_ptr()
+
+
 # The features kept beside the rollout struct, in the order they are attached: is it on, the arrays it owns in ``self.t``
 # ((name, shape, dtype) for capacity B and horizon T: allocated zeroed when it is switched on, freed when it is switched off), its
 # struct and how to fill it, the entry points that attach and detach it.  The next feature is one more row.
@@ -120,6 +125,9 @@ _SIDE = {
     "term": _Side(lambda buf: buf.term_head is not None,
                   lambda B, T: (("term_pred_t", (B,), torch.float32), ("term_votes_t", (B,), torch.uint8)),
                   _lib.TermHeadStruct, _term_fill, "cmbpo_rollout_term_head_attach", "cmbpo_rollout_term_head_detach"),
+    "cost": _Side(lambda buf: buf.cost_head is not None,
+                  lambda B, T: (("cost_logit_t", (B,), torch.float32),),
+                  _lib.CostHeadStruct, _cost_fill, "cmbpo_rollout_cost_head_attach", "cmbpo_rollout_cost_head_detach"),
 }
 
 
@@ -163,6 +171,7 @@ class ModelBuffer:
         self.disagreement, self.rew_pessimism, self.cost_pessimism = False, 0.0, 0.0
         self.value_disagreement, self.v_pessimism, self.vc_pessimism = False, 0.0, 0.0
         self.term_head = None                 # (threshold, members) of the learned termination head, None: off
+        self.cost_head = None                 # (loss, logit_shift) of a logistic learned-cost head, None: the magnitude reading
         self.trust_var, self.last_weights = None, None
         self.rs = None
         self._iv_key = [0]                    # iscal of the arrays the library's table may hold an entry for
@@ -307,6 +316,25 @@ class ModelBuffer:
             raise RuntimeError("set_term_head: the buffer holds samples (call it after get() / reset())")
         self.term_head = head
         self._side_sync("term")
+
+    # -- the reading of the learned-cost column -------------------------------------------------------
+    def set_cost_head(self, loss='gaussian', logit_shift=0.0):
+        """Read the model's cost column as a logit (``loss='logistic'``, ``FakeEnv(cost_loss='logistic')``, DESIGN §3w: the
+        sampler hands its environment's head over at every reset) or as a magnitude ('gaussian': nothing attached); legal
+        whenever nothing is stored.  Under 'logistic' ``cost_t`` / ``cost_buf`` hold probabilities and the step's raw logits
+        are kept in ``cost_logit_t`` [B]."""
+        if loss not in _lib.COST_KINDS:
+            raise ValueError(f"cost_loss: 'gaussian' or 'logistic', got {loss!r}")
+        shift = float(logit_shift)
+        if not np.isfinite(shift):
+            raise ValueError(f"cost_logit_shift must be a finite number, got {shift}")
+        head = (loss, shift) if loss == 'logistic' else None
+        if head == self.cost_head:
+            return
+        if self.ptr != 0 or self._size != 0:
+            raise RuntimeError("set_cost_head: the buffer holds samples (call it after get() / reset())")
+        self.cost_head = head
+        self._side_sync("cost")
 
     # -- the state beside the struct ------------------------------------------------------------
     def _side_sync(self, feature):

@@ -114,9 +114,15 @@ class ReplayBuffers:
     def finish(self):
         _lib.check(_lib.lib().cmbpo_replay_finish(C.byref(self.rs), _lib.current_stream()), "cmbpo_replay_finish")
 
-    def run(self, model_handle, task_id, ensemble, elite, term_head=None):
+    def run(self, model_handle, task_id, ensemble, elite, term_head=None, cost_head=None):
         """``cmbpo_replay_run``; elite: [H, B] int32 device tensor.  term_head: a ``_lib.TermHeadStruct`` -- the learned
-        termination head in the post step (``cmbpo_replay_run_term``)."""
+        termination head in the post step (``cmbpo_replay_run_term``).  cost_head: a ``_lib.CostHeadStruct`` -- the reading of
+        the learned-cost column (``cmbpo_replay_run_cost``)."""
+        if cost_head is not None:
+            _lib.check(_lib.lib().cmbpo_replay_run_cost(C.byref(self.rs), None, C.byref(term_head) if term_head is not None else None,
+                                                        C.byref(cost_head), model_handle, int(task_id), int(ensemble),
+                                                        elite.data_ptr(), _lib.current_stream()), "cmbpo_replay_run_cost")
+            return
         if term_head is not None:
             _lib.check(_lib.lib().cmbpo_replay_run_term(C.byref(self.rs), None, C.byref(term_head), model_handle, int(task_id),
                                                         int(ensemble), elite.data_ptr(), _lib.current_stream()),
@@ -148,11 +154,17 @@ class ReplayBuffers:
         _lib.check(_lib.lib().cmbpo_replay_calib_finish(C.byref(self.rs), self._calib(), _lib.current_stream()),
                    "cmbpo_replay_calib_finish")
 
-    def run_calibrated(self, model_handle, task_id, ensemble, elite=None, term_head=None):
-        """``cmbpo_replay_run_calibrated``; elite: [H, B] members (None: those of the last ``set_elite``).  term_head: as in
-        ``run``."""
+    def run_calibrated(self, model_handle, task_id, ensemble, elite=None, term_head=None, cost_head=None):
+        """``cmbpo_replay_run_calibrated``; elite: [H, B] members (None: those of the last ``set_elite``).  term_head,
+        cost_head: as in ``run``."""
         if elite is not None:
             self.set_elite(elite)
+        if cost_head is not None:
+            _lib.check(_lib.lib().cmbpo_replay_run_cost(C.byref(self.rs), self._calib(),
+                                                        C.byref(term_head) if term_head is not None else None, C.byref(cost_head),
+                                                        model_handle, int(task_id), int(ensemble), None, _lib.current_stream()),
+                       "cmbpo_replay_run_cost")
+            return
         if term_head is not None:
             _lib.check(_lib.lib().cmbpo_replay_run_term(C.byref(self.rs), self._calib(), C.byref(term_head), model_handle,
                                                         int(task_id), int(ensemble), None, _lib.current_stream()),

@@ -334,6 +334,48 @@ int cmbpo_fakeenv_post_term(int task, int ensemble, int obs_dim, int act_dim,
                             float *d_rew_var, float *d_cost_var,
                             const cmbpo_term_head_t *th, void *stream);
 
+/* How the learned-cost column is READ.  Every cost of the built-in tasks and of a rule table is an indicator; a
+ * model that learns it with the Bernoulli likelihood (cmbpo_trainer_set_column_kinds, kind 1 on column obs_dim + 1) puts a
+ * logit there, and the cost of an imagined step is its probability.  THE definition -- cc = obs_dim + 1, which needs
+ * CMBPO_TASK_LEARNED_COST; with a logistic head (kind 1) the members' means there are logits z_e = mean[e][r][cc]:
+ *   zs_e     = fl32(z_e - logit_shift)               (logit_shift == 0: z_e bit for bit, no subtraction executed)
+ *   p_e      = sigma32(zs_e) = 1 / (1 + expf(-zs))  for zs >= 0,  expf(zs) / (1 + expf(zs))  otherwise;
+ *              float32, no contraction, the division correctly rounded; +inf -> 1, -inf -> 0, NaN -> NaN
+ *   cost     = p_elite                                without disagreement, or with kappa_cost == 0: bit for bit
+ *   cost_var = np.var(p_e over ALL E members) in cmbpo_fakeenv_post_disagreement's order of operations, on the probabilities
+ *   cost     = clip1(fl32(p_elite + fl32(kappa_cost * sqrtf(cost_var))))   if kappa_cost > 0;  clip1(c) = c > 1 ? 1 : c
+ *              (a positive test: a NaN passes)
+ *   cost_logit[r] = z_elite   (raw, unshifted; slot indexed like d_cost; may be NULL)
+ * sigma32 is one device function used by every instance and every lane: a member's probability has the same bits wherever it
+ * is computed.  logit_shift undoes a class weight: a weight omega on the positive class shifts the fitted logit by log omega
+ * (DESIGN 3v), and logit_shift = log omega reads the column as if it had been fitted without.  Nothing else moves: next_obs,
+ * term, rew, rew_var, dkl_path and ep_var* do not depend on the head; the termination rule's own `done` is what it was; the
+ * column takes no transition noise.  With a termination head as well, the termination column stays the LAST one and cc stays
+ * obs_dim + 1.  kind 0 is the magnitude reading -- the call without the struct, logit_shift and cost_logit unused.  There is no
+ * bit for it in `task`. */
+#define CMBPO_COST_MAGNITUDE 0
+#define CMBPO_COST_LOGISTIC 1
+typedef struct cmbpo_cost_head {
+  int32_t kind;           /* CMBPO_COST_* */
+  float logit_shift;      /* finite */
+  float *cost_logit;      /* [.] or NULL */
+} cmbpo_cost_head_t; /* 16 bytes */
+/* cmbpo_fakeenv_post_term's arguments plus the cost head: the superset, every feature optional.  ch == NULL or kind 0 is exactly
+ * cmbpo_fakeenv_post_term's call (the same kernel instances with the same argument block).  Beside its checks: kind in {0, 1},
+ * a finite logit_shift, kind 1 only with CMBPO_TASK_LEARNED_COST -- each refused with a message naming the cost head, before
+ * any HIP call. */
+int cmbpo_fakeenv_post_cost(int task, int ensemble, int obs_dim, int act_dim,
+                            const float *d_mean, const float *d_var, int ld_rows,
+                            const float *d_obs, const float *d_act,
+                            const int32_t *d_elite, const int32_t *d_row_idx,
+                            const int32_t *d_n_rows, int n_rows, float *d_next_obs,
+                            float *d_rew, uint8_t *d_term, float *d_cost,
+                            float *d_dkl_path, float *d_ep_var_mean,
+                            float *d_ep_var, const float *d_xi,
+                            float kappa_rew, float kappa_cost,
+                            float *d_rew_var, float *d_cost_var,
+                            const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, void *stream);
+
 /* ------------------------------------------------------------------------ *
  * Device-resident rollout state: the fused counterpart of ModelSampler
  * (samplers/model_sampler.py:203-444) + ModelBuffer (buffers/modelbuffer.py).
@@ -450,6 +492,7 @@ int cmbpo_rollout_compact(const cmbpo_rollout_t *r, void *stream);
  * cmbpo_ens_forward -> cmbpo_fakeenv_post -> decide -> finish(PRE) -> store -> cmbpo_ens_predict_mean x 2 at next_obs ->
  * finish(POST), every buffer taken from *r (slot-indexed d_eps [B, act], d_elite [B]; scratch d_mean / d_var
  * [E, B, model out_dim]: obs + 1, or obs + 2 with CMBPO_TASK_LEARNED_COST in `task`).  n_alive = the host's copy of iscal[CMBPO_I_N_ALIVE].
+ * (With a cmbpo_cost_head_t attached -- cmbpo_rollout_cost_head_attach below -- the post-processing is cmbpo_fakeenv_post_cost.)
  * With r->xi != NULL the post-processing is cmbpo_fakeenv_post_noise on those draws; with a cmbpo_disagreement_t attached it is
  * cmbpo_fakeenv_post_disagreement (with or without draws); with a cmbpo_value_disagreement_t attached the critics at next_obs are
  * cmbpo_critic_pair_predict_var (refused before the first launch unless cmbpo_critic_pair_supported(v, vc)). */
@@ -556,6 +599,16 @@ int cmbpo_rollout_value_disagreement_detach(const cmbpo_rollout_t *r);
 int cmbpo_rollout_term_head_attach(const cmbpo_rollout_t *r, const cmbpo_term_head_t *th);
 /* Back to the rules alone (no error when nothing was attached). */
 int cmbpo_rollout_term_head_detach(const cmbpo_rollout_t *r);
+
+/* The cost head's reading along imagined rollouts: a copy of *ch travels beside an unchanged cmbpo_rollout_t in the same table.
+ * Attached, cmbpo_rollout_step / _run post-process with cmbpo_fakeenv_post_cost (with whatever else is attached), so cost_t --
+ * and with it cost_buf, the cost GAE, path_cost and the cost totals -- holds probabilities; with kind 1 they refuse (-1), before
+ * the first launch of a step, a task without CMBPO_TASK_LEARNED_COST and a model whose out_dim is not obs + 2 (+ 1 with a
+ * termination head), with a message naming the cost head.  cost_logit: [B] slot indexed, this step's raw logits, or NULL; owned
+ * by the caller, valid until the detach.  Checked here: kind in {0, 1} and a finite logit_shift. */
+int cmbpo_rollout_cost_head_attach(const cmbpo_rollout_t *r, const cmbpo_cost_head_t *ch);
+/* Back to the magnitude reading (no error when nothing was attached). */
+int cmbpo_rollout_cost_head_detach(const cmbpo_rollout_t *r);
 
 /* ModelBuffer.get (modelbuffer.py:184-226): d_offsets[B+1] = exclusive scan of
  * len; d_stats[8] = {n, adv_mean, adv_std, cadv_mean, ret_mean, cret_mean}
@@ -1083,6 +1136,14 @@ int cmbpo_replay_run_calibrated(const cmbpo_replay_t *rp, const cmbpo_replay_cal
  * forwards to the two existing entry points.  Bitwise the result of the same calls issued one at a time. */
 int cmbpo_replay_run_term(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th,
                           cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream);
+/* ... and with the cost head's reading in its post step (cmbpo_fakeenv_post_cost without noise or disagreement): the superset of
+ * the run entries.  With kind 1 p_cost is the elite's probability, so the table's `p_cost > 0.5` counts are a decision rule on a
+ * probability and the cost's squared error is the Brier score of the column.  The model's out_dim must be obs_dim + 2 (+ 1 with
+ * th), refused with a message naming the cost head; ch == NULL is cmbpo_replay_run_term's call.  Bitwise the result of the same
+ * calls issued one at a time. */
+int cmbpo_replay_run_cost(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th,
+                          const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite,
+                          void *stream);
 
 #ifdef __cplusplus
 }
