@@ -82,6 +82,30 @@ SIGNATURES.update({
     "cmbpo_task_rules_count": (_i, []),
 })
 
+RULE_SRC_DERIVED = 3                              # CMBPO_RULE_SRC_DERIVED: a clause over derived quantities
+RULE_MAX_DERIVED, RULE_MAX_TERMS = 8, 4           # CMBPO_RULE_MAX_DERIVED / _TERMS
+
+
+class RuleTermStruct(C.Structure):
+    """ctypes image of ``cmbpo_rule_term_t`` (16 bytes)."""
+    _fields_ = [("src", C.c_int16), ("pow", C.c_int16), ("col", C.c_int32), ("w", C.c_float), ("c", C.c_float)]
+
+
+class RuleDerivedStruct(C.Structure):
+    """ctypes image of ``cmbpo_rule_derived_t`` (80 bytes)."""
+    _fields_ = [("n_terms", C.c_int32), ("bias", C.c_float), ("reserved", C.c_int32 * 2), ("term", RuleTermStruct * RULE_MAX_TERMS)]
+
+
+class RuleDerivedTableStruct(C.Structure):
+    """ctypes image of ``cmbpo_rule_derived_table_t`` (656 bytes)."""
+    _fields_ = [("n_derived", C.c_int32), ("reserved", C.c_int32 * 3), ("derived", RuleDerivedStruct * RULE_MAX_DERIVED)]
+
+
+SIGNATURES.update({
+    "cmbpo_task_rules_register_ex": (_i, [C.POINTER(TaskRulesStruct), C.POINTER(RuleDerivedTableStruct), C.POINTER(C.c_int)]),
+    "cmbpo_task_rules_get_derived": (_i, [_i, C.POINTER(RuleDerivedTableStruct)]),
+})
+
 
 class RolloutStruct(C.Structure):
     """ctypes image of ``cmbpo_rollout_t`` (include/cmbpo_hip.h), field for field."""

@@ -34,8 +34,10 @@ int cmbpo_grant_lds(K *kern, size_t bytes) { return cmbpo_grant_lds(reinterpret_
 // The registered rule table behind a `task` argument >= CMBPO_TASK_USER_BASE (learned-cost bit allowed), with every clause's
 // columns resolved against the launch's widths: col0 absolute, n_cols a count.  Host code only.  CMBPO_EINVAL with the error set
 // (prefixed with `who`) for an unregistered id, columns outside the source's width, or an act clause without actions.
-// out may be NULL (validation only).
-int cmbpo_internal_task_rules_resolve(const char *who, int task, int obs_dim, int act_dim, bool have_act, cmbpo_task_rules_t *out);
+// out may be NULL (validation only).  The id's derived quantities (cmbpo_rule_derived_table_t) are checked with it -- a term's
+// column inside its source's width, an act term with actions -- and go out resolved through out_derived (n_derived == 0: none).
+int cmbpo_internal_task_rules_resolve(const char *who, int task, int obs_dim, int act_dim, bool have_act, cmbpo_task_rules_t *out,
+                                      cmbpo_rule_derived_table_t *out_derived = nullptr);
 
 #define CMBPO_HIP_CHECK(expr)                                                  \
   do {                                                                         \

@@ -50,39 +50,49 @@ struct PostArgsNoise : PostArgs {
 struct PostArgsRulesNoise : PostArgsRules {
   const float *xi;
 };
-template <bool RULES, bool NOISE>
-using PostArgsBase = std::conditional_t<NOISE, std::conditional_t<RULES, PostArgsRulesNoise, PostArgsNoise>,
-                                        std::conditional_t<RULES, PostArgsRules, PostArgs>>;
+// RULES == 2: a rule id with derived quantities (include/cmbpo_hip.h, cmbpo_rule_derived_table_t) -- their table travels behind the
+// clause table, by value again (656 bytes), and again only in the argument types of instances of their own: a built-in task and a
+// registered table without derived quantities launch the instances, with the argument blocks, they always launched
+struct PostArgsDerived : PostArgsRules {
+  cmbpo_rule_derived_table_t der;   // term columns resolved on the host: absolute, inside the source's width
+};
+struct PostArgsDerivedNoise : PostArgsDerived {
+  const float *xi;
+};
+template <int RULES, bool NOISE>
+using PostArgsBase =
+    std::conditional_t<NOISE, std::conditional_t<RULES == 2, PostArgsDerivedNoise, std::conditional_t<RULES == 1, PostArgsRulesNoise, PostArgsNoise>>,
+                       std::conditional_t<RULES == 2, PostArgsDerived, std::conditional_t<RULES == 1, PostArgsRules, PostArgs>>>;
 // DIS: ensemble disagreement on the reward and the learned-cost column (np.var over ALL members, like ens_ep_var on the
 // observation columns) and the pessimistic reward / cost made from it -- again fields that exist only in the argument types
 // of instances of their own: a launch without the feature runs the kernels it always ran, with the arguments it always had
-template <bool RULES, bool NOISE>
+template <int RULES, bool NOISE>
 struct PostArgsDis : PostArgsBase<RULES, NOISE> {
   float kappa_rew, kappa_cost;    // >= 0, finite; 0: the elite member's value goes out untouched
   float *rew_var, *cost_var;      // [.] slot indexed like rew / cost
 };
-template <bool RULES, bool NOISE, bool DIS = false>
+template <int RULES, bool NOISE, bool DIS = false>
 using PostArgsT = std::conditional_t<DIS, PostArgsDis<RULES, NOISE>, PostArgsBase<RULES, NOISE>>;
 // TERM: the learned termination head (include/cmbpo_hip.h, cmbpo_term_head_t) -- the model's LAST column, out_dim - 1, read by
 // the row's eight lanes in the tail; once more fields that exist only in the argument types of instances of their own
-template <bool RULES, bool NOISE, bool DIS>
+template <int RULES, bool NOISE, bool DIS>
 struct PostArgsTerm : PostArgsT<RULES, NOISE, DIS> {
   float threshold;                // finite
   int members;                    // CMBPO_TERM_ELITE / _ANY / _MAJORITY
   float *term_pred;               // [.] slot indexed like term, or NULL
   uint8_t *term_votes;            // [.] or NULL
 };
-template <bool RULES, bool NOISE, bool DIS = false, bool TERM = false>
+template <int RULES, bool NOISE, bool DIS = false, bool TERM = false>
 using PostArgsX = std::conditional_t<TERM, PostArgsTerm<RULES, NOISE, DIS>, PostArgsT<RULES, NOISE, DIS>>;
 // COST: the logistic learned-cost head (include/cmbpo_hip.h, cmbpo_cost_head_t, kind 1) -- column obs_dim + 1 is a logit and the
 // cost its probability; the same pattern: fields of an argument type of their own, selecting instances of their own.  They are
 // launched with CMBPO_TASK_LEARNED_COST only (checked on the host), so `learned_cost` is not read in their COST parts.
-template <bool RULES, bool NOISE, bool DIS, bool TERM>
+template <int RULES, bool NOISE, bool DIS, bool TERM>
 struct PostArgsCost : PostArgsX<RULES, NOISE, DIS, TERM> {
   float logit_shift;              // finite; 0: the logit goes into sigma32 bit for bit
   float *cost_logit;              // [.] slot indexed like cost: the elite's raw logit, or NULL
 };
-template <bool RULES, bool NOISE, bool DIS = false, bool TERM = false, bool COST = false>
+template <int RULES, bool NOISE, bool DIS = false, bool TERM = false, bool COST = false>
 using PostArgsY = std::conditional_t<COST, PostArgsCost<RULES, NOISE, DIS, TERM>, PostArgsX<RULES, NOISE, DIS, TERM>>;
 
 // np.clip(x, lo, hi): comparisons are false for a NaN, which therefore passes through (fminf / fmaxf would drop it)
@@ -104,7 +114,7 @@ __device__ __forceinline__ float cost_prob(float z, float logit_shift) {
 // EC: the ensemble size at compile time (0: read it at run time) -- with a run-time size the member loops are unrolled to
 // kEMax and masked: 56 pair terms computed and selected for the 42 that exist, a third more instructions
 #define POST_WAVES 5      // waves per SIMD the register allocation aims at (swept 4 / 5 / 6 / 8: 57.7 / 51.1 / 51.3 / 77.4 us at 100 k rows)
-template <int EC, bool RULES = false, bool NOISE = false, bool DIS = false, bool TERM = false, bool COST = false>
+template <int EC, int RULES = 0, bool NOISE = false, bool DIS = false, bool TERM = false, bool COST = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgsY<RULES, NOISE, DIS, TERM, COST> p) {
   extern __shared__ float sm[];
   const int D = p.obs_dim;
@@ -310,6 +320,24 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
         if (k < E) xt = p.mean[k * mstride + (size_t)r * p.out_dim + (p.out_dim - 1)];
       }
     }
+    // RULES == 2: lane k of the row owns derived quantity k.  Its table entry is picked out of the (uniform, scalar-loaded) table
+    // by a chain of selects -- indexing the argument block by the lane would put it into scratch or behind a memory round trip of
+    // its own -- and its operands are requested here, like the DIS / TERM loads ahead of the row sums: next_obs from the s_next
+    // image, obs / act from global memory.  Rows past the end read nothing from global memory, lanes past n_derived nothing at all.
+    [[maybe_unused]] cmbpo_rule_derived_t dq{};
+    [[maybe_unused]] float dx[CMBPO_RULE_MAX_TERMS] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (RULES == 2) {
+#pragma unroll
+      for (int j = 0; j < CMBPO_RULE_MAX_DERIVED; ++j)
+        if (j < p.der.n_derived && k == j) dq = p.der.derived[j];
+#pragma unroll
+      for (int t = 0; t < CMBPO_RULE_MAX_TERMS; ++t)
+        if (t < dq.n_terms) {
+          const int col = dq.term[t].col;
+          if (dq.term[t].src == CMBPO_RULE_SRC_NEXT_OBS) dx[t] = nx[col];
+          else if (r >= 0) dx[t] = dq.term[t].src == CMBPO_RULE_SRC_OBS ? p.obs[(size_t)r * D + col] : p.act[(size_t)r * p.act_dim + col];
+        }
+    }
     auto row_sum = [&](const float *a) {
       float res;
       if (D < 8) {
@@ -335,14 +363,33 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
     // clause; the loop and every field of a clause are uniform over the launch.  All 64 lanes are still here (rows past the
     // end read their stale LDS image and nothing from global memory; their result is dropped below).
     [[maybe_unused]] bool rule_done = false, rule_obj = false;
-    if constexpr (RULES) {
+    // RULES == 2: g = bias; per term t = fl32(x - c), squared with pow 2, g = fl32(g + fl32(w * t)) -- single roundings in the
+    // header's order (the file is built without contraction); a lane past n_derived holds +0, which no clause can address
+    [[maybe_unused]] float g = 0.0f;
+    if constexpr (RULES == 2) {
+      g = dq.bias;
+#pragma unroll
+      for (int t = 0; t < CMBPO_RULE_MAX_TERMS; ++t)
+        if (t < dq.n_terms) {
+          float tt = __fsub_rn(dx[t], dq.term[t].c);
+          if (dq.term[t].pow == 2) tt = __fmul_rn(tt, tt);
+          g = __fadd_rn(g, __fmul_rn(dq.term[t].w, tt));
+        }
+    }
+    if constexpr (RULES != 0) {
       for (int c = 0; c < p.rules.n_clauses; ++c) {
         const cmbpo_rule_clause_t &cl = p.rules.clause[c];
         const bool any = (cl.flags & CMBPO_RULE_ANY) != 0;
         bool all_k = true, any_k = false;
+        // a derived clause: lane k of the row tests quantity col0 + k, fetched from the lane that owns it -- here, where all 64
+        // lanes are converged (the column loop below is not), at most 8 quantities: one pass of that loop
+        [[maybe_unused]] float xg = 0.0f;
+        if constexpr (RULES == 2)
+          if (cl.src == CMBPO_RULE_SRC_DERIVED) xg = __shfl(g, 8 * rw + ((cl.col0 + k) & 7), 64);
         for (int d = cl.col0 + k; d < cl.col0 + cl.n_cols; d += 8) {
           float x = 0.0f;
           if (cl.src == CMBPO_RULE_SRC_NEXT_OBS) x = nx[d];
+          else if (RULES == 2 && cl.src == CMBPO_RULE_SRC_DERIVED) x = xg;
           else if (r >= 0) x = cl.src == CMBPO_RULE_SRC_OBS ? p.obs[(size_t)r * D + d] : p.act[(size_t)r * p.act_dim + d];
           float f = __fmul_rn(x, cl.scale);
           if (cl.flags & CMBPO_RULE_ABS) f = fabsf(f);
@@ -419,7 +466,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
     }
     uint8_t done = 0;
     float cost = 0.0f;
-    if constexpr (RULES) {
+    if constexpr (RULES != 0) {
       done = ((p.rules.require_finite && !fin) || rule_done) ? 1 : 0;
       const float obj = rule_obj ? 1.0f : 0.0f;
       cost = p.rules.cost_on_term ? fminf(__fadd_rn((float)done, obj), 1.0f) : obj;      // statics.py:51-52
@@ -472,14 +519,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
 }
 
 // one launch of the instance for (ensemble size, RULES, NOISE, DIS, TERM, COST)
-template <bool RULES, bool NOISE, bool DIS = false, bool TERM = false, bool COST = false>
+template <int RULES, bool NOISE, bool DIS = false, bool TERM = false, bool COST = false>
 void launch_post(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsY<RULES, NOISE, DIS, TERM, COST> &a) {
   if (ensemble == 7) hipLaunchKernelGGL((fakeenv_post_kernel<7, RULES, NOISE, DIS, TERM, COST>), grid, dim3(kThreads), lds, stream, a);   // the shipped configs
   else if (ensemble == 5) hipLaunchKernelGGL((fakeenv_post_kernel<5, RULES, NOISE, DIS, TERM, COST>), grid, dim3(kThreads), lds, stream, a);
   else hipLaunchKernelGGL((fakeenv_post_kernel<0, RULES, NOISE, DIS, TERM, COST>), grid, dim3(kThreads), lds, stream, a);
 }
 // ... and the logistic cost head (ch == NULL: the instances without it, with the argument block they always had)
-template <bool RULES, bool NOISE, bool DIS, bool TERM>
+template <int RULES, bool NOISE, bool DIS, bool TERM>
 void launch_post_cost(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsX<RULES, NOISE, DIS, TERM> &a,
                       const cmbpo_cost_head_t *ch) {
   if (ch == nullptr) return launch_post<RULES, NOISE, DIS, TERM>(ensemble, grid, lds, stream, a);
@@ -491,7 +538,7 @@ void launch_post_cost(int ensemble, dim3 grid, size_t lds, hipStream_t stream, c
 
 // DisExtra (fakeenv_post_internal.h): what the disagreement adds to the arguments (NULL: the instances without the feature)
 // ... and cmbpo_fakeenv_post_term (th == NULL: the instances without the head, with the argument block they always had)
-template <bool RULES, bool NOISE, bool DIS>
+template <int RULES, bool NOISE, bool DIS>
 void launch_post_term(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsT<RULES, NOISE, DIS> &a,
                       const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch) {
   if (th == nullptr) return launch_post_cost<RULES, NOISE, DIS, false>(ensemble, grid, lds, stream, a, ch);
@@ -500,7 +547,7 @@ void launch_post_term(int ensemble, dim3 grid, size_t lds, hipStream_t stream, c
   at.threshold = th->threshold; at.members = th->members; at.term_pred = th->term_pred; at.term_votes = th->term_votes;
   launch_post_cost<RULES, NOISE, DIS, true>(ensemble, grid, lds, stream, at, ch);
 }
-template <bool RULES, bool NOISE>
+template <int RULES, bool NOISE>
 void launch_post_ext(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsBase<RULES, NOISE> &a, const DisExtra *dis,
                      const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch) {
   if (dis == nullptr) return launch_post_term<RULES, NOISE, false>(ensemble, grid, lds, stream, a, th, ch);
@@ -541,9 +588,10 @@ int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream) {
     CMBPO_REQUIRE(c.ch->kind == 0 || learned_cost,
                   "%s: cost head: kind 1 (logistic) needs CMBPO_TASK_LEARNED_COST (a static cost rule has no logit), task %d", who, task_arg);
   }
-  PostArgsRules ar{};
+  PostArgsDerived ar{};
   if (user)     // (registered? columns inside obs_dim / act_dim? -- host code, before any HIP call)
-    if (int rc = cmbpo_internal_task_rules_resolve(who, task_arg, obs_dim, act_dim, c.act != nullptr, &ar.rules)) return rc;
+    if (int rc = cmbpo_internal_task_rules_resolve(who, task_arg, obs_dim, act_dim, c.act != nullptr, &ar.rules, &ar.der)) return rc;
+  const bool derived = user && ar.der.n_derived > 0;      // the instances with the derived table in their arguments
   CMBPO_REQUIRE(c.mean && c.var && c.obs && c.elite && c.next_obs && c.rew && c.term && c.cost && c.dkl_path && c.ep_var_mean,
                 "%s: NULL buffer", who);
   if (dis != nullptr) {
@@ -570,19 +618,25 @@ int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   if (user) static_cast<PostArgs &>(ar) = a;
   if (c.xi != nullptr) {
-    if (user) {
+    if (derived) {
+      PostArgsDerivedNoise an{};
+      static_cast<PostArgsDerived &>(an) = ar;
+      an.xi = c.xi;
+      launch_post_ext<2, true>(ensemble, grid, lds, s, an, dis, th, ch);
+    } else if (user) {
       PostArgsRulesNoise an{};
       static_cast<PostArgsRules &>(an) = ar;
       an.xi = c.xi;
-      launch_post_ext<true, true>(ensemble, grid, lds, s, an, dis, th, ch);
+      launch_post_ext<1, true>(ensemble, grid, lds, s, an, dis, th, ch);
     } else {
       PostArgsNoise an{};
       static_cast<PostArgs &>(an) = a;
       an.xi = c.xi;
-      launch_post_ext<false, true>(ensemble, grid, lds, s, an, dis, th, ch);
+      launch_post_ext<0, true>(ensemble, grid, lds, s, an, dis, th, ch);
     }
-  } else if (user) launch_post_ext<true, false>(ensemble, grid, lds, s, ar, dis, th, ch);
-  else launch_post_ext<false, false>(ensemble, grid, lds, s, a, dis, th, ch);
+  } else if (derived) launch_post_ext<2, false>(ensemble, grid, lds, s, ar, dis, th, ch);
+  else if (user) launch_post_ext<1, false>(ensemble, grid, lds, s, ar, dis, th, ch);
+  else launch_post_ext<0, false>(ensemble, grid, lds, s, a, dis, th, ch);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }

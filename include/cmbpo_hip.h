@@ -68,7 +68,9 @@ extern "C" {
  *   done = (require_finite && !isfinite(next_obs).all()) || some HEALTHY clause does not hold || some FATAL clause holds
  *   obj  = 1.0f if some COST clause holds, else 0.0f
  *   cost = cost_on_term ? min(1, done + obj) : obj            (the shape of models/statics.py:51-52)
- * With CMBPO_TASK_LEARNED_COST the cost is the model's column; COST clauses and cost_on_term are ignored, done is not. */
+ * With CMBPO_TASK_LEARNED_COST the cost is the model's column; COST clauses and cost_on_term are ignored, done is not.
+ * What an interval on one column cannot say (a distance, a speed, a tilt) is a derived quantity, below: a fourth source,
+ * CMBPO_RULE_SRC_DERIVED, known to cmbpo_task_rules_register_ex only. */
 #define CMBPO_TASK_USER_BASE 16
 #define CMBPO_TASK_USER_SLOTS 64
 #define CMBPO_RULE_MAX_CLAUSES 16
@@ -102,6 +104,54 @@ int cmbpo_task_rules_register(const cmbpo_task_rules_t *rules, int *out_task);
 int cmbpo_task_rules_get(int task, cmbpo_task_rules_t *out);
 /* number of registered tables */
 int cmbpo_task_rules_count(void);
+
+/* Derived quantities: what an interval on a single column cannot say -- "within radius r of a point", a planar speed limit,
+ * a tilt limit 1 - 2 (q1^2 + q2^2) >= c (models/statics.py:22, z_rot).  A rule set may declare up to 8 of them, each a bias
+ * and up to 4 terms, evaluated per branch in float32 with single roundings, in this order, without contraction:
+ *   g = bias
+ *   for each term in order:
+ *     t = fl32(x - c)                     x: column `col` of the term's source row (next_obs, obs or act; col < 0 counts
+ *     if pow == 2: t = fl32(t * t)           from the end, resolved against obs_dim / act_dim at launch)
+ *     g = fl32(g + fl32(w * t))
+ * A clause with src CMBPO_RULE_SRC_DERIVED tests derived quantities instead of columns: col0 / n_cols index them (col0 < 0
+ * counts from the last one, n_cols == -1 means through the last one) and everything else about the clause -- scale, ABS,
+ * the interval, ANY, the role -- applies to g unchanged.  A NaN g never holds; inf - inf is NaN by the arithmetic above.
+ * Products of two different columns stay out. */
+#define CMBPO_RULE_SRC_DERIVED 3
+#define CMBPO_RULE_MAX_DERIVED 8
+#define CMBPO_RULE_MAX_TERMS 4
+
+typedef struct cmbpo_rule_term {
+  int16_t src; /* CMBPO_RULE_SRC_NEXT_OBS / _OBS / _ACT */
+  int16_t pow; /* 1 or 2 */
+  int32_t col;
+  float w, c;  /* finite */
+} cmbpo_rule_term_t; /* 16 bytes */
+
+typedef struct cmbpo_rule_derived {
+  int32_t n_terms; /* 1..4 */
+  float bias;      /* finite */
+  int32_t reserved[2];
+  cmbpo_rule_term_t term[CMBPO_RULE_MAX_TERMS];
+} cmbpo_rule_derived_t; /* 80 bytes */
+
+typedef struct cmbpo_rule_derived_table {
+  int32_t n_derived; /* 0 (none) .. 8 */
+  int32_t reserved[3];
+  cmbpo_rule_derived_t derived[CMBPO_RULE_MAX_DERIVED];
+} cmbpo_rule_derived_table_t; /* 656 bytes */
+
+/* cmbpo_task_rules_register with derived quantities.  derived == NULL or n_derived == 0 IS cmbpo_task_rules_register (the
+ * same checks, the same messages, the same id for a byte-identical table; src CMBPO_RULE_SRC_DERIVED stays unknown there).
+ * Otherwise the clause table is checked as before, with CMBPO_RULE_SRC_DERIVED a known source, and the derived table:
+ * n_derived in 1..8, n_terms in 1..4, a term's src in {next_obs, obs, act}, pow in {1, 2}, finite w / c / bias, reserved
+ * fields zero, a derived clause's indices inside [0, n_derived).  Every rejection names the field and its place
+ * ("derived 2: term 1: w ...", "clause 0: ... derived ...").  Ids are deduplicated on the pair of byte images and share
+ * the slots of cmbpo_task_rules_register. */
+int cmbpo_task_rules_register_ex(const cmbpo_task_rules_t *rules, const cmbpo_rule_derived_table_t *derived, int *out_task);
+/* the derived table behind a registered rule id (all zeros for an id registered without one); CMBPO_EINVAL if the id is
+ * not registered */
+int cmbpo_task_rules_get_derived(int task, cmbpo_rule_derived_table_t *out);
 
 const char *cmbpo_last_error(void);
 int cmbpo_version(void);
