@@ -76,9 +76,11 @@ __global__ void norm_finalize(int n, int pass, double *st) {
 __global__ void norm_apply(int n, float *adv, float *cadv, const double *st) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float m = (float)st[1], den = (float)st[2] + 1e-8f, cm = (float)st[3];
+  const float m = (float)st[1], den = (float)st[2] + 1e-8f;
   adv[i] = __fsub_rn(adv[i], m) / den;
-  cadv[i] = __fsub_rn(cadv[i], cm);
+  // centred against the float64 mean and rounded once: a mean cast to float32 first costs an entry near the mean up to
+  // u |mean| (2^-24 relative to the MEAN, not to the entry), which nothing downstream rescales away
+  cadv[i] = (float)__dsub_rn((double)cadv[i], st[3]);
 }
 
 }  // namespace

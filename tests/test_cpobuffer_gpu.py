@@ -1,6 +1,10 @@
 """GPU: CPOBuffer (HIP GAE + normalisation behind the reference's buffer API) vs golden G8 recorded from the
 reference's own CPOBuffer.  ret / cret are bit-exact (float64 recurrence, float32 casts, incl. the float64-zero
-bootstrap promotion); normalised advantages within 1e-5 (statistics summed in a different order)."""
+bootstrap promotion); normalised advantages within 1e-5 (statistics summed in a different order).
+
+The kernel-level bounds -- cmbpo_gae_segments bit for bit at many paths, empty segments and every mask value, cmbpo_adv_normalize
+against float64 at sizes up to the workgroup cap -- are in tests/test_gae_segments_gpu.py, derived in tests/vec_gae_ref.py and
+shown to reject a wrong kernel in tests/test_vec_gae_cpu.py."""
 import os
 
 import numpy as np
