@@ -24,6 +24,7 @@
 #include "common.h"
 #include "ens_mlp_internal.h"
 #include "mfma_tile.h"
+#include "train_loss.h"
 
 #include <math.h>
 #include <string.h>
@@ -447,38 +448,11 @@ __global__ __launch_bounds__(kThreads, (BT == 1 ? 2 : 1)) void ens_mlp_kernel(
         p.out0[((size_t)e * n_rows + row0 + b) * ow + n] = reduced(b, n);
       }
       if (p.tr_loss_part) {
-        // this tile's share of the loss statistics (sum (m - t)^2, sum (var - mse)^2, sum lv^2): the backward kernel
-        // adds the tiles' partials in a fixed order, so the training step needs no separate reduction kernels
-        const int D = p.tr_tdim;
-        const bool prob = ow == 2 * D;
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-        for (int i = tid; i < BB * D; i += kThreads) {
-          const int b = i / D, d = i - b * D;
-          const int r = rows[b];
-          if (r < 0) continue;
-          float t = p.tr_targets[(size_t)r * D + d];
-          if (p.out_mu) t = (t - p.out_mu[d]) / p.out_sig[d];
-          const float diff = reduced(b, d) - t;
-          const float mse = diff * diff;
-          s0 += (double)mse;
-          if (prob) {
-            const float lv = reduced(b, D + d);
-            const float dv = expf(lv) - mse;
-            s1 += (double)(dv * dv);
-            s2 += (double)(lv * lv);
-          }
-        }
-        __shared__ double s_loss[3][kWaves];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          s0 += __shfl_down(s0, o, 64);
-          s1 += __shfl_down(s1, o, 64);
-          s2 += __shfl_down(s2, o, 64);
-        }
-        if (lane == 0) { s_loss[0][wave] = s0; s_loss[1][wave] = s1; s_loss[2][wave] = s2; }
-        __syncthreads();
-        if (tid < 3)
-          p.tr_loss_part[(size_t)item * 3 + tid] = (s_loss[tid][0] + s_loss[tid][1]) + (s_loss[tid][2] + s_loss[tid][3]);
+        // this tile's share of the loss statistics (tile_loss_stats; the rows are gathered already: rows[])
+        const TargetView tv{p.tr_targets, nullptr, 0, p.out_mu, p.out_sig, p.tr_tdim};
+        const double v = tile_loss_stats<BB, kThreads, LOSS_PLAIN>(tv, LossExtras<LOSS_PLAIN>{}, ow == 2 * tv.D, wave, reduced,
+                                                                   [&](int b) { return rows[b]; });
+        store_tile_stats(p.tr_loss_part, item, false, v);
       }
     } else if constexpr (HEAD == CMBPO_HEAD_DETMEAN) {
       const int out = p.out_dim;

@@ -22,6 +22,7 @@
 #include "f16_split.h"
 #include "mfma_tile.h"
 #include "row_tile.h"
+#include "train_loss.h"
 
 #include <math.h>
 #include <new>
@@ -34,35 +35,7 @@ namespace {
 constexpr int kThreads = 256;
 
 // ------------------------------------------------------------------------------------------------------------
-// Optional terms of the deterministic ('MSE') loss, pe.py:866-868,881-905,917: per-sample weights and the clipped
-// prediction of a trust-region value update.  Kernels that know them are template instances of their own whose argument
-// type carries this block; the plain instances have neither the pointers nor the code.
-// ------------------------------------------------------------------------------------------------------------
-struct ValueExtras {
-  const float *w;          // [N] weight of data row r (nullptr: 1)
-  const float *old_pred;   // [N][D] earlier prediction of row r, unscaled (nullptr: no clipping)
-  const float *clip_c;     // the step's clip range c = sqrt(2) sqrt(kl old_var) (old_var_final_kernel); read when old_pred is set
-};
-
-// (m_c - t') w of one output, with the gradient of tf.clip_by_value: nothing outside [-c, c].  olds is the scaled old prediction.
-__device__ __forceinline__ float value_delta(float m, float t, bool clip, float olds, float c, float w) {
-  float d = m - t;
-  if (clip) {
-    const float dm = m - olds;
-    const float mc = olds + fminf(fmaxf(dm, -c), c);
-    d = (dm >= -c && dm <= c) ? mc - t : 0.0f;
-  }
-  return w * d;
-}
-
-__device__ __forceinline__ float scaled_old(const ValueExtras &x, int src, int D, int d, const float *out_mu, const float *out_sig) {
-  float v = x.old_pred[(size_t)src * D + d];
-  if (out_mu) v = (v - out_mu[d]) / out_sig[d];     // the transform of the targets: both sides of the clip in one unit
-  return v;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// loss: per-member sums, then d(train_loss)/d(raw output)
+// loss: per-member sums, then d(train_loss)/d(raw output).  What the loss of an element is stands in train_loss.h.
 // ------------------------------------------------------------------------------------------------------------
 struct LossArgs {
   const float *o;          // [E][B][O] raw network output
@@ -71,75 +44,29 @@ struct LossArgs {
   int idx_stride;
   const float *out_mu, *out_sig;   // output scaler (nullptr: identity)
   int E, B, O, D;
-  double *sums;            // [E]: sum (mean - t)^2
-};
-struct LossWArgs : LossArgs {
-  const float *w;          // [N] sample weights: sum w[row] (mean - t)^2
+  double *sums;            // [E]: sum w (mean - t)^2 on Gaussian columns and of 2 w l on logistic ones (finalize halves)
 };
 
-// Column and class weights of the probabilistic losses (the definition stands in include/cmbpo_hip.h): element (row,
-// d) of a member's batch weighs col[d], times pos[d] where the RAW target (before the output scaler) is positive.  The test is
-// written positively: a NaN target takes the plain weight.  Kernels that know them are instances of their own, like the ones of
-// ValueExtras above.
-struct ColWeights {
-  const float *col, *pos;  // [D] each, both set
-};
-__device__ __forceinline__ float column_weight(const ColWeights &c, int d, float raw_target) {
-  return c.col[d] * (raw_target > 0.5f ? c.pos[d] : 1.0f);
-}
-struct LossCArgs : LossArgs {
-  ColWeights c;            // sum w[row][d] (mean - t)^2
-};
-
-// Column kinds of the probabilistic losses (the definition stands in include/cmbpo_hip.h at
-// cmbpo_trainer_set_column_kinds): kind[d] != 0 reads the mean output of column d as a logit z and trains it with the Bernoulli
-// negative log-likelihood of y = (raw target > 0.5f), never through the output scaler.  Kernels that know the kinds are instances
-// of their own again; they always carry ColWeights (all ones from the trainer's pool when none are attached).
-__device__ __forceinline__ float bernoulli_nll(float z, bool y) {     // softplus(z) - y z, finite for every finite z
-  return fmaxf(z, 0.0f) - (y ? z : 0.0f) + log1pf(expf(-fabsf(z)));
-}
-__device__ __forceinline__ float sigmoid_of(float z) {
-  if (z >= 0.0f) return 1.0f / (1.0f + expf(-z));
-  const float ez = expf(z);
-  return ez / (1.0f + ez);
-}
-struct LossLArgs : LossCArgs {
-  const unsigned char *kind;   // [D]; sum of w (mean - t)^2 on Gaussian columns and of 2 w l on logistic ones (finalize halves)
-};
-
-__device__ __forceinline__ float scaled_target(const LossArgs &p, int e, int b, int d) {
-  const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
-  float t = p.targets[(size_t)row * p.D + d];
-  if (p.out_mu) t = (t - p.out_mu[d]) / p.out_sig[d];   // TensorStandardScaler.transform, models/pens/utils.py:156
-  return t;
-}
-
-template <class P>
-__global__ __launch_bounds__(kThreads) void loss_sums_kernel(const P p) {
+template <LossMode M>
+__global__ __launch_bounds__(kThreads) void loss_sums_kernel(const WithLoss<LossArgs, M> p) {
+  const LossExtras<M> &x = p;
+  const TargetView tv = target_view(p);
   const int e = blockIdx.y;
   double s_mse = 0.0;
   const int n = p.B * p.D;
   for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
     const int b = i / p.D, d = i - b * p.D;
     const float *orow = p.o + ((size_t)e * p.B + b) * p.O;
-    if constexpr (std::is_same<P, LossLArgs>::value) {
-      if (p.kind[d]) {
-        const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
-        const float traw = p.targets[(size_t)row * p.D + d];
-        s_mse += 2.0 * (double)(column_weight(p.c, d, traw) * bernoulli_nll(orow[d], traw > 0.5f));
+    const int src = tv.src_row(e, b);
+    const float traw = tv.raw(src, d);
+    if constexpr (has_kinds(M)) {
+      if (x.kind[d]) {
+        s_mse += 2.0 * (double)(column_weight(x, d, traw) * bernoulli_nll(orow[d], traw > 0.5f));
         continue;
       }
     }
-    const float diff = orow[d] - scaled_target(p, e, b, d);
-    if constexpr (std::is_same<P, LossWArgs>::value) {
-      const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
-      s_mse += (double)p.w[row] * (double)(diff * diff);
-    } else if constexpr (std::is_same<P, LossCArgs>::value || std::is_same<P, LossLArgs>::value) {
-      const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
-      s_mse += (double)column_weight(p.c, d, p.targets[(size_t)row * p.D + d]) * (double)(diff * diff);
-    } else {
-      s_mse += (double)(diff * diff);
-    }
+    const float diff = orow[d] - tv.scaled(traw, d);
+    s_mse += (double)loss_weight<M>(x, src, d, traw) * (double)(diff * diff);     // (the product in float64, unlike the statistics')
   }
   __shared__ double sm[kThreads / 64];
   s_mse = wave_sum(s_mse);
@@ -175,14 +102,14 @@ struct OldVarArgs {
 __global__ __launch_bounds__(kThreads) void old_var_part_kernel(const OldVarArgs p) {
   const long n = (long)p.E * p.B * p.D;
   const int bd = p.B * p.D;
+  const TargetView tv = target_view(p);
   double s = 0.0;
   for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) {
     const int e = (int)(i / bd), r = (int)(i - (long)e * bd);
     const int b = r / p.D, d = r - b * p.D;
-    const int row = p.idx ? p.idx[(size_t)e * p.idx_stride + b] : b;
-    float t = p.targets[(size_t)row * p.D + d], o = p.old_pred[(size_t)row * p.D + d];
-    if (p.out_mu) { t = (t - p.out_mu[d]) / p.out_sig[d]; o = (o - p.out_mu[d]) / p.out_sig[d]; }
-    const float diff = o - t;
+    const int row = tv.src_row(e, b);
+    const float t = tv.raw(row, d), o = p.old_pred[(size_t)row * p.D + d];
+    const float diff = tv.scaled(o, d) - tv.scaled(t, d);
     s += (double)(0.5f * (diff * diff));
   }
   __shared__ double sm[kThreads / 64];
@@ -204,9 +131,8 @@ __global__ __launch_bounds__(64) void old_var_final_kernel(const double *part, i
 
 // The per-tile loss statistics of a column-weighted 'MSPE' step: sum w mse, sum w (var - mse)^2, sum lv^2 of every tile, from the
 // raw outputs the training forward stored, into the [items][3] layout its epilogue writes (mspe_ratio adds them).  ROWS = 32
-// walks the tiles of ens_mlp_kernel<HEAD_TRAIN> on 256 threads, ROWS = 64 the items of fwd_train_h_kernel on 512 (whose sums
-// stand in the first of an item's two 32-row slots): the same element-to-thread map, the same float32 terms and the same order
-// of the float64 sums as the forward that ran, so all-ones weights reproduce its statistics bit for bit.  No atomics.
+// walks the tiles of ens_mlp_kernel<HEAD_TRAIN> on 256 threads, ROWS = 64 the items of fwd_train_h_kernel on 512: the same
+// tile_loss_stats as the forward that ran, so all-ones weights reproduce its statistics bit for bit.  No atomics.
 struct ColStatsArgs {
   const float *o;          // [E][B][O] raw network output, O == 2 D
   const float *targets;    // [N][D]
@@ -214,63 +140,20 @@ struct ColStatsArgs {
   int idx_stride;
   const float *out_mu, *out_sig;
   int B, O, D, tiles32;
-  ColWeights c;
   double *loss_part;       // [E * tiles32][3]
 };
 
-struct ColStatsLArgs : ColStatsArgs {
-  const unsigned char *kind;   // [D]: logistic columns stay out of sum w mse and sum w (var - mse)^2, and in sum lv^2
-};
-
-template <int ROWS, class A>
-__device__ __forceinline__ void col_stats_body(const A &p) {
-  constexpr int NT = 8 * ROWS, NW = NT / 64;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+template <int ROWS, LossMode M>
+__global__ __launch_bounds__(8 * ROWS) void col_stats_kernel(const WithLoss<ColStatsArgs, M> p) {
   const int e = blockIdx.y, row0 = blockIdx.x * ROWS;
-  const int D = p.D;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-  for (int i = tid; i < ROWS * D; i += NT) {
-    const int b = i / D, d = i - b * D;
-    const int row = row0 + b;
-    if (row >= p.B) continue;
-    const int src = p.idx ? p.idx[(size_t)e * p.idx_stride + row] : row;
-    const float traw = p.targets[(size_t)src * D + d];
-    float t = traw;
-    if (p.out_mu) t = (t - p.out_mu[d]) / p.out_sig[d];
-    const float *orow = p.o + ((size_t)e * p.B + row) * p.O;
-    if constexpr (std::is_same<A, ColStatsLArgs>::value) {
-      if (p.kind[d]) { s2 += (double)(orow[D + d] * orow[D + d]); continue; }
-    }
-    const float diff = orow[d] - t;
-    const float mse = diff * diff;
-    const float w = column_weight(p.c, d, traw);
-    s0 += (double)(w * mse);
-    const float lv = orow[D + d];
-    const float dv = expf(lv) - mse;
-    s1 += (double)(w * (dv * dv));
-    s2 += (double)(lv * lv);
-  }
-  __shared__ double s_loss[3][NW];
-  s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
-  if (lane == 0) { s_loss[0][wave] = s0; s_loss[1][wave] = s1; s_loss[2][wave] = s2; }
-  __syncthreads();
-  if (tid < 3) {
-    if constexpr (ROWS == 32) {
-      p.loss_part[((size_t)e * p.tiles32 + blockIdx.x) * 3 + tid] = (s_loss[tid][0] + s_loss[tid][1]) + (s_loss[tid][2] + s_loss[tid][3]);
-    } else {
-      const size_t item0 = (size_t)e * p.tiles32 + 2 * blockIdx.x;
-      double tsum = 0.0;
-      for (int w = 0; w < NW; ++w) tsum += s_loss[tid][w];
-      p.loss_part[item0 * 3 + tid] = tsum;
-      if (2 * (int)blockIdx.x + 1 < p.tiles32) p.loss_part[(item0 + 1) * 3 + tid] = 0.0;
-    }
-  }
+  const TargetView tv = target_view(p);
+  const float *o0 = p.o + ((size_t)e * p.B + row0) * p.O;
+  const double v = tile_loss_stats<ROWS, 8 * ROWS, M>(
+      tv, p, true, threadIdx.x >> 6, [&](int b, int k) { return o0[(size_t)b * p.O + k]; },
+      [&](int b) { return row0 + b < p.B ? tv.src_row(e, row0 + b) : -1; });
+  const size_t item = (size_t)e * p.tiles32 + (ROWS / 32) * blockIdx.x;
+  store_tile_stats(p.loss_part, item, ROWS == 64 && 2 * (int)blockIdx.x + 1 < p.tiles32, v);
 }
-
-template <int ROWS>
-__global__ __launch_bounds__(8 * ROWS) void col_stats_kernel(const ColStatsArgs p) { col_stats_body<ROWS>(p); }
-template <int ROWS>
-__global__ __launch_bounds__(8 * ROWS) void col_stats_l_kernel(const ColStatsLArgs p) { col_stats_body<ROWS>(p); }
 
 // ------------------------------------------------------------------------------------------------------------
 // backward chain:  d2 = (d3 W2^T) * g2 ;  d1 = (d2 W1^T) * g1      (g = swish'(z) exported by the forward)
@@ -294,15 +177,8 @@ struct BwdArgs {
   float *d3_out;             // [E][B][OPk], written for the weight-gradient kernel
   float *opmax;              // [E * tiles][8]: largest |d1|, |d2|, |d3| of the tile into slots 3..5 (nullptr: not wanted)
 };
-struct BwdXArgs : BwdArgs {
-  ValueExtras x;             // deterministic heads (prob == 0) only
-};
-struct BwdCArgs : BwdArgs {
-  ColWeights c;              // probabilistic heads (prob != 0) only; loss_part then holds the weighted sums (col_stats_kernel)
-};
-struct BwdLArgs : BwdCArgs {
-  const unsigned char *kind; // [D] column kinds; loss_part holds the sums over the Gaussian columns (col_stats_l_kernel)
-};
+// (LOSS_VALUE: deterministic heads, prob == 0, only.  LOSS_COLW / LOSS_KINDS: probabilistic heads, prob != 0, only; loss_part
+// then holds the weighted sums, over the Gaussian columns, that col_stats_kernel left.)
 
 // `ratio` of the MSPE loss, 0.05 * mean_all(mse) / mean_all((var - mse)^2): a constant of the step.  The two sums come from
 // the forward's per-tile statistics (with column weights attached: sum w mse and sum w (var - mse)^2, rewritten by
@@ -336,51 +212,44 @@ __device__ __forceinline__ float mspe_ratio(const BwdArgs &p, int tid) {
 // NLL (pe.py:840-919, inc_var_loss = True; prob == 2): total_e = mean 0.5 exp(-lv) (m - t)^2 + mean 0.5 lv; no
 // coupling between members.  (Its max_logvar / min_logvar variables only carry a constant regulariser gradient
 // and never enter the network, pe.py:198-209,263,789-838: they are host-side bookkeeping, pens.PE.)
-template <class P>
-__device__ __forceinline__ float output_delta(const P &p, int e, int row, int k, float ratio, float inv_bd) {
+template <LossMode M>
+__device__ __forceinline__ float output_delta(const WithLoss<BwdArgs, M> &p, int e, int row, int k, float ratio, float inv_bd) {
   if (k >= p.O) return 0.0f;
+  const LossExtras<M> &x = p;
+  const TargetView tv = target_view(p);
   const float *orow = p.o + ((size_t)e * p.B + row) * p.O;
-  const int src = p.idx ? p.idx[(size_t)e * p.idx_stride + row] : row;
+  const int src = tv.src_row(e, row);
   const int dd = (k < p.D) ? k : k - p.D;
-  const float traw = p.targets[(size_t)src * p.D + dd];
-  float t = traw;
-  if (p.out_mu) t = (t - p.out_mu[dd]) / p.out_sig[dd];
-  if constexpr (std::is_same<P, BwdXArgs>::value) {     // weighted / clipped 'MSE' (DESIGN §3j); the host admits no other head
-    const bool clip = p.x.old_pred != nullptr;
-    const float olds = clip ? scaled_old(p.x, src, p.D, dd, p.out_mu, p.out_sig) : 0.0f;
-    return value_delta(orow[dd], t, clip, olds, clip ? *p.x.clip_c : 0.0f, p.x.w ? p.x.w[src] : 1.0f) * inv_bd;
+  const float traw = tv.raw(src, dd);
+  const float t = tv.scaled(traw, dd);
+  if constexpr (has_value(M)) {     // weighted / clipped 'MSE' (DESIGN §3j); the host admits no other head
+    const bool clip = x.old_pred != nullptr;
+    const float olds = clip ? scaled_old(x, tv, src, dd) : 0.0f;
+    return value_delta(orow[dd], t, clip, olds, clip ? *x.clip_c : 0.0f, loss_weight<M>(x, src, dd, traw)) * inv_bd;
   }
-  if constexpr (std::is_same<P, BwdLArgs>::value) {     // a logistic column: w (sigma(z) - y) on the raw logit and
-    if (p.kind[dd]) {                                   // target; its log-variance output keeps 'MSPE''s regulariser alone
-      if (k < p.D) return column_weight(p.c, dd, traw) * (sigmoid_of(orow[dd]) - (traw > 0.5f ? 1.0f : 0.0f)) * inv_bd;
+  if constexpr (has_kinds(M)) {     // a logistic column: w (sigma(z) - y) on the raw logit and
+    if (x.kind[dd]) {               // target; its log-variance output keeps 'MSPE''s regulariser alone
+      if (k < p.D) return column_weight(x, dd, traw) * (sigmoid_of(orow[dd]) - (traw > 0.5f ? 1.0f : 0.0f)) * inv_bd;
       return p.prob == 2 ? 0.0f : (0.1f * orow[k]) * inv_bd;
     }
   }
   const float diff = orow[dd] - t;
-  // column / class weights, also the Gaussian columns of a model with kinds: w on every data term, the log-variance
-  // regulariser stays plain; the host admits no 'MSE' head.  (With w == 1 every product below is the plain one: same bits.)
-  if constexpr (std::is_same<P, BwdCArgs>::value || std::is_same<P, BwdLArgs>::value) {
-    const float w = column_weight(p.c, dd, traw);
-    if (p.prob == 2) {
-      const float iv = expf(-orow[p.D + dd]);
-      return (k < p.D) ? w * (iv * diff) * inv_bd : w * (0.5f - 0.5f * iv * diff * diff) * inv_bd;
-    }
-    if (k < p.D) return w * (2.0f * diff) * inv_bd;
-    const float lv = orow[k], var = expf(lv);
-    return (w * (2.0f * ratio * (var - diff * diff) * var) + 0.1f * lv) * inv_bd;
+  if constexpr (!has_colw(M)) {     // (the host admits no 'MSE' head with column weights)
+    if (!p.prob) return diff * inv_bd;
   }
-  if (!p.prob) return diff * inv_bd;
+  // w (the literal 1 without column weights) on every data term, the log-variance regulariser stays plain
+  const float w = loss_weight<M>(x, src, dd, traw);
   if (p.prob == 2) {
     const float iv = expf(-orow[p.D + dd]);
-    return (k < p.D) ? iv * diff * inv_bd : (0.5f - 0.5f * iv * diff * diff) * inv_bd;
+    return (k < p.D) ? w * (iv * diff) * inv_bd : w * (0.5f - 0.5f * iv * diff * diff) * inv_bd;
   }
-  if (k < p.D) return 2.0f * diff * inv_bd;
+  if (k < p.D) return w * (2.0f * diff) * inv_bd;
   const float lv = orow[k], var = expf(lv);
-  return (2.0f * ratio * (var - diff * diff) * var + 0.1f * lv) * inv_bd;
+  return (w * (2.0f * ratio * (var - diff * diff) * var) + 0.1f * lv) * inv_bd;
 }
 
-template <int HID, class P>
-__global__ __launch_bounds__(kThreads, 2) void bwd_chain_kernel(const P p) {
+template <int HID, LossMode M>
+__global__ __launch_bounds__(kThreads, 2) void bwd_chain_kernel(const WithLoss<BwdArgs, M> p) {
   constexpr int BB = 32, NT = HID / 128, KG_H = HID / 8;
   extern __shared__ f32x4 smem[];
   f32x4 *hbuf = smem;                    // d2 tile, T-layout [HID/4][BB]
@@ -399,7 +268,7 @@ __global__ __launch_bounds__(kThreads, 2) void bwd_chain_kernel(const P p) {
       float v = 0.0f;
       const int row = row0 + b;
       if (row < p.B) {
-        v = output_delta(p, e, row, k, ratio, inv_bd);
+        v = output_delta<M>(p, e, row, k, ratio, inv_bd);
         p.d3_out[((size_t)e * p.B + row) * p.OPk + k] = v;
       }
       xf[((k >> 2) * BB + b) * 4 + (k & 3)] = v;
@@ -489,9 +358,9 @@ __global__ __launch_bounds__(kThreads, 2) void bwd_chain_kernel(const P p) {
 //   row tiles) -> stored, and split into the [64][512] two-piece image under a lift known before the product (|d2| <=
 //   1.1 max |W2| OPk max |d3[row]|) -> d1 = (d2 W1^T) * g1 (A fragments a slab ahead through a three-slot ring) -> stored.
 // ------------------------------------------------------------------------------------------------------------
-template <class BA>
+template <LossMode M>
 struct BwdHArgs {
-  BA b;
+  WithLoss<BwdArgs, M> b;
   const f16x8 *w2t, *w1t;          // images [member][n-tile 16][k-slab][piece 2][lane 64] of 8 halves
   size_t w2t_stride, w1t_stride;    // per member, 16-byte units
   const float *stats;               // [E][NSTAT]: the weights' lift of layer l at [4 l], max |W| at [4 l + 3]
@@ -506,9 +375,9 @@ __host__ __device__ constexpr size_t bh_lds_bytes(int s3) {
   return (size_t)2 * kBhRows * kBhD2Str * 2 + (size_t)2 * kBhRows * bh_d3str(s3) * 2 + (size_t)4 * kBhRows * 4;
 }
 
-template <class BA>
-__global__ __launch_bounds__(kBhThreads) void bwd_chain_h_kernel(const BwdHArgs<BA> a) {
-  const BA &p = a.b;
+template <LossMode M>
+__global__ __launch_bounds__(kBhThreads) void bwd_chain_h_kernel(const BwdHArgs<M> a) {
+  const WithLoss<BwdArgs, M> &p = a.b;
   extern __shared__ f32x4 smem[];
   _Float16 *d2img = reinterpret_cast<_Float16 *>(smem);                         // [2 pieces][64][kBhD2Str]
   float *d3f = reinterpret_cast<float *>(smem);                                 // [64][OPk] fp32 (aliases d2img: consumed first)
@@ -535,7 +404,7 @@ __global__ __launch_bounds__(kBhThreads) void bwd_chain_h_kernel(const BwdHArgs<
       float v = 0.0f;
       const int row = row0 + b;
       if (row < p.B) {
-        v = output_delta(p, e, row, k, ratio, inv_bd);
+        v = output_delta<M>(p, e, row, k, ratio, inv_bd);
         p.d3_out[((size_t)e * p.B + row) * p.OPk + k] = v;
       }
       d3f[b * p.OPk + k] = v;
@@ -977,36 +846,12 @@ __global__ __launch_bounds__(kBhThreads) void fwd_train_h_kernel(const FwdHArgs 
     a.opmax[item0 * 8 + tid] = m;
     if (second) a.opmax[(item0 + 1) * 8 + tid] = m;
   }
-  if (a.loss_part) {
-    const int D = a.D;
-    const bool prob = a.O == 2 * D;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int i = tid; i < kBhRows * D; i += kBhThreads) {
-      const int b = i / D, d = i - b * D;
-      const int src = s_rows[b];
-      if (src < 0) continue;
-      float t = a.targets[(size_t)src * D + d];
-      if (a.out_mu) t = (t - a.out_mu[d]) / a.out_sig[d];
-      const float diff = otile[b * kFhOStr + d] - t;
-      const float mse = diff * diff;
-      s0 += (double)mse;
-      if (prob) {
-        const float lv = otile[b * kFhOStr + D + d];
-        const float dv = expf(lv) - mse;
-        s1 += (double)(dv * dv);
-        s2 += (double)(lv * lv);
-      }
-    }
-    __shared__ double s_loss[3][kBhThreads / 64];
-    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
-    if (lane == 0) { s_loss[0][wave] = s0; s_loss[1][wave] = s1; s_loss[2][wave] = s2; }
-    __syncthreads();
-    if (tid < 3) {
-      double tsum = 0.0;
-      for (int w = 0; w < kBhThreads / 64; ++w) tsum += s_loss[tid][w];
-      a.loss_part[item0 * 3 + tid] = tsum;                 // (the backward kernel adds the entries of all 32-row tiles:
-      if (second) a.loss_part[(item0 + 1) * 3 + tid] = 0.0;   //  this item's sums stand in the first of its two)
-    }
+  if (a.loss_part) {     // (the rows are gathered already: s_rows)
+    const TargetView tv{a.targets, nullptr, 0, a.out_mu, a.out_sig, a.D};
+    const double v = tile_loss_stats<kBhRows, kBhThreads, LOSS_PLAIN>(
+        tv, LossExtras<LOSS_PLAIN>{}, a.O == 2 * a.D, wave, [&](int b, int k) { return otile[b * kFhOStr + k]; },
+        [&](int b) { return s_rows[b]; });
+    store_tile_stats(a.loss_part, item0, second, v);
   }
 }
 
@@ -1481,9 +1326,6 @@ struct FusedArgs {
   float *pW[3], *pB[3];                    // partial buffers [workgroup][E][...]
   size_t sW[3], sB[3];                     // floats per partial
 };
-struct FusedXArgs : FusedArgs {
-  ValueExtras x;
-};
 
 // One workgroup per CU (the grid is at most 32 x E workgroups) buys a 512-register budget, and that changes the
 // shape of the kernel: with one 32-column n-tile per wave a k-group is only 4 MFMAs (256 cycles), far too short to
@@ -1515,9 +1357,11 @@ __device__ __forceinline__ void mfma_frags(const f32x4 (&a)[KG], int kg, const f
   }
 }
 
-template <int N_IT, class P>
-__global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const P p) {
-  constexpr bool X = std::is_same<P, FusedXArgs>::value;     // weights / clipping
+template <int N_IT, LossMode M>
+__global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const WithLoss<FusedArgs, M> p) {
+  constexpr bool X = has_value(M);          // weights / clipping
+  const LossExtras<M> &x = p;
+  const TargetView tv{p.targets, p.idx, p.idx_stride, p.out_mu, p.out_sig, p.O};     // (target width = output width)
   constexpr int HID = 128, KGH = HID / 8, RS = HID + 4, RED_LD = BB + 1;
   constexpr int KG0 = 4 * N_IT;             // k-groups of the (padded) input width
   extern __shared__ f32x4 smem4[];
@@ -1572,7 +1416,7 @@ __global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const P p) 
   float on[X ? 4 : 1], wn = 1.0f;           // X: the scaled old predictions beside the targets, the row's weight
   float clip_c = 0.0f;
   if constexpr (X) {
-    if (p.x.old_pred) clip_c = *p.x.clip_c;
+    if (x.old_pred) clip_c = *x.clip_c;
   }
   auto gather = [&](int tile) {
     const int row0 = tile * BB;
@@ -1584,7 +1428,7 @@ __global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const P p) 
         const int b = i / p.IP, k = i - b * p.IP;
         const int r = row0 + b;
         if (r < p.B && k < p.I) {
-          const int src = p.idx ? p.idx[(size_t)e * p.idx_stride + r] : r;
+          const int src = tv.src_row(e, r);
           float v = p.inputs[(size_t)src * p.I + k];
           if (p.in_mu) v = (v - p.in_mu[k]) / p.in_sig[k];
           xn[u] = v;
@@ -1592,22 +1436,18 @@ __global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const P p) 
       }
     }
     const int er = row0 + (tid & 31);
-    const int src = (er < p.B) ? (p.idx ? p.idx[(size_t)e * p.idx_stride + er] : er) : -1;
+    const int src = (er < p.B) ? tv.src_row(e, er) : -1;
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int a = (tid >> 5) + 8 * it;
       tn[it] = 0.0f;
-      if (a < p.O && src >= 0) {
-        float t = p.targets[(size_t)src * p.O + a];
-        if (p.out_mu) t = (t - p.out_mu[a]) / p.out_sig[a];
-        tn[it] = t;
-      }
+      if (a < p.O && src >= 0) tn[it] = tv.scaled(tv.raw(src, a), a);
       if constexpr (X) {
         on[it] = 0.0f;
-        if (a < p.O && src >= 0 && p.x.old_pred) on[it] = scaled_old(p.x, src, p.O, a, p.out_mu, p.out_sig);
+        if (a < p.O && src >= 0 && x.old_pred) on[it] = scaled_old(x, tv, src, a);
       }
     }
-    if constexpr (X) wn = (src >= 0 && p.x.w) ? p.x.w[src] : 1.0f;
+    if constexpr (X) wn = src >= 0 ? loss_weight<M>(x, src, 0, 0.0f) : 1.0f;
   };
   if ((int)blockIdx.x < n_tiles) gather(blockIdx.x);
   __syncthreads();
@@ -1682,7 +1522,7 @@ __global__ __launch_bounds__(kThreads, 1) void fused_mse_step_kernel(const P p) 
           m += red[(3 * 32 + a) * RED_LD + eb];
           m += b2[a];
           float cot = valid ? (m - tc[it]) * inv_bd : 0.0f;
-          if constexpr (X) cot = valid ? value_delta(m, tc[it], p.x.old_pred != nullptr, oc[it], clip_c, wc) * inv_bd : 0.0f;
+          if constexpr (X) cot = valid ? value_delta(m, tc[it], x.old_pred != nullptr, oc[it], clip_c, wc) * inv_bd : 0.0f;
           wR[eb * 36 + a] = cot;
           gb2p[it] += cot;
         }
@@ -2034,10 +1874,10 @@ void fill_wgrad_args(cmbpo_trainer *t, int layer, int batch, WgradArgs &a, int &
   a.max_tiles = cmbpo_ceil_div(batch, 32);
 }
 
-template <int HID, class P>
-int launch_bwd(const P &a, int tiles, int E, size_t lds, hipStream_t s) {
-  if (int rc = cmbpo_grant_lds(bwd_chain_kernel<HID, P>, lds)) return rc;
-  hipLaunchKernelGGL((bwd_chain_kernel<HID, P>), dim3(tiles, E), dim3(kThreads), lds, s, a);
+template <int HID, LossMode M>
+int launch_bwd(const WithLoss<BwdArgs, M> &a, int tiles, int E, size_t lds, hipStream_t s) {
+  if (int rc = cmbpo_grant_lds(bwd_chain_kernel<HID, M>, lds)) return rc;
+  hipLaunchKernelGGL((bwd_chain_kernel<HID, M>), dim3(tiles, E), dim3(kThreads), lds, s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -2081,11 +1921,11 @@ int prepare_f16(cmbpo_trainer *t, hipStream_t s) {
   return CMBPO_OK;
 }
 
-template <class BA>
-int launch_bwd_h(cmbpo_trainer *t, const BA &b, int batch, hipStream_t s) {
+template <LossMode M>
+int launch_bwd_h(cmbpo_trainer *t, const WithLoss<BwdArgs, M> &b, int batch, hipStream_t s) {
   if (int rc = prepare_f16(t, s)) return rc;
   f16x8 *base = reinterpret_cast<f16x8 *>(t->b16);
-  BwdHArgs<BA> a{};
+  BwdHArgs<M> a{};
   a.b = b;
   a.w1t = base; a.w2t = base + t->b16_w2t_off;
   a.w1t_stride = t->b16_w1_units; a.w2t_stride = t->b16_w2t_units;
@@ -2093,8 +1933,8 @@ int launch_bwd_h(cmbpo_trainer *t, const BA &b, int batch, hipStream_t s) {
   a.s3 = t->b16_s3;
   a.tiles32 = cmbpo_ceil_div(batch, 32);
   const size_t lds = bh_lds_bytes(t->b16_s3);
-  if (int rc = cmbpo_grant_lds(bwd_chain_h_kernel<BA>, lds)) return rc;
-  hipLaunchKernelGGL(bwd_chain_h_kernel<BA>, dim3(cmbpo_ceil_div(batch, kBhRows), t->E), dim3(kBhThreads), lds, s, a);
+  if (int rc = cmbpo_grant_lds(bwd_chain_h_kernel<M>, lds)) return rc;
+  hipLaunchKernelGGL(bwd_chain_h_kernel<M>, dim3(cmbpo_ceil_div(batch, kBhRows), t->E), dim3(kBhThreads), lds, s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -2173,12 +2013,11 @@ int launch_update(cmbpo_trainer *t, int apply, float lr_t, hipStream_t s) {
   return CMBPO_OK;
 }
 
-template <class P>
+template <LossMode M>
 int launch_fused(cmbpo_trainer *t, const float *d_inputs, const float *d_targets, const int32_t *d_idx, int idx_stride,
-                 int batch, hipStream_t s, const ValueExtras *x = nullptr) {
+                 int batch, hipStream_t s, const LossExtras<M> &x) {
   cmbpo_mlp *m = t->m;
-  P a{};
-  if constexpr (std::is_same<P, FusedXArgs>::value) a.x = *x;
+  WithLoss<FusedArgs, M> a{{}, x};
   a.F0 = reinterpret_cast<const f32x4 *>(m->pack(0));
   a.F1 = reinterpret_cast<const f32x4 *>(m->pack(1));
   a.F2 = reinterpret_cast<const f32x4 *>(m->pack(2));
@@ -2199,23 +2038,23 @@ int launch_fused(cmbpo_trainer *t, const float *d_inputs, const float *d_targets
   const int G = t->ks[0];
   // every partial slot is written: workgroups beyond the batch's tiles store zeros
   if (t->IP <= 32) {
-    if (int rc = cmbpo_grant_lds(fused_mse_step_kernel<1, P>, 152 * 1024)) return rc;
-    hipLaunchKernelGGL((fused_mse_step_kernel<1, P>), dim3(G, t->E), dim3(kThreads), lds, s, a);
+    if (int rc = cmbpo_grant_lds(fused_mse_step_kernel<1, M>, 152 * 1024)) return rc;
+    hipLaunchKernelGGL((fused_mse_step_kernel<1, M>), dim3(G, t->E), dim3(kThreads), lds, s, a);
   } else {
-    if (int rc = cmbpo_grant_lds(fused_mse_step_kernel<2, P>, 152 * 1024)) return rc;
-    hipLaunchKernelGGL((fused_mse_step_kernel<2, P>), dim3(G, t->E), dim3(kThreads), lds, s, a);
+    if (int rc = cmbpo_grant_lds(fused_mse_step_kernel<2, M>, 152 * 1024)) return rc;
+    hipLaunchKernelGGL((fused_mse_step_kernel<2, M>), dim3(G, t->E), dim3(kThreads), lds, s, a);
   }
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
 
-template <class P>
-int launch_bwd_any(cmbpo_trainer *t, const P &b, int batch, hipStream_t s) {
+template <LossMode M>
+int launch_bwd_any(cmbpo_trainer *t, const WithLoss<BwdArgs, M> &b, int batch, hipStream_t s) {
   const int H = t->H, E = t->E;
   const size_t lds = ((size_t)H / 4 * 32 + (size_t)t->OPk / 4 * 32) * sizeof(f32x4);
   const int tiles = cmbpo_ceil_div(batch, 32);
   if (t->b16) return launch_bwd_h(t, b, batch, s);
-  return (H == 512) ? launch_bwd<512>(b, tiles, E, lds, s) : (H == 256 ? launch_bwd<256>(b, tiles, E, lds, s) : launch_bwd<128>(b, tiles, E, lds, s));
+  return (H == 512) ? launch_bwd<512, M>(b, tiles, E, lds, s) : (H == 256 ? launch_bwd<256, M>(b, tiles, E, lds, s) : launch_bwd<128, M>(b, tiles, E, lds, s));
 }
 
 // the clip range of a step into t->old_var_part's last slot (old_var_part_kernel, old_var_final_kernel)
@@ -2235,27 +2074,47 @@ int launch_old_var(cmbpo_trainer *t, const float *d_targets, const float *d_old_
   return CMBPO_OK;
 }
 
-ColWeights col_weights_of(const cmbpo_trainer *t) {
-  const float *w = t->colw_on ? t->colw : t->ones;
-  return ColWeights{w, w + t->D};
+// The loss mode of the trainer's state; x: the per-call block of a deterministic head (check_extras), which no probabilistic
+// head takes, as no deterministic head takes column weights or kinds.
+LossMode loss_mode(const cmbpo_trainer *t, bool x) {
+  return x ? LOSS_VALUE : t->kind_on ? LOSS_KINDS : t->colw_on ? LOSS_COLW : LOSS_PLAIN;
+}
+
+// f(tag) with the mode as a compile-time constant: constexpr LossMode M = tag()
+template <class F>
+int dispatch(LossMode m, F f) {
+  switch (m) {
+    case LOSS_VALUE: return f(std::integral_constant<LossMode, LOSS_VALUE>{});
+    case LOSS_COLW: return f(std::integral_constant<LossMode, LOSS_COLW>{});
+    case LOSS_KINDS: return f(std::integral_constant<LossMode, LOSS_KINDS>{});
+    default: return f(std::integral_constant<LossMode, LOSS_PLAIN>{});
+  }
+}
+
+// the extras of mode M: column weights from the trainer (all ones from its pool when kinds are on without weights)
+template <LossMode M>
+LossExtras<M> loss_extras_of(const cmbpo_trainer *t, const ValueExtras *x) {
+  LossExtras<M> ex{};
+  if constexpr (has_value(M)) static_cast<ValueExtras &>(ex) = *x;
+  if constexpr (has_colw(M)) {
+    ex.col = t->colw_on ? t->colw : t->ones;
+    ex.pos = ex.col + t->D;
+  }
+  if constexpr (has_kinds(M)) ex.kind = t->kind;
+  return ex;
 }
 
 // the weighted loss statistics of an 'MSPE' step over the forward's (col_stats_kernel), in the layout of the forward that ran
-int launch_col_stats(cmbpo_trainer *t, const float *d_targets, const int32_t *d_idx, int idx_stride, int batch, hipStream_t s) {
-  ColStatsLArgs a{};
+template <LossMode M>
+int launch_col_stats(cmbpo_trainer *t, const float *d_targets, const int32_t *d_idx, int idx_stride, int batch, hipStream_t s,
+                     const LossExtras<M> &x) {
+  WithLoss<ColStatsArgs, M> a{{}, x};
   a.o = t->o; a.targets = d_targets; a.idx = d_idx; a.idx_stride = idx_stride;
   a.out_mu = t->m->out_mu(); a.out_sig = t->m->out_sig();
   a.B = batch; a.O = t->O; a.D = t->D; a.tiles32 = cmbpo_ceil_div(batch, 32);
-  a.c = col_weights_of(t);
   a.loss_part = t->loss_part;
-  const ColStatsArgs &c = a;
-  const bool rows64 = t->b16 && t->b16_fwd;
-  if (t->kind_on) {
-    a.kind = t->kind;
-    if (rows64) hipLaunchKernelGGL(col_stats_l_kernel<64>, dim3(cmbpo_ceil_div(batch, 64), t->E), dim3(512), 0, s, a);
-    else hipLaunchKernelGGL(col_stats_l_kernel<32>, dim3(a.tiles32, t->E), dim3(256), 0, s, a);
-  } else if (rows64) hipLaunchKernelGGL(col_stats_kernel<64>, dim3(cmbpo_ceil_div(batch, 64), t->E), dim3(512), 0, s, c);
-  else hipLaunchKernelGGL(col_stats_kernel<32>, dim3(a.tiles32, t->E), dim3(256), 0, s, c);
+  if (t->b16 && t->b16_fwd) hipLaunchKernelGGL((col_stats_kernel<64, M>), dim3(cmbpo_ceil_div(batch, 64), t->E), dim3(512), 0, s, a);
+  else hipLaunchKernelGGL((col_stats_kernel<32, M>), dim3(a.tiles32, t->E), dim3(256), 0, s, a);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
@@ -2603,9 +2462,15 @@ int trainer_step(const char *who, cmbpo_trainer_t *t, const float *d_inputs, int
     rc = launch_old_var(t, d_targets, x->old_pred, d_idx, idx_stride, batch, kl, s);
     if (rc != CMBPO_OK) return rc;
   }
-  if (t->fused) {
-    rc = x ? launch_fused<FusedXArgs>(t, d_inputs, d_targets, d_idx, idx_stride, batch, s, x)
-           : launch_fused<FusedArgs>(t, d_inputs, d_targets, d_idx, idx_stride, batch, s);
+  const LossMode mode = loss_mode(t, x != nullptr);
+  if (t->fused) {       // (deterministic: plain or LOSS_VALUE)
+    rc = dispatch(mode, [&](auto tag) {
+      constexpr LossMode M = tag();
+      if constexpr (has_colw(M)) {
+        cmbpo_set_error("%s: column weights on a deterministic head", who);     // (the setters refuse them)
+        return (int)CMBPO_ESTATE;
+      } else return launch_fused<M>(t, d_inputs, d_targets, d_idx, idx_stride, batch, s, loss_extras_of<M>(t, x));
+    });
     if (rc != CMBPO_OK) return rc;
     t->step += 1;
     return launch_update(t, 1, adam_rate(t), s);
@@ -2615,7 +2480,7 @@ int trainer_step(const char *who, cmbpo_trainer_t *t, const float *d_inputs, int
   rc = run_forward(t, d_inputs, d_idx, idx_stride, batch, true, s, d_targets);
   if (rc != CMBPO_OK) return rc;
 
-  BwdXArgs b{};
+  BwdArgs b{};
   b.wpb2 = reinterpret_cast<const f32x4 *>(t->wpb2); b.wpb1 = reinterpret_cast<const f32x4 *>(t->wpb1);
   b.wpb2_stride = t->wpb2_floats / 4; b.wpb1_stride = t->wpb1_floats / 4;
   b.g2 = t->g2; b.g1 = t->g1; b.d2 = t->d2; b.d1 = t->d1;
@@ -2625,31 +2490,15 @@ int trainer_step(const char *who, cmbpo_trainer_t *t, const float *d_inputs, int
   b.out_mu = t->m->out_mu(); b.out_sig = t->m->out_sig();
   b.loss_part = t->loss_part; b.d3_out = t->d3;
   b.opmax = t->opmax;
-  if (x) {
-    b.x = *x;
-    rc = launch_bwd_any<BwdXArgs>(t, b, batch, s);
-  } else if (t->kind_on) {
-    if (b.prob == 1) {
-      rc = launch_col_stats(t, d_targets, d_idx, idx_stride, batch, s);
-      if (rc != CMBPO_OK) return rc;
+  rc = dispatch(mode, [&](auto tag) {
+    constexpr LossMode M = tag();
+    const LossExtras<M> ex = loss_extras_of<M>(t, x);
+    if constexpr (has_colw(M)) {      // 'MSPE': the ratio's sums are weighted sums
+      if (b.prob == 1)
+        if (int rc2 = launch_col_stats<M>(t, d_targets, d_idx, idx_stride, batch, s, ex)) return rc2;
     }
-    BwdLArgs l{};
-    static_cast<BwdArgs &>(l) = b;
-    l.c = col_weights_of(t);
-    l.kind = t->kind;
-    rc = launch_bwd_any<BwdLArgs>(t, l, batch, s);
-  } else if (t->colw_on) {
-    if (b.prob == 1) {
-      rc = launch_col_stats(t, d_targets, d_idx, idx_stride, batch, s);
-      if (rc != CMBPO_OK) return rc;
-    }
-    BwdCArgs c{};
-    static_cast<BwdArgs &>(c) = b;
-    c.c = col_weights_of(t);
-    rc = launch_bwd_any<BwdCArgs>(t, c, batch, s);
-  } else {
-    rc = launch_bwd_any<BwdArgs>(t, b, batch, s);
-  }
+    return launch_bwd_any<M>(t, WithLoss<BwdArgs, M>{b, ex}, batch, s);
+  });
   if (rc != CMBPO_OK) return rc;
 
   if (t->H == 512) {
@@ -2699,27 +2548,18 @@ int trainer_losses(const char *who, cmbpo_trainer_t *t, const float *d_inputs, i
     const int32_t *idx = d_idx ? d_idx + r0 : nullptr;
     int rc = run_forward(t, d_inputs, idx, idx_stride, rows, false, s);
     if (rc != CMBPO_OK) return rc;
-    LossWArgs l{};   // (only the squared error of the mean head is needed)
+    LossArgs l{};    // (only the squared error of the mean head is needed)
     l.o = t->o; l.targets = d_targets; l.idx = idx; l.idx_stride = idx_stride;
     l.out_mu = t->m->out_mu(); l.out_sig = t->m->out_sig();
     l.E = E; l.B = rows; l.O = t->O; l.D = t->D;
     l.sums = t->sums;
-    l.w = d_weights;
     const int gx = min(cmbpo_ceil_div(rows * t->D, kThreads), 64);
-    if (d_weights) {
-      hipLaunchKernelGGL(loss_sums_kernel<LossWArgs>, dim3(gx, E), dim3(kThreads), 0, s, l);
-    } else if (t->kind_on) {
-      LossLArgs ll{};
-      static_cast<LossArgs &>(ll) = l;
-      ll.c = col_weights_of(t);
-      ll.kind = t->kind;
-      hipLaunchKernelGGL(loss_sums_kernel<LossLArgs>, dim3(gx, E), dim3(kThreads), 0, s, ll);
-    } else if (t->colw_on) {
-      LossCArgs lc{};
-      static_cast<LossArgs &>(lc) = l;
-      lc.c = col_weights_of(t);
-      hipLaunchKernelGGL(loss_sums_kernel<LossCArgs>, dim3(gx, E), dim3(kThreads), 0, s, lc);
-    } else hipLaunchKernelGGL(loss_sums_kernel<LossArgs>, dim3(gx, E), dim3(kThreads), 0, s, static_cast<const LossArgs &>(l));
+    dispatch(loss_mode(t, d_weights != nullptr), [&](auto tag) {
+      constexpr LossMode M = tag();
+      const ValueExtras xw{d_weights, nullptr, nullptr};
+      hipLaunchKernelGGL(loss_sums_kernel<M>, dim3(gx, E), dim3(kThreads), 0, s, WithLoss<LossArgs, M>{l, loss_extras_of<M>(t, &xw)});
+      return CMBPO_OK;
+    });
   }
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, s, t->sums, E, 1.0 / ((double)n_rows * t->D), d_losses);
   CMBPO_HIP_CHECK(hipGetLastError());

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Registers, scratch and LDS of every pi_kernel* instantiation, as the compiler reports them
+"""Registers, scratch and LDS of every pi_kernel* instantiation (or, with --file / --kernels, of the kernels of another
+source file whose demangled name matches a regular expression), as the compiler reports them
 (-Rpass-analysis=kernel-resource-usage, the build's flags, no GPU needed), for several trees side by side.
 
     python tools/pi_kernel_resources.py --tree parent=/path/to/parent/checkout --tree tree=. \
@@ -8,6 +9,8 @@
 A tree is `label=checkout[:extra flag]`.  One row per (instantiation, tree); the last template argument says whether the
 instantiation takes sample weights (a tree from before the weights has only `false` rows).  Every row of the first tree must
 be found unchanged in the others: the tool lists the ones that are not and exits 1.
+
+    python tools/pi_kernel_resources.py --file ens_train.hip --kernels . --tree parent=... --tree tree=. --out ...
 """
 import argparse
 import os
@@ -25,9 +28,9 @@ FIELDS = (("TotalSGPRs", "sgprs"), ("VGPRs", "vgprs"), ("AGPRs", "agprs"), ("Scr
           ("LDS Size [bytes/block]", "static_lds_bytes"))
 
 
-def remarks(checkout, extra):
-    cmd = [G.HIPCC] + G.HIP_FLAGS + extra + ["-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c",
-                                              "policy_update.hip", "-o", os.devnull]
+def remarks(checkout, extra, src):
+    cmd = [G.HIPCC] + G.HIP_FLAGS + G.FILE_FLAGS.get(src, []) + extra + ["-Rpass-analysis=kernel-resource-usage",
+                                                                       "--cuda-device-only", "-c", src, "-o", os.devnull]
     return subprocess.run(cmd, cwd=os.path.join(checkout, CSRC), check=True, capture_output=True, text=True).stderr
 
 
@@ -36,11 +39,11 @@ def demangle(names):
     clean = []
     for d in out[:len(names)]:
         d = d.replace("(anonymous namespace)::", "").replace("void ", "")
-        clean.append(re.sub(r"\(.*$", "", d))
+        clean.append(re.sub(r"\((?!\w+\)\d).*$", "", d))      # the parameter list goes, an enum template argument `(LossMode)2` stays
     return clean
 
 
-def parse(text):
+def parse(text, kernels):
     rows, cur = {}, None
     for line in text.splitlines():
         m = re.search(r"remark: Function Name: (\S+)", line)
@@ -54,8 +57,8 @@ def parse(text):
     names = list(rows)
     out = {}
     for n, d in zip(names, demangle(names)):
-        if d.startswith("pi_kernel"):
-            if d.count(",") == 2:      # a tree from before the weights: its instantiations are the unweighted ones
+        if kernels.search(d):
+            if d.startswith("pi_kernel") and d.count(",") == 2:      # a tree from before the weights: its instantiations are the unweighted ones
                 d = d[:-1] + ", false>"
             out[d] = rows[n]
     return out
@@ -65,12 +68,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tree", action="append", required=True, help="label=checkout[:extra compiler flag]")
     ap.add_argument("--out", required=True)
+    ap.add_argument("--file", default="policy_update.hip", help="source file under csrc/")
+    ap.add_argument("--kernels", default="^pi_kernel", help="regular expression searched in the demangled kernel names")
     a = ap.parse_args()
     tables = []
     for spec in a.tree:
         label, rest = spec.split("=", 1)
         checkout, _, flag = rest.partition(":")
-        tables.append((label, parse(remarks(os.path.abspath(checkout), [flag] if flag else []))))
+        tables.append((label, parse(remarks(os.path.abspath(checkout), [flag] if flag else [], a.file), re.compile(a.kernels))))
     cols = [c for _, c in FIELDS]
     with open(a.out, "w") as f:
         f.write("\t".join(["kernel", "tree"] + cols) + "\n")

@@ -7,6 +7,8 @@
                      here -- a step without kinds must not pay for them; the yardstick is the other library's own
                      (max - min) / median.  Both start from the same weights and see the same batches: their weights afterwards
                      are compared bit for bit.
+                 (c) with --other-lib too: the logistic step there (other_kinds) against the logistic step here, judged and
+                     compared bit for bit in the same way.
   --fixed-point  tests/test_logistic_head_gpu.py's fixed point for seeds 0 / 1 / 2 and both losses: the excess of every member's
                  held-out Bernoulli NLL over the Bayes value, mean sigma(z) against the positive rate, and the share of the
                  Gaussian head's predictions outside [0, 1].
@@ -119,7 +121,7 @@ if args.step:
             return run
         fns = {"here_plain": make("here", False), "here_logistic": make("here", True), "here_plain_again": make("here", False)}
         if args.other_lib:
-            fns = {"other_plain": make("other", False), **fns}
+            fns = {"other_plain": make("other", False), "other_kinds": make("other", True), **fns}
         us = alternate(fns, args.rounds)
         k = dict(us_per_step=us, logistic_over_plain=statistics.median(us["here_logistic"]) / statistics.median(us["here_plain"]),
                  here_spread=spread(us["here_plain"]),
@@ -138,6 +140,18 @@ if args.step:
                      median_ratio_here_over_other=ratio, within_other_spread=bool(abs(ratio - 1.0) <= sp))
             print("%s (b) plain step here / other: %.4f (other's own spread %.4f) -> %s; weights bit-identical: %s"
                   % (loss, ratio, sp, "within" if k["within_other_spread"] else "OUTSIDE", same))
+            # (c) the same for the logistic step of the two libraries
+            with library(here):
+                mine = made[("here", True)].get_weights()
+            with library(libs["other"]):
+                theirs = made[("other", True)].get_weights()
+            same = all(np.array_equal(a, b) for a, b in zip(mine[0] + mine[1], theirs[0] + theirs[1]))
+            sp = spread(us["other_kinds"])
+            ratio = statistics.median(us["here_logistic"]) / statistics.median(us["other_kinds"])
+            k["other_kinds"] = dict(weights_bit_identical_to_other_lib_after_all_rounds=bool(same), other_spread=sp,
+                                  median_ratio_here_over_other=ratio, within_other_spread=bool(abs(ratio - 1.0) <= sp))
+            print("%s (c) logistic step here / other: %.4f (other's own spread %.4f) -> %s; weights bit-identical: %s"
+                  % (loss, ratio, sp, "within" if k["other_kinds"]["within_other_spread"] else "OUTSIDE", same))
         print("%s     a second set of plain trainers of this tree / the first: %.4f" % (loss, k["second_set_over_first_same_code"]))
         print("%s (a) logistic step / plain step, here: %.4f (%.1f us / %.1f us)"
               % (loss, k["logistic_over_plain"], statistics.median(us["here_logistic"]), statistics.median(us["here_plain"])))
