@@ -233,6 +233,13 @@ SIGNATURES.update({
     "cmbpo_rollout_cost_head_detach": (_i, [_rp]),
 })
 
+# sampled terminations: a threshold per row in place of the head's scalar (thresholds: utils.term_thresholds)
+SIGNATURES.update({
+    "cmbpo_fakeenv_post_term_draws": (_i, [_i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i,
+                                           _p, _p, _p, _p, _p, _p, _p, _p, C.c_float, C.c_float, _p, _p, _tp, _chp, _p, _p]),
+    "cmbpo_rollout_term_draws_attach": (_i, [_rp, _p, C.c_long]),
+})
+
 
 class PiBatchStruct(C.Structure):
     """ctypes image of ``cmbpo_pi_batch_t``."""

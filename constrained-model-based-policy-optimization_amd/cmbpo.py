@@ -73,6 +73,16 @@ log-likelihood on its output read as a logit (``PE.set_logistic_columns([-1])``)
 above go on applying, as weights on the Bernoulli term.  ``save`` / ``load`` keep the choice in ``term_loss_<epoch>.json`` (a
 missing file means 'gaussian').
 
+``m_term_sampling=True`` (needs ``m_learn_term`` and ``use_model``) reads the termination column as a hazard, not
+as a classifier: an imagined branch whose column says p ends with probability p (``ModelSampler(term_sampling=True)``: one
+uniform draw per branch and step, from a generator of the sampler's own, compared in the post kernel as a per-row threshold),
+so with a calibrated head imagined branches end at the rate real episodes do, without a threshold to tune.
+``m_term_threshold`` and ``m_term_members`` stay in force for the validation replay, which keeps the threshold rule
+(``term_cm`` goes on describing the classifier); ``m_term_members`` also stays the vote of the sampled rule.  Recommended with
+``m_term_loss='logistic'`` and ``m_term_pos_weight=1.0``: a class-weighted level is not a probability
+(``utils.pos_weight_level``), and a least-squares column is one only inside [0, 1].  ``save`` / ``load`` keep the flag in
+``term_sampling_<epoch>.json`` beside the head's threshold and vote (a missing file or key means off).
+
 ``m_cost_loss='logistic'`` (needs ``m_learn_cost``) does the same for the cost column, ``obs_dim + 1``: it is trained
 with the Bernoulli likelihood (targets above 0.5 count as 1) and ``FakeEnv(cost_loss='logistic')`` reads it as a logit, so every
 imagined cost is a probability in [0, 1].  A task whose cost is a magnitude, not an indicator, should keep 'gaussian'.
@@ -153,6 +163,14 @@ def _calibration_args(validate_horizon, use_model, stochastic, validate_calibrat
     if not (0.0 < lo <= hi and np.isfinite(hi)):
         raise ValueError("m_noise_temperature_range: 0 < lo <= hi < inf expected, got %r" % (temperature_range,))
     return validate_calibration, calibrated_noise, (lo, hi)
+
+
+def _term_sampling_args(learn_term, term_sampling):
+    """``m_term_sampling`` checked against ``m_learn_term`` (and ``use_model``), or a ValueError in words."""
+    if term_sampling and not learn_term:
+        raise ValueError("m_term_sampling=True needs m_learn_term=True (and use_model): it samples the imagined terminations "
+                         "from the model's termination column, and there is none")
+    return bool(term_sampling)
 
 
 def _term_loss_args(learn_term, term_loss, term_threshold):
@@ -264,12 +282,14 @@ class CMBPO:
                  m_learn_term=False, m_term_threshold=0.5, m_term_members='elite',
                  m_term_pos_weight=1.0, m_term_loss_weight=1.0, m_cost_loss_weight=1.0, m_pos_weight_max=20.0,
                  m_term_loss='gaussian', m_cost_loss='gaussian', m_cost_pos_weight=1.0, m_cost_pos_weight_undo=False,
-                 **_unused):
+                 m_term_sampling=False, **_unused):
         # column / class weights of the model's binary columns; refused in words before anything is built
         self._column_weights = _column_weight_args(bool(m_learn_term) and bool(use_model), bool(m_learn_cost), m_term_pos_weight,
                                                    m_term_loss_weight, m_cost_loss_weight, m_pos_weight_max)
         # the likelihood of the termination column; likewise
         self._m_term_loss = _term_loss_args(bool(m_learn_term) and bool(use_model), m_term_loss, m_term_threshold)
+        # sampled terminations; likewise
+        self._m_term_sampling = _term_sampling_args(bool(m_learn_term) and bool(use_model), m_term_sampling)
         # the likelihood and the class weight of the cost column; likewise
         self._m_cost_loss, self._cost_pos_weight, self._cost_pos_weight_undo = _cost_loss_args(
             bool(m_learn_cost) and bool(use_model), m_cost_loss, m_cost_pos_weight, m_cost_pos_weight_undo, m_pos_weight_max)
@@ -382,7 +402,8 @@ class CMBPO:
                 self.model_buf.set_value_disagreement(True, kv, kvc)
             self.model_sampler = ModelSampler(max_path_length=maxroll, batch_size=self._rollout_batch_size,
                                               logger=None, rollout_mode=self.rollout_mode,
-                                              stochastic=bool(m_stochastic))
+                                              stochastic=bool(m_stochastic),
+                                              **({'term_sampling': True} if self._m_term_sampling else {}))
         # open-loop validation of the model on each epoch's real samples (0: off -- no call, no key, no random number)
         self._validate_horizon, self._validate_windows = int(m_validate_horizon), int(m_validate_windows)
         if self._validate_horizon < 0 or (self._validate_horizon > 0 and self._validate_windows < 1):
@@ -711,6 +732,9 @@ class CMBPO:
                 # the column's likelihood, a file of its own: term_head_<epoch>.json keeps exactly its keys
                 with open(os.path.join(savedir, 'term_loss_%d.json' % self._epoch), 'w') as fh:
                     json.dump({'m_term_loss': self._m_term_loss}, fh)
+                # sampled terminations, likewise
+                with open(os.path.join(savedir, 'term_sampling_%d.json' % self._epoch), 'w') as fh:
+                    json.dump({'m_term_sampling': bool(getattr(self, '_m_term_sampling', False))}, fh)
             if self._m_learn_cost:      # the reading of the cost column, a file of its own
                 import json
                 import os
@@ -776,6 +800,24 @@ class CMBPO:
         self._model.set_logistic_columns(self._logistic_columns())
         return term_loss
 
+    def _load_term_sampling(self, savedir, timestep):
+        """The flag of the sampled terminations that ``save`` wrote (a checkpoint from before it has no such file, or no such
+        key: off), handed to the model sampler."""
+        import json
+        import os
+        if not self._m_learn_term:
+            return
+        path = os.path.join(savedir, 'term_sampling_%d.json' % int(timestep))
+        on = False
+        if os.path.exists(path):
+            with open(path) as fh:
+                on = bool(json.load(fh).get('m_term_sampling', False))
+        self._m_term_sampling = on
+        sampler = getattr(self, 'model_sampler', None)
+        if sampler is not None and sampler.term_sampling != on:
+            sampler.term_sampling = on
+            sampler._draws = None       # (the next step draws a chunk with / without the thresholds)
+
     def load(self, savedir, timestep):
         """The model ``save`` wrote at epoch ``timestep`` and, with the termination head, its threshold and vote."""
         if not self._use_model:
@@ -794,3 +836,4 @@ class CMBPO:
             with open(os.path.join(savedir, 'term_head_%d.json' % int(timestep))) as fh:
                 head = json.load(fh)
             self.fake_env.set_term_head(head['threshold'], head['members'], loss=term_loss)
+            self._load_term_sampling(savedir, timestep)

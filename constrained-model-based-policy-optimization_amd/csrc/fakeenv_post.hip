@@ -82,18 +82,25 @@ struct PostArgsTerm : PostArgsT<RULES, NOISE, DIS> {
   float *term_pred;               // [.] slot indexed like term, or NULL
   uint8_t *term_votes;            // [.] or NULL
 };
-template <int RULES, bool NOISE, bool DIS = false, bool TERM = false>
-using PostArgsX = std::conditional_t<TERM, PostArgsTerm<RULES, NOISE, DIS>, PostArgsT<RULES, NOISE, DIS>>;
+// DRAW: sampled terminations (include/cmbpo_hip.h, cmbpo_fakeenv_post_term_draws) -- a threshold per row in place of the head's one
+// scalar; it exists only together with TERM, and its pointer only in the argument types of instances of their own
+template <int RULES, bool NOISE, bool DIS>
+struct PostArgsDraw : PostArgsTerm<RULES, NOISE, DIS> {
+  const float *term_thr;          // [.] slot indexed like term, the column's own units; any value (a NaN never hits)
+};
+template <int RULES, bool NOISE, bool DIS = false, bool TERM = false, bool DRAW = false>
+using PostArgsX = std::conditional_t<DRAW, PostArgsDraw<RULES, NOISE, DIS>,
+                                     std::conditional_t<TERM, PostArgsTerm<RULES, NOISE, DIS>, PostArgsT<RULES, NOISE, DIS>>>;
 // COST: the logistic learned-cost head (include/cmbpo_hip.h, cmbpo_cost_head_t, kind 1) -- column obs_dim + 1 is a logit and the
 // cost its probability; the same pattern: fields of an argument type of their own, selecting instances of their own.  They are
 // launched with CMBPO_TASK_LEARNED_COST only (checked on the host), so `learned_cost` is not read in their COST parts.
-template <int RULES, bool NOISE, bool DIS, bool TERM>
-struct PostArgsCost : PostArgsX<RULES, NOISE, DIS, TERM> {
+template <int RULES, bool NOISE, bool DIS, bool TERM, bool DRAW = false>
+struct PostArgsCost : PostArgsX<RULES, NOISE, DIS, TERM, DRAW> {
   float logit_shift;              // finite; 0: the logit goes into sigma32 bit for bit
   float *cost_logit;              // [.] slot indexed like cost: the elite's raw logit, or NULL
 };
-template <int RULES, bool NOISE, bool DIS = false, bool TERM = false, bool COST = false>
-using PostArgsY = std::conditional_t<COST, PostArgsCost<RULES, NOISE, DIS, TERM>, PostArgsX<RULES, NOISE, DIS, TERM>>;
+template <int RULES, bool NOISE, bool DIS = false, bool TERM = false, bool COST = false, bool DRAW = false>
+using PostArgsY = std::conditional_t<COST, PostArgsCost<RULES, NOISE, DIS, TERM, DRAW>, PostArgsX<RULES, NOISE, DIS, TERM, DRAW>>;
 
 // np.clip(x, lo, hi): comparisons are false for a NaN, which therefore passes through (fminf / fmaxf would drop it)
 __device__ __forceinline__ float clip_np(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
@@ -114,8 +121,9 @@ __device__ __forceinline__ float cost_prob(float z, float logit_shift) {
 // EC: the ensemble size at compile time (0: read it at run time) -- with a run-time size the member loops are unrolled to
 // kEMax and masked: 56 pair terms computed and selected for the 42 that exist, a third more instructions
 #define POST_WAVES 5      // waves per SIMD the register allocation aims at (swept 4 / 5 / 6 / 8: 57.7 / 51.1 / 51.3 / 77.4 us at 100 k rows)
-template <int EC, int RULES = 0, bool NOISE = false, bool DIS = false, bool TERM = false, bool COST = false>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgsY<RULES, NOISE, DIS, TERM, COST> p) {
+template <int EC, int RULES = 0, bool NOISE = false, bool DIS = false, bool TERM = false, bool COST = false, bool DRAW = false>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_WAVES, POST_WAVES))) void fakeenv_post_kernel(const PostArgsY<RULES, NOISE, DIS, TERM, COST, DRAW> p) {
+  static_assert(TERM || !DRAW, "DRAW exists only together with TERM");
   extern __shared__ float sm[];
   const int D = p.obs_dim;
   float *s_dkl = sm;                  // [kRows][D]
@@ -320,6 +328,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
         if (k < E) xt = p.mean[k * mstride + (size_t)r * p.out_dim + (p.out_dim - 1)];
       }
     }
+    // DRAW: the row's own threshold, one address for the row's eight lanes (one request, broadcast), requested with the column
+    [[maybe_unused]] float thr_r = 0.0f;
+    if constexpr (DRAW) {
+      if (r >= 0) thr_r = p.term_thr[r];
+    }
     // RULES == 2: lane k of the row owns derived quantity k.  Its table entry is picked out of the (uniform, scalar-loaded) table
     // by a chain of selects -- indexing the argument block by the lane would put it into scratch or behind a memory round trip of
     // its own -- and its operands are requested here, like the DIS / TERM loads ahead of the row sums: next_obs from the s_next
@@ -440,12 +453,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
         cost_var = member_var(xc, &cost_me);
       } else if (p.learned_cost) cost_var = member_var(xc, &cost_me);     // (uniform over the launch; a static cost rule has no spread: +0)
     }
-    // TERM: hit_e = x_e > threshold, written positively (a NaN never hits); one ballot gives the row's member mask in the row's
+    // TERM: hit_e = x_e > threshold (DRAW: the header's rule, the row's own threshold), written positively (a NaN never hits); one ballot gives the row's member mask in the row's
     // byte -- the elite's bit is me & 7, the votes are a popcount.  All 64 lanes are still here.  The elite's own value goes out
     // from the lane that loaded it.
     [[maybe_unused]] unsigned term_mask = 0u;
     if constexpr (TERM) {
-      const bool hit = r >= 0 && k < E && xt > p.threshold;
+      bool hit;
+      if constexpr (DRAW) hit = r >= 0 && k < E && xt > thr_r;
+      else hit = r >= 0 && k < E && xt > p.threshold;
       term_mask = (unsigned)(__ballot(hit) >> (8 * rw)) & 0xffu;
       if (p.term_pred != nullptr && r >= 0 && k == (me_t & 7)) p.term_pred[r] = xt;
     }
@@ -518,43 +533,48 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(POST_W
   }
 }
 
-// one launch of the instance for (ensemble size, RULES, NOISE, DIS, TERM, COST)
-template <int RULES, bool NOISE, bool DIS = false, bool TERM = false, bool COST = false>
-void launch_post(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsY<RULES, NOISE, DIS, TERM, COST> &a) {
-  if (ensemble == 7) hipLaunchKernelGGL((fakeenv_post_kernel<7, RULES, NOISE, DIS, TERM, COST>), grid, dim3(kThreads), lds, stream, a);   // the shipped configs
-  else if (ensemble == 5) hipLaunchKernelGGL((fakeenv_post_kernel<5, RULES, NOISE, DIS, TERM, COST>), grid, dim3(kThreads), lds, stream, a);
-  else hipLaunchKernelGGL((fakeenv_post_kernel<0, RULES, NOISE, DIS, TERM, COST>), grid, dim3(kThreads), lds, stream, a);
+// one launch of the instance for (ensemble size, RULES, NOISE, DIS, TERM, COST, DRAW)
+template <int RULES, bool NOISE, bool DIS = false, bool TERM = false, bool COST = false, bool DRAW = false>
+void launch_post(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsY<RULES, NOISE, DIS, TERM, COST, DRAW> &a) {
+  if (ensemble == 7) hipLaunchKernelGGL((fakeenv_post_kernel<7, RULES, NOISE, DIS, TERM, COST, DRAW>), grid, dim3(kThreads), lds, stream, a);   // the shipped configs
+  else if (ensemble == 5) hipLaunchKernelGGL((fakeenv_post_kernel<5, RULES, NOISE, DIS, TERM, COST, DRAW>), grid, dim3(kThreads), lds, stream, a);
+  else hipLaunchKernelGGL((fakeenv_post_kernel<0, RULES, NOISE, DIS, TERM, COST, DRAW>), grid, dim3(kThreads), lds, stream, a);
 }
 // ... and the logistic cost head (ch == NULL: the instances without it, with the argument block they always had)
-template <int RULES, bool NOISE, bool DIS, bool TERM>
-void launch_post_cost(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsX<RULES, NOISE, DIS, TERM> &a,
+template <int RULES, bool NOISE, bool DIS, bool TERM, bool DRAW = false>
+void launch_post_cost(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsX<RULES, NOISE, DIS, TERM, DRAW> &a,
                       const cmbpo_cost_head_t *ch) {
-  if (ch == nullptr) return launch_post<RULES, NOISE, DIS, TERM>(ensemble, grid, lds, stream, a);
-  PostArgsCost<RULES, NOISE, DIS, TERM> ac{};
-  static_cast<PostArgsX<RULES, NOISE, DIS, TERM> &>(ac) = a;
+  if (ch == nullptr) return launch_post<RULES, NOISE, DIS, TERM, false, DRAW>(ensemble, grid, lds, stream, a);
+  PostArgsCost<RULES, NOISE, DIS, TERM, DRAW> ac{};
+  static_cast<PostArgsX<RULES, NOISE, DIS, TERM, DRAW> &>(ac) = a;
   ac.logit_shift = ch->logit_shift; ac.cost_logit = ch->cost_logit;
-  launch_post<RULES, NOISE, DIS, TERM, true>(ensemble, grid, lds, stream, ac);
+  launch_post<RULES, NOISE, DIS, TERM, true, DRAW>(ensemble, grid, lds, stream, ac);
 }
 
 // DisExtra (fakeenv_post_internal.h): what the disagreement adds to the arguments (NULL: the instances without the feature)
 // ... and cmbpo_fakeenv_post_term (th == NULL: the instances without the head, with the argument block they always had)
+// ... and cmbpo_fakeenv_post_term_draws (thr == NULL: the TERM instances without the draws, likewise)
 template <int RULES, bool NOISE, bool DIS>
 void launch_post_term(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsT<RULES, NOISE, DIS> &a,
-                      const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch) {
+                      const cmbpo_term_head_t *th, const float *thr, const cmbpo_cost_head_t *ch) {
   if (th == nullptr) return launch_post_cost<RULES, NOISE, DIS, false>(ensemble, grid, lds, stream, a, ch);
   PostArgsTerm<RULES, NOISE, DIS> at{};
   static_cast<PostArgsT<RULES, NOISE, DIS> &>(at) = a;
   at.threshold = th->threshold; at.members = th->members; at.term_pred = th->term_pred; at.term_votes = th->term_votes;
-  launch_post_cost<RULES, NOISE, DIS, true>(ensemble, grid, lds, stream, at, ch);
+  if (thr == nullptr) return launch_post_cost<RULES, NOISE, DIS, true>(ensemble, grid, lds, stream, at, ch);
+  PostArgsDraw<RULES, NOISE, DIS> aw{};
+  static_cast<PostArgsTerm<RULES, NOISE, DIS> &>(aw) = at;
+  aw.term_thr = thr;
+  launch_post_cost<RULES, NOISE, DIS, true, true>(ensemble, grid, lds, stream, aw, ch);
 }
 template <int RULES, bool NOISE>
 void launch_post_ext(int ensemble, dim3 grid, size_t lds, hipStream_t stream, const PostArgsBase<RULES, NOISE> &a, const DisExtra *dis,
-                     const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch) {
-  if (dis == nullptr) return launch_post_term<RULES, NOISE, false>(ensemble, grid, lds, stream, a, th, ch);
+                     const cmbpo_term_head_t *th, const float *thr, const cmbpo_cost_head_t *ch) {
+  if (dis == nullptr) return launch_post_term<RULES, NOISE, false>(ensemble, grid, lds, stream, a, th, thr, ch);
   PostArgsDis<RULES, NOISE> ad{};
   static_cast<PostArgsBase<RULES, NOISE> &>(ad) = a;
   ad.kappa_rew = dis->kappa_rew; ad.kappa_cost = dis->kappa_cost; ad.rew_var = dis->rew_var; ad.cost_var = dis->cost_var;
-  launch_post_term<RULES, NOISE, true>(ensemble, grid, lds, stream, ad, th, ch);
+  launch_post_term<RULES, NOISE, true>(ensemble, grid, lds, stream, ad, th, thr, ch);
 }
 
 }  // namespace
@@ -565,7 +585,7 @@ int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream) {
   // the naming rule (fakeenv_post_internal.h, DESIGN): the narrowest entry point that can express the call
   // (kind 0 is the magnitude reading: the instances without the head; `ch` below is the LOGISTIC head or NULL)
   const cmbpo_cost_head_t *ch = (c.ch != nullptr && c.ch->kind == 1) ? c.ch : nullptr;
-  const char *who = c.ch ? "cmbpo_fakeenv_post_cost" : th ? "cmbpo_fakeenv_post_term" : dis ? "cmbpo_fakeenv_post_disagreement"
+  const char *who = c.term_thr ? "cmbpo_fakeenv_post_term_draws" : c.ch ? "cmbpo_fakeenv_post_cost" : th ? "cmbpo_fakeenv_post_term" : dis ? "cmbpo_fakeenv_post_disagreement"
                     : c.xi ? "cmbpo_fakeenv_post_noise" : "cmbpo_fakeenv_post";
   const int obs_dim = c.obs_dim, act_dim = c.act_dim, ensemble = c.ensemble;
   const int learned_cost = (c.task & CMBPO_TASK_LEARNED_COST) ? 1 : 0;     // every other bit outside the rule id is an error
@@ -582,6 +602,9 @@ int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream) {
     CMBPO_REQUIRE(th->members >= CMBPO_TERM_ELITE && th->members <= CMBPO_TERM_MAJORITY,
                   "%s: termination head: members %d not in 0..2 (CMBPO_TERM_ELITE / _ANY / _MAJORITY)", who, th->members);
   }
+  // (host code: nothing reads the draws here, any float may stand in them)
+  CMBPO_REQUIRE(c.term_thr == nullptr || th != nullptr,
+                "%s: termination draws (d_term_thr) need a termination head: th is NULL, and there is no column to compare them with", who);
   if (c.ch != nullptr) {
     CMBPO_REQUIRE(c.ch->kind == 0 || c.ch->kind == 1, "%s: cost head: kind %d not in {0, 1} (0 magnitude, 1 logistic)", who, c.ch->kind);
     CMBPO_REQUIRE(isfinite(c.ch->logit_shift), "%s: cost head: logit_shift %g is not a finite number", who, (double)c.ch->logit_shift);
@@ -622,26 +645,26 @@ int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream) {
       PostArgsDerivedNoise an{};
       static_cast<PostArgsDerived &>(an) = ar;
       an.xi = c.xi;
-      launch_post_ext<2, true>(ensemble, grid, lds, s, an, dis, th, ch);
+      launch_post_ext<2, true>(ensemble, grid, lds, s, an, dis, th, c.term_thr, ch);
     } else if (user) {
       PostArgsRulesNoise an{};
       static_cast<PostArgsRules &>(an) = ar;
       an.xi = c.xi;
-      launch_post_ext<1, true>(ensemble, grid, lds, s, an, dis, th, ch);
+      launch_post_ext<1, true>(ensemble, grid, lds, s, an, dis, th, c.term_thr, ch);
     } else {
       PostArgsNoise an{};
       static_cast<PostArgs &>(an) = a;
       an.xi = c.xi;
-      launch_post_ext<0, true>(ensemble, grid, lds, s, an, dis, th, ch);
+      launch_post_ext<0, true>(ensemble, grid, lds, s, an, dis, th, c.term_thr, ch);
     }
-  } else if (derived) launch_post_ext<2, false>(ensemble, grid, lds, s, ar, dis, th, ch);
-  else if (user) launch_post_ext<1, false>(ensemble, grid, lds, s, ar, dis, th, ch);
-  else launch_post_ext<0, false>(ensemble, grid, lds, s, a, dis, th, ch);
+  } else if (derived) launch_post_ext<2, false>(ensemble, grid, lds, s, ar, dis, th, c.term_thr, ch);
+  else if (user) launch_post_ext<1, false>(ensemble, grid, lds, s, ar, dis, th, c.term_thr, ch);
+  else launch_post_ext<0, false>(ensemble, grid, lds, s, a, dis, th, c.term_thr, ch);
   CMBPO_HIP_CHECK(hipGetLastError());
   return CMBPO_OK;
 }
 
-// The five public entry points fill the descriptor and make that call; none forwards to another.  POST_COMMON: the 20 leading
+// The six public entry points fill the descriptor and make that call; none forwards to another.  POST_COMMON: the 20 leading
 // parameters they share (the stream goes beside the descriptor).
 #define POST_COMMON                                                                                                              \
   int task, int ensemble, int obs_dim, int act_dim, const float *d_mean, const float *d_var, int ld_rows, const float *d_obs,    \
@@ -706,6 +729,21 @@ extern "C" int cmbpo_fakeenv_post_cost(POST_COMMON, const float *d_xi, float kap
   c.dis = DisExtra{kappa_rew, kappa_cost, d_rew_var, d_cost_var};
   c.th = th;
   c.ch = ch;
+  return cmbpo_internal_fakeenv_post(c, stream);
+}
+
+// ... with sampled terminations (see the kernel's DRAW parts and the header): the superset -- every feature is optional;
+// d_term_thr == NULL is cmbpo_fakeenv_post_cost's call
+extern "C" int cmbpo_fakeenv_post_term_draws(POST_COMMON, const float *d_xi, float kappa_rew, float kappa_cost, float *d_rew_var,
+                                             float *d_cost_var, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch,
+                                             const float *d_term_thr, void *stream) {
+  FakeenvPostCall c = post_common(POST_COMMON_ARGS);
+  c.xi = d_xi;
+  c.dis_on = d_rew_var != nullptr || d_cost_var != nullptr || kappa_rew != 0.0f || kappa_cost != 0.0f;
+  c.dis = DisExtra{kappa_rew, kappa_cost, d_rew_var, d_cost_var};
+  c.th = th;
+  c.ch = ch;
+  c.term_thr = d_term_thr;
   return cmbpo_internal_fakeenv_post(c, stream);
 }
 

@@ -1,4 +1,4 @@
-// Internal (not part of the C-ABI): the ONE call behind the five cmbpo_fakeenv_post* entry points (fakeenv_post.hip), which the
+// Internal (not part of the C-ABI): the ONE call behind the six cmbpo_fakeenv_post* entry points (fakeenv_post.hip), which the
 // one-call rollout step (rollout_step.hip) and the model replay (replay.hip) make directly.
 #pragma once
 #include "common.h"
@@ -9,7 +9,7 @@ struct DisExtra {
   float *rew_var, *cost_var;
 };
 
-// One post step: the arguments every entry point shares, in the order of cmbpo_fakeenv_post (include/cmbpo_hip.h), and the four
+// One post step: the arguments every entry point shares, in the order of cmbpo_fakeenv_post (include/cmbpo_hip.h), and the five
 // optional features.  A feature that is off selects the kernel instances without it, with the argument block they always had.
 struct FakeenvPostCall {
   int task, ensemble, obs_dim, act_dim;
@@ -26,13 +26,15 @@ struct FakeenvPostCall {
   DisExtra dis;
   const cmbpo_term_head_t *th;    // learned termination head; NULL: off
   const cmbpo_cost_head_t *ch;    // how the learned-cost column is read; NULL or kind 0: as a magnitude
+  const float *term_thr;          // sampled terminations: a threshold per slot in place of th->threshold; NULL: off (needs th)
 };
 
-// Checks the call, then launches the instance for (ensemble size, rule table, xi, dis_on, th, ch).  The messages carry the name of the
+// Checks the call, then launches the instance for (ensemble size, rule table, xi, dis_on, th, ch, term_thr).  The messages carry the name of the
 // narrowest public entry point that can express the call, derived here and nowhere else:
-//   1. ch != NULL     cmbpo_fakeenv_post_cost
-//   2. else th != NULL cmbpo_fakeenv_post_term
-//   3. else dis_on    cmbpo_fakeenv_post_disagreement
-//   4. else xi != NULL cmbpo_fakeenv_post_noise
-//   5. else           cmbpo_fakeenv_post
+//   1. term_thr != NULL cmbpo_fakeenv_post_term_draws
+//   2. else ch != NULL cmbpo_fakeenv_post_cost
+//   3. else th != NULL cmbpo_fakeenv_post_term
+//   4. else dis_on    cmbpo_fakeenv_post_disagreement
+//   5. else xi != NULL cmbpo_fakeenv_post_noise
+//   6. else           cmbpo_fakeenv_post
 int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream);

@@ -1313,7 +1313,8 @@ void side_update(const cmbpo_rollout_t *r, Change change) {
   std::lock_guard<std::mutex> lock(g_side_mu);
   RolloutSide &sd = g_side[r->iscal];
   change(sd);
-  if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr && sd.vd.part == nullptr && !sd.th_on && !sd.ch_on) g_side.erase(r->iscal);
+  if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr && sd.vd.part == nullptr && !sd.th_on && !sd.ch_on && sd.thr == nullptr)
+    g_side.erase(r->iscal);
 }
 
 }  // namespace
@@ -1380,6 +1381,14 @@ extern "C" int cmbpo_rollout_term_head_attach(const cmbpo_rollout_t *r, const cm
 extern "C" int cmbpo_rollout_term_head_detach(const cmbpo_rollout_t *r) {
   CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_term_head_detach: NULL rollout struct / iscal");
   side_update(r, [](RolloutSide &sd) { sd.th = {}; sd.th_on = 0; });
+  return CMBPO_OK;
+}
+
+// (whether a termination head is attached is the step's question: the two attach in either order)
+extern "C" int cmbpo_rollout_term_draws_attach(const cmbpo_rollout_t *r, const float *d_thr, long step_stride) {
+  CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_term_draws_attach: NULL rollout struct / iscal");
+  CMBPO_REQUIRE(step_stride >= 0, "cmbpo_rollout_term_draws_attach: step_stride %ld < 0", step_stride);
+  side_update(r, [&](RolloutSide &sd) { sd.thr = d_thr; sd.thr_stride = d_thr ? step_stride : 0; });   // (d_thr == NULL: detached)
   return CMBPO_OK;
 }
 

@@ -25,11 +25,12 @@ struct Ahead {
 
 // policy_ready: this step's actions are already in act_t / logp_t / mu_t / ls_t (the previous step's critic launch carried
 // the actor along).  d_eps_next != NULL: let this step's critic launch carry the actor for the NEXT step (its noise), if the
-// three networks allow it; *next_ready says whether it did.
+// three networks allow it; *next_ready says whether it did.  run_step: which step of a cmbpo_rollout_run call this is (0 for
+// cmbpo_rollout_step) -- the attached termination draws are read that many strides in.
 static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy, cmbpo_mlp_t *model, cmbpo_mlp_t *v,
                      cmbpo_mlp_t *vc, int task, int ensemble, const float *d_eps, const int32_t *d_elite, float *d_mean,
                      float *d_var, bool policy_ready, const float *d_eps_next, bool *next_ready, uint32_t *d_mirror, uint32_t seq,
-                     const Ahead &ahead, const float *d_xi, void *stream) {
+                     const Ahead &ahead, const float *d_xi, int run_step, void *stream) {
   CMBPO_REQUIRE(r && policy && model && v && vc && d_eps && d_elite && d_mean && d_var, "cmbpo_rollout_step: NULL argument");
   CMBPO_REQUIRE(n_alive >= 1 && n_alive <= r->B, "cmbpo_rollout_step: n_alive %d not in [1, B=%d]", n_alive, r->B);
   // what is attached beside *r, looked up once for every launch of the step
@@ -44,6 +45,10 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
                   "cmbpo_rollout_step: a logistic cost head (cmbpo_cost_head_t, kind 1) is attached: model out_dim %d does not match "
                   "obs_dim %d + 2 (+ 1 with a termination head attached), task 0x%x", model->out_dim, r->obs_dim, task);
   }
+  // sampled terminations: thresholds without a column to compare them with -- refused before the first launch of the step
+  CMBPO_REQUIRE(sd.thr == nullptr || sd.th_on,
+                "cmbpo_rollout_step: termination draws are attached (cmbpo_rollout_term_draws_attach) without a termination head "
+                "(cmbpo_rollout_term_head_attach): there is no column to compare them with");
   if (sd.th_on)
     CMBPO_REQUIRE(model->out_dim == r->obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0) + 1,
                   "cmbpo_rollout_step: a termination head (cmbpo_term_head_t) is attached: model out_dim %d does not match obs_dim %d + 1 "
@@ -86,6 +91,7 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   pc.dis = DisExtra{sd.dg.kappa_rew, sd.dg.kappa_cost, sd.dg.rew_var_t, sd.dg.cost_var_t};
   pc.th = sd.th_on ? &sd.th : nullptr;
   pc.ch = sd.ch_on ? &sd.ch : nullptr;
+  pc.term_thr = sd.thr ? sd.thr + (size_t)run_step * (size_t)sd.thr_stride : nullptr;     // step j of a run: as xi_at does for xi
   if ((rc = cmbpo_internal_fakeenv_post(pc, stream))) return rc;
   const bool small = ahead.on || (n_alive <= cmbpo_rollout_book_pre_max_rows() && !r->use_host_budget);
   // small batches: decide + finish(PRE) + the store's scalar half in one launch; its vector half (obs, act, mu, log_std) rides
@@ -144,7 +150,7 @@ extern "C" int cmbpo_rollout_step(const cmbpo_rollout_t *r, int n_alive, cmbpo_m
                                   const int32_t *d_elite, float *d_mean, float *d_var, void *stream) {
   bool unused = false;
   return step_impl(r, n_alive, policy, model, v, vc, task, ensemble, d_eps, d_elite, d_mean, d_var, false, nullptr, &unused, nullptr, 0u,
-                   Ahead{}, r ? r->xi : nullptr, stream);
+                   Ahead{}, r ? r->xi : nullptr, 0, stream);
 }
 
 // Several steps in one call: what ModelSampler.sample()'s caller does between two steps (read the step's counters, swap the
@@ -258,7 +264,7 @@ extern "C" int cmbpo_rollout_run(cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *p
         p.seq = next_seq();
         const int rc = step_impl(r, n_alive, policy, model, v, vc, task, ensemble, d_eps + (size_t)k * eps_stride,
                                  d_elite + (size_t)k * elite_stride, d_mean, d_var, ready, eps_next, &next_ready,
-                                 mir.d + (size_t)p.slot * kMirrorDwords, p.seq, ah, xi_at(k), stream);
+                                 mir.d + (size_t)p.slot * kMirrorDwords, p.seq, ah, xi_at(k), k, stream);
         ready = next_ready;
         if (rc == 0) cmbpo_set_error("cmbpo_rollout_run: look-ahead step took the large-batch path");
         return rc == 1 ? CMBPO_OK : (rc == 0 ? CMBPO_EINVAL : rc);
@@ -293,7 +299,7 @@ extern "C" int cmbpo_rollout_run(cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *p
     uint32_t *d_slot = mir.d ? mir.d + (size_t)slot * kMirrorDwords : nullptr;
     int rc = step_impl(r, n_alive, policy, model, v, vc, task, ensemble, d_eps + (size_t)done * eps_stride,
                        d_elite + (size_t)done * elite_stride, d_mean, d_var, ready, eps_next, &next_ready, d_slot, seq, Ahead{},
-                       xi_at(done), stream);
+                       xi_at(done), done, stream);
     ready = next_ready;
     if (rc != 0 && rc != 1) return rc;
     char *h = static_cast<char *>(h_scalars) + (size_t)done * 384;

@@ -38,6 +38,13 @@ adds ``info['term_pred']`` (the elite's value of the column) and ``info['term_vo
 logit z, ``term_threshold`` a probability tau strictly inside (0, 1), and the test ``sigma(z) > tau`` runs in the same kernel as
 ``z > float32(logit(tau))``; ``info['term_pred']`` is ``sigma(z)`` in float32.
 
+``term_draws=`` of ``step()`` ([n] uniform draws u in (0, 1], in the order of ``obs``) and ``term_thr=`` of ``step_device()``
+(a slot-indexed float32 CUDA tensor of thresholds) SAMPLE the learned termination: row r's members are compared
+with the row's own threshold instead of ``term_threshold`` -- ``utils.term_thresholds(u, term_loss)``: ``logit(u)`` under
+'logistic', ``u`` under 'gaussian' -- so a branch whose column says p ends with probability p
+(``cmbpo_fakeenv_post_term_draws``).  The vote, ``info['term_pred']`` and ``info['term_votes']`` are what they were; all members
+of a row share the row's draw.  Both need ``predicts_term=True``.
+
 ``cost_loss='logistic'`` (needs ``predicts_cost=True``; a model whose cost column is logistic,
 ``PE(logistic_columns=[obs_dim + 1])``): the column is a logit z and the cost of a step its probability
 ``sigma(z - cost_logit_shift)`` in [0, 1], computed in the kernel; the disagreement variance is taken on the members'
@@ -200,7 +207,7 @@ class FakeEnv:
         elites = np.asarray(self._model.elite_inds, dtype=np.int32)
         return elites[self._rng.integers(0, len(elites), size=size)]
 
-    def step_device(self, obs, act, model_inds, out, row_idx=None, n_rows=None, scratch=None, noise=None):
+    def step_device(self, obs, act, model_inds, out, row_idx=None, n_rows=None, scratch=None, noise=None, term_thr=None):
         """Device-resident step: all arguments are CUDA tensors indexed by branch slot (noise: [B, obs_dim] float32
         N(0, 1) draws for stochastic transitions, None: the elite member's mean).
 
@@ -209,9 +216,17 @@ class FakeEnv:
         rew_var[B] and cost_var[B]; they are filled, and rew / cost are the penalised values.  With `predicts_term`, term is
         rule_done or learned_done, and out's optional term_pred[B] / term_votes[B] u8 are filled (under
         ``term_loss='logistic'`` term_pred carries the logit).  With ``cost_loss='logistic'`` cost is the probability and out's
-        optional cost_logit[B] is filled with the elite's raw logit.
+        optional cost_logit[B] is filled with the elite's raw logit.  term_thr: [B] float32 thresholds of the sampled
+        terminations, in the column's own units (``utils.term_thresholds``), in place of the head's threshold; None: the head's.
         """
         B = obs.shape[0]
+        if term_thr is not None:
+            if not self._predicts_term:
+                raise ValueError("term_thr needs predicts_term=True: the model has no termination column to compare the "
+                                 "thresholds with")
+            if not (term_thr.is_cuda and term_thr.dtype == torch.float32 and term_thr.is_contiguous()
+                    and tuple(term_thr.shape) == (B,)):
+                raise ValueError("term_thr must be a contiguous float32 CUDA tensor of shape [%d]" % B)
         if noise is not None and not (noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
                                       and tuple(noise.shape) == (B, self.obs_dim)):
             raise ValueError("noise must be a contiguous float32 CUDA tensor of shape [%d, %d]" % (B, self.obs_dim))
@@ -239,17 +254,22 @@ class FakeEnv:
             if self.disagreement else (0.0, 0.0, None, None)
         th = self.term_head_struct(out.get("term_pred"), out.get("term_votes"))
         ch = self.cost_head_struct(out.get("cost_logit"))
-        _lib.check(lib.cmbpo_fakeenv_post_cost(
-            self._task_id, E, self.obs_dim, self.act_dim, _lib.ptr(mean), _lib.ptr(var), B, _lib.ptr(obs), _lib.ptr(act),
-            _lib.ptr(model_inds), _lib.ptr(row_idx), None, n, _lib.ptr(out["next_obs"]), _lib.ptr(out["rew"]),
-            _lib.ptr(out["term"]), _lib.ptr(out["cost"]), _lib.ptr(out["dkl_path"]), _lib.ptr(out["ep_var_mean"]),
-            _lib.ptr(out.get("ep_var")), _lib.ptr(noise), *dis, C.byref(th) if th is not None else None,
-            C.byref(ch) if ch is not None else None, stream), "cmbpo_fakeenv_post_cost")
+        args = (self._task_id, E, self.obs_dim, self.act_dim, _lib.ptr(mean), _lib.ptr(var), B, _lib.ptr(obs), _lib.ptr(act),
+                _lib.ptr(model_inds), _lib.ptr(row_idx), None, n, _lib.ptr(out["next_obs"]), _lib.ptr(out["rew"]),
+                _lib.ptr(out["term"]), _lib.ptr(out["cost"]), _lib.ptr(out["dkl_path"]), _lib.ptr(out["ep_var_mean"]),
+                _lib.ptr(out.get("ep_var")), _lib.ptr(noise), *dis, C.byref(th) if th is not None else None,
+                C.byref(ch) if ch is not None else None)
+        if term_thr is None:
+            _lib.check(lib.cmbpo_fakeenv_post_cost(*args, stream), "cmbpo_fakeenv_post_cost")
+        else:       # sampled terminations: the same call with the thresholds behind it
+            _lib.check(lib.cmbpo_fakeenv_post_term_draws(*args, _lib.ptr(term_thr), stream), "cmbpo_fakeenv_post_term_draws")
         return out
 
-    def step(self, obs, act, deterministic=True, model_inds=None, noise=None):
+    def step(self, obs, act, deterministic=True, model_inds=None, noise=None, term_draws=None):
         assert len(obs.shape) == len(act.shape)
         assert obs.shape[-1] == self.obs_dim and act.shape[-1] == self.act_dim
+        if term_draws is not None and not self._predicts_term:
+            raise ValueError("term_draws needs predicts_term=True: the model has no termination column to sample from")
         if not deterministic:
             raise NotImplementedError("deterministic=False (mean + std) is never used by the trainer; pass "
                                       "noise=np.ones((n, obs_dim), np.float32) for the reference's mean + std, or "
@@ -274,6 +294,16 @@ class FakeEnv:
                                      else noise, dtype=torch.float32, device=self.device).contiguous()
                 if tuple(xi.shape) != (n, self.obs_dim):
                     raise ValueError("noise must have shape [%d, %d], got %s" % (n, self.obs_dim, tuple(xi.shape)))
+            thr = None
+            if term_draws is not None:
+                from .utils import term_thresholds
+                u = term_draws if isinstance(term_draws, torch.Tensor) else np.asarray(term_draws)
+                if tuple(u.shape) == () and single:
+                    u = u[None]
+                if tuple(u.shape) != (n,):
+                    raise ValueError("term_draws must have shape [%d], got %s" % (n, tuple(u.shape)))
+                thr = term_thresholds(u, self.term_loss)      # (rows are slots here)
+                thr = torch.as_tensor(thr, dtype=torch.float32, device=self.device).contiguous()
             if model_inds is None:
                 model_inds = self.random_inds(n)
             inds = torch.as_tensor(np.asarray(model_inds, dtype=np.int32), device=self.device) \
@@ -289,7 +319,7 @@ class FakeEnv:
                 out.update(term_pred=torch.empty(n, **f), term_votes=torch.empty(n, dtype=torch.uint8, device=self.device))
             if self.cost_loss == 'logistic':
                 out.update(cost_logit=torch.empty(n, **f))
-            self.step_device(o, a, inds, out, noise=xi)
+            self.step_device(o, a, inds, out, noise=xi, term_thr=thr)
         next_obs, r, terms = out["next_obs"], out["rew"][:, None], out["term"].bool()[:, None]
         c = out["cost"][:, None]
         if self._bool_cost:      # (not with a learned cost: the float32 prediction is the cost)

@@ -30,6 +30,14 @@ step, the native loop and the sharded per-step path alike; ``pool.t['term_pred_t
 ``reset()`` also takes the reading of the learned-cost column (``FakeEnv(cost_loss='logistic', cost_logit_shift=...)``, DESIGN
 §3w): every step then stores the cost as a probability, and ``pool.t['cost_logit_t']`` holds the step's raw logits.
 
+``ModelSampler(term_sampling=True)`` SAMPLES the learned termination (needs an ``env`` with ``predicts_term``): a
+branch whose termination column says p ends with probability p instead of where p is above the head's threshold.  The sampler
+draws u = 1 - rand() in (0, 1] per branch and step from a generator of its own (seeded ``seed + 1``), a whole chunk ``[K, B]``
+at a time with the chunk's K, turns them into thresholds (``utils.term_thresholds`` with the environment's ``term_loss``) and
+attaches them beside the rollout struct (``cmbpo_rollout_term_draws_attach``) for the one-call step and the native loop.  The
+action noise, the elite picks and the transition noise are the numbers they were, at the same chunk boundaries; off (the
+default) no generator is made and no call is added.  Sharded samplers refuse it: per-rank streams are not defined here.
+
 ``sample()`` returns ``(next_obs, reward, terminal, info)`` like the reference, but as slot-indexed CUDA
 tensors (the trainer only reads ``info['alive_ratio']``, ``algorithms/cmbpo.py:254-263``).
 """
@@ -47,13 +55,19 @@ EPS = 1e-8  # utilities/utils.py:19
 
 class ModelSampler:
     def __init__(self, max_path_length, batch_size=1000, rollout_mode=False, logger=None, seed=0,
-                 comm=None, stochastic=False):
+                 comm=None, stochastic=False, term_sampling=False):
         self._max_path_length = int(max_path_length)
         self.batch_size = int(batch_size)
         self.rollout_mode = rollout_mode
         self.logger = logger
         self.comm = comm
         self.stochastic = bool(stochastic)     # transitions drawn from N(mean, var) instead of the elite member's mean
+        self.term_sampling = bool(term_sampling)    # learned terminations drawn from the head's probability, not thresholded
+        if self.term_sampling and comm is not None and comm.world > 1:
+            raise NotImplementedError("term_sampling=True on a sharded sampler (world size %d): per-rank streams of termination "
+                                      "draws are not defined here" % comm.world)
+        self._term_gen = None                       # the generator of the termination draws (term_sampling only)
+        self._thr_attached = False                  # thresholds are attached beside the pool's struct
         self.dkl_lim = float("inf")
         self.env = self.policy = self.pool = None
         self._n_episodes = 0
@@ -69,10 +83,14 @@ class ModelSampler:
 
     # -- wiring -----------------------------------------------------------------------------------
     def initialize(self, env, policy, pool):
+        if self.term_sampling and not getattr(env, "predicts_term", False):
+            raise ValueError("term_sampling=True needs an environment with predicts_term=True: the model has no termination "
+                             "column to sample from")
         self.env, self.policy, self.pool = env, policy, pool
         self.device = pool.device
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(self._seed)
+        self._term_gen = None                       # (made with the first chunk of termination draws)
         # everything bound to the device starts over
         self._elites = self._elites_host = None     # the model's elite indices on the device / as last uploaded
         self._draws = None                          # chunk of draws, see _draw_chunk()
@@ -273,14 +291,27 @@ class ModelSampler:
         full[idx.long()] = torch.as_tensor(np.ascontiguousarray(compact), device=self.device).to(dtype)
         return full
 
-    def sample(self, max_samples=None, eps=None, model_inds=None, xi=None):
+    def _attach_thresholds(self, ptr, stride):
+        """The thresholds of the next native call: step j reads ptr + 4 * j * stride (None: back to the head's threshold)."""
+        if ptr is None and not self._thr_attached:
+            return
+        _lib.check(_lib.lib().cmbpo_rollout_term_draws_attach(C.byref(self.pool.rs), ptr, stride),
+                   "cmbpo_rollout_term_draws_attach")
+        self._thr_attached = ptr is not None
+
+    def sample(self, max_samples=None, eps=None, model_inds=None, xi=None, term_draws=None):
         """One imagined step of every alive branch (model_sampler.py:239-375).
 
         eps / model_inds (optional, compact alive-only order like the reference's arrays) inject the
         N(0,1) action noise (ac_network.py:109) and the per-branch elite draw (fake_env.py:174-178);
         xi ([n, obs_dim], the same order) the transition noise: next_obs = mean + std * xi + obs.  Without it a
-        `stochastic` sampler draws its own, any other sampler steps to the elite member's mean.
+        `stochastic` sampler draws its own, any other sampler steps to the elite member's mean.  term_draws ([n] uniform
+        numbers in (0, 1], the same order) sample the learned termination of this step; without them a `term_sampling`
+        sampler draws its own, any other sampler keeps the head's threshold.
         """
+        if term_draws is not None and not getattr(self.env, "predicts_term", False):
+            raise ValueError("term_draws needs an environment with predicts_term=True: the model has no termination column to "
+                             "sample from")
         pool = self.pool
         assert pool.has_room                       # pool full! empty before sampling.
         sharded = self.comm is not None and self.comm.world > 1
@@ -290,10 +321,10 @@ class ModelSampler:
         assert pool.n_alive > 0                    # reset before sampling !
         if torch.cuda.current_device() != self.device.index:
             with torch.cuda.device(self.device):
-                return self._step(sharded, max_samples, eps, model_inds, xi)
-        return self._step(sharded, max_samples, eps, model_inds, xi)
+                return self._step(sharded, max_samples, eps, model_inds, xi, term_draws)
+        return self._step(sharded, max_samples, eps, model_inds, xi, term_draws)
 
-    def _step(self, sharded, max_samples, eps, model_inds, xi):
+    def _step(self, sharded, max_samples, eps, model_inds, xi, term_draws=None):
         """sample() on the sampler's device.  On one rank with the sampler's own draws the whole step is ONE C call
         (cmbpo_rollout_step) plus the read of the step's counters -- at the shipped configurations' 1e3 - 1e4 branches a step
         is ~100 us of kernels, so the host side of that case is kept to pointer arithmetic."""
@@ -304,9 +335,22 @@ class ModelSampler:
         h = self._prepare_call(max_samples)
         exchange = sharded and rs.max_samples != 0      # the reference's `if max_samples:` (negative budgets count)
         separate = exchange or env.kernel_events is not None
-        if eps is None or model_inds is None or (xi is None and self.stochastic):
+        if eps is None or model_inds is None or (xi is None and self.stochastic) or (term_draws is None and self.term_sampling):
             ck, k, eps_ptr, inds_ptr, xi_ptr = self._next_draws()
             ck[0] = k + 1
+        # sampled terminations: this step's thresholds, slot indexed (injected draws are scattered like the others)
+        thr_t = None
+        if term_draws is not None:
+            from .utils import term_thresholds
+            u = torch.as_tensor(np.ascontiguousarray(term_draws)) if not isinstance(term_draws, torch.Tensor) else term_draws
+            if tuple(u.shape) != (n,):
+                raise ValueError("term_draws must have shape [%d] (one draw per alive branch), got %s" % (n, tuple(u.shape)))
+            thr = term_thresholds(u, getattr(env, "term_loss", "gaussian"))
+            # (dead slots: +inf, which never hits)
+            thr_t = torch.full((self.batch_size,), float("inf"), dtype=torch.float32, device=self.device)
+            thr_t[t["alive_idx"][:n].long()] = thr.to(self.device)
+        elif self.term_sampling:
+            thr_t = ck[4][k]
         if separate or eps is not None or model_inds is not None or xi is not None:
             # injected draws are scattered to slot order; the separate entries below take tensors
             idx = t["alive_idx"][:n]
@@ -320,6 +364,7 @@ class ModelSampler:
         rs.xi = xi_ptr
         rc = 0
         if not separate:
+            self._attach_thresholds(None if thr_t is None else thr_t.data_ptr(), 0)
             # the whole step in one call: at small rollout batches a step is bound by host latency
             rc = _lib.lib().cmbpo_rollout_step(C.byref(rs), n, h[0], h[1], h[2], h[3], env._task_id, env._model.num_nets,
                                                eps_ptr, inds_ptr, h[4], h[5], _lib.current_stream())
@@ -341,7 +386,8 @@ class ModelSampler:
             if pool.cost_head is not None:
                 outs.update(cost_logit=t["cost_logit_t"])
             env.step_device(t["cur_obs"], t["act_t"], inds_t, outs,
-                            row_idx=idx, n_rows=n, scratch=self._scratch, noise=xi_t)
+                            row_idx=idx, n_rows=n, scratch=self._scratch, noise=xi_t,
+                            **({} if thr_t is None else dict(term_thr=thr_t)))
             if exchange:
                 # budget rule across shards: gather {n_alive, n_unc, total}, rank the survivors globally
                 pool._call("cmbpo_rollout_count")
@@ -361,9 +407,10 @@ class ModelSampler:
     def _draw_chunk(self):
         """Action noise and elite picks for several steps at a time (three torch launches per chunk instead of per step:
         at small rollout batches a step is a chain of launch latencies).  Returns the chunk list
-        [next step, eps [K, B, A], elite indices [K, B], xi [K, B, obs] or None].  A `stochastic` sampler draws the
-        transition noise after the elite picks, with K such that the chunk's bytes stay under the same cap; any other
-        sampler makes exactly the generator calls it always made."""
+        [next step, eps [K, B, A], elite indices [K, B], xi [K, B, obs] or None, termination thresholds [K, B] or None].  A
+        `stochastic` sampler draws the transition noise after the elite picks, with K such that the chunk's bytes stay under
+        the same cap; any other sampler makes exactly the generator calls it always made.  A `term_sampling` sampler draws the
+        chunk's termination draws from a generator of its own: K and the other streams are what they are without it."""
         B, A = self.batch_size, self.pool.act_dim
         step_bytes = max(B * (A + (self.pool.obs_dim if self.stochastic else 0)) * 4, 1)
         K = max(1, min(40, max(2 ** 23 // step_bytes, min(8, 2 ** 28 // step_bytes))))    # a whole rollout at small batches
@@ -374,16 +421,26 @@ class ModelSampler:
             x_ck = torch.randn((K, B, self.pool.obs_dim), generator=self._gen, dtype=torch.float32, device=self.device)
             if self._noise_scale is not None:
                 x_ck.mul_(self._noise_scale.to(self.device))
-        self._draws = [0, e_ck, self._elites[d_ck], x_ck]
+        t_ck = None
+        if self.term_sampling:
+            from .utils import term_thresholds
+            if self._term_gen is None:
+                self._term_gen = torch.Generator(device=self.device)
+                self._term_gen.manual_seed(self._seed + 1)
+            # u = 1 - rand() in (0, 1]: a probability of exactly 0 never ends a branch
+            u_ck = 1.0 - torch.rand((K, B), generator=self._term_gen, dtype=torch.float32, device=self.device)
+            t_ck = term_thresholds(u_ck, getattr(self.env, "term_loss", "gaussian"), check=False).contiguous()
+        self._draws = [0, e_ck, self._elites[d_ck], x_ck, t_ck]
         return self._draws
 
     def _next_draws(self):
         """The draw chunk, its first unused step k and the device addresses of that step's eps, elite indices and xi (None without
         transition noise).  The chunk is drawn again when it is used up or was drawn for another batch size or another
-        `stochastic`.  The caller advances chunk[0] by the steps it takes."""
+        `stochastic` / `term_sampling`.  The caller advances chunk[0] by the steps it takes; step k's thresholds are chunk[4][k]."""
         ck = self._draws
         B = self.batch_size
-        if ck is None or ck[0] >= ck[1].shape[0] or ck[1].shape[1] != B or (ck[3] is None) == self.stochastic:
+        if ck is None or ck[0] >= ck[1].shape[0] or ck[1].shape[1] != B or (ck[3] is None) == self.stochastic \
+                or (ck[4] is None) == self.term_sampling:
             ck = self._draw_chunk()
         k = ck[0]
         return (ck, k, ck[1].data_ptr() + k * B * self.pool.act_dim * 4, ck[2].data_ptr() + k * B * ck[2].element_size(),
@@ -484,6 +541,8 @@ class ModelSampler:
                 ck, k, eps_ptr, inds_ptr, rs.xi = self._next_draws()
                 take = min(left, ck[1].shape[0] - k, 64)
                 rs.xi_stride = B * pool.obs_dim
+                # (sampled terminations: step j of the call reads the chunk's thresholds + j * B)
+                self._attach_thresholds(ck[4].data_ptr() + k * B * 4 if ck[4] is not None else None, B)
                 _lib.check(lib.cmbpo_rollout_run(
                     C.byref(rs), pool.n_alive, h[0], h[1], h[2], h[3], env._task_id, env._model.num_nets,
                     eps_ptr, inds_ptr, B * pool.act_dim, B,

@@ -135,6 +135,8 @@ def _detach_all(rs):
     """Drop whatever the library's table holds under this struct's key (its iscal)."""
     for side in _SIDE.values():
         _lib.check(getattr(_lib.lib(), side.detach)(C.byref(rs)), side.detach)
+    # (the sampler's termination thresholds travel in the same entry: ModelSampler(term_sampling=True))
+    _lib.check(_lib.lib().cmbpo_rollout_term_draws_attach(C.byref(rs), None, 0), "cmbpo_rollout_term_draws_attach")
 
 
 def _iv_release(key):

@@ -45,6 +45,42 @@ def logit_threshold(tau):
                          "got %r" % (tau,)) from None
 
 
+def term_thresholds(u, loss, check=True):
+    """THE place that turns termination draws into the thresholds of ``cmbpo_fakeenv_post_term_draws`` (sampled terminations,
+    DESIGN §3y): a branch whose termination column says p ends where ``column > threshold``, which happens with probability p for
+    ``u`` uniform on (0, 1].  ``loss`` says how the column was trained: under ``'logistic'`` it is a logit and the threshold
+    ``log(u) - log1p(-u)``, computed in float64 and rounded to float32 (u = 1 gives +inf: a probability of exactly 0 never
+    ends a branch; u = 0.5 gives 0; u = 0 gives -inf); under ``'gaussian'`` it is in 0 / 1 target units and the threshold ``u``
+    itself.  ``u``: a NumPy array or a torch tensor, any shape; the result is float32 of the same kind (and device).  A ``u``
+    outside [0, 1] or NaN raises ``ValueError``; ``check=False`` skips that test for draws that are inside by construction
+    (on a device tensor it costs a synchronisation)."""
+    if loss not in ('gaussian', 'logistic'):
+        raise ValueError(f"term_thresholds: loss 'gaussian' or 'logistic', got {loss!r}")
+    import torch
+    if not isinstance(u, torch.Tensor):
+        u = np.asarray(u)
+        if u.dtype.kind not in 'fiu':
+            raise ValueError("term_thresholds: draws must be real numbers, got dtype %s" % (u.dtype,))
+        # (written positively: a NaN is refused)
+        if check and not bool(np.all((u >= 0) & (u <= 1))):
+            raise ValueError("term_thresholds: draws must lie in [0, 1] (NaN is refused): they are uniform numbers, "
+                             "u = 1 - rand() in (0, 1]")
+        if loss == 'gaussian':
+            return u.astype(np.float32)
+        u64 = u.astype(np.float64)
+        with np.errstate(divide='ignore'):
+            return (np.log(u64) - np.log1p(-u64)).astype(np.float32)
+    if not u.is_floating_point():
+        raise ValueError("term_thresholds: draws must be a floating-point tensor, got %s" % (u.dtype,))
+    if check and not bool(((u >= 0) & (u <= 1)).all()):
+        raise ValueError("term_thresholds: draws must lie in [0, 1] (NaN is refused): they are uniform numbers, "
+                         "u = 1 - rand() in (0, 1]")
+    if loss == 'gaussian':
+        return u.to(torch.float32)
+    u64 = u.to(torch.float64)
+    return (torch.log(u64) - torch.log1p(-u64)).to(torch.float32)
+
+
 def get_cpobuffer(env, *args, **kwargs):
     from .cpobuffer import CPOBuffer
     return CPOBuffer(*args, observation_space=env.observation_space, action_space=env.action_space, **kwargs)

@@ -426,6 +426,32 @@ int cmbpo_fakeenv_post_cost(int task, int ensemble, int obs_dim, int act_dim,
                             float *d_rew_var, float *d_cost_var,
                             const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, void *stream);
 
+/* Sampled terminations: the termination head read as a hazard, not as a classifier.  THE rule:
+ *   hit_e = x_e > thr[r]          thr[r] replaces th->threshold for row r
+ *   everything else of cmbpo_term_head_t is unchanged
+ * The test is written positively: a NaN on either side never hits; thr = -inf hits every non-NaN x, -inf excepted; thr = +inf
+ * never hits; x == thr does not hit.  d_term_thr: float32 [.], slot indexed like d_term, in the column's own units, any value.
+ * votes, the three `members` modes, term_pred, term_votes and term = rule_done || learned_done are cmbpo_term_head_t's; all
+ * members of a row share the row's threshold; the cost still reads the rule's own done; th->threshold is checked and not read.
+ * The kernel knows nothing about uniform numbers: the caller turns a draw u in (0, 1] into a threshold -- logit(u) for a column
+ * trained with the Bernoulli likelihood, u itself for one in 0 / 1 target units -- so a branch whose column says p ends with
+ * probability p (u = 1 gives +inf under the logit: a probability of exactly 0 never ends a branch).
+ * cmbpo_fakeenv_post_cost's arguments plus the thresholds: the superset, every feature optional.  d_term_thr == NULL is exactly
+ * cmbpo_fakeenv_post_cost's call (the same kernel instances with the same argument block).  Beside its checks: d_term_thr != NULL
+ * needs th != NULL -- refused with a message naming the draws, before any HIP call. */
+int cmbpo_fakeenv_post_term_draws(int task, int ensemble, int obs_dim, int act_dim,
+                                  const float *d_mean, const float *d_var, int ld_rows,
+                                  const float *d_obs, const float *d_act,
+                                  const int32_t *d_elite, const int32_t *d_row_idx,
+                                  const int32_t *d_n_rows, int n_rows, float *d_next_obs,
+                                  float *d_rew, uint8_t *d_term, float *d_cost,
+                                  float *d_dkl_path, float *d_ep_var_mean,
+                                  float *d_ep_var, const float *d_xi,
+                                  float kappa_rew, float kappa_cost,
+                                  float *d_rew_var, float *d_cost_var,
+                                  const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch,
+                                  const float *d_term_thr, void *stream);
+
 /* ------------------------------------------------------------------------ *
  * Device-resident rollout state: the fused counterpart of ModelSampler
  * (samplers/model_sampler.py:203-444) + ModelBuffer (buffers/modelbuffer.py).
@@ -649,6 +675,13 @@ int cmbpo_rollout_value_disagreement_detach(const cmbpo_rollout_t *r);
 int cmbpo_rollout_term_head_attach(const cmbpo_rollout_t *r, const cmbpo_term_head_t *th);
 /* Back to the rules alone (no error when nothing was attached). */
 int cmbpo_rollout_term_head_detach(const cmbpo_rollout_t *r);
+/* Sampled terminations along imagined rollouts: {d_thr, step_stride} travels in the same table.  Attached, cmbpo_rollout_step /
+ * _run post-process with cmbpo_fakeenv_post_term_draws: cmbpo_rollout_step reads d_thr, step j of a cmbpo_rollout_run call reads
+ * d_thr + j * step_stride (floats; as the run reads xi + j * xi_stride).  d_thr: [B] per step, slot indexed, owned by the caller,
+ * valid until the detach; d_thr == NULL detaches (no error when nothing was attached).  Draws attached without a termination
+ * head are refused (-1) before the first launch of a step, with a message naming both.  Nothing else of a step or of the native
+ * loop changes.  Checked here: the struct, and step_stride >= 0. */
+int cmbpo_rollout_term_draws_attach(const cmbpo_rollout_t *r, const float *d_thr, long step_stride);
 
 /* The cost head's reading along imagined rollouts: a copy of *ch travels beside an unchanged cmbpo_rollout_t in the same table.
  * Attached, cmbpo_rollout_step / _run post-process with cmbpo_fakeenv_post_cost (with whatever else is attached), so cost_t --
