@@ -1,5 +1,6 @@
 // The policy kernels with every matrix product as three f16 MFMAs on two-piece operands (f16_split.h); included by
-// policy_update.hip inside its anonymous namespace, after PiArgs / PiPack / the row-tile helpers.
+// policy_update.hip inside its anonymous namespace, after PiArgs / PiPack / the row-tile helpers and pi_elem.h (what it shares
+// with pi_kernel outside the matrix products).
 //
 // Same tiling as pi_kernel (one persistent workgroup walks tiles of 32 samples, wave w owns hidden units 32 w .. 32 w + 31,
 // weight gradients stay in registers across tiles), same results to fp32 rounding, ~3 x fewer MFMA cycles:
@@ -303,9 +304,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
   static_assert(ST::tab.L == (MODE == MODE_EVAL ? P_WF2 + 2 : P_WB1 + 8), "stream positions");
 
   extern __shared__ f32x4 smem4[];
-  if constexpr (MODE == MODE_PPO) {
-    if ((p.ppo_flags & PPO_GATED) && p.state[ST_STOP] != 0.0) return;     // the loop's gate has stopped it (uniform: one scalar load, one branch)
-  }
+  if (pi_ppo_stopped<MODE>(p)) return;
   const PiDims d = p.d;
   float *sm = reinterpret_cast<float *>(smem4);
   float *xR = sm;                       // [BB][XS] fp32
@@ -347,13 +346,8 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
   double s_obj = 0;     // MODE_PPO: the clipped objective ...
   int s_nclip = 0;      // ... and the samples whose advantage term is clipped away
   float s_clipw = 0.0f; // (WT: their weights; one thread adds a few hundred at most)
-  float ppo_cr = 1.0f, ppo_cc = 0.0f;
-  if constexpr (MODE == MODE_PPO) {
-    if (p.ppo_flags & PPO_PENALIZED) {
-      ppo_cr = (float)p.state[ST_CR];
-      ppo_cc = (float)p.state[ST_CC];
-    }
-  }
+  float ppo_cr, ppo_cc;
+  pi_ppo_coeffs<MODE>(p, ppo_cr, ppo_cc);
   Ring R;
   ring_fill<ST>(R, imgs, tid0 & 63);
   __shared__ unsigned s_mx[2][4];    // per tile parity: largest |x|, |cotangent|, |dh2|, |delta1| (float bits)
@@ -365,11 +359,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
   }
   const float bnd_c = (float)d.A * p.w.mx[2];   // |delta2| <= max |cot| A max |W2|
 
-  // zero the padded cotangent columns (a in [A, 36)) and the padded input columns (k in [D, XS)) once: nothing else
-  // ever writes them
-  for (int i = tid0; i < BB * 36; i += kThreads) wR[i] = 0.0f;
-  for (int i = tid0; i < BB * XS; i += kThreads) xR[i] = 0.0f;
-  __syncthreads();
+  pi_zero_pads<kThreads>(wR, xR, XS, tid0);
 
   // the tile's observations: fetched one tile ahead into registers (N_IT == 1), see pi_kernel
   constexpr bool PRE = (N_IT == 1);
@@ -386,13 +376,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
   };
   if ((int)blockIdx.x < n_tiles) fetch_x(blockIdx.x, tid0);
   __shared__ float c_b2[32], c_e2[32];
-  if constexpr (MODE == MODE_FVP) {
-    if (tid0 < 32) {
-      c_b2[tid0] = (tid0 < d.A) ? p.v.b2[tid0] : 0.0f;
-      c_e2[tid0] = (tid0 < d.A) ? 2.0f * expf(2.0f * p.w.ls[tid0]) : 0.0f;
-    }
-    __syncthreads();
-  }
+  pi_fisher_consts<MODE>(p, d, c_b2, c_e2, tid0);
 
   // saved activations: a tile's block [h1 image | h2 rows] travels global -> LDS by LDS-DMA (one wave-instruction = 64 lanes x
   // 16 B = 1 KiB, destination = wave-uniform base + 16 lane), requested as soon as the previous tile has no reader of the
@@ -418,7 +402,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
   auto fetch_lso = [&](int t, int tid) {
     const int er0 = t * BB + (tid & 31), a0 = tid >> 5;
     lso_pre = (er0 < p.n && a0 < d.A) ? p.ls_old[(size_t)er0 * d.A + a0] : 0.0f;
-    if constexpr (WT && !CMBPO_PI_WT_LATE) w_pre = (er0 < p.n) ? p.wt[er0] : 0.0f;
+    if constexpr (WT) w_pre = (er0 < p.n) ? p.wt[er0] : 0.0f;
   };
   if constexpr (ACT_DMA) {
     if ((int)blockIdx.x < n_tiles) fetch_lso(blockIdx.x, tid0);
@@ -469,7 +453,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
     {
       const int er0 = row0 + (tid & 31), a0 = tid >> 5;
       if (er0 < p.n) {
-        if constexpr (WT && !CMBPO_PI_WT_LATE && !ACT_DMA) e_w = p.wt[er0];
+        if constexpr (WT && !ACT_DMA) e_w = p.wt[er0];
         if constexpr (MODE != MODE_FVP) {
           e_logp = p.logp_old[er0];
           e_adv = p.adv[er0];
@@ -490,7 +474,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
       // the first tile) and has had the rest of that tile and this tile's staging to arrive: THIS barrier publishes it (the
       // barrier that ends a tile, a few hundred cycles after the request, waited ~14 % of a tile for it)
       lso0 = lso_pre;
-      if constexpr (WT && !CMBPO_PI_WT_LATE) e_w = w_pre;
+      if constexpr (WT) e_w = w_pre;
       __syncthreads();
       asm volatile("" ::"v"(warm));   // the previous tile's warm-up load must be issued, its value is not used
       t_x = pow2_lift(__uint_as_float(mx[0]));
@@ -611,7 +595,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
     const int eb = tid & 31, er = row0 + eb;
     const bool valid = er < p.n;
     float sw = 1.0f;      // WT: the weight of sample er (0 past the batch end)
-    if constexpr (WT) sw = CMBPO_PI_WT_LATE ? (valid ? p.wt[er] : 0.0f) : e_w;
+    if constexpr (WT) sw = e_w;
     float z_[4], mu_[4];
     float cmax = 0.0f;      // largest |cotangent| this thread writes
 #pragma unroll
@@ -825,30 +809,7 @@ __global__ __launch_bounds__(kThreads, 2) void pi_kernel_h(const PiArgs p) {
     }
   }
   if constexpr (MODE != MODE_FVP) {
-    // tid < 32 hold the per-sample sums; s_kl is spread over every thread
     __shared__ double sd[4];
-    const double kl = wave_sum(s_kl);
-    if (lane == 0) sd[wave] = kl;
-    __syncthreads();
-    if (wave == 0) {
-      const double n = wave_sum(s_n), ra = wave_sum(s_ra), rc = wave_sum(s_rc), c = wave_sum(s_cost);
-      if constexpr (MODE == MODE_PPO) {
-        const double ob = wave_sum(s_obj), nc = wave_sum(WT ? (double)s_clipw : (double)s_nclip);
-        const double wsum = WT ? wave_sum(tile_walk_weights(p.wt, p.n, n_tiles, lane)) : 0.0;
-        if (lane == 0) {
-          double *sp = p.sums_part + (size_t)blockIdx.x * 8;
-          int rows = 0;
-          if constexpr (!WT)
-            for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) rows += min(BB, p.n - t * BB);
-          sp[0] = WT ? wsum : (double)rows; sp[1] = ob; sp[2] = rc; sp[3] = sd[0] + sd[1] + sd[2] + sd[3]; sp[4] = c; sp[5] = nc; sp[6] = ra; sp[7] = 0.0;
-        }
-      } else if (lane == 0) {
-        atomicAdd(&p.sums[0], n);
-        atomicAdd(&p.sums[1], ra);
-        atomicAdd(&p.sums[2], rc);
-        atomicAdd(&p.sums[3], sd[0] + sd[1] + sd[2] + sd[3]);
-        atomicAdd(&p.sums[4], c);
-      }
-    }
+    pi_flush_sums<MODE, WT, 4>(p, sd, n_tiles, lane, wave, s_n, s_ra, s_rc, s_kl, s_cost, s_obj, s_nclip, s_clipw);
   }
 }

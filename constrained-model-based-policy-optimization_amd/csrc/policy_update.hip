@@ -97,40 +97,7 @@ struct PiArgs {
   const float *wt;        // [n] per-sample weights (cmbpo_pi_set_sample_weights) or NULL
 };
 
-// Where a weighted instantiation requests its sample's weight: with e_logp at the top of the tile (the load's latency passes
-// behind the forward chain, one VGPR stays live across it) or in the element phase, where it is first used.
-#ifndef CMBPO_PI_WT_LATE
-#define CMBPO_PI_WT_LATE 0
-#endif
-
-// the per-sample weight of the clipped, penalised surrogate's cotangent, and what the sample adds to the objective:
-//   min_adv = adv > 0 ? (1 + clip) adv : (1 - clip) adv;  active = !clipped || ratio adv <= min_adv   (positive test: a NaN
-//   ratio is inactive; on a tie the first argument of the minimum is the active one, as in tf.minimum)
-//   w = -c_r (active ? adv : 0) + c_c cadv
-__device__ __forceinline__ float ppo_weight(float ratio, float adv, float cadv, float clip, bool clipped, float c_r, float c_c,
-                                            float &obj, bool &active) {
-  const float ra = ratio * adv;
-  const float min_adv = adv > 0.0f ? (1.0f + clip) * adv : (1.0f - clip) * adv;
-  active = !clipped || (ra <= min_adv);
-  obj = active ? ra : min_adv;
-  return -c_r * (active ? adv : 0.0f) + c_c * cadv;
-}
-
-// MODE_PPO with weights: this lane's share of the weights of the workgroup's tiles (a second walk over them, behind the tile
-// loop, where it costs no register: the rows can be counted from the tile walk, their weights cannot)
-__device__ __forceinline__ double tile_walk_weights(const float *wt, int n, int n_tiles, int lane) {
-  double s = 0.0;
-  for (int t = blockIdx.x + (lane >> 5) * gridDim.x; t < n_tiles; t += 2 * gridDim.x) {
-    const int r = t * BB + (lane & 31);
-    if (r < n) s += (double)wt[r];
-  }
-  return s;
-}
-
-// one (sample, action) term of gaussian_kl(mu, log_std, mu_old, log_std_old), ac_network.py:50-55; dm = mu_old - mu
-__device__ __forceinline__ float gauss_kl_term(float dm, float ls, float lso) {
-  return 0.5f * ((dm * dm + expf(2.0f * ls)) / (expf(2.0f * lso) + 1e-8f) - 1.0f) + lso - ls;
-}
+#include "pi_elem.h"
 
 // ---- packing (device side, so set_params / FVP directions never visit the host) -------------------
 // One launch packs every piece of a flat parameter vector.  Matrix pieces:
@@ -268,12 +235,10 @@ template <int MODE, int N_IT, int HIDT, bool WT = false>
 __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const PiArgs p) {
   // HIDT = the hidden width (128: the shipped policies; 256: configs/baseconfig/base.py's default): a wave per 32 hidden
   // units, 2 HIDT threads, images of HIDT + pad floats a row
-  constexpr int kThreads = 2 * HIDT, HID = HIDT, KGH = HIDT / 8, RS = pi_rs(HIDT), NW = HIDT / 32;
-  constexpr int AS = kThreads / 32, NITE = 32 / AS;     // element phase: a = tid / 32 + AS it, it < NITE
+  constexpr int NTHR = 2 * HIDT, KGH = HIDT / 8, RS = pi_rs(HIDT), NW = HIDT / 32;
+  constexpr int AS = NTHR / 32, NITE = 32 / AS;     // element phase: a = tid / 32 + AS it, it < NITE
   extern __shared__ f32x4 smem4[];
-  if constexpr (MODE == MODE_PPO) {
-    if ((p.ppo_flags & PPO_GATED) && p.state[ST_STOP] != 0.0) return;     // the loop's gate has stopped it (uniform: one scalar load, one branch)
-  }
+  if (pi_ppo_stopped<MODE>(p)) return;
   const PiDims d = p.d;
   float *sm = reinterpret_cast<float *>(smem4);
   const int XS = d.in_pad + 4;
@@ -293,7 +258,7 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 31, h = lane >> 5;
   const int n_tiles = (p.n + BB - 1) / BB;
-  constexpr int IMG4 = BB * HID / 4;    // float4s of one dense [32][128] activation image
+  constexpr int IMG4 = BB * HIDT / 4;   // float4s of one dense [32][HIDT] activation image
   const bool cached = (MODE == MODE_FVP) && p.cache_r != nullptr;
 
   // persistent accumulators
@@ -309,19 +274,9 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
   double s_obj = 0;     // MODE_PPO: the clipped objective ...
   int s_nclip = 0;      // ... and the samples whose advantage term is clipped away
   float s_clipw = 0.0f; // (WT: their weights; one thread adds a few hundred at most)
-  float ppo_cr = 1.0f, ppo_cc = 0.0f;
-  if constexpr (MODE == MODE_PPO) {
-    if (p.ppo_flags & PPO_PENALIZED) {
-      ppo_cr = (float)p.state[ST_CR];
-      ppo_cc = (float)p.state[ST_CC];
-    }
-  }
-
-  // zero the padded cotangent columns (a in [A, 36)) and the padded input columns (k in [D, in_pad)) once: nothing
-  // else ever writes them
-  for (int i = tid; i < BB * 36; i += kThreads) wR[i] = 0.0f;
-  for (int i = tid; i < BB * XS; i += kThreads) xR[i] = 0.0f;
-  __syncthreads();
+  float ppo_cr, ppo_cc;
+  pi_ppo_coeffs<MODE>(p, ppo_cr, ppo_cc);
+  pi_zero_pads<NTHR>(wR, xR, XS, tid);
 
   // The tile's observations are one contiguous block of 32 D floats: each thread keeps its <= 4 N_IT of them in
   // registers, fetched one tile ahead (behind the weight-gradient MFMAs), so that staging never waits for HBM.
@@ -334,20 +289,13 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     const int lim = min(BB, p.n - t * BB) * d.D;      // rows past the batch end read as zeros
 #pragma unroll
     for (int q = 0; q < 4 * N_IT; ++q) {
-      const int i = tid + q * kThreads;
+      const int i = tid + q * NTHR;
       xpre[q] = (i < lim) ? p.obs[base + i] : 0.0f;
     }
   };
   if ((int)blockIdx.x < n_tiles) fetch_x(blockIdx.x);
-  // Fisher cotangent: its tile-invariant factors per action column, computed once (LDS: no registers to spare)
   __shared__ float c_b2[32], c_e2[32];
-  if constexpr (MODE == MODE_FVP) {
-    if (tid < 32) {
-      c_b2[tid] = (tid < d.A) ? p.v.b2[tid] : 0.0f;
-      c_e2[tid] = (tid < d.A) ? 2.0f * expf(2.0f * p.w.ls[tid]) : 0.0f;
-    }
-    __syncthreads();
-  }
+  pi_fisher_consts<MODE>(p, d, c_b2, c_e2, tid);
 
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int row0 = tile * BB;
@@ -355,14 +303,14 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     if constexpr (PRE) {
 #pragma unroll
       for (int q = 0; q < 4 * N_IT; ++q) {
-        const int i = tid + q * kThreads;
+        const int i = tid + q * NTHR;
         if (i < BB * d.D) {
           const int b = i / d.D, k = i - b * d.D;
           xR[b * XS + k] = xpre[q];
         }
       }
     } else {
-      for (int i = tid; i < BB * d.D; i += kThreads) {
+      for (int i = tid; i < BB * d.D; i += NTHR) {
         const int b = i / d.D, k = i - b * d.D;
         xR[b * XS + k] = (row0 + b < p.n) ? p.obs[(size_t)row0 * d.D + i] : 0.0f;
       }
@@ -378,7 +326,7 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     {
       const int er0 = row0 + (tid & 31), a0 = tid >> 5;
       if (er0 < p.n) {
-        if constexpr (WT && !CMBPO_PI_WT_LATE) e_w = p.wt[er0];
+        if constexpr (WT) e_w = p.wt[er0];
         if constexpr (MODE != MODE_FVP) {
           e_logp = p.logp_old[er0];
           e_adv = p.adv[er0];
@@ -399,12 +347,12 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
       f32x4 t1[4], t2[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        t1[i] = src[tid + kThreads * i];
-        t2[i] = src[IMG4 + tid + kThreads * i];
+        t1[i] = src[tid + NTHR * i];
+        t2[i] = src[IMG4 + tid + NTHR * i];
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int idx = tid + kThreads * i, b = idx / (HID / 4), c = idx % (HID / 4);
+        const int idx = tid + NTHR * i, b = idx / (HIDT / 4), c = idx % (HIDT / 4);
         reinterpret_cast<f32x4 *>(h1R)[b * (RS / 4) + c] = t1[i];
         reinterpret_cast<f32x4 *>(h2R)[b * (RS / 4) + c] = t2[i];
       }
@@ -435,7 +383,7 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
           f32x4 *dst = p.cache_w + (size_t)tile * (2 * IMG4);
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            const int idx = tid + kThreads * i, b = idx / (HID / 4), c = idx % (HID / 4);
+            const int idx = tid + NTHR * i, b = idx / (HIDT / 4), c = idx % (HIDT / 4);
             dst[idx] = h1R4[b * (RS / 4) + c];
             dst[IMG4 + idx] = h2R4[b * (RS / 4) + c];
           }
@@ -487,9 +435,8 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     const int eb = tid & 31, er = row0 + eb;
     const bool valid = er < p.n;
     float sw = 1.0f;      // WT: the weight of sample er (0 past the batch end)
-    if constexpr (WT) sw = CMBPO_PI_WT_LATE ? (valid ? p.wt[er] : 0.0f) : e_w;
+    if constexpr (WT) sw = e_w;
     float z_[NITE], mu_[NITE];
-    float logp_part = 0.0f;
 #pragma unroll
     for (int it = 0; it < NITE; ++it) {
       const int a = (tid >> 5) + AS * it;
@@ -538,7 +485,7 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     }
     if constexpr (MODE != MODE_FVP) {
       __syncthreads();
-      float logp = logp_part;
+      float logp = 0.0f;
       for (int a = 0; a < d.A; ++a) logp += wR[eb * 36 + a];
       const float ratio = valid ? expf(logp - e_logp) : 0.0f;                // cpo_policy.py:522
       // (zero past the batch end)  WT: the weight rides in the advantages -- every term below is linear in them, the clip
@@ -633,8 +580,8 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     for (int t = 0; t < N_IT; ++t) wgrad_tile(gW0[t], xR, XS, 32 * t, d1R, RS, wave * 32, lane);
     {
       // bias gradients: column sums over the tile's samples (conflict-free: adjacent threads, adjacent columns)
-      const float *img = (tid < HID) ? d2R : d1R;
-      const int n = tid & (HID - 1);
+      const float *img = (tid < HIDT) ? d2R : d1R;
+      const int n = tid & (HIDT - 1);
       float sb = 0.0f;
 #pragma unroll 8
       for (int b = 0; b < BB; ++b) sb += img[b * RS + n];
@@ -651,13 +598,13 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     for (int r = 0; r < 16; ++r) {
       const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
 #pragma unroll
-      for (int J = 0; J < NW; ++J) part[d.oW1 + (wave * 32 + row) * HID + J * 32 + j] = gW1[J][r];
+      for (int J = 0; J < NW; ++J) part[d.oW1 + (wave * 32 + row) * HIDT + J * 32 + j] = gW1[J][r];
 #pragma unroll
       for (int t = 0; t < N_IT; ++t)
-        if (32 * t + row < d.D) part[d.oW0 + (32 * t + row) * HID + wave * 32 + j] = gW0[t][r];
+        if (32 * t + row < d.D) part[d.oW0 + (32 * t + row) * HIDT + wave * 32 + j] = gW0[t][r];
       if (j < d.A) part[d.oW2 + (wave * 32 + row) * d.A + j] = gW2[r];
     }
-    part[(tid < HID ? d.ob1 : d.ob0) + (tid & (HID - 1))] = gbias;
+    part[(tid < HIDT ? d.ob1 : d.ob0) + (tid & (HIDT - 1))] = gbias;
 #pragma unroll
     for (int it = 0; it < NITE; ++it) {
       const int a = (tid >> 5) + AS * it;
@@ -670,37 +617,8 @@ __global__ __launch_bounds__(2 * HIDT, HIDT == 128 ? 2 : 1) void pi_kernel(const
     }
   }
   if constexpr (MODE != MODE_FVP) {
-    // tid < 32 hold the per-sample sums; s_kl is spread over every thread
     __shared__ double sd[NW];
-    const double kl = wave_sum(s_kl);
-    if (lane == 0) sd[wave] = kl;
-    __syncthreads();
-    if (wave == 0) {
-      const double n = wave_sum(s_n), ra = wave_sum(s_ra), rc = wave_sum(s_rc), c = wave_sum(s_cost);
-      if constexpr (MODE == MODE_PPO) {
-        const double ob = wave_sum(s_obj), nc = wave_sum(WT ? (double)s_clipw : (double)s_nclip);
-        const double wsum = WT ? wave_sum(tile_walk_weights(p.wt, p.n, n_tiles, lane)) : 0.0;
-        if (lane == 0) {
-          double klt = sd[0];
-#pragma unroll
-          for (int wv = 1; wv < NW; ++wv) klt += sd[wv];
-          double *sp = p.sums_part + (size_t)blockIdx.x * 8;
-          int rows = 0;
-          if constexpr (!WT)
-            for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) rows += min(BB, p.n - t * BB);
-          sp[0] = WT ? wsum : (double)rows; sp[1] = ob; sp[2] = rc; sp[3] = klt; sp[4] = c; sp[5] = nc; sp[6] = ra; sp[7] = 0.0;
-        }
-      } else if (lane == 0) {
-        atomicAdd(&p.sums[0], n);
-        atomicAdd(&p.sums[1], ra);
-        atomicAdd(&p.sums[2], rc);
-        double klt = sd[0];
-#pragma unroll
-        for (int wv = 1; wv < NW; ++wv) klt += sd[wv];
-        atomicAdd(&p.sums[3], klt);
-        atomicAdd(&p.sums[4], c);
-      }
-    }
+    pi_flush_sums<MODE, WT, NW>(p, sd, n_tiles, lane, wave, s_n, s_ra, s_rc, s_kl, s_cost, s_obj, s_nclip, s_clipw);
   }
 }
 

@@ -4,7 +4,7 @@ source file whose demangled name matches a regular expression), as the compiler 
 (-Rpass-analysis=kernel-resource-usage, the build's flags, no GPU needed), for several trees side by side.
 
     python tools/pi_kernel_resources.py --tree parent=/path/to/parent/checkout --tree tree=. \
-        --tree tree_wt_late=.:-DCMBPO_PI_WT_LATE=1 --out profiles/r10/kernel_resources_policy_weights.tsv
+        --out profiles/r25/kernel_resources_pi.tsv
 
 A tree is `label=checkout[:extra flag]`.  One row per (instantiation, tree); the last template argument says whether the
 instantiation takes sample weights (a tree from before the weights has only `false` rows).  Every row of the first tree must
