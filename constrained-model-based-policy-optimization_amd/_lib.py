@@ -394,6 +394,26 @@ SIGNATURES.update({
     "cmbpo_replay_run_cost": (_i, [_pp, _cpp, _tp, _chp, _p, _i, _i, _p, _p]),
 })
 
+# reliability tables of the logistic columns in the replay: per (column, reading) 2 K + 2 float64 sums and 2 K int64 counts
+RELIAB_COST, RELIAB_TERM = 0, 1                                   # CMBPO_RELIAB_COST / _TERM: the recorded flag of a column
+RELIAB_MAX_BINS, RELIAB_MAX_COLS, RELIAB_MAX_ENSEMBLE = 32, 2, 8  # CMBPO_RELIAB_MAX_*
+RELIAB_TARGETS = {"cost": RELIAB_COST, "term": RELIAB_TERM}
+
+
+class ReplayReliabStruct(C.Structure):
+    """ctypes image of ``cmbpo_replay_reliab_t`` (104 bytes), field for field."""
+    _fields_ = [(n, C.c_int32) for n in ("ensemble", "out_dim", "n_bins", "n_cols", "reserved")] + \
+               [("col", C.c_int32 * 2), ("target", C.c_int32 * 2), ("shift", C.c_float * 2)] + \
+               [(n, C.c_void_p) for n in ("elite", "edges", "term", "part_sum", "part_cnt", "sums", "counts")]
+
+
+_rrp = C.POINTER(ReplayReliabStruct)
+SIGNATURES.update({
+    "cmbpo_replay_reliab": (_i, [_pp, _rrp, _i, _p]),
+    "cmbpo_replay_reliab_finish": (_i, [_pp, _rrp, _p]),
+    "cmbpo_replay_run_reliab": (_i, [_pp, _cpp, _rrp, _tp, _chp, _p, _i, _i, _p, _p]),
+})
+
 _lib = None
 
 

@@ -92,6 +92,19 @@ targets, 'balanced' by the termination head's rule on each fit's cost targets an
 (``FakeEnv.set_cost_head(logit_shift=)``), which undoes what the weight did to the fitted level.  ``save`` / ``load`` keep all of
 it in ``cost_loss_<epoch>.json`` (a missing file means 'gaussian').
 
+``m_validate_reliability=True`` (needs ``m_validate_horizon > 0`` and a logistic head, ``m_cost_loss`` or ``m_term_loss``; DESIGN
+§3z) has the validation replay also measure whether each logistic column is a PROBABILITY: a reliability table per column in
+``m_reliability_bins`` bins (``last_validation['reliability']``) and from its one-step row ``model/val_ece_cost_h1`` /
+``val_ece_term_h1``, ``val_logloss_*_h1``, ``val_base_rate_*_h1``, ``val_mean_p_*_h1`` (the elite reading) and
+``val_rel_skipped``.  It reads and does not steer.  ``m_recalibrate_cost=True`` (needs it and ``m_cost_loss='logistic'``) and
+``m_recalibrate_term=True`` (needs it, ``m_term_loss='logistic'`` and ``m_term_sampling=True``) feed the one-step result back
+after every validation: the logit offset that makes the column's mean probability the observed rate
+(``replay.logit_offset``, clipped to ``m_recalibration_range``) goes into the imagined cost
+(``FakeEnv.set_cost_recalibration``; ``model/cost_recal_offset``) and into the sampled termination thresholds
+(``ModelSampler.set_term_logit_offset``; ``model/term_recal_offset``).  The offset is set absolutely each time and the table is
+always measured without it.  ``save`` / ``load`` keep the switches and the two offsets in ``recalibration_<epoch>.json`` (a
+missing file means off, offsets 0).
+
 ``static_fns`` takes a ``statics.TaskRules``: user-defined termination / cost rules for the imagined rollouts, with
 precedence over ``task`` (which may itself be a name given to ``statics.register_task``).
 """
@@ -163,6 +176,38 @@ def _calibration_args(validate_horizon, use_model, stochastic, validate_calibrat
     if not (0.0 < lo <= hi and np.isfinite(hi)):
         raise ValueError("m_noise_temperature_range: 0 < lo <= hi < inf expected, got %r" % (temperature_range,))
     return validate_calibration, calibrated_noise, (lo, hi)
+
+
+def _reliability_args(validate_horizon, use_model, cost_loss, term_loss, term_sampling, validate_reliability, bins, recalibrate_cost,
+                      recalibrate_term, recalibration_range):
+    """The five reliability arguments of ``CMBPO`` checked against the heads they measure, or a ValueError in words:
+    (validate_reliability, bins, recalibrate_cost, recalibrate_term, (lo, hi))."""
+    logistic = cost_loss == 'logistic' or term_loss == 'logistic'
+    if validate_reliability:
+        if not (int(validate_horizon) > 0 and use_model):
+            raise ValueError("m_validate_reliability needs m_validate_horizon > 0 (and use_model): it is measured in the validation replay")
+        if not logistic:
+            raise ValueError("m_validate_reliability needs a logistic head (m_cost_loss='logistic' or m_term_loss='logistic'): a "
+                             "Gaussian column is not a logit, it has no reliability table")
+    try:
+        bins = int(bins)
+    except (TypeError, ValueError):
+        raise ValueError("m_reliability_bins: an integer in 1..32, got %r" % (bins,))
+    if not 1 <= bins <= 32:
+        raise ValueError("m_reliability_bins: an integer in 1..32, got %r" % (bins,))
+    if recalibrate_cost and not (validate_reliability and cost_loss == 'logistic'):
+        raise ValueError("m_recalibrate_cost needs m_validate_reliability=True and m_cost_loss='logistic': the offset is derived "
+                         "from the cost column's reliability table")
+    if recalibrate_term and not (validate_reliability and term_loss == 'logistic' and term_sampling):
+        raise ValueError("m_recalibrate_term needs m_validate_reliability=True, m_term_loss='logistic' and m_term_sampling=True: "
+                         "the offset is derived from the termination column's reliability table and shifts the sampled thresholds")
+    try:
+        lo, hi = (float(x) for x in recalibration_range)
+    except (TypeError, ValueError):
+        raise ValueError("m_recalibration_range: a pair (lo, hi), got %r" % (recalibration_range,))
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+        raise ValueError("m_recalibration_range: finite lo <= hi expected, got %r" % (recalibration_range,))
+    return bool(validate_reliability), bins, bool(recalibrate_cost), bool(recalibrate_term), (lo, hi)
 
 
 def _term_sampling_args(learn_term, term_sampling):
@@ -265,6 +310,9 @@ class CMBPO:
     """Constrained Model-Based Policy Optimization (``algorithms/cmbpo.py:30``)."""
     # the reading of the cost column (DESIGN 3w) where the constructor has not set it: a magnitude, no class weight
     _m_cost_loss, _cost_pos_weight, _cost_pos_weight_undo = 'gaussian', 1.0, False
+    # reliability of the logistic columns (DESIGN 3z) where the constructor has not set it: off
+    _validate_reliability, _reliability_bins, _recalibrate_cost, _recalibrate_term = False, 15, False, False
+    _recalibration_range = (-2.0, 2.0)
 
     def __init__(self, env, policy, buffer, sampler=None, task='default', static_fns=None, n_env_interacts=1e7,
                  eval_every_n_steps=5e3, use_model=True, m_learn_cost=False, m_train_freq=250, m_loss_type='MSPE',
@@ -282,7 +330,8 @@ class CMBPO:
                  m_learn_term=False, m_term_threshold=0.5, m_term_members='elite',
                  m_term_pos_weight=1.0, m_term_loss_weight=1.0, m_cost_loss_weight=1.0, m_pos_weight_max=20.0,
                  m_term_loss='gaussian', m_cost_loss='gaussian', m_cost_pos_weight=1.0, m_cost_pos_weight_undo=False,
-                 m_term_sampling=False, **_unused):
+                 m_term_sampling=False, m_validate_reliability=False, m_reliability_bins=15, m_recalibrate_cost=False,
+                 m_recalibrate_term=False, m_recalibration_range=(-2.0, 2.0), **_unused):
         # column / class weights of the model's binary columns; refused in words before anything is built
         self._column_weights = _column_weight_args(bool(m_learn_term) and bool(use_model), bool(m_learn_cost), m_term_pos_weight,
                                                    m_term_loss_weight, m_cost_loss_weight, m_pos_weight_max)
@@ -297,6 +346,12 @@ class CMBPO:
         # noise; refused in words before anything is built
         self._validate_calibration, self._calibrated_noise, self._noise_temperature_range = _calibration_args(
             m_validate_horizon, use_model, m_stochastic, m_validate_calibration, m_calibrated_noise, m_noise_temperature_range)
+        # reliability tables of the logistic columns in the validation replay and, from their one-step row, the logit offsets of
+        # the imagined cost and the sampled terminations; likewise
+        (self._validate_reliability, self._reliability_bins, self._recalibrate_cost, self._recalibrate_term,
+         self._recalibration_range) = _reliability_args(
+            m_validate_horizon, use_model, self._m_cost_loss, self._m_term_loss, self._m_term_sampling, m_validate_reliability,
+            m_reliability_bins, m_recalibrate_cost, m_recalibrate_term, m_recalibration_range)
         # RLAlgorithm.__init__ (algorithms/rl_algorithm.py:22-74)
         self.sampler = sampler if sampler is not None else CpoSampler(max_path_length=getattr(policy, "max_path_length", 1000))
         self._n_epochs, self._epoch_length = n_epochs, epoch_length
@@ -510,8 +565,17 @@ class CMBPO:
             raise ValueError("validate_model: pass horizon >= 1 (the trainer was built with m_validate_horizon=0)")
         if self._validate_rng is None:
             self._validate_rng = np.random.default_rng(0x76616c)
-        _, _, win = self._buffer.windows(H, int(n_windows or self._validate_windows), epochs=epochs, rng=self._validate_rng)
-        tab = self.fake_env.replay(**win, calibration=True) if self._validate_calibration else self.fake_env.replay(**win)
+        start, length, win = self._buffer.windows(H, int(n_windows or self._validate_windows), epochs=epochs, rng=self._validate_rng)
+        # (every switch that is off is left out of the call: the call of a trainer that never heard of it)
+        kw = {'calibration': True} if self._validate_calibration else {}
+        if self._validate_reliability:
+            kw.update(reliability=True, reliability_bins=self._reliability_bins)
+            if self._m_learn_term and self._m_term_loss == 'logistic':
+                # the windows carry the recorded `done`; the column was trained on term_targets, where a time-out is 0: the
+                # table is held against the training target, the same steps of the same windows
+                idx = start[None, :] + np.minimum(np.arange(H)[:, None], length[None, :] - 1)
+                kw.update(reliability_terminals=self._buffer.term_targets(self.sampler.max_path_length)[idx])
+        tab = self.fake_env.replay(**win, **kw)
         self.last_validation = tab
         ratio = lambda a, b: float(a) / float(b) if b > 0 else float('nan')
         cm, tm = tab['cost_cm'].sum(axis=0), tab['term_cm'].sum(axis=0)      # [real, predicted], all horizons
@@ -531,6 +595,8 @@ class CMBPO:
                     self.model_sampler.set_noise_scale(np.sqrt(temperature(cal, 'al', 0, *self._noise_temperature_range)))
                 scale = self.model_sampler.noise_scale
                 extra['noise_scale_mean'] = 1.0 if scale is None else float(np.mean(scale))
+        if self._validate_reliability:
+            extra.update(self._reliability_diagnostics(tab['reliability']))
         if self._m_learn_term:
             # the head at h = 1, the one-step row: the share of real terminations it reports, of continuing steps it ends
             t1 = tab['term_cm'][0]
@@ -545,6 +611,28 @@ class CMBPO:
                 'val_term_false_rate': ratio(tm[0, 1], tm[0, 0] + tm[0, 1]),
                 'val_epvar_over_mse_hH': ratio(tab['ep_var_mean'][last], np.mean(tab['mse_obs'][last])),
                 'val_nonfinite': int(tab['n_nonfinite'].sum())}
+
+    def _reliability_diagnostics(self, rel):
+        """The one-step row of the reliability tables (the elite reading) as ``val_*`` entries and, with the recalibration
+        switches, the offsets derived from it: set absolutely (the table is measured without them, so nothing winds up), kept
+        where fewer than 100 rows entered."""
+        from .replay import logit_offset
+        out = {'val_rel_skipped': int(sum(col['n_skipped'].sum() for col in rel.values()))}
+        for name, col in rel.items():
+            d = col['elite']
+            out.update({'val_ece_%s_h1' % name: float(d['ece'][0]), 'val_logloss_%s_h1' % name: float(d['logloss'][0]),
+                        'val_base_rate_%s_h1' % name: float(d['base_rate'][0]), 'val_mean_p_%s_h1' % name: float(d['mean_p'][0])})
+        if self._recalibrate_cost:
+            b = logit_offset(rel, 'cost', 'elite', 0, *self._recalibration_range)
+            if b is not None:
+                self.fake_env.set_cost_recalibration(b)
+            out['cost_recal_offset'] = float(self.fake_env.cost_recalibration)
+        if self._recalibrate_term:
+            b = logit_offset(rel, 'term', 'elite', 0, *self._recalibration_range)
+            if b is not None:
+                self.model_sampler.set_term_logit_offset(b)
+            out['term_recal_offset'] = float(self.model_sampler.term_logit_offset or 0.0)
+        return out
 
     def _set_rollout_length(self):
         """algorithms/cmbpo.py:494-512"""
@@ -748,6 +836,49 @@ class CMBPO:
                 with open(os.path.join(savedir, 'column_weights_%d.json' % self._epoch), 'w') as fh:
                     json.dump(self._column_weights, fh)
 
+            if self._m_learn_term or self._m_learn_cost:      # reliability and recalibration, a file of their own
+                import json
+                import os
+                with open(os.path.join(savedir, 'recalibration_%d.json' % self._epoch), 'w') as fh:
+                    json.dump(self._recalibration_state(), fh)
+
+    RECALIBRATION_KEYS = ('m_validate_reliability', 'm_reliability_bins', 'm_recalibrate_cost', 'm_recalibrate_term',
+                          'm_recalibration_range', 'cost_recal_offset', 'term_recal_offset')
+
+    def _recalibration_state(self):
+        """What ``recalibration_<epoch>.json`` keeps: the five switches and the two offsets in force."""
+        sampler = getattr(self, 'model_sampler', None)
+        return {'m_validate_reliability': self._validate_reliability, 'm_reliability_bins': self._reliability_bins,
+                'm_recalibrate_cost': self._recalibrate_cost, 'm_recalibrate_term': self._recalibrate_term,
+                'm_recalibration_range': list(self._recalibration_range),
+                'cost_recal_offset': float(getattr(self.fake_env, 'cost_recalibration', 0.0)),
+                'term_recal_offset': float(getattr(sampler, 'term_logit_offset', None) or 0.0)}
+
+    def _load_recalibration(self, savedir, timestep):
+        """The switches and offsets ``save`` wrote, checked like the constructor's and handed to the environment and the model
+        sampler (a checkpoint from before them has no such file: the constructor's switches stay, the offsets are 0)."""
+        import json
+        import os
+        path = os.path.join(savedir, 'recalibration_%d.json' % int(timestep))
+        kw = {'cost_recal_offset': 0.0, 'term_recal_offset': 0.0}
+        if os.path.exists(path):
+            with open(path) as fh:
+                kw = json.load(fh)
+            (self._validate_reliability, self._reliability_bins, self._recalibrate_cost, self._recalibrate_term,
+             self._recalibration_range) = _reliability_args(
+                getattr(self, '_validate_horizon', 0), self._use_model, self._m_cost_loss, getattr(self, '_m_term_loss', 'gaussian'),
+                getattr(self, '_m_term_sampling', False), kw['m_validate_reliability'], kw['m_reliability_bins'],
+                kw['m_recalibrate_cost'], kw['m_recalibrate_term'], kw['m_recalibration_range'])
+        # (an offset is handed over only where it changes something: an environment or a sampler without one is left alone)
+        b_cost = float(kw['cost_recal_offset']) if self._m_cost_loss == 'logistic' else 0.0
+        if b_cost != getattr(self.fake_env, 'cost_recalibration', 0.0):
+            self.fake_env.set_cost_recalibration(b_cost)
+        sampler = getattr(self, 'model_sampler', None)
+        on = getattr(self, '_m_term_sampling', False) and getattr(self, '_m_term_loss', 'gaussian') == 'logistic'
+        b_term = (float(kw['term_recal_offset']) if on else 0.0) or None
+        if sampler is not None and b_term != getattr(sampler, 'term_logit_offset', None):
+            sampler.set_term_logit_offset(b_term)
+
     def _load_column_weights(self, savedir, timestep):
         """The four keys ``save`` wrote (a checkpoint from before them has no such file: the constructor's stay)."""
         import json
@@ -837,3 +968,4 @@ class CMBPO:
                 head = json.load(fh)
             self.fake_env.set_term_head(head['threshold'], head['members'], loss=term_loss)
             self._load_term_sampling(savedir, timestep)
+        self._load_recalibration(savedir, timestep)

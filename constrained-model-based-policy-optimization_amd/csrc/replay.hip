@@ -8,6 +8,9 @@
 // and, for a replay that also checks the model's variance, between post and compare of a step:
 //   replay_calibrate_kernel     one horizon step of the calibration table: squared errors against two predictive variances
 //   replay_calib_finish_kernel  its partials -> the [H] calibration table, in slot order
+// and, for a replay that also checks whether a logistic column is a probability, at the same place:
+//   replay_reliab_kernel        one horizon step of the reliability table: the members' logits, binned, against the recorded flag
+//   replay_reliab_finish_kernel its partials -> the [H] reliability table, in slot order
 // Sums are float64, counts int64, every addition in a fixed order (no floating-point atomics): two runs are bitwise equal.
 #include "common.h"
 #include "ens_mlp_internal.h"
@@ -363,6 +366,159 @@ __global__ __launch_bounds__(kThreads) void replay_calib_finish_kernel(cmbpo_rep
   }
 }
 
+// ---- reliability tables of the logistic columns -------------------------------------------------------------
+constexpr int kRelBins = CMBPO_RELIAB_MAX_BINS;
+constexpr int kRelCols = CMBPO_RELIAB_MAX_COLS;
+static_assert(CMBPO_RELIAB_MAX_ENSEMBLE <= kCalBatch, "one batch of loads holds every member's logit");
+static_assert(2 * kRelCols * kRows == kThreads, "one thread per (column, reading, row)");
+static_assert(2 * kRelCols * kRelBins <= kThreads / 2, "the bin owners sit below the owners of the per-reading and per-column entries");
+
+__device__ __forceinline__ int rel_sums(int n_bins, int n_cols) { return 2 * n_cols * (2 * n_bins + 2); }
+__device__ __forceinline__ int rel_counts(int n_bins, int n_cols) { return 2 * n_cols * 2 * n_bins + 2 * n_cols; }
+
+// One horizon step of the reliability table; the geometry of replay_compare_kernel (kRows rows per workgroup, slot =
+// workgroup).  Thread t sits on row t % kRows of (column, reading) pair t / kRows, j = pair / 2 and r = pair % 2: it loads every
+// member's logit of its row and column in one batch (they are B * out_dim floats apart; the two readings of a row load the
+// same 2 E floats, the second from L1), settles the row's verdict, computes its own reading's z, bin and terms and leaves them in
+// LDS.  Then thread u < 2 C K owns bin u % K of pair u / K and adds its rows in row order, threads kThreads / 2 + pair own the
+// two sums of a reading, threads 3 kThreads / 4 + j the two counts of a column: every entry of the slot has one writer, the
+// order is fixed.  Reads alive / predictions / recording / mean, writes its partial slot only.
+__global__ __launch_bounds__(kThreads) void replay_reliab_kernel(cmbpo_replay_t rp, cmbpo_replay_reliab_t rr, int h) {
+  __shared__ uint8_t s_alive[kRows];    // alive on entry
+  __shared__ int s_bad[kRows];          // a non-finite prediction in the row (the compare kernel's verdict)
+  __shared__ double s_edge[kRelBins];
+  __shared__ int s_bin[kThreads];       // the bin of (pair, row); -1: the row does not enter
+  __shared__ uint8_t s_y[kThreads], s_skip[kThreads];
+  __shared__ double s_p[kThreads], s_z[kThreads], s_br[kThreads], s_ll[kThreads];
+
+  const int t = threadIdx.x;
+  const int B = rp.B, D = rp.obs_dim, E = rr.ensemble, O = rr.out_dim, K = rr.n_bins, nc = rr.n_cols;
+  const int row0 = blockIdx.x * kRows;
+  const int rows = min(kRows, B - row0);
+  const size_t hb = (size_t)h * B;
+  const int NS = rel_sums(K, nc), NC = rel_counts(K, nc);
+  double *psum = rr.part_sum + ((size_t)h * gridDim.x + blockIdx.x) * NS;
+  int64_t *pcnt = rr.part_cnt + ((size_t)h * gridDim.x + blockIdx.x) * NC;
+
+  if (t < kRows) {
+    const bool alive = t < rows && rp.alive[row0 + t] != 0;
+    s_alive[t] = alive;
+    s_bad[t] = (alive && !(isfinite(rp.p_rew[row0 + t]) && isfinite(rp.p_cost[row0 + t]))) ? 1 : 0;
+  } else if (t - kRows < K - 1) {
+    s_edge[t - kRows] = (double)rr.edges[t - kRows];
+  }
+  __syncthreads();
+
+  // the members' logits of (row, column): issued ahead of the scan of the predictions, used behind it
+  const int row = t % kRows, pair = t / kRows, j = pair >> 1, rd = pair & 1;
+  const bool mine = j < nc && s_alive[row] != 0;
+  const int col = j ? rr.col[1] : rr.col[0];                     // (selects, not indexed: the descriptor stays in scalars)
+  const int target = j ? rr.target[1] : rr.target[0];
+  const float shift = j ? rr.shift[1] : rr.shift[0];
+  float zm[kCalBatch];
+#pragma unroll
+  for (int e = 0; e < kCalBatch; ++e) zm[e] = 0.0f;
+  int m = -1;
+  if (mine) {
+    load_members(rp.mean + (size_t)(row0 + row) * O + col, (size_t)B * O, 0, E, zm);
+    m = rr.elite[hb + row0 + row];
+  }
+
+  // the compare kernel's rule on the predicted observations (integer LDS flag: order cannot matter)
+  const float *pred = rp.p_next_obs + (size_t)row0 * D;
+  for (int i = t, total = rows * D; i < total; i += kThreads) {
+    const int r = i / D;
+    if (s_alive[r] && !isfinite(pred[i])) atomicOr(&s_bad[r], 1);
+  }
+  __syncthreads();
+
+  int bin = -1;
+  bool skip = false, y = false;
+  double z = 0.0, p = 0.0, br = 0.0, ll = 0.0;
+  if (mine && s_bad[row] == 0) {
+    bool ok = m >= 0 && m < E;
+    double s = 0.0;
+    float z_m = 0.0f;
+#pragma unroll
+    for (int e = 0; e < kCalBatch; ++e) {
+      if (e < E) {
+        const float v = shift != 0.0f ? __fsub_rn(zm[e], shift) : zm[e];
+        ok = ok && isfinite(v);
+        s += (double)v;
+        if (e == m) z_m = v;
+      }
+    }
+    skip = !ok;
+    if (ok) {
+      z = rd ? s / (double)E : (double)z_m;
+      const uint8_t *flags = rr.term ? rr.term : rp.term;
+      y = target == CMBPO_RELIAB_COST ? rp.cost[hb + row0 + row] > 0.5f : flags[hb + row0 + row] != 0;
+      bin = 0;
+      for (int k = 0; k < K - 1; ++k) bin += z > s_edge[k];
+      const double yd = y ? 1.0 : 0.0;
+      p = 1.0 / (1.0 + exp(-z));
+      ll = fmax(z, 0.0) - yd * z + log1p(exp(-fabs(z)));
+      const double q = 1.0 / (1.0 + exp(y ? z : -z));      // |p - y| without the cancellation of p - 1
+      br = q * q;
+    }
+  }
+  s_bin[t] = bin; s_y[t] = y; s_skip[t] = skip;
+  s_p[t] = p; s_z[t] = z; s_br[t] = br; s_ll[t] = ll;
+  __syncthreads();
+
+  if (t < 2 * nc * K) {                                  // one bin of one (column, reading)
+    const int pr = t / K, k = t % K;
+    int64_t n = 0, pos = 0;
+    double sp = 0.0, sz = 0.0;
+    for (int r = 0; r < kRows; ++r) {
+      const int i = pr * kRows + r;
+      if (s_bin[i] == k) { n += 1; pos += s_y[i]; sp += s_p[i]; sz += s_z[i]; }
+    }
+    psum[pr * (2 * K + 2) + k] = sp;
+    psum[pr * (2 * K + 2) + K + k] = sz;
+    pcnt[pr * 2 * K + k] = n;
+    pcnt[pr * 2 * K + K + k] = pos;
+  } else if (t >= kThreads / 2 && t - kThreads / 2 < 2 * nc) {      // the two sums of one (column, reading)
+    const int pr = t - kThreads / 2;
+    double sb = 0.0, sl = 0.0;
+    for (int r = 0; r < kRows; ++r) {
+      const int i = pr * kRows + r;
+      if (s_bin[i] >= 0) { sb += s_br[i]; sl += s_ll[i]; }
+    }
+    psum[pr * (2 * K + 2) + 2 * K] = sb;
+    psum[pr * (2 * K + 2) + 2 * K + 1] = sl;
+  } else if (t >= 3 * kThreads / 4 && t - 3 * kThreads / 4 < nc) {  // the two counts of one column (its reading 0 decides)
+    const int c = t - 3 * kThreads / 4;
+    int64_t n_rel = 0, n_skip = 0;
+    for (int r = 0; r < kRows; ++r) {
+      const int i = 2 * c * kRows + r;
+      n_rel += s_bin[i] >= 0;
+      n_skip += s_skip[i];
+    }
+    pcnt[2 * nc * 2 * K + 2 * c] = n_rel;
+    pcnt[2 * nc * 2 * K + 2 * c + 1] = n_skip;
+  }
+}
+
+// the reliability table: sums and counts over the slots, in slot order; one workgroup per horizon, one thread per entry
+__global__ __launch_bounds__(kThreads) void replay_reliab_finish_kernel(cmbpo_replay_reliab_t rr, int n_part) {
+  const int h = blockIdx.x;
+  const int NS = rel_sums(rr.n_bins, rr.n_cols), NC = rel_counts(rr.n_bins, rr.n_cols);
+  for (int j = threadIdx.x; j < NS + NC; j += kThreads) {
+    if (j < NS) {
+      const double *p = rr.part_sum + (size_t)h * n_part * NS + j;
+      double s = 0.0;
+      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NS];
+      rr.sums[(size_t)h * NS + j] = s;
+    } else {
+      const int64_t *p = rr.part_cnt + (size_t)h * n_part * NC + (j - NS);
+      int64_t s = 0;
+      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NC];
+      rr.counts[(size_t)h * NC + (j - NS)] = s;
+    }
+  }
+}
+
 int check_shape(const char *who, const cmbpo_replay_t *rp) {
   CMBPO_REQUIRE(rp != nullptr, "%s: descriptor is NULL", who);
   CMBPO_REQUIRE(rp->B >= 1, "%s: B %d < 1", who, rp->B);
@@ -440,6 +596,53 @@ int launch_calib_finish(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc
   return CMBPO_OK;
 }
 
+int check_reliab(const char *who, const cmbpo_replay_reliab_t *rr) {
+  CMBPO_REQUIRE(rr != nullptr, "%s: reliability descriptor is NULL", who);
+  CMBPO_REQUIRE(rr->ensemble >= 1 && rr->ensemble <= CMBPO_RELIAB_MAX_ENSEMBLE, "%s: reliability ensemble %d outside [1, %d]", who,
+                rr->ensemble, CMBPO_RELIAB_MAX_ENSEMBLE);
+  CMBPO_REQUIRE(rr->n_bins >= 1 && rr->n_bins <= kRelBins, "%s: n_bins %d outside [1, %d]", who, rr->n_bins, kRelBins);
+  CMBPO_REQUIRE(rr->n_cols >= 1 && rr->n_cols <= kRelCols, "%s: n_cols %d outside [1, %d]", who, rr->n_cols, kRelCols);
+  CMBPO_REQUIRE(rr->reserved == 0, "%s: reliability reserved %d != 0", who, rr->reserved);
+  for (int j = 0; j < rr->n_cols; ++j) {
+    CMBPO_REQUIRE(rr->col[j] >= 0 && rr->col[j] < rr->out_dim, "%s: col[%d] %d outside [0, out_dim = %d)", who, j, rr->col[j],
+                  rr->out_dim);
+    CMBPO_REQUIRE(rr->target[j] == CMBPO_RELIAB_COST || rr->target[j] == CMBPO_RELIAB_TERM, "%s: unknown target[%d] %d", who, j,
+                  rr->target[j]);
+    CMBPO_REQUIRE(std::isfinite(rr->shift[j]), "%s: shift[%d] is not finite", who, j);
+  }
+  return CMBPO_OK;
+}
+
+int check_reliab_step(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_reliab_t *rr) {
+  if (int r = check_compare(who, rp)) return r;
+  if (int r = check_reliab(who, rr)) return r;
+  CMBPO_REQUIRE(rp->mean, "%s: NULL buffer (mean)", who);
+  CMBPO_REQUIRE(rr->elite, "%s: NULL buffer (reliability elite)", who);
+  CMBPO_REQUIRE(rr->n_bins == 1 || rr->edges, "%s: NULL buffer (edges)", who);
+  CMBPO_REQUIRE(rr->part_sum && rr->part_cnt, "%s: NULL buffer (reliability partials)", who);
+  return CMBPO_OK;
+}
+
+int check_reliab_finish(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_reliab_t *rr) {
+  if (int r = check_shape(who, rp)) return r;
+  if (int r = check_reliab(who, rr)) return r;
+  CMBPO_REQUIRE(rr->part_sum && rr->part_cnt, "%s: NULL buffer (reliability partials)", who);
+  CMBPO_REQUIRE(rr->sums && rr->counts, "%s: NULL buffer (reliability table)", who);
+  return CMBPO_OK;
+}
+
+int launch_reliab(const cmbpo_replay_t *rp, const cmbpo_replay_reliab_t *rr, int h, hipStream_t s) {
+  hipLaunchKernelGGL(replay_reliab_kernel, dim3(cmbpo_replay_parts(rp->B)), dim3(kThreads), 0, s, *rp, *rr, h);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
+int launch_reliab_finish(const cmbpo_replay_t *rp, const cmbpo_replay_reliab_t *rr, hipStream_t s) {
+  hipLaunchKernelGGL(replay_reliab_finish_kernel, dim3(rp->H), dim3(kThreads), 0, s, *rr, cmbpo_replay_parts(rp->B));
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
 // a callee's refusal, passed on under this entry point's name
 int refused_by(const char *who, int rc) {
   char inner[400];
@@ -449,10 +652,11 @@ int refused_by(const char *who, int rc) {
 }
 
 // the steps of a run: cal == nullptr is exactly cmbpo_replay_run's launches, else the calibrate kernel goes between post and
-// compare and its finish behind the plain one; th / ch != nullptr: the heads' instances of the post kernel.  Every argument has been
-// checked by the caller.
-int run_steps(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *cal, cmbpo_mlp_t *model, int task, int ensemble,
-              const int32_t *d_elite, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, void *stream) {
+// compare and its finish behind the plain one; rel != nullptr: the reliability kernel behind it, its finish last; th / ch !=
+// nullptr: the heads' instances of the post kernel.  Every argument has been checked by the caller.
+int run_steps(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *cal, const cmbpo_replay_reliab_t *rel,
+              cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, const cmbpo_term_head_t *th,
+              const cmbpo_cost_head_t *ch, void *stream) {
   const int B = rp->B, D = rp->obs_dim, A = rp->act_dim;
   // the post step; act, elite and n_rows follow the horizon
   FakeenvPostCall pc{};
@@ -475,25 +679,34 @@ int run_steps(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_cali
     if (int rc = cmbpo_internal_fakeenv_post(pc, stream)) return refused_by(who, rc);
     if (cal)
       if (int rc = launch_calibrate(rp, cal, h, (hipStream_t)stream)) return rc;
+    if (rel)
+      if (int rc = launch_reliab(rp, rel, h, (hipStream_t)stream)) return rc;
     if (int rc = launch_compare(rp, h, (hipStream_t)stream)) return rc;
   }
   if (int rc = launch_finish(rp, (hipStream_t)stream)) return rc;
-  return cal ? launch_calib_finish(rp, cal, (hipStream_t)stream) : CMBPO_OK;
+  if (cal)
+    if (int rc = launch_calib_finish(rp, cal, (hipStream_t)stream)) return rc;
+  return rel ? launch_reliab_finish(rp, rel, (hipStream_t)stream) : CMBPO_OK;
 }
 
-// The four run entry points: ONE check list, keyed on which of rc (calibration), th (termination head) and ch (cost head) are
-// given.  The messages carry the name of the narrowest entry point that can express the call (DESIGN): ch given --
+// The five run entry points: ONE check list, keyed on which of rc (calibration), rr (reliability), th (termination head) and ch
+// (cost head) are given.  The messages carry the name of the narrowest entry point that can express the call (DESIGN): rr given --
+// cmbpo_replay_run_reliab, else ch given --
 // cmbpo_replay_run_cost, else th given -- cmbpo_replay_run_term, else rc given -- cmbpo_replay_run_calibrated, else
 // cmbpo_replay_run.  Where the entry points have always differed in the order
 // or the wording of a check, each combination keeps its own.
-int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch,
-               cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream) {
-  const bool ext = th || ch;      // (the two entries that take d_elite beside a calibration descriptor share their checks)
-  const char *who = ch ? "cmbpo_replay_run_cost" : th ? "cmbpo_replay_run_term" : rc ? "cmbpo_replay_run_calibrated" : "cmbpo_replay_run";
+int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_replay_reliab_t *rr, const cmbpo_term_head_t *th,
+               const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream) {
+  const bool ext = th || ch || rr;      // (the entries that take d_elite beside a calibration descriptor share their checks)
+  const char *who = rr ? "cmbpo_replay_run_reliab" : ch ? "cmbpo_replay_run_cost" : th ? "cmbpo_replay_run_term" : rc ? "cmbpo_replay_run_calibrated" : "cmbpo_replay_run";
   if (int r = rc ? check_calibrate(who, rp, rc) : check_compare(who, rp)) return r;      // (check_calibrate: mean / var as well)
   if (int r = check_finish(who, rp)) return r;
   if (rc)
     if (int r = check_calib_finish(who, rp, rc)) return r;
+  if (rr) {
+    if (int r = check_reliab_step(who, rp, rr)) return r;
+    if (int r = check_reliab_finish(who, rp, rr)) return r;
+  }
   CMBPO_REQUIRE(model != nullptr, "%s: model handle is NULL", who);
   if (!rc && !ext) CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);     // (the plain run names it before act)
   if (rc && !ext) CMBPO_REQUIRE(rp->act_dim == 0 || rp->act, "%s: NULL buffer (act)", who);
@@ -503,6 +716,14 @@ int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const c
     // (cmbpo_replay_run_calibrated has no d_elite; without a head cmbpo_replay_run_term has always ignored its own)
     if (ext) CMBPO_REQUIRE(d_elite == nullptr || d_elite == rc->elite, "%s: d_elite differs from the calibration descriptor's elite", who);
     d_elite = rc->elite;
+  }
+  if (rr) {
+    CMBPO_REQUIRE(ensemble == rr->ensemble, "%s: ensemble %d, the reliability descriptor's is %d", who, ensemble, rr->ensemble);
+    CMBPO_REQUIRE(model->out_dim == rr->out_dim, "%s: the reliability descriptor's out_dim %d is not the model's %d", who, rr->out_dim,
+                  model->out_dim);
+    CMBPO_REQUIRE(!rc || rc->elite == rr->elite, "%s: the calibration descriptor's elite differs from the reliability descriptor's", who);
+    CMBPO_REQUIRE(d_elite == nullptr || d_elite == rr->elite, "%s: d_elite differs from the reliability descriptor's elite", who);
+    d_elite = rr->elite;
   }
   if (ext) CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);
   if (ch && ch->kind == 1)
@@ -515,7 +736,7 @@ int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const c
                   "%s: termination head (cmbpo_term_head_t): model out_dim %d does not match obs_dim %d + 1 (+ 1 with CMBPO_TASK_LEARNED_COST) "
                   "+ 1 for the head's column, task 0x%x", who, model->out_dim, rp->obs_dim, task);
   }
-  return run_steps(who, rp, rc, model, task, ensemble, d_elite, th, ch, stream);
+  return run_steps(who, rp, rc, rr, model, task, ensemble, d_elite, th, ch, stream);
 }
 
 }  // namespace
@@ -536,7 +757,7 @@ extern "C" int cmbpo_replay_finish(const cmbpo_replay_t *rp, void *stream) {
 
 extern "C" int cmbpo_replay_run(const cmbpo_replay_t *rp, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite,
                                 void *stream) {
-  return replay_run(rp, nullptr, nullptr, nullptr, model, task, ensemble, d_elite, stream);
+  return replay_run(rp, nullptr, nullptr, nullptr, nullptr, model, task, ensemble, d_elite, stream);
 }
 
 extern "C" int cmbpo_replay_calibrate(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, int h, void *stream) {
@@ -554,16 +775,34 @@ extern "C" int cmbpo_replay_calib_finish(const cmbpo_replay_t *rp, const cmbpo_r
 extern "C" int cmbpo_replay_run_calibrated(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, cmbpo_mlp_t *model, int task,
                                            int ensemble, void *stream) {
   if (rc == nullptr) return check_calibrate("cmbpo_replay_run_calibrated", rp, rc);      // (this entry's own error, not the plain run)
-  return replay_run(rp, rc, nullptr, nullptr, model, task, ensemble, nullptr, stream);
+  return replay_run(rp, rc, nullptr, nullptr, nullptr, model, task, ensemble, nullptr, stream);
 }
 
 extern "C" int cmbpo_replay_run_term(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th,
                                      cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream) {
-  return replay_run(rp, rc, th, nullptr, model, task, ensemble, d_elite, stream);
+  return replay_run(rp, rc, nullptr, th, nullptr, model, task, ensemble, d_elite, stream);
 }
 
 extern "C" int cmbpo_replay_run_cost(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th,
                                      const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite,
                                      void *stream) {
-  return replay_run(rp, rc, th, ch, model, task, ensemble, d_elite, stream);
+  return replay_run(rp, rc, nullptr, th, ch, model, task, ensemble, d_elite, stream);
+}
+
+extern "C" int cmbpo_replay_reliab(const cmbpo_replay_t *rp, const cmbpo_replay_reliab_t *rr, int h, void *stream) {
+  const char *who = "cmbpo_replay_reliab";
+  if (int r = check_reliab_step(who, rp, rr)) return r;
+  CMBPO_REQUIRE(h >= 0 && h < rp->H, "%s: h %d outside [0, %d)", who, h, rp->H);
+  return launch_reliab(rp, rr, h, (hipStream_t)stream);
+}
+
+extern "C" int cmbpo_replay_reliab_finish(const cmbpo_replay_t *rp, const cmbpo_replay_reliab_t *rr, void *stream) {
+  if (int r = check_reliab_finish("cmbpo_replay_reliab_finish", rp, rr)) return r;
+  return launch_reliab_finish(rp, rr, (hipStream_t)stream);
+}
+
+extern "C" int cmbpo_replay_run_reliab(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_replay_reliab_t *rr,
+                                       const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model, int task,
+                                       int ensemble, const int32_t *d_elite, void *stream) {
+  return replay_run(rp, rc, rr, th, ch, model, task, ensemble, d_elite, stream);
 }

@@ -55,6 +55,9 @@ task whose cost is a magnitude, not an indicator, should keep the default ``'gau
 
 ``replay(...)`` has no counterpart in the reference: it replays windows of real steps through the model with the recorded
 actions and returns, per horizon, how far the predictions are from the recording (open-loop model validation).
+``replay(..., reliability=True)`` also measures whether a logistic column is a probability, and
+``set_cost_recalibration(b)`` feeds the measured logit offset of the cost column back: the kernels then subtract
+``float32(cost_logit_shift + b)``.
 
 ``task`` is a built-in task name, a name given to ``statics.register_task``, or a ``statics.TaskRules`` (user-defined
 termination / cost rules, evaluated by the same kernel); any other name is the default task, as in the reference.
@@ -112,6 +115,7 @@ class FakeEnv:
         elif term_loss != 'gaussian':
             raise ValueError("term_loss='logistic' needs predicts_term=True: the model has no termination column")
         self.cost_loss, self.cost_logit_shift = 'gaussian', 0.0
+        self.cost_recalibration = 0.0               # see set_cost_recalibration()
         self.set_cost_head(cost_loss, cost_logit_shift)
         self.device = model.device
         # bench.py sets this to a list to collect (start, end) HIP events around the dominant kernel
@@ -193,14 +197,49 @@ class FakeEnv:
             raise ValueError(f"cost_logit_shift must be a finite number, got {shift}")
         self.cost_loss, self.cost_logit_shift = loss, shift
 
+    def set_cost_recalibration(self, offset):
+        """The logit offset b of a measured recalibration of the logistic cost column (``replay.logit_offset``): the
+        shift handed to the kernels becomes ``float32(cost_logit_shift + b)``, the cost ``sigma(z - cost_logit_shift - b)``.  It is
+        set absolutely, not accumulated; 0.0 (the default) hands over ``cost_logit_shift`` as it always was.  ``replay(...,
+        reliability=True)`` measures the column WITHOUT it.  A rollout pool picks it up at the sampler's ``reset()``."""
+        offset = float(offset)
+        if not np.isfinite(offset):
+            raise ValueError(f"set_cost_recalibration: the offset must be a finite number, got {offset}")
+        if offset != 0.0 and self.cost_loss != 'logistic':
+            raise ValueError("set_cost_recalibration needs cost_loss='logistic': a Gaussian cost column is not a logit, there is "
+                             "nothing to shift")
+        self.cost_recalibration = offset
+
+    @property
+    def cost_kernel_shift(self):
+        """The number the kernels subtract from the cost logit: ``cost_logit_shift``, with a recalibration offset b the float32
+        sum ``cost_logit_shift + b``."""
+        if self.cost_recalibration == 0.0:
+            return self.cost_logit_shift
+        return float(np.float32(self.cost_logit_shift + self.cost_recalibration))
+
     def cost_head_struct(self, cost_logit=None):
         """The ``cmbpo_cost_head_t`` of this head (None under 'gaussian': the call without one); the optional output is a device
         tensor or None."""
         if self.cost_loss != 'logistic':
             return None
         ch = _lib.CostHeadStruct()
-        ch.kind, ch.logit_shift, ch.cost_logit = _lib.COST_LOGISTIC, self.cost_logit_shift, _lib.ptr(cost_logit)
+        ch.kind, ch.logit_shift, ch.cost_logit = _lib.COST_LOGISTIC, self.cost_kernel_shift, _lib.ptr(cost_logit)
         return ch
+
+    def reliability_columns(self):
+        """The columns ``replay(..., reliability=True)`` measures: whichever of the cost and the termination head is logistic, as
+        the list ``ReplayBuffers(reliability=dict(columns=...))`` takes.  The cost column carries ``cost_logit_shift`` (the class-
+        weight undo, NOT the recalibration offset: the table measures what the offset is derived from), the termination column 0."""
+        cols = []
+        if self.cost_loss == 'logistic':
+            cols.append(dict(name='cost', col=self.obs_dim + 1, target='cost', shift=self.cost_logit_shift))
+        if self._predicts_term and self.term_loss == 'logistic':
+            cols.append(dict(name='term', col=self.output_dim - 1, target='term', shift=0.0))
+        if not cols:
+            raise ValueError("reliability=True needs a logistic head (cost_loss='logistic' or term_loss='logistic'): a Gaussian "
+                             "column is not a logit, it has no reliability table")
+        return cols
 
     def random_inds(self, size):
         """One elite per branch (models/fake_env.py:174-178), from this object's seeded generator."""
@@ -352,7 +391,7 @@ class FakeEnv:
         return next_obs, r, terms, info
 
     def replay(self, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, model_inds=None, mode='open_loop',
-               calibration=False):
+               calibration=False, reliability=False, reliability_bins=15, reliability_terminals=None):
         """Open-loop model validation: replay B windows of up to H consecutive REAL steps through the model and hold its
         predictions against the recording, horizon by horizon (``cmbpo_replay_run``).
 
@@ -384,12 +423,27 @@ class FakeEnv:
         ``calibration=True`` runs ``cmbpo_replay_run_calibrated`` instead: the same launches with one more kernel
         per step, the same table bit for bit, and under the key ``'calibration'`` the dict of
         ``cmbpo_amd.replay.calibration_table`` -- is the predictive VARIANCE the size of the real error, per horizon and per
-        column (the observation columns, then the reward).  False is the call as it always was."""
+        column (the observation columns, then the reward).  False is the call as it always was.
+
+        ``reliability=True`` runs ``cmbpo_replay_run_reliab``: one more kernel per step again, every other table
+        bit for bit, and under the key ``'reliability'`` the dict of ``cmbpo_amd.replay.reliability_table`` with one entry per
+        logistic head, ``'cost'`` and / or ``'term'`` -- is the column a PROBABILITY: per horizon, in ``reliability_bins`` bins
+        of equal probability width, what the column said against how often the event happened, with ECE, MCE, Brier score and log
+        loss, for the elite member's logit and for the members' mean logit.  The cost column is measured with
+        ``cost_logit_shift`` and WITHOUT the offset of ``set_cost_recalibration``, the termination column as it is.  With neither
+        head logistic it raises ValueError: a Gaussian column is not a logit.  ``reliability_terminals`` [H, B]: the flags the
+        termination column's table is held against where they are not ``terminals`` -- the head's training targets, which
+        count a time-out as 0 (``CPOBuffer.term_targets``); the replay itself goes on ending windows at ``terminals``.  False is
+        the call as it always was."""
         from .replay import ReplayBuffers
+        if reliability_terminals is not None and not reliability:
+            raise ValueError("replay: reliability_terminals needs reliability=True: they are the flags of the reliability table")
+        rel = dict(columns=self.reliability_columns(), bins=int(reliability_bins), terminals=reliability_terminals) \
+            if reliability else None
         E = self._model.num_nets
         with torch.cuda.device(self.device):
             rb = ReplayBuffers(obs0, actions, next_obs, rewards, costs, terminals, lengths=lengths, mode=mode, ensemble=E,
-                               out_dim=self.output_dim, device=self.device, calibration=bool(calibration))
+                               out_dim=self.output_dim, device=self.device, calibration=bool(calibration), reliability=rel)
             if (rb.obs_dim, rb.act_dim) != (self.obs_dim, self.act_dim):
                 raise ValueError("replay: windows of width (%d, %d), the model's is (%d, %d)"
                                  % (rb.obs_dim, rb.act_dim, self.obs_dim, self.act_dim))
@@ -411,9 +465,12 @@ class FakeEnv:
                 rb.run_calibrated(self._model.mlp.handle, self._task_id, E, elite, term_head=th, cost_head=ch)
                 tab = rb.table()
                 tab['calibration'] = rb.calibration_table()
-                return tab
-            rb.run(self._model.mlp.handle, self._task_id, E, elite, term_head=th, cost_head=ch)
-            return rb.table()
+            else:
+                rb.run(self._model.mlp.handle, self._task_id, E, elite, term_head=th, cost_head=ch)
+                tab = rb.table()
+            if reliability:
+                tab['reliability'] = rb.reliability_table()
+            return tab
 
     def close(self):
         pass

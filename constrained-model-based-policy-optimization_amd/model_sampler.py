@@ -37,6 +37,8 @@ at a time with the chunk's K, turns them into thresholds (``utils.term_threshold
 attaches them beside the rollout struct (``cmbpo_rollout_term_draws_attach``) for the one-call step and the native loop.  The
 action noise, the elite picks and the transition noise are the numbers they were, at the same chunk boundaries; off (the
 default) no generator is made and no call is added.  Sharded samplers refuse it: per-rank streams are not defined here.
+``set_term_logit_offset(b)`` (a logistic head only) adds a measured recalibration offset to every chunk of thresholds
+drawn from then on: the hazard becomes ``sigma(z - b)``.
 
 ``sample()`` returns ``(next_obs, reward, terminal, info)`` like the reference, but as slot-indexed CUDA
 tensors (the trainer only reads ``info['alive_ratio']``, ``algorithms/cmbpo.py:254-263``).
@@ -78,7 +80,8 @@ class ModelSampler:
         self._calib_total_samples = 0.0
         self._diag = None
         self._noise_scale = None                    # [obs] factors on the xi draws (host tensor), see set_noise_scale()
-        self.global_alive = 1                      # alive branches over all shards (sharded samplers), see reset()
+        self._term_logit_offset = None              # added to the termination thresholds, see set_term_logit_offset()
+        self.global_alive = 1                     # alive branches over all shards (sharded samplers), see reset()
         self._global_total_samples = 0.0
 
     # -- wiring -----------------------------------------------------------------------------------
@@ -86,6 +89,8 @@ class ModelSampler:
         if self.term_sampling and not getattr(env, "predicts_term", False):
             raise ValueError("term_sampling=True needs an environment with predicts_term=True: the model has no termination "
                              "column to sample from")
+        if self._term_logit_offset is not None:
+            self._check_term_logit_offset(env)
         self.env, self.policy, self.pool = env, policy, pool
         self.device = pool.device
         self._gen = torch.Generator(device=self.device)
@@ -137,6 +142,36 @@ class ModelSampler:
             raise ValueError("set_noise_scale: the factors must be finite and positive")
         if self._noise_scale is None or not torch.equal(self._noise_scale, s):
             self._noise_scale, self._draws = s, None
+
+    @property
+    def term_logit_offset(self):
+        """The offset of ``set_term_logit_offset`` as a float, or None."""
+        return self._term_logit_offset
+
+    def _check_term_logit_offset(self, env):
+        if not self.term_sampling:
+            raise ValueError("set_term_logit_offset: this sampler was built with term_sampling=False, it draws no termination "
+                             "thresholds to shift")
+        if env is not None and getattr(env, "term_loss", "gaussian") != 'logistic':
+            raise ValueError("set_term_logit_offset needs an environment with term_loss='logistic': a Gaussian termination column "
+                             "is not a logit, an offset in logit space means nothing to it")
+
+    def set_term_logit_offset(self, offset):
+        """Recalibrated termination hazard: a `term_sampling` sampler under a logistic head adds ``offset`` (b of
+        ``replay.logit_offset``) to every chunk of termination thresholds it draws from now on -- one float32 rounding per element,
+        +inf stays +inf --, since ``z - b > logit(u)`` is ``z > logit(u) + b``.  Explicit ``term_draws=`` of ``sample`` are never
+        shifted.  An offset that differs from the one in force drops the rest of the chunk of draws in hand; the same offset again
+        drops nothing.  None or 0.0 (the default): the thresholds as they come, exactly the calls of a sampler that never heard
+        of this."""
+        b = None if offset is None else float(offset)
+        if b is not None and not np.isfinite(b):
+            raise ValueError("set_term_logit_offset: the offset must be a finite number, got %r" % (offset,))
+        if b == 0.0:
+            b = None
+        if b is not None:
+            self._check_term_logit_offset(self.env)
+        if b != self._term_logit_offset:
+            self._term_logit_offset, self._draws = b, None
 
     def batch_ready(self):
         return self.pool.size >= self.pool.max_size
@@ -256,7 +291,9 @@ class ModelSampler:
                                getattr(self.env, "term_kernel_threshold", getattr(self.env, "term_threshold", 0.5)),
                                getattr(self.env, "term_members", "elite"))
             # ... and the reading of its learned-cost column (a shift changed between two fits is picked up here)
-            pool.set_cost_head(getattr(self.env, "cost_loss", "gaussian"), getattr(self.env, "cost_logit_shift", 0.0))
+            # (with a recalibration offset: the float32 sum of the two, FakeEnv.cost_kernel_shift)
+            pool.set_cost_head(getattr(self.env, "cost_loss", "gaussian"),
+                               getattr(self.env, "cost_kernel_shift", getattr(self.env, "cost_logit_shift", 0.0)))
             if observations is None:
                 fill(pool.t["cur_obs"])
             else:
@@ -430,6 +467,8 @@ class ModelSampler:
             # u = 1 - rand() in (0, 1]: a probability of exactly 0 never ends a branch
             u_ck = 1.0 - torch.rand((K, B), generator=self._term_gen, dtype=torch.float32, device=self.device)
             t_ck = term_thresholds(u_ck, getattr(self.env, "term_loss", "gaussian"), check=False).contiguous()
+            if self._term_logit_offset is not None:
+                t_ck.add_(torch.tensor(self._term_logit_offset, dtype=torch.float32, device=self.device))
         self._draws = [0, e_ck, self._elites[d_ck], x_ck, t_ck]
         return self._draws
 

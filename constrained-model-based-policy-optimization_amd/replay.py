@@ -9,6 +9,11 @@ state, the post kernel's outputs of the step, the partial sums and the table -- 
 Predictive calibration: ``ReplayBuffers(..., calibration=True)`` also owns the arrays of
 ``cmbpo_replay_calib_t``; ``calibration_table`` builds the per-horizon, per-column table from its raw sums and counts, and
 ``temperature`` turns one row of it into the variance temperature ``ModelSampler.set_noise_scale`` takes the root of.
+
+Reliability of the logistic columns: ``ReplayBuffers(..., reliability=dict(columns=[...], bins=K))`` also owns the
+arrays of ``cmbpo_replay_reliab_t``; ``reliability_table`` builds, per column and reading, the per-bin confidence against the
+observed frequency with ECE / MCE / Brier / log loss from the raw sums and counts, and ``logit_offset`` turns one horizon of
+it into the logit offset that makes the column's mean probability the observed rate (calibration-in-the-large).
 """
 import ctypes as C
 
@@ -22,6 +27,7 @@ SUM_KEYS = ("se_rew", "se_cost", "sum_ep_var", "sum_dkl")      # columns obs_dim
 # the calibration table's raw arrays, [H, obs + 1] each, in the order of `sums` [H, 6, obs + 1] / `counts` [H, 4, obs + 1]
 CALIB_SUM_KEYS = ("sum_z2_al", "sum_z2_tot", "sum_log_v_al", "sum_log_v_tot", "sum_v_bar", "sum_s2")
 CALIB_COUNT_KEYS = ("n_cover1_al", "n_cover2_al", "n_cover1_tot", "n_cover2_tot")
+READINGS = ("elite", "pooled")     # reading 0 / 1 of a reliability column: the elite member's logit / the members' mean logit
 
 
 def _as(x, dtype, device):
@@ -33,11 +39,16 @@ def _as(x, dtype, device):
 
 class ReplayBuffers:
     def __init__(self, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, mode="open_loop", ensemble=0,
-                 out_dim=0, device="cuda", calibration=False):
+                 out_dim=0, device="cuda", calibration=False, reliability=None):
         """obs0 [B, obs]; actions [H, B, act]; next_obs [H, B, obs]; rewards / costs / terminals [H, B] (a trailing axis
         of one is dropped); lengths [B] in 1..H (None: H).  NumPy arrays or tensors.  ``ensemble`` / ``out_dim`` > 0 also
         allocate the forward's scratch ``cmbpo_replay_run`` needs.  ``calibration=True`` (needs both) also allocates the
-        arrays of the calibration table and its member indices ``elite`` [H, B] int32, zeros until ``set_elite``."""
+        arrays of the calibration table and its member indices ``elite`` [H, B] int32, zeros until ``set_elite``.
+        ``reliability=dict(columns=[dict(name=, col=, target='cost' | 'term', shift=0.0), ...], bins=15, edges=None,
+        terminals=None)`` (needs both too) also allocates the arrays of the reliability table of one or two logistic columns;
+        ``edges`` [bins - 1] (ascending, finite; None: ``default_edges(bins)``) are the bin edges in logit space; ``terminals``
+        [H, B] are the flags the 'term' columns are held against where they are not the recorded ones (a head's training
+        targets).  It shares ``elite`` with the calibration table."""
         if mode not in MODES:
             raise ValueError("replay mode: 'open_loop' or 'one_step', got %r" % (mode,))
         dev = torch.device(device)
@@ -85,13 +96,15 @@ class ReplayBuffers:
         for k, v in self.t.items():
             setattr(rs, k, v.data_ptr())
         self.rs = rs
-        self.cs = self.c = None
+        self.cs = self.c = self.elite = None
+        self.rr = self.r = None
         if calibration:
             if ensemble < 1 or out_dim < D + 1:
                 raise ValueError("replay: calibration needs the forward's scratch: ensemble >= 1 and out_dim >= obs + 1 = %d, "
                                  "got %d and %d" % (D + 1, ensemble, out_dim))
             ns, nc = _lib.REPLAY_CALIB_SUMS * (D + 1), _lib.REPLAY_CALIB_COUNTS * (D + 1) + 2
-            self.c = dict(elite=torch.zeros((H, B), dtype=i32, device=dev),
+            self.elite = torch.zeros((H, B), dtype=i32, device=dev)
+            self.c = dict(elite=self.elite,
                           part_sum=torch.zeros((H, self.n_part, ns), dtype=torch.float64, device=dev),
                           part_cnt=torch.zeros((H, self.n_part, nc), dtype=torch.int64, device=dev),
                           sums=torch.zeros((H, ns), dtype=torch.float64, device=dev),
@@ -101,6 +114,55 @@ class ReplayBuffers:
             for k, v in self.c.items():
                 setattr(cs, k, v.data_ptr())
             self.cs = cs
+        if reliability is not None:
+            self._init_reliability(dict(reliability), int(ensemble), int(out_dim))
+
+    def _init_reliability(self, spec, ensemble, out_dim):
+        H, B, dev = self.H, self.B, self.device
+        columns = list(spec.pop("columns", ()))
+        K = int(spec.pop("bins", 15))
+        edges = spec.pop("edges", None)
+        terminals = spec.pop("terminals", None)
+        if spec:
+            raise ValueError("replay: unknown reliability keys %s" % sorted(spec))
+        if not 1 <= ensemble <= _lib.RELIAB_MAX_ENSEMBLE or out_dim < 1:
+            raise ValueError("replay: reliability needs the forward's scratch: ensemble in 1..%d and out_dim >= 1, got %d and %d"
+                             % (_lib.RELIAB_MAX_ENSEMBLE, ensemble, out_dim))
+        if not 1 <= len(columns) <= _lib.RELIAB_MAX_COLS:
+            raise ValueError("replay: reliability takes 1..%d columns, got %d" % (_lib.RELIAB_MAX_COLS, len(columns)))
+        if not 1 <= K <= _lib.RELIAB_MAX_BINS:
+            raise ValueError("replay: reliability bins must lie in 1..%d, got %d" % (_lib.RELIAB_MAX_BINS, K))
+        edges = default_edges(K) if edges is None else np.asarray(edges, np.float32).reshape(-1)
+        if edges.shape != (K - 1,) or not np.isfinite(edges).all() or not (np.diff(edges) > 0).all():
+            raise ValueError("replay: reliability edges must be %d ascending finite numbers" % (K - 1))
+        rr = _lib.ReplayReliabStruct()
+        rr.ensemble, rr.out_dim, rr.n_bins, rr.n_cols, rr.reserved = ensemble, out_dim, K, len(columns), 0
+        names = []
+        for j, c in enumerate(columns):
+            col, shift = int(c["col"]), float(c.get("shift", 0.0))
+            if not 0 <= col < out_dim:
+                raise ValueError("replay: reliability column %d outside the model's %d outputs" % (col, out_dim))
+            if c["target"] not in _lib.RELIAB_TARGETS:
+                raise ValueError("replay: reliability target is 'cost' or 'term', got %r" % (c["target"],))
+            if not np.isfinite(np.float32(shift)):
+                raise ValueError("replay: reliability shift must be a finite number, got %r" % (shift,))
+            rr.col[j], rr.target[j], rr.shift[j] = col, _lib.RELIAB_TARGETS[c["target"]], shift
+            names.append(str(c.get("name", c["target"])))
+        if len(set(names)) != len(names):
+            raise ValueError("replay: reliability columns need distinct names, got %s" % (names,))
+        if self.elite is None:
+            self.elite = torch.zeros((H, B), dtype=torch.int32, device=dev)
+        ns, nc = 2 * len(columns) * (2 * K + 2), 2 * len(columns) * 2 * K + 2 * len(columns)
+        self.r = dict(elite=self.elite, edges=torch.from_numpy(np.ascontiguousarray(edges)).to(dev),
+                      term=torch.zeros(0, dtype=torch.uint8, device=dev) if terminals is None
+                      else _as(terminals, torch.uint8, dev).reshape(H, B),
+                      part_sum=torch.zeros((H, self.n_part, ns), dtype=torch.float64, device=dev),
+                      part_cnt=torch.zeros((H, self.n_part, nc), dtype=torch.int64, device=dev),
+                      sums=torch.zeros((H, ns), dtype=torch.float64, device=dev),
+                      counts=torch.zeros((H, nc), dtype=torch.int64, device=dev))
+        for k, v in self.r.items():
+            setattr(rr, k, v.data_ptr() if v.numel() else None)
+        self.rr, self.rel_names, self.rel_edges, self.n_bins = rr, tuple(names), edges, K
 
     def step_outputs(self):
         """The dict ``FakeEnv.step_device`` fills: the prediction arrays ``cmbpo_replay_compare`` reads."""
@@ -114,10 +176,22 @@ class ReplayBuffers:
     def finish(self):
         _lib.check(_lib.lib().cmbpo_replay_finish(C.byref(self.rs), _lib.current_stream()), "cmbpo_replay_finish")
 
-    def run(self, model_handle, task_id, ensemble, elite, term_head=None, cost_head=None):
-        """``cmbpo_replay_run``; elite: [H, B] int32 device tensor.  term_head: a ``_lib.TermHeadStruct`` -- the learned
-        termination head in the post step (``cmbpo_replay_run_term``).  cost_head: a ``_lib.CostHeadStruct`` -- the reading of
-        the learned-cost column (``cmbpo_replay_run_cost``)."""
+    def _run_reliab(self, calib, model_handle, task_id, ensemble, elite, term_head, cost_head):
+        if elite is not None:
+            self.set_elite(elite)
+        ref = lambda s: C.byref(s) if s is not None else None
+        _lib.check(_lib.lib().cmbpo_replay_run_reliab(C.byref(self.rs), calib, C.byref(self.rr), ref(term_head), ref(cost_head),
+                                                      model_handle, int(task_id), int(ensemble), None, _lib.current_stream()),
+                   "cmbpo_replay_run_reliab")
+
+    def run(self, model_handle, task_id, ensemble, elite, term_head=None, cost_head=None, reliability=True):
+        """The narrowest run entry that can express the call.  ``cmbpo_replay_run``; elite: [H, B] int32 device tensor.
+        term_head: a ``_lib.TermHeadStruct`` -- the learned termination head in the post step (``cmbpo_replay_run_term``).
+        cost_head: a ``_lib.CostHeadStruct`` -- the reading of the learned-cost column (``cmbpo_replay_run_cost``).  Buffers built
+        with ``reliability=`` go through ``cmbpo_replay_run_reliab`` (elite is copied into their own array) unless
+        ``reliability=False``."""
+        if self.rr is not None and reliability:
+            return self._run_reliab(None, model_handle, task_id, ensemble, elite, term_head, cost_head)
         if cost_head is not None:
             _lib.check(_lib.lib().cmbpo_replay_run_cost(C.byref(self.rs), None, C.byref(term_head) if term_head is not None else None,
                                                         C.byref(cost_head), model_handle, int(task_id), int(ensemble),
@@ -141,9 +215,10 @@ class ReplayBuffers:
         return C.byref(self.cs)
 
     def set_elite(self, elite):
-        """The member of every window at every step, [H, B] (what ``calibrate`` and ``run_calibrated`` read)."""
-        self._calib()
-        self.c["elite"].copy_(_as(elite, torch.int32, self.device).reshape(self.H, self.B))
+        """The member of every window at every step, [H, B] (what ``calibrate``, ``reliab`` and the runs with either read)."""
+        if self.elite is None:
+            self._calib()
+        self.elite.copy_(_as(elite, torch.int32, self.device).reshape(self.H, self.B))
 
     def calibrate(self, h):
         """``cmbpo_replay_calibrate``: call it BEFORE ``compare(h)``, which clears ``alive`` and overwrites ``cur_obs``."""
@@ -154,9 +229,11 @@ class ReplayBuffers:
         _lib.check(_lib.lib().cmbpo_replay_calib_finish(C.byref(self.rs), self._calib(), _lib.current_stream()),
                    "cmbpo_replay_calib_finish")
 
-    def run_calibrated(self, model_handle, task_id, ensemble, elite=None, term_head=None, cost_head=None):
+    def run_calibrated(self, model_handle, task_id, ensemble, elite=None, term_head=None, cost_head=None, reliability=True):
         """``cmbpo_replay_run_calibrated``; elite: [H, B] members (None: those of the last ``set_elite``).  term_head,
-        cost_head: as in ``run``."""
+        cost_head, reliability: as in ``run``."""
+        if self.rr is not None and reliability:
+            return self._run_reliab(self._calib(), model_handle, task_id, ensemble, elite, term_head, cost_head)
         if elite is not None:
             self.set_elite(elite)
         if cost_head is not None:
@@ -176,6 +253,26 @@ class ReplayBuffers:
     def calibration_table(self):
         self._calib()
         return calibration_table(self.c["sums"].cpu().numpy(), self.c["counts"].cpu().numpy(), self.obs_dim)
+
+    # -- reliability of the logistic columns (reliability=dict(...)) ---------------------------------------------------
+    def _reliab(self):
+        if self.rr is None:
+            raise ValueError("replay: these buffers were built with reliability=None")
+        return C.byref(self.rr)
+
+    def reliab(self, h):
+        """``cmbpo_replay_reliab``: call it BEFORE ``compare(h)``, which clears ``alive`` and overwrites ``cur_obs``."""
+        _lib.check(_lib.lib().cmbpo_replay_reliab(C.byref(self.rs), self._reliab(), int(h), _lib.current_stream()),
+                   "cmbpo_replay_reliab")
+
+    def reliab_finish(self):
+        _lib.check(_lib.lib().cmbpo_replay_reliab_finish(C.byref(self.rs), self._reliab(), _lib.current_stream()),
+                   "cmbpo_replay_reliab_finish")
+
+    def reliability_table(self):
+        self._reliab()
+        return reliability_table(self.r["sums"].cpu().numpy(), self.r["counts"].cpu().numpy(), self.n_bins, self.rel_names,
+                                 edges=self.rel_edges)
 
 
 def table(sums, counts, obs_dim):
@@ -245,3 +342,77 @@ def temperature(cal, which="al", horizon=0, lo=0.25, hi=4.0):
         raise ValueError("temperature: 0 < lo <= hi < inf expected, got %r, %r" % (lo, hi))
     z2 = np.asarray(cal["z2_" + which], np.float64)[int(horizon), :-1]
     return np.where(np.isnan(z2), 1.0, np.clip(z2, lo, hi)).astype(np.float32)
+
+
+def default_edges(n_bins):
+    """The bin edges of ``n_bins`` equal-width PROBABILITY bins, in logit space: ``float32(logit(k / n_bins))``, k = 1 ..
+    n_bins - 1 (the logarithm in float64, one rounding to float32)."""
+    q = np.arange(1, int(n_bins), dtype=np.float64) / float(n_bins)
+    return np.log(q / (1.0 - q)).astype(np.float32)
+
+
+def reliability_table(sums, counts, n_bins, names, edges=None):
+    """The reliability dict from the raw ``sums`` [H, 2 C (2 K + 2)] (float64) and ``counts`` [H, 4 C K + 2 C] (int64) of C =
+    ``len(names)`` columns and K = ``n_bins`` bins: ``{name: column}``.  A column holds ``n_rel`` / ``n_skipped`` [H] (the rows
+    that entered / that the plain table sums and this column rejects), ``edges`` and, under ``'elite'`` and ``'pooled'`` (the
+    elite member's logit / the members' mean logit), the raw ``n``, ``pos``, ``sum_p``, ``sum_z`` [H, K], ``sum_brier``,
+    ``sum_logloss`` [H] and what follows from them: per bin ``conf = sum_p / n`` (what the column said), ``freq = pos / n`` (what
+    happened), ``zbar = sum_z / n``; per horizon ``ece = sum_k (n_k / N) |conf_k - freq_k|`` and ``mce`` (its largest gap) over
+    the non-empty bins, ``brier``, ``logloss``, ``base_rate = pos / N`` and ``mean_p``.  NaN where ``n == 0``."""
+    sums, counts = np.asarray(sums, np.float64), np.asarray(counts, np.int64)
+    H, K, Cn = sums.shape[0], int(n_bins), len(names)
+    if sums.shape != (H, 2 * Cn * (2 * K + 2)) or counts.shape != (H, 4 * Cn * K + 2 * Cn):
+        raise ValueError("reliability_table: sums [H, %d] and counts [H, %d] expected for %d columns of %d bins, got %s and %s"
+                         % (2 * Cn * (2 * K + 2), 4 * Cn * K + 2 * Cn, Cn, K, sums.shape, counts.shape))
+    s = sums.reshape(H, Cn, 2, 2 * K + 2)
+    c = counts[:, :4 * Cn * K].reshape(H, Cn, 2, 2 * K)
+    tail = counts[:, 4 * Cn * K:].reshape(H, Cn, 2)
+    out = {}
+    for j, name in enumerate(names):
+        col = dict(n_rel=tail[:, j, 0].copy(), n_skipped=tail[:, j, 1].copy(),
+                   edges=None if edges is None else np.asarray(edges, np.float32).copy())
+        for r, reading in enumerate(READINGS):
+            n, pos = c[:, j, r, :K].copy(), c[:, j, r, K:].copy()
+            d = dict(n=n, pos=pos, sum_p=s[:, j, r, :K].copy(), sum_z=s[:, j, r, K:2 * K].copy(),
+                     sum_brier=s[:, j, r, 2 * K].copy(), sum_logloss=s[:, j, r, 2 * K + 1].copy())
+            N = n.sum(axis=1)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                nf, Nf = n.astype(np.float64), N.astype(np.float64)
+                d["conf"], d["freq"], d["zbar"] = d["sum_p"] / nf, pos / nf, d["sum_z"] / nf
+                gap = np.where(n > 0, np.abs(d["conf"] - d["freq"]), 0.0)
+                nan = np.where(N > 0, 0.0, np.nan)
+                d["ece"] = (nf * gap).sum(axis=1) / Nf + nan
+                d["mce"] = gap.max(axis=1) + nan
+                d["brier"], d["logloss"] = d["sum_brier"] / Nf + nan, d["sum_logloss"] / Nf + nan
+                d["base_rate"], d["mean_p"] = pos.sum(axis=1) / Nf + nan, d["sum_p"].sum(axis=1) / Nf + nan
+            col[reading] = d
+        out[name] = col
+    return out
+
+
+def logit_offset(rel, column, reading="elite", horizon=0, lo=-2.0, hi=2.0, min_n=100):
+    """The logit offset b that makes the column's mean probability the observed rate at one horizon of a reliability table:
+    the root of ``sum_k n_k sigma(zbar_k - b) = sum_k pos_k`` over the non-empty bins, by 100 bisections of [-30, 30] in float64,
+    clipped to [lo, hi].  ``None`` where fewer than ``min_n`` rows entered (keep what you had).  This is calibration-in-the-
+    large THROUGH THE BIN MEANS -- every row of a bin stands at the bin's mean logit --, not an exact per-row solve; no positives
+    give ``hi``, only positives ``lo``.  Subtract b from the logit: ``sigma(z - b)``."""
+    if reading not in READINGS:
+        raise ValueError("logit_offset: reading is 'elite' or 'pooled', got %r" % (reading,))
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+        raise ValueError("logit_offset: finite lo <= hi expected, got %r, %r" % (lo, hi))
+    d = rel[column][reading]
+    n, pos = np.asarray(d["n"])[int(horizon)], np.asarray(d["pos"])[int(horizon)]
+    N = int(n.sum())
+    if N < max(int(min_n), 1):
+        return None
+    keep = n > 0
+    nk, zk, want = n[keep].astype(np.float64), np.asarray(d["zbar"], np.float64)[int(horizon)][keep], float(pos.sum())
+    a, b = -30.0, 30.0
+    for _ in range(100):
+        mid = 0.5 * (a + b)
+        if float((nk / (1.0 + np.exp(-(zk - mid)))).sum()) > want:       # too many predicted: a larger offset
+            a = mid
+        else:
+            b = mid
+    return float(min(max(0.5 * (a + b), lo), hi))

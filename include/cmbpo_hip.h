@@ -1228,6 +1228,75 @@ int cmbpo_replay_run_cost(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *
                           const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite,
                           void *stream);
 
+/* ---- reliability tables of the logistic columns in the replay (csrc/replay.hip) -------------
+ * Is a logistic column a PROBABILITY?  At horizon h of a replay the forward's mean[E][B][out_dim] scratch holds every member's
+ * logit beside the recorded cost / term flags; the reliability table bins the logits and holds, per bin, how often the event
+ * happened against what the column said.  Up to two RELIABILITY COLUMNS j: col[j] indexes the model's output (obs_dim + 1 for
+ * the logistic cost, the last column for the logistic termination head), shift[j] is subtracted from the logit first (the
+ * cost head's class-weight undo; 0 executes no subtraction, as in the post kernel's cost_prob), target[j] names the recorded
+ * flag: CMBPO_RELIAB_COST y = cost[h][b] > 0.5 (the rule the logistic cost is trained with), CMBPO_RELIAB_TERM y = term[h][b] != 0
+ * -- with the descriptor's own `term` array where it is given: the recorded `done` of a step is not always the head's training
+ * target (a time-out is target 0), and the table must be held against what the column was trained on, while the replay
+ * itself goes on ending windows at rp->term.
+ *   z'_e = fl32(mean[e][b][col[j]] - shift[j])
+ *
+ * A row ENTERS column j at h iff (a) alive[b] != 0 on entry to the step -- the call goes BEFORE that step's compare call, like
+ * the calibrate call --, (b) p_next_obs[b], p_rew[b], p_cost[b] are finite (the compare call's rule), (c) elite[h][b] lies in
+ * [0, ensemble) and z'_e is finite for every member e.  Rows with (a) and (b) but not (c) count in n_skipped[h][j], rows with
+ * all three in n_rel[h][j]; both per column; nothing else of a row that does not enter is summed.
+ *
+ * Two READINGS r per column, float64 arithmetic on the float32 inputs, every operation rounded separately, members in the
+ * order 0 .. E-1, m = elite[h][b]:
+ *   r = 0, elite:   z = (double)z'_m                    (what the cost and the 'elite' vote read)
+ *   r = 1, pooled:  z = (sum_e (double)z'_e) / E        (the mean logit: geometric pooling of the odds)
+ * The bin of z is #{k : z > (double)edges[k]}, k < n_bins - 1: bins live in LOGIT space, equality stays in the lower bin, no
+ * exponential decides a bin, so membership and every count are exact.  The rule is defined for ANY edges (a bin index is a
+ * count of edges below z); ascending, finite edges are what makes the bins intervals, and the host's to insist on.
+ *   y = 0.0 / 1.0     p = 1 / (1 + exp(-z))     l = max(z, 0) - y z + log1p(exp(-|z|))
+ *   brier = (p - y)^2, evaluated as q^2 with q = |p - y| = 1 / (1 + exp(y ? z : -z)): no cancellation where p is close to y
+ * Layout, with K = n_bins and C = n_cols, [j][r] running over 2 C (column, reading) pairs, j outermost:
+ *   sums   [H][2 C][2 K + 2]:  sum p [0 .. K) | sum z [0 .. K) | sum brier | sum l
+ *   counts [H][2 C (2 K) + 2 C]:  per [j][r]: n [0 .. K) | pos [0 .. K) (rows with y = 1);  behind all of them per j: n_rel | n_skipped
+ * Per-workgroup partials (slot = workgroup, cmbpo_replay_parts(B) slots per horizon, every entry of a slot written on every
+ * call; inside a slot a bin's rows are added in row order) added in slot order by the finish call: no floating-point atomics,
+ * two runs are bitwise equal.  Reads alive / predictions / recording / mean of the cmbpo_replay_t handed in beside the
+ * descriptor, writes its partial slot only; cmbpo_replay_t (184 bytes) and cmbpo_replay_calib_t (56) are what they were. */
+#define CMBPO_RELIAB_COST 0
+#define CMBPO_RELIAB_TERM 1
+#define CMBPO_RELIAB_MAX_BINS 32
+#define CMBPO_RELIAB_MAX_COLS 2
+#define CMBPO_RELIAB_MAX_ENSEMBLE 8
+
+typedef struct cmbpo_replay_reliab {
+  int32_t ensemble, out_dim, n_bins, n_cols, reserved;  /* members E (1..8); columns of mean; K (1..32); C (1..2); must be 0 */
+  int32_t col[2], target[2];  /* column of mean; CMBPO_RELIAB_COST / _TERM -- entries j >= n_cols are ignored */
+  float shift[2];           /* finite                                              */
+  const int32_t *elite;     /* [H,B] the member each window steps through at h     */
+  const float *edges;       /* [n_bins - 1] bin edges in logit space (may be NULL for n_bins == 1) */
+  const uint8_t *term;      /* [H,B] the flags CMBPO_RELIAB_TERM columns are held against; NULL: rp->term */
+  double *part_sum;         /* [H][cmbpo_replay_parts(B)][2 C (2 K + 2)]           */
+  int64_t *part_cnt;        /* [H][cmbpo_replay_parts(B)][4 C K + 2 C]             */
+  double *sums;             /* [H][2 C (2 K + 2)]                                  */
+  int64_t *counts;          /* [H][4 C K + 2 C]                                    */
+} cmbpo_replay_reliab_t; /* 104 bytes (4 of padding behind `shift`) */
+
+/* Every entry: CMBPO_EINVAL with a message naming the entry point for a NULL descriptor, a NULL array it uses, n_bins outside
+ * [1, 32], n_cols outside [1, 2], col[j] outside [0, out_dim), an unknown target, a non-finite shift, reserved != 0, ensemble
+ * outside [1, 8], h outside [0, H) and every shape refusal of the compare call -- all before any HIP call. */
+/* one horizon step of the reliability table, from the arrays the compare call of the same step reads plus rp->mean.  Enqueue it
+ * BEFORE that step's compare call (beside a calibrate call: in either order); it writes nothing but its partial slot. */
+int cmbpo_replay_reliab(const cmbpo_replay_t *rp, const cmbpo_replay_reliab_t *rr, int h, void *stream);
+/* partials -> rr->sums / rr->counts, all H horizons */
+int cmbpo_replay_reliab_finish(const cmbpo_replay_t *rp, const cmbpo_replay_reliab_t *rr, void *stream);
+/* The superset of the run entries: H x (forward -> post -> [calibrate] -> [reliab] -> compare), then the finish calls (plain,
+ * calibration, reliability), enqueued without a host wait; bitwise the single calls.  rr == NULL is exactly
+ * cmbpo_replay_run_cost's call.  With rr: `ensemble` must equal rr->ensemble and the model's out_dim rr->out_dim; the members
+ * are rr->elite, d_elite may be NULL or equal to it, and rc->elite (rc given) must equal it.  The plain table, the calibration
+ * table, cur_obs and alive are bitwise those of the run without rr on the same inputs. */
+int cmbpo_replay_run_reliab(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_replay_reliab_t *rr,
+                            const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model, int task,
+                            int ensemble, const int32_t *d_elite, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
