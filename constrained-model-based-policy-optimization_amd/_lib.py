@@ -241,6 +241,26 @@ SIGNATURES.update({
 })
 
 
+VOTE_MEAN = 3                                     # CMBPO_VOTE_MEAN: the expected indicator votes / E (the static cost only)
+RULE_DONE_MEMBERS = TERM_MEMBERS                  # whose vote ends a branch by the task's static termination rule
+RULE_COST_MEMBERS = dict(TERM_MEMBERS, mean=VOTE_MEAN)     # ... and whose vote a step costs by its static cost rule
+
+
+class RuleVotesStruct(C.Structure):
+    """ctypes image of ``cmbpo_rule_votes_t`` (24 bytes): the votes of the ensemble-voted static rules and their two optional
+    per-row outputs."""
+    _fields_ = [("done_members", C.c_int32), ("cost_members", C.c_int32), ("done_votes", C.c_void_p), ("cost_votes", C.c_void_p)]
+
+
+_rvp = C.POINTER(RuleVotesStruct)
+SIGNATURES.update({
+    "cmbpo_fakeenv_post_votes": (_i, [_i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i,
+                                      _p, _p, _p, _p, _p, _p, _p, _p, C.c_float, C.c_float, _p, _p, _tp, _chp, _p, _rvp, _p]),
+    "cmbpo_rollout_rule_votes_attach": (_i, [_rp, _rvp]),
+    "cmbpo_rollout_rule_votes_detach": (_i, [_rp]),
+})
+
+
 class PiBatchStruct(C.Structure):
     """ctypes image of ``cmbpo_pi_batch_t``."""
     _fields_ = [("n", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32)] + \

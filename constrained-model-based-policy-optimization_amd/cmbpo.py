@@ -27,7 +27,11 @@ on the way to them (``ModelBuffer(iv_gae=True, iv_eps=m_iv_eps)``: the weighted 
 rollouts (``msampler/rew_var_perstep``, ``msampler/cost_var_perstep``); ``m_rew_pessimism`` / ``m_cost_pessimism`` (kappa >= 0,
 > 0 implies the measurement) make the imagined reward ``r - kappa_r * sigma_r`` and the imagined learned cost
 ``c + kappa_c * sigma_c``: a constraint is no longer satisfied on the say-so of one member (``FakeEnv(disagreement=...)``).
-``m_cost_pessimism > 0`` needs ``m_learn_cost=True``.  Real samples and the rollout lengths are not affected.
+``m_cost_pessimism > 0`` needs ``m_learn_cost=True`` or the static votes.  ``m_static_term_members`` / ``m_static_cost_members``
+('elite' | 'any' | 'majority', the cost also 'mean') and ``m_static_votes`` (measure only) let the ensemble vote on the task's
+static termination / cost rule in the imagined rollouts (``FakeEnv(static_*_members=, static_votes=)``); with
+``m_disagreement`` ``msampler/cost_var_perstep`` then carries the static cost's spread.  The validation replay keeps the elite's
+rule.  Real samples and the rollout lengths are not affected.
 
 ``m_value_disagreement=True`` measures the variance over the members of both critics at every state an imagined rollout
 evaluates (``msampler/v_var_perstep``, ``msampler/vc_var_perstep``); ``m_v_pessimism`` / ``m_vc_pessimism`` (kappa >= 0, > 0
@@ -210,6 +214,24 @@ def _reliability_args(validate_horizon, use_model, cost_loss, term_loss, term_sa
     return bool(validate_reliability), bins, bool(recalibrate_cost), bool(recalibrate_term), (lo, hi)
 
 
+def _static_votes_args(use_model, learn_cost, term_members, cost_members, votes, cost_pessimism):
+    """``m_static_term_members`` / ``m_static_cost_members`` / ``m_static_votes`` checked against ``m_learn_cost`` and
+    ``m_cost_pessimism``, or a ValueError in words; returns whether the vote kernel runs."""
+    from . import _lib
+    if term_members not in _lib.RULE_DONE_MEMBERS:
+        raise ValueError("m_static_term_members: 'elite', 'any' or 'majority', got %r" % (term_members,))
+    if cost_members not in _lib.RULE_COST_MEMBERS:
+        raise ValueError("m_static_cost_members: 'elite', 'any', 'majority' or 'mean', got %r" % (cost_members,))
+    if cost_members != 'elite' and learn_cost:
+        raise ValueError("m_static_cost_members=%r needs m_learn_cost=False: with a learned cost the task's static cost rule is "
+                         "skipped, there is nothing to vote on" % (cost_members,))
+    on = bool(use_model) and (bool(votes) or term_members != 'elite' or cost_members != 'elite')
+    if float(cost_pessimism) > 0.0 and not learn_cost and not on:
+        raise ValueError("m_cost_pessimism > 0 needs m_learn_cost=True: only a learned cost head has an ensemble spread (or the "
+                         "static votes: m_static_votes=True or an m_static_*_members mode other than 'elite')")
+    return on
+
+
 def _term_sampling_args(learn_term, term_sampling):
     """``m_term_sampling`` checked against ``m_learn_term`` (and ``use_model``), or a ValueError in words."""
     if term_sampling and not learn_term:
@@ -331,12 +353,16 @@ class CMBPO:
                  m_term_pos_weight=1.0, m_term_loss_weight=1.0, m_cost_loss_weight=1.0, m_pos_weight_max=20.0,
                  m_term_loss='gaussian', m_cost_loss='gaussian', m_cost_pos_weight=1.0, m_cost_pos_weight_undo=False,
                  m_term_sampling=False, m_validate_reliability=False, m_reliability_bins=15, m_recalibrate_cost=False,
-                 m_recalibrate_term=False, m_recalibration_range=(-2.0, 2.0), **_unused):
+                 m_recalibrate_term=False, m_recalibration_range=(-2.0, 2.0),
+                 m_static_term_members='elite', m_static_cost_members='elite', m_static_votes=False, **_unused):
         # column / class weights of the model's binary columns; refused in words before anything is built
         self._column_weights = _column_weight_args(bool(m_learn_term) and bool(use_model), bool(m_learn_cost), m_term_pos_weight,
                                                    m_term_loss_weight, m_cost_loss_weight, m_pos_weight_max)
         # the likelihood of the termination column; likewise
         self._m_term_loss = _term_loss_args(bool(m_learn_term) and bool(use_model), m_term_loss, m_term_threshold)
+        # ensemble-voted static rules; likewise
+        self._static_votes_on = _static_votes_args(use_model, bool(m_learn_cost), m_static_term_members, m_static_cost_members,
+                                                   m_static_votes, m_cost_pessimism)
         # sampled terminations; likewise
         self._m_term_sampling = _term_sampling_args(bool(m_learn_term) and bool(use_model), m_term_sampling)
         # the likelihood and the class weight of the cost column; likewise
@@ -389,8 +415,6 @@ class CMBPO:
                 raise ValueError("m_term_threshold must be a finite number, got %r" % (m_term_threshold,))
             if m_term_members not in _lib.TERM_MEMBERS:
                 raise ValueError("m_term_members: 'elite', 'any' or 'majority', got %r" % (m_term_members,))
-        if float(m_cost_pessimism) > 0.0 and not self._m_learn_cost:
-            raise ValueError("m_cost_pessimism > 0 needs m_learn_cost=True: only a learned cost head has an ensemble spread")
         # critic disagreement: kappa > 0 implies the measurement; only the one-launch critic kernels measure it
         kv, kvc = float(m_v_pessimism), float(m_vc_pessimism)
         if not (np.isfinite(kv) and kv >= 0.0 and np.isfinite(kvc) and kvc >= 0.0):
@@ -444,7 +468,8 @@ class CMBPO:
                                     disagreement=bool(m_disagreement), rew_pessimism=m_rew_pessimism,
                                     cost_pessimism=m_cost_pessimism, predicts_term=self._m_learn_term,
                                     term_threshold=m_term_threshold, term_members=m_term_members, term_loss=m_term_loss,
-                                    cost_loss=m_cost_loss)
+                                    cost_loss=m_cost_loss, static_term_members=m_static_term_members,
+                                    static_cost_members=m_static_cost_members, static_votes=bool(m_static_votes))
             self.rollout_mode = rollout_mode
             self.model_buf = ModelBuffer(batch_size=self._rollout_batch_size, obs_dim=self.obs_dim, act_dim=self.act_dim,
                                          max_path_length=maxroll, device=self.device, iv_gae=bool(m_iv_gae),

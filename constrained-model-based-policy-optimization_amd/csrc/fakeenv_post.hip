@@ -585,7 +585,7 @@ int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream) {
   // the naming rule (fakeenv_post_internal.h, DESIGN): the narrowest entry point that can express the call
   // (kind 0 is the magnitude reading: the instances without the head; `ch` below is the LOGISTIC head or NULL)
   const cmbpo_cost_head_t *ch = (c.ch != nullptr && c.ch->kind == 1) ? c.ch : nullptr;
-  const char *who = c.term_thr ? "cmbpo_fakeenv_post_term_draws" : c.ch ? "cmbpo_fakeenv_post_cost" : th ? "cmbpo_fakeenv_post_term" : dis ? "cmbpo_fakeenv_post_disagreement"
+  const char *who = c.rv ? "cmbpo_fakeenv_post_votes" : c.term_thr ? "cmbpo_fakeenv_post_term_draws" : c.ch ? "cmbpo_fakeenv_post_cost" : th ? "cmbpo_fakeenv_post_term" : dis ? "cmbpo_fakeenv_post_disagreement"
                     : c.xi ? "cmbpo_fakeenv_post_noise" : "cmbpo_fakeenv_post";
   const int obs_dim = c.obs_dim, act_dim = c.act_dim, ensemble = c.ensemble;
   const int learned_cost = (c.task & CMBPO_TASK_LEARNED_COST) ? 1 : 0;     // every other bit outside the rule id is an error
@@ -611,6 +611,9 @@ int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream) {
     CMBPO_REQUIRE(c.ch->kind == 0 || learned_cost,
                   "%s: cost head: kind 1 (logistic) needs CMBPO_TASK_LEARNED_COST (a static cost rule has no logit), task %d", who, task_arg);
   }
+  // (host code: the votes' modes, the byte mask, the learned-cost refusal, the head's two outputs)
+  if (c.rv != nullptr)
+    if (int rc = cmbpo_internal_rule_votes_check(who, c)) return rc;
   PostArgsDerived ar{};
   if (user)     // (registered? columns inside obs_dim / act_dim? -- host code, before any HIP call)
     if (int rc = cmbpo_internal_task_rules_resolve(who, task_arg, obs_dim, act_dim, c.act != nullptr, &ar.rules, &ar.der)) return rc;
@@ -621,13 +624,20 @@ int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream) {
     // (x >= 0 is false for a NaN; the infinities are excluded on their own)
     CMBPO_REQUIRE(dis->kappa_rew >= 0.0f && isfinite(dis->kappa_rew), "%s: kappa_rew %g is not a finite number >= 0", who, (double)dis->kappa_rew);
     CMBPO_REQUIRE(dis->kappa_cost >= 0.0f && isfinite(dis->kappa_cost), "%s: kappa_cost %g is not a finite number >= 0", who, (double)dis->kappa_cost);
-    CMBPO_REQUIRE(!(dis->kappa_cost > 0.0f) || learned_cost,
+    // (with the votes a static cost has a member spread: the vote kernel applies kappa_cost, the post kernel gets 0 below)
+    CMBPO_REQUIRE(!(dis->kappa_cost > 0.0f) || learned_cost || c.rv != nullptr,
                   "%s: kappa_cost %g > 0 needs CMBPO_TASK_LEARNED_COST (a static cost rule has no member spread), task %d", who,
                   (double)dis->kappa_cost, task_arg);
     CMBPO_REQUIRE(dis->rew_var && dis->cost_var, "%s: NULL buffer (d_rew_var / d_cost_var)", who);
   }
   CMBPO_REQUIRE(c.n_rows >= 0 && c.ld_rows >= c.n_rows, "%s: n_rows %d / ld_rows %d", who, c.n_rows, c.ld_rows);
   if (c.n_rows == 0) return CMBPO_OK;
+  DisExtra dis_post;
+  if (dis != nullptr && c.rv != nullptr && !learned_cost) {
+    dis_post = *dis;
+    dis_post.kappa_cost = 0.0f;     // (the post kernel does not read it with a static cost; its check of the call is the one above)
+    dis = &dis_post;
+  }
   PostArgs a{};
   a.task = task; a.ensemble = ensemble; a.obs_dim = obs_dim; a.act_dim = act_dim;
   a.out_dim = obs_dim + 1 + learned_cost + (th ? 1 : 0);  // delta-obs + reward (+ cost: algorithms/cmbpo.py:121-123, m_learn_cost) (+ the termination head's column)
@@ -661,10 +671,12 @@ int cmbpo_internal_fakeenv_post(const FakeenvPostCall &c, void *stream) {
   else if (user) launch_post_ext<1, false>(ensemble, grid, lds, s, ar, dis, th, c.term_thr, ch);
   else launch_post_ext<0, false>(ensemble, grid, lds, s, a, dis, th, c.term_thr, ch);
   CMBPO_HIP_CHECK(hipGetLastError());
+  // the votes: one more kernel behind the post kernel, on the same stream; it overwrites term, cost and (dis_on) cost_var
+  if (c.rv != nullptr) return cmbpo_internal_rule_votes_launch(c, task, a.out_dim, user ? &ar.rules : nullptr, derived ? &ar.der : nullptr, stream);
   return CMBPO_OK;
 }
 
-// The six public entry points fill the descriptor and make that call; none forwards to another.  POST_COMMON: the 20 leading
+// The seven public entry points fill the descriptor and make that call; none forwards to another.  POST_COMMON: the 20 leading
 // parameters they share (the stream goes beside the descriptor).
 #define POST_COMMON                                                                                                              \
   int task, int ensemble, int obs_dim, int act_dim, const float *d_mean, const float *d_var, int ld_rows, const float *d_obs,    \
@@ -744,6 +756,22 @@ extern "C" int cmbpo_fakeenv_post_term_draws(POST_COMMON, const float *d_xi, flo
   c.th = th;
   c.ch = ch;
   c.term_thr = d_term_thr;
+  return cmbpo_internal_fakeenv_post(c, stream);
+}
+
+// ... with the ensemble-voted static rules (csrc/rule_votes.hip and the header): the superset -- every feature is optional;
+// rv == NULL is cmbpo_fakeenv_post_term_draws's call
+extern "C" int cmbpo_fakeenv_post_votes(POST_COMMON, const float *d_xi, float kappa_rew, float kappa_cost, float *d_rew_var,
+                                        float *d_cost_var, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch,
+                                        const float *d_term_thr, const cmbpo_rule_votes_t *rv, void *stream) {
+  FakeenvPostCall c = post_common(POST_COMMON_ARGS);
+  c.xi = d_xi;
+  c.dis_on = d_rew_var != nullptr || d_cost_var != nullptr || kappa_rew != 0.0f || kappa_cost != 0.0f;
+  c.dis = DisExtra{kappa_rew, kappa_cost, d_rew_var, d_cost_var};
+  c.th = th;
+  c.ch = ch;
+  c.term_thr = d_term_thr;
+  c.rv = rv;
   return cmbpo_internal_fakeenv_post(c, stream);
 }
 

@@ -3,7 +3,7 @@
 #include "common.h"
 
 // what is attached beside *r (cmbpo_rollout_iv_attach / _disagreement_attach / _value_disagreement_attach / _term_head_attach /
-// _cost_head_attach / _term_draws_attach); a feature that is not: all-zero (an all-zero cmbpo_term_head_t is a valid head and an all-zero
+// _cost_head_attach / _term_draws_attach / _rule_votes_attach); a feature that is not: all-zero (an all-zero cmbpo_term_head_t is a valid head and an all-zero
 // cmbpo_cost_head_t the magnitude reading, so those two have a flag)
 struct RolloutSide {
   cmbpo_iv_gae_t iv;
@@ -15,6 +15,8 @@ struct RolloutSide {
   int ch_on;
   const float *thr;       // sampled terminations: this step's thresholds [B], slot indexed; NULL: the head's own threshold
   long thr_stride;        // floats between two steps of a cmbpo_rollout_run call
+  cmbpo_rule_votes_t rv;  // ensemble-voted static rules (an all-zero struct is the valid measure-nothing vote: a flag)
+  int rv_on;
 };
 RolloutSide cmbpo_internal_side_lookup(const cmbpo_rollout_t *r);
 

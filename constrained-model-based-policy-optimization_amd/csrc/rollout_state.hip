@@ -9,6 +9,7 @@
 // buffers make both the per-step store and the per-branch backward GAE recurrence coalesced
 // (adjacent lanes = adjacent branches).
 #include "common.h"
+#include "fakeenv_post_internal.h"
 #include "rollout_internal.h"
 #include <type_traits>
 
@@ -1313,7 +1314,8 @@ void side_update(const cmbpo_rollout_t *r, Change change) {
   std::lock_guard<std::mutex> lock(g_side_mu);
   RolloutSide &sd = g_side[r->iscal];
   change(sd);
-  if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr && sd.vd.part == nullptr && !sd.th_on && !sd.ch_on && sd.thr == nullptr)
+  if (sd.iv.cumvar_buf == nullptr && sd.dg.part == nullptr && sd.vd.part == nullptr && !sd.th_on && !sd.ch_on && sd.thr == nullptr &&
+      !sd.rv_on)
     g_side.erase(r->iscal);
 }
 
@@ -1406,6 +1408,21 @@ extern "C" int cmbpo_rollout_cost_head_attach(const cmbpo_rollout_t *r, const cm
 extern "C" int cmbpo_rollout_cost_head_detach(const cmbpo_rollout_t *r) {
   CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_cost_head_detach: NULL rollout struct / iscal");
   side_update(r, [](RolloutSide &sd) { sd.ch = {}; sd.ch_on = 0; });
+  return CMBPO_OK;
+}
+
+extern "C" int cmbpo_rollout_rule_votes_detach(const cmbpo_rollout_t *r) {
+  CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_rule_votes_detach: NULL rollout struct / iscal");
+  side_update(r, [](RolloutSide &sd) { sd.rv = {}; sd.rv_on = 0; });
+  return CMBPO_OK;
+}
+
+// (what the votes need of the task and of an attached termination head is the step's question: they attach in any order)
+extern "C" int cmbpo_rollout_rule_votes_attach(const cmbpo_rollout_t *r, const cmbpo_rule_votes_t *rv) {
+  CMBPO_REQUIRE(r != nullptr && r->iscal != nullptr, "cmbpo_rollout_rule_votes_attach: NULL rollout struct / iscal");
+  if (rv == nullptr) return cmbpo_rollout_rule_votes_detach(r);
+  if (int rc = cmbpo_internal_rule_votes_check_struct("cmbpo_rollout_rule_votes_attach", rv)) return rc;
+  side_update(r, [&](RolloutSide &sd) { sd.rv = *rv; sd.rv_on = 1; });      // (no kernel of this file reads it: the one-call step hands it to the post step)
   return CMBPO_OK;
 }
 

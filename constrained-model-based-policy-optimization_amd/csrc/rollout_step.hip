@@ -49,6 +49,13 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   CMBPO_REQUIRE(sd.thr == nullptr || sd.th_on,
                 "cmbpo_rollout_step: termination draws are attached (cmbpo_rollout_term_draws_attach) without a termination head "
                 "(cmbpo_rollout_term_head_attach): there is no column to compare them with");
+  // ensemble-voted static rules: what the post step would refuse at the third launch -- the learned-cost refusal, a termination
+  // head without its two outputs -- refused before the first
+  if (sd.rv_on) {
+    FakeenvPostCall chk{};
+    chk.task = task; chk.ensemble = ensemble; chk.th = sd.th_on ? &sd.th : nullptr; chk.rv = &sd.rv;
+    if (int rc0 = cmbpo_internal_rule_votes_check("cmbpo_rollout_step", chk)) return rc0;
+  }
   if (sd.th_on)
     CMBPO_REQUIRE(model->out_dim == r->obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0) + 1,
                   "cmbpo_rollout_step: a termination head (cmbpo_term_head_t) is attached: model out_dim %d does not match obs_dim %d + 1 "
@@ -92,6 +99,7 @@ static int step_impl(const cmbpo_rollout_t *r, int n_alive, cmbpo_mlp_t *policy,
   pc.th = sd.th_on ? &sd.th : nullptr;
   pc.ch = sd.ch_on ? &sd.ch : nullptr;
   pc.term_thr = sd.thr ? sd.thr + (size_t)run_step * (size_t)sd.thr_stride : nullptr;     // step j of a run: as xi_at does for xi
+  pc.rv = sd.rv_on ? &sd.rv : nullptr;        // ensemble-voted static rules: the vote kernel behind the post kernel
   if ((rc = cmbpo_internal_fakeenv_post(pc, stream))) return rc;
   const bool small = ahead.on || (n_alive <= cmbpo_rollout_book_pre_max_rows() && !r->use_host_budget);
   // small batches: decide + finish(PRE) + the store's scalar half in one launch; its vector half (obs, act, mu, log_std) rides

@@ -25,7 +25,8 @@ prediction, not thresholded.
 ``predicts_cost``, of the cost column; without it the cost variance is 0).  ``rew_pessimism`` / ``cost_pessimism`` (kappa >= 0;
 > 0 switches the measurement on) make the returned reward ``r - kappa_r * sqrt(rew_var)`` and the learned cost
 ``c + kappa_c * sqrt(cost_var)`` (``cmbpo_fakeenv_post_disagreement``); ``set_pessimism(rew, cost)`` changes them later.
-``cost_pessimism > 0`` needs ``predicts_cost``: a static cost rule has no member spread.  Off (the default) the calls made
+``cost_pessimism > 0`` needs ``predicts_cost`` or the static votes below: a static cost rule judged on the elite's state alone
+has no member spread.  Off (the default) the calls made
 and the keys returned are what they were.
 
 ``predicts_term=True`` (no counterpart in the reference, ``m_learn_term`` of the trainer): the model has one more
@@ -53,6 +54,17 @@ and adds ``info['cost_logit']`` (the elite's raw logit); ``set_cost_head(loss, l
 ``cost_logit_shift = log(omega)`` undoes a class weight omega the column was trained with.  Targets above 0.5 count as 1, so a
 task whose cost is a magnitude, not an indicator, should keep the default ``'gaussian'``.
 
+``static_term_members`` / ``static_cost_members`` (``'elite'`` | ``'any'`` | ``'majority'``, the cost also ``'mean'``)
+let the ensemble VOTE on the task's own static rules: the termination and cost rule (``AntSafe``, ``HCS``, a ``TaskRules`` table)
+are evaluated on every member's predicted next state, not only on the elite's, and a branch ends / a step costs by the elite's
+verdict (what it always was), any member's, more than half of all members', or -- the cost only -- the share of members
+``votes / E``.  ``static_votes=True`` measures without changing a verdict.  The vote kernel runs iff a mode is not ``'elite'`` or
+``static_votes`` is set; ``step()`` then adds ``info['static_term_votes']`` / ``info['static_cost_votes']`` (uint8), and with
+``disagreement`` ``info['ensemble_cost_var']`` carries the static cost's spread, which ``cost_pessimism > 0`` may now act on
+(``min(1, c + kappa_c * sqrt(var))``).  ``static_cost_members != 'elite'`` needs ``predicts_cost=False`` (a learned cost skips the
+static rule).  ``set_static_votes(...)`` changes them later.  A replay keeps the elite's rule.  Off (the default) the calls made and
+the keys returned are what they were.
+
 ``replay(...)`` has no counterpart in the reference: it replays windows of real steps through the model with the recorded
 actions and returns, per horizon, how far the predictions are from the recording (open-loop model validation).
 ``replay(..., reliability=True)`` also measures whether a logistic column is a probability, and
@@ -74,7 +86,8 @@ class FakeEnv:
     def __init__(self, true_environment, task, model, predicts_delta, predicts_rew, predicts_cost,
                  seed=0, disagreement=False, rew_pessimism=0.0, cost_pessimism=0.0,
                  predicts_term=False, term_threshold=0.5, term_members='elite', term_loss='gaussian',
-                 cost_loss='gaussian', cost_logit_shift=0.0):
+                 cost_loss='gaussian', cost_logit_shift=0.0,
+                 static_term_members='elite', static_cost_members='elite', static_votes=False):
         self.env = true_environment
         self.obs_dim = int(np.prod(self.observation_space.shape))
         self.act_dim = int(np.prod(self.action_space.shape))
@@ -106,6 +119,8 @@ class FakeEnv:
         self._replay_rng = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(1,)))
         self._disagreement = bool(disagreement)
         self.rew_pessimism = self.cost_pessimism = 0.0
+        self.static_term_members, self.static_cost_members, self.static_votes = 'elite', 'elite', False
+        self.set_static_votes(static_term_members, static_cost_members, static_votes)
         self.set_pessimism(rew_pessimism, cost_pessimism)
         self.term_threshold, self.term_members, self.term_loss = 0.5, 'elite', 'gaussian'
         if term_loss not in ('gaussian', 'logistic'):
@@ -139,9 +154,46 @@ class FakeEnv:
         rew, cost = float(rew), float(cost)
         if not (np.isfinite(rew) and rew >= 0.0 and np.isfinite(cost) and cost >= 0.0):
             raise ValueError(f"rew_pessimism / cost_pessimism must be finite numbers >= 0, got {rew}, {cost}")
-        if cost > 0.0 and not self._predicts_cost:
-            raise ValueError("cost_pessimism > 0 needs predicts_cost=True: a static cost rule has no ensemble spread")
+        if cost > 0.0 and not self._predicts_cost and not self.static_votes_on:
+            raise ValueError("cost_pessimism > 0 needs predicts_cost=True: a static cost rule has no ensemble spread (unless the "
+                             "members vote on it: static_votes=True or a static_*_members mode other than 'elite')")
         self.rew_pessimism, self.cost_pessimism = rew, cost
+
+    @property
+    def static_votes_on(self):
+        """True when the vote kernel runs behind the post kernel: a mode other than 'elite', or ``static_votes``."""
+        return self.static_votes or self.static_term_members != 'elite' or self.static_cost_members != 'elite'
+
+    def set_static_votes(self, term_members=None, cost_members=None, votes=None):
+        """Whose verdict of the task's static termination rule ends a branch ('elite' / 'any' / 'majority') and whose verdict of
+        its static cost rule a step costs (those, or 'mean': votes / E); ``votes=True`` measures the votes without changing a
+        verdict.  None leaves a setting as it is."""
+        tm = self.static_term_members if term_members is None else term_members
+        cm = self.static_cost_members if cost_members is None else cost_members
+        on = self.static_votes if votes is None else bool(votes)
+        if tm not in _lib.RULE_DONE_MEMBERS:
+            raise ValueError(f"static_term_members: 'elite', 'any' or 'majority', got {tm!r}")
+        if cm not in _lib.RULE_COST_MEMBERS:
+            raise ValueError(f"static_cost_members: 'elite', 'any', 'majority' or 'mean', got {cm!r}")
+        if cm != 'elite' and self._predicts_cost:
+            raise ValueError(f"static_cost_members={cm!r} needs predicts_cost=False: with a learned cost the task's static cost "
+                             "rule is skipped, there is nothing to vote on")
+        if not (on or tm != 'elite' or cm != 'elite') and self.cost_pessimism > 0.0 and not self._predicts_cost:
+            raise ValueError("the static votes cannot be switched off while cost_pessimism > 0 acts on a static cost "
+                             "(set_pessimism(rew, 0.0) first)")
+        self.static_term_members, self.static_cost_members, self.static_votes = tm, cm, on
+
+    def rule_votes_struct(self, done_votes=None, cost_votes=None):
+        """The ``cmbpo_rule_votes_t`` of the static votes (None when they are off: the call without the vote kernel); the two
+        optional outputs are device tensors or None (no cost votes with a learned cost)."""
+        if not self.static_votes_on:
+            return None
+        rv = _lib.RuleVotesStruct()
+        rv.done_members = _lib.RULE_DONE_MEMBERS[self.static_term_members]
+        rv.cost_members = _lib.RULE_COST_MEMBERS[self.static_cost_members]
+        rv.done_votes = _lib.ptr(done_votes)
+        rv.cost_votes = None if self._predicts_cost else _lib.ptr(cost_votes)
+        return rv
 
     @property
     def predicts_term(self):
@@ -257,6 +309,8 @@ class FakeEnv:
         ``term_loss='logistic'`` term_pred carries the logit).  With ``cost_loss='logistic'`` cost is the probability and out's
         optional cost_logit[B] is filled with the elite's raw logit.  term_thr: [B] float32 thresholds of the sampled
         terminations, in the column's own units (``utils.term_thresholds``), in place of the head's threshold; None: the head's.
+        With the static votes on (``static_votes_on``) term / cost are the voted ones, out's optional static_term_votes[B] /
+        static_cost_votes[B] u8 are filled, and with `predicts_term` out's term_pred and term_votes are required.
         """
         B = obs.shape[0]
         if term_thr is not None:
@@ -298,7 +352,10 @@ class FakeEnv:
                 _lib.ptr(out["term"]), _lib.ptr(out["cost"]), _lib.ptr(out["dkl_path"]), _lib.ptr(out["ep_var_mean"]),
                 _lib.ptr(out.get("ep_var")), _lib.ptr(noise), *dis, C.byref(th) if th is not None else None,
                 C.byref(ch) if ch is not None else None)
-        if term_thr is None:
+        rv = self.rule_votes_struct(out.get("static_term_votes"), out.get("static_cost_votes"))
+        if rv is not None:      # the votes on the static rules: the same call with the thresholds (or NULL) and the votes behind it
+            _lib.check(lib.cmbpo_fakeenv_post_votes(*args, _lib.ptr(term_thr), C.byref(rv), stream), "cmbpo_fakeenv_post_votes")
+        elif term_thr is None:
             _lib.check(lib.cmbpo_fakeenv_post_cost(*args, stream), "cmbpo_fakeenv_post_cost")
         else:       # sampled terminations: the same call with the thresholds behind it
             _lib.check(lib.cmbpo_fakeenv_post_term_draws(*args, _lib.ptr(term_thr), stream), "cmbpo_fakeenv_post_term_draws")
@@ -358,6 +415,9 @@ class FakeEnv:
                 out.update(term_pred=torch.empty(n, **f), term_votes=torch.empty(n, dtype=torch.uint8, device=self.device))
             if self.cost_loss == 'logistic':
                 out.update(cost_logit=torch.empty(n, **f))
+            if self.static_votes_on:
+                out.update(static_term_votes=torch.zeros(n, dtype=torch.uint8, device=self.device),
+                           static_cost_votes=torch.zeros(n, dtype=torch.uint8, device=self.device))
             self.step_device(o, a, inds, out, noise=xi, term_thr=thr)
         next_obs, r, terms = out["next_obs"], out["rew"][:, None], out["term"].bool()[:, None]
         c = out["cost"][:, None]
@@ -388,6 +448,11 @@ class FakeEnv:
         if self.cost_loss == 'logistic':
             cl = out["cost_logit"]
             info["cost_logit"] = cl.cpu().numpy() if was_np else cl
+        if self.static_votes_on:
+            tv, cv = out["static_term_votes"], out["static_cost_votes"]      # (cost votes with a learned cost: zeros, nothing voted)
+            if was_np:
+                tv, cv = tv.cpu().numpy(), cv.cpu().numpy()
+            info["static_term_votes"], info["static_cost_votes"] = tv, cv
         return next_obs, r, terms, info
 
     def replay(self, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, model_inds=None, mode='open_loop',

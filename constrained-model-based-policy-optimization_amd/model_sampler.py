@@ -30,6 +30,10 @@ step, the native loop and the sharded per-step path alike; ``pool.t['term_pred_t
 ``reset()`` also takes the reading of the learned-cost column (``FakeEnv(cost_loss='logistic', cost_logit_shift=...)``, DESIGN
 §3w): every step then stores the cost as a probability, and ``pool.t['cost_logit_t']`` holds the step's raw logits.
 
+``reset()`` also takes the votes on the task's static rules (``FakeEnv(static_term_members=..., static_cost_members=...,
+static_votes=...)``): every step then evaluates the rules on every member's next state, ends a branch / charges a
+step by the vote, and ``pool.t['rule_done_votes_t']`` / ``['rule_cost_votes_t']`` hold the step's votes; no new random numbers.
+
 ``ModelSampler(term_sampling=True)`` SAMPLES the learned termination (needs an ``env`` with ``predicts_term``): a
 branch whose termination column says p ends with probability p instead of where p is above the head's threshold.  The sampler
 draws u = 1 - rand() in (0, 1] per branch and step from a generator of its own (seeded ``seed + 1``), a whole chunk ``[K, B]``
@@ -294,6 +298,10 @@ class ModelSampler:
             # (with a recalibration offset: the float32 sum of the two, FakeEnv.cost_kernel_shift)
             pool.set_cost_head(getattr(self.env, "cost_loss", "gaussian"),
                                getattr(self.env, "cost_kernel_shift", getattr(self.env, "cost_logit_shift", 0.0)))
+            # ... and whose verdict of the task's static rules counts (the vote kernel behind the post kernel; off: nothing attached)
+            pool.set_rule_votes(getattr(self.env, "static_votes_on", False), getattr(self.env, "static_term_members", "elite"),
+                                getattr(self.env, "static_cost_members", "elite"),
+                                not getattr(self.env, "_predicts_cost", False))
             if observations is None:
                 fill(pool.t["cur_obs"])
             else:
@@ -422,6 +430,8 @@ class ModelSampler:
                 outs.update(term_pred=t["term_pred_t"], term_votes=t["term_votes_t"])
             if pool.cost_head is not None:
                 outs.update(cost_logit=t["cost_logit_t"])
+            if pool.rule_votes is not None:
+                outs.update(static_term_votes=t["rule_done_votes_t"], static_cost_votes=t["rule_cost_votes_t"])
             env.step_device(t["cur_obs"], t["act_t"], inds_t, outs,
                             row_idx=idx, n_rows=n, scratch=self._scratch, noise=xi_t,
                             **({} if thr_t is None else dict(term_thr=thr_t)))

@@ -38,6 +38,11 @@ allocated and nothing is measured.
 returned sample, ``ref_var / (ref_var + accumulated variance)`` from the same ``cumvar_buf`` (1 where the model has accumulated
 no variance, 1/2 at ``ref_var``; with ``ref_var = iv_eps`` proportional to the GAE's own weight) -- for the weighted policy and
 critic updates.  What ``get()`` returns is unchanged.
+
+``set_rule_votes(on, term_members, cost_members)`` attaches the votes on the task's static rules (``cmbpo_rule_votes_t``, DESIGN
+3za): the one-call step and the native loop then evaluate the termination / cost rule on every member's next state, ``term_t`` /
+``cost_t`` (and, with the disagreement, ``cost_var_t``) are the voted ones, and ``rule_done_votes_t`` / ``rule_cost_votes_t`` [B]
+hold the step's votes.  Off (the default) nothing is allocated, nothing is attached and no kernel is added.
 """
 import collections
 import ctypes as C
@@ -103,6 +108,14 @@ def _cost_fill(buf, ch):
     ch.cost_logit = buf.t["cost_logit_t"].data_ptr()
 
 
+def _votes_fill(buf, rv):
+    t = buf.t
+    rv.done_members = _lib.RULE_DONE_MEMBERS[buf.rule_votes[0]]
+    rv.cost_members = _lib.RULE_COST_MEMBERS[buf.rule_votes[1]]
+    rv.done_votes = t["rule_done_votes_t"].data_ptr()
+    rv.cost_votes = t["rule_cost_votes_t"].data_ptr() if buf.rule_votes[2] else None
+
+
 # The features kept beside the rollout struct, in the order they are attached: is it on, the arrays it owns in ``self.t``
 # ((name, shape, dtype) for capacity B and horizon T: allocated zeroed when it is switched on, freed when it is switched off), its
 # struct and how to fill it, the entry points that attach and detach it.  The next feature is one more row.
@@ -125,6 +138,9 @@ _SIDE = {
     "term": _Side(lambda buf: buf.term_head is not None,
                   lambda B, T: (("term_pred_t", (B,), torch.float32), ("term_votes_t", (B,), torch.uint8)),
                   _lib.TermHeadStruct, _term_fill, "cmbpo_rollout_term_head_attach", "cmbpo_rollout_term_head_detach"),
+    "votes": _Side(lambda buf: buf.rule_votes is not None,
+                   lambda B, T: (("rule_done_votes_t", (B,), torch.uint8), ("rule_cost_votes_t", (B,), torch.uint8)),
+                   _lib.RuleVotesStruct, _votes_fill, "cmbpo_rollout_rule_votes_attach", "cmbpo_rollout_rule_votes_detach"),
     "cost": _Side(lambda buf: buf.cost_head is not None,
                   lambda B, T: (("cost_logit_t", (B,), torch.float32),),
                   _lib.CostHeadStruct, _cost_fill, "cmbpo_rollout_cost_head_attach", "cmbpo_rollout_cost_head_detach"),
@@ -174,6 +190,7 @@ class ModelBuffer:
         self.value_disagreement, self.v_pessimism, self.vc_pessimism = False, 0.0, 0.0
         self.term_head = None                 # (threshold, members) of the learned termination head, None: off
         self.cost_head = None                 # (loss, logit_shift) of a logistic learned-cost head, None: the magnitude reading
+        self.rule_votes = None                # (term members, cost members, count the cost votes) of the static votes, None: off
         self.trust_var, self.last_weights = None, None
         self.rs = None
         self._iv_key = [0]                    # iscal of the arrays the library's table may hold an entry for
@@ -337,6 +354,26 @@ class ModelBuffer:
             raise RuntimeError("set_cost_head: the buffer holds samples (call it after get() / reset())")
         self.cost_head = head
         self._side_sync("cost")
+
+    # -- ensemble-voted static rules --------------------------------------------------------------------
+    def set_rule_votes(self, on, term_members='elite', cost_members='elite', cost_votes=True):
+        """Let the ensemble vote on the task's static termination / cost rule along the rollout (``FakeEnv(static_*_members=,
+        static_votes=)``, DESIGN §3za: the sampler hands its environment's setting over at every reset); legal whenever nothing is
+        stored.  The step's ``rule_done_votes_t`` / ``rule_cost_votes_t`` [B] are kept beside the per-step arrays;
+        ``cost_votes=False`` (a learned cost: the static cost rule is skipped) counts no cost votes."""
+        votes = None
+        if on:
+            if term_members not in _lib.RULE_DONE_MEMBERS:
+                raise ValueError(f"static_term_members: 'elite', 'any' or 'majority', got {term_members!r}")
+            if cost_members not in _lib.RULE_COST_MEMBERS:
+                raise ValueError(f"static_cost_members: 'elite', 'any', 'majority' or 'mean', got {cost_members!r}")
+            votes = (term_members, cost_members, bool(cost_votes))
+        if votes == self.rule_votes:
+            return
+        if self.ptr != 0 or self._size != 0:
+            raise RuntimeError("set_rule_votes: the buffer holds samples (call it after get() / reset())")
+        self.rule_votes = votes
+        self._side_sync("votes")
 
     # -- the state beside the struct ------------------------------------------------------------
     def _side_sync(self, feature):

@@ -452,6 +452,54 @@ int cmbpo_fakeenv_post_term_draws(int task, int ensemble, int obs_dim, int act_d
                                   const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch,
                                   const float *d_term_thr, void *stream);
 
+/* Ensemble-voted static rules: the task's own termination and cost rule evaluated on EVERY member's predicted next
+ * state, not only on the elite's.  THE rule -- for row r and every member e in 0..E-1, over ALL members like ens_ep_var and the
+ * termination head's votes:
+ *   nx_e[d]  = fl32(mu_e[d] + obs[d]);  mu_e = mean_e, with d_xi fl32(mean_e + fl32(sqrtf(var_e) * xi[d])) -- the expression
+ *              cmbpo_fakeenv_post_noise applies to every member, so nx_elite has the bits of next_obs
+ *   done_e, cost_e = the task's rule on (obs, act, nx_e), exactly as cmbpo_fakeenv_post defines it for the elite: AntSafe with its
+ *              finite gate and the `gate * z_rot >= -0.7` quirk, HCS, a registered clause table with or without derived
+ *              quantities, require_finite and cost_on_term; the default task and every no_done task: done_e = 0.  cost_e uses the
+ *              member's own done_e and is an indicator in {0, 1}
+ *   done_votes[r] = #{e : done_e},  cost_votes[r] = #{e : cost_e > 0}      (uint8, slot indexed like d_term, either may be NULL)
+ *   rule_done = done_elite (CMBPO_TERM_ELITE: what cmbpo_fakeenv_post writes) | votes > 0 (_ANY) | 2 * votes > E (_MAJORITY)
+ *   term      = rule_done || learned_done      learned_done: the termination head's verdict, unchanged, sampled thresholds included
+ *   cost      = cost_elite (CMBPO_TERM_ELITE) | cost_votes > 0 ? 1 : 0 (_ANY) | 2 * cost_votes > E ? 1 : 0 (_MAJORITY)
+ *               | (float)cost_votes / (float)E (CMBPO_VOTE_MEAN: one division, a probability like the logistic head's)
+ * With the disagreement on and a static cost (no CMBPO_TASK_LEARNED_COST):
+ *   cost_var[r] = np.var(cost_e over ALL E members) in cmbpo_fakeenv_post_disagreement's order of operations (without the votes: +0)
+ *   cost        = clip1(fl32(cost + fl32(kappa_cost * sqrtf(cost_var))))  if kappa_cost > 0;  clip1(c) = c > 1 ? 1 : c
+ * so kappa_cost > 0 is accepted with a static cost once the votes are given.  next_obs, rew, rew_var, dkl_path, ep_var*,
+ * term_pred, term_votes and cost_logit do not depend on any of it.  With CMBPO_TASK_LEARNED_COST the static cost rule is skipped
+ * as it always was: cost, cost_var and kappa_cost are the learned column's, cost_members != CMBPO_TERM_ELITE or a non-NULL
+ * cost_votes is refused, done_members and done_votes stay available. */
+#define CMBPO_VOTE_MEAN 3     /* cost_members only: the expected indicator votes / E */
+typedef struct cmbpo_rule_votes {
+  int32_t done_members;   /* CMBPO_TERM_ELITE / _ANY / _MAJORITY */
+  int32_t cost_members;   /* CMBPO_TERM_ELITE / _ANY / _MAJORITY / CMBPO_VOTE_MEAN */
+  uint8_t *done_votes;    /* [.] or NULL */
+  uint8_t *cost_votes;    /* [.] or NULL */
+} cmbpo_rule_votes_t; /* 24 bytes */
+/* cmbpo_fakeenv_post_term_draws's arguments plus the votes: the superset, every feature optional.  rv == NULL is exactly
+ * cmbpo_fakeenv_post_term_draws's call (the same kernel instances with the same argument blocks, no further launch).  With rv,
+ * one more kernel (csrc/rule_votes.hip) runs behind the post kernel on the same stream and overwrites d_term, d_cost and, with
+ * the disagreement on and a static cost, d_cost_var.  It recovers learned_done from the head's own outputs: with th != NULL both
+ * th->term_pred and th->term_votes are required.  Beside cmbpo_fakeenv_post_term_draws's checks: done_members in 0..2,
+ * cost_members in 0..3 (CMBPO_VOTE_MEAN for the cost only), the learned-cost refusal above, ensemble <= 8 (the votes of a row
+ * live in a byte mask) -- each refused with a message naming the votes, before any HIP call. */
+int cmbpo_fakeenv_post_votes(int task, int ensemble, int obs_dim, int act_dim,
+                             const float *d_mean, const float *d_var, int ld_rows,
+                             const float *d_obs, const float *d_act,
+                             const int32_t *d_elite, const int32_t *d_row_idx,
+                             const int32_t *d_n_rows, int n_rows, float *d_next_obs,
+                             float *d_rew, uint8_t *d_term, float *d_cost,
+                             float *d_dkl_path, float *d_ep_var_mean,
+                             float *d_ep_var, const float *d_xi,
+                             float kappa_rew, float kappa_cost,
+                             float *d_rew_var, float *d_cost_var,
+                             const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch,
+                             const float *d_term_thr, const cmbpo_rule_votes_t *rv, void *stream);
+
 /* ------------------------------------------------------------------------ *
  * Device-resident rollout state: the fused counterpart of ModelSampler
  * (samplers/model_sampler.py:203-444) + ModelBuffer (buffers/modelbuffer.py).
@@ -692,6 +740,18 @@ int cmbpo_rollout_term_draws_attach(const cmbpo_rollout_t *r, const float *d_thr
 int cmbpo_rollout_cost_head_attach(const cmbpo_rollout_t *r, const cmbpo_cost_head_t *ch);
 /* Back to the magnitude reading (no error when nothing was attached). */
 int cmbpo_rollout_cost_head_detach(const cmbpo_rollout_t *r);
+
+/* Ensemble-voted static rules along imagined rollouts: a copy of *rv travels beside an unchanged cmbpo_rollout_t in the same
+ * table.  Attached, cmbpo_rollout_step / _run post-process with cmbpo_fakeenv_post_votes (with whatever else is attached), so
+ * term_t -- and with it every finish decision -- and cost_t -- and with it cost_buf, the cost GAE, path_cost and the cost
+ * totals -- are the voted ones, and with a cmbpo_disagreement_t attached cost_var_t and its totals carry the static cost's spread
+ * (kappa_cost > 0 is then accepted with a static cost).  done_votes / cost_votes: [B] slot indexed, this step's values, or NULL;
+ * owned by the caller, valid until the detach.  With a termination head attached its term_pred / term_votes are required, and
+ * with CMBPO_TASK_LEARNED_COST cost_members != CMBPO_TERM_ELITE or cost_votes is refused: both at the step, with the post step's
+ * messages.  Checked here: the two modes' ranges.  rv == NULL detaches, as cmbpo_rollout_rule_votes_detach does (no error when
+ * nothing was attached).  Nothing else of a step or of the native loop changes. */
+int cmbpo_rollout_rule_votes_attach(const cmbpo_rollout_t *r, const cmbpo_rule_votes_t *rv);
+int cmbpo_rollout_rule_votes_detach(const cmbpo_rollout_t *r);
 
 /* ModelBuffer.get (modelbuffer.py:184-226): d_offsets[B+1] = exclusive scan of
  * len; d_stats[8] = {n, adv_mean, adv_std, cadv_mean, ret_mean, cret_mean}
