@@ -434,6 +434,24 @@ SIGNATURES.update({
     "cmbpo_replay_run_reliab": (_i, [_pp, _cpp, _rrp, _tp, _chp, _p, _i, _i, _p, _p]),
 })
 
+# the static rules' votes in the replay: a histogram of the two vote counts against the recorded flags, int64 only
+REPLAY_VOTE_COUNTS, REPLAY_VOTES_MAX_ENSEMBLE = 38, 8             # CMBPO_REPLAY_VOTE_COUNTS / _VOTES_MAX_ENSEMBLE
+REPLAY_VOTE_SLOTS = REPLAY_VOTES_MAX_ENSEMBLE + 1                 # v = 0 .. 8: counts = hist_cost [9][2] | hist_term [9][2] | n_vote | n_skipped
+
+
+class ReplayVotesStruct(C.Structure):
+    """ctypes image of ``cmbpo_replay_votes_t`` (56 bytes), field for field."""
+    _fields_ = [(n, C.c_int32) for n in ("ensemble", "done_members", "cost_members", "reserved")] + \
+               [(n, C.c_void_p) for n in ("done_votes", "cost_votes", "term", "part_cnt", "counts")]
+
+
+_rvtp = C.POINTER(ReplayVotesStruct)
+SIGNATURES.update({
+    "cmbpo_replay_votes": (_i, [_pp, _rvtp, _i, _p]),
+    "cmbpo_replay_votes_finish": (_i, [_pp, _rvtp, _p]),
+    "cmbpo_replay_run_votes": (_i, [_pp, _cpp, _rrp, _rvtp, _tp, _chp, _p, _i, _i, _p, _p]),
+})
+
 _lib = None
 
 

@@ -96,6 +96,14 @@ targets, 'balanced' by the termination head's rule on each fit's cost targets an
 (``FakeEnv.set_cost_head(logit_shift=)``), which undoes what the weight did to the fitted level.  ``save`` / ``load`` keep all of
 it in ``cost_loss_<epoch>.json`` (a missing file means 'gaussian').
 
+``m_validate_votes=True`` (needs ``m_validate_horizon > 0`` and the static votes: ``m_static_votes=True`` or an
+``m_static_*_members`` mode other than 'elite') has the validation replay run under the vote the rollouts use --
+``model/val_cost_miss_rate`` and its neighbours then describe the rule in force -- and count the members' votes against the
+recorded flags (``last_validation['votes']``): from the one-step row ``model/val_vote_ece_cost_h1`` / ``_term_h1`` (is the share
+``votes / E`` a probability), ``val_vote_split_*_h1`` (how often the members split), ``val_cost_miss_rate_any`` /
+``_majority``, ``val_cost_false_alarm_rate_any`` / ``_majority`` and the ``term`` counterparts (what each reading of the vote would
+miss and report in vain) and ``val_vote_skipped``.  It reads and does not steer.
+
 ``m_validate_reliability=True`` (needs ``m_validate_horizon > 0`` and a logistic head, ``m_cost_loss`` or ``m_term_loss``; DESIGN
 §3z) has the validation replay also measure whether each logistic column is a PROBABILITY: a reliability table per column in
 ``m_reliability_bins`` bins (``last_validation['reliability']``) and from its one-step row ``model/val_ece_cost_h1`` /
@@ -232,6 +240,19 @@ def _static_votes_args(use_model, learn_cost, term_members, cost_members, votes,
     return on
 
 
+def _validate_votes_args(validate_horizon, use_model, static_votes_on, validate_votes):
+    """``m_validate_votes`` checked against ``m_validate_horizon`` and the static votes, or a ValueError in words."""
+    if not validate_votes:
+        return False
+    if not (int(validate_horizon) > 0 and use_model):
+        raise ValueError("m_validate_votes needs m_validate_horizon > 0 (and use_model): the vote table is measured in the "
+                         "validation replay")
+    if not static_votes_on:
+        raise ValueError("m_validate_votes needs the static votes: m_static_votes=True or an m_static_*_members mode other than "
+                         "'elite' -- the imagined rollouts use the elite's rule, and that is what the validation replay measures")
+    return True
+
+
 def _term_sampling_args(learn_term, term_sampling):
     """``m_term_sampling`` checked against ``m_learn_term`` (and ``use_model``), or a ValueError in words."""
     if term_sampling and not learn_term:
@@ -335,6 +356,8 @@ class CMBPO:
     # reliability of the logistic columns where the constructor has not set it: off
     _validate_reliability, _reliability_bins, _recalibrate_cost, _recalibrate_term = False, 15, False, False
     _recalibration_range = (-2.0, 2.0)
+    # the validation replay under the static votes where the constructor has not set it: off
+    _validate_votes = False
 
     def __init__(self, env, policy, buffer, sampler=None, task='default', static_fns=None, n_env_interacts=1e7,
                  eval_every_n_steps=5e3, use_model=True, m_learn_cost=False, m_train_freq=250, m_loss_type='MSPE',
@@ -354,7 +377,8 @@ class CMBPO:
                  m_term_loss='gaussian', m_cost_loss='gaussian', m_cost_pos_weight=1.0, m_cost_pos_weight_undo=False,
                  m_term_sampling=False, m_validate_reliability=False, m_reliability_bins=15, m_recalibrate_cost=False,
                  m_recalibrate_term=False, m_recalibration_range=(-2.0, 2.0),
-                 m_static_term_members='elite', m_static_cost_members='elite', m_static_votes=False, **_unused):
+                 m_static_term_members='elite', m_static_cost_members='elite', m_static_votes=False, m_validate_votes=False,
+                 **_unused):
         # column / class weights of the model's binary columns; refused in words before anything is built
         self._column_weights = _column_weight_args(bool(m_learn_term) and bool(use_model), bool(m_learn_cost), m_term_pos_weight,
                                                    m_term_loss_weight, m_cost_loss_weight, m_pos_weight_max)
@@ -363,6 +387,8 @@ class CMBPO:
         # ensemble-voted static rules; likewise
         self._static_votes_on = _static_votes_args(use_model, bool(m_learn_cost), m_static_term_members, m_static_cost_members,
                                                    m_static_votes, m_cost_pessimism)
+        # the validation replay under that vote, with the vote table; likewise
+        self._validate_votes = _validate_votes_args(m_validate_horizon, use_model, self._static_votes_on, m_validate_votes)
         # sampled terminations; likewise
         self._m_term_sampling = _term_sampling_args(bool(m_learn_term) and bool(use_model), m_term_sampling)
         # the likelihood and the class weight of the cost column; likewise
@@ -600,6 +626,10 @@ class CMBPO:
                 # table is held against the training target, the same steps of the same windows
                 idx = start[None, :] + np.minimum(np.arange(H)[:, None], length[None, :] - 1)
                 kw.update(reliability_terminals=self._buffer.term_targets(self.sampler.max_path_length)[idx])
+        if self._validate_votes:
+            # the static rule knows no time-out either: its histogram is held against the same targets
+            idx = start[None, :] + np.minimum(np.arange(H)[:, None], length[None, :] - 1)
+            kw.update(votes=True, reliability_terminals=self._buffer.term_targets(self.sampler.max_path_length)[idx])
         tab = self.fake_env.replay(**win, **kw)
         self.last_validation = tab
         ratio = lambda a, b: float(a) / float(b) if b > 0 else float('nan')
@@ -622,6 +652,8 @@ class CMBPO:
                 extra['noise_scale_mean'] = 1.0 if scale is None else float(np.mean(scale))
         if self._validate_reliability:
             extra.update(self._reliability_diagnostics(tab['reliability']))
+        if self._validate_votes:
+            extra.update(self._votes_diagnostics(tab['votes']))
         if self._m_learn_term:
             # the head at h = 1, the one-step row: the share of real terminations it reports, of continuing steps it ends
             t1 = tab['term_cm'][0]
@@ -636,6 +668,23 @@ class CMBPO:
                 'val_term_false_rate': ratio(tm[0, 1], tm[0, 0] + tm[0, 1]),
                 'val_epvar_over_mse_hH': ratio(tab['ep_var_mean'][last], np.mean(tab['mse_obs'][last])),
                 'val_nonfinite': int(tab['n_nonfinite'].sum())}
+
+    @staticmethod
+    def _votes_diagnostics(vt):
+        """The one-step row of the vote table as ``val_*`` entries: is the share a probability (ECE), how often do the members
+        split, and what each reading of the vote would miss and report in vain."""
+        ratio = lambda a, b: float(a) / float(b) if b > 0 else float('nan')
+        out = {'val_vote_skipped': int(vt['n_skipped'].sum())}
+        for name in ('cost', 'term'):
+            if name not in vt:
+                continue
+            d = vt[name]
+            out.update({'val_vote_ece_%s_h1' % name: float(d['ece'][0]), 'val_vote_split_%s_h1' % name: float(d['split_rate'][0])})
+            for mode in ('any', 'majority'):
+                c = d['cm'][mode][0]
+                out.update({'val_%s_miss_rate_%s' % (name, mode): ratio(c[1, 0], c[1, 0] + c[1, 1]),
+                            'val_%s_false_alarm_rate_%s' % (name, mode): ratio(c[0, 1], c[0, 0] + c[0, 1])})
+        return out
 
     def _reliability_diagnostics(self, rel):
         """The one-step row of the reliability tables (the elite reading) as ``val_*`` entries and, with the recalibration

@@ -11,6 +11,9 @@
 // and, for a replay that also checks whether a logistic column is a probability, at the same place:
 //   replay_reliab_kernel        one horizon step of the reliability table: the members' logits, binned, against the recorded flag
 //   replay_reliab_finish_kernel its partials -> the [H] reliability table, in slot order
+// and, for a replay whose post step runs the static rules' votes, at the same place:
+//   replay_votes_kernel         one horizon step of the vote table: the two vote counts of a row against the recorded flags
+//   replay_votes_finish_kernel  its partials -> the [H] vote table, in slot order
 // Sums are float64, counts int64, every addition in a fixed order (no floating-point atomics): two runs are bitwise equal.
 #include "common.h"
 #include "ens_mlp_internal.h"
@@ -519,6 +522,88 @@ __global__ __launch_bounds__(kThreads) void replay_reliab_finish_kernel(cmbpo_re
   }
 }
 
+// ---- the static rules' votes ---------------------------------------------------------------------------------
+constexpr int kVoteCounts = CMBPO_REPLAY_VOTE_COUNTS;            // hist_cost[9][2] | hist_term[9][2] | n_vote | n_skipped
+constexpr int kVoteSlots = CMBPO_REPLAY_VOTES_MAX_ENSEMBLE + 1;  // v = 0 .. 8
+static_assert(kVoteCounts == 2 * kVoteSlots * 2 + 2 && kVoteCounts <= kRows, "one lane of wave 0 per entry of a slot");
+
+// One horizon step of the vote table; the geometry of replay_compare_kernel (kRows rows per workgroup, slot = workgroup).  All
+// threads scan the predicted observations for the compare kernel's rule, then wave 0, lane = row, reads its row's two vote
+// counts and flags.  An entry of the slot is the number of lanes with one (signal, v, y): a ballot and its population count, a
+// wave-uniform scalar, which lane k keeps when it is entry k's -- 36 ballots on registers in place of LDS atomics on 36
+// addresses, no second barrier, and the slot leaves as one coalesced store of 38 lanes.  Reads alive / predictions / recording
+// and the vote arrays, writes its partial slot only.
+__global__ __launch_bounds__(kThreads) void replay_votes_kernel(cmbpo_replay_t rp, cmbpo_replay_votes_t rv, int h) {
+  __shared__ uint8_t s_alive[kRows];   // alive on entry
+  __shared__ int s_bad[kRows];         // a non-finite prediction in the row (the compare kernel's verdict)
+
+  const int t = threadIdx.x;
+  const int B = rp.B, D = rp.obs_dim, E = rv.ensemble;
+  const int row0 = blockIdx.x * kRows;
+  const int rows = min(kRows, B - row0);
+  const size_t hb = (size_t)h * B;
+  int64_t *pcnt = rv.part_cnt + ((size_t)h * gridDim.x + blockIdx.x) * kVoteCounts;
+
+  // the row's votes and flags: issued ahead of the scan of the predictions, used behind it
+  bool alive = false, y_c = false, y_t = false;
+  int v_c = 0, v_d = 0;
+  if (t < kRows) {
+    alive = t < rows && rp.alive[row0 + t] != 0;
+    bool bad = false;
+    if (alive) {
+      bad = !(isfinite(rp.p_rew[row0 + t]) && isfinite(rp.p_cost[row0 + t]));
+      v_d = rv.done_votes[row0 + t];
+      if (rv.cost_votes != nullptr) {
+        v_c = rv.cost_votes[row0 + t];
+        y_c = rp.cost[hb + row0 + t] > 0.0f;
+      }
+      const uint8_t *flags = rv.term ? rv.term : rp.term;
+      y_t = flags[hb + row0 + t] != 0;
+    }
+    s_alive[t] = alive;
+    s_bad[t] = bad;
+  }
+  __syncthreads();
+
+  // the compare kernel's rule on the predicted observations (integer LDS flag: order cannot matter)
+  const float *pred = rp.p_next_obs + (size_t)row0 * D;
+  for (int i = t, total = rows * D; i < total; i += kThreads) {
+    const int r = i / D;
+    if (s_alive[r] && !isfinite(pred[i])) atomicOr(&s_bad[r], 1);
+  }
+  __syncthreads();
+
+  if (t >= kRows) return;
+  const bool cand = alive && s_bad[t] == 0;                      // the rows the compare kernel sums
+  const bool in = cand && v_c <= E && v_d <= E;
+  const bool cost_on = rv.cost_votes != nullptr;
+  int64_t mine = 0;
+#pragma unroll
+  for (int v = 0; v < kVoteSlots; ++v) {
+#pragma unroll
+    for (int y = 0; y < 2; ++y) {
+      const int64_t n_c = lanes_set(in && cost_on && v_c == v && y_c == (y != 0));
+      const int64_t n_t = lanes_set(in && v_d == v && y_t == (y != 0));
+      if (t == 2 * v + y) mine = n_c;
+      if (t == 2 * kVoteSlots + 2 * v + y) mine = n_t;
+    }
+  }
+  const int64_t n_vote = lanes_set(in), n_skip = lanes_set(cand && !in);
+  if (t == kVoteCounts - 2) mine = n_vote;
+  if (t == kVoteCounts - 1) mine = n_skip;
+  if (t < kVoteCounts) pcnt[t] = mine;
+}
+
+// the vote table: counts over the slots, in slot order; one workgroup per horizon, one thread per entry
+__global__ __launch_bounds__(kRows) void replay_votes_finish_kernel(cmbpo_replay_votes_t rv, int n_part) {
+  const int h = blockIdx.x, j = threadIdx.x;
+  if (j >= kVoteCounts) return;
+  const int64_t *p = rv.part_cnt + (size_t)h * n_part * kVoteCounts + j;
+  int64_t s = 0;
+  for (int k = 0; k < n_part; ++k) s += p[(size_t)k * kVoteCounts];
+  rv.counts[(size_t)h * kVoteCounts + j] = s;
+}
+
 int check_shape(const char *who, const cmbpo_replay_t *rp) {
   CMBPO_REQUIRE(rp != nullptr, "%s: descriptor is NULL", who);
   CMBPO_REQUIRE(rp->B >= 1, "%s: B %d < 1", who, rp->B);
@@ -643,6 +728,47 @@ int launch_reliab_finish(const cmbpo_replay_t *rp, const cmbpo_replay_reliab_t *
   return CMBPO_OK;
 }
 
+// `modes`: the single-step entries check ensemble <= 8 and the two modes' ranges themselves; the run entry leaves them to the
+// post step, whose refusal it passes on
+int check_votes(const char *who, const cmbpo_replay_votes_t *rv, bool modes) {
+  CMBPO_REQUIRE(rv != nullptr, "%s: vote descriptor is NULL", who);
+  CMBPO_REQUIRE(rv->ensemble >= 1, "%s: vote ensemble %d < 1", who, rv->ensemble);
+  CMBPO_REQUIRE(rv->reserved == 0, "%s: vote reserved %d != 0", who, rv->reserved);
+  if (!modes) return CMBPO_OK;
+  CMBPO_REQUIRE(rv->ensemble <= CMBPO_REPLAY_VOTES_MAX_ENSEMBLE, "%s: vote ensemble %d outside [1, %d]", who, rv->ensemble,
+                CMBPO_REPLAY_VOTES_MAX_ENSEMBLE);
+  const cmbpo_rule_votes_t post{rv->done_members, rv->cost_members, rv->done_votes, rv->cost_votes};
+  return cmbpo_internal_rule_votes_check_struct(who, &post);
+}
+
+int check_votes_step(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_votes_t *rv, bool modes) {
+  if (int r = check_compare(who, rp)) return r;
+  if (int r = check_votes(who, rv, modes)) return r;
+  CMBPO_REQUIRE(rv->done_votes, "%s: NULL buffer (done_votes)", who);
+  CMBPO_REQUIRE(rv->part_cnt, "%s: NULL buffer (vote partials)", who);
+  return CMBPO_OK;
+}
+
+int check_votes_finish(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_votes_t *rv, bool modes) {
+  if (int r = check_shape(who, rp)) return r;
+  if (int r = check_votes(who, rv, modes)) return r;
+  CMBPO_REQUIRE(rv->part_cnt, "%s: NULL buffer (vote partials)", who);
+  CMBPO_REQUIRE(rv->counts, "%s: NULL buffer (vote table)", who);
+  return CMBPO_OK;
+}
+
+int launch_votes(const cmbpo_replay_t *rp, const cmbpo_replay_votes_t *rv, int h, hipStream_t s) {
+  hipLaunchKernelGGL(replay_votes_kernel, dim3(cmbpo_replay_parts(rp->B)), dim3(kThreads), 0, s, *rp, *rv, h);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
+int launch_votes_finish(const cmbpo_replay_t *rp, const cmbpo_replay_votes_t *rv, hipStream_t s) {
+  hipLaunchKernelGGL(replay_votes_finish_kernel, dim3(rp->H), dim3(kRows), 0, s, *rv, cmbpo_replay_parts(rp->B));
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
 // a callee's refusal, passed on under this entry point's name
 int refused_by(const char *who, int rc) {
   char inner[400];
@@ -653,10 +779,11 @@ int refused_by(const char *who, int rc) {
 
 // the steps of a run: cal == nullptr is exactly cmbpo_replay_run's launches, else the calibrate kernel goes between post and
 // compare and its finish behind the plain one; rel != nullptr: the reliability kernel behind it, its finish last; th / ch !=
-// nullptr: the heads' instances of the post kernel.  Every argument has been checked by the caller.
+// nullptr: the heads' instances of the post kernel; vot != nullptr: the vote kernel behind the post kernel (FakeenvPostCall::rv), the
+// vote table's kernel behind the reliability kernel, its finish last.  Every argument has been checked by the caller.
 int run_steps(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *cal, const cmbpo_replay_reliab_t *rel,
-              cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, const cmbpo_term_head_t *th,
-              const cmbpo_cost_head_t *ch, void *stream) {
+              const cmbpo_replay_votes_t *vot, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite,
+              const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, void *stream) {
   const int B = rp->B, D = rp->obs_dim, A = rp->act_dim;
   // the post step; act, elite and n_rows follow the horizon
   FakeenvPostCall pc{};
@@ -666,6 +793,15 @@ int run_steps(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_cali
   pc.dkl_path = rp->p_dkl_path; pc.ep_var_mean = rp->p_ep_var_mean;
   pc.th = th;
   pc.ch = ch;
+  cmbpo_rule_votes_t post_votes{};
+  if (vot) {
+    post_votes.done_members = vot->done_members; post_votes.cost_members = vot->cost_members;
+    post_votes.done_votes = vot->done_votes; post_votes.cost_votes = vot->cost_votes;
+    pc.rv = &post_votes;
+    // the votes' own refusals come first: they need nothing of the model, so they can be had without one
+    pc.act = rp->act; pc.elite = d_elite; pc.n_rows = 0;
+    if (int rc = cmbpo_internal_fakeenv_post(pc, stream)) return refused_by(who, rc);
+  }
   // the two callees' own argument checks, on a call of no rows (neither launches anything for it)
   if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, rp->act, A, nullptr, nullptr, 0, B, rp->mean, rp->var, stream))
     return refused_by(who, rc);
@@ -681,24 +817,29 @@ int run_steps(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_cali
       if (int rc = launch_calibrate(rp, cal, h, (hipStream_t)stream)) return rc;
     if (rel)
       if (int rc = launch_reliab(rp, rel, h, (hipStream_t)stream)) return rc;
+    if (vot)
+      if (int rc = launch_votes(rp, vot, h, (hipStream_t)stream)) return rc;
     if (int rc = launch_compare(rp, h, (hipStream_t)stream)) return rc;
   }
   if (int rc = launch_finish(rp, (hipStream_t)stream)) return rc;
   if (cal)
     if (int rc = launch_calib_finish(rp, cal, (hipStream_t)stream)) return rc;
-  return rel ? launch_reliab_finish(rp, rel, (hipStream_t)stream) : CMBPO_OK;
+  if (rel)
+    if (int rc = launch_reliab_finish(rp, rel, (hipStream_t)stream)) return rc;
+  return vot ? launch_votes_finish(rp, vot, (hipStream_t)stream) : CMBPO_OK;
 }
 
-// The five run entry points: ONE check list, keyed on which of rc (calibration), rr (reliability), th (termination head) and ch
-// (cost head) are given.  The messages carry the name of the narrowest entry point that can express the call (DESIGN): rr given --
-// cmbpo_replay_run_reliab, else ch given --
+// The six run entry points: ONE check list, keyed on which of rc (calibration), rr (reliability), rv (votes), th (termination head)
+// and ch (cost head) are given.  The messages carry the name of the narrowest entry point that can express the call (DESIGN): rv
+// given -- cmbpo_replay_run_votes, else rr given -- cmbpo_replay_run_reliab, else ch given --
 // cmbpo_replay_run_cost, else th given -- cmbpo_replay_run_term, else rc given -- cmbpo_replay_run_calibrated, else
 // cmbpo_replay_run.  Where the entry points have always differed in the order
 // or the wording of a check, each combination keeps its own.
-int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_replay_reliab_t *rr, const cmbpo_term_head_t *th,
-               const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream) {
-  const bool ext = th || ch || rr;      // (the entries that take d_elite beside a calibration descriptor share their checks)
-  const char *who = rr ? "cmbpo_replay_run_reliab" : ch ? "cmbpo_replay_run_cost" : th ? "cmbpo_replay_run_term" : rc ? "cmbpo_replay_run_calibrated" : "cmbpo_replay_run";
+int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_replay_reliab_t *rr,
+               const cmbpo_replay_votes_t *rv, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model,
+               int task, int ensemble, const int32_t *d_elite, void *stream) {
+  const bool ext = th || ch || rr || rv;      // (the entries that take d_elite beside a calibration descriptor share their checks)
+  const char *who = rv ? "cmbpo_replay_run_votes" : rr ? "cmbpo_replay_run_reliab" : ch ? "cmbpo_replay_run_cost" : th ? "cmbpo_replay_run_term" : rc ? "cmbpo_replay_run_calibrated" : "cmbpo_replay_run";
   if (int r = rc ? check_calibrate(who, rp, rc) : check_compare(who, rp)) return r;      // (check_calibrate: mean / var as well)
   if (int r = check_finish(who, rp)) return r;
   if (rc)
@@ -706,6 +847,10 @@ int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const c
   if (rr) {
     if (int r = check_reliab_step(who, rp, rr)) return r;
     if (int r = check_reliab_finish(who, rp, rr)) return r;
+  }
+  if (rv) {
+    if (int r = check_votes_step(who, rp, rv, false)) return r;
+    if (int r = check_votes_finish(who, rp, rv, false)) return r;
   }
   CMBPO_REQUIRE(model != nullptr, "%s: model handle is NULL", who);
   if (!rc && !ext) CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);     // (the plain run names it before act)
@@ -725,6 +870,7 @@ int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const c
     CMBPO_REQUIRE(d_elite == nullptr || d_elite == rr->elite, "%s: d_elite differs from the reliability descriptor's elite", who);
     d_elite = rr->elite;
   }
+  if (rv) CMBPO_REQUIRE(ensemble == rv->ensemble, "%s: ensemble %d, the vote descriptor's is %d", who, ensemble, rv->ensemble);
   if (ext) CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);
   if (ch && ch->kind == 1)
     CMBPO_REQUIRE(model->out_dim == rp->obs_dim + 2 + (th ? 1 : 0),
@@ -736,7 +882,7 @@ int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const c
                   "%s: termination head (cmbpo_term_head_t): model out_dim %d does not match obs_dim %d + 1 (+ 1 with CMBPO_TASK_LEARNED_COST) "
                   "+ 1 for the head's column, task 0x%x", who, model->out_dim, rp->obs_dim, task);
   }
-  return run_steps(who, rp, rc, rr, model, task, ensemble, d_elite, th, ch, stream);
+  return run_steps(who, rp, rc, rr, rv, model, task, ensemble, d_elite, th, ch, stream);
 }
 
 }  // namespace
@@ -757,7 +903,7 @@ extern "C" int cmbpo_replay_finish(const cmbpo_replay_t *rp, void *stream) {
 
 extern "C" int cmbpo_replay_run(const cmbpo_replay_t *rp, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite,
                                 void *stream) {
-  return replay_run(rp, nullptr, nullptr, nullptr, nullptr, model, task, ensemble, d_elite, stream);
+  return replay_run(rp, nullptr, nullptr, nullptr, nullptr, nullptr, model, task, ensemble, d_elite, stream);
 }
 
 extern "C" int cmbpo_replay_calibrate(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, int h, void *stream) {
@@ -775,18 +921,18 @@ extern "C" int cmbpo_replay_calib_finish(const cmbpo_replay_t *rp, const cmbpo_r
 extern "C" int cmbpo_replay_run_calibrated(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, cmbpo_mlp_t *model, int task,
                                            int ensemble, void *stream) {
   if (rc == nullptr) return check_calibrate("cmbpo_replay_run_calibrated", rp, rc);      // (this entry's own error, not the plain run)
-  return replay_run(rp, rc, nullptr, nullptr, nullptr, model, task, ensemble, nullptr, stream);
+  return replay_run(rp, rc, nullptr, nullptr, nullptr, nullptr, model, task, ensemble, nullptr, stream);
 }
 
 extern "C" int cmbpo_replay_run_term(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th,
                                      cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream) {
-  return replay_run(rp, rc, nullptr, th, nullptr, model, task, ensemble, d_elite, stream);
+  return replay_run(rp, rc, nullptr, nullptr, th, nullptr, model, task, ensemble, d_elite, stream);
 }
 
 extern "C" int cmbpo_replay_run_cost(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_term_head_t *th,
                                      const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite,
                                      void *stream) {
-  return replay_run(rp, rc, nullptr, th, ch, model, task, ensemble, d_elite, stream);
+  return replay_run(rp, rc, nullptr, nullptr, th, ch, model, task, ensemble, d_elite, stream);
 }
 
 extern "C" int cmbpo_replay_reliab(const cmbpo_replay_t *rp, const cmbpo_replay_reliab_t *rr, int h, void *stream) {
@@ -804,5 +950,23 @@ extern "C" int cmbpo_replay_reliab_finish(const cmbpo_replay_t *rp, const cmbpo_
 extern "C" int cmbpo_replay_run_reliab(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_replay_reliab_t *rr,
                                        const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model, int task,
                                        int ensemble, const int32_t *d_elite, void *stream) {
-  return replay_run(rp, rc, rr, th, ch, model, task, ensemble, d_elite, stream);
+  return replay_run(rp, rc, rr, nullptr, th, ch, model, task, ensemble, d_elite, stream);
+}
+
+extern "C" int cmbpo_replay_votes(const cmbpo_replay_t *rp, const cmbpo_replay_votes_t *rv, int h, void *stream) {
+  const char *who = "cmbpo_replay_votes";
+  if (int r = check_votes_step(who, rp, rv, true)) return r;
+  CMBPO_REQUIRE(h >= 0 && h < rp->H, "%s: h %d outside [0, %d)", who, h, rp->H);
+  return launch_votes(rp, rv, h, (hipStream_t)stream);
+}
+
+extern "C" int cmbpo_replay_votes_finish(const cmbpo_replay_t *rp, const cmbpo_replay_votes_t *rv, void *stream) {
+  if (int r = check_votes_finish("cmbpo_replay_votes_finish", rp, rv, true)) return r;
+  return launch_votes_finish(rp, rv, (hipStream_t)stream);
+}
+
+extern "C" int cmbpo_replay_run_votes(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_replay_reliab_t *rr,
+                                      const cmbpo_replay_votes_t *rv, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch,
+                                      cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream) {
+  return replay_run(rp, rc, rr, rv, th, ch, model, task, ensemble, d_elite, stream);
 }

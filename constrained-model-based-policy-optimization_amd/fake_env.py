@@ -62,7 +62,8 @@ verdict (what it always was), any member's, more than half of all members', or -
 ``static_votes`` is set; ``step()`` then adds ``info['static_term_votes']`` / ``info['static_cost_votes']`` (uint8), and with
 ``disagreement`` ``info['ensemble_cost_var']`` carries the static cost's spread, which ``cost_pessimism > 0`` may now act on
 (``min(1, c + kappa_c * sqrt(var))``).  ``static_cost_members != 'elite'`` needs ``predicts_cost=False`` (a learned cost skips the
-static rule).  ``set_static_votes(...)`` changes them later.  A replay keeps the elite's rule.  Off (the default) the calls made and
+static rule).  ``set_static_votes(...)`` changes them later.  A replay keeps the elite's rule unless asked: ``replay(..., votes=True)`` replays
+under the vote and adds the vote table.  Off (the default) the calls made and
 the keys returned are what they were.
 
 ``replay(...)`` has no counterpart in the reference: it replays windows of real steps through the model with the recorded
@@ -456,7 +457,7 @@ class FakeEnv:
         return next_obs, r, terms, info
 
     def replay(self, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, model_inds=None, mode='open_loop',
-               calibration=False, reliability=False, reliability_bins=15, reliability_terminals=None):
+               calibration=False, reliability=False, reliability_bins=15, reliability_terminals=None, votes=False):
         """Open-loop model validation: replay B windows of up to H consecutive REAL steps through the model and hold its
         predictions against the recording, horizon by horizon (``cmbpo_replay_run``).
 
@@ -473,7 +474,9 @@ class FakeEnv:
         [H, B] array.
 
         A replay always measures the UNPENALISED means: it runs ``cmbpo_ens_forward`` and the plain ``cmbpo_fakeenv_post``,
-        never the noise or disagreement entries, whatever ``disagreement`` / ``rew_pessimism`` / ``cost_pessimism`` are.  With
+        never the noise or disagreement entries, whatever ``disagreement`` / ``rew_pessimism`` / ``cost_pessimism`` are, and
+        -- unless ``votes`` is given -- the ELITE's verdict of the static rules, whatever ``static_term_members`` /
+        ``static_cost_members`` are.  With
         ``predicts_term`` the post step carries the head (``cmbpo_replay_run_term``): the predicted terminations, ``term_cm``
         among them, are ``rule_done or learned_done``.  With ``cost_loss='logistic'`` it carries the cost head
         (``cmbpo_replay_run_cost``): the predicted cost is the probability, so ``cost_cm``'s ``cost > 0.5`` is a decision rule
@@ -499,16 +502,40 @@ class FakeEnv:
         head logistic it raises ValueError: a Gaussian column is not a logit.  ``reliability_terminals`` [H, B]: the flags the
         termination column's table is held against where they are not ``terminals`` -- the head's training targets, which
         count a time-out as 0 (``CPOBuffer.term_targets``); the replay itself goes on ending windows at ``terminals``.  False is
-        the call as it always was."""
+        the call as it always was.
+
+        ``votes=True`` (needs ``static_votes_on``) runs ``cmbpo_replay_run_votes``: the post step of every horizon is
+        the rollouts' own, the vote kernel behind the post kernel under this environment's ``static_term_members`` /
+        ``static_cost_members`` -- still without noise, disagreement or pessimism.  The predicted terminations and costs are the
+        vote's verdicts: ``cost_cm`` / ``term_cm`` describe the rule in force, an ``open_loop`` window ends where the vote ends
+        it, and under ``'mean'`` the predicted cost is ``votes / E``, so ``mse_cost`` is the Brier score of the share and
+        ``cost_cm``'s ``cost > 0.5`` the strict majority.  Under the key ``'votes'``: the dict of ``cmbpo_amd.replay.votes_table``
+        -- per horizon the histogram of the vote count against the recorded flag, the reliability of the share and the 2x2
+        counts of the ``'any'`` and ``'majority'`` readings, for ``'cost'`` (not with ``predicts_cost``) and ``'term'``.
+        ``votes='measure'`` runs the vote kernel under ``'elite'`` / ``'elite'`` whatever the environment's modes are: every
+        other table is the call's without votes bit for bit, only the histogram is new.  ``reliability_terminals`` also serves
+        as the flags the ``'term'`` histogram is held against.  False is the call as it always was."""
         from .replay import ReplayBuffers
-        if reliability_terminals is not None and not reliability:
+        if votes not in (False, True, 'measure'):
+            raise ValueError(f"replay: votes is False, True or 'measure', got {votes!r}")
+        if votes is True and not self.static_votes_on:
+            raise ValueError("replay: votes=True needs the static votes on (static_votes=True or a static_*_members mode other "
+                             "than 'elite'): there is no vote in force to replay under; votes='measure' only counts them")
+        if reliability_terminals is not None and not (reliability or votes):
             raise ValueError("replay: reliability_terminals needs reliability=True: they are the flags of the reliability table")
         rel = dict(columns=self.reliability_columns(), bins=int(reliability_bins), terminals=reliability_terminals) \
             if reliability else None
         E = self._model.num_nets
+        vot = None
+        if votes:
+            measure = votes == 'measure'
+            vot = dict(done_members='elite' if measure else self.static_term_members,
+                       cost_members='elite' if measure else self.static_cost_members, learned_cost=self._predicts_cost,
+                       terminals=reliability_terminals)
         with torch.cuda.device(self.device):
             rb = ReplayBuffers(obs0, actions, next_obs, rewards, costs, terminals, lengths=lengths, mode=mode, ensemble=E,
-                               out_dim=self.output_dim, device=self.device, calibration=bool(calibration), reliability=rel)
+                               out_dim=self.output_dim, device=self.device, calibration=bool(calibration), reliability=rel,
+                               votes=vot)
             if (rb.obs_dim, rb.act_dim) != (self.obs_dim, self.act_dim):
                 raise ValueError("replay: windows of width (%d, %d), the model's is (%d, %d)"
                                  % (rb.obs_dim, rb.act_dim, self.obs_dim, self.act_dim))
@@ -526,7 +553,14 @@ class FakeEnv:
                 raise ValueError("replay: model_inds must be an int or an [%d, %d] array of members in 0..%d" % (H, B, E - 1))
             elite = torch.from_numpy(np.ascontiguousarray(inds, dtype=np.int32)).to(self.device)
             th, ch = self.term_head_struct(), self.cost_head_struct()
-            if calibration:
+            if votes:
+                rb.run_votes(self._model.mlp.handle, self._task_id, E, elite, term_head=th, cost_head=ch,
+                             calibration=bool(calibration), reliability=bool(reliability))
+                tab = rb.table()
+                if calibration:
+                    tab['calibration'] = rb.calibration_table()
+                tab['votes'] = rb.votes_table()
+            elif calibration:
                 rb.run_calibrated(self._model.mlp.handle, self._task_id, E, elite, term_head=th, cost_head=ch)
                 tab = rb.table()
                 tab['calibration'] = rb.calibration_table()

@@ -14,6 +14,11 @@ Reliability of the logistic columns: ``ReplayBuffers(..., reliabil
 arrays of ``cmbpo_replay_reliab_t``; ``reliability_table`` builds, per column and reading, the per-bin confidence against the
 observed frequency with ECE / MCE / Brier / log loss from the raw sums and counts, and ``logit_offset`` turns one horizon of
 it into the logit offset that makes the column's mean probability the observed rate (calibration-in-the-large).
+
+The static rules' votes: ``ReplayBuffers(..., votes=dict(done_members=, cost_members=, learned_cost=))`` also owns
+the arrays of ``cmbpo_replay_votes_t``; ``run_votes`` replays with the vote kernel in the post step, and ``votes_table`` builds,
+per signal and horizon, the histogram of the vote count against the recorded flag, the reliability of the share ``v / E`` and the
+2x2 counts of the 'any' and 'majority' readings from the raw integer counts.
 """
 import ctypes as C
 
@@ -39,7 +44,7 @@ def _as(x, dtype, device):
 
 class ReplayBuffers:
     def __init__(self, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, mode="open_loop", ensemble=0,
-                 out_dim=0, device="cuda", calibration=False, reliability=None):
+                 out_dim=0, device="cuda", calibration=False, reliability=None, votes=None):
         """obs0 [B, obs]; actions [H, B, act]; next_obs [H, B, obs]; rewards / costs / terminals [H, B] (a trailing axis
         of one is dropped); lengths [B] in 1..H (None: H).  NumPy arrays or tensors.  ``ensemble`` / ``out_dim`` > 0 also
         allocate the forward's scratch ``cmbpo_replay_run`` needs.  ``calibration=True`` (needs both) also allocates the
@@ -48,7 +53,12 @@ class ReplayBuffers:
         terminals=None)`` (needs both too) also allocates the arrays of the reliability table of one or two logistic columns;
         ``edges`` [bins - 1] (ascending, finite; None: ``default_edges(bins)``) are the bin edges in logit space; ``terminals``
         [H, B] are the flags the 'term' columns are held against where they are not the recorded ones (a head's training
-        targets).  It shares ``elite`` with the calibration table."""
+        targets).  It shares ``elite`` with the calibration table.
+        ``votes=dict(done_members='elite', cost_members='elite', learned_cost=False, terminals=None)`` (needs ``ensemble`` in
+        1..8) also allocates the arrays of the vote table: the two ``[B]`` uint8 vote arrays of a step (no cost votes under
+        ``learned_cost``), the ``[B]`` ``term_pred`` / ``term_votes`` scratch a termination head needs beside the vote kernel, the
+        partials and the table; the modes are those of the post step (``'elite'`` / ``'elite'`` measures only); ``terminals``
+        [H, B] as for ``reliability``."""
         if mode not in MODES:
             raise ValueError("replay mode: 'open_loop' or 'one_step', got %r" % (mode,))
         dev = torch.device(device)
@@ -116,6 +126,40 @@ class ReplayBuffers:
             self.cs = cs
         if reliability is not None:
             self._init_reliability(dict(reliability), int(ensemble), int(out_dim))
+        self.vs = self.v = None
+        if votes is not None:
+            self._init_votes(dict(votes), int(ensemble))
+
+    def _init_votes(self, spec, ensemble):
+        H, B, dev = self.H, self.B, self.device
+        dm, cm = spec.pop("done_members", "elite"), spec.pop("cost_members", "elite")
+        learned = bool(spec.pop("learned_cost", False))
+        terminals = spec.pop("terminals", None)
+        if spec:
+            raise ValueError("replay: unknown votes keys %s" % sorted(spec))
+        if not 1 <= ensemble <= _lib.REPLAY_VOTES_MAX_ENSEMBLE or "mean" not in self.t:
+            raise ValueError("replay: votes need the forward's scratch and ensemble in 1..%d (the votes of a row live in a byte "
+                             "mask), got %d" % (_lib.REPLAY_VOTES_MAX_ENSEMBLE, ensemble))
+        if dm not in _lib.RULE_DONE_MEMBERS:
+            raise ValueError("replay: votes done_members is 'elite', 'any' or 'majority', got %r" % (dm,))
+        if cm not in _lib.RULE_COST_MEMBERS:
+            raise ValueError("replay: votes cost_members is 'elite', 'any', 'majority' or 'mean', got %r" % (cm,))
+        if learned and cm != "elite":
+            raise ValueError("replay: votes cost_members=%r with learned_cost: the static cost rule is skipped, there is nothing to "
+                             "vote on" % (cm,))
+        u8 = dict(dtype=torch.uint8, device=dev)
+        nv = _lib.REPLAY_VOTE_COUNTS
+        self.v = dict(done_votes=torch.zeros(B, **u8), cost_votes=torch.zeros(0 if learned else B, **u8),
+                      term=torch.zeros(0, **u8) if terminals is None else _as(terminals, torch.uint8, dev).reshape(H, B),
+                      part_cnt=torch.zeros((H, self.n_part, nv), dtype=torch.int64, device=dev),
+                      counts=torch.zeros((H, nv), dtype=torch.int64, device=dev))
+        self.head_scratch = dict(term_pred=torch.zeros(B, dtype=torch.float32, device=dev), term_votes=torch.zeros(B, **u8))
+        vs = _lib.ReplayVotesStruct()
+        vs.ensemble, vs.reserved = ensemble, 0
+        vs.done_members, vs.cost_members = _lib.RULE_DONE_MEMBERS[dm], _lib.RULE_COST_MEMBERS[cm]
+        for k, v in self.v.items():
+            setattr(vs, k, v.data_ptr() if v.numel() else None)
+        self.vs, self.vote_modes, self.learned_cost, self.vote_ensemble = vs, (dm, cm), learned, ensemble
 
     def _init_reliability(self, spec, ensemble, out_dim):
         H, B, dev = self.H, self.B, self.device
@@ -183,6 +227,29 @@ class ReplayBuffers:
         _lib.check(_lib.lib().cmbpo_replay_run_reliab(C.byref(self.rs), calib, C.byref(self.rr), ref(term_head), ref(cost_head),
                                                       model_handle, int(task_id), int(ensemble), None, _lib.current_stream()),
                    "cmbpo_replay_run_reliab")
+
+    def run_votes(self, model_handle, task_id, ensemble, elite, term_head=None, cost_head=None, calibration=False,
+                  reliability=True):
+        """``cmbpo_replay_run_votes``: the replay with the vote kernel in its post step and the vote table (buffers built with
+        ``votes=``); elite, term_head, cost_head as in ``run``.  ``calibration`` / ``reliability``: also the tables these buffers
+        were built with.  A termination head without outputs of its own gets these buffers' ``[B]`` scratch."""
+        self._votes()
+        ref = lambda s: C.byref(s) if s is not None else None
+        lib = _lib.lib()
+        if elite is not None and self.elite is not None:
+            self.set_elite(elite)
+        if term_head is not None and not (term_head.term_pred and term_head.term_votes):
+            th = _lib.TermHeadStruct()
+            th.threshold, th.members = term_head.threshold, term_head.members
+            th.term_pred = term_head.term_pred or self.head_scratch["term_pred"].data_ptr()
+            th.term_votes = term_head.term_votes or self.head_scratch["term_votes"].data_ptr()
+            term_head = th
+        rr = self.rr if reliability else None
+        cal = self._calib() if calibration else None
+        d_elite = None if (rr is not None or cal is not None) else elite.data_ptr()
+        _lib.check(lib.cmbpo_replay_run_votes(C.byref(self.rs), cal, ref(rr), C.byref(self.vs), ref(term_head), ref(cost_head),
+                                              model_handle, int(task_id), int(ensemble), d_elite, _lib.current_stream()),
+                   "cmbpo_replay_run_votes")
 
     def run(self, model_handle, task_id, ensemble, elite, term_head=None, cost_head=None, reliability=True):
         """The narrowest run entry that can express the call.  ``cmbpo_replay_run``; elite: [H, B] int32 device tensor.
@@ -273,6 +340,25 @@ class ReplayBuffers:
         self._reliab()
         return reliability_table(self.r["sums"].cpu().numpy(), self.r["counts"].cpu().numpy(), self.n_bins, self.rel_names,
                                  edges=self.rel_edges)
+
+    # -- the static rules' votes (votes=dict(...)) ---------------------------------------------------------------------
+    def _votes(self):
+        if self.vs is None:
+            raise ValueError("replay: these buffers were built with votes=None")
+        return C.byref(self.vs)
+
+    def votes(self, h):
+        """``cmbpo_replay_votes``: call it BEFORE ``compare(h)``, behind the step's ``cmbpo_fakeenv_post_votes``."""
+        rv = self._votes()
+        _lib.check(_lib.lib().cmbpo_replay_votes(C.byref(self.rs), rv, int(h), _lib.current_stream()), "cmbpo_replay_votes")
+
+    def votes_finish(self):
+        rv = self._votes()
+        _lib.check(_lib.lib().cmbpo_replay_votes_finish(C.byref(self.rs), rv, _lib.current_stream()), "cmbpo_replay_votes_finish")
+
+    def votes_table(self):
+        self._votes()
+        return votes_table(self.v["counts"].cpu().numpy(), self.vote_ensemble, self.learned_cost)
 
 
 def table(sums, counts, obs_dim):
@@ -416,3 +502,55 @@ def logit_offset(rel, column, reading="elite", horizon=0, lo=-2.0, hi=2.0, min_n
         else:
             b = mid
     return float(min(max(0.5 * (a + b), lo), hi))
+
+
+VOTE_SIGNALS = ("cost", "term")      # signal 0 / 1 of the vote table's histogram
+
+
+def votes_table(counts, E, learned_cost=False):
+    """The vote dict from the raw ``counts`` [H, 38] (int64: ``hist_cost`` [9, 2] | ``hist_term`` [9, 2] | ``n_vote`` |
+    ``n_skipped``) of an ensemble of ``E`` members: ``n_vote`` / ``n_skipped`` [H] (the rows that entered / whose vote count lay
+    above E) and, per signal -- ``'cost'`` (not under ``learned_cost``) and ``'term'`` --, ``hist`` [H, E + 1, 2] indexed [votes,
+    recorded flag], ``n`` [H], ``conf`` [E + 1] = v / E (what the share says), ``freq`` [H, E + 1] (how often the flag was set
+    among the rows with v votes), ``ece = sum_v n_v / n |v / E - freq_v|`` and ``mce`` (its largest gap) over the non-empty vote
+    counts, ``brier = sum_v (n_v0 (v / E)^2 + n_v1 (1 - v / E)^2) / n``, ``base_rate``, ``mean_share``, ``split_rate`` (the
+    share of rows with 0 < v < E: where the modes can differ at all) and ``cm['any']`` / ``cm['majority']`` [H, 2, 2] indexed
+    [real, predicted]: the 2x2 counts of ``v > 0`` and of ``2 v > E``.  Float64 from exact integers; a horizon with ``n == 0``
+    has NaN rates and zero counts."""
+    counts = np.asarray(counts, np.int64)
+    E, S = int(E), _lib.REPLAY_VOTE_SLOTS
+    if counts.ndim != 2 or counts.shape[1] != _lib.REPLAY_VOTE_COUNTS:
+        raise ValueError("votes_table: counts [H, %d] expected, got %s" % (_lib.REPLAY_VOTE_COUNTS, counts.shape))
+    if not 1 <= E <= _lib.REPLAY_VOTES_MAX_ENSEMBLE:
+        raise ValueError("votes_table: E must lie in 1..%d, got %d" % (_lib.REPLAY_VOTES_MAX_ENSEMBLE, E))
+    H = counts.shape[0]
+    full = counts[:, :4 * S].reshape(H, 2, S, 2)
+    if full[:, :, E + 1:].any():
+        raise ValueError("votes_table: counts hold rows with more than E = %d votes" % E)
+    out = dict(n_vote=counts[:, 4 * S].copy(), n_skipped=counts[:, 4 * S + 1].copy())
+    v = np.arange(E + 1, dtype=np.float64)
+    conf = v / float(E)
+    for j, name in enumerate(VOTE_SIGNALS):
+        if name == "cost" and learned_cost:
+            continue
+        hist = full[:, j, :E + 1].copy()
+        nv = hist.sum(axis=2)                                   # [H, E + 1]
+        n = nv.sum(axis=1)
+        hf, nvf, nf = hist.astype(np.float64), nv.astype(np.float64), n.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            nan = np.where(n > 0, 0.0, np.nan)
+            freq = hf[:, :, 1] / nvf
+            gap = np.where(nv > 0, np.abs(conf[None] - freq), 0.0)
+            d = dict(hist=hist, n=n, conf=conf.copy(), freq=freq, ece=(nvf * gap).sum(axis=1) / nf + nan, mce=gap.max(axis=1) + nan,
+                     brier=(hf[:, :, 0] * conf[None] ** 2 + hf[:, :, 1] * (1.0 - conf[None]) ** 2).sum(axis=1) / nf + nan,
+                     base_rate=hf[:, :, 1].sum(axis=1) / nf + nan, mean_share=(nvf * conf[None]).sum(axis=1) / nf + nan,
+                     split_rate=nvf[:, 1:E].sum(axis=1) / nf + nan)
+        cm = {}
+        for mode, hit in (("any", v > 0), ("majority", 2 * v > E)):
+            m = np.zeros((H, 2, 2), np.int64)
+            m[:, :, 1] = hist[:, hit].sum(axis=1)               # [real][pred = 1]
+            m[:, :, 0] = hist[:, ~hit].sum(axis=1)
+            cm[mode] = m
+        d["cm"] = cm
+        out[name] = d
+    return out

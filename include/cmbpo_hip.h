@@ -1357,6 +1357,66 @@ int cmbpo_replay_run_reliab(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t
                             const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model, int task,
                             int ensemble, const int32_t *d_elite, void *stream);
 
+/* ---- the static rules' votes in the replay (csrc/replay.hip) -------------------------------
+ * Which of the vote's readings is right, and is the vote SHARE a probability?  With a vote descriptor the post step of a replay
+ * is cmbpo_fakeenv_post_votes's (the vote kernel of csrc/rule_votes.hip behind the post kernel at every horizon, without noise,
+ * disagreement or kappa_cost): p_term / p_cost are the vote's verdicts under done_members / cost_members, so the plain table's
+ * term_cm / cost_cm describe the rule in force, a CMBPO_REPLAY_OPEN_LOOP window ends where the vote ends it, and under
+ * CMBPO_VOTE_MEAN p_cost = votes / E: se_cost is the Brier score of the share and the compare call's `p_cost > 0.5` the strict
+ * majority.  CMBPO_TERM_ELITE / CMBPO_TERM_ELITE measures: the verdicts are the elite's, only the vote table is new.
+ *
+ * The vote table is a histogram of the two vote counts the vote kernel left in done_votes / cost_votes [B] for the step, against
+ * the recorded flags.  A row ENTERS at h iff (a) alive[b] != 0 on entry to the step -- the call goes BEFORE that step's compare
+ * call, like the calibrate and reliab calls --, (b) p_next_obs[b], p_rew[b], p_cost[b] are finite (the compare call's rule).  An
+ * entering row with done_votes[b] > ensemble or cost_votes[b] > ensemble counts in n_skipped[h] and adds nothing else (the vote
+ * kernel never writes such a count: only caller-made arrays handed to the single-step entry reach it); every other entering row
+ * counts in n_vote[h] and adds
+ *   hist_cost[h][v_c][y_c] += 1,   v_c = cost_votes[b],  y_c = cost[h][b] > 0        (the compare call's rule for a real cost)
+ *   hist_term[h][v_d][y_t] += 1,   v_d = done_votes[b],  y_t = term[h][b] != 0       (the descriptor's `term` where given)
+ * The descriptor's own `term` serves as in cmbpo_replay_reliab_t: the termination RULE is held against a head's training targets
+ * (a time-out is 0 there) while the replay goes on ending windows at rp->term.  cost_votes == NULL (a learned cost: the static
+ * cost rule is skipped) leaves the cost half 0.  Layout, int64:
+ *   counts [H][38]:  hist_cost [9][2] ([v][y], v = 0 .. 8) | hist_term [9][2] | n_vote | n_skipped      slots v > ensemble stay 0
+ * Integers only: inside a workgroup every entry is one wave ballot's population count, per-workgroup partials (slot = workgroup,
+ * cmbpo_replay_parts(B) slots per horizon, every entry of a slot written on every call) are added in slot order by the finish
+ * call; no atomics on global memory, no floating point, two runs are bitwise equal.  Reads alive / predictions / recording of the
+ * cmbpo_replay_t handed in beside the descriptor and the two vote arrays, writes its partial slot only; the three other
+ * descriptors (184, 56 and 104 bytes) are what they were. */
+#define CMBPO_REPLAY_VOTE_COUNTS 38
+#define CMBPO_REPLAY_VOTES_MAX_ENSEMBLE 8
+
+typedef struct cmbpo_replay_votes {
+  int32_t ensemble;         /* members E (1..8)                                     */
+  int32_t done_members;     /* CMBPO_TERM_ELITE / _ANY / _MAJORITY                  */
+  int32_t cost_members;     /* CMBPO_TERM_ELITE / _ANY / _MAJORITY / CMBPO_VOTE_MEAN */
+  int32_t reserved;         /* must be 0                                            */
+  uint8_t *done_votes;      /* [B] step scratch: the vote kernel writes, the table kernel reads */
+  uint8_t *cost_votes;      /* [B] likewise; NULL with CMBPO_TASK_LEARNED_COST      */
+  const uint8_t *term;      /* [H,B] the flags hist_term is held against; NULL: rp->term */
+  int64_t *part_cnt;        /* [H][cmbpo_replay_parts(B)][38]                       */
+  int64_t *counts;          /* [H][38]                                              */
+} cmbpo_replay_votes_t; /* 56 bytes */
+
+/* Every entry: CMBPO_EINVAL with a message naming the entry point for a NULL descriptor, a NULL array it uses (cost_votes and
+ * term may be NULL), ensemble outside [1, 8], done_members outside 0..2, cost_members outside 0..3, reserved != 0, h outside
+ * [0, H) and every shape refusal of the compare call -- all before any HIP call. */
+/* one horizon step of the vote table, from the arrays the compare call of the same step reads plus the two vote arrays.  Enqueue
+ * it BEFORE that step's compare call (beside a calibrate / reliab call: in any order); it writes nothing but its partial slot. */
+int cmbpo_replay_votes(const cmbpo_replay_t *rp, const cmbpo_replay_votes_t *rv, int h, void *stream);
+/* partials -> rv->counts, all H horizons */
+int cmbpo_replay_votes_finish(const cmbpo_replay_t *rp, const cmbpo_replay_votes_t *rv, void *stream);
+/* The superset of the run entries: H x (forward -> post [-> vote kernel] -> [calibrate] -> [reliab] -> [votes] -> compare), then
+ * the finish calls (plain, calibration, reliability, votes), enqueued without a host wait; bitwise the single calls (the post
+ * step: cmbpo_fakeenv_post_votes with rv's modes and vote arrays, d_xi NULL, kappa 0).  rv == NULL is exactly
+ * cmbpo_replay_run_reliab's call: the same launches, the same messages.  With rv: `ensemble` must equal rv->ensemble; with th,
+ * th->term_pred and th->term_votes [B] are required (the vote kernel recovers learned_done from them).  The post step's own
+ * refusals are passed on under this entry's name: a mode out of range, ensemble above 8, and with CMBPO_TASK_LEARNED_COST
+ * cost_members != CMBPO_TERM_ELITE or a non-NULL cost_votes.  Under CMBPO_TERM_ELITE / CMBPO_TERM_ELITE the plain, calibration
+ * and reliability tables, cur_obs and alive are bitwise those of the run without rv on the same inputs. */
+int cmbpo_replay_run_votes(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const cmbpo_replay_reliab_t *rr,
+                           const cmbpo_replay_votes_t *rv, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch,
+                           cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
