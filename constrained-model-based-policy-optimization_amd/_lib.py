@@ -452,6 +452,27 @@ SIGNATURES.update({
     "cmbpo_replay_run_votes": (_i, [_pp, _cpp, _rrp, _rvtp, _tp, _chp, _p, _i, _i, _p, _p]),
 })
 
+# particle replay: a window's S sampled particles against the recording -- rank histograms, CRPS terms, moments
+REPLAY_PARTICLES_MAX_OBS = 384                                    # CMBPO_REPLAY_PARTICLES_MAX_OBS
+REPLAY_PARTICLES_MAX = 64                                         # S: a power of two in 2..64
+
+
+class ReplayParticlesStruct(C.Structure):
+    """ctypes image of ``cmbpo_replay_particles_t`` (200 bytes), field for field."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "H", "S", "obs_dim", "act_dim", "mode", "reserved", "reserved2")] + \
+               [(n, C.c_void_p) for n in ("act", "next_obs", "rew", "cost", "term", "len", "xi", "cur_obs", "alive",
+                                          "p_next_obs", "p_rew", "p_term", "p_cost", "p_dkl_path", "p_ep_var_mean",
+                                          "mean", "var", "part_sum", "part_cnt", "sums", "counts")]
+
+
+_rpp = C.POINTER(ReplayParticlesStruct)
+SIGNATURES.update({
+    "cmbpo_replay_particles_parts": (_i, [_i, _i]),
+    "cmbpo_replay_particles": (_i, [_rpp, _i, _p]),
+    "cmbpo_replay_particles_finish": (_i, [_rpp, _p]),
+    "cmbpo_replay_run_particles": (_i, [_rpp, _tp, _chp, _p, _i, _i, _p, _p]),
+})
+
 _lib = None
 
 

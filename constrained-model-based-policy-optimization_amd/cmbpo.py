@@ -104,6 +104,17 @@ recorded flags (``last_validation['votes']``): from the one-step row ``model/val
 ``_majority``, ``val_cost_false_alarm_rate_any`` / ``_majority`` and the ``term`` counterparts (what each reading of the vote would
 miss and report in vain) and ``val_vote_skipped``.  It reads and does not steer.
 
+``m_validate_particles=S`` (S a power of two in 2..64; needs ``m_validate_horizon > 0``) adds a second pass to that
+replay: the first ``m_validate_particle_windows`` windows (None: ``min(m_validate_windows, 1024)``) are replayed by S sampled
+particles each, with the transition noise the rollouts actually use (``model_sampler.noise_scale``), and the recorded next
+state is held against the particles at every horizon (``last_validation['particles']``): ``model/val_crps_h1`` / ``_hH`` (the fair
+CRPS), ``val_rank_dev_h1`` / ``_hH`` (the rank histogram's distance from flat), ``val_outlier_rate_hH`` (recordings outside the
+cloud; 2 / (S + 1) when calibrated), ``val_spread_skill_h1`` / ``_hH`` (1 when calibrated) -- means over the observation columns --
+and ``val_particles_nonfinite``.  Refused in words, before anything is built: S not a power of two in 2..64, no
+``m_validate_horizon``, and ``m_validate_particles`` together with ``m_validate_votes=True`` (the particle pass runs no vote kernel:
+its table would describe another rule than the vote-ruled tables beside it).  It reads and does not steer: policy and model are
+bitwise those of the run without it.
+
 ``m_validate_reliability=True`` (needs ``m_validate_horizon > 0`` and a logistic head, ``m_cost_loss`` or ``m_term_loss``; DESIGN
 §3z) has the validation replay also measure whether each logistic column is a PROBABILITY: a reliability table per column in
 ``m_reliability_bins`` bins (``last_validation['reliability']``) and from its one-step row ``model/val_ece_cost_h1`` /
@@ -349,6 +360,27 @@ def balanced_pos_weight(targets, pos_weight_max):
     return float(np.clip(neg / max(pos, 1), 1.0, float(pos_weight_max)))
 
 
+def _validate_particles_args(horizon, use_model, windows, particles, particle_windows, validate_votes=False):
+    """``m_validate_particles`` / ``m_validate_particle_windows`` checked against ``m_validate_horizon`` and
+    ``m_validate_votes``, or a ValueError in words: (S, windows of the particle pass)."""
+    if not particles:
+        if particle_windows is not None:
+            raise ValueError("m_validate_particle_windows needs m_validate_particles > 0: there is no particle pass to size")
+        return 0, 0
+    from .replay import check_particles
+    S = check_particles(particles)
+    if not (use_model and int(horizon) > 0):
+        raise ValueError("m_validate_particles needs m_validate_horizon > 0 (and use_model): the particle table is measured in the "
+                         "validation replay")
+    if validate_votes:
+        raise ValueError("m_validate_particles together with m_validate_votes=True is not supported: the particle pass runs no "
+                         "vote kernel, its table would describe another rule than the vote-ruled tables beside it")
+    n = min(int(windows), 1024) if particle_windows is None else int(particle_windows)
+    if n < 1:
+        raise ValueError("m_validate_particle_windows must be >= 1, got %r" % (particle_windows,))
+    return S, n
+
+
 class CMBPO:
     """Constrained Model-Based Policy Optimization (``algorithms/cmbpo.py:30``)."""
     # the reading of the cost column (DESIGN 3w) where the constructor has not set it: a magnitude, no class weight
@@ -378,7 +410,10 @@ class CMBPO:
                  m_term_sampling=False, m_validate_reliability=False, m_reliability_bins=15, m_recalibrate_cost=False,
                  m_recalibrate_term=False, m_recalibration_range=(-2.0, 2.0),
                  m_static_term_members='elite', m_static_cost_members='elite', m_static_votes=False, m_validate_votes=False,
-                 **_unused):
+                 m_validate_particles=0, m_validate_particle_windows=None, **_unused):
+        # the particle pass of the validation replay; refused in words before anything is built
+        self._validate_particles, self._validate_particle_windows = _validate_particles_args(
+            m_validate_horizon, use_model, m_validate_windows, m_validate_particles, m_validate_particle_windows, m_validate_votes)
         # column / class weights of the model's binary columns; refused in words before anything is built
         self._column_weights = _column_weight_args(bool(m_learn_term) and bool(use_model), bool(m_learn_cost), m_term_pos_weight,
                                                    m_term_loss_weight, m_cost_loss_weight, m_pos_weight_max)
@@ -630,7 +665,16 @@ class CMBPO:
             # the static rule knows no time-out either: its histogram is held against the same targets
             idx = start[None, :] + np.minimum(np.arange(H)[:, None], length[None, :] - 1)
             kw.update(votes=True, reliability_terminals=self._buffer.term_targets(self.sampler.max_path_length)[idx])
+        S = self._validate_particles
+        n_part = min(self._validate_particle_windows, len(length)) if S else 0
+        pkw = dict(noise_scale=self.model_sampler.noise_scale) if S else {}      # (the noise the rollouts actually use)
+        if S and n_part == len(length):
+            kw.update(particles=S, **pkw)
         tab = self.fake_env.replay(**win, **kw)
+        if S and 'particles' not in tab:
+            # fewer windows than the plain replay's: the particle pass alone, on the first of them (the windows are a random draw)
+            head = {k: (v[:n_part] if k in ('obs0', 'lengths') else v[:, :n_part]) for k, v in win.items()}
+            tab['particles'] = self.fake_env._replay_particles(S, **head, **pkw)
         self.last_validation = tab
         ratio = lambda a, b: float(a) / float(b) if b > 0 else float('nan')
         cm, tm = tab['cost_cm'].sum(axis=0), tab['term_cm'].sum(axis=0)      # [real, predicted], all horizons
@@ -654,6 +698,8 @@ class CMBPO:
             extra.update(self._reliability_diagnostics(tab['reliability']))
         if self._validate_votes:
             extra.update(self._votes_diagnostics(tab['votes']))
+        if S:
+            extra.update(self._particles_diagnostics(tab['particles'], self.obs_dim))
         if self._m_learn_term:
             # the head at h = 1, the one-step row: the share of real terminations it reports, of continuing steps it ends
             t1 = tab['term_cm'][0]
@@ -668,6 +714,18 @@ class CMBPO:
                 'val_term_false_rate': ratio(tm[0, 1], tm[0, 0] + tm[0, 1]),
                 'val_epvar_over_mse_hH': ratio(tab['ep_var_mean'][last], np.mean(tab['mse_obs'][last])),
                 'val_nonfinite': int(tab['n_nonfinite'].sum())}
+
+    @staticmethod
+    def _particles_diagnostics(pt, obs_dim):
+        """The first and the last horizon of the particle table as ``val_*`` entries, means over the observation columns: the
+        fair CRPS, the rank histogram's distance from flat, the share of recordings outside the cloud, spread over skill."""
+        last = len(pt['n']) - 1
+        col = lambda k, h: float(np.mean(pt[k][h, :obs_dim]))
+        return {'val_crps_h1': col('crps', 0), 'val_crps_hH': col('crps', last),
+                'val_rank_dev_h1': col('rank_dev', 0), 'val_rank_dev_hH': col('rank_dev', last),
+                'val_outlier_rate_hH': col('outlier_rate', last),
+                'val_spread_skill_h1': col('spread_skill', 0), 'val_spread_skill_hH': col('spread_skill', last),
+                'val_particles_nonfinite': int(pt['n_nonfinite'].sum())}
 
     @staticmethod
     def _votes_diagnostics(vt):

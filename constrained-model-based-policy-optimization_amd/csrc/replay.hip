@@ -14,6 +14,11 @@
 // and, for a replay whose post step runs the static rules' votes, at the same place:
 //   replay_votes_kernel         one horizon step of the vote table: the two vote counts of a row against the recorded flags
 //   replay_votes_finish_kernel  its partials -> the [H] vote table, in slot order
+// and, for a replay of S sampled particles per window (the post step with xi, a descriptor of its own), in place of
+// the compare kernel:
+//   replay_particles_kernel         one horizon step: the recorded next state against a window's S particles -- ranks, absolute
+//                                   errors, pair differences, moments -- and the rows' next state
+//   replay_particles_finish_kernel  its partials -> the [H] particle table, in slot order
 // Sums are float64, counts int64, every addition in a fixed order (no floating-point atomics): two runs are bitwise equal.
 #include "common.h"
 #include "ens_mlp_internal.h"
@@ -604,6 +609,177 @@ __global__ __launch_bounds__(kRows) void replay_votes_finish_kernel(cmbpo_replay
   rv.counts[(size_t)h * kVoteCounts + j] = s;
 }
 
+// ---- particle replay: rank histograms and CRPS of sampled rollouts ------------------------------------------
+constexpr int kWaves = kThreads / kRows;
+// CMBPO_REPLAY_PARTICLES_MAX_OBS is a chosen constant, so that the refusal needs no HIP call; the one place that holds it
+// against the LDS of a gfx950 workgroup is the static_assert below.  The launch asks cmbpo_grant_lds for the bytes of its shape.
+constexpr size_t kLdsWorkgroup = 160 * 1024;
+
+// row stride of the staged tile in floats: the C = obs_dim + 1 columns (the reward behind the observation), made odd -- in the
+// column phase lane = row reads column c of its row, 64 addresses `ld` floats apart, which an odd stride spreads over all banks
+__host__ __device__ inline int part_ld(int obs_dim) { return (obs_dim + 1) | 1; }
+// the staged tile: kRows rows of predictions and the recording of the kRows / S windows behind them
+inline size_t part_lds_bytes(int obs_dim, int S) { return (size_t)(kRows + kRows / S) * part_ld(obs_dim) * sizeof(float); }
+static_assert((size_t)(kRows + kRows / 2) * ((CMBPO_REPLAY_PARTICLES_MAX_OBS + 1) | 1) * sizeof(float) + 1024 <= kLdsWorkgroup,
+              "the tile of the widest observation at the smallest S, and the static arrays, fit one workgroup's LDS");
+
+// sum over the S lanes of a window (S consecutive lanes, S a power of two): a butterfly, so every lane of the window holds the
+// same bits (each level adds the same two numbers in both partners, and a + b == b + a)
+__device__ __forceinline__ double group_sum(double v, int S) {
+  for (int o = S >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// One horizon step of the particle table.  One workgroup = kRows consecutive rows = kRows / S whole windows (slot = workgroup).
+// The [rows, obs_dim] tile of p_next_obs is one contiguous run: all threads walk it once, row by column, into LDS (stride part_ld, the
+// reward in column obs_dim), marking non-finite rows on the way (integer LDS flag: order cannot matter); the windows' recording
+// goes in behind it.  Wave 0, lane = row, settles the windows' verdicts (a window's flags are the bits of one ballot under the
+// window's lane mask), the two Brier terms and the counts.  Then every thread writes the rows' next state from the staged tile,
+// and the waves take the columns in turn, lane = row: the rank is the population count of a ballot under the window's mask, the
+// sums over a window's particles are butterflies over its S lanes, the S (S - 1) pair differences come from S - 1 lane
+// rotations inside the window (registers only), and a column's sum over the windows is wave_sum over the windows' first lanes.
+// Every entry of the slot has one writer and a fixed order.  Global memory: every input is read once.
+__global__ __launch_bounds__(kThreads) void replay_particles_kernel(cmbpo_replay_particles_t rp, int h) {
+  extern __shared__ float s_tile[];    // [kRows][ld] predictions | [kRows / S][ld] recording
+  __shared__ uint8_t s_alive[kRows];   // alive on entry
+  __shared__ int s_bad[kRows];         // a non-finite prediction in the row
+  __shared__ uint8_t s_ok[kRows];      // the row's window is alive and finite: it is summed
+  __shared__ uint8_t s_next[kRows];    // the row's window lives on to h + 1: cur_obs is written
+
+  const int t = threadIdx.x, lane = t & (kRows - 1), wave = t / kRows;
+  const int S = rp.S, D = rp.obs_dim, C = D + 1, ld = part_ld(D);
+  const int lgS = 31 - __clz(S);
+  const int R = rp.B * S;
+  const int row0 = blockIdx.x * kRows;
+  const int rows = min(kRows, R - row0);           // a multiple of S
+  const int win0 = row0 >> lgS, wins = rows >> lgS;
+  const size_t hb = (size_t)h * rp.B;
+  float *s_x = s_tile, *s_q = s_tile + kRows * ld;
+  const int NS = 4 * C + 2, NC = C * (S + 1) + 2;
+  double *psum = rp.part_sum + ((size_t)h * gridDim.x + blockIdx.x) * NS;
+  int64_t *pcnt = rp.part_cnt + ((size_t)h * gridDim.x + blockIdx.x) * NC;
+  const uint64_t gmask = (S == 64 ? ~0ull : (1ull << S) - 1) << (lane & ~(S - 1));      // the lanes of this lane's window
+  const bool first = (lane & (S - 1)) == 0;                                             // the window's first lane speaks for it
+
+  float p_rew = 0.0f, p_cost = 0.0f;
+  bool p_term = false, alive = false;
+  if (t < kRows) {
+    alive = t < rows && rp.alive[row0 + t] != 0;
+    if (alive) { p_rew = rp.p_rew[row0 + t]; p_cost = rp.p_cost[row0 + t]; p_term = rp.p_term[row0 + t] != 0; }
+    s_alive[t] = alive;
+    s_bad[t] = (alive && !(isfinite(p_rew) && isfinite(p_cost))) ? 1 : 0;
+    s_x[t * ld + D] = p_rew;
+    if (t < wins) s_q[t * ld + D] = rp.rew[hb + win0 + t];
+  }
+  __syncthreads();
+
+  // the tile, once.  The walk of replay_compare_kernel: thread t sits on column t % W of row t / W and advances by kThreads / W
+  // rows -- consecutive threads read consecutive floats, and the one division is per thread, not per element (obs_dim >
+  // kThreads: a second trip over the columns)
+  const int W = min(D, kThreads), rpp = kThreads / W;
+  const int tr = t / W, tc = t - tr * W;
+  const bool walker = tr < rpp;
+  const float *pred = rp.p_next_obs + (size_t)row0 * D;
+  const float *real = rp.next_obs + (hb + win0) * D;
+  if (walker) {
+    for (int c = tc; c < D; c += W) {
+      for (int r = tr; r < rows; r += rpp) {
+        const float v = pred[r * D + c];
+        s_x[r * ld + c] = v;
+        if (s_alive[r] && !isfinite(v)) atomicOr(&s_bad[r], 1);
+      }
+      for (int w = tr; w < wins; w += rpp) s_q[w * ld + c] = real[w * D + c];
+    }
+  }
+  __syncthreads();
+
+  // the windows' verdicts, Brier terms and counts: wave 0, lane = row
+  if (t < kRows) {
+    const bool wbad = (__ballot(s_bad[t] != 0) & gmask) != 0;
+    const bool ok = alive && !wbad, bad = alive && wbad;
+    const int n_term = __popcll(__ballot(ok && p_term) & gmask);
+    const double m_cost = group_sum(ok ? (double)p_cost : 0.0, S) / (double)S;
+    double b_term = 0.0, b_cost = 0.0;
+    bool next = false;
+    if (ok) {
+      const int w = win0 + (t >> lgS);
+      const bool y_t = rp.term[hb + w] != 0, y_c = rp.cost[hb + w] > 0.0f;
+      const double dt = (double)n_term / (double)S - (y_t ? 1.0 : 0.0), dc = m_cost - (y_c ? 1.0 : 0.0);
+      b_term = dt * dt;
+      b_cost = dc * dc;
+      next = h + 1 < rp.len[w] && !y_t;
+    }
+    s_ok[t] = ok;
+    s_next[t] = next;
+    if (alive && !next) rp.alive[row0 + t] = 0;
+    b_term = wave_sum(first ? b_term : 0.0);
+    b_cost = wave_sum(first ? b_cost : 0.0);
+    const int64_t n = lanes_set(ok && first), n_bad = lanes_set(bad && first);
+    if (t == 0) { psum[4 * C] = b_term; psum[4 * C + 1] = b_cost; pcnt[C * (S + 1)] = n; pcnt[C * (S + 1) + 1] = n_bad; }
+  }
+  __syncthreads();
+
+  // the rows' next state, from the staged tile: the same walk
+  float *cur = rp.cur_obs + (size_t)row0 * D;
+  const bool open = rp.mode == CMBPO_REPLAY_OPEN_LOOP;
+  if (walker) {
+    for (int c = tc; c < D; c += W)
+      for (int r = tr; r < rows; r += rpp)
+        if (s_next[r]) cur[r * D + c] = open ? s_x[r * ld + c] : s_q[(r >> lgS) * ld + c];
+  }
+
+  // the columns: wave `wave` takes c = wave, wave + kWaves, ..., lane = row
+  const bool ok = s_ok[lane] != 0, keep = ok && first;
+  const int gl = lane & ~(S - 1);
+  const double dS = (double)S;
+  for (int c = wave; c < C; c += kWaves) {
+    const float x = ok ? s_x[lane * ld + c] : 0.0f, q = ok ? s_q[(lane >> lgS) * ld + c] : 0.0f;
+    const int k = __popcll(__ballot(ok && x < q) & gmask);
+    double pr = 0.0;
+    for (int j = 1; j < S; ++j) {
+      const float xo = __shfl(x, gl + ((lane + j) & (S - 1)), 64);
+      pr += (double)fabsf(__fsub_rn(x, xo));
+    }
+    const double a = group_sum((double)fabsf(__fsub_rn(x, q)), S) / dS;
+    const double g = group_sum(pr, S) / (dS * (dS - 1.0));           // every pair from both ends: 2 sum_{p < p'}
+    const double m = group_sum((double)x, S) / dS;
+    const double dq = m - (double)q, dx = (double)x - m;
+    const double v = group_sum(dx * dx, S) / (dS - 1.0);
+    const double s_a = wave_sum(keep ? a : 0.0), s_g = wave_sum(keep ? g : 0.0);
+    const double s_e = wave_sum(keep ? dq * dq : 0.0), s_v = wave_sum(keep ? v : 0.0);
+    if (lane == 0) { psum[c] = s_a; psum[C + c] = s_g; psum[2 * C + c] = s_e; psum[3 * C + c] = s_v; }
+    // rank_hist[c][kk]: the windows with k == kk, a ballot each; lane kk keeps entry kk (lane 0 also entry 64 at S = 64)
+    int64_t mine = 0, last = 0;
+    for (int kk = 0; kk <= S; ++kk) {
+      const int64_t n = lanes_set(keep && k == kk);
+      if (kk < kRows) { if (lane == kk) mine = n; } else last = n;
+    }
+    int64_t *hist = pcnt + (size_t)c * (S + 1);
+    if (lane <= S && lane < kRows) hist[lane] = mine;
+    if (S == kRows && lane == 0) hist[kRows] = last;
+  }
+}
+
+// the particle table: sums and counts over the slots, in slot order; one workgroup per horizon, one thread per entry
+__global__ __launch_bounds__(kThreads) void replay_particles_finish_kernel(cmbpo_replay_particles_t rp, int n_part) {
+  const int h = blockIdx.x;
+  const int C = rp.obs_dim + 1;
+  const int NS = 4 * C + 2, NC = C * (rp.S + 1) + 2;
+  for (int j = threadIdx.x; j < NS + NC; j += kThreads) {
+    if (j < NS) {
+      const double *p = rp.part_sum + (size_t)h * n_part * NS + j;
+      double s = 0.0;
+      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NS];
+      rp.sums[(size_t)h * NS + j] = s;
+    } else {
+      const int64_t *p = rp.part_cnt + (size_t)h * n_part * NC + (j - NS);
+      int64_t s = 0;
+      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NC];
+      rp.counts[(size_t)h * NC + (j - NS)] = s;
+    }
+  }
+}
+
 int check_shape(const char *who, const cmbpo_replay_t *rp) {
   CMBPO_REQUIRE(rp != nullptr, "%s: descriptor is NULL", who);
   CMBPO_REQUIRE(rp->B >= 1, "%s: B %d < 1", who, rp->B);
@@ -885,7 +1061,122 @@ int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const c
   return run_steps(who, rp, rc, rr, rv, model, task, ensemble, d_elite, th, ch, stream);
 }
 
+// ---- particle replay: host side ---------------------------------------------------------------------------------------------
+bool particles_ok(int S) { return S >= 2 && S <= kRows && (S & (S - 1)) == 0; }
+
+int check_part_shape(const char *who, const cmbpo_replay_particles_t *rp) {
+  CMBPO_REQUIRE(rp != nullptr, "%s: descriptor is NULL", who);
+  CMBPO_REQUIRE(rp->B >= 1, "%s: B %d < 1", who, rp->B);
+  CMBPO_REQUIRE(rp->H >= 1, "%s: H %d < 1", who, rp->H);
+  CMBPO_REQUIRE(particles_ok(rp->S), "%s: S %d is not a power of two in 2..%d (the particles of a window are the lanes of a part of "
+                "one wave)", who, rp->S, kRows);
+  CMBPO_REQUIRE(rp->B <= INT32_MAX / kRows, "%s: B %d windows of S %d particles: the rows B S must stay below 2^31", who, rp->B, rp->S);
+  CMBPO_REQUIRE(rp->obs_dim >= 1 && rp->act_dim >= 0, "%s: bad dims (obs_dim %d, act_dim %d)", who, rp->obs_dim, rp->act_dim);
+  CMBPO_REQUIRE(rp->obs_dim <= CMBPO_REPLAY_PARTICLES_MAX_OBS,
+                "%s: obs_dim %d above %d: the 64-row tile a workgroup stages in LDS cannot hold it, and it is not split", who,
+                rp->obs_dim, CMBPO_REPLAY_PARTICLES_MAX_OBS);
+  CMBPO_REQUIRE(rp->mode == CMBPO_REPLAY_OPEN_LOOP || rp->mode == CMBPO_REPLAY_ONE_STEP, "%s: unknown mode %d", who, rp->mode);
+  CMBPO_REQUIRE(rp->reserved == 0 && rp->reserved2 == 0, "%s: reserved %d, %d != 0", who, rp->reserved, rp->reserved2);
+  return CMBPO_OK;
+}
+
+int check_part_step(const char *who, const cmbpo_replay_particles_t *rp) {
+  if (int rc = check_part_shape(who, rp)) return rc;
+  CMBPO_REQUIRE(rp->next_obs && rp->rew && rp->cost && rp->term && rp->len, "%s: NULL buffer (recorded arrays)", who);
+  CMBPO_REQUIRE(rp->cur_obs && rp->alive, "%s: NULL buffer (cur_obs / alive)", who);
+  CMBPO_REQUIRE(rp->p_next_obs && rp->p_rew && rp->p_term && rp->p_cost, "%s: NULL buffer (predictions)", who);
+  CMBPO_REQUIRE(rp->part_sum && rp->part_cnt, "%s: NULL buffer (partials)", who);
+  return CMBPO_OK;
+}
+
+int check_part_finish(const char *who, const cmbpo_replay_particles_t *rp) {
+  if (int rc = check_part_shape(who, rp)) return rc;
+  CMBPO_REQUIRE(rp->part_sum && rp->part_cnt, "%s: NULL buffer (partials)", who);
+  CMBPO_REQUIRE(rp->sums && rp->counts, "%s: NULL buffer (result table)", who);
+  return CMBPO_OK;
+}
+
+int launch_particles(const cmbpo_replay_particles_t *rp, int h, hipStream_t s) {
+  const size_t lds = part_lds_bytes(rp->obs_dim, rp->S);
+  if (int rc = cmbpo_grant_lds(replay_particles_kernel, lds)) return rc;
+  hipLaunchKernelGGL(replay_particles_kernel, dim3(cmbpo_replay_particles_parts(rp->B, rp->S)), dim3(kThreads), lds, s, *rp, h);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
+int launch_particles_finish(const cmbpo_replay_particles_t *rp, hipStream_t s) {
+  hipLaunchKernelGGL(replay_particles_finish_kernel, dim3(rp->H), dim3(kThreads), 0, s, *rp,
+                     cmbpo_replay_particles_parts(rp->B, rp->S));
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
+int run_particles(const cmbpo_replay_particles_t *rp, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model,
+                  int task, int ensemble, const int32_t *d_elite, void *stream) {
+  const char *who = "cmbpo_replay_run_particles";
+  if (int r = check_part_step(who, rp)) return r;
+  if (int r = check_part_finish(who, rp)) return r;
+  CMBPO_REQUIRE(model != nullptr, "%s: model handle is NULL", who);
+  CMBPO_REQUIRE(rp->xi != nullptr, "%s: NULL buffer (xi): a particle replay samples its transitions", who);
+  CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);
+  CMBPO_REQUIRE((rp->act_dim == 0 || rp->act) && rp->mean && rp->var, "%s: NULL buffer (act / mean / var)", who);
+  CMBPO_REQUIRE(rp->p_dkl_path && rp->p_ep_var_mean, "%s: NULL buffer (p_dkl_path / p_ep_var_mean)", who);
+  if (ch && ch->kind == 1)
+    CMBPO_REQUIRE(model->out_dim == rp->obs_dim + 2 + (th ? 1 : 0),
+                  "%s: logistic cost head (cmbpo_cost_head_t, kind 1): model out_dim %d does not match obs_dim %d + 2 (+ 1 with a "
+                  "termination head), task 0x%x", who, model->out_dim, rp->obs_dim, task);
+  if (th) {
+    const int want = rp->obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0) + 1;
+    CMBPO_REQUIRE(model->out_dim == want,
+                  "%s: termination head (cmbpo_term_head_t): model out_dim %d does not match obs_dim %d + 1 (+ 1 with CMBPO_TASK_LEARNED_COST) "
+                  "+ 1 for the head's column, task 0x%x", who, model->out_dim, rp->obs_dim, task);
+  }
+  const int R = rp->B * rp->S, D = rp->obs_dim, A = rp->act_dim;
+  FakeenvPostCall pc{};
+  pc.task = task; pc.ensemble = ensemble; pc.obs_dim = D; pc.act_dim = A;
+  pc.mean = rp->mean; pc.var = rp->var; pc.ld_rows = R; pc.obs = rp->cur_obs;
+  pc.next_obs = rp->p_next_obs; pc.rew = rp->p_rew; pc.term = rp->p_term; pc.cost = rp->p_cost;
+  pc.dkl_path = rp->p_dkl_path; pc.ep_var_mean = rp->p_ep_var_mean;
+  pc.th = th;
+  pc.ch = ch;
+  // the two callees' own argument checks, on a call of no rows (neither launches anything for it)
+  if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, rp->act, A, nullptr, nullptr, 0, R, rp->mean, rp->var, stream))
+    return refused_by(who, rc);
+  pc.act = rp->act; pc.elite = d_elite; pc.xi = rp->xi; pc.n_rows = 0;
+  if (int rc = cmbpo_internal_fakeenv_post(pc, stream)) return refused_by(who, rc);
+  for (int h = 0; h < rp->H; ++h) {
+    const float *act_h = rp->act ? rp->act + (size_t)h * R * A : nullptr;
+    if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, act_h, A, nullptr, nullptr, R, R, rp->mean, rp->var, stream))
+      return refused_by(who, rc);
+    pc.act = act_h; pc.elite = d_elite + (size_t)h * R; pc.xi = rp->xi + (size_t)h * R * D; pc.n_rows = R;
+    if (int rc = cmbpo_internal_fakeenv_post(pc, stream)) return refused_by(who, rc);
+    if (int rc = launch_particles(rp, h, (hipStream_t)stream)) return rc;
+  }
+  return launch_particles_finish(rp, (hipStream_t)stream);
+}
+
 }  // namespace
+
+extern "C" int cmbpo_replay_particles_parts(int B, int S) {
+  return B >= 1 && particles_ok(S) && B <= INT32_MAX / kRows ? cmbpo_ceil_div(B * S, kRows) : 0;
+}
+
+extern "C" int cmbpo_replay_particles(const cmbpo_replay_particles_t *rp, int h, void *stream) {
+  const char *who = "cmbpo_replay_particles";
+  if (int rc = check_part_step(who, rp)) return rc;
+  CMBPO_REQUIRE(h >= 0 && h < rp->H, "%s: h %d outside [0, %d)", who, h, rp->H);
+  return launch_particles(rp, h, (hipStream_t)stream);
+}
+
+extern "C" int cmbpo_replay_particles_finish(const cmbpo_replay_particles_t *rp, void *stream) {
+  if (int rc = check_part_finish("cmbpo_replay_particles_finish", rp)) return rc;
+  return launch_particles_finish(rp, (hipStream_t)stream);
+}
+
+extern "C" int cmbpo_replay_run_particles(const cmbpo_replay_particles_t *rp, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch,
+                                          cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream) {
+  return run_particles(rp, th, ch, model, task, ensemble, d_elite, stream);
+}
 
 extern "C" int cmbpo_replay_parts(int n_rows) { return n_rows >= 1 ? cmbpo_ceil_div(n_rows, kRows) : 0; }
 

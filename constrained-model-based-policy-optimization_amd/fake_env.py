@@ -70,7 +70,8 @@ the keys returned are what they were.
 actions and returns, per horizon, how far the predictions are from the recording (open-loop model validation).
 ``replay(..., reliability=True)`` also measures whether a logistic column is a probability, and
 ``set_cost_recalibration(b)`` feeds the measured logit offset of the cost column back: the kernels then subtract
-``float32(cost_logit_shift + b)``.
+``float32(cost_logit_shift + b)``.  ``replay(..., particles=S)`` adds a second pass in which every window is replayed by S
+sampled particles and the recording is held against their cloud (rank histograms, CRPS, spread against skill).
 
 ``task`` is a built-in task name, a name given to ``statics.register_task``, or a ``statics.TaskRules`` (user-defined
 termination / cost rules, evaluated by the same kernel); any other name is the default task, as in the reference.
@@ -118,6 +119,8 @@ class FakeEnv:
         self._rng = np.random.default_rng(seed)
         # the elite draws of replay(): a stream of its own, so that a run that validates is in all else the run that does not
         self._replay_rng = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(1,)))
+        # the seeds of replay(particles=S) calls without a particle_seed: a third stream, for the same reason
+        self._particle_seeds = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(2,)))
         self._disagreement = bool(disagreement)
         self.rew_pessimism = self.cost_pessimism = 0.0
         self.static_term_members, self.static_cost_members, self.static_votes = 'elite', 'elite', False
@@ -457,7 +460,8 @@ class FakeEnv:
         return next_obs, r, terms, info
 
     def replay(self, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, model_inds=None, mode='open_loop',
-               calibration=False, reliability=False, reliability_bins=15, reliability_terminals=None, votes=False):
+               calibration=False, reliability=False, reliability_bins=15, reliability_terminals=None, votes=False,
+               particles=0, particle_seed=None, noise_scale=None, particle_noise=None, particle_inds=None):
         """Open-loop model validation: replay B windows of up to H consecutive REAL steps through the model and hold its
         predictions against the recording, horizon by horizon (``cmbpo_replay_run``).
 
@@ -514,10 +518,44 @@ class FakeEnv:
         counts of the ``'any'`` and ``'majority'`` readings, for ``'cost'`` (not with ``predicts_cost``) and ``'term'``.
         ``votes='measure'`` runs the vote kernel under ``'elite'`` / ``'elite'`` whatever the environment's modes are: every
         other table is the call's without votes bit for bit, only the histogram is new.  ``reliability_terminals`` also serves
-        as the flags the ``'term'`` histogram is held against.  False is the call as it always was."""
-        from .replay import ReplayBuffers
+        as the flags the ``'term'`` histogram is held against.  False is the call as it always was.
+
+        ``particles=S`` (S a power of two in 2..64) adds a SECOND pass of its own behind the replay above, which
+        runs exactly as without it (every other key bit for bit): each window is replayed by S sampled particles
+        (``cmbpo_replay_run_particles``: B S rows, the post step with transition noise, the termination and cost heads as above,
+        no sampled terminations, disagreement, pessimism or votes), and under the key ``'particles'`` comes the dict of
+        ``cmbpo_amd.replay.particles_table`` -- per horizon and column (the observation columns, then the reward) the rank
+        histogram of the recorded value among the S particles, the fair CRPS, the particles' spread against the error of
+        their mean, and the Brier scores of their termination share and mean cost.  Is the CLOUD of sampled branches as wide
+        as the real spread after h compounded steps (``mode='open_loop'``), or after one (``mode='one_step'``: every particle
+        restarts from the recording)?  A predicted termination does not end a particle; the particles of a window live and
+        die together, with ``lengths`` and the recorded terminals.  The reward carries no transition noise by design (§3i):
+        its histogram shows the spread over members and states only.
+        The draws: the noise ``xi ~ N(0, 1)`` [H, B, S, obs] comes from a device generator of this call's own, the members
+        [H, B, S] uniformly from ``elite_inds`` from a NumPy generator of its own, both seeded by ``particle_seed`` (None: the
+        next seed of a stream this object keeps for nothing else) -- nothing is consumed from the replay's elite stream,
+        ``np.random``, torch's global generators or a sampler's.  (The recipe, for a seed s: ``xi = torch.randn((H, B, S, obs),
+        generator=g, dtype=torch.float32, device=...)`` with ``g = torch.Generator(device)`` after ``g.manual_seed(s)``; members
+        ``elite_inds[np.random.default_rng(np.random.SeedSequence(s, spawn_key=(1,))).integers(0, len(elite_inds), (H, B, S))]``.)
+        ``model_inds`` as an int sends every particle through that
+        member too (the aleatoric spread alone); as an [H, B] array it names the plain pass's member per window and the
+        particles still draw their own.  ``noise_scale`` [obs] multiplies the draws, one float32 rounding per element,
+        as ``ModelSampler`` scales its own (``set_noise_scale``).  ``particle_noise`` [H, B, S, obs] / ``particle_inds``
+        [H, B, S] supply the N(0, 1) draws (``noise_scale`` still applies) / the members directly.  Refused in words:
+        S not a power of two in 2..64; ``particles`` together with ``votes=True`` (the particle pass runs no vote kernel, its
+        table would describe another rule than the tables beside it; ``votes='measure'`` changes no verdict and is allowed);
+        any of the four particle arguments without ``particles``.  0 is the call as it always was."""
+        from .replay import ReplayBuffers, check_particles
         if votes not in (False, True, 'measure'):
             raise ValueError(f"replay: votes is False, True or 'measure', got {votes!r}")
+        if particles:
+            particles = check_particles(particles)
+            if votes is True:
+                raise ValueError("replay: particles together with votes=True is not supported: the particle pass runs no vote "
+                                 "kernel, its table would describe another rule than the tables beside it (votes='measure' is "
+                                 "allowed)")
+        elif not (particle_seed is None and noise_scale is None and particle_noise is None and particle_inds is None):
+            raise ValueError("replay: particle_seed / noise_scale / particle_noise / particle_inds need particles=S")
         if votes is True and not self.static_votes_on:
             raise ValueError("replay: votes=True needs the static votes on (static_votes=True or a static_*_members mode other "
                              "than 'elite'): there is no vote in force to replay under; votes='measure' only counts them")
@@ -569,7 +607,60 @@ class FakeEnv:
                 tab = rb.table()
             if reliability:
                 tab['reliability'] = rb.reliability_table()
+            if particles:
+                tab['particles'] = self._replay_particles(particles, obs0, actions, next_obs, rewards, costs, terminals,
+                                                         lengths=lengths, model_inds=model_inds, mode=mode,
+                                                         particle_seed=particle_seed, noise_scale=noise_scale,
+                                                         particle_noise=particle_noise, particle_inds=particle_inds)
             return tab
+
+    def _replay_particles(self, S, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, model_inds=None,
+                          mode='open_loop', particle_seed=None, noise_scale=None, particle_noise=None, particle_inds=None):
+        """The second pass of ``replay(particles=S)`` alone -- its own buffers, its own draws, ``cmbpo_replay_run_particles`` --,
+        with that call's arguments; returns the dict of ``cmbpo_amd.replay.particles_table``.  Internal: ``replay`` (which has
+        refused ``votes=True`` by then) and the trainer (which refuses ``m_validate_votes`` beside it) call it.  ``model_inds``
+        counts only as an int -- every particle through that member --: an [H, B] array names one member per window, the
+        particles draw their own."""
+        from .replay import ParticleBuffers, check_particles
+        S, seed, noise, inds = check_particles(S), particle_seed, particle_noise, particle_inds
+        E, D = self._model.num_nets, self.obs_dim
+        H, B = tuple(actions.shape[:2]) if hasattr(actions, "shape") else np.shape(actions)[:2]
+        widths = (int(np.shape(next_obs)[-1]), int(np.shape(actions)[-1]))
+        if widths != (self.obs_dim, self.act_dim):
+            raise ValueError("replay: windows of width (%d, %d), the model's is (%d, %d)" % (widths + (self.obs_dim, self.act_dim)))
+        if seed is None:
+            seed = int(self._particle_seeds.integers(0, 2 ** 62))
+        seed = int(seed)
+        if noise is None:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(seed)
+            xi = torch.randn((H, B, S, D), generator=gen, dtype=torch.float32, device=self.device)
+        else:
+            xi = torch.as_tensor(noise, dtype=torch.float32).to(self.device).clone()
+            if tuple(xi.shape) != (H, B, S, D):
+                raise ValueError("replay: particle_noise must be [%d, %d, %d, %d], got %s" % (H, B, S, D, tuple(xi.shape)))
+        if noise_scale is not None:
+            sc = torch.as_tensor(np.asarray(noise_scale, dtype=np.float32).reshape(-1))
+            if tuple(sc.shape) != (D,) or not bool(torch.isfinite(sc).all()) or not bool((sc > 0).all()):
+                raise ValueError("replay: noise_scale must be %d finite positive factors, one per observation column" % D)
+            xi.mul_(sc.to(self.device))
+        if inds is not None:
+            m = inds.detach().cpu().numpy() if isinstance(inds, torch.Tensor) else np.asarray(inds)
+        elif model_inds is not None and not isinstance(model_inds, torch.Tensor) and np.ndim(model_inds) == 0:
+            m = np.full((H, B, S), int(model_inds))
+        else:
+            elites = np.asarray(self._model.elite_inds, dtype=np.int32)
+            rng = np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(1,)))
+            m = elites[rng.integers(0, len(elites), size=(H, B, S))]
+        if m.shape != (H, B, S) or m.min() < 0 or m.max() >= E:
+            raise ValueError("replay: particle_inds must be an [%d, %d, %d] array of members in 0..%d" % (H, B, S, E - 1))
+        elite = torch.from_numpy(np.ascontiguousarray(m.reshape(H, B * S), dtype=np.int32)).to(self.device)
+        with torch.cuda.device(self.device):
+            pb = ParticleBuffers(S, obs0, actions, next_obs, rewards, costs, terminals, lengths=lengths, mode=mode, ensemble=E,
+                                 out_dim=self.output_dim, noise=xi, device=self.device)
+            pb.run(self._model.mlp.handle, self._task_id, E, elite, term_head=self.term_head_struct(),
+                   cost_head=self.cost_head_struct())
+            return pb.table()
 
     def close(self):
         pass

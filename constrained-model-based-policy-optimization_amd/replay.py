@@ -19,6 +19,10 @@ The static rules' votes: ``ReplayBuffers(..., votes=dict(done_mem
 the arrays of ``cmbpo_replay_votes_t``; ``run_votes`` replays with the vote kernel in the post step, and ``votes_table`` builds,
 per signal and horizon, the histogram of the vote count against the recorded flag, the reliability of the share ``v / E`` and the
 2x2 counts of the 'any' and 'majority' readings from the raw integer counts.
+
+The particle replay: ``ParticleBuffers`` owns the arrays of ``cmbpo_replay_particles_t`` -- every window replayed
+by S sampled particles, R = B S rows --, and ``particles_table`` builds, per horizon and column, the rank histogram of the
+recorded value among the particles, the fair CRPS and the spread / skill ratio from the raw sums and counts.
 """
 import ctypes as C
 
@@ -502,6 +506,152 @@ def logit_offset(rel, column, reading="elite", horizon=0, lo=-2.0, hi=2.0, min_n
         else:
             b = mid
     return float(min(max(0.5 * (a + b), lo), hi))
+
+
+def check_particles(S):
+    """S as the particle kernel takes it: a power of two in 2..64 (ValueError in words otherwise)."""
+    if isinstance(S, bool) or int(S) != S or not (2 <= int(S) <= _lib.REPLAY_PARTICLES_MAX and (int(S) & (int(S) - 1)) == 0):
+        raise ValueError("replay: particles must be a power of two in 2..%d (the particles of a window are lanes of one wave), "
+                         "got %r" % (_lib.REPLAY_PARTICLES_MAX, S))
+    return int(S)
+
+
+class ParticleBuffers:
+    """The device arrays of a particle replay (``cmbpo_replay_particles_t``): B windows of S particles, stepped as
+    R = B S rows, particle p of window b in row ``b * S + p``.  A sibling of ``ReplayBuffers`` with arrays of its own -- the
+    plain replay's are not touched."""
+
+    def __init__(self, S, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, mode="open_loop", ensemble=0,
+                 out_dim=0, noise=None, device="cuda"):
+        """obs0 [B, obs]; actions [H, B, act]; next_obs [H, B, obs]; rewards / costs / terminals [H, B]; lengths [B] in 1..H
+        (None: H) -- as ``ReplayBuffers`` takes them.  noise: [H, B, S, obs] (or [H, B S, obs]) float32 N(0, 1) draws, needed by
+        ``run`` only.  ``ensemble`` / ``out_dim`` > 0 also allocate the forward's scratch for R rows.  The recorded actions are
+        expanded to the R rows on the device."""
+        if mode not in MODES:
+            raise ValueError("replay mode: 'open_loop' or 'one_step', got %r" % (mode,))
+        S = check_particles(S)
+        dev = torch.device(device)
+        self.device, self.mode, self.S = dev, mode, S
+        f32, u8, i32 = torch.float32, torch.uint8, torch.int32
+        act, nxt = _as(actions, f32, dev), _as(next_obs, f32, dev)
+        if nxt.dim() != 3 or act.dim() != 3 or act.shape[:2] != nxt.shape[:2]:
+            raise ValueError("replay: actions [H, B, act] and next_obs [H, B, obs] expected, got %s and %s"
+                             % (tuple(act.shape), tuple(nxt.shape)))
+        H, B, D = nxt.shape
+        A = act.shape[2]
+        if H < 1 or B < 1:
+            raise ValueError("replay: at least one window of one step, got H = %d, B = %d" % (H, B))
+        if D > _lib.REPLAY_PARTICLES_MAX_OBS:
+            raise ValueError("replay: particles need obs_dim <= %d (the 64-row tile a workgroup stages in LDS), got %d"
+                             % (_lib.REPLAY_PARTICLES_MAX_OBS, D))
+        obs0 = _as(obs0, f32, dev)
+        if tuple(obs0.shape) != (B, D):
+            raise ValueError("replay: obs0 must be [%d, %d], got %s" % (B, D, tuple(obs0.shape)))
+        R = B * S
+        flat = lambda x, dt: _as(x, dt, dev).reshape(H, B)
+        if lengths is None:
+            ln = torch.full((B,), H, dtype=i32, device=dev)
+        else:
+            ln = _as(lengths, i32, dev).reshape(B)
+            lo, hi = int(ln.min()), int(ln.max())
+            if lo < 1 or hi > H:
+                raise ValueError("replay: lengths must lie in 1..%d, got %d..%d" % (H, lo, hi))
+        self.B, self.H, self.R, self.obs_dim, self.act_dim = B, H, R, D, A
+        self.n_part = _lib.lib().cmbpo_replay_particles_parts(B, S)
+        C_ = D + 1
+        ns, nc = 4 * C_ + 2, C_ * (S + 1) + 2
+        f = dict(dtype=f32, device=dev)
+        self.t = dict(act=act.repeat_interleave(S, dim=1).contiguous(), next_obs=nxt, rew=flat(rewards, f32),
+                      cost=flat(costs, f32), term=flat(terminals, u8), len=ln,
+                      cur_obs=obs0.repeat_interleave(S, dim=0).contiguous(), alive=torch.ones(R, dtype=u8, device=dev),
+                      p_next_obs=torch.empty((R, D), **f), p_rew=torch.empty(R, **f), p_term=torch.empty(R, dtype=u8, device=dev),
+                      p_cost=torch.empty(R, **f), p_dkl_path=torch.empty(R, **f), p_ep_var_mean=torch.empty(R, **f),
+                      part_sum=torch.zeros((H, self.n_part, ns), dtype=torch.float64, device=dev),
+                      part_cnt=torch.zeros((H, self.n_part, nc), dtype=torch.int64, device=dev),
+                      sums=torch.zeros((H, ns), dtype=torch.float64, device=dev),
+                      counts=torch.zeros((H, nc), dtype=torch.int64, device=dev))
+        if noise is not None:
+            xi = _as(noise, f32, dev)
+            if xi.numel() != H * R * D or xi.shape[0] != H or xi.shape[-1] != D:
+                raise ValueError("replay: particle noise must be [%d, %d, %d, %d], got %s" % (H, B, S, D, tuple(xi.shape)))
+            self.t["xi"] = xi.reshape(H, R, D)
+        if ensemble > 0:
+            self.t["mean"] = torch.empty((ensemble, R, out_dim), **f)
+            self.t["var"] = torch.empty_like(self.t["mean"])
+        ps = _lib.ReplayParticlesStruct()
+        ps.B, ps.H, ps.S, ps.obs_dim, ps.act_dim, ps.mode, ps.reserved, ps.reserved2 = B, H, S, D, A, MODES[mode], 0, 0
+        for k, v in self.t.items():
+            setattr(ps, k, v.data_ptr() if v.numel() else None)
+        self.ps = ps
+
+    def step_outputs(self):
+        """The dict ``FakeEnv.step_device`` fills: the prediction arrays ``cmbpo_replay_particles`` reads."""
+        t = self.t
+        return dict(next_obs=t["p_next_obs"], rew=t["p_rew"], term=t["p_term"], cost=t["p_cost"], dkl_path=t["p_dkl_path"],
+                    ep_var_mean=t["p_ep_var_mean"])
+
+    def particles(self, h):
+        _lib.check(_lib.lib().cmbpo_replay_particles(C.byref(self.ps), int(h), _lib.current_stream()), "cmbpo_replay_particles")
+
+    def finish(self):
+        _lib.check(_lib.lib().cmbpo_replay_particles_finish(C.byref(self.ps), _lib.current_stream()),
+                   "cmbpo_replay_particles_finish")
+
+    def run(self, model_handle, task_id, ensemble, elite, term_head=None, cost_head=None):
+        """``cmbpo_replay_run_particles``; elite: [H, R] int32 device tensor, the member of every row at every step."""
+        ref = lambda s: C.byref(s) if s is not None else None
+        _lib.check(_lib.lib().cmbpo_replay_run_particles(C.byref(self.ps), ref(term_head), ref(cost_head), model_handle, int(task_id),
+                                                         int(ensemble), _lib.ptr(elite), _lib.current_stream()),
+                   "cmbpo_replay_run_particles")
+
+    def table(self):
+        return particles_table(self.t["sums"].cpu().numpy(), self.t["counts"].cpu().numpy(), self.obs_dim, self.S)
+
+
+def particles_table(sums, counts, obs_dim, S):
+    """The particle dict from the raw ``sums`` [H, 4 C + 2] (float64) and ``counts`` [H, C (S + 1) + 2] (int64) of C = obs_dim + 1
+    columns (the observation columns, then the reward) and S particles per window.  ``n`` / ``n_nonfinite`` [H]: the windows
+    held against their particles / that went non-finite at the horizon; ``S``.  Per horizon and column, [H, C]: ``rank_hist``
+    [H, C, S + 1] (windows by the number of particles strictly below the recorded value), ``rank_freq`` = rank_hist / n,
+    ``rank_dev = 0.5 sum_k |freq_k - 1 / (S + 1)|`` (the total-variation distance from the flat histogram of a calibrated cloud),
+    ``outlier_rate = freq_0 + freq_S`` (the recording outside the cloud; 2 / (S + 1) when calibrated, more when the cloud is too
+    narrow), ``chi2 = sum_k (hist_k - n / (S + 1))^2 / (n / (S + 1))`` (S degrees of freedom), ``mae`` (mean absolute error of a
+    particle), ``crps = mean(a - g / 2)`` (the fair CRPS of the S-particle ensemble), ``spread`` (mean unbiased variance of the
+    particles), ``mse_mean`` (squared error of the particle mean), ``spread_skill = sqrt((S + 1) / S * spread / mse_mean)`` (1 when
+    calibrated).  Per horizon: ``brier_term`` / ``brier_cost`` (the particles' share of predicted terminations / mean predicted
+    cost against the recorded flag).  And the raw ``sum_abs``, ``sum_pair``, ``sum_se``, ``sum_var`` [H, C], ``sum_brier_term``,
+    ``sum_brier_cost`` [H].  A horizon with ``n == 0`` has NaN means and zero counts.  The reward column carries no transition
+    noise by design: its histogram shows the member and state spread only."""
+    sums, counts = np.asarray(sums, np.float64), np.asarray(counts, np.int64)
+    S = check_particles(S)
+    H, Cc = sums.shape[0], int(obs_dim) + 1
+    if sums.shape != (H, 4 * Cc + 2) or counts.shape != (H, Cc * (S + 1) + 2):
+        raise ValueError("particles_table: sums [H, %d] and counts [H, %d] expected for obs_dim %d and S %d, got %s and %s"
+                         % (4 * Cc + 2, Cc * (S + 1) + 2, obs_dim, S, sums.shape, counts.shape))
+    hist = counts[:, :Cc * (S + 1)].reshape(H, Cc, S + 1).copy()
+    n = counts[:, Cc * (S + 1)].copy()
+    s = sums[:, :4 * Cc].reshape(H, 4, Cc)
+    out = dict(n=n, n_nonfinite=counts[:, Cc * (S + 1) + 1].copy(), S=S, rank_hist=hist,
+               sum_abs=s[:, 0].copy(), sum_pair=s[:, 1].copy(), sum_se=s[:, 2].copy(), sum_var=s[:, 3].copy(),
+               sum_brier_term=sums[:, 4 * Cc].copy(), sum_brier_cost=sums[:, 4 * Cc + 1].copy())
+    den = np.where(n > 0, n, 1).astype(np.float64)
+    nan = np.where(n > 0, 0.0, np.nan)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        freq = hist / den[:, None, None] + nan[:, None, None]
+        flat = 1.0 / (S + 1)
+        expect = den[:, None, None] * flat
+        out["rank_freq"] = freq
+        out["rank_dev"] = 0.5 * np.abs(freq - flat).sum(axis=2)
+        out["outlier_rate"] = freq[:, :, 0] + freq[:, :, S]
+        out["chi2"] = ((hist - expect) ** 2 / expect).sum(axis=2) + nan[:, None]
+        out["mae"] = out["sum_abs"] / den[:, None] + nan[:, None]
+        out["crps"] = (out["sum_abs"] - 0.5 * out["sum_pair"]) / den[:, None] + nan[:, None]
+        out["spread"] = out["sum_var"] / den[:, None] + nan[:, None]
+        out["mse_mean"] = out["sum_se"] / den[:, None] + nan[:, None]
+        out["spread_skill"] = np.sqrt((S + 1.0) / S * out["spread"] / out["mse_mean"])
+        out["brier_term"] = out["sum_brier_term"] / den + nan
+        out["brier_cost"] = out["sum_brier_cost"] / den + nan
+    return out
 
 
 VOTE_SIGNALS = ("cost", "term")      # signal 0 / 1 of the vote table's histogram

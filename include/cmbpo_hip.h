@@ -1417,6 +1417,87 @@ int cmbpo_replay_run_votes(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t 
                            const cmbpo_replay_votes_t *rv, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch,
                            cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream);
 
+/* ---- particle replay: rank histograms and CRPS of sampled rollouts (csrc/replay.hip) --------
+ * Is the CLOUD of sampled branches as wide as the real spread, k compounded steps out?  Every window is replayed by S sampled
+ * particles, each with its own member draws and its own transition noise; at every horizon the recorded next state is held
+ * against the S particles.
+ *
+ * Layout.  B windows, H horizons, S particles per window, S a power of two in 2..64.  The stepping runs on R = B S rows: particle
+ * p of window b is row b S + p, a window's particles are adjacent rows.  Step h: cmbpo_ens_forward on all R rows from the
+ * particles' own cur_obs (act [H][R][act]: the recorded action of window b, repeated for its S rows), then the post step with
+ * xi + h R obs_dim and d_elite + h R, the environment's termination head (th) and cost head (ch) as the plain replay passes them;
+ * never term_thr, disagreement or votes.  Then cmbpo_replay_particles, on windows:
+ *   1. a window is ALIVE at h iff h < len[b], no recorded terminal came before h and it has not gone non-finite; alive [R] holds
+ *      the same value in all S rows of a window (the S particles live and die together).  A PREDICTED termination does not end
+ *      a particle -- its state goes on through the model: a fixed S per window is what makes the ranks comparable.  It is
+ *      only measured (brier_term);
+ *   2. a non-finite value in any of the window's S rows of p_next_obs, p_rew or p_cost: the window counts in n_nonfinite[h],
+ *      ends, and enters nothing else.  Otherwise it counts in n[h];
+ *   3. columns c = 0 .. obs_dim - 1: x_p = p_next_obs[b S + p][c] against q = next_obs[h][b][c]; c = obs_dim: x_p = p_rew[b S + p]
+ *      against q = rew[h][b]; C = obs_dim + 1 in all.  (The reward carries no aleatoric draw by design, DESIGN 3i: its particles
+ *      differ by member and by state only.)  Per (h, c):
+ *        rank_hist[h][c][k] += 1,  k = #{p : x_p < q}: strict, float32, k in 0 .. S; a tie counts as not below
+ *        sum_abs  += a = (sum_p |fl32(x_p - q)|) / S
+ *        sum_pair += g = (2 sum_{p < p'} |fl32(x_p - x_p')|) / (S (S - 1))
+ *        sum_se   += (m - q)^2,  m = (sum_p x_p) / S
+ *        sum_var  += (sum_p (x_p - m)^2) / (S - 1)            (two-pass)
+ *      float64 arithmetic on the float32 terms; the order of the additions inside a window is the kernel's own and fixed;
+ *   4. per window: brier_term += (mean_p [p_term != 0] - [term[h][b] != 0])^2,  brier_cost += (mean_p p_cost - [cost[h][b] > 0])^2;
+ *   5. the window lives on to h + 1 iff h + 1 < len[b] and term[h][b] == 0; then for each of its rows cur_obs[row] =
+ *      p_next_obs[row] (CMBPO_REPLAY_OPEN_LOOP) or next_obs[h][b] (CMBPO_REPLAY_ONE_STEP: every particle restarts from the
+ *      recording, a one-step PIT at every h); otherwise alive = 0 in its S rows.  Rows of a dead window are frozen.
+ *   sums   [H][4 C + 2]:        sum_abs [C] | sum_pair [C] | sum_se [C] | sum_var [C] | brier_term | brier_cost
+ *   counts [H][C (S + 1) + 2]:  rank_hist [C][S + 1] | n | n_nonfinite
+ * One workgroup takes 64 consecutive rows = 64 / S whole windows; per-workgroup partials (slot = workgroup,
+ * cmbpo_replay_particles_parts(B, S) slots per horizon, every entry of a slot written on every call) are added in slot order by
+ * the finish call: no floating-point atomics, two runs are bitwise equal.  The workgroup stages its 64 x obs_dim tile of
+ * predictions and its windows' recording in LDS; an obs_dim above CMBPO_REPLAY_PARTICLES_MAX_OBS (a chosen cap, below
+ * what the LDS of a gfx950 workgroup holds at every S: the tile of 384 columns at S = 2 takes 144 of its 160 KiB) is refused, not
+ * split.  cmbpo_replay_t and the three other descriptors are what they were. */
+#define CMBPO_REPLAY_PARTICLES_MAX_OBS 384
+
+typedef struct cmbpo_replay_particles {
+  int32_t B, H, S, obs_dim, act_dim, mode, reserved, reserved2;  /* windows; horizons; particles; ...; the last two must be 0 */
+  /* recorded, time-major */
+  const float *act;         /* [H,R,act]  the recorded actions, expanded to rows (cmbpo_replay_run_particles only) */
+  const float *next_obs;    /* [H,B,obs]                                        */
+  const float *rew, *cost;  /* [H,B]                                            */
+  const uint8_t *term;      /* [H,B]                                            */
+  const int32_t *len;       /* [B] real steps of the window, 1 .. H             */
+  const float *xi;          /* [H,R,obs] N(0,1) draws of the transition noise (cmbpo_replay_run_particles only) */
+  /* state, R = B S rows */
+  float *cur_obs;           /* [R,obs] the observation step h starts from       */
+  uint8_t *alive;           /* [R]                                              */
+  /* the post step's outputs, row indexed */
+  float *p_next_obs;        /* [R,obs]                                          */
+  float *p_rew;             /* [R]                                              */
+  uint8_t *p_term;          /* [R]                                              */
+  float *p_cost, *p_dkl_path, *p_ep_var_mean; /* [R] (the last two: cmbpo_replay_run_particles only) */
+  float *mean, *var;        /* [E,R,model out_dim] scratch of the forward (cmbpo_replay_run_particles only) */
+  /* partial sums and the result table */
+  double *part_sum;         /* [H][parts][4 (obs + 1) + 2]                      */
+  int64_t *part_cnt;        /* [H][parts][(obs + 1) (S + 1) + 2]                */
+  double *sums;             /* [H][4 (obs + 1) + 2]                             */
+  int64_t *counts;          /* [H][(obs + 1) (S + 1) + 2]                       */
+} cmbpo_replay_particles_t; /* 200 bytes */
+
+/* Every entry: CMBPO_EINVAL with a message naming the entry point for a NULL descriptor, B < 1, H < 1, S not a power of two in
+ * 2..64, B S beyond int32, obs_dim outside [1, CMBPO_REPLAY_PARTICLES_MAX_OBS], an unknown mode, reserved != 0, a NULL array it
+ * uses, h outside [0, H) -- all before any HIP call. */
+/* partial-sum slots per horizon of B windows of S particles: ceil(B S / 64) (0 for B < 1 or a refused S) */
+int cmbpo_replay_particles_parts(int B, int S);
+/* one horizon step of the particle statistics and the advance, on the prediction arrays in *rp */
+int cmbpo_replay_particles(const cmbpo_replay_particles_t *rp, int h, void *stream);
+/* partials -> sums / counts, all H horizons */
+int cmbpo_replay_particles_finish(const cmbpo_replay_particles_t *rp, void *stream);
+/* H x (cmbpo_ens_forward on all R rows -> the post step with xi, th, ch -> cmbpo_replay_particles), then the finish call, enqueued
+ * without a host wait; bitwise the result of the same calls issued one at a time.  d_elite is [H][R]: the member of every row at
+ * every step.  xi == NULL is refused (a particle replay without noise is S copies of the plain replay's rows per member draw:
+ * hand zeros if that is what is wanted).  th / ch and `task` as for cmbpo_replay_run_cost, with the same out_dim refusals; the
+ * callees' own refusals are passed on under this entry point's name. */
+int cmbpo_replay_run_particles(const cmbpo_replay_particles_t *rp, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch,
+                               cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
