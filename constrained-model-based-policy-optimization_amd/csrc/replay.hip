@@ -4,21 +4,18 @@
 // applies the recorded actions; at every horizon h it holds the model's prediction against what was recorded.  The stepping is
 // the existing cmbpo_ens_forward + cmbpo_fakeenv_post (the unpenalised means, no noise); what is new is the comparison:
 //   replay_compare_kernel   one horizon step: per-row verdicts, squared errors, 2x2 counts, the row's next state
-//   replay_finish_kernel    per-workgroup partials -> the [H] result table, in slot order
 // and, for a replay that also checks the model's variance, between post and compare of a step:
-//   replay_calibrate_kernel     one horizon step of the calibration table: squared errors against two predictive variances
-//   replay_calib_finish_kernel  its partials -> the [H] calibration table, in slot order
+//   replay_calibrate_kernel one horizon step of the calibration table: squared errors against two predictive variances
 // and, for a replay that also checks whether a logistic column is a probability, at the same place:
-//   replay_reliab_kernel        one horizon step of the reliability table: the members' logits, binned, against the recorded flag
-//   replay_reliab_finish_kernel its partials -> the [H] reliability table, in slot order
+//   replay_reliab_kernel    one horizon step of the reliability table: the members' logits, binned, against the recorded flag
 // and, for a replay whose post step runs the static rules' votes, at the same place:
-//   replay_votes_kernel         one horizon step of the vote table: the two vote counts of a row against the recorded flags
-//   replay_votes_finish_kernel  its partials -> the [H] vote table, in slot order
+//   replay_votes_kernel     one horizon step of the vote table: the two vote counts of a row against the recorded flags
 // and, for a replay of S sampled particles per window (the post step with xi, a descriptor of its own), in place of
 // the compare kernel:
-//   replay_particles_kernel         one horizon step: the recorded next state against a window's S particles -- ranks, absolute
-//                                   errors, pair differences, moments -- and the rows' next state
-//   replay_particles_finish_kernel  its partials -> the [H] particle table, in slot order
+//   replay_particles_kernel one horizon step: the recorded next state against a window's S particles -- ranks, absolute
+//                           errors, pair differences, moments -- and the rows' next state
+// Every step kernel writes its workgroup's slot of the table's partials, and one kernel serves all five tables:
+//   replay_fold_kernel      per-workgroup partials -> the [H] table, in slot order
 // Sums are float64, counts int64, every addition in a fixed order (no floating-point atomics): two runs are bitwise equal.
 #include "common.h"
 #include "ens_mlp_internal.h"
@@ -32,6 +29,30 @@ constexpr int kScalarSums = CMBPO_REPLAY_SCALAR_SUMS;  // se_rew, se_cost, sum e
 constexpr int kCounts = CMBPO_REPLAY_COUNTS;           // n, n_nonfinite, cost_cm[2][2], term_cm[2][2]
 
 __device__ __forceinline__ int64_t lanes_set(bool p) { return (int64_t)__popcll(__ballot(p)); }
+
+// The entries of one slot (= of one horizon of the table) per table, float64 sums and int64 counts: the step kernels, the fold's
+// launches and replay.py (*_sizes) say the same.  The plain table's counts are kCounts, the vote table has kVoteCounts and no sums.
+__host__ __device__ inline int cmp_sums(int obs_dim) { return obs_dim + kScalarSums; }
+__host__ __device__ inline int cal_sums(int obs_dim) { return CMBPO_REPLAY_CALIB_SUMS * (obs_dim + 1); }
+__host__ __device__ inline int cal_counts(int obs_dim) { return CMBPO_REPLAY_CALIB_COUNTS * (obs_dim + 1) + 2; }
+__host__ __device__ inline int rel_sums(int n_bins, int n_cols) { return 2 * n_cols * (2 * n_bins + 2); }
+__host__ __device__ inline int rel_counts(int n_bins, int n_cols) { return 2 * n_cols * 2 * n_bins + 2 * n_cols; }
+__host__ __device__ inline int part_sums(int obs_dim) { return 4 * (obs_dim + 1) + 2; }
+__host__ __device__ inline int part_counts(int obs_dim, int S) { return (obs_dim + 1) * (S + 1) + 2; }
+
+// this workgroup's slot of horizon h in partials of n entries per slot, [H][gridDim.x][n]
+template <typename T>
+__device__ __forceinline__ T *slot(T *part, int h, int n) { return part + ((size_t)h * gridDim.x + blockIdx.x) * n; }
+
+// The row verdict every table shares: a non-finite value in the [rows, obs_dim] tile `pred` of p_next_obs marks its row, if the
+// row is alive (integer LDS atomic: order cannot matter).  The caller's s_bad holds the verdict on p_rew / p_cost already; a
+// barrier on either side is the caller's.  The tables are subsets of the rows this leaves unmarked.
+__device__ __forceinline__ void mark_nonfinite_rows(const float *pred, int rows, int D, const uint8_t *s_alive, int *s_bad) {
+  for (int i = threadIdx.x, total = rows * D; i < total; i += kThreads) {
+    const int r = i / D;
+    if (s_alive[r] && !isfinite(pred[i])) atomicOr(&s_bad[r], 1);
+  }
+}
 
 // One workgroup = kRows consecutive windows.  The [rows, obs_dim] tile of a row-major array is one contiguous run of
 // rows * obs_dim floats, so the threads walk it flat: thread t starts at element t and advances by `stride` =
@@ -51,9 +72,8 @@ __global__ __launch_bounds__(kThreads) void replay_compare_kernel(cmbpo_replay_t
   const int row0 = blockIdx.x * kRows;
   const int rows = min(kRows, B - row0);
   const size_t hb = (size_t)h * B;
-  const int C = D + kScalarSums;
-  double *psum = rp.part_sum + ((size_t)h * gridDim.x + blockIdx.x) * C;
-  int64_t *pcnt = rp.part_cnt + ((size_t)h * gridDim.x + blockIdx.x) * kCounts;
+  double *psum = slot(rp.part_sum, h, cmp_sums(D));
+  int64_t *pcnt = slot(rp.part_cnt, h, kCounts);
 
   float p_rew = 0.0f, p_cost = 0.0f;
   if (t < kRows) {
@@ -65,14 +85,9 @@ __global__ __launch_bounds__(kThreads) void replay_compare_kernel(cmbpo_replay_t
   }
   __syncthreads();
 
-  // pass 1: a non-finite predicted observation marks its row (integer LDS atomic: order cannot matter)
+  // pass 1: a non-finite predicted observation marks its row
   const float *pred = rp.p_next_obs + (size_t)row0 * D;
-  const int total = rows * D;
-  for (int i = t; i < total; i += kThreads) {
-    const float v = pred[i];
-    const int r = i / D;
-    if (s_alive[r] && !isfinite(v)) atomicOr(&s_bad[r], 1);
-  }
+  mark_nonfinite_rows(pred, rows, D, s_alive, s_bad);
   __syncthreads();
 
   // the rows' verdicts, scalar sums and counts: wave 0, lane = row
@@ -144,21 +159,23 @@ __global__ __launch_bounds__(kThreads) void replay_compare_kernel(cmbpo_replay_t
   }
 }
 
-// table[h][j] = sum over the slots, in slot order; one workgroup per horizon, one thread per entry
-__global__ __launch_bounds__(kThreads) void replay_finish_kernel(cmbpo_replay_t rp, int n_part) {
+// table[h][j] = sum over the slots, in slot order, for any of the tables: one workgroup per horizon, its threads strided over the
+// NS sums and NC counts of the horizon.  The loop over the slots is sequential on purpose: that order IS the table's bits.
+// NS == 0 (the vote table): part_sum and sums are not touched and may be NULL.
+__global__ __launch_bounds__(kThreads) void replay_fold_kernel(const double *part_sum, const int64_t *part_cnt, double *sums,
+                                                               int64_t *counts, int NS, int NC, int n_part) {
   const int h = blockIdx.x;
-  const int C = rp.obs_dim + kScalarSums;
-  for (int j = threadIdx.x; j < C + kCounts; j += kThreads) {
-    if (j < C) {
-      const double *p = rp.part_sum + (size_t)h * n_part * C + j;
+  for (int j = threadIdx.x; j < NS + NC; j += kThreads) {
+    if (j < NS) {
+      const double *p = part_sum + (size_t)h * n_part * NS + j;
       double s = 0.0;
-      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * C];
-      rp.sums[(size_t)h * C + j] = s;
+      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NS];
+      sums[(size_t)h * NS + j] = s;
     } else {
-      const int64_t *p = rp.part_cnt + (size_t)h * n_part * kCounts + (j - C);
+      const int64_t *p = part_cnt + (size_t)h * n_part * NC + (j - NS);
       int64_t s = 0;
-      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * kCounts];
-      rp.counts[(size_t)h * kCounts + (j - C)] = s;
+      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NC];
+      counts[(size_t)h * NC + (j - NS)] = s;
     }
   }
 }
@@ -185,7 +202,7 @@ __device__ __forceinline__ void load_members(const float *p, size_t member, int 
 // sums.  Reads alive / predictions / recording / mean / var, writes its partial slot only.
 __global__ __launch_bounds__(kThreads) void replay_calibrate_kernel(cmbpo_replay_t rp, cmbpo_replay_calib_t rc, int h) {
   __shared__ uint8_t s_alive[kRows];              // alive on entry
-  __shared__ int s_bad[kRows];                    // a non-finite prediction in the row (the compare kernel's verdict)
+  __shared__ int s_bad[kRows];                    // a non-finite prediction in the row
   __shared__ int s_rej[kRows];                    // a mean / variance this table cannot use, or no such member
   __shared__ int s_elite[kRows];
   __shared__ uint8_t s_in[kRows];                 // the row enters the table
@@ -198,8 +215,10 @@ __global__ __launch_bounds__(kThreads) void replay_calibrate_kernel(cmbpo_replay
   const int row0 = blockIdx.x * kRows;
   const int rows = min(kRows, B - row0);
   const size_t hb = (size_t)h * B;
-  double *psum = rc.part_sum + ((size_t)h * gridDim.x + blockIdx.x) * (kCalSums * C);
-  int64_t *pcnt = rc.part_cnt + ((size_t)h * gridDim.x + blockIdx.x) * (kCalCounts * C + 2);
+  // (cal_sums(D) and cal_counts(D), spelled on C: through the calls the compiler folds the + 1 another way and this kernel's
+  // register allocation moves)
+  double *psum = slot(rc.part_sum, h, kCalSums * C);
+  int64_t *pcnt = slot(rc.part_cnt, h, kCalCounts * C + 2);
 
   if (t < kRows) {
     const bool alive = t < rows && rp.alive[row0 + t] != 0;
@@ -218,12 +237,9 @@ __global__ __launch_bounds__(kThreads) void replay_calibrate_kernel(cmbpo_replay
   }
   __syncthreads();
 
-  // pass 1a: the compare kernel's rule on the predicted observations
+  // pass 1a: the shared row verdict on the predicted observations
   const float *pred = rp.p_next_obs + (size_t)row0 * D;
-  for (int i = t, total = rows * D; i < total; i += kThreads) {
-    const int r = i / D;
-    if (s_alive[r] && !isfinite(pred[i])) atomicOr(&s_bad[r], 1);
-  }
+  mark_nonfinite_rows(pred, rows, D, s_alive, s_bad);
   __syncthreads();
 
   // pass 1b: every member's mean and variance of the calibrated columns
@@ -355,34 +371,12 @@ __global__ __launch_bounds__(kThreads) void replay_calibrate_kernel(cmbpo_replay
   }
 }
 
-// the calibration table: sums and counts over the slots, in slot order; one workgroup per horizon, one thread per entry
-__global__ __launch_bounds__(kThreads) void replay_calib_finish_kernel(cmbpo_replay_calib_t rc, int obs_dim, int n_part) {
-  const int h = blockIdx.x;
-  const int NS = kCalSums * (obs_dim + 1), NC = kCalCounts * (obs_dim + 1) + 2;
-  for (int j = threadIdx.x; j < NS + NC; j += kThreads) {
-    if (j < NS) {
-      const double *p = rc.part_sum + (size_t)h * n_part * NS + j;
-      double s = 0.0;
-      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NS];
-      rc.sums[(size_t)h * NS + j] = s;
-    } else {
-      const int64_t *p = rc.part_cnt + (size_t)h * n_part * NC + (j - NS);
-      int64_t s = 0;
-      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NC];
-      rc.counts[(size_t)h * NC + (j - NS)] = s;
-    }
-  }
-}
-
 // ---- reliability tables of the logistic columns -------------------------------------------------------------
 constexpr int kRelBins = CMBPO_RELIAB_MAX_BINS;
 constexpr int kRelCols = CMBPO_RELIAB_MAX_COLS;
 static_assert(CMBPO_RELIAB_MAX_ENSEMBLE <= kCalBatch, "one batch of loads holds every member's logit");
 static_assert(2 * kRelCols * kRows == kThreads, "one thread per (column, reading, row)");
 static_assert(2 * kRelCols * kRelBins <= kThreads / 2, "the bin owners sit below the owners of the per-reading and per-column entries");
-
-__device__ __forceinline__ int rel_sums(int n_bins, int n_cols) { return 2 * n_cols * (2 * n_bins + 2); }
-__device__ __forceinline__ int rel_counts(int n_bins, int n_cols) { return 2 * n_cols * 2 * n_bins + 2 * n_cols; }
 
 // One horizon step of the reliability table; the geometry of replay_compare_kernel (kRows rows per workgroup, slot =
 // workgroup).  Thread t sits on row t % kRows of (column, reading) pair t / kRows, j = pair / 2 and r = pair % 2: it loads every
@@ -393,7 +387,7 @@ __device__ __forceinline__ int rel_counts(int n_bins, int n_cols) { return 2 * n
 // order is fixed.  Reads alive / predictions / recording / mean, writes its partial slot only.
 __global__ __launch_bounds__(kThreads) void replay_reliab_kernel(cmbpo_replay_t rp, cmbpo_replay_reliab_t rr, int h) {
   __shared__ uint8_t s_alive[kRows];    // alive on entry
-  __shared__ int s_bad[kRows];          // a non-finite prediction in the row (the compare kernel's verdict)
+  __shared__ int s_bad[kRows];          // a non-finite prediction in the row
   __shared__ double s_edge[kRelBins];
   __shared__ int s_bin[kThreads];       // the bin of (pair, row); -1: the row does not enter
   __shared__ uint8_t s_y[kThreads], s_skip[kThreads];
@@ -404,9 +398,8 @@ __global__ __launch_bounds__(kThreads) void replay_reliab_kernel(cmbpo_replay_t 
   const int row0 = blockIdx.x * kRows;
   const int rows = min(kRows, B - row0);
   const size_t hb = (size_t)h * B;
-  const int NS = rel_sums(K, nc), NC = rel_counts(K, nc);
-  double *psum = rr.part_sum + ((size_t)h * gridDim.x + blockIdx.x) * NS;
-  int64_t *pcnt = rr.part_cnt + ((size_t)h * gridDim.x + blockIdx.x) * NC;
+  double *psum = slot(rr.part_sum, h, rel_sums(K, nc));
+  int64_t *pcnt = slot(rr.part_cnt, h, rel_counts(K, nc));
 
   if (t < kRows) {
     const bool alive = t < rows && rp.alive[row0 + t] != 0;
@@ -432,12 +425,8 @@ __global__ __launch_bounds__(kThreads) void replay_reliab_kernel(cmbpo_replay_t 
     m = rr.elite[hb + row0 + row];
   }
 
-  // the compare kernel's rule on the predicted observations (integer LDS flag: order cannot matter)
-  const float *pred = rp.p_next_obs + (size_t)row0 * D;
-  for (int i = t, total = rows * D; i < total; i += kThreads) {
-    const int r = i / D;
-    if (s_alive[r] && !isfinite(pred[i])) atomicOr(&s_bad[r], 1);
-  }
+  // the shared row verdict on the predicted observations
+  mark_nonfinite_rows(rp.p_next_obs + (size_t)row0 * D, rows, D, s_alive, s_bad);
   __syncthreads();
 
   int bin = -1;
@@ -508,46 +497,27 @@ __global__ __launch_bounds__(kThreads) void replay_reliab_kernel(cmbpo_replay_t 
   }
 }
 
-// the reliability table: sums and counts over the slots, in slot order; one workgroup per horizon, one thread per entry
-__global__ __launch_bounds__(kThreads) void replay_reliab_finish_kernel(cmbpo_replay_reliab_t rr, int n_part) {
-  const int h = blockIdx.x;
-  const int NS = rel_sums(rr.n_bins, rr.n_cols), NC = rel_counts(rr.n_bins, rr.n_cols);
-  for (int j = threadIdx.x; j < NS + NC; j += kThreads) {
-    if (j < NS) {
-      const double *p = rr.part_sum + (size_t)h * n_part * NS + j;
-      double s = 0.0;
-      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NS];
-      rr.sums[(size_t)h * NS + j] = s;
-    } else {
-      const int64_t *p = rr.part_cnt + (size_t)h * n_part * NC + (j - NS);
-      int64_t s = 0;
-      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NC];
-      rr.counts[(size_t)h * NC + (j - NS)] = s;
-    }
-  }
-}
-
 // ---- the static rules' votes ---------------------------------------------------------------------------------
 constexpr int kVoteCounts = CMBPO_REPLAY_VOTE_COUNTS;            // hist_cost[9][2] | hist_term[9][2] | n_vote | n_skipped
 constexpr int kVoteSlots = CMBPO_REPLAY_VOTES_MAX_ENSEMBLE + 1;  // v = 0 .. 8
 static_assert(kVoteCounts == 2 * kVoteSlots * 2 + 2 && kVoteCounts <= kRows, "one lane of wave 0 per entry of a slot");
 
 // One horizon step of the vote table; the geometry of replay_compare_kernel (kRows rows per workgroup, slot = workgroup).  All
-// threads scan the predicted observations for the compare kernel's rule, then wave 0, lane = row, reads its row's two vote
+// threads scan the predicted observations for the shared row verdict, then wave 0, lane = row, reads its row's two vote
 // counts and flags.  An entry of the slot is the number of lanes with one (signal, v, y): a ballot and its population count, a
 // wave-uniform scalar, which lane k keeps when it is entry k's -- 36 ballots on registers in place of LDS atomics on 36
 // addresses, no second barrier, and the slot leaves as one coalesced store of 38 lanes.  Reads alive / predictions / recording
 // and the vote arrays, writes its partial slot only.
 __global__ __launch_bounds__(kThreads) void replay_votes_kernel(cmbpo_replay_t rp, cmbpo_replay_votes_t rv, int h) {
   __shared__ uint8_t s_alive[kRows];   // alive on entry
-  __shared__ int s_bad[kRows];         // a non-finite prediction in the row (the compare kernel's verdict)
+  __shared__ int s_bad[kRows];         // a non-finite prediction in the row
 
   const int t = threadIdx.x;
   const int B = rp.B, D = rp.obs_dim, E = rv.ensemble;
   const int row0 = blockIdx.x * kRows;
   const int rows = min(kRows, B - row0);
   const size_t hb = (size_t)h * B;
-  int64_t *pcnt = rv.part_cnt + ((size_t)h * gridDim.x + blockIdx.x) * kVoteCounts;
+  int64_t *pcnt = slot(rv.part_cnt, h, kVoteCounts);
 
   // the row's votes and flags: issued ahead of the scan of the predictions, used behind it
   bool alive = false, y_c = false, y_t = false;
@@ -570,12 +540,8 @@ __global__ __launch_bounds__(kThreads) void replay_votes_kernel(cmbpo_replay_t r
   }
   __syncthreads();
 
-  // the compare kernel's rule on the predicted observations (integer LDS flag: order cannot matter)
-  const float *pred = rp.p_next_obs + (size_t)row0 * D;
-  for (int i = t, total = rows * D; i < total; i += kThreads) {
-    const int r = i / D;
-    if (s_alive[r] && !isfinite(pred[i])) atomicOr(&s_bad[r], 1);
-  }
+  // the shared row verdict on the predicted observations
+  mark_nonfinite_rows(rp.p_next_obs + (size_t)row0 * D, rows, D, s_alive, s_bad);
   __syncthreads();
 
   if (t >= kRows) return;
@@ -597,16 +563,6 @@ __global__ __launch_bounds__(kThreads) void replay_votes_kernel(cmbpo_replay_t r
   if (t == kVoteCounts - 2) mine = n_vote;
   if (t == kVoteCounts - 1) mine = n_skip;
   if (t < kVoteCounts) pcnt[t] = mine;
-}
-
-// the vote table: counts over the slots, in slot order; one workgroup per horizon, one thread per entry
-__global__ __launch_bounds__(kRows) void replay_votes_finish_kernel(cmbpo_replay_votes_t rv, int n_part) {
-  const int h = blockIdx.x, j = threadIdx.x;
-  if (j >= kVoteCounts) return;
-  const int64_t *p = rv.part_cnt + (size_t)h * n_part * kVoteCounts + j;
-  int64_t s = 0;
-  for (int k = 0; k < n_part; ++k) s += p[(size_t)k * kVoteCounts];
-  rv.counts[(size_t)h * kVoteCounts + j] = s;
 }
 
 // ---- particle replay: rank histograms and CRPS of sampled rollouts ------------------------------------------
@@ -655,9 +611,8 @@ __global__ __launch_bounds__(kThreads) void replay_particles_kernel(cmbpo_replay
   const int win0 = row0 >> lgS, wins = rows >> lgS;
   const size_t hb = (size_t)h * rp.B;
   float *s_x = s_tile, *s_q = s_tile + kRows * ld;
-  const int NS = 4 * C + 2, NC = C * (S + 1) + 2;
-  double *psum = rp.part_sum + ((size_t)h * gridDim.x + blockIdx.x) * NS;
-  int64_t *pcnt = rp.part_cnt + ((size_t)h * gridDim.x + blockIdx.x) * NC;
+  double *psum = slot(rp.part_sum, h, part_sums(D));
+  int64_t *pcnt = slot(rp.part_cnt, h, part_counts(D, S));
   const uint64_t gmask = (S == 64 ? ~0ull : (1ull << S) - 1) << (lane & ~(S - 1));      // the lanes of this lane's window
   const bool first = (lane & (S - 1)) == 0;                                             // the window's first lane speaks for it
 
@@ -760,24 +715,23 @@ __global__ __launch_bounds__(kThreads) void replay_particles_kernel(cmbpo_replay
   }
 }
 
-// the particle table: sums and counts over the slots, in slot order; one workgroup per horizon, one thread per entry
-__global__ __launch_bounds__(kThreads) void replay_particles_finish_kernel(cmbpo_replay_particles_t rp, int n_part) {
-  const int h = blockIdx.x;
-  const int C = rp.obs_dim + 1;
-  const int NS = 4 * C + 2, NC = C * (rp.S + 1) + 2;
-  for (int j = threadIdx.x; j < NS + NC; j += kThreads) {
-    if (j < NS) {
-      const double *p = rp.part_sum + (size_t)h * n_part * NS + j;
-      double s = 0.0;
-      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NS];
-      rp.sums[(size_t)h * NS + j] = s;
-    } else {
-      const int64_t *p = rp.part_cnt + (size_t)h * n_part * NC + (j - NS);
-      int64_t s = 0;
-      for (int k = 0; k < n_part; ++k) s += p[(size_t)k * NC];
-      rp.counts[(size_t)h * NC + (j - NS)] = s;
-    }
-  }
+// ---- host side ---------------------------------------------------------------------------------------------------------------
+// every launch of this file: kThreads threads; a step kernel takes one workgroup per slot, the fold one per horizon
+template <typename... P, typename... A>
+int launch(void (*kern)(P...), int grid, size_t lds, hipStream_t s, A... args) {
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, s, args...);
+  CMBPO_HIP_CHECK(hipGetLastError());
+  return CMBPO_OK;
+}
+
+int launch_fold(const double *part_sum, const int64_t *part_cnt, double *sums, int64_t *counts, int NS, int NC, int H, int n_part,
+                hipStream_t s) {
+  return launch(replay_fold_kernel, H, 0, s, part_sum, part_cnt, sums, counts, NS, NC, n_part);
+}
+
+int check_h(const char *who, int h, int H) {
+  CMBPO_REQUIRE(h >= 0 && h < H, "%s: h %d outside [0, %d)", who, h, H);
+  return CMBPO_OK;
 }
 
 int check_shape(const char *who, const cmbpo_replay_t *rp) {
@@ -809,15 +763,11 @@ int check_finish(const char *who, const cmbpo_replay_t *rp) {
 }
 
 int launch_compare(const cmbpo_replay_t *rp, int h, hipStream_t s) {
-  hipLaunchKernelGGL(replay_compare_kernel, dim3(cmbpo_replay_parts(rp->B)), dim3(kThreads), 0, s, *rp, h);
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
+  return launch(replay_compare_kernel, cmbpo_replay_parts(rp->B), 0, s, *rp, h);
 }
 
 int launch_finish(const cmbpo_replay_t *rp, hipStream_t s) {
-  hipLaunchKernelGGL(replay_finish_kernel, dim3(rp->H), dim3(kThreads), 0, s, *rp, cmbpo_replay_parts(rp->B));
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
+  return launch_fold(rp->part_sum, rp->part_cnt, rp->sums, rp->counts, cmp_sums(rp->obs_dim), kCounts, rp->H, cmbpo_replay_parts(rp->B), s);
 }
 
 int check_calib(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc) {
@@ -846,15 +796,12 @@ int check_calib_finish(const char *who, const cmbpo_replay_t *rp, const cmbpo_re
 }
 
 int launch_calibrate(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, int h, hipStream_t s) {
-  hipLaunchKernelGGL(replay_calibrate_kernel, dim3(cmbpo_replay_parts(rp->B)), dim3(kThreads), 0, s, *rp, *rc, h);
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
+  return launch(replay_calibrate_kernel, cmbpo_replay_parts(rp->B), 0, s, *rp, *rc, h);
 }
 
 int launch_calib_finish(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, hipStream_t s) {
-  hipLaunchKernelGGL(replay_calib_finish_kernel, dim3(rp->H), dim3(kThreads), 0, s, *rc, rp->obs_dim, cmbpo_replay_parts(rp->B));
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
+  return launch_fold(rc->part_sum, rc->part_cnt, rc->sums, rc->counts, cal_sums(rp->obs_dim), cal_counts(rp->obs_dim), rp->H,
+                     cmbpo_replay_parts(rp->B), s);
 }
 
 int check_reliab(const char *who, const cmbpo_replay_reliab_t *rr) {
@@ -893,15 +840,12 @@ int check_reliab_finish(const char *who, const cmbpo_replay_t *rp, const cmbpo_r
 }
 
 int launch_reliab(const cmbpo_replay_t *rp, const cmbpo_replay_reliab_t *rr, int h, hipStream_t s) {
-  hipLaunchKernelGGL(replay_reliab_kernel, dim3(cmbpo_replay_parts(rp->B)), dim3(kThreads), 0, s, *rp, *rr, h);
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
+  return launch(replay_reliab_kernel, cmbpo_replay_parts(rp->B), 0, s, *rp, *rr, h);
 }
 
 int launch_reliab_finish(const cmbpo_replay_t *rp, const cmbpo_replay_reliab_t *rr, hipStream_t s) {
-  hipLaunchKernelGGL(replay_reliab_finish_kernel, dim3(rp->H), dim3(kThreads), 0, s, *rr, cmbpo_replay_parts(rp->B));
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
+  return launch_fold(rr->part_sum, rr->part_cnt, rr->sums, rr->counts, rel_sums(rr->n_bins, rr->n_cols),
+                     rel_counts(rr->n_bins, rr->n_cols), rp->H, cmbpo_replay_parts(rp->B), s);
 }
 
 // `modes`: the single-step entries check ensemble <= 8 and the two modes' ranges themselves; the run entry leaves them to the
@@ -934,15 +878,11 @@ int check_votes_finish(const char *who, const cmbpo_replay_t *rp, const cmbpo_re
 }
 
 int launch_votes(const cmbpo_replay_t *rp, const cmbpo_replay_votes_t *rv, int h, hipStream_t s) {
-  hipLaunchKernelGGL(replay_votes_kernel, dim3(cmbpo_replay_parts(rp->B)), dim3(kThreads), 0, s, *rp, *rv, h);
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
+  return launch(replay_votes_kernel, cmbpo_replay_parts(rp->B), 0, s, *rp, *rv, h);
 }
 
 int launch_votes_finish(const cmbpo_replay_t *rp, const cmbpo_replay_votes_t *rv, hipStream_t s) {
-  hipLaunchKernelGGL(replay_votes_finish_kernel, dim3(rp->H), dim3(kRows), 0, s, *rv, cmbpo_replay_parts(rp->B));
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
+  return launch_fold(nullptr, rv->part_cnt, nullptr, rv->counts, 0, kVoteCounts, rp->H, cmbpo_replay_parts(rp->B), s);
 }
 
 // a callee's refusal, passed on under this entry point's name
@@ -953,6 +893,50 @@ int refused_by(const char *who, int rc) {
   return rc;
 }
 
+// the heads of a run against the model's width
+int check_heads(const char *who, int obs_dim, const cmbpo_mlp_t *model, int task, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch) {
+  if (ch && ch->kind == 1)
+    CMBPO_REQUIRE(model->out_dim == obs_dim + 2 + (th ? 1 : 0),
+                  "%s: logistic cost head (cmbpo_cost_head_t, kind 1): model out_dim %d does not match obs_dim %d + 2 (+ 1 with a "
+                  "termination head), task 0x%x", who, model->out_dim, obs_dim, task);
+  if (th) {
+    const int want = obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0) + 1;
+    CMBPO_REQUIRE(model->out_dim == want,
+                  "%s: termination head (cmbpo_term_head_t): model out_dim %d does not match obs_dim %d + 1 (+ 1 with CMBPO_TASK_LEARNED_COST) "
+                  "+ 1 for the head's column, task 0x%x", who, model->out_dim, obs_dim, task);
+  }
+  return CMBPO_OK;
+}
+
+// The stepping of a run, for either descriptor (RP: cmbpo_replay_t or cmbpo_replay_particles_t; R rows a horizon, B or B S).
+// post_call: the post step of a replay; act, elite, xi and n_rows follow the horizon (step_model), rv is the vote run's.
+template <typename RP>
+FakeenvPostCall post_call(const RP *rp, int R, int task, int ensemble, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch) {
+  FakeenvPostCall pc{};
+  pc.task = task; pc.ensemble = ensemble; pc.obs_dim = rp->obs_dim; pc.act_dim = rp->act_dim;
+  pc.mean = rp->mean; pc.var = rp->var; pc.ld_rows = R; pc.obs = rp->cur_obs;
+  pc.next_obs = rp->p_next_obs; pc.rew = rp->p_rew; pc.term = rp->p_term; pc.cost = rp->p_cost;
+  pc.dkl_path = rp->p_dkl_path; pc.ep_var_mean = rp->p_ep_var_mean;
+  pc.th = th;
+  pc.ch = ch;
+  return pc;
+}
+
+// h >= 0: the forward and the post step of horizon h.  h < 0: the two callees' own argument checks, on a call of no rows (neither
+// launches anything for it).  xi: the particle run's noise [H][R][obs_dim], NULL for the plain run.
+template <typename RP>
+int step_model(const char *who, const RP *rp, FakeenvPostCall &pc, int h, cmbpo_mlp_t *model, const int32_t *d_elite, const float *xi,
+               void *stream) {
+  const int R = pc.ld_rows, D = rp->obs_dim, A = rp->act_dim;
+  const size_t at = h < 0 ? 0 : (size_t)h * R;
+  const float *act_h = rp->act ? rp->act + at * A : nullptr;
+  if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, act_h, A, nullptr, nullptr, h < 0 ? 0 : R, R, rp->mean, rp->var, stream))
+    return refused_by(who, rc);
+  pc.act = act_h; pc.elite = d_elite + at; pc.xi = xi ? xi + at * D : nullptr; pc.n_rows = h < 0 ? 0 : R;
+  if (int rc = cmbpo_internal_fakeenv_post(pc, stream)) return refused_by(who, rc);
+  return CMBPO_OK;
+}
+
 // the steps of a run: cal == nullptr is exactly cmbpo_replay_run's launches, else the calibrate kernel goes between post and
 // compare and its finish behind the plain one; rel != nullptr: the reliability kernel behind it, its finish last; th / ch !=
 // nullptr: the heads' instances of the post kernel; vot != nullptr: the vote kernel behind the post kernel (FakeenvPostCall::rv), the
@@ -960,15 +944,7 @@ int refused_by(const char *who, int rc) {
 int run_steps(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *cal, const cmbpo_replay_reliab_t *rel,
               const cmbpo_replay_votes_t *vot, cmbpo_mlp_t *model, int task, int ensemble, const int32_t *d_elite,
               const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, void *stream) {
-  const int B = rp->B, D = rp->obs_dim, A = rp->act_dim;
-  // the post step; act, elite and n_rows follow the horizon
-  FakeenvPostCall pc{};
-  pc.task = task; pc.ensemble = ensemble; pc.obs_dim = D; pc.act_dim = A;
-  pc.mean = rp->mean; pc.var = rp->var; pc.ld_rows = B; pc.obs = rp->cur_obs;
-  pc.next_obs = rp->p_next_obs; pc.rew = rp->p_rew; pc.term = rp->p_term; pc.cost = rp->p_cost;
-  pc.dkl_path = rp->p_dkl_path; pc.ep_var_mean = rp->p_ep_var_mean;
-  pc.th = th;
-  pc.ch = ch;
+  FakeenvPostCall pc = post_call(rp, rp->B, task, ensemble, th, ch);
   cmbpo_rule_votes_t post_votes{};
   if (vot) {
     post_votes.done_members = vot->done_members; post_votes.cost_members = vot->cost_members;
@@ -978,17 +954,9 @@ int run_steps(const char *who, const cmbpo_replay_t *rp, const cmbpo_replay_cali
     pc.act = rp->act; pc.elite = d_elite; pc.n_rows = 0;
     if (int rc = cmbpo_internal_fakeenv_post(pc, stream)) return refused_by(who, rc);
   }
-  // the two callees' own argument checks, on a call of no rows (neither launches anything for it)
-  if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, rp->act, A, nullptr, nullptr, 0, B, rp->mean, rp->var, stream))
-    return refused_by(who, rc);
-  pc.act = rp->act; pc.elite = d_elite; pc.n_rows = 0;
-  if (int rc = cmbpo_internal_fakeenv_post(pc, stream)) return refused_by(who, rc);
+  if (int rc = step_model(who, rp, pc, -1, model, d_elite, nullptr, stream)) return rc;
   for (int h = 0; h < rp->H; ++h) {
-    const float *act_h = rp->act ? rp->act + (size_t)h * B * A : nullptr;
-    if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, act_h, A, nullptr, nullptr, B, B, rp->mean, rp->var, stream))
-      return refused_by(who, rc);
-    pc.act = act_h; pc.elite = d_elite + (size_t)h * B; pc.n_rows = B;
-    if (int rc = cmbpo_internal_fakeenv_post(pc, stream)) return refused_by(who, rc);
+    if (int rc = step_model(who, rp, pc, h, model, d_elite, nullptr, stream)) return rc;
     if (cal)
       if (int rc = launch_calibrate(rp, cal, h, (hipStream_t)stream)) return rc;
     if (rel)
@@ -1048,16 +1016,7 @@ int replay_run(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, const c
   }
   if (rv) CMBPO_REQUIRE(ensemble == rv->ensemble, "%s: ensemble %d, the vote descriptor's is %d", who, ensemble, rv->ensemble);
   if (ext) CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);
-  if (ch && ch->kind == 1)
-    CMBPO_REQUIRE(model->out_dim == rp->obs_dim + 2 + (th ? 1 : 0),
-                  "%s: logistic cost head (cmbpo_cost_head_t, kind 1): model out_dim %d does not match obs_dim %d + 2 (+ 1 with a "
-                  "termination head), task 0x%x", who, model->out_dim, rp->obs_dim, task);
-  if (th) {
-    const int want = rp->obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0) + 1;
-    CMBPO_REQUIRE(model->out_dim == want,
-                  "%s: termination head (cmbpo_term_head_t): model out_dim %d does not match obs_dim %d + 1 (+ 1 with CMBPO_TASK_LEARNED_COST) "
-                  "+ 1 for the head's column, task 0x%x", who, model->out_dim, rp->obs_dim, task);
-  }
+  if (int r = check_heads(who, rp->obs_dim, model, task, th, ch)) return r;
   return run_steps(who, rp, rc, rr, rv, model, task, ensemble, d_elite, th, ch, stream);
 }
 
@@ -1099,16 +1058,12 @@ int check_part_finish(const char *who, const cmbpo_replay_particles_t *rp) {
 int launch_particles(const cmbpo_replay_particles_t *rp, int h, hipStream_t s) {
   const size_t lds = part_lds_bytes(rp->obs_dim, rp->S);
   if (int rc = cmbpo_grant_lds(replay_particles_kernel, lds)) return rc;
-  hipLaunchKernelGGL(replay_particles_kernel, dim3(cmbpo_replay_particles_parts(rp->B, rp->S)), dim3(kThreads), lds, s, *rp, h);
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
+  return launch(replay_particles_kernel, cmbpo_replay_particles_parts(rp->B, rp->S), lds, s, *rp, h);
 }
 
 int launch_particles_finish(const cmbpo_replay_particles_t *rp, hipStream_t s) {
-  hipLaunchKernelGGL(replay_particles_finish_kernel, dim3(rp->H), dim3(kThreads), 0, s, *rp,
-                     cmbpo_replay_particles_parts(rp->B, rp->S));
-  CMBPO_HIP_CHECK(hipGetLastError());
-  return CMBPO_OK;
+  return launch_fold(rp->part_sum, rp->part_cnt, rp->sums, rp->counts, part_sums(rp->obs_dim), part_counts(rp->obs_dim, rp->S), rp->H,
+                     cmbpo_replay_particles_parts(rp->B, rp->S), s);
 }
 
 int run_particles(const cmbpo_replay_particles_t *rp, const cmbpo_term_head_t *th, const cmbpo_cost_head_t *ch, cmbpo_mlp_t *model,
@@ -1121,35 +1076,11 @@ int run_particles(const cmbpo_replay_particles_t *rp, const cmbpo_term_head_t *t
   CMBPO_REQUIRE(d_elite != nullptr, "%s: NULL buffer (d_elite)", who);
   CMBPO_REQUIRE((rp->act_dim == 0 || rp->act) && rp->mean && rp->var, "%s: NULL buffer (act / mean / var)", who);
   CMBPO_REQUIRE(rp->p_dkl_path && rp->p_ep_var_mean, "%s: NULL buffer (p_dkl_path / p_ep_var_mean)", who);
-  if (ch && ch->kind == 1)
-    CMBPO_REQUIRE(model->out_dim == rp->obs_dim + 2 + (th ? 1 : 0),
-                  "%s: logistic cost head (cmbpo_cost_head_t, kind 1): model out_dim %d does not match obs_dim %d + 2 (+ 1 with a "
-                  "termination head), task 0x%x", who, model->out_dim, rp->obs_dim, task);
-  if (th) {
-    const int want = rp->obs_dim + 1 + ((task & CMBPO_TASK_LEARNED_COST) ? 1 : 0) + 1;
-    CMBPO_REQUIRE(model->out_dim == want,
-                  "%s: termination head (cmbpo_term_head_t): model out_dim %d does not match obs_dim %d + 1 (+ 1 with CMBPO_TASK_LEARNED_COST) "
-                  "+ 1 for the head's column, task 0x%x", who, model->out_dim, rp->obs_dim, task);
-  }
-  const int R = rp->B * rp->S, D = rp->obs_dim, A = rp->act_dim;
-  FakeenvPostCall pc{};
-  pc.task = task; pc.ensemble = ensemble; pc.obs_dim = D; pc.act_dim = A;
-  pc.mean = rp->mean; pc.var = rp->var; pc.ld_rows = R; pc.obs = rp->cur_obs;
-  pc.next_obs = rp->p_next_obs; pc.rew = rp->p_rew; pc.term = rp->p_term; pc.cost = rp->p_cost;
-  pc.dkl_path = rp->p_dkl_path; pc.ep_var_mean = rp->p_ep_var_mean;
-  pc.th = th;
-  pc.ch = ch;
-  // the two callees' own argument checks, on a call of no rows (neither launches anything for it)
-  if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, rp->act, A, nullptr, nullptr, 0, R, rp->mean, rp->var, stream))
-    return refused_by(who, rc);
-  pc.act = rp->act; pc.elite = d_elite; pc.xi = rp->xi; pc.n_rows = 0;
-  if (int rc = cmbpo_internal_fakeenv_post(pc, stream)) return refused_by(who, rc);
+  if (int r = check_heads(who, rp->obs_dim, model, task, th, ch)) return r;
+  FakeenvPostCall pc = post_call(rp, rp->B * rp->S, task, ensemble, th, ch);
+  if (int rc = step_model(who, rp, pc, -1, model, d_elite, rp->xi, stream)) return rc;
   for (int h = 0; h < rp->H; ++h) {
-    const float *act_h = rp->act ? rp->act + (size_t)h * R * A : nullptr;
-    if (int rc = cmbpo_ens_forward(model, rp->cur_obs, D, act_h, A, nullptr, nullptr, R, R, rp->mean, rp->var, stream))
-      return refused_by(who, rc);
-    pc.act = act_h; pc.elite = d_elite + (size_t)h * R; pc.xi = rp->xi + (size_t)h * R * D; pc.n_rows = R;
-    if (int rc = cmbpo_internal_fakeenv_post(pc, stream)) return refused_by(who, rc);
+    if (int rc = step_model(who, rp, pc, h, model, d_elite, rp->xi, stream)) return rc;
     if (int rc = launch_particles(rp, h, (hipStream_t)stream)) return rc;
   }
   return launch_particles_finish(rp, (hipStream_t)stream);
@@ -1164,7 +1095,7 @@ extern "C" int cmbpo_replay_particles_parts(int B, int S) {
 extern "C" int cmbpo_replay_particles(const cmbpo_replay_particles_t *rp, int h, void *stream) {
   const char *who = "cmbpo_replay_particles";
   if (int rc = check_part_step(who, rp)) return rc;
-  CMBPO_REQUIRE(h >= 0 && h < rp->H, "%s: h %d outside [0, %d)", who, h, rp->H);
+  if (int r = check_h(who, h, rp->H)) return r;
   return launch_particles(rp, h, (hipStream_t)stream);
 }
 
@@ -1183,7 +1114,7 @@ extern "C" int cmbpo_replay_parts(int n_rows) { return n_rows >= 1 ? cmbpo_ceil_
 extern "C" int cmbpo_replay_compare(const cmbpo_replay_t *rp, int h, void *stream) {
   const char *who = "cmbpo_replay_compare";
   if (int rc = check_compare(who, rp)) return rc;
-  CMBPO_REQUIRE(h >= 0 && h < rp->H, "%s: h %d outside [0, %d)", who, h, rp->H);
+  if (int r = check_h(who, h, rp->H)) return r;
   return launch_compare(rp, h, (hipStream_t)stream);
 }
 
@@ -1200,7 +1131,7 @@ extern "C" int cmbpo_replay_run(const cmbpo_replay_t *rp, cmbpo_mlp_t *model, in
 extern "C" int cmbpo_replay_calibrate(const cmbpo_replay_t *rp, const cmbpo_replay_calib_t *rc, int h, void *stream) {
   const char *who = "cmbpo_replay_calibrate";
   if (int r = check_calibrate(who, rp, rc)) return r;
-  CMBPO_REQUIRE(h >= 0 && h < rp->H, "%s: h %d outside [0, %d)", who, h, rp->H);
+  if (int r = check_h(who, h, rp->H)) return r;
   return launch_calibrate(rp, rc, h, (hipStream_t)stream);
 }
 
@@ -1229,7 +1160,7 @@ extern "C" int cmbpo_replay_run_cost(const cmbpo_replay_t *rp, const cmbpo_repla
 extern "C" int cmbpo_replay_reliab(const cmbpo_replay_t *rp, const cmbpo_replay_reliab_t *rr, int h, void *stream) {
   const char *who = "cmbpo_replay_reliab";
   if (int r = check_reliab_step(who, rp, rr)) return r;
-  CMBPO_REQUIRE(h >= 0 && h < rp->H, "%s: h %d outside [0, %d)", who, h, rp->H);
+  if (int r = check_h(who, h, rp->H)) return r;
   return launch_reliab(rp, rr, h, (hipStream_t)stream);
 }
 
@@ -1247,7 +1178,7 @@ extern "C" int cmbpo_replay_run_reliab(const cmbpo_replay_t *rp, const cmbpo_rep
 extern "C" int cmbpo_replay_votes(const cmbpo_replay_t *rp, const cmbpo_replay_votes_t *rv, int h, void *stream) {
   const char *who = "cmbpo_replay_votes";
   if (int r = check_votes_step(who, rp, rv, true)) return r;
-  CMBPO_REQUIRE(h >= 0 && h < rp->H, "%s: h %d outside [0, %d)", who, h, rp->H);
+  if (int r = check_h(who, h, rp->H)) return r;
   return launch_votes(rp, rv, h, (hipStream_t)stream);
 }
 

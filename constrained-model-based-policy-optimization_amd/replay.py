@@ -46,7 +46,69 @@ def _as(x, dtype, device):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np_dtype)).to(device)
 
 
-class ReplayBuffers:
+def _windows(obs0, actions, next_obs, rewards, costs, terminals, lengths, mode, dev, max_obs=None):
+    """The recorded windows, validated and on the device: ``H, B, D, A`` and the tensors ``act``, ``next_obs``, ``rew``, ``cost``,
+    ``term``, ``len`` (the descriptors' names) and ``obs0``.  ``max_obs``: the particle kernel's limit on obs_dim."""
+    if mode not in MODES:
+        raise ValueError("replay mode: 'open_loop' or 'one_step', got %r" % (mode,))
+    f32, u8, i32 = torch.float32, torch.uint8, torch.int32
+    act, nxt = _as(actions, f32, dev), _as(next_obs, f32, dev)
+    if nxt.dim() != 3 or act.dim() != 3 or act.shape[:2] != nxt.shape[:2]:
+        raise ValueError("replay: actions [H, B, act] and next_obs [H, B, obs] expected, got %s and %s"
+                         % (tuple(act.shape), tuple(nxt.shape)))
+    H, B, D = nxt.shape
+    if H < 1 or B < 1:
+        raise ValueError("replay: at least one window of one step, got H = %d, B = %d" % (H, B))
+    if max_obs is not None and D > max_obs:
+        raise ValueError("replay: particles need obs_dim <= %d (the 64-row tile a workgroup stages in LDS), got %d" % (max_obs, D))
+    obs0 = _as(obs0, f32, dev)
+    if tuple(obs0.shape) != (B, D):
+        raise ValueError("replay: obs0 must be [%d, %d], got %s" % (B, D, tuple(obs0.shape)))
+    flat = lambda x, dt: _as(x, dt, dev).reshape(H, B)
+    t = dict(act=act, next_obs=nxt, rew=flat(rewards, f32), cost=flat(costs, f32), term=flat(terminals, u8), obs0=obs0)
+    if lengths is None:
+        t["len"] = torch.full((B,), H, dtype=i32, device=dev)
+    else:
+        t["len"] = _as(lengths, i32, dev).reshape(B)
+        lo, hi = int(t["len"].min()), int(t["len"].max())
+        if lo < 1 or hi > H:
+            raise ValueError("replay: lengths must lie in 1..%d, got %d..%d" % (H, lo, hi))
+    return H, B, D, act.shape[2], t
+
+
+def _table(H, n_part, ns, nc, dev):
+    """The four arrays of a table of ``ns`` float64 sums and ``nc`` int64 counts per horizon: the per-slot partials and the
+    table, zeros.  ``ns == 0`` (the vote table): the counts only."""
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+    t = dict(part_cnt=z((H, n_part, nc), torch.int64), counts=z((H, nc), torch.int64))
+    if ns:
+        t.update(part_sum=z((H, n_part, ns), torch.float64), sums=z((H, ns), torch.float64))
+    return t
+
+
+# the entries of one horizon of each table, (float64 sums, int64 counts): what csrc/replay.hip's *_sums / *_counts say
+def calib_sizes(obs_dim):
+    return _lib.REPLAY_CALIB_SUMS * (obs_dim + 1), _lib.REPLAY_CALIB_COUNTS * (obs_dim + 1) + 2
+
+
+def reliab_sizes(n_bins, n_cols):
+    return 2 * n_cols * (2 * n_bins + 2), 2 * n_cols * 2 * n_bins + 2 * n_cols
+
+
+def particle_sizes(obs_dim, S):
+    return 4 * (obs_dim + 1) + 2, (obs_dim + 1) * (S + 1) + 2
+
+
+class _Buffers:
+    def step_outputs(self):
+        """The dict ``FakeEnv.step_device`` fills: the prediction arrays ``cmbpo_replay_compare`` / ``cmbpo_replay_particles``
+        read."""
+        t = self.t
+        return dict(next_obs=t["p_next_obs"], rew=t["p_rew"], term=t["p_term"], cost=t["p_cost"], dkl_path=t["p_dkl_path"],
+                    ep_var_mean=t["p_ep_var_mean"])
+
+
+class ReplayBuffers(_Buffers):
     def __init__(self, obs0, actions, next_obs, rewards, costs, terminals, lengths=None, mode="open_loop", ensemble=0,
                  out_dim=0, device="cuda", calibration=False, reliability=None, votes=None):
         """obs0 [B, obs]; actions [H, B, act]; next_obs [H, B, obs]; rewards / costs / terminals [H, B] (a trailing axis
@@ -63,45 +125,19 @@ class ReplayBuffers:
         ``learned_cost``), the ``[B]`` ``term_pred`` / ``term_votes`` scratch a termination head needs beside the vote kernel, the
         partials and the table; the modes are those of the post step (``'elite'`` / ``'elite'`` measures only); ``terminals``
         [H, B] as for ``reliability``."""
-        if mode not in MODES:
-            raise ValueError("replay mode: 'open_loop' or 'one_step', got %r" % (mode,))
         dev = torch.device(device)
+        H, B, D, A, w = _windows(obs0, actions, next_obs, rewards, costs, terminals, lengths, mode, dev)
+        cur = w.pop("obs0").clone()
         self.device, self.mode = dev, mode
         f32, u8, i32 = torch.float32, torch.uint8, torch.int32
-        act, nxt = _as(actions, f32, dev), _as(next_obs, f32, dev)
-        if nxt.dim() != 3 or act.dim() != 3 or act.shape[:2] != nxt.shape[:2]:
-            raise ValueError("replay: actions [H, B, act] and next_obs [H, B, obs] expected, got %s and %s"
-                             % (tuple(act.shape), tuple(nxt.shape)))
-        H, B, D = nxt.shape
-        A = act.shape[2]
-        if H < 1 or B < 1:
-            raise ValueError("replay: at least one window of one step, got H = %d, B = %d" % (H, B))
-        cur = _as(obs0, f32, dev).clone()
-        if tuple(cur.shape) != (B, D):
-            raise ValueError("replay: obs0 must be [%d, %d], got %s" % (B, D, tuple(cur.shape)))
-        flat = lambda x, dt: _as(x, dt, dev).reshape(H, B)
-        rew, cost = flat(rewards, f32), flat(costs, f32)
-        term = flat(terminals, u8)
-        if lengths is None:
-            ln = torch.full((B,), H, dtype=i32, device=dev)
-        else:
-            ln = _as(lengths, i32, dev).reshape(B)
-            lo, hi = int(ln.min()), int(ln.max())
-            if lo < 1 or hi > H:
-                raise ValueError("replay: lengths must lie in 1..%d, got %d..%d" % (H, lo, hi))
         self.B, self.H, self.obs_dim, self.act_dim = B, H, D, A
         self.n_part = _lib.lib().cmbpo_replay_parts(B)
         f = dict(dtype=f32, device=dev)
-        ncol = D + _lib.REPLAY_SCALAR_SUMS
-        self.t = dict(act=act, next_obs=nxt, rew=rew, cost=cost, term=term, len=ln, cur_obs=cur,
-                      alive=torch.ones(B, dtype=u8, device=dev),
+        self.t = dict(w, cur_obs=cur, alive=torch.ones(B, dtype=u8, device=dev),
                       p_next_obs=torch.empty((B, D), **f), p_rew=torch.empty(B, **f),
                       p_term=torch.empty(B, dtype=u8, device=dev), p_cost=torch.empty(B, **f),
                       p_dkl_path=torch.empty(B, **f), p_ep_var_mean=torch.empty(B, **f),
-                      part_sum=torch.zeros((H, self.n_part, ncol), dtype=torch.float64, device=dev),
-                      part_cnt=torch.zeros((H, self.n_part, _lib.REPLAY_COUNTS), dtype=torch.int64, device=dev),
-                      sums=torch.zeros((H, ncol), dtype=torch.float64, device=dev),
-                      counts=torch.zeros((H, _lib.REPLAY_COUNTS), dtype=torch.int64, device=dev))
+                      **_table(H, self.n_part, D + _lib.REPLAY_SCALAR_SUMS, _lib.REPLAY_COUNTS, dev))
         if ensemble > 0:
             self.t["mean"] = torch.empty((ensemble, B, out_dim), **f)
             self.t["var"] = torch.empty_like(self.t["mean"])
@@ -116,13 +152,8 @@ class ReplayBuffers:
             if ensemble < 1 or out_dim < D + 1:
                 raise ValueError("replay: calibration needs the forward's scratch: ensemble >= 1 and out_dim >= obs + 1 = %d, "
                                  "got %d and %d" % (D + 1, ensemble, out_dim))
-            ns, nc = _lib.REPLAY_CALIB_SUMS * (D + 1), _lib.REPLAY_CALIB_COUNTS * (D + 1) + 2
             self.elite = torch.zeros((H, B), dtype=i32, device=dev)
-            self.c = dict(elite=self.elite,
-                          part_sum=torch.zeros((H, self.n_part, ns), dtype=torch.float64, device=dev),
-                          part_cnt=torch.zeros((H, self.n_part, nc), dtype=torch.int64, device=dev),
-                          sums=torch.zeros((H, ns), dtype=torch.float64, device=dev),
-                          counts=torch.zeros((H, nc), dtype=torch.int64, device=dev))
+            self.c = dict(elite=self.elite, **_table(H, self.n_part, *calib_sizes(D), dev))
             cs = _lib.ReplayCalibStruct()
             cs.ensemble, cs.out_dim, cs.reserved = int(ensemble), int(out_dim), 0
             for k, v in self.c.items():
@@ -152,11 +183,9 @@ class ReplayBuffers:
             raise ValueError("replay: votes cost_members=%r with learned_cost: the static cost rule is skipped, there is nothing to "
                              "vote on" % (cm,))
         u8 = dict(dtype=torch.uint8, device=dev)
-        nv = _lib.REPLAY_VOTE_COUNTS
         self.v = dict(done_votes=torch.zeros(B, **u8), cost_votes=torch.zeros(0 if learned else B, **u8),
                       term=torch.zeros(0, **u8) if terminals is None else _as(terminals, torch.uint8, dev).reshape(H, B),
-                      part_cnt=torch.zeros((H, self.n_part, nv), dtype=torch.int64, device=dev),
-                      counts=torch.zeros((H, nv), dtype=torch.int64, device=dev))
+                      **_table(H, self.n_part, 0, _lib.REPLAY_VOTE_COUNTS, dev))
         self.head_scratch = dict(term_pred=torch.zeros(B, dtype=torch.float32, device=dev), term_votes=torch.zeros(B, **u8))
         vs = _lib.ReplayVotesStruct()
         vs.ensemble, vs.reserved = ensemble, 0
@@ -200,23 +229,13 @@ class ReplayBuffers:
             raise ValueError("replay: reliability columns need distinct names, got %s" % (names,))
         if self.elite is None:
             self.elite = torch.zeros((H, B), dtype=torch.int32, device=dev)
-        ns, nc = 2 * len(columns) * (2 * K + 2), 2 * len(columns) * 2 * K + 2 * len(columns)
         self.r = dict(elite=self.elite, edges=torch.from_numpy(np.ascontiguousarray(edges)).to(dev),
                       term=torch.zeros(0, dtype=torch.uint8, device=dev) if terminals is None
                       else _as(terminals, torch.uint8, dev).reshape(H, B),
-                      part_sum=torch.zeros((H, self.n_part, ns), dtype=torch.float64, device=dev),
-                      part_cnt=torch.zeros((H, self.n_part, nc), dtype=torch.int64, device=dev),
-                      sums=torch.zeros((H, ns), dtype=torch.float64, device=dev),
-                      counts=torch.zeros((H, nc), dtype=torch.int64, device=dev))
+                      **_table(H, self.n_part, *reliab_sizes(K, len(columns)), dev))
         for k, v in self.r.items():
             setattr(rr, k, v.data_ptr() if v.numel() else None)
         self.rr, self.rel_names, self.rel_edges, self.n_bins = rr, tuple(names), edges, K
-
-    def step_outputs(self):
-        """The dict ``FakeEnv.step_device`` fills: the prediction arrays ``cmbpo_replay_compare`` reads."""
-        t = self.t
-        return dict(next_obs=t["p_next_obs"], rew=t["p_rew"], term=t["p_term"], cost=t["p_cost"], dkl_path=t["p_dkl_path"],
-                    ep_var_mean=t["p_ep_var_mean"])
 
     def compare(self, h):
         _lib.check(_lib.lib().cmbpo_replay_compare(C.byref(self.rs), int(h), _lib.current_stream()), "cmbpo_replay_compare")
@@ -399,9 +418,10 @@ def calibration_table(sums, counts, obs_dim):
     sums, counts = np.asarray(sums, np.float64), np.asarray(counts, np.int64)
     H, Cc = sums.shape[0], int(obs_dim) + 1
     ks, kc = _lib.REPLAY_CALIB_SUMS, _lib.REPLAY_CALIB_COUNTS
-    if sums.shape != (H, ks * Cc) or counts.shape != (H, kc * Cc + 2):
+    ns, nc = calib_sizes(int(obs_dim))
+    if sums.shape != (H, ns) or counts.shape != (H, nc):
         raise ValueError("calibration_table: sums [H, %d] and counts [H, %d] expected for obs_dim %d, got %s and %s"
-                         % (ks * Cc, kc * Cc + 2, obs_dim, sums.shape, counts.shape))
+                         % (ns, nc, obs_dim, sums.shape, counts.shape))
     s, c = sums.reshape(H, ks, Cc), counts[:, :kc * Cc].reshape(H, kc, Cc)
     n = counts[:, kc * Cc].copy()
     out = dict(n=n, n_skipped=counts[:, kc * Cc + 1].copy())
@@ -451,9 +471,10 @@ def reliability_table(sums, counts, n_bins, names, edges=None):
     the non-empty bins, ``brier``, ``logloss``, ``base_rate = pos / N`` and ``mean_p``.  NaN where ``n == 0``."""
     sums, counts = np.asarray(sums, np.float64), np.asarray(counts, np.int64)
     H, K, Cn = sums.shape[0], int(n_bins), len(names)
-    if sums.shape != (H, 2 * Cn * (2 * K + 2)) or counts.shape != (H, 4 * Cn * K + 2 * Cn):
+    ns, nc = reliab_sizes(K, Cn)
+    if sums.shape != (H, ns) or counts.shape != (H, nc):
         raise ValueError("reliability_table: sums [H, %d] and counts [H, %d] expected for %d columns of %d bins, got %s and %s"
-                         % (2 * Cn * (2 * K + 2), 4 * Cn * K + 2 * Cn, Cn, K, sums.shape, counts.shape))
+                         % (ns, nc, Cn, K, sums.shape, counts.shape))
     s = sums.reshape(H, Cn, 2, 2 * K + 2)
     c = counts[:, :4 * Cn * K].reshape(H, Cn, 2, 2 * K)
     tail = counts[:, 4 * Cn * K:].reshape(H, Cn, 2)
@@ -516,7 +537,7 @@ def check_particles(S):
     return int(S)
 
 
-class ParticleBuffers:
+class ParticleBuffers(_Buffers):
     """The device arrays of a particle replay (``cmbpo_replay_particles_t``): B windows of S particles, stepped as
     R = B S rows, particle p of window b in row ``b * S + p``.  A sibling of ``ReplayBuffers`` with arrays of its own -- the
     plain replay's are not touched."""
@@ -527,49 +548,22 @@ class ParticleBuffers:
         (None: H) -- as ``ReplayBuffers`` takes them.  noise: [H, B, S, obs] (or [H, B S, obs]) float32 N(0, 1) draws, needed by
         ``run`` only.  ``ensemble`` / ``out_dim`` > 0 also allocate the forward's scratch for R rows.  The recorded actions are
         expanded to the R rows on the device."""
-        if mode not in MODES:
+        if mode not in MODES:      # (ahead of S, as it has always been)
             raise ValueError("replay mode: 'open_loop' or 'one_step', got %r" % (mode,))
         S = check_particles(S)
         dev = torch.device(device)
+        H, B, D, A, w = _windows(obs0, actions, next_obs, rewards, costs, terminals, lengths, mode, dev, _lib.REPLAY_PARTICLES_MAX_OBS)
+        obs0, R = w.pop("obs0"), B * S
         self.device, self.mode, self.S = dev, mode, S
-        f32, u8, i32 = torch.float32, torch.uint8, torch.int32
-        act, nxt = _as(actions, f32, dev), _as(next_obs, f32, dev)
-        if nxt.dim() != 3 or act.dim() != 3 or act.shape[:2] != nxt.shape[:2]:
-            raise ValueError("replay: actions [H, B, act] and next_obs [H, B, obs] expected, got %s and %s"
-                             % (tuple(act.shape), tuple(nxt.shape)))
-        H, B, D = nxt.shape
-        A = act.shape[2]
-        if H < 1 or B < 1:
-            raise ValueError("replay: at least one window of one step, got H = %d, B = %d" % (H, B))
-        if D > _lib.REPLAY_PARTICLES_MAX_OBS:
-            raise ValueError("replay: particles need obs_dim <= %d (the 64-row tile a workgroup stages in LDS), got %d"
-                             % (_lib.REPLAY_PARTICLES_MAX_OBS, D))
-        obs0 = _as(obs0, f32, dev)
-        if tuple(obs0.shape) != (B, D):
-            raise ValueError("replay: obs0 must be [%d, %d], got %s" % (B, D, tuple(obs0.shape)))
-        R = B * S
-        flat = lambda x, dt: _as(x, dt, dev).reshape(H, B)
-        if lengths is None:
-            ln = torch.full((B,), H, dtype=i32, device=dev)
-        else:
-            ln = _as(lengths, i32, dev).reshape(B)
-            lo, hi = int(ln.min()), int(ln.max())
-            if lo < 1 or hi > H:
-                raise ValueError("replay: lengths must lie in 1..%d, got %d..%d" % (H, lo, hi))
+        f32, u8 = torch.float32, torch.uint8
         self.B, self.H, self.R, self.obs_dim, self.act_dim = B, H, R, D, A
         self.n_part = _lib.lib().cmbpo_replay_particles_parts(B, S)
-        C_ = D + 1
-        ns, nc = 4 * C_ + 2, C_ * (S + 1) + 2
         f = dict(dtype=f32, device=dev)
-        self.t = dict(act=act.repeat_interleave(S, dim=1).contiguous(), next_obs=nxt, rew=flat(rewards, f32),
-                      cost=flat(costs, f32), term=flat(terminals, u8), len=ln,
+        self.t = dict(w, act=w["act"].repeat_interleave(S, dim=1).contiguous(),
                       cur_obs=obs0.repeat_interleave(S, dim=0).contiguous(), alive=torch.ones(R, dtype=u8, device=dev),
                       p_next_obs=torch.empty((R, D), **f), p_rew=torch.empty(R, **f), p_term=torch.empty(R, dtype=u8, device=dev),
                       p_cost=torch.empty(R, **f), p_dkl_path=torch.empty(R, **f), p_ep_var_mean=torch.empty(R, **f),
-                      part_sum=torch.zeros((H, self.n_part, ns), dtype=torch.float64, device=dev),
-                      part_cnt=torch.zeros((H, self.n_part, nc), dtype=torch.int64, device=dev),
-                      sums=torch.zeros((H, ns), dtype=torch.float64, device=dev),
-                      counts=torch.zeros((H, nc), dtype=torch.int64, device=dev))
+                      **_table(H, self.n_part, *particle_sizes(D, S), dev))
         if noise is not None:
             xi = _as(noise, f32, dev)
             if xi.numel() != H * R * D or xi.shape[0] != H or xi.shape[-1] != D:
@@ -583,12 +577,6 @@ class ParticleBuffers:
         for k, v in self.t.items():
             setattr(ps, k, v.data_ptr() if v.numel() else None)
         self.ps = ps
-
-    def step_outputs(self):
-        """The dict ``FakeEnv.step_device`` fills: the prediction arrays ``cmbpo_replay_particles`` reads."""
-        t = self.t
-        return dict(next_obs=t["p_next_obs"], rew=t["p_rew"], term=t["p_term"], cost=t["p_cost"], dkl_path=t["p_dkl_path"],
-                    ep_var_mean=t["p_ep_var_mean"])
 
     def particles(self, h):
         _lib.check(_lib.lib().cmbpo_replay_particles(C.byref(self.ps), int(h), _lib.current_stream()), "cmbpo_replay_particles")
@@ -625,9 +613,10 @@ def particles_table(sums, counts, obs_dim, S):
     sums, counts = np.asarray(sums, np.float64), np.asarray(counts, np.int64)
     S = check_particles(S)
     H, Cc = sums.shape[0], int(obs_dim) + 1
-    if sums.shape != (H, 4 * Cc + 2) or counts.shape != (H, Cc * (S + 1) + 2):
+    ns, nc = particle_sizes(int(obs_dim), S)
+    if sums.shape != (H, ns) or counts.shape != (H, nc):
         raise ValueError("particles_table: sums [H, %d] and counts [H, %d] expected for obs_dim %d and S %d, got %s and %s"
-                         % (4 * Cc + 2, Cc * (S + 1) + 2, obs_dim, S, sums.shape, counts.shape))
+                         % (ns, nc, obs_dim, S, sums.shape, counts.shape))
     hist = counts[:, :Cc * (S + 1)].reshape(H, Cc, S + 1).copy()
     n = counts[:, Cc * (S + 1)].copy()
     s = sums[:, :4 * Cc].reshape(H, 4, Cc)
